@@ -17,8 +17,15 @@ timeline on rank 0); --workload cfg2: the SIFT + L2 matcher of configs[2] instea
 Rank 0 prints one JSON line.  `roofline` is the dominant kernel (the exact
 Hamming kNN: knn_tile2_kernel by default, knn_tile4_kernel with --knn mfma4, knn_hamming_kernel with --knn valu), timed with HIP events on its
 launch stream inside the
-library; `cpu_baseline` is the CPU restatement (oracle/, kind "port") on a
-bounded sample of the same workload on the host cores.
+library.  A plain run sets up, warms up, times the K steps and prints the line; --full adds what takes runs of its own
+after the timed region: `cpu_baseline` (the CPU restatement, oracle/, kind "port", on a bounded sample of the same
+workload on the host cores), `host_frames` (the PCIe-inclusive rate), the kernels with one batch in flight
+(`roofline.one_batch_in_flight`, `stage_ms_one_batch_in_flight`) and, for cfg2, the in-run checks against the CPU
+restatement and numpy.
+
+--dump-outputs DIR writes the verdict records of the last timed step (every rank's, after the all-gather; cfg2:
+rank 0's) as DIR/<field>.npy in float32 / float64: page_idx, similarity, inliers, n_keypoints.  The inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -153,23 +160,26 @@ def bench_cfg2(args, wl, rank, world, local_rank, use_dist, barrier_fn):
         dt = float(td.item())
     prof, _ = m.read_profile()
     m.set_profiling(False)
-    # ---- checkers (outside the timed region)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, v)
+    # ---- checkers (outside the timed region; --full)
     acc = float((v["page_idx"] == truth).mean())
     nq = int(v["n_keypoints"].sum())
-    gk0, gd0 = m.sift(frames[0], sc)
-    assert len(gk0) == int(v["n_keypoints"][0]), "the matcher's frame 0 has another keypoint count than the SIFT tap"
-    t_rows = np.concatenate([m.page_features(p_)[1] for p_ in range(0, P, max(1, P // 40))][:40])      # a sample of the deck's rows
-    sample = np.random.default_rng(5).integers(0, len(gd0), 64)
-    gi, gdist = m.knn_l2_u8(gd0[sample], t_rows, 2)
-    knn_ok = True
-    for j, i in enumerate(sample):
-        diff = t_rows.astype(np.int32) - gd0[i].astype(np.int32)
-        d2 = (diff * diff).sum(1)
-        order = np.lexsort((np.arange(len(t_rows)), d2))[:2]
-        knn_ok &= bool(np.array_equal(order, gi[j]) and np.array_equal(d2[order].astype(np.uint32), gdist[j]))
-    assert knn_ok, "L2 k-NN disagrees with the numpy recomputation"
-    sift_ok = None
-    if rank == 0 and not args.no_cpu_baseline:
+    knn_ok = sift_ok = None
+    if args.full:
+        gk0, gd0 = m.sift(frames[0], sc)
+        assert len(gk0) == int(v["n_keypoints"][0]), "the matcher's frame 0 has another keypoint count than the SIFT tap"
+        t_rows = np.concatenate([m.page_features(p_)[1] for p_ in range(0, P, max(1, P // 40))][:40])      # a sample of the deck's rows
+        sample = np.random.default_rng(5).integers(0, len(gd0), 64)
+        gi, gdist = m.knn_l2_u8(gd0[sample], t_rows, 2)
+        knn_ok = True
+        for j, i in enumerate(sample):
+            diff = t_rows.astype(np.int32) - gd0[i].astype(np.int32)
+            d2 = (diff * diff).sum(1)
+            order = np.lexsort((np.arange(len(t_rows)), d2))[:2]
+            knn_ok &= bool(np.array_equal(order, gi[j]) and np.array_equal(d2[order].astype(np.uint32), gdist[j]))
+        assert knn_ok, "L2 k-NN disagrees with the numpy recomputation"
+    if args.full and rank == 0 and not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import pyoracle
         t1 = time.time()
@@ -219,6 +229,15 @@ def bench_cfg2(args, wl, rank, world, local_rank, use_dist, barrier_fn):
     if rank == 0:
         print(json.dumps(out), flush=True)
     m.close()
+
+
+def dump_outputs(dirname, recs):
+    """--dump-outputs: the verdict records a caller of the timed path receives, one .npy per field (float64 holds the int32
+    fields exactly, similarity stays float32)."""
+    os.makedirs(dirname, exist_ok=True)
+    for name in recs.dtype.names:
+        col = recs[name]
+        np.save(os.path.join(dirname, name + ".npy"), col.astype(np.float32 if col.dtype == np.float32 else np.float64))
 
 
 def knn_kernel_label(args):
@@ -289,8 +308,13 @@ def main():
                          "memory — a control-flow dry run of the N-rank job on a box with fewer GPUs than ranks (with --share-device)")
     ap.add_argument("--share-device", action="store_true",
                     help="gloo only: ranks may share devices (rank r uses device r mod the visible GPUs). Never a measurement of scaling.")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-host-frames", action="store_true", help="skip the PCIe-inclusive host-frames record (3 calls after the timed region)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what takes runs of its own after the timed region: the CPU baseline, the host-frames "
+                         "record, the kernels with one batch in flight, cfg2's checks against the CPU restatement and numpy")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the verdict records of the last timed step as DIR/<field>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-host-frames", action="store_true", help="--full without the PCIe-inclusive host-frames record (3 calls after the timed region)")
     ap.add_argument("--cpu-sample", type=int, default=0, help="frames in the CPU baseline sample")
     args = ap.parse_args()
 
@@ -496,7 +520,7 @@ def main():
     # outside the timed region: the same launches with one batch in flight, i.e. each kernel alone on the GPU
     # (under overlap the kNN shares the CUs with the other batch's ORB / verify kernels and its launches stretch)
     prof_alone = None
-    if rank == 0 and not args.no_overlap and args.inflight > 1:
+    if args.full and rank == 0 and not args.no_overlap and args.inflight > 1:
         m.set_profiling(True)
         run_stream(3 * U, depth=1, local=True, first_unit_only=True)      # (three launches of the stream's first unit)
         torch.cuda.synchronize()
@@ -510,6 +534,9 @@ def main():
         # the gathered records of the last step: this rank's slice must be its own verdicts
         mine = d_all[rank * B:(rank + 1) * B].cpu().numpy().view(_capi.VERDICT_DTYPE).reshape(-1)
         gathered_ok = bool(np.array_equal(mine, v))
+    if args.dump_outputs and rank == 0:
+        gathered = use_dist and os.environ.get("SLIDEO_BENCH_SKIP_GATHER") != "1"
+        dump_outputs(args.dump_outputs, d_all.cpu().numpy().view(_capi.VERDICT_DTYPE).reshape(-1) if gathered else v)
 
     truth_step = truth_of(g_last, B)                # the truth of the last step's frames
     acc = float((v["page_idx"] == truth_step).mean())
@@ -673,8 +700,8 @@ def main():
 
     # ---- the drop-in path's rate: HOST frames in (what crates/matching-hip and every host mirror hand over), PCIe-inclusive —
     # never `value` (inputs are resident in HBM when the timed region starts); 1 warm-up + 3 calls on pinned memory, outside the
-    # timed region (rank 0, N=1)
-    if rank == 0 and world == 1 and not args.no_host_frames:
+    # timed region (rank 0, N=1; --full)
+    if args.full and rank == 0 and world == 1 and not args.no_host_frames:
         hf = torch.from_numpy(frames).pin_memory().numpy()
         hv = m.match_frames(hf)
         t0 = time.perf_counter()
@@ -688,8 +715,8 @@ def main():
                                       "reported beside `value`, never as it"}
         del hf
 
-    # ---- CPU baseline: the CPU restatement on the host cores, bounded sample (rank 0, N=1 only)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    # ---- CPU baseline: the CPU restatement on the host cores, bounded sample (rank 0, N=1 only; --full)
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import pyoracle
         ocfg = pyoracle.default_config(nfeatures=wl["nfeatures"], verify_model=verify_model, ocv_hdlt=args.hdlt, matcher=1 if args.matcher == "lsh" else 0,

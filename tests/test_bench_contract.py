@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -20,7 +21,7 @@ def _json_line(out):
 
 
 def test_single_gpu_line():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "tiny", "--steps", "3", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "tiny", "--steps", "3", "--warmup", "1", "--full"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     j = _json_line(r.stdout)
@@ -48,11 +49,45 @@ def test_single_gpu_line():
     assert cb["kind"] == "port" and cb["cores"] >= 1 and cb["value"] > 0 and cb["verdict_agreement_with_gpu"] == 1.0
 
 
-def test_two_ranks_control_flow_over_gloo():
+def _dumped(d):
+    names = ("page_idx", "similarity", "inliers", "n_keypoints")
+    arrs = {n: np.load(os.path.join(d, n + ".npy")) for n in names}
+    assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+    assert sum(os.path.getsize(os.path.join(d, n + ".npy")) for n in names) <= 64 << 20
+    return arrs
+
+
+def test_plain_line_is_lean_and_dumps_the_last_step(tmp_path):
+    """A plain run does only what the headline figure needs (no CPU baseline, no host-frames record, no one-batch-in-flight
+    launches: those are --full's); --dump-outputs writes the last timed step's verdict records, identical from run to run."""
+    runs = []
+    for i in range(2):
+        d = str(tmp_path / ("out%d" % i))
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "tiny", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", d], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        j = _json_line(r.stdout)
+        for k in REQUIRED:
+            assert k in j, k
+        assert j["steps"] == 3 and j["warmup"] == 1 and j["ms_per_step"] > 0 and j["value"] > 0
+        for k in ("cpu_baseline", "host_frames", "stage_ms_one_batch_in_flight"):
+            assert k not in j, k
+        assert "one_batch_in_flight" not in j["roofline"]
+        runs.append(_dumped(d))
+    a, b = runs
+    n = 16                                                          # the tiny workload's frames per step
+    assert len(a["page_idx"]) == n and a["similarity"].dtype == np.float32
+    assert (a["n_keypoints"] >= 0).all() and a["n_keypoints"].max() > 0                  # (the synthetic set holds blank frames)
+    assert ((a["page_idx"] >= -1) & (a["page_idx"] < 8)).all()                            # -1 or one of the tiny deck's 8 pages
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+
+
+def test_two_ranks_control_flow_over_gloo(tmp_path):
     env = dict(os.environ, SLIDEO_BENCH_BACKEND="gloo")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", "29541", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "tiny", "--steps", "2",
-                        "--warmup", "1"], capture_output=True, text=True, timeout=420, cwd=ROOT, env=env)
+                        "--warmup", "1", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=420, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     j = _json_line(r.stdout)
     for k in REQUIRED:
@@ -60,6 +95,7 @@ def test_two_ranks_control_flow_over_gloo():
     assert j["n_gpus"] == 2 and j["steps"] == 2 and "cpu_baseline" not in j       # the CPU leg runs at N=1 only
     assert j["config"]["frames_per_step_per_gpu"] == 16 and j["value"] > 0
     assert j["config"]["collective"] == {"backend": "gloo", "all_gather_of_verdicts_checked": True}
+    assert len(_dumped(str(tmp_path))["page_idx"]) == 32           # both ranks' records of the last step, after the all-gather
 
 
 def test_plain_command_starts_its_own_ranks():
@@ -105,7 +141,7 @@ def test_cfg2_sift_l2_line():
     matrix cores, ratio test, the path's own verify stages; verdicts against the truth, frame 0's SIFT output bit-exact against
     the CPU restatement and sampled neighbours against numpy, inside the run."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "cfg2", "--batch", "8", "--pages", "20",
-                        "--steps", "2", "--warmup", "1"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                        "--steps", "2", "--warmup", "1", "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     j = _json_line(r.stdout)
     assert j["roofline"]["bound"] == "mfma" and j["roofline"]["kernel"] == "knn_l2_kernel" and j["sift_stage"]["bound"] == "hbm"
@@ -118,7 +154,7 @@ def test_cfg2_sift_l2_line():
 
 def test_cfg2_full_size():
     """BASELINE configs[2] at its full size: 256 1080p frames x SIFT-1000 against the SIFT descriptors of 500 pages."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "cfg2", "--steps", "2", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "cfg2", "--steps", "2", "--warmup", "1", "--full"],
                        capture_output=True, text=True, timeout=1500, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     j = _json_line(r.stdout)

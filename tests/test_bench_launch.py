@@ -18,3 +18,10 @@ def test_plain_gpus_2_spawns_two_ranks():
                        capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
     assert r.returncode != 0
     assert "[rank 0 of 2]" in r.stderr and "[rank 1 of 2]" in r.stderr, r.stderr[-2000:]
+
+
+def test_full_and_dump_outputs_options_exist():
+    """--full (what takes runs of its own after the timed region) and --dump-outputs DIR are part of the command line."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert "--full" in r.stdout and "--dump-outputs DIR" in r.stdout

@@ -7,7 +7,7 @@ out=gpurun_out/abe_$1; shift; args="$1"; shift
 mkdir -p $out
 for rep in $(seq 1 ${REPS:-3}); do for v in "$@"; do
   n=${v%%=*}; e=${v#*=}
-  env $e python bench.py $args --no-cpu-baseline 2>$out/${n}_$rep.err | tail -1 > $out/${n}_$rep.json
+  env $e python bench.py $args --full --no-cpu-baseline 2>$out/${n}_$rep.err | tail -1 > $out/${n}_$rep.json
 done; done
 python - "$out" <<'PY'
 import json,glob,sys,os,collections

@@ -7,8 +7,8 @@ out=gpurun_out/abl_$1; shift; args="$1"; shift
 mkdir -p $out
 for rep in $(seq 1 ${REPS:-3}); do for v in "$@"; do
   n=${v%%=*}; p=${v#*=}
-  if [ "$p" = product ]; then env -u SLIDEO_LIB_PATH python bench.py $args --no-cpu-baseline 2>$out/${n}_$rep.err | tail -1 > $out/${n}_$rep.json
-  else SLIDEO_LIB_PATH=$p python bench.py $args --no-cpu-baseline 2>$out/${n}_$rep.err | tail -1 > $out/${n}_$rep.json; fi
+  if [ "$p" = product ]; then env -u SLIDEO_LIB_PATH python bench.py $args --full --no-cpu-baseline 2>$out/${n}_$rep.err | tail -1 > $out/${n}_$rep.json
+  else SLIDEO_LIB_PATH=$p python bench.py $args --full --no-cpu-baseline 2>$out/${n}_$rep.err | tail -1 > $out/${n}_$rep.json; fi
 done; done
 python - "$out" <<'PY'
 import json,glob,sys,os,collections

@@ -16,7 +16,7 @@ done
 for rep in $(seq 1 ${REPS:-2}); do for s in "${specs[@]}"; do
   IFS='|' read -r n f e a <<< "$s"
   tag=$(echo "x$f" | md5sum | cut -c1-8)
-  env $e SLIDEO_LIB_PATH=slideo_amd/lib/variants/$tag/libslideo_amd.so timeout 300 python bench.py ${a:---steps 40 --warmup 5} --no-cpu-baseline 2>$out/${n}_$rep.err | tail -1 > $out/${n}_$rep.json
+  env $e SLIDEO_LIB_PATH=slideo_amd/lib/variants/$tag/libslideo_amd.so timeout 300 python bench.py ${a:---steps 40 --warmup 5} --full --no-cpu-baseline 2>$out/${n}_$rep.err | tail -1 > $out/${n}_$rep.json
 done; done
 python - "$out" <<'PY'
 import json,glob,sys,os

@@ -13,7 +13,7 @@ for v in "$@"; do
   names+=($n)
 done
 for rep in $(seq 1 ${REPS:-2}); do for n in "${names[@]}"; do
-  SLIDEO_LIB_PATH=slideo_amd/lib/variants/$n/libslideo_amd.so python bench.py $args --no-cpu-baseline 2>$out/${n}_$rep.err | tail -1 > $out/${n}_$rep.json
+  SLIDEO_LIB_PATH=slideo_amd/lib/variants/$n/libslideo_amd.so python bench.py $args --full --no-cpu-baseline 2>$out/${n}_$rep.err | tail -1 > $out/${n}_$rep.json
 done; done
 python - "$out" <<'PY'
 import json,glob,sys,os

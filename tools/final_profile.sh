@@ -2,7 +2,7 @@
 # usage (on the GPU box): tools/final_profile.sh <tag>   -> everything profiles/ needs for one state of the code
 tag=$1
 out=gpurun_out/final_$tag; mkdir -p $out; cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
-python bench.py > $out/bench_default.json 2> $out/bench_default.err
+python bench.py --full > $out/bench_default.json 2> $out/bench_default.err
 rocprofv3 --kernel-trace --stats -d $out/stats -o t -- python bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-host-frames --no-overlap > $out/bench_no_overlap.json 2>&1
 python profiles/summarize_rocpd.py $out/stats/t_results.db | grep -v rocclr > $out/kernel_stats_no_overlap.txt
 rocprofv3 --kernel-trace --stats -d $out/stats2 -o t -- python bench.py --steps 12 --warmup 3 --no-cpu-baseline --no-host-frames > $out/bench_overlap.json 2>&1
@@ -23,23 +23,23 @@ done
 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU GRBM_GUI_ACTIVE SQ_BUSY_CYCLES -d $out/pmc_sq -o t -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-host-frames --no-overlap > $out/pmc_sq.log 2>&1
 python profiles/summarize_pmc.py $out/pmc_sq/t_results.db knn_tile > $out/pmc_sq_knn.txt
 rm -rf $out/stats $out/stats2 $out/pmc_FETCH_SIZE $out/pmc_WRITE_SIZE $out/pmcov_FETCH_SIZE $out/pmcov_WRITE_SIZE $out/pmc_sq
-{ python bench.py --workload cfg1 --steps 20 --warmup 4 --no-cpu-baseline --no-host-frames 2>/dev/null | tail -1
-  python bench.py --workload cfg3 --steps 20 --warmup 2 --no-cpu-baseline --no-host-frames 2>/dev/null | tail -1
-  python bench.py --workload cfg4 --steps 12 --warmup 4 --no-cpu-baseline --no-host-frames 2>/dev/null | tail -1
-  python bench.py --workload tiny --steps 200 --warmup 20 --no-cpu-baseline --no-host-frames 2>/dev/null | tail -1
-  python bench.py --workload cfg2 2>/dev/null | tail -1; } > $out/bench_other_workloads.jsonl
+{ python bench.py --full --workload cfg1 --steps 20 --warmup 4 --no-cpu-baseline --no-host-frames 2>/dev/null | tail -1
+  python bench.py --full --workload cfg3 --steps 20 --warmup 2 --no-cpu-baseline --no-host-frames 2>/dev/null | tail -1
+  python bench.py --full --workload cfg4 --steps 12 --warmup 4 --no-cpu-baseline --no-host-frames 2>/dev/null | tail -1
+  python bench.py --full --workload tiny --steps 200 --warmup 20 --no-cpu-baseline --no-host-frames 2>/dev/null | tail -1
+  python bench.py --full --workload cfg2 2>/dev/null | tail -1; } > $out/bench_other_workloads.jsonl
 # the modes: the 8-DOF homography verifier (the sample solvers: the library's default since ABI 6 is hdlt 1; both verdict rules), the LSH-compatible index,
 # configs[4] with either verifier, configs[2] with Lowe's test instead of its default tolerance vote
-{ python bench.py --verify-model 1 --persp 0.1 --steps 20 --warmup 3 --no-cpu-baseline --no-host-frames 2>/dev/null | tail -1
-  python bench.py --verify-model 1 --persp 0.1 --verdict-rule 1 --steps 20 --warmup 3 --no-cpu-baseline --no-host-frames 2>/dev/null | tail -1
-  python bench.py --verify-model 1 --verdict-rule 1 --steps 20 --warmup 3 --no-cpu-baseline --no-host-frames 2>/dev/null | tail -1
-  python bench.py --verify-model 0 --verdict-rule 1 --steps 20 --warmup 3 --no-cpu-baseline --no-host-frames 2>/dev/null | tail -1
-  python bench.py --verify-model 1 --hdlt 0 --persp 0.1 --steps 6 --warmup 2 --no-cpu-baseline --no-host-frames 2>/dev/null | tail -1
-  python bench.py --matcher lsh --steps 20 --warmup 3 --no-cpu-baseline --no-host-frames 2>/dev/null | tail -1
-  python bench.py --workload cfg4 --verify-model 0 --persp 0 --steps 12 --warmup 4 --no-cpu-baseline --no-host-frames 2>/dev/null | tail -1
-  python bench.py --workload cfg4 --hdlt 0 --steps 6 --warmup 2 --no-cpu-baseline --no-host-frames 2>/dev/null | tail -1
-  python bench.py --workload cfg4 --hdlt 2 --steps 12 --warmup 4 --no-cpu-baseline --no-host-frames 2>/dev/null | tail -1
-  python bench.py --workload cfg2 --sift-vote ratio --steps 20 --warmup 3 --no-cpu-baseline --no-host-frames 2>/dev/null | tail -1; } > $out/bench_modes.jsonl
+{ python bench.py --full --verify-model 1 --persp 0.1 --steps 20 --warmup 3 --no-cpu-baseline --no-host-frames 2>/dev/null | tail -1
+  python bench.py --full --verify-model 1 --persp 0.1 --verdict-rule 1 --steps 20 --warmup 3 --no-cpu-baseline --no-host-frames 2>/dev/null | tail -1
+  python bench.py --full --verify-model 1 --verdict-rule 1 --steps 20 --warmup 3 --no-cpu-baseline --no-host-frames 2>/dev/null | tail -1
+  python bench.py --full --verify-model 0 --verdict-rule 1 --steps 20 --warmup 3 --no-cpu-baseline --no-host-frames 2>/dev/null | tail -1
+  python bench.py --full --verify-model 1 --hdlt 0 --persp 0.1 --steps 6 --warmup 2 --no-cpu-baseline --no-host-frames 2>/dev/null | tail -1
+  python bench.py --full --matcher lsh --steps 20 --warmup 3 --no-cpu-baseline --no-host-frames 2>/dev/null | tail -1
+  python bench.py --full --workload cfg4 --verify-model 0 --persp 0 --steps 12 --warmup 4 --no-cpu-baseline --no-host-frames 2>/dev/null | tail -1
+  python bench.py --full --workload cfg4 --hdlt 0 --steps 6 --warmup 2 --no-cpu-baseline --no-host-frames 2>/dev/null | tail -1
+  python bench.py --full --workload cfg4 --hdlt 2 --steps 12 --warmup 4 --no-cpu-baseline --no-host-frames 2>/dev/null | tail -1
+  python bench.py --full --workload cfg2 --sift-vote ratio --steps 20 --warmup 3 --no-cpu-baseline --no-host-frames 2>/dev/null | tail -1; } > $out/bench_modes.jsonl
 rocprofv3 --kernel-trace --stats -d $out/stats3 -o t -- python bench.py --workload cfg2 --steps 3 --warmup 1 --no-cpu-baseline --no-host-frames > $out/bench_cfg2_under_rocprof.json 2>&1
 python profiles/summarize_rocpd.py $out/stats3/t_results.db | grep -v rocclr > $out/kernel_stats_cfg2.txt
 rocprofv3 --kernel-trace --stats -d $out/stats4 -o t -- python bench.py --verify-model 1 --persp 0.1 --steps 3 --warmup 1 --no-cpu-baseline --no-host-frames --no-overlap > $out/bench_homography_under_rocprof.json 2>&1

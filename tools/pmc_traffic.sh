@@ -8,5 +8,5 @@ for c in FETCH_SIZE WRITE_SIZE; do
   python profiles/summarize_pmc.py $out/pmcov_$c/t_results.db > $out/pmc_overlap_$c.txt
   rm -rf $out/pmc_$c $out/pmcov_$c
 done
-python bench.py > $out/bench_default.json 2> $out/bench_default.err
+python bench.py --full > $out/bench_default.json 2> $out/bench_default.err
 grep -A2 "knn_tile2_kernel" $out/pmc_FETCH_SIZE.txt | head -3
