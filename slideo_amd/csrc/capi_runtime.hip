@@ -176,14 +176,7 @@ void unit_submit(slideo_matcher* m, Slot& S, const uint8_t* frames_dev, int n, i
     vp.rng_len = m->rng_len;
     HIP_CHECK(hipMemsetAsync(S.d_fcs.p, 0, (size_t)n * sizeof(FrameCands), st));
     if (prof) HIP_CHECK(hipEventRecord(S.ev[1], st));
-    if (qtot > 0 && S.st_knn) {                                         // SLIDEO_CU_SPLIT: the search on its own CUs, ordered by events
-        HIP_CHECK(hipEventRecord(S.ev_k0, st));
-        HIP_CHECK(hipStreamWaitEvent(S.st_knn, S.ev_k0, 0));
-        unit_knn(m, S, n, qplan, qtot, async, prof, S.st_knn);
-        HIP_CHECK(hipEventRecord(S.ev_k1, S.st_knn));
-        HIP_CHECK(hipStreamWaitEvent(st, S.ev_k1, 0));
-    } else
-    if (qtot > 0) unit_knn(m, S, n, qplan, qtot, async, prof, st);      // (records S.ev[2] behind the search when profiling)
+    if (qtot > 0) unit_knn(m, S, n, qplan, qtot, async, prof);      // (records S.ev[2] behind the search when profiling)
     unit_verify(m, S, vp, frames_dev, n, w, h, stride, frame_stride, qtot);
 }
 
@@ -467,9 +460,8 @@ int32_t slideo_matcher_create(const slideo_config* cfg, int32_t device, slideo_m
     mm->cfg = *cfg; mm->device = device;
     // environment switches of a matcher (include/slideo_amd.h, "Environment"); none changes a result
     { const long v = env_long("SLIDEO_KNN_ENGINE", 0); if (v >= 0 && v <= 3) mm->knn_engine = (int)v; }
-    { const long v = env_long("SLIDEO_KNN_SHARE", -1); if ((v >= -1 && v <= 1) || (v >= 3 && v <= 6)) mm->knn_share = (int)v; }
+    { const long v = env_long("SLIDEO_KNN_SHARE", -1); if ((v >= -1 && v <= 1) || v == 3 || v == 4) mm->knn_share = (int)v; }
     if (const char* e = std::getenv("SLIDEO_KNN_W12_RATIO")) mm->knn_w12_ratio = std::atof(e);
-    mm->knn_nseg_force = (int)std::max(0l, std::min(64l, env_long("SLIDEO_KNN_NSEG", 0)));
     mm->async_submit = env_long("SLIDEO_ASYNC_SUBMIT", 1) != 0;
     mm->knn_dedup = env_long("SLIDEO_KNN_DEDUP", 1) != 0;
     if (const char* e = std::getenv("SLIDEO_LSH_ENGINE")) mm->lsh_gather = std::string(e) == "gather";
@@ -481,44 +473,13 @@ int32_t slideo_matcher_create(const slideo_config* cfg, int32_t device, slideo_m
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && total_b >= ((size_t)192 << 30)) mm->sift_ws_mb = 96l << 10;
     }
     if (const char* e = std::getenv("SLIDEO_WS_GB")) { double gb = std::atof(e); if (gb > 0.1) mm->ws_budget = (size_t)(gb * (double)((size_t)1 << 30)); }
-    // SLIDEO_CU_SPLIT=N (measurement only: VERDICT r04 asked for spatial instead of per-CU sharing): N of the 256 CUs for the
-    // search streams, the rest for the slots' own streams.  Bit i of a HIP CU mask may be CU (i / 8) of XCD (i % 8) or CU (i % 32) of
-    // XCD (i / 32) depending on the runtime; the pattern below enables the same number of CUs in every XCD under either reading.
-    mm->cu_split = (int)std::min(248l, std::max(0l, env_long("SLIDEO_CU_SPLIT", 0))) / 8 * 8;
-    const int cu_split_others = (int)env_long("SLIDEO_CU_SPLIT_OTHERS", 1);      // 0: only the search is confined, the other stages may run anywhere
-    uint32_t mask_knn[8] = {0, 0, 0, 0, 0, 0, 0, 0}, mask_rest[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (mm->cu_split) {
-        for (int i = 0; i < 256; ++i) {
-            const int a = i & 7, b = (i >> 3) & 3, c = i >> 5;
-            const bool knn = ((a + c) & 7) * 4 + b < mm->cu_split / 8;
-            (knn ? mask_knn : mask_rest)[i >> 5] |= 1u << (i & 31);
-        }
-        if (mm->knn_share < 0) mm->knn_share = 0;    // the search has its CUs to itself: two blocks per CU (SLIDEO_KNN_SHARE=1 still forces one)
-    }
     hipStream_t picked[NSLOTS];
-    const bool pick = !mm->cu_split && env_long("SLIDEO_STREAM_PICK", 1) != 0;
+    const bool pick = env_long("SLIDEO_STREAM_PICK", 1) != 0;
     if (pick) pick_independent_streams(picked, NSLOTS);
     int slot_i = 0;
     for (Slot& S : mm->slots) {
-        if (pick) {
-            S.st = picked[slot_i++];
-            for (auto& e : S.ev) HIP_CHECK(hipEventCreate(&e));
-            HIP_CHECK(hipEventCreateWithFlags(&S.ev_in, hipEventDisableTiming));
-            HIP_CHECK(hipEventCreateWithFlags(&S.ev_orb, hipEventDisableTiming));
-            HIP_CHECK(hipEventCreateWithFlags(&S.ev_up, hipEventDisableTiming));
-            continue;
-        }
-        if (mm->cu_split) {
-            // (hipExtStreamCreateWithCUMask has no flags argument: these are BLOCKING streams — they synchronise implicitly with the
-            // legacy NULL stream, unlike the hipStreamNonBlocking streams of the normal path; a caller with default-stream work of its
-            // own distorts what the switch measures)
-            if (cu_split_others) HIP_CHECK(hipExtStreamCreateWithCUMask(&S.st, 8, mask_rest));
-            else HIP_CHECK(hipStreamCreateWithFlags(&S.st, hipStreamNonBlocking));
-            HIP_CHECK(hipExtStreamCreateWithCUMask(&S.st_knn, 8, mask_knn));
-            HIP_CHECK(hipEventCreateWithFlags(&S.ev_k0, hipEventDisableTiming));
-            HIP_CHECK(hipEventCreateWithFlags(&S.ev_k1, hipEventDisableTiming));
-        } else
-        HIP_CHECK(hipStreamCreateWithFlags(&S.st, hipStreamNonBlocking));
+        if (pick) S.st = picked[slot_i++];
+        else HIP_CHECK(hipStreamCreateWithFlags(&S.st, hipStreamNonBlocking));
         for (auto& e : S.ev) HIP_CHECK(hipEventCreate(&e));
         HIP_CHECK(hipEventCreateWithFlags(&S.ev_in, hipEventDisableTiming));
         HIP_CHECK(hipEventCreateWithFlags(&S.ev_orb, hipEventDisableTiming));
@@ -551,9 +512,6 @@ void slideo_matcher_destroy(slideo_matcher* m) {
     (void)hipSetDevice(m->device);
     for (Slot& S : m->slots) {
         if (S.st) { (void)hipStreamSynchronize(S.st); (void)hipStreamDestroy(S.st); }
-        if (S.st_knn) { (void)hipStreamSynchronize(S.st_knn); (void)hipStreamDestroy(S.st_knn); }
-        if (S.ev_k0) (void)hipEventDestroy(S.ev_k0);
-        if (S.ev_k1) (void)hipEventDestroy(S.ev_k1);
         for (auto& e : S.ev) if (e) (void)hipEventDestroy(e);
         if (S.ev_in) (void)hipEventDestroy(S.ev_in);
         if (S.ev_orb) (void)hipEventDestroy(S.ev_orb);

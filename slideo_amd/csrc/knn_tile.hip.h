@@ -325,10 +325,6 @@ __device__ __forceinline__ void knn_tile_body(const uint8_t* __restrict__ q, int
     uint32_t cntp = 0;                                                 // keys pending in this lane's private buffers, 8 bits per query tile
 #pragma unroll
     for (int i = 0; i < NT; ++i) h[i] = M::open_thr(nq_of(i));
-#ifdef KT_EXPERIMENT_NOSLOW          // measurement only (tools/knn_experiments.sh): no row ever qualifies, the pure streaming rate
-#pragma unroll
-    for (int i = 0; i < NT; ++i) h[i] = (Thr)1e9f;
-#endif
     auto cnt_of = [&](uint32_t packed, int i) -> uint32_t { return (packed >> (8 * i)) & 255u; };
 
     // owners drain the pending buffers of their two source lanes into their sorted lists (which live in `out`)
@@ -584,24 +580,17 @@ __device__ __forceinline__ void knn_tile_body(const uint8_t* __restrict__ q, int
         // One tile (tt = its index in the super-tile, compile time): (c*) = F(t) are live on entry, (n*) = F(t + 1) on exit;
         // group A (accumulators 0 .. G-1) already holds tile t.  Lc / Ln: this lane's fragment pointers into the slot of the
         // current / the next tile's super-tile; sdc: side array of the current slot.
-#ifdef KT_N23_EARLY      /* experiment: all four fragments of the next tile requested at the tile's start */
-#define KT_EARLY_N23(x) x
-#define KT_LATE_N23(x)
-#else
-#define KT_EARLY_N23(x)
-#define KT_LATE_N23(x) x
-#endif
 #define KT_TILE(tt, c0, c1, c2, c3, n0, n1, n2, n3)                                                                    \
         {                                                                                                             \
             const uint4* Lx_ = (tt) == KT_TPS - 1 ? Ln : Lc + ((tt) + 1) * 256;                                       \
-            n0 = Lx_[0]; n1 = Lx_[64]; KT_EARLY_N23(n2 = Lx_[128]; n3 = Lx_[192];)                                   \
+            n0 = Lx_[0]; n1 = Lx_[64];                                                                                \
             const uint32_t nmh_ = (tt) == 0 ? nm4.x : (tt) == 1 ? nm4.y : (tt) == 2 ? nm4.z : nm4.w;                  \
             {                                                                                                         \
                 KT_MFMAS(G, c0, c1, c2, c3)                                                                            \
                 KT_TREES(0, nmh_)                                                                                     \
                 KT_INTERLEAVE                                                                                         \
                 _Pragma("unroll") for (int g_ = 0; g_ < G; ++g_) asm volatile("" : "+v"(a[G + g_]));   /* keeps the MFMAs above the branch below */ \
-                KT_LATE_N23(n2 = Lx_[128]; n3 = Lx_[192];)                                                            \
+                n2 = Lx_[128]; n3 = Lx_[192];                                                                         \
                 KT_TEST(0, sdc, tt)                                                                                   \
             }                                                                                                         \
             {                                                                                                         \
@@ -662,8 +651,6 @@ __device__ __forceinline__ void knn_tile_body(const uint8_t* __restrict__ q, int
             }
         }
 #undef KT_TILE
-#undef KT_EARLY_N23
-#undef KT_LATE_N23
 #undef KT_TEST
 #undef KT_TREES
 #undef KT_INTERLEAVE
@@ -691,19 +678,10 @@ void knn_tile4_kernel(const uint32_t* __restrict__ q, int nq, const uint4* __res
     knn_tile_body<4, KtHamming>(reinterpret_cast<const uint8_t*>(q), nq, tx, side, reinterpret_cast<const uint4*>(nminh), nt_pad, st_per_seg, out, pend_ws,
                                 prune_tol, nq_dev);
 }
-#ifdef KT2_CLOBBER
-__global__ __launch_bounds__(KT_THREADS, 2)
-#elif defined(KT2_VGPRS)   /* experiments only: a cap below the 128 that 4 waves per SIMD allow */
-__global__ __attribute__((amdgpu_num_vgpr(KT2_VGPRS))) __launch_bounds__(KT_THREADS, 4)
-#else
 __global__ __launch_bounds__(KT_THREADS, 4)
-#endif
 void knn_tile2_kernel(const uint32_t* __restrict__ q, int nq, const uint4* __restrict__ tx, const uint32_t* __restrict__ side,
                       const float4* __restrict__ nminh, int nt_pad, int st_per_seg, uint32_t* __restrict__ out,
                       uint32_t* __restrict__ pend_ws, float prune_tol, const uint32_t* __restrict__ nq_dev, unsigned long long* __restrict__ clk) {
-#ifdef KT2_CLOBBER      /* experiment: the register allocation of a larger wave shape without its code */
-    asm volatile("" ::: KT2_CLOBBER);
-#endif
     knn_tile_body<2, KtHamming>(reinterpret_cast<const uint8_t*>(q), nq, tx, side, reinterpret_cast<const uint4*>(nminh), nt_pad, st_per_seg, out, pend_ws,
                                 prune_tol, nq_dev, KtNoCtx(), clk);
 }

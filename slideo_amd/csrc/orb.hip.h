@@ -34,14 +34,6 @@
 
 namespace slideo {
 
-// compile-time experiment hook (-DORB_PRIO=n, tools/ab_matrix.sh; not in the product build): the ORB stage's waves at instruction priority n
-// (the search's matrix sections run at 1 / 2, everything else at 0)
-#ifdef ORB_PRIO
-#define SLIDEO_ORB_PRIO() __builtin_amdgcn_s_setprio(ORB_PRIO)
-#else
-#define SLIDEO_ORB_PRIO()
-#endif
-
 // ---------------------------------------------------------------------------
 // [OCV A.1] gray = (B*3735 + G*19235 + R*9798 + 2^14) >> 15
 // grid (ceil(w/4/256), h, B)
@@ -49,7 +41,6 @@ namespace slideo {
 __global__ __launch_bounds__(256) void gray_kernel(const uint8_t* __restrict__ frames, int64_t frame_stride,
                                                    int stride, uint8_t* __restrict__ pyr, int64_t pyr_frame_bytes,
                                                    int w, int h, int pitch, int aligned4, GrayCoef gc) {
-    SLIDEO_ORB_PRIO();
     const uint32_t half = 1u << (gc.shift - 1);
     // (coefficients < 2^15, pixels < 2^8: 24-bit multiplies — full rate, where v_mul_lo_u32 takes four issue slots)
     auto gray_of = [&](uint32_t b, uint32_t g, uint32_t r) { return (__umul24(b, gc.cb) + __umul24(g, gc.cg) + __umul24(r, gc.cr) + half) >> gc.shift; };
@@ -93,7 +84,6 @@ constexpr int RESIZE_ROWS = 4;
 __global__ __launch_bounds__(256) void resize_kernel(uint8_t* __restrict__ pyr, int64_t pyr_frame_bytes,
                                                      LevelGeom src, LevelGeom dst,
                                                      const uint32_t* __restrict__ lin_tab, int nxq, uint32_t nxq_magic) {
-    SLIDEO_ORB_PRIO();
     const uint32_t t = blockIdx.x * 256 + threadIdx.x;
     const int yg = nxq_magic ? (int)__umulhi(t, nxq_magic) : (int)t;     // t / nxq (exact, see build_pyr_geom)
     const int y0 = yg * RESIZE_ROWS;
@@ -171,7 +161,6 @@ __global__ __launch_bounds__(256) void resize_kernel(uint8_t* __restrict__ pyr, 
 __global__ __launch_bounds__(256) void resize_quad_kernel(uint8_t* __restrict__ pyr, int64_t pyr_frame_bytes,
                                                           LevelGeom src, LevelGeom dst,
                                                           const uint32_t* __restrict__ lin_tab, int nxq, uint32_t nxq_magic) {
-    SLIDEO_ORB_PRIO();
     const uint32_t t = blockIdx.x * 256 + threadIdx.x;
     const uint32_t yg = nxq_magic ? __umulhi(t, nxq_magic) : t;
     const uint32_t y0 = yg * 4u;
@@ -339,17 +328,9 @@ __device__ __forceinline__ void fast_issue_loads(const PyrGeom& g, const FastTil
     }
 }
 
-#ifdef FAST_WAVES_EU      /* compile-time experiment hook: a register cap (6 waves per SIMD = 80 registers spills the tile offsets) */
-#define FAST_KERNEL_ATTR __attribute__((amdgpu_waves_per_eu(FAST_WAVES_EU)))
-#elif defined(FAST_VGPRS)  /* experiment hook: a HARD cap (amdgpu_num_vgpr counts in units of two: 32 = 64 registers; what does not fit spills) */
-#define FAST_KERNEL_ATTR __attribute__((amdgpu_num_vgpr(FAST_VGPRS)))
-#else
-#define FAST_KERNEL_ATTR
-#endif
-__global__ FAST_KERNEL_ATTR __launch_bounds__(256) void fast_kernel(PyrGeom g, const uint8_t* __restrict__ pyr,
+__global__ __launch_bounds__(256) void fast_kernel(PyrGeom g, const uint8_t* __restrict__ pyr,
                                                    uint32_t* __restrict__ cand, uint32_t* __restrict__ cand_count,
                                                    uint32_t* __restrict__ hist, const int4* __restrict__ tile_tab) {
-    SLIDEO_ORB_PRIO();
     __shared__ __attribute__((aligned(16))) uint8_t raw[FAST_RH][FAST_RW];
     __shared__ __attribute__((aligned(16))) uint8_t sc[FAST_SH][FAST_SW];
     // a wave's private share of the queue: its score rows (sy % 4 == wave), back to back
@@ -419,9 +400,6 @@ __global__ FAST_KERNEL_ATTR __launch_bounds__(256) void fast_kernel(PyrGeom g, c
     // left) leave only corner-like pixels, which are queued for the full test.  Positions past the keep-region's 1-px halo are
     // not needed (score 0); needed ones are >= 3 px inside the level.  Every wave appends to its own quarters of the two queues
     // with wave-uniform counts: no atomics, no waits.
-#if defined(FAST_ABL) && FAST_ABL == 0      /* timing experiments only (results invalid): 0 = load + commit only, 1 = + A1, 2 = + A2, 3 = + B */
-    T = Tn; continue;
-#endif
     const fast_us2 tt = {(unsigned short)t, (unsigned short)t};
     uint32_t myn = 0;
     // the position queue's share of a wave = what it can append in phase A2: four positions per group of the pool it walks
@@ -518,10 +496,6 @@ __global__ FAST_KERNEL_ATTR __launch_bounds__(256) void fast_kernel(PyrGeom g, c
         push1((fl & 8u) != 0u, p0 + 3);
     }
     const uint32_t mym = myn;
-#if defined(FAST_ABL) && FAST_ABL == 2
-    if (mym == 0xFFFFFFFFu) sc[0][0] = 1;
-    T = Tn; continue;
-#endif
     if (lane == 0) qcnt[wave] = mym;
     __syncthreads();
     // the queue = the four quarters back to back
@@ -582,9 +556,6 @@ __global__ FAST_KERNEL_ATTR __launch_bounds__(256) void fast_kernel(PyrGeom g, c
         }
         sc[sy][sx] = (uint8_t)score;      // every other position keeps score 0
     }
-#if defined(FAST_ABL) && FAST_ABL == 3
-    T = Tn; continue;
-#endif
     __syncthreads();
     // Phase C — NMS (strictly greater than all 8 neighbours) + emit, again only over the queue: a survivor is a
     // queued corner inside the output tile and the keep-region.
@@ -754,17 +725,11 @@ typedef float blur_f2 __attribute__((ext_vector_type(2)));
 //     k3 A[t] + k4 (M[t] + M[t-1]) + k5 (A[t+1] + A[t-1]) + k6 (M[t+1] + M[t-2])
 // is 7 packed instructions per pixel pair, in OpenCV's order of operations component by component.  The final
 // saturate_cast<uchar>(cvRound(s)) is one v_cvt_pk_u8_f32 per pixel (round to nearest even, saturating: tools/cvt_pk_probe.hip).
-#ifdef BLUR_VGPRS          /* experiment hook: hard register cap (units of two) */
-#define BLUR_KERNEL_ATTR __attribute__((amdgpu_num_vgpr(BLUR_VGPRS)))
-#else
-#define BLUR_KERNEL_ATTR
-#endif
 template <bool FMA>
-__global__ BLUR_KERNEL_ATTR __launch_bounds__(256) void blur_f32_kernel(PyrGeom g, const uint8_t* __restrict__ pyr,
+__global__ __launch_bounds__(256) void blur_f32_kernel(PyrGeom g, const uint8_t* __restrict__ pyr,
                                                        uint8_t* __restrict__ blur, OrbTables const* __restrict__ tab,
                                                        const uint8_t* __restrict__ strip_mask) {
     static_assert(BLUR_RH % 8 == 0, "four row pairs per unrolled round");
-    SLIDEO_ORB_PRIO();
     const int f = blockIdx.y;
     // strip_mask (frame path): one byte per (frame, tile, wave) strip, set by blur_mark_kernel iff some keypoint's BRIEF
     // samples can fall into the strip; the other strips of the blurred pyramid are never read, so they are not computed.
@@ -1240,7 +1205,6 @@ __global__ __launch_bounds__(256) void describe_blurred_kernel(PyrGeom g, const 
                                                                const uint64_t* __restrict__ items, uint32_t qtot,
                                                                const uint2* __restrict__ ic_tab, int ic_shift, int ic_entries,
                                                                slideo_keypoint* __restrict__ kp, uint8_t* __restrict__ desc, int atan_fma) {
-    SLIDEO_ORB_PRIO();
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // (scalar: the keypoint, its level and frame stay on the SALU)
     const uint32_t gi = blockIdx.x * 4 + wave;
     const int lane = threadIdx.x & 63;

@@ -68,10 +68,6 @@ struct Slot {
     hipStream_t st = nullptr;
     hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     hipEvent_t ev_in = nullptr, ev_orb = nullptr, ev_up = nullptr;
-    // SLIDEO_CU_SPLIT (measurement switch, off by default): the search on a stream of its own whose CU mask holds N CUs, the other
-    // stages on the complement — spatial instead of per-CU sharing; ev_k0 / ev_k1 order the search stream behind / before the slot's
-    hipStream_t st_knn = nullptr;
-    hipEvent_t ev_k0 = nullptr, ev_k1 = nullptr;
     // arguments of the unit in flight (re-run through the exact-size path if the capacity-sized one overflowed)
     const uint8_t* u_frames = nullptr; int u_w = 0, u_h = 0, u_stride = 0; int64_t u_fs = 0; bool u_async = false; int u_nt = 0; bool u_shared = false, u_w12 = false;
     DevBuf d_stage, d_pyr, d_blur, d_cand, d_hist, d_candcount, d_flags, d_thr, d_lvlofs, d_kpcount, d_qofs, d_info;
@@ -157,15 +153,15 @@ struct slideo_matcher {
     struct Kept { bool valid = false; int n = 0, w = 0, h = 0, stride = 0; } kept;
     slideo::DevBuf d_kept;
     bool units_pending = false;   // the call being served has more units than the one submitted now
-    int cu_split = 0;       // SLIDEO_CU_SPLIT=N: the search on N CUs (two blocks per CU), ORB / verify on the other 256 - N (0 = off: every stream on every CU)
     // while units share the chip the search runs the 12-wave block (three waves per SIMD, 128 registers each) instead of the 8-wave
     // block + LDS pad when a unit carries at least this many (query, train row) pairs per frame pixel: the larger the deck, the more of
     // a step is search, and from ~290 pairs per pixel on the fuller matrix pipe is worth more than the co-runners' occupancy
     // (profiles/r06_experiments.txt 7: headline 197: - 2..4 %; 700 pages 275: - 1.7 %; 800 pages 314: + 5.5 %; configs[3] 392:
     // + 6.8 %; configs[4] 352: + 4.7 %).  SLIDEO_KNN_W12_RATIO overrides (0 = never).
     double knn_w12_ratio = 290.0;
-    int knn_nseg_force = 0; // SLIDEO_KNN_NSEG=n (measurement): train-stream segments of the matrix-core search instead of the plan's
-    int knn_share = -1;     // search blocks per CU: -1 = one while other units are in flight, two otherwise (default); 0 = always two; 1 = always one; 3 / 4 = the 12-wave block while shared / always; 5 / 6 = the 1-tile 12-wave block (knn_tile1.hip.h) while shared / always (SLIDEO_KNN_SHARE)
+    int knn_share = -1;     // the search's block shape (SLIDEO_KNN_SHARE; stage_knn.hip knn_shape): -1 = while other units are in flight one 8-wave block per CU,
+                            // or the 12-wave block for large decks (knn_w12_ratio), two 8-wave blocks otherwise (default); 0 = always two 8-wave blocks;
+                            // 1 = always one; 3 / 4 = the 12-wave block while shared / always
     int knn_engine = 0;     // 0 = FP4 MFMA, wave shape chosen per launch (default), 1 = integer VALU popcount,
                             // 2 = FP4 MFMA, 2 waves/SIMD x 4 query tiles (knn_tile4_kernel), 3 = 4 waves/SIMD x 2 tiles (knn_tile2_kernel)
     int knn_exact_lists = 0;  // 1 = the matcher's kNN stage keeps full exact k-NN lists (no fused vote filter)
@@ -246,7 +242,7 @@ void knn_build_index(slideo_matcher* m, const std::vector<uint8_t>& train, int64
 // workspace of a unit's search (before the timed interval) and the search itself: S.d_desc -> S.d_keys (+ the expansion of the
 // collapsed rows).  qplan: the query count the launch is planned for, qtot: the capacity (async) or the real count.
 void knn_reserve_unit(slideo_matcher* m, Slot& S, uint32_t qplan, uint32_t qtot);
-void unit_knn(slideo_matcher* m, Slot& S, int n, uint32_t qplan, uint32_t qtot, bool async, bool prof, hipStream_t st);
+void unit_knn(slideo_matcher* m, Slot& S, int n, uint32_t qplan, uint32_t qtot, bool async, bool prof);
 bool knn_unit_is_valu(const slideo_matcher* m, int nq);
 int knn_unit_rows(const slideo_matcher* m, int nq);        // train rows a unit's search evaluates (Mu, or M for the VALU engine)
 void l2_prepare(slideo_matcher::L2Set& L, const uint8_t* t, int nt, hipStream_t st);

@@ -438,17 +438,12 @@ constexpr int SIFT_EX_RCH = 34;                 // output rows per block (+ 2 ha
 constexpr int SIFT_EX_COLS = 126;               // output columns per wave
 constexpr int SIFT_EX_STAGE = 512;              // candidates a wave stages in LDS before its one list append
 
-#ifdef SIFT_EX_BPERMUTE
-__device__ __forceinline__ float sift_wave_shr1(float v) { return __shfl_up(v, 1); }
-__device__ __forceinline__ float sift_wave_shl1(float v) { return __shfl_down(v, 1); }
-#else
 __device__ __forceinline__ float sift_wave_shr1(float v) {      // lane i <- lane i - 1 (lane 0 keeps its own)
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, v), __builtin_bit_cast(int, v), 0x138, 0xF, 0xF, false));
 }
 __device__ __forceinline__ float sift_wave_shl1(float v) {      // lane i <- lane i + 1 (lane 63 keeps its own)
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, v), __builtin_bit_cast(int, v), 0x130, 0xF, 0xF, false));
 }
-#endif
 
 __global__ __launch_bounds__(256) void sift_extrema_kernel(SiftGeom g, SiftParams sp, int o, const float* __restrict__ gauss,
                                                            uint32_t* __restrict__ cand, uint32_t* __restrict__ cand_count, uint32_t* __restrict__ flags) {

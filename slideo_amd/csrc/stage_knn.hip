@@ -2,7 +2,6 @@
 #include "runtime.hpp"
 #include "knn.hip.h"
 #include "knn_tile.hip.h"
-#include "knn_tile1.hip.h"
 #include "knn_l2.hip.h"
 #include "knn_lsh.hip.h"
 
@@ -123,23 +122,20 @@ void knn_probe_report() {
     (void)hipMemcpyToSymbol(HIP_SYMBOL(slideo::kt_probe), z, sizeof(z));
 }
 #endif
-static unsigned share_pad(const slideo_matcher* m, const Slot& S) { return (m->knn_share == 1 || ((m->knn_share < 0 || m->knn_share >= 5) && S.u_shared)) ? KT_SHARE_PAD : 0u; }
+static unsigned share_pad(const slideo_matcher* m, const Slot& S) { return (m->knn_share == 1 || (m->knn_share < 0 && S.u_shared)) ? KT_SHARE_PAD : 0u; }
 // The block shape of the exact Hamming search (engine 3).  SHAPE_T2: knn_tile2_kernel, 8 waves x 2 query tiles, two blocks per CU or
 // — with the LDS pad — one.  SHAPE_T2W12 (by default for LARGE decks while units share the chip — knn_w12_ratio —; SLIDEO_KNN_SHARE=3 / 4 force it):
-// the same wave shape, 12 waves, one block per CU by its registers.  SHAPE_T1W12 (knn_tile1.hip.h; SLIDEO_KNN_SHARE=5: while other units are in flight, 6: always): 12 waves x 1 query
-// tile at 80 registers — three waves per SIMD in the registers two 2-tile waves take; one block per CU by the LDS pad while units
-// share the chip, two otherwise.  Only the exact search (matcher 0): the LSH-filtered stream has its own kernel and plan.
-enum KnnShape { SHAPE_T2 = 0, SHAPE_T2W12 = 1, SHAPE_T1W12 = 2 };
+// the same wave shape, 12 waves, one block per CU by its registers.  Only the exact search (matcher 0): the LSH-filtered stream has
+// its own kernel and plan.
+enum KnnShape { SHAPE_T2 = 0, SHAPE_T2W12 = 1 };
 static KnnShape knn_shape(const slideo_matcher* m, const Slot& S) {
     if (m->cfg.matcher != 0) return SHAPE_T2;
     if ((m->knn_share == 3 && S.u_shared) || m->knn_share == 4) return SHAPE_T2W12;
     if (m->knn_share < 0 && S.u_shared && S.u_w12) return SHAPE_T2W12;       // large decks (runtime.hpp knn_w12_ratio)
-    if ((m->knn_share == 5 && S.u_shared) || m->knn_share == 6) return SHAPE_T1W12;
     return SHAPE_T2;
 }
-static int shape_qpb(KnnShape sh) { return sh == SHAPE_T1W12 ? KT1_QPB : sh == SHAPE_T2W12 ? knn_qpb<2, KT_WAVES12>() : knn_qpb<2>(); }
-static int shape_waves(KnnShape sh) { return sh == SHAPE_T1W12 ? KT1_WAVES : sh == SHAPE_T2W12 ? KT_WAVES12 : KT_WAVES; }
-static size_t shape_pend_words(KnnShape sh) { return sh == SHAPE_T1W12 ? KT1_PEND_WORDS_PER_WAVE : knn_pend_words_per_wave<2>(); }
+static int shape_qpb(KnnShape sh) { return sh == SHAPE_T2W12 ? knn_qpb<2, KT_WAVES12>() : knn_qpb<2>(); }
+static int shape_waves(KnnShape sh) { return sh == SHAPE_T2W12 ? KT_WAVES12 : KT_WAVES; }
 struct KnnPlan { int engine, qblocks, nseg, per_seg; };
 // Engine 0 ("mfma") = the 2-tile wave shape (knn_tile2_kernel: 4 waves/SIMD, two 512-query blocks per CU) at every size: since the
 // {0,1} operand alphabet it runs the headline launch in 10.0 ms alone against 11.3 for the 4-tile shape and the step is 2 %
@@ -175,7 +171,6 @@ static KnnPlan knn_plan(const slideo_matcher* m, int nq, int nt, int nq_grid = 0
         // empty slots do).  Measured (r01): 236 query blocks x 1.8 M rows (64 4K frames): 1 segment 33.2 ms, 2 segments 24.2 ms,
         // 3 segments 23.5 ms; 239 query blocks x 517 k rows (128 1080p frames): 2 segments 6.24 ms, 3 segments 6.65 ms
         int nseg = p.qblocks >= (w12 ? 192 : 384) ? 1 : std::min(std::max((w12 ? 256 : 512) / std::max(p.qblocks, 1), 1), n_st);
-        if (m->knn_nseg_force > 0) nseg = std::min(m->knn_nseg_force, n_st);      // (SLIDEO_KNN_NSEG: measurement)
         p.per_seg = cdiv(n_st, std::max(nseg, 1));
         p.nseg = cdiv(n_st, p.per_seg);
         p.qblocks = cdiv(nq_grid, qpb);
@@ -197,7 +192,7 @@ static void knn_reserve(slideo_matcher* m, Slot& S, int nq, int nt, int nq_grid 
     const KnnPlan p = knn_plan(m, nq, nt, nq_grid, sh);
     S.d_keys.reserve((size_t)p.nseg * std::max(std::max(nq, nq_grid), 1) * KLIST * 4);
     if (p.engine == 2) S.d_knn_pend.reserve((size_t)p.qblocks * p.nseg * KT_WAVES * knn_pend_words_per_wave<4>() * 4);
-    if (p.engine == 3) S.d_knn_pend.reserve((size_t)p.qblocks * p.nseg * shape_waves(sh) * shape_pend_words(sh) * 4);
+    if (p.engine == 3) S.d_knn_pend.reserve((size_t)p.qblocks * p.nseg * shape_waves(sh) * knn_pend_words_per_wave<2>() * 4);
 }
 
 // prune_tol > 0: only neighbours that can pass the vote's `d < best * tol` need to be exact (matrix-core engine; the VALU
@@ -212,9 +207,9 @@ struct TrainOps {             // device operands of one train set, per engine
 // nq_dev != null: the real query count lives on the device (the host did not wait for the ORB counts); then `nq` is the
 // estimate the plan is made for and nq_grid the capacity the grid and the buffers cover.  Only the matrix-core engine.
 static void run_knn(slideo_matcher* m, Slot& S, const uint32_t* q_dev, int nq, const TrainOps& T, int nt, float prune_tol,
-             const uint32_t* nq_dev = nullptr, int nq_grid = 0, hipStream_t st_arg = nullptr) {
+             const uint32_t* nq_dev = nullptr, int nq_grid = 0) {
     if (nq <= 0 && !nq_dev) return;
-    hipStream_t st = st_arg ? st_arg : S.st;
+    hipStream_t st = S.st;
     if ((int64_t)nt >= ((int64_t)1 << KNN_KEY_SHIFT)) fail(SLIDEO_ERR_UNSUPPORTED, "train set of %d rows exceeds %d", nt, 1 << KNN_KEY_SHIFT);
     const KnnShape sh = knn_shape(m, S);
     const KnnPlan p = knn_plan(m, nq, nt, nq_grid, sh);
@@ -225,9 +220,6 @@ static void run_knn(slideo_matcher* m, Slot& S, const uint32_t* q_dev, int nq, c
         if (p.engine == 2)
             knn_tile4_kernel<<<dim3(p.qblocks, p.nseg), KT_THREADS, 0, st>>>(q_dev, nq, T.txb, T.side, T.nminh, knn_pad_rows(nt), p.per_seg,
                                                                              S.d_keys.as<uint32_t>(), S.d_knn_pend.as<uint32_t>(), prune_tol, nq_dev);
-        else if (sh == SHAPE_T1W12)
-            knn_tile1w12_kernel<<<dim3(p.qblocks, p.nseg), KT1_WAVES * 64, 0, st>>>(q_dev, nq, T.txb, T.side, T.nminh, knn_pad_rows(nt), p.per_seg,
-                                                                             S.d_keys.as<uint32_t>(), S.d_knn_pend.as<uint32_t>(), prune_tol, nq_dev, clk);
         else if (sh == SHAPE_T2W12)
             knn_tile2w12_kernel<<<dim3(p.qblocks, p.nseg), KT_WAVES12 * 64, 0, st>>>(q_dev, nq, T.txb, T.side, T.nminh, knn_pad_rows(nt), p.per_seg,
                                                                              S.d_keys.as<uint32_t>(), S.d_knn_pend.as<uint32_t>(), prune_tol, nq_dev, clk);
@@ -262,8 +254,9 @@ void knn_reserve_unit(slideo_matcher* m, Slot& S, uint32_t qplan, uint32_t qtot)
 
 // A unit's search: S.d_desc (n frames' descriptors, offsets S.d_qofs) -> S.d_keys.  async: the real query count lives on the
 // device (S.d_qofs[n]), qplan is what the launch is planned for and qtot the capacity the grid covers.
-void unit_knn(slideo_matcher* m, Slot& S, int n, uint32_t qplan, uint32_t qtot, bool async, bool prof, hipStream_t st) {
+void unit_knn(slideo_matcher* m, Slot& S, int n, uint32_t qplan, uint32_t qtot, bool async, bool prof) {
     const slideo_config& c = m->cfg;
+    hipStream_t st = S.st;
     const bool dedup = knn_unit_dedup(m, (int)qplan);
     const int nt_knn = knn_unit_rows(m, (int)qplan);
     // a neighbour counts iff d < best * vote_tolerance (verify.hip.h vote_kernel); with tolerance < 1 rows below the
@@ -294,7 +287,7 @@ void unit_knn(slideo_matcher* m, Slot& S, int n, uint32_t qplan, uint32_t qtot, 
             check_launch("knn_merge_kernel");
         }
     } else
-        run_knn(m, S, S.d_desc.as<uint32_t>(), (int)qplan, T, nt_knn, prune, async ? S.d_qofs.as<uint32_t>() + n : nullptr, (int)qtot, st);
+        run_knn(m, S, S.d_desc.as<uint32_t>(), (int)qplan, T, nt_knn, prune, async ? S.d_qofs.as<uint32_t>() + n : nullptr, (int)qtot);
     if (prof) HIP_CHECK(hipEventRecord(S.ev[2], st));      // the kNN interval ends here: the search kernel (+ its segment merge)
     if (dedup) {
         knn_expand_dups_kernel<KLIST><<<cdiv((int)std::max(qtot, 1u), KNN_BLOCK), KNN_BLOCK, 0, st>>>(

@@ -24,6 +24,22 @@ def test_library_exports_every_declared_symbol(capi):
     assert L.slideo_abi_version() == 7        # ABI 7: + slideo_matcher_read_shader_clock (6: verdict_rule, slideo_device_list, n_devices 0; ocv.hdlt defaults to 1)
 
 
+def test_header_lists_every_environment_switch():
+    """include/slideo_amd.h "Environment" lists every SLIDEO_* variable that csrc/ reads, and csrc/ reads every one listed there
+    (the build-time line aside: the Python build and loader read those)."""
+    hdr = open(os.path.join(ROOT, "include", "slideo_amd.h")).read()
+    block = hdr[hdr.index(" * Environment"):]
+    block = block[:block.index("*/")]
+    listed = {n for line in block.splitlines() if "build time only" not in line for n in re.findall(r"\bSLIDEO_[A-Z0-9_]+", line)}
+    csrc = os.path.join(ROOT, "slideo_amd", "csrc")
+    read = set()
+    for f in os.listdir(csrc):
+        read |= set(re.findall(r'(?:env_long|getenv)\("(SLIDEO_[A-Z0-9_]+)"', open(os.path.join(csrc, f)).read()))
+    assert len(read) >= 10
+    assert not read - listed, "read in csrc/ but not listed in the header: %s" % sorted(read - listed)
+    assert not listed - read, "listed in the header but read nowhere in csrc/: %s" % sorted(listed - read)
+
+
 def test_config_struct_matches_oracle_layout(capi, oracle):
     import ctypes as C
     a, b = capi.default_config(), oracle.default_config()

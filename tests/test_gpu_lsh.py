@@ -42,7 +42,7 @@ def test_knn_lsh_many_ties_at_the_kth_distance(capi, oracle):
     m.close()
 
 
-@pytest.mark.parametrize("share", [None, "4", "6"])
+@pytest.mark.parametrize("share", [None, "4"])
 def test_lsh_mode_traces(capi, oracle, synth, cfg0_data, monkeypatch, share):
     """(share: SLIDEO_KNN_SHARE forcing the 12-wave block shapes of the EXACT search — the LSH-filtered stream keeps its own 8-wave
     kernel and plan, and its buffers must be reserved for that plan: ADVICE r05, stage_knn.hip knn_shape)"""
