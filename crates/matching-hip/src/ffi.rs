@@ -2,7 +2,7 @@
 //! uses.  Field order and types mirror the C structs exactly; tests/test_capi_load.py pins the C side's layout
 //! (sizeof(slideo_config) == 168) and `assert_abi()` below pins the version at run time.
 #![allow(non_camel_case_types)]
-use std::os::raw::c_char;
+use std::os::raw::{c_char, c_void};
 
 pub const SLIDEO_ABI_VERSION: u32 = 7;
 
@@ -87,6 +87,35 @@ pub struct slideo_group {
     _private: [u8; 0],
 }
 
+/// One matcher on one device (the single-device handle; this crate drives the group, the YUV twins take either).
+#[repr(C)]
+pub struct slideo_matcher {
+    _private: [u8; 0],
+}
+
+/// slideo_yuv420_layout (include/slideo_amd.h, "YUV 4:2:0 frames"): where the planes of one decoded frame sit, so that a VCN or
+/// FFmpeg FrameSource hands its NV12 / I420 surface to the *_yuv420 calls as it is (pitched; chroma at pitch * aligned_height).
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct slideo_yuv420_layout {
+    /// bytes between luma rows, >= width
+    pub y_stride: i32,
+    /// bytes between chroma rows
+    pub uv_stride: i32,
+    /// byte offset of the first U sample from the frame's base; the Y plane starts at the base
+    pub u_offset: i64,
+    /// byte offset of the first V sample
+    pub v_offset: i64,
+    /// 2 = interleaved (NV12 / NV21), 1 = planar (I420 / YV12)
+    pub uv_step: i32,
+    pub _pad: i32,
+}
+
+pub const SLIDEO_YUV420_NV12: i32 = 0;
+pub const SLIDEO_YUV420_NV21: i32 = 1;
+pub const SLIDEO_YUV420_I420: i32 = 2;
+pub const SLIDEO_YUV420_YV12: i32 = 3;
+
 extern "C" {
     pub fn slideo_abi_version() -> u32;
     pub fn slideo_config_default(cfg: *mut slideo_config);
@@ -141,6 +170,85 @@ extern "C" {
         changed_out: *mut u8,
         similarity_out: *mut f32,
     ) -> i32;
+    // ---- decoded YUV 4:2:0 frames: the twins of the frame calls (same results as the BGR call on cvtColor's BGR image)
+    pub fn slideo_yuv420_layout_packed(format: i32, width: i32, height: i32, out: *mut slideo_yuv420_layout) -> i32;
+    pub fn slideo_group_match_frames_yuv420(
+        g: *mut slideo_group,
+        n_frames: i32,
+        frames: *const u8,
+        width: i32,
+        height: i32,
+        layout: *const slideo_yuv420_layout,
+        frame_stride_bytes: i64,
+        verdicts_out: *mut slideo_verdict,
+    ) -> i32;
+    pub fn slideo_group_changed_mask_yuv420(
+        g: *mut slideo_group,
+        n_frames: i32,
+        frames: *const u8,
+        width: i32,
+        height: i32,
+        layout: *const slideo_yuv420_layout,
+        frame_stride_bytes: i64,
+        prev_small: *const u8,
+        last_small_out: *mut u8,
+        changed_out: *mut u8,
+        similarity_out: *mut f32,
+    ) -> i32;
+    pub fn slideo_match_frames_yuv420(
+        m: *mut slideo_matcher,
+        n_frames: i32,
+        frames: *const u8,
+        width: i32,
+        height: i32,
+        layout: *const slideo_yuv420_layout,
+        frame_stride_bytes: i64,
+        verdicts_out: *mut slideo_verdict,
+    ) -> i32;
+    pub fn slideo_match_frames_yuv420_dev(
+        m: *mut slideo_matcher,
+        n_frames: i32,
+        frames_dev: *const u8,
+        width: i32,
+        height: i32,
+        layout: *const slideo_yuv420_layout,
+        frame_stride_bytes: i64,
+        verdicts_out: *mut slideo_verdict,
+        hip_stream: *mut c_void,
+    ) -> i32;
+    pub fn slideo_match_frames_submit_yuv420_dev(
+        m: *mut slideo_matcher,
+        n_frames: i32,
+        frames_dev: *const u8,
+        width: i32,
+        height: i32,
+        layout: *const slideo_yuv420_layout,
+        frame_stride_bytes: i64,
+        hip_stream: *mut c_void,
+        ticket_out: *mut i64,
+    ) -> i32;
+    pub fn slideo_changed_mask_yuv420(
+        m: *mut slideo_matcher,
+        n_frames: i32,
+        frames: *const u8,
+        width: i32,
+        height: i32,
+        layout: *const slideo_yuv420_layout,
+        frame_stride_bytes: i64,
+        prev_small: *const u8,
+        last_small_out: *mut u8,
+        changed_out: *mut u8,
+        similarity_out: *mut f32,
+    ) -> i32;
+    pub fn slideo_yuv420_to_bgr8(
+        m: *mut slideo_matcher,
+        frame: *const u8,
+        width: i32,
+        height: i32,
+        layout: *const slideo_yuv420_layout,
+        bgr_out: *mut u8,
+        out_capacity: i64,
+    ) -> i32;
 }
 
 /// The struct layouts above are only valid for one ABI version of the library.
@@ -153,4 +261,5 @@ pub fn assert_abi() {
     );
     assert_eq!(std::mem::size_of::<slideo_config>(), 168);
     assert_eq!(std::mem::size_of::<slideo_verdict>(), 16);
+    assert_eq!(std::mem::size_of::<slideo_yuv420_layout>(), 32);
 }

@@ -16,6 +16,8 @@
  *   - no C++ exception crosses the ABI;
  *   - images are 8-bit, 3 channels, BGR interleaved, row-major with a byte
  *     stride (the cv::Mat 8UC3 layout the reference holds, mo/lib.rs:77-83);
+ *     the frame entry points also come as *_yuv420 twins that take decoded
+ *     YUV 4:2:0 frames (NV12 / NV21 / I420 / YV12, section "YUV 4:2:0 frames");
  *   - "page" = one rasterised PDF page, "frame" = one decoded video frame,
  *     page indices are 0-based positions in the order pages were added.
  *   - there is NO CPU fallback: without a gfx950 device every compute entry
@@ -569,6 +571,70 @@ int32_t     slideo_group_changed_mask_bgr8(slideo_group* g, int32_t n_frames, co
                                            int32_t stride_bytes, int64_t frame_stride_bytes, const uint8_t* prev_small,
                                            uint8_t* last_small_out, uint8_t* changed_out, float* similarity_out);
 int32_t     slideo_group_match_kept_frames(slideo_group* g, int32_t n_sel, const int32_t* sel, slideo_verdict* verdicts_out);
+
+/* ---- YUV 4:2:0 frames ----------------------------------------------------------------------------------------------
+ * Video decoders (VCN, FFmpeg's software H.264 / HEVC decoders, VA-API) hand out YUV 4:2:0 — NV12, or planar I420 — not BGR.
+ * Every frame entry point above has a *_yuv420 twin that takes such frames: half the bytes of BGR over PCIe, converted on the
+ * GPU (csrc/yuv420.hip.h yuv420_to_bgr_kernel) into the BGR image the rest of the pipeline reads, unchanged.
+ *
+ * Semantics: a 4:2:0 frame STANDS FOR the BGR image OpenCV 4.x cvtColor(COLOR_YUV2BGR_NV12 / _NV21 / _I420 / _YV12) makes of it
+ * [OCV A.14, recalled from imgproc/src/color_yuv.simd.hpp, confidence M]: BT.601 limited range, nearest chroma (pixel (x, y) takes
+ * the chroma sample (x/2, y/2)), fixed point with SHIFT 20:
+ *     CY = 1220542, CUB = 2116026, CUG = -409993, CVG = -852492, CVR = 1673527, half = 1 << 19
+ *     u = U - 128, v = V - 128, y = max(0, Y - 16) * CY                       (int32; >> is arithmetic)
+ *     R = sat_u8((y + half + CVR*v) >> 20)
+ *     G = sat_u8((y + half + CVG*v + CUG*u) >> 20)
+ *     B = sat_u8((y + half + CUB*u) >> 20)
+ * Contract: every *_yuv420 call returns exactly what the matching *_bgr8 call returns on that BGR image, bit for bit (verdicts,
+ * candidate traces, changed flags, similarities, small images).  slideo_yuv420_to_bgr8 returns the image itself.
+ * DEPARTURE: the reference's own BGR comes from swscale inside OpenCV's FFmpeg backend (mo/video_capture.rs:42-57), not from
+ * cvtColor, and is not reproduced bit for bit; both read the stream as BT.601 (OpenCV 4.5.2's FFmpeg backend sets no
+ * sws_setColorspaceDetails — also recalled).
+ * Width and height must be even (as cvtColor requires): else SLIDEO_ERR_UNSUPPORTED.  A bad layout is SLIDEO_ERR_INVALID_ARG,
+ * and the message names the rule: uv_step 1 or 2; offsets >= 0; y_stride >= width; uv_stride >= (width/2) * uv_step; with
+ * uv_step 2 the V byte sits next to the U byte (|v_offset - u_offset| == 1); the Y, U and V planes do not overlap (an interleaved
+ * chroma plane counts as one); frame_stride covers the furthest byte of every plane. */
+typedef struct slideo_yuv420_layout {
+    int32_t y_stride;     /* bytes between luma rows, >= width                                                       */
+    int32_t uv_stride;    /* bytes between chroma rows                                                               */
+    int64_t u_offset;     /* byte offset of the first U sample from the frame's base; the Y plane starts at the base */
+    int64_t v_offset;     /* byte offset of the first V sample                                                       */
+    int32_t uv_step;      /* 2 = interleaved (NV12: v_offset = u_offset + 1; NV21: the reverse); 1 = planar (I420, YV12) */
+    int32_t _pad;
+} slideo_yuv420_layout;   /* 32 bytes.  Decoder surfaces are pitched: the chroma plane sits at pitch * aligned_height */
+
+#define SLIDEO_YUV420_NV12 0
+#define SLIDEO_YUV420_NV21 1
+#define SLIDEO_YUV420_I420 2
+#define SLIDEO_YUV420_YV12 3
+/* The tightly packed layout of `format` (SLIDEO_YUV420_*) at width x height: y_stride = width, chroma right after the luma rows
+ * (I420: U then V, each (width/2) x (height/2); YV12: V then U).  Such a frame is width * height * 3 / 2 bytes. */
+int32_t     slideo_yuv420_layout_packed(int32_t format, int32_t width, int32_t height, slideo_yuv420_layout* out);
+
+/* The twins.  Each takes (frames, width, height, layout, frame_stride_bytes) in place of (frames, width, height, stride_bytes,
+ * frame_stride_bytes); everything else is as for the BGR call.  Host calls upload the YUV bytes (the furthest byte of each frame)
+ * and convert on the GPU; device calls convert from the caller's memory.  The BGR image lives in the matcher's workspace until
+ * the unit is collected: slideo_match_frames_collect[_dev] collects what slideo_match_frames_submit_yuv420_dev submits, and
+ * slideo_match_kept_frames / slideo_group_match_kept_frames work after the YUV mask calls unchanged. */
+int32_t     slideo_match_frames_yuv420(slideo_matcher* m, int32_t n_frames, const uint8_t* frames, int32_t width, int32_t height,
+                                       const slideo_yuv420_layout* layout, int64_t frame_stride_bytes, slideo_verdict* verdicts_out);
+int32_t     slideo_match_frames_yuv420_dev(slideo_matcher* m, int32_t n_frames, const uint8_t* frames_dev, int32_t width, int32_t height,
+                                           const slideo_yuv420_layout* layout, int64_t frame_stride_bytes, slideo_verdict* verdicts_out,
+                                           void* hip_stream);
+int32_t     slideo_match_frames_submit_yuv420_dev(slideo_matcher* m, int32_t n_frames, const uint8_t* frames_dev, int32_t width,
+                                                  int32_t height, const slideo_yuv420_layout* layout, int64_t frame_stride_bytes,
+                                                  void* hip_stream, int64_t* ticket_out);
+int32_t     slideo_changed_mask_yuv420(slideo_matcher* m, int32_t n_frames, const uint8_t* frames, int32_t width, int32_t height,
+                                       const slideo_yuv420_layout* layout, int64_t frame_stride_bytes, const uint8_t* prev_small,
+                                       uint8_t* last_small_out, uint8_t* changed_out, float* similarity_out);
+/* Tap: the BGR image (stride width * 3, out_capacity >= width * height * 3) of one host frame. */
+int32_t     slideo_yuv420_to_bgr8(slideo_matcher* m, const uint8_t* frame, int32_t width, int32_t height,
+                                  const slideo_yuv420_layout* layout, uint8_t* bgr_out, int64_t out_capacity);
+int32_t     slideo_group_match_frames_yuv420(slideo_group* g, int32_t n_frames, const uint8_t* frames, int32_t width, int32_t height,
+                                             const slideo_yuv420_layout* layout, int64_t frame_stride_bytes, slideo_verdict* verdicts_out);
+int32_t     slideo_group_changed_mask_yuv420(slideo_group* g, int32_t n_frames, const uint8_t* frames, int32_t width, int32_t height,
+                                             const slideo_yuv420_layout* layout, int64_t frame_stride_bytes, const uint8_t* prev_small,
+                                             uint8_t* last_small_out, uint8_t* changed_out, float* similarity_out);
 
 #ifdef __cplusplus
 }

@@ -44,6 +44,54 @@ class SiftConfig(C.Structure):
                 ("edge_threshold", C.c_double), ("sigma", C.c_double)]
 
 
+class Yuv420Layout(C.Structure):
+    """slideo_yuv420_layout (include/slideo_amd.h, "YUV 4:2:0 frames"): where the planes of one decoded frame sit."""
+    _fields_ = [("y_stride", C.c_int32), ("uv_stride", C.c_int32), ("u_offset", C.c_int64), ("v_offset", C.c_int64),
+                ("uv_step", C.c_int32), ("_pad", C.c_int32)]
+
+
+YUV420_FORMATS = {"nv12": 0, "nv21": 1, "i420": 2, "yv12": 3}
+
+
+def yuv420_layout(fmt, w, h, pitch=None, row_align=None):
+    """Layout of a `fmt` frame ('nv12', 'nv21', 'i420', 'yv12') of w x h -> (Yuv420Layout, frame bytes).  pitch: bytes per luma
+    row (default w; a planar format's chroma rows take pitch / 2); row_align: the chroma plane starts at pitch * align(h, row_align),
+    as on a decoder surface.  Without either, the tightly packed layout (what slideo_yuv420_layout_packed returns)."""
+    if fmt not in YUV420_FORMATS:
+        raise ValueError("unknown 4:2:0 format %r" % (fmt,))
+    p = int(pitch or w)
+    ah = -(-h // row_align) * row_align if row_align else h
+    luma = p * ah
+    L = Yuv420Layout()
+    L.y_stride = p
+    if fmt in ("nv12", "nv21"):
+        L.uv_stride, L.uv_step = p, 2
+        L.u_offset, L.v_offset = (luma, luma + 1) if fmt == "nv12" else (luma + 1, luma)
+    else:
+        L.uv_stride, L.uv_step = p // 2, 1
+        first, second = luma, luma + (p // 2) * (ah // 2)
+        L.u_offset, L.v_offset = (first, second) if fmt == "i420" else (second, first)
+    return L, luma * 3 // 2
+
+
+def yuv420_layout_packed(fmt, w, h):
+    """slideo_yuv420_layout_packed: the library's own tightly packed layout of `fmt`."""
+    L = Yuv420Layout()
+    rc = lib().slideo_yuv420_layout_packed(YUV420_FORMATS[fmt], int(w), int(h), C.byref(L))
+    if rc != OK:
+        raise SlideoError(rc, "slideo_yuv420_layout_packed(%s, %d, %d)" % (fmt, w, h))
+    return L
+
+
+def _yuv_frames(frames, w, h, layout):
+    """frames: uint8 [n, frame_bytes] (or one frame, 1-D) -> (contiguous [n, frame_bytes], layout, frame stride)."""
+    frames = np.ascontiguousarray(frames, np.uint8)
+    frames = frames.reshape(1 if frames.ndim == 1 else frames.shape[0], -1)
+    if isinstance(layout, str):
+        layout = yuv420_layout(layout, w, h)[0]
+    return frames, layout, frames.shape[1]
+
+
 def sift_config(**over):
     c = SiftConfig()
     lib().slideo_sift_config_default(C.byref(c))
@@ -78,6 +126,8 @@ EXPORTS = [
     "slideo_group_member", "slideo_group_set_progress", "slideo_group_use_sift", "slideo_group_add_pages_bgr8",
     "slideo_group_finalize_pages", "slideo_group_page_count", "slideo_group_descriptor_count", "slideo_group_match_frames_bgr8",
     "slideo_group_last_frame_candidates", "slideo_group_changed_mask_bgr8", "slideo_group_match_kept_frames",
+    "slideo_yuv420_layout_packed", "slideo_match_frames_yuv420", "slideo_match_frames_yuv420_dev", "slideo_match_frames_submit_yuv420_dev",
+    "slideo_changed_mask_yuv420", "slideo_yuv420_to_bgr8", "slideo_group_match_frames_yuv420", "slideo_group_changed_mask_yuv420",
 ]
 
 _lib = None
@@ -301,6 +351,51 @@ class Matcher:
         self._check(lib().slideo_changed_mask_bgr8(self._h, n, _p(frames), w, h, w * 3, C.c_int64(w * h * 3),
                                                    _p(prev_small), _p(last), _p(changed), _p(sims)))
         return changed.astype(bool), sims, last
+
+    # ---- YUV 4:2:0 frames (include/slideo_amd.h "YUV 4:2:0 frames") ---------------------------
+    # frames: uint8 [n, frame_bytes] in host memory; layout: a Yuv420Layout or a format name (its packed layout)
+    def match_frames_yuv420(self, frames, w, h, layout="nv12"):
+        frames, layout, fs = _yuv_frames(frames, w, h, layout)
+        out = np.zeros(frames.shape[0], VERDICT_DTYPE)
+        self._check(lib().slideo_match_frames_yuv420(self._h, frames.shape[0], _p(frames), w, h, C.byref(layout), C.c_int64(fs), _p(out)))
+        return out
+
+    def match_frames_yuv420_dev(self, dev_ptr, n, w, h, layout, frame_stride, stream=0):
+        if isinstance(layout, str):
+            layout = yuv420_layout(layout, w, h)[0]
+        out = np.zeros(n, VERDICT_DTYPE)
+        self._check(lib().slideo_match_frames_yuv420_dev(self._h, n, C.c_void_p(dev_ptr), w, h, C.byref(layout), C.c_int64(frame_stride),
+                                                         _p(out), C.c_void_p(stream)))
+        return out
+
+    def submit_yuv420_dev(self, dev_ptr, n, w, h, layout, frame_stride, stream=0):
+        """As submit_dev; collect() collects it."""
+        if isinstance(layout, str):
+            layout = yuv420_layout(layout, w, h)[0]
+        t = C.c_int64()
+        self._check(lib().slideo_match_frames_submit_yuv420_dev(self._h, n, C.c_void_p(dev_ptr), w, h, C.byref(layout),
+                                                                C.c_int64(frame_stride), C.c_void_p(stream), C.byref(t)))
+        return (t.value, n)
+
+    def changed_mask_yuv420(self, frames, w, h, layout="nv12", prev_small=None):
+        frames, layout, fs = _yuv_frames(frames, w, h, layout)
+        n = frames.shape[0]
+        changed = np.zeros(n, np.uint8)
+        sims = np.zeros(n, np.float32)
+        sw, sh = small_size(w, h, self.cfg.small_area)
+        last = np.zeros((sh, sw, 3), np.uint8)
+        if prev_small is not None:
+            prev_small = np.ascontiguousarray(prev_small, np.uint8)
+        self._check(lib().slideo_changed_mask_yuv420(self._h, n, _p(frames), w, h, C.byref(layout), C.c_int64(fs), _p(prev_small), _p(last),
+                                                     _p(changed), _p(sims)))
+        return changed.astype(bool), sims, last
+
+    def yuv420_to_bgr(self, frame, w, h, layout="nv12"):
+        """The BGR image (h, w, 3) the library makes of one 4:2:0 frame (the conversion tap)."""
+        frame, layout, _ = _yuv_frames(frame, w, h, layout)
+        out = np.empty((h, w, 3), np.uint8)
+        self._check(lib().slideo_yuv420_to_bgr8(self._h, _p(frame), w, h, C.byref(layout), _p(out), C.c_int64(out.size)))
+        return out
 
     # ---- SIFT (north-star extension, csrc/sift.hip.h) ---------------------------------------
     def sift(self, bgr, scfg=None, cap=20000):
@@ -542,6 +637,25 @@ class Group:
             prev_small = np.ascontiguousarray(prev_small, np.uint8)
         self._check(lib().slideo_group_changed_mask_bgr8(self._h, n, _p(frames), w, h, w * 3, C.c_int64(w * h * 3),
                                                          _p(prev_small), _p(last), _p(changed), _p(sims)))
+        return changed.astype(bool), sims, last
+
+    def match_frames_yuv420(self, frames, w, h, layout="nv12"):
+        frames, layout, fs = _yuv_frames(frames, w, h, layout)
+        out = np.zeros(frames.shape[0], VERDICT_DTYPE)
+        self._check(lib().slideo_group_match_frames_yuv420(self._h, frames.shape[0], _p(frames), w, h, C.byref(layout), C.c_int64(fs), _p(out)))
+        return out
+
+    def changed_mask_yuv420(self, frames, w, h, layout="nv12", prev_small=None):
+        frames, layout, fs = _yuv_frames(frames, w, h, layout)
+        n = frames.shape[0]
+        changed = np.zeros(n, np.uint8)
+        sims = np.zeros(n, np.float32)
+        sw, sh = small_size(w, h, self.cfg.small_area)
+        last = np.zeros((sh, sw, 3), np.uint8)
+        if prev_small is not None:
+            prev_small = np.ascontiguousarray(prev_small, np.uint8)
+        self._check(lib().slideo_group_changed_mask_yuv420(self._h, n, _p(frames), w, h, C.byref(layout), C.c_int64(fs), _p(prev_small),
+                                                           _p(last), _p(changed), _p(sims)))
         return changed.astype(bool), sims, last
 
     def match_kept_frames(self, sel):

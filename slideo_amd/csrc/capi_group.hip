@@ -103,6 +103,61 @@ void begin_progress(slideo_group* g, uint64_t total, const char* msg_override) {
     for (auto& t : g->tramps) t.last = 0;
 }
 
+// slideo_group_match_frames_bgr8 / _yuv420 (yuv != null: each member converts its shard, stride_bytes is ignored)
+void group_match_impl(slideo_group* g, int32_t n_frames, const uint8_t* frames, int32_t width, int32_t height, int32_t stride_bytes,
+                      int64_t frame_stride_bytes, const slideo_yuv420_layout* yuv, slideo_verdict* verdicts_out) {
+    if (n_frames < 0 || (n_frames > 0 && (!frames || !verdicts_out))) fail(SLIDEO_ERR_INVALID_ARG, "null frames/verdicts");
+    const int N = (int)g->members.size();
+    begin_progress(g, (uint64_t)n_frames, nullptr);
+    g->match_lo.assign((size_t)N + 1, 0);
+    for (int r = 0; r < N; ++r) { int lo, hi; shard_range(n_frames, r, N, lo, hi); g->match_lo[r] = lo; g->match_lo[r + 1] = hi; }
+    g->kept_valid = false;
+    for_each_member(g, [&](int r) {
+        const int lo = g->match_lo[r], hi = g->match_lo[r + 1];
+        // (an empty shard still runs the call's checks: every member reports a matcher that was never finalized, say)
+        match_frames_impl(g->members[r], hi - lo, frames + (int64_t)lo * frame_stride_bytes, false, width, height, stride_bytes, frame_stride_bytes,
+                          verdicts_out + lo, nullptr, yuv);
+    });
+}
+
+// slideo_group_changed_mask_bgr8 / _yuv420 (yuv != null: every member's kept frames are the BGR images of its block)
+void group_mask_impl(slideo_group* g, int32_t n_frames, const uint8_t* frames, int32_t width, int32_t height, int32_t stride_bytes,
+                     int64_t frame_stride_bytes, const slideo_yuv420_layout* yuv, const uint8_t* prev_small, uint8_t* last_small_out,
+                     uint8_t* changed_out, float* similarity_out) {
+    if (n_frames < 0 || (n_frames > 0 && (!frames || !changed_out))) fail(SLIDEO_ERR_INVALID_ARG, "null frames/changed");
+    g->kept_valid = false;
+    if (n_frames == 0) return;
+    const int N = (int)g->members.size();
+    // MarkSimilarIter compares every sampled frame with the one before it (video_capture.rs:86-98): a shard reads ONE frame
+    // before its block (the halo; slideo_amd/distributed.py halo_range) and drops that frame's own flag.
+    g->kept.assign((size_t)N, slideo_group::KeptShard{});
+    int last_r = 0;
+    for (int r = 0; r < N; ++r) {
+        int lo, hi;
+        shard_range(n_frames, r, N, lo, hi);
+        g->kept[r] = slideo_group::KeptShard{(lo > 0 && hi > lo) ? lo - 1 : lo, lo, hi};
+        if (hi > lo) last_r = r;
+    }
+    for_each_member(g, [&](int r) {
+        const slideo_group::KeptShard k = g->kept[r];
+        if (k.hi <= k.lo) return;
+        const int cnt = k.hi - k.read_lo, halo = k.lo - k.read_lo;
+        std::vector<uint8_t> ch((size_t)cnt);
+        std::vector<float> sim((size_t)cnt);
+        slideo_matcher* m = g->members[r];
+        const uint8_t* src = frames + (int64_t)k.read_lo * frame_stride_bytes;
+        const uint8_t* prev = r == 0 ? prev_small : nullptr;
+        uint8_t* last = r == last_r ? last_small_out : nullptr;
+        check_member_call(m, yuv ? slideo_changed_mask_yuv420(m, cnt, src, width, height, yuv, frame_stride_bytes, prev, last, ch.data(), sim.data())
+                                 : slideo_changed_mask_bgr8(m, cnt, src, width, height, stride_bytes, frame_stride_bytes, prev, last, ch.data(), sim.data()));
+        for (int i = halo; i < cnt; ++i) {
+            changed_out[k.read_lo + i] = ch[i];
+            if (similarity_out) similarity_out[k.read_lo + i] = sim[i];
+        }
+    });
+    g->kept_valid = true;
+}
+
 }  // namespace
 
 #define GROUP_TRY try {
@@ -238,18 +293,16 @@ int32_t slideo_group_match_frames_bgr8(slideo_group* g, int32_t n_frames, const 
                                        int32_t stride_bytes, int64_t frame_stride_bytes, slideo_verdict* verdicts_out) {
     if (!g) return SLIDEO_ERR_INVALID_ARG;
     GROUP_TRY
-    if (n_frames < 0 || (n_frames > 0 && (!frames || !verdicts_out))) fail(SLIDEO_ERR_INVALID_ARG, "null frames/verdicts");
-    const int N = (int)g->members.size();
-    begin_progress(g, (uint64_t)n_frames, nullptr);
-    g->match_lo.assign((size_t)N + 1, 0);
-    for (int r = 0; r < N; ++r) { int lo, hi; shard_range(n_frames, r, N, lo, hi); g->match_lo[r] = lo; g->match_lo[r + 1] = hi; }
-    g->kept_valid = false;
-    for_each_member(g, [&](int r) {
-        const int lo = g->match_lo[r], hi = g->match_lo[r + 1];
-        // (an empty shard still runs the call's checks: every member reports a matcher that was never finalized, say)
-        match_frames_impl(g->members[r], hi - lo, frames + (int64_t)lo * frame_stride_bytes, false, width, height, stride_bytes, frame_stride_bytes,
-                          verdicts_out + lo, nullptr);
-    });
+    group_match_impl(g, n_frames, frames, width, height, stride_bytes, frame_stride_bytes, nullptr, verdicts_out);
+    GROUP_CATCH(g)
+}
+
+int32_t slideo_group_match_frames_yuv420(slideo_group* g, int32_t n_frames, const uint8_t* frames, int32_t width, int32_t height,
+                                         const slideo_yuv420_layout* layout, int64_t frame_stride_bytes, slideo_verdict* verdicts_out) {
+    if (!g) return SLIDEO_ERR_INVALID_ARG;
+    GROUP_TRY
+    if (!layout) fail(SLIDEO_ERR_INVALID_ARG, "null yuv420 layout");
+    group_match_impl(g, n_frames, frames, width, height, 0, frame_stride_bytes, layout, verdicts_out);
     GROUP_CATCH(g)
 }
 
@@ -266,35 +319,19 @@ int32_t slideo_group_changed_mask_bgr8(slideo_group* g, int32_t n_frames, const 
                                        uint8_t* last_small_out, uint8_t* changed_out, float* similarity_out) {
     if (!g) return SLIDEO_ERR_INVALID_ARG;
     GROUP_TRY
-    if (n_frames < 0 || (n_frames > 0 && (!frames || !changed_out))) fail(SLIDEO_ERR_INVALID_ARG, "null frames/changed");
-    g->kept_valid = false;
-    if (n_frames == 0) return SLIDEO_OK;
-    const int N = (int)g->members.size();
-    // MarkSimilarIter compares every sampled frame with the one before it (video_capture.rs:86-98): a shard reads ONE frame
-    // before its block (the halo; slideo_amd/distributed.py halo_range) and drops that frame's own flag.
-    g->kept.assign((size_t)N, slideo_group::KeptShard{});
-    int last_r = 0;
-    for (int r = 0; r < N; ++r) {
-        int lo, hi;
-        shard_range(n_frames, r, N, lo, hi);
-        g->kept[r] = slideo_group::KeptShard{(lo > 0 && hi > lo) ? lo - 1 : lo, lo, hi};
-        if (hi > lo) last_r = r;
-    }
-    for_each_member(g, [&](int r) {
-        const slideo_group::KeptShard k = g->kept[r];
-        if (k.hi <= k.lo) return;
-        const int cnt = k.hi - k.read_lo, halo = k.lo - k.read_lo;
-        std::vector<uint8_t> ch((size_t)cnt);
-        std::vector<float> sim((size_t)cnt);
-        check_member_call(g->members[r], slideo_changed_mask_bgr8(g->members[r], cnt, frames + (int64_t)k.read_lo * frame_stride_bytes, width, height, stride_bytes,
-                                                                   frame_stride_bytes, r == 0 ? prev_small : nullptr,
-                                                                   r == last_r ? last_small_out : nullptr, ch.data(), sim.data()));
-        for (int i = halo; i < cnt; ++i) {
-            changed_out[k.read_lo + i] = ch[i];
-            if (similarity_out) similarity_out[k.read_lo + i] = sim[i];
-        }
-    });
-    g->kept_valid = true;
+    group_mask_impl(g, n_frames, frames, width, height, stride_bytes, frame_stride_bytes, nullptr, prev_small, last_small_out, changed_out,
+                    similarity_out);
+    GROUP_CATCH(g)
+}
+
+int32_t slideo_group_changed_mask_yuv420(slideo_group* g, int32_t n_frames, const uint8_t* frames, int32_t width, int32_t height,
+                                         const slideo_yuv420_layout* layout, int64_t frame_stride_bytes, const uint8_t* prev_small,
+                                         uint8_t* last_small_out, uint8_t* changed_out, float* similarity_out) {
+    if (!g) return SLIDEO_ERR_INVALID_ARG;
+    GROUP_TRY
+    if (!layout) fail(SLIDEO_ERR_INVALID_ARG, "null yuv420 layout");
+    group_mask_impl(g, n_frames, frames, width, height, 0, frame_stride_bytes, layout, prev_small, last_small_out, changed_out,
+                    similarity_out);
     GROUP_CATCH(g)
 }
 

@@ -56,8 +56,9 @@ void upload_area(slideo_matcher* m) {
 }
 
 // max frames of size (w,h) per unit under the workspace budget (the slots share it)
-int sub_batch_for(slideo_matcher* m, const PyrGeom& g, int n) {
+int sub_batch_for(slideo_matcher* m, const PyrGeom& g, int n, bool yuv) {
     size_t per = (size_t)g.frame_bytes * (blur_is_f32(m) ? 2 : 1) + (size_t)g.cand_per_frame * 4 + (size_t)g.nlevels * 258 * 4 + (size_t)g.w * g.h * 3;
+    if (yuv) per += (size_t)g.w * g.h * 3 / 2;          // the 4:2:0 staging in front of the BGR image (BGR calls keep their unit sizes)
     // downstream of ORB, sized by the per-frame keypoint capacity: items 8 + keypoint 24 + descriptor 32 B, the key lists
     // (32 x 4 B, times the train-set segments of a small query set: at most ~4 at sizes where the budget matters), and per
     // (keypoint, neighbour) the vote 8 B + point pair 16 B + mask 1 B
@@ -94,6 +95,25 @@ void upload_frames(Slot& S, const uint8_t* host, int n, int h, int stride, int64
     }
 }
 
+// the same for 4:2:0 frames: their bytes into S.d_yuv (frame stride span), then the conversion into S.d_stage on S.st
+void upload_yuv420(Slot& S, const uint8_t* host, int n, int w, int h, const slideo_yuv420_layout& L, int64_t span, int64_t frame_stride,
+                   hipStream_t cs) {
+    S.d_yuv.reserve((size_t)span * n + 16);
+    S.d_stage.reserve((size_t)w * h * 3 * n + 16);
+    hipStream_t st = cs ? cs : S.st;
+    if (frame_stride == span) {
+        HIP_CHECK(hipMemcpyAsync(S.d_yuv.p, host, (size_t)span * n, hipMemcpyHostToDevice, st));
+    } else {
+        for (int i = 0; i < n; ++i)
+            HIP_CHECK(hipMemcpyAsync(S.d_yuv.as<uint8_t>() + (size_t)span * i, host + frame_stride * i, (size_t)span, hipMemcpyHostToDevice, st));
+    }
+    if (cs) {
+        HIP_CHECK(hipEventRecord(S.ev_up, cs));
+        HIP_CHECK(hipStreamWaitEvent(S.st, S.ev_up, 0));
+    }
+    launch_yuv420_to_bgr(S.d_yuv.as<uint8_t>(), span, L, w, h, n, S.d_stage.as<uint8_t>(), S.st);
+}
+
 // page-locked (hipHostMalloc / hipHostRegister) host memory?  Copies from it are truly asynchronous DMA; copies from pageable
 // memory are staged by the runtime inside the call.
 bool host_is_pinned(const void* p) {
@@ -104,6 +124,45 @@ bool host_is_pinned(const void* p) {
 
 void validate_image(int w, int h, int stride) {
     if (w < 1 || h < 1 || stride < w * 3) fail(SLIDEO_ERR_INVALID_ARG, "bad image geometry w=%d h=%d stride=%d", w, h, stride);
+}
+
+int64_t yuv420_validate(int w, int h, const slideo_yuv420_layout* L, int64_t frame_stride) {
+    if (!L) fail(SLIDEO_ERR_INVALID_ARG, "null yuv420 layout");
+    if (w < 1 || h < 1) fail(SLIDEO_ERR_INVALID_ARG, "bad image geometry w=%d h=%d", w, h);
+    if ((w | h) & 1) fail(SLIDEO_ERR_UNSUPPORTED, "yuv420: width and height must be even (%dx%d), as cvtColor requires", w, h);
+    if (w > MAX_DIM || h > MAX_DIM) fail(SLIDEO_ERR_UNSUPPORTED, "image size %dx%d outside 1..%d", w, h, MAX_DIM);
+    if (L->uv_step != 1 && L->uv_step != 2) fail(SLIDEO_ERR_INVALID_ARG, "yuv420 layout: uv_step %d is neither 1 (planar) nor 2 (interleaved)", L->uv_step);
+    if (L->u_offset < 0 || L->v_offset < 0) fail(SLIDEO_ERR_INVALID_ARG, "yuv420 layout: negative plane offset");
+    if (L->y_stride < w) fail(SLIDEO_ERR_INVALID_ARG, "yuv420 layout: y_stride %d < width %d", L->y_stride, w);
+    const int cw = w / 2, ch = h / 2;
+    if ((int64_t)L->uv_stride < (int64_t)cw * L->uv_step)
+        fail(SLIDEO_ERR_INVALID_ARG, "yuv420 layout: uv_stride %d < %d (width/2 chroma samples of %d bytes' step)", L->uv_stride, cw * L->uv_step, L->uv_step);
+    if (L->uv_step == 2 && std::llabs(L->u_offset - L->v_offset) != 1)
+        fail(SLIDEO_ERR_INVALID_ARG, "yuv420 layout: interleaved chroma needs |v_offset - u_offset| == 1 (got %lld, %lld)",
+             (long long)L->u_offset, (long long)L->v_offset);
+    // planes as byte ranges [lo, hi): Y, then U and V (one range when interleaved)
+    const int64_t y_hi = (int64_t)(h - 1) * L->y_stride + w;
+    const int64_t c_rows = (int64_t)(ch - 1) * L->uv_stride;
+    struct R { int64_t lo, hi; const char* name; };
+    std::vector<R> pl{{0, y_hi, "Y"}};
+    if (L->uv_step == 2) {
+        const int64_t lo = std::min(L->u_offset, L->v_offset);
+        pl.push_back({lo, lo + c_rows + 2 * cw, "UV"});
+    } else {
+        pl.push_back({L->u_offset, L->u_offset + c_rows + cw, "U"});
+        pl.push_back({L->v_offset, L->v_offset + c_rows + cw, "V"});
+    }
+    int64_t span = 0;
+    for (size_t i = 0; i < pl.size(); ++i) {
+        span = std::max(span, pl[i].hi);
+        for (size_t j = 0; j < i; ++j)
+            if (pl[i].lo < pl[j].hi && pl[j].lo < pl[i].hi)
+                fail(SLIDEO_ERR_INVALID_ARG, "yuv420 layout: the %s plane [%lld, %lld) overlaps the %s plane [%lld, %lld)", pl[i].name,
+                     (long long)pl[i].lo, (long long)pl[i].hi, pl[j].name, (long long)pl[j].lo, (long long)pl[j].hi);
+    }
+    if (frame_stride >= 0 && frame_stride < span)
+        fail(SLIDEO_ERR_INVALID_ARG, "yuv420: frame_stride %lld does not cover the frame's furthest byte (%lld)", (long long)frame_stride, (long long)span);
+    return span;
 }
 
 // ---- one unit of the per-frame hot path: enqueue everything, then collect ---------------
@@ -240,8 +299,16 @@ void check_match_args(slideo_matcher* m, int n, const void* frames, const void* 
 
 // Synchronous matching of n frames: cut into units and run them through the slots as a pipeline.
 void match_frames_impl(slideo_matcher* m, int n, const uint8_t* frames, bool on_device, int w, int h, int stride,
-                       int64_t frame_stride, slideo_verdict* out, hipStream_t user_stream) {
-    check_match_args(m, n, frames, out, w, h, stride, frame_stride);
+                       int64_t frame_stride, slideo_verdict* out, hipStream_t user_stream, const slideo_yuv420_layout* yuv) {
+    int64_t span = 0;
+    if (yuv) {
+        span = yuv420_validate(w, h, yuv, frame_stride);
+        stride = w * 3;                                            // the BGR image the units read (d_stage)
+        check_match_args(m, n, frames, out, w, h, stride, (int64_t)h * stride);
+        m->kept.valid = false;                                     // (slot 0's d_stage receives BGR)
+    } else {
+        check_match_args(m, n, frames, out, w, h, stride, frame_stride);
+    }
     HIP_CHECK(hipSetDevice(m->device));
     require_idle(m);
     m->last_fcs.clear();
@@ -249,7 +316,7 @@ void match_frames_impl(slideo_matcher* m, int n, const uint8_t* frames, bool on_
     GeomEntry& ge = geom_for(m, w, h);
     area_class_for(m, w, h);
     upload_area(m);
-    int unit = sub_batch_for(m, ge.g, n);
+    int unit = sub_batch_for(m, ge.g, n, yuv != nullptr);
     if (n >= 128 && unit >= (n + 1) / 2) unit = (n + 1) / 2;      // two halves overlap ORB with kNN / verify
     // Host frames: the call is bound by the H2D copies (6.2 MB per 1080p frame: 256 frames = 29 ms at 55 GB/s against 14 ms of
     // kernels), so what matters is that the copy engines never wait: short units, each copied on its slot's stream while the
@@ -278,7 +345,17 @@ void match_frames_impl(slideo_matcher* m, int n, const uint8_t* frames, bool on_
             m->next_slot = (m->next_slot + 1) % NSLOTS;
             const uint8_t* dev;
             int64_t fs = frame_stride;
-            if (on_device) dev = frames + (int64_t)i * frame_stride;
+            if (yuv) {
+                // 4:2:0 frames: converted on the slot's stream into its d_stage, which lives until the unit is collected (verify's
+                // re-projection reads the frames); host sources are uploaded first, exactly as BGR ones are
+                if (on_device) {
+                    S.d_stage.reserve((size_t)w * h * 3 * cnt + 16);
+                    launch_yuv420_to_bgr(frames + (int64_t)i * frame_stride, frame_stride, *yuv, w, h, cnt, S.d_stage.as<uint8_t>(), S.st);
+                } else {
+                    upload_yuv420(S, frames + (int64_t)i * frame_stride, cnt, w, h, *yuv, span, frame_stride, src_pinned ? m->copy_st : nullptr);
+                }
+                dev = S.d_stage.as<uint8_t>(); fs = (int64_t)h * stride;
+            } else if (on_device) dev = frames + (int64_t)i * frame_stride;
             else {
                 // pinned source: asynchronous copies, kept in submission order on the one copy stream (see copy_st); pageable
                 // source: the runtime stages the copy inside the call, on the unit's own stream (measured: 32.7 ms per 256 frames
@@ -716,20 +793,28 @@ int32_t slideo_match_frames_bgr8_dev(slideo_matcher* m, int32_t n_frames, const 
     API_CATCH(m)
 }
 
-int32_t slideo_match_frames_submit_dev(slideo_matcher* m, int32_t n_frames, const uint8_t* frames_dev, int32_t width, int32_t height,
-                                       int32_t stride_bytes, int64_t frame_stride_bytes, void* hip_stream, int64_t* ticket_out) {
-    if (!m) return SLIDEO_ERR_INVALID_ARG;
-    API_TRY
+}  // extern "C"
+
+namespace {
+
+// slideo_match_frames_submit[_yuv420]_dev; yuv != null: the unit's frames are converted into the slot's d_stage first
+void submit_impl(slideo_matcher* m, int32_t n_frames, const uint8_t* frames_dev, int32_t width, int32_t height, int32_t stride_bytes,
+                 int64_t frame_stride_bytes, const slideo_yuv420_layout* yuv, void* hip_stream, int64_t* ticket_out) {
     if (!ticket_out) fail(SLIDEO_ERR_INVALID_ARG, "null ticket_out");
-    check_match_args(m, n_frames, frames_dev, ticket_out, width, height, stride_bytes, frame_stride_bytes);
+    if (yuv) {
+        yuv420_validate(width, height, yuv, frame_stride_bytes);
+        check_match_args(m, n_frames, frames_dev, ticket_out, width, height, width * 3, (int64_t)height * width * 3);
+    } else {
+        check_match_args(m, n_frames, frames_dev, ticket_out, width, height, stride_bytes, frame_stride_bytes);
+    }
     if (n_frames < 1) fail(SLIDEO_ERR_INVALID_ARG, "submit needs at least one frame");
     HIP_CHECK(hipSetDevice(m->device));
     Slot& S = m->slots[m->next_slot];
     if (S.busy) fail(SLIDEO_ERR_STATE, "all slots are in flight: collect ticket %lld first", (long long)S.ticket);
     GeomEntry& ge = geom_for(m, width, height);
-    if (n_frames > sub_batch_for(m, ge.g, n_frames))
+    if (n_frames > sub_batch_for(m, ge.g, n_frames, yuv != nullptr))
         fail(SLIDEO_ERR_CAPACITY, "%d frames exceed the per-slot workspace budget (%d); submit smaller units or raise SLIDEO_WS_GB",
-             n_frames, sub_batch_for(m, ge.g, n_frames));
+             n_frames, sub_batch_for(m, ge.g, n_frames, yuv != nullptr));
     area_class_for(m, width, height);
     upload_area(m);
     { bool any = false; for (const Slot& c : m->slots) any |= c.busy; if (!any) m->last_fcs.clear(); }
@@ -737,11 +822,75 @@ int32_t slideo_match_frames_submit_dev(slideo_matcher* m, int32_t n_frames, cons
         HIP_CHECK(hipEventRecord(S.ev_in, reinterpret_cast<hipStream_t>(hip_stream)));
         HIP_CHECK(hipStreamWaitEvent(S.st, S.ev_in, 0));
     }
+    if (yuv) {
+        // the BGR image lives in the slot's d_stage until the unit is collected (verify's re-projection reads it then)
+        m->kept.valid = false;
+        S.d_stage.reserve((size_t)width * height * 3 * n_frames + 16);
+        launch_yuv420_to_bgr(frames_dev, frame_stride_bytes, *yuv, width, height, n_frames, S.d_stage.as<uint8_t>(), S.st);
+        frames_dev = S.d_stage.as<uint8_t>(); stride_bytes = width * 3; frame_stride_bytes = (int64_t)height * width * 3;
+    }
     unit_submit(m, S, frames_dev, n_frames, width, height, stride_bytes, frame_stride_bytes);
     S.ticket = m->next_ticket++;
     *ticket_out = S.ticket;
     m->next_slot = (m->next_slot + 1) % NSLOTS;
     for (Slot& O : m->slots) if (&O != &S && !O.busy) O.match_capacity(S);  // the next units find their workspace sized
+}
+
+// slideo_changed_mask_bgr8 / _yuv420 (yuv != null: converted into slot 0's d_stage at stride 3w, which m->kept then describes)
+void changed_mask_impl(slideo_matcher* m, int32_t n_frames, const uint8_t* frames, int32_t width, int32_t height, int32_t stride_bytes,
+                       int64_t frame_stride_bytes, const slideo_yuv420_layout* yuv, const uint8_t* prev_small, uint8_t* last_small_out,
+                       uint8_t* changed_out, float* similarity_out) {
+    if (n_frames < 0 || (n_frames > 0 && (!frames || !changed_out))) fail(SLIDEO_ERR_INVALID_ARG, "null frames/changed");
+    const int64_t span = yuv ? yuv420_validate(width, height, yuv, frame_stride_bytes) : 0;
+    if (yuv) stride_bytes = width * 3;
+    validate_image(width, height, stride_bytes);
+    if (n_frames == 0) return;
+    HIP_CHECK(hipSetDevice(m->device));
+    require_idle(m);
+    Slot& S = m->slots[0];
+    hipStream_t st = S.st;
+    int sw = 0, sh = 0;
+    const size_t fb = (size_t)height * stride_bytes;
+    stage_for_upload(m, fb * (size_t)n_frames);
+    if (yuv) upload_yuv420(S, frames, n_frames, width, height, *yuv, span, frame_stride_bytes, nullptr);
+    else upload_frames(S, frames, n_frames, height, stride_bytes, frame_stride_bytes);
+    m->kept = slideo_matcher::Kept{true, n_frames, width, height, stride_bytes};   // stays in slot 0's staging buffer: slideo_match_kept_frames
+    run_small(m, S.d_stage.as<uint8_t>(), n_frames, width, height, stride_bytes, (int64_t)fb, sw, sh, st);
+    const size_t sb = (size_t)sw * sh * 3;
+    DevBuf& prev = m->d_prev_small;
+    prev.reserve(sb);
+    if (prev_small) HIP_CHECK(hipMemcpyAsync(prev.p, prev_small, sb, hipMemcpyHostToDevice, st));
+    m->d_ssd.reserve((size_t)n_frames * 8);
+    // pair i: (small[i-1], small[i]); pair 0 uses prev
+    if (prev_small) launch_ssd(prev.as<uint8_t>(), 0, m->d_small.as<uint8_t>(), 0, (int64_t)sb, m->d_ssd.as<unsigned long long>(), 1, st);
+    if (n_frames > 1)
+        launch_ssd(m->d_small.as<uint8_t>(), (int64_t)sb, m->d_small.as<uint8_t>() + sb, (int64_t)sb, (int64_t)sb, m->d_ssd.as<unsigned long long>() + 1, n_frames - 1, st);
+    std::vector<unsigned long long> ssd(n_frames, 0);
+    HIP_CHECK(hipMemcpyAsync(ssd.data(), m->d_ssd.p, (size_t)n_frames * 8, hipMemcpyDeviceToHost, st));
+    if (last_small_out)
+        HIP_CHECK(hipMemcpyAsync(last_small_out, m->d_small.as<uint8_t>() + sb * (n_frames - 1), sb, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    for (int i = 0; i < n_frames; ++i) {
+        float sim = 0.0f;   // video_capture.rs:92: the first frame compares as 0.0
+        if (i > 0 || prev_small) {
+            double e = std::sqrt((double)ssd[i]);
+            float max_error = std::sqrt((255.0f * 255.0f * 3.0f) * (float)(sw * sh));
+            sim = 1.0f - (float)e / max_error;
+        }
+        changed_out[i] = sim < m->cfg.changed_similarity ? 1 : 0;
+        if (similarity_out) similarity_out[i] = sim;
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t slideo_match_frames_submit_dev(slideo_matcher* m, int32_t n_frames, const uint8_t* frames_dev, int32_t width, int32_t height,
+                                       int32_t stride_bytes, int64_t frame_stride_bytes, void* hip_stream, int64_t* ticket_out) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    submit_impl(m, n_frames, frames_dev, width, height, stride_bytes, frame_stride_bytes, nullptr, hip_stream, ticket_out);
     API_CATCH(m)
 }
 
@@ -791,43 +940,8 @@ int32_t slideo_changed_mask_bgr8(slideo_matcher* m, int32_t n_frames, const uint
                                  uint8_t* last_small_out, uint8_t* changed_out, float* similarity_out) {
     if (!m) return SLIDEO_ERR_INVALID_ARG;
     API_TRY
-    if (n_frames < 0 || (n_frames > 0 && (!frames || !changed_out))) fail(SLIDEO_ERR_INVALID_ARG, "null frames/changed");
-    validate_image(width, height, stride_bytes);
-    if (n_frames == 0) return SLIDEO_OK;
-    HIP_CHECK(hipSetDevice(m->device));
-    require_idle(m);
-    Slot& S = m->slots[0];
-    hipStream_t st = S.st;
-    int sw = 0, sh = 0;
-    const size_t fb = (size_t)height * stride_bytes;
-    stage_for_upload(m, fb * (size_t)n_frames);
-    upload_frames(S, frames, n_frames, height, stride_bytes, frame_stride_bytes);
-    m->kept = slideo_matcher::Kept{true, n_frames, width, height, stride_bytes};   // stays in slot 0's staging buffer: slideo_match_kept_frames
-    run_small(m, S.d_stage.as<uint8_t>(), n_frames, width, height, stride_bytes, (int64_t)fb, sw, sh, st);
-    const size_t sb = (size_t)sw * sh * 3;
-    DevBuf& prev = m->d_prev_small;
-    prev.reserve(sb);
-    if (prev_small) HIP_CHECK(hipMemcpyAsync(prev.p, prev_small, sb, hipMemcpyHostToDevice, st));
-    m->d_ssd.reserve((size_t)n_frames * 8);
-    // pair i: (small[i-1], small[i]); pair 0 uses prev
-    if (prev_small) launch_ssd(prev.as<uint8_t>(), 0, m->d_small.as<uint8_t>(), 0, (int64_t)sb, m->d_ssd.as<unsigned long long>(), 1, st);
-    if (n_frames > 1)
-        launch_ssd(m->d_small.as<uint8_t>(), (int64_t)sb, m->d_small.as<uint8_t>() + sb, (int64_t)sb, (int64_t)sb, m->d_ssd.as<unsigned long long>() + 1, n_frames - 1, st);
-    std::vector<unsigned long long> ssd(n_frames, 0);
-    HIP_CHECK(hipMemcpyAsync(ssd.data(), m->d_ssd.p, (size_t)n_frames * 8, hipMemcpyDeviceToHost, st));
-    if (last_small_out)
-        HIP_CHECK(hipMemcpyAsync(last_small_out, m->d_small.as<uint8_t>() + sb * (n_frames - 1), sb, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    for (int i = 0; i < n_frames; ++i) {
-        float sim = 0.0f;   // video_capture.rs:92: the first frame compares as 0.0
-        if (i > 0 || prev_small) {
-            double e = std::sqrt((double)ssd[i]);
-            float max_error = std::sqrt((255.0f * 255.0f * 3.0f) * (float)(sw * sh));
-            sim = 1.0f - (float)e / max_error;
-        }
-        changed_out[i] = sim < m->cfg.changed_similarity ? 1 : 0;
-        if (similarity_out) similarity_out[i] = sim;
-    }
+    changed_mask_impl(m, n_frames, frames, width, height, stride_bytes, frame_stride_bytes, nullptr, prev_small, last_small_out,
+                      changed_out, similarity_out);
     API_CATCH(m)
 }
 
@@ -866,6 +980,68 @@ int32_t slideo_host_register(void* ptr, size_t bytes) {
 int32_t slideo_host_unregister(void* ptr) {
     if (!ptr) return SLIDEO_ERR_INVALID_ARG;
     return hipHostUnregister(ptr) == hipSuccess ? SLIDEO_OK : SLIDEO_ERR_HIP;
+}
+
+// ---- YUV 4:2:0 frames (include/slideo_amd.h "YUV 4:2:0 frames") -------------------------------------------------------------
+
+int32_t slideo_yuv420_layout_packed(int32_t format, int32_t w, int32_t h, slideo_yuv420_layout* out) {
+    if (!out || format < SLIDEO_YUV420_NV12 || format > SLIDEO_YUV420_YV12 || w < 1 || h < 1) return SLIDEO_ERR_INVALID_ARG;
+    if ((w | h) & 1) return SLIDEO_ERR_UNSUPPORTED;
+    const int64_t luma = (int64_t)w * h, chroma = luma / 4;
+    slideo_yuv420_layout L{};
+    L.y_stride = w;
+    if (format == SLIDEO_YUV420_NV12 || format == SLIDEO_YUV420_NV21) {
+        L.uv_stride = w; L.uv_step = 2;
+        L.u_offset = luma + (format == SLIDEO_YUV420_NV21);
+        L.v_offset = luma + (format == SLIDEO_YUV420_NV12);
+    } else {
+        L.uv_stride = w / 2; L.uv_step = 1;
+        L.u_offset = format == SLIDEO_YUV420_I420 ? luma : luma + chroma;
+        L.v_offset = format == SLIDEO_YUV420_I420 ? luma + chroma : luma;
+    }
+    *out = L;
+    return SLIDEO_OK;
+}
+
+int32_t slideo_match_frames_yuv420(slideo_matcher* m, int32_t n_frames, const uint8_t* frames, int32_t width, int32_t height,
+                                   const slideo_yuv420_layout* layout, int64_t frame_stride_bytes, slideo_verdict* verdicts_out) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    if (!layout) fail(SLIDEO_ERR_INVALID_ARG, "null yuv420 layout");
+    match_frames_impl(m, n_frames, frames, false, width, height, 0, frame_stride_bytes, verdicts_out, nullptr, layout);
+    API_CATCH(m)
+}
+
+int32_t slideo_match_frames_yuv420_dev(slideo_matcher* m, int32_t n_frames, const uint8_t* frames_dev, int32_t width, int32_t height,
+                                       const slideo_yuv420_layout* layout, int64_t frame_stride_bytes, slideo_verdict* verdicts_out,
+                                       void* hip_stream) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    if (!layout) fail(SLIDEO_ERR_INVALID_ARG, "null yuv420 layout");
+    match_frames_impl(m, n_frames, frames_dev, true, width, height, 0, frame_stride_bytes, verdicts_out,
+                      reinterpret_cast<hipStream_t>(hip_stream), layout);
+    API_CATCH(m)
+}
+
+int32_t slideo_match_frames_submit_yuv420_dev(slideo_matcher* m, int32_t n_frames, const uint8_t* frames_dev, int32_t width, int32_t height,
+                                              const slideo_yuv420_layout* layout, int64_t frame_stride_bytes, void* hip_stream,
+                                              int64_t* ticket_out) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    if (!layout) fail(SLIDEO_ERR_INVALID_ARG, "null yuv420 layout");
+    submit_impl(m, n_frames, frames_dev, width, height, 0, frame_stride_bytes, layout, hip_stream, ticket_out);
+    API_CATCH(m)
+}
+
+int32_t slideo_changed_mask_yuv420(slideo_matcher* m, int32_t n_frames, const uint8_t* frames, int32_t width, int32_t height,
+                                   const slideo_yuv420_layout* layout, int64_t frame_stride_bytes, const uint8_t* prev_small,
+                                   uint8_t* last_small_out, uint8_t* changed_out, float* similarity_out) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    if (!layout) fail(SLIDEO_ERR_INVALID_ARG, "null yuv420 layout");
+    changed_mask_impl(m, n_frames, frames, width, height, 0, frame_stride_bytes, layout, prev_small, last_small_out, changed_out,
+                      similarity_out);
+    API_CATCH(m)
 }
 
 }  // extern "C"

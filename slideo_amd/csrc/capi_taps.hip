@@ -80,4 +80,22 @@ int32_t slideo_small_image_bgr8(slideo_matcher* m, const uint8_t* bgr, int32_t w
     API_CATCH(m)
 }
 
+int32_t slideo_yuv420_to_bgr8(slideo_matcher* m, const uint8_t* frame, int32_t width, int32_t height, const slideo_yuv420_layout* layout,
+                              uint8_t* bgr_out, int64_t out_capacity) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    if (!frame || !bgr_out) fail(SLIDEO_ERR_INVALID_ARG, "null frame/bgr_out");
+    const int64_t span = yuv420_validate(width, height, layout, -1);
+    const size_t fb = (size_t)width * height * 3;
+    if ((int64_t)fb > out_capacity) fail(SLIDEO_ERR_CAPACITY, "the BGR image needs %zu bytes", fb);
+    HIP_CHECK(hipSetDevice(m->device));
+    require_idle(m);
+    Slot& S = m->slots[0];
+    stage_for_upload(m, fb);
+    upload_yuv420(S, frame, 1, width, height, *layout, span, span, nullptr);
+    HIP_CHECK(hipMemcpyAsync(bgr_out, S.d_stage.p, fb, hipMemcpyDeviceToHost, S.st));
+    HIP_CHECK(hipStreamSynchronize(S.st));
+    API_CATCH(m)
+}
+
 }  // extern "C"

@@ -1,7 +1,7 @@
 // runtime.hpp — the host runtime behind include/slideo_amd.h, shared by its translation units.
 //
 //   capi_runtime.hip   handles, page database, slots, unit submit / collect, the match entry points
-//   stage_orb.hip      ORB stage drivers          (kernels: orb.hip.h)
+//   stage_orb.hip      ORB stage drivers          (kernels: orb.hip.h, yuv420.hip.h)
 //   stage_knn.hip      index build + k-NN stage   (kernels: knn.hip.h, knn_tile.hip.h, knn_l2.hip.h, knn_lsh.hip.h)
 //   stage_verify.hip   vote .. verdict, small img (kernels: verify.hip.h, homography.hip.h)
 //   stage_sift.hip     SIFT stage + entry points  (kernels: sift.hip.h)
@@ -72,6 +72,7 @@ struct Slot {
     const uint8_t* u_frames = nullptr; int u_w = 0, u_h = 0, u_stride = 0; int64_t u_fs = 0; bool u_async = false; int u_nt = 0; bool u_shared = false, u_w12 = false;
     DevBuf d_stage, d_pyr, d_blur, d_cand, d_hist, d_candcount, d_flags, d_thr, d_lvlofs, d_kpcount, d_qofs, d_info;
     DevBuf d_items, d_kp, d_desc, d_keys, d_knn_pend, d_votes, d_gpts, d_gmask, d_fcs, d_verdicts, d_pairs, d_blurmask, d_qkeys, d_tail, d_refine;
+    DevBuf d_yuv;              // host YUV 4:2:0 frames of the unit, converted into d_stage (reserved by the first YUV call only)
     PinBuf h_info, h_out;
     OrbOut orb;
     // unit in flight
@@ -201,7 +202,8 @@ int area_class_for(slideo_matcher* m, int w, int h);
 void upload_area(slideo_matcher* m);
 inline bool blur_is_f32(const slideo_matcher* m) { return m->cfg.ocv.blur <= 1; }
 uint32_t kp_cap_for(const slideo_matcher* m, const PyrGeom& g);
-int sub_batch_for(slideo_matcher* m, const PyrGeom& g, int n);
+// yuv: the unit's frames arrive as YUV 4:2:0 (+ 1.5 B per pixel and frame of staging)
+int sub_batch_for(slideo_matcher* m, const PyrGeom& g, int n, bool yuv = false);
 void require_idle(slideo_matcher* m);
 // slot 0's staging buffer with room for `bytes` (taps, page ingest, the changed mask): whatever slideo_changed_mask_bgr8 kept there
 // is gone afterwards
@@ -209,12 +211,20 @@ uint8_t* stage_for_upload(slideo_matcher* m, size_t bytes);
 void upload_frames(Slot& S, const uint8_t* host, int n, int h, int stride, int64_t frame_stride, hipStream_t cs = nullptr);
 bool host_is_pinned(const void* p);
 void validate_image(int w, int h, int stride);
+// the rules of include/slideo_amd.h "YUV 4:2:0 frames"; returns the bytes of one frame (its furthest byte + 1).  frame_stride < 0:
+// a single frame, no stride to check
+int64_t yuv420_validate(int w, int h, const slideo_yuv420_layout* L, int64_t frame_stride);
+// n host YUV frames (span bytes each, frame stride frame_stride) -> BGR8 in S.d_stage (stride 3w, frame stride 3wh), on S.st;
+// `cs` != null: copied on that (copy) stream, S.st waits for it
+void upload_yuv420(Slot& S, const uint8_t* host, int n, int w, int h, const slideo_yuv420_layout& L, int64_t span, int64_t frame_stride,
+                   hipStream_t cs);
 void upload_rng_stream(slideo_matcher* m, uint32_t len);
 void unit_submit(slideo_matcher* m, Slot& S, const uint8_t* frames_dev, int n, int w, int h, int stride, int64_t frame_stride, bool allow_async = true);
 void unit_collect(slideo_matcher* m, Slot& S, slideo_verdict* out_host);
 void check_match_args(slideo_matcher* m, int n, const void* frames, const void* out, int w, int h, int stride, int64_t frame_stride);
+// yuv != null: the frames are YUV 4:2:0 in that layout (stride is ignored), converted unit by unit into the slots' d_stage
 void match_frames_impl(slideo_matcher* m, int n, const uint8_t* frames, bool on_device, int w, int h, int stride, int64_t frame_stride,
-                       slideo_verdict* out, hipStream_t user_stream);
+                       slideo_verdict* out, hipStream_t user_stream, const slideo_yuv420_layout* yuv = nullptr);
 // ProcessedImage::compute over n host pages (mo/lib.rs:92-131) WITHOUT appending them: the analysed pages, in order, into `out`
 void analyse_pages(slideo_matcher* m, int n_pages, const uint8_t* const* data, const int32_t* width, const int32_t* height, const int32_t* stride_bytes,
                    std::vector<HostPage>& out, uint64_t progress_base, uint64_t progress_total);
@@ -234,6 +244,8 @@ void run_orb(slideo_matcher* m, Slot& S, const uint8_t* frames_dev, int n, int w
 void orb_launch_gray(const slideo_matcher* m, const uint8_t* frames_dev, int64_t frame_stride, int stride, uint8_t* gray, int64_t gframe, int w, int h,
                      int pitch, int n, hipStream_t st);
 void orb_launch_scan(const uint32_t* counts, int n, uint32_t* qofs, uint32_t* info, hipStream_t st);
+// n decoded YUV 4:2:0 frames (a layout yuv420_validate accepted, frame stride src_fs) -> BGR8 at dst, stride 3w, frame stride 3wh
+void launch_yuv420_to_bgr(const uint8_t* src, int64_t src_fs, const slideo_yuv420_layout& L, int w, int h, int n, uint8_t* dst, hipStream_t st);
 
 // ---- stage_knn.hip --------------------------------------------------------------------------------
 // FlannMatcher::new (mo/flann.rs:65-71) for the Hamming index: uploads the M packed rows, collapses equal rows, builds the

@@ -1,6 +1,7 @@
-// stage_orb.hip — drivers of the ORB stage (kernels: orb.hip.h).
+// stage_orb.hip — drivers of the ORB stage (kernels: orb.hip.h) and of the YUV 4:2:0 front door in front of it (yuv420.hip.h).
 #include "runtime.hpp"
 #include "orb.hip.h"
+#include "yuv420.hip.h"
 
 using namespace slideo;
 
@@ -47,6 +48,27 @@ void orb_launch_gray(const slideo_matcher* m, const uint8_t* frames_dev, int64_t
     const int aligned4 = ((uintptr_t)frames_dev % 4 == 0) && (stride % 4 == 0) && (frame_stride % 4 == 0);
     gray_kernel<<<dim3(cdiv(cdiv(w, 4), 256), h, n), 256, 0, st>>>(frames_dev, frame_stride, stride, gray, gframe, w, h, pitch, aligned4, gray_coef(m));
     check_launch("gray_kernel");
+}
+
+// n decoded 4:2:0 frames (validated layout, frame stride src_fs) -> BGR8 at dst (stride 3w, frame stride 3wh)
+void launch_yuv420_to_bgr(const uint8_t* src, int64_t src_fs, const slideo_yuv420_layout& L, int w, int h, int n, uint8_t* dst, hipStream_t st) {
+    Yuv420Args a{};
+    a.src = src; a.src_frame_stride = src_fs;
+    a.interleaved = L.uv_step == 2;
+    a.v_first = a.interleaved && L.v_offset < L.u_offset;
+    a.c_ofs = a.interleaved ? std::min(L.u_offset, L.v_offset) : L.u_offset;
+    a.v_ofs = L.v_offset;
+    a.y_stride = L.y_stride; a.uv_stride = L.uv_stride;
+    a.dst = dst; a.w = w; a.h = h;
+    // dword luma loads at x % 4 == 0, a dword (interleaved) or u16 (planar) chroma load at x (x / 2), 3 dword stores at 3x
+    const bool luma4 = (uintptr_t)src % 4 == 0 && src_fs % 4 == 0 && L.y_stride % 4 == 0;
+    const bool chroma = a.interleaved ? (a.c_ofs % 4 == 0 && L.uv_stride % 4 == 0)
+                                      : (L.u_offset % 2 == 0 && L.v_offset % 2 == 0 && L.uv_stride % 2 == 0);
+    const bool out4 = (uintptr_t)dst % 4 == 0 && w % 4 == 0;
+    a.fast = luma4 && chroma && out4;
+    dim3 grid(cdiv(cdiv(w, 4), YUV_TX), cdiv(h / 2, YUV_TY), n);
+    yuv420_to_bgr_kernel<<<grid, dim3(YUV_TX, YUV_TY), 0, st>>>(a);
+    check_launch("yuv420_to_bgr_kernel");
 }
 
 void orb_launch_scan(const uint32_t* counts, int n, uint32_t* qofs, uint32_t* info, hipStream_t st) {

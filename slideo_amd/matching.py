@@ -88,6 +88,54 @@ class RawVideo:
         return np.frombuffer(buf, np.uint8).reshape(self.height, self.width, 3)
 
 
+class RawVideoYuv420:
+    """The same container for decoded YUV 4:2:0 frames, as a VCN or FFmpeg decoder hands them out (NV12 or I420, tightly packed).
+
+    Layout: b'SLVY' u32 width u32 height f64 fps u64 n_frames u32 format (0 NV12, 2 I420: slideo_yuv420_layout_packed), then
+    n_frames * w*h*3/2 bytes.  read() returns a frame's bytes (1-D); the task hands them to the *_yuv420 calls unconverted.
+    """
+    MAGIC = b"SLVY"
+    HDR = struct.Struct("<4sIIdQI")
+    FORMATS = {0: "nv12", 2: "i420"}
+
+    def __init__(self, path):
+        self.path = path
+        with open(path, "rb") as f:
+            magic, self.width, self.height, self.fps, self.n_frames, fmt = self.HDR.unpack(f.read(self.HDR.size))
+        if magic != self.MAGIC or fmt not in self.FORMATS:
+            raise ValueError("not a raw 4:2:0 frame container: %s" % path)
+        self.yuv420_format = self.FORMATS[fmt]
+        self._frame_bytes = self.width * self.height * 3 // 2
+
+    @staticmethod
+    def write(path, frames, width, height, fps, fmt="nv12"):
+        """frames: uint8 [n, w*h*3/2] packed `fmt` frames."""
+        code = {v: k for k, v in RawVideoYuv420.FORMATS.items()}[fmt]
+        frames = np.ascontiguousarray(frames, np.uint8).reshape(-1, width * height * 3 // 2)
+        with open(path, "wb") as f:
+            f.write(RawVideoYuv420.HDR.pack(RawVideoYuv420.MAGIC, width, height, float(fps), frames.shape[0], code))
+            f.write(frames.tobytes())
+
+    def total_frames(self):
+        return float(self.n_frames)
+
+    def total_time(self):
+        return self.n_frames / self.fps
+
+    def read(self, idx):
+        with open(self.path, "rb") as f:
+            f.seek(self.HDR.size + idx * self._frame_bytes)
+            buf = f.read(self._frame_bytes)
+        return np.frombuffer(buf, np.uint8)
+
+
+def open_raw_video(path):
+    """RawVideo or RawVideoYuv420, by the container's magic."""
+    with open(path, "rb") as f:
+        magic = f.read(4)
+    return RawVideoYuv420(path) if magic == RawVideoYuv420.MAGIC else RawVideo(path)
+
+
 def sampled_frames(video, interval_s=5.0):
     """VideoCaptureIter (video_capture.rs:42-57): grab every frame, retrieve when
     frame_idx % floor(fps * interval) < 1; yields (frame, time_s, frame_idx)."""
@@ -120,17 +168,26 @@ class HipVideoMatcherTask:
             self._rep.report(progress[0], frames_to_process, "Processing frames of '%s'..." % name)   # lib.rs:192-203
 
         pend_frames, pend_meta, prev_small = [], [], None
+        yuv = getattr(video, "yuv420_format", None)              # RawVideoYuv420: 'nv12' / 'i420'; RawVideo: None (BGR)
 
         def flush():
             nonlocal prev_small
             if not pend_frames:
                 return
             stack = np.stack(pend_frames)
-            changed, _, prev_small = m.changed_mask(stack, prev_small)               # MarkSimilarIter, video_capture.rs:86-98
+            if yuv:                                                                   # decoded 4:2:0 frames: converted on the GPU
+                changed, _, prev_small = m.changed_mask_yuv420(stack, video.width, video.height, yuv, prev_small)
+            else:
+                changed, _, prev_small = m.changed_mask(stack, prev_small)           # MarkSimilarIter, video_capture.rs:86-98
             idx = np.nonzero(changed)[0]
             if len(idx):
                 # match_images_with_frame, lib.rs:213-214 — on the copy of the frames the mask call left on the device
-                verdicts = m.match_kept_frames(idx) if hasattr(m, "match_kept_frames") else m.match_frames(stack[idx])
+                if hasattr(m, "match_kept_frames"):
+                    verdicts = m.match_kept_frames(idx)
+                elif yuv:
+                    verdicts = m.match_frames_yuv420(stack[idx], video.width, video.height, yuv)
+                else:
+                    verdicts = m.match_frames(stack[idx])
                 for j, v in zip(idx, verdicts):
                     t, fi = pend_meta[j]
                     img = self._images[v["page_idx"]] if v["page_idx"] >= 0 else None
@@ -173,7 +230,7 @@ class HipVideoMatcher:
         self._m, self._images = matcher, images
 
     def match_images_with_video(self, video_path, progress_reporter: ProgressReporter) -> HipVideoMatcherTask:
-        video = RawVideo(video_path) if isinstance(video_path, (str, os.PathLike)) else video_path
+        video = open_raw_video(video_path) if isinstance(video_path, (str, os.PathLike)) else video_path
         frames_to_process = int(video.total_time() / 5.0)                             # lib.rs:148
         progress_reporter.report(0, frames_to_process, "")                            # lib.rs:150
         return HipVideoMatcherTask(self._m, self._images, video, progress_reporter)
