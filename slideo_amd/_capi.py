@@ -197,8 +197,68 @@ def _img3(a):
     return a
 
 
-class Matcher:
+class _FrameCalls:
+    """The host frame calls a Matcher and a Group share: the same C entry points under the symbol prefix _PREFIX ("slideo_" /
+    "slideo_group_"), failures raised through the class's own _check."""
+    _PREFIX = None
+
+    def _call(self, name, *args):
+        self._check(getattr(lib(), self._PREFIX + name)(self._h, *args))
+
+    def match_frames(self, frames):
+        """frames: uint8 [n, h, w, 3] in host memory -> verdict records."""
+        frames = np.ascontiguousarray(frames, np.uint8)
+        n, h, w, c = frames.shape
+        assert c == 3
+        out = np.zeros(n, VERDICT_DTYPE)
+        self._call("match_frames_bgr8", n, _p(frames), w, h, w * 3, C.c_int64(w * h * 3), _p(out))
+        return out
+
+    def last_candidates(self, frame_in_batch):
+        cands = np.zeros(64, CANDIDATE_DTYPE)
+        n = C.c_int32()
+        self._call("last_frame_candidates", frame_in_batch, _p(cands), 64, C.byref(n))
+        return cands[: n.value].copy()
+
+    def changed_mask(self, frames, prev_small=None):
+        frames = np.ascontiguousarray(frames, np.uint8)
+        n, h, w, _ = frames.shape
+        return self._mask("changed_mask_bgr8", n, w, h, prev_small, _p(frames), w, h, w * 3, C.c_int64(w * h * 3))
+
+    # YUV 4:2:0 frames (include/slideo_amd.h "YUV 4:2:0 frames"): uint8 [n, frame_bytes] in host memory; layout: a Yuv420Layout
+    # or a format name (its packed layout)
+    def match_frames_yuv420(self, frames, w, h, layout="nv12"):
+        frames, layout, fs = _yuv_frames(frames, w, h, layout)
+        out = np.zeros(frames.shape[0], VERDICT_DTYPE)
+        self._call("match_frames_yuv420", frames.shape[0], _p(frames), w, h, C.byref(layout), C.c_int64(fs), _p(out))
+        return out
+
+    def changed_mask_yuv420(self, frames, w, h, layout="nv12", prev_small=None):
+        frames, layout, fs = _yuv_frames(frames, w, h, layout)
+        return self._mask("changed_mask_yuv420", frames.shape[0], w, h, prev_small, _p(frames), w, h, C.byref(layout), C.c_int64(fs))
+
+    def _mask(self, name, n, w, h, prev_small, *frame_args):
+        """-> (changed [n] bool, similarity [n] f32, the last frame's small image)"""
+        changed = np.zeros(n, np.uint8)
+        sims = np.zeros(n, np.float32)
+        sw, sh = small_size(w, h, self.cfg.small_area)
+        last = np.zeros((sh, sw, 3), np.uint8)
+        if prev_small is not None:
+            prev_small = np.ascontiguousarray(prev_small, np.uint8)
+        self._call(name, n, *frame_args, _p(prev_small), _p(last), _p(changed), _p(sims))
+        return changed.astype(bool), sims, last
+
+    def match_kept_frames(self, sel):
+        """Verdicts of frames `sel` (indices) of the LAST changed_mask call, from the copy that call left on the device."""
+        sel = np.ascontiguousarray(sel, np.int32)
+        out = np.zeros(len(sel), VERDICT_DTYPE)
+        self._call("match_kept_frames", len(sel), _p(sel), _p(out))
+        return out
+
+
+class Matcher(_FrameCalls):
     """Owns one slideo_matcher handle (page database + workspace on one GPU)."""
+    _PREFIX = "slideo_"
 
     def __init__(self, cfg=None, device=0):
         self.cfg = cfg if cfg is not None else default_config()
@@ -293,17 +353,7 @@ class Matcher:
         self._check(lib().slideo_matcher_get_page_features(self._h, page, _p(kp), _p(desc), n.value, C.byref(n)))
         return kp, desc
 
-    # ---- frames ------------------------------------------------------------------
-    def match_frames(self, frames):
-        """frames: uint8 [n, h, w, 3] in host memory -> verdict records."""
-        frames = np.ascontiguousarray(frames, np.uint8)
-        n, h, w, c = frames.shape
-        assert c == 3
-        out = np.zeros(n, VERDICT_DTYPE)
-        self._check(lib().slideo_match_frames_bgr8(self._h, n, _p(frames), w, h, w * 3,
-                                                   C.c_int64(w * h * 3), _p(out)))
-        return out
-
+    # ---- frames (the host calls: _FrameCalls) --------------------------------------------
     def match_frames_dev(self, dev_ptr, n, w, h, stride=None, frame_stride=None, stream=0):
         """Frames already resident in HBM (raw device pointer)."""
         stride = stride or w * 3
@@ -333,33 +383,7 @@ class Matcher:
         self._check(lib().slideo_match_frames_collect_dev(self._h, C.c_int64(t), _p(out), C.c_void_p(dev_out or None)))
         return out
 
-    def last_candidates(self, frame_in_batch):
-        cands = np.zeros(64, CANDIDATE_DTYPE)
-        n = C.c_int32()
-        self._check(lib().slideo_last_frame_candidates(self._h, frame_in_batch, _p(cands), 64, C.byref(n)))
-        return cands[: n.value].copy()
-
-    def changed_mask(self, frames, prev_small=None):
-        frames = np.ascontiguousarray(frames, np.uint8)
-        n, h, w, _ = frames.shape
-        changed = np.zeros(n, np.uint8)
-        sims = np.zeros(n, np.float32)
-        sw, sh = small_size(w, h, self.cfg.small_area)
-        last = np.zeros((sh, sw, 3), np.uint8)
-        if prev_small is not None:
-            prev_small = np.ascontiguousarray(prev_small, np.uint8)
-        self._check(lib().slideo_changed_mask_bgr8(self._h, n, _p(frames), w, h, w * 3, C.c_int64(w * h * 3),
-                                                   _p(prev_small), _p(last), _p(changed), _p(sims)))
-        return changed.astype(bool), sims, last
-
     # ---- YUV 4:2:0 frames (include/slideo_amd.h "YUV 4:2:0 frames") ---------------------------
-    # frames: uint8 [n, frame_bytes] in host memory; layout: a Yuv420Layout or a format name (its packed layout)
-    def match_frames_yuv420(self, frames, w, h, layout="nv12"):
-        frames, layout, fs = _yuv_frames(frames, w, h, layout)
-        out = np.zeros(frames.shape[0], VERDICT_DTYPE)
-        self._check(lib().slideo_match_frames_yuv420(self._h, frames.shape[0], _p(frames), w, h, C.byref(layout), C.c_int64(fs), _p(out)))
-        return out
-
     def match_frames_yuv420_dev(self, dev_ptr, n, w, h, layout, frame_stride, stream=0):
         if isinstance(layout, str):
             layout = yuv420_layout(layout, w, h)[0]
@@ -376,19 +400,6 @@ class Matcher:
         self._check(lib().slideo_match_frames_submit_yuv420_dev(self._h, n, C.c_void_p(dev_ptr), w, h, C.byref(layout),
                                                                 C.c_int64(frame_stride), C.c_void_p(stream), C.byref(t)))
         return (t.value, n)
-
-    def changed_mask_yuv420(self, frames, w, h, layout="nv12", prev_small=None):
-        frames, layout, fs = _yuv_frames(frames, w, h, layout)
-        n = frames.shape[0]
-        changed = np.zeros(n, np.uint8)
-        sims = np.zeros(n, np.float32)
-        sw, sh = small_size(w, h, self.cfg.small_area)
-        last = np.zeros((sh, sw, 3), np.uint8)
-        if prev_small is not None:
-            prev_small = np.ascontiguousarray(prev_small, np.uint8)
-        self._check(lib().slideo_changed_mask_yuv420(self._h, n, _p(frames), w, h, C.byref(layout), C.c_int64(fs), _p(prev_small), _p(last),
-                                                     _p(changed), _p(sims)))
-        return changed.astype(bool), sims, last
 
     def yuv420_to_bgr(self, frame, w, h, layout="nv12"):
         """The BGR image (h, w, 3) the library makes of one 4:2:0 frame (the conversion tap)."""
@@ -429,13 +440,6 @@ class Matcher:
         self._check(lib().slideo_sift_frames_dev(self._h, C.byref(scfg), n, C.c_void_p(frames_ptr), w, h, w * 3, C.c_int64(w * h * 3),
                                                  C.c_int64(capacity_total), C.c_void_p(kp_ptr), C.c_void_p(desc_ptr), _p(qofs), C.byref(ms)))
         return qofs, float(ms.value)
-
-    def match_kept_frames(self, sel):
-        """Verdicts of frames `sel` (indices) of the LAST changed_mask call, from the copy that call left on the device."""
-        sel = np.ascontiguousarray(sel, np.int32)
-        out = np.zeros(len(sel), VERDICT_DTYPE)
-        self._check(lib().slideo_match_kept_frames(self._h, len(sel), _p(sel), _p(out)))
-        return out
 
     def set_knn_engine(self, engine):
         """'mfma' (default: FP4 matrix cores, wave shape chosen per launch), 'mfma4' / 'mfma2' (the two shapes forced:
@@ -535,10 +539,11 @@ class Matcher:
         return out
 
 
-class Group:
+class Group(_FrameCalls):
     """slideo_group (include/slideo_amd.h, "N-device group"): one matcher per device behind one handle — page DB replicated,
     a call's pages and frames sharded contiguously over the devices, verdicts gathered into one host array.  Results equal
     a single Matcher's bit for bit.  `devices`: HIP ordinals (may repeat); None or empty = every gfx950 device of the node."""
+    _PREFIX = "slideo_group_"
 
     def __init__(self, cfg=None, devices=None):
         self.cfg = cfg if cfg is not None else default_config()
@@ -611,58 +616,6 @@ class Group:
     @property
     def descriptor_count(self):
         return int(lib().slideo_group_descriptor_count(self._h))
-
-    def match_frames(self, frames):
-        frames = np.ascontiguousarray(frames, np.uint8)
-        n, h, w, c = frames.shape
-        assert c == 3
-        out = np.zeros(n, VERDICT_DTYPE)
-        self._check(lib().slideo_group_match_frames_bgr8(self._h, n, _p(frames), w, h, w * 3, C.c_int64(w * h * 3), _p(out)))
-        return out
-
-    def last_candidates(self, frame_in_batch):
-        cands = np.zeros(64, CANDIDATE_DTYPE)
-        n = C.c_int32()
-        self._check(lib().slideo_group_last_frame_candidates(self._h, frame_in_batch, _p(cands), 64, C.byref(n)))
-        return cands[: n.value].copy()
-
-    def changed_mask(self, frames, prev_small=None):
-        frames = np.ascontiguousarray(frames, np.uint8)
-        n, h, w, _ = frames.shape
-        changed = np.zeros(n, np.uint8)
-        sims = np.zeros(n, np.float32)
-        sw, sh = small_size(w, h, self.cfg.small_area)
-        last = np.zeros((sh, sw, 3), np.uint8)
-        if prev_small is not None:
-            prev_small = np.ascontiguousarray(prev_small, np.uint8)
-        self._check(lib().slideo_group_changed_mask_bgr8(self._h, n, _p(frames), w, h, w * 3, C.c_int64(w * h * 3),
-                                                         _p(prev_small), _p(last), _p(changed), _p(sims)))
-        return changed.astype(bool), sims, last
-
-    def match_frames_yuv420(self, frames, w, h, layout="nv12"):
-        frames, layout, fs = _yuv_frames(frames, w, h, layout)
-        out = np.zeros(frames.shape[0], VERDICT_DTYPE)
-        self._check(lib().slideo_group_match_frames_yuv420(self._h, frames.shape[0], _p(frames), w, h, C.byref(layout), C.c_int64(fs), _p(out)))
-        return out
-
-    def changed_mask_yuv420(self, frames, w, h, layout="nv12", prev_small=None):
-        frames, layout, fs = _yuv_frames(frames, w, h, layout)
-        n = frames.shape[0]
-        changed = np.zeros(n, np.uint8)
-        sims = np.zeros(n, np.float32)
-        sw, sh = small_size(w, h, self.cfg.small_area)
-        last = np.zeros((sh, sw, 3), np.uint8)
-        if prev_small is not None:
-            prev_small = np.ascontiguousarray(prev_small, np.uint8)
-        self._check(lib().slideo_group_changed_mask_yuv420(self._h, n, _p(frames), w, h, C.byref(layout), C.c_int64(fs), _p(prev_small),
-                                                           _p(last), _p(changed), _p(sims)))
-        return changed.astype(bool), sims, last
-
-    def match_kept_frames(self, sel):
-        sel = np.ascontiguousarray(sel, np.int32)
-        out = np.zeros(len(sel), VERDICT_DTYPE)
-        self._check(lib().slideo_group_match_kept_frames(self._h, len(sel), _p(sel), _p(out)))
-        return out
 
 
 def device_count():

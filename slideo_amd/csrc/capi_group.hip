@@ -103,10 +103,9 @@ void begin_progress(slideo_group* g, uint64_t total, const char* msg_override) {
     for (auto& t : g->tramps) t.last = 0;
 }
 
-// slideo_group_match_frames_bgr8 / _yuv420 (yuv != null: each member converts its shard, stride_bytes is ignored)
-void group_match_impl(slideo_group* g, int32_t n_frames, const uint8_t* frames, int32_t width, int32_t height, int32_t stride_bytes,
-                      int64_t frame_stride_bytes, const slideo_yuv420_layout* yuv, slideo_verdict* verdicts_out) {
-    if (n_frames < 0 || (n_frames > 0 && (!frames || !verdicts_out))) fail(SLIDEO_ERR_INVALID_ARG, "null frames/verdicts");
+// slideo_group_match_frames_bgr8 / _yuv420
+void group_match_impl(slideo_group* g, int32_t n_frames, const FrameSrc& src, slideo_verdict* verdicts_out) {
+    if (n_frames < 0 || (n_frames > 0 && (!src.p || !verdicts_out))) fail(SLIDEO_ERR_INVALID_ARG, "null frames/verdicts");
     const int N = (int)g->members.size();
     begin_progress(g, (uint64_t)n_frames, nullptr);
     g->match_lo.assign((size_t)N + 1, 0);
@@ -115,16 +114,14 @@ void group_match_impl(slideo_group* g, int32_t n_frames, const uint8_t* frames, 
     for_each_member(g, [&](int r) {
         const int lo = g->match_lo[r], hi = g->match_lo[r + 1];
         // (an empty shard still runs the call's checks: every member reports a matcher that was never finalized, say)
-        match_frames_impl(g->members[r], hi - lo, frames + (int64_t)lo * frame_stride_bytes, false, width, height, stride_bytes, frame_stride_bytes,
-                          verdicts_out + lo, nullptr, yuv);
+        match_frames_impl(g->members[r], hi - lo, src.from(lo), verdicts_out + lo, nullptr);
     });
 }
 
-// slideo_group_changed_mask_bgr8 / _yuv420 (yuv != null: every member's kept frames are the BGR images of its block)
-void group_mask_impl(slideo_group* g, int32_t n_frames, const uint8_t* frames, int32_t width, int32_t height, int32_t stride_bytes,
-                     int64_t frame_stride_bytes, const slideo_yuv420_layout* yuv, const uint8_t* prev_small, uint8_t* last_small_out,
+// slideo_group_changed_mask_bgr8 / _yuv420 (every member's kept frames are the BGR images of its block)
+void group_mask_impl(slideo_group* g, int32_t n_frames, const FrameSrc& src, const uint8_t* prev_small, uint8_t* last_small_out,
                      uint8_t* changed_out, float* similarity_out) {
-    if (n_frames < 0 || (n_frames > 0 && (!frames || !changed_out))) fail(SLIDEO_ERR_INVALID_ARG, "null frames/changed");
+    if (n_frames < 0 || (n_frames > 0 && (!src.p || !changed_out))) fail(SLIDEO_ERR_INVALID_ARG, "null frames/changed");
     g->kept_valid = false;
     if (n_frames == 0) return;
     const int N = (int)g->members.size();
@@ -144,12 +141,8 @@ void group_mask_impl(slideo_group* g, int32_t n_frames, const uint8_t* frames, i
         const int cnt = k.hi - k.read_lo, halo = k.lo - k.read_lo;
         std::vector<uint8_t> ch((size_t)cnt);
         std::vector<float> sim((size_t)cnt);
-        slideo_matcher* m = g->members[r];
-        const uint8_t* src = frames + (int64_t)k.read_lo * frame_stride_bytes;
-        const uint8_t* prev = r == 0 ? prev_small : nullptr;
-        uint8_t* last = r == last_r ? last_small_out : nullptr;
-        check_member_call(m, yuv ? slideo_changed_mask_yuv420(m, cnt, src, width, height, yuv, frame_stride_bytes, prev, last, ch.data(), sim.data())
-                                 : slideo_changed_mask_bgr8(m, cnt, src, width, height, stride_bytes, frame_stride_bytes, prev, last, ch.data(), sim.data()));
+        changed_mask_impl(g->members[r], cnt, src.from(k.read_lo), r == 0 ? prev_small : nullptr, r == last_r ? last_small_out : nullptr,
+                          ch.data(), sim.data());
         for (int i = halo; i < cnt; ++i) {
             changed_out[k.read_lo + i] = ch[i];
             if (similarity_out) similarity_out[k.read_lo + i] = sim[i];
@@ -293,7 +286,7 @@ int32_t slideo_group_match_frames_bgr8(slideo_group* g, int32_t n_frames, const 
                                        int32_t stride_bytes, int64_t frame_stride_bytes, slideo_verdict* verdicts_out) {
     if (!g) return SLIDEO_ERR_INVALID_ARG;
     GROUP_TRY
-    group_match_impl(g, n_frames, frames, width, height, stride_bytes, frame_stride_bytes, nullptr, verdicts_out);
+    group_match_impl(g, n_frames, FrameSrc::bgr8(frames, false, width, height, stride_bytes, frame_stride_bytes), verdicts_out);
     GROUP_CATCH(g)
 }
 
@@ -301,8 +294,7 @@ int32_t slideo_group_match_frames_yuv420(slideo_group* g, int32_t n_frames, cons
                                          const slideo_yuv420_layout* layout, int64_t frame_stride_bytes, slideo_verdict* verdicts_out) {
     if (!g) return SLIDEO_ERR_INVALID_ARG;
     GROUP_TRY
-    if (!layout) fail(SLIDEO_ERR_INVALID_ARG, "null yuv420 layout");
-    group_match_impl(g, n_frames, frames, width, height, 0, frame_stride_bytes, layout, verdicts_out);
+    group_match_impl(g, n_frames, FrameSrc::yuv420(frames, false, width, height, layout, frame_stride_bytes), verdicts_out);
     GROUP_CATCH(g)
 }
 
@@ -319,8 +311,8 @@ int32_t slideo_group_changed_mask_bgr8(slideo_group* g, int32_t n_frames, const 
                                        uint8_t* last_small_out, uint8_t* changed_out, float* similarity_out) {
     if (!g) return SLIDEO_ERR_INVALID_ARG;
     GROUP_TRY
-    group_mask_impl(g, n_frames, frames, width, height, stride_bytes, frame_stride_bytes, nullptr, prev_small, last_small_out, changed_out,
-                    similarity_out);
+    group_mask_impl(g, n_frames, FrameSrc::bgr8(frames, false, width, height, stride_bytes, frame_stride_bytes), prev_small, last_small_out,
+                    changed_out, similarity_out);
     GROUP_CATCH(g)
 }
 
@@ -329,9 +321,8 @@ int32_t slideo_group_changed_mask_yuv420(slideo_group* g, int32_t n_frames, cons
                                          uint8_t* last_small_out, uint8_t* changed_out, float* similarity_out) {
     if (!g) return SLIDEO_ERR_INVALID_ARG;
     GROUP_TRY
-    if (!layout) fail(SLIDEO_ERR_INVALID_ARG, "null yuv420 layout");
-    group_mask_impl(g, n_frames, frames, width, height, 0, frame_stride_bytes, layout, prev_small, last_small_out, changed_out,
-                    similarity_out);
+    group_mask_impl(g, n_frames, FrameSrc::yuv420(frames, false, width, height, layout, frame_stride_bytes), prev_small, last_small_out,
+                    changed_out, similarity_out);
     GROUP_CATCH(g)
 }
 

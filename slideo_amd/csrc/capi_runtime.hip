@@ -72,51 +72,9 @@ void require_idle(slideo_matcher* m) {
     for (const Slot& S : m->slots) if (S.busy) fail(SLIDEO_ERR_STATE, "a submitted unit has not been collected yet");
 }
 
-uint8_t* stage_for_upload(slideo_matcher* m, size_t bytes) {
-    m->kept.valid = false;             // slideo_match_kept_frames reads this buffer: whatever the mask call left there is overwritten
-    m->slots[0].d_stage.reserve(bytes + 16);
-    return m->slots[0].d_stage.as<uint8_t>();
-}
-
-// copies n host frames into S.d_stage with frame stride h*stride; `cs` != null: on that (copy) stream, and S.st waits for it
-void upload_frames(Slot& S, const uint8_t* host, int n, int h, int stride, int64_t frame_stride, hipStream_t cs) {
-    const size_t fb = (size_t)h * stride;
-    S.d_stage.reserve(fb * n + 16);
-    hipStream_t st = cs ? cs : S.st;
-    if ((size_t)frame_stride == fb) {
-        HIP_CHECK(hipMemcpyAsync(S.d_stage.p, host, fb * n, hipMemcpyHostToDevice, st));
-    } else {
-        for (int i = 0; i < n; ++i)
-            HIP_CHECK(hipMemcpyAsync(S.d_stage.as<uint8_t>() + fb * i, host + (size_t)frame_stride * i, fb, hipMemcpyHostToDevice, st));
-    }
-    if (cs) {
-        HIP_CHECK(hipEventRecord(S.ev_up, cs));
-        HIP_CHECK(hipStreamWaitEvent(S.st, S.ev_up, 0));
-    }
-}
-
-// the same for 4:2:0 frames: their bytes into S.d_yuv (frame stride span), then the conversion into S.d_stage on S.st
-void upload_yuv420(Slot& S, const uint8_t* host, int n, int w, int h, const slideo_yuv420_layout& L, int64_t span, int64_t frame_stride,
-                   hipStream_t cs) {
-    S.d_yuv.reserve((size_t)span * n + 16);
-    S.d_stage.reserve((size_t)w * h * 3 * n + 16);
-    hipStream_t st = cs ? cs : S.st;
-    if (frame_stride == span) {
-        HIP_CHECK(hipMemcpyAsync(S.d_yuv.p, host, (size_t)span * n, hipMemcpyHostToDevice, st));
-    } else {
-        for (int i = 0; i < n; ++i)
-            HIP_CHECK(hipMemcpyAsync(S.d_yuv.as<uint8_t>() + (size_t)span * i, host + frame_stride * i, (size_t)span, hipMemcpyHostToDevice, st));
-    }
-    if (cs) {
-        HIP_CHECK(hipEventRecord(S.ev_up, cs));
-        HIP_CHECK(hipStreamWaitEvent(S.st, S.ev_up, 0));
-    }
-    launch_yuv420_to_bgr(S.d_yuv.as<uint8_t>(), span, L, w, h, n, S.d_stage.as<uint8_t>(), S.st);
-}
-
 // page-locked (hipHostMalloc / hipHostRegister) host memory?  Copies from it are truly asynchronous DMA; copies from pageable
 // memory are staged by the runtime inside the call.
-bool host_is_pinned(const void* p) {
+static bool host_is_pinned(const void* p) {
     hipPointerAttribute_t a{};
     if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return false; }
     return a.type == hipMemoryTypeHost;
@@ -126,8 +84,9 @@ void validate_image(int w, int h, int stride) {
     if (w < 1 || h < 1 || stride < w * 3) fail(SLIDEO_ERR_INVALID_ARG, "bad image geometry w=%d h=%d stride=%d", w, h, stride);
 }
 
-int64_t yuv420_validate(int w, int h, const slideo_yuv420_layout* L, int64_t frame_stride) {
-    if (!L) fail(SLIDEO_ERR_INVALID_ARG, "null yuv420 layout");
+// the rules of include/slideo_amd.h "YUV 4:2:0 frames"; returns the bytes of one frame (its furthest byte + 1).  frame_stride < 0:
+// a single frame, no stride to check
+static int64_t yuv420_validate(int w, int h, const slideo_yuv420_layout* L, int64_t frame_stride) {
     if (w < 1 || h < 1) fail(SLIDEO_ERR_INVALID_ARG, "bad image geometry w=%d h=%d", w, h);
     if ((w | h) & 1) fail(SLIDEO_ERR_UNSUPPORTED, "yuv420: width and height must be even (%dx%d), as cvtColor requires", w, h);
     if (w > MAX_DIM || h > MAX_DIM) fail(SLIDEO_ERR_UNSUPPORTED, "image size %dx%d outside 1..%d", w, h, MAX_DIM);
@@ -165,6 +124,60 @@ int64_t yuv420_validate(int w, int h, const slideo_yuv420_layout* L, int64_t fra
     return span;
 }
 
+void validate_frames(FrameSrc& src, slideo_matcher* m, int n, const void* out) {
+    if (src.yuv) {
+        src.yuv_span = yuv420_validate(src.w, src.h, src.yuv, src.frame_stride);
+        src.stride = src.w * 3;                                    // the BGR image the units read (d_stage)
+    }
+    if (m) {
+        if (!m->finalized) fail(SLIDEO_ERR_STATE, "slideo_matcher_finalize_pages must be called before matching");
+        if (m->M <= 0) fail(SLIDEO_ERR_EMPTY_INDEX, "no page produced a descriptor");
+        if (n < 0 || (n > 0 && (!src.p || !out))) fail(SLIDEO_ERR_INVALID_ARG, "null frames/verdicts");
+    }
+    validate_image(src.w, src.h, src.stride);
+    if (m && m->sift_on) sift_check_cfg(&m->sift_cfg, src.w, src.h);          // (the doubled image's coordinates travel in 13 bits)
+    if (m && !src.yuv && src.frame_stride < (int64_t)src.h * src.stride) fail(SLIDEO_ERR_INVALID_ARG, "frame_stride smaller than one frame");
+    src.pinned = !src.on_device && src.p && host_is_pinned(src.p);
+}
+
+// S's staging buffer with room for `bytes`.  Slot 0's holds the frames slideo_changed_mask_bgr8 kept for slideo_match_kept_frames:
+// whatever the mask call left there is overwritten (any slot's, as a call's units cycle through them all)
+static uint8_t* stage_for_upload(slideo_matcher* m, Slot& S, size_t bytes) {
+    m->kept.valid = false;
+    S.d_stage.reserve(bytes + 16);
+    return S.d_stage.as<uint8_t>();
+}
+
+DevFrames stage_frames(slideo_matcher* m, Slot& S, const FrameSrc& src, int first, int n, hipStream_t cs) {
+    const uint8_t* p = src.p + (int64_t)first * src.frame_stride;
+    if (src.on_device && !src.yuv) return DevFrames{p, src.w, src.h, src.stride, src.frame_stride};
+    const int64_t fb = (int64_t)src.h * src.stride;              // one frame of the BGR view (stride 3w for YUV frames)
+    uint8_t* stage = stage_for_upload(m, S, (size_t)fb * n);
+    int64_t fs = src.frame_stride;
+    if (!src.on_device) {
+        // host frames back to back into d_stage, or into d_yuv for the conversion below
+        const int64_t bytes = src.yuv ? src.yuv_span : fb;
+        uint8_t* dst = stage;
+        if (src.yuv) { S.d_yuv.reserve((size_t)bytes * n + 16); dst = S.d_yuv.as<uint8_t>(); }
+        hipStream_t st = cs ? cs : S.st;
+        if (fs == bytes) {
+            HIP_CHECK(hipMemcpyAsync(dst, p, (size_t)bytes * n, hipMemcpyHostToDevice, st));
+        } else {
+            for (int i = 0; i < n; ++i)
+                HIP_CHECK(hipMemcpyAsync(dst + bytes * i, p + fs * i, (size_t)bytes, hipMemcpyHostToDevice, st));
+        }
+        if (cs) {
+            HIP_CHECK(hipEventRecord(S.ev_up, cs));
+            HIP_CHECK(hipStreamWaitEvent(S.st, S.ev_up, 0));
+        }
+        p = dst; fs = bytes;
+    }
+    // 4:2:0 frames: converted on the slot's stream into its d_stage, which lives until the unit is collected (verify's re-projection
+    // reads the frames)
+    if (src.yuv) launch_yuv420_to_bgr(p, fs, *src.yuv, src.w, src.h, n, stage, S.st);
+    return DevFrames{stage, src.w, src.h, src.stride, fb};
+}
+
 // ---- one unit of the per-frame hot path: enqueue everything, then collect ---------------
 // `frames_dev` must stay valid until the unit is collected (reproject reads the frames).
 // keypoints per frame the capacity-sized path provides for: twice the quota (ties at a level's retainBest threshold are kept, so
@@ -186,15 +199,14 @@ uint32_t kp_cap_for(const slideo_matcher* m, const PyrGeom& g) {
     return (uint32_t)std::max(1, std::min(cap, std::max(g.cand_per_frame, 1)));
 }
 
-void unit_submit(slideo_matcher* m, Slot& S, const uint8_t* frames_dev, int n, int w, int h, int stride, int64_t frame_stride,
-                 bool allow_async) {
+void unit_submit(slideo_matcher* m, Slot& S, const DevFrames& f, int n, bool allow_async) {
     // (does this unit share the chip with others?  the search then runs one block per CU: stage_knn.hip share_pad)
     { bool others = m->units_pending; for (const Slot& o : m->slots) others |= (&o != &S && o.busy); S.u_shared = others; }
-    if (m->sift_on) { unit_submit_sift(m, S, frames_dev, n, w, h, stride, frame_stride); return; }
+    if (m->sift_on) { unit_submit_sift(m, S, f, n); return; }
     const slideo_config& c = m->cfg;
     hipStream_t st = S.st;
     const bool prof = m->profiling;
-    const PyrGeom& g = geom_for(m, w, h).g;
+    const PyrGeom& g = geom_for(m, f.w, f.h).g;
     // Capacity-sized (no host wait in the middle of the unit) when the matrix-core kNN runs: every kernel downstream of the ORB
     // counts reads them on the device.  The VALU engine (A/B only) keeps the exact-size path.
     const uint32_t kpcap = kp_cap_for(m, g);
@@ -203,10 +215,10 @@ void unit_submit(slideo_matcher* m, Slot& S, const uint8_t* frames_dev, int n, i
     const bool async = allow_async && m->async_submit && !knn_unit_is_valu(m, n * (int)std::min<uint32_t>(kpcap, (uint32_t)c.nfeatures)) &&
                        (int64_t)n * kpcap < ((int64_t)1 << 30) &&
                        (kpcap >= (uint32_t)c.nfeatures + 1024u || kpcap >= (uint32_t)std::max(g.cand_per_frame, 1));
-    S.timed = prof; S.u_frames = frames_dev; S.u_w = w; S.u_h = h; S.u_stride = stride; S.u_fs = frame_stride; S.u_async = async;
+    S.timed = prof; S.u_in = f; S.u_async = async;
     if (m->orb_chain && m->last_orb_ev && m->last_orb_ev != S.ev_orb) HIP_CHECK(hipStreamWaitEvent(st, m->last_orb_ev, 0));
     if (prof) HIP_CHECK(hipEventRecord(S.ev[0], st));
-    orb_stage1(m, S, frames_dev, n, w, h, stride, frame_stride, false, async ? kpcap : 0xFFFFFFFFu);
+    orb_stage1(m, S, f, n, false, async ? kpcap : 0xFFFFFFFFu);
     uint32_t qtot, qplan;
     if (async) {
         qtot = (uint32_t)n * kpcap;                                          // capacity
@@ -219,7 +231,7 @@ void unit_submit(slideo_matcher* m, Slot& S, const uint8_t* frames_dev, int n, i
     // all workspace before the timed kNN interval
     S.u_nt = knn_unit_rows(m, (int)qplan);
     // the search's block shape while units share the chip (stage_knn.hip knn_shape): how much search there is per pixel of ORB work
-    S.u_w12 = m->knn_w12_ratio > 0.0 && (double)qplan * (double)S.u_nt >= m->knn_w12_ratio * (double)n * (double)w * (double)h;
+    S.u_w12 = m->knn_w12_ratio > 0.0 && (double)qplan * (double)S.u_nt >= m->knn_w12_ratio * (double)n * (double)f.w * (double)f.h;
     knn_reserve_unit(m, S, qplan, qtot);
     S.d_votes.reserve(std::max<size_t>((size_t)qtot * c.knn_k * sizeof(uint2), 16));
     S.d_gpts.reserve(std::max<size_t>((size_t)qtot * c.knn_k * sizeof(float4), 16));
@@ -228,7 +240,7 @@ void unit_submit(slideo_matcher* m, Slot& S, const uint8_t* frames_dev, int n, i
     S.d_verdicts.reserve((size_t)n * sizeof(slideo_verdict));
     S.d_pairs.reserve((size_t)n * MAXR * sizeof(PairDesc) + 64);
     S.h_out.reserve((size_t)n * (sizeof(slideo_verdict) + sizeof(FrameCands)) + 64);
-    orb_stage2(m, S, w, h, async);
+    orb_stage2(m, S, f.w, f.h, async);
     HIP_CHECK(hipEventRecord(S.ev_orb, st));
     m->last_orb_ev = S.ev_orb;
     VerifyParams vp = make_vp(c);
@@ -236,7 +248,7 @@ void unit_submit(slideo_matcher* m, Slot& S, const uint8_t* frames_dev, int n, i
     HIP_CHECK(hipMemsetAsync(S.d_fcs.p, 0, (size_t)n * sizeof(FrameCands), st));
     if (prof) HIP_CHECK(hipEventRecord(S.ev[1], st));
     if (qtot > 0) unit_knn(m, S, n, qplan, qtot, async, prof);      // (records S.ev[2] behind the search when profiling)
-    unit_verify(m, S, vp, frames_dev, n, w, h, stride, frame_stride, qtot);
+    unit_verify(m, S, vp, f, n, qtot);
 }
 
 void unit_collect(slideo_matcher* m, Slot& S, slideo_verdict* out_host) {
@@ -253,7 +265,7 @@ void unit_collect(slideo_matcher* m, Slot& S, slideo_verdict* out_host) {
         if (fl & 8u) {
             // a frame had more keypoints than the capacity-sized path provides for (ties at a retainBest threshold are kept, as
             // in OpenCV): the whole unit again, through the exact-size path
-            unit_submit(m, S, S.u_frames, n, S.u_w, S.u_h, S.u_stride, S.u_fs, false);
+            unit_submit(m, S, S.u_in, n, false);
             unit_collect(m, S, out_host);
             return;
         }
@@ -268,7 +280,7 @@ void unit_collect(slideo_matcher* m, Slot& S, slideo_verdict* out_host) {
         if (m->rng_len >= cap) fail(SLIDEO_ERR_CAPACITY, "RANSAC sample schedule exceeded %u pre-drawn RNG outputs", m->rng_len);
         HIP_CHECK(hipDeviceSynchronize());
         upload_rng_stream(m, (uint32_t)std::min<uint64_t>((uint64_t)m->rng_len * 4, cap));
-        unit_submit(m, S, S.u_frames, n, S.u_w, S.u_h, S.u_stride, S.u_fs, false);
+        unit_submit(m, S, S.u_in, n, false);
         unit_collect(m, S, out_host);
         return;
     }
@@ -288,49 +300,34 @@ void unit_collect(slideo_matcher* m, Slot& S, slideo_verdict* out_host) {
     std::memcpy(m->last_fcs.data() + base, ho + (size_t)n * sizeof(slideo_verdict), (size_t)n * sizeof(FrameCands));
 }
 
-void check_match_args(slideo_matcher* m, int n, const void* frames, const void* out, int w, int h, int stride, int64_t frame_stride) {
-    if (!m->finalized) fail(SLIDEO_ERR_STATE, "slideo_matcher_finalize_pages must be called before matching");
-    if (m->M <= 0) fail(SLIDEO_ERR_EMPTY_INDEX, "no page produced a descriptor");
-    if (n < 0 || (n > 0 && (!frames || !out))) fail(SLIDEO_ERR_INVALID_ARG, "null frames/verdicts");
-    validate_image(w, h, stride);
-    if (m->sift_on) sift_check_cfg(&m->sift_cfg, w, h);          // (the doubled image's coordinates travel in 13 bits)
-    if (frame_stride < (int64_t)h * stride) fail(SLIDEO_ERR_INVALID_ARG, "frame_stride smaller than one frame");
-}
-
 // Synchronous matching of n frames: cut into units and run them through the slots as a pipeline.
-void match_frames_impl(slideo_matcher* m, int n, const uint8_t* frames, bool on_device, int w, int h, int stride,
-                       int64_t frame_stride, slideo_verdict* out, hipStream_t user_stream, const slideo_yuv420_layout* yuv) {
-    int64_t span = 0;
-    if (yuv) {
-        span = yuv420_validate(w, h, yuv, frame_stride);
-        stride = w * 3;                                            // the BGR image the units read (d_stage)
-        check_match_args(m, n, frames, out, w, h, stride, (int64_t)h * stride);
-        m->kept.valid = false;                                     // (slot 0's d_stage receives BGR)
-    } else {
-        check_match_args(m, n, frames, out, w, h, stride, frame_stride);
-    }
+void match_frames_impl(slideo_matcher* m, int n, FrameSrc src, slideo_verdict* out, hipStream_t user_stream) {
+    validate_frames(src, m, n, out);
     HIP_CHECK(hipSetDevice(m->device));
     require_idle(m);
     m->last_fcs.clear();
     if (n == 0) return;
-    GeomEntry& ge = geom_for(m, w, h);
-    area_class_for(m, w, h);
+    GeomEntry& ge = geom_for(m, src.w, src.h);
+    area_class_for(m, src.w, src.h);
     upload_area(m);
-    int unit = sub_batch_for(m, ge.g, n, yuv != nullptr);
+    int unit = sub_batch_for(m, ge.g, n, src.yuv != nullptr);
     if (n >= 128 && unit >= (n + 1) / 2) unit = (n + 1) / 2;      // two halves overlap ORB with kNN / verify
     // Host frames: the call is bound by the H2D copies (6.2 MB per 1080p frame: 256 frames = 29 ms at 55 GB/s against 14 ms of
     // kernels), so what matters is that the copy engines never wait: short units, each copied on its slot's stream while the
     // units before it compute — with two halves the second half's kernels start only when all of it has arrived.
-    if (!on_device && m->host_unit > 0 && n >= 2 * m->host_unit) unit = std::min(unit, m->host_unit);
+    if (!src.on_device && m->host_unit > 0 && n >= 2 * m->host_unit) unit = std::min(unit, m->host_unit);
     struct Pending { Slot* S; int ofs; };
     std::vector<Pending> pend;
-    if (on_device && user_stream)
+    if (src.on_device && user_stream)
         for (Slot& S : m->slots) {      // inputs produced on the caller's stream: order our streams behind it
             HIP_CHECK(hipEventRecord(S.ev_in, user_stream));
             HIP_CHECK(hipStreamWaitEvent(S.st, S.ev_in, 0));
         }
     int done = 0;
-    const bool src_pinned = !on_device && host_is_pinned(frames);
+    // pinned source: asynchronous copies, kept in submission order on the one copy stream (see copy_st); pageable source: the
+    // runtime stages the copy inside the call, on the unit's own stream (measured: 32.7 ms per 256 frames that way against 54.8
+    // through the copy stream)
+    hipStream_t cs = src.pinned ? m->copy_st : nullptr;
     m->units_pending = n > unit;
     try {
         for (int i = 0; i < n; i += unit) {
@@ -343,28 +340,7 @@ void match_frames_impl(slideo_matcher* m, int n, const uint8_t* frames, bool on_
             }
             Slot& S = m->slots[m->next_slot];
             m->next_slot = (m->next_slot + 1) % NSLOTS;
-            const uint8_t* dev;
-            int64_t fs = frame_stride;
-            if (yuv) {
-                // 4:2:0 frames: converted on the slot's stream into its d_stage, which lives until the unit is collected (verify's
-                // re-projection reads the frames); host sources are uploaded first, exactly as BGR ones are
-                if (on_device) {
-                    S.d_stage.reserve((size_t)w * h * 3 * cnt + 16);
-                    launch_yuv420_to_bgr(frames + (int64_t)i * frame_stride, frame_stride, *yuv, w, h, cnt, S.d_stage.as<uint8_t>(), S.st);
-                } else {
-                    upload_yuv420(S, frames + (int64_t)i * frame_stride, cnt, w, h, *yuv, span, frame_stride, src_pinned ? m->copy_st : nullptr);
-                }
-                dev = S.d_stage.as<uint8_t>(); fs = (int64_t)h * stride;
-            } else if (on_device) dev = frames + (int64_t)i * frame_stride;
-            else {
-                // pinned source: asynchronous copies, kept in submission order on the one copy stream (see copy_st); pageable
-                // source: the runtime stages the copy inside the call, on the unit's own stream (measured: 32.7 ms per 256 frames
-                // that way against 54.8 through the copy stream)
-                upload_frames(S, frames + (int64_t)i * frame_stride, cnt, h, stride, frame_stride, src_pinned ? m->copy_st : nullptr);
-                dev = S.d_stage.as<uint8_t>(); fs = (int64_t)h * stride;
-                m->kept.valid = false;                       // (slot 0's staging buffer may be overwritten)
-            }
-            unit_submit(m, S, dev, cnt, w, h, stride, fs);
+            unit_submit(m, S, stage_frames(m, S, src, i, cnt, cs), cnt);
             pend.push_back({&S, i});
         }
         for (Pending& p : pend) {
@@ -400,12 +376,12 @@ void analyse_pages(slideo_matcher* m, int n_pages, const uint8_t* const* data, c
         int cap = std::min(sub_batch_for(m, ge.g, n_pages - i), 64), cnt = 1;
         while (cnt < cap && width[i + cnt] == w && height[i + cnt] == h && stride_bytes[i + cnt] == stride && data[i + cnt]) ++cnt;
         const size_t fb = (size_t)h * stride;
-        stage_for_upload(m, fb * cnt);
-        for (int j = 0; j < cnt; ++j)
-            HIP_CHECK(hipMemcpyAsync(S.d_stage.as<uint8_t>() + fb * j, data[i + j], fb, hipMemcpyHostToDevice, st));
+        uint8_t* stage = stage_for_upload(m, S, fb * cnt);
+        for (int j = 0; j < cnt; ++j) HIP_CHECK(hipMemcpyAsync(stage + fb * j, data[i + j], fb, hipMemcpyHostToDevice, st));
+        const DevFrames staged{stage, w, h, stride, (int64_t)fb};
         const size_t dbytes = m->sift_on ? 128 : 32;                       // descriptor bytes per keypoint
-        if (m->sift_on) add_pages_sift(m, S, cnt, w, h, stride, (int64_t)fb);     // -> S.d_kp / S.d_desc / S.orb.qofs, like run_orb
-        else run_orb(m, S, S.d_stage.as<uint8_t>(), cnt, w, h, stride, (int64_t)fb, true);
+        if (m->sift_on) add_pages_sift(m, S, staged, cnt);                 // -> S.d_kp / S.d_desc / S.orb.qofs, like run_orb
+        else run_orb(m, S, staged, cnt, true);
         const uint32_t qtot = S.orb.qtot;
         std::vector<slideo_keypoint> kp(qtot);
         std::vector<uint8_t> desc((size_t)qtot * dbytes);
@@ -414,7 +390,7 @@ void analyse_pages(slideo_matcher* m, int n_pages, const uint8_t* const* data, c
             HIP_CHECK(hipMemcpyAsync(desc.data(), S.d_desc.p, (size_t)qtot * dbytes, hipMemcpyDeviceToHost, st));
         }
         int sw = 0, sh = 0;
-        run_small(m, S.d_stage.as<uint8_t>(), cnt, w, h, stride, (int64_t)fb, sw, sh, st);
+        run_small(m, staged, cnt, sw, sh, st);
         std::vector<uint8_t> smalls((size_t)cnt * sw * sh * 3);
         HIP_CHECK(hipMemcpyAsync(smalls.data(), m->d_small.p, smalls.size(), hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipStreamSynchronize(st));
@@ -780,7 +756,7 @@ int32_t slideo_match_frames_bgr8(slideo_matcher* m, int32_t n_frames, const uint
                                  int32_t stride_bytes, int64_t frame_stride_bytes, slideo_verdict* verdicts_out) {
     if (!m) return SLIDEO_ERR_INVALID_ARG;
     API_TRY
-    match_frames_impl(m, n_frames, frames, false, width, height, stride_bytes, frame_stride_bytes, verdicts_out, nullptr);
+    match_frames_impl(m, n_frames, FrameSrc::bgr8(frames, false, width, height, stride_bytes, frame_stride_bytes), verdicts_out, nullptr);
     API_CATCH(m)
 }
 
@@ -788,7 +764,7 @@ int32_t slideo_match_frames_bgr8_dev(slideo_matcher* m, int32_t n_frames, const 
                                      int32_t stride_bytes, int64_t frame_stride_bytes, slideo_verdict* verdicts_out, void* hip_stream) {
     if (!m) return SLIDEO_ERR_INVALID_ARG;
     API_TRY
-    match_frames_impl(m, n_frames, frames_dev, true, width, height, stride_bytes, frame_stride_bytes, verdicts_out,
+    match_frames_impl(m, n_frames, FrameSrc::bgr8(frames_dev, true, width, height, stride_bytes, frame_stride_bytes), verdicts_out,
                       reinterpret_cast<hipStream_t>(hip_stream));
     API_CATCH(m)
 }
@@ -797,65 +773,49 @@ int32_t slideo_match_frames_bgr8_dev(slideo_matcher* m, int32_t n_frames, const 
 
 namespace {
 
-// slideo_match_frames_submit[_yuv420]_dev; yuv != null: the unit's frames are converted into the slot's d_stage first
-void submit_impl(slideo_matcher* m, int32_t n_frames, const uint8_t* frames_dev, int32_t width, int32_t height, int32_t stride_bytes,
-                 int64_t frame_stride_bytes, const slideo_yuv420_layout* yuv, void* hip_stream, int64_t* ticket_out) {
+// slideo_match_frames_submit[_yuv420]_dev
+void submit_impl(slideo_matcher* m, int32_t n_frames, FrameSrc src, void* hip_stream, int64_t* ticket_out) {
     if (!ticket_out) fail(SLIDEO_ERR_INVALID_ARG, "null ticket_out");
-    if (yuv) {
-        yuv420_validate(width, height, yuv, frame_stride_bytes);
-        check_match_args(m, n_frames, frames_dev, ticket_out, width, height, width * 3, (int64_t)height * width * 3);
-    } else {
-        check_match_args(m, n_frames, frames_dev, ticket_out, width, height, stride_bytes, frame_stride_bytes);
-    }
+    validate_frames(src, m, n_frames, ticket_out);
     if (n_frames < 1) fail(SLIDEO_ERR_INVALID_ARG, "submit needs at least one frame");
     HIP_CHECK(hipSetDevice(m->device));
     Slot& S = m->slots[m->next_slot];
     if (S.busy) fail(SLIDEO_ERR_STATE, "all slots are in flight: collect ticket %lld first", (long long)S.ticket);
-    GeomEntry& ge = geom_for(m, width, height);
-    if (n_frames > sub_batch_for(m, ge.g, n_frames, yuv != nullptr))
+    GeomEntry& ge = geom_for(m, src.w, src.h);
+    if (n_frames > sub_batch_for(m, ge.g, n_frames, src.yuv != nullptr))
         fail(SLIDEO_ERR_CAPACITY, "%d frames exceed the per-slot workspace budget (%d); submit smaller units or raise SLIDEO_WS_GB",
-             n_frames, sub_batch_for(m, ge.g, n_frames, yuv != nullptr));
-    area_class_for(m, width, height);
+             n_frames, sub_batch_for(m, ge.g, n_frames, src.yuv != nullptr));
+    area_class_for(m, src.w, src.h);
     upload_area(m);
     { bool any = false; for (const Slot& c : m->slots) any |= c.busy; if (!any) m->last_fcs.clear(); }
     if (hip_stream) {
         HIP_CHECK(hipEventRecord(S.ev_in, reinterpret_cast<hipStream_t>(hip_stream)));
         HIP_CHECK(hipStreamWaitEvent(S.st, S.ev_in, 0));
     }
-    if (yuv) {
-        // the BGR image lives in the slot's d_stage until the unit is collected (verify's re-projection reads it then)
-        m->kept.valid = false;
-        S.d_stage.reserve((size_t)width * height * 3 * n_frames + 16);
-        launch_yuv420_to_bgr(frames_dev, frame_stride_bytes, *yuv, width, height, n_frames, S.d_stage.as<uint8_t>(), S.st);
-        frames_dev = S.d_stage.as<uint8_t>(); stride_bytes = width * 3; frame_stride_bytes = (int64_t)height * width * 3;
-    }
-    unit_submit(m, S, frames_dev, n_frames, width, height, stride_bytes, frame_stride_bytes);
+    unit_submit(m, S, stage_frames(m, S, src, 0, n_frames), n_frames);
     S.ticket = m->next_ticket++;
     *ticket_out = S.ticket;
     m->next_slot = (m->next_slot + 1) % NSLOTS;
     for (Slot& O : m->slots) if (&O != &S && !O.busy) O.match_capacity(S);  // the next units find their workspace sized
 }
 
-// slideo_changed_mask_bgr8 / _yuv420 (yuv != null: converted into slot 0's d_stage at stride 3w, which m->kept then describes)
-void changed_mask_impl(slideo_matcher* m, int32_t n_frames, const uint8_t* frames, int32_t width, int32_t height, int32_t stride_bytes,
-                       int64_t frame_stride_bytes, const slideo_yuv420_layout* yuv, const uint8_t* prev_small, uint8_t* last_small_out,
-                       uint8_t* changed_out, float* similarity_out) {
-    if (n_frames < 0 || (n_frames > 0 && (!frames || !changed_out))) fail(SLIDEO_ERR_INVALID_ARG, "null frames/changed");
-    const int64_t span = yuv ? yuv420_validate(width, height, yuv, frame_stride_bytes) : 0;
-    if (yuv) stride_bytes = width * 3;
-    validate_image(width, height, stride_bytes);
+}  // namespace
+
+namespace slideo {
+
+void changed_mask_impl(slideo_matcher* m, int n_frames, FrameSrc src, const uint8_t* prev_small, uint8_t* last_small_out, uint8_t* changed_out,
+                       float* similarity_out) {
+    if (n_frames < 0 || (n_frames > 0 && (!src.p || !changed_out))) fail(SLIDEO_ERR_INVALID_ARG, "null frames/changed");
+    validate_frames(src);
     if (n_frames == 0) return;
     HIP_CHECK(hipSetDevice(m->device));
     require_idle(m);
     Slot& S = m->slots[0];
     hipStream_t st = S.st;
     int sw = 0, sh = 0;
-    const size_t fb = (size_t)height * stride_bytes;
-    stage_for_upload(m, fb * (size_t)n_frames);
-    if (yuv) upload_yuv420(S, frames, n_frames, width, height, *yuv, span, frame_stride_bytes, nullptr);
-    else upload_frames(S, frames, n_frames, height, stride_bytes, frame_stride_bytes);
-    m->kept = slideo_matcher::Kept{true, n_frames, width, height, stride_bytes};   // stays in slot 0's staging buffer: slideo_match_kept_frames
-    run_small(m, S.d_stage.as<uint8_t>(), n_frames, width, height, stride_bytes, (int64_t)fb, sw, sh, st);
+    const DevFrames f = stage_frames(m, S, src, 0, n_frames);
+    m->kept = slideo_matcher::Kept{true, n_frames, f.w, f.h, f.stride};      // stays in slot 0's staging buffer: slideo_match_kept_frames
+    run_small(m, f, n_frames, sw, sh, st);
     const size_t sb = (size_t)sw * sh * 3;
     DevBuf& prev = m->d_prev_small;
     prev.reserve(sb);
@@ -882,7 +842,7 @@ void changed_mask_impl(slideo_matcher* m, int32_t n_frames, const uint8_t* frame
     }
 }
 
-}  // namespace
+}  // namespace slideo
 
 extern "C" {
 
@@ -890,7 +850,7 @@ int32_t slideo_match_frames_submit_dev(slideo_matcher* m, int32_t n_frames, cons
                                        int32_t stride_bytes, int64_t frame_stride_bytes, void* hip_stream, int64_t* ticket_out) {
     if (!m) return SLIDEO_ERR_INVALID_ARG;
     API_TRY
-    submit_impl(m, n_frames, frames_dev, width, height, stride_bytes, frame_stride_bytes, nullptr, hip_stream, ticket_out);
+    submit_impl(m, n_frames, FrameSrc::bgr8(frames_dev, true, width, height, stride_bytes, frame_stride_bytes), hip_stream, ticket_out);
     API_CATCH(m)
 }
 
@@ -940,7 +900,7 @@ int32_t slideo_changed_mask_bgr8(slideo_matcher* m, int32_t n_frames, const uint
                                  uint8_t* last_small_out, uint8_t* changed_out, float* similarity_out) {
     if (!m) return SLIDEO_ERR_INVALID_ARG;
     API_TRY
-    changed_mask_impl(m, n_frames, frames, width, height, stride_bytes, frame_stride_bytes, nullptr, prev_small, last_small_out,
+    changed_mask_impl(m, n_frames, FrameSrc::bgr8(frames, false, width, height, stride_bytes, frame_stride_bytes), prev_small, last_small_out,
                       changed_out, similarity_out);
     API_CATCH(m)
 }
@@ -966,7 +926,7 @@ int32_t slideo_match_kept_frames(slideo_matcher* m, int32_t n_sel, const int32_t
         HIP_CHECK(hipMemcpyAsync(m->d_kept.as<uint8_t>() + fb * i, m->slots[0].d_stage.as<uint8_t>() + fb * sel[i], fb * (size_t)(j - i), hipMemcpyDeviceToDevice, st));
         i = j;
     }
-    match_frames_impl(m, n_sel, m->d_kept.as<uint8_t>(), true, k.w, k.h, k.stride, (int64_t)fb, verdicts_out, st);
+    match_frames_impl(m, n_sel, FrameSrc::bgr8(m->d_kept.as<uint8_t>(), true, k.w, k.h, k.stride, (int64_t)fb), verdicts_out, st);
     API_CATCH(m)
 }
 
@@ -1007,8 +967,7 @@ int32_t slideo_match_frames_yuv420(slideo_matcher* m, int32_t n_frames, const ui
                                    const slideo_yuv420_layout* layout, int64_t frame_stride_bytes, slideo_verdict* verdicts_out) {
     if (!m) return SLIDEO_ERR_INVALID_ARG;
     API_TRY
-    if (!layout) fail(SLIDEO_ERR_INVALID_ARG, "null yuv420 layout");
-    match_frames_impl(m, n_frames, frames, false, width, height, 0, frame_stride_bytes, verdicts_out, nullptr, layout);
+    match_frames_impl(m, n_frames, FrameSrc::yuv420(frames, false, width, height, layout, frame_stride_bytes), verdicts_out, nullptr);
     API_CATCH(m)
 }
 
@@ -1017,9 +976,8 @@ int32_t slideo_match_frames_yuv420_dev(slideo_matcher* m, int32_t n_frames, cons
                                        void* hip_stream) {
     if (!m) return SLIDEO_ERR_INVALID_ARG;
     API_TRY
-    if (!layout) fail(SLIDEO_ERR_INVALID_ARG, "null yuv420 layout");
-    match_frames_impl(m, n_frames, frames_dev, true, width, height, 0, frame_stride_bytes, verdicts_out,
-                      reinterpret_cast<hipStream_t>(hip_stream), layout);
+    match_frames_impl(m, n_frames, FrameSrc::yuv420(frames_dev, true, width, height, layout, frame_stride_bytes), verdicts_out,
+                      reinterpret_cast<hipStream_t>(hip_stream));
     API_CATCH(m)
 }
 
@@ -1028,8 +986,7 @@ int32_t slideo_match_frames_submit_yuv420_dev(slideo_matcher* m, int32_t n_frame
                                               int64_t* ticket_out) {
     if (!m) return SLIDEO_ERR_INVALID_ARG;
     API_TRY
-    if (!layout) fail(SLIDEO_ERR_INVALID_ARG, "null yuv420 layout");
-    submit_impl(m, n_frames, frames_dev, width, height, 0, frame_stride_bytes, layout, hip_stream, ticket_out);
+    submit_impl(m, n_frames, FrameSrc::yuv420(frames_dev, true, width, height, layout, frame_stride_bytes), hip_stream, ticket_out);
     API_CATCH(m)
 }
 
@@ -1038,9 +995,8 @@ int32_t slideo_changed_mask_yuv420(slideo_matcher* m, int32_t n_frames, const ui
                                    uint8_t* last_small_out, uint8_t* changed_out, float* similarity_out) {
     if (!m) return SLIDEO_ERR_INVALID_ARG;
     API_TRY
-    if (!layout) fail(SLIDEO_ERR_INVALID_ARG, "null yuv420 layout");
-    changed_mask_impl(m, n_frames, frames, width, height, 0, frame_stride_bytes, layout, prev_small, last_small_out, changed_out,
-                      similarity_out);
+    changed_mask_impl(m, n_frames, FrameSrc::yuv420(frames, false, width, height, layout, frame_stride_bytes), prev_small, last_small_out,
+                      changed_out, similarity_out);
     API_CATCH(m)
 }
 

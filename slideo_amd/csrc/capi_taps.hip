@@ -12,15 +12,13 @@ int32_t slideo_orb_bgr8(slideo_matcher* m, const uint8_t* bgr, int32_t width, in
     if (!m) return SLIDEO_ERR_INVALID_ARG;
     API_TRY
     if (!bgr || !n_out) fail(SLIDEO_ERR_INVALID_ARG, "null image/n_out");
-    validate_image(width, height, stride_bytes);
+    FrameSrc img = FrameSrc::image(bgr, width, height, stride_bytes);
+    validate_frames(img);
     HIP_CHECK(hipSetDevice(m->device));
     require_idle(m);
     Slot& S = m->slots[0];
     hipStream_t st = S.st;
-    const size_t fb = (size_t)height * stride_bytes;
-    stage_for_upload(m, fb);
-    HIP_CHECK(hipMemcpyAsync(S.d_stage.p, bgr, fb, hipMemcpyHostToDevice, st));
-    run_orb(m, S, S.d_stage.as<uint8_t>(), 1, width, height, stride_bytes, (int64_t)fb, false);
+    run_orb(m, S, stage_frames(m, S, img, 0, 1), 1, false);
     const uint32_t q = S.orb.qtot;
     *n_out = (int32_t)q;
     if ((int64_t)q > capacity) fail(SLIDEO_ERR_CAPACITY, "%u keypoints, capacity %d", q, capacity);
@@ -37,16 +35,14 @@ int32_t slideo_pyramid_level_bgr8(slideo_matcher* m, const uint8_t* bgr, int32_t
     if (!m) return SLIDEO_ERR_INVALID_ARG;
     API_TRY
     if (!bgr || !out || !lw || !lh) fail(SLIDEO_ERR_INVALID_ARG, "null argument");
-    validate_image(width, height, stride_bytes);
+    FrameSrc img = FrameSrc::image(bgr, width, height, stride_bytes);
+    validate_frames(img);
     if (level < 0 || level >= m->cfg.nlevels) fail(SLIDEO_ERR_INVALID_ARG, "level out of range");
     HIP_CHECK(hipSetDevice(m->device));
     require_idle(m);
     Slot& S = m->slots[0];
     hipStream_t st = S.st;
-    const size_t fb = (size_t)height * stride_bytes;
-    stage_for_upload(m, fb);
-    HIP_CHECK(hipMemcpyAsync(S.d_stage.p, bgr, fb, hipMemcpyHostToDevice, st));
-    run_orb(m, S, S.d_stage.as<uint8_t>(), 1, width, height, stride_bytes, (int64_t)fb, false, blurred != 0);
+    run_orb(m, S, stage_frames(m, S, img, 0, 1), 1, false, blurred != 0);
     const LevelGeom& L = geom_for(m, width, height).g.lv[level];
     *lw = L.w; *lh = L.h;
     if ((int64_t)L.w * L.h > out_capacity) fail(SLIDEO_ERR_CAPACITY, "level needs %lld bytes", (long long)L.w * L.h);
@@ -63,16 +59,14 @@ int32_t slideo_small_image_bgr8(slideo_matcher* m, const uint8_t* bgr, int32_t w
     if (!m) return SLIDEO_ERR_INVALID_ARG;
     API_TRY
     if (!bgr || !out || !sw_out || !sh_out) fail(SLIDEO_ERR_INVALID_ARG, "null argument");
-    validate_image(width, height, stride_bytes);
+    FrameSrc img = FrameSrc::image(bgr, width, height, stride_bytes);
+    validate_frames(img);
     HIP_CHECK(hipSetDevice(m->device));
     require_idle(m);
     Slot& S = m->slots[0];
     hipStream_t st = S.st;
-    const size_t fb = (size_t)height * stride_bytes;
-    stage_for_upload(m, fb);
-    HIP_CHECK(hipMemcpyAsync(S.d_stage.p, bgr, fb, hipMemcpyHostToDevice, st));
     int sw = 0, sh = 0;
-    run_small(m, S.d_stage.as<uint8_t>(), 1, width, height, stride_bytes, (int64_t)fb, sw, sh, st);
+    run_small(m, stage_frames(m, S, img, 0, 1), 1, sw, sh, st);
     *sw_out = sw; *sh_out = sh;
     if ((int64_t)sw * sh * 3 > out_capacity) fail(SLIDEO_ERR_CAPACITY, "small image needs %lld bytes", (long long)sw * sh * 3);
     HIP_CHECK(hipMemcpyAsync(out, m->d_small.p, (size_t)sw * sh * 3, hipMemcpyDeviceToHost, st));
@@ -85,15 +79,14 @@ int32_t slideo_yuv420_to_bgr8(slideo_matcher* m, const uint8_t* frame, int32_t w
     if (!m) return SLIDEO_ERR_INVALID_ARG;
     API_TRY
     if (!frame || !bgr_out) fail(SLIDEO_ERR_INVALID_ARG, "null frame/bgr_out");
-    const int64_t span = yuv420_validate(width, height, layout, -1);
+    FrameSrc img = FrameSrc::yuv420(frame, false, width, height, layout, -1);
+    validate_frames(img);
     const size_t fb = (size_t)width * height * 3;
     if ((int64_t)fb > out_capacity) fail(SLIDEO_ERR_CAPACITY, "the BGR image needs %zu bytes", fb);
     HIP_CHECK(hipSetDevice(m->device));
     require_idle(m);
     Slot& S = m->slots[0];
-    stage_for_upload(m, fb);
-    upload_yuv420(S, frame, 1, width, height, *layout, span, span, nullptr);
-    HIP_CHECK(hipMemcpyAsync(bgr_out, S.d_stage.p, fb, hipMemcpyDeviceToHost, S.st));
+    HIP_CHECK(hipMemcpyAsync(bgr_out, stage_frames(m, S, img, 0, 1).p, fb, hipMemcpyDeviceToHost, S.st));
     HIP_CHECK(hipStreamSynchronize(S.st));
     API_CATCH(m)
 }

@@ -1,6 +1,6 @@
 // runtime.hpp — the host runtime behind include/slideo_amd.h, shared by its translation units.
 //
-//   capi_runtime.hip   handles, page database, slots, unit submit / collect, the match entry points
+//   capi_runtime.hip   handles, page database, slots, frame staging (FrameSrc -> DevFrames), unit submit / collect, the match entry points
 //   stage_orb.hip      ORB stage drivers          (kernels: orb.hip.h, yuv420.hip.h)
 //   stage_knn.hip      index build + k-NN stage   (kernels: knn.hip.h, knn_tile.hip.h, knn_l2.hip.h, knn_lsh.hip.h)
 //   stage_verify.hip   vote .. verdict, small img (kernels: verify.hip.h, homography.hip.h)
@@ -55,6 +55,39 @@ struct HostPage {
     std::vector<uint8_t> small_img;
 };
 
+// A call's frames as the caller handed them over: BGR8 (yuv null) or YUV 4:2:0 in the layout `yuv`, in host or device memory.
+// validate_frames checks them and fills the derived fields; stage_frames turns a block of them into a unit's BGR8 view.
+struct FrameSrc {
+    const uint8_t* p = nullptr;
+    bool on_device = false;
+    int w = 0, h = 0;
+    int stride = 0;                             // BGR rows; a YUV source's BGR image (d_stage) has 3w, set by validate_frames
+    int64_t frame_stride = 0;                   // (a single frame: -1 = no stride to check)
+    const slideo_yuv420_layout* yuv = nullptr;
+    int64_t yuv_span = 0;                       // (derived) bytes of one YUV frame: its furthest byte + 1
+    bool pinned = false;                        // (derived) page-locked host memory: its copies are truly asynchronous DMA
+
+    static FrameSrc bgr8(const uint8_t* p, bool on_device, int w, int h, int stride, int64_t frame_stride) {
+        return FrameSrc{p, on_device, w, h, stride, frame_stride};
+    }
+    static FrameSrc yuv420(const uint8_t* p, bool on_device, int w, int h, const slideo_yuv420_layout* L, int64_t frame_stride) {
+        if (!L) fail(SLIDEO_ERR_INVALID_ARG, "null yuv420 layout");
+        FrameSrc s{p, on_device, w, h};
+        s.frame_stride = frame_stride; s.yuv = L;
+        return s;
+    }
+    static FrameSrc image(const uint8_t* p, int w, int h, int stride) { return bgr8(p, false, w, h, stride, (int64_t)h * stride); }   // one host image
+    // the same frames from frame `first` on (a group member's shard)
+    FrameSrc from(int first) const { FrameSrc s = *this; s.p += (int64_t)first * frame_stride; return s; }
+};
+
+// The BGR8 frames a unit's kernels read (device memory).
+struct DevFrames {
+    const uint8_t* p = nullptr;
+    int w = 0, h = 0, stride = 0;
+    int64_t frame_stride = 0;
+};
+
 struct OrbOut {            // where the last ORB run of a slot left its results (device)
     uint32_t qtot = 0, max_count = 0;
     int nframes = 0;
@@ -69,7 +102,7 @@ struct Slot {
     hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     hipEvent_t ev_in = nullptr, ev_orb = nullptr, ev_up = nullptr;
     // arguments of the unit in flight (re-run through the exact-size path if the capacity-sized one overflowed)
-    const uint8_t* u_frames = nullptr; int u_w = 0, u_h = 0, u_stride = 0; int64_t u_fs = 0; bool u_async = false; int u_nt = 0; bool u_shared = false, u_w12 = false;
+    DevFrames u_in; bool u_async = false; int u_nt = 0; bool u_shared = false, u_w12 = false;
     DevBuf d_stage, d_pyr, d_blur, d_cand, d_hist, d_candcount, d_flags, d_thr, d_lvlofs, d_kpcount, d_qofs, d_info;
     DevBuf d_items, d_kp, d_desc, d_keys, d_knn_pend, d_votes, d_gpts, d_gmask, d_fcs, d_verdicts, d_pairs, d_blurmask, d_qkeys, d_tail, d_refine;
     DevBuf d_yuv;              // host YUV 4:2:0 frames of the unit, converted into d_stage (reserved by the first YUV call only)
@@ -205,26 +238,23 @@ uint32_t kp_cap_for(const slideo_matcher* m, const PyrGeom& g);
 // yuv: the unit's frames arrive as YUV 4:2:0 (+ 1.5 B per pixel and frame of staging)
 int sub_batch_for(slideo_matcher* m, const PyrGeom& g, int n, bool yuv = false);
 void require_idle(slideo_matcher* m);
-// slot 0's staging buffer with room for `bytes` (taps, page ingest, the changed mask): whatever slideo_changed_mask_bgr8 kept there
-// is gone afterwards
-uint8_t* stage_for_upload(slideo_matcher* m, size_t bytes);
-void upload_frames(Slot& S, const uint8_t* host, int n, int h, int stride, int64_t frame_stride, hipStream_t cs = nullptr);
-bool host_is_pinned(const void* p);
 void validate_image(int w, int h, int stride);
-// the rules of include/slideo_amd.h "YUV 4:2:0 frames"; returns the bytes of one frame (its furthest byte + 1).  frame_stride < 0:
-// a single frame, no stride to check
-int64_t yuv420_validate(int w, int h, const slideo_yuv420_layout* L, int64_t frame_stride);
-// n host YUV frames (span bytes each, frame stride frame_stride) -> BGR8 in S.d_stage (stride 3w, frame stride 3wh), on S.st;
-// `cs` != null: copied on that (copy) stream, S.st waits for it
-void upload_yuv420(Slot& S, const uint8_t* host, int n, int w, int h, const slideo_yuv420_layout& L, int64_t span, int64_t frame_stride,
-                   hipStream_t cs);
+// The argument rules of a call's frames (include/slideo_amd.h), in the order the entry points report them: a YUV source's layout
+// (its span; the stride of its BGR image), then — m != null: a match call — the matcher's state and the null frames / verdicts
+// `out`, then a BGR source's geometry, the SIFT limits and — match calls — a BGR source's frame stride.
+void validate_frames(FrameSrc& src, slideo_matcher* m = nullptr, int n = 0, const void* out = nullptr);
+// Frames [first, first + n) of a validated `src` as BGR8 on the device, for slot S: a device BGR source as it is; host frames
+// copied into S.d_stage (BGR) or S.d_yuv (YUV), on `cs` when given (S.st waits for it) and on S.st otherwise; YUV converted into
+// S.d_stage on S.st.  Every write of a slot's d_stage goes through here (page ingest through its staging buffer) and ends the
+// frames slideo_changed_mask_bgr8 kept for slideo_match_kept_frames.
+DevFrames stage_frames(slideo_matcher* m, Slot& S, const FrameSrc& src, int first, int n, hipStream_t cs = nullptr);
 void upload_rng_stream(slideo_matcher* m, uint32_t len);
-void unit_submit(slideo_matcher* m, Slot& S, const uint8_t* frames_dev, int n, int w, int h, int stride, int64_t frame_stride, bool allow_async = true);
+void unit_submit(slideo_matcher* m, Slot& S, const DevFrames& f, int n, bool allow_async = true);
 void unit_collect(slideo_matcher* m, Slot& S, slideo_verdict* out_host);
-void check_match_args(slideo_matcher* m, int n, const void* frames, const void* out, int w, int h, int stride, int64_t frame_stride);
-// yuv != null: the frames are YUV 4:2:0 in that layout (stride is ignored), converted unit by unit into the slots' d_stage
-void match_frames_impl(slideo_matcher* m, int n, const uint8_t* frames, bool on_device, int w, int h, int stride, int64_t frame_stride,
-                       slideo_verdict* out, hipStream_t user_stream, const slideo_yuv420_layout* yuv = nullptr);
+void match_frames_impl(slideo_matcher* m, int n, FrameSrc src, slideo_verdict* out, hipStream_t user_stream);
+// slideo_changed_mask_bgr8 / _yuv420: the frames stay in slot 0's d_stage, which m->kept then describes
+void changed_mask_impl(slideo_matcher* m, int n, FrameSrc src, const uint8_t* prev_small, uint8_t* last_small_out, uint8_t* changed_out,
+                       float* similarity_out);
 // ProcessedImage::compute over n host pages (mo/lib.rs:92-131) WITHOUT appending them: the analysed pages, in order, into `out`
 void analyse_pages(slideo_matcher* m, int n_pages, const uint8_t* const* data, const int32_t* width, const int32_t* height, const int32_t* stride_bytes,
                    std::vector<HostPage>& out, uint64_t progress_base, uint64_t progress_total);
@@ -234,12 +264,10 @@ void append_page(slideo_matcher* m, const HostPage& pg);
 // ---- stage_orb.hip --------------------------------------------------------------------------------
 void orb_stage_init(slideo_matcher* m);          // device tables of the ORB kernels + their launch attributes (slideo_matcher_create)
 void orb_geom_init(slideo_matcher* m, GeomEntry& e, const std::vector<uint32_t>& lin_tab);      // per frame size: the kernels' device tables
-void orb_stage1(slideo_matcher* m, Slot& S, const uint8_t* frames_dev, int n, int w, int h, int stride, int64_t frame_stride,
-                bool with_blur = false, uint32_t kp_cap = 0xFFFFFFFFu);
+void orb_stage1(slideo_matcher* m, Slot& S, const DevFrames& f, int n, bool with_blur = false, uint32_t kp_cap = 0xFFFFFFFFu);
 void orb_wait_info(slideo_matcher* m, Slot& S);
 void orb_stage2(slideo_matcher* m, Slot& S, int w, int h, bool by_capacity = false);
-void run_orb(slideo_matcher* m, Slot& S, const uint8_t* frames_dev, int n, int w, int h, int stride, int64_t frame_stride,
-             bool keep_host_qofs, bool with_blur = false);
+void run_orb(slideo_matcher* m, Slot& S, const DevFrames& f, int n, bool keep_host_qofs, bool with_blur = false);
 // the two ORB kernels the SIFT stage shares: BGR -> gray u8 (pitch `pitch`, frame stride gframe), and the per-frame offsets scan
 void orb_launch_gray(const slideo_matcher* m, const uint8_t* frames_dev, int64_t frame_stride, int stride, uint8_t* gray, int64_t gframe, int w, int h,
                      int pitch, int n, hipStream_t st);
@@ -266,16 +294,15 @@ void l2_lists_to_keys(slideo_matcher* m, Slot& S, const DevBuf& lists, int kq, u
 // ---- stage_verify.hip -----------------------------------------------------------------------------
 void verify_stage_init(slideo_matcher* m);
 VerifyParams make_vp(const slideo_config& c);
-void unit_verify(slideo_matcher* m, Slot& S, const VerifyParams& vp, const uint8_t* frames_dev, int n, int w, int h, int stride, int64_t frame_stride,
-                 uint32_t qtot);
-void run_small(slideo_matcher* m, const uint8_t* imgs_dev, int n, int w, int h, int stride, int64_t img_stride, int& sw, int& sh, hipStream_t st);
+void unit_verify(slideo_matcher* m, Slot& S, const VerifyParams& vp, const DevFrames& f, int n, uint32_t qtot);
+void run_small(slideo_matcher* m, const DevFrames& imgs, int n, int& sw, int& sh, hipStream_t st);
 // ssd[i] = sum of squared differences of the small images a + i * a_stride and b + i * b_stride (`bytes` each), i < n
 void launch_ssd(const uint8_t* a, int64_t a_stride, const uint8_t* b, int64_t b_stride, int64_t bytes, unsigned long long* ssd, int n, hipStream_t st);
 
 // ---- stage_sift.hip -------------------------------------------------------------------------------
 void sift_check_cfg(const slideo_sift_config* sc, int w, int h);
-void unit_submit_sift(slideo_matcher* m, Slot& S, const uint8_t* frames_dev, int n, int w, int h, int stride, int64_t frame_stride);
-void add_pages_sift(slideo_matcher* m, Slot& S, int cnt, int w, int h, int stride, int64_t fb);
+void unit_submit_sift(slideo_matcher* m, Slot& S, const DevFrames& f, int n);
+void add_pages_sift(slideo_matcher* m, Slot& S, const DevFrames& pages, int cnt);
 
 }  // namespace slideo
 

@@ -95,9 +95,9 @@ static bool resize_generic_forced() { return env_long("SLIDEO_RESIZE_GENERIC", 0
 // `with_blur`: also materialise the WHOLE blurred pyramid (only the pyramid tap wants it)
 // the f32 blur of ocv.blur 0 / 1 cannot be evaluated per BRIEF sample in integer arithmetic: those variants always
 // materialise the blurred pyramid (blur_f32_kernel) and describe from it (describe_blurred_kernel)
-void orb_stage1(slideo_matcher* m, Slot& S, const uint8_t* frames_dev, int n, int w, int h, int stride, int64_t frame_stride,
-                bool with_blur, uint32_t kp_cap) {
+void orb_stage1(slideo_matcher* m, Slot& S, const DevFrames& f, int n, bool with_blur, uint32_t kp_cap) {
     hipStream_t st = S.st;
+    const int w = f.w, h = f.h;
     const bool full_blur = with_blur;
     with_blur = with_blur || blur_is_f32(m);
     GeomEntry& ge = geom_for(m, w, h);
@@ -120,10 +120,10 @@ void orb_stage1(slideo_matcher* m, Slot& S, const uint8_t* frames_dev, int n, in
     S.d_qofs.reserve((size_t)(n + 1) * 4); S.d_info.reserve(64);
     S.h_info.reserve(64);
 
-    const int aligned4 = ((uintptr_t)frames_dev % 4 == 0) && (stride % 4 == 0) && (frame_stride % 4 == 0);
+    const int aligned4 = ((uintptr_t)f.p % 4 == 0) && (f.stride % 4 == 0) && (f.frame_stride % 4 == 0);
     {
         dim3 grid(cdiv(cdiv(w, 4), 256), h, n);
-        gray_kernel<<<grid, 256, 0, st>>>(frames_dev, frame_stride, stride, S.d_pyr.as<uint8_t>(), g.frame_bytes, w, h,
+        gray_kernel<<<grid, 256, 0, st>>>(f.p, f.frame_stride, f.stride, S.d_pyr.as<uint8_t>(), g.frame_bytes, w, h,
                                           g.lv[0].pitch, aligned4, gray_coef(m));
         check_launch("gray_kernel");
     }
@@ -218,11 +218,10 @@ void orb_stage2(slideo_matcher* m, Slot& S, int w, int h, bool by_capacity) {
 }
 
 // synchronous ORB (page ingest, taps).  Leaves: d_qofs[n+1], d_kp[qtot], d_desc[qtot*32]; S.orb filled.
-void run_orb(slideo_matcher* m, Slot& S, const uint8_t* frames_dev, int n, int w, int h, int stride, int64_t frame_stride,
-             bool keep_host_qofs, bool with_blur) {
-    orb_stage1(m, S, frames_dev, n, w, h, stride, frame_stride, with_blur);
+void run_orb(slideo_matcher* m, Slot& S, const DevFrames& f, int n, bool keep_host_qofs, bool with_blur) {
+    orb_stage1(m, S, f, n, with_blur);
     orb_wait_info(m, S);
-    orb_stage2(m, S, w, h);
+    orb_stage2(m, S, f.w, f.h);
     if (keep_host_qofs) {
         S.orb.qofs.resize(n + 1);
         HIP_CHECK(hipMemcpyAsync(S.orb.qofs.data(), S.d_qofs.p, (size_t)(n + 1) * 4, hipMemcpyDeviceToHost, S.st));

@@ -239,11 +239,11 @@ static int64_t sift_unit_capacity(const slideo_matcher* m, int n) {
 // Hamming-format neighbour lists (l2_ratio_keys_kernel) -> the common verify stage.  The SIFT workspace belongs to the matcher,
 // so the extraction stages of consecutive units take turns (event chain); a unit's search (matrix cores, the slot's own list
 // buffers) and verify stages overlap the next unit's extraction.  The keypoint counts come back to the host inside sift_batch: the submit blocks for the extraction.
-void unit_submit_sift(slideo_matcher* m, Slot& S, const uint8_t* frames_dev, int n, int w, int h, int stride, int64_t frame_stride) {
+void unit_submit_sift(slideo_matcher* m, Slot& S, const DevFrames& f, int n) {
     const slideo_config& c = m->cfg;
     hipStream_t st = S.st;
     const bool prof = m->profiling;
-    S.timed = prof; S.u_frames = frames_dev; S.u_w = w; S.u_h = h; S.u_stride = stride; S.u_fs = frame_stride; S.u_async = false;
+    S.timed = prof; S.u_in = f; S.u_async = false;
     if (m->sift_ev_set) HIP_CHECK(hipStreamWaitEvent(st, m->sift_ev, 0));
     if (prof) HIP_CHECK(hipEventRecord(S.ev[0], st));
     std::vector<uint32_t> counts((size_t)std::max(n, 1), 0);
@@ -251,7 +251,7 @@ void unit_submit_sift(slideo_matcher* m, Slot& S, const uint8_t* frames_dev, int
     for (int attempt = 0; attempt < 2; ++attempt) {
         S.d_kp.reserve(std::max<size_t>((size_t)cap * sizeof(slideo_keypoint), 64));
         S.d_desc.reserve(std::max<size_t>((size_t)cap * 128, 128));
-        rows = sift_batch(m, frames_dev, n, w, h, stride, frame_stride, m->sift_cfg, 0, cap, S.d_kp.as<slideo_keypoint>(), S.d_desc.as<uint8_t>(),
+        rows = sift_batch(m, f.p, n, f.w, f.h, f.stride, f.frame_stride, m->sift_cfg, 0, cap, S.d_kp.as<slideo_keypoint>(), S.d_desc.as<uint8_t>(),
                           counts.data(), st);
         if (rows <= cap) break;
         cap = rows;                                                           // (nfeatures 0 on a very busy frame: once more with room)
@@ -296,19 +296,19 @@ void unit_submit_sift(slideo_matcher* m, Slot& S, const uint8_t* frames_dev, int
     // (the lists carry the outcome of the vote rule: l2_ratio_keys_kernel / l2_tol_keys_kernel)
     if (lowe) { vp.k = 2; vp.ratio = 1.f; }
     else { vp.k = kq; vp.ratio = 0.f; vp.tol = 1.5f; }
-    unit_verify(m, S, vp, frames_dev, n, w, h, stride, frame_stride, qtot);
+    unit_verify(m, S, vp, f, n, qtot);
 }
 
-// page ingest in SIFT mode: the staged pages (S.d_stage) -> S.d_kp / S.d_desc (128 B rows) / S.orb.qofs, as run_orb leaves them
-void add_pages_sift(slideo_matcher* m, Slot& S, int cnt, int w, int h, int stride, int64_t fb) {
-    sift_check_cfg(&m->sift_cfg, w, h);
+// page ingest in SIFT mode: the staged pages -> S.d_kp / S.d_desc (128 B rows) / S.orb.qofs, as run_orb leaves them
+void add_pages_sift(slideo_matcher* m, Slot& S, const DevFrames& pages, int cnt) {
+    sift_check_cfg(&m->sift_cfg, pages.w, pages.h);
     std::vector<uint32_t> counts((size_t)cnt, 0);
     int64_t cap = sift_unit_capacity(m, cnt), rows = 0;
     for (int attempt = 0; attempt < 2; ++attempt) {
         S.d_kp.reserve(std::max<size_t>((size_t)cap * sizeof(slideo_keypoint), 64));
         S.d_desc.reserve(std::max<size_t>((size_t)cap * 128, 128));
-        rows = sift_batch(m, S.d_stage.as<uint8_t>(), cnt, w, h, stride, fb, m->sift_cfg, 0, cap, S.d_kp.as<slideo_keypoint>(), S.d_desc.as<uint8_t>(),
-                          counts.data(), S.st);
+        rows = sift_batch(m, pages.p, cnt, pages.w, pages.h, pages.stride, pages.frame_stride, m->sift_cfg, 0, cap, S.d_kp.as<slideo_keypoint>(),
+                          S.d_desc.as<uint8_t>(), counts.data(), S.st);
         if (rows <= cap) break;
         cap = rows;
     }
@@ -367,19 +367,18 @@ int32_t slideo_sift_bgr8(slideo_matcher* m, const slideo_sift_config* cfg, const
     if (!m) return SLIDEO_ERR_INVALID_ARG;
     API_TRY
     if (!bgr || !n_out) fail(SLIDEO_ERR_INVALID_ARG, "null image/n_out");
-    validate_image(width, height, stride_bytes);
+    FrameSrc img = FrameSrc::image(bgr, width, height, stride_bytes);
+    validate_frames(img);
     sift_check_cfg(cfg, width, height);
     HIP_CHECK(hipSetDevice(m->device));
     require_idle(m);
     Slot& S = m->slots[0];
-    const size_t fb = (size_t)height * stride_bytes;
-    stage_for_upload(m, fb);
-    HIP_CHECK(hipMemcpyAsync(S.d_stage.p, bgr, fb, hipMemcpyHostToDevice, S.st));
+    const DevFrames f = stage_frames(m, S, img, 0, 1);
     const int64_t cap = std::max<int64_t>(capacity, 0);
     m->sift.kp.reserve(std::max<size_t>((size_t)cap * sizeof(slideo_keypoint), 64));
     m->sift.desc.reserve(std::max<size_t>((size_t)cap * 128, 128));
     uint32_t cnt = 0;
-    const int64_t rows = sift_batch(m, S.d_stage.as<uint8_t>(), 1, width, height, stride_bytes, (int64_t)fb, *cfg, 0, cap,
+    const int64_t rows = sift_batch(m, f.p, 1, f.w, f.h, f.stride, f.frame_stride, *cfg, 0, cap,
                                     m->sift.kp.as<slideo_keypoint>(), m->sift.desc.as<uint8_t>(), &cnt, S.st);
     *n_out = (int32_t)rows;
     if (rows > cap) fail(SLIDEO_ERR_CAPACITY, "image has %lld SIFT keypoints, capacity %d", (long long)rows, capacity);
@@ -396,17 +395,16 @@ int32_t slideo_sift_layer_bgr8(slideo_matcher* m, const slideo_sift_config* cfg,
     if (!m) return SLIDEO_ERR_INVALID_ARG;
     API_TRY
     if (!bgr || !out || !lw || !lh) fail(SLIDEO_ERR_INVALID_ARG, "null argument");
-    validate_image(width, height, stride_bytes);
+    FrameSrc img = FrameSrc::image(bgr, width, height, stride_bytes);
+    validate_frames(img);
     sift_check_cfg(cfg, width, height);
     HIP_CHECK(hipSetDevice(m->device));
     require_idle(m);
     Slot& S = m->slots[0];
     const SiftGeom g = sift_geom(width, height);
     if (octave < 0 || octave >= g.n_oct || layer < 0 || layer >= (dog ? SIFT_NL + 2 : SIFT_NL + 3)) fail(SLIDEO_ERR_INVALID_ARG, "no such pyramid layer");
-    const size_t fb = (size_t)height * stride_bytes;
-    stage_for_upload(m, fb);
-    HIP_CHECK(hipMemcpyAsync(S.d_stage.p, bgr, fb, hipMemcpyHostToDevice, S.st));
-    sift_pyramids(m, S.d_stage.as<uint8_t>(), 1, width, height, stride_bytes, (int64_t)fb, *cfg, g, S.st);
+    const DevFrames f = stage_frames(m, S, img, 0, 1);
+    sift_pyramids(m, f.p, 1, f.w, f.h, f.stride, f.frame_stride, *cfg, g, S.st);
     const int64_t lsz = (int64_t)g.ow[octave] * g.oh[octave];
     *lw = g.ow[octave]; *lh = g.oh[octave];
     if (lsz > out_capacity) fail(SLIDEO_ERR_CAPACITY, "layer has %lld values", (long long)lsz);

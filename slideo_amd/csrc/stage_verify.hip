@@ -19,16 +19,15 @@ VerifyParams make_vp(const slideo_config& c) {
 }
 
 // ---- to_small_image of n equally sized device images into m->d_small --------------------
-void run_small(slideo_matcher* m, const uint8_t* imgs_dev, int n, int w, int h, int stride, int64_t img_stride,
-               int& sw, int& sh, hipStream_t st) {
-    int ac = area_class_for(m, w, h);
+void run_small(slideo_matcher* m, const DevFrames& imgs, int n, int& sw, int& sh, hipStream_t st) {
+    int ac = area_class_for(m, imgs.w, imgs.h);
     upload_area(m);
     const AreaGeom& ag = m->area_geoms[ac];
     sw = ag.dw; sh = ag.dh;
     m->d_small.reserve((size_t)n * sw * sh * 3);
     int tiles = cdiv(sw, SM_TW) * cdiv(sh, SM_TH);
-    small_image_kernel<<<dim3(tiles, n), 256, 0, st>>>(ag, m->d_area_taps.as<AreaTap>(), m->d_area_idx.as<int32_t>(), imgs_dev,
-                                                       img_stride, stride, m->d_small.as<uint8_t>(), (int64_t)sw * sh * 3);
+    small_image_kernel<<<dim3(tiles, n), 256, 0, st>>>(ag, m->d_area_taps.as<AreaTap>(), m->d_area_idx.as<int32_t>(), imgs.p,
+                                                       imgs.frame_stride, imgs.stride, m->d_small.as<uint8_t>(), (int64_t)sw * sh * 3);
     check_launch("small_image_kernel");
 }
 
@@ -38,9 +37,8 @@ void launch_ssd(const uint8_t* a, int64_t a_stride, const uint8_t* b, int64_t b_
 }
 
 // Everything after the neighbour lists (S.d_keys, Hamming key format) of a unit: the per-page vote, RANSAC (similarity or
-// homography), rating, re-projection, verdicts, and the unit's one D2H copy.  `frames_dev`: the unit's frames (re-projection).
-void unit_verify(slideo_matcher* m, Slot& S, const VerifyParams& vp, const uint8_t* frames_dev, int n, int w, int h, int stride, int64_t frame_stride,
-                 uint32_t qtot) {
+// homography), rating, re-projection, verdicts, and the unit's one D2H copy.  `f`: the unit's frames (re-projection).
+void unit_verify(slideo_matcher* m, Slot& S, const VerifyParams& vp, const DevFrames& f, int n, uint32_t qtot) {
     const slideo_config& c = m->cfg;
     hipStream_t st = S.st;
     const bool prof = m->profiling;
@@ -132,7 +130,7 @@ void unit_verify(slideo_matcher* m, Slot& S, const VerifyParams& vp, const uint8
             any_vt |= vt; any_win |= !vt;
         }
         const dim3 rgrid(max_tile_rows, std::min(n, 65535));
-#define SLIDEO_RP_TAIL m->d_page_small.as<uint8_t>(), frames_dev, frame_stride, stride, w, h, S.d_fcs.as<FrameCands>(), pair_list, pair_count
+#define SLIDEO_RP_TAIL m->d_page_small.as<uint8_t>(), f.p, f.frame_stride, f.stride, f.w, f.h, S.d_fcs.as<FrameCands>(), pair_list, pair_count
 #define SLIDEO_RP_ARGS m->d_area_geoms.as<AreaGeom>(), m->d_area_taps.as<AreaTap>(), m->d_area_idx.as<int32_t>(), SLIDEO_RP_TAIL
 #define SLIDEO_VT_ARGS m->d_area_geoms.as<AreaGeom>(), m->d_area_taps.as<AreaTap>(), m->d_area_idx.as<int32_t>(), m->d_area_recs.as<AreaRec>(), SLIDEO_RP_TAIL
         if (any_vt) {

@@ -217,6 +217,21 @@ def test_errors(capi, cfg0_data):
     m.changed_mask(bgr)
     m.match_frames_yuv420(yuv, w, h, L)
     assert code(lambda: m.match_kept_frames([0]))[0] == 4
+    # device-resident 4:2:0 frames are converted into a slot's staging buffer as well (match and submit); device-resident BGR
+    # frames are read where they are, and the kept frames stay usable
+    import torch
+    d_yuv, d_bgr = torch.from_numpy(yuv).cuda(), torch.from_numpy(bgr).cuda()
+    m.changed_mask(bgr)
+    m.match_frames_yuv420_dev(d_yuv.data_ptr(), len(yuv), w, h, L, yuv.shape[1])
+    assert code(lambda: m.match_kept_frames([0]))[0] == 4
+    m.changed_mask(bgr)
+    m.collect(m.submit_yuv420_dev(d_yuv.data_ptr(), len(yuv), w, h, L, yuv.shape[1]))
+    assert code(lambda: m.match_kept_frames([0]))[0] == 4
+    m.changed_mask(bgr)
+    want_kept = m.match_kept_frames([0, 1])
+    m.changed_mask(bgr)
+    m.match_frames_dev(d_bgr.data_ptr(), len(bgr), w, h)
+    assert _same(m.match_kept_frames([0, 1]), want_kept)
     m.close()
 
 
