@@ -377,6 +377,34 @@ int32_t     slideo_host_unregister(void* ptr);
 int32_t     slideo_matcher_set_progress(slideo_matcher* m, slideo_progress_fn fn, void* user);
 
 
+/* ---- page sets (extension: the reference has no counterpart; its README advises one invocation per PDF instead) ------------
+ * A page set S is a non-empty set of deck page indices of a finalized matcher.  A frame call made while S is selected searches
+ * S's pages only, and every result — slideo_verdict (page, similarity, inliers, keypoints) and the slideo_last_frame_candidates
+ * trace (votes, inliers, survived, similarity, transform) — equals, bit for bit, what a REFERENCE SUB-MATCHER returns for the
+ * same frames: a matcher of the same config built from exactly S's pages in ascending deck order (slideo_matcher_add_page_features
+ * with this matcher's slideo_matcher_get_page_features / slideo_matcher_get_page_small output), its page index j mapped to the
+ * j-th smallest index of S.  (Keys carry deck row ids, which keep the sub-matcher's row order; candidates tie by ascending page,
+ * which the map keeps; duplicate rows are chained within S only, so a descriptor shared with an unselected page votes for the
+ * selected one alone.)  A set is a second search operand plus a second duplicate chain, built on the device from the finalized
+ * deck in a few launches (csrc/stage_page_set.hip); the deck's pages, keypoints and small images are shared.
+ * Set 0 is the whole deck and the default: a matcher that never selects a set behaves as before.  The selection is state of the
+ * matcher that every frame call reads (BGR and YUV 4:2:0, host and device, sync and submit / collect, slideo_match_kept_frames).
+ * Sets cover the exact Hamming search (matcher 0) with engines 0 / 2 / 3; LSH (matcher 1), slideo_matcher_use_sift and the VALU
+ * engine (set_knn_engine(1)) are refused with SLIDEO_ERR_UNSUPPORTED at slideo_matcher_use_page_set or at the first frame call
+ * under a set, whichever comes first (slideo_matcher_create_page_set refuses LSH and SIFT matchers too).
+ * Status: SLIDEO_ERR_STATE before finalize; SLIDEO_ERR_INVALID_ARG for n_pages < 1, an index out of range or listed twice, an
+ * unknown set id (and set 0 in release); SLIDEO_ERR_EMPTY_INDEX when the selected pages hold no descriptor; SLIDEO_ERR_STATE for
+ * releasing the selected set or a set an uncollected unit searches; SLIDEO_ERR_UNSUPPORTED beyond 64 live sets. */
+/* After finalize.  pages: n_pages distinct deck indices, any order.  *set_out >= 1 (ids are not reused). */
+int32_t     slideo_matcher_create_page_set(slideo_matcher* m, int32_t n_pages, const int32_t* pages, int32_t* set_out);
+/* Units submitted from now on search `set` (0 = whole deck).  Units already in flight keep theirs. */
+int32_t     slideo_matcher_use_page_set(slideo_matcher* m, int32_t set);
+int32_t     slideo_matcher_release_page_set(slideo_matcher* m, int32_t set);
+/* Selected pages, their descriptor rows, the distinct rows among them (what the search streams), device bytes the set's operand
+ * and chain hold.  Set 0: the deck's.  Any output may be NULL. */
+int32_t     slideo_matcher_page_set_info(const slideo_matcher* m, int32_t set, int32_t* n_pages, int64_t* rows, int64_t* unique_rows,
+                                         int64_t* bytes);
+
 /* ---- measurement ---------------------------------------------------------- */
 
 /* Stage timing with HIP events recorded on the stream the kernels are launched
@@ -571,6 +599,10 @@ int32_t     slideo_group_changed_mask_bgr8(slideo_group* g, int32_t n_frames, co
                                            int32_t stride_bytes, int64_t frame_stride_bytes, const uint8_t* prev_small,
                                            uint8_t* last_small_out, uint8_t* changed_out, float* similarity_out);
 int32_t     slideo_group_match_kept_frames(slideo_group* g, int32_t n_sel, const int32_t* sel, slideo_verdict* verdicts_out);
+/* Page sets on every member (the members hand out identical ids); results equal a single matcher's under the same set. */
+int32_t     slideo_group_create_page_set(slideo_group* g, int32_t n_pages, const int32_t* pages, int32_t* set_out);
+int32_t     slideo_group_use_page_set(slideo_group* g, int32_t set);
+int32_t     slideo_group_release_page_set(slideo_group* g, int32_t set);
 
 /* ---- YUV 4:2:0 frames ----------------------------------------------------------------------------------------------
  * Video decoders (VCN, FFmpeg's software H.264 / HEVC decoders, VA-API) hand out YUV 4:2:0 — NV12, or planar I420 — not BGR.

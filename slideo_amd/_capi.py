@@ -128,6 +128,8 @@ EXPORTS = [
     "slideo_group_last_frame_candidates", "slideo_group_changed_mask_bgr8", "slideo_group_match_kept_frames",
     "slideo_yuv420_layout_packed", "slideo_match_frames_yuv420", "slideo_match_frames_yuv420_dev", "slideo_match_frames_submit_yuv420_dev",
     "slideo_changed_mask_yuv420", "slideo_yuv420_to_bgr8", "slideo_group_match_frames_yuv420", "slideo_group_changed_mask_yuv420",
+    "slideo_matcher_create_page_set", "slideo_matcher_use_page_set", "slideo_matcher_release_page_set", "slideo_matcher_page_set_info",
+    "slideo_group_create_page_set", "slideo_group_use_page_set", "slideo_group_release_page_set",
 ]
 
 _lib = None
@@ -255,10 +257,49 @@ class _FrameCalls:
         self._call("match_kept_frames", len(sel), _p(sel), _p(out))
         return out
 
+    # page sets (include/slideo_amd.h "page sets"): frame calls made while a set is selected search its pages only.  The argument
+    # rules the library checks are checked here first, so that a bad call fails the same way before any device is involved.
+    _SETS = None        # symbol prefix of the set calls: "slideo_matcher_" / "slideo_group_"
+
+    def create_page_set(self, pages):
+        """pages: distinct deck page indices (any order) -> the set's id (>= 1)."""
+        arr = _page_set_pages(pages)
+        out = C.c_int32()
+        self._check(getattr(lib(), self._SETS + "create_page_set")(self._h, len(arr), _p(arr), C.byref(out)))
+        return int(out.value)
+
+    def use_page_set(self, set_id):
+        """Frame calls from now on search `set_id` (0 = the whole deck); units already in flight keep theirs."""
+        self._check(getattr(lib(), self._SETS + "use_page_set")(self._h, _page_set_id(set_id, 0)))
+
+    def release_page_set(self, set_id):
+        self._check(getattr(lib(), self._SETS + "release_page_set")(self._h, _page_set_id(set_id, 1)))
+
+
+def _page_set_pages(pages):
+    """A page set's index list as int32, with the library's argument rules (SLIDEO_ERR_INVALID_ARG) applied on the host."""
+    arr = np.asarray(list(pages) if not isinstance(pages, np.ndarray) else pages).reshape(-1)
+    if arr.size < 1:
+        raise SlideoError(1, "a page set needs at least one page")
+    if arr.dtype.kind not in "iu":
+        raise SlideoError(1, "page indices must be integers (got %s)" % arr.dtype)
+    if (arr < 0).any() or (arr > np.iinfo(np.int32).max).any():
+        raise SlideoError(1, "page index %d out of range" % int(arr[(arr < 0) | (arr > np.iinfo(np.int32).max)][0]))
+    if len(np.unique(arr)) != arr.size:
+        raise SlideoError(1, "a page is listed twice")
+    return np.ascontiguousarray(arr, np.int32)
+
+
+def _page_set_id(set_id, lowest):
+    if isinstance(set_id, bool) or not isinstance(set_id, (int, np.integer)) or not lowest <= int(set_id) <= np.iinfo(np.int32).max:
+        raise SlideoError(1, "page set id %r is not one the library hands out" % (set_id,))
+    return int(set_id)
+
 
 class Matcher(_FrameCalls):
     """Owns one slideo_matcher handle (page database + workspace on one GPU)."""
     _PREFIX = "slideo_"
+    _SETS = "slideo_matcher_"
 
     def __init__(self, cfg=None, device=0):
         self.cfg = cfg if cfg is not None else default_config()
@@ -301,6 +342,13 @@ class Matcher(_FrameCalls):
         h = (C.c_int32 * n)(*[p.shape[0] for p in pages])
         s = (C.c_int32 * n)(*[p.shape[1] * 3 for p in pages])
         self._check(lib().slideo_matcher_add_pages_bgr8(self._h, n, ptrs, w, h, s))
+
+    def page_set_info(self, set_id):
+        """-> {n_pages, rows, unique_rows, bytes} of set `set_id` (0: the whole deck)."""
+        n, rows, urows, nbytes = C.c_int32(), C.c_int64(), C.c_int64(), C.c_int64()
+        self._check(lib().slideo_matcher_page_set_info(self._h, _page_set_id(set_id, 0), C.byref(n), C.byref(rows), C.byref(urows),
+                                                       C.byref(nbytes)))
+        return {"n_pages": n.value, "rows": rows.value, "unique_rows": urows.value, "bytes": nbytes.value}
 
     def page_small(self, page):
         """Small image of a page (to_small_image), as slideo_matcher_get_page_small returns it."""
@@ -544,6 +592,7 @@ class Group(_FrameCalls):
     a call's pages and frames sharded contiguously over the devices, verdicts gathered into one host array.  Results equal
     a single Matcher's bit for bit.  `devices`: HIP ordinals (may repeat); None or empty = every gfx950 device of the node."""
     _PREFIX = "slideo_group_"
+    _SETS = "slideo_group_"
 
     def __init__(self, cfg=None, devices=None):
         self.cfg = cfg if cfg is not None else default_config()
@@ -616,6 +665,10 @@ class Group(_FrameCalls):
     @property
     def descriptor_count(self):
         return int(lib().slideo_group_descriptor_count(self._h))
+
+    def page_set_info(self, set_id):
+        """Member 0's record of set `set_id` (every member holds the same set)."""
+        return self.member(0).page_set_info(set_id)
 
 
 def device_count():

@@ -245,6 +245,41 @@ int32_t slideo_group_use_sift(slideo_group* g, const slideo_sift_config* cfg, fl
     GROUP_CATCH(g)
 }
 
+// Page sets: every member builds the same set from the same deck (ids are handed out in the same order: they agree)
+int32_t slideo_group_create_page_set(slideo_group* g, int32_t n_pages, const int32_t* pages, int32_t* set_out) {
+    if (!g) return SLIDEO_ERR_INVALID_ARG;
+    GROUP_TRY
+    if (!set_out) fail(SLIDEO_ERR_INVALID_ARG, "null set_out");
+    std::vector<int32_t> ids;
+    try {
+        for (slideo_matcher* m : g->members) {
+            int32_t id = 0;
+            check_member_call(m, slideo_matcher_create_page_set(m, n_pages, pages, &id));
+            ids.push_back(id);
+            if (id != ids[0]) fail(SLIDEO_ERR_STATE, "members handed out page set ids %d and %d (sets made on a member directly)", ids[0], id);
+        }
+    } catch (...) {
+        for (size_t r = 0; r < ids.size(); ++r) (void)slideo_matcher_release_page_set(g->members[r], ids[r]);
+        throw;
+    }
+    *set_out = ids[0];
+    GROUP_CATCH(g)
+}
+
+int32_t slideo_group_use_page_set(slideo_group* g, int32_t set) {
+    if (!g) return SLIDEO_ERR_INVALID_ARG;
+    GROUP_TRY
+    for (slideo_matcher* m : g->members) check_member_call(m, slideo_matcher_use_page_set(m, set));
+    GROUP_CATCH(g)
+}
+
+int32_t slideo_group_release_page_set(slideo_group* g, int32_t set) {
+    if (!g) return SLIDEO_ERR_INVALID_ARG;
+    GROUP_TRY
+    for (slideo_matcher* m : g->members) check_member_call(m, slideo_matcher_release_page_set(m, set));
+    GROUP_CATCH(g)
+}
+
 int32_t slideo_group_add_pages_bgr8(slideo_group* g, int32_t n_pages, const uint8_t* const* data, const int32_t* width,
                                     const int32_t* height, const int32_t* stride_bytes) {
     if (!g) return SLIDEO_ERR_INVALID_ARG;

@@ -136,6 +136,7 @@ void validate_frames(FrameSrc& src, slideo_matcher* m, int n, const void* out) {
     }
     validate_image(src.w, src.h, src.stride);
     if (m && m->sift_on) sift_check_cfg(&m->sift_cfg, src.w, src.h);          // (the doubled image's coordinates travel in 13 bits)
+    if (m && m->cur_set != 0) page_set_check_mode(m);                          // (a mode switched on after slideo_matcher_use_page_set)
     if (m && !src.yuv && src.frame_stride < (int64_t)src.h * src.stride) fail(SLIDEO_ERR_INVALID_ARG, "frame_stride smaller than one frame");
     src.pinned = !src.on_device && src.p && host_is_pinned(src.p);
 }
@@ -202,6 +203,8 @@ uint32_t kp_cap_for(const slideo_matcher* m, const PyrGeom& g) {
 void unit_submit(slideo_matcher* m, Slot& S, const DevFrames& f, int n, bool allow_async) {
     // (does this unit share the chip with others?  the search then runs one block per CU: stage_knn.hip share_pad)
     { bool others = m->units_pending; for (const Slot& o : m->slots) others |= (&o != &S && o.busy); S.u_shared = others; }
+    if (!S.u_rerun) S.u_set = m->cur_set;          // (a re-run of an overflowed unit searches the set it was submitted with)
+    S.u_rerun = false;
     if (m->sift_on) { unit_submit_sift(m, S, f, n); return; }
     const slideo_config& c = m->cfg;
     hipStream_t st = S.st;
@@ -229,7 +232,7 @@ void unit_submit(slideo_matcher* m, Slot& S, const DevFrames& f, int n, bool all
         qtot = qplan = S.orb.qtot;
     }
     // all workspace before the timed kNN interval
-    S.u_nt = knn_unit_rows(m, (int)qplan);
+    S.u_nt = knn_unit_rows(m, (int)qplan, S.u_set);
     // the search's block shape while units share the chip (stage_knn.hip knn_shape): how much search there is per pixel of ORB work
     S.u_w12 = m->knn_w12_ratio > 0.0 && (double)qplan * (double)S.u_nt >= m->knn_w12_ratio * (double)n * (double)f.w * (double)f.h;
     knn_reserve_unit(m, S, qplan, qtot);
@@ -265,6 +268,7 @@ void unit_collect(slideo_matcher* m, Slot& S, slideo_verdict* out_host) {
         if (fl & 8u) {
             // a frame had more keypoints than the capacity-sized path provides for (ties at a retainBest threshold are kept, as
             // in OpenCV): the whole unit again, through the exact-size path
+            S.u_rerun = true;
             unit_submit(m, S, S.u_in, n, false);
             unit_collect(m, S, out_host);
             return;
@@ -280,6 +284,7 @@ void unit_collect(slideo_matcher* m, Slot& S, slideo_verdict* out_host) {
         if (m->rng_len >= cap) fail(SLIDEO_ERR_CAPACITY, "RANSAC sample schedule exceeded %u pre-drawn RNG outputs", m->rng_len);
         HIP_CHECK(hipDeviceSynchronize());
         upload_rng_stream(m, (uint32_t)std::min<uint64_t>((uint64_t)m->rng_len * 4, cap));
+        S.u_rerun = true;
         unit_submit(m, S, S.u_in, n, false);
         unit_collect(m, S, out_host);
         return;

@@ -5,6 +5,7 @@
 //   stage_knn.hip      index build + k-NN stage   (kernels: knn.hip.h, knn_tile.hip.h, knn_l2.hip.h, knn_lsh.hip.h)
 //   stage_verify.hip   vote .. verdict, small img (kernels: verify.hip.h, homography.hip.h)
 //   stage_sift.hip     SIFT stage + entry points  (kernels: sift.hip.h)
+//   stage_page_set.hip page sets: a subset's search operand built from the finalized deck (kernels: page_set.hip.h)
 //   capi_taps.hip      debug taps of the parity tests
 //   capi_group.cpp     the N-device group (slideo_group_*)
 //
@@ -16,6 +17,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <map>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -103,6 +105,8 @@ struct Slot {
     hipEvent_t ev_in = nullptr, ev_orb = nullptr, ev_up = nullptr;
     // arguments of the unit in flight (re-run through the exact-size path if the capacity-sized one overflowed)
     DevFrames u_in; bool u_async = false; int u_nt = 0; bool u_shared = false, u_w12 = false;
+    int u_set = 0;             // the page set the unit searches (0 = the whole deck), taken from the matcher at submission
+    bool u_rerun = false;      // (unit_collect's re-runs: the unit keeps its set)
     DevBuf d_stage, d_pyr, d_blur, d_cand, d_hist, d_candcount, d_flags, d_thr, d_lvlofs, d_kpcount, d_qofs, d_info;
     DevBuf d_items, d_kp, d_desc, d_keys, d_knn_pend, d_votes, d_gpts, d_gmask, d_fcs, d_verdicts, d_pairs, d_blurmask, d_qkeys, d_tail, d_refine;
     DevBuf d_yuv;              // host YUV 4:2:0 frames of the unit, converted into d_stage (reserved by the first YUV call only)
@@ -131,6 +135,17 @@ struct Slot {
         h_info.reserve_cap(o.h_info.cap); h_out.reserve_cap(o.h_out.cap);
     }
 };
+
+// A page set (slideo_matcher_create_page_set): the search operand and duplicate chain of a subset of the finalized deck's pages,
+// built on the device (stage_page_set.hip).  Keys carry deck row ids, so everything downstream of the search is the deck's.
+struct PageSet {
+    int n_pages = 0;
+    int64_t rows = 0, urows = 0;                  // the selected pages' rows, the distinct rows among them (what the search streams)
+    DevBuf d_trainb, d_side, d_nminh, d_perm;     // the operand in the layout of prepare_train_bits (knn_tile.hip.h)
+    DevBuf d_grp_next;                            // [M] the chain of the selected rows of each duplicate group (-1 elsewhere)
+    size_t bytes() const { return d_trainb.cap + d_side.cap + d_nminh.cap + d_perm.cap + d_grp_next.cap; }
+};
+constexpr int MAX_PAGE_SETS = 64;                 // live sets per matcher
 
 }  // namespace slideo
 
@@ -174,6 +189,12 @@ struct slideo_matcher {
     // train-set de-duplication (knn.hip.h knn_expand_dups_kernel): the matrix-core engine searches the Mu unique rows, keys carry
     // the lowest original row of a group, d_grp_next chains the equal rows.  SLIDEO_KNN_DEDUP=0 searches all M rows.
     slideo::DevBuf d_utrain, d_grp_next;
+    // page sets: what finalize computed on the host for them (the distinct rows' head rows — empty: the identity — and their norm
+    // order before the tile shuffle), uploaded by the first slideo_matcher_create_page_set; the live sets by id; the selected one
+    std::vector<int32_t> h_urow, h_uorder;
+    slideo::DevBuf d_urow, d_uorder;
+    std::map<int, std::unique_ptr<slideo::PageSet>> page_sets;
+    int cur_set = 0, next_set_id = 1;
     struct LshSet { slideo::DevBuf ofs, rows, keys; slideo::LshDev dev{}; bool ready = false; } lsh;      // slideo_config.matcher 1 (knn_lsh.hip.h)
     int64_t Mu = -1;
     int knn_dedup = 1;
@@ -284,7 +305,12 @@ void knn_build_index(slideo_matcher* m, const std::vector<uint8_t>& train, int64
 void knn_reserve_unit(slideo_matcher* m, Slot& S, uint32_t qplan, uint32_t qtot);
 void unit_knn(slideo_matcher* m, Slot& S, int n, uint32_t qplan, uint32_t qtot, bool async, bool prof);
 bool knn_unit_is_valu(const slideo_matcher* m, int nq);
-int knn_unit_rows(const slideo_matcher* m, int nq);        // train rows a unit's search evaluates (Mu, or M for the VALU engine)
+int knn_unit_rows(const slideo_matcher* m, int nq, int set = 0);   // train rows a unit's search evaluates (Mu, or M for the VALU engine; a page set's distinct rows)
+// the {0,1} FP4 expansion of the operand rows perm[0 .. nt_pad) of t (knn_tile.hip.h knn_tile_expand_kernel)
+void knn_expand_operand(const uint32_t* t, int nt, int nt_pad, const int32_t* perm, uint4* tx, hipStream_t st);
+int knn_operand_rows(int nt);                              // nt padded to whole super-tiles
+struct OperandLayout { int st_rows, side_u32; float pad_norm; };   // the side array's shape (knn_tile.hip.h KT_ST_ROWS, KT_SIDE_U32, KT_PAD_NORM)
+OperandLayout knn_operand_layout();
 void l2_prepare(slideo_matcher::L2Set& L, const uint8_t* t, int nt, hipStream_t st);
 void l2_query(slideo_matcher* m, slideo_matcher::L2Set& L, const uint8_t* q_dev, int nq, int k, hipStream_t st, Slot& S, bool timed,
               DevBuf* keys = nullptr, DevBuf* pend = nullptr, float prune_tol = 0.f);
@@ -298,6 +324,14 @@ void unit_verify(slideo_matcher* m, Slot& S, const VerifyParams& vp, const DevFr
 void run_small(slideo_matcher* m, const DevFrames& imgs, int n, int& sw, int& sh, hipStream_t st);
 // ssd[i] = sum of squared differences of the small images a + i * a_stride and b + i * b_stride (`bytes` each), i < n
 void launch_ssd(const uint8_t* a, int64_t a_stride, const uint8_t* b, int64_t b_stride, int64_t bytes, unsigned long long* ssd, int n, hipStream_t st);
+
+// ---- stage_page_set.hip ---------------------------------------------------------------------------
+// the set's operand from pages[0 .. n) (validated: distinct, in range) on m->stream; the set's id
+int page_set_create(slideo_matcher* m, int n, const int32_t* pages);
+// a unit's page set (nullptr: the whole deck)
+const PageSet* page_set_of(const slideo_matcher* m, int set);
+// the frame modes a page set does not cover (SLIDEO_ERR_UNSUPPORTED): checked by use_page_set and by every frame call under a set
+void page_set_check_mode(const slideo_matcher* m);
 
 // ---- stage_sift.hip -------------------------------------------------------------------------------
 void sift_check_cfg(const slideo_sift_config* sc, int w, int h);

@@ -11,13 +11,22 @@ namespace slideo {
 
 // ---- exact Hamming kNN: keys into S.d_keys[0 .. nq*KLIST) ------------------------------
 static int knn_pad_rows(int nt) { return cdiv(std::max(nt, 1), KT_ST_ROWS) * KT_ST_ROWS; }
+int knn_operand_rows(int nt) { return knn_pad_rows(nt); }
+OperandLayout knn_operand_layout() { return OperandLayout{KT_ST_ROWS, KT_SIDE_U32, KT_PAD_NORM}; }
+
+void knn_expand_operand(const uint32_t* t, int nt, int nt_pad, const int32_t* perm, uint4* tx, hipStream_t st) {
+    knn_tile_expand_kernel<<<cdiv(nt_pad * 8, 256), 256, 0, st>>>(t, nt, nt_pad, perm, tx);
+    check_launch("knn_tile_expand_kernel");
+}
 
 // Operand of the {0,1} x {0,1} engine (knn_tile.hip.h): rows in ascending popcount order (stable counting sort on the host:
 // nt x 32 bytes of popcounts), expanded to tile-major FP4 on the device, plus per super-tile the rows' norms and original
 // indices and per tile half its smallest norm.  `t_host`: the packed rows in host memory.
 struct TrainBits { DevBuf *tx, *side, *nminh, *perm; };
-// rowid (may be null): the row number a key carries for row i of t_host / t_dev (de-duplicated sets: the lowest original row)
-static void prepare_train_bits(const uint8_t* t_host, const uint32_t* t_dev, int nt, TrainBits o, hipStream_t st, const int32_t* rowid = nullptr) {
+// rowid (may be null): the row number a key carries for row i of t_host / t_dev (de-duplicated sets: the lowest original row).
+// norm_order (may be null): receives the nt rows' norm order before the tile shuffle (what a page set compacts, stage_page_set.hip)
+static void prepare_train_bits(const uint8_t* t_host, const uint32_t* t_dev, int nt, TrainBits o, hipStream_t st, const int32_t* rowid = nullptr,
+                               std::vector<int32_t>* norm_order = nullptr) {
     const int nt_pad = knn_pad_rows(nt), n_st = nt_pad / KT_ST_ROWS;
     std::vector<uint16_t> norm((size_t)std::max(nt, 1));
     uint32_t hist[258] = {0};
@@ -30,6 +39,7 @@ static void prepare_train_bits(const uint8_t* t_host, const uint32_t* t_dev, int
     for (int i = 0; i < 257; ++i) hist[i + 1] += hist[i];
     std::vector<int32_t> perm((size_t)nt_pad, -1);
     for (int i = 0; i < nt; ++i) perm[hist[norm[i]]++] = i;             // stable: ties keep row order
+    if (norm_order) norm_order->assign(perm.begin(), perm.begin() + nt);
     {
         // The 32-row TILES (each of one norm, which is all the fast path needs) are then put in a fixed pseudo-random order.
         // Streaming them in norm order is adversarial for the running thresholds: E[d] = |q| + |t| (1 - |q| / 128), so for every
@@ -244,12 +254,19 @@ static void run_knn(slideo_matcher* m, Slot& S, const uint32_t* q_dev, int nq, c
 
 bool knn_unit_is_valu(const slideo_matcher* m, int nq) { return knn_engine_for(m, nq) == 1; }
 
-// (the matrix-core engine searches the unique rows of the train set, the VALU engine — A/B only — all of them)
-static bool knn_unit_dedup(const slideo_matcher* m, int nq) { return m->Mu < m->M && knn_engine_for(m, nq) != 1; }
-int knn_unit_rows(const slideo_matcher* m, int nq) { return (int)(knn_unit_dedup(m, nq) ? m->Mu : m->M); }
+// (the matrix-core engine searches the unique rows of the train set, the VALU engine — A/B only — all of them; a page set — never
+// under the VALU engine, page_set_check_mode — its own distinct rows)
+static bool knn_unit_dedup(const slideo_matcher* m, int nq, int set = 0) {
+    if (const PageSet* ps = page_set_of(m, set)) return ps->urows < ps->rows;
+    return m->Mu < m->M && knn_engine_for(m, nq) != 1;
+}
+int knn_unit_rows(const slideo_matcher* m, int nq, int set) {
+    if (const PageSet* ps = page_set_of(m, set)) return (int)ps->urows;
+    return (int)(knn_unit_dedup(m, nq) ? m->Mu : m->M);
+}
 
 void knn_reserve_unit(slideo_matcher* m, Slot& S, uint32_t qplan, uint32_t qtot) {
-    knn_reserve(m, S, (int)qplan, knn_unit_rows(m, (int)qplan), (int)qtot);
+    knn_reserve(m, S, (int)qplan, knn_unit_rows(m, (int)qplan, S.u_set), (int)qtot);
 }
 
 // A unit's search: S.d_desc (n frames' descriptors, offsets S.d_qofs) -> S.d_keys.  async: the real query count lives on the
@@ -257,13 +274,15 @@ void knn_reserve_unit(slideo_matcher* m, Slot& S, uint32_t qplan, uint32_t qtot)
 void unit_knn(slideo_matcher* m, Slot& S, int n, uint32_t qplan, uint32_t qtot, bool async, bool prof) {
     const slideo_config& c = m->cfg;
     hipStream_t st = S.st;
-    const bool dedup = knn_unit_dedup(m, (int)qplan);
-    const int nt_knn = knn_unit_rows(m, (int)qplan);
+    const PageSet* ps = page_set_of(m, S.u_set);            // (the unit's page set: its operand and chain instead of the deck's)
+    const bool dedup = knn_unit_dedup(m, (int)qplan, S.u_set);
+    const int nt_knn = knn_unit_rows(m, (int)qplan, S.u_set);
     // a neighbour counts iff d < best * vote_tolerance (verify.hip.h vote_kernel); with tolerance < 1 rows below the
     // current best must still be kept, hence max(tol, 1)
     // (the ratio test needs the exact two nearest rows: exact lists)
     const float prune = (m->knn_exact_lists || m->cfg.ratio_test > 0.f) ? 0.f : std::max(m->cfg.vote_tolerance, 1.0f);
-    const TrainOps T{m->d_train.as<uint32_t>(), m->d_trainb.as<uint4>(), m->d_train_side.as<uint32_t>(), m->d_train_nminh.as<float4>()};
+    const TrainOps T = ps ? TrainOps{nullptr, ps->d_trainb.as<uint4>(), ps->d_side.as<uint32_t>(), ps->d_nminh.as<float4>()}
+                          : TrainOps{m->d_train.as<uint32_t>(), m->d_trainb.as<uint4>(), m->d_train_side.as<uint32_t>(), m->d_train_nminh.as<float4>()};
     if (c.matcher == 1 && (m->lsh_gather || knn_engine_for(m, (int)qplan) == 1)) {
         // the reference's index, gathered: only the LSH candidates of a query are scored (knn_lsh.hip.h); same key lists out
         knn_lsh_kernel<KLIST><<<cdiv((int)std::max(qtot, 1u), 4), 256, 0, st>>>(m->lsh.dev, S.d_desc.as<uint32_t>(), (int)qtot, m->d_train.as<uint32_t>(),
@@ -291,7 +310,7 @@ void unit_knn(slideo_matcher* m, Slot& S, int n, uint32_t qplan, uint32_t qtot, 
     if (prof) HIP_CHECK(hipEventRecord(S.ev[2], st));      // the kNN interval ends here: the search kernel (+ its segment merge)
     if (dedup) {
         knn_expand_dups_kernel<KLIST><<<cdiv((int)std::max(qtot, 1u), KNN_BLOCK), KNN_BLOCK, 0, st>>>(
-            S.d_keys.as<uint32_t>(), (int)qtot, m->d_grp_next.as<int32_t>(), async ? S.d_qofs.as<uint32_t>() + n : nullptr);
+            S.d_keys.as<uint32_t>(), (int)qtot, (ps ? ps->d_grp_next : m->d_grp_next).as<int32_t>(), async ? S.d_qofs.as<uint32_t>() + n : nullptr);
         check_launch("knn_expand_dups_kernel");
     }
 }
@@ -327,9 +346,12 @@ void knn_build_index(slideo_matcher* m, const std::vector<uint8_t>& train, int64
         m->d_utrain.reserve(utrain.size() + 64);
         HIP_CHECK(hipMemcpy(m->d_utrain.p, utrain.data(), utrain.size(), hipMemcpyHostToDevice));
         prepare_train_bits(utrain.data(), m->d_utrain.as<uint32_t>(), (int)m->Mu, TrainBits{&m->d_trainb, &m->d_train_side, &m->d_train_nminh, &m->d_train_perm},
-                           m->stream, urow.data());
+                           m->stream, urow.data(), &m->h_uorder);
+        m->h_urow.swap(urow);                                              // (page sets: distinct row -> its head row)
     } else {
-        prepare_train_bits(train.data(), m->d_train.as<uint32_t>(), (int)M, TrainBits{&m->d_trainb, &m->d_train_side, &m->d_train_nminh, &m->d_train_perm}, m->stream);
+        prepare_train_bits(train.data(), m->d_train.as<uint32_t>(), (int)M, TrainBits{&m->d_trainb, &m->d_train_side, &m->d_train_nminh, &m->d_train_perm}, m->stream,
+                           nullptr, &m->h_uorder);
+        m->h_urow.clear();                                                 // (every row is its own head)
     }
     HIP_CHECK(hipStreamSynchronize(m->stream));
 }

@@ -150,11 +150,25 @@ def sampled_frames(video, interval_s=5.0):
 class HipVideoMatcherTask:
     """OpenCVVideoMatcherTask (lib.rs:161-246)."""
 
-    def __init__(self, matcher, images, video, progress_reporter, batch=None):
+    def __init__(self, matcher, images, video, progress_reporter, batch=None, pages=None):
         self._m, self._images, self._video, self._rep = matcher, images, video, progress_reporter
         self._batch = batch or 64 * len(getattr(matcher, "devices", [0]))       # one shard of 64 sampled frames per device and call
+        self._pages = pages          # deck indices of the images this task matches against (None: all of them)
 
     def process(self) -> List[Matching]:
+        if self._pages is None:
+            return self._process()
+        # a page set of the task's images for the task's frame calls (include/slideo_amd.h "page sets"), released afterwards
+        m = self._m
+        set_id = m.create_page_set(self._pages)
+        try:
+            m.use_page_set(set_id)
+            return self._process()
+        finally:
+            m.use_page_set(0)
+            m.release_page_set(set_id)
+
+    def _process(self) -> List[Matching]:
         video, m = self._video, self._m
         interval = 5.0
         total_time, total_frames = video.total_time(), video.total_frames()
@@ -229,11 +243,29 @@ class HipVideoMatcher:
     def __init__(self, matcher, images):
         self._m, self._images = matcher, images
 
-    def match_images_with_video(self, video_path, progress_reporter: ProgressReporter) -> HipVideoMatcherTask:
+    def match_images_with_video(self, video_path, progress_reporter: ProgressReporter, images=None) -> HipVideoMatcherTask:
+        """images (an extension): a subset of the images this matcher was created with.  The task then matches the video against
+        those pages only, on a page set of the one page analysis (the upstream README's "lecture1 <-> video1, lecture2 <-> video2",
+        without a second matcher), and every Matching.image it returns is one of them.  None: every image, as upstream."""
+        pages = None if images is None else self._page_indices(images)
         video = open_raw_video(video_path) if isinstance(video_path, (str, os.PathLike)) else video_path
         frames_to_process = int(video.total_time() / 5.0)                             # lib.rs:148
         progress_reporter.report(0, frames_to_process, "")                            # lib.rs:150
-        return HipVideoMatcherTask(self._m, self._images, video, progress_reporter)
+        return HipVideoMatcherTask(self._m, self._images, video, progress_reporter, pages=pages)
+
+    def _page_indices(self, images):
+        """Deck indices of `images` (each one of the matcher's images: the same object, or an equal one), ascending."""
+        idx = set()
+        for im in images:
+            hit = next((i for i, own in enumerate(self._images) if own is im), None)
+            if hit is None:
+                hit = next((i for i, own in enumerate(self._images) if own == im), None)
+            if hit is None:
+                raise ValueError("image %r is not one this video matcher was created with" % (im,))
+            idx.add(hit)
+        if not idx:
+            raise ValueError("images: at least one image is needed")
+        return sorted(idx)
 
 
 class HipImageVideoMatcher:
