@@ -492,7 +492,9 @@ int32_t     slideo_l2_knn_dev(slideo_matcher* m, const void* q_dev, int32_t nq, 
  * retainBest(nfeatures) by response with ties kept, 4 x 4 x 8 descriptors as 128 bytes (OpenCV's are integer-valued 0..255).
  * Keypoints come back in canonical order (octave, layer, row, column, orientation bin); `octave` holds OpenCV's packed field
  * (octave & 255 | layer << 8 | sub-layer << 16), x / y / size in input-image pixels.  The descriptors feed slideo_l2_knn_dev.
- * Limits: n_octave_layers must be 3; image sides <= 4095 (the doubled image's coordinates travel in 13 bits). */
+ * Limits: n_octave_layers must be 3; the sides of the image the extractor reads <= 4095 (the doubled image's coordinates travel
+ * in 13 bits): pages, and frames after the working-size reduce — a 4096-wide frame is accepted under a working size that reduces
+ * it ("Working size"). */
 typedef struct slideo_sift_config {
     int32_t nfeatures;            /* 0 = keep every keypoint (cv::SIFT::create default)  */
     int32_t n_octave_layers;      /* 3    */
@@ -667,6 +669,36 @@ int32_t     slideo_group_match_frames_yuv420(slideo_group* g, int32_t n_frames, 
 int32_t     slideo_group_changed_mask_yuv420(slideo_group* g, int32_t n_frames, const uint8_t* frames, int32_t width, int32_t height,
                                              const slideo_yuv420_layout* layout, int64_t frame_stride_bytes, const uint8_t* prev_small,
                                              uint8_t* last_small_out, uint8_t* changed_out, float* similarity_out);
+
+/* ---- Working size (extension: the reference analyses every frame at the size it arrives in) ---------------------------------
+ * A matcher carries a working size (max_w, max_h); (0, 0) = none, the default.  While one is set, a frame of w x h with
+ * w <= max_w and h <= max_h is untouched; any other frame STANDS FOR the image cv::resize(frame, Size(dw, dh), 0, 0, INTER_AREA)
+ * [OCV A.11], reduced on the GPU in front of the pipeline (csrc/reduce.hip.h), with (dw, dh) by this rule in 64-bit integers:
+ *     if (w * max_h >= h * max_w) { dw = max_w; dh = max(1, (2*h*max_w + w) / (2*w)); }      width binds
+ *     else                        { dh = max_h; dw = max(1, (2*w*max_h + h) / (2*h)); }      height binds
+ * (aspect kept, the free side rounded half up; dw <= max_w, dh <= max_h, dw <= w, dh <= h).  3840x2160 under 1920x1080 is
+ * 1920x1080 (ResizeAreaFast's 2x2 path, (sum + 2) >> 2); 4096x2160 is 1920x1013.
+ * Contract: every frame call made while a working size is set — BGR and YUV 4:2:0, host and device, sync and submit / collect,
+ * the mask calls and slideo_match_kept_frames, the group's calls — returns, bit for bit, what the same call without a working
+ * size returns on the reduced images: verdicts, the slideo_last_frame_candidates trace, changed flags, similarities and the last
+ * small image.  COORDINATES in traces and transforms are therefore those of the REDUCED image.  The reduced image is what
+ * slideo_reduce_bgr8 returns, which equals the CPU restatement (oracle/ so_resize_area_bgr8_v under the matcher's ocv.area) bit
+ * for bit.  A 4:2:0 frame is converted first: the reduce reads the BGR image of "YUV 4:2:0 frames".
+ * Limits apply to the reduced size (area >= small_area; sides <= 4095 in SIFT mode); the source may be up to 4096 x 4096 in
+ * every mode.  Pages are never reduced.  The mask calls keep the REDUCED frames for slideo_match_kept_frames.
+ * DEPARTURE: the reference never reduces a frame.  With a working size set, verdicts are those of the reduced video, as if it had
+ * been encoded at that size; off by default; a front door, not another matcher. */
+/* The rule as a pure host function (no device).  SLIDEO_ERR_INVALID_ARG for a non-positive argument or a null output. */
+int32_t     slideo_working_size(int32_t w, int32_t h, int32_t max_w, int32_t max_h, int32_t* dw, int32_t* dh);
+/* Before or after finalize, any number of times; (0, 0) clears.  SLIDEO_ERR_STATE with units in flight; SLIDEO_ERR_INVALID_ARG for
+ * a negative side or exactly one zero.  Ends the kept frames of an earlier mask call. */
+int32_t     slideo_matcher_set_working_size(slideo_matcher* m, int32_t max_w, int32_t max_h);
+int32_t     slideo_matcher_get_working_size(const slideo_matcher* m, int32_t* max_w, int32_t* max_h);
+int32_t     slideo_group_set_working_size(slideo_group* g, int32_t max_w, int32_t max_h);
+/* Tap: one host image reduced to an explicit dw x dh under the matcher's ocv.area (out: stride dw * 3, out_capacity >= dw * dh * 3).
+ * SLIDEO_ERR_INVALID_ARG for dw > width, dh > height or dw == width && dh == height (no upscale, no copy). */
+int32_t     slideo_reduce_bgr8(slideo_matcher* m, const uint8_t* bgr, int32_t width, int32_t height, int32_t stride_bytes,
+                               int32_t dw, int32_t dh, uint8_t* out, int64_t out_capacity);
 
 #ifdef __cplusplus
 }

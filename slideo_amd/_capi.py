@@ -130,6 +130,8 @@ EXPORTS = [
     "slideo_changed_mask_yuv420", "slideo_yuv420_to_bgr8", "slideo_group_match_frames_yuv420", "slideo_group_changed_mask_yuv420",
     "slideo_matcher_create_page_set", "slideo_matcher_use_page_set", "slideo_matcher_release_page_set", "slideo_matcher_page_set_info",
     "slideo_group_create_page_set", "slideo_group_use_page_set", "slideo_group_release_page_set",
+    "slideo_working_size", "slideo_matcher_set_working_size", "slideo_matcher_get_working_size", "slideo_group_set_working_size",
+    "slideo_reduce_bgr8",
 ]
 
 _lib = None
@@ -243,7 +245,7 @@ class _FrameCalls:
         """-> (changed [n] bool, similarity [n] f32, the last frame's small image)"""
         changed = np.zeros(n, np.uint8)
         sims = np.zeros(n, np.float32)
-        sw, sh = small_size(w, h, self.cfg.small_area)
+        sw, sh = small_size(*self._unit_size(w, h), self.cfg.small_area)
         last = np.zeros((sh, sw, 3), np.uint8)
         if prev_small is not None:
             prev_small = np.ascontiguousarray(prev_small, np.uint8)
@@ -256,6 +258,21 @@ class _FrameCalls:
         out = np.zeros(len(sel), VERDICT_DTYPE)
         self._call("match_kept_frames", len(sel), _p(sel), _p(out))
         return out
+
+    # working size (include/slideo_amd.h "Working size"): frames beyond it stand for their INTER_AREA reduction
+    def set_working_size(self, max_w, max_h):
+        """Frames larger than max_w x max_h are reduced on the GPU before matching ((0, 0): none).  The matcher must be idle."""
+        self._check(getattr(lib(), self._SETS + "set_working_size")(self._h, int(max_w), int(max_h)))
+        self._ws = (int(max_w), int(max_h))
+
+    @property
+    def working_size(self):
+        return getattr(self, "_ws", (0, 0))
+
+    def _unit_size(self, w, h):
+        """The size of the image the pipeline reads for a w x h frame."""
+        mw, mh = self.working_size
+        return working_size(w, h, mw, mh) if mw > 0 else (w, h)
 
     # page sets (include/slideo_amd.h "page sets"): frame calls made while a set is selected search its pages only.  The argument
     # rules the library checks are checked here first, so that a bad call fails the same way before any device is involved.
@@ -378,6 +395,12 @@ class Matcher(_FrameCalls):
     @property
     def descriptor_count(self):
         return int(lib().slideo_matcher_descriptor_count(self._h))
+
+    @property
+    def working_size(self):
+        mw, mh = C.c_int32(), C.c_int32()
+        self._check(lib().slideo_matcher_get_working_size(self._h, C.byref(mw), C.byref(mh)))
+        return mw.value, mh.value
 
     @property
     def unique_descriptor_count(self):
@@ -576,6 +599,21 @@ class Matcher(_FrameCalls):
         self._check(lib().slideo_knn_l2_u8(self._h, _p(q), q.shape[0], _p(t), t.shape[0], k, _p(idx), _p(dist)))
         return idx, dist
 
+    def reduce(self, bgr, dw, dh):
+        """cv::resize(bgr, (dw, dh), INTER_AREA) as the working-size reduce computes it (the reduce tap)."""
+        bgr = np.ascontiguousarray(bgr, np.uint8)
+        if bgr.ndim != 3 or bgr.shape[2] != 3:
+            raise ValueError("expected an HxWx3 uint8 BGR image")
+        h, w, _ = bgr.shape
+        return self.reduce_pitched(bgr, w, h, w * 3, dw, dh)
+
+    def reduce_pitched(self, buf, w, h, stride, dw, dh):
+        """The same for an image of w x h in `buf` with rows `stride` bytes apart."""
+        buf = np.ascontiguousarray(buf, np.uint8)
+        out = np.empty((max(int(dh), 0), max(int(dw), 0), 3), np.uint8)
+        self._check(lib().slideo_reduce_bgr8(self._h, _p(buf), int(w), int(h), int(stride), int(dw), int(dh), _p(out), C.c_int64(out.size)))
+        return out
+
     def small_image(self, bgr):
         bgr = _img3(bgr)
         h, w, _ = bgr.shape
@@ -682,6 +720,15 @@ def device_list():
     arr = (C.c_int32 * max(n, 1))()
     n = min(n, int(lib().slideo_device_list(arr, n)))
     return [int(arr[i]) for i in range(n)]
+
+
+def working_size(w, h, max_w, max_h):
+    """slideo_working_size: the size a w x h frame stands for under the working size (max_w, max_h) — (w, h) when it fits."""
+    dw, dh = C.c_int32(), C.c_int32()
+    rc = lib().slideo_working_size(int(w), int(h), int(max_w), int(max_h), C.byref(dw), C.byref(dh))
+    if rc != OK:
+        raise SlideoError(rc, "slideo_working_size(%d, %d, %d, %d)" % (w, h, max_w, max_h))
+    return dw.value, dh.value
 
 
 def small_size(w, h, small_area=120000):

@@ -245,6 +245,14 @@ int32_t slideo_group_use_sift(slideo_group* g, const slideo_sift_config* cfg, fl
     GROUP_CATCH(g)
 }
 
+int32_t slideo_group_set_working_size(slideo_group* g, int32_t max_w, int32_t max_h) {
+    if (!g) return SLIDEO_ERR_INVALID_ARG;
+    GROUP_TRY
+    for (slideo_matcher* m : g->members) check_member_call(m, slideo_matcher_set_working_size(m, max_w, max_h));
+    g->kept_valid = false;
+    GROUP_CATCH(g)
+}
+
 // Page sets: every member builds the same set from the same deck (ids are handed out in the same order: they agree)
 int32_t slideo_group_create_page_set(slideo_group* g, int32_t n_pages, const int32_t* pages, int32_t* set_out) {
     if (!g) return SLIDEO_ERR_INVALID_ARG;

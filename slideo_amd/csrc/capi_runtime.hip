@@ -56,9 +56,9 @@ void upload_area(slideo_matcher* m) {
 }
 
 // max frames of size (w,h) per unit under the workspace budget (the slots share it)
-int sub_batch_for(slideo_matcher* m, const PyrGeom& g, int n, bool yuv) {
+int sub_batch_for(slideo_matcher* m, const PyrGeom& g, int n, size_t staging) {
     size_t per = (size_t)g.frame_bytes * (blur_is_f32(m) ? 2 : 1) + (size_t)g.cand_per_frame * 4 + (size_t)g.nlevels * 258 * 4 + (size_t)g.w * g.h * 3;
-    if (yuv) per += (size_t)g.w * g.h * 3 / 2;          // the 4:2:0 staging in front of the BGR image (BGR calls keep their unit sizes)
+    per += staging;          // the 4:2:0 staging in front of the BGR image, the source-sized frames of a reducing call (other calls keep their unit sizes)
     // downstream of ORB, sized by the per-frame keypoint capacity: items 8 + keypoint 24 + descriptor 32 B, the key lists
     // (32 x 4 B, times the train-set segments of a small query set: at most ~4 at sizes where the budget matters), and per
     // (keypoint, neighbour) the vote 8 B + point pair 16 B + mask 1 B
@@ -135,10 +135,19 @@ void validate_frames(FrameSrc& src, slideo_matcher* m, int n, const void* out) {
         if (n < 0 || (n > 0 && (!src.p || !out))) fail(SLIDEO_ERR_INVALID_ARG, "null frames/verdicts");
     }
     validate_image(src.w, src.h, src.stride);
-    if (m && m->sift_on) sift_check_cfg(&m->sift_cfg, src.w, src.h);          // (the doubled image's coordinates travel in 13 bits)
+    if (m) apply_working_size(m, src);
+    if (m && src.reduce && (src.w > MAX_DIM || src.h > MAX_DIM)) fail(SLIDEO_ERR_UNSUPPORTED, "image size %dx%d outside 1..%d", src.w, src.h, MAX_DIM);
+    if (m && m->sift_on) sift_check_cfg(&m->sift_cfg, src.unit_w(), src.unit_h());          // (the doubled image's coordinates travel in 13 bits)
     if (m && m->cur_set != 0) page_set_check_mode(m);                          // (a mode switched on after slideo_matcher_use_page_set)
     if (m && !src.yuv && src.frame_stride < (int64_t)src.h * src.stride) fail(SLIDEO_ERR_INVALID_ARG, "frame_stride smaller than one frame");
     src.pinned = !src.on_device && src.p && host_is_pinned(src.p);
+}
+
+void apply_working_size(const slideo_matcher* m, FrameSrc& src) {
+    src.reduce = false;
+    if (m->work_w <= 0 || (src.w <= m->work_w && src.h <= m->work_h)) return;
+    working_size_rule(src.w, src.h, m->work_w, m->work_h, src.rw, src.rh);
+    src.reduce = true;
 }
 
 // S's staging buffer with room for `bytes`.  Slot 0's holds the frames slideo_changed_mask_bgr8 kept for slideo_match_kept_frames:
@@ -151,15 +160,17 @@ static uint8_t* stage_for_upload(slideo_matcher* m, Slot& S, size_t bytes) {
 
 DevFrames stage_frames(slideo_matcher* m, Slot& S, const FrameSrc& src, int first, int n, hipStream_t cs) {
     const uint8_t* p = src.p + (int64_t)first * src.frame_stride;
-    if (src.on_device && !src.yuv) return DevFrames{p, src.w, src.h, src.stride, src.frame_stride};
-    const int64_t fb = (int64_t)src.h * src.stride;              // one frame of the BGR view (stride 3w for YUV frames)
-    uint8_t* stage = stage_for_upload(m, S, (size_t)fb * n);
+    if (src.on_device && !src.yuv && !src.reduce) return DevFrames{p, src.w, src.h, src.stride, src.frame_stride};
+    const int uw = src.unit_w(), uh = src.unit_h();
+    const int64_t fb = (int64_t)src.h * src.stride;              // one frame of the BGR view at source size (stride 3w for YUV frames)
+    const int64_t ub = src.reduce ? (int64_t)uh * uw * 3 : fb;   // one frame of the unit's BGR image
+    uint8_t* stage = stage_for_upload(m, S, (size_t)ub * n);
     int64_t fs = src.frame_stride;
     if (!src.on_device) {
-        // host frames back to back into d_stage, or into d_yuv for the conversion below
+        // host frames back to back into d_stage, or into d_yuv for the conversion / the reduce below
         const int64_t bytes = src.yuv ? src.yuv_span : fb;
         uint8_t* dst = stage;
-        if (src.yuv) { S.d_yuv.reserve((size_t)bytes * n + 16); dst = S.d_yuv.as<uint8_t>(); }
+        if (src.yuv || src.reduce) { S.d_yuv.reserve((size_t)bytes * n + 16); dst = S.d_yuv.as<uint8_t>(); }
         hipStream_t st = cs ? cs : S.st;
         if (fs == bytes) {
             HIP_CHECK(hipMemcpyAsync(dst, p, (size_t)bytes * n, hipMemcpyHostToDevice, st));
@@ -174,9 +185,16 @@ DevFrames stage_frames(slideo_matcher* m, Slot& S, const FrameSrc& src, int firs
         p = dst; fs = bytes;
     }
     // 4:2:0 frames: converted on the slot's stream into its d_stage, which lives until the unit is collected (verify's re-projection
-    // reads the frames)
-    if (src.yuv) launch_yuv420_to_bgr(p, fs, *src.yuv, src.w, src.h, n, stage, S.st);
-    return DevFrames{stage, src.w, src.h, src.stride, fb};
+    // reads the frames); into d_full when the image is reduced next (reduce comes after convert)
+    if (src.yuv) {
+        uint8_t* bgr = stage;
+        if (src.reduce) { S.d_full.reserve((size_t)fb * n + 16); bgr = S.d_full.as<uint8_t>(); }
+        launch_yuv420_to_bgr(p, fs, *src.yuv, src.w, src.h, n, bgr, S.st);
+        p = bgr; fs = fb;
+    }
+    if (!src.reduce) return DevFrames{stage, src.w, src.h, src.stride, fb};
+    launch_reduce(m, p, fs, src.stride, src.w, src.h, uw, uh, n, stage, S.st);
+    return DevFrames{stage, uw, uh, uw * 3, ub};
 }
 
 // ---- one unit of the per-frame hot path: enqueue everything, then collect ---------------
@@ -312,10 +330,10 @@ void match_frames_impl(slideo_matcher* m, int n, FrameSrc src, slideo_verdict* o
     require_idle(m);
     m->last_fcs.clear();
     if (n == 0) return;
-    GeomEntry& ge = geom_for(m, src.w, src.h);
-    area_class_for(m, src.w, src.h);
+    GeomEntry& ge = geom_for(m, src.unit_w(), src.unit_h());
+    area_class_for(m, src.unit_w(), src.unit_h());
     upload_area(m);
-    int unit = sub_batch_for(m, ge.g, n, src.yuv != nullptr);
+    int unit = sub_batch_for(m, ge.g, n, src.staging_bytes());
     if (n >= 128 && unit >= (n + 1) / 2) unit = (n + 1) / 2;      // two halves overlap ORB with kNN / verify
     // Host frames: the call is bound by the H2D copies (6.2 MB per 1080p frame: 256 frames = 29 ms at 55 GB/s against 14 ms of
     // kernels), so what matters is that the copy engines never wait: short units, each copied on its slot's stream while the
@@ -582,6 +600,55 @@ void slideo_matcher_destroy(slideo_matcher* m) {
 
 int32_t slideo_matcher_max_in_flight(const slideo_matcher* m) { return m ? NSLOTS : 0; }
 
+// ---- working size (include/slideo_amd.h "Working size") ---------------------------------------------------------------------
+
+int32_t slideo_working_size(int32_t w, int32_t h, int32_t max_w, int32_t max_h, int32_t* dw, int32_t* dh) {
+    if (w < 1 || h < 1 || max_w < 1 || max_h < 1 || !dw || !dh) return SLIDEO_ERR_INVALID_ARG;
+    int a = 0, b = 0;
+    working_size_rule(w, h, max_w, max_h, a, b);
+    *dw = a; *dh = b;
+    return SLIDEO_OK;
+}
+
+int32_t slideo_matcher_set_working_size(slideo_matcher* m, int32_t max_w, int32_t max_h) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    if (max_w < 0 || max_h < 0 || (max_w == 0) != (max_h == 0))
+        fail(SLIDEO_ERR_INVALID_ARG, "working size %dx%d: both sides positive, or 0, 0 for none", max_w, max_h);
+    require_idle(m);
+    m->work_w = max_w; m->work_h = max_h;
+    m->kept.valid = false;          // (the kept frames of an earlier mask call were sized under the earlier setting)
+    API_CATCH(m)
+}
+
+int32_t slideo_matcher_get_working_size(const slideo_matcher* m, int32_t* max_w, int32_t* max_h) {
+    if (!m || !max_w || !max_h) return SLIDEO_ERR_INVALID_ARG;
+    *max_w = m->work_w; *max_h = m->work_h;
+    return SLIDEO_OK;
+}
+
+// Tap: one host image reduced to dw x dh (the image a frame of that size stands for when the rule gives dw x dh)
+int32_t slideo_reduce_bgr8(slideo_matcher* m, const uint8_t* bgr, int32_t width, int32_t height, int32_t stride_bytes, int32_t dw, int32_t dh,
+                           uint8_t* out, int64_t out_capacity) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    if (!bgr || !out) fail(SLIDEO_ERR_INVALID_ARG, "null image/out");
+    FrameSrc img = FrameSrc::image(bgr, width, height, stride_bytes);
+    validate_frames(img);
+    if (width > MAX_DIM || height > MAX_DIM) fail(SLIDEO_ERR_UNSUPPORTED, "image size %dx%d outside 1..%d", width, height, MAX_DIM);
+    if (dw < 1 || dh < 1 || dw > width || dh > height || (dw == width && dh == height))
+        fail(SLIDEO_ERR_INVALID_ARG, "reduce %dx%d -> %dx%d: the target must be smaller along at least one side and larger along none", width, height, dw, dh);
+    const int64_t ob = (int64_t)dw * dh * 3;
+    if (ob > out_capacity) fail(SLIDEO_ERR_CAPACITY, "the reduced image needs %lld bytes", (long long)ob);
+    HIP_CHECK(hipSetDevice(m->device));
+    require_idle(m);
+    Slot& S = m->slots[0];
+    img.reduce = true; img.rw = dw; img.rh = dh;
+    HIP_CHECK(hipMemcpyAsync(out, stage_frames(m, S, img, 0, 1).p, (size_t)ob, hipMemcpyDeviceToHost, S.st));
+    HIP_CHECK(hipStreamSynchronize(S.st));
+    API_CATCH(m)
+}
+
 int32_t slideo_matcher_set_knn_engine(slideo_matcher* m, int32_t engine) {
     if (!m || engine < 0 || engine > 3) return SLIDEO_ERR_INVALID_ARG;
     m->knn_engine = engine;
@@ -786,11 +853,11 @@ void submit_impl(slideo_matcher* m, int32_t n_frames, FrameSrc src, void* hip_st
     HIP_CHECK(hipSetDevice(m->device));
     Slot& S = m->slots[m->next_slot];
     if (S.busy) fail(SLIDEO_ERR_STATE, "all slots are in flight: collect ticket %lld first", (long long)S.ticket);
-    GeomEntry& ge = geom_for(m, src.w, src.h);
-    if (n_frames > sub_batch_for(m, ge.g, n_frames, src.yuv != nullptr))
+    GeomEntry& ge = geom_for(m, src.unit_w(), src.unit_h());
+    if (n_frames > sub_batch_for(m, ge.g, n_frames, src.staging_bytes()))
         fail(SLIDEO_ERR_CAPACITY, "%d frames exceed the per-slot workspace budget (%d); submit smaller units or raise SLIDEO_WS_GB",
-             n_frames, sub_batch_for(m, ge.g, n_frames, src.yuv != nullptr));
-    area_class_for(m, src.w, src.h);
+             n_frames, sub_batch_for(m, ge.g, n_frames, src.staging_bytes()));
+    area_class_for(m, src.unit_w(), src.unit_h());
     upload_area(m);
     { bool any = false; for (const Slot& c : m->slots) any |= c.busy; if (!any) m->last_fcs.clear(); }
     if (hip_stream) {
@@ -812,6 +879,7 @@ void changed_mask_impl(slideo_matcher* m, int n_frames, FrameSrc src, const uint
                        float* similarity_out) {
     if (n_frames < 0 || (n_frames > 0 && (!src.p || !changed_out))) fail(SLIDEO_ERR_INVALID_ARG, "null frames/changed");
     validate_frames(src);
+    apply_working_size(m, src);
     if (n_frames == 0) return;
     HIP_CHECK(hipSetDevice(m->device));
     require_idle(m);

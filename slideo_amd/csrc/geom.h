@@ -379,11 +379,12 @@ inline void small_size(int w, int h, int small_area, int& sw, int& sh) {
 }
 
 // Returns false when the resize is not a shrink (INTER_AREA would fall back to bilinear).
-inline bool build_area_geom(int w, int h, int small_area, AreaGeom& a, std::vector<AreaTap>& taps, std::vector<int32_t>& idx, int variant = 0,
-                            std::vector<AreaRec>* recs = nullptr) {
+// (build_area_geom_to: the same for an explicit target size dw x dh — the working-size reduce, reduce.hip.h)
+inline bool build_area_geom_to(int w, int h, int dw, int dh, AreaGeom& a, std::vector<AreaTap>& taps, std::vector<int32_t>& idx, int variant = 0,
+                               std::vector<AreaRec>* recs = nullptr) {
     a = AreaGeom();
     a.sw = w; a.sh = h;
-    small_size(w, h, small_area, a.dw, a.dh);
+    a.dw = dw; a.dh = dh;
     if (a.dw <= 0 || a.dh <= 0 || a.dw > w || a.dh > h) return false;
     double scale_x = 1. / ((double)a.dw / w), scale_y = 1. / ((double)a.dh / h);
     a.iscale_x = (int)std::llrint(scale_x); a.iscale_y = (int)std::llrint(scale_y);
@@ -432,6 +433,22 @@ inline bool build_area_geom(int w, int h, int small_area, AreaGeom& a, std::vect
         a.yrec_ofs = emit(a.ytap_ofs, a.yidx_ofs, a.dh);
     }
     return true;
+}
+
+inline bool build_area_geom(int w, int h, int small_area, AreaGeom& a, std::vector<AreaTap>& taps, std::vector<int32_t>& idx, int variant = 0,
+                            std::vector<AreaRec>* recs = nullptr) {
+    int dw = 0, dh = 0;
+    small_size(w, h, small_area, dw, dh);
+    return build_area_geom_to(w, h, dw, dh, a, taps, idx, variant, recs);
+}
+
+// The working-size rule of include/slideo_amd.h "Working size": the size a w x h frame stands for under (max_w, max_h) — itself when
+// it fits, else the aspect-preserving size whose binding side is the limit, the other side rounded half up.  All arguments positive.
+inline void working_size_rule(int w, int h, int max_w, int max_h, int& dw, int& dh) {
+    const int64_t W = w, H = h, MW = max_w, MH = max_h;
+    if (w <= max_w && h <= max_h) { dw = w; dh = h; }
+    else if (W * MH >= H * MW) { dw = max_w; dh = (int)std::max<int64_t>(1, (2 * H * MW + W) / (2 * W)); }
+    else { dh = max_h; dw = (int)std::max<int64_t>(1, (2 * W * MH + H) / (2 * H)); }
 }
 
 }  // namespace slideo

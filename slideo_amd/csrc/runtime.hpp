@@ -1,7 +1,7 @@
 // runtime.hpp — the host runtime behind include/slideo_amd.h, shared by its translation units.
 //
 //   capi_runtime.hip   handles, page database, slots, frame staging (FrameSrc -> DevFrames), unit submit / collect, the match entry points
-//   stage_orb.hip      ORB stage drivers          (kernels: orb.hip.h, yuv420.hip.h)
+//   stage_orb.hip      ORB stage drivers          (kernels: orb.hip.h, yuv420.hip.h, reduce.hip.h)
 //   stage_knn.hip      index build + k-NN stage   (kernels: knn.hip.h, knn_tile.hip.h, knn_l2.hip.h, knn_lsh.hip.h)
 //   stage_verify.hip   vote .. verdict, small img (kernels: verify.hip.h, homography.hip.h)
 //   stage_sift.hip     SIFT stage + entry points  (kernels: sift.hip.h)
@@ -50,6 +50,12 @@ struct GeomEntry {
     DevBuf fast_tiles;                // per FAST tile: level, origin, raw-column alignment (orb.hip.h fast_tile_entry)
 };
 
+// One class of the working-size reduce: frames of ag.sw x ag.sh -> ag.dw x ag.dh (reduce.hip.h), with its own tap tables
+struct ReduceEntry {
+    AreaGeom ag;
+    DevBuf d_taps, d_idx;
+};
+
 struct HostPage {
     int w = 0, h = 0, sw = 0, sh = 0, area_idx = -1;
     std::vector<slideo_keypoint> kp;
@@ -68,6 +74,20 @@ struct FrameSrc {
     const slideo_yuv420_layout* yuv = nullptr;
     int64_t yuv_span = 0;                       // (derived) bytes of one YUV frame: its furthest byte + 1
     bool pinned = false;                        // (derived) page-locked host memory: its copies are truly asynchronous DMA
+    // (derived, match and mask calls) the matcher's working size does not hold the frame: the units read its INTER_AREA reduction
+    // to rw x rh (include/slideo_amd.h "Working size")
+    bool reduce = false;
+    int rw = 0, rh = 0;
+
+    int unit_w() const { return reduce ? rw : w; }      // the BGR image the units read
+    int unit_h() const { return reduce ? rh : h; }
+    // per frame, the staging in front of the unit's BGR image: 1.5 B per pixel for 4:2:0 frames (BGR calls keep their unit sizes);
+    // a reducing call: the uploaded source frame (host sources) and the source-sized BGR image of a 4:2:0 frame
+    size_t staging_bytes() const {
+        const size_t px = (size_t)w * h;
+        if (!reduce) return yuv ? px * 3 / 2 : 0;
+        return (on_device ? 0 : (yuv ? px * 3 / 2 : (size_t)h * stride)) + (yuv ? px * 3 : 0);
+    }
 
     static FrameSrc bgr8(const uint8_t* p, bool on_device, int w, int h, int stride, int64_t frame_stride) {
         return FrameSrc{p, on_device, w, h, stride, frame_stride};
@@ -109,7 +129,9 @@ struct Slot {
     bool u_rerun = false;      // (unit_collect's re-runs: the unit keeps its set)
     DevBuf d_stage, d_pyr, d_blur, d_cand, d_hist, d_candcount, d_flags, d_thr, d_lvlofs, d_kpcount, d_qofs, d_info;
     DevBuf d_items, d_kp, d_desc, d_keys, d_knn_pend, d_votes, d_gpts, d_gmask, d_fcs, d_verdicts, d_pairs, d_blurmask, d_qkeys, d_tail, d_refine;
-    DevBuf d_yuv;              // host YUV 4:2:0 frames of the unit, converted into d_stage (reserved by the first YUV call only)
+    DevBuf d_yuv;              // host frames of the unit in front of d_stage: YUV 4:2:0 frames to convert, source-sized frames to reduce
+                               // (reserved by the first YUV or reducing call only)
+    DevBuf d_full;             // the source-sized BGR image of 4:2:0 frames that are reduced (reserved by the first such call only)
     PinBuf h_info, h_out;
     OrbOut orb;
     // unit in flight
@@ -164,6 +186,9 @@ struct slideo_matcher {
     uint32_t rng_len = 0;
     int ic_shift = 0, ic_entries = 0;     // intensity-centroid weight table of describe_kernel (geom.h ic_weight_table)
     std::vector<std::unique_ptr<slideo::GeomEntry>> geoms;
+    // working size (slideo_matcher_set_working_size): frames beyond it are reduced in front of the pipeline; 0, 0 = none
+    int work_w = 0, work_h = 0;
+    std::vector<std::unique_ptr<slideo::ReduceEntry>> reduces;
 
     // INTER_AREA size classes
     std::vector<slideo::AreaGeom> area_geoms;
@@ -256,17 +281,21 @@ int area_class_for(slideo_matcher* m, int w, int h);
 void upload_area(slideo_matcher* m);
 inline bool blur_is_f32(const slideo_matcher* m) { return m->cfg.ocv.blur <= 1; }
 uint32_t kp_cap_for(const slideo_matcher* m, const PyrGeom& g);
-// yuv: the unit's frames arrive as YUV 4:2:0 (+ 1.5 B per pixel and frame of staging)
-int sub_batch_for(slideo_matcher* m, const PyrGeom& g, int n, bool yuv = false);
+// staging: bytes per frame in front of the unit's BGR image (FrameSrc::staging_bytes)
+int sub_batch_for(slideo_matcher* m, const PyrGeom& g, int n, size_t staging = 0);
 void require_idle(slideo_matcher* m);
 void validate_image(int w, int h, int stride);
 // The argument rules of a call's frames (include/slideo_amd.h), in the order the entry points report them: a YUV source's layout
 // (its span; the stride of its BGR image), then — m != null: a match call — the matcher's state and the null frames / verdicts
-// `out`, then a BGR source's geometry, the SIFT limits and — match calls — a BGR source's frame stride.
+// `out`, then a BGR source's geometry, the working size (apply_working_size), the SIFT limits (on the size the units read) and —
+// match calls — a BGR source's frame stride.
 void validate_frames(FrameSrc& src, slideo_matcher* m = nullptr, int n = 0, const void* out = nullptr);
+// fills src.reduce / rw / rh from m's working size (the mask calls, which validate without a matcher, call it themselves)
+void apply_working_size(const slideo_matcher* m, FrameSrc& src);
 // Frames [first, first + n) of a validated `src` as BGR8 on the device, for slot S: a device BGR source as it is; host frames
 // copied into S.d_stage (BGR) or S.d_yuv (YUV), on `cs` when given (S.st waits for it) and on S.st otherwise; YUV converted into
-// S.d_stage on S.st.  Every write of a slot's d_stage goes through here (page ingest through its staging buffer) and ends the
+// S.d_stage on S.st; a source the working size reduces: host frames into S.d_yuv, 4:2:0 frames converted into S.d_full, then
+// reduced into S.d_stage (the DevFrames are rw x rh).  Every write of a slot's d_stage goes through here (page ingest through its staging buffer) and ends the
 // frames slideo_changed_mask_bgr8 kept for slideo_match_kept_frames.
 DevFrames stage_frames(slideo_matcher* m, Slot& S, const FrameSrc& src, int first, int n, hipStream_t cs = nullptr);
 void upload_rng_stream(slideo_matcher* m, uint32_t len);
@@ -293,6 +322,9 @@ void run_orb(slideo_matcher* m, Slot& S, const DevFrames& f, int n, bool keep_ho
 void orb_launch_gray(const slideo_matcher* m, const uint8_t* frames_dev, int64_t frame_stride, int stride, uint8_t* gray, int64_t gframe, int w, int h,
                      int pitch, int n, hipStream_t st);
 void orb_launch_scan(const uint32_t* counts, int n, uint32_t* qofs, uint32_t* info, hipStream_t st);
+// n BGR8 frames of w x h -> cv::resize(INTER_AREA) to dw x dh under m's ocv.area, at dst (stride 3dw, frame stride 3dw dh)
+void launch_reduce(slideo_matcher* m, const uint8_t* src, int64_t src_fs, int stride, int w, int h, int dw, int dh, int n, uint8_t* dst,
+                   hipStream_t st);
 // n decoded YUV 4:2:0 frames (a layout yuv420_validate accepted, frame stride src_fs) -> BGR8 at dst, stride 3w, frame stride 3wh
 void launch_yuv420_to_bgr(const uint8_t* src, int64_t src_fs, const slideo_yuv420_layout& L, int w, int h, int n, uint8_t* dst, hipStream_t st);
 

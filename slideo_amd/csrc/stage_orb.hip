@@ -1,7 +1,9 @@
-// stage_orb.hip — drivers of the ORB stage (kernels: orb.hip.h) and of the YUV 4:2:0 front door in front of it (yuv420.hip.h).
+// stage_orb.hip — drivers of the ORB stage (kernels: orb.hip.h) and of the front doors in front of it: YUV 4:2:0 frames
+// (yuv420.hip.h) and the working-size reduce (reduce.hip.h).
 #include "runtime.hpp"
 #include "orb.hip.h"
 #include "yuv420.hip.h"
+#include "reduce.hip.h"
 
 using namespace slideo;
 
@@ -69,6 +71,45 @@ void launch_yuv420_to_bgr(const uint8_t* src, int64_t src_fs, const slideo_yuv42
     dim3 grid(cdiv(cdiv(w, 4), YUV_TX), cdiv(h / 2, YUV_TY), n);
     yuv420_to_bgr_kernel<<<grid, dim3(YUV_TX, YUV_TY), 0, st>>>(a);
     check_launch("yuv420_to_bgr_kernel");
+}
+
+// the reduce class (w, h) -> (dw, dh): ResizeAreaFast when both factors are integers (the test of resize.cpp, in double), else the
+// tap tables under the matcher's ocv.area, uploaded once
+static ReduceEntry& reduce_for(slideo_matcher* m, int w, int h, int dw, int dh) {
+    for (auto& r : m->reduces) if (r->ag.sw == w && r->ag.sh == h && r->ag.dw == dw && r->ag.dh == dh) return *r;
+    auto e = std::make_unique<ReduceEntry>();
+    std::vector<AreaTap> taps;
+    std::vector<int32_t> idx;
+    if (!build_area_geom_to(w, h, dw, dh, e->ag, taps, idx, m->cfg.ocv.area))
+        fail(SLIDEO_ERR_INVALID_ARG, "reduce %dx%d -> %dx%d is not a shrink", w, h, dw, dh);
+    e->d_taps.reserve(std::max<size_t>(taps.size() * sizeof(AreaTap), 16));
+    e->d_idx.reserve(std::max<size_t>(idx.size() * 4, 16));
+    HIP_CHECK(hipMemcpyAsync(e->d_taps.p, taps.data(), taps.size() * sizeof(AreaTap), hipMemcpyHostToDevice, m->stream));
+    HIP_CHECK(hipMemcpyAsync(e->d_idx.p, idx.data(), idx.size() * 4, hipMemcpyHostToDevice, m->stream));
+    HIP_CHECK(hipStreamSynchronize(m->stream));              // the host vectors die here
+    m->reduces.push_back(std::move(e));
+    return *m->reduces.back();
+}
+
+// n BGR8 frames of w x h (rows `stride`, frames src_fs apart) -> resize(INTER_AREA) to dw x dh at dst (stride 3dw, frame stride 3dw dh)
+void launch_reduce(slideo_matcher* m, const uint8_t* src, int64_t src_fs, int stride, int w, int h, int dw, int dh, int n, uint8_t* dst,
+                   hipStream_t st) {
+    const ReduceEntry& e = reduce_for(m, w, h, dw, dh);
+    ReduceArgs a{};
+    a.src = src; a.src_frame_stride = src_fs; a.src_stride = stride;
+    a.dst = dst; a.sw = w; a.sh = h; a.dw = dw; a.dh = dh;
+    a.ix = e.ag.iscale_x; a.iy = e.ag.iscale_y; a.inv_area = e.ag.fast_scale;
+    a.out4 = (uintptr_t)dst % 4 == 0 && dw % 4 == 0;
+    const dim3 grid(cdiv(cdiv(dw, 4), RED_TX), cdiv(dh, RED_TY), n), block(RED_TX, RED_TY);
+    if (e.ag.fast) {
+        // whole factors: w == ix dw and h == iy dh.  2x2 from 8-byte aligned rows through the dword kernel
+        const bool aligned = a.ix == 2 && a.iy == 2 && a.out4 && (uintptr_t)src % 8 == 0 && stride % 8 == 0 && src_fs % 8 == 0;
+        if (aligned) reduce2x2_kernel<<<grid, block, 0, st>>>(a);
+        else reduce_int_kernel<<<grid, block, 0, st>>>(a);
+    } else {
+        reduce_area_kernel<<<grid, block, 0, st>>>(a, e.ag, e.d_taps.as<AreaTap>(), e.d_idx.as<int32_t>());
+    }
+    check_launch("reduce kernel");
 }
 
 void orb_launch_scan(const uint32_t* counts, int n, uint32_t* qofs, uint32_t* info, hipStream_t st) {

@@ -166,6 +166,7 @@ namespace detail {
 struct Handle {
     slideo_group* g = nullptr;
     int n_devices = 1;
+    int32_t work_w = 0, work_h = 0;          // the working size the group was given (0, 0: none)
     ~Handle() { if (g) slideo_group_destroy(g); }
     void check(int32_t rc) const {
         if (rc != SLIDEO_OK) throw std::runtime_error(std::string("slideo_amd error ") + std::to_string(rc) + ": " + slideo_group_last_error(g));
@@ -217,9 +218,16 @@ public:
             const int n = (int)meta.size();
             std::vector<uint8_t> changed(n);
             if (last_small.empty()) {       // size of the small image: ask once
-                std::vector<uint8_t> tmp(fb);
-                int32_t a, b;
-                h_->check(slideo_small_image_bgr8(slideo_group_member(h_->g, 0), frames.data(), video.width, video.height, video.width * 3, tmp.data(), (int64_t)tmp.size(), &a, &b));
+                std::vector<uint8_t> tmp(fb), red;
+                const uint8_t* img = frames.data();
+                int32_t a, b, uw = video.width, uh = video.height;
+                if (h_->work_w > 0) h_->check(slideo_working_size(video.width, video.height, h_->work_w, h_->work_h, &uw, &uh));
+                if (uw != video.width || uh != video.height) {      // the mask compares the small images of the REDUCED frames
+                    red.resize((size_t)uw * uh * 3);
+                    h_->check(slideo_reduce_bgr8(slideo_group_member(h_->g, 0), frames.data(), video.width, video.height, video.width * 3, uw, uh, red.data(), (int64_t)red.size()));
+                    img = red.data();
+                }
+                h_->check(slideo_small_image_bgr8(slideo_group_member(h_->g, 0), img, uw, uh, uw * 3, tmp.data(), (int64_t)tmp.size(), &a, &b));
                 sw = a; sh = b; last_small.resize((size_t)sw * sh * 3);
             }
             h_->check(slideo_group_changed_mask_bgr8(h_->g, n, frames.data(), video.width, video.height, video.width * 3, (int64_t)fb,
@@ -295,6 +303,9 @@ public:
     // path's own 5 % tolerance vote on the L2 distances — the robust choice on decks whose pages share a template; ratio in
     // (0, 1]: Lowe's ratio test on the two nearest rows (the north_star's wording)
     HipImageVideoMatcher& with_sift(float ratio = 0.f) { sift_on_ = true; sift_ratio_ = ratio; return *this; }
+    // Frames beyond max_w x max_h are reduced on the GPU before matching (slideo_group_set_working_size; include/slideo_amd.h
+    // "Working size").  The reference never reduces a frame: verdicts are then those of the reduced video.  Default: none
+    HipImageVideoMatcher& with_working_size(int32_t max_w, int32_t max_h) { work_w_ = max_w; work_h_ = max_h; return *this; }
     template <class I>
     std::unique_ptr<VideoMatcher<I>> create_video_matcher(std::vector<I> images, ProgressReporter reporter) const {
         auto h = std::make_shared<detail::Handle>();
@@ -306,6 +317,10 @@ public:
             slideo_sift_config sc;
             slideo_sift_config_default(&sc);
             h->check(slideo_group_use_sift(h->g, &sc, sift_ratio_));
+        }
+        if (work_w_ > 0 || work_h_ > 0) {
+            h->check(slideo_group_set_working_size(h->g, work_w_, work_h_));
+            h->work_w = work_w_; h->work_h = work_h_;
         }
         h->check(slideo_group_set_progress(h->g, detail::tramp, &reporter));                         // "Analyzing PDF pages..." protocol, mo/lib.rs:43-58
         const size_t CH = 32 * (size_t)h->n_devices;
@@ -324,6 +339,7 @@ private:
     std::vector<int32_t> devices_;
     bool sift_on_ = false;
     float sift_ratio_ = 0.f;
+    int32_t work_w_ = 0, work_h_ = 0;
     slideo_config cfg_;
     ImageLoader loader_;
 };
