@@ -219,8 +219,8 @@ uint32_t kp_cap_for(const slideo_matcher* m, const PyrGeom& g) {
 }
 
 void unit_submit(slideo_matcher* m, Slot& S, const DevFrames& f, int n, bool allow_async) {
-    // (does this unit share the chip with others?  the search then runs one block per CU: stage_knn.hip share_pad)
-    { bool others = m->units_pending; for (const Slot& o : m->slots) others |= (&o != &S && o.busy); S.u_shared = others; }
+    // (does this unit share the chip with others?  the search then runs one block per CU: stage_knn.hip knn_plan)
+    { bool others = m->units_pending; for (const Slot& o : m->slots) others |= (&o != &S && o.busy); S.knn.shared = others; }
     if (!S.u_rerun) S.u_set = m->cur_set;          // (a re-run of an overflowed unit searches the set it was submitted with)
     S.u_rerun = false;
     if (m->sift_on) { unit_submit_sift(m, S, f, n); return; }
@@ -233,7 +233,7 @@ void unit_submit(slideo_matcher* m, Slot& S, const DevFrames& f, int n, bool all
     const uint32_t kpcap = kp_cap_for(m, g);
     // (a capacity below quota + margin — the KP_SORT_LDS clamp at nfeatures >= ~7 k — would overflow on every busy frame and run
     // every unit twice: those configurations take the exact-size path from the start)
-    const bool async = allow_async && m->async_submit && !knn_unit_is_valu(m, n * (int)std::min<uint32_t>(kpcap, (uint32_t)c.nfeatures)) &&
+    const bool async = allow_async && m->async_submit && !knn_unit_is_valu(m) &&
                        (int64_t)n * kpcap < ((int64_t)1 << 30) &&
                        (kpcap >= (uint32_t)c.nfeatures + 1024u || kpcap >= (uint32_t)std::max(g.cand_per_frame, 1));
     S.timed = prof; S.u_in = f; S.u_async = async;
@@ -250,10 +250,7 @@ void unit_submit(slideo_matcher* m, Slot& S, const DevFrames& f, int n, bool all
         qtot = qplan = S.orb.qtot;
     }
     // all workspace before the timed kNN interval
-    S.u_nt = knn_unit_rows(m, (int)qplan, S.u_set);
-    // the search's block shape while units share the chip (stage_knn.hip knn_shape): how much search there is per pixel of ORB work
-    S.u_w12 = m->knn_w12_ratio > 0.0 && (double)qplan * (double)S.u_nt >= m->knn_w12_ratio * (double)n * (double)f.w * (double)f.h;
-    knn_reserve_unit(m, S, qplan, qtot);
+    knn_plan_unit(m, S, n, (int64_t)f.w * f.h, qplan, qtot);
     S.d_votes.reserve(std::max<size_t>((size_t)qtot * c.knn_k * sizeof(uint2), 16));
     S.d_gpts.reserve(std::max<size_t>((size_t)qtot * c.knn_k * sizeof(float4), 16));
     S.d_gmask.reserve(std::max<size_t>((size_t)qtot * c.knn_k, 16));
@@ -312,7 +309,7 @@ void unit_collect(slideo_matcher* m, Slot& S, slideo_verdict* out_host) {
         HIP_CHECK(hipEventElapsedTime(&t, S.ev[0], S.ev[1])); m->prof_ms[0] += t; m->prof_n[0]++;
         if (qtot > 0) {
             HIP_CHECK(hipEventElapsedTime(&t, S.ev[1], S.ev[2])); m->prof_ms[1] += t; m->prof_n[1]++;
-            m->prof_pairs += (int64_t)qtot * S.u_nt;       // pairs EVALUATED: unique train rows when the set is de-duplicated
+            m->prof_pairs += (int64_t)qtot * S.knn.nt;       // pairs EVALUATED: unique train rows when the set is de-duplicated
             HIP_CHECK(hipEventElapsedTime(&t, S.ev[2], S.ev[3])); m->prof_ms[2] += t; m->prof_n[2]++;
         }
         HIP_CHECK(hipEventElapsedTime(&t, S.ev[0], S.ev[4])); m->prof_ms[3] += t; m->prof_n[3]++;

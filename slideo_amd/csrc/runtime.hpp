@@ -7,7 +7,7 @@
 //   stage_sift.hip     SIFT stage + entry points  (kernels: sift.hip.h)
 //   stage_page_set.hip page sets: a subset's search operand built from the finalized deck (kernels: page_set.hip.h)
 //   capi_taps.hip      debug taps of the parity tests
-//   capi_group.cpp     the N-device group (slideo_group_*)
+//   capi_group.hip     the N-device group (slideo_group_*)
 //
 // Every kernel header is compiled by exactly one unit; what crosses units is the functions declared below and the plain
 // records of types.h.  There is no CPU fallback anywhere in here.
@@ -117,6 +117,17 @@ struct OrbOut {            // where the last ORB run of a slot left its results 
     std::vector<uint32_t> qofs;   // host copy, nframes+1
 };
 
+// The search of one unit (or tap), as stage_knn.hip knn_plan decides it
+struct KnnPlan {
+    bool shared = false, w12 = false;   // observed: other units are in flight; the large-deck rule holds (stage_knn.hip knn_plan_unit)
+    int nt = 0;                         // train rows searched (unit_collect: the pairs evaluated)
+    bool dedup = false;                 // ... which are distinct rows: the keys are expanded along the duplicate chains
+    int engine = 0, shape = 0;          // 1 = VALU, 2 / 3 = matrix cores (4 / 2 query tiles per wave); stage_knn.hip KnnShape
+    unsigned lds_pad = 0;               // dynamic LDS that keeps the 8-wave block alone on its CU
+    int nq_all = 0;                     // the query rows the grid and the buffers cover
+    int qblocks = 0, nseg = 0, per_seg = 0;
+};
+
 // One workspace + stream.  Several slots let the ORB stage of one unit of frames run concurrently with the
 // kNN / verification stages of the previous units (matrix-core bound vs VALU/LDS/HBM bound work).
 struct Slot {
@@ -124,7 +135,8 @@ struct Slot {
     hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     hipEvent_t ev_in = nullptr, ev_orb = nullptr, ev_up = nullptr;
     // arguments of the unit in flight (re-run through the exact-size path if the capacity-sized one overflowed)
-    DevFrames u_in; bool u_async = false; int u_nt = 0; bool u_shared = false, u_w12 = false;
+    DevFrames u_in; bool u_async = false;
+    KnnPlan knn;               // the unit's search as knn_plan_unit decided it (stage_knn.hip)
     int u_set = 0;             // the page set the unit searches (0 = the whole deck), taken from the matcher at submission
     bool u_rerun = false;      // (unit_collect's re-runs: the unit keeps its set)
     DevBuf d_stage, d_pyr, d_blur, d_cand, d_hist, d_candcount, d_flags, d_thr, d_lvlofs, d_kpcount, d_qofs, d_info;
@@ -158,14 +170,32 @@ struct Slot {
     }
 };
 
+// The matrix-core search operand of one train set (knn_tile.hip.h): the Hamming deck's, a page set's, the L2 set's, a tap's.  Built
+// by stage_knn.hip (prepare_train_bits, l2_prepare) or, a page set's, on the device (stage_page_set.hip).
+struct OperandLayout { int st_rows, side_u32; float pad_norm; };   // the side array's shape (knn_tile.hip.h KT_ST_ROWS, KT_SIDE_U32, KT_PAD_NORM)
+struct SearchOperand {
+    DevBuf tx;                 // [nt_pad][128 B] the rows in stream order, tile-major: {0,1} FP4 (Hamming), centred bytes (L2)
+    DevBuf side;               // per super-tile: the rows' norms (Hamming f32, L2 negated i32), then the row ids their keys carry
+    DevBuf bound;              // per 32-row tile the bound its first row gives (Hamming: half its norm; L2: its negated norm)
+    DevBuf perm;               // [nt_pad] stream row -> source row (-1: a pad row)
+    int nt = 0, nt_pad = 0;    // rows, rows padded to whole super-tiles
+    size_t bytes() const { return tx.cap + side.cap + bound.cap + perm.cap; }
+    // perm_slack: the bytes behind the permutation (the L2 set has never carried them)
+    void reserve(int nt_, int nt_pad_, const OperandLayout& L, size_t perm_slack = 16) {
+        nt = nt_; nt_pad = nt_pad_;
+        tx.reserve((size_t)nt_pad * 128); side.reserve((size_t)(nt_pad / L.st_rows) * L.side_u32 * 4 + 16);
+        bound.reserve((size_t)nt_pad / 32 * 4 + 16); perm.reserve((size_t)nt_pad * 4 + perm_slack);
+    }
+};
+
 // A page set (slideo_matcher_create_page_set): the search operand and duplicate chain of a subset of the finalized deck's pages,
 // built on the device (stage_page_set.hip).  Keys carry deck row ids, so everything downstream of the search is the deck's.
 struct PageSet {
     int n_pages = 0;
     int64_t rows = 0, urows = 0;                  // the selected pages' rows, the distinct rows among them (what the search streams)
-    DevBuf d_trainb, d_side, d_nminh, d_perm;     // the operand in the layout of prepare_train_bits (knn_tile.hip.h)
+    SearchOperand op;                             // as prepare_train_bits lays out a deck of exactly the selected pages
     DevBuf d_grp_next;                            // [M] the chain of the selected rows of each duplicate group (-1 elsewhere)
-    size_t bytes() const { return d_trainb.cap + d_side.cap + d_nminh.cap + d_perm.cap + d_grp_next.cap; }
+    size_t bytes() const { return op.bytes() + d_grp_next.cap; }
 };
 constexpr int MAX_PAGE_SETS = 64;                 // live sets per matcher
 
@@ -182,7 +212,7 @@ struct slideo_matcher {
     long sift_ws_mb = 24l << 10;              // pyramids of one SIFT pass (SLIDEO_SIFT_WS_MB); 96 GB on a device with >= 192 GB: 256 1080p frames in ONE pass
 
     slideo::DevBuf d_tables, d_rng, d_ictab;
-    struct L2Set { slideo::DevBuf d_tx, d_tn, d_side, d_perm, d_keys, d_pend; int nt = 0, nt_pad = 0; bool ready = false; } l2;   // cfg2: the L2 train set
+    struct L2Set { slideo::SearchOperand op; slideo::DevBuf d_keys, d_pend; bool ready = false; } l2;   // cfg2: the L2 train set
     uint32_t rng_len = 0;
     int ic_shift = 0, ic_entries = 0;     // intensity-centroid weight table of describe_kernel (geom.h ic_weight_table)
     std::vector<std::unique_ptr<slideo::GeomEntry>> geoms;
@@ -210,7 +240,7 @@ struct slideo_matcher {
     bool sift_ev_set = false;
     int64_t M = -1;
     slideo::DevBuf d_train, d_train_page, d_page_xy, d_pageinfo, d_page_small;
-    slideo::DevBuf d_trainb, d_train_side, d_train_nminh, d_train_perm;   // {0,1} FP4 operand in norm order + its side arrays (knn_tile.hip.h)
+    slideo::SearchOperand train_op;    // the deck's {0,1} FP4 operand: its distinct rows in norm order, tiles shuffled (prepare_train_bits)
     // train-set de-duplication (knn.hip.h knn_expand_dups_kernel): the matrix-core engine searches the Mu unique rows, keys carry
     // the lowest original row of a group, d_grp_next chains the equal rows.  SLIDEO_KNN_DEDUP=0 searches all M rows.
     slideo::DevBuf d_utrain, d_grp_next;
@@ -233,12 +263,7 @@ struct slideo_matcher {
     struct Kept { bool valid = false; int n = 0, w = 0, h = 0, stride = 0; } kept;
     slideo::DevBuf d_kept;
     bool units_pending = false;   // the call being served has more units than the one submitted now
-    // while units share the chip the search runs the 12-wave block (three waves per SIMD, 128 registers each) instead of the 8-wave
-    // block + LDS pad when a unit carries at least this many (query, train row) pairs per frame pixel: the larger the deck, the more of
-    // a step is search, and from ~290 pairs per pixel on the fuller matrix pipe is worth more than the co-runners' occupancy
-    // (profiles/r06_experiments.txt 7: headline 197: - 2..4 %; 700 pages 275: - 1.7 %; 800 pages 314: + 5.5 %; configs[3] 392:
-    // + 6.8 %; configs[4] 352: + 4.7 %).  SLIDEO_KNN_W12_RATIO overrides (0 = never).
-    double knn_w12_ratio = 290.0;
+    double knn_w12_ratio = 290.0;   // the large-deck rule of the search's block shape (stage_knn.hip knn_plan_unit; SLIDEO_KNN_W12_RATIO)
     int knn_share = -1;     // the search's block shape (SLIDEO_KNN_SHARE; stage_knn.hip knn_shape): -1 = while other units are in flight one 8-wave block per CU,
                             // or the 12-wave block for large decks (knn_w12_ratio), two 8-wave blocks otherwise (default); 0 = always two 8-wave blocks;
                             // 1 = always one; 3 / 4 = the 12-wave block while shared / always
@@ -332,17 +357,18 @@ void launch_yuv420_to_bgr(const uint8_t* src, int64_t src_fs, const slideo_yuv42
 // FlannMatcher::new (mo/flann.rs:65-71) for the Hamming index: uploads the M packed rows, collapses equal rows, builds the
 // matrix-core operand (and the LSH tables for matcher 1).  Sets m->Mu.
 void knn_build_index(slideo_matcher* m, const std::vector<uint8_t>& train, int64_t M);
-// workspace of a unit's search (before the timed interval) and the search itself: S.d_desc -> S.d_keys (+ the expansion of the
-// collapsed rows).  qplan: the query count the launch is planned for, qtot: the capacity (async) or the real count.
-void knn_reserve_unit(slideo_matcher* m, Slot& S, uint32_t qplan, uint32_t qtot);
+// A unit's search, decided once from what unit_submit observes (S.knn.shared, S.u_set, the n frames' pixels): rows searched,
+// de-duplication, engine, block shape, segments, grid.  Reserves the search's workspace (before the timed interval) and leaves the
+// plan in S.knn.  qplan: the query count the launch is planned for, qtot: the capacity (async) or the real count.
+void knn_plan_unit(slideo_matcher* m, Slot& S, int n, int64_t frame_pixels, uint32_t qplan, uint32_t qtot);
+// the search as S.knn plans it: S.d_desc -> S.d_keys (+ the expansion of the collapsed rows)
 void unit_knn(slideo_matcher* m, Slot& S, int n, uint32_t qplan, uint32_t qtot, bool async, bool prof);
-bool knn_unit_is_valu(const slideo_matcher* m, int nq);
-int knn_unit_rows(const slideo_matcher* m, int nq, int set = 0);   // train rows a unit's search evaluates (Mu, or M for the VALU engine; a page set's distinct rows)
+bool knn_unit_is_valu(const slideo_matcher* m);
 // the {0,1} FP4 expansion of the operand rows perm[0 .. nt_pad) of t (knn_tile.hip.h knn_tile_expand_kernel)
 void knn_expand_operand(const uint32_t* t, int nt, int nt_pad, const int32_t* perm, uint4* tx, hipStream_t st);
 int knn_operand_rows(int nt);                              // nt padded to whole super-tiles
-struct OperandLayout { int st_rows, side_u32; float pad_norm; };   // the side array's shape (knn_tile.hip.h KT_ST_ROWS, KT_SIDE_U32, KT_PAD_NORM)
 OperandLayout knn_operand_layout();
+std::vector<int32_t> knn_tile_order(int ntiles);           // the fixed pseudo-random order the operand's 32-row tiles are streamed in
 void l2_prepare(slideo_matcher::L2Set& L, const uint8_t* t, int nt, hipStream_t st);
 void l2_query(slideo_matcher* m, slideo_matcher::L2Set& L, const uint8_t* q_dev, int nq, int k, hipStream_t st, Slot& S, bool timed,
               DevBuf* keys = nullptr, DevBuf* pend = nullptr, float prune_tol = 0.f);

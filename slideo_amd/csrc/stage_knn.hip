@@ -10,8 +10,7 @@ using namespace slideo;
 namespace slideo {
 
 // ---- exact Hamming kNN: keys into S.d_keys[0 .. nq*KLIST) ------------------------------
-static int knn_pad_rows(int nt) { return cdiv(std::max(nt, 1), KT_ST_ROWS) * KT_ST_ROWS; }
-int knn_operand_rows(int nt) { return knn_pad_rows(nt); }
+int knn_operand_rows(int nt) { return cdiv(std::max(nt, 1), KT_ST_ROWS) * KT_ST_ROWS; }
 OperandLayout knn_operand_layout() { return OperandLayout{KT_ST_ROWS, KT_SIDE_U32, KT_PAD_NORM}; }
 
 void knn_expand_operand(const uint32_t* t, int nt, int nt_pad, const int32_t* perm, uint4* tx, hipStream_t st) {
@@ -19,15 +18,62 @@ void knn_expand_operand(const uint32_t* t, int nt, int nt_pad, const int32_t* pe
     check_launch("knn_tile_expand_kernel");
 }
 
+// The 32-row TILES of an operand (each of one norm, which is all the fast path needs) are streamed in a fixed pseudo-random order.
+// Streaming them in norm order is adversarial for the running thresholds: E[d] = |q| + |t| (1 - |q| / 128), so for every
+// query with more than 128 set bits the nearest rows would come LAST, the k-th distance would keep falling along the
+// stream and almost every tile would send some lane to the slow path (measured: 17.3 ms against 11.9 ms for the
+// +-1 engine on the headline launch).  A shuffled tile order makes the stream i.i.d. again for every query.  The L2 engine alike:
+// in norm order a query meets its neighbours — rows of about its own norm — only at its own place in the stream and keeps a loose
+// threshold until then.  The order depends on the tile count alone: a page set (stage_page_set.hip) draws the one a deck of its
+// pages would.
+std::vector<int32_t> knn_tile_order(int ntiles) {
+    std::vector<int32_t> order((size_t)ntiles);
+    for (int i = 0; i < ntiles; ++i) order[i] = i;
+    uint64_t st_ = 0x9E3779B97F4A7C15ull;
+    for (int i = ntiles - 1; i > 0; --i) {
+        st_ = st_ * 6364136223846793005ull + 1442695040888963407ull;
+        std::swap(order[i], order[(int)((st_ >> 33) % (uint64_t)(i + 1))]);
+    }
+    return order;
+}
+
+// The host side of an operand's build: `sorted` (the nt source rows in ascending norm order) put in tile order and padded to
+// op.nt_pad (-1: pad rows, which may then sit inside the stream: the partial last tile), the side array per super-tile ([norm |
+// row id]) and the per-tile bounds filled, all three uploaded.  enc(source row or -1, bound&): the side word of the row's norm and
+// the bound a tile takes from it when the row is the tile's first (ascending order: its smallest norm).  rowid (may be null): the
+// row number a key carries for a source row.  expand(): the caller's kernel that gathers op.tx through op.perm.
+template <class Enc, class Expand>
+static void operand_build(SearchOperand& op, const std::vector<int32_t>& sorted, const int32_t* rowid, Enc enc, Expand expand, hipStream_t st) {
+    const int nt = op.nt, nt_pad = op.nt_pad, n_st = nt_pad / KT_ST_ROWS;
+    const std::vector<int32_t> order = knn_tile_order(cdiv(nt, 32));
+    std::vector<int32_t> perm((size_t)nt_pad, -1);
+    for (size_t p = 0; p < order.size(); ++p)
+        for (int r = 0; r < 32; ++r) {
+            const size_t src = (size_t)order[p] * 32 + r;
+            if (src < (size_t)nt) perm[p * 32 + r] = sorted[src];
+        }
+    std::vector<uint32_t> side((size_t)n_st * KT_SIDE_U32), bound((size_t)n_st * 4);
+    for (int r = 0; r < nt_pad; ++r) {
+        uint32_t b;
+        side[(size_t)(r / KT_ST_ROWS) * KT_SIDE_U32 + (r % KT_ST_ROWS)] = enc(perm[r], b);
+        side[(size_t)(r / KT_ST_ROWS) * KT_SIDE_U32 + KT_ST_ROWS + (r % KT_ST_ROWS)] = (uint32_t)(perm[r] >= 0 && rowid ? rowid[perm[r]] : perm[r]);
+        if (r % 32 == 0) bound[r / 32] = b;
+    }
+    HIP_CHECK(hipMemcpyAsync(op.perm.p, perm.data(), perm.size() * 4, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(op.side.p, side.data(), side.size() * 4, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(op.bound.p, bound.data(), bound.size() * 4, hipMemcpyHostToDevice, st));
+    expand();
+    HIP_CHECK(hipStreamSynchronize(st));                                 // the host vectors die here
+}
+
 // Operand of the {0,1} x {0,1} engine (knn_tile.hip.h): rows in ascending popcount order (stable counting sort on the host:
 // nt x 32 bytes of popcounts), expanded to tile-major FP4 on the device, plus per super-tile the rows' norms and original
-// indices and per tile half its smallest norm.  `t_host`: the packed rows in host memory.
-struct TrainBits { DevBuf *tx, *side, *nminh, *perm; };
+// indices and per tile half its smallest norm; the tiles in the order of knn_tile_order (see there for why).  `t_host`: the packed
+// rows in host memory.
 // rowid (may be null): the row number a key carries for row i of t_host / t_dev (de-duplicated sets: the lowest original row).
 // norm_order (may be null): receives the nt rows' norm order before the tile shuffle (what a page set compacts, stage_page_set.hip)
-static void prepare_train_bits(const uint8_t* t_host, const uint32_t* t_dev, int nt, TrainBits o, hipStream_t st, const int32_t* rowid = nullptr,
+static void prepare_train_bits(const uint8_t* t_host, const uint32_t* t_dev, int nt, SearchOperand& op, hipStream_t st, const int32_t* rowid = nullptr,
                                std::vector<int32_t>* norm_order = nullptr) {
-    const int nt_pad = knn_pad_rows(nt), n_st = nt_pad / KT_ST_ROWS;
     std::vector<uint16_t> norm((size_t)std::max(nt, 1));
     uint32_t hist[258] = {0};
     for (int i = 0; i < nt; ++i) {
@@ -37,44 +83,15 @@ static void prepare_train_bits(const uint8_t* t_host, const uint32_t* t_dev, int
         norm[i] = (uint16_t)n; hist[n + 1]++;
     }
     for (int i = 0; i < 257; ++i) hist[i + 1] += hist[i];
-    std::vector<int32_t> perm((size_t)nt_pad, -1);
-    for (int i = 0; i < nt; ++i) perm[hist[norm[i]]++] = i;             // stable: ties keep row order
-    if (norm_order) norm_order->assign(perm.begin(), perm.begin() + nt);
-    {
-        // The 32-row TILES (each of one norm, which is all the fast path needs) are then put in a fixed pseudo-random order.
-        // Streaming them in norm order is adversarial for the running thresholds: E[d] = |q| + |t| (1 - |q| / 128), so for every
-        // query with more than 128 set bits the nearest rows would come LAST, the k-th distance would keep falling along the
-        // stream and almost every tile would send some lane to the slow path (measured: 17.3 ms against 11.9 ms for the
-        // +-1 engine on the headline launch).  A shuffled tile order makes the stream i.i.d. again for every query.
-        const int ntiles = cdiv(nt, 32);
-        std::vector<int32_t> order((size_t)ntiles), shuffled((size_t)nt_pad, -1);
-        for (int i = 0; i < ntiles; ++i) order[i] = i;
-        uint64_t st_ = 0x9E3779B97F4A7C15ull;
-        for (int i = ntiles - 1; i > 0; --i) {
-            st_ = st_ * 6364136223846793005ull + 1442695040888963407ull;
-            std::swap(order[i], order[(int)((st_ >> 33) % (uint64_t)(i + 1))]);
-        }
-        for (int p = 0; p < ntiles; ++p)
-            for (int r = 0; r < 32; ++r) shuffled[(size_t)p * 32 + r] = perm[(size_t)order[p] * 32 + r];   // (perm is -1 past nt: pad rows)
-        perm.swap(shuffled);
-    }
-    std::vector<uint32_t> side((size_t)n_st * KT_SIDE_U32);
-    std::vector<float> nminh((size_t)n_st * 4);
-    for (int r = 0; r < nt_pad; ++r) {
-        const float nf = perm[r] >= 0 ? (float)norm[perm[r]] : KT_PAD_NORM;     // (pad rows may now sit inside the stream: the partial last tile)
-        uint32_t bits; std::memcpy(&bits, &nf, 4);
-        side[(size_t)(r / KT_ST_ROWS) * KT_SIDE_U32 + (r % KT_ST_ROWS)] = bits;
-        side[(size_t)(r / KT_ST_ROWS) * KT_SIDE_U32 + KT_ST_ROWS + (r % KT_ST_ROWS)] = (uint32_t)(perm[r] >= 0 && rowid ? rowid[perm[r]] : perm[r]);
-        if (r % 32 == 0) nminh[r / 32] = 0.5f * nf;                      // ascending order: a tile's first row has its smallest norm
-    }
-    o.tx->reserve((size_t)nt_pad * 128); o.side->reserve(side.size() * 4 + 16); o.nminh->reserve(nminh.size() * 4 + 16);
-    o.perm->reserve(perm.size() * 4 + 16);
-    HIP_CHECK(hipMemcpyAsync(o.perm->p, perm.data(), perm.size() * 4, hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipMemcpyAsync(o.side->p, side.data(), side.size() * 4, hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipMemcpyAsync(o.nminh->p, nminh.data(), nminh.size() * 4, hipMemcpyHostToDevice, st));
-    knn_tile_expand_kernel<<<cdiv(nt_pad * 8, 256), 256, 0, st>>>(t_dev, nt, nt_pad, o.perm->as<int32_t>(), o.tx->as<uint4>());
-    check_launch("knn_tile_expand_kernel");
-    HIP_CHECK(hipStreamSynchronize(st));                                 // the host vectors die here
+    std::vector<int32_t> sorted((size_t)nt);
+    for (int i = 0; i < nt; ++i) sorted[hist[norm[i]]++] = i;             // stable: ties keep row order
+    if (norm_order) *norm_order = sorted;
+    op.reserve(nt, knn_operand_rows(nt), knn_operand_layout());
+    operand_build(op, sorted, rowid, [&](int32_t row, uint32_t& b) {
+        const float nf = row >= 0 ? (float)norm[row] : KT_PAD_NORM, half = 0.5f * nf;
+        uint32_t bits; std::memcpy(&bits, &nf, 4); std::memcpy(&b, &half, 4);
+        return bits;
+    }, [&] { knn_expand_operand(t_dev, nt, op.nt_pad, op.perm.as<int32_t>(), op.tx.as<uint4>(), st); }, st);
 }
 
 // slideo_config.matcher 1: the tables of FLANN's LshIndex over `nt` host rows (geom.h lsh_params / lsh_key_host), uploaded
@@ -132,141 +149,126 @@ void knn_probe_report() {
     (void)hipMemcpyToSymbol(HIP_SYMBOL(slideo::kt_probe), z, sizeof(z));
 }
 #endif
-static unsigned share_pad(const slideo_matcher* m, const Slot& S) { return (m->knn_share == 1 || (m->knn_share < 0 && S.u_shared)) ? KT_SHARE_PAD : 0u; }
+static unsigned share_pad(const slideo_matcher* m, bool shared) { return (m->knn_share == 1 || (m->knn_share < 0 && shared)) ? KT_SHARE_PAD : 0u; }
 // The block shape of the exact Hamming search (engine 3).  SHAPE_T2: knn_tile2_kernel, 8 waves x 2 query tiles, two blocks per CU or
 // — with the LDS pad — one.  SHAPE_T2W12 (by default for LARGE decks while units share the chip — knn_w12_ratio —; SLIDEO_KNN_SHARE=3 / 4 force it):
 // the same wave shape, 12 waves, one block per CU by its registers.  Only the exact search (matcher 0): the LSH-filtered stream has
-// its own kernel and plan.
+// its own kernel, the 8-wave shape and no LDS pad.
 enum KnnShape { SHAPE_T2 = 0, SHAPE_T2W12 = 1 };
-static KnnShape knn_shape(const slideo_matcher* m, const Slot& S) {
+static KnnShape knn_shape(const slideo_matcher* m, bool shared, bool w12) {
     if (m->cfg.matcher != 0) return SHAPE_T2;
-    if ((m->knn_share == 3 && S.u_shared) || m->knn_share == 4) return SHAPE_T2W12;
-    if (m->knn_share < 0 && S.u_shared && S.u_w12) return SHAPE_T2W12;       // large decks (runtime.hpp knn_w12_ratio)
+    if ((m->knn_share == 3 && shared) || m->knn_share == 4) return SHAPE_T2W12;
+    if (m->knn_share < 0 && shared && w12) return SHAPE_T2W12;       // large decks (knn_plan_unit)
     return SHAPE_T2;
 }
-static int shape_qpb(KnnShape sh) { return sh == SHAPE_T2W12 ? knn_qpb<2, KT_WAVES12>() : knn_qpb<2>(); }
-static int shape_waves(KnnShape sh) { return sh == SHAPE_T2W12 ? KT_WAVES12 : KT_WAVES; }
-struct KnnPlan { int engine, qblocks, nseg, per_seg; };
 // Engine 0 ("mfma") = the 2-tile wave shape (knn_tile2_kernel: 4 waves/SIMD, two 512-query blocks per CU) at every size: since the
 // {0,1} operand alphabet it runs the headline launch in 10.0 ms alone against 11.3 for the 4-tile shape and the step is 2 %
 // shorter.  The 4-tile shape (engine 2) and the VALU popcount kernel (engine 1) stay selectable for A/B: identical results.
-static int knn_engine_for(const slideo_matcher* m, int nq) {
-    if (m->knn_engine != 0) return m->knn_engine;
-    (void)nq;
-    return 3;
-}
-// nq: the query count the plan is made for (the real one, or its estimate when only the device knows it); nq_grid >= nq:
-// what the grid and the buffers are sized for (blocks past the device-side count leave at once)
-static KnnPlan knn_plan(const slideo_matcher* m, int nq, int nt, int nq_grid = 0, KnnShape sh = SHAPE_T2) {
+static int knn_engine_for(const slideo_matcher* m) { return m->knn_engine != 0 ? m->knn_engine : 3; }
+bool knn_unit_is_valu(const slideo_matcher* m) { return knn_engine_for(m) == 1; }
+
+// The plan of one search over nt train rows.  shared / w12: what the unit observed (KnnPlan).  nq: the query count the plan is made
+// for (the real one, or its estimate when only the device knows it); nq_grid >= nq: what the grid and the buffers are sized for
+// (blocks past the device-side count leave at once)
+static KnnPlan knn_plan(const slideo_matcher* m, bool shared, bool w12, int nq, int nt, int nq_grid = 0) {
     KnnPlan p{};
+    p.shared = shared; p.w12 = w12; p.nt = nt;
     nq = std::max(nq, 1);            // a unit may hold no keypoint at all (e.g. one flat frame)
-    nq_grid = std::max(nq_grid, nq);
-    p.engine = knn_engine_for(m, nq);
-    if (p.engine == 2 && nt > 0) {
-        // one block of 1024 queries per CU: split the train set when fewer query blocks than 3/4 of the CUs exist
-        p.qblocks = cdiv(nq, knn_qpb<4>());
-        const int n_st = knn_pad_rows(nt) / KT_ST_ROWS;
-        int nseg = p.qblocks >= 192 ? 1 : std::min(std::max(256 / std::max(p.qblocks, 1), 1), n_st);
-        p.per_seg = cdiv(n_st, std::max(nseg, 1));
-        p.nseg = cdiv(n_st, p.per_seg);
-        p.qblocks = cdiv(nq_grid, knn_qpb<4>());
-    } else if (p.engine == 3 && nt > 0) {
-        const int qpb = shape_qpb(sh);
-        const bool w12 = sh == SHAPE_T2W12;                              // (one block per CU whatever else runs: 256 slots)
-        p.qblocks = cdiv(nq, qpb);
-        const int n_st = knn_pad_rows(nt) / KT_ST_ROWS;
-        // the chip holds 512 blocks (two per CU).  From 3/4 of that on, one pass over the train set is best (every
+    p.nq_all = std::max(nq_grid, nq);
+    p.engine = nt > 0 ? knn_engine_for(m) : 1;
+    p.shape = knn_shape(m, shared, w12);
+    p.lds_pad = share_pad(m, shared);
+    if (p.engine != 1) {
+        const bool t4 = p.engine == 2, w12s = !t4 && p.shape == SHAPE_T2W12;
+        const int qpb = t4 ? knn_qpb<4>() : w12s ? knn_qpb<2, KT_WAVES12>() : knn_qpb<2>();
+        // the chip holds 512 blocks of the 8-wave 2-tile shape (two per CU); 256 of the 1024-query blocks of the 4-tile shape and of
+        // the 12-wave blocks (one per CU whatever else runs).  From 3/4 of that on, one pass over the train set is best (every
         // segment pays its own list warm-up and the merge); fewer query blocks split the train set so that the blocks
         // fill the chip in ONE round (floor, not ceil: 1.4 rounds of smaller blocks lose more to the tail than the
         // empty slots do).  Measured (r01): 236 query blocks x 1.8 M rows (64 4K frames): 1 segment 33.2 ms, 2 segments 24.2 ms,
         // 3 segments 23.5 ms; 239 query blocks x 517 k rows (128 1080p frames): 2 segments 6.24 ms, 3 segments 6.65 ms
-        int nseg = p.qblocks >= (w12 ? 192 : 384) ? 1 : std::min(std::max((w12 ? 256 : 512) / std::max(p.qblocks, 1), 1), n_st);
+        const int slots = t4 || w12s ? 256 : 512;
+        p.qblocks = cdiv(nq, qpb);
+        const int n_st = knn_operand_rows(nt) / KT_ST_ROWS;
+        const int nseg = p.qblocks >= slots * 3 / 4 ? 1 : std::min(std::max(slots / std::max(p.qblocks, 1), 1), n_st);
         p.per_seg = cdiv(n_st, std::max(nseg, 1));
         p.nseg = cdiv(n_st, p.per_seg);
-        p.qblocks = cdiv(nq_grid, qpb);
+        p.qblocks = cdiv(p.nq_all, qpb);
     } else {
-        p.engine = 1;
         p.qblocks = cdiv(nq, KNN_BLOCK);
         int nseg = 1;
         if (p.qblocks < 1024) nseg = std::min(cdiv(1024, p.qblocks), std::max(1, nt / 4096));
         p.nseg = std::max(1, std::min(nseg, 256));
         p.per_seg = cdiv(std::max(nt, 1), p.nseg);
-        p.qblocks = cdiv(nq_grid, KNN_BLOCK);
+        p.qblocks = cdiv(p.nq_all, KNN_BLOCK);
     }
     return p;
 }
 
-static void knn_reserve(slideo_matcher* m, Slot& S, int nq, int nt, int nq_grid = 0) {
-    // (always for the plan that is launched: knn_shape is SHAPE_T2 for the LSH-filtered stream, whose launch plans without a shape)
-    const KnnShape sh = knn_shape(m, S);
-    const KnnPlan p = knn_plan(m, nq, nt, nq_grid, sh);
-    S.d_keys.reserve((size_t)p.nseg * std::max(std::max(nq, nq_grid), 1) * KLIST * 4);
+static void knn_reserve(Slot& S, const KnnPlan& p) {
+    S.d_keys.reserve((size_t)p.nseg * p.nq_all * KLIST * 4);
     if (p.engine == 2) S.d_knn_pend.reserve((size_t)p.qblocks * p.nseg * KT_WAVES * knn_pend_words_per_wave<4>() * 4);
-    if (p.engine == 3) S.d_knn_pend.reserve((size_t)p.qblocks * p.nseg * shape_waves(sh) * knn_pend_words_per_wave<2>() * 4);
+    if (p.engine == 3) S.d_knn_pend.reserve((size_t)p.qblocks * p.nseg * (p.shape == SHAPE_T2W12 ? KT_WAVES12 : KT_WAVES) * knn_pend_words_per_wave<2>() * 4);
 }
 
-// prune_tol > 0: only neighbours that can pass the vote's `d < best * tol` need to be exact (matrix-core engine; the VALU
-// engine always returns full lists)
-struct TrainOps {             // device operands of one train set, per engine
-    const uint32_t* t;        // packed [nt][8] (VALU engine)
-    const uint4* txb;         // {0,1} FP4 expansion in norm order + side arrays (knn_tile.hip.h)
-    const uint32_t* side;
-    const float4* nminh;
-};
+void knn_plan_unit(slideo_matcher* m, Slot& S, int n, int64_t frame_pixels, uint32_t qplan, uint32_t qtot) {
+    // (the matrix-core engine searches the unique rows of the train set, the VALU engine — A/B only — all of them; a page set — never
+    // under the VALU engine, page_set_check_mode — its own distinct rows)
+    const PageSet* ps = page_set_of(m, S.u_set);
+    const bool dedup = ps ? ps->urows < ps->rows : (m->Mu < m->M && !knn_unit_is_valu(m));
+    const int nt = (int)(ps ? ps->urows : dedup ? m->Mu : m->M);
+    // While units share the chip the search runs the 12-wave block (three waves per SIMD, 128 registers each) instead of the 8-wave
+    // block + LDS pad when a unit carries at least knn_w12_ratio (query, train row) pairs per frame pixel — how much search there is
+    // per pixel of ORB work: the larger the deck, the more of a step is search, and from ~290 pairs per pixel on the fuller matrix
+    // pipe is worth more than the co-runners' occupancy (profiles/r06_experiments.txt 7: headline 197: - 2..4 %; 700 pages 275:
+    // - 1.7 %; 800 pages 314: + 5.5 %; configs[3] 392: + 6.8 %; configs[4] 352: + 4.7 %).  SLIDEO_KNN_W12_RATIO overrides (0 = never).
+    const bool w12 = m->knn_w12_ratio > 0.0 && (double)qplan * (double)nt >= m->knn_w12_ratio * (double)n * (double)frame_pixels;
+    S.knn = knn_plan(m, S.knn.shared, w12, (int)qplan, nt, (int)qtot);
+    S.knn.dedup = dedup;
+    knn_reserve(S, S.knn);
+}
 
-// nq_dev != null: the real query count lives on the device (the host did not wait for the ORB counts); then `nq` is the
-// estimate the plan is made for and nq_grid the capacity the grid and the buffers cover.  Only the matrix-core engine.
-static void run_knn(slideo_matcher* m, Slot& S, const uint32_t* q_dev, int nq, const TrainOps& T, int nt, float prune_tol,
-             const uint32_t* nq_dev = nullptr, int nq_grid = 0) {
-    if (nq <= 0 && !nq_dev) return;
+// The matrix-core search over `op` as p plans it, then the merge of its segments' lists.  lsh: the LSH-filtered stream's context
+// (its own kernel) or null: the exact search in p's engine and block shape.  nq_dev != null: the real query count lives on the
+// device (the host did not wait for the ORB counts); then `nq` is the estimate the plan was made for.
+static void knn_launch_tiles(slideo_matcher* m, Slot& S, const KnnPlan& p, const uint32_t* q_dev, int nq, const SearchOperand& op, float prune_tol,
+                             const uint32_t* nq_dev, const KtLshCtx* lsh = nullptr) {
     hipStream_t st = S.st;
-    if ((int64_t)nt >= ((int64_t)1 << KNN_KEY_SHIFT)) fail(SLIDEO_ERR_UNSUPPORTED, "train set of %d rows exceeds %d", nt, 1 << KNN_KEY_SHIFT);
-    const KnnShape sh = knn_shape(m, S);
-    const KnnPlan p = knn_plan(m, nq, nt, nq_grid, sh);
-    knn_reserve(m, S, nq, nt, nq_grid);
-    const int nq_all = std::max(std::max(nq, nq_grid), 1);
+    const dim3 grid(p.qblocks, p.nseg);
+    const uint4* tx = op.tx.as<uint4>(); const uint32_t* side = op.side.as<uint32_t>(); const float4* nminh = op.bound.as<float4>();
+    const int nt_pad = knn_operand_rows(p.nt);
+    uint32_t *keys = S.d_keys.as<uint32_t>(), *pend = S.d_knn_pend.as<uint32_t>();
     unsigned long long* const clk = m->profiling ? m->d_clk.as<unsigned long long>() : nullptr;      // (slideo_matcher_read_shader_clock)
-    if ((p.engine == 2 || p.engine == 3) && nt > 0) {
-        if (p.engine == 2)
-            knn_tile4_kernel<<<dim3(p.qblocks, p.nseg), KT_THREADS, 0, st>>>(q_dev, nq, T.txb, T.side, T.nminh, knn_pad_rows(nt), p.per_seg,
-                                                                             S.d_keys.as<uint32_t>(), S.d_knn_pend.as<uint32_t>(), prune_tol, nq_dev);
-        else if (sh == SHAPE_T2W12)
-            knn_tile2w12_kernel<<<dim3(p.qblocks, p.nseg), KT_WAVES12 * 64, 0, st>>>(q_dev, nq, T.txb, T.side, T.nminh, knn_pad_rows(nt), p.per_seg,
-                                                                             S.d_keys.as<uint32_t>(), S.d_knn_pend.as<uint32_t>(), prune_tol, nq_dev, clk);
-        else
-            knn_tile2_kernel<<<dim3(p.qblocks, p.nseg), KT_THREADS, share_pad(m, S), st>>>(q_dev, nq, T.txb, T.side, T.nminh, knn_pad_rows(nt), p.per_seg,
-                                                                             S.d_keys.as<uint32_t>(), S.d_knn_pend.as<uint32_t>(), prune_tol, nq_dev, clk);
-        check_launch("knn_tile_kernel");
-        if (p.nseg > 1) {
-            knn_merge_kernel<KLIST><<<cdiv(nq_all, KNN_BLOCK), KNN_BLOCK, 0, st>>>(S.d_keys.as<uint32_t>(), nq, p.nseg, nq_dev);
-            check_launch("knn_merge_kernel");
-        }
-        return;
-    }
-    if (nq_dev) fail(SLIDEO_ERR_STATE, "internal: the VALU kNN engine needs the query count on the host");
-    knn_hamming_kernel<KLIST><<<dim3(p.qblocks, p.nseg), KNN_BLOCK, 0, st>>>(q_dev, nq, T.t, nt, p.per_seg, S.d_keys.as<uint32_t>());
-    check_launch("knn_hamming_kernel");
+    if (lsh)
+        knn_tile2_lsh_kernel<<<grid, KT_THREADS, 0, st>>>(q_dev, nq, tx, side, nminh, nt_pad, p.per_seg, keys, pend, prune_tol, nq_dev, *lsh);
+    else if (p.engine == 2)
+        knn_tile4_kernel<<<grid, KT_THREADS, 0, st>>>(q_dev, nq, tx, side, nminh, nt_pad, p.per_seg, keys, pend, prune_tol, nq_dev);
+    else if (p.shape == SHAPE_T2W12)
+        knn_tile2w12_kernel<<<grid, KT_WAVES12 * 64, 0, st>>>(q_dev, nq, tx, side, nminh, nt_pad, p.per_seg, keys, pend, prune_tol, nq_dev, clk);
+    else
+        knn_tile2_kernel<<<grid, KT_THREADS, p.lds_pad, st>>>(q_dev, nq, tx, side, nminh, nt_pad, p.per_seg, keys, pend, prune_tol, nq_dev, clk);
+    check_launch(lsh ? "knn_tile2_lsh_kernel" : "knn_tile_kernel");
     if (p.nseg > 1) {
-        knn_merge_kernel<KLIST><<<p.qblocks, KNN_BLOCK, 0, st>>>(S.d_keys.as<uint32_t>(), nq, p.nseg);
+        knn_merge_kernel<KLIST><<<cdiv(p.nq_all, KNN_BLOCK), KNN_BLOCK, 0, st>>>(keys, nq, p.nseg, nq_dev);
         check_launch("knn_merge_kernel");
     }
 }
 
-bool knn_unit_is_valu(const slideo_matcher* m, int nq) { return knn_engine_for(m, nq) == 1; }
-
-// (the matrix-core engine searches the unique rows of the train set, the VALU engine — A/B only — all of them; a page set — never
-// under the VALU engine, page_set_check_mode — its own distinct rows)
-static bool knn_unit_dedup(const slideo_matcher* m, int nq, int set = 0) {
-    if (const PageSet* ps = page_set_of(m, set)) return ps->urows < ps->rows;
-    return m->Mu < m->M && knn_engine_for(m, nq) != 1;
-}
-int knn_unit_rows(const slideo_matcher* m, int nq, int set) {
-    if (const PageSet* ps = page_set_of(m, set)) return (int)ps->urows;
-    return (int)(knn_unit_dedup(m, nq) ? m->Mu : m->M);
-}
-
-void knn_reserve_unit(slideo_matcher* m, Slot& S, uint32_t qplan, uint32_t qtot) {
-    knn_reserve(m, S, (int)qplan, knn_unit_rows(m, (int)qplan, S.u_set), (int)qtot);
+// The exact search as p plans it (its workspace reserved): q_dev -> S.d_keys.  t: the packed rows (VALU engine), op: their operand
+// (matrix-core engines).  prune_tol > 0: only neighbours that can pass the vote's `d < best * tol` need to be exact (matrix-core
+// engine; the VALU engine always returns full lists).  nq_dev: see knn_launch_tiles; only the matrix-core engine.
+static void run_knn(slideo_matcher* m, Slot& S, const KnnPlan& p, const uint32_t* q_dev, int nq, const uint32_t* t, const SearchOperand& op,
+                    float prune_tol, const uint32_t* nq_dev = nullptr) {
+    if (nq <= 0 && !nq_dev) return;
+    if ((int64_t)p.nt >= ((int64_t)1 << KNN_KEY_SHIFT)) fail(SLIDEO_ERR_UNSUPPORTED, "train set of %d rows exceeds %d", p.nt, 1 << KNN_KEY_SHIFT);
+    if (p.engine != 1) { knn_launch_tiles(m, S, p, q_dev, nq, op, prune_tol, nq_dev); return; }
+    if (nq_dev) fail(SLIDEO_ERR_STATE, "internal: the VALU kNN engine needs the query count on the host");
+    knn_hamming_kernel<KLIST><<<dim3(p.qblocks, p.nseg), KNN_BLOCK, 0, S.st>>>(q_dev, nq, t, p.nt, p.per_seg, S.d_keys.as<uint32_t>());
+    check_launch("knn_hamming_kernel");
+    if (p.nseg > 1) {
+        knn_merge_kernel<KLIST><<<p.qblocks, KNN_BLOCK, 0, S.st>>>(S.d_keys.as<uint32_t>(), nq, p.nseg);
+        check_launch("knn_merge_kernel");
+    }
 }
 
 // A unit's search: S.d_desc (n frames' descriptors, offsets S.d_qofs) -> S.d_keys.  async: the real query count lives on the
@@ -274,43 +276,34 @@ void knn_reserve_unit(slideo_matcher* m, Slot& S, uint32_t qplan, uint32_t qtot)
 void unit_knn(slideo_matcher* m, Slot& S, int n, uint32_t qplan, uint32_t qtot, bool async, bool prof) {
     const slideo_config& c = m->cfg;
     hipStream_t st = S.st;
+    const KnnPlan& p = S.knn;
     const PageSet* ps = page_set_of(m, S.u_set);            // (the unit's page set: its operand and chain instead of the deck's)
-    const bool dedup = knn_unit_dedup(m, (int)qplan, S.u_set);
-    const int nt_knn = knn_unit_rows(m, (int)qplan, S.u_set);
+    const SearchOperand& op = ps ? ps->op : m->train_op;
+    const uint32_t* nqd = async ? S.d_qofs.as<uint32_t>() + n : nullptr;
     // a neighbour counts iff d < best * vote_tolerance (verify.hip.h vote_kernel); with tolerance < 1 rows below the
     // current best must still be kept, hence max(tol, 1)
     // (the ratio test needs the exact two nearest rows: exact lists)
     const float prune = (m->knn_exact_lists || m->cfg.ratio_test > 0.f) ? 0.f : std::max(m->cfg.vote_tolerance, 1.0f);
-    const TrainOps T = ps ? TrainOps{nullptr, ps->d_trainb.as<uint4>(), ps->d_side.as<uint32_t>(), ps->d_nminh.as<float4>()}
-                          : TrainOps{m->d_train.as<uint32_t>(), m->d_trainb.as<uint4>(), m->d_train_side.as<uint32_t>(), m->d_train_nminh.as<float4>()};
-    if (c.matcher == 1 && (m->lsh_gather || knn_engine_for(m, (int)qplan) == 1)) {
+    if (c.matcher == 1 && (m->lsh_gather || knn_unit_is_valu(m))) {
         // the reference's index, gathered: only the LSH candidates of a query are scored (knn_lsh.hip.h); same key lists out
         knn_lsh_kernel<KLIST><<<cdiv((int)std::max(qtot, 1u), 4), 256, 0, st>>>(m->lsh.dev, S.d_desc.as<uint32_t>(), (int)qtot, m->d_train.as<uint32_t>(),
-                                                                               S.d_keys.as<uint32_t>(), async ? S.d_qofs.as<uint32_t>() + n : nullptr);
+                                                                               S.d_keys.as<uint32_t>(), nqd);
         check_launch("knn_lsh_kernel");
     } else if (c.matcher == 1) {
         // the same result from the matrix-core stream over ALL rows with the candidate rule applied where a row passes the
         // distance test (KtHammingLsh): a fifth of all rows are candidates of a query on these descriptors (skewed buckets),
         // so gathering them is 60x slower than streaming everything
-        const uint32_t* nqd = async ? S.d_qofs.as<uint32_t>() + n : nullptr;
         S.d_qkeys.reserve(std::max<size_t>((size_t)qtot * c.lsh_tables * 2, 64));
         lsh_query_keys_kernel<<<cdiv((int)std::max(qtot, 1u), 256), 256, 0, st>>>(m->lsh.dev.p, S.d_desc.as<uint32_t>(), (int)qtot, S.d_qkeys.as<uint16_t>(), nqd);
         check_launch("lsh_query_keys_kernel");
-        const KnnPlan p = knn_plan(m, (int)qplan, nt_knn, (int)qtot);
         const KtLshCtx ctx{m->lsh.dev.keys, S.d_qkeys.as<uint16_t>(), c.lsh_tables, c.lsh_multi_probe};
-        knn_tile2_lsh_kernel<<<dim3(p.qblocks, p.nseg), KT_THREADS, 0, st>>>(S.d_desc.as<uint32_t>(), (int)qplan, T.txb, T.side, T.nminh, knn_pad_rows(nt_knn), p.per_seg,
-                                                                             S.d_keys.as<uint32_t>(), S.d_knn_pend.as<uint32_t>(), prune, nqd, ctx);
-        check_launch("knn_tile2_lsh_kernel");
-        if (p.nseg > 1) {
-            knn_merge_kernel<KLIST><<<cdiv((int)std::max(qtot, 1u), KNN_BLOCK), KNN_BLOCK, 0, st>>>(S.d_keys.as<uint32_t>(), (int)qplan, p.nseg, nqd);
-            check_launch("knn_merge_kernel");
-        }
+        knn_launch_tiles(m, S, p, S.d_desc.as<uint32_t>(), (int)qplan, op, prune, nqd, &ctx);
     } else
-        run_knn(m, S, S.d_desc.as<uint32_t>(), (int)qplan, T, nt_knn, prune, async ? S.d_qofs.as<uint32_t>() + n : nullptr, (int)qtot);
+        run_knn(m, S, p, S.d_desc.as<uint32_t>(), (int)qplan, ps ? nullptr : m->d_train.as<uint32_t>(), op, prune, nqd);
     if (prof) HIP_CHECK(hipEventRecord(S.ev[2], st));      // the kNN interval ends here: the search kernel (+ its segment merge)
-    if (dedup) {
+    if (p.dedup) {
         knn_expand_dups_kernel<KLIST><<<cdiv((int)std::max(qtot, 1u), KNN_BLOCK), KNN_BLOCK, 0, st>>>(
-            S.d_keys.as<uint32_t>(), (int)qtot, (ps ? ps->d_grp_next : m->d_grp_next).as<int32_t>(), async ? S.d_qofs.as<uint32_t>() + n : nullptr);
+            S.d_keys.as<uint32_t>(), (int)qtot, (ps ? ps->d_grp_next : m->d_grp_next).as<int32_t>(), nqd);
         check_launch("knn_expand_dups_kernel");
     }
 }
@@ -345,12 +338,10 @@ void knn_build_index(slideo_matcher* m, const std::vector<uint8_t>& train, int64
         for (int64_t i = 0; i < m->Mu; ++i) std::memcpy(utrain.data() + (size_t)i * 32, train.data() + (size_t)urow[i] * 32, 32);
         m->d_utrain.reserve(utrain.size() + 64);
         HIP_CHECK(hipMemcpy(m->d_utrain.p, utrain.data(), utrain.size(), hipMemcpyHostToDevice));
-        prepare_train_bits(utrain.data(), m->d_utrain.as<uint32_t>(), (int)m->Mu, TrainBits{&m->d_trainb, &m->d_train_side, &m->d_train_nminh, &m->d_train_perm},
-                           m->stream, urow.data(), &m->h_uorder);
+        prepare_train_bits(utrain.data(), m->d_utrain.as<uint32_t>(), (int)m->Mu, m->train_op, m->stream, urow.data(), &m->h_uorder);
         m->h_urow.swap(urow);                                              // (page sets: distinct row -> its head row)
     } else {
-        prepare_train_bits(train.data(), m->d_train.as<uint32_t>(), (int)M, TrainBits{&m->d_trainb, &m->d_train_side, &m->d_train_nminh, &m->d_train_perm}, m->stream,
-                           nullptr, &m->h_uorder);
+        prepare_train_bits(train.data(), m->d_train.as<uint32_t>(), (int)M, m->train_op, m->stream, nullptr, &m->h_uorder);
         m->h_urow.clear();                                                 // (every row is its own head)
     }
     HIP_CHECK(hipStreamSynchronize(m->stream));
@@ -358,54 +349,38 @@ void knn_build_index(slideo_matcher* m, const std::vector<uint8_t>& train, int64
 
 // ---- L2 k-NN (cfg2): train set prepared once, queries from device memory ----
 void l2_prepare(slideo_matcher::L2Set& L, const uint8_t* t, int nt, hipStream_t st) {
-    const int nt_pad = knn_pad_rows(nt);
+    SearchOperand& op = L.op;
     DevBuf d_t, d_norm;
     d_t.reserve(std::max<size_t>((size_t)nt * 128, 64)); d_norm.reserve(std::max<size_t>((size_t)nt * 4, 64));
-    L.d_tx.reserve((size_t)nt_pad * 128); L.d_perm.reserve((size_t)nt_pad * 4);
+    op.reserve(nt, knn_operand_rows(nt), knn_operand_layout(), 0);
     // norms on the device, the norm order on the host (a stable index sort), then the centred tile-major operand gathered in
-    // that order
-    std::vector<int32_t> h_norm((size_t)std::max(nt, 1)), h_perm((size_t)nt_pad, -1);
+    // that order, its tiles shuffled (knn_tile_order)
+    std::vector<int32_t> h_norm((size_t)std::max(nt, 1)), sorted((size_t)nt);
     if (nt) {
         HIP_CHECK(hipMemcpyAsync(d_t.p, t, (size_t)nt * 128, hipMemcpyHostToDevice, st));
         knl_norms_kernel<<<cdiv(nt, 256), 256, 0, st>>>(d_t.as<uint8_t>(), nt, d_norm.as<int32_t>());
         check_launch("knl_norms_kernel");
         HIP_CHECK(hipMemcpyAsync(h_norm.data(), d_norm.p, (size_t)nt * 4, hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipStreamSynchronize(st));
-        for (int i = 0; i < nt; ++i) h_perm[i] = i;
-        std::stable_sort(h_perm.begin(), h_perm.begin() + nt, [&](int32_t a, int32_t b) { return h_norm[a] < h_norm[b]; });
-        // the 32-row tiles (each of nearly one norm, which is all the fast path needs) in a fixed pseudo-random order: streamed in
-        // norm order a query meets its neighbours — rows of about its own norm — only at its own place in the stream and keeps a
-        // loose threshold until then (the Hamming engine's finding, prepare_train_bits)
-        const int ntiles = cdiv(nt, 32);
-        std::vector<int32_t> order((size_t)ntiles), shuffled((size_t)nt_pad, -1);
-        for (int i = 0; i < ntiles; ++i) order[i] = i;
-        uint64_t st_ = 0x9E3779B97F4A7C15ull;
-        for (int i = ntiles - 1; i > 0; --i) {
-            st_ = st_ * 6364136223846793005ull + 1442695040888963407ull;
-            std::swap(order[i], order[(int)((st_ >> 33) % (uint64_t)(i + 1))]);
-        }
-        for (int p = 0; p < ntiles; ++p)
-            for (int r = 0; r < 32; ++r) shuffled[(size_t)p * 32 + r] = h_perm[(size_t)order[p] * 32 + r];
-        h_perm.swap(shuffled);
+        for (int i = 0; i < nt; ++i) sorted[i] = i;
+        std::stable_sort(sorted.begin(), sorted.end(), [&](int32_t a, int32_t b) { return h_norm[a] < h_norm[b]; });
     }
     // the side array of the tile engine (knn_tile.hip.h): per super-tile 128 negated norms (as i32) and 128 original rows; and
     // per tile the negated norm of its first row (the tile's bound: rows ascend inside a tile)
-    const int n_st = nt_pad / KT_ST_ROWS;
-    std::vector<uint32_t> side((size_t)n_st * KT_SIDE_U32), tnorm((size_t)n_st * 4);
-    for (int r = 0; r < nt_pad; ++r) {
-        const int32_t nn = h_perm[r] >= 0 ? -h_norm[h_perm[r]] : -KNL_PAD_NORM;
-        side[(size_t)(r / KT_ST_ROWS) * KT_SIDE_U32 + (r % KT_ST_ROWS)] = (uint32_t)nn;
-        side[(size_t)(r / KT_ST_ROWS) * KT_SIDE_U32 + KT_ST_ROWS + (r % KT_ST_ROWS)] = (uint32_t)h_perm[r];
-        if (r % 32 == 0) tnorm[r / 32] = (uint32_t)nn;
-    }
-    L.d_side.reserve(side.size() * 4 + 16); L.d_tn.reserve(tnorm.size() * 4 + 16);
-    HIP_CHECK(hipMemcpyAsync(L.d_side.p, side.data(), side.size() * 4, hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipMemcpyAsync(L.d_tn.p, tnorm.data(), tnorm.size() * 4, hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipMemcpyAsync(L.d_perm.p, h_perm.data(), (size_t)nt_pad * 4, hipMemcpyHostToDevice, st));
-    knl_expand_train_kernel<<<cdiv(nt_pad * 8, 256), 256, 0, st>>>(d_t.as<uint8_t>(), nt_pad, L.d_perm.as<int32_t>(), L.d_tx.as<uint4>());
-    check_launch("knl_expand_train_kernel");
-    HIP_CHECK(hipStreamSynchronize(st));            // d_t / d_norm / the host vectors go out of scope
-    L.nt = nt; L.nt_pad = nt_pad; L.ready = true;
+    operand_build(op, sorted, nullptr, [&](int32_t row, uint32_t& b) { return b = (uint32_t)(row >= 0 ? -h_norm[row] : -KNL_PAD_NORM); }, [&] {
+        knl_expand_train_kernel<<<cdiv(op.nt_pad * 8, 256), 256, 0, st>>>(d_t.as<uint8_t>(), op.nt_pad, op.perm.as<int32_t>(), op.tx.as<uint4>());
+        check_launch("knl_expand_train_kernel");
+    }, st);                                          // (synchronised: d_t / d_norm go out of scope)
+    L.ready = true;
+}
+
+// list length of the kernel instance that serves k neighbours (see knn_l2.hip.h)
+static int l2_list_len(int k) { return k <= 8 ? 8 : (k <= 16 ? 16 : KLIST); }
+
+template <int KL>
+static void launch_knn_l2(int qblocks, hipStream_t st, const uint8_t* q_dev, int nq, const SearchOperand& op, DevBuf* keys, DevBuf* pend, float prune_tol) {
+    knn_l2_kernel<KL><<<qblocks, KT_THREADS, 0, st>>>(q_dev, nq, op.tx.as<uint4>(), op.side.as<uint32_t>(), op.bound.as<uint4>(), op.nt_pad,
+                                                      keys->as<unsigned long long>(), pend->as<unsigned long long>(), prune_tol);
 }
 
 // queries on the device -> idx / dist on the device (m->d_tapidx / d_tapdist); kernel time between two events if asked for
@@ -419,16 +394,12 @@ void l2_query(slideo_matcher* m, slideo_matcher::L2Set& L, const uint8_t* q_dev,
     keys->reserve((size_t)nq * KLIST * 8); pend->reserve((size_t)qblocks * KT_WAVES * knn_pend_words_per_wave<2>() * 8);   // (u64 keys)
     if (own) { m->d_tapidx.reserve((size_t)nq * k * 4); m->d_tapdist.reserve((size_t)nq * k * 4); }
     if (timed) HIP_CHECK(hipEventRecord(S.ev[0], st));
-    const int kl = k <= 8 ? 8 : (k <= 16 ? 16 : KLIST);      // list length of the kernel instance (see knn_l2.hip.h)
-    if (kl == 8)
-        knn_l2_kernel<8><<<qblocks, KT_THREADS, 0, st>>>(q_dev, nq, L.d_tx.as<uint4>(), L.d_side.as<uint32_t>(), L.d_tn.as<uint4>(), L.nt_pad,
-                                                          keys->as<unsigned long long>(), pend->as<unsigned long long>(), prune_tol);
-    else if (kl == 16)
-        knn_l2_kernel<16><<<qblocks, KT_THREADS, 0, st>>>(q_dev, nq, L.d_tx.as<uint4>(), L.d_side.as<uint32_t>(), L.d_tn.as<uint4>(), L.nt_pad,
-                                                           keys->as<unsigned long long>(), pend->as<unsigned long long>(), prune_tol);
-    else
-        knn_l2_kernel<KLIST><<<qblocks, KT_THREADS, 0, st>>>(q_dev, nq, L.d_tx.as<uint4>(), L.d_side.as<uint32_t>(), L.d_tn.as<uint4>(), L.nt_pad,
-                                                              keys->as<unsigned long long>(), pend->as<unsigned long long>(), prune_tol);
+    const int kl = l2_list_len(k);
+    switch (kl) {
+        case 8: launch_knn_l2<8>(qblocks, st, q_dev, nq, L.op, keys, pend, prune_tol); break;
+        case 16: launch_knn_l2<16>(qblocks, st, q_dev, nq, L.op, keys, pend, prune_tol); break;
+        default: launch_knn_l2<KLIST>(qblocks, st, q_dev, nq, L.op, keys, pend, prune_tol);
+    }
     check_launch("knn_l2_kernel");
     if (own) {
         knl_unpack_kernel<<<cdiv(nq * k, 256), 256, 0, st>>>(keys->as<unsigned long long>(), nq, kl, k, m->d_tapidx.as<int32_t>(), m->d_tapdist.as<uint32_t>());
@@ -440,7 +411,7 @@ void l2_query(slideo_matcher* m, slideo_matcher::L2Set& L, const uint8_t* q_dev,
 // SIFT matcher mode: the outcome of the vote rule on the L2 lists (u64 keys, kl per query) as neighbour lists in the HAMMING key
 // format, so that the vote kernel and everything after it run unchanged (knn_l2.hip.h l2_ratio_keys_kernel / l2_tol_keys_kernel)
 void l2_lists_to_keys(slideo_matcher* m, Slot& S, const DevBuf& lists, int kq, uint32_t qtot, bool lowe, hipStream_t st) {
-    const int kl = kq <= 8 ? 8 : (kq <= 16 ? 16 : KLIST);                 // (the list length of the instance l2_query picked)
+    const int kl = l2_list_len(kq);                                       // (the instance l2_query picked)
     if (lowe)
         l2_ratio_keys_kernel<<<cdiv((int)qtot, 256), 256, 0, st>>>(lists.as<unsigned long long>(), kl, (int)qtot, m->sift_ratio, S.d_keys.as<uint32_t>(), KLIST);
     else
@@ -450,61 +421,67 @@ void l2_lists_to_keys(slideo_matcher* m, Slot& S, const DevBuf& lists, int kq, u
 
 }  // namespace slideo
 
+// The argument rules the k-NN taps share
+static void tap_check_args(const void* q, int nq, const void* t, int nt, int k, const void* idx_out, const void* dist_out) {
+    if (nq < 0 || nt < 0 || k < 1 || k > KLIST) fail(SLIDEO_ERR_INVALID_ARG, "bad nq/nt/k (k must be 1..%d)", KLIST);
+    if ((nq && !q) || (nt && !t) || (nq && (!idx_out || !dist_out))) fail(SLIDEO_ERR_INVALID_ARG, "null argument");
+}
+
+// The two taps over 32-byte descriptors, on slot 0: queries and train rows to m->d_tapq / d_tapt (t_slack bytes behind the rows),
+// search(S) fills S.d_keys with nq whole key lists, their first k entries unpacked and downloaded.
+template <class Search>
+static void tap_hamming(slideo_matcher* m, const uint8_t* q, int nq, const uint8_t* t, int nt, int k, int32_t* idx_out, uint16_t* dist_out, size_t t_slack,
+                        Search search) {
+    HIP_CHECK(hipSetDevice(m->device));
+    require_idle(m);
+    Slot& S = m->slots[0];
+    hipStream_t st = S.st;
+    m->d_tapq.reserve((size_t)nq * 32); m->d_tapt.reserve(std::max<size_t>((size_t)nt * 32, 64) + t_slack);
+    HIP_CHECK(hipMemcpyAsync(m->d_tapq.p, q, (size_t)nq * 32, hipMemcpyHostToDevice, st));
+    if (nt) HIP_CHECK(hipMemcpyAsync(m->d_tapt.p, t, (size_t)nt * 32, hipMemcpyHostToDevice, st));
+    search(S);
+    m->d_tapidx.reserve((size_t)nq * k * 4); m->d_tapdist.reserve((size_t)nq * k * 2);
+    knn_unpack_kernel<<<cdiv(nq * k, 256), 256, 0, st>>>(S.d_keys.as<uint32_t>(), nq, KLIST, k, m->d_tapidx.as<int32_t>(), m->d_tapdist.as<uint16_t>());
+    check_launch("knn_unpack_kernel");
+    HIP_CHECK(hipMemcpyAsync(idx_out, m->d_tapidx.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(dist_out, m->d_tapdist.p, (size_t)nq * k * 2, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+}
+
 extern "C" {
 
 int32_t slideo_knn_hamming(slideo_matcher* m, const uint8_t* q, int32_t nq, const uint8_t* t, int32_t nt, int32_t k,
                            int32_t* idx_out, uint16_t* dist_out) {
     if (!m) return SLIDEO_ERR_INVALID_ARG;
     API_TRY
-    if (nq < 0 || nt < 0 || k < 1 || k > KLIST) fail(SLIDEO_ERR_INVALID_ARG, "bad nq/nt/k (k must be 1..%d)", KLIST);
-    if ((nq && !q) || (nt && !t) || (nq && (!idx_out || !dist_out))) fail(SLIDEO_ERR_INVALID_ARG, "null argument");
+    tap_check_args(q, nq, t, nt, k, idx_out, dist_out);
     if (nq == 0) return SLIDEO_OK;
-    HIP_CHECK(hipSetDevice(m->device));
-    require_idle(m);
-    Slot& S = m->slots[0];
-    hipStream_t st = S.st;
-    m->d_tapq.reserve((size_t)nq * 32); m->d_tapt.reserve(std::max<size_t>((size_t)nt * 32, 64));
-    HIP_CHECK(hipMemcpyAsync(m->d_tapq.p, q, (size_t)nq * 32, hipMemcpyHostToDevice, st));
-    if (nt) HIP_CHECK(hipMemcpyAsync(m->d_tapt.p, t, (size_t)nt * 32, hipMemcpyHostToDevice, st));
-    DevBuf tapb, tap_side, tap_nminh, tap_perm;
-    if (knn_engine_for(m, nq) != 1 && nt > 0) prepare_train_bits(t, m->d_tapt.as<uint32_t>(), nt, TrainBits{&tapb, &tap_side, &tap_nminh, &tap_perm}, st);
-    run_knn(m, S, m->d_tapq.as<uint32_t>(), nq, TrainOps{m->d_tapt.as<uint32_t>(), tapb.as<uint4>(), tap_side.as<uint32_t>(), tap_nminh.as<float4>()}, nt, 0.f);
-    m->d_tapidx.reserve((size_t)nq * k * 4); m->d_tapdist.reserve((size_t)nq * k * 2);
-    knn_unpack_kernel<<<cdiv(nq * k, 256), 256, 0, st>>>(S.d_keys.as<uint32_t>(), nq, KLIST, k, m->d_tapidx.as<int32_t>(), m->d_tapdist.as<uint16_t>());
-    check_launch("knn_unpack_kernel");
-    HIP_CHECK(hipMemcpyAsync(idx_out, m->d_tapidx.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipMemcpyAsync(dist_out, m->d_tapdist.p, (size_t)nq * k * 2, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
+    SearchOperand tap;                            // (lives until the tap has synchronised)
+    tap_hamming(m, q, nq, t, nt, k, idx_out, dist_out, 0, [&](Slot& S) {
+        if (!knn_unit_is_valu(m) && nt > 0) prepare_train_bits(t, m->d_tapt.as<uint32_t>(), nt, tap, S.st);
+        // (no unit: the block shape follows what slot 0's last unit observed; every shape gives the same lists)
+        const KnnPlan p = knn_plan(m, S.knn.shared, S.knn.w12, nq, nt);
+        knn_reserve(S, p);
+        run_knn(m, S, p, m->d_tapq.as<uint32_t>(), nq, m->d_tapt.as<uint32_t>(), tap, 0.f);
+    });
     API_CATCH(m)
 }
 
 int32_t slideo_knn_lsh(slideo_matcher* m, const uint8_t* q, int32_t nq, const uint8_t* t, int32_t nt, int32_t k, int32_t* idx_out, uint16_t* dist_out) {
     if (!m) return SLIDEO_ERR_INVALID_ARG;
     API_TRY
-    if (nq < 0 || nt < 0 || k < 1 || k > KLIST) fail(SLIDEO_ERR_INVALID_ARG, "bad nq/nt/k (k must be 1..%d)", KLIST);
-    if ((nq && !q) || (nt && !t) || (nq && (!idx_out || !dist_out))) fail(SLIDEO_ERR_INVALID_ARG, "null argument");
+    tap_check_args(q, nq, t, nt, k, idx_out, dist_out);
     if ((int64_t)nt >= ((int64_t)1 << KNN_KEY_SHIFT)) fail(SLIDEO_ERR_UNSUPPORTED, "train set of %d rows exceeds %d", nt, 1 << KNN_KEY_SHIFT);
     if (m->cfg.lsh_tables < 1 || m->cfg.lsh_tables > 8 || m->cfg.lsh_key_bits < 1 || m->cfg.lsh_key_bits > 16 || m->cfg.lsh_multi_probe < 0 || m->cfg.lsh_multi_probe > 2)
         fail(SLIDEO_ERR_UNSUPPORTED, "lsh_tables must be 1..8, lsh_key_bits 1..16, lsh_multi_probe 0..2");
     if (nq == 0) return SLIDEO_OK;
-    HIP_CHECK(hipSetDevice(m->device));
-    require_idle(m);
-    Slot& S = m->slots[0];
-    hipStream_t st = S.st;
-    slideo_matcher::LshSet set;
-    build_lsh_set(m->cfg, t, nt, set, st);
-    m->d_tapq.reserve((size_t)nq * 32); m->d_tapt.reserve(std::max<size_t>((size_t)nt * 32, 64) + 64);
-    HIP_CHECK(hipMemcpyAsync(m->d_tapq.p, q, (size_t)nq * 32, hipMemcpyHostToDevice, st));
-    if (nt) HIP_CHECK(hipMemcpyAsync(m->d_tapt.p, t, (size_t)nt * 32, hipMemcpyHostToDevice, st));
-    S.d_keys.reserve((size_t)nq * KLIST * 4);
-    knn_lsh_kernel<KLIST><<<cdiv(nq, 4), 256, 0, st>>>(set.dev, m->d_tapq.as<uint32_t>(), nq, m->d_tapt.as<uint32_t>(), S.d_keys.as<uint32_t>(), nullptr);
-    check_launch("knn_lsh_kernel");
-    m->d_tapidx.reserve((size_t)nq * k * 4); m->d_tapdist.reserve((size_t)nq * k * 2);
-    knn_unpack_kernel<<<cdiv(nq * k, 256), 256, 0, st>>>(S.d_keys.as<uint32_t>(), nq, KLIST, k, m->d_tapidx.as<int32_t>(), m->d_tapdist.as<uint16_t>());
-    check_launch("knn_unpack_kernel");
-    HIP_CHECK(hipMemcpyAsync(idx_out, m->d_tapidx.p, (size_t)nq * k * 4, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipMemcpyAsync(dist_out, m->d_tapdist.p, (size_t)nq * k * 2, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
+    slideo_matcher::LshSet set;                   // (lives until the tap has synchronised)
+    tap_hamming(m, q, nq, t, nt, k, idx_out, dist_out, 64, [&](Slot& S) {
+        build_lsh_set(m->cfg, t, nt, set, S.st);
+        S.d_keys.reserve((size_t)nq * KLIST * 4);
+        knn_lsh_kernel<KLIST><<<cdiv(nq, 4), 256, 0, S.st>>>(set.dev, m->d_tapq.as<uint32_t>(), nq, m->d_tapt.as<uint32_t>(), S.d_keys.as<uint32_t>(), nullptr);
+        check_launch("knn_lsh_kernel");
+    });
     API_CATCH(m)
 }
 
@@ -543,8 +520,7 @@ int32_t slideo_knn_l2_u8(slideo_matcher* m, const uint8_t* q, int32_t nq, const 
                          int32_t* idx_out, uint32_t* dist_out) {
     if (!m) return SLIDEO_ERR_INVALID_ARG;
     API_TRY
-    if (nq < 0 || nt < 0 || k < 1 || k > KLIST) fail(SLIDEO_ERR_INVALID_ARG, "bad nq/nt/k (k must be 1..%d)", KLIST);
-    if ((nq && !q) || (nt && !t) || (nq && (!idx_out || !dist_out))) fail(SLIDEO_ERR_INVALID_ARG, "null argument");
+    tap_check_args(q, nq, t, nt, k, idx_out, dist_out);
     if ((int64_t)nt >= ((int64_t)1 << KNN_KEY_SHIFT)) fail(SLIDEO_ERR_UNSUPPORTED, "train set of %d rows exceeds %d", nt, 1 << KNN_KEY_SHIFT);
     if (nq == 0) return SLIDEO_OK;
     HIP_CHECK(hipSetDevice(m->device));

@@ -22,7 +22,7 @@ void page_set_check_mode(const slideo_matcher* m) {
 
 // The set's operand is what prepare_train_bits (stage_knn.hip) builds for a deck of exactly the selected pages, with deck row ids
 // in the keys: the selected rows of every duplicate group chained in row order (their first one the group's head), the surviving
-// groups in the deck's norm order, the same tile shuffle for the same tile count.
+// groups in the deck's norm order, the tile order of that tile count (knn_tile_order).
 int page_set_create(slideo_matcher* m, int n, const int32_t* pages) {
     hipStream_t st = m->stream;
     const int P = (int)m->pages.size();
@@ -63,28 +63,20 @@ int page_set_create(slideo_matcher* m, int n, const int32_t* pages) {
     HIP_CHECK(hipMemcpyAsync(&ns, d_cnt.as<uint32_t>() + nb, 4, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
     if (ns == 0 || ns > (uint32_t)nu) fail(SLIDEO_ERR_HIP, "internal: page set compaction kept %u of %d distinct rows", ns, nu);
-    // the tile shuffle of prepare_train_bits for ntiles tiles (the same LCG, the same draws)
-    const int ntiles = cdiv((int)ns, 32);
-    std::vector<int32_t> order((size_t)ntiles);
-    for (int i = 0; i < ntiles; ++i) order[i] = i;
-    uint64_t st_ = 0x9E3779B97F4A7C15ull;
-    for (int i = ntiles - 1; i > 0; --i) {
-        st_ = st_ * 6364136223846793005ull + 1442695040888963407ull;
-        std::swap(order[i], order[(int)((st_ >> 33) % (uint64_t)(i + 1))]);
-    }
+    const std::vector<int32_t> order = knn_tile_order(cdiv((int)ns, 32));
     const OperandLayout L = knn_operand_layout();
-    const int nt_pad = knn_operand_rows((int)ns), n_st = nt_pad / L.st_rows;
+    SearchOperand& op = ps->op;
+    op.reserve((int)ns, knn_operand_rows((int)ns), L);
+    const int nt_pad = op.nt_pad;
     d_order.reserve(order.size() * 4 + 16);
     HIP_CHECK(hipMemcpyAsync(d_order.p, order.data(), order.size() * 4, hipMemcpyHostToDevice, st));
-    ps->d_trainb.reserve((size_t)nt_pad * 128); ps->d_side.reserve((size_t)n_st * L.side_u32 * 4 + 16);
-    ps->d_nminh.reserve((size_t)nt_pad / 32 * 4 + 16); ps->d_perm.reserve((size_t)nt_pad * 4 + 16);
     // the distinct rows: d_utrain when the deck collapsed equal rows, else the deck's rows themselves
     const uint32_t* t = (m->Mu < m->M ? m->d_utrain : m->d_train).as<uint32_t>();
     ps_layout_kernel<<<cdiv(nt_pad, PS_BLOCK), PS_BLOCK, 0, st>>>(d_cu.as<int32_t>(), (int)ns, d_order.as<int32_t>(), nt_pad, t, d_head.as<int32_t>(),
-                                                                  L.st_rows, L.side_u32, L.pad_norm, ps->d_perm.as<int32_t>(), ps->d_side.as<uint32_t>(),
-                                                                  ps->d_nminh.as<float>());
+                                                                  L.st_rows, L.side_u32, L.pad_norm, op.perm.as<int32_t>(), op.side.as<uint32_t>(),
+                                                                  op.bound.as<float>());
     check_launch("ps_layout_kernel");
-    knn_expand_operand(t, (int)ns, nt_pad, ps->d_perm.as<int32_t>(), ps->d_trainb.as<uint4>(), st);
+    knn_expand_operand(t, (int)ns, nt_pad, op.perm.as<int32_t>(), op.tx.as<uint4>(), st);
     HIP_CHECK(hipStreamSynchronize(st));                                  // (the scratch buffers die here)
     ps->n_pages = n; ps->rows = rows; ps->urows = ns;
     const int id = m->next_set_id++;
@@ -148,7 +140,7 @@ int32_t slideo_matcher_page_set_info(const slideo_matcher* cm, int32_t set, int3
         if (n_pages) *n_pages = (int32_t)m->pages.size();
         if (rows) *rows = m->M;
         if (unique_rows) *unique_rows = m->Mu;
-        if (bytes) *bytes = (int64_t)(m->d_trainb.cap + m->d_train_side.cap + m->d_train_nminh.cap + m->d_train_perm.cap + m->d_grp_next.cap);
+        if (bytes) *bytes = (int64_t)(m->train_op.bytes() + m->d_grp_next.cap);
         return SLIDEO_OK;
     }
     const auto it = m->page_sets.find(set);

@@ -261,7 +261,7 @@ void unit_submit_sift(slideo_matcher* m, Slot& S, const DevFrames& f, int n) {
     uint32_t mx = 0;
     for (int i = 0; i < n; ++i) { S.orb.qofs[i + 1] = S.orb.qofs[i] + counts[i]; mx = std::max(mx, counts[i]); }
     S.orb.qtot = qtot; S.orb.max_count = mx; S.orb.nframes = n;
-    S.u_nt = (int)m->M;
+    S.knn.nt = (int)m->M;
     S.d_qofs.reserve((size_t)(n + 1) * 4 + 16); S.d_info.reserve(16); S.d_flags.reserve(16);
     S.h_info.reserve((size_t)(n + 1) * 4 + 16);
     uint32_t* hq = S.h_info.as<uint32_t>();
