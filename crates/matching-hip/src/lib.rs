@@ -200,6 +200,15 @@ impl<I: MatchableImage + Send + Sync + Copy + Eq> VideoMatcherTask<I> for HipVid
         let h = guard.0;
         let mut progress = 0u64;
         let mut prev_small: Option<Vec<u8>> = None;
+        // The changed-frame gate (slideo_amd.h "Changed-frame gate"): a one-device group gates through its member: one call per
+        // batch decides on the device which frames changed and matches those, and the last small image stays in the matcher.  A
+        // group of several devices has no gated form (a shard needs the frame before its block) and keeps the mask + kept pair.
+        let gate: *mut ffi::slideo_matcher =
+            if self.n_devices == 1 { unsafe { ffi::slideo_group_member(h, 0) } } else { std::ptr::null_mut() };
+        if !gate.is_null() {
+            // the first frame of the video is always changed
+            unsafe { check(h, ffi::slideo_matcher_gate_reset(gate, std::ptr::null(), 0, 0)) };
+        }
         // one call = one shard of FRAMES_PER_CALL_PER_DEVICE sampled frames per device (mo/lib.rs:213: one task per frame over the pool)
         for batch in decode::batches(vid, FRAMES_PER_CALL_PER_DEVICE * self.n_devices) {
             let n = batch.meta.len();
@@ -208,6 +217,40 @@ impl<I: MatchableImage + Send + Sync + Copy + Eq> VideoMatcherTask<I> for HipVid
             // first frame of the video is always changed (prev_small == None); the last small image of this call is the
             // `prev` of the next one.
             let mut changed = vec![0u8; n];
+            if !gate.is_null() {
+                let mut all = vec![ffi::slideo_verdict::default(); n];
+                unsafe {
+                    check(
+                        h,
+                        ffi::slideo_match_changed_frames_bgr8(
+                            gate,
+                            n as i32,
+                            batch.frames.as_ptr(),
+                            batch.width,
+                            batch.height,
+                            batch.width * 3,
+                            fb as i64,
+                            changed.as_mut_ptr(),
+                            std::ptr::null_mut(),
+                            all.as_mut_ptr(),
+                        ),
+                    );
+                }
+                for i in (0..n).filter(|&i| changed[i] != 0) {
+                    let (time, frame_idx) = batch.meta[i];
+                    let v = &all[i];
+                    results.push(Matching {
+                        video_time: time,
+                        video_frame_idx: frame_idx,
+                        image: if v.page_idx >= 0 { Some(self.images[v.page_idx as usize]) } else { None },
+                    });
+                }
+                for _ in 0..n {
+                    progress += 1;
+                    self.progress_reporter.report(progress, frames_to_process as u64, &message);
+                }
+                continue;
+            }
             let mut last_small = vec![0u8; small_image_bytes(batch.width, batch.height)];
             unsafe {
                 check(

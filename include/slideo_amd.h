@@ -700,6 +700,72 @@ int32_t     slideo_group_set_working_size(slideo_group* g, int32_t max_w, int32_
 int32_t     slideo_reduce_bgr8(slideo_matcher* m, const uint8_t* bgr, int32_t width, int32_t height, int32_t stride_bytes,
                                int32_t dw, int32_t dh, uint8_t* out, int64_t out_capacity);
 
+/* ---- Changed-frame gate (MarkSimilarIter, mo/video_capture.rs:86-98, inside the unit pipeline) ---------------------------------
+ * slideo_changed_mask_* + slideo_match_kept_frames are a stop-and-go pair: host frames, an idle matcher, the flags made on the host.
+ * A GATED call or unit decides on the device which of its frames changed and runs ORB / search / verify on those alone; host and
+ * device frames, BGR and YUV 4:2:0, synchronous and submit / collect.
+ * A matcher carries a GATE STATE: "none" (the next gated frame is changed, with similarity 0.0: video_capture.rs:92) or the small
+ * image of the last gated frame, kept on the device from unit to unit.  Let f_0 .. f_{N-1} be the frames of all gated calls and
+ * units since the last reset, in submission order.  They must have one size and one format family (BGR or YUV 4:2:0); another size
+ * or family without a reset is SLIDEO_ERR_STATE.  Then
+ *   1. changed[i] and similarity[i] equal, bit for bit, what ONE slideo_changed_mask_bgr8 (_yuv420) call over the concatenation
+ *      returns with the reset's prev_small, wherever unit and call boundaries fall;
+ *   2. for changed[i] == 1 the slideo_verdict equals, bit for bit, what slideo_match_frames_* of the same family returns for those
+ *      frames;
+ *   3. slideo_last_frame_candidates(k) is the trace of the k-th CHANGED frame of the call, or of the units collected since the
+ *      matcher was last idle: the indexing slideo_match_kept_frames over the flagged frames gives;
+ *   4. an unchanged frame's record is {page_idx -1, similarity 0, inliers 0, keypoints 0}; the flag tells it from a "no slide"
+ *      verdict;
+ *   5. the small image slideo_matcher_gate_last_small returns after the last collect is the mask call's last_small_out;
+ *   6. every matcher option is picked up as by the mask + match pair under the same option: the selected page set (recorded per
+ *      unit at submission), the working size (the small image is the reduced image's), verify_model 1, ratio_test, SIFT mode,
+ *      matcher 1.  Plain units may be in flight beside gated ones and do not touch the gate state.
+ * The flag does not depend on device floating point: the mask call tests sim = 1 - (float)sqrt((double)ssd) / max_error against
+ * cfg.changed_similarity, which is monotone in the integer SSD, so the device compares ssd >= T in 64-bit integers, with T from
+ * slideo_changed_ssd_threshold.  The similarities returned are computed on the host, by the mask call's own expression, from the
+ * SSDs read back.  Where it runs (csrc/stage_gate.hip, csrc/gate.hip.h): small images and SSDs of all n frames of a unit on the
+ * unit's stream, pair 0 and the write of the new state ordered behind the previous gated unit's by an event; gate_kernel (flags,
+ * kept list, count); gather_frames_kernel packs the kept frames; the kept count reaches the host in ONE short wait inside the
+ * submit, and the unchanged pipeline runs for the kept frames only.  A unit without a changed frame runs no pipeline.
+ * A size, format or argument error leaves the gate state untouched.  slideo_matcher_set_working_size resets it.
+ * The N-device group has no gated form: a group shards contiguous blocks of a call, and a shard's first frame needs the frame
+ * before its block (the one-frame halo of slideo_group_changed_mask_bgr8); gate per member, or use the group's mask call. */
+/* The smallest SSD of two small_w x small_h small images that counts as changed under changed_similarity: found by bisection over
+ * the mask call's host expression itself.  INT64_MAX: no SSD (0 .. 255^2 * 3 * small_w * small_h) does.  A pure host function (no
+ * device).  -1 for a non-positive size. */
+int64_t     slideo_changed_ssd_threshold(float changed_similarity, int32_t small_w, int32_t small_h);
+/* Idle matcher.  prev_small: a small_w x small_h small image (3 bytes per pixel, as last_small_out / slideo_matcher_gate_last_small
+ * return it) the next gated frame compares against; NULL (the sizes are then ignored): the state "none".  A small image whose size
+ * is not the next gated frames' is SLIDEO_ERR_STATE at that call. */
+int32_t     slideo_matcher_gate_reset(slideo_matcher* m, const uint8_t* prev_small, int32_t small_w, int32_t small_h);
+/* Idle matcher.  The gate state's small image; *sw, *sh its size (out may be NULL).  SLIDEO_ERR_STATE when the state is "none". */
+int32_t     slideo_matcher_gate_last_small(slideo_matcher* m, uint8_t* out, int64_t out_capacity, int32_t* sw, int32_t* sh);
+/* The synchronous forms (idle matcher): the call is cut into units and pipelined through the slots as slideo_match_frames_* is;
+ * host frames in short units through the ordered copy stream, so that unit u + 1 uploads and gates while unit u matches.
+ * changed_out [n] and verdicts_out [n] are required, similarity_out [n] may be NULL. */
+int32_t     slideo_match_changed_frames_bgr8(slideo_matcher* m, int32_t n_frames, const uint8_t* frames, int32_t width, int32_t height,
+                                             int32_t stride_bytes, int64_t frame_stride_bytes, uint8_t* changed_out, float* similarity_out,
+                                             slideo_verdict* verdicts_out);
+int32_t     slideo_match_changed_frames_yuv420(slideo_matcher* m, int32_t n_frames, const uint8_t* frames, int32_t width, int32_t height,
+                                               const slideo_yuv420_layout* layout, int64_t frame_stride_bytes, uint8_t* changed_out,
+                                               float* similarity_out, slideo_verdict* verdicts_out);
+int32_t     slideo_match_changed_frames_bgr8_dev(slideo_matcher* m, int32_t n_frames, const uint8_t* frames_dev, int32_t width, int32_t height,
+                                                 int32_t stride_bytes, int64_t frame_stride_bytes, uint8_t* changed_out, float* similarity_out,
+                                                 slideo_verdict* verdicts_out, void* hip_stream);
+int32_t     slideo_match_changed_frames_yuv420_dev(slideo_matcher* m, int32_t n_frames, const uint8_t* frames_dev, int32_t width, int32_t height,
+                                                   const slideo_yuv420_layout* layout, int64_t frame_stride_bytes, uint8_t* changed_out,
+                                                   float* similarity_out, slideo_verdict* verdicts_out, void* hip_stream);
+/* The streaming forms.  Tickets share the sequence and the in-order collect rule of slideo_match_frames_submit_dev; a gated ticket
+ * is collected by slideo_match_changed_frames_collect alone and a plain one by slideo_match_frames_collect[_dev] alone (the other
+ * is SLIDEO_ERR_STATE, and the unit stays in flight).  The frames must stay valid until the unit is collected. */
+int32_t     slideo_match_changed_frames_submit_dev(slideo_matcher* m, int32_t n_frames, const uint8_t* frames_dev, int32_t width, int32_t height,
+                                                   int32_t stride_bytes, int64_t frame_stride_bytes, void* hip_stream, int64_t* ticket_out);
+int32_t     slideo_match_changed_frames_submit_yuv420_dev(slideo_matcher* m, int32_t n_frames, const uint8_t* frames_dev, int32_t width,
+                                                          int32_t height, const slideo_yuv420_layout* layout, int64_t frame_stride_bytes,
+                                                          void* hip_stream, int64_t* ticket_out);
+int32_t     slideo_match_changed_frames_collect(slideo_matcher* m, int64_t ticket, uint8_t* changed_out, float* similarity_out,
+                                                slideo_verdict* verdicts_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -132,6 +132,10 @@ EXPORTS = [
     "slideo_group_create_page_set", "slideo_group_use_page_set", "slideo_group_release_page_set",
     "slideo_working_size", "slideo_matcher_set_working_size", "slideo_matcher_get_working_size", "slideo_group_set_working_size",
     "slideo_reduce_bgr8",
+    "slideo_changed_ssd_threshold", "slideo_matcher_gate_reset", "slideo_matcher_gate_last_small",
+    "slideo_match_changed_frames_bgr8", "slideo_match_changed_frames_yuv420", "slideo_match_changed_frames_bgr8_dev",
+    "slideo_match_changed_frames_yuv420_dev", "slideo_match_changed_frames_submit_dev", "slideo_match_changed_frames_submit_yuv420_dev",
+    "slideo_match_changed_frames_collect",
 ]
 
 _lib = None
@@ -175,6 +179,9 @@ def lib():
         L.slideo_group_page_count.argtypes = [C.c_void_p]
         L.slideo_group_descriptor_count.argtypes = [C.c_void_p]
         L.slideo_group_descriptor_count.restype = C.c_int64
+        if hasattr(L, "slideo_changed_ssd_threshold"):             # (SLIDEO_LIB_PATH may name an older build: tools/ab_libs.sh)
+            L.slideo_changed_ssd_threshold.restype = C.c_int64
+            L.slideo_changed_ssd_threshold.argtypes = [C.c_float, C.c_int32, C.c_int32]
         _lib = L
     return _lib
 
@@ -454,6 +461,86 @@ class Matcher(_FrameCalls):
         self._check(lib().slideo_match_frames_collect_dev(self._h, C.c_int64(t), _p(out), C.c_void_p(dev_out or None)))
         return out
 
+    # ---- changed-frame gate (include/slideo_amd.h "Changed-frame gate") ------------------------
+    # Gated calls return (changed [n] bool, similarity [n] f32, verdicts [n]); an unchanged frame's verdict is (-1, 0, 0, 0).
+    def gate_reset(self, prev_small=None):
+        """The gate state: the small image (sh, sw, 3) the next gated frame compares against, or None (that frame is changed)."""
+        if prev_small is None:
+            self._check(lib().slideo_matcher_gate_reset(self._h, None, 0, 0))
+            return
+        prev_small = np.ascontiguousarray(prev_small, np.uint8)
+        if prev_small.ndim != 3 or prev_small.shape[2] != 3:
+            raise SlideoError(1, "gate_reset: expected an (sh, sw, 3) uint8 small image")
+        self._check(lib().slideo_matcher_gate_reset(self._h, _p(prev_small), prev_small.shape[1], prev_small.shape[0]))
+
+    def gate_last_small(self):
+        """The small image of the last gated frame (SLIDEO_ERR_STATE when no frame was gated since a reset to None)."""
+        sw, sh = C.c_int32(), C.c_int32()
+        self._check(lib().slideo_matcher_gate_last_small(self._h, None, C.c_int64(1 << 40), C.byref(sw), C.byref(sh)))
+        out = np.empty((sh.value, sw.value, 3), np.uint8)
+        self._check(lib().slideo_matcher_gate_last_small(self._h, _p(out), C.c_int64(out.size), C.byref(sw), C.byref(sh)))
+        return out
+
+    @staticmethod
+    def _gated_out(n):
+        return np.zeros(n, np.uint8), np.zeros(n, np.float32), np.zeros(n, VERDICT_DTYPE)
+
+    def match_changed_frames(self, frames):
+        """frames: uint8 [n, h, w, 3] in host memory, continuing the gate."""
+        frames = np.ascontiguousarray(frames, np.uint8)
+        n, h, w, c = frames.shape
+        assert c == 3
+        ch, sim, out = self._gated_out(n)
+        self._check(lib().slideo_match_changed_frames_bgr8(self._h, n, _p(frames), w, h, w * 3, C.c_int64(w * h * 3), _p(ch), _p(sim), _p(out)))
+        return ch.astype(bool), sim, out
+
+    def match_changed_frames_yuv420(self, frames, w, h, layout="nv12"):
+        frames, layout, fs = _yuv_frames(frames, w, h, layout)
+        n = frames.shape[0]
+        ch, sim, out = self._gated_out(n)
+        self._check(lib().slideo_match_changed_frames_yuv420(self._h, n, _p(frames), w, h, C.byref(layout), C.c_int64(fs), _p(ch), _p(sim),
+                                                             _p(out)))
+        return ch.astype(bool), sim, out
+
+    def match_changed_frames_dev(self, dev_ptr, n, w, h, stride=None, frame_stride=None, stream=0):
+        stride = stride or w * 3
+        frame_stride = frame_stride or stride * h
+        ch, sim, out = self._gated_out(n)
+        self._check(lib().slideo_match_changed_frames_bgr8_dev(self._h, n, C.c_void_p(dev_ptr), w, h, stride, C.c_int64(frame_stride),
+                                                               _p(ch), _p(sim), _p(out), C.c_void_p(stream)))
+        return ch.astype(bool), sim, out
+
+    def match_changed_frames_yuv420_dev(self, dev_ptr, n, w, h, layout, frame_stride, stream=0):
+        if isinstance(layout, str):
+            layout = yuv420_layout(layout, w, h)[0]
+        ch, sim, out = self._gated_out(n)
+        self._check(lib().slideo_match_changed_frames_yuv420_dev(self._h, n, C.c_void_p(dev_ptr), w, h, C.byref(layout),
+                                                                 C.c_int64(frame_stride), _p(ch), _p(sim), _p(out), C.c_void_p(stream)))
+        return ch.astype(bool), sim, out
+
+    def submit_changed_dev(self, dev_ptr, n, w, h, stride=None, frame_stride=None, stream=0):
+        """A gated unit (streaming form): a ticket for collect_changed; tickets of gated and plain units share one order."""
+        stride = stride or w * 3
+        frame_stride = frame_stride or stride * h
+        t = C.c_int64()
+        self._check(lib().slideo_match_changed_frames_submit_dev(self._h, n, C.c_void_p(dev_ptr), w, h, stride, C.c_int64(frame_stride),
+                                                                 C.c_void_p(stream), C.byref(t)))
+        return (t.value, n)
+
+    def submit_changed_yuv420_dev(self, dev_ptr, n, w, h, layout, frame_stride, stream=0):
+        if isinstance(layout, str):
+            layout = yuv420_layout(layout, w, h)[0]
+        t = C.c_int64()
+        self._check(lib().slideo_match_changed_frames_submit_yuv420_dev(self._h, n, C.c_void_p(dev_ptr), w, h, C.byref(layout),
+                                                                        C.c_int64(frame_stride), C.c_void_p(stream), C.byref(t)))
+        return (t.value, n)
+
+    def collect_changed(self, ticket):
+        t, n = ticket
+        ch, sim, out = self._gated_out(n)
+        self._check(lib().slideo_match_changed_frames_collect(self._h, C.c_int64(t), _p(ch), _p(sim), _p(out)))
+        return ch.astype(bool), sim, out
+
     # ---- YUV 4:2:0 frames (include/slideo_amd.h "YUV 4:2:0 frames") ---------------------------
     def match_frames_yuv420_dev(self, dev_ptr, n, w, h, layout, frame_stride, stream=0):
         if isinstance(layout, str):
@@ -720,6 +807,15 @@ def device_list():
     arr = (C.c_int32 * max(n, 1))()
     n = min(n, int(lib().slideo_device_list(arr, n)))
     return [int(arr[i]) for i in range(n)]
+
+
+def changed_ssd_threshold(changed_similarity, small_w, small_h):
+    """The smallest SSD of two small_w x small_h small images that counts as changed (slideo_changed_ssd_threshold; a host rule).
+    2**63 - 1: no SSD does."""
+    t = int(lib().slideo_changed_ssd_threshold(C.c_float(changed_similarity), int(small_w), int(small_h)))
+    if t < 0:
+        raise SlideoError(1, "changed_ssd_threshold: bad small-image size %rx%r" % (small_w, small_h))
+    return t
 
 
 def working_size(w, h, max_w, max_h):

@@ -152,19 +152,21 @@ void apply_working_size(const slideo_matcher* m, FrameSrc& src) {
 
 // S's staging buffer with room for `bytes`.  Slot 0's holds the frames slideo_changed_mask_bgr8 kept for slideo_match_kept_frames:
 // whatever the mask call left there is overwritten (any slot's, as a call's units cycle through them all)
-static uint8_t* stage_for_upload(slideo_matcher* m, Slot& S, size_t bytes) {
+uint8_t* stage_for_upload(slideo_matcher* m, Slot& S, size_t bytes) {
     m->kept.valid = false;
     S.d_stage.reserve(bytes + 16);
     return S.d_stage.as<uint8_t>();
 }
 
-DevFrames stage_frames(slideo_matcher* m, Slot& S, const FrameSrc& src, int first, int n, hipStream_t cs) {
+DevFrames stage_frames(slideo_matcher* m, Slot& S, const FrameSrc& src, int first, int n, hipStream_t cs, DevBuf* into) {
     const uint8_t* p = src.p + (int64_t)first * src.frame_stride;
     if (src.on_device && !src.yuv && !src.reduce) return DevFrames{p, src.w, src.h, src.stride, src.frame_stride};
     const int uw = src.unit_w(), uh = src.unit_h();
     const int64_t fb = (int64_t)src.h * src.stride;              // one frame of the BGR view at source size (stride 3w for YUV frames)
     const int64_t ub = src.reduce ? (int64_t)uh * uw * 3 : fb;   // one frame of the unit's BGR image
-    uint8_t* stage = stage_for_upload(m, S, (size_t)ub * n);
+    uint8_t* stage;
+    if (into) { into->reserve((size_t)ub * n + 16); stage = into->as<uint8_t>(); }
+    else stage = stage_for_upload(m, S, (size_t)ub * n);
     int64_t fs = src.frame_stride;
     if (!src.on_device) {
         // host frames back to back into d_stage, or into d_yuv for the conversion / the reduce below
@@ -221,6 +223,7 @@ uint32_t kp_cap_for(const slideo_matcher* m, const PyrGeom& g) {
 void unit_submit(slideo_matcher* m, Slot& S, const DevFrames& f, int n, bool allow_async) {
     // (does this unit share the chip with others?  the search then runs one block per CU: stage_knn.hip knn_plan)
     { bool others = m->units_pending; for (const Slot& o : m->slots) others |= (&o != &S && o.busy); S.knn.shared = others; }
+    S.gate.on = false;                             // (a gated unit: stage_gate.hip marks it after this submit)
     if (!S.u_rerun) S.u_set = m->cur_set;          // (a re-run of an overflowed unit searches the set it was submitted with)
     S.u_rerun = false;
     if (m->sift_on) { unit_submit_sift(m, S, f, n); return; }
@@ -592,6 +595,7 @@ void slideo_matcher_destroy(slideo_matcher* m) {
     }
     if (m->copy_st) (void)hipStreamDestroy(m->copy_st);
     if (m->sift_ev) (void)hipEventDestroy(m->sift_ev);
+    gate_release(m);
     delete m;
 }
 
@@ -615,6 +619,7 @@ int32_t slideo_matcher_set_working_size(slideo_matcher* m, int32_t max_w, int32_
     require_idle(m);
     m->work_w = max_w; m->work_h = max_h;
     m->kept.valid = false;          // (the kept frames of an earlier mask call were sized under the earlier setting)
+    gate_state_reset(m);            // (and so was the gate's small image)
     API_CATCH(m)
 }
 
@@ -902,11 +907,7 @@ void changed_mask_impl(slideo_matcher* m, int n_frames, FrameSrc src, const uint
     HIP_CHECK(hipStreamSynchronize(st));
     for (int i = 0; i < n_frames; ++i) {
         float sim = 0.0f;   // video_capture.rs:92: the first frame compares as 0.0
-        if (i > 0 || prev_small) {
-            double e = std::sqrt((double)ssd[i]);
-            float max_error = std::sqrt((255.0f * 255.0f * 3.0f) * (float)(sw * sh));
-            sim = 1.0f - (float)e / max_error;
-        }
+        if (i > 0 || prev_small) sim = changed_similarity(ssd[i], sw, sh);
         changed_out[i] = sim < m->cfg.changed_similarity ? 1 : 0;
         if (similarity_out) similarity_out[i] = sim;
     }
@@ -933,6 +934,7 @@ int32_t slideo_match_frames_collect_dev(slideo_matcher* m, int64_t ticket, slide
     for (Slot& c : m->slots) if (c.busy && c.ticket == ticket) S = &c;
     if (!S) fail(SLIDEO_ERR_STATE, "ticket %lld is not in flight", (long long)ticket);
     for (Slot& c : m->slots) if (c.busy && c.ticket < ticket) fail(SLIDEO_ERR_STATE, "collect ticket %lld first (in order)", (long long)c.ticket);
+    if (S->gate.on) fail(SLIDEO_ERR_STATE, "ticket %lld is a gated unit: slideo_match_changed_frames_collect collects it", (long long)ticket);
     unit_collect(m, *S, verdicts_out);
     if (verdicts_dev_out) {           // (after the collect: a unit re-run through the exact-size path has rewritten d_verdicts)
         HIP_CHECK(hipMemcpyAsync(verdicts_dev_out, S->d_verdicts.p, (size_t)S->n * sizeof(slideo_verdict), hipMemcpyDeviceToDevice, S->st));

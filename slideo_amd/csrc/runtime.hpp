@@ -6,6 +6,7 @@
 //   stage_verify.hip   vote .. verdict, small img (kernels: verify.hip.h, homography.hip.h)
 //   stage_sift.hip     SIFT stage + entry points  (kernels: sift.hip.h)
 //   stage_page_set.hip page sets: a subset's search operand built from the finalized deck (kernels: page_set.hip.h)
+//   stage_gate.hip     changed-frame gate: gated units, their entry points, the gate state (kernels: gate.hip.h)
 //   capi_taps.hip      debug taps of the parity tests
 //   capi_group.hip     the N-device group (slideo_group_*)
 //
@@ -82,11 +83,14 @@ struct FrameSrc {
     int unit_w() const { return reduce ? rw : w; }      // the BGR image the units read
     int unit_h() const { return reduce ? rh : h; }
     // per frame, the staging in front of the unit's BGR image: 1.5 B per pixel for 4:2:0 frames (BGR calls keep their unit sizes);
-    // a reducing call: the uploaded source frame (host sources) and the source-sized BGR image of a 4:2:0 frame
-    size_t staging_bytes() const {
+    // a reducing call: the uploaded source frame (host sources) and the source-sized BGR image of a 4:2:0 frame;
+    // gated (a gated call, include/slideo_amd.h "Changed-frame gate"): + the gate staging — the BGR unit image of every frame that
+    // is not the caller's own device memory — and the frame's small image (gate_small: at most 3 * small_area bytes) and gate record
+    size_t staging_bytes(size_t gate_small = 0) const {
         const size_t px = (size_t)w * h;
-        if (!reduce) return yuv ? px * 3 / 2 : 0;
-        return (on_device ? 0 : (yuv ? px * 3 / 2 : (size_t)h * stride)) + (yuv ? px * 3 : 0);
+        size_t b = !reduce ? (yuv ? px * 3 / 2 : 0) : (on_device ? 0 : (yuv ? px * 3 / 2 : (size_t)h * stride)) + (yuv ? px * 3 : 0);
+        if (gate_small) b += (on_device && !yuv && !reduce ? 0 : (size_t)unit_w() * unit_h() * 3) + gate_small + 32;
+        return b;
     }
 
     static FrameSrc bgr8(const uint8_t* p, bool on_device, int w, int h, int stride, int64_t frame_stride) {
@@ -146,6 +150,17 @@ struct Slot {
     DevBuf d_full;             // the source-sized BGR image of 4:2:0 frames that are reduced (reserved by the first such call only)
     PinBuf h_info, h_out;
     OrbOut orb;
+    // a gated unit (stage_gate.hip): all its frames as BGR unit images (d_gstage; plain device BGR frames stay in the caller's
+    // memory), their small images, the gate record {ssd n x u64 | kept idx n x i32 | flags n x u8 | count} and its pinned twin
+    DevBuf d_gstage, d_gsmall, d_gate;
+    PinBuf h_gate;
+    hipEvent_t ev_gate = nullptr;             // the unit's small images are made and the gate state is this unit's last one
+    struct GateUnit {
+        bool on = false;                      // the unit in flight is gated: slideo_match_changed_frames_collect collects it
+        int n = 0, k = 0;                     // frames submitted, frames changed (S.n = k: what the pipeline ran for)
+        int sw = 0, sh = 0;
+        bool force0 = false;                  // no gate state at submission: frame 0 is changed, similarity 0.0
+    } gate;
     // unit in flight
     bool busy = false;
     int64_t ticket = 0;
@@ -278,6 +293,18 @@ struct slideo_matcher {
     int orb_chain = 1;
     hipEvent_t last_orb_ev = nullptr;
 
+    // changed-frame gate (include/slideo_amd.h "Changed-frame gate"): the small image of the last gated frame (device), and what
+    // the gated frames since the last reset were.  A gated unit's pair-0 SSD and its write of the new state wait for the previous
+    // gated unit's (last_gate_ev, event to event, as last_orb_ev chains the ORB stages).
+    struct GateState {
+        bool has = false;                     // false: "none", the next gated frame is changed
+        bool seen = false;                    // frames were gated since the reset: w, h, yuv are theirs
+        int w = 0, h = 0; bool yuv = false;
+        int sw = 0, sh = 0;                   // (has) the small image's size
+    } gate;
+    slideo::DevBuf d_gate_small;
+    hipEvent_t last_gate_ev = nullptr;
+
     // workspaces
     slideo::Slot slots[slideo::NSLOTS];
     int next_slot = 0;
@@ -322,7 +349,8 @@ void apply_working_size(const slideo_matcher* m, FrameSrc& src);
 // S.d_stage on S.st; a source the working size reduces: host frames into S.d_yuv, 4:2:0 frames converted into S.d_full, then
 // reduced into S.d_stage (the DevFrames are rw x rh).  Every write of a slot's d_stage goes through here (page ingest through its staging buffer) and ends the
 // frames slideo_changed_mask_bgr8 kept for slideo_match_kept_frames.
-DevFrames stage_frames(slideo_matcher* m, Slot& S, const FrameSrc& src, int first, int n, hipStream_t cs = nullptr);
+// into: the staging buffer in place of S.d_stage (a gated unit's S.d_gstage; the kept frames of a mask call then stay).
+DevFrames stage_frames(slideo_matcher* m, Slot& S, const FrameSrc& src, int first, int n, hipStream_t cs = nullptr, DevBuf* into = nullptr);
 void upload_rng_stream(slideo_matcher* m, uint32_t len);
 void unit_submit(slideo_matcher* m, Slot& S, const DevFrames& f, int n, bool allow_async = true);
 void unit_collect(slideo_matcher* m, Slot& S, slideo_verdict* out_host);
@@ -330,6 +358,15 @@ void match_frames_impl(slideo_matcher* m, int n, FrameSrc src, slideo_verdict* o
 // slideo_changed_mask_bgr8 / _yuv420: the frames stay in slot 0's d_stage, which m->kept then describes
 void changed_mask_impl(slideo_matcher* m, int n, FrameSrc src, const uint8_t* prev_small, uint8_t* last_small_out, uint8_t* changed_out,
                        float* similarity_out);
+// the similarity MarkSimilarIter compares (video_capture.rs:86-98) from the integer SSD of two sw x sh small images: the ONE host
+// expression behind the mask calls' flags, the gate's similarities and slideo_changed_ssd_threshold
+inline float changed_similarity(unsigned long long ssd, int sw, int sh) {
+    double e = std::sqrt((double)ssd);
+    float max_error = std::sqrt((255.0f * 255.0f * 3.0f) * (float)(sw * sh));
+    return 1.0f - (float)e / max_error;
+}
+// S's staging buffer with room for `bytes` (ends the kept frames of a mask call)
+uint8_t* stage_for_upload(slideo_matcher* m, Slot& S, size_t bytes);
 // ProcessedImage::compute over n host pages (mo/lib.rs:92-131) WITHOUT appending them: the analysed pages, in order, into `out`
 void analyse_pages(slideo_matcher* m, int n_pages, const uint8_t* const* data, const int32_t* width, const int32_t* height, const int32_t* stride_bytes,
                    std::vector<HostPage>& out, uint64_t progress_base, uint64_t progress_total);
@@ -380,6 +417,8 @@ void verify_stage_init(slideo_matcher* m);
 VerifyParams make_vp(const slideo_config& c);
 void unit_verify(slideo_matcher* m, Slot& S, const VerifyParams& vp, const DevFrames& f, int n, uint32_t qtot);
 void run_small(slideo_matcher* m, const DevFrames& imgs, int n, int& sw, int& sh, hipStream_t st);
+// the same into `dst` (n small images back to back) in place of m->d_small: small images of consecutive gated units overlap
+void run_small_into(slideo_matcher* m, const DevFrames& imgs, int n, DevBuf& dst, int& sw, int& sh, hipStream_t st);
 // ssd[i] = sum of squared differences of the small images a + i * a_stride and b + i * b_stride (`bytes` each), i < n
 void launch_ssd(const uint8_t* a, int64_t a_stride, const uint8_t* b, int64_t b_stride, int64_t bytes, unsigned long long* ssd, int n, hipStream_t st);
 
@@ -390,6 +429,10 @@ int page_set_create(slideo_matcher* m, int n, const int32_t* pages);
 const PageSet* page_set_of(const slideo_matcher* m, int set);
 // the frame modes a page set does not cover (SLIDEO_ERR_UNSUPPORTED): checked by use_page_set and by every frame call under a set
 void page_set_check_mode(const slideo_matcher* m);
+
+// ---- stage_gate.hip -------------------------------------------------------------------------------
+void gate_release(slideo_matcher* m);          // the gate's events (slideo_matcher_destroy)
+inline void gate_state_reset(slideo_matcher* m) { m->gate = slideo_matcher::GateState{}; }
 
 // ---- stage_sift.hip -------------------------------------------------------------------------------
 void sift_check_cfg(const slideo_sift_config* sc, int w, int h);

@@ -1,0 +1,326 @@
+// stage_gate.hip — the changed-frame gate of include/slideo_amd.h "Changed-frame gate": gated units (small images of all frames, SSDs,
+// gate_kernel, gather_frames_kernel in front of the unchanged unit_submit), the gate state and the entry points (kernels: gate.hip.h).
+#include "runtime.hpp"
+#include "gate.hip.h"
+
+#include <climits>
+
+using namespace slideo;
+
+namespace slideo {
+
+void gate_release(slideo_matcher* m) {
+    for (Slot& S : m->slots) if (S.ev_gate) { (void)hipEventDestroy(S.ev_gate); S.ev_gate = nullptr; }
+}
+
+namespace {
+
+size_t gate_small_budget(const slideo_matcher* m) { return (size_t)m->cfg.small_area * 3 + 64; }      // (a small image has at most small_area pixels)
+
+int64_t ssd_threshold(float changed_similarity_, int sw, int sh) {
+    const int64_t max_ssd = (int64_t)255 * 255 * 3 * sw * sh;
+    auto changed = [&](int64_t s) { return changed_similarity((unsigned long long)s, sw, sh) < changed_similarity_; };
+    if (!changed(max_ssd)) return INT64_MAX;
+    if (changed(0)) return 0;
+    int64_t lo = 0, hi = max_ssd;                   // changed(lo) false, changed(hi) true; the expression is monotone in the SSD
+    while (hi - lo > 1) {
+        const int64_t mid = lo + (hi - lo) / 2;
+        if (changed(mid)) hi = mid; else lo = mid;
+    }
+    return hi;
+}
+
+// The frames of a gated call against the gate state: one size and one format family since the last reset.  Nothing is changed here.
+void gate_check(const slideo_matcher* m, const FrameSrc& src) {
+    const slideo_matcher::GateState& g = m->gate;
+    if (g.seen && (g.w != src.w || g.h != src.h || g.yuv != (src.yuv != nullptr)))
+        fail(SLIDEO_ERR_STATE, "gated frames changed from %dx%d %s to %dx%d %s without slideo_matcher_gate_reset", g.w, g.h, g.yuv ? "yuv420" : "bgr8",
+             src.w, src.h, src.yuv ? "yuv420" : "bgr8");
+    if (g.has && !g.seen) {
+        int sw = 0, sh = 0;
+        small_size(src.unit_w(), src.unit_h(), m->cfg.small_area, sw, sh);
+        if (sw != g.sw || sh != g.sh)
+            fail(SLIDEO_ERR_STATE, "the gate holds a %dx%d small image, these frames' is %dx%d: slideo_matcher_gate_reset first", g.sw, g.sh, sw, sh);
+    }
+}
+
+// One gated unit: frames [first, first + n) of src through the gate, the changed ones through unit_submit.  One short host wait
+// in the middle (the kept count), as the exact-size path's orb_wait_info: the other slots' units keep the GPU busy meanwhile.
+void gate_unit_submit(slideo_matcher* m, Slot& S, const FrameSrc& src, int first, int n, hipStream_t cs) {
+    hipStream_t st = S.st;
+    if (!S.ev_gate) HIP_CHECK(hipEventCreateWithFlags(&S.ev_gate, hipEventDisableTiming));
+    const DevFrames all = stage_frames(m, S, src, first, n, cs, &S.d_gstage);
+    int sw = 0, sh = 0;
+    run_small_into(m, all, n, S.d_gsmall, sw, sh, st);
+    const int64_t sb = (int64_t)sw * sh * 3;
+    const uint8_t* small = S.d_gsmall.as<uint8_t>();
+    S.d_gate.reserve((size_t)n * 13 + 16);
+    unsigned long long* ssd = S.d_gate.as<unsigned long long>();
+    int32_t* idx = reinterpret_cast<int32_t*>(S.d_gate.as<uint8_t>() + (size_t)n * 8);
+    uint32_t* count = reinterpret_cast<uint32_t*>(idx + n);
+    uint8_t* flags = reinterpret_cast<uint8_t*>(count + 1);
+    S.h_gate.reserve(gate_rec_bytes(n));
+    const bool force0 = !m->gate.has;
+    m->d_gate_small.reserve((size_t)sb);            // (grows only from the state "none": no gated unit is reading it)
+    // pair i: (small[i - 1], small[i]); pair 0: (gate state, small[0]), behind the previous gated unit's write of the state
+    if (n > 1) launch_ssd(small, sb, small + sb, sb, sb, ssd + 1, n - 1, st);
+    if (m->last_gate_ev && m->last_gate_ev != S.ev_gate) HIP_CHECK(hipStreamWaitEvent(st, m->last_gate_ev, 0));
+    if (!force0) launch_ssd(m->d_gate_small.as<uint8_t>(), 0, small, 0, sb, ssd, 1, st);
+    HIP_CHECK(hipMemcpyAsync(m->d_gate_small.p, small + sb * (n - 1), (size_t)sb, hipMemcpyDeviceToDevice, st));
+    HIP_CHECK(hipEventRecord(S.ev_gate, st));
+    m->last_gate_ev = S.ev_gate;
+    slideo_matcher::GateState& g = m->gate;
+    g.has = true; g.seen = true; g.w = src.w; g.h = src.h; g.yuv = src.yuv != nullptr; g.sw = sw; g.sh = sh;
+
+    const long long thr = ssd_threshold(m->cfg.changed_similarity, sw, sh);
+    gate_kernel<<<1, GATE_BLOCK, 0, st>>>(ssd, n, thr, force0 ? 1 : 0, flags, idx, count, S.h_gate.as<uint8_t>());
+    check_launch("gate_kernel");
+    HIP_CHECK(hipStreamSynchronize(st));
+    const GateHostRec rec = *S.h_gate.as<GateHostRec>();
+    if (rec.n != (uint32_t)n || rec.count > (uint32_t)n) fail(SLIDEO_ERR_HIP, "internal: gate record %u of %u for a unit of %d", rec.count, rec.n, n);
+    const int k = (int)rec.count;
+    Slot::GateUnit gu;
+    gu.on = true; gu.n = n; gu.k = k; gu.sw = sw; gu.sh = sh; gu.force0 = force0;
+    if (k == 0) {                                   // no frame changed: no pipeline; the collect returns the flags at once
+        S.busy = true; S.n = 0; S.u_async = false; S.timed = false;
+        S.gate = gu;
+        return;
+    }
+    DevFrames f = all;
+    if (k < n) {
+        // the kept frames back to back in the slot's d_stage (all kept: the staged images as they are)
+        const int row_bytes = all.w * 3;
+        const int64_t fb = (int64_t)row_bytes * all.h;
+        uint8_t* dst = stage_for_upload(m, S, (size_t)fb * k);
+        const bool contiguous = all.stride == row_bytes;
+        const int64_t seg_bytes = contiguous ? fb : row_bytes;
+        const int nseg = contiguous ? 1 : all.h;
+        const int bps = contiguous ? (int)std::min<int64_t>(256, std::max<int64_t>(1, cdiv64(fb / 16, GATHER_BLOCK * 8))) : 1;
+        const int gx = contiguous ? bps : std::min(all.h, 128);
+        gather_frames_kernel<<<dim3(gx, k), GATHER_BLOCK, 0, st>>>(all.p, all.frame_stride, all.stride, idx, seg_bytes, nseg, bps, dst);
+        check_launch("gather_frames_kernel");
+        f = DevFrames{dst, all.w, all.h, row_bytes, fb};
+    }
+    unit_submit(m, S, f, k);
+    S.gate = gu;
+}
+
+void gate_unit_collect(slideo_matcher* m, Slot& S, uint8_t* changed_out, float* similarity_out, slideo_verdict* verdicts_out) {
+    const Slot::GateUnit g = S.gate;
+    const uint8_t* rec = S.h_gate.as<uint8_t>();
+    std::vector<slideo_verdict> v((size_t)g.k);
+    if (g.k > 0) unit_collect(m, S, v.data());      // (an overflowed unit is re-run from its gathered frames, S.u_in: never the gate)
+    else S.busy = false;
+    S.gate.on = false;
+    const uint8_t* flag = rec + gate_rec_flag_ofs(g.n);
+    int r = 0;
+    for (int i = 0; i < g.n; ++i) {
+        unsigned long long s;
+        std::memcpy(&s, rec + gate_rec_ssd_ofs() + (size_t)i * 8, 8);
+        const float sim = (i == 0 && g.force0) ? 0.0f : changed_similarity(s, g.sw, g.sh);      // video_capture.rs:92
+        if ((sim < m->cfg.changed_similarity) != (flag[i] != 0))
+            fail(SLIDEO_ERR_HIP, "internal: the gate's flag of frame %d (%d, SSD %llu) is not the host expression's", i, (int)flag[i], s);
+        changed_out[i] = flag[i];
+        if (similarity_out) similarity_out[i] = sim;
+        if (flag[i]) verdicts_out[i] = v[(size_t)r++];
+        else verdicts_out[i] = slideo_verdict{-1, 0.0f, 0, 0};
+    }
+}
+
+void gate_validate(slideo_matcher* m, int n, FrameSrc& src, const uint8_t* changed_out, const slideo_verdict* verdicts_out) {
+    if (n > 0 && !changed_out) fail(SLIDEO_ERR_INVALID_ARG, "null changed_out");
+    validate_frames(src, m, n, verdicts_out);
+    gate_check(m, src);
+}
+
+// slideo_match_changed_frames_*: the call cut into units and pipelined through the slots, as match_frames_impl does
+void match_changed_impl(slideo_matcher* m, int n, FrameSrc src, uint8_t* changed_out, float* similarity_out, slideo_verdict* out, hipStream_t user_stream) {
+    gate_validate(m, n, src, changed_out, out);
+    HIP_CHECK(hipSetDevice(m->device));
+    require_idle(m);
+    m->last_fcs.clear();
+    if (n == 0) return;
+    GeomEntry& ge = geom_for(m, src.unit_w(), src.unit_h());
+    area_class_for(m, src.unit_w(), src.unit_h());
+    upload_area(m);
+    int unit = sub_batch_for(m, ge.g, n, src.staging_bytes(gate_small_budget(m)));
+    if (n >= 128 && unit >= (n + 1) / 2) unit = (n + 1) / 2;
+    if (!src.on_device && m->host_unit > 0 && n >= 2 * m->host_unit) unit = std::min(unit, m->host_unit);      // unit u + 1 uploads and gates while unit u matches
+    struct Pending { Slot* S; int ofs; };
+    std::vector<Pending> pend;
+    if (src.on_device && user_stream)
+        for (Slot& S : m->slots) {
+            HIP_CHECK(hipEventRecord(S.ev_in, user_stream));
+            HIP_CHECK(hipStreamWaitEvent(S.st, S.ev_in, 0));
+        }
+    int done = 0;
+    hipStream_t cs = src.pinned ? m->copy_st : nullptr;
+    m->units_pending = n > unit;
+    auto collect = [&](const Pending& p) {
+        gate_unit_collect(m, *p.S, changed_out + p.ofs, similarity_out ? similarity_out + p.ofs : nullptr, out + p.ofs);
+        done += p.S->gate.n;
+        if (m->progress) m->progress(m->progress_user, (uint64_t)done, (uint64_t)n, "Processing frames...");
+    };
+    try {
+        for (int i = 0; i < n; i += unit) {
+            const int cnt = std::min(unit, n - i);
+            if ((int)pend.size() == NSLOTS) { collect(pend[0]); pend.erase(pend.begin()); }
+            Slot& S = m->slots[m->next_slot];
+            m->next_slot = (m->next_slot + 1) % NSLOTS;
+            gate_unit_submit(m, S, src, i, cnt, cs);
+            pend.push_back({&S, i});
+        }
+        for (Pending& p : pend) collect(p);
+        m->units_pending = false;
+    } catch (...) {
+        m->units_pending = false;
+        (void)hipStreamSynchronize(m->copy_st);
+        for (Slot& S : m->slots) { (void)hipStreamSynchronize(S.st); S.busy = false; S.gate.on = false; }
+        throw;
+    }
+}
+
+// slideo_match_changed_frames_submit[_yuv420]_dev
+void submit_changed_impl(slideo_matcher* m, int32_t n, FrameSrc src, void* hip_stream, int64_t* ticket_out) {
+    if (!ticket_out) fail(SLIDEO_ERR_INVALID_ARG, "null ticket_out");
+    validate_frames(src, m, n, ticket_out);
+    if (n < 1) fail(SLIDEO_ERR_INVALID_ARG, "submit needs at least one frame");
+    gate_check(m, src);
+    HIP_CHECK(hipSetDevice(m->device));
+    Slot& S = m->slots[m->next_slot];
+    if (S.busy) fail(SLIDEO_ERR_STATE, "all slots are in flight: collect ticket %lld first", (long long)S.ticket);
+    GeomEntry& ge = geom_for(m, src.unit_w(), src.unit_h());
+    const int fit = sub_batch_for(m, ge.g, n, src.staging_bytes(gate_small_budget(m)));
+    if (n > fit)
+        fail(SLIDEO_ERR_CAPACITY, "%d frames exceed the per-slot workspace budget (%d); submit smaller units or raise SLIDEO_WS_GB", n, fit);
+    area_class_for(m, src.unit_w(), src.unit_h());
+    upload_area(m);
+    { bool any = false; for (const Slot& c : m->slots) any |= c.busy; if (!any) m->last_fcs.clear(); }
+    if (hip_stream) {
+        HIP_CHECK(hipEventRecord(S.ev_in, reinterpret_cast<hipStream_t>(hip_stream)));
+        HIP_CHECK(hipStreamWaitEvent(S.st, S.ev_in, 0));
+    }
+    gate_unit_submit(m, S, src, 0, n, nullptr);
+    S.ticket = m->next_ticket++;
+    *ticket_out = S.ticket;
+    m->next_slot = (m->next_slot + 1) % NSLOTS;
+    if (S.gate.k > 0)
+        for (Slot& O : m->slots) if (&O != &S && !O.busy) O.match_capacity(S);
+}
+
+}  // namespace
+}  // namespace slideo
+
+extern "C" {
+
+int64_t slideo_changed_ssd_threshold(float changed_similarity, int32_t small_w, int32_t small_h) {
+    if (small_w < 1 || small_h < 1 || (int64_t)small_w * small_h > INT32_MAX) return -1;
+    return ssd_threshold(changed_similarity, small_w, small_h);
+}
+
+int32_t slideo_matcher_gate_reset(slideo_matcher* m, const uint8_t* prev_small, int32_t small_w, int32_t small_h) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    if (prev_small && (small_w < 1 || small_h < 1 || (int64_t)small_w * small_h > m->cfg.small_area))
+        fail(SLIDEO_ERR_INVALID_ARG, "gate_reset: a %dx%d small image (at most small_area = %d pixels)", small_w, small_h, m->cfg.small_area);
+    require_idle(m);
+    if (!prev_small) { gate_state_reset(m); return SLIDEO_OK; }
+    HIP_CHECK(hipSetDevice(m->device));
+    const size_t sb = (size_t)small_w * small_h * 3;
+    m->d_gate_small.reserve(sb);
+    HIP_CHECK(hipMemcpyAsync(m->d_gate_small.p, prev_small, sb, hipMemcpyHostToDevice, m->stream));
+    HIP_CHECK(hipStreamSynchronize(m->stream));
+    gate_state_reset(m);
+    m->gate.has = true; m->gate.sw = small_w; m->gate.sh = small_h;
+    API_CATCH(m)
+}
+
+int32_t slideo_matcher_gate_last_small(slideo_matcher* m, uint8_t* out, int64_t out_capacity, int32_t* sw, int32_t* sh) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    if (!sw || !sh) fail(SLIDEO_ERR_INVALID_ARG, "null sw/sh");
+    require_idle(m);
+    if (!m->gate.has) fail(SLIDEO_ERR_STATE, "the gate state is \"none\": no frame was gated since the last reset");
+    *sw = m->gate.sw; *sh = m->gate.sh;
+    const int64_t sb = (int64_t)m->gate.sw * m->gate.sh * 3;
+    if (sb > out_capacity) fail(SLIDEO_ERR_CAPACITY, "small image needs %lld bytes", (long long)sb);
+    if (out) {
+        HIP_CHECK(hipSetDevice(m->device));
+        for (Slot& S : m->slots) HIP_CHECK(hipStreamSynchronize(S.st));          // (a collected unit's write of the state may still be running)
+        HIP_CHECK(hipMemcpyAsync(out, m->d_gate_small.p, (size_t)sb, hipMemcpyDeviceToHost, m->stream));
+        HIP_CHECK(hipStreamSynchronize(m->stream));
+    }
+    API_CATCH(m)
+}
+
+int32_t slideo_match_changed_frames_bgr8(slideo_matcher* m, int32_t n_frames, const uint8_t* frames, int32_t width, int32_t height, int32_t stride_bytes,
+                                         int64_t frame_stride_bytes, uint8_t* changed_out, float* similarity_out, slideo_verdict* verdicts_out) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    match_changed_impl(m, n_frames, FrameSrc::bgr8(frames, false, width, height, stride_bytes, frame_stride_bytes), changed_out, similarity_out,
+                       verdicts_out, nullptr);
+    API_CATCH(m)
+}
+
+int32_t slideo_match_changed_frames_yuv420(slideo_matcher* m, int32_t n_frames, const uint8_t* frames, int32_t width, int32_t height,
+                                           const slideo_yuv420_layout* layout, int64_t frame_stride_bytes, uint8_t* changed_out, float* similarity_out,
+                                           slideo_verdict* verdicts_out) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    match_changed_impl(m, n_frames, FrameSrc::yuv420(frames, false, width, height, layout, frame_stride_bytes), changed_out, similarity_out,
+                       verdicts_out, nullptr);
+    API_CATCH(m)
+}
+
+int32_t slideo_match_changed_frames_bgr8_dev(slideo_matcher* m, int32_t n_frames, const uint8_t* frames_dev, int32_t width, int32_t height,
+                                             int32_t stride_bytes, int64_t frame_stride_bytes, uint8_t* changed_out, float* similarity_out,
+                                             slideo_verdict* verdicts_out, void* hip_stream) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    match_changed_impl(m, n_frames, FrameSrc::bgr8(frames_dev, true, width, height, stride_bytes, frame_stride_bytes), changed_out, similarity_out,
+                       verdicts_out, reinterpret_cast<hipStream_t>(hip_stream));
+    API_CATCH(m)
+}
+
+int32_t slideo_match_changed_frames_yuv420_dev(slideo_matcher* m, int32_t n_frames, const uint8_t* frames_dev, int32_t width, int32_t height,
+                                               const slideo_yuv420_layout* layout, int64_t frame_stride_bytes, uint8_t* changed_out,
+                                               float* similarity_out, slideo_verdict* verdicts_out, void* hip_stream) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    match_changed_impl(m, n_frames, FrameSrc::yuv420(frames_dev, true, width, height, layout, frame_stride_bytes), changed_out, similarity_out,
+                       verdicts_out, reinterpret_cast<hipStream_t>(hip_stream));
+    API_CATCH(m)
+}
+
+int32_t slideo_match_changed_frames_submit_dev(slideo_matcher* m, int32_t n_frames, const uint8_t* frames_dev, int32_t width, int32_t height,
+                                               int32_t stride_bytes, int64_t frame_stride_bytes, void* hip_stream, int64_t* ticket_out) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    submit_changed_impl(m, n_frames, FrameSrc::bgr8(frames_dev, true, width, height, stride_bytes, frame_stride_bytes), hip_stream, ticket_out);
+    API_CATCH(m)
+}
+
+int32_t slideo_match_changed_frames_submit_yuv420_dev(slideo_matcher* m, int32_t n_frames, const uint8_t* frames_dev, int32_t width, int32_t height,
+                                                      const slideo_yuv420_layout* layout, int64_t frame_stride_bytes, void* hip_stream,
+                                                      int64_t* ticket_out) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    submit_changed_impl(m, n_frames, FrameSrc::yuv420(frames_dev, true, width, height, layout, frame_stride_bytes), hip_stream, ticket_out);
+    API_CATCH(m)
+}
+
+int32_t slideo_match_changed_frames_collect(slideo_matcher* m, int64_t ticket, uint8_t* changed_out, float* similarity_out, slideo_verdict* verdicts_out) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    if (!changed_out || !verdicts_out) fail(SLIDEO_ERR_INVALID_ARG, "null changed_out/verdicts_out");
+    HIP_CHECK(hipSetDevice(m->device));
+    Slot* S = nullptr;
+    for (Slot& c : m->slots) if (c.busy && c.ticket == ticket) S = &c;
+    if (!S) fail(SLIDEO_ERR_STATE, "ticket %lld is not in flight", (long long)ticket);
+    for (Slot& c : m->slots) if (c.busy && c.ticket < ticket) fail(SLIDEO_ERR_STATE, "collect ticket %lld first (in order)", (long long)c.ticket);
+    if (!S->gate.on) fail(SLIDEO_ERR_STATE, "ticket %lld is not a gated unit: slideo_match_frames_collect collects it", (long long)ticket);
+    gate_unit_collect(m, *S, changed_out, similarity_out, verdicts_out);
+    API_CATCH(m)
+}
+
+}  // extern "C"

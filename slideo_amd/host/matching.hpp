@@ -213,10 +213,32 @@ public:
         std::vector<uint8_t> frames, prev_small, last_small;
         std::vector<std::pair<double, size_t>> meta;
         int sw = 0, sh = 0;
+        // the changed-frame gate (slideo_amd.h "Changed-frame gate"): a one-device group gates through its member, one call per flush,
+        // the last small image carried in the matcher; a group of several devices keeps the mask + kept pair (it has no gated form)
+        slideo_matcher* gate = h_->n_devices == 1 ? slideo_group_member(h_->g, 0) : nullptr;
+        if (gate) h_->check(slideo_matcher_gate_reset(gate, nullptr, 0, 0));            // the first frame of the video is always changed
+        auto emit = [&](const std::vector<int32_t>& idx, const slideo_verdict* v) {
+            for (size_t k = 0; k < idx.size(); ++k) {
+                std::optional<I> img;
+                if (v[k].page_idx >= 0) img = (*images_)[(size_t)v[k].page_idx];
+                results.push_back({meta[idx[k]].first, meta[idx[k]].second, img});
+            }
+        };
         auto flush = [&]() {
             if (meta.empty()) return;
             const int n = (int)meta.size();
             std::vector<uint8_t> changed(n);
+            if (gate) {       // MarkSimilarIter + match_images_with_frame of the changed frames (mo/lib.rs:205-214) in one call
+                std::vector<slideo_verdict> all(n), v;
+                h_->check(slideo_match_changed_frames_bgr8(gate, n, frames.data(), video.width, video.height, video.width * 3, (int64_t)fb,
+                                                           changed.data(), nullptr, all.data()));
+                std::vector<int32_t> idx;
+                for (int i = 0; i < n; ++i) if (changed[i]) { idx.push_back(i); v.push_back(all[i]); }
+                emit(idx, v.data());
+                for (int i = 0; i < n; ++i) rep_.report(++progress, frames_to_process, "Processing frames of '" + name + "'...");   // mo/lib.rs:192-203
+                meta.clear(); frames.clear();
+                return;
+            }
             if (last_small.empty()) {       // size of the small image: ask once
                 std::vector<uint8_t> tmp(fb), red;
                 const uint8_t* img = frames.data();
@@ -239,11 +261,7 @@ public:
                 std::vector<slideo_verdict> v(idx.size());
                 // mo/lib.rs:213-214 on the copy of the frames the mask call left on the devices (no second upload)
                 h_->check(slideo_group_match_kept_frames(h_->g, (int32_t)idx.size(), idx.data(), v.data()));
-                for (size_t k = 0; k < idx.size(); ++k) {
-                    std::optional<I> img;
-                    if (v[k].page_idx >= 0) img = (*images_)[(size_t)v[k].page_idx];
-                    results.push_back({meta[idx[k]].first, meta[idx[k]].second, img});
-                }
+                emit(idx, v.data());
             }
             for (int i = 0; i < n; ++i) rep_.report(++progress, frames_to_process, "Processing frames of '" + name + "'...");   // mo/lib.rs:192-203
             meta.clear(); frames.clear();

@@ -183,12 +183,34 @@ class HipVideoMatcherTask:
 
         pend_frames, pend_meta, prev_small = [], [], None
         yuv = getattr(video, "yuv420_format", None)              # RawVideoYuv420: 'nv12' / 'i420'; RawVideo: None (BGR)
+        # the changed-frame gate (include/slideo_amd.h "Changed-frame gate"): one gated call per flush, the last small image carried
+        # in the matcher.  None (a matcher without the gated calls, a group of several devices): the mask + kept pair below.
+        gate = _gated_matcher(m)
+        if gate is not None:
+            gate.gate_reset(None)                                # the first frame of the video is always changed
+
+        def emit(idx, verdicts):
+            for j, v in zip(idx, verdicts):
+                t, fi = pend_meta[j]
+                img = self._images[v["page_idx"]] if v["page_idx"] >= 0 else None
+                results.append(Matching(video_time=t, video_frame_idx=fi, image=img))
 
         def flush():
             nonlocal prev_small
             if not pend_frames:
                 return
             stack = np.stack(pend_frames)
+            if gate is not None:                       # MarkSimilarIter + match_images_with_frame of the changed frames, one call
+                if yuv:
+                    changed, _, verdicts = gate.match_changed_frames_yuv420(stack, video.width, video.height, yuv)
+                else:
+                    changed, _, verdicts = gate.match_changed_frames(stack)
+                idx = np.nonzero(changed)[0]
+                emit(idx, verdicts[idx])
+                for _ in pend_frames:
+                    report_progress()
+                pend_frames.clear(); pend_meta.clear()
+                return
             if yuv:                                                                   # decoded 4:2:0 frames: converted on the GPU
                 changed, _, prev_small = m.changed_mask_yuv420(stack, video.width, video.height, yuv, prev_small)
             else:
@@ -202,10 +224,7 @@ class HipVideoMatcherTask:
                     verdicts = m.match_frames_yuv420(stack[idx], video.width, video.height, yuv)
                 else:
                     verdicts = m.match_frames(stack[idx])
-                for j, v in zip(idx, verdicts):
-                    t, fi = pend_meta[j]
-                    img = self._images[v["page_idx"]] if v["page_idx"] >= 0 else None
-                    results.append(Matching(video_time=t, video_frame_idx=fi, image=img))
+                emit(idx, verdicts)
             for _ in pend_frames:
                 report_progress()
             pend_frames.clear(); pend_meta.clear()
@@ -217,6 +236,17 @@ class HipVideoMatcherTask:
         flush()
         self._rep.report(frames_to_process, frames_to_process, "Finished!")           # lib.rs:223-227
         return dedup_timeline(results)
+
+
+def _gated_matcher(m):
+    """The handle whose gated calls serve a task over `m`: m itself (a Matcher), the one member of a one-device group (the group
+    has no gated form: a shard needs the frame before its block), or None."""
+    if hasattr(m, "match_changed_frames"):
+        return m
+    if hasattr(m, "member") and len(getattr(m, "devices", [])) == 1:
+        one = m.member(0)
+        return one if hasattr(one, "match_changed_frames") else None
+    return None
 
 
 def dedup_timeline(mappings: List[Matching]) -> List[Matching]:
