@@ -199,10 +199,6 @@ DevFrames stage_frames(slideo_matcher* m, Slot& S, const FrameSrc& src, int firs
     return DevFrames{stage, uw, uh, uw * 3, ub};
 }
 
-// ---- one unit of the per-frame hot path: enqueue everything, then collect ---------------
-// `frames_dev` must stay valid until the unit is collected (reproject reads the frames).
-// keypoints per frame the capacity-sized path provides for: twice the quota (ties at a level's retainBest threshold are kept, so
-// no finite bound is safe; a frame beyond it is detected on the device and the unit re-run through the exact-size path)
 // the cv::RNG((uint64)-1) stream RANSACPointSetRegistrator draws its samples from, pre-drawn (ptsetreg.cpp: rng state
 // starts at -1 on every call, so every candidate reads the same stream from position 0)
 void upload_rng_stream(slideo_matcher* m, uint32_t len) {
@@ -214,12 +210,16 @@ void upload_rng_stream(slideo_matcher* m, uint32_t len) {
     m->rng_len = len;
 }
 
+// keypoints per frame the capacity-sized path provides for: twice the quota (ties at a level's retainBest threshold are kept, so
+// no finite bound is safe; a frame beyond it is detected on the device and the unit re-run through the exact-size path)
 uint32_t kp_cap_for(const slideo_matcher* m, const PyrGeom& g) {
     int cap = std::max(2 * m->cfg.nfeatures, m->cfg.nfeatures + 1024);
     cap = std::min(cap, KP_SORT_LDS);
     return (uint32_t)std::max(1, std::min(cap, std::max(g.cand_per_frame, 1)));
 }
 
+// ---- one unit of the per-frame hot path: enqueue everything, then collect ---------------
+// `f` must stay valid until the unit is collected (reproject reads the frames).
 void unit_submit(slideo_matcher* m, Slot& S, const DevFrames& f, int n, bool allow_async) {
     // (does this unit share the chip with others?  the search then runs one block per CU: stage_knn.hip knn_plan)
     { bool others = m->units_pending; for (const Slot& o : m->slots) others |= (&o != &S && o.busy); S.knn.shared = others; }
@@ -323,21 +323,36 @@ void unit_collect(slideo_matcher* m, Slot& S, slideo_verdict* out_host) {
     std::memcpy(m->last_fcs.data() + base, ho + (size_t)n * sizeof(slideo_verdict), (size_t)n * sizeof(FrameCands));
 }
 
-// Synchronous matching of n frames: cut into units and run them through the slots as a pipeline.
-void match_frames_impl(slideo_matcher* m, int n, FrameSrc src, slideo_verdict* out, hipStream_t user_stream) {
+// A unit of either kind begun on slot S: frames [first, first + n) of src staged and, plain, all of them through unit_submit;
+// gated, through the gate and the changed ones through unit_submit (stage_gate.hip)
+static void unit_begin(slideo_matcher* m, Slot& S, const FrameSrc& src, int first, int n, hipStream_t cs, bool gated) {
+    if (gated) gate_unit_submit(m, S, src, first, n, cs);
+    else unit_submit(m, S, stage_frames(m, S, src, first, n, cs), n);
+}
+
+// max frames per unit of a call of either kind under the workspace budget
+static int unit_fit(slideo_matcher* m, const FrameSrc& src, int n, bool gated) {
+    return sub_batch_for(m, geom_for(m, src.unit_w(), src.unit_h()).g, n, src.staging_bytes(gated ? gate_small_budget(m) : 0));
+}
+
+// Synchronous matching of n frames, plain or gated (changed_out, similarity_out: a gated call's): cut into units and run them
+// through the slots as a pipeline.
+void match_frames_impl(slideo_matcher* m, int n, FrameSrc src, slideo_verdict* out, hipStream_t user_stream, bool gated, uint8_t* changed_out,
+                       float* similarity_out) {
+    if (gated && n > 0 && !changed_out) fail(SLIDEO_ERR_INVALID_ARG, "null changed_out");
     validate_frames(src, m, n, out);
+    if (gated) gate_check(m, src);
     HIP_CHECK(hipSetDevice(m->device));
     require_idle(m);
     m->last_fcs.clear();
     if (n == 0) return;
-    GeomEntry& ge = geom_for(m, src.unit_w(), src.unit_h());
+    int unit = unit_fit(m, src, n, gated);
     area_class_for(m, src.unit_w(), src.unit_h());
     upload_area(m);
-    int unit = sub_batch_for(m, ge.g, n, src.staging_bytes());
     if (n >= 128 && unit >= (n + 1) / 2) unit = (n + 1) / 2;      // two halves overlap ORB with kNN / verify
     // Host frames: the call is bound by the H2D copies (6.2 MB per 1080p frame: 256 frames = 29 ms at 55 GB/s against 14 ms of
-    // kernels), so what matters is that the copy engines never wait: short units, each copied on its slot's stream while the
-    // units before it compute — with two halves the second half's kernels start only when all of it has arrived.
+    // kernels), so what matters is that the copy engines never wait: short units, each copied (and, in a gated call, gated) on its
+    // slot's stream while the units before it compute — with two halves the second half's kernels start only when all of it has arrived.
     if (!src.on_device && m->host_unit > 0 && n >= 2 * m->host_unit) unit = std::min(unit, m->host_unit);
     struct Pending { Slot* S; int ofs; };
     std::vector<Pending> pend;
@@ -352,31 +367,107 @@ void match_frames_impl(slideo_matcher* m, int n, FrameSrc src, slideo_verdict* o
     // through the copy stream)
     hipStream_t cs = src.pinned ? m->copy_st : nullptr;
     m->units_pending = n > unit;
-    try {
-        for (int i = 0; i < n; i += unit) {
-            const int cnt = std::min(unit, n - i);
-            if ((int)pend.size() == NSLOTS) {
-                unit_collect(m, *pend[0].S, out + pend[0].ofs);
-                done += pend[0].S->n;
-                pend.erase(pend.begin());
-                if (m->progress) m->progress(m->progress_user, (uint64_t)done, (uint64_t)n, "Processing frames...");
-            }
-            Slot& S = m->slots[m->next_slot];
-            m->next_slot = (m->next_slot + 1) % NSLOTS;
-            unit_submit(m, S, stage_frames(m, S, src, i, cnt, cs), cnt);
-            pend.push_back({&S, i});
-        }
-        for (Pending& p : pend) {
+    auto collect = [&](const Pending& p) {
+        if (gated) {
+            gate_unit_collect(m, *p.S, changed_out + p.ofs, similarity_out ? similarity_out + p.ofs : nullptr, out + p.ofs);
+            done += p.S->gate.n;
+        } else {
             unit_collect(m, *p.S, out + p.ofs);
             done += p.S->n;
-            if (m->progress) m->progress(m->progress_user, (uint64_t)done, (uint64_t)n, "Processing frames...");
         }
+        if (m->progress) m->progress(m->progress_user, (uint64_t)done, (uint64_t)n, "Processing frames...");
+    };
+    try {
+        for (int i = 0; i < n; i += unit) {
+            if ((int)pend.size() == NSLOTS) { collect(pend[0]); pend.erase(pend.begin()); }
+            Slot& S = m->slots[m->next_slot];
+            m->next_slot = (m->next_slot + 1) % NSLOTS;
+            unit_begin(m, S, src, i, std::min(unit, n - i), cs, gated);
+            pend.push_back({&S, i});
+        }
+        for (Pending& p : pend) collect(p);
         m->units_pending = false;
     } catch (...) {
         m->units_pending = false;
         (void)hipStreamSynchronize(m->copy_st);          // (DMA from the caller's pinned buffer may still be running)
-        for (Slot& S : m->slots) { (void)hipStreamSynchronize(S.st); S.busy = false; }
+        for (Slot& S : m->slots) { (void)hipStreamSynchronize(S.st); S.busy = false; S.gate.on = false; }
         throw;
+    }
+}
+
+// slideo_match_frames_submit[_yuv420]_dev and their gated twins: one unit admitted to the next slot
+static void submit_impl(slideo_matcher* m, int32_t n_frames, FrameSrc src, void* hip_stream, int64_t* ticket_out, bool gated) {
+    if (!ticket_out) fail(SLIDEO_ERR_INVALID_ARG, "null ticket_out");
+    validate_frames(src, m, n_frames, ticket_out);
+    if (n_frames < 1) fail(SLIDEO_ERR_INVALID_ARG, "submit needs at least one frame");
+    if (gated) gate_check(m, src);
+    HIP_CHECK(hipSetDevice(m->device));
+    Slot& S = m->slots[m->next_slot];
+    if (S.busy) fail(SLIDEO_ERR_STATE, "all slots are in flight: collect ticket %lld first", (long long)S.ticket);
+    const int fit = unit_fit(m, src, n_frames, gated);
+    if (n_frames > fit)
+        fail(SLIDEO_ERR_CAPACITY, "%d frames exceed the per-slot workspace budget (%d); submit smaller units or raise SLIDEO_WS_GB", n_frames, fit);
+    area_class_for(m, src.unit_w(), src.unit_h());
+    upload_area(m);
+    { bool any = false; for (const Slot& c : m->slots) any |= c.busy; if (!any) m->last_fcs.clear(); }
+    if (hip_stream) {
+        HIP_CHECK(hipEventRecord(S.ev_in, reinterpret_cast<hipStream_t>(hip_stream)));
+        HIP_CHECK(hipStreamWaitEvent(S.st, S.ev_in, 0));
+    }
+    unit_begin(m, S, src, 0, n_frames, nullptr, gated);
+    S.ticket = m->next_ticket++;
+    *ticket_out = S.ticket;
+    m->next_slot = (m->next_slot + 1) % NSLOTS;
+    // the next units find their workspace sized (S.n = 0: a gated unit none of whose frames changed, which ran no pipeline)
+    if (S.n > 0)
+        for (Slot& O : m->slots) if (&O != &S && !O.busy) O.match_capacity(S);
+}
+
+// The slot whose unit a collect call of the given kind collects: in flight, the oldest ticket in flight, and of that kind
+static Slot& slot_of_ticket(slideo_matcher* m, int64_t ticket, bool gated) {
+    Slot* S = nullptr;
+    for (Slot& c : m->slots) if (c.busy && c.ticket == ticket) S = &c;
+    if (!S) fail(SLIDEO_ERR_STATE, "ticket %lld is not in flight", (long long)ticket);
+    for (Slot& c : m->slots) if (c.busy && c.ticket < ticket) fail(SLIDEO_ERR_STATE, "collect ticket %lld first (in order)", (long long)c.ticket);
+    if (S->gate.on && !gated) fail(SLIDEO_ERR_STATE, "ticket %lld is a gated unit: slideo_match_changed_frames_collect collects it", (long long)ticket);
+    if (!S->gate.on && gated) fail(SLIDEO_ERR_STATE, "ticket %lld is not a gated unit: slideo_match_frames_collect collects it", (long long)ticket);
+    return *S;
+}
+
+// slideo_changed_mask_bgr8 / _yuv420
+void changed_mask_impl(slideo_matcher* m, int n_frames, FrameSrc src, const uint8_t* prev_small, uint8_t* last_small_out, uint8_t* changed_out,
+                       float* similarity_out) {
+    if (n_frames < 0 || (n_frames > 0 && (!src.p || !changed_out))) fail(SLIDEO_ERR_INVALID_ARG, "null frames/changed");
+    validate_frames(src);
+    apply_working_size(m, src);
+    if (n_frames == 0) return;
+    HIP_CHECK(hipSetDevice(m->device));
+    require_idle(m);
+    Slot& S = m->slots[0];
+    hipStream_t st = S.st;
+    int sw = 0, sh = 0;
+    const DevFrames f = stage_frames(m, S, src, 0, n_frames);
+    m->kept = slideo_matcher::Kept{true, n_frames, f.w, f.h, f.stride};      // stays in slot 0's staging buffer: slideo_match_kept_frames
+    run_small(m, f, n_frames, sw, sh, st);
+    const size_t sb = (size_t)sw * sh * 3;
+    DevBuf& prev = m->d_prev_small;
+    prev.reserve(sb);
+    if (prev_small) HIP_CHECK(hipMemcpyAsync(prev.p, prev_small, sb, hipMemcpyHostToDevice, st));
+    m->d_ssd.reserve((size_t)n_frames * 8);
+    // pair i: (small[i-1], small[i]); pair 0 uses prev
+    if (prev_small) launch_ssd(prev.as<uint8_t>(), 0, m->d_small.as<uint8_t>(), 0, (int64_t)sb, m->d_ssd.as<unsigned long long>(), 1, st);
+    if (n_frames > 1)
+        launch_ssd(m->d_small.as<uint8_t>(), (int64_t)sb, m->d_small.as<uint8_t>() + sb, (int64_t)sb, (int64_t)sb, m->d_ssd.as<unsigned long long>() + 1, n_frames - 1, st);
+    std::vector<unsigned long long> ssd(n_frames, 0);
+    HIP_CHECK(hipMemcpyAsync(ssd.data(), m->d_ssd.p, (size_t)n_frames * 8, hipMemcpyDeviceToHost, st));
+    if (last_small_out)
+        HIP_CHECK(hipMemcpyAsync(last_small_out, m->d_small.as<uint8_t>() + sb * (n_frames - 1), sb, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    for (int i = 0; i < n_frames; ++i) {
+        float sim = 0.0f;   // video_capture.rs:92: the first frame compares as 0.0
+        if (i > 0 || prev_small) sim = changed_similarity(ssd[i], sw, sh);
+        changed_out[i] = sim < m->cfg.changed_similarity ? 1 : 0;
+        if (similarity_out) similarity_out[i] = sim;
     }
 }
 
@@ -843,85 +934,11 @@ int32_t slideo_match_frames_bgr8_dev(slideo_matcher* m, int32_t n_frames, const 
     API_CATCH(m)
 }
 
-}  // extern "C"
-
-namespace {
-
-// slideo_match_frames_submit[_yuv420]_dev
-void submit_impl(slideo_matcher* m, int32_t n_frames, FrameSrc src, void* hip_stream, int64_t* ticket_out) {
-    if (!ticket_out) fail(SLIDEO_ERR_INVALID_ARG, "null ticket_out");
-    validate_frames(src, m, n_frames, ticket_out);
-    if (n_frames < 1) fail(SLIDEO_ERR_INVALID_ARG, "submit needs at least one frame");
-    HIP_CHECK(hipSetDevice(m->device));
-    Slot& S = m->slots[m->next_slot];
-    if (S.busy) fail(SLIDEO_ERR_STATE, "all slots are in flight: collect ticket %lld first", (long long)S.ticket);
-    GeomEntry& ge = geom_for(m, src.unit_w(), src.unit_h());
-    if (n_frames > sub_batch_for(m, ge.g, n_frames, src.staging_bytes()))
-        fail(SLIDEO_ERR_CAPACITY, "%d frames exceed the per-slot workspace budget (%d); submit smaller units or raise SLIDEO_WS_GB",
-             n_frames, sub_batch_for(m, ge.g, n_frames, src.staging_bytes()));
-    area_class_for(m, src.unit_w(), src.unit_h());
-    upload_area(m);
-    { bool any = false; for (const Slot& c : m->slots) any |= c.busy; if (!any) m->last_fcs.clear(); }
-    if (hip_stream) {
-        HIP_CHECK(hipEventRecord(S.ev_in, reinterpret_cast<hipStream_t>(hip_stream)));
-        HIP_CHECK(hipStreamWaitEvent(S.st, S.ev_in, 0));
-    }
-    unit_submit(m, S, stage_frames(m, S, src, 0, n_frames), n_frames);
-    S.ticket = m->next_ticket++;
-    *ticket_out = S.ticket;
-    m->next_slot = (m->next_slot + 1) % NSLOTS;
-    for (Slot& O : m->slots) if (&O != &S && !O.busy) O.match_capacity(S);  // the next units find their workspace sized
-}
-
-}  // namespace
-
-namespace slideo {
-
-void changed_mask_impl(slideo_matcher* m, int n_frames, FrameSrc src, const uint8_t* prev_small, uint8_t* last_small_out, uint8_t* changed_out,
-                       float* similarity_out) {
-    if (n_frames < 0 || (n_frames > 0 && (!src.p || !changed_out))) fail(SLIDEO_ERR_INVALID_ARG, "null frames/changed");
-    validate_frames(src);
-    apply_working_size(m, src);
-    if (n_frames == 0) return;
-    HIP_CHECK(hipSetDevice(m->device));
-    require_idle(m);
-    Slot& S = m->slots[0];
-    hipStream_t st = S.st;
-    int sw = 0, sh = 0;
-    const DevFrames f = stage_frames(m, S, src, 0, n_frames);
-    m->kept = slideo_matcher::Kept{true, n_frames, f.w, f.h, f.stride};      // stays in slot 0's staging buffer: slideo_match_kept_frames
-    run_small(m, f, n_frames, sw, sh, st);
-    const size_t sb = (size_t)sw * sh * 3;
-    DevBuf& prev = m->d_prev_small;
-    prev.reserve(sb);
-    if (prev_small) HIP_CHECK(hipMemcpyAsync(prev.p, prev_small, sb, hipMemcpyHostToDevice, st));
-    m->d_ssd.reserve((size_t)n_frames * 8);
-    // pair i: (small[i-1], small[i]); pair 0 uses prev
-    if (prev_small) launch_ssd(prev.as<uint8_t>(), 0, m->d_small.as<uint8_t>(), 0, (int64_t)sb, m->d_ssd.as<unsigned long long>(), 1, st);
-    if (n_frames > 1)
-        launch_ssd(m->d_small.as<uint8_t>(), (int64_t)sb, m->d_small.as<uint8_t>() + sb, (int64_t)sb, (int64_t)sb, m->d_ssd.as<unsigned long long>() + 1, n_frames - 1, st);
-    std::vector<unsigned long long> ssd(n_frames, 0);
-    HIP_CHECK(hipMemcpyAsync(ssd.data(), m->d_ssd.p, (size_t)n_frames * 8, hipMemcpyDeviceToHost, st));
-    if (last_small_out)
-        HIP_CHECK(hipMemcpyAsync(last_small_out, m->d_small.as<uint8_t>() + sb * (n_frames - 1), sb, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    for (int i = 0; i < n_frames; ++i) {
-        float sim = 0.0f;   // video_capture.rs:92: the first frame compares as 0.0
-        if (i > 0 || prev_small) sim = changed_similarity(ssd[i], sw, sh);
-        changed_out[i] = sim < m->cfg.changed_similarity ? 1 : 0;
-        if (similarity_out) similarity_out[i] = sim;
-    }
-}
-
-}  // namespace slideo
-
-extern "C" {
-
 int32_t slideo_match_frames_submit_dev(slideo_matcher* m, int32_t n_frames, const uint8_t* frames_dev, int32_t width, int32_t height,
                                        int32_t stride_bytes, int64_t frame_stride_bytes, void* hip_stream, int64_t* ticket_out) {
     if (!m) return SLIDEO_ERR_INVALID_ARG;
     API_TRY
-    submit_impl(m, n_frames, FrameSrc::bgr8(frames_dev, true, width, height, stride_bytes, frame_stride_bytes), hip_stream, ticket_out);
+    submit_impl(m, n_frames, FrameSrc::bgr8(frames_dev, true, width, height, stride_bytes, frame_stride_bytes), hip_stream, ticket_out, false);
     API_CATCH(m)
 }
 
@@ -930,15 +947,11 @@ int32_t slideo_match_frames_collect_dev(slideo_matcher* m, int64_t ticket, slide
     API_TRY
     if (!verdicts_out) fail(SLIDEO_ERR_INVALID_ARG, "null verdicts_out");
     HIP_CHECK(hipSetDevice(m->device));
-    Slot* S = nullptr;
-    for (Slot& c : m->slots) if (c.busy && c.ticket == ticket) S = &c;
-    if (!S) fail(SLIDEO_ERR_STATE, "ticket %lld is not in flight", (long long)ticket);
-    for (Slot& c : m->slots) if (c.busy && c.ticket < ticket) fail(SLIDEO_ERR_STATE, "collect ticket %lld first (in order)", (long long)c.ticket);
-    if (S->gate.on) fail(SLIDEO_ERR_STATE, "ticket %lld is a gated unit: slideo_match_changed_frames_collect collects it", (long long)ticket);
-    unit_collect(m, *S, verdicts_out);
+    Slot& S = slot_of_ticket(m, ticket, false);
+    unit_collect(m, S, verdicts_out);
     if (verdicts_dev_out) {           // (after the collect: a unit re-run through the exact-size path has rewritten d_verdicts)
-        HIP_CHECK(hipMemcpyAsync(verdicts_dev_out, S->d_verdicts.p, (size_t)S->n * sizeof(slideo_verdict), hipMemcpyDeviceToDevice, S->st));
-        HIP_CHECK(hipStreamSynchronize(S->st));
+        HIP_CHECK(hipMemcpyAsync(verdicts_dev_out, S.d_verdicts.p, (size_t)S.n * sizeof(slideo_verdict), hipMemcpyDeviceToDevice, S.st));
+        HIP_CHECK(hipStreamSynchronize(S.st));
     }
     API_CATCH(m)
 }
@@ -1058,7 +1071,7 @@ int32_t slideo_match_frames_submit_yuv420_dev(slideo_matcher* m, int32_t n_frame
                                               int64_t* ticket_out) {
     if (!m) return SLIDEO_ERR_INVALID_ARG;
     API_TRY
-    submit_impl(m, n_frames, FrameSrc::yuv420(frames_dev, true, width, height, layout, frame_stride_bytes), hip_stream, ticket_out);
+    submit_impl(m, n_frames, FrameSrc::yuv420(frames_dev, true, width, height, layout, frame_stride_bytes), hip_stream, ticket_out, false);
     API_CATCH(m)
 }
 
@@ -1069,6 +1082,73 @@ int32_t slideo_changed_mask_yuv420(slideo_matcher* m, int32_t n_frames, const ui
     API_TRY
     changed_mask_impl(m, n_frames, FrameSrc::yuv420(frames, false, width, height, layout, frame_stride_bytes), prev_small, last_small_out,
                       changed_out, similarity_out);
+    API_CATCH(m)
+}
+
+// ---- the gated frame calls (include/slideo_amd.h "Changed-frame gate"; the gate itself: stage_gate.hip) ----------------------------
+
+int32_t slideo_match_changed_frames_bgr8(slideo_matcher* m, int32_t n_frames, const uint8_t* frames, int32_t width, int32_t height, int32_t stride_bytes,
+                                         int64_t frame_stride_bytes, uint8_t* changed_out, float* similarity_out, slideo_verdict* verdicts_out) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    match_frames_impl(m, n_frames, FrameSrc::bgr8(frames, false, width, height, stride_bytes, frame_stride_bytes), verdicts_out, nullptr, true,
+                      changed_out, similarity_out);
+    API_CATCH(m)
+}
+
+int32_t slideo_match_changed_frames_yuv420(slideo_matcher* m, int32_t n_frames, const uint8_t* frames, int32_t width, int32_t height,
+                                           const slideo_yuv420_layout* layout, int64_t frame_stride_bytes, uint8_t* changed_out, float* similarity_out,
+                                           slideo_verdict* verdicts_out) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    match_frames_impl(m, n_frames, FrameSrc::yuv420(frames, false, width, height, layout, frame_stride_bytes), verdicts_out, nullptr, true,
+                      changed_out, similarity_out);
+    API_CATCH(m)
+}
+
+int32_t slideo_match_changed_frames_bgr8_dev(slideo_matcher* m, int32_t n_frames, const uint8_t* frames_dev, int32_t width, int32_t height,
+                                             int32_t stride_bytes, int64_t frame_stride_bytes, uint8_t* changed_out, float* similarity_out,
+                                             slideo_verdict* verdicts_out, void* hip_stream) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    match_frames_impl(m, n_frames, FrameSrc::bgr8(frames_dev, true, width, height, stride_bytes, frame_stride_bytes), verdicts_out,
+                      reinterpret_cast<hipStream_t>(hip_stream), true, changed_out, similarity_out);
+    API_CATCH(m)
+}
+
+int32_t slideo_match_changed_frames_yuv420_dev(slideo_matcher* m, int32_t n_frames, const uint8_t* frames_dev, int32_t width, int32_t height,
+                                               const slideo_yuv420_layout* layout, int64_t frame_stride_bytes, uint8_t* changed_out,
+                                               float* similarity_out, slideo_verdict* verdicts_out, void* hip_stream) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    match_frames_impl(m, n_frames, FrameSrc::yuv420(frames_dev, true, width, height, layout, frame_stride_bytes), verdicts_out,
+                      reinterpret_cast<hipStream_t>(hip_stream), true, changed_out, similarity_out);
+    API_CATCH(m)
+}
+
+int32_t slideo_match_changed_frames_submit_dev(slideo_matcher* m, int32_t n_frames, const uint8_t* frames_dev, int32_t width, int32_t height,
+                                               int32_t stride_bytes, int64_t frame_stride_bytes, void* hip_stream, int64_t* ticket_out) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    submit_impl(m, n_frames, FrameSrc::bgr8(frames_dev, true, width, height, stride_bytes, frame_stride_bytes), hip_stream, ticket_out, true);
+    API_CATCH(m)
+}
+
+int32_t slideo_match_changed_frames_submit_yuv420_dev(slideo_matcher* m, int32_t n_frames, const uint8_t* frames_dev, int32_t width, int32_t height,
+                                                      const slideo_yuv420_layout* layout, int64_t frame_stride_bytes, void* hip_stream,
+                                                      int64_t* ticket_out) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    submit_impl(m, n_frames, FrameSrc::yuv420(frames_dev, true, width, height, layout, frame_stride_bytes), hip_stream, ticket_out, true);
+    API_CATCH(m)
+}
+
+int32_t slideo_match_changed_frames_collect(slideo_matcher* m, int64_t ticket, uint8_t* changed_out, float* similarity_out, slideo_verdict* verdicts_out) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    if (!changed_out || !verdicts_out) fail(SLIDEO_ERR_INVALID_ARG, "null changed_out/verdicts_out");
+    HIP_CHECK(hipSetDevice(m->device));
+    gate_unit_collect(m, slot_of_ticket(m, ticket, true), changed_out, similarity_out, verdicts_out);
     API_CATCH(m)
 }
 

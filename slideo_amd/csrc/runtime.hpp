@@ -1,12 +1,13 @@
 // runtime.hpp — the host runtime behind include/slideo_amd.h, shared by its translation units.
 //
-//   capi_runtime.hip   handles, page database, slots, frame staging (FrameSrc -> DevFrames), unit submit / collect, the match entry points
+//   capi_runtime.hip   handles, page database, slots, frame staging (FrameSrc -> DevFrames), unit submit / collect, the drivers of the
+//                      frame calls (pipeline, submit, collect: plain and gated) and their entry points
 //   stage_orb.hip      ORB stage drivers          (kernels: orb.hip.h, yuv420.hip.h, reduce.hip.h)
 //   stage_knn.hip      index build + k-NN stage   (kernels: knn.hip.h, knn_tile.hip.h, knn_l2.hip.h, knn_lsh.hip.h)
 //   stage_verify.hip   vote .. verdict, small img (kernels: verify.hip.h, homography.hip.h)
 //   stage_sift.hip     SIFT stage + entry points  (kernels: sift.hip.h)
 //   stage_page_set.hip page sets: a subset's search operand built from the finalized deck (kernels: page_set.hip.h)
-//   stage_gate.hip     changed-frame gate: gated units, their entry points, the gate state (kernels: gate.hip.h)
+//   stage_gate.hip     changed-frame gate: gated units, the gate state and its entry points (kernels: gate.hip.h)
 //   capi_taps.hip      debug taps of the parity tests
 //   capi_group.hip     the N-device group (slideo_group_*)
 //
@@ -354,7 +355,9 @@ DevFrames stage_frames(slideo_matcher* m, Slot& S, const FrameSrc& src, int firs
 void upload_rng_stream(slideo_matcher* m, uint32_t len);
 void unit_submit(slideo_matcher* m, Slot& S, const DevFrames& f, int n, bool allow_async = true);
 void unit_collect(slideo_matcher* m, Slot& S, slideo_verdict* out_host);
-void match_frames_impl(slideo_matcher* m, int n, FrameSrc src, slideo_verdict* out, hipStream_t user_stream);
+// a synchronous frame call through the unit pipeline; gated: through the gate (changed_out, similarity_out as the gated entry points')
+void match_frames_impl(slideo_matcher* m, int n, FrameSrc src, slideo_verdict* out, hipStream_t user_stream, bool gated = false,
+                       uint8_t* changed_out = nullptr, float* similarity_out = nullptr);
 // slideo_changed_mask_bgr8 / _yuv420: the frames stay in slot 0's d_stage, which m->kept then describes
 void changed_mask_impl(slideo_matcher* m, int n, FrameSrc src, const uint8_t* prev_small, uint8_t* last_small_out, uint8_t* changed_out,
                        float* similarity_out);
@@ -433,6 +436,14 @@ void page_set_check_mode(const slideo_matcher* m);
 // ---- stage_gate.hip -------------------------------------------------------------------------------
 void gate_release(slideo_matcher* m);          // the gate's events (slideo_matcher_destroy)
 inline void gate_state_reset(slideo_matcher* m) { m->gate = slideo_matcher::GateState{}; }
+// FrameSrc::staging_bytes' gate_small of a gated call (a small image has at most small_area pixels)
+inline size_t gate_small_budget(const slideo_matcher* m) { return (size_t)m->cfg.small_area * 3 + 64; }
+// a validated source's frames against the gate state: one size and one format family since the last reset (SLIDEO_ERR_STATE)
+void gate_check(const slideo_matcher* m, const FrameSrc& src);
+// One gated unit on slot S: frames [first, first + n) of src through the gate, the changed ones through unit_submit (S.n = their
+// count, 0: no pipeline ran); its collect: flags and similarities of all n frames, verdicts of the changed ones
+void gate_unit_submit(slideo_matcher* m, Slot& S, const FrameSrc& src, int first, int n, hipStream_t cs);
+void gate_unit_collect(slideo_matcher* m, Slot& S, uint8_t* changed_out, float* similarity_out, slideo_verdict* verdicts_out);
 
 // ---- stage_sift.hip -------------------------------------------------------------------------------
 void sift_check_cfg(const slideo_sift_config* sc, int w, int h);

@@ -1,5 +1,6 @@
 // stage_gate.hip — the changed-frame gate of include/slideo_amd.h "Changed-frame gate": gated units (small images of all frames, SSDs,
-// gate_kernel, gather_frames_kernel in front of the unchanged unit_submit), the gate state and the entry points (kernels: gate.hip.h).
+// gate_kernel, gather_frames_kernel in front of the unchanged unit_submit), the gate state and its entry points (kernels: gate.hip.h).
+// The frame calls that run gated units are capi_runtime.hip's, beside their plain twins.
 #include "runtime.hpp"
 #include "gate.hip.h"
 
@@ -15,8 +16,6 @@ void gate_release(slideo_matcher* m) {
 
 namespace {
 
-size_t gate_small_budget(const slideo_matcher* m) { return (size_t)m->cfg.small_area * 3 + 64; }      // (a small image has at most small_area pixels)
-
 int64_t ssd_threshold(float changed_similarity_, int sw, int sh) {
     const int64_t max_ssd = (int64_t)255 * 255 * 3 * sw * sh;
     auto changed = [&](int64_t s) { return changed_similarity((unsigned long long)s, sw, sh) < changed_similarity_; };
@@ -29,6 +28,8 @@ int64_t ssd_threshold(float changed_similarity_, int sw, int sh) {
     }
     return hi;
 }
+
+}  // namespace
 
 // The frames of a gated call against the gate state: one size and one format family since the last reset.  Nothing is changed here.
 void gate_check(const slideo_matcher* m, const FrameSrc& src) {
@@ -127,88 +128,6 @@ void gate_unit_collect(slideo_matcher* m, Slot& S, uint8_t* changed_out, float* 
     }
 }
 
-void gate_validate(slideo_matcher* m, int n, FrameSrc& src, const uint8_t* changed_out, const slideo_verdict* verdicts_out) {
-    if (n > 0 && !changed_out) fail(SLIDEO_ERR_INVALID_ARG, "null changed_out");
-    validate_frames(src, m, n, verdicts_out);
-    gate_check(m, src);
-}
-
-// slideo_match_changed_frames_*: the call cut into units and pipelined through the slots, as match_frames_impl does
-void match_changed_impl(slideo_matcher* m, int n, FrameSrc src, uint8_t* changed_out, float* similarity_out, slideo_verdict* out, hipStream_t user_stream) {
-    gate_validate(m, n, src, changed_out, out);
-    HIP_CHECK(hipSetDevice(m->device));
-    require_idle(m);
-    m->last_fcs.clear();
-    if (n == 0) return;
-    GeomEntry& ge = geom_for(m, src.unit_w(), src.unit_h());
-    area_class_for(m, src.unit_w(), src.unit_h());
-    upload_area(m);
-    int unit = sub_batch_for(m, ge.g, n, src.staging_bytes(gate_small_budget(m)));
-    if (n >= 128 && unit >= (n + 1) / 2) unit = (n + 1) / 2;
-    if (!src.on_device && m->host_unit > 0 && n >= 2 * m->host_unit) unit = std::min(unit, m->host_unit);      // unit u + 1 uploads and gates while unit u matches
-    struct Pending { Slot* S; int ofs; };
-    std::vector<Pending> pend;
-    if (src.on_device && user_stream)
-        for (Slot& S : m->slots) {
-            HIP_CHECK(hipEventRecord(S.ev_in, user_stream));
-            HIP_CHECK(hipStreamWaitEvent(S.st, S.ev_in, 0));
-        }
-    int done = 0;
-    hipStream_t cs = src.pinned ? m->copy_st : nullptr;
-    m->units_pending = n > unit;
-    auto collect = [&](const Pending& p) {
-        gate_unit_collect(m, *p.S, changed_out + p.ofs, similarity_out ? similarity_out + p.ofs : nullptr, out + p.ofs);
-        done += p.S->gate.n;
-        if (m->progress) m->progress(m->progress_user, (uint64_t)done, (uint64_t)n, "Processing frames...");
-    };
-    try {
-        for (int i = 0; i < n; i += unit) {
-            const int cnt = std::min(unit, n - i);
-            if ((int)pend.size() == NSLOTS) { collect(pend[0]); pend.erase(pend.begin()); }
-            Slot& S = m->slots[m->next_slot];
-            m->next_slot = (m->next_slot + 1) % NSLOTS;
-            gate_unit_submit(m, S, src, i, cnt, cs);
-            pend.push_back({&S, i});
-        }
-        for (Pending& p : pend) collect(p);
-        m->units_pending = false;
-    } catch (...) {
-        m->units_pending = false;
-        (void)hipStreamSynchronize(m->copy_st);
-        for (Slot& S : m->slots) { (void)hipStreamSynchronize(S.st); S.busy = false; S.gate.on = false; }
-        throw;
-    }
-}
-
-// slideo_match_changed_frames_submit[_yuv420]_dev
-void submit_changed_impl(slideo_matcher* m, int32_t n, FrameSrc src, void* hip_stream, int64_t* ticket_out) {
-    if (!ticket_out) fail(SLIDEO_ERR_INVALID_ARG, "null ticket_out");
-    validate_frames(src, m, n, ticket_out);
-    if (n < 1) fail(SLIDEO_ERR_INVALID_ARG, "submit needs at least one frame");
-    gate_check(m, src);
-    HIP_CHECK(hipSetDevice(m->device));
-    Slot& S = m->slots[m->next_slot];
-    if (S.busy) fail(SLIDEO_ERR_STATE, "all slots are in flight: collect ticket %lld first", (long long)S.ticket);
-    GeomEntry& ge = geom_for(m, src.unit_w(), src.unit_h());
-    const int fit = sub_batch_for(m, ge.g, n, src.staging_bytes(gate_small_budget(m)));
-    if (n > fit)
-        fail(SLIDEO_ERR_CAPACITY, "%d frames exceed the per-slot workspace budget (%d); submit smaller units or raise SLIDEO_WS_GB", n, fit);
-    area_class_for(m, src.unit_w(), src.unit_h());
-    upload_area(m);
-    { bool any = false; for (const Slot& c : m->slots) any |= c.busy; if (!any) m->last_fcs.clear(); }
-    if (hip_stream) {
-        HIP_CHECK(hipEventRecord(S.ev_in, reinterpret_cast<hipStream_t>(hip_stream)));
-        HIP_CHECK(hipStreamWaitEvent(S.st, S.ev_in, 0));
-    }
-    gate_unit_submit(m, S, src, 0, n, nullptr);
-    S.ticket = m->next_ticket++;
-    *ticket_out = S.ticket;
-    m->next_slot = (m->next_slot + 1) % NSLOTS;
-    if (S.gate.k > 0)
-        for (Slot& O : m->slots) if (&O != &S && !O.busy) O.match_capacity(S);
-}
-
-}  // namespace
 }  // namespace slideo
 
 extern "C" {
@@ -250,76 +169,6 @@ int32_t slideo_matcher_gate_last_small(slideo_matcher* m, uint8_t* out, int64_t 
         HIP_CHECK(hipMemcpyAsync(out, m->d_gate_small.p, (size_t)sb, hipMemcpyDeviceToHost, m->stream));
         HIP_CHECK(hipStreamSynchronize(m->stream));
     }
-    API_CATCH(m)
-}
-
-int32_t slideo_match_changed_frames_bgr8(slideo_matcher* m, int32_t n_frames, const uint8_t* frames, int32_t width, int32_t height, int32_t stride_bytes,
-                                         int64_t frame_stride_bytes, uint8_t* changed_out, float* similarity_out, slideo_verdict* verdicts_out) {
-    if (!m) return SLIDEO_ERR_INVALID_ARG;
-    API_TRY
-    match_changed_impl(m, n_frames, FrameSrc::bgr8(frames, false, width, height, stride_bytes, frame_stride_bytes), changed_out, similarity_out,
-                       verdicts_out, nullptr);
-    API_CATCH(m)
-}
-
-int32_t slideo_match_changed_frames_yuv420(slideo_matcher* m, int32_t n_frames, const uint8_t* frames, int32_t width, int32_t height,
-                                           const slideo_yuv420_layout* layout, int64_t frame_stride_bytes, uint8_t* changed_out, float* similarity_out,
-                                           slideo_verdict* verdicts_out) {
-    if (!m) return SLIDEO_ERR_INVALID_ARG;
-    API_TRY
-    match_changed_impl(m, n_frames, FrameSrc::yuv420(frames, false, width, height, layout, frame_stride_bytes), changed_out, similarity_out,
-                       verdicts_out, nullptr);
-    API_CATCH(m)
-}
-
-int32_t slideo_match_changed_frames_bgr8_dev(slideo_matcher* m, int32_t n_frames, const uint8_t* frames_dev, int32_t width, int32_t height,
-                                             int32_t stride_bytes, int64_t frame_stride_bytes, uint8_t* changed_out, float* similarity_out,
-                                             slideo_verdict* verdicts_out, void* hip_stream) {
-    if (!m) return SLIDEO_ERR_INVALID_ARG;
-    API_TRY
-    match_changed_impl(m, n_frames, FrameSrc::bgr8(frames_dev, true, width, height, stride_bytes, frame_stride_bytes), changed_out, similarity_out,
-                       verdicts_out, reinterpret_cast<hipStream_t>(hip_stream));
-    API_CATCH(m)
-}
-
-int32_t slideo_match_changed_frames_yuv420_dev(slideo_matcher* m, int32_t n_frames, const uint8_t* frames_dev, int32_t width, int32_t height,
-                                               const slideo_yuv420_layout* layout, int64_t frame_stride_bytes, uint8_t* changed_out,
-                                               float* similarity_out, slideo_verdict* verdicts_out, void* hip_stream) {
-    if (!m) return SLIDEO_ERR_INVALID_ARG;
-    API_TRY
-    match_changed_impl(m, n_frames, FrameSrc::yuv420(frames_dev, true, width, height, layout, frame_stride_bytes), changed_out, similarity_out,
-                       verdicts_out, reinterpret_cast<hipStream_t>(hip_stream));
-    API_CATCH(m)
-}
-
-int32_t slideo_match_changed_frames_submit_dev(slideo_matcher* m, int32_t n_frames, const uint8_t* frames_dev, int32_t width, int32_t height,
-                                               int32_t stride_bytes, int64_t frame_stride_bytes, void* hip_stream, int64_t* ticket_out) {
-    if (!m) return SLIDEO_ERR_INVALID_ARG;
-    API_TRY
-    submit_changed_impl(m, n_frames, FrameSrc::bgr8(frames_dev, true, width, height, stride_bytes, frame_stride_bytes), hip_stream, ticket_out);
-    API_CATCH(m)
-}
-
-int32_t slideo_match_changed_frames_submit_yuv420_dev(slideo_matcher* m, int32_t n_frames, const uint8_t* frames_dev, int32_t width, int32_t height,
-                                                      const slideo_yuv420_layout* layout, int64_t frame_stride_bytes, void* hip_stream,
-                                                      int64_t* ticket_out) {
-    if (!m) return SLIDEO_ERR_INVALID_ARG;
-    API_TRY
-    submit_changed_impl(m, n_frames, FrameSrc::yuv420(frames_dev, true, width, height, layout, frame_stride_bytes), hip_stream, ticket_out);
-    API_CATCH(m)
-}
-
-int32_t slideo_match_changed_frames_collect(slideo_matcher* m, int64_t ticket, uint8_t* changed_out, float* similarity_out, slideo_verdict* verdicts_out) {
-    if (!m) return SLIDEO_ERR_INVALID_ARG;
-    API_TRY
-    if (!changed_out || !verdicts_out) fail(SLIDEO_ERR_INVALID_ARG, "null changed_out/verdicts_out");
-    HIP_CHECK(hipSetDevice(m->device));
-    Slot* S = nullptr;
-    for (Slot& c : m->slots) if (c.busy && c.ticket == ticket) S = &c;
-    if (!S) fail(SLIDEO_ERR_STATE, "ticket %lld is not in flight", (long long)ticket);
-    for (Slot& c : m->slots) if (c.busy && c.ticket < ticket) fail(SLIDEO_ERR_STATE, "collect ticket %lld first (in order)", (long long)c.ticket);
-    if (!S->gate.on) fail(SLIDEO_ERR_STATE, "ticket %lld is not a gated unit: slideo_match_frames_collect collects it", (long long)ticket);
-    gate_unit_collect(m, *S, changed_out, similarity_out, verdicts_out);
     API_CATCH(m)
 }
 
