@@ -249,8 +249,8 @@ extern "C" {
         bgr_out: *mut u8,
         out_capacity: i64,
     ) -> i32;
-    // ---- changed-frame gate: MarkSimilarIter inside the unit pipeline (slideo_amd.h "Changed-frame gate").  A group has no gated
-    // form; a one-device group gates through its member.
+    // ---- changed-frame gate: MarkSimilarIter inside the unit pipeline (slideo_amd.h "Changed-frame gate").  A group of any member
+    // count carries one gate state (slideo_group_gate_*, slideo_group_match_changed_frames_*): results equal a single matcher's.
     pub fn slideo_group_member(g: *mut slideo_group, i: i32) -> *mut slideo_matcher;
     pub fn slideo_changed_ssd_threshold(changed_similarity: f32, small_w: i32, small_h: i32) -> i64;
     pub fn slideo_matcher_gate_reset(m: *mut slideo_matcher, prev_small: *const u8, small_w: i32, small_h: i32) -> i32;
@@ -336,6 +336,68 @@ extern "C" {
     pub fn slideo_match_changed_frames_collect(
         m: *mut slideo_matcher,
         ticket: i64,
+        changed_out: *mut u8,
+        similarity_out: *mut f32,
+        verdicts_out: *mut slideo_verdict,
+    ) -> i32;
+    pub fn slideo_matcher_gate_reset_from_frame_bgr8(
+        m: *mut slideo_matcher,
+        frame: *const u8,
+        width: i32,
+        height: i32,
+        stride_bytes: i32,
+    ) -> i32;
+    pub fn slideo_matcher_gate_reset_from_frame_yuv420(
+        m: *mut slideo_matcher,
+        frame: *const u8,
+        width: i32,
+        height: i32,
+        layout: *const slideo_yuv420_layout,
+    ) -> i32;
+    pub fn slideo_matcher_gate_reset_from_frame_bgr8_dev(
+        m: *mut slideo_matcher,
+        frame_dev: *const u8,
+        width: i32,
+        height: i32,
+        stride_bytes: i32,
+        hip_stream: *mut c_void,
+    ) -> i32;
+    pub fn slideo_matcher_gate_reset_from_frame_yuv420_dev(
+        m: *mut slideo_matcher,
+        frame_dev: *const u8,
+        width: i32,
+        height: i32,
+        layout: *const slideo_yuv420_layout,
+        hip_stream: *mut c_void,
+    ) -> i32;
+    pub fn slideo_group_gate_reset(g: *mut slideo_group, prev_small: *const u8, small_w: i32, small_h: i32) -> i32;
+    pub fn slideo_group_gate_last_small(
+        g: *mut slideo_group,
+        out: *mut u8,
+        out_capacity: i64,
+        sw: *mut i32,
+        sh: *mut i32,
+    ) -> i32;
+    pub fn slideo_group_match_changed_frames_bgr8(
+        g: *mut slideo_group,
+        n_frames: i32,
+        frames: *const u8,
+        width: i32,
+        height: i32,
+        stride_bytes: i32,
+        frame_stride_bytes: i64,
+        changed_out: *mut u8,
+        similarity_out: *mut f32,
+        verdicts_out: *mut slideo_verdict,
+    ) -> i32;
+    pub fn slideo_group_match_changed_frames_yuv420(
+        g: *mut slideo_group,
+        n_frames: i32,
+        frames: *const u8,
+        width: i32,
+        height: i32,
+        layout: *const slideo_yuv420_layout,
+        frame_stride_bytes: i64,
         changed_out: *mut u8,
         similarity_out: *mut f32,
         verdicts_out: *mut slideo_verdict,

@@ -7,6 +7,8 @@
 //!                                                  finalize_pages: pages analysed across the devices, DB replicated
 //!   match_images_with_video (mo/lib.rs:140-158) -> opens the video to size the progress bar, as the reference does
 //!   process                 (mo/lib.rs:168-246) -> sampled frames in batches, each batch sharded over the devices:
+//!                                                  slideo_group_match_changed_frames_bgr8 (MarkSimilarIter and the
+//!                                                  match of the changed frames in one gated call); without the gate:
 //!                                                  slideo_group_changed_mask_bgr8 (MarkSimilarIter,
 //!                                                  mo/video_capture.rs:86-98), then slideo_group_match_kept_frames on
 //!                                                  the changed ones (the mask's upload, on the device that holds it)
@@ -32,6 +34,9 @@ use std::{
 /// (or the previous small image carried over, which is what happens at batch seams); 64 x 1080p = 400 MB of host memory
 /// per device of the group.
 const FRAMES_PER_CALL_PER_DEVICE: usize = 64;
+/// The changed-frame gate inside the unit pipeline (slideo_group_match_changed_frames_bgr8); false: the stop-and-go pair
+/// slideo_group_changed_mask_bgr8 + slideo_group_match_kept_frames, for comparisons.
+const CHANGED_GATE: bool = true;
 
 struct RawHandle(*mut ffi::slideo_group);
 // The pointer itself may move between threads; USE is serialised by the Mutex below — include/slideo_amd.h: "a matcher
@@ -200,14 +205,13 @@ impl<I: MatchableImage + Send + Sync + Copy + Eq> VideoMatcherTask<I> for HipVid
         let h = guard.0;
         let mut progress = 0u64;
         let mut prev_small: Option<Vec<u8>> = None;
-        // The changed-frame gate (slideo_amd.h "Changed-frame gate"): a one-device group gates through its member: one call per
-        // batch decides on the device which frames changed and matches those, and the last small image stays in the matcher.  A
-        // group of several devices has no gated form (a shard needs the frame before its block) and keeps the mask + kept pair.
-        let gate: *mut ffi::slideo_matcher =
-            if self.n_devices == 1 { unsafe { ffi::slideo_group_member(h, 0) } } else { std::ptr::null_mut() };
-        if !gate.is_null() {
+        // The changed-frame gate (slideo_amd.h "Changed-frame gate"): the group's gated call, for any member count: one call per
+        // batch decides on the devices which frames changed and matches those, every shard after the first primed from the frame
+        // before its block; the last small image stays in the group.  CHANGED_GATE false: the stop-and-go mask + kept pair below.
+        let gate = CHANGED_GATE;
+        if gate {
             // the first frame of the video is always changed
-            unsafe { check(h, ffi::slideo_matcher_gate_reset(gate, std::ptr::null(), 0, 0)) };
+            unsafe { check(h, ffi::slideo_group_gate_reset(h, std::ptr::null(), 0, 0)) };
         }
         // one call = one shard of FRAMES_PER_CALL_PER_DEVICE sampled frames per device (mo/lib.rs:213: one task per frame over the pool)
         for batch in decode::batches(vid, FRAMES_PER_CALL_PER_DEVICE * self.n_devices) {
@@ -217,13 +221,13 @@ impl<I: MatchableImage + Send + Sync + Copy + Eq> VideoMatcherTask<I> for HipVid
             // first frame of the video is always changed (prev_small == None); the last small image of this call is the
             // `prev` of the next one.
             let mut changed = vec![0u8; n];
-            if !gate.is_null() {
+            if gate {
                 let mut all = vec![ffi::slideo_verdict::default(); n];
                 unsafe {
                     check(
                         h,
-                        ffi::slideo_match_changed_frames_bgr8(
-                            gate,
+                        ffi::slideo_group_match_changed_frames_bgr8(
+                            h,
                             n as i32,
                             batch.frames.as_ptr(),
                             batch.width,

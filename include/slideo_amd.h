@@ -728,8 +728,23 @@ int32_t     slideo_reduce_bgr8(slideo_matcher* m, const uint8_t* bgr, int32_t wi
  * kept list, count); gather_frames_kernel packs the kept frames; the kept count reaches the host in ONE short wait inside the
  * submit, and the unchanged pipeline runs for the kept frames only.  A unit without a changed frame runs no pipeline.
  * A size, format or argument error leaves the gate state untouched.  slideo_matcher_set_working_size resets it.
- * The N-device group has no gated form: a group shards contiguous blocks of a call, and a shard's first frame needs the frame
- * before its block (the one-frame halo of slideo_group_changed_mask_bgr8); gate per member, or use the group's mask call. */
+ *
+ * The N-device group's form.  A group carries ONE gate state: "none", or a small image.  For any sequence of slideo_group_gate_reset
+ * and slideo_group_match_changed_frames_* calls, changed_out, similarity_out, verdicts_out, the small image
+ * slideo_group_gate_last_small returns and the trace slideo_group_last_frame_candidates(g, k, ...) returns after a gated group call
+ * (k: the k-th CHANGED frame of that call, rule 3) equal, bit for bit, what a single slideo_matcher of the same config, pages and
+ * options returns for the same sequence of slideo_matcher_gate_reset and slideo_match_changed_frames_* calls — for every member
+ * count, more members than frames included, and wherever the shard boundaries fall.  Rules 1 - 6 hold unchanged; the call's
+ * arguments are checked once, before any member is touched, so a size, format or argument error leaves the state untouched.
+ * How: the call is cut into the group's contiguous shards; member 0 continues the group's state, and every later non-empty shard
+ * [lo, hi) first sets its member's state from frame lo - 1 (slideo_matcher_gate_reset_from_frame_*: the one-frame halo of
+ * slideo_group_changed_mask_bgr8 as a gate state, one extra frame upload per member and call), then runs the gated call over its
+ * block.  After the call the state is the last non-empty shard's member's; the next call moves it to member 0 through a host copy of
+ * at most 3 * small_area bytes.  Page sets, the working size, verify_model 1, ratio_test and SIFT mode are the members' own, set
+ * through the group's calls; slideo_group_set_working_size resets the state.  n_frames == 0 is a no-op.  Progress counts the n
+ * frames of the call (a halo frame is not counted).  If a member fails in the middle of a call the group's state becomes "none", and
+ * the message says so.  Calling a member's own gated entry points (through slideo_group_member) between gated group calls is
+ * undefined.  Shards are contiguous: a run of changed frames loads one member (no re-deal of the kept frames). */
 /* The smallest SSD of two small_w x small_h small images that counts as changed under changed_similarity: found by bisection over
  * the mask call's host expression itself.  INT64_MAX: no SSD (0 .. 255^2 * 3 * small_w * small_h) does.  A pure host function (no
  * device).  -1 for a non-positive size. */
@@ -740,6 +755,19 @@ int64_t     slideo_changed_ssd_threshold(float changed_similarity, int32_t small
 int32_t     slideo_matcher_gate_reset(slideo_matcher* m, const uint8_t* prev_small, int32_t small_w, int32_t small_h);
 /* Idle matcher.  The gate state's small image; *sw, *sh its size (out may be NULL).  SLIDEO_ERR_STATE when the state is "none". */
 int32_t     slideo_matcher_gate_last_small(slideo_matcher* m, uint8_t* out, int64_t out_capacity, int32_t* sw, int32_t* sh);
+/* Idle matcher.  The gate state from a FRAME: afterwards the state is exactly what slideo_matcher_gate_reset(m, S, sw, sh) leaves,
+ * S being the last_small_out of a one-frame slideo_changed_mask_* call on that frame under the matcher's working size
+ * (slideo_matcher_gate_last_small returns S bit for bit; the next gated frame is compared against S).  The frame is staged as a gated
+ * unit stages its frames (upload, 4:2:0 conversion, reduce; plain device BGR is read in place).  Argument, size and layout errors
+ * are those of a gated call and leave the state untouched.  hip_stream: the stream the device frame was produced on (may be NULL). */
+int32_t     slideo_matcher_gate_reset_from_frame_bgr8(slideo_matcher* m, const uint8_t* frame, int32_t width, int32_t height,
+                                                      int32_t stride_bytes);
+int32_t     slideo_matcher_gate_reset_from_frame_yuv420(slideo_matcher* m, const uint8_t* frame, int32_t width, int32_t height,
+                                                        const slideo_yuv420_layout* layout);
+int32_t     slideo_matcher_gate_reset_from_frame_bgr8_dev(slideo_matcher* m, const uint8_t* frame_dev, int32_t width, int32_t height,
+                                                          int32_t stride_bytes, void* hip_stream);
+int32_t     slideo_matcher_gate_reset_from_frame_yuv420_dev(slideo_matcher* m, const uint8_t* frame_dev, int32_t width, int32_t height,
+                                                            const slideo_yuv420_layout* layout, void* hip_stream);
 /* The synchronous forms (idle matcher): the call is cut into units and pipelined through the slots as slideo_match_frames_* is;
  * host frames in short units through the ordered copy stream, so that unit u + 1 uploads and gates while unit u matches.
  * changed_out [n] and verdicts_out [n] are required, similarity_out [n] may be NULL. */
@@ -765,6 +793,16 @@ int32_t     slideo_match_changed_frames_submit_yuv420_dev(slideo_matcher* m, int
                                                           void* hip_stream, int64_t* ticket_out);
 int32_t     slideo_match_changed_frames_collect(slideo_matcher* m, int64_t ticket, uint8_t* changed_out, float* similarity_out,
                                                 slideo_verdict* verdicts_out);
+/* The group's gated calls ("The N-device group's form" above): host frames, every member idle.  slideo_group_gate_reset and
+ * slideo_group_gate_last_small are slideo_matcher_gate_reset / _gate_last_small on the group's one state. */
+int32_t     slideo_group_gate_reset(slideo_group* g, const uint8_t* prev_small, int32_t small_w, int32_t small_h);
+int32_t     slideo_group_gate_last_small(slideo_group* g, uint8_t* out, int64_t out_capacity, int32_t* sw, int32_t* sh);
+int32_t     slideo_group_match_changed_frames_bgr8(slideo_group* g, int32_t n_frames, const uint8_t* frames, int32_t width, int32_t height,
+                                                   int32_t stride_bytes, int64_t frame_stride_bytes, uint8_t* changed_out,
+                                                   float* similarity_out, slideo_verdict* verdicts_out);
+int32_t     slideo_group_match_changed_frames_yuv420(slideo_group* g, int32_t n_frames, const uint8_t* frames, int32_t width, int32_t height,
+                                                     const slideo_yuv420_layout* layout, int64_t frame_stride_bytes, uint8_t* changed_out,
+                                                     float* similarity_out, slideo_verdict* verdicts_out);
 
 #ifdef __cplusplus
 }

@@ -136,6 +136,9 @@ EXPORTS = [
     "slideo_match_changed_frames_bgr8", "slideo_match_changed_frames_yuv420", "slideo_match_changed_frames_bgr8_dev",
     "slideo_match_changed_frames_yuv420_dev", "slideo_match_changed_frames_submit_dev", "slideo_match_changed_frames_submit_yuv420_dev",
     "slideo_match_changed_frames_collect",
+    "slideo_matcher_gate_reset_from_frame_bgr8", "slideo_matcher_gate_reset_from_frame_yuv420", "slideo_matcher_gate_reset_from_frame_bgr8_dev",
+    "slideo_matcher_gate_reset_from_frame_yuv420_dev", "slideo_group_gate_reset", "slideo_group_gate_last_small",
+    "slideo_group_match_changed_frames_bgr8", "slideo_group_match_changed_frames_yuv420",
 ]
 
 _lib = None
@@ -182,6 +185,16 @@ def lib():
         if hasattr(L, "slideo_changed_ssd_threshold"):             # (SLIDEO_LIB_PATH may name an older build: tools/ab_libs.sh)
             L.slideo_changed_ssd_threshold.restype = C.c_int64
             L.slideo_changed_ssd_threshold.argtypes = [C.c_float, C.c_int32, C.c_int32]
+        if hasattr(L, "slideo_group_match_changed_frames_bgr8"):
+            vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
+            L.slideo_matcher_gate_reset_from_frame_bgr8.argtypes = [vp, vp, i32, i32, i32]
+            L.slideo_matcher_gate_reset_from_frame_yuv420.argtypes = [vp, vp, i32, i32, vp]
+            L.slideo_matcher_gate_reset_from_frame_bgr8_dev.argtypes = [vp, vp, i32, i32, i32, vp]
+            L.slideo_matcher_gate_reset_from_frame_yuv420_dev.argtypes = [vp, vp, i32, i32, vp, vp]
+            L.slideo_group_gate_reset.argtypes = [vp, vp, i32, i32]
+            L.slideo_group_gate_last_small.argtypes = [vp, vp, i64, vp, vp]
+            L.slideo_group_match_changed_frames_bgr8.argtypes = [vp, i32, vp, i32, i32, i32, i64, vp, vp, vp]
+            L.slideo_group_match_changed_frames_yuv420.argtypes = [vp, i32, vp, i32, i32, vp, i64, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -265,6 +278,47 @@ class _FrameCalls:
         out = np.zeros(len(sel), VERDICT_DTYPE)
         self._call("match_kept_frames", len(sel), _p(sel), _p(out))
         return out
+
+    # ---- changed-frame gate (include/slideo_amd.h "Changed-frame gate"): the host forms a Matcher and a Group share -------------
+    # Gated calls return (changed [n] bool, similarity [n] f32, verdicts [n]); an unchanged frame's verdict is (-1, 0, 0, 0).
+    # A Group carries ONE gate state and returns what a single Matcher returns for the same sequence of calls.
+    def gate_reset(self, prev_small=None):
+        """The gate state: the small image (sh, sw, 3) the next gated frame compares against, or None (that frame is changed)."""
+        if prev_small is None:
+            self._check(getattr(lib(), self._SETS + "gate_reset")(self._h, None, 0, 0))
+            return
+        prev_small = np.ascontiguousarray(prev_small, np.uint8)
+        if prev_small.ndim != 3 or prev_small.shape[2] != 3:
+            raise SlideoError(1, "gate_reset: expected an (sh, sw, 3) uint8 small image")
+        self._check(getattr(lib(), self._SETS + "gate_reset")(self._h, _p(prev_small), prev_small.shape[1], prev_small.shape[0]))
+
+    def gate_last_small(self):
+        """The small image of the last gated frame (SLIDEO_ERR_STATE when no frame was gated since a reset to None)."""
+        sw, sh = C.c_int32(), C.c_int32()
+        self._check(getattr(lib(), self._SETS + "gate_last_small")(self._h, None, C.c_int64(1 << 40), C.byref(sw), C.byref(sh)))
+        out = np.empty((sh.value, sw.value, 3), np.uint8)
+        self._check(getattr(lib(), self._SETS + "gate_last_small")(self._h, _p(out), C.c_int64(out.size), C.byref(sw), C.byref(sh)))
+        return out
+
+    @staticmethod
+    def _gated_out(n):
+        return np.zeros(n, np.uint8), np.zeros(n, np.float32), np.zeros(n, VERDICT_DTYPE)
+
+    def match_changed_frames(self, frames):
+        """frames: uint8 [n, h, w, 3] in host memory, continuing the gate."""
+        frames = np.ascontiguousarray(frames, np.uint8)
+        n, h, w, c = frames.shape
+        assert c == 3
+        ch, sim, out = self._gated_out(n)
+        self._call("match_changed_frames_bgr8", n, _p(frames), w, h, w * 3, C.c_int64(w * h * 3), _p(ch), _p(sim), _p(out))
+        return ch.astype(bool), sim, out
+
+    def match_changed_frames_yuv420(self, frames, w, h, layout="nv12"):
+        frames, layout, fs = _yuv_frames(frames, w, h, layout)
+        n = frames.shape[0]
+        ch, sim, out = self._gated_out(n)
+        self._call("match_changed_frames_yuv420", n, _p(frames), w, h, C.byref(layout), C.c_int64(fs), _p(ch), _p(sim), _p(out))
+        return ch.astype(bool), sim, out
 
     # working size (include/slideo_amd.h "Working size"): frames beyond it stand for their INTER_AREA reduction
     def set_working_size(self, max_w, max_h):
@@ -463,44 +517,23 @@ class Matcher(_FrameCalls):
 
     # ---- changed-frame gate (include/slideo_amd.h "Changed-frame gate") ------------------------
     # Gated calls return (changed [n] bool, similarity [n] f32, verdicts [n]); an unchanged frame's verdict is (-1, 0, 0, 0).
-    def gate_reset(self, prev_small=None):
-        """The gate state: the small image (sh, sw, 3) the next gated frame compares against, or None (that frame is changed)."""
-        if prev_small is None:
-            self._check(lib().slideo_matcher_gate_reset(self._h, None, 0, 0))
-            return
-        prev_small = np.ascontiguousarray(prev_small, np.uint8)
-        if prev_small.ndim != 3 or prev_small.shape[2] != 3:
-            raise SlideoError(1, "gate_reset: expected an (sh, sw, 3) uint8 small image")
-        self._check(lib().slideo_matcher_gate_reset(self._h, _p(prev_small), prev_small.shape[1], prev_small.shape[0]))
+    def gate_reset_from_frame(self, frame):
+        """The gate state from one host BGR frame [h, w, 3]: what gate_reset(changed_mask([frame])'s last small image) leaves."""
+        frame = _img3(frame)
+        h, w, _ = frame.shape
+        self._check(lib().slideo_matcher_gate_reset_from_frame_bgr8(self._h, _p(frame), w, h, w * 3))
 
-    def gate_last_small(self):
-        """The small image of the last gated frame (SLIDEO_ERR_STATE when no frame was gated since a reset to None)."""
-        sw, sh = C.c_int32(), C.c_int32()
-        self._check(lib().slideo_matcher_gate_last_small(self._h, None, C.c_int64(1 << 40), C.byref(sw), C.byref(sh)))
-        out = np.empty((sh.value, sw.value, 3), np.uint8)
-        self._check(lib().slideo_matcher_gate_last_small(self._h, _p(out), C.c_int64(out.size), C.byref(sw), C.byref(sh)))
-        return out
+    def gate_reset_from_frame_yuv420(self, frame, w, h, layout="nv12"):
+        frames, layout, _ = _yuv_frames(np.asarray(frame).reshape(-1), w, h, layout)
+        self._check(lib().slideo_matcher_gate_reset_from_frame_yuv420(self._h, _p(frames), w, h, C.byref(layout)))
 
-    @staticmethod
-    def _gated_out(n):
-        return np.zeros(n, np.uint8), np.zeros(n, np.float32), np.zeros(n, VERDICT_DTYPE)
+    def gate_reset_from_frame_dev(self, dev_ptr, w, h, stride=None, stream=0):
+        self._check(lib().slideo_matcher_gate_reset_from_frame_bgr8_dev(self._h, C.c_void_p(dev_ptr), w, h, stride or w * 3, C.c_void_p(stream)))
 
-    def match_changed_frames(self, frames):
-        """frames: uint8 [n, h, w, 3] in host memory, continuing the gate."""
-        frames = np.ascontiguousarray(frames, np.uint8)
-        n, h, w, c = frames.shape
-        assert c == 3
-        ch, sim, out = self._gated_out(n)
-        self._check(lib().slideo_match_changed_frames_bgr8(self._h, n, _p(frames), w, h, w * 3, C.c_int64(w * h * 3), _p(ch), _p(sim), _p(out)))
-        return ch.astype(bool), sim, out
-
-    def match_changed_frames_yuv420(self, frames, w, h, layout="nv12"):
-        frames, layout, fs = _yuv_frames(frames, w, h, layout)
-        n = frames.shape[0]
-        ch, sim, out = self._gated_out(n)
-        self._check(lib().slideo_match_changed_frames_yuv420(self._h, n, _p(frames), w, h, C.byref(layout), C.c_int64(fs), _p(ch), _p(sim),
-                                                             _p(out)))
-        return ch.astype(bool), sim, out
+    def gate_reset_from_frame_yuv420_dev(self, dev_ptr, w, h, layout, stream=0):
+        if isinstance(layout, str):
+            layout = yuv420_layout(layout, w, h)[0]
+        self._check(lib().slideo_matcher_gate_reset_from_frame_yuv420_dev(self._h, C.c_void_p(dev_ptr), w, h, C.byref(layout), C.c_void_p(stream)))
 
     def match_changed_frames_dev(self, dev_ptr, n, w, h, stride=None, frame_stride=None, stream=0):
         stride = stride or w * 3

@@ -36,6 +36,12 @@ struct slideo_group {
     struct KeptShard { int read_lo = 0, lo = 0, hi = 0; };
     std::vector<KeptShard> kept;
     bool kept_valid = false;
+    // the group's ONE gate state (include/slideo_amd.h "Changed-frame gate", the group's form).  Its small image lives in the gate
+    // state of member gate_owner (the last non-empty shard's member of the last gated call), or, gate_owner -1, in gate_small (a
+    // reset's prev_small); the next gated call moves it to member 0, where the call's first frame is compared.
+    slideo_matcher::GateState gate;
+    int gate_owner = -1;
+    std::vector<uint8_t> gate_small;
 };
 
 namespace {
@@ -151,6 +157,79 @@ void group_mask_impl(slideo_group* g, int32_t n_frames, const FrameSrc& src, con
     g->kept_valid = true;
 }
 
+void group_gate_none(slideo_group* g) {
+    g->gate = slideo_matcher::GateState{};
+    g->gate_owner = -1;
+}
+
+// slideo_group_match_changed_frames_bgr8 / _yuv420: member 0 continues the group's gate state; every later non-empty shard [lo, hi)
+// primes its member from frame lo - 1 (the one-frame halo of group_mask_impl, as a gate state) and runs the single matcher's gated
+// call over its block.  The pairs compared, the small images and the pipeline of the changed frames are the single matcher's.
+void group_gated_impl(slideo_group* g, int32_t n_frames, const FrameSrc& src, uint8_t* changed_out, float* similarity_out,
+                      slideo_verdict* verdicts_out) {
+    const int N = (int)g->members.size();
+    slideo_matcher* m0 = g->members[0];
+    // the whole call's checks once, before any member is touched: an error leaves the gate state as it was
+    if (n_frames > 0 && !changed_out) fail(SLIDEO_ERR_INVALID_ARG, "null changed_out");
+    FrameSrc checked = src;
+    validate_frames(checked, m0, n_frames, verdicts_out);
+    gate_check(g->gate, m0->cfg.small_area, checked);
+    for (slideo_matcher* m : g->members) require_idle(m);
+    if (n_frames == 0) return;                      // a no-op: the state, the last call's traces and a mask call's kept frames stay
+    g->match_lo.assign((size_t)N + 1, 0);
+    g->kept_valid = false;
+    begin_progress(g, (uint64_t)n_frames, nullptr);
+    try {
+        // the state to member 0
+        if (g->gate_owner != 0) {
+            if (!g->gate.has) check_member_call(m0, slideo_matcher_gate_reset(m0, nullptr, 0, 0));
+            else {
+                if (g->gate_owner > 0) {
+                    slideo_matcher* o = g->members[g->gate_owner];
+                    int32_t sw = 0, sh = 0;
+                    g->gate_small.resize((size_t)g->gate.sw * g->gate.sh * 3);
+                    check_member_call(o, slideo_matcher_gate_last_small(o, g->gate_small.data(), (int64_t)g->gate_small.size(), &sw, &sh));
+                    if (sw != g->gate.sw || sh != g->gate.sh)
+                        fail(SLIDEO_ERR_STATE, "member %d holds a %dx%d small image, the group's is %dx%d (a member was gated directly)", g->gate_owner,
+                             sw, sh, g->gate.sw, g->gate.sh);
+                }
+                check_member_call(m0, slideo_matcher_gate_reset(m0, g->gate_small.data(), g->gate.sw, g->gate.sh));
+            }
+            g->gate_owner = 0;
+        }
+        int last_r = 0;
+        for (int r = 0; r < N; ++r) { int lo, hi; shard_range(n_frames, r, N, lo, hi); if (hi > lo) last_r = r; }
+        for_each_member(g, [&](int r) {
+            int lo, hi;
+            shard_range(n_frames, r, N, lo, hi);
+            if (hi <= lo) return;
+            slideo_matcher* m = g->members[r];
+            if (r > 0) {
+                FrameSrc halo = src.from(lo - 1);
+                if (halo.yuv) halo.frame_stride = -1;           // (a single frame: no stride to check)
+                gate_prime(m, halo, nullptr);
+            }
+            match_frames_impl(m, hi - lo, src.from(lo), verdicts_out + lo, nullptr, true, changed_out + lo,
+                              similarity_out ? similarity_out + lo : nullptr);
+        });
+        g->gate = g->members[last_r]->gate;
+        g->gate_owner = last_r;
+    } catch (const slideo::Error& e) {
+        group_gate_none(g);
+        fail(e.code, "%s (the group's gate state is now \"none\")", e.what());
+    } catch (const std::exception& e) {
+        group_gate_none(g);
+        fail(SLIDEO_ERR_HIP, "%s (the group's gate state is now \"none\")", e.what());
+    }
+    // the trace lookup counts CHANGED frames: member r's are [match_lo[r], match_lo[r + 1])
+    for (int r = 0; r < N; ++r) {
+        int lo, hi, k = 0;
+        shard_range(n_frames, r, N, lo, hi);
+        for (int i = lo; i < hi; ++i) k += changed_out[i] != 0;
+        g->match_lo[r + 1] = g->match_lo[r] + k;
+    }
+}
+
 }  // namespace
 
 #define GROUP_TRY try {
@@ -250,6 +329,7 @@ int32_t slideo_group_set_working_size(slideo_group* g, int32_t max_w, int32_t ma
     GROUP_TRY
     for (slideo_matcher* m : g->members) check_member_call(m, slideo_matcher_set_working_size(m, max_w, max_h));
     g->kept_valid = false;
+    group_gate_none(g);
     GROUP_CATCH(g)
 }
 
@@ -391,6 +471,57 @@ int32_t slideo_group_match_kept_frames(slideo_group* g, int32_t n_sel, const int
         check_member_call(g->members[r], slideo_match_kept_frames(g->members[r], (int32_t)local[r].size(), local[r].data(), v.data()));
         for (size_t j = 0; j < v.size(); ++j) verdicts_out[where[r][j]] = v[j];
     });
+    GROUP_CATCH(g)
+}
+
+int32_t slideo_group_gate_reset(slideo_group* g, const uint8_t* prev_small, int32_t small_w, int32_t small_h) {
+    if (!g) return SLIDEO_ERR_INVALID_ARG;
+    GROUP_TRY
+    const int small_area = g->members[0]->cfg.small_area;
+    if (prev_small && (small_w < 1 || small_h < 1 || (int64_t)small_w * small_h > small_area))
+        fail(SLIDEO_ERR_INVALID_ARG, "gate_reset: a %dx%d small image (at most small_area = %d pixels)", small_w, small_h, small_area);
+    for (slideo_matcher* m : g->members) require_idle(m);
+    group_gate_none(g);
+    if (!prev_small) return SLIDEO_OK;
+    g->gate_small.assign(prev_small, prev_small + (size_t)small_w * small_h * 3);
+    g->gate.has = true; g->gate.sw = small_w; g->gate.sh = small_h;
+    GROUP_CATCH(g)
+}
+
+int32_t slideo_group_gate_last_small(slideo_group* g, uint8_t* out, int64_t out_capacity, int32_t* sw, int32_t* sh) {
+    if (!g) return SLIDEO_ERR_INVALID_ARG;
+    GROUP_TRY
+    if (!sw || !sh) fail(SLIDEO_ERR_INVALID_ARG, "null sw/sh");
+    for (slideo_matcher* m : g->members) require_idle(m);
+    if (!g->gate.has) fail(SLIDEO_ERR_STATE, "the gate state is \"none\": no frame was gated since the last reset");
+    if (g->gate_owner >= 0) {
+        slideo_matcher* o = g->members[g->gate_owner];
+        check_member_call(o, slideo_matcher_gate_last_small(o, out, out_capacity, sw, sh));
+        return SLIDEO_OK;
+    }
+    *sw = g->gate.sw; *sh = g->gate.sh;
+    if ((int64_t)g->gate_small.size() > out_capacity) fail(SLIDEO_ERR_CAPACITY, "small image needs %lld bytes", (long long)g->gate_small.size());
+    if (out) std::memcpy(out, g->gate_small.data(), g->gate_small.size());
+    GROUP_CATCH(g)
+}
+
+int32_t slideo_group_match_changed_frames_bgr8(slideo_group* g, int32_t n_frames, const uint8_t* frames, int32_t width, int32_t height,
+                                               int32_t stride_bytes, int64_t frame_stride_bytes, uint8_t* changed_out, float* similarity_out,
+                                               slideo_verdict* verdicts_out) {
+    if (!g) return SLIDEO_ERR_INVALID_ARG;
+    GROUP_TRY
+    group_gated_impl(g, n_frames, FrameSrc::bgr8(frames, false, width, height, stride_bytes, frame_stride_bytes), changed_out, similarity_out,
+                     verdicts_out);
+    GROUP_CATCH(g)
+}
+
+int32_t slideo_group_match_changed_frames_yuv420(slideo_group* g, int32_t n_frames, const uint8_t* frames, int32_t width, int32_t height,
+                                                 const slideo_yuv420_layout* layout, int64_t frame_stride_bytes, uint8_t* changed_out,
+                                                 float* similarity_out, slideo_verdict* verdicts_out) {
+    if (!g) return SLIDEO_ERR_INVALID_ARG;
+    GROUP_TRY
+    group_gated_impl(g, n_frames, FrameSrc::yuv420(frames, false, width, height, layout, frame_stride_bytes), changed_out, similarity_out,
+                     verdicts_out);
     GROUP_CATCH(g)
 }
 

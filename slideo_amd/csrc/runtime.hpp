@@ -440,6 +440,11 @@ inline void gate_state_reset(slideo_matcher* m) { m->gate = slideo_matcher::Gate
 inline size_t gate_small_budget(const slideo_matcher* m) { return (size_t)m->cfg.small_area * 3 + 64; }
 // a validated source's frames against the gate state: one size and one format family since the last reset (SLIDEO_ERR_STATE)
 void gate_check(const slideo_matcher* m, const FrameSrc& src);
+// the same against a state held elsewhere (the N-device group's, capi_group.hip)
+void gate_check(const slideo_matcher::GateState& g, int small_area, const FrameSrc& src);
+// slideo_matcher_gate_reset_from_frame_*: the gate state of an idle matcher := the small image of the ONE frame of src (frame_stride
+// as of a single frame), staged as a gated unit stages it; user_stream: the stream a device frame was produced on
+void gate_prime(slideo_matcher* m, FrameSrc src, hipStream_t user_stream);
 // One gated unit on slot S: frames [first, first + n) of src through the gate, the changed ones through unit_submit (S.n = their
 // count, 0: no pipeline ran); its collect: flags and similarities of all n frames, verdicts of the changed ones
 void gate_unit_submit(slideo_matcher* m, Slot& S, const FrameSrc& src, int first, int n, hipStream_t cs);

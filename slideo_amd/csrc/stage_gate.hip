@@ -32,17 +32,43 @@ int64_t ssd_threshold(float changed_similarity_, int sw, int sh) {
 }  // namespace
 
 // The frames of a gated call against the gate state: one size and one format family since the last reset.  Nothing is changed here.
-void gate_check(const slideo_matcher* m, const FrameSrc& src) {
-    const slideo_matcher::GateState& g = m->gate;
+void gate_check(const slideo_matcher* m, const FrameSrc& src) { gate_check(m->gate, m->cfg.small_area, src); }
+
+void gate_check(const slideo_matcher::GateState& g, int small_area, const FrameSrc& src) {
     if (g.seen && (g.w != src.w || g.h != src.h || g.yuv != (src.yuv != nullptr)))
         fail(SLIDEO_ERR_STATE, "gated frames changed from %dx%d %s to %dx%d %s without slideo_matcher_gate_reset", g.w, g.h, g.yuv ? "yuv420" : "bgr8",
              src.w, src.h, src.yuv ? "yuv420" : "bgr8");
     if (g.has && !g.seen) {
         int sw = 0, sh = 0;
-        small_size(src.unit_w(), src.unit_h(), m->cfg.small_area, sw, sh);
+        small_size(src.unit_w(), src.unit_h(), small_area, sw, sh);
         if (sw != g.sw || sh != g.sh)
             fail(SLIDEO_ERR_STATE, "the gate holds a %dx%d small image, these frames' is %dx%d: slideo_matcher_gate_reset first", g.sw, g.sh, sw, sh);
     }
+}
+
+// slideo_matcher_gate_reset_from_frame_*: the one frame staged as a gated unit stages its frames (slot 0; plain device BGR is read in
+// place), its small image written into the gate state behind the last gated unit's write of it.  What slideo_matcher_gate_reset
+// leaves with that small image: the frame's own size and format family are not recorded.
+void gate_prime(slideo_matcher* m, FrameSrc src, hipStream_t user_stream) {
+    validate_frames(src, m, 1, src.p);              // (a gated call's rules; the frame itself stands for the null frames / verdicts check)
+    HIP_CHECK(hipSetDevice(m->device));
+    require_idle(m);
+    Slot& S = m->slots[0];
+    hipStream_t st = S.st;
+    if (!S.ev_gate) HIP_CHECK(hipEventCreateWithFlags(&S.ev_gate, hipEventDisableTiming));
+    if (src.on_device && user_stream) {             // the frame was produced on the caller's stream
+        HIP_CHECK(hipEventRecord(S.ev_in, user_stream));
+        HIP_CHECK(hipStreamWaitEvent(st, S.ev_in, 0));
+    }
+    if (m->last_gate_ev && m->last_gate_ev != S.ev_gate) HIP_CHECK(hipStreamWaitEvent(st, m->last_gate_ev, 0));
+    const DevFrames f = stage_frames(m, S, src, 0, 1, nullptr, &S.d_gstage);
+    int sw = 0, sh = 0;
+    run_small_into(m, f, 1, m->d_gate_small, sw, sh, st);
+    HIP_CHECK(hipEventRecord(S.ev_gate, st));
+    m->last_gate_ev = S.ev_gate;
+    HIP_CHECK(hipStreamSynchronize(st));            // (the caller's frame is free again)
+    gate_state_reset(m);
+    m->gate.has = true; m->gate.sw = sw; m->gate.sh = sh;
 }
 
 // One gated unit: frames [first, first + n) of src through the gate, the changed ones through unit_submit.  One short host wait
@@ -151,6 +177,38 @@ int32_t slideo_matcher_gate_reset(slideo_matcher* m, const uint8_t* prev_small, 
     HIP_CHECK(hipStreamSynchronize(m->stream));
     gate_state_reset(m);
     m->gate.has = true; m->gate.sw = small_w; m->gate.sh = small_h;
+    API_CATCH(m)
+}
+
+int32_t slideo_matcher_gate_reset_from_frame_bgr8(slideo_matcher* m, const uint8_t* frame, int32_t width, int32_t height, int32_t stride_bytes) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    gate_prime(m, FrameSrc::image(frame, width, height, stride_bytes), nullptr);
+    API_CATCH(m)
+}
+
+int32_t slideo_matcher_gate_reset_from_frame_yuv420(slideo_matcher* m, const uint8_t* frame, int32_t width, int32_t height,
+                                                    const slideo_yuv420_layout* layout) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    gate_prime(m, FrameSrc::yuv420(frame, false, width, height, layout, -1), nullptr);
+    API_CATCH(m)
+}
+
+int32_t slideo_matcher_gate_reset_from_frame_bgr8_dev(slideo_matcher* m, const uint8_t* frame_dev, int32_t width, int32_t height,
+                                                      int32_t stride_bytes, void* hip_stream) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    gate_prime(m, FrameSrc::bgr8(frame_dev, true, width, height, stride_bytes, (int64_t)height * stride_bytes),
+               reinterpret_cast<hipStream_t>(hip_stream));
+    API_CATCH(m)
+}
+
+int32_t slideo_matcher_gate_reset_from_frame_yuv420_dev(slideo_matcher* m, const uint8_t* frame_dev, int32_t width, int32_t height,
+                                                        const slideo_yuv420_layout* layout, void* hip_stream) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    gate_prime(m, FrameSrc::yuv420(frame_dev, true, width, height, layout, -1), reinterpret_cast<hipStream_t>(hip_stream));
     API_CATCH(m)
 }
 

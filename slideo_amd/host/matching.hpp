@@ -167,6 +167,7 @@ struct Handle {
     slideo_group* g = nullptr;
     int n_devices = 1;
     int32_t work_w = 0, work_h = 0;          // the working size the group was given (0, 0: none)
+    bool gated = true;                       // tasks use the group's gated call (false: the stop-and-go mask + kept pair)
     ~Handle() { if (g) slideo_group_destroy(g); }
     void check(int32_t rc) const {
         if (rc != SLIDEO_OK) throw std::runtime_error(std::string("slideo_amd error ") + std::to_string(rc) + ": " + slideo_group_last_error(g));
@@ -213,10 +214,10 @@ public:
         std::vector<uint8_t> frames, prev_small, last_small;
         std::vector<std::pair<double, size_t>> meta;
         int sw = 0, sh = 0;
-        // the changed-frame gate (slideo_amd.h "Changed-frame gate"): a one-device group gates through its member, one call per flush,
-        // the last small image carried in the matcher; a group of several devices keeps the mask + kept pair (it has no gated form)
-        slideo_matcher* gate = h_->n_devices == 1 ? slideo_group_member(h_->g, 0) : nullptr;
-        if (gate) h_->check(slideo_matcher_gate_reset(gate, nullptr, 0, 0));            // the first frame of the video is always changed
+        // the changed-frame gate (slideo_amd.h "Changed-frame gate"): the group's gated call for any member count, one call per flush,
+        // every shard after the first primed from the frame before its block, the last small image carried in the group
+        const bool gate = h_->gated;
+        if (gate) h_->check(slideo_group_gate_reset(h_->g, nullptr, 0, 0));             // the first frame of the video is always changed
         auto emit = [&](const std::vector<int32_t>& idx, const slideo_verdict* v) {
             for (size_t k = 0; k < idx.size(); ++k) {
                 std::optional<I> img;
@@ -230,8 +231,8 @@ public:
             std::vector<uint8_t> changed(n);
             if (gate) {       // MarkSimilarIter + match_images_with_frame of the changed frames (mo/lib.rs:205-214) in one call
                 std::vector<slideo_verdict> all(n), v;
-                h_->check(slideo_match_changed_frames_bgr8(gate, n, frames.data(), video.width, video.height, video.width * 3, (int64_t)fb,
-                                                           changed.data(), nullptr, all.data()));
+                h_->check(slideo_group_match_changed_frames_bgr8(h_->g, n, frames.data(), video.width, video.height, video.width * 3, (int64_t)fb,
+                                                                 changed.data(), nullptr, all.data()));
                 std::vector<int32_t> idx;
                 for (int i = 0; i < n; ++i) if (changed[i]) { idx.push_back(i); v.push_back(all[i]); }
                 emit(idx, v.data());
@@ -324,6 +325,9 @@ public:
     // Frames beyond max_w x max_h are reduced on the GPU before matching (slideo_group_set_working_size; include/slideo_amd.h
     // "Working size").  The reference never reduces a frame: verdicts are then those of the reduced video.  Default: none
     HipImageVideoMatcher& with_working_size(int32_t max_w, int32_t max_h) { work_w_ = max_w; work_h_ = max_h; return *this; }
+    // false: tasks run the stop-and-go pair slideo_group_changed_mask_bgr8 + slideo_group_match_kept_frames in place of the group's
+    // gated call (the same timeline; for comparisons).  Default: gated
+    HipImageVideoMatcher& with_changed_gate(bool on) { gated_ = on; return *this; }
     template <class I>
     std::unique_ptr<VideoMatcher<I>> create_video_matcher(std::vector<I> images, ProgressReporter reporter) const {
         auto h = std::make_shared<detail::Handle>();
@@ -331,6 +335,7 @@ public:
         int32_t rc = slideo_group_create(&cfg_, (int32_t)devices_.size(), devices_.empty() ? nullptr : devices_.data(), &h->g);
         if (rc != SLIDEO_OK) throw std::runtime_error(std::string("slideo_amd error ") + std::to_string(rc) + ": " + slideo_group_last_error(nullptr));
         h->n_devices = (int)slideo_group_device_count(h->g);
+        h->gated = gated_;
         if (sift_on_) {                                                                             // the north-star's SIFT + L2 front end
             slideo_sift_config sc;
             slideo_sift_config_default(&sc);
@@ -355,7 +360,7 @@ public:
     }
 private:
     std::vector<int32_t> devices_;
-    bool sift_on_ = false;
+    bool sift_on_ = false, gated_ = true;
     float sift_ratio_ = 0.f;
     int32_t work_w_ = 0, work_h_ = 0;
     slideo_config cfg_;

@@ -184,7 +184,7 @@ class HipVideoMatcherTask:
         pend_frames, pend_meta, prev_small = [], [], None
         yuv = getattr(video, "yuv420_format", None)              # RawVideoYuv420: 'nv12' / 'i420'; RawVideo: None (BGR)
         # the changed-frame gate (include/slideo_amd.h "Changed-frame gate"): one gated call per flush, the last small image carried
-        # in the matcher.  None (a matcher without the gated calls, a group of several devices): the mask + kept pair below.
+        # in the matcher (a group: in the group).  None (a handle without the gated calls): the mask + kept pair below.
         gate = _gated_matcher(m)
         if gate is not None:
             gate.gate_reset(None)                                # the first frame of the video is always changed
@@ -239,14 +239,9 @@ class HipVideoMatcherTask:
 
 
 def _gated_matcher(m):
-    """The handle whose gated calls serve a task over `m`: m itself (a Matcher), the one member of a one-device group (the group
-    has no gated form: a shard needs the frame before its block), or None."""
-    if hasattr(m, "match_changed_frames"):
-        return m
-    if hasattr(m, "member") and len(getattr(m, "devices", [])) == 1:
-        one = m.member(0)
-        return one if hasattr(one, "match_changed_frames") else None
-    return None
+    """The handle whose gated calls serve a task over `m`: m itself — a Matcher, or a Group of any member count (the group's gated
+    call shards the frames and primes every later shard from the frame before its block) — or None for a handle without them."""
+    return m if hasattr(m, "match_changed_frames") and hasattr(m, "gate_reset") else None
 
 
 def dedup_timeline(mappings: List[Matching]) -> List[Matching]:

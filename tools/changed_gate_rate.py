@@ -11,7 +11,17 @@ ORB-1000) on a lecture-like sequence: holds of identical frames whose lengths ar
     python tools/changed_gate_rate.py [--share 0.1] [--frames 256] [--reps 3] [--kernels-only]
 
 Prints one line per measurement and a JSON line at the end.  --kernels-only: (c) alone, twice, for a
-rocprofv3 --kernel-trace --stats run of its own (gate_kernel, gather_frames_kernel beside yuv420_to_bgr_kernel)."""
+rocprofv3 --kernel-trace --stats run of its own (gate_kernel, gather_frames_kernel beside yuv420_to_bgr_kernel).
+
+--devices 0,1,2 | 0,0 | all: the N-device group over these HIP ordinals instead (an ordinal may repeat: members then share a
+device, which measures the mechanism and not scaling; all = every gfx950 device of the node).  Pinned BGR and NV12 host frames in
+calls of 64 frames per member, at --share 0.1 and 0.5 unless one is given, the three forms as alternated repeats on the one library:
+
+  (g) the gated group call (slideo_group_match_changed_frames_*)
+  (p) the group's stop-and-go pair: changed_mask + match_kept_frames
+  (u) the ungated group call over ALL frames (slideo_group_match_frames_*)
+
+with the changed frames each member kept (shards are contiguous: a run of changed frames loads one member)."""
 import argparse
 import json
 import os
@@ -55,14 +65,106 @@ def stream(m, submit, collect, n, unit):
         collect(t)
 
 
+def shard(n, r, world):
+    """slideo_amd/distributed.py shard_range: member r's block of a call of n frames."""
+    base, rem = divmod(n, world)
+    lo = r * base + min(r, rem)
+    return lo, lo + base + (1 if r < rem else 0)
+
+
+def group_main(a):
+    devices = None if a.devices == "all" else [int(d) for d in a.devices.split(",")]
+    N = a.frames
+    pages = synth.pages(a.pages, 2001, 1125, threads=NCPU)
+    g = _capi.Group(_capi.default_config(nfeatures=1000), devices)
+    for i in range(0, a.pages, 50):
+        g.add_pages(list(pages[i:i + 50]))
+    g.finalize()
+    members = len(g.devices)
+    batch = BATCH * members
+    shared = len(set(g.devices)) < members
+    label = "%d members on devices %s%s" % (members, g.devices, " (members share a device: the mechanism, not scaling)" if shared else "")
+    print(label, flush=True)
+    L, fb = _capi.yuv420_layout("nv12", W, H)
+    res = {"shape": "%d pages, %d 1080p frames, ORB-1000, calls of %d frames" % (a.pages, N, batch), "devices": g.devices, "label": label, "shares": {}}
+    for share in ([a.share] if a.share is not None else [0.1, 0.5]):
+        seq = lecture(pages, N, share)
+        src = {"bgr": torch.from_numpy(seq).pin_memory().numpy(), "nv12": torch.from_numpy(yuv420_ref.frames_to_yuv(seq, L, fb)).pin_memory().numpy()}
+        del seq
+
+        def gated(kind):
+            g.gate_reset(None)
+            out = []
+            for i in range(0, N, batch):
+                f = src[kind][i:i + batch]
+                out.append(g.match_changed_frames(f) if kind == "bgr" else g.match_changed_frames_yuv420(f, W, H, L))
+            return out
+
+        def pair(kind):
+            prev, out = None, []
+            for i in range(0, N, batch):
+                f = src[kind][i:i + batch]
+                c, _, prev = g.changed_mask(f, prev) if kind == "bgr" else g.changed_mask_yuv420(f, W, H, L, prev)
+                idx = np.nonzero(c)[0]
+                out.append((c, g.match_kept_frames(idx) if len(idx) else np.zeros(0, _capi.VERDICT_DTYPE)))
+            return out
+
+        def plain(kind):
+            for i in range(0, N, batch):
+                f = src[kind][i:i + batch]
+                g.match_frames(f) if kind == "bgr" else g.match_frames_yuv420(f, W, H, L)
+
+        r = {}
+        runs = {}
+        for kind in ("bgr", "nv12"):
+            # (warm, and the check that both forms return one result) the flags and the verdicts of the changed frames
+            got, want = gated(kind), pair(kind)
+            kept = [0] * members
+            for (c, _, v), (pc, pv) in zip(got, want):
+                assert np.array_equal(c, pc) and v[c].tobytes() == pv.tobytes(), "the gated call and the pair disagree"
+                for m in range(members):
+                    lo, hi = shard(len(c), m, members)
+                    kept[m] += int(c[lo:hi].sum())
+            plain(kind)
+            r["changed_share_%s" % kind] = sum(kept) / N
+            r["kept_per_member_%s" % kind] = kept
+            print("share %.2f %s: changed %.3f, kept per member %s" % (share, kind, sum(kept) / N, kept), flush=True)
+            runs["g_gated_%s" % kind] = lambda k=kind: gated(k)
+            runs["p_pair_%s" % kind] = lambda k=kind: pair(k)
+            runs["u_plain_all_%s" % kind] = lambda k=kind: plain(k)
+        t = {k: [] for k in runs}
+        for _ in range(a.reps):                                                 # (alternating, so that clock and thermal drift hit all alike)
+            for k, fn in runs.items():
+                t0 = time.perf_counter()
+                fn()
+                t[k].append(time.perf_counter() - t0)
+        for k in runs:
+            ms = sorted(x * 1e3 for x in t[k])
+            r[k + "_ms"] = {"min": ms[0], "median": float(np.median(ms)), "max": ms[-1]}
+            print("share %.2f %-18s min %.2f median %.2f max %.2f ms per %d frames = %.0f frames/s (of the stream)"
+                  % (share, k, ms[0], float(np.median(ms)), ms[-1], N, N / (float(np.median(ms)) * 1e-3)), flush=True)
+        for kind in ("bgr", "nv12"):
+            gm, pm, um = (r["%s_%s_ms" % (k, kind)] for k in ("g_gated", "p_pair", "u_plain_all"))
+            r["g_minus_p_%s_ms" % kind] = gm["median"] - pm["median"]
+            print("share %.2f %s: (g) - (p) %.2f ms (spread of (p) %.2f, of (g) %.2f)   (u) / (g) %.2fx"
+                  % (share, kind, gm["median"] - pm["median"], pm["max"] - pm["min"], gm["max"] - gm["min"], um["median"] / gm["median"]), flush=True)
+        res["shares"]["%.2f" % share] = r
+    g.close()
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--share", type=float, default=0.1)
+    ap.add_argument("--share", type=float, default=None)
+    ap.add_argument("--devices", default=None, help="the N-device group over these ordinals (0,1 | 0,0 | all)")
     ap.add_argument("--frames", type=int, default=256)
     ap.add_argument("--pages", type=int, default=500)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--kernels-only", action="store_true")
     a = ap.parse_args()
+    if a.devices:
+        return group_main(a)
+    a.share = 0.1 if a.share is None else a.share
     N = a.frames
     pages = synth.pages(a.pages, 2001, 1125, threads=NCPU)
     seq = lecture(pages, N, a.share)
