@@ -402,6 +402,35 @@ extern "C" {
         similarity_out: *mut f32,
         verdicts_out: *mut slideo_verdict,
     ) -> i32;
+    // frame mask (include/slideo_amd.h "Frame mask"): mask null clears it
+    pub fn slideo_matcher_set_frame_mask(
+        m: *mut slideo_matcher,
+        mask: *const u8,
+        width: i32,
+        height: i32,
+        stride_bytes: i32,
+    ) -> i32;
+    pub fn slideo_matcher_frame_mask_info(
+        m: *const slideo_matcher,
+        width: *mut i32,
+        height: *mut i32,
+        is_set: *mut i32,
+    ) -> i32;
+    pub fn slideo_group_set_frame_mask(
+        g: *mut slideo_group,
+        mask: *const u8,
+        width: i32,
+        height: i32,
+        stride_bytes: i32,
+    ) -> i32;
+    pub fn slideo_frame_mask_level(
+        m: *mut slideo_matcher,
+        level: i32,
+        out: *mut u8,
+        out_capacity: i64,
+        lw: *mut i32,
+        lh: *mut i32,
+    ) -> i32;
 }
 
 /// The struct layouts above are only valid for one ABI version of the library.

@@ -700,6 +700,50 @@ int32_t     slideo_group_set_working_size(slideo_group* g, int32_t max_w, int32_
 int32_t     slideo_reduce_bgr8(slideo_matcher* m, const uint8_t* bgr, int32_t width, int32_t height, int32_t stride_bytes,
                                int32_t dw, int32_t dh, uint8_t* out, int64_t out_capacity);
 
+/* ---- Frame mask (cv::ORB::detectAndCompute's `mask` argument; the reference passes no_array(), mo/feature_extractor.rs:35) ----------
+ * [OCV — recalled, unpinned, like the rest of SURVEY.md Appendix A: OpenCV 4.5.2 features2d/orb.cpp detectAndCompute /
+ * computeKeyPoints and KeyPointsFilter::runByPixelsMask.]
+ * A matcher carries an optional FRAME MASK: a u8 image of mw x mh, nonzero = "detect here".  While one is set, a frame call whose
+ * ANALYSED size — the size after 4:2:0 conversion and the working-size reduce — equals (mw, mh) detects its ORB keypoints as
+ * detectAndCompute(frame, mask, ...) does:
+ *   mask pyramid   level 0 is the mask as given; level l > 0 is resize(level l - 1, size of image level l, INTER_LINEAR_EXACT)
+ *                  followed by threshold(254, THRESH_TOZERO).  The resize is the image pyramid's own (resize_kernel and the size's
+ *                  tap tables, csrc/orb.hip.h), bit-identical to what that kernel does to a u8 image, so a deeper-level pixel is
+ *                  nonzero only where the interpolated value is exactly 255.  slideo_frame_mask_level returns a level.
+ *   filter         a FAST candidate at integer level coordinates (x, y) of level l, after non-max suppression, is dropped iff mask
+ *                  level l is 0 at (x, y) ((int)(pt + 0.5f) is the identity there).  This happens BEFORE retainBest: the level's
+ *                  quota is filled from the unmasked candidates, ties kept as without a mask.  Orientation, blur and BRIEF read
+ *                  the unmasked image, as in OpenCV.
+ * DETECTION ONLY: the small image, the changed-frame flags and similarities, the re-projection similarity and the verdict rule see
+ * the whole frame.  (A masked gate SSD / masked re-projection is a possible follow-up, not part of this.)
+ * Pages are never masked, a page of the mask's size included.  A frame call whose analysed size differs from the mask's fails
+ * with SLIDEO_ERR_INVALID_ARG, naming both sizes; it is not silently unmasked.  SIFT mode refuses a mask with SLIDEO_ERR_UNSUPPORTED,
+ * at slideo_matcher_set_frame_mask and at slideo_matcher_use_sift.  Everything behind ORB is unchanged, so every option is picked
+ * up as without a mask: matcher 1 (LSH), page sets, verify_model 1, ratio_test, the gate, the mask-call + slideo_match_kept_frames
+ * pair, submit / collect, the group.  A mask of all 255 gives, bit for bit, the results of no mask; a mask of all 0 gives
+ * n_keypoints 0 and page_idx -1 for every frame.
+ * Where it runs (csrc/frame_mask.hip.h, csrc/stage_orb.hip): the pyramid is made once, at set time; per unit ONE more kernel,
+ * mask_filter_kernel, between fast_kernel and threshold_kernel on the unit's stream: a block per (frame, level) compacts the level's
+ * candidate list in place and rebuilds its score histogram and count from the survivors.  A unit re-run through the exact-size
+ * path applies the mask again.  Without a mask no call launches anything it did not launch before.
+ * Measured (one MI355X, 500 pages, ORB-1000, 256 device-resident 1080p frames per step, a hole of 20 % of the frame;
+ * docs/EXTENSIONS.md, profiles/r10_frame_mask_*): mask_filter_kernel 0.13 ms per 256 frames (18 VGPRs, 1044 B LDS, no scratch); the
+ * masked step 13.21 ms against 13.00 ms without a mask (spread 0.4 ms); on frames with a random-texture inset over that 20 %, 0.984
+ * of the frames are assigned to the truth with the inset masked against 0.922 without. */
+/* Idle matcher (SLIDEO_ERR_STATE with units in flight), before or after finalize, any number of times: a second mask replaces the
+ * first.  mask: width x height bytes, rows stride_bytes apart, host memory; the bytes are copied.  mask == NULL clears it (the sizes
+ * are then ignored).  SLIDEO_ERR_INVALID_ARG for width or height < 1 or stride_bytes < width; SLIDEO_ERR_UNSUPPORTED for a side
+ * beyond 4096 and in SIFT mode.  Ends the kept frames of an earlier mask call; the gate state stays. */
+int32_t     slideo_matcher_set_frame_mask(slideo_matcher* m, const uint8_t* mask, int32_t width, int32_t height, int32_t stride_bytes);
+/* *is_set 1 and the mask's size, or 0 and 0 x 0.  SLIDEO_ERR_INVALID_ARG for a null argument. */
+int32_t     slideo_matcher_frame_mask_info(const slideo_matcher* m, int32_t* width, int32_t* height, int32_t* is_set);
+/* Forwards to every member (every member idle); ends the group's kept frames. */
+int32_t     slideo_group_set_frame_mask(slideo_group* g, const uint8_t* mask, int32_t width, int32_t height, int32_t stride_bytes);
+/* Tap: level `level` of the mask pyramid (out: stride *lw, out_capacity >= *lw * *lh).  SLIDEO_ERR_STATE without a mask,
+ * SLIDEO_ERR_INVALID_ARG for a level outside 0 .. nlevels - 1 or a null argument, SLIDEO_ERR_CAPACITY (with *lw, *lh set).
+ * The tap slideo_orb_bgr8 honours the mask for an image of the mask's size; the page-side calls and slideo_pyramid_level_bgr8 never do. */
+int32_t     slideo_frame_mask_level(slideo_matcher* m, int32_t level, uint8_t* out, int64_t out_capacity, int32_t* lw, int32_t* lh);
+
 /* ---- Changed-frame gate (MarkSimilarIter, mo/video_capture.rs:86-98, inside the unit pipeline) ---------------------------------
  * slideo_changed_mask_* + slideo_match_kept_frames are a stop-and-go pair: host frames, an idle matcher, the flags made on the host.
  * A GATED call or unit decides on the device which of its frames changed and runs ORB / search / verify on those alone; host and

@@ -139,6 +139,7 @@ EXPORTS = [
     "slideo_matcher_gate_reset_from_frame_bgr8", "slideo_matcher_gate_reset_from_frame_yuv420", "slideo_matcher_gate_reset_from_frame_bgr8_dev",
     "slideo_matcher_gate_reset_from_frame_yuv420_dev", "slideo_group_gate_reset", "slideo_group_gate_last_small",
     "slideo_group_match_changed_frames_bgr8", "slideo_group_match_changed_frames_yuv420",
+    "slideo_matcher_set_frame_mask", "slideo_matcher_frame_mask_info", "slideo_group_set_frame_mask", "slideo_frame_mask_level",
 ]
 
 _lib = None
@@ -195,6 +196,12 @@ def lib():
             L.slideo_group_gate_last_small.argtypes = [vp, vp, i64, vp, vp]
             L.slideo_group_match_changed_frames_bgr8.argtypes = [vp, i32, vp, i32, i32, i32, i64, vp, vp, vp]
             L.slideo_group_match_changed_frames_yuv420.argtypes = [vp, i32, vp, i32, i32, vp, i64, vp, vp, vp]
+        if hasattr(L, "slideo_matcher_set_frame_mask"):
+            vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
+            L.slideo_matcher_set_frame_mask.argtypes = [vp, vp, i32, i32, i32]
+            L.slideo_matcher_frame_mask_info.argtypes = [vp, vp, vp, vp]
+            L.slideo_group_set_frame_mask.argtypes = [vp, vp, i32, i32, i32]
+            L.slideo_frame_mask_level.argtypes = [vp, i32, vp, i64, vp, vp]
         _lib = L
     return _lib
 
@@ -329,6 +336,18 @@ class _FrameCalls:
     @property
     def working_size(self):
         return getattr(self, "_ws", (0, 0))
+
+    # frame mask (include/slideo_amd.h "Frame mask"): ORB keypoints of frames of the mask's size are detected under it
+    def set_frame_mask(self, mask):
+        """mask: uint8 [h, w], nonzero = detect here; None clears it.  Detection only; pages are never masked.  The matcher must
+        be idle; frames of another analysed size are then an error (SLIDEO_ERR_INVALID_ARG)."""
+        if mask is None:
+            self._check(getattr(lib(), self._SETS + "set_frame_mask")(self._h, None, 0, 0, 0))
+            return
+        mask = np.ascontiguousarray(mask)
+        if mask.ndim != 2 or mask.dtype != np.uint8:
+            raise SlideoError(1, "set_frame_mask: expected an (h, w) uint8 mask")
+        self._check(getattr(lib(), self._SETS + "set_frame_mask")(self._h, _p(mask), mask.shape[1], mask.shape[0], mask.shape[1]))
 
     def _unit_size(self, w, h):
         """The size of the image the pipeline reads for a w x h frame."""
@@ -657,6 +676,25 @@ class Matcher(_FrameCalls):
         mhz = C.c_double(); n = C.c_int64()
         self._check(lib().slideo_matcher_read_shader_clock(self._h, C.byref(mhz), C.byref(n)))
         return mhz.value, n.value
+
+    # ---- frame mask (the setter: _FrameCalls) ----------------------------------------------
+    @property
+    def frame_mask_info(self):
+        """(w, h) of the frame mask, or None."""
+        w, h, on = C.c_int32(), C.c_int32(), C.c_int32()
+        self._check(lib().slideo_matcher_frame_mask_info(self._h, C.byref(w), C.byref(h), C.byref(on)))
+        return (w.value, h.value) if on.value else None
+
+    def frame_mask_level(self, level):
+        """Level `level` of the mask pyramid, uint8 [lh, lw] (the pyramid tap)."""
+        lw, lh = C.c_int32(), C.c_int32()
+        rc = lib().slideo_frame_mask_level(self._h, int(level), _p(np.empty(1, np.uint8)), C.c_int64(0), C.byref(lw), C.byref(lh))
+        if rc not in (OK, 7):
+            self._check(rc)
+        out = np.empty((lh.value, lw.value), np.uint8)
+        if out.size:
+            self._check(lib().slideo_frame_mask_level(self._h, int(level), _p(out), C.c_int64(out.size), C.byref(lw), C.byref(lh)))
+        return out
 
     # ---- debug taps -----------------------------------------------------------------
     def orb(self, bgr, cap=None):

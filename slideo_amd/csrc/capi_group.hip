@@ -333,6 +333,14 @@ int32_t slideo_group_set_working_size(slideo_group* g, int32_t max_w, int32_t ma
     GROUP_CATCH(g)
 }
 
+int32_t slideo_group_set_frame_mask(slideo_group* g, const uint8_t* mask, int32_t width, int32_t height, int32_t stride_bytes) {
+    if (!g) return SLIDEO_ERR_INVALID_ARG;
+    GROUP_TRY
+    for (slideo_matcher* m : g->members) check_member_call(m, slideo_matcher_set_frame_mask(m, mask, width, height, stride_bytes));
+    g->kept_valid = false;
+    GROUP_CATCH(g)
+}
+
 // Page sets: every member builds the same set from the same deck (ids are handed out in the same order: they agree)
 int32_t slideo_group_create_page_set(slideo_group* g, int32_t n_pages, const int32_t* pages, int32_t* set_out) {
     if (!g) return SLIDEO_ERR_INVALID_ARG;

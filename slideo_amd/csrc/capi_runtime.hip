@@ -139,6 +139,7 @@ void validate_frames(FrameSrc& src, slideo_matcher* m, int n, const void* out) {
     if (m && src.reduce && (src.w > MAX_DIM || src.h > MAX_DIM)) fail(SLIDEO_ERR_UNSUPPORTED, "image size %dx%d outside 1..%d", src.w, src.h, MAX_DIM);
     if (m && m->sift_on) sift_check_cfg(&m->sift_cfg, src.unit_w(), src.unit_h());          // (the doubled image's coordinates travel in 13 bits)
     if (m && m->cur_set != 0) page_set_check_mode(m);                          // (a mode switched on after slideo_matcher_use_page_set)
+    if (m) (void)frame_mask_for(m, src.unit_w(), src.unit_h());                // (a frame mask holds frames of its own size only)
     if (m && !src.yuv && src.frame_stride < (int64_t)src.h * src.stride) fail(SLIDEO_ERR_INVALID_ARG, "frame_stride smaller than one frame");
     src.pinned = !src.on_device && src.p && host_is_pinned(src.p);
 }
@@ -242,7 +243,7 @@ void unit_submit(slideo_matcher* m, Slot& S, const DevFrames& f, int n, bool all
     S.timed = prof; S.u_in = f; S.u_async = async;
     if (m->orb_chain && m->last_orb_ev && m->last_orb_ev != S.ev_orb) HIP_CHECK(hipStreamWaitEvent(st, m->last_orb_ev, 0));
     if (prof) HIP_CHECK(hipEventRecord(S.ev[0], st));
-    orb_stage1(m, S, f, n, false, async ? kpcap : 0xFFFFFFFFu);
+    orb_stage1(m, S, f, n, false, async ? kpcap : 0xFFFFFFFFu, frame_mask_for(m, f.w, f.h));      // (a re-run applies the mask again)
     uint32_t qtot, qplan;
     if (async) {
         qtot = (uint32_t)n * kpcap;                                          // capacity
@@ -712,6 +713,29 @@ int32_t slideo_matcher_set_working_size(slideo_matcher* m, int32_t max_w, int32_
     m->kept.valid = false;          // (the kept frames of an earlier mask call were sized under the earlier setting)
     gate_state_reset(m);            // (and so was the gate's small image)
     API_CATCH(m)
+}
+
+// ---- frame mask (include/slideo_amd.h "Frame mask") -------------------------------------------------------------------------
+
+int32_t slideo_matcher_set_frame_mask(slideo_matcher* m, const uint8_t* mask, int32_t width, int32_t height, int32_t stride_bytes) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    if (mask) {
+        if (m->sift_on) fail(SLIDEO_ERR_UNSUPPORTED, "the frame mask filters ORB's FAST candidates: not in SIFT mode");
+        if (width < 1 || height < 1 || stride_bytes < width)
+            fail(SLIDEO_ERR_INVALID_ARG, "bad mask geometry w=%d h=%d stride=%d", width, height, stride_bytes);
+    }
+    HIP_CHECK(hipSetDevice(m->device));
+    require_idle(m);
+    m->kept.valid = false;          // (the kept frames of an earlier mask call end, as under slideo_matcher_set_working_size)
+    frame_mask_set(m, mask, width, height, stride_bytes);
+    API_CATCH(m)
+}
+
+int32_t slideo_matcher_frame_mask_info(const slideo_matcher* m, int32_t* width, int32_t* height, int32_t* is_set) {
+    if (!m || !width || !height || !is_set) return SLIDEO_ERR_INVALID_ARG;
+    *width = m->mask.set ? m->mask.w : 0; *height = m->mask.set ? m->mask.h : 0; *is_set = m->mask.set ? 1 : 0;
+    return SLIDEO_OK;
 }
 
 int32_t slideo_matcher_get_working_size(const slideo_matcher* m, int32_t* max_w, int32_t* max_h) {

@@ -18,7 +18,9 @@ int32_t slideo_orb_bgr8(slideo_matcher* m, const uint8_t* bgr, int32_t width, in
     require_idle(m);
     Slot& S = m->slots[0];
     hipStream_t st = S.st;
-    run_orb(m, S, stage_frames(m, S, img, 0, 1), 1, false);
+    // an image of the frame mask's size is analysed as a frame of that size is: under the mask
+    const uint8_t* mask_pyr = (m->mask.set && width == m->mask.w && height == m->mask.h) ? frame_mask_for(m, width, height) : nullptr;
+    run_orb(m, S, stage_frames(m, S, img, 0, 1), 1, false, false, mask_pyr);
     const uint32_t q = S.orb.qtot;
     *n_out = (int32_t)q;
     if ((int64_t)q > capacity) fail(SLIDEO_ERR_CAPACITY, "%u keypoints, capacity %d", q, capacity);
@@ -50,6 +52,24 @@ int32_t slideo_pyramid_level_bgr8(slideo_matcher* m, const uint8_t* bgr, int32_t
         const uint8_t* src = (blurred ? S.d_blur.as<uint8_t>() : S.d_pyr.as<uint8_t>()) + L.ofs;
         HIP_CHECK(hipMemcpy2DAsync(out, L.w, src, L.pitch, L.w, L.h, hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipStreamSynchronize(st));
+    }
+    API_CATCH(m)
+}
+
+int32_t slideo_frame_mask_level(slideo_matcher* m, int32_t level, uint8_t* out, int64_t out_capacity, int32_t* lw, int32_t* lh) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    if (!out || !lw || !lh) fail(SLIDEO_ERR_INVALID_ARG, "null argument");
+    if (!m->mask.set) fail(SLIDEO_ERR_STATE, "no frame mask is set");
+    if (level < 0 || level >= m->cfg.nlevels) fail(SLIDEO_ERR_INVALID_ARG, "level out of range");
+    HIP_CHECK(hipSetDevice(m->device));
+    require_idle(m);
+    const LevelGeom& L = geom_for(m, m->mask.w, m->mask.h).g.lv[level];
+    *lw = L.w; *lh = L.h;
+    if ((int64_t)L.w * L.h > out_capacity) fail(SLIDEO_ERR_CAPACITY, "level needs %lld bytes", (long long)L.w * L.h);
+    if (L.w > 0 && L.h > 0) {
+        HIP_CHECK(hipMemcpy2DAsync(out, L.w, m->mask.d_pyr.as<uint8_t>() + L.ofs, L.pitch, L.w, L.h, hipMemcpyDeviceToHost, m->stream));
+        HIP_CHECK(hipStreamSynchronize(m->stream));
     }
     API_CATCH(m)
 }

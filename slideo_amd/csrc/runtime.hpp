@@ -2,7 +2,7 @@
 //
 //   capi_runtime.hip   handles, page database, slots, frame staging (FrameSrc -> DevFrames), unit submit / collect, the drivers of the
 //                      frame calls (pipeline, submit, collect: plain and gated) and their entry points
-//   stage_orb.hip      ORB stage drivers          (kernels: orb.hip.h, yuv420.hip.h, reduce.hip.h)
+//   stage_orb.hip      ORB stage drivers          (kernels: orb.hip.h, yuv420.hip.h, reduce.hip.h, frame_mask.hip.h)
 //   stage_knn.hip      index build + k-NN stage   (kernels: knn.hip.h, knn_tile.hip.h, knn_l2.hip.h, knn_lsh.hip.h)
 //   stage_verify.hip   vote .. verdict, small img (kernels: verify.hip.h, homography.hip.h)
 //   stage_sift.hip     SIFT stage + entry points  (kernels: sift.hip.h)
@@ -235,6 +235,9 @@ struct slideo_matcher {
     // working size (slideo_matcher_set_working_size): frames beyond it are reduced in front of the pipeline; 0, 0 = none
     int work_w = 0, work_h = 0;
     std::vector<std::unique_ptr<slideo::ReduceEntry>> reduces;
+    // frame mask (slideo_matcher_set_frame_mask): the mask pyramid of a w x h mask, one frame in the level layout of the w x h
+    // image pyramid (stage_orb.hip frame_mask_set); frames of that analysed size keep only the FAST candidates it allows
+    struct FrameMask { bool set = false; int w = 0, h = 0; slideo::DevBuf d_pyr; } mask;
 
     // INTER_AREA size classes
     std::vector<slideo::AreaGeom> area_geoms;
@@ -379,10 +382,17 @@ void append_page(slideo_matcher* m, const HostPage& pg);
 // ---- stage_orb.hip --------------------------------------------------------------------------------
 void orb_stage_init(slideo_matcher* m);          // device tables of the ORB kernels + their launch attributes (slideo_matcher_create)
 void orb_geom_init(slideo_matcher* m, GeomEntry& e, const std::vector<uint32_t>& lin_tab);      // per frame size: the kernels' device tables
-void orb_stage1(slideo_matcher* m, Slot& S, const DevFrames& f, int n, bool with_blur = false, uint32_t kp_cap = 0xFFFFFFFFu);
+// mask_pyr: the mask pyramid of frames of f's size (frame_mask_for), nullptr: no mask — pages, and frames of a matcher without one
+void orb_stage1(slideo_matcher* m, Slot& S, const DevFrames& f, int n, bool with_blur = false, uint32_t kp_cap = 0xFFFFFFFFu,
+                const uint8_t* mask_pyr = nullptr);
 void orb_wait_info(slideo_matcher* m, Slot& S);
 void orb_stage2(slideo_matcher* m, Slot& S, int w, int h, bool by_capacity = false);
-void run_orb(slideo_matcher* m, Slot& S, const DevFrames& f, int n, bool keep_host_qofs, bool with_blur = false);
+void run_orb(slideo_matcher* m, Slot& S, const DevFrames& f, int n, bool keep_host_qofs, bool with_blur = false, const uint8_t* mask_pyr = nullptr);
+// Frame mask (include/slideo_amd.h "Frame mask").  frame_mask_set: the pyramid of the w x h mask (rows `stride` apart, host memory)
+// on m->stream, replacing the one before; mask null: none.  frame_mask_for: the pyramid a frame call of analysed size w x h
+// filters its candidates with — nullptr without a mask, SLIDEO_ERR_INVALID_ARG at another size.
+void frame_mask_set(slideo_matcher* m, const uint8_t* mask, int w, int h, int stride);
+const uint8_t* frame_mask_for(const slideo_matcher* m, int w, int h);
 // the two ORB kernels the SIFT stage shares: BGR -> gray u8 (pitch `pitch`, frame stride gframe), and the per-frame offsets scan
 void orb_launch_gray(const slideo_matcher* m, const uint8_t* frames_dev, int64_t frame_stride, int stride, uint8_t* gray, int64_t gframe, int w, int h,
                      int pitch, int n, hipStream_t st);

@@ -1,9 +1,10 @@
 // stage_orb.hip — drivers of the ORB stage (kernels: orb.hip.h) and of the front doors in front of it: YUV 4:2:0 frames
-// (yuv420.hip.h) and the working-size reduce (reduce.hip.h).
+// (yuv420.hip.h) and the working-size reduce (reduce.hip.h); the frame mask's pyramid and candidate filter (frame_mask.hip.h).
 #include "runtime.hpp"
 #include "orb.hip.h"
 #include "yuv420.hip.h"
 #include "reduce.hip.h"
+#include "frame_mask.hip.h"
 
 using namespace slideo;
 
@@ -136,7 +137,7 @@ static bool resize_generic_forced() { return env_long("SLIDEO_RESIZE_GENERIC", 0
 // `with_blur`: also materialise the WHOLE blurred pyramid (only the pyramid tap wants it)
 // the f32 blur of ocv.blur 0 / 1 cannot be evaluated per BRIEF sample in integer arithmetic: those variants always
 // materialise the blurred pyramid (blur_f32_kernel) and describe from it (describe_blurred_kernel)
-void orb_stage1(slideo_matcher* m, Slot& S, const DevFrames& f, int n, bool with_blur, uint32_t kp_cap) {
+void orb_stage1(slideo_matcher* m, Slot& S, const DevFrames& f, int n, bool with_blur, uint32_t kp_cap, const uint8_t* mask_pyr) {
     hipStream_t st = S.st;
     const int w = f.w, h = f.h;
     const bool full_blur = with_blur;
@@ -186,6 +187,11 @@ void orb_stage1(slideo_matcher* m, Slot& S, const DevFrames& f, int n, bool with
     if (g.fast_tiles > 0) {
         fast_kernel<<<dim3(cdiv(g.fast_tiles, FAST_TPB), n), 256, 0, st>>>(g, S.d_pyr.as<uint8_t>(), S.d_cand.as<uint32_t>(), cand_count, hist, ge.fast_tiles.as<int4>());
         check_launch("fast_kernel");
+        // frame mask: the candidates the mask forbids leave the lists before retainBest counts them
+        if (mask_pyr) {
+            mask_filter_kernel<<<dim3(L, n), MASK_BLOCK, 0, st>>>(g, mask_pyr, S.d_cand.as<uint32_t>(), cand_count, hist);
+            check_launch("mask_filter_kernel");
+        }
     }
     // the whole blurred pyramid only for the pyramid tap; on the frame path the f32 variants blur in stage 2, and only the strips
     // the kept keypoints sample (blur_mark_kernel)
@@ -259,8 +265,8 @@ void orb_stage2(slideo_matcher* m, Slot& S, int w, int h, bool by_capacity) {
 }
 
 // synchronous ORB (page ingest, taps).  Leaves: d_qofs[n+1], d_kp[qtot], d_desc[qtot*32]; S.orb filled.
-void run_orb(slideo_matcher* m, Slot& S, const DevFrames& f, int n, bool keep_host_qofs, bool with_blur) {
-    orb_stage1(m, S, f, n, with_blur);
+void run_orb(slideo_matcher* m, Slot& S, const DevFrames& f, int n, bool keep_host_qofs, bool with_blur, const uint8_t* mask_pyr) {
+    orb_stage1(m, S, f, n, with_blur, 0xFFFFFFFFu, mask_pyr);
     orb_wait_info(m, S);
     orb_stage2(m, S, f.w, f.h);
     if (keep_host_qofs) {
@@ -268,6 +274,42 @@ void run_orb(slideo_matcher* m, Slot& S, const DevFrames& f, int n, bool keep_ho
         HIP_CHECK(hipMemcpyAsync(S.orb.qofs.data(), S.d_qofs.p, (size_t)(n + 1) * 4, hipMemcpyDeviceToHost, S.st));
         HIP_CHECK(hipStreamSynchronize(S.st));
     }
+}
+
+// ---- frame mask (include/slideo_amd.h "Frame mask") ---------------------------------------------------------------------------
+// The mask pyramid: level 0 the mask as given, level l the image pyramid's own resize (resize_kernel, the w x h geometry's tap
+// tables) of level l - 1 followed by threshold(254, THRESH_TOZERO) — one frame in the pyramid's level layout, so that a FAST
+// candidate's (y, x) indexes its level directly.  Made once per mask, here; the matcher is idle.
+void frame_mask_set(slideo_matcher* m, const uint8_t* mask, int w, int h, int stride) {
+    if (!mask) { m->mask.set = false; m->mask.w = m->mask.h = 0; return; }
+    GeomEntry& ge = geom_for(m, w, h);
+    const PyrGeom& g = ge.g;
+    hipStream_t st = m->stream;
+    m->mask.set = false;                                  // (a failure below leaves no mask rather than half of one)
+    m->mask.d_pyr.reserve((size_t)g.frame_bytes + 256);
+    uint8_t* pyr = m->mask.d_pyr.as<uint8_t>();
+    HIP_CHECK(hipMemsetAsync(pyr, 0, (size_t)g.frame_bytes + 256, st));
+    HIP_CHECK(hipMemcpy2DAsync(pyr + g.lv[0].ofs, g.lv[0].pitch, mask, stride, w, h, hipMemcpyHostToDevice, st));
+    for (int l = 1; l < g.nlevels; ++l) {
+        if (g.lv[l].w <= 0 || g.lv[l].h <= 0) continue;
+        const int nxq = cdiv(g.lv[l].w, 4);               // (the launch arithmetic of orb_stage1's pyramid loop)
+        const uint32_t magic = nxq > 1 ? (uint32_t)(((1ull << 32) + (uint64_t)nxq - 1) / (uint64_t)nxq) : 0u;
+        resize_kernel<<<dim3(cdiv(nxq * cdiv(g.lv[l].h, RESIZE_ROWS), 256), 1, 1), 256, 0, st>>>(pyr, g.frame_bytes, g.lv[l - 1], g.lv[l],
+                                                                                                 ge.lin_tab.as<uint32_t>(), nxq, magic);
+        check_launch("resize_kernel (frame mask)");
+        mask_threshold_kernel<<<cdiv(g.lv[l].w * g.lv[l].h, MASK_BLOCK), MASK_BLOCK, 0, st>>>(pyr, g.lv[l]);
+        check_launch("mask_threshold_kernel");
+    }
+    HIP_CHECK(hipStreamSynchronize(st));                  // (the caller's mask bytes are copied: they may go)
+    m->mask.set = true; m->mask.w = w; m->mask.h = h;
+}
+
+const uint8_t* frame_mask_for(const slideo_matcher* m, int w, int h) {
+    if (!m->mask.set) return nullptr;
+    if (w != m->mask.w || h != m->mask.h)
+        fail(SLIDEO_ERR_INVALID_ARG, "frame mask: the frames are analysed at %dx%d, the mask is %dx%d (slideo_matcher_set_frame_mask)", w, h,
+             m->mask.w, m->mask.h);
+    return m->mask.d_pyr.as<uint8_t>();
 }
 
 }  // namespace slideo

@@ -325,6 +325,14 @@ public:
     // Frames beyond max_w x max_h are reduced on the GPU before matching (slideo_group_set_working_size; include/slideo_amd.h
     // "Working size").  The reference never reduces a frame: verdicts are then those of the reduced video.  Default: none
     HipImageVideoMatcher& with_working_size(int32_t max_w, int32_t max_h) { work_w_ = max_w; work_h_ = max_h; return *this; }
+    // ORB keypoints of the frames are detected under `mask` (width x height bytes, nonzero = detect here; slideo_group_set_frame_mask,
+    // include/slideo_amd.h "Frame mask"): a speaker inset, a logo or subtitles stay out of the features.  Detection only; the frames'
+    // analysed size must be the mask's.  The reference passes no mask.  Default: none
+    HipImageVideoMatcher& with_frame_mask(std::vector<uint8_t> mask, int32_t width, int32_t height) {
+        if (width < 1 || height < 1 || mask.size() != (size_t)width * (size_t)height) throw std::runtime_error("with_frame_mask: mask is not width x height bytes");
+        mask_ = std::move(mask); mask_w_ = width; mask_h_ = height;
+        return *this;
+    }
     // false: tasks run the stop-and-go pair slideo_group_changed_mask_bgr8 + slideo_group_match_kept_frames in place of the group's
     // gated call (the same timeline; for comparisons).  Default: gated
     HipImageVideoMatcher& with_changed_gate(bool on) { gated_ = on; return *this; }
@@ -345,6 +353,7 @@ public:
             h->check(slideo_group_set_working_size(h->g, work_w_, work_h_));
             h->work_w = work_w_; h->work_h = work_h_;
         }
+        if (!mask_.empty()) h->check(slideo_group_set_frame_mask(h->g, mask_.data(), mask_w_, mask_h_, mask_w_));
         h->check(slideo_group_set_progress(h->g, detail::tramp, &reporter));                         // "Analyzing PDF pages..." protocol, mo/lib.rs:43-58
         const size_t CH = 32 * (size_t)h->n_devices;
         for (size_t i = 0; i < images.size(); i += CH) {
@@ -363,6 +372,8 @@ private:
     bool sift_on_ = false, gated_ = true;
     float sift_ratio_ = 0.f;
     int32_t work_w_ = 0, work_h_ = 0;
+    std::vector<uint8_t> mask_;
+    int32_t mask_w_ = 0, mask_h_ = 0;
     slideo_config cfg_;
     ImageLoader loader_;
 };
