@@ -5,6 +5,8 @@
 use std::os::raw::{c_char, c_void};
 
 pub const SLIDEO_ABI_VERSION: u32 = 7;
+pub const SLIDEO_MASK_DETECT: u32 = 1;
+pub const SLIDEO_MASK_GATE: u32 = 2;
 
 /// slideo_ocv_variants: which restatement of each OpenCV primitive runs.  slideo_config_default fills it; the
 /// application never touches it.
@@ -430,6 +432,19 @@ extern "C" {
         out_capacity: i64,
         lw: *mut i32,
         lh: *mut i32,
+    ) -> i32;
+    // frame mask scope (include/slideo_amd.h "Frame mask scope"): SLIDEO_MASK_DETECT | SLIDEO_MASK_GATE
+    pub fn slideo_matcher_set_frame_mask_scope(m: *mut slideo_matcher, scope: u32) -> i32;
+    pub fn slideo_matcher_frame_mask_scope(m: *const slideo_matcher, scope: *mut u32) -> i32;
+    pub fn slideo_group_set_frame_mask_scope(g: *mut slideo_group, scope: u32) -> i32;
+    pub fn slideo_changed_ssd_threshold_n(changed_similarity: f32, n_pixels: i64) -> i64;
+    pub fn slideo_frame_mask_small(
+        m: *mut slideo_matcher,
+        out: *mut u8,
+        out_capacity: i64,
+        sw: *mut i32,
+        sh: *mut i32,
+        n_valid: *mut i64,
     ) -> i32;
 }
 

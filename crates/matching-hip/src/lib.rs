@@ -72,11 +72,22 @@ pub struct HipImageVideoMatcher {
     /// Some(0.0) keeps the path's own 5 % tolerance vote on the L2 distances (the robust choice on decks whose pages
     /// share a template), Some(r > 0) is Lowe's ratio test.  None (default) = the reference's extractor and matcher.
     pub sift_ratio: Option<f32>,
+    /// Some((mask, width, height)): the frame mask (slideo_group_set_frame_mask), width x height bytes, nonzero = detect
+    /// here; the frames' analysed size must be the mask's.  None (default) = no mask, as the reference.
+    pub frame_mask: Option<(Vec<u8>, i32, i32)>,
+    /// Which stages the frame mask applies to (slideo_group_set_frame_mask_scope): ffi::SLIDEO_MASK_DETECT (default),
+    /// ffi::SLIDEO_MASK_GATE, or both.  With SLIDEO_MASK_GATE the changed-frame gate ignores the masked regions too.
+    pub frame_mask_scope: u32,
 }
 
 impl Default for HipImageVideoMatcher {
     fn default() -> Self {
-        HipImageVideoMatcher { devices: Vec::new(), sift_ratio: None }
+        HipImageVideoMatcher {
+            devices: Vec::new(),
+            sift_ratio: None,
+            frame_mask: None,
+            frame_mask_scope: ffi::SLIDEO_MASK_DETECT,
+        }
     }
 }
 
@@ -103,6 +114,13 @@ impl<'i> ImageVideoMatcher<'i> for HipImageVideoMatcher {
                 let mut sc = std::mem::MaybeUninit::<ffi::slideo_sift_config>::uninit();
                 ffi::slideo_sift_config_default(sc.as_mut_ptr());
                 check(h, ffi::slideo_group_use_sift(h, sc.as_ptr(), ratio));
+            }
+            if self.frame_mask_scope != ffi::SLIDEO_MASK_DETECT {
+                check(h, ffi::slideo_group_set_frame_mask_scope(h, self.frame_mask_scope));
+            }
+            if let Some((mask, w, hh)) = &self.frame_mask {
+                assert_eq!(mask.len(), (*w as usize) * (*hh as usize), "frame_mask is not width x height bytes");
+                check(h, ffi::slideo_group_set_frame_mask(h, mask.as_ptr(), *w, *hh, *w));
             }
         }
         // Page analysis (mo/lib.rs:43-58).  Pages are decoded on the host and handed over in groups, so that a 1000-page

@@ -714,8 +714,10 @@ int32_t     slideo_reduce_bgr8(slideo_matcher* m, const uint8_t* bgr, int32_t wi
  *                  level l is 0 at (x, y) ((int)(pt + 0.5f) is the identity there).  This happens BEFORE retainBest: the level's
  *                  quota is filled from the unmasked candidates, ties kept as without a mask.  Orientation, blur and BRIEF read
  *                  the unmasked image, as in OpenCV.
- * DETECTION ONLY: the small image, the changed-frame flags and similarities, the re-projection similarity and the verdict rule see
- * the whole frame.  (A masked gate SSD / masked re-projection is a possible follow-up, not part of this.)
+ * DETECTION ONLY under the default scope: the small image, the changed-frame flags and similarities, the re-projection similarity
+ * and the verdict rule see the whole frame.  The changed-frame gate can be told to ignore the masked regions too: "Frame mask
+ * scope" below.  Masked re-projection: not built.  The re-projection samples the frame only where the page maps, what an inset
+ * costs there is slide area it hides, which no mask recovers, and reproject_vt_kernel is at its register limit.
  * Pages are never masked, a page of the mask's size included.  A frame call whose analysed size differs from the mask's fails
  * with SLIDEO_ERR_INVALID_ARG, naming both sizes; it is not silently unmasked.  SIFT mode refuses a mask with SLIDEO_ERR_UNSUPPORTED,
  * at slideo_matcher_set_frame_mask and at slideo_matcher_use_sift.  Everything behind ORB is unchanged, so every option is picked
@@ -743,6 +745,54 @@ int32_t     slideo_group_set_frame_mask(slideo_group* g, const uint8_t* mask, in
  * SLIDEO_ERR_INVALID_ARG for a level outside 0 .. nlevels - 1 or a null argument, SLIDEO_ERR_CAPACITY (with *lw, *lh set).
  * The tap slideo_orb_bgr8 honours the mask for an image of the mask's size; the page-side calls and slideo_pyramid_level_bgr8 never do. */
 int32_t     slideo_frame_mask_level(slideo_matcher* m, int32_t level, uint8_t* out, int64_t out_capacity, int32_t* lw, int32_t* lh);
+
+/* ---- Frame mask scope (extension: which stages the frame mask applies to) -------------------------------------------------------
+ * A matcher carries a SCOPE for its frame mask: SLIDEO_MASK_DETECT (the default: the section above, nothing else), SLIDEO_MASK_GATE,
+ * or both.  The scope is the matcher's: it may be set before or after the mask, survives clearing or replacing the mask, and does
+ * nothing while no mask is set.  Without the DETECT bit frame calls run no mask_filter_kernel (a GATE-only mask); the rule that a
+ * frame call at another analysed size than the mask's is an error holds under either bit.
+ * While a mask is set AND the scope has SLIDEO_MASK_GATE, every call that makes changed flags — slideo_changed_mask_bgr8 / _yuv420,
+ * slideo_match_changed_frames_* in every form, their group forms, and what follows slideo_matcher_gate_reset* — compares small images
+ * over the VALID small pixels only:
+ *   validity map   B = the mask binarised (nonzero -> 255) and replicated to three channels; S = to_small_image(B), exactly what a
+ *                  frame of the mask's size gets (the same small_area, ocv.area variant and small_image_kernel).  Small pixel (x, y)
+ *                  is valid iff S[y, x, 0] == 255: every mask pixel it averages is nonzero.  n_valid = the number of valid pixels.
+ *                  Built once, when the second of {mask, GATE scope} is set, on the matcher's stream.  If n_valid == 0 that set call
+ *                  fails with SLIDEO_ERR_INVALID_ARG and the previous mask and scope stay.  slideo_frame_mask_small returns the map.
+ *   similarity     ssd = the sum over the valid pixels' 3 channels of (a - b)^2; the similarity is the mask call's expression with
+ *                  n_valid in place of sw * sh and nothing else changed; changed iff it is < cfg.changed_similarity.  The first
+ *                  frame after the state "none" stays similarity 0.0 and changed.  On the device the decision stays integer:
+ *                  ssd >= slideo_changed_ssd_threshold_n(cfg.changed_similarity, n_valid); the collect-time check of the device's
+ *                  flag against the host expression stays, with n_valid.
+ *   size rule      a call that makes flags fails with SLIDEO_ERR_INVALID_ARG, naming both sizes, if the frames' analysed size is
+ *                  not the mask's — slideo_changed_mask_* included, which under the DETECT-only scope does not look at the mask.
+ * Small images are never masked: the gate state, last_small_out, slideo_matcher_gate_last_small and slideo_matcher_gate_reset's
+ * prev_small are the unmasked small image.  Rules 1 - 6 of "Changed-frame gate" hold unchanged, with "the mask call" read as the
+ * mask call under the same scope, and so does the group's "equal to a single matcher for every member count" rule.  A mask of all
+ * 255 under the GATE scope gives, bit for bit, the results of no mask.  With the default scope no call launches anything it did not
+ * launch before.
+ * Where it runs (csrc/gate.hip.h, csrc/stage_gate.hip): at set time mask_bgr_kernel, the small image, gate_valid_kernel (one byte
+ * weight 0xFF / 0x00 per small-image byte; n_valid by wave ballots and LDS, one store); per call ssd_masked_kernel in place of
+ * ssd_kernel: the same pairs, every image read as aligned dwords whatever its byte alignment (v_alignbyte_b32), weights ANDed in,
+ * the squares as 4 x u8 dot products.  Registers, LDS and measurements: docs/EXTENSIONS.md "Frame mask scope". */
+#define SLIDEO_MASK_DETECT 1u
+#define SLIDEO_MASK_GATE   2u
+/* Idle matcher (SLIDEO_ERR_STATE with units in flight).  scope: a non-empty combination of the two bits; 0 or an unknown bit is
+ * SLIDEO_ERR_INVALID_ARG.  Like slideo_matcher_set_frame_mask it ends the kept frames of an earlier mask call and leaves the gate
+ * state alone. */
+int32_t     slideo_matcher_set_frame_mask_scope(slideo_matcher* m, uint32_t scope);
+/* The matcher's scope (SLIDEO_MASK_DETECT unless set).  SLIDEO_ERR_INVALID_ARG for a null argument. */
+int32_t     slideo_matcher_frame_mask_scope(const slideo_matcher* m, uint32_t* scope);
+/* Forwards to every member (every member idle); ends the group's kept frames and leaves the group's gate state. */
+int32_t     slideo_group_set_frame_mask_scope(slideo_group* g, uint32_t scope);
+/* slideo_changed_ssd_threshold with the similarity normalised over n_pixels pixels: the same bisection over the same expression;
+ * slideo_changed_ssd_threshold(s, w, h) == slideo_changed_ssd_threshold_n(s, (int64_t)w * h).  A pure host function.  -1 for
+ * n_pixels < 1 or > INT32_MAX. */
+int64_t     slideo_changed_ssd_threshold_n(float changed_similarity, int64_t n_pixels);
+/* Tap: the validity map, u8 0 / 255, *sw x *sh (out: stride *sw; may be NULL to ask for the sizes), and *n_valid.  Idle matcher.
+ * SLIDEO_ERR_STATE without a mask or when the scope lacks SLIDEO_MASK_GATE, SLIDEO_ERR_CAPACITY (with the sizes set),
+ * SLIDEO_ERR_INVALID_ARG for a null sw, sh or n_valid. */
+int32_t     slideo_frame_mask_small(slideo_matcher* m, uint8_t* out, int64_t out_capacity, int32_t* sw, int32_t* sh, int64_t* n_valid);
 
 /* ---- Changed-frame gate (MarkSimilarIter, mo/video_capture.rs:86-98, inside the unit pipeline) ---------------------------------
  * slideo_changed_mask_* + slideo_match_kept_frames are a stop-and-go pair: host frames, an idle matcher, the flags made on the host.

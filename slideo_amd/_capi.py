@@ -140,7 +140,13 @@ EXPORTS = [
     "slideo_matcher_gate_reset_from_frame_yuv420_dev", "slideo_group_gate_reset", "slideo_group_gate_last_small",
     "slideo_group_match_changed_frames_bgr8", "slideo_group_match_changed_frames_yuv420",
     "slideo_matcher_set_frame_mask", "slideo_matcher_frame_mask_info", "slideo_group_set_frame_mask", "slideo_frame_mask_level",
+    "slideo_matcher_set_frame_mask_scope", "slideo_matcher_frame_mask_scope", "slideo_group_set_frame_mask_scope",
+    "slideo_changed_ssd_threshold_n", "slideo_frame_mask_small",
 ]
+
+# frame mask scope (include/slideo_amd.h "Frame mask scope")
+MASK_DETECT = 1
+MASK_GATE = 2
 
 _lib = None
 
@@ -202,6 +208,14 @@ def lib():
             L.slideo_matcher_frame_mask_info.argtypes = [vp, vp, vp, vp]
             L.slideo_group_set_frame_mask.argtypes = [vp, vp, i32, i32, i32]
             L.slideo_frame_mask_level.argtypes = [vp, i32, vp, i64, vp, vp]
+        if hasattr(L, "slideo_matcher_set_frame_mask_scope"):
+            vp, u32, i64 = C.c_void_p, C.c_uint32, C.c_int64
+            L.slideo_matcher_set_frame_mask_scope.argtypes = [vp, u32]
+            L.slideo_matcher_frame_mask_scope.argtypes = [vp, vp]
+            L.slideo_group_set_frame_mask_scope.argtypes = [vp, u32]
+            L.slideo_changed_ssd_threshold_n.restype = i64
+            L.slideo_changed_ssd_threshold_n.argtypes = [C.c_float, i64]
+            L.slideo_frame_mask_small.argtypes = [vp, vp, i64, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -348,6 +362,37 @@ class _FrameCalls:
         if mask.ndim != 2 or mask.dtype != np.uint8:
             raise SlideoError(1, "set_frame_mask: expected an (h, w) uint8 mask")
         self._check(getattr(lib(), self._SETS + "set_frame_mask")(self._h, _p(mask), mask.shape[1], mask.shape[0], mask.shape[1]))
+
+    # frame mask scope (include/slideo_amd.h "Frame mask scope"): which stages the frame mask applies to
+    def set_frame_mask_scope(self, scope):
+        """scope: MASK_DETECT (the default), MASK_GATE or both.  Under MASK_GATE the changed-frame flags and similarities ignore the
+        masked regions.  The matcher's own: it survives clearing or replacing the mask.  The matcher must be idle."""
+        self._check(getattr(lib(), self._SETS + "set_frame_mask_scope")(self._h, int(scope)))
+
+    def _mask_owner(self):
+        """The matcher handle the mask's getters read (a group's members agree: member 0)."""
+        return self._h if self._SETS == "slideo_matcher_" else C.c_void_p(lib().slideo_group_member(self._h, 0))
+
+    @property
+    def frame_mask_scope(self):
+        scope = C.c_uint32()
+        rc = lib().slideo_matcher_frame_mask_scope(self._mask_owner(), C.byref(scope))
+        if rc != OK:
+            raise SlideoError(rc, "frame_mask_scope")
+        return scope.value
+
+    def frame_mask_small(self):
+        """The gate's validity map under MASK_GATE: (bool [sh, sw], n_valid)."""
+        h = self._mask_owner()
+        sw, sh, nv = C.c_int32(), C.c_int32(), C.c_int64()
+
+        def check(rc):
+            if rc != OK:
+                raise SlideoError(rc, lib().slideo_last_error(h).decode())
+        check(lib().slideo_frame_mask_small(h, None, C.c_int64(0), C.byref(sw), C.byref(sh), C.byref(nv)))
+        out = np.empty((sh.value, sw.value), np.uint8)
+        check(lib().slideo_frame_mask_small(h, _p(out), C.c_int64(out.size), C.byref(sw), C.byref(sh), C.byref(nv)))
+        return out == 255, int(nv.value)
 
     def _unit_size(self, w, h):
         """The size of the image the pipeline reads for a w x h frame."""
@@ -886,6 +931,15 @@ def changed_ssd_threshold(changed_similarity, small_w, small_h):
     t = int(lib().slideo_changed_ssd_threshold(C.c_float(changed_similarity), int(small_w), int(small_h)))
     if t < 0:
         raise SlideoError(1, "changed_ssd_threshold: bad small-image size %rx%r" % (small_w, small_h))
+    return t
+
+
+def changed_ssd_threshold_n(changed_similarity, n_pixels):
+    """slideo_changed_ssd_threshold_n: the smallest changed SSD when the similarity is normalised over n_pixels pixels (the n_valid
+    of the frame mask's GATE scope)."""
+    t = int(lib().slideo_changed_ssd_threshold_n(C.c_float(changed_similarity), C.c_int64(int(n_pixels))))
+    if t < 0:
+        raise SlideoError(1, "changed_ssd_threshold_n: bad pixel count %r" % (n_pixels,))
     return t
 
 

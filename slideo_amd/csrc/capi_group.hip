@@ -341,6 +341,15 @@ int32_t slideo_group_set_frame_mask(slideo_group* g, const uint8_t* mask, int32_
     GROUP_CATCH(g)
 }
 
+int32_t slideo_group_set_frame_mask_scope(slideo_group* g, uint32_t scope) {
+    if (!g) return SLIDEO_ERR_INVALID_ARG;
+    GROUP_TRY
+    for (slideo_matcher* m : g->members) require_idle(m);
+    for (slideo_matcher* m : g->members) check_member_call(m, slideo_matcher_set_frame_mask_scope(m, scope));
+    g->kept_valid = false;
+    GROUP_CATCH(g)
+}
+
 // Page sets: every member builds the same set from the same deck (ids are handed out in the same order: they agree)
 int32_t slideo_group_create_page_set(slideo_group* g, int32_t n_pages, const int32_t* pages, int32_t* set_out) {
     if (!g) return SLIDEO_ERR_INVALID_ARG;

@@ -441,6 +441,8 @@ void changed_mask_impl(slideo_matcher* m, int n_frames, FrameSrc src, const uint
     if (n_frames < 0 || (n_frames > 0 && (!src.p || !changed_out))) fail(SLIDEO_ERR_INVALID_ARG, "null frames/changed");
     validate_frames(src);
     apply_working_size(m, src);
+    // (under the frame mask's GATE scope the flags are the mask's: frames of another analysed size are an error, before anything is touched)
+    if (m->mask.set && (m->mask_scope & SLIDEO_MASK_GATE)) { int npx_ = 0; (void)gate_map_for(m, src.unit_w(), src.unit_h(), m->gate_map.sw, m->gate_map.sh, &npx_); }
     if (n_frames == 0) return;
     HIP_CHECK(hipSetDevice(m->device));
     require_idle(m);
@@ -451,14 +453,16 @@ void changed_mask_impl(slideo_matcher* m, int n_frames, FrameSrc src, const uint
     m->kept = slideo_matcher::Kept{true, n_frames, f.w, f.h, f.stride};      // stays in slot 0's staging buffer: slideo_match_kept_frames
     run_small(m, f, n_frames, sw, sh, st);
     const size_t sb = (size_t)sw * sh * 3;
+    int npx = 0;
+    const uint8_t* weights = gate_map_for(m, f.w, f.h, sw, sh, &npx);
     DevBuf& prev = m->d_prev_small;
     prev.reserve(sb);
     if (prev_small) HIP_CHECK(hipMemcpyAsync(prev.p, prev_small, sb, hipMemcpyHostToDevice, st));
     m->d_ssd.reserve((size_t)n_frames * 8);
     // pair i: (small[i-1], small[i]); pair 0 uses prev
-    if (prev_small) launch_ssd(prev.as<uint8_t>(), 0, m->d_small.as<uint8_t>(), 0, (int64_t)sb, m->d_ssd.as<unsigned long long>(), 1, st);
+    if (prev_small) launch_gate_ssd(weights, prev.as<uint8_t>(), 0, m->d_small.as<uint8_t>(), 0, (int64_t)sb, m->d_ssd.as<unsigned long long>(), 1, st);
     if (n_frames > 1)
-        launch_ssd(m->d_small.as<uint8_t>(), (int64_t)sb, m->d_small.as<uint8_t>() + sb, (int64_t)sb, (int64_t)sb, m->d_ssd.as<unsigned long long>() + 1, n_frames - 1, st);
+        launch_gate_ssd(weights, m->d_small.as<uint8_t>(), (int64_t)sb, m->d_small.as<uint8_t>() + sb, (int64_t)sb, (int64_t)sb, m->d_ssd.as<unsigned long long>() + 1, n_frames - 1, st);
     std::vector<unsigned long long> ssd(n_frames, 0);
     HIP_CHECK(hipMemcpyAsync(ssd.data(), m->d_ssd.p, (size_t)n_frames * 8, hipMemcpyDeviceToHost, st));
     if (last_small_out)
@@ -466,7 +470,7 @@ void changed_mask_impl(slideo_matcher* m, int n_frames, FrameSrc src, const uint
     HIP_CHECK(hipStreamSynchronize(st));
     for (int i = 0; i < n_frames; ++i) {
         float sim = 0.0f;   // video_capture.rs:92: the first frame compares as 0.0
-        if (i > 0 || prev_small) sim = changed_similarity(ssd[i], sw, sh);
+        if (i > 0 || prev_small) sim = changed_similarity(ssd[i], npx);
         changed_out[i] = sim < m->cfg.changed_similarity ? 1 : 0;
         if (similarity_out) similarity_out[i] = sim;
     }
@@ -717,6 +721,11 @@ int32_t slideo_matcher_set_working_size(slideo_matcher* m, int32_t max_w, int32_
 
 // ---- frame mask (include/slideo_amd.h "Frame mask") -------------------------------------------------------------------------
 
+static void gate_map_swap(slideo_matcher::GateMap& a, slideo_matcher::GateMap& b) {
+    std::swap(a.on, b.on); std::swap(a.sw, b.sw); std::swap(a.sh, b.sh); std::swap(a.n_valid, b.n_valid);
+    std::swap(a.d_w.p, b.d_w.p); std::swap(a.d_w.cap, b.d_w.cap);
+}
+
 int32_t slideo_matcher_set_frame_mask(slideo_matcher* m, const uint8_t* mask, int32_t width, int32_t height, int32_t stride_bytes) {
     if (!m) return SLIDEO_ERR_INVALID_ARG;
     API_TRY
@@ -727,9 +736,48 @@ int32_t slideo_matcher_set_frame_mask(slideo_matcher* m, const uint8_t* mask, in
     }
     HIP_CHECK(hipSetDevice(m->device));
     require_idle(m);
+    // under the GATE scope the new mask's validity map comes first: a mask it refuses leaves the mask before in force
+    slideo_matcher::GateMap map;
+    if (mask && (m->mask_scope & SLIDEO_MASK_GATE)) {
+        (void)geom_for(m, width, height);                              // (the size rules of the mask itself, before any work)
+        DevBuf d_mask;
+        d_mask.reserve((size_t)width * height);
+        HIP_CHECK(hipMemcpy2DAsync(d_mask.p, (size_t)width, mask, (size_t)stride_bytes, (size_t)width, (size_t)height, hipMemcpyHostToDevice, m->stream));
+        gate_map_build(m, d_mask.as<uint8_t>(), width, width, height, map);      // (synchronises the stream: d_mask may go)
+    }
     m->kept.valid = false;          // (the kept frames of an earlier mask call end, as under slideo_matcher_set_working_size)
+    m->gate_map.on = false;
     frame_mask_set(m, mask, width, height, stride_bytes);
+    if (map.on) gate_map_swap(m->gate_map, map);
     API_CATCH(m)
+}
+
+// ---- frame mask scope (include/slideo_amd.h "Frame mask scope") -------------------------------------------------------------
+
+int32_t slideo_matcher_set_frame_mask_scope(slideo_matcher* m, uint32_t scope) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    if (scope == 0 || (scope & ~(SLIDEO_MASK_DETECT | SLIDEO_MASK_GATE)))
+        fail(SLIDEO_ERR_INVALID_ARG, "frame mask scope %u: a non-empty combination of SLIDEO_MASK_DETECT (1) and SLIDEO_MASK_GATE (2)", scope);
+    HIP_CHECK(hipSetDevice(m->device));
+    require_idle(m);
+    if ((scope & SLIDEO_MASK_GATE) && m->mask.set && !m->gate_map.on) {
+        // the second of {mask, GATE scope}: the map from the mask as given, level 0 of its pyramid
+        const LevelGeom& L0 = geom_for(m, m->mask.w, m->mask.h).g.lv[0];
+        slideo_matcher::GateMap map;
+        gate_map_build(m, m->mask.d_pyr.as<uint8_t>() + L0.ofs, L0.pitch, m->mask.w, m->mask.h, map);
+        gate_map_swap(m->gate_map, map);
+    }
+    if (!(scope & SLIDEO_MASK_GATE)) m->gate_map.on = false;
+    m->mask_scope = scope;
+    m->kept.valid = false;          // (as slideo_matcher_set_frame_mask; the gate state stays)
+    API_CATCH(m)
+}
+
+int32_t slideo_matcher_frame_mask_scope(const slideo_matcher* m, uint32_t* scope) {
+    if (!m || !scope) return SLIDEO_ERR_INVALID_ARG;
+    *scope = m->mask_scope;
+    return SLIDEO_OK;
 }
 
 int32_t slideo_matcher_frame_mask_info(const slideo_matcher* m, int32_t* width, int32_t* height, int32_t* is_set) {

@@ -74,6 +74,28 @@ int32_t slideo_frame_mask_level(slideo_matcher* m, int32_t level, uint8_t* out, 
     API_CATCH(m)
 }
 
+int32_t slideo_frame_mask_small(slideo_matcher* m, uint8_t* out, int64_t out_capacity, int32_t* sw, int32_t* sh, int64_t* n_valid) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    if (!sw || !sh || !n_valid) fail(SLIDEO_ERR_INVALID_ARG, "null sw/sh/n_valid");
+    if (!m->mask.set) fail(SLIDEO_ERR_STATE, "no frame mask is set");
+    if (!(m->mask_scope & SLIDEO_MASK_GATE) || !m->gate_map.on)
+        fail(SLIDEO_ERR_STATE, "the frame mask's scope lacks SLIDEO_MASK_GATE: there is no validity map (slideo_matcher_set_frame_mask_scope)");
+    require_idle(m);
+    const slideo_matcher::GateMap& g = m->gate_map;
+    *sw = g.sw; *sh = g.sh; *n_valid = g.n_valid;
+    const int64_t npx = (int64_t)g.sw * g.sh;
+    if (out && npx > out_capacity) fail(SLIDEO_ERR_CAPACITY, "the validity map needs %lld bytes", (long long)npx);
+    if (out) {
+        HIP_CHECK(hipSetDevice(m->device));
+        std::vector<uint8_t> w((size_t)npx * 3);
+        HIP_CHECK(hipMemcpyAsync(w.data(), g.d_w.p, w.size(), hipMemcpyDeviceToHost, m->stream));
+        HIP_CHECK(hipStreamSynchronize(m->stream));
+        for (int64_t i = 0; i < npx; ++i) out[i] = w[(size_t)i * 3];      // (a pixel's three weight bytes are equal)
+    }
+    API_CATCH(m)
+}
+
 int32_t slideo_small_image_bgr8(slideo_matcher* m, const uint8_t* bgr, int32_t width, int32_t height, int32_t stride_bytes,
                                 uint8_t* out, int64_t out_capacity, int32_t* sw_out, int32_t* sh_out) {
     if (!m) return SLIDEO_ERR_INVALID_ARG;

@@ -160,6 +160,7 @@ struct Slot {
         bool on = false;                      // the unit in flight is gated: slideo_match_changed_frames_collect collects it
         int n = 0, k = 0;                     // frames submitted, frames changed (S.n = k: what the pipeline ran for)
         int sw = 0, sh = 0;
+        int npx = 0;                          // the pixels the similarity is normalised over: sw * sh, the gate map's n_valid under one
         bool force0 = false;                  // no gate state at submission: frame 0 is changed, similarity 0.0
     } gate;
     // unit in flight
@@ -238,6 +239,11 @@ struct slideo_matcher {
     // frame mask (slideo_matcher_set_frame_mask): the mask pyramid of a w x h mask, one frame in the level layout of the w x h
     // image pyramid (stage_orb.hip frame_mask_set); frames of that analysed size keep only the FAST candidates it allows
     struct FrameMask { bool set = false; int w = 0, h = 0; slideo::DevBuf d_pyr; } mask;
+    // frame mask scope (slideo_matcher_set_frame_mask_scope): SLIDEO_MASK_DETECT | SLIDEO_MASK_GATE; the matcher's, whatever
+    // happens to the mask.  While a mask is set and the scope has GATE, the gate's validity map (stage_gate.hip gate_map_build):
+    // one weight byte (0xFF valid, 0x00) per byte of the sw x sh small image of frames of the mask's size, n_valid valid pixels
+    uint32_t mask_scope = SLIDEO_MASK_DETECT;
+    struct GateMap { bool on = false; int sw = 0, sh = 0; int64_t n_valid = 0; slideo::DevBuf d_w; } gate_map;
 
     // INTER_AREA size classes
     std::vector<slideo::AreaGeom> area_geoms;
@@ -366,11 +372,13 @@ void changed_mask_impl(slideo_matcher* m, int n, FrameSrc src, const uint8_t* pr
                        float* similarity_out);
 // the similarity MarkSimilarIter compares (video_capture.rs:86-98) from the integer SSD of two sw x sh small images: the ONE host
 // expression behind the mask calls' flags, the gate's similarities and slideo_changed_ssd_threshold
-inline float changed_similarity(unsigned long long ssd, int sw, int sh) {
+// (n pixels: sw * sh, or the n_valid of the frame mask's GATE scope)
+inline float changed_similarity(unsigned long long ssd, int n) {
     double e = std::sqrt((double)ssd);
-    float max_error = std::sqrt((255.0f * 255.0f * 3.0f) * (float)(sw * sh));
+    float max_error = std::sqrt((255.0f * 255.0f * 3.0f) * (float)n);
     return 1.0f - (float)e / max_error;
 }
+inline float changed_similarity(unsigned long long ssd, int sw, int sh) { return changed_similarity(ssd, sw * sh); }
 // S's staging buffer with room for `bytes` (ends the kept frames of a mask call)
 uint8_t* stage_for_upload(slideo_matcher* m, Slot& S, size_t bytes);
 // ProcessedImage::compute over n host pages (mo/lib.rs:92-131) WITHOUT appending them: the analysed pages, in order, into `out`
@@ -459,6 +467,19 @@ void gate_prime(slideo_matcher* m, FrameSrc src, hipStream_t user_stream);
 // count, 0: no pipeline ran); its collect: flags and similarities of all n frames, verdicts of the changed ones
 void gate_unit_submit(slideo_matcher* m, Slot& S, const FrameSrc& src, int first, int n, hipStream_t cs);
 void gate_unit_collect(slideo_matcher* m, Slot& S, uint8_t* changed_out, float* similarity_out, slideo_verdict* verdicts_out);
+
+// Frame mask scope (include/slideo_amd.h "Frame mask scope").  gate_map_build: the validity map of the w x h mask at dmask (DEVICE
+// memory, rows `pitch` apart) into `out`, on m->stream (SLIDEO_ERR_INVALID_ARG when no small pixel is valid; out is then unchanged
+// apart from its buffer).  gate_map_for: the weights a call that makes changed flags from frames of analysed size w x h sums its
+// SSDs under, *npx the pixels its similarities are normalised over — nullptr and sw * sh unless a mask is set under the GATE scope;
+// SLIDEO_ERR_INVALID_ARG at another size than the mask's.
+void gate_map_build(slideo_matcher* m, const uint8_t* dmask, int pitch, int w, int h, slideo_matcher::GateMap& out);
+const uint8_t* gate_map_for(const slideo_matcher* m, int w, int h, int sw, int sh, int* npx);
+// launch_ssd, under `weights` (gate_map_for) when not null
+void launch_gate_ssd(const uint8_t* weights, const uint8_t* a, int64_t a_stride, const uint8_t* b, int64_t b_stride, int64_t bytes,
+                     unsigned long long* ssd, int n, hipStream_t st);
+// the smallest SSD that counts as changed when the similarity is normalised over n pixels (slideo_changed_ssd_threshold_n)
+int64_t gate_ssd_threshold(float changed_similarity_, int64_t n);
 
 // ---- stage_sift.hip -------------------------------------------------------------------------------
 void sift_check_cfg(const slideo_sift_config* sc, int w, int h);

@@ -14,11 +14,9 @@ void gate_release(slideo_matcher* m) {
     for (Slot& S : m->slots) if (S.ev_gate) { (void)hipEventDestroy(S.ev_gate); S.ev_gate = nullptr; }
 }
 
-namespace {
-
-int64_t ssd_threshold(float changed_similarity_, int sw, int sh) {
-    const int64_t max_ssd = (int64_t)255 * 255 * 3 * sw * sh;
-    auto changed = [&](int64_t s) { return changed_similarity((unsigned long long)s, sw, sh) < changed_similarity_; };
+int64_t gate_ssd_threshold(float changed_similarity_, int64_t n) {
+    const int64_t max_ssd = (int64_t)255 * 255 * 3 * n;
+    auto changed = [&](int64_t s) { return changed_similarity((unsigned long long)s, (int)n) < changed_similarity_; };
     if (!changed(max_ssd)) return INT64_MAX;
     if (changed(0)) return 0;
     int64_t lo = 0, hi = max_ssd;                   // changed(lo) false, changed(hi) true; the expression is monotone in the SSD
@@ -29,7 +27,51 @@ int64_t ssd_threshold(float changed_similarity_, int sw, int sh) {
     return hi;
 }
 
-}  // namespace
+// ---- frame mask scope (include/slideo_amd.h "Frame mask scope") ----------------------------------------------------------------
+// The validity map: B = the mask binarised and replicated to three channels (mask_bgr_kernel), S = to_small_image(B) through the
+// run_small_into every frame of that size goes through, then gate_valid_kernel: weights and n_valid.  Set time; the matcher is idle.
+void gate_map_build(slideo_matcher* m, const uint8_t* dmask, int pitch, int w, int h, slideo_matcher::GateMap& out) {
+    hipStream_t st = m->stream;
+    DevBuf d_bgr, d_s, d_n;
+    d_bgr.reserve((size_t)w * h * 3);
+    mask_bgr_kernel<<<(unsigned)cdiv64((int64_t)w * h, GATE_BLOCK), GATE_BLOCK, 0, st>>>(dmask, pitch, w, h, d_bgr.as<uint8_t>());
+    check_launch("mask_bgr_kernel");
+    int sw = 0, sh = 0;
+    run_small_into(m, DevFrames{d_bgr.as<uint8_t>(), w, h, w * 3, (int64_t)w * h * 3}, 1, d_s, sw, sh, st);
+    const size_t sb = (size_t)sw * sh * 3;
+    out.on = false;
+    out.d_w.reserve(sb + 4);
+    d_n.reserve(8);
+    gate_valid_kernel<<<1, GATE_BLOCK, 0, st>>>(d_s.as<uint8_t>(), sw * sh, out.d_w.as<uint8_t>(), d_n.as<long long>());
+    check_launch("gate_valid_kernel");
+    long long nv = -1;
+    HIP_CHECK(hipMemcpyAsync(&nv, d_n.p, 8, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    if (nv < 0 || nv > (long long)sw * sh) fail(SLIDEO_ERR_HIP, "internal: %lld valid pixels of a %dx%d small image", nv, sw, sh);
+    if (nv == 0)
+        fail(SLIDEO_ERR_INVALID_ARG, "frame mask scope: no pixel of the %dx%d small image of a %dx%d frame is valid under this mask (a small "
+             "pixel is valid only where every mask pixel it averages is nonzero): the gate would have nothing to compare", sw, sh, w, h);
+    out.on = true; out.sw = sw; out.sh = sh; out.n_valid = nv;
+}
+
+const uint8_t* gate_map_for(const slideo_matcher* m, int w, int h, int sw, int sh, int* npx) {
+    *npx = sw * sh;
+    if (!m->mask.set || !(m->mask_scope & SLIDEO_MASK_GATE)) return nullptr;
+    if (w != m->mask.w || h != m->mask.h)
+        fail(SLIDEO_ERR_INVALID_ARG, "frame mask scope: the frames are analysed at %dx%d, the mask the gate ignores regions under is %dx%d "
+             "(slideo_matcher_set_frame_mask)", w, h, m->mask.w, m->mask.h);
+    const slideo_matcher::GateMap& g = m->gate_map;
+    if (!g.on || g.sw != sw || g.sh != sh) fail(SLIDEO_ERR_HIP, "internal: the gate's validity map is %dx%d (%d), the small images are %dx%d", g.sw, g.sh, (int)g.on, sw, sh);
+    *npx = (int)g.n_valid;
+    return g.d_w.as<uint8_t>();
+}
+
+void launch_gate_ssd(const uint8_t* weights, const uint8_t* a, int64_t a_stride, const uint8_t* b, int64_t b_stride, int64_t bytes,
+                     unsigned long long* ssd, int n, hipStream_t st) {
+    if (!weights) { launch_ssd(a, a_stride, b, b_stride, bytes, ssd, n, st); return; }
+    ssd_masked_kernel<<<n, 256, 0, st>>>(a, a_stride, b, b_stride, bytes, weights, ssd);
+    check_launch("ssd_masked_kernel");
+}
 
 // The frames of a gated call against the gate state: one size and one format family since the last reset.  Nothing is changed here.
 void gate_check(const slideo_matcher* m, const FrameSrc& src) { gate_check(m->gate, m->cfg.small_area, src); }
@@ -81,6 +123,8 @@ void gate_unit_submit(slideo_matcher* m, Slot& S, const FrameSrc& src, int first
     run_small_into(m, all, n, S.d_gsmall, sw, sh, st);
     const int64_t sb = (int64_t)sw * sh * 3;
     const uint8_t* small = S.d_gsmall.as<uint8_t>();
+    int npx = 0;
+    const uint8_t* weights = gate_map_for(m, all.w, all.h, sw, sh, &npx);      // (validate_frames held the frames to the mask's size)
     S.d_gate.reserve((size_t)n * 13 + 16);
     unsigned long long* ssd = S.d_gate.as<unsigned long long>();
     int32_t* idx = reinterpret_cast<int32_t*>(S.d_gate.as<uint8_t>() + (size_t)n * 8);
@@ -90,16 +134,16 @@ void gate_unit_submit(slideo_matcher* m, Slot& S, const FrameSrc& src, int first
     const bool force0 = !m->gate.has;
     m->d_gate_small.reserve((size_t)sb);            // (grows only from the state "none": no gated unit is reading it)
     // pair i: (small[i - 1], small[i]); pair 0: (gate state, small[0]), behind the previous gated unit's write of the state
-    if (n > 1) launch_ssd(small, sb, small + sb, sb, sb, ssd + 1, n - 1, st);
+    if (n > 1) launch_gate_ssd(weights, small, sb, small + sb, sb, sb, ssd + 1, n - 1, st);
     if (m->last_gate_ev && m->last_gate_ev != S.ev_gate) HIP_CHECK(hipStreamWaitEvent(st, m->last_gate_ev, 0));
-    if (!force0) launch_ssd(m->d_gate_small.as<uint8_t>(), 0, small, 0, sb, ssd, 1, st);
+    if (!force0) launch_gate_ssd(weights, m->d_gate_small.as<uint8_t>(), 0, small, 0, sb, ssd, 1, st);
     HIP_CHECK(hipMemcpyAsync(m->d_gate_small.p, small + sb * (n - 1), (size_t)sb, hipMemcpyDeviceToDevice, st));
     HIP_CHECK(hipEventRecord(S.ev_gate, st));
     m->last_gate_ev = S.ev_gate;
     slideo_matcher::GateState& g = m->gate;
     g.has = true; g.seen = true; g.w = src.w; g.h = src.h; g.yuv = src.yuv != nullptr; g.sw = sw; g.sh = sh;
 
-    const long long thr = ssd_threshold(m->cfg.changed_similarity, sw, sh);
+    const long long thr = gate_ssd_threshold(m->cfg.changed_similarity, npx);
     gate_kernel<<<1, GATE_BLOCK, 0, st>>>(ssd, n, thr, force0 ? 1 : 0, flags, idx, count, S.h_gate.as<uint8_t>());
     check_launch("gate_kernel");
     HIP_CHECK(hipStreamSynchronize(st));
@@ -107,7 +151,7 @@ void gate_unit_submit(slideo_matcher* m, Slot& S, const FrameSrc& src, int first
     if (rec.n != (uint32_t)n || rec.count > (uint32_t)n) fail(SLIDEO_ERR_HIP, "internal: gate record %u of %u for a unit of %d", rec.count, rec.n, n);
     const int k = (int)rec.count;
     Slot::GateUnit gu;
-    gu.on = true; gu.n = n; gu.k = k; gu.sw = sw; gu.sh = sh; gu.force0 = force0;
+    gu.on = true; gu.n = n; gu.k = k; gu.sw = sw; gu.sh = sh; gu.npx = npx; gu.force0 = force0;
     if (k == 0) {                                   // no frame changed: no pipeline; the collect returns the flags at once
         S.busy = true; S.n = 0; S.u_async = false; S.timed = false;
         S.gate = gu;
@@ -144,7 +188,7 @@ void gate_unit_collect(slideo_matcher* m, Slot& S, uint8_t* changed_out, float* 
     for (int i = 0; i < g.n; ++i) {
         unsigned long long s;
         std::memcpy(&s, rec + gate_rec_ssd_ofs() + (size_t)i * 8, 8);
-        const float sim = (i == 0 && g.force0) ? 0.0f : changed_similarity(s, g.sw, g.sh);      // video_capture.rs:92
+        const float sim = (i == 0 && g.force0) ? 0.0f : changed_similarity(s, g.npx);      // video_capture.rs:92
         if ((sim < m->cfg.changed_similarity) != (flag[i] != 0))
             fail(SLIDEO_ERR_HIP, "internal: the gate's flag of frame %d (%d, SSD %llu) is not the host expression's", i, (int)flag[i], s);
         changed_out[i] = flag[i];
@@ -160,7 +204,12 @@ extern "C" {
 
 int64_t slideo_changed_ssd_threshold(float changed_similarity, int32_t small_w, int32_t small_h) {
     if (small_w < 1 || small_h < 1 || (int64_t)small_w * small_h > INT32_MAX) return -1;
-    return ssd_threshold(changed_similarity, small_w, small_h);
+    return gate_ssd_threshold(changed_similarity, (int64_t)small_w * small_h);
+}
+
+int64_t slideo_changed_ssd_threshold_n(float changed_similarity, int64_t n_pixels) {
+    if (n_pixels < 1 || n_pixels > INT32_MAX) return -1;
+    return gate_ssd_threshold(changed_similarity, n_pixels);
 }
 
 int32_t slideo_matcher_gate_reset(slideo_matcher* m, const uint8_t* prev_small, int32_t small_w, int32_t small_h) {

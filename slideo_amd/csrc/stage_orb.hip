@@ -309,6 +309,7 @@ const uint8_t* frame_mask_for(const slideo_matcher* m, int w, int h) {
     if (w != m->mask.w || h != m->mask.h)
         fail(SLIDEO_ERR_INVALID_ARG, "frame mask: the frames are analysed at %dx%d, the mask is %dx%d (slideo_matcher_set_frame_mask)", w, h,
              m->mask.w, m->mask.h);
+    if (!(m->mask_scope & SLIDEO_MASK_DETECT)) return nullptr;       // (a GATE-only mask: the size rule above, no filter)
     return m->mask.d_pyr.as<uint8_t>();
 }
 

@@ -333,6 +333,10 @@ public:
         mask_ = std::move(mask); mask_w_ = width; mask_h_ = height;
         return *this;
     }
+    // Which stages the frame mask applies to: SLIDEO_MASK_DETECT (default), SLIDEO_MASK_GATE or both (slideo_group_set_frame_mask_scope,
+    // include/slideo_amd.h "Frame mask scope").  With SLIDEO_MASK_GATE the changed-frame gate ignores the masked regions too: an
+    // inset that moves on every frame no longer flags every held slide as changed
+    HipImageVideoMatcher& with_frame_mask_scope(uint32_t scope) { mask_scope_ = scope; return *this; }
     // false: tasks run the stop-and-go pair slideo_group_changed_mask_bgr8 + slideo_group_match_kept_frames in place of the group's
     // gated call (the same timeline; for comparisons).  Default: gated
     HipImageVideoMatcher& with_changed_gate(bool on) { gated_ = on; return *this; }
@@ -353,6 +357,7 @@ public:
             h->check(slideo_group_set_working_size(h->g, work_w_, work_h_));
             h->work_w = work_w_; h->work_h = work_h_;
         }
+        if (mask_scope_ != SLIDEO_MASK_DETECT) h->check(slideo_group_set_frame_mask_scope(h->g, mask_scope_));
         if (!mask_.empty()) h->check(slideo_group_set_frame_mask(h->g, mask_.data(), mask_w_, mask_h_, mask_w_));
         h->check(slideo_group_set_progress(h->g, detail::tramp, &reporter));                         // "Analyzing PDF pages..." protocol, mo/lib.rs:43-58
         const size_t CH = 32 * (size_t)h->n_devices;
@@ -374,6 +379,7 @@ private:
     int32_t work_w_ = 0, work_h_ = 0;
     std::vector<uint8_t> mask_;
     int32_t mask_w_ = 0, mask_h_ = 0;
+    uint32_t mask_scope_ = SLIDEO_MASK_DETECT;
     slideo_config cfg_;
     ImageLoader loader_;
 };

@@ -296,7 +296,7 @@ class HipVideoMatcher:
 class HipImageVideoMatcher:
     """Drop-in for OpenCVImageVideoMatcher (lib.rs:34-73) behind matching::ImageVideoMatcher."""
 
-    def __init__(self, cfg=None, device=None, sift=None, devices=None, working_size=None, frame_mask=None):
+    def __init__(self, cfg=None, device=None, sift=None, devices=None, working_size=None, frame_mask=None, frame_mask_scope=None):
         """devices: HIP ordinals, one matcher each behind one slideo_group (the reference fans out over the whole machine, the
         global rayon pool of lib.rs:45,174); None = every gfx950 device of the node; `device` = d is short for devices = [d].
         sift = (slideo_sift_config, ratio): the north-star's SIFT + L2 front end instead of the reference's ORB + Hamming
@@ -305,10 +305,14 @@ class HipImageVideoMatcher:
         the reference never reduces a frame: verdicts are then those of the reduced video); None = frames as they arrive.
         frame_mask = uint8 [h, w], nonzero = detect here: ORB keypoints of the frames are detected under it (slideo_group_set_frame_mask;
         a speaker inset, a logo or subtitles stay out of the features; detection only; the frames' analysed size must be the
-        mask's; the reference passes no mask); None = no mask."""
+        mask's; the reference passes no mask); None = no mask.
+        frame_mask_scope = _capi.MASK_DETECT | _capi.MASK_GATE bits (slideo_group_set_frame_mask_scope): with MASK_GATE the
+        changed-frame gate ignores the masked regions too, so that an inset which moves on every frame does not flag every held
+        slide as changed; None = the default, MASK_DETECT."""
         self._cfg, self._sift = cfg, sift
         self._working_size = working_size
         self._frame_mask = frame_mask
+        self._frame_mask_scope = frame_mask_scope
         self._devices = [device] if device is not None else devices
 
     def create_video_matcher(self, images, progress_reporter: ProgressReporter) -> HipVideoMatcher:
@@ -319,6 +323,8 @@ class HipImageVideoMatcher:
             m.use_sift(*self._sift)
         if self._working_size is not None:
             m.set_working_size(*self._working_size)
+        if self._frame_mask_scope is not None:
+            m.set_frame_mask_scope(self._frame_mask_scope)
         if self._frame_mask is not None:
             m.set_frame_mask(self._frame_mask)
         m.set_progress(progress_reporter.report)        # "Analyzing PDF pages..." protocol, lib.rs:43-58
