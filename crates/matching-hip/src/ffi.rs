@@ -446,6 +446,19 @@ extern "C" {
         sh: *mut i32,
         n_valid: *mut i64,
     ) -> i32;
+    // direct page look-up (include/slideo_amd.h "Direct page look-up")
+    pub fn slideo_matcher_set_direct_similarity(m: *mut slideo_matcher, t: f32) -> i32;
+    pub fn slideo_matcher_direct_similarity(m: *const slideo_matcher, t: *mut f32) -> i32;
+    pub fn slideo_group_set_direct_similarity(g: *mut slideo_group, t: f32) -> i32;
+    pub fn slideo_direct_ssd_threshold(t: f32, n_pixels: i64) -> i64;
+    pub fn slideo_page_small_ssd(
+        m: *mut slideo_matcher,
+        small: *const u8,
+        n: i32,
+        sw: i32,
+        sh: i32,
+        ssd_out: *mut u64,
+    ) -> i32;
 }
 
 /// The struct layouts above are only valid for one ABI version of the library.

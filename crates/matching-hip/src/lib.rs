@@ -78,6 +78,10 @@ pub struct HipImageVideoMatcher {
     /// Which stages the frame mask applies to (slideo_group_set_frame_mask_scope): ffi::SLIDEO_MASK_DETECT (default),
     /// ffi::SLIDEO_MASK_GATE, or both.  With SLIDEO_MASK_GATE the changed-frame gate ignores the masked regions too.
     pub frame_mask_scope: u32,
+    /// The direct page look-up (slideo_group_set_direct_similarity): t in (0, 1]; a changed frame whose small image is at
+    /// least that similar to a page's is resolved to that page without ORB, search or verify (full-screen slide frames of a
+    /// screen recording; the reference never decides without keypoints).  Not together with SLIDEO_MASK_GATE.  0.0 (default) = off.
+    pub direct_similarity: f32,
 }
 
 impl Default for HipImageVideoMatcher {
@@ -87,6 +91,7 @@ impl Default for HipImageVideoMatcher {
             sift_ratio: None,
             frame_mask: None,
             frame_mask_scope: ffi::SLIDEO_MASK_DETECT,
+            direct_similarity: 0.0,
         }
     }
 }
@@ -121,6 +126,9 @@ impl<'i> ImageVideoMatcher<'i> for HipImageVideoMatcher {
             if let Some((mask, w, hh)) = &self.frame_mask {
                 assert_eq!(mask.len(), (*w as usize) * (*hh as usize), "frame_mask is not width x height bytes");
                 check(h, ffi::slideo_group_set_frame_mask(h, mask.as_ptr(), *w, *hh, *w));
+            }
+            if self.direct_similarity != 0.0 {
+                check(h, ffi::slideo_group_set_direct_similarity(h, self.direct_similarity));
             }
         }
         // Page analysis (mo/lib.rs:43-58).  Pages are decoded on the host and handed over in groups, so that a 1000-page

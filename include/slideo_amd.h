@@ -898,6 +898,60 @@ int32_t     slideo_group_match_changed_frames_yuv420(slideo_group* g, int32_t n_
                                                      const slideo_yuv420_layout* layout, int64_t frame_stride_bytes, uint8_t* changed_out,
                                                      float* similarity_out, slideo_verdict* verdicts_out);
 
+/* ---- Direct page look-up (extension: the reference never decides without keypoints) ---------------------------------------------
+ * In a screen recording the frame IS the slide, full screen, plus codec noise.  The reference's final score for a candidate is
+ * compute_similarity(to_small(warp(frame)), page.small); for such a frame the warp is the identity up to scale, so
+ * compute_similarity(to_small(frame), page.small) is the same quantity without keypoints, search or RANSAC.
+ * A matcher carries a DIRECT SIMILARITY t.  0 means off and is the default; valid values are 0 < t <= 1.  While t > 0, in every
+ * GATED frame call (slideo_match_changed_frames_* in every form: host or device frames, BGR or 4:2:0, synchronous or submit /
+ * collect, and slideo_group_match_changed_frames_*), for a frame i whose flag is changed:
+ *   eligible pages   the pages of the selected page set (set 0 = the deck) whose small size (sw_p, sh_p) equals the frame's (sw, sh);
+ *   distance         ssd_i(p) = the sum over all 3 sw sh bytes of (small_i - page_small_p)^2, in integers;
+ *   best page        best_i = the smallest ssd_i(p) over the eligible pages, page_i = the lowest deck page index that attains it;
+ *   similarity       s_i = the mask call's host expression 1 - (float)sqrt((double)best_i) / max_error over sw sh pixels
+ *                    (compute_similarity, image_utils.rs:22-27);
+ *   direct verdict   if there is an eligible page and s_i >= t, frame i is DIRECT: its verdict is {page_i, s_i, inliers 0,
+ *                    n_keypoints 0}, and it does NOT go through ORB, search or verify.  A direct verdict is recognisable as
+ *                    page_idx >= 0 && inliers == 0: the normal path never produces that (a verdict needs a rating above 50).
+ * Every other changed frame gets exactly what it gets today, bit for bit, verdict and trace; an unchanged frame stays {-1, 0, 0, 0}
+ * and is never looked up; flags, similarities, the gate state and slideo_matcher_gate_last_small do not depend on t.
+ * slideo_last_frame_candidates(k) (and the group's form) is the trace of the k-th frame THAT WENT THROUGH THE PIPELINE, i.e. changed
+ * and not direct; with t = 0 that is rule 3's k-th changed frame.  Under a working size the small image is the reduced frame's.
+ * SIFT mode, matcher 1, verify_model 1 and ratio_test need nothing: the look-up sits in front of the unit pipeline.  The group
+ * equals a single matcher for every member count, as for the gate.
+ * The device decides in integers: best_i <= slideo_direct_ssd_threshold(t, sw sh), the largest SSD whose host similarity is >= t,
+ * found by bisection over that very expression.  At collect the host recomputes s_i from the SSD read back and checks the device's
+ * decision against the host expression (a mismatch is an internal error, as for the gate's flag).
+ * The plain calls (slideo_match_frames_*) and the mask + kept pair do NOT look up: their units have no small images, no kept list
+ * and no host wait to ride on.
+ * Departure from the reference: a direct verdict's similarity is the identity warp's, not a verified transform's, and no keypoint
+ * was matched for it.  No default t is chosen here; tools/direct_rate.py reports what a user needs to choose one.
+ * Refused: t > 0 together with a frame mask under the SLIDEO_MASK_GATE scope is SLIDEO_ERR_UNSUPPORTED at whichever of
+ * slideo_matcher_set_direct_similarity, slideo_matcher_set_frame_mask and slideo_matcher_set_frame_mask_scope would complete the
+ * combination; the state before stays in force.  SLIDEO_MASK_DETECT alone is fine.
+ * Where it runs (csrc/direct.hip.h, csrc/stage_direct.hip): the page operand is built at the first use with t > 0 after finalize
+ * (a matcher that never turns the feature on allocates and launches nothing new): per small-size class of the deck the pages'
+ * small images centred to i8 (x ^ 0x80) in the MFMA's tile order, zero padded to the K granule, |b'|^2 per page as i64 and the
+ * class's ascending page list; a page set selects through a per-set eligible list cached with the set.  Per gated unit, on the
+ * slot's stream: stage, small images, gate SSDs, direct_centre_kernel (the frames' aligned centred copy and |a'|^2),
+ * page_ssd_kernel over all n frames (v_mfma_i32_32x32x32_i8, split over K, i64 partial sums by non-returning vector atomics),
+ * direct_best_kernel, gate_kernel, direct_gate_kernel (the direct frames leave the kept list in place), the unit's ONE host wait
+ * (it reads the reduced count), gather, the pipeline of the remaining frames.  Registers, LDS and measurements:
+ * docs/EXTENSIONS.md "Direct page look-up". */
+/* Idle matcher (SLIDEO_ERR_STATE with units in flight).  t < 0, t > 1 or NaN is SLIDEO_ERR_INVALID_ARG. */
+int32_t     slideo_matcher_set_direct_similarity(slideo_matcher* m, float t);
+/* The matcher's direct similarity (0 unless set).  SLIDEO_ERR_INVALID_ARG for a null argument. */
+int32_t     slideo_matcher_direct_similarity(const slideo_matcher* m, float* t);
+/* Forwards to every member; validated once (the value, every member idle, the refusal above), before any member is touched. */
+int32_t     slideo_group_set_direct_similarity(slideo_group* g, float t);
+/* The largest SSD of two small images of n_pixels pixels whose similarity is >= t.  A pure host function (no device).  -1 for
+ * t outside (0, 1], NaN, n_pixels < 1 or > INT32_MAX, and where no SSD qualifies. */
+int64_t     slideo_direct_ssd_threshold(float t, int64_t n_pixels);
+/* Tap: n host small images of sw x sh (3 bytes per pixel, back to back) against the deck: ssd_out[i * page_count + p] = ssd_i(p) for
+ * every deck page p, UINT64_MAX for a page of another small size.  The same kernels and the same page operand as the gated path
+ * (it builds the operand if no gated call has).  Finalized, idle matcher; sw * sh at most cfg.small_area. */
+int32_t     slideo_page_small_ssd(slideo_matcher* m, const uint8_t* small, int32_t n, int32_t sw, int32_t sh, uint64_t* ssd_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -142,6 +142,8 @@ EXPORTS = [
     "slideo_matcher_set_frame_mask", "slideo_matcher_frame_mask_info", "slideo_group_set_frame_mask", "slideo_frame_mask_level",
     "slideo_matcher_set_frame_mask_scope", "slideo_matcher_frame_mask_scope", "slideo_group_set_frame_mask_scope",
     "slideo_changed_ssd_threshold_n", "slideo_frame_mask_small",
+    "slideo_matcher_set_direct_similarity", "slideo_matcher_direct_similarity", "slideo_group_set_direct_similarity",
+    "slideo_direct_ssd_threshold", "slideo_page_small_ssd",
 ]
 
 # frame mask scope (include/slideo_amd.h "Frame mask scope")
@@ -216,6 +218,14 @@ def lib():
             L.slideo_changed_ssd_threshold_n.restype = i64
             L.slideo_changed_ssd_threshold_n.argtypes = [C.c_float, i64]
             L.slideo_frame_mask_small.argtypes = [vp, vp, i64, vp, vp, vp]
+        if hasattr(L, "slideo_matcher_set_direct_similarity"):
+            vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
+            L.slideo_matcher_set_direct_similarity.argtypes = [vp, C.c_float]
+            L.slideo_matcher_direct_similarity.argtypes = [vp, vp]
+            L.slideo_group_set_direct_similarity.argtypes = [vp, C.c_float]
+            L.slideo_direct_ssd_threshold.restype = i64
+            L.slideo_direct_ssd_threshold.argtypes = [C.c_float, i64]
+            L.slideo_page_small_ssd.argtypes = [vp, vp, i32, i32, i32, vp]
         _lib = L
     return _lib
 
@@ -368,6 +378,21 @@ class _FrameCalls:
         """scope: MASK_DETECT (the default), MASK_GATE or both.  Under MASK_GATE the changed-frame flags and similarities ignore the
         masked regions.  The matcher's own: it survives clearing or replacing the mask.  The matcher must be idle."""
         self._check(getattr(lib(), self._SETS + "set_frame_mask_scope")(self._h, int(scope)))
+
+    # direct page look-up (include/slideo_amd.h "Direct page look-up"): gated calls resolve full-screen slide frames without ORB
+    def set_direct_similarity(self, t):
+        """t: 0 (off, the default) or 0 < t <= 1.  While t > 0 a changed frame of a gated call whose small image is at least that
+        similar to an eligible page's gets the verdict (page, similarity, 0 inliers, 0 keypoints) without the pipeline.  The
+        matcher must be idle."""
+        self._check(getattr(lib(), self._SETS + "set_direct_similarity")(self._h, C.c_float(t)))
+
+    @property
+    def direct_similarity(self):
+        t = C.c_float()
+        rc = lib().slideo_matcher_direct_similarity(self._mask_owner(), C.byref(t))
+        if rc != OK:
+            raise SlideoError(rc, "direct_similarity")
+        return float(t.value)
 
     def _mask_owner(self):
         """The matcher handle the mask's getters read (a group's members agree: member 0)."""
@@ -817,6 +842,17 @@ class Matcher(_FrameCalls):
         self._check(lib().slideo_reduce_bgr8(self._h, _p(buf), int(w), int(h), int(stride), int(dw), int(dh), _p(out), C.c_int64(out.size)))
         return out
 
+    def page_small_ssd(self, smalls):
+        """slideo_page_small_ssd: smalls uint8 [n, sh, sw, 3] -> uint64 [n, page_count], the integer SSD of every small image with
+        every deck page's (UINT64_MAX: a page of another small size).  The kernels and page operand of the direct page look-up."""
+        smalls = np.ascontiguousarray(smalls, np.uint8)
+        if smalls.ndim != 4 or smalls.shape[3] != 3:
+            raise ValueError("expected [n, sh, sw, 3] uint8 small images")
+        n, sh, sw, _ = smalls.shape
+        out = np.empty((n, self.page_count), np.uint64)
+        self._check(lib().slideo_page_small_ssd(self._h, _p(smalls), n, sw, sh, _p(out)))
+        return out
+
     def small_image(self, bgr):
         bgr = _img3(bgr)
         h, w, _ = bgr.shape
@@ -932,6 +968,12 @@ def changed_ssd_threshold(changed_similarity, small_w, small_h):
     if t < 0:
         raise SlideoError(1, "changed_ssd_threshold: bad small-image size %rx%r" % (small_w, small_h))
     return t
+
+
+def direct_ssd_threshold(t, n_pixels):
+    """slideo_direct_ssd_threshold: the largest SSD of two small images of n_pixels pixels whose similarity is >= t (-1: bad
+    arguments, or none)."""
+    return int(lib().slideo_direct_ssd_threshold(C.c_float(t), C.c_int64(int(n_pixels))))
 
 
 def changed_ssd_threshold_n(changed_similarity, n_pixels):

@@ -221,11 +221,12 @@ void group_gated_impl(slideo_group* g, int32_t n_frames, const FrameSrc& src, ui
         group_gate_none(g);
         fail(SLIDEO_ERR_HIP, "%s (the group's gate state is now \"none\")", e.what());
     }
-    // the trace lookup counts CHANGED frames: member r's are [match_lo[r], match_lo[r + 1])
+    // the trace lookup counts the frames that went through the pipeline — changed and not direct (page_idx >= 0 with 0 inliers:
+    // include/slideo_amd.h "Direct page look-up"): member r's are [match_lo[r], match_lo[r + 1])
     for (int r = 0; r < N; ++r) {
         int lo, hi, k = 0;
         shard_range(n_frames, r, N, lo, hi);
-        for (int i = lo; i < hi; ++i) k += changed_out[i] != 0;
+        for (int i = lo; i < hi; ++i) k += changed_out[i] != 0 && !(verdicts_out[i].page_idx >= 0 && verdicts_out[i].inliers == 0);
         g->match_lo[r + 1] = g->match_lo[r] + k;
     }
 }
@@ -347,6 +348,16 @@ int32_t slideo_group_set_frame_mask_scope(slideo_group* g, uint32_t scope) {
     for (slideo_matcher* m : g->members) require_idle(m);
     for (slideo_matcher* m : g->members) check_member_call(m, slideo_matcher_set_frame_mask_scope(m, scope));
     g->kept_valid = false;
+    GROUP_CATCH(g)
+}
+
+int32_t slideo_group_set_direct_similarity(slideo_group* g, float t) {
+    if (!g) return SLIDEO_ERR_INVALID_ARG;
+    GROUP_TRY
+    // validated once, before any member is touched
+    if (!(t >= 0.f) || t > 1.f) fail(SLIDEO_ERR_INVALID_ARG, "direct similarity %g: 0 (off) or 0 < t <= 1", (double)t);
+    for (slideo_matcher* m : g->members) { require_idle(m); direct_check_mask(m->mask.set, m->mask_scope, t); }
+    for (slideo_matcher* m : g->members) check_member_call(m, slideo_matcher_set_direct_similarity(m, t));
     GROUP_CATCH(g)
 }
 

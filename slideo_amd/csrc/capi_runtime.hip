@@ -736,6 +736,7 @@ int32_t slideo_matcher_set_frame_mask(slideo_matcher* m, const uint8_t* mask, in
     }
     HIP_CHECK(hipSetDevice(m->device));
     require_idle(m);
+    direct_check_mask(mask != nullptr, m->mask_scope, m->direct_t);       // (the mask before stays in force)
     // under the GATE scope the new mask's validity map comes first: a mask it refuses leaves the mask before in force
     slideo_matcher::GateMap map;
     if (mask && (m->mask_scope & SLIDEO_MASK_GATE)) {
@@ -761,6 +762,7 @@ int32_t slideo_matcher_set_frame_mask_scope(slideo_matcher* m, uint32_t scope) {
         fail(SLIDEO_ERR_INVALID_ARG, "frame mask scope %u: a non-empty combination of SLIDEO_MASK_DETECT (1) and SLIDEO_MASK_GATE (2)", scope);
     HIP_CHECK(hipSetDevice(m->device));
     require_idle(m);
+    direct_check_mask(m->mask.set, scope, m->direct_t);                   // (the scope before stays in force)
     if ((scope & SLIDEO_MASK_GATE) && m->mask.set && !m->gate_map.on) {
         // the second of {mask, GATE scope}: the map from the mask as given, level 0 of its pyramid
         const LevelGeom& L0 = geom_for(m, m->mask.w, m->mask.h).g.lv[0];

@@ -8,6 +8,7 @@
 //   stage_sift.hip     SIFT stage + entry points  (kernels: sift.hip.h)
 //   stage_page_set.hip page sets: a subset's search operand built from the finalized deck (kernels: page_set.hip.h)
 //   stage_gate.hip     changed-frame gate: gated units, the gate state and its entry points (kernels: gate.hip.h)
+//   stage_direct.hip   direct page look-up: the page operand, a gated unit's look-up, its entry points (kernels: direct.hip.h)
 //   capi_taps.hip      debug taps of the parity tests
 //   capi_group.hip     the N-device group (slideo_group_*)
 //
@@ -155,6 +156,9 @@ struct Slot {
     // memory), their small images, the gate record {ssd n x u64 | kept idx n x i32 | flags n x u8 | count} and its pinned twin
     DevBuf d_gstage, d_gsmall, d_gate;
     PinBuf h_gate;
+    // ... under a direct similarity (stage_direct.hip): the frames' centred operand, {|a'|^2 n x i64 | best n x DirectBest} and the
+    // n x np dot products (reserved by the first such unit only)
+    DevBuf d_dir_a, d_dir_rec, d_dir_dot;
     hipEvent_t ev_gate = nullptr;             // the unit's small images are made and the gate state is this unit's last one
     struct GateUnit {
         bool on = false;                      // the unit in flight is gated: slideo_match_changed_frames_collect collects it
@@ -162,6 +166,11 @@ struct Slot {
         int sw = 0, sh = 0;
         int npx = 0;                          // the pixels the similarity is normalised over: sw * sh, the gate map's n_valid under one
         bool force0 = false;                  // no gate state at submission: frame 0 is changed, similarity 0.0
+        // the direct page look-up ran for the unit (direct_t: the matcher's direct similarity at submission): k counts the changed
+        // frames that are not direct, the record's tail (direct.hip.h direct_rec_*) is at direct_ofs; has_elig: a page was eligible
+        bool direct = false, has_elig = false;
+        float direct_t = 0.f;
+        size_t direct_ofs = 0;
     } gate;
     // unit in flight
     bool busy = false;
@@ -207,14 +216,30 @@ struct SearchOperand {
 
 // A page set (slideo_matcher_create_page_set): the search operand and duplicate chain of a subset of the finalized deck's pages,
 // built on the device (stage_page_set.hip).  Keys carry deck row ids, so everything downstream of the search is the deck's.
+struct DirectClass;
 struct PageSet {
     int n_pages = 0;
+    std::vector<int32_t> pages;                   // the selected deck pages, ascending
+    // direct page look-up: per size class of the deck the set's eligible pages, as ascending positions in the class's page list
+    // (built on the host at the first gated unit that needs it; the class's operand is the deck's)
+    struct DirectElig { const DirectClass* cls = nullptr; int n = 0; DevBuf d; };
+    std::vector<std::unique_ptr<DirectElig>> direct_elig;
     int64_t rows = 0, urows = 0;                  // the selected pages' rows, the distinct rows among them (what the search streams)
     SearchOperand op;                             // as prepare_train_bits lays out a deck of exactly the selected pages
     DevBuf d_grp_next;                            // [M] the chain of the selected rows of each duplicate group (-1 elsewhere)
     size_t bytes() const { return op.bytes() + d_grp_next.cap; }
 };
 constexpr int MAX_PAGE_SETS = 64;                 // live sets per matcher
+
+// Direct page look-up (include/slideo_amd.h "Direct page look-up"): one size class of the deck's small images as the page operand
+// of page_ssd_kernel (direct.hip.h: centred i8, MFMA tile order, rows padded to DIRECT_TILE, K to DIRECT_KGRAN)
+struct DirectClass {
+    int sw = 0, sh = 0;
+    int np = 0, np_pad = 0;                       // pages of the class, padded to whole wave tiles
+    int64_t L = 0, kp = 0;                        // bytes of a small image, padded to the K granule
+    std::vector<int32_t> pages;                   // the class's deck pages, ascending
+    DevBuf d_op, d_norm, d_pages, d_all;          // operand, |b'|^2 (i64), the page list, the identity eligible list 0 .. np - 1
+};
 
 }  // namespace slideo
 
@@ -314,6 +339,12 @@ struct slideo_matcher {
     } gate;
     slideo::DevBuf d_gate_small;
     hipEvent_t last_gate_ev = nullptr;
+
+    // direct page look-up (include/slideo_amd.h "Direct page look-up"): the direct similarity (0: off) and, built at the first use
+    // with t > 0 after finalize, the deck's size classes
+    float direct_t = 0.f;
+    bool direct_built = false;
+    std::vector<std::unique_ptr<slideo::DirectClass>> direct_classes;
 
     // workspaces
     slideo::Slot slots[slideo::NSLOTS];
@@ -455,7 +486,11 @@ void page_set_check_mode(const slideo_matcher* m);
 void gate_release(slideo_matcher* m);          // the gate's events (slideo_matcher_destroy)
 inline void gate_state_reset(slideo_matcher* m) { m->gate = slideo_matcher::GateState{}; }
 // FrameSrc::staging_bytes' gate_small of a gated call (a small image has at most small_area pixels)
-inline size_t gate_small_budget(const slideo_matcher* m) { return (size_t)m->cfg.small_area * 3 + 64; }
+// (under a direct similarity: + the frame's centred operand row, its row of dot products and its record)
+inline size_t gate_small_budget(const slideo_matcher* m) {
+    const size_t small = (size_t)m->cfg.small_area * 3 + 64;
+    return m->direct_t > 0.f ? 2 * small + 128 + m->pages.size() * 8 + 64 : small;
+}
 // a validated source's frames against the gate state: one size and one format family since the last reset (SLIDEO_ERR_STATE)
 void gate_check(const slideo_matcher* m, const FrameSrc& src);
 // the same against a state held elsewhere (the N-device group's, capi_group.hip)
@@ -480,6 +515,28 @@ void launch_gate_ssd(const uint8_t* weights, const uint8_t* a, int64_t a_stride,
                      unsigned long long* ssd, int n, hipStream_t st);
 // the smallest SSD that counts as changed when the similarity is normalised over n pixels (slideo_changed_ssd_threshold_n)
 int64_t gate_ssd_threshold(float changed_similarity_, int64_t n);
+
+// ---- stage_direct.hip -----------------------------------------------------------------------------
+// the largest SSD whose host similarity over n pixels is >= t (slideo_direct_ssd_threshold; -1: none)
+int64_t direct_ssd_threshold(float t, int64_t n);
+// t > 0 together with a frame mask under the GATE scope (SLIDEO_ERR_UNSUPPORTED): checked by whichever of the three set calls
+// would complete the combination, before it changes anything
+void direct_check_mask(bool mask_set, uint32_t scope, float t);
+// What a gated unit of n frames with sw x sh small images looks up in: everything that can fail for want of memory — the page
+// operand at its first use, the selected set's eligible list, the slot's workspaces — happens here, in front of any change to the
+// gate state.  cls == null: no page of the set shares the small size, the unit does not look up.
+struct DirectPlan { const DirectClass* cls = nullptr; const int32_t* elig = nullptr; int ne = 0; };
+DirectPlan direct_unit_prepare(slideo_matcher* m, Slot& S, int n, int sw, int sh);
+// The look-up on S.st, behind the unit's small images (S.d_gsmall) and in front of gate_kernel: the frames' operand,
+// page_ssd_kernel over all n frames, direct_best_kernel over the eligible pages.  Launches only.
+void direct_unit_lookup(Slot& S, const DirectPlan& plan, int n);
+// behind gate_kernel: direct_gate_kernel on the unit's kept list idx / count, the record's tail at h_rec, the list's pinned twin h_idx
+void direct_unit_gate(slideo_matcher* m, Slot& S, int n, int npx, int32_t* idx, uint32_t* count, int32_t* h_idx, uint8_t* h_rec);
+size_t direct_unit_rec_bytes(int n);
+// one frame's entry of the record's tail
+struct DirectFrameRec { unsigned long long ssd; int32_t page; bool direct; };
+uint32_t direct_rec_kept(const uint8_t* h_rec, int n);
+DirectFrameRec direct_rec_frame(const uint8_t* h_rec, int n, int i);
 
 // ---- stage_sift.hip -------------------------------------------------------------------------------
 void sift_check_cfg(const slideo_sift_config* sc, int w, int h);

@@ -118,9 +118,19 @@ void gate_prime(slideo_matcher* m, FrameSrc src, hipStream_t user_stream) {
 void gate_unit_submit(slideo_matcher* m, Slot& S, const FrameSrc& src, int first, int n, hipStream_t cs) {
     hipStream_t st = S.st;
     if (!S.ev_gate) HIP_CHECK(hipEventCreateWithFlags(&S.ev_gate, hipEventDisableTiming));
+    // under a direct similarity: the page operand, the set's eligible list and the look-up's workspaces first, so that a failure
+    // there leaves the gate state as it was (include/slideo_amd.h "Direct page look-up")
+    const bool look = m->direct_t > 0.f;
+    DirectPlan plan;
+    int psw = 0, psh = 0;
+    if (look) {
+        small_size(src.unit_w(), src.unit_h(), m->cfg.small_area, psw, psh);
+        plan = direct_unit_prepare(m, S, n, psw, psh);
+    }
     const DevFrames all = stage_frames(m, S, src, first, n, cs, &S.d_gstage);
     int sw = 0, sh = 0;
     run_small_into(m, all, n, S.d_gsmall, sw, sh, st);
+    if (look && (sw != psw || sh != psh)) fail(SLIDEO_ERR_HIP, "internal: the look-up was prepared for %dx%d small images, the unit's are %dx%d", psw, psh, sw, sh);
     const int64_t sb = (int64_t)sw * sh * 3;
     const uint8_t* small = S.d_gsmall.as<uint8_t>();
     int npx = 0;
@@ -130,7 +140,9 @@ void gate_unit_submit(slideo_matcher* m, Slot& S, const FrameSrc& src, int first
     int32_t* idx = reinterpret_cast<int32_t*>(S.d_gate.as<uint8_t>() + (size_t)n * 8);
     uint32_t* count = reinterpret_cast<uint32_t*>(idx + n);
     uint8_t* flags = reinterpret_cast<uint8_t*>(count + 1);
-    S.h_gate.reserve(gate_rec_bytes(n));
+    // under a direct similarity the record grows by the look-up's tail (include/slideo_amd.h "Direct page look-up")
+    const size_t direct_ofs = (gate_rec_bytes(n) + 7) & ~(size_t)7;
+    S.h_gate.reserve(look ? direct_ofs + direct_unit_rec_bytes(n) : gate_rec_bytes(n));
     const bool force0 = !m->gate.has;
     m->d_gate_small.reserve((size_t)sb);            // (grows only from the state "none": no gated unit is reading it)
     // pair i: (small[i - 1], small[i]); pair 0: (gate state, small[0]), behind the previous gated unit's write of the state
@@ -143,16 +155,29 @@ void gate_unit_submit(slideo_matcher* m, Slot& S, const FrameSrc& src, int first
     slideo_matcher::GateState& g = m->gate;
     g.has = true; g.seen = true; g.w = src.w; g.h = src.h; g.yuv = src.yuv != nullptr; g.sw = sw; g.sh = sh;
 
+    // the look-up of all n frames (it does not depend on the flags); none when no page of the selected set shares the small size
+    const bool direct = plan.cls != nullptr;
+    if (direct) direct_unit_lookup(S, plan, n);
     const long long thr = gate_ssd_threshold(m->cfg.changed_similarity, npx);
     gate_kernel<<<1, GATE_BLOCK, 0, st>>>(ssd, n, thr, force0 ? 1 : 0, flags, idx, count, S.h_gate.as<uint8_t>());
     check_launch("gate_kernel");
+    // the direct frames leave the kept list: the one host wait below reads the reduced count
+    if (direct)
+        direct_unit_gate(m, S, n, npx, idx, count, reinterpret_cast<int32_t*>(S.h_gate.as<uint8_t>() + gate_rec_idx_ofs(n)),
+                         S.h_gate.as<uint8_t>() + direct_ofs);
     HIP_CHECK(hipStreamSynchronize(st));
     const GateHostRec rec = *S.h_gate.as<GateHostRec>();
     if (rec.n != (uint32_t)n || rec.count > (uint32_t)n) fail(SLIDEO_ERR_HIP, "internal: gate record %u of %u for a unit of %d", rec.count, rec.n, n);
-    const int k = (int)rec.count;
+    int k = (int)rec.count;
+    if (direct) {
+        const int kept = (int)direct_rec_kept(S.h_gate.as<uint8_t>() + direct_ofs, n);
+        if (kept > k) fail(SLIDEO_ERR_HIP, "internal: %d frames kept behind the look-up, %d changed", kept, k);
+        k = kept;
+    }
     Slot::GateUnit gu;
     gu.on = true; gu.n = n; gu.k = k; gu.sw = sw; gu.sh = sh; gu.npx = npx; gu.force0 = force0;
-    if (k == 0) {                                   // no frame changed: no pipeline; the collect returns the flags at once
+    gu.direct = direct; gu.direct_t = m->direct_t; gu.direct_ofs = direct_ofs;
+    if (k == 0) {                                   // no frame changed (or every changed one is direct): no pipeline; the collect returns at once
         S.busy = true; S.n = 0; S.u_async = false; S.timed = false;
         S.gate = gu;
         return;
@@ -193,9 +218,20 @@ void gate_unit_collect(slideo_matcher* m, Slot& S, uint8_t* changed_out, float* 
             fail(SLIDEO_ERR_HIP, "internal: the gate's flag of frame %d (%d, SSD %llu) is not the host expression's", i, (int)flag[i], s);
         changed_out[i] = flag[i];
         if (similarity_out) similarity_out[i] = sim;
-        if (flag[i]) verdicts_out[i] = v[(size_t)r++];
-        else verdicts_out[i] = slideo_verdict{-1, 0.0f, 0, 0};
+        if (!flag[i]) { verdicts_out[i] = slideo_verdict{-1, 0.0f, 0, 0}; continue; }
+        if (g.direct) {
+            // a changed frame's look-up: the similarity from the SSD read back, the device's decision against the host expression
+            const DirectFrameRec d = direct_rec_frame(rec + g.direct_ofs, g.n, i);
+            const float s = changed_similarity(d.ssd, g.npx);
+            if (d.page < 0 || (s >= g.direct_t) != d.direct)
+                fail(SLIDEO_ERR_HIP, "internal: the look-up's decision for frame %d (%d, page %d, SSD %llu) is not the host expression's", i, (int)d.direct,
+                     d.page, d.ssd);
+            if (d.direct) { verdicts_out[i] = slideo_verdict{d.page, s, 0, 0}; continue; }
+        }
+        if (r >= g.k) fail(SLIDEO_ERR_HIP, "internal: more frames through the pipeline than the %d it ran for", g.k);
+        verdicts_out[i] = v[(size_t)r++];
     }
+    if (r != g.k) fail(SLIDEO_ERR_HIP, "internal: %d frames scattered, the pipeline ran for %d", r, g.k);
 }
 
 }  // namespace slideo

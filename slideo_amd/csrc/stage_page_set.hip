@@ -79,6 +79,8 @@ int page_set_create(slideo_matcher* m, int n, const int32_t* pages) {
     knn_expand_operand(t, (int)ns, nt_pad, op.perm.as<int32_t>(), op.tx.as<uint4>(), st);
     HIP_CHECK(hipStreamSynchronize(st));                                  // (the scratch buffers die here)
     ps->n_pages = n; ps->rows = rows; ps->urows = ns;
+    ps->pages.assign(pages, pages + n);
+    std::sort(ps->pages.begin(), ps->pages.end());
     const int id = m->next_set_id++;
     m->page_sets[id] = std::move(ps);
     return id;

@@ -337,6 +337,11 @@ public:
     // include/slideo_amd.h "Frame mask scope").  With SLIDEO_MASK_GATE the changed-frame gate ignores the masked regions too: an
     // inset that moves on every frame no longer flags every held slide as changed
     HipImageVideoMatcher& with_frame_mask_scope(uint32_t scope) { mask_scope_ = scope; return *this; }
+    // The direct page look-up (slideo_group_set_direct_similarity, include/slideo_amd.h "Direct page look-up"): t in (0, 1]; a
+    // changed frame whose small image is at least that similar to a page's is resolved to that page without ORB, search or
+    // verify (full-screen slide frames of a screen recording; the reference never decides without keypoints).  Not together with
+    // SLIDEO_MASK_GATE.  Default 0: off
+    HipImageVideoMatcher& with_direct_similarity(float t) { direct_t_ = t; return *this; }
     // false: tasks run the stop-and-go pair slideo_group_changed_mask_bgr8 + slideo_group_match_kept_frames in place of the group's
     // gated call (the same timeline; for comparisons).  Default: gated
     HipImageVideoMatcher& with_changed_gate(bool on) { gated_ = on; return *this; }
@@ -359,6 +364,7 @@ public:
         }
         if (mask_scope_ != SLIDEO_MASK_DETECT) h->check(slideo_group_set_frame_mask_scope(h->g, mask_scope_));
         if (!mask_.empty()) h->check(slideo_group_set_frame_mask(h->g, mask_.data(), mask_w_, mask_h_, mask_w_));
+        if (direct_t_ != 0.f) h->check(slideo_group_set_direct_similarity(h->g, direct_t_));
         h->check(slideo_group_set_progress(h->g, detail::tramp, &reporter));                         // "Analyzing PDF pages..." protocol, mo/lib.rs:43-58
         const size_t CH = 32 * (size_t)h->n_devices;
         for (size_t i = 0; i < images.size(); i += CH) {
@@ -375,7 +381,7 @@ public:
 private:
     std::vector<int32_t> devices_;
     bool sift_on_ = false, gated_ = true;
-    float sift_ratio_ = 0.f;
+    float sift_ratio_ = 0.f, direct_t_ = 0.f;
     int32_t work_w_ = 0, work_h_ = 0;
     std::vector<uint8_t> mask_;
     int32_t mask_w_ = 0, mask_h_ = 0;

@@ -296,7 +296,8 @@ class HipVideoMatcher:
 class HipImageVideoMatcher:
     """Drop-in for OpenCVImageVideoMatcher (lib.rs:34-73) behind matching::ImageVideoMatcher."""
 
-    def __init__(self, cfg=None, device=None, sift=None, devices=None, working_size=None, frame_mask=None, frame_mask_scope=None):
+    def __init__(self, cfg=None, device=None, sift=None, devices=None, working_size=None, frame_mask=None, frame_mask_scope=None,
+                 direct_similarity=None):
         """devices: HIP ordinals, one matcher each behind one slideo_group (the reference fans out over the whole machine, the
         global rayon pool of lib.rs:45,174); None = every gfx950 device of the node; `device` = d is short for devices = [d].
         sift = (slideo_sift_config, ratio): the north-star's SIFT + L2 front end instead of the reference's ORB + Hamming
@@ -308,11 +309,15 @@ class HipImageVideoMatcher:
         mask's; the reference passes no mask); None = no mask.
         frame_mask_scope = _capi.MASK_DETECT | _capi.MASK_GATE bits (slideo_group_set_frame_mask_scope): with MASK_GATE the
         changed-frame gate ignores the masked regions too, so that an inset which moves on every frame does not flag every held
-        slide as changed; None = the default, MASK_DETECT."""
+        slide as changed; None = the default, MASK_DETECT.
+        direct_similarity = t in (0, 1] (slideo_group_set_direct_similarity): a changed frame whose small image is at least that
+        similar to a page's is resolved to that page without ORB, search or verify — full-screen slide frames of a screen
+        recording (the reference never decides without keypoints); not together with MASK_GATE; None = off."""
         self._cfg, self._sift = cfg, sift
         self._working_size = working_size
         self._frame_mask = frame_mask
         self._frame_mask_scope = frame_mask_scope
+        self._direct_similarity = direct_similarity
         self._devices = [device] if device is not None else devices
 
     def create_video_matcher(self, images, progress_reporter: ProgressReporter) -> HipVideoMatcher:
@@ -327,6 +332,8 @@ class HipImageVideoMatcher:
             m.set_frame_mask_scope(self._frame_mask_scope)
         if self._frame_mask is not None:
             m.set_frame_mask(self._frame_mask)
+        if self._direct_similarity is not None:
+            m.set_direct_similarity(self._direct_similarity)
         m.set_progress(progress_reporter.report)        # "Analyzing PDF pages..." protocol, lib.rs:43-58
         CH = 32 * len(m.devices)
         for i in range(0, len(images), CH):
