@@ -7,6 +7,8 @@ use std::os::raw::{c_char, c_void};
 pub const SLIDEO_ABI_VERSION: u32 = 7;
 pub const SLIDEO_MASK_DETECT: u32 = 1;
 pub const SLIDEO_MASK_GATE: u32 = 2;
+pub const SLIDEO_DIRECT_WHOLE: u32 = 0;
+pub const SLIDEO_DIRECT_VALID: u32 = 1;
 
 /// slideo_ocv_variants: which restatement of each OpenCV primitive runs.  slideo_config_default fills it; the
 /// application never touches it.
@@ -452,6 +454,18 @@ extern "C" {
     pub fn slideo_group_set_direct_similarity(g: *mut slideo_group, t: f32) -> i32;
     pub fn slideo_direct_ssd_threshold(t: f32, n_pixels: i64) -> i64;
     pub fn slideo_page_small_ssd(
+        m: *mut slideo_matcher,
+        small: *const u8,
+        n: i32,
+        sw: i32,
+        sh: i32,
+        ssd_out: *mut u64,
+    ) -> i32;
+    // direct look-up scope (include/slideo_amd.h "Direct look-up scope"): SLIDEO_DIRECT_WHOLE / SLIDEO_DIRECT_VALID
+    pub fn slideo_matcher_set_direct_scope(m: *mut slideo_matcher, scope: u32) -> i32;
+    pub fn slideo_matcher_direct_scope(m: *const slideo_matcher, scope: *mut u32) -> i32;
+    pub fn slideo_group_set_direct_scope(g: *mut slideo_group, scope: u32) -> i32;
+    pub fn slideo_page_small_ssd_valid(
         m: *mut slideo_matcher,
         small: *const u8,
         n: i32,

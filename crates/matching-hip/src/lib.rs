@@ -82,6 +82,10 @@ pub struct HipImageVideoMatcher {
     /// least that similar to a page's is resolved to that page without ORB, search or verify (full-screen slide frames of a
     /// screen recording; the reference never decides without keypoints).  Not together with SLIDEO_MASK_GATE.  0.0 (default) = off.
     pub direct_similarity: f32,
+    /// What the direct page look-up compares (slideo_group_set_direct_scope): ffi::SLIDEO_DIRECT_WHOLE (default: whole small
+    /// images, refused beside SLIDEO_MASK_GATE) or ffi::SLIDEO_DIRECT_VALID (the valid pixels of the gate's validity map: a
+    /// full-screen slide under a speaker thumbnail).  Applied before direct_similarity.
+    pub direct_scope: u32,
 }
 
 impl Default for HipImageVideoMatcher {
@@ -92,6 +96,7 @@ impl Default for HipImageVideoMatcher {
             frame_mask: None,
             frame_mask_scope: ffi::SLIDEO_MASK_DETECT,
             direct_similarity: 0.0,
+            direct_scope: ffi::SLIDEO_DIRECT_WHOLE,
         }
     }
 }
@@ -126,6 +131,9 @@ impl<'i> ImageVideoMatcher<'i> for HipImageVideoMatcher {
             if let Some((mask, w, hh)) = &self.frame_mask {
                 assert_eq!(mask.len(), (*w as usize) * (*hh as usize), "frame_mask is not width x height bytes");
                 check(h, ffi::slideo_group_set_frame_mask(h, mask.as_ptr(), *w, *hh, *w));
+            }
+            if self.direct_scope != ffi::SLIDEO_DIRECT_WHOLE {
+                check(h, ffi::slideo_group_set_direct_scope(h, self.direct_scope));
             }
             if self.direct_similarity != 0.0 {
                 check(h, ffi::slideo_group_set_direct_similarity(h, self.direct_similarity));

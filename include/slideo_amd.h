@@ -928,7 +928,8 @@ int32_t     slideo_group_match_changed_frames_yuv420(slideo_group* g, int32_t n_
  * was matched for it.  No default t is chosen here; tools/direct_rate.py reports what a user needs to choose one.
  * Refused: t > 0 together with a frame mask under the SLIDEO_MASK_GATE scope is SLIDEO_ERR_UNSUPPORTED at whichever of
  * slideo_matcher_set_direct_similarity, slideo_matcher_set_frame_mask and slideo_matcher_set_frame_mask_scope would complete the
- * combination; the state before stays in force.  SLIDEO_MASK_DETECT alone is fine.
+ * combination; the state before stays in force.  SLIDEO_MASK_DETECT alone is fine.  That is the default DIRECT SCOPE,
+ * SLIDEO_DIRECT_WHOLE; under SLIDEO_DIRECT_VALID the combination is allowed ("Direct look-up scope" below).
  * Where it runs (csrc/direct.hip.h, csrc/stage_direct.hip): the page operand is built at the first use with t > 0 after finalize
  * (a matcher that never turns the feature on allocates and launches nothing new): per small-size class of the deck the pages'
  * small images centred to i8 (x ^ 0x80) in the MFMA's tile order, zero padded to the K granule, |b'|^2 per page as i64 and the
@@ -951,6 +952,43 @@ int64_t     slideo_direct_ssd_threshold(float t, int64_t n_pixels);
  * every deck page p, UINT64_MAX for a page of another small size.  The same kernels and the same page operand as the gated path
  * (it builds the operand if no gated call has).  Finalized, idle matcher; sw * sh at most cfg.small_area. */
 int32_t     slideo_page_small_ssd(slideo_matcher* m, const uint8_t* small, int32_t n, int32_t sw, int32_t sh, uint64_t* ssd_out);
+/* Direct look-up scope.  A screen share with a speaker thumbnail on top needs both the gate's mask scope and the look-up; a
+ * matcher therefore carries a DIRECT SCOPE, additive at the unchanged ABI:
+ *   SLIDEO_DIRECT_WHOLE (default)  everything above, the refusal included.
+ *   SLIDEO_DIRECT_VALID            the refusal is lifted (no set call raises it), and WHILE A VALIDITY MAP IS IN FORCE - a frame mask
+ *                    is set and the mask scope has SLIDEO_MASK_GATE: the very map slideo_frame_mask_small returns, with its n_valid -
+ *                    every gated call looks up over the valid pixels: ssd_i(p) = the sum over the valid small pixels' three channels
+ *                    of (small_i - page_small_p)^2, in integers; best_i and page_i as above (the smallest SSD, the lowest deck page
+ *                    that attains it among the eligible pages); s_i = the host expression over n_valid pixels; the frame is direct
+ *                    iff s_i >= t; the device decides best_i <= slideo_direct_ssd_threshold(t, n_valid), and the collect-time check
+ *                    of that decision against the host expression stays.  A direct verdict is {page_i, s_i, 0, 0}.
+ * With no map in force (no mask, or SLIDEO_MASK_DETECT alone) SLIDEO_DIRECT_VALID behaves as SLIDEO_DIRECT_WHOLE, bit for bit; under an
+ * all-255 mask with DETECT | GATE every result equals the result of no mask under WHOLE, bit for bit.  Everything else of the
+ * definition holds unchanged: unchanged frames are never looked up; flags, similarities, the gate state and
+ * slideo_matcher_gate_last_small depend neither on t nor on the direct scope; a frame that is not direct gets what it gets with t = 0
+ * under the same mask and mask scope; page sets, working size (the mask is then of the reduced size), host and device frames, BGR and
+ * 4:2:0, synchronous and submit / collect calls, and the group for every member count.
+ * Where it runs: the deck's page operand is NOT rebuilt and not copied.  With a'_m = a' at the valid bytes and 0 elsewhere, the sum
+ * over the valid bytes of a' b' is <a'_m, b'> against the unmasked page operand, so page_ssd_kernel, direct_best_kernel and
+ * direct_gate_kernel run unchanged; direct_centre_valid_kernel (csrc/direct.hip.h) writes the frames' operand as (x ^ 0x80) & w under
+ * the gate's byte weights with the norm over the valid bytes, and its store-less instance makes the pages' masked norms, one i64 per
+ * page of the class, built in front of any change to the gate state at the first look-up (or tap) under a map and cached with the
+ * class until the map changes (slideo_matcher_set_frame_mask, _set_frame_mask_scope, _set_working_size).  docs/EXTENSIONS.md "Direct
+ * look-up scope". */
+#define SLIDEO_DIRECT_WHOLE 0u   /* default: the look-up compares whole small images (and is refused beside SLIDEO_MASK_GATE, as today) */
+#define SLIDEO_DIRECT_VALID 1u   /* the look-up compares what the gate compares: the valid pixels of the gate's validity map */
+/* Idle matcher (SLIDEO_ERR_STATE with units in flight).  A value other than the two above is SLIDEO_ERR_INVALID_ARG.  Going back to
+ * SLIDEO_DIRECT_WHOLE while t > 0 and a mask is set under SLIDEO_MASK_GATE is SLIDEO_ERR_UNSUPPORTED (the fourth set call that can
+ * complete the refused combination); the state before stays in force. */
+int32_t     slideo_matcher_set_direct_scope(slideo_matcher* m, uint32_t scope);
+/* The matcher's direct scope (SLIDEO_DIRECT_WHOLE unless set).  SLIDEO_ERR_INVALID_ARG for a null argument. */
+int32_t     slideo_matcher_direct_scope(const slideo_matcher* m, uint32_t* scope);
+/* Forwards to every member; validated once (the value, every member idle, the refusal), before any member is touched. */
+int32_t     slideo_group_set_direct_scope(slideo_group* g, uint32_t scope);
+/* Tap: slideo_page_small_ssd with the masked SSDs under the matcher's current validity map, whatever t and the direct scope are.
+ * SLIDEO_ERR_STATE without a map in force; SLIDEO_ERR_INVALID_ARG for (sw, sh) other than the map's; UINT64_MAX for a page of another
+ * small size.  The kernels and the masked page norms of the gated path (it builds the norms if no gated call has). */
+int32_t     slideo_page_small_ssd_valid(slideo_matcher* m, const uint8_t* small, int32_t n, int32_t sw, int32_t sh, uint64_t* ssd_out);
 
 #ifdef __cplusplus
 }

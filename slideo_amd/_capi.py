@@ -144,11 +144,15 @@ EXPORTS = [
     "slideo_changed_ssd_threshold_n", "slideo_frame_mask_small",
     "slideo_matcher_set_direct_similarity", "slideo_matcher_direct_similarity", "slideo_group_set_direct_similarity",
     "slideo_direct_ssd_threshold", "slideo_page_small_ssd",
+    "slideo_matcher_set_direct_scope", "slideo_matcher_direct_scope", "slideo_group_set_direct_scope", "slideo_page_small_ssd_valid",
 ]
 
 # frame mask scope (include/slideo_amd.h "Frame mask scope")
 MASK_DETECT = 1
 MASK_GATE = 2
+# direct look-up scope (include/slideo_amd.h "Direct look-up scope")
+DIRECT_WHOLE = 0
+DIRECT_VALID = 1
 
 _lib = None
 
@@ -226,6 +230,12 @@ def lib():
             L.slideo_direct_ssd_threshold.restype = i64
             L.slideo_direct_ssd_threshold.argtypes = [C.c_float, i64]
             L.slideo_page_small_ssd.argtypes = [vp, vp, i32, i32, i32, vp]
+        if hasattr(L, "slideo_matcher_set_direct_scope"):
+            vp, i32, u32 = C.c_void_p, C.c_int32, C.c_uint32
+            L.slideo_matcher_set_direct_scope.argtypes = [vp, u32]
+            L.slideo_matcher_direct_scope.argtypes = [vp, vp]
+            L.slideo_group_set_direct_scope.argtypes = [vp, u32]
+            L.slideo_page_small_ssd_valid.argtypes = [vp, vp, i32, i32, i32, vp]
         _lib = L
     return _lib
 
@@ -393,6 +403,20 @@ class _FrameCalls:
         if rc != OK:
             raise SlideoError(rc, "direct_similarity")
         return float(t.value)
+
+    # direct look-up scope (include/slideo_amd.h "Direct look-up scope"): what the look-up compares
+    def set_direct_scope(self, scope):
+        """scope: DIRECT_WHOLE (the default: whole small images, refused beside MASK_GATE) or DIRECT_VALID (the valid pixels of the
+        gate's validity map while a mask is set under MASK_GATE).  The matcher must be idle."""
+        self._check(getattr(lib(), self._SETS + "set_direct_scope")(self._h, int(scope)))
+
+    @property
+    def direct_scope(self):
+        scope = C.c_uint32()
+        rc = lib().slideo_matcher_direct_scope(self._mask_owner(), C.byref(scope))
+        if rc != OK:
+            raise SlideoError(rc, "direct_scope")
+        return scope.value
 
     def _mask_owner(self):
         """The matcher handle the mask's getters read (a group's members agree: member 0)."""
@@ -851,6 +875,17 @@ class Matcher(_FrameCalls):
         n, sh, sw, _ = smalls.shape
         out = np.empty((n, self.page_count), np.uint64)
         self._check(lib().slideo_page_small_ssd(self._h, _p(smalls), n, sw, sh, _p(out)))
+        return out
+
+    def page_small_ssd_valid(self, smalls):
+        """slideo_page_small_ssd_valid: page_small_ssd over the valid pixels of the matcher's current validity map (a mask under
+        MASK_GATE), whatever the direct similarity and scope are."""
+        smalls = np.ascontiguousarray(smalls, np.uint8)
+        if smalls.ndim != 4 or smalls.shape[3] != 3:
+            raise ValueError("expected [n, sh, sw, 3] uint8 small images")
+        n, sh, sw, _ = smalls.shape
+        out = np.empty((n, self.page_count), np.uint64)
+        self._check(lib().slideo_page_small_ssd_valid(self._h, _p(smalls), n, sw, sh, _p(out)))
         return out
 
     def small_image(self, bgr):

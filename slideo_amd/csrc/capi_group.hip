@@ -356,8 +356,19 @@ int32_t slideo_group_set_direct_similarity(slideo_group* g, float t) {
     GROUP_TRY
     // validated once, before any member is touched
     if (!(t >= 0.f) || t > 1.f) fail(SLIDEO_ERR_INVALID_ARG, "direct similarity %g: 0 (off) or 0 < t <= 1", (double)t);
-    for (slideo_matcher* m : g->members) { require_idle(m); direct_check_mask(m->mask.set, m->mask_scope, t); }
+    for (slideo_matcher* m : g->members) { require_idle(m); direct_check_mask(m->mask.set, m->mask_scope, t, m->direct_scope); }
     for (slideo_matcher* m : g->members) check_member_call(m, slideo_matcher_set_direct_similarity(m, t));
+    GROUP_CATCH(g)
+}
+
+int32_t slideo_group_set_direct_scope(slideo_group* g, uint32_t scope) {
+    if (!g) return SLIDEO_ERR_INVALID_ARG;
+    GROUP_TRY
+    // validated once, before any member is touched
+    if (scope != SLIDEO_DIRECT_WHOLE && scope != SLIDEO_DIRECT_VALID)
+        fail(SLIDEO_ERR_INVALID_ARG, "direct scope %u: SLIDEO_DIRECT_WHOLE (0) or SLIDEO_DIRECT_VALID (1)", scope);
+    for (slideo_matcher* m : g->members) { require_idle(m); direct_check_mask(m->mask.set, m->mask_scope, m->direct_t, scope); }
+    for (slideo_matcher* m : g->members) check_member_call(m, slideo_matcher_set_direct_scope(m, scope));
     GROUP_CATCH(g)
 }
 

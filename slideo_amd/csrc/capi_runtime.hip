@@ -716,6 +716,7 @@ int32_t slideo_matcher_set_working_size(slideo_matcher* m, int32_t max_w, int32_
     m->work_w = max_w; m->work_h = max_h;
     m->kept.valid = false;          // (the kept frames of an earlier mask call were sized under the earlier setting)
     gate_state_reset(m);            // (and so was the gate's small image)
+    ++m->gate_map_gen;              // (the look-up's masked page norms are built again under the new setting)
     API_CATCH(m)
 }
 
@@ -736,7 +737,7 @@ int32_t slideo_matcher_set_frame_mask(slideo_matcher* m, const uint8_t* mask, in
     }
     HIP_CHECK(hipSetDevice(m->device));
     require_idle(m);
-    direct_check_mask(mask != nullptr, m->mask_scope, m->direct_t);       // (the mask before stays in force)
+    direct_check_mask(mask != nullptr, m->mask_scope, m->direct_t, m->direct_scope);       // (the mask before stays in force)
     // under the GATE scope the new mask's validity map comes first: a mask it refuses leaves the mask before in force
     slideo_matcher::GateMap map;
     if (mask && (m->mask_scope & SLIDEO_MASK_GATE)) {
@@ -748,6 +749,7 @@ int32_t slideo_matcher_set_frame_mask(slideo_matcher* m, const uint8_t* mask, in
     }
     m->kept.valid = false;          // (the kept frames of an earlier mask call end, as under slideo_matcher_set_working_size)
     m->gate_map.on = false;
+    ++m->gate_map_gen;              // (what was derived from the map before — the look-up's masked page norms — is stale)
     frame_mask_set(m, mask, width, height, stride_bytes);
     if (map.on) gate_map_swap(m->gate_map, map);
     API_CATCH(m)
@@ -762,7 +764,7 @@ int32_t slideo_matcher_set_frame_mask_scope(slideo_matcher* m, uint32_t scope) {
         fail(SLIDEO_ERR_INVALID_ARG, "frame mask scope %u: a non-empty combination of SLIDEO_MASK_DETECT (1) and SLIDEO_MASK_GATE (2)", scope);
     HIP_CHECK(hipSetDevice(m->device));
     require_idle(m);
-    direct_check_mask(m->mask.set, scope, m->direct_t);                   // (the scope before stays in force)
+    direct_check_mask(m->mask.set, scope, m->direct_t, m->direct_scope);  // (the scope before stays in force)
     if ((scope & SLIDEO_MASK_GATE) && m->mask.set && !m->gate_map.on) {
         // the second of {mask, GATE scope}: the map from the mask as given, level 0 of its pyramid
         const LevelGeom& L0 = geom_for(m, m->mask.w, m->mask.h).g.lv[0];
@@ -771,6 +773,7 @@ int32_t slideo_matcher_set_frame_mask_scope(slideo_matcher* m, uint32_t scope) {
         gate_map_swap(m->gate_map, map);
     }
     if (!(scope & SLIDEO_MASK_GATE)) m->gate_map.on = false;
+    ++m->gate_map_gen;
     m->mask_scope = scope;
     m->kept.valid = false;          // (as slideo_matcher_set_frame_mask; the gate state stays)
     API_CATCH(m)

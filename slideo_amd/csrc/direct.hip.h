@@ -2,6 +2,8 @@
 //
 //   direct_centre_kernel  small images (any byte alignment) -> the centred i8 operand of page_ssd_kernel + |x'|^2 per image:
 //                         the deck's pages once per size class, a gated unit's frames once per unit
+//   direct_centre_valid_kernel  the same under the gate's byte weights (the direct scope SLIDEO_DIRECT_VALID): the frames' operand
+//                         zero at the masked bytes and the norm over the valid bytes; without the store, the pages' masked norms
 //   page_ssd_kernel       <a', b'> of every frame with every page of the class on v_mfma_i32_32x32x32_i8, split over K, the
 //                         partial sums added to i64 with non-returning vector atomics
 //   direct_best_kernel    per frame: ssd(p) = |a'|^2 + |b'|^2 - 2 <a', b'> over the eligible pages, the smallest one and the
@@ -97,6 +99,74 @@ __global__ __launch_bounds__(DIRECT_BLOCK) void direct_centre_kernel(const uint8
                 sq += s2 + 262144u - 256u * s1;
             }
             o[(size_t)s * 64] = make_uint4(w[0] ^ 0x80808080u, w[1] ^ 0x80808080u, w[2] ^ 0x80808080u, w[3] ^ 0x80808080u);
+        }
+    }
+    sq += __shfl_xor(sq, 32);
+    if (live && h == 0) (void)__hip_atomic_fetch_add(norm + r, sq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// direct_centre_kernel's job under the gate's byte weights wgt[0 .. L) (0xFF valid, 0x00 masked; one array for all rows, 16-byte
+// aligned, readable up to L + 4): the direct scope SLIDEO_DIRECT_VALID.  Same grid, same operand layout, same aligned-dword reads
+// of the rows.  The stored operand is (x ^ 0x80) & w, so a masked byte is the centred zero and <a'_m, b'> against the UNMASKED page
+// operand is the sum over the valid bytes of a' b'.  norm[row] += sum over the valid bytes of x'^2: per piece, with xm = x & w,
+// sum xm^2 - 256 sum xm + 16384 * (valid bytes), the sums as 4 x u8 dot products (a masked byte adds 0 to each of the three).  The
+// weights of a 16-byte piece at K (a multiple of 16) are ONE aligned 16-byte load; it is taken where the row's dwords are
+// (K + 20 <= L, so it ends inside L + 4).  The last pieces read row and weights as bytes, weight 0 behind the end.
+// STORE = false: the norms alone (the pages' masked norms; `out` is not touched).  No LDS.
+template <bool STORE>
+__global__ __launch_bounds__(DIRECT_BLOCK) void direct_centre_valid_kernel(const uint8_t* __restrict__ src, int64_t stride, const long long* __restrict__ ofs,
+                                                                           int n, int64_t L, int64_t kp, const uint8_t* __restrict__ wgt,
+                                                                           uint4* __restrict__ out, unsigned long long* __restrict__ norm) {
+    const int lane = threadIdx.x & 63, h = lane >> 5;
+    const int r = blockIdx.x * 32 + (lane & 31);
+    const int64_t steps = kp / 32;
+    uint4* o = STORE ? out + (size_t)blockIdx.x * (size_t)steps * 64 + lane : nullptr;
+    const int64_t groups = steps / 4;
+    const int64_t g0 = (int64_t)blockIdx.y * (DIRECT_BLOCK / 64) + (threadIdx.x >> 6), gstep = (int64_t)gridDim.y * (DIRECT_BLOCK / 64);
+    const bool live = r < n;
+    const uint8_t* p = live ? src + (ofs ? (int64_t)ofs[r] : (int64_t)r * stride) : src;
+    const uint32_t sh = (uint32_t)(reinterpret_cast<uintptr_t>(p) & 3);
+    const uint32_t* q = reinterpret_cast<const uint32_t*>(p - sh);
+    const uint4* wq = reinterpret_cast<const uint4*>(wgt);
+    unsigned long long sq = 0;
+    for (int64_t g = g0; g < groups; g += gstep) {
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const int64_t s = g * 4 + t, c = 2 * s + h, k = c * 16;
+            uint32_t x[4] = {0u, 0u, 0u, 0u}, w[4] = {0u, 0u, 0u, 0u};
+            if (live) {
+                if (k + 20 <= L) {
+                    const uint32_t* d = q + c * 4;
+                    const uint32_t d0 = d[0], d1 = d[1], d2 = d[2], d3 = d[3], d4 = d[4];
+                    const uint4 wv = wq[c];
+                    x[0] = __builtin_amdgcn_alignbyte(d1, d0, sh); x[1] = __builtin_amdgcn_alignbyte(d2, d1, sh);
+                    x[2] = __builtin_amdgcn_alignbyte(d3, d2, sh); x[3] = __builtin_amdgcn_alignbyte(d4, d3, sh);
+                    w[0] = wv.x; w[1] = wv.y; w[2] = wv.z; w[3] = wv.w;
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        uint32_t v = 0, u = 0;
+#pragma unroll
+                        for (int b = 0; b < 4; ++b) {
+                            const int64_t i = k + j * 4 + b;
+                            if (i < L) { v |= (uint32_t)p[i] << (8 * b); u |= (uint32_t)wgt[i] << (8 * b); }
+                        }
+                        x[j] = v; w[j] = u;
+                    }
+                }
+                uint32_t s2 = 0, s1 = 0, nv = 0;                       // (16 bytes: at most 16 * 65 025, 16 * 255 and 16)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const uint32_t xm = x[j] & w[j];
+                    s2 = __builtin_amdgcn_udot4(xm, xm, s2, false);
+                    s1 = __builtin_amdgcn_udot4(xm, 0x01010101u, s1, false);
+                    nv = __builtin_amdgcn_udot4(w[j] & 0x01010101u, 0x01010101u, nv, false);
+                }
+                sq += s2 + 16384u * nv - 256u * s1;                    // (a sum of squares over the valid bytes: never negative)
+            }
+            if (STORE)
+                o[(size_t)s * 64] = make_uint4((x[0] ^ 0x80808080u) & w[0], (x[1] ^ 0x80808080u) & w[1], (x[2] ^ 0x80808080u) & w[2],
+                                               (x[3] ^ 0x80808080u) & w[3]);
         }
     }
     sq += __shfl_xor(sq, 32);

@@ -239,6 +239,10 @@ struct DirectClass {
     int64_t L = 0, kp = 0;                        // bytes of a small image, padded to the K granule
     std::vector<int32_t> pages;                   // the class's deck pages, ascending
     DevBuf d_op, d_norm, d_pages, d_all;          // operand, |b'|^2 (i64), the page list, the identity eligible list 0 .. np - 1
+    // SLIDEO_DIRECT_VALID: |b'|^2 over the valid bytes of the gate's validity map (i64 per page), built at the first look-up under
+    // a map of the class's small size and kept while the matcher's gate_map_gen equals norm_v_gen (0: none)
+    DevBuf d_norm_v;
+    uint64_t norm_v_gen = 0;
 };
 
 }  // namespace slideo
@@ -269,6 +273,9 @@ struct slideo_matcher {
     // one weight byte (0xFF valid, 0x00) per byte of the sw x sh small image of frames of the mask's size, n_valid valid pixels
     uint32_t mask_scope = SLIDEO_MASK_DETECT;
     struct GateMap { bool on = false; int sw = 0, sh = 0; int64_t n_valid = 0; slideo::DevBuf d_w; } gate_map;
+    // the map's generation: every call that can change the map (set_frame_mask, set_frame_mask_scope, set_working_size) moves it
+    // on, and what is derived from the map (the direct look-up's masked page norms) is cached under it
+    uint64_t gate_map_gen = 1;
 
     // INTER_AREA size classes
     std::vector<slideo::AreaGeom> area_geoms;
@@ -343,6 +350,7 @@ struct slideo_matcher {
     // direct page look-up (include/slideo_amd.h "Direct page look-up"): the direct similarity (0: off) and, built at the first use
     // with t > 0 after finalize, the deck's size classes
     float direct_t = 0.f;
+    uint32_t direct_scope = SLIDEO_DIRECT_WHOLE;      // slideo_matcher_set_direct_scope: VALID = the look-up over the gate's valid pixels
     bool direct_built = false;
     std::vector<std::unique_ptr<slideo::DirectClass>> direct_classes;
 
@@ -486,10 +494,13 @@ void page_set_check_mode(const slideo_matcher* m);
 void gate_release(slideo_matcher* m);          // the gate's events (slideo_matcher_destroy)
 inline void gate_state_reset(slideo_matcher* m) { m->gate = slideo_matcher::GateState{}; }
 // FrameSrc::staging_bytes' gate_small of a gated call (a small image has at most small_area pixels)
-// (under a direct similarity: + the frame's centred operand row, its row of dot products and its record)
+// (under a direct similarity: + the frame's centred operand row, its row of dot products and its record; under the direct scope
+// VALID + the masked page norms, 8 bytes per page once per matcher: counted with every frame, a unit has at least one)
 inline size_t gate_small_budget(const slideo_matcher* m) {
     const size_t small = (size_t)m->cfg.small_area * 3 + 64;
-    return m->direct_t > 0.f ? 2 * small + 128 + m->pages.size() * 8 + 64 : small;
+    if (!(m->direct_t > 0.f)) return small;
+    const size_t look = 2 * small + 128 + m->pages.size() * 8 + 64;
+    return m->direct_scope == SLIDEO_DIRECT_VALID ? look + m->pages.size() * 8 : look;
 }
 // a validated source's frames against the gate state: one size and one format family since the last reset (SLIDEO_ERR_STATE)
 void gate_check(const slideo_matcher* m, const FrameSrc& src);
@@ -520,13 +531,18 @@ int64_t gate_ssd_threshold(float changed_similarity_, int64_t n);
 // the largest SSD whose host similarity over n pixels is >= t (slideo_direct_ssd_threshold; -1: none)
 int64_t direct_ssd_threshold(float t, int64_t n);
 // t > 0 together with a frame mask under the GATE scope (SLIDEO_ERR_UNSUPPORTED): checked by whichever of the three set calls
-// would complete the combination, before it changes anything
-void direct_check_mask(bool mask_set, uint32_t scope, float t);
+// would complete the combination, before it changes anything; never under the direct scope SLIDEO_DIRECT_VALID
+void direct_check_mask(bool mask_set, uint32_t scope, float t, uint32_t direct_scope);
 // What a gated unit of n frames with sw x sh small images looks up in: everything that can fail for want of memory — the page
 // operand at its first use, the selected set's eligible list, the slot's workspaces — happens here, in front of any change to the
 // gate state.  cls == null: no page of the set shares the small size, the unit does not look up.
-struct DirectPlan { const DirectClass* cls = nullptr; const int32_t* elig = nullptr; int ne = 0; };
-DirectPlan direct_unit_prepare(slideo_matcher* m, Slot& S, int n, int sw, int sh);
+// weights: the gate's validity map (gate_map_for) under SLIDEO_DIRECT_VALID, null otherwise: the look-up then runs over the valid
+// bytes — the frames' operand masked, bnorm the class's masked page norms (built here when the map's generation has moved on).
+struct DirectPlan {
+    const DirectClass* cls = nullptr; const int32_t* elig = nullptr; int ne = 0;
+    const uint8_t* weights = nullptr; const long long* bnorm = nullptr;
+};
+DirectPlan direct_unit_prepare(slideo_matcher* m, Slot& S, int n, int sw, int sh, const uint8_t* weights);
 // The look-up on S.st, behind the unit's small images (S.d_gsmall) and in front of gate_kernel: the frames' operand,
 // page_ssd_kernel over all n frames, direct_best_kernel over the eligible pages.  Launches only.
 void direct_unit_lookup(Slot& S, const DirectPlan& plan, int n);

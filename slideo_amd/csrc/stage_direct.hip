@@ -23,10 +23,11 @@ int64_t direct_ssd_threshold(float t, int64_t n) {
     return lo;
 }
 
-void direct_check_mask(bool mask_set, uint32_t scope, float t) {
+void direct_check_mask(bool mask_set, uint32_t scope, float t, uint32_t direct_scope) {
+    if (direct_scope == SLIDEO_DIRECT_VALID) return;                   // (the look-up compares what the gate compares)
     if (t > 0.f && mask_set && (scope & SLIDEO_MASK_GATE))
         fail(SLIDEO_ERR_UNSUPPORTED, "the direct page look-up compares whole small images: not together with a frame mask under SLIDEO_MASK_GATE "
-             "(a look-up over the valid pixels only is not implemented)");
+             "(a look-up over the valid pixels only: slideo_matcher_set_direct_scope(m, SLIDEO_DIRECT_VALID))");
 }
 
 namespace {
@@ -34,14 +35,25 @@ namespace {
 int64_t direct_kp(int64_t L) { return cdiv64(L, DIRECT_KGRAN) * DIRECT_KGRAN; }
 int direct_rows_pad(int rows) { return cdiv(rows, DIRECT_TILE) * DIRECT_TILE; }
 
+// weights (the gate's validity map, SLIDEO_DIRECT_VALID; null: whole images): the operand zero at the masked bytes, the norms over
+// the valid ones; out null (weights only): the norms alone
 void launch_centre(const uint8_t* src, int64_t stride, const long long* ofs, int n, int rows_pad, int64_t L, int64_t kp, uint4* out,
-                   long long* norm, hipStream_t st) {
+                   long long* norm, hipStream_t st, const uint8_t* weights = nullptr) {
     // 32-row tiles x K slices: about 2048 waves, a wave at least one group of four K steps; the norms are added to
     const int tiles = rows_pad / 32;
     const int ky = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv64(512, tiles), cdiv64(kp / DIRECT_KGRAN, DIRECT_BLOCK / 64)));
     HIP_CHECK(hipMemsetAsync(norm, 0, (size_t)n * 8, st));
-    direct_centre_kernel<<<dim3(tiles, ky), DIRECT_BLOCK, 0, st>>>(src, stride, ofs, n, L, kp, out, reinterpret_cast<unsigned long long*>(norm));
-    check_launch("direct_centre_kernel");
+    unsigned long long* nrm = reinterpret_cast<unsigned long long*>(norm);
+    if (!weights) {
+        direct_centre_kernel<<<dim3(tiles, ky), DIRECT_BLOCK, 0, st>>>(src, stride, ofs, n, L, kp, out, nrm);
+        check_launch("direct_centre_kernel");
+    } else if (out) {
+        direct_centre_valid_kernel<true><<<dim3(tiles, ky), DIRECT_BLOCK, 0, st>>>(src, stride, ofs, n, L, kp, weights, out, nrm);
+        check_launch("direct_centre_valid_kernel");
+    } else {
+        direct_centre_valid_kernel<false><<<dim3(tiles, ky), DIRECT_BLOCK, 0, st>>>(src, stride, ofs, n, L, kp, weights, nullptr, nrm);
+        check_launch("direct_centre_valid_kernel (norms)");
+    }
 }
 
 // The deck's size classes and their operands, on m->stream (finalized, idle matcher or the first gated unit under t > 0: nothing
@@ -87,10 +99,38 @@ void direct_build(slideo_matcher* m) {
     m->direct_built = true;
 }
 
-const DirectClass* direct_class_for(slideo_matcher* m, int sw, int sh) {
+DirectClass* direct_class_for(slideo_matcher* m, int sw, int sh) {
     direct_build(m);
     for (auto& k : m->direct_classes) if (k->sw == sw && k->sh == sh) return k.get();
     return nullptr;
+}
+
+// The masked page norms of class c under the matcher's current validity map (SLIDEO_DIRECT_VALID): sum over the valid bytes of
+// b'^2 per page, cached with the class under the map's generation.  On m->stream, synchronised: the map changes on an idle
+// matcher only, so the unit that finds the norms stale is the only one in flight.  The deck operand is neither rebuilt nor copied.
+const long long* direct_masked_norms(slideo_matcher* m, DirectClass& c) {
+    const slideo_matcher::GateMap& g = m->gate_map;
+    if (!g.on || g.sw != c.sw || g.sh != c.sh)
+        fail(SLIDEO_ERR_HIP, "internal: the gate's validity map is %dx%d (%d), the class's small images are %dx%d", g.sw, g.sh, (int)g.on, c.sw, c.sh);
+    if (c.norm_v_gen == m->gate_map_gen) return c.d_norm_v.as<long long>();
+    hipStream_t st = m->stream;
+    std::vector<long long> ofs((size_t)c.np);
+    {
+        std::vector<long long> small_ofs(m->pages.size());
+        long long o = 0;
+        for (size_t p = 0; p < m->pages.size(); ++p) { small_ofs[p] = o; o += (long long)m->pages[p].small_img.size(); }
+        for (int i = 0; i < c.np; ++i) ofs[i] = small_ofs[c.pages[i]];
+    }
+    c.norm_v_gen = 0;
+    c.d_norm_v.reserve((size_t)c.np * 8);
+    DevBuf d_ofs;
+    d_ofs.reserve((size_t)c.np * 8);
+    HIP_CHECK(hipMemcpyAsync(d_ofs.p, ofs.data(), ofs.size() * 8, hipMemcpyHostToDevice, st));
+    launch_centre(m->d_page_small.as<uint8_t>(), 0, d_ofs.as<long long>(), c.np, c.np_pad, c.L, c.kp, nullptr, c.d_norm_v.as<long long>(), st,
+                  g.d_w.as<uint8_t>());
+    HIP_CHECK(hipStreamSynchronize(st));
+    c.norm_v_gen = m->gate_map_gen;
+    return c.d_norm_v.as<long long>();
 }
 
 // the eligible pages of `set` in class c: positions in c.pages (device, ascending) and their count
@@ -129,9 +169,10 @@ void direct_reserve(Slot& S, const DirectClass& c, int n) {
 
 // n small images at `small` (stride L, device) against class c: S.d_dir_a, S.d_dir_rec's norms and S.d_dir_dot (direct_reserve)
 // filled on st
-void direct_dots(Slot& S, const DirectClass& c, const uint8_t* small, int n, hipStream_t st) {
+// (weights: the gate's validity map, the frames' operand masked; null: today's launch)
+void direct_dots(Slot& S, const DirectClass& c, const uint8_t* small, int n, hipStream_t st, const uint8_t* weights) {
     const int n_pad = direct_rows_pad(n);
-    launch_centre(small, c.L, nullptr, n, n_pad, c.L, c.kp, S.d_dir_a.as<uint4>(), S.d_dir_rec.as<long long>(), st);
+    launch_centre(small, c.L, nullptr, n, n_pad, c.L, c.kp, S.d_dir_a.as<uint4>(), S.d_dir_rec.as<long long>(), st, weights);
     HIP_CHECK(hipMemsetAsync(S.d_dir_dot.p, 0, (size_t)n * c.np * 8, st));
     const int64_t kchunk = direct_kchunk(n, c.np, c.kp);
     const int64_t nz = cdiv64(c.kp, kchunk);
@@ -145,23 +186,25 @@ DirectBest* direct_best_of(Slot& S, int n) { return reinterpret_cast<DirectBest*
 
 }  // namespace
 
-DirectPlan direct_unit_prepare(slideo_matcher* m, Slot& S, int n, int sw, int sh) {
+DirectPlan direct_unit_prepare(slideo_matcher* m, Slot& S, int n, int sw, int sh, const uint8_t* weights) {
     DirectPlan plan;
-    const DirectClass* c = direct_class_for(m, sw, sh);
+    DirectClass* c = direct_class_for(m, sw, sh);
     if (!c) return plan;
     int ne = 0;
     const int32_t* elig = direct_eligible(m, *c, m->cur_set, &ne);
     if (ne == 0) return plan;
     direct_reserve(S, *c, n);
     plan.cls = c; plan.elig = elig; plan.ne = ne;
+    plan.weights = weights;
+    plan.bnorm = weights ? direct_masked_norms(m, *c) : c->d_norm.as<long long>();
     return plan;
 }
 
 void direct_unit_lookup(Slot& S, const DirectPlan& plan, int n) {
     const DirectClass* c = plan.cls;
     hipStream_t st = S.st;
-    direct_dots(S, *c, S.d_gsmall.as<uint8_t>(), n, st);
-    direct_best_kernel<<<n, DIRECT_BLOCK, 0, st>>>(S.d_dir_dot.as<unsigned long long>(), c->np, S.d_dir_rec.as<long long>(), c->d_norm.as<long long>(),
+    direct_dots(S, *c, S.d_gsmall.as<uint8_t>(), n, st, plan.weights);
+    direct_best_kernel<<<n, DIRECT_BLOCK, 0, st>>>(S.d_dir_dot.as<unsigned long long>(), c->np, S.d_dir_rec.as<long long>(), plan.bnorm,
                                                    c->d_pages.as<int32_t>(), plan.elig, plan.ne, direct_best_of(S, n), nullptr, 0);
     check_launch("direct_best_kernel");
 }
@@ -202,7 +245,7 @@ int32_t slideo_matcher_set_direct_similarity(slideo_matcher* m, float t) {
     API_TRY
     if (!(t >= 0.f) || t > 1.f) fail(SLIDEO_ERR_INVALID_ARG, "direct similarity %g: 0 (off) or 0 < t <= 1", (double)t);
     require_idle(m);
-    direct_check_mask(m->mask.set, m->mask_scope, t);
+    direct_check_mask(m->mask.set, m->mask_scope, t, m->direct_scope);
     m->direct_t = t;
     API_CATCH(m)
 }
@@ -213,37 +256,76 @@ int32_t slideo_matcher_direct_similarity(const slideo_matcher* m, float* t) {
     return SLIDEO_OK;
 }
 
-int32_t slideo_page_small_ssd(slideo_matcher* m, const uint8_t* small, int32_t n, int32_t sw, int32_t sh, uint64_t* ssd_out) {
+int32_t slideo_matcher_set_direct_scope(slideo_matcher* m, uint32_t scope) {
     if (!m) return SLIDEO_ERR_INVALID_ARG;
     API_TRY
+    if (scope != SLIDEO_DIRECT_WHOLE && scope != SLIDEO_DIRECT_VALID)
+        fail(SLIDEO_ERR_INVALID_ARG, "direct scope %u: SLIDEO_DIRECT_WHOLE (0) or SLIDEO_DIRECT_VALID (1)", scope);
+    require_idle(m);
+    direct_check_mask(m->mask.set, m->mask_scope, m->direct_t, scope);    // (the way back to WHOLE: the scope before stays in force)
+    m->direct_scope = scope;
+    API_CATCH(m)
+}
+
+int32_t slideo_matcher_direct_scope(const slideo_matcher* m, uint32_t* scope) {
+    if (!m || !scope) return SLIDEO_ERR_INVALID_ARG;
+    *scope = m->direct_scope;
+    return SLIDEO_OK;
+}
+
+// slideo_page_small_ssd (valid false) and slideo_page_small_ssd_valid (true: under the matcher's current validity map)
+static void page_small_ssd_impl(slideo_matcher* m, const uint8_t* small, int32_t n, int32_t sw, int32_t sh, uint64_t* ssd_out, bool valid) {
     if (!m->finalized) fail(SLIDEO_ERR_STATE, "slideo_matcher_finalize_pages must be called before the page look-up");
     if (n < 0 || sw < 1 || sh < 1 || (int64_t)sw * sh > m->cfg.small_area || (n > 0 && (!small || !ssd_out)))
         fail(SLIDEO_ERR_INVALID_ARG, "page_small_ssd: %d small images of %dx%d (at most small_area = %d pixels), small and ssd_out not null", n, sw, sh,
              m->cfg.small_area);
+    const uint8_t* weights = nullptr;
+    if (valid) {
+        const slideo_matcher::GateMap& g = m->gate_map;
+        if (!m->mask.set || !(m->mask_scope & SLIDEO_MASK_GATE) || !g.on)
+            fail(SLIDEO_ERR_STATE, "page_small_ssd_valid: no validity map is in force (a frame mask under SLIDEO_MASK_GATE)");
+        if (sw != g.sw || sh != g.sh)
+            fail(SLIDEO_ERR_INVALID_ARG, "page_small_ssd_valid: %dx%d small images, the validity map is %dx%d", sw, sh, g.sw, g.sh);
+        weights = g.d_w.as<uint8_t>();
+    }
     HIP_CHECK(hipSetDevice(m->device));
     require_idle(m);
-    if (n == 0) return SLIDEO_OK;
+    if (n == 0) return;
     const int P = (int)m->pages.size();
     const size_t out_n = (size_t)n * P;
     for (size_t i = 0; i < out_n; ++i) ssd_out[i] = UINT64_MAX;
-    const DirectClass* c = direct_class_for(m, sw, sh);
-    if (!c) return SLIDEO_OK;
+    DirectClass* c = direct_class_for(m, sw, sh);
+    if (!c) return;
     Slot& S = m->slots[0];
     hipStream_t st = S.st;
     const size_t sb = (size_t)sw * sh * 3;
     DevBuf d_small, d_out;
     d_small.reserve(sb * n);
     d_out.reserve(out_n * 8);
+    const long long* bnorm = weights ? direct_masked_norms(m, *c) : c->d_norm.as<long long>();
     HIP_CHECK(hipMemcpyAsync(d_small.p, small, sb * n, hipMemcpyHostToDevice, st));
     HIP_CHECK(hipMemsetAsync(d_out.p, 0xFF, out_n * 8, st));
     direct_reserve(S, *c, n);
-    direct_dots(S, *c, d_small.as<uint8_t>(), n, st);
-    direct_best_kernel<<<n, DIRECT_BLOCK, 0, st>>>(S.d_dir_dot.as<unsigned long long>(), c->np, S.d_dir_rec.as<long long>(), c->d_norm.as<long long>(),
+    direct_dots(S, *c, d_small.as<uint8_t>(), n, st, weights);
+    direct_best_kernel<<<n, DIRECT_BLOCK, 0, st>>>(S.d_dir_dot.as<unsigned long long>(), c->np, S.d_dir_rec.as<long long>(), bnorm,
                                                    c->d_pages.as<int32_t>(), c->d_all.as<int32_t>(), c->np, direct_best_of(S, n),
                                                    d_out.as<unsigned long long>(), P);
     check_launch("direct_best_kernel");
     HIP_CHECK(hipMemcpyAsync(ssd_out, d_out.p, out_n * 8, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
+}
+
+int32_t slideo_page_small_ssd(slideo_matcher* m, const uint8_t* small, int32_t n, int32_t sw, int32_t sh, uint64_t* ssd_out) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    page_small_ssd_impl(m, small, n, sw, sh, ssd_out, false);
+    API_CATCH(m)
+}
+
+int32_t slideo_page_small_ssd_valid(slideo_matcher* m, const uint8_t* small, int32_t n, int32_t sw, int32_t sh, uint64_t* ssd_out) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    page_small_ssd_impl(m, small, n, sw, sh, ssd_out, true);
     API_CATCH(m)
 }
 

@@ -125,7 +125,10 @@ void gate_unit_submit(slideo_matcher* m, Slot& S, const FrameSrc& src, int first
     int psw = 0, psh = 0;
     if (look) {
         small_size(src.unit_w(), src.unit_h(), m->cfg.small_area, psw, psh);
-        plan = direct_unit_prepare(m, S, n, psw, psh);
+        // the direct scope VALID: over the pixels the gate compares (null without a map in force: whole images)
+        int npx_ = 0;
+        const uint8_t* dw = m->direct_scope == SLIDEO_DIRECT_VALID ? gate_map_for(m, src.unit_w(), src.unit_h(), psw, psh, &npx_) : nullptr;
+        plan = direct_unit_prepare(m, S, n, psw, psh, dw);
     }
     const DevFrames all = stage_frames(m, S, src, first, n, cs, &S.d_gstage);
     int sw = 0, sh = 0;

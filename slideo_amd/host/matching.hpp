@@ -342,6 +342,10 @@ public:
     // verify (full-screen slide frames of a screen recording; the reference never decides without keypoints).  Not together with
     // SLIDEO_MASK_GATE.  Default 0: off
     HipImageVideoMatcher& with_direct_similarity(float t) { direct_t_ = t; return *this; }
+    // What the direct page look-up compares (slideo_group_set_direct_scope, include/slideo_amd.h "Direct look-up scope"):
+    // SLIDEO_DIRECT_WHOLE (default: whole small images, refused beside SLIDEO_MASK_GATE) or SLIDEO_DIRECT_VALID (the valid pixels
+    // of the gate's validity map: a full-screen slide under a speaker thumbnail).  Applied before the direct similarity
+    HipImageVideoMatcher& with_direct_scope(uint32_t scope) { direct_scope_ = scope; return *this; }
     // false: tasks run the stop-and-go pair slideo_group_changed_mask_bgr8 + slideo_group_match_kept_frames in place of the group's
     // gated call (the same timeline; for comparisons).  Default: gated
     HipImageVideoMatcher& with_changed_gate(bool on) { gated_ = on; return *this; }
@@ -364,6 +368,7 @@ public:
         }
         if (mask_scope_ != SLIDEO_MASK_DETECT) h->check(slideo_group_set_frame_mask_scope(h->g, mask_scope_));
         if (!mask_.empty()) h->check(slideo_group_set_frame_mask(h->g, mask_.data(), mask_w_, mask_h_, mask_w_));
+        if (direct_scope_ != SLIDEO_DIRECT_WHOLE) h->check(slideo_group_set_direct_scope(h->g, direct_scope_));
         if (direct_t_ != 0.f) h->check(slideo_group_set_direct_similarity(h->g, direct_t_));
         h->check(slideo_group_set_progress(h->g, detail::tramp, &reporter));                         // "Analyzing PDF pages..." protocol, mo/lib.rs:43-58
         const size_t CH = 32 * (size_t)h->n_devices;
@@ -385,7 +390,7 @@ private:
     int32_t work_w_ = 0, work_h_ = 0;
     std::vector<uint8_t> mask_;
     int32_t mask_w_ = 0, mask_h_ = 0;
-    uint32_t mask_scope_ = SLIDEO_MASK_DETECT;
+    uint32_t mask_scope_ = SLIDEO_MASK_DETECT, direct_scope_ = SLIDEO_DIRECT_WHOLE;
     slideo_config cfg_;
     ImageLoader loader_;
 };

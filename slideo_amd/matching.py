@@ -297,7 +297,7 @@ class HipImageVideoMatcher:
     """Drop-in for OpenCVImageVideoMatcher (lib.rs:34-73) behind matching::ImageVideoMatcher."""
 
     def __init__(self, cfg=None, device=None, sift=None, devices=None, working_size=None, frame_mask=None, frame_mask_scope=None,
-                 direct_similarity=None):
+                 direct_similarity=None, direct_scope=None):
         """devices: HIP ordinals, one matcher each behind one slideo_group (the reference fans out over the whole machine, the
         global rayon pool of lib.rs:45,174); None = every gfx950 device of the node; `device` = d is short for devices = [d].
         sift = (slideo_sift_config, ratio): the north-star's SIFT + L2 front end instead of the reference's ORB + Hamming
@@ -312,12 +312,17 @@ class HipImageVideoMatcher:
         slide as changed; None = the default, MASK_DETECT.
         direct_similarity = t in (0, 1] (slideo_group_set_direct_similarity): a changed frame whose small image is at least that
         similar to a page's is resolved to that page without ORB, search or verify — full-screen slide frames of a screen
-        recording (the reference never decides without keypoints); not together with MASK_GATE; None = off."""
+        recording (the reference never decides without keypoints); not together with MASK_GATE unless direct_scope says so;
+        None = off.
+        direct_scope = _capi.DIRECT_WHOLE or _capi.DIRECT_VALID (slideo_group_set_direct_scope): with DIRECT_VALID the look-up
+        compares what the gate compares, the valid pixels of the gate's validity map, so MASK_GATE and direct_similarity work
+        together (a full-screen slide under a speaker thumbnail); applied before direct_similarity; None = DIRECT_WHOLE."""
         self._cfg, self._sift = cfg, sift
         self._working_size = working_size
         self._frame_mask = frame_mask
         self._frame_mask_scope = frame_mask_scope
         self._direct_similarity = direct_similarity
+        self._direct_scope = direct_scope
         self._devices = [device] if device is not None else devices
 
     def create_video_matcher(self, images, progress_reporter: ProgressReporter) -> HipVideoMatcher:
@@ -332,6 +337,8 @@ class HipImageVideoMatcher:
             m.set_frame_mask_scope(self._frame_mask_scope)
         if self._frame_mask is not None:
             m.set_frame_mask(self._frame_mask)
+        if self._direct_scope is not None:
+            m.set_direct_scope(self._direct_scope)
         if self._direct_similarity is not None:
             m.set_direct_similarity(self._direct_similarity)
         m.set_progress(progress_reporter.report)        # "Analyzing PDF pages..." protocol, lib.rs:43-58
