@@ -473,6 +473,42 @@ extern "C" {
         sh: i32,
         ssd_out: *mut u64,
     ) -> i32;
+    // frame region (include/slideo_amd.h "Frame region"): frames stand for a rectified quadrilateral of themselves
+    pub fn slideo_matcher_set_frame_region(
+        m: *mut slideo_matcher,
+        src_w: i32,
+        src_h: i32,
+        m9: *const f64,
+        out_w: i32,
+        out_h: i32,
+    ) -> i32;
+    pub fn slideo_matcher_frame_region(
+        m: *const slideo_matcher,
+        src_w: *mut i32,
+        src_h: *mut i32,
+        m9_out: *mut f64,
+        out_w: *mut i32,
+        out_h: *mut i32,
+        is_set: *mut i32,
+    ) -> i32;
+    pub fn slideo_group_set_frame_region(
+        g: *mut slideo_group,
+        src_w: i32,
+        src_h: i32,
+        m9: *const f64,
+        out_w: i32,
+        out_h: i32,
+    ) -> i32;
+    pub fn slideo_frame_region_from_quad(quad: *const f64, out_w: i32, out_h: i32, m9_out: *mut f64) -> i32;
+    pub fn slideo_rectify_bgr8(
+        m: *mut slideo_matcher,
+        bgr: *const u8,
+        width: i32,
+        height: i32,
+        stride_bytes: i32,
+        out: *mut u8,
+        out_capacity: i64,
+    ) -> i32;
 }
 
 /// The struct layouts above are only valid for one ABI version of the library.

@@ -86,6 +86,11 @@ pub struct HipImageVideoMatcher {
     /// images, refused beside SLIDEO_MASK_GATE) or ffi::SLIDEO_DIRECT_VALID (the valid pixels of the gate's validity map: a
     /// full-screen slide under a speaker thumbnail).  Applied before direct_similarity.
     pub direct_scope: u32,
+    /// Some((src_w, src_h, quad, out_w, out_h)): the frame region (slideo_group_set_frame_region): frames of src_w x src_h
+    /// stand for the out_w x out_h image rectified from the quad — the source coordinates x, y of the slide's top-left,
+    /// top-right, bottom-right and bottom-left corner (slideo_frame_region_from_quad): a filmed projection screen, a slide
+    /// in a sub-window.  The reference analyses the whole frame.  None (default) = no region.
+    pub frame_region: Option<(i32, i32, [f64; 8], i32, i32)>,
 }
 
 impl Default for HipImageVideoMatcher {
@@ -97,6 +102,7 @@ impl Default for HipImageVideoMatcher {
             frame_mask_scope: ffi::SLIDEO_MASK_DETECT,
             direct_similarity: 0.0,
             direct_scope: ffi::SLIDEO_DIRECT_WHOLE,
+            frame_region: None,
         }
     }
 }
@@ -124,6 +130,11 @@ impl<'i> ImageVideoMatcher<'i> for HipImageVideoMatcher {
                 let mut sc = std::mem::MaybeUninit::<ffi::slideo_sift_config>::uninit();
                 ffi::slideo_sift_config_default(sc.as_mut_ptr());
                 check(h, ffi::slideo_group_use_sift(h, sc.as_ptr(), ratio));
+            }
+            if let Some((sw, sh, quad, ow, oh)) = &self.frame_region {
+                let mut m9 = [0f64; 9];
+                check(std::ptr::null_mut(), ffi::slideo_frame_region_from_quad(quad.as_ptr(), *ow, *oh, m9.as_mut_ptr()));
+                check(h, ffi::slideo_group_set_frame_region(h, *sw, *sh, m9.as_ptr(), *ow, *oh));
             }
             if self.frame_mask_scope != ffi::SLIDEO_MASK_DETECT {
                 check(h, ffi::slideo_group_set_frame_mask_scope(h, self.frame_mask_scope));

@@ -700,6 +700,55 @@ int32_t     slideo_group_set_working_size(slideo_group* g, int32_t max_w, int32_
 int32_t     slideo_reduce_bgr8(slideo_matcher* m, const uint8_t* bgr, int32_t width, int32_t height, int32_t stride_bytes,
                                int32_t dw, int32_t dh, uint8_t* out, int64_t out_capacity);
 
+/* ---- Frame region (extension: the reference analyses the whole frame) -----------------------------------------------------------
+ * [OCV — recalled, unpinned, like the rest of SURVEY.md Appendix A: OpenCV 4.5.2 imgproc/imgwarp.cpp WarpPerspectiveInvoker and
+ * remapBilinear, INTER_BITS 5, INTER_TAB_SIZE 32, INTER_REMAP_COEF_BITS 15.]
+ * A matcher carries an optional FRAME REGION: a fixed 3x3 map M from a rectified out_w x out_h image into source frames of
+ * src_w x src_h.  While one is set, a frame call whose source size is (src_w, src_h) STANDS FOR
+ *     R = cv::warpPerspective(frame, M, Size(out_w, out_h), INTER_LINEAR | WARP_INVERSE_MAP, BORDER_REPLICATE)
+ * made on the GPU in front of the pipeline (csrc/frame_region.hip.h).  A 4:2:0 frame is converted first ("YUV 4:2:0 frames").
+ * Coordinates, for destination pixel (x, y), every product and sum rounded on its own in float64, nothing fused:
+ *     bw0 = max(1, min(1024 / max(min(16, out_h), 1), out_w));  xb = (x / bw0) * bw0;  x1 = x - xb
+ *     X0 = M0*xb + M1*y + M2;  Y0 = M3*xb + M4*y + M5;  W0 = M6*xb + M7*y + M8;  W = W0 + M6*x1;  W = W != 0 ? 32.0 / W : 0
+ *     fX = clamp((X0 + M0*x1) * W, INT_MIN, INT_MAX);  X = (int)rint(fX);   Y likewise from Y0, M3
+ * Taps: sx = X >> 5, ax = X & 31, sy = Y >> 5, ay = Y & 31; the four taps p00 p01 / p10 p11 at columns clamp(sx | sx + 1, 0, src_w - 1)
+ * and rows clamp(sy | sy + 1, 0, src_h - 1); the bilinear table's weights at 1/32 steps are exact integers, so per channel
+ *     R = (p00*(32-ax)*(32-ay) + p01*ax*(32-ay) + p10*(32-ax)*ay + p11*ax*ay + 512) >> 10
+ * Contract: every frame call made under a region — BGR and YUV 4:2:0, host and device, sync and submit / collect, the mask calls
+ * and slideo_match_kept_frames, the gated calls and slideo_matcher_gate_reset_from_frame_*, the group's calls — returns, bit for
+ * bit, what the same call without a region returns on the rectified images: verdicts, the slideo_last_frame_candidates trace,
+ * changed flags, similarities, the last small image and direct verdicts.  COORDINATES in traces and transforms are those of the
+ * RECTIFIED image.  The rectified image is what slideo_rectify_bgr8 returns.  Pages are never rectified.
+ * A frame call at another source size than (src_w, src_h) is SLIDEO_ERR_INVALID_ARG (both sizes in the message): it is not
+ * silently left unrectified.  The small_area limit and SIFT's side limit apply to (out_w, out_h); a frame mask's size is
+ * (out_w, out_h).  WORKING SIZE: the source frame of a rectifying call is exempt from it, and the output must fit it: a region
+ * whose output exceeds a set working size, or a working size smaller than a set region's output, is SLIDEO_ERR_UNSUPPORTED at
+ * whichever set call comes second (the caller chooses the output size, so nothing is lost).
+ * Out of scope: uploading only the region's bounding rows of host frames; a per-call or moving region; finding the quad; a region
+ * together with a larger working size.
+ * DEPARTURE: the reference never rectifies a frame.  With a region set, verdicts are those of the rectified video; off by default. */
+/* M: 9 doubles, row-major, copied; NULL clears the region (the other arguments are then ignored).  Before or after finalize, any
+ * number of times.  SLIDEO_ERR_STATE with units in flight.  SLIDEO_ERR_INVALID_ARG, the rule named: a non-finite M; W = M6 x + M7 y
+ * + M8 zero or of two signs over the four corners of the destination rectangle; out_w or out_h outside 1..4096; a source size
+ * outside 1..4096.  Ends the kept frames of an earlier mask call and resets the gate state to "none". */
+int32_t     slideo_matcher_set_frame_region(slideo_matcher* m, int32_t src_w, int32_t src_h, const double* M, int32_t out_w, int32_t out_h);
+/* The region as set (is_set 0: none; the sizes are then 0 and M_out the identity). */
+int32_t     slideo_matcher_frame_region(const slideo_matcher* m, int32_t* src_w, int32_t* src_h, double* M_out, int32_t* out_w,
+                                        int32_t* out_h, int32_t* is_set);
+/* Forwards to every member and resets the group's gate state. */
+int32_t     slideo_group_set_frame_region(slideo_group* g, int32_t src_w, int32_t src_h, const double* M, int32_t out_w, int32_t out_h);
+/* The map of a quad, a pure host function (no device).  quad: the source coordinates (pixel centres) x, y of the slide's top-left,
+ * top-right, bottom-right and bottom-left corner; M_out maps (0, 0), (out_w-1, 0), (out_w-1, out_h-1), (0, out_h-1) onto them.
+ * The library's own definition (not getPerspectiveTransform's bits): an axis-aligned rectangle in closed form, M = [(x1-x0)/(out_w-1)
+ * 0 x0; 0 (y1-y0)/(out_h-1) y0; 0 0 1] — an integer rectangle with out equal to its size is the crop, every ax = ay = 0 and R the
+ * source sub-image byte for byte — and any other quad by Gaussian elimination with partial pivoting on the 8x8 system with M8 = 1,
+ * in float64.  SLIDEO_ERR_INVALID_ARG: a null argument, out_w or out_h outside 2..4096, a degenerate (collinear) or non-convex quad. */
+int32_t     slideo_frame_region_from_quad(const double* quad, int32_t out_w, int32_t out_h, double* M_out);
+/* Tap: R of one host image under the matcher's region (out: stride out_w * 3, out_capacity >= out_w * out_h * 3).  No small_area
+ * limit.  SLIDEO_ERR_STATE without a region; SLIDEO_ERR_INVALID_ARG at another size than the region's source. */
+int32_t     slideo_rectify_bgr8(slideo_matcher* m, const uint8_t* bgr, int32_t width, int32_t height, int32_t stride_bytes, uint8_t* out,
+                                int64_t out_capacity);
+
 /* ---- Frame mask (cv::ORB::detectAndCompute's `mask` argument; the reference passes no_array(), mo/feature_extractor.rs:35) ----------
  * [OCV — recalled, unpinned, like the rest of SURVEY.md Appendix A: OpenCV 4.5.2 features2d/orb.cpp detectAndCompute /
  * computeKeyPoints and KeyPointsFilter::runByPixelsMask.]

@@ -145,6 +145,8 @@ EXPORTS = [
     "slideo_matcher_set_direct_similarity", "slideo_matcher_direct_similarity", "slideo_group_set_direct_similarity",
     "slideo_direct_ssd_threshold", "slideo_page_small_ssd",
     "slideo_matcher_set_direct_scope", "slideo_matcher_direct_scope", "slideo_group_set_direct_scope", "slideo_page_small_ssd_valid",
+    "slideo_matcher_set_frame_region", "slideo_matcher_frame_region", "slideo_group_set_frame_region", "slideo_frame_region_from_quad",
+    "slideo_rectify_bgr8",
 ]
 
 # frame mask scope (include/slideo_amd.h "Frame mask scope")
@@ -236,6 +238,13 @@ def lib():
             L.slideo_matcher_direct_scope.argtypes = [vp, vp]
             L.slideo_group_set_direct_scope.argtypes = [vp, u32]
             L.slideo_page_small_ssd_valid.argtypes = [vp, vp, i32, i32, i32, vp]
+        if hasattr(L, "slideo_matcher_set_frame_region"):
+            vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
+            L.slideo_matcher_set_frame_region.argtypes = [vp, i32, i32, vp, i32, i32]
+            L.slideo_matcher_frame_region.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+            L.slideo_group_set_frame_region.argtypes = [vp, i32, i32, vp, i32, i32]
+            L.slideo_frame_region_from_quad.argtypes = [vp, i32, i32, vp]
+            L.slideo_rectify_bgr8.argtypes = [vp, vp, i32, i32, i32, vp, i64]
         _lib = L
     return _lib
 
@@ -443,8 +452,59 @@ class _FrameCalls:
         check(lib().slideo_frame_mask_small(h, _p(out), C.c_int64(out.size), C.byref(sw), C.byref(sh), C.byref(nv)))
         return out == 255, int(nv.value)
 
+    # frame region (include/slideo_amd.h "Frame region"): frames of the region's source size stand for their rectified image
+    def set_frame_region(self, src_w, src_h, M, out_w, out_h):
+        """M: a 3x3 map (9 floats) from the rectified out_w x out_h image into src_w x src_h frames, or a quad — 4 (x, y) source
+        corners: top-left, top-right, bottom-right, bottom-left (frame_region_from_quad).  The matcher must be idle."""
+        M = np.asarray(M, np.float64)
+        if M.size == 8:
+            M = frame_region_from_quad(M, out_w, out_h)
+        if M.size != 9:
+            raise SlideoError(1, "set_frame_region: expected a 3x3 map or a 4x2 quad")
+        M = np.ascontiguousarray(M.reshape(9))
+        self._check(getattr(lib(), self._SETS + "set_frame_region")(self._h, int(src_w), int(src_h), _p(M), int(out_w), int(out_h)))
+
+    def clear_frame_region(self):
+        self._check(getattr(lib(), self._SETS + "set_frame_region")(self._h, 0, 0, None, 0, 0))
+
+    @property
+    def frame_region(self):
+        """(src_w, src_h, M [3, 3], out_w, out_h), or None."""
+        if not hasattr(lib(), "slideo_matcher_frame_region"):       # (SLIDEO_LIB_PATH may name an older build: tools/ab_libs.sh)
+            return None
+        h = self._mask_owner()
+        v = [C.c_int32() for _ in range(5)]
+        M = np.zeros(9, np.float64)
+        rc = lib().slideo_matcher_frame_region(h, C.byref(v[0]), C.byref(v[1]), _p(M), C.byref(v[2]), C.byref(v[3]), C.byref(v[4]))
+        if rc != OK:
+            raise SlideoError(rc, "frame_region")
+        return (v[0].value, v[1].value, M.reshape(3, 3), v[2].value, v[3].value) if v[4].value else None
+
+    def rectify(self, bgr):
+        """The rectified image of one host image under the region (the rectify tap; a Group: member 0's)."""
+        bgr = _img3(bgr)
+        h, w, _ = bgr.shape
+        return self.rectify_pitched(bgr, w, h, w * 3)
+
+    def rectify_pitched(self, buf, w, h, stride):
+        """The same for an image of w x h in `buf` with rows `stride` bytes apart."""
+        buf = np.ascontiguousarray(buf, np.uint8)
+        reg = self.frame_region
+        ow, oh = (reg[3], reg[4]) if reg else (0, 0)
+        out = np.empty((oh, ow, 3), np.uint8)
+        hd = self._mask_owner()
+        rc = lib().slideo_rectify_bgr8(hd, _p(buf), int(w), int(h), int(stride), _p(out), C.c_int64(out.size))
+        if rc != OK:
+            raise SlideoError(rc, lib().slideo_last_error(hd).decode())
+        return out
+
+    frame_region_from_quad = staticmethod(lambda quad, out_w, out_h: frame_region_from_quad(quad, out_w, out_h))
+
     def _unit_size(self, w, h):
         """The size of the image the pipeline reads for a w x h frame."""
+        reg = self.frame_region
+        if reg is not None:
+            return reg[3], reg[4]
         mw, mh = self.working_size
         return working_size(w, h, mw, mh) if mw > 0 else (w, h)
 
@@ -1018,6 +1078,19 @@ def changed_ssd_threshold_n(changed_similarity, n_pixels):
     if t < 0:
         raise SlideoError(1, "changed_ssd_threshold_n: bad pixel count %r" % (n_pixels,))
     return t
+
+
+def frame_region_from_quad(quad, out_w, out_h):
+    """slideo_frame_region_from_quad: the 3x3 map (float64 [3, 3]) that takes the corners of the out_w x out_h image onto `quad` —
+    the source coordinates of the slide's top-left, top-right, bottom-right and bottom-left corner.  A pure host function."""
+    q = np.ascontiguousarray(np.asarray(quad, np.float64).reshape(-1))
+    if q.size != 8:
+        raise SlideoError(1, "frame_region_from_quad: expected 4 (x, y) corners")
+    M = np.zeros(9, np.float64)
+    rc = lib().slideo_frame_region_from_quad(_p(q), int(out_w), int(out_h), _p(M))
+    if rc != OK:
+        raise SlideoError(rc, "slideo_frame_region_from_quad: a degenerate or non-convex quad, or an output size outside 2..4096")
+    return M.reshape(3, 3)
 
 
 def working_size(w, h, max_w, max_h):

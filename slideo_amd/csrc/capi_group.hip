@@ -334,6 +334,16 @@ int32_t slideo_group_set_working_size(slideo_group* g, int32_t max_w, int32_t ma
     GROUP_CATCH(g)
 }
 
+int32_t slideo_group_set_frame_region(slideo_group* g, int32_t src_w, int32_t src_h, const double* M, int32_t out_w, int32_t out_h) {
+    if (!g) return SLIDEO_ERR_INVALID_ARG;
+    GROUP_TRY
+    for (slideo_matcher* m : g->members) require_idle(m);
+    for (slideo_matcher* m : g->members) check_member_call(m, slideo_matcher_set_frame_region(m, src_w, src_h, M, out_w, out_h));
+    g->kept_valid = false;
+    group_gate_none(g);
+    GROUP_CATCH(g)
+}
+
 int32_t slideo_group_set_frame_mask(slideo_group* g, const uint8_t* mask, int32_t width, int32_t height, int32_t stride_bytes) {
     if (!g) return SLIDEO_ERR_INVALID_ARG;
     GROUP_TRY

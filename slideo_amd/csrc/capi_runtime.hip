@@ -135,6 +135,7 @@ void validate_frames(FrameSrc& src, slideo_matcher* m, int n, const void* out) {
         if (n < 0 || (n > 0 && (!src.p || !out))) fail(SLIDEO_ERR_INVALID_ARG, "null frames/verdicts");
     }
     validate_image(src.w, src.h, src.stride);
+    if (m) apply_frame_region(m, src);
     if (m) apply_working_size(m, src);
     if (m && src.reduce && (src.w > MAX_DIM || src.h > MAX_DIM)) fail(SLIDEO_ERR_UNSUPPORTED, "image size %dx%d outside 1..%d", src.w, src.h, MAX_DIM);
     if (m && m->sift_on) sift_check_cfg(&m->sift_cfg, src.unit_w(), src.unit_h());          // (the doubled image's coordinates travel in 13 bits)
@@ -144,8 +145,18 @@ void validate_frames(FrameSrc& src, slideo_matcher* m, int n, const void* out) {
     src.pinned = !src.on_device && src.p && host_is_pinned(src.p);
 }
 
+void apply_frame_region(const slideo_matcher* m, FrameSrc& src) {
+    const FrameRegion& R = m->region;
+    src.rectify = false;
+    if (!R.set || src.analysed) return;
+    if (src.w != R.src_w || src.h != R.src_h)
+        fail(SLIDEO_ERR_INVALID_ARG, "frame size %dx%d is not the frame region's source size %dx%d", src.w, src.h, R.src_w, R.src_h);
+    src.rectify = true; src.ow = R.out_w; src.oh = R.out_h;
+}
+
 void apply_working_size(const slideo_matcher* m, FrameSrc& src) {
     src.reduce = false;
+    if (src.rectify) return;        // (the region's output fits the working size: the set calls' rule)
     if (m->work_w <= 0 || (src.w <= m->work_w && src.h <= m->work_h)) return;
     working_size_rule(src.w, src.h, m->work_w, m->work_h, src.rw, src.rh);
     src.reduce = true;
@@ -161,19 +172,20 @@ uint8_t* stage_for_upload(slideo_matcher* m, Slot& S, size_t bytes) {
 
 DevFrames stage_frames(slideo_matcher* m, Slot& S, const FrameSrc& src, int first, int n, hipStream_t cs, DevBuf* into) {
     const uint8_t* p = src.p + (int64_t)first * src.frame_stride;
-    if (src.on_device && !src.yuv && !src.reduce) return DevFrames{p, src.w, src.h, src.stride, src.frame_stride};
+    const bool pre = src.reduce || src.rectify;                  // a kernel stands between the BGR view at source size and the unit's image
+    if (src.on_device && !src.yuv && !pre) return DevFrames{p, src.w, src.h, src.stride, src.frame_stride};
     const int uw = src.unit_w(), uh = src.unit_h();
     const int64_t fb = (int64_t)src.h * src.stride;              // one frame of the BGR view at source size (stride 3w for YUV frames)
-    const int64_t ub = src.reduce ? (int64_t)uh * uw * 3 : fb;   // one frame of the unit's BGR image
+    const int64_t ub = pre ? (int64_t)uh * uw * 3 : fb;          // one frame of the unit's BGR image
     uint8_t* stage;
     if (into) { into->reserve((size_t)ub * n + 16); stage = into->as<uint8_t>(); }
     else stage = stage_for_upload(m, S, (size_t)ub * n);
     int64_t fs = src.frame_stride;
     if (!src.on_device) {
-        // host frames back to back into d_stage, or into d_yuv for the conversion / the reduce below
+        // host frames back to back into d_stage, or into d_yuv for the conversion / the reduce / the rectify below
         const int64_t bytes = src.yuv ? src.yuv_span : fb;
         uint8_t* dst = stage;
-        if (src.yuv || src.reduce) { S.d_yuv.reserve((size_t)bytes * n + 16); dst = S.d_yuv.as<uint8_t>(); }
+        if (src.yuv || pre) { S.d_yuv.reserve((size_t)bytes * n + 16); dst = S.d_yuv.as<uint8_t>(); }
         hipStream_t st = cs ? cs : S.st;
         if (fs == bytes) {
             HIP_CHECK(hipMemcpyAsync(dst, p, (size_t)bytes * n, hipMemcpyHostToDevice, st));
@@ -188,15 +200,16 @@ DevFrames stage_frames(slideo_matcher* m, Slot& S, const FrameSrc& src, int firs
         p = dst; fs = bytes;
     }
     // 4:2:0 frames: converted on the slot's stream into its d_stage, which lives until the unit is collected (verify's re-projection
-    // reads the frames); into d_full when the image is reduced next (reduce comes after convert)
+    // reads the frames); into d_full when the image is reduced or rectified next (both come after convert)
     if (src.yuv) {
         uint8_t* bgr = stage;
-        if (src.reduce) { S.d_full.reserve((size_t)fb * n + 16); bgr = S.d_full.as<uint8_t>(); }
+        if (pre) { S.d_full.reserve((size_t)fb * n + 16); bgr = S.d_full.as<uint8_t>(); }
         launch_yuv420_to_bgr(p, fs, *src.yuv, src.w, src.h, n, bgr, S.st);
         p = bgr; fs = fb;
     }
-    if (!src.reduce) return DevFrames{stage, src.w, src.h, src.stride, fb};
-    launch_reduce(m, p, fs, src.stride, src.w, src.h, uw, uh, n, stage, S.st);
+    if (!pre) return DevFrames{stage, src.w, src.h, src.stride, fb};
+    if (src.rectify) launch_rectify(m->region, p, fs, src.stride, n, stage, S.st);
+    else launch_reduce(m, p, fs, src.stride, src.w, src.h, uw, uh, n, stage, S.st);
     return DevFrames{stage, uw, uh, uw * 3, ub};
 }
 
@@ -440,6 +453,7 @@ void changed_mask_impl(slideo_matcher* m, int n_frames, FrameSrc src, const uint
                        float* similarity_out) {
     if (n_frames < 0 || (n_frames > 0 && (!src.p || !changed_out))) fail(SLIDEO_ERR_INVALID_ARG, "null frames/changed");
     validate_frames(src);
+    apply_frame_region(m, src);
     apply_working_size(m, src);
     // (under the frame mask's GATE scope the flags are the mask's: frames of another analysed size are an error, before anything is touched)
     if (m->mask.set && (m->mask_scope & SLIDEO_MASK_GATE)) { int npx_ = 0; (void)gate_map_for(m, src.unit_w(), src.unit_h(), m->gate_map.sw, m->gate_map.sh, &npx_); }
@@ -713,6 +727,9 @@ int32_t slideo_matcher_set_working_size(slideo_matcher* m, int32_t max_w, int32_
     if (max_w < 0 || max_h < 0 || (max_w == 0) != (max_h == 0))
         fail(SLIDEO_ERR_INVALID_ARG, "working size %dx%d: both sides positive, or 0, 0 for none", max_w, max_h);
     require_idle(m);
+    if (m->region.set && max_w > 0 && (m->region.out_w > max_w || m->region.out_h > max_h))
+        fail(SLIDEO_ERR_UNSUPPORTED, "working size %dx%d is smaller than the frame region's output %dx%d: a region's output must fit the working size",
+             max_w, max_h, m->region.out_w, m->region.out_h);
     m->work_w = max_w; m->work_h = max_h;
     m->kept.valid = false;          // (the kept frames of an earlier mask call were sized under the earlier setting)
     gate_state_reset(m);            // (and so was the gate's small image)
@@ -814,6 +831,120 @@ int32_t slideo_reduce_bgr8(slideo_matcher* m, const uint8_t* bgr, int32_t width,
     require_idle(m);
     Slot& S = m->slots[0];
     img.reduce = true; img.rw = dw; img.rh = dh;
+    HIP_CHECK(hipMemcpyAsync(out, stage_frames(m, S, img, 0, 1).p, (size_t)ob, hipMemcpyDeviceToHost, S.st));
+    HIP_CHECK(hipStreamSynchronize(S.st));
+    API_CATCH(m)
+}
+
+// ---- frame region (include/slideo_amd.h "Frame region") ---------------------------------------------------------------------
+
+// the rules of a region's map and sizes (slideo_matcher_set_frame_region)
+static void frame_region_check(int src_w, int src_h, const double* M, int out_w, int out_h) {
+    if (out_w < 1 || out_h < 1 || out_w > MAX_DIM || out_h > MAX_DIM)
+        fail(SLIDEO_ERR_INVALID_ARG, "frame region: output size %dx%d outside 1..%d", out_w, out_h, MAX_DIM);
+    if (src_w < 1 || src_h < 1 || src_w > MAX_DIM || src_h > MAX_DIM)
+        fail(SLIDEO_ERR_INVALID_ARG, "frame region: source size %dx%d outside 1..%d", src_w, src_h, MAX_DIM);
+    for (int i = 0; i < 9; ++i) if (!std::isfinite(M[i])) fail(SLIDEO_ERR_INVALID_ARG, "frame region: M[%d] is not finite", i);
+    // W = M6 x + M7 y + M8 is affine over the destination rectangle: one sign at its four corners is one sign everywhere
+    const double xs[2] = {0.0, (double)(out_w - 1)}, ys[2] = {0.0, (double)(out_h - 1)};
+    int pos = 0, neg = 0;
+    for (double y : ys) for (double x : xs) { const double W = M[6] * x + M[7] * y + M[8]; pos += W > 0.0; neg += W < 0.0; }
+    if (pos != 4 && neg != 4)
+        fail(SLIDEO_ERR_INVALID_ARG, "frame region: W = M6 x + M7 y + M8 is zero or changes sign over the corners of the %dx%d destination", out_w, out_h);
+}
+
+int32_t slideo_matcher_set_frame_region(slideo_matcher* m, int32_t src_w, int32_t src_h, const double* M, int32_t out_w, int32_t out_h) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    FrameRegion R;
+    if (M) {
+        frame_region_check(src_w, src_h, M, out_w, out_h);
+        if (m->work_w > 0 && (out_w > m->work_w || out_h > m->work_h))
+            fail(SLIDEO_ERR_UNSUPPORTED, "frame region: output %dx%d exceeds the working size %dx%d: a region's output must fit the working size",
+                 out_w, out_h, m->work_w, m->work_h);
+        R.set = true; R.src_w = src_w; R.src_h = src_h; R.out_w = out_w; R.out_h = out_h;
+        for (int i = 0; i < 9; ++i) R.M[i] = M[i];
+        frame_region_classify(R);
+    }
+    require_idle(m);
+    m->region = R;
+    m->kept.valid = false;          // (the kept frames of an earlier mask call were made under the earlier setting)
+    gate_state_reset(m);            // (and so was the gate's small image)
+    API_CATCH(m)
+}
+
+int32_t slideo_matcher_frame_region(const slideo_matcher* m, int32_t* src_w, int32_t* src_h, double* M_out, int32_t* out_w, int32_t* out_h,
+                                    int32_t* is_set) {
+    if (!m || !src_w || !src_h || !M_out || !out_w || !out_h || !is_set) return SLIDEO_ERR_INVALID_ARG;
+    const FrameRegion& R = m->region;
+    *src_w = R.src_w; *src_h = R.src_h; *out_w = R.out_w; *out_h = R.out_h; *is_set = R.set ? 1 : 0;
+    for (int i = 0; i < 9; ++i) M_out[i] = R.M[i];
+    return SLIDEO_OK;
+}
+
+// the map of a quad (no device, no matcher).  An axis-aligned rectangle in closed form (exact: the crop and the plain scalings);
+// any other quad by Gaussian elimination with partial pivoting on the 8x8 system with M8 = 1, in float64
+int32_t slideo_frame_region_from_quad(const double* quad, int32_t out_w, int32_t out_h, double* M_out) {
+    if (!quad || !M_out || out_w < 2 || out_h < 2 || out_w > MAX_DIM || out_h > MAX_DIM) return SLIDEO_ERR_INVALID_ARG;
+    for (int i = 0; i < 8; ++i) if (!std::isfinite(quad[i])) return SLIDEO_ERR_INVALID_ARG;
+    // strictly convex, one orientation: the cross products of consecutive edges are nonzero and of one sign
+    int pos = 0, neg = 0;
+    for (int i = 0; i < 4; ++i) {
+        const double* a = quad + 2 * i; const double* b = quad + 2 * ((i + 1) % 4); const double* c = quad + 2 * ((i + 2) % 4);
+        const double cr = (b[0] - a[0]) * (c[1] - b[1]) - (b[1] - a[1]) * (c[0] - b[0]);
+        pos += cr > 0.0; neg += cr < 0.0;
+    }
+    if (pos != 4 && neg != 4) return SLIDEO_ERR_INVALID_ARG;
+    const double U = (double)(out_w - 1), V = (double)(out_h - 1);
+    if (quad[0] == quad[6] && quad[2] == quad[4] && quad[1] == quad[3] && quad[5] == quad[7]) {
+        const double m[9] = {(quad[2] - quad[0]) / U, 0.0, quad[0], 0.0, (quad[7] - quad[1]) / V, quad[1], 0.0, 0.0, 1.0};
+        for (int i = 0; i < 9; ++i) M_out[i] = m[i];
+        return SLIDEO_OK;
+    }
+    const double du[4] = {0.0, U, U, 0.0}, dv[4] = {0.0, 0.0, V, V};
+    double A[8][9];
+    for (int i = 0; i < 4; ++i) {
+        const double x = quad[2 * i], y = quad[2 * i + 1];
+        const double r0[9] = {du[i], dv[i], 1.0, 0.0, 0.0, 0.0, -x * du[i], -x * dv[i], x};
+        const double r1[9] = {0.0, 0.0, 0.0, du[i], dv[i], 1.0, -y * du[i], -y * dv[i], y};
+        for (int j = 0; j < 9; ++j) { A[2 * i][j] = r0[j]; A[2 * i + 1][j] = r1[j]; }
+    }
+    for (int c = 0; c < 8; ++c) {
+        int piv = c;
+        for (int r = c + 1; r < 8; ++r) if (std::fabs(A[r][c]) > std::fabs(A[piv][c])) piv = r;
+        if (!(std::fabs(A[piv][c]) > 1e-12)) return SLIDEO_ERR_INVALID_ARG;
+        if (piv != c) for (int j = 0; j < 9; ++j) std::swap(A[piv][j], A[c][j]);
+        for (int r = c + 1; r < 8; ++r) {
+            const double f = A[r][c] / A[c][c];
+            for (int j = c; j < 9; ++j) A[r][j] -= f * A[c][j];
+        }
+    }
+    double sol[8];
+    for (int c = 7; c >= 0; --c) {
+        double v = A[c][8];
+        for (int j = c + 1; j < 8; ++j) v -= A[c][j] * sol[j];
+        sol[c] = v / A[c][c];
+    }
+    for (int i = 0; i < 8; ++i) { if (!std::isfinite(sol[i])) return SLIDEO_ERR_INVALID_ARG; M_out[i] = sol[i]; }
+    M_out[8] = 1.0;
+    return SLIDEO_OK;
+}
+
+// Tap: the rectified image of one host image under the matcher's region (no small_area limit: edge shapes can be small)
+int32_t slideo_rectify_bgr8(slideo_matcher* m, const uint8_t* bgr, int32_t width, int32_t height, int32_t stride_bytes, uint8_t* out,
+                            int64_t out_capacity) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    if (!bgr || !out) fail(SLIDEO_ERR_INVALID_ARG, "null image/out");
+    if (!m->region.set) fail(SLIDEO_ERR_STATE, "no frame region is set");
+    FrameSrc img = FrameSrc::image(bgr, width, height, stride_bytes);
+    validate_frames(img);
+    apply_frame_region(m, img);
+    const int64_t ob = (int64_t)img.ow * img.oh * 3;
+    if (ob > out_capacity) fail(SLIDEO_ERR_CAPACITY, "the rectified image needs %lld bytes", (long long)ob);
+    HIP_CHECK(hipSetDevice(m->device));
+    require_idle(m);
+    Slot& S = m->slots[0];
     HIP_CHECK(hipMemcpyAsync(out, stage_frames(m, S, img, 0, 1).p, (size_t)ob, hipMemcpyDeviceToHost, S.st));
     HIP_CHECK(hipStreamSynchronize(S.st));
     API_CATCH(m)
@@ -1088,7 +1219,9 @@ int32_t slideo_match_kept_frames(slideo_matcher* m, int32_t n_sel, const int32_t
         HIP_CHECK(hipMemcpyAsync(m->d_kept.as<uint8_t>() + fb * i, m->slots[0].d_stage.as<uint8_t>() + fb * sel[i], fb * (size_t)(j - i), hipMemcpyDeviceToDevice, st));
         i = j;
     }
-    match_frames_impl(m, n_sel, FrameSrc::bgr8(m->d_kept.as<uint8_t>(), true, k.w, k.h, k.stride, (int64_t)fb), verdicts_out, st);
+    FrameSrc kept = FrameSrc::bgr8(m->d_kept.as<uint8_t>(), true, k.w, k.h, k.stride, (int64_t)fb);
+    kept.analysed = true;           // (under a frame region the mask call kept the RECTIFIED frames)
+    match_frames_impl(m, n_sel, kept, verdicts_out, st);
     API_CATCH(m)
 }
 

@@ -2,7 +2,7 @@
 //
 //   capi_runtime.hip   handles, page database, slots, frame staging (FrameSrc -> DevFrames), unit submit / collect, the drivers of the
 //                      frame calls (pipeline, submit, collect: plain and gated) and their entry points
-//   stage_orb.hip      ORB stage drivers          (kernels: orb.hip.h, yuv420.hip.h, reduce.hip.h, frame_mask.hip.h)
+//   stage_orb.hip      ORB stage drivers          (kernels: orb.hip.h, yuv420.hip.h, reduce.hip.h, frame_region.hip.h, frame_mask.hip.h)
 //   stage_knn.hip      index build + k-NN stage   (kernels: knn.hip.h, knn_tile.hip.h, knn_l2.hip.h, knn_lsh.hip.h)
 //   stage_verify.hip   vote .. verdict, small img (kernels: verify.hip.h, homography.hip.h)
 //   stage_sift.hip     SIFT stage + entry points  (kernels: sift.hip.h)
@@ -81,17 +81,24 @@ struct FrameSrc {
     // to rw x rh (include/slideo_amd.h "Working size")
     bool reduce = false;
     int rw = 0, rh = 0;
+    // (derived, match and mask calls) the matcher carries a frame region: the units read the frame's rectified ow x oh image
+    // (include/slideo_amd.h "Frame region"); never together with reduce
+    bool rectify = false;
+    int ow = 0, oh = 0;
+    // the frames are unit images already — the frames a mask call kept (slideo_match_kept_frames): no region applies to them
+    bool analysed = false;
 
-    int unit_w() const { return reduce ? rw : w; }      // the BGR image the units read
-    int unit_h() const { return reduce ? rh : h; }
+    int unit_w() const { return rectify ? ow : reduce ? rw : w; }      // the BGR image the units read
+    int unit_h() const { return rectify ? oh : reduce ? rh : h; }
     // per frame, the staging in front of the unit's BGR image: 1.5 B per pixel for 4:2:0 frames (BGR calls keep their unit sizes);
-    // a reducing call: the uploaded source frame (host sources) and the source-sized BGR image of a 4:2:0 frame;
+    // a reducing or rectifying call: the uploaded source frame (host sources) and the source-sized BGR image of a 4:2:0 frame;
     // gated (a gated call, include/slideo_amd.h "Changed-frame gate"): + the gate staging — the BGR unit image of every frame that
     // is not the caller's own device memory — and the frame's small image (gate_small: at most 3 * small_area bytes) and gate record
     size_t staging_bytes(size_t gate_small = 0) const {
         const size_t px = (size_t)w * h;
-        size_t b = !reduce ? (yuv ? px * 3 / 2 : 0) : (on_device ? 0 : (yuv ? px * 3 / 2 : (size_t)h * stride)) + (yuv ? px * 3 : 0);
-        if (gate_small) b += (on_device && !yuv && !reduce ? 0 : (size_t)unit_w() * unit_h() * 3) + gate_small + 32;
+        const bool pre = reduce || rectify;
+        size_t b = !pre ? (yuv ? px * 3 / 2 : 0) : (on_device ? 0 : (yuv ? px * 3 / 2 : (size_t)h * stride)) + (yuv ? px * 3 : 0);
+        if (gate_small) b += (on_device && !yuv && !pre ? 0 : (size_t)unit_w() * unit_h() * 3) + gate_small + 32;
         return b;
     }
 
@@ -107,6 +114,15 @@ struct FrameSrc {
     static FrameSrc image(const uint8_t* p, int w, int h, int stride) { return bgr8(p, false, w, h, stride, (int64_t)h * stride); }   // one host image
     // the same frames from frame `first` on (a group member's shard)
     FrameSrc from(int first) const { FrameSrc s = *this; s.p += (int64_t)first * frame_stride; return s; }
+};
+
+// The frame region of a matcher (slideo_matcher_set_frame_region): the 3x3 map M from the rectified out_w x out_h image into source
+// frames of src_w x src_h, and the rectify_kernel instance the host chose from M (frame_region.hip.h RECT_*; tx, ty: RECT_TRANSLATE)
+struct FrameRegion {
+    bool set = false;
+    int src_w = 0, src_h = 0, out_w = 0, out_h = 0;
+    double M[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    int kind = 0, tx = 0, ty = 0;
 };
 
 // The BGR8 frames a unit's kernels read (device memory).
@@ -148,8 +164,8 @@ struct Slot {
     DevBuf d_stage, d_pyr, d_blur, d_cand, d_hist, d_candcount, d_flags, d_thr, d_lvlofs, d_kpcount, d_qofs, d_info;
     DevBuf d_items, d_kp, d_desc, d_keys, d_knn_pend, d_votes, d_gpts, d_gmask, d_fcs, d_verdicts, d_pairs, d_blurmask, d_qkeys, d_tail, d_refine;
     DevBuf d_yuv;              // host frames of the unit in front of d_stage: YUV 4:2:0 frames to convert, source-sized frames to reduce
-                               // (reserved by the first YUV or reducing call only)
-    DevBuf d_full;             // the source-sized BGR image of 4:2:0 frames that are reduced (reserved by the first such call only)
+                               // or rectify (reserved by the first YUV, reducing or rectifying call only)
+    DevBuf d_full;             // the source-sized BGR image of 4:2:0 frames that are reduced or rectified (reserved by the first such call only)
     PinBuf h_info, h_out;
     OrbOut orb;
     // a gated unit (stage_gate.hip): all its frames as BGR unit images (d_gstage; plain device BGR frames stay in the caller's
@@ -265,6 +281,8 @@ struct slideo_matcher {
     // working size (slideo_matcher_set_working_size): frames beyond it are reduced in front of the pipeline; 0, 0 = none
     int work_w = 0, work_h = 0;
     std::vector<std::unique_ptr<slideo::ReduceEntry>> reduces;
+    // frame region (slideo_matcher_set_frame_region): frames of region.src_w x src_h stand for their rectified out_w x out_h image
+    slideo::FrameRegion region;
     // frame mask (slideo_matcher_set_frame_mask): the mask pyramid of a w x h mask, one frame in the level layout of the w x h
     // image pyramid (stage_orb.hip frame_mask_set); frames of that analysed size keep only the FAST candidates it allows
     struct FrameMask { bool set = false; int w = 0, h = 0; slideo::DevBuf d_pyr; } mask;
@@ -391,12 +409,16 @@ void validate_image(int w, int h, int stride);
 // `out`, then a BGR source's geometry, the working size (apply_working_size), the SIFT limits (on the size the units read) and —
 // match calls — a BGR source's frame stride.
 void validate_frames(FrameSrc& src, slideo_matcher* m = nullptr, int n = 0, const void* out = nullptr);
-// fills src.reduce / rw / rh from m's working size (the mask calls, which validate without a matcher, call it themselves)
+// fills src.reduce / rw / rh from m's working size (the mask calls, which validate without a matcher, call it themselves);
+// a rectifying call is exempt: its output fits the working size by the set calls' rule
 void apply_working_size(const slideo_matcher* m, FrameSrc& src);
+// fills src.rectify / ow / oh from m's frame region; SLIDEO_ERR_INVALID_ARG for a frame of another size than the region's source
+void apply_frame_region(const slideo_matcher* m, FrameSrc& src);
 // Frames [first, first + n) of a validated `src` as BGR8 on the device, for slot S: a device BGR source as it is; host frames
 // copied into S.d_stage (BGR) or S.d_yuv (YUV), on `cs` when given (S.st waits for it) and on S.st otherwise; YUV converted into
 // S.d_stage on S.st; a source the working size reduces: host frames into S.d_yuv, 4:2:0 frames converted into S.d_full, then
-// reduced into S.d_stage (the DevFrames are rw x rh).  Every write of a slot's d_stage goes through here (page ingest through its staging buffer) and ends the
+// reduced into S.d_stage (the DevFrames are rw x rh); under a frame region the same with the rectify in place of the reduce (device
+// BGR frames are read in the caller's memory; the DevFrames are ow x oh).  Every write of a slot's d_stage goes through here (page ingest through its staging buffer) and ends the
 // frames slideo_changed_mask_bgr8 kept for slideo_match_kept_frames.
 // into: the staging buffer in place of S.d_stage (a gated unit's S.d_gstage; the kept frames of a mask call then stay).
 DevFrames stage_frames(slideo_matcher* m, Slot& S, const FrameSrc& src, int first, int n, hipStream_t cs = nullptr, DevBuf* into = nullptr);
@@ -447,6 +469,10 @@ void orb_launch_scan(const uint32_t* counts, int n, uint32_t* qofs, uint32_t* in
 // n BGR8 frames of w x h -> cv::resize(INTER_AREA) to dw x dh under m's ocv.area, at dst (stride 3dw, frame stride 3dw dh)
 void launch_reduce(slideo_matcher* m, const uint8_t* src, int64_t src_fs, int stride, int w, int h, int dw, int dh, int n, uint8_t* dst,
                    hipStream_t st);
+// n BGR8 frames of R.src_w x R.src_h -> their rectified R.out_w x R.out_h images at dst (stride 3 out_w, frame stride 3 out_w out_h)
+void launch_rectify(const FrameRegion& R, const uint8_t* src, int64_t src_fs, int stride, int n, uint8_t* dst, hipStream_t st);
+// the rectify_kernel instance of a map: R.kind, R.tx, R.ty from R.M
+void frame_region_classify(FrameRegion& R);
 // n decoded YUV 4:2:0 frames (a layout yuv420_validate accepted, frame stride src_fs) -> BGR8 at dst, stride 3w, frame stride 3wh
 void launch_yuv420_to_bgr(const uint8_t* src, int64_t src_fs, const slideo_yuv420_layout& L, int w, int h, int n, uint8_t* dst, hipStream_t st);
 

@@ -1,9 +1,11 @@
 // stage_orb.hip — drivers of the ORB stage (kernels: orb.hip.h) and of the front doors in front of it: YUV 4:2:0 frames
-// (yuv420.hip.h) and the working-size reduce (reduce.hip.h); the frame mask's pyramid and candidate filter (frame_mask.hip.h).
+// (yuv420.hip.h), the working-size reduce (reduce.hip.h) and the frame region's rectify (frame_region.hip.h); the frame mask's
+// pyramid and candidate filter (frame_mask.hip.h).
 #include "runtime.hpp"
 #include "orb.hip.h"
 #include "yuv420.hip.h"
 #include "reduce.hip.h"
+#include "frame_region.hip.h"
 #include "frame_mask.hip.h"
 
 using namespace slideo;
@@ -111,6 +113,18 @@ void launch_reduce(slideo_matcher* m, const uint8_t* src, int64_t src_fs, int st
         reduce_area_kernel<<<grid, block, 0, st>>>(a, e.ag, e.d_taps.as<AreaTap>(), e.d_idx.as<int32_t>());
     }
     check_launch("reduce kernel");
+}
+
+void frame_region_classify(FrameRegion& R) { R.kind = rect_classify(R.M, R.tx, R.ty); }
+
+// n BGR8 frames of R.src_w x R.src_h (rows `stride`, frames src_fs apart) -> their rectified images at dst (stride 3 out_w)
+void launch_rectify(const FrameRegion& R, const uint8_t* src, int64_t src_fs, int stride, int n, uint8_t* dst, hipStream_t st) {
+    const RectifyArgs a = rect_args(R.M, R.kind, R.tx, R.ty, src, src_fs, stride, R.src_w, R.src_h, dst, R.out_w, R.out_h);
+    const dim3 grid(cdiv(cdiv(R.out_w, 4), RECT_TX), cdiv(R.out_h, RECT_TY), n), block(RECT_TX, RECT_TY);
+    if (R.kind == RECT_TRANSLATE) rectify_kernel<RECT_TRANSLATE><<<grid, block, 0, st>>>(a);
+    else if (R.kind == RECT_AFFINE) rectify_kernel<RECT_AFFINE><<<grid, block, 0, st>>>(a);
+    else rectify_kernel<RECT_PROJECTIVE><<<grid, block, 0, st>>>(a);
+    check_launch("rectify_kernel");
 }
 
 void orb_launch_scan(const uint32_t* counts, int n, uint32_t* qofs, uint32_t* info, hipStream_t st) {

@@ -167,6 +167,7 @@ struct Handle {
     slideo_group* g = nullptr;
     int n_devices = 1;
     int32_t work_w = 0, work_h = 0;          // the working size the group was given (0, 0: none)
+    int32_t reg_w = 0, reg_h = 0;            // the output size of the frame region the group was given (0, 0: none)
     bool gated = true;                       // tasks use the group's gated call (false: the stop-and-go mask + kept pair)
     ~Handle() { if (g) slideo_group_destroy(g); }
     void check(int32_t rc) const {
@@ -244,8 +245,13 @@ public:
                 std::vector<uint8_t> tmp(fb), red;
                 const uint8_t* img = frames.data();
                 int32_t a, b, uw = video.width, uh = video.height;
-                if (h_->work_w > 0) h_->check(slideo_working_size(video.width, video.height, h_->work_w, h_->work_h, &uw, &uh));
-                if (uw != video.width || uh != video.height) {      // the mask compares the small images of the REDUCED frames
+                if (h_->reg_w > 0) {                                 // the mask compares the small images of the RECTIFIED frames
+                    uw = h_->reg_w; uh = h_->reg_h;
+                    red.resize((size_t)uw * uh * 3);
+                    h_->check(slideo_rectify_bgr8(slideo_group_member(h_->g, 0), frames.data(), video.width, video.height, video.width * 3, red.data(), (int64_t)red.size()));
+                    img = red.data();
+                } else if (h_->work_w > 0) h_->check(slideo_working_size(video.width, video.height, h_->work_w, h_->work_h, &uw, &uh));
+                if (h_->reg_w == 0 && (uw != video.width || uh != video.height)) {      // the mask compares the small images of the REDUCED frames
                     red.resize((size_t)uw * uh * 3);
                     h_->check(slideo_reduce_bgr8(slideo_group_member(h_->g, 0), frames.data(), video.width, video.height, video.width * 3, uw, uh, red.data(), (int64_t)red.size()));
                     img = red.data();
@@ -328,6 +334,15 @@ public:
     // ORB keypoints of the frames are detected under `mask` (width x height bytes, nonzero = detect here; slideo_group_set_frame_mask,
     // include/slideo_amd.h "Frame mask"): a speaker inset, a logo or subtitles stay out of the features.  Detection only; the frames'
     // analysed size must be the mask's.  The reference passes no mask.  Default: none
+    // Frames of src_w x src_h stand for the out_w x out_h image rectified from `quad`: the source coordinates x, y of the slide's
+    // top-left, top-right, bottom-right and bottom-left corner (slideo_frame_region_from_quad, slideo_group_set_frame_region;
+    // include/slideo_amd.h "Frame region"): a filmed projection screen, a slide in a sub-window.  The output must fit a working
+    // size.  The reference analyses the whole frame.  Default: none
+    HipImageVideoMatcher& with_frame_region(int32_t src_w, int32_t src_h, const double (&quad)[8], int32_t out_w, int32_t out_h) {
+        if (slideo_frame_region_from_quad(quad, out_w, out_h, reg_M_) != SLIDEO_OK) throw std::runtime_error("with_frame_region: a degenerate or non-convex quad");
+        reg_sw_ = src_w; reg_sh_ = src_h; reg_ow_ = out_w; reg_oh_ = out_h;
+        return *this;
+    }
     HipImageVideoMatcher& with_frame_mask(std::vector<uint8_t> mask, int32_t width, int32_t height) {
         if (width < 1 || height < 1 || mask.size() != (size_t)width * (size_t)height) throw std::runtime_error("with_frame_mask: mask is not width x height bytes");
         mask_ = std::move(mask); mask_w_ = width; mask_h_ = height;
@@ -366,6 +381,10 @@ public:
             h->check(slideo_group_set_working_size(h->g, work_w_, work_h_));
             h->work_w = work_w_; h->work_h = work_h_;
         }
+        if (reg_ow_ > 0) {
+            h->check(slideo_group_set_frame_region(h->g, reg_sw_, reg_sh_, reg_M_, reg_ow_, reg_oh_));
+            h->reg_w = reg_ow_; h->reg_h = reg_oh_;
+        }
         if (mask_scope_ != SLIDEO_MASK_DETECT) h->check(slideo_group_set_frame_mask_scope(h->g, mask_scope_));
         if (!mask_.empty()) h->check(slideo_group_set_frame_mask(h->g, mask_.data(), mask_w_, mask_h_, mask_w_));
         if (direct_scope_ != SLIDEO_DIRECT_WHOLE) h->check(slideo_group_set_direct_scope(h->g, direct_scope_));
@@ -388,6 +407,8 @@ private:
     bool sift_on_ = false, gated_ = true;
     float sift_ratio_ = 0.f, direct_t_ = 0.f;
     int32_t work_w_ = 0, work_h_ = 0;
+    int32_t reg_sw_ = 0, reg_sh_ = 0, reg_ow_ = 0, reg_oh_ = 0;
+    double reg_M_[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
     std::vector<uint8_t> mask_;
     int32_t mask_w_ = 0, mask_h_ = 0;
     uint32_t mask_scope_ = SLIDEO_MASK_DETECT, direct_scope_ = SLIDEO_DIRECT_WHOLE;

@@ -297,7 +297,7 @@ class HipImageVideoMatcher:
     """Drop-in for OpenCVImageVideoMatcher (lib.rs:34-73) behind matching::ImageVideoMatcher."""
 
     def __init__(self, cfg=None, device=None, sift=None, devices=None, working_size=None, frame_mask=None, frame_mask_scope=None,
-                 direct_similarity=None, direct_scope=None):
+                 direct_similarity=None, direct_scope=None, frame_region=None):
         """devices: HIP ordinals, one matcher each behind one slideo_group (the reference fans out over the whole machine, the
         global rayon pool of lib.rs:45,174); None = every gfx950 device of the node; `device` = d is short for devices = [d].
         sift = (slideo_sift_config, ratio): the north-star's SIFT + L2 front end instead of the reference's ORB + Hamming
@@ -316,13 +316,19 @@ class HipImageVideoMatcher:
         None = off.
         direct_scope = _capi.DIRECT_WHOLE or _capi.DIRECT_VALID (slideo_group_set_direct_scope): with DIRECT_VALID the look-up
         compares what the gate compares, the valid pixels of the gate's validity map, so MASK_GATE and direct_similarity work
-        together (a full-screen slide under a speaker thumbnail); applied before direct_similarity; None = DIRECT_WHOLE."""
+        together (a full-screen slide under a speaker thumbnail); applied before direct_similarity; None = DIRECT_WHOLE.
+        frame_region = (src_w, src_h, M_or_quad, out_w, out_h) (slideo_group_set_frame_region): frames of src_w x src_h stand for
+        the out_w x out_h image rectified from a fixed quadrilateral of them — a filmed projection screen, a slide in a
+        sub-window; M_or_quad: the 3x3 map from the rectified image into the frame, or the slide's four corners in the frame
+        (top-left, top-right, bottom-right, bottom-left); a frame mask is then of the output size, and the output must fit a
+        working size (the reference analyses the whole frame); None = no region."""
         self._cfg, self._sift = cfg, sift
         self._working_size = working_size
         self._frame_mask = frame_mask
         self._frame_mask_scope = frame_mask_scope
         self._direct_similarity = direct_similarity
         self._direct_scope = direct_scope
+        self._frame_region = frame_region
         self._devices = [device] if device is not None else devices
 
     def create_video_matcher(self, images, progress_reporter: ProgressReporter) -> HipVideoMatcher:
@@ -333,6 +339,8 @@ class HipImageVideoMatcher:
             m.use_sift(*self._sift)
         if self._working_size is not None:
             m.set_working_size(*self._working_size)
+        if self._frame_region is not None:
+            m.set_frame_region(*self._frame_region)
         if self._frame_mask_scope is not None:
             m.set_frame_mask_scope(self._frame_mask_scope)
         if self._frame_mask is not None:
