@@ -29,7 +29,7 @@ HIP_UNIT_HEADERS = {"stage_orb.hip": ["orb.hip.h", "cv_math.hip.h", "yuv420.hip.
                     "stage_page_set.hip": ["page_set.hip.h"],
                     "stage_gate.hip": ["gate.hip.h"],
                     "stage_direct.hip": ["direct.hip.h"]}
-HIP_COMMON_HEADERS = ["runtime.hpp", "common.h", "geom.h", "types.h"]
+HIP_COMMON_HEADERS = ["runtime.hpp", "common.h", "error.h", "frame_settings.h", "geom.h", "types.h"]
 OBJDIR = os.path.join(LIBDIR, "obj")
 
 

@@ -173,7 +173,7 @@ void group_gated_impl(slideo_group* g, int32_t n_frames, const FrameSrc& src, ui
     if (n_frames > 0 && !changed_out) fail(SLIDEO_ERR_INVALID_ARG, "null changed_out");
     FrameSrc checked = src;
     validate_frames(checked, m0, n_frames, verdicts_out);
-    gate_check(g->gate, m0->cfg.small_area, checked);
+    gate_check(g->gate, checked);
     for (slideo_matcher* m : g->members) require_idle(m);
     if (n_frames == 0) return;                      // a no-op: the state, the last call's traces and a mask call's kept frames stay
     g->match_lo.assign((size_t)N + 1, 0);
@@ -240,6 +240,23 @@ void group_gated_impl(slideo_group* g, int32_t n_frames, const FrameSrc& src, ui
     catch (const std::exception& e) { set_group_err(g, e.what()); return SLIDEO_ERR_HIP; } \
     catch (...) { set_group_err(g, "unknown error"); return SLIDEO_ERR_HIP; } \
     return SLIDEO_OK;
+
+// The one path of the group's six frame setters, as the entry point's return code.  propose: frame_settings.h propose_* on a member's
+// settings.  Validated before any member is touched — the arguments, every member idle, the rules between settings on every
+// member —, then every member's commit, then the group's half of what the setting ends.
+template <class Propose>
+int32_t group_set(slideo_group* g, Setting what, Propose propose, const uint8_t* mask = nullptr, int stride = 0) {
+    if (!g) return SLIDEO_ERR_INVALID_ARG;
+    GROUP_TRY
+    std::vector<FrameSettings> next;
+    for (slideo_matcher* m : g->members) next.push_back(propose(m->fs));
+    for (slideo_matcher* m : g->members) require_idle(m);
+    for (size_t r = 0; r < next.size(); ++r) frame_settings_rules(next[r], what, g->members[r]->sift_on);
+    for (size_t r = 0; r < next.size(); ++r) settings_commit(g->members[r], what, next[r], mask, stride);
+    if (SETTING_ENDS[what].kept) g->kept_valid = false;
+    if (SETTING_ENDS[what].gate) group_gate_none(g);
+    GROUP_CATCH(g)
+}
 
 extern "C" {
 
@@ -326,60 +343,23 @@ int32_t slideo_group_use_sift(slideo_group* g, const slideo_sift_config* cfg, fl
 }
 
 int32_t slideo_group_set_working_size(slideo_group* g, int32_t max_w, int32_t max_h) {
-    if (!g) return SLIDEO_ERR_INVALID_ARG;
-    GROUP_TRY
-    for (slideo_matcher* m : g->members) check_member_call(m, slideo_matcher_set_working_size(m, max_w, max_h));
-    g->kept_valid = false;
-    group_gate_none(g);
-    GROUP_CATCH(g)
+    return group_set(g, SET_WORKING_SIZE, [&](const FrameSettings& s) { return propose_working_size(s, max_w, max_h); });
 }
-
 int32_t slideo_group_set_frame_region(slideo_group* g, int32_t src_w, int32_t src_h, const double* M, int32_t out_w, int32_t out_h) {
-    if (!g) return SLIDEO_ERR_INVALID_ARG;
-    GROUP_TRY
-    for (slideo_matcher* m : g->members) require_idle(m);
-    for (slideo_matcher* m : g->members) check_member_call(m, slideo_matcher_set_frame_region(m, src_w, src_h, M, out_w, out_h));
-    g->kept_valid = false;
-    group_gate_none(g);
-    GROUP_CATCH(g)
+    return group_set(g, SET_FRAME_REGION, [&](const FrameSettings& s) { return propose_frame_region(s, src_w, src_h, M, out_w, out_h); });
 }
-
 int32_t slideo_group_set_frame_mask(slideo_group* g, const uint8_t* mask, int32_t width, int32_t height, int32_t stride_bytes) {
-    if (!g) return SLIDEO_ERR_INVALID_ARG;
-    GROUP_TRY
-    for (slideo_matcher* m : g->members) check_member_call(m, slideo_matcher_set_frame_mask(m, mask, width, height, stride_bytes));
-    g->kept_valid = false;
-    GROUP_CATCH(g)
+    return group_set(g, SET_FRAME_MASK, [&](const FrameSettings& s) { return propose_frame_mask(s, mask != nullptr, width, height, stride_bytes); }, mask,
+                     stride_bytes);
 }
-
 int32_t slideo_group_set_frame_mask_scope(slideo_group* g, uint32_t scope) {
-    if (!g) return SLIDEO_ERR_INVALID_ARG;
-    GROUP_TRY
-    for (slideo_matcher* m : g->members) require_idle(m);
-    for (slideo_matcher* m : g->members) check_member_call(m, slideo_matcher_set_frame_mask_scope(m, scope));
-    g->kept_valid = false;
-    GROUP_CATCH(g)
+    return group_set(g, SET_FRAME_MASK_SCOPE, [&](const FrameSettings& s) { return propose_frame_mask_scope(s, scope); });
 }
-
 int32_t slideo_group_set_direct_similarity(slideo_group* g, float t) {
-    if (!g) return SLIDEO_ERR_INVALID_ARG;
-    GROUP_TRY
-    // validated once, before any member is touched
-    if (!(t >= 0.f) || t > 1.f) fail(SLIDEO_ERR_INVALID_ARG, "direct similarity %g: 0 (off) or 0 < t <= 1", (double)t);
-    for (slideo_matcher* m : g->members) { require_idle(m); direct_check_mask(m->mask.set, m->mask_scope, t, m->direct_scope); }
-    for (slideo_matcher* m : g->members) check_member_call(m, slideo_matcher_set_direct_similarity(m, t));
-    GROUP_CATCH(g)
+    return group_set(g, SET_DIRECT_SIMILARITY, [&](const FrameSettings& s) { return propose_direct_similarity(s, t); });
 }
-
 int32_t slideo_group_set_direct_scope(slideo_group* g, uint32_t scope) {
-    if (!g) return SLIDEO_ERR_INVALID_ARG;
-    GROUP_TRY
-    // validated once, before any member is touched
-    if (scope != SLIDEO_DIRECT_WHOLE && scope != SLIDEO_DIRECT_VALID)
-        fail(SLIDEO_ERR_INVALID_ARG, "direct scope %u: SLIDEO_DIRECT_WHOLE (0) or SLIDEO_DIRECT_VALID (1)", scope);
-    for (slideo_matcher* m : g->members) { require_idle(m); direct_check_mask(m->mask.set, m->mask_scope, m->direct_t, scope); }
-    for (slideo_matcher* m : g->members) check_member_call(m, slideo_matcher_set_direct_scope(m, scope));
-    GROUP_CATCH(g)
+    return group_set(g, SET_DIRECT_SCOPE, [&](const FrameSettings& s) { return propose_direct_scope(s, scope); });
 }
 
 // Page sets: every member builds the same set from the same deck (ids are handed out in the same order: they agree)

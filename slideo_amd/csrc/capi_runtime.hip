@@ -135,31 +135,63 @@ void validate_frames(FrameSrc& src, slideo_matcher* m, int n, const void* out) {
         if (n < 0 || (n > 0 && (!src.p || !out))) fail(SLIDEO_ERR_INVALID_ARG, "null frames/verdicts");
     }
     validate_image(src.w, src.h, src.stride);
-    if (m) apply_frame_region(m, src);
-    if (m) apply_working_size(m, src);
-    if (m && src.reduce && (src.w > MAX_DIM || src.h > MAX_DIM)) fail(SLIDEO_ERR_UNSUPPORTED, "image size %dx%d outside 1..%d", src.w, src.h, MAX_DIM);
-    if (m && m->sift_on) sift_check_cfg(&m->sift_cfg, src.unit_w(), src.unit_h());          // (the doubled image's coordinates travel in 13 bits)
-    if (m && m->cur_set != 0) page_set_check_mode(m);                          // (a mode switched on after slideo_matcher_use_page_set)
-    if (m) (void)frame_mask_for(m, src.unit_w(), src.unit_h());                // (a frame mask holds frames of its own size only)
+    if (m) resolve_frames(m, src, true);
     if (m && !src.yuv && src.frame_stride < (int64_t)src.h * src.stride) fail(SLIDEO_ERR_INVALID_ARG, "frame_stride smaller than one frame");
     src.pinned = !src.on_device && src.p && host_is_pinned(src.p);
 }
 
-void apply_frame_region(const slideo_matcher* m, FrameSrc& src) {
-    const FrameRegion& R = m->region;
-    src.rectify = false;
-    if (!R.set || src.analysed) return;
-    if (src.w != R.src_w || src.h != R.src_h)
-        fail(SLIDEO_ERR_INVALID_ARG, "frame size %dx%d is not the frame region's source size %dx%d", src.w, src.h, R.src_w, R.src_h);
-    src.rectify = true; src.ow = R.out_w; src.oh = R.out_h;
+// prep, unit size and small size: the frame region, else the working size (the region's output fits it: the set calls' rule)
+static void resolve_unit(const slideo_matcher* m, FrameSrc& src) {
+    const FrameSettings& fs = m->fs;
+    const FrameRegion& R = fs.region;
+    const int small_area = m->cfg.small_area;
+    if (R.set && !src.analysed) {
+        if (src.w != R.src_w || src.h != R.src_h)
+            fail(SLIDEO_ERR_INVALID_ARG, "frame size %dx%d is not the frame region's source size %dx%d", src.w, src.h, R.src_w, R.src_h);
+        src.plan.unit(PREP_RECTIFY, R.out_w, R.out_h, small_area);
+    } else if (fs.work_w > 0 && (src.w > fs.work_w || src.h > fs.work_h)) {
+        int rw = 0, rh = 0;
+        working_size_rule(src.w, src.h, fs.work_w, fs.work_h, rw, rh);
+        src.plan.unit(PREP_REDUCE, rw, rh, small_area);
+    } else src.plan.unit(PREP_NONE, src.w, src.h, small_area);
 }
 
-void apply_working_size(const slideo_matcher* m, FrameSrc& src) {
-    src.reduce = false;
-    if (src.rectify) return;        // (the region's output fits the working size: the set calls' rule)
-    if (m->work_w <= 0 || (src.w <= m->work_w && src.h <= m->work_h)) return;
-    working_size_rule(src.w, src.h, m->work_w, m->work_h, src.rw, src.rh);
-    src.reduce = true;
+void resolve_frames(const slideo_matcher* m, FrameSrc& src, bool match) {
+    FramePlan& P = src.plan;
+    resolve_unit(m, src);
+    if (match) {
+        if (P.prep == PREP_REDUCE && (src.w > MAX_DIM || src.h > MAX_DIM)) fail(SLIDEO_ERR_UNSUPPORTED, "image size %dx%d outside 1..%d", src.w, src.h, MAX_DIM);
+        if (m->sift_on) sift_check_cfg(&m->sift_cfg, P.uw, P.uh);              // (the doubled image's coordinates travel in 13 bits)
+        if (m->cur_set != 0) page_set_check_mode(m);                          // (a mode switched on after slideo_matcher_use_page_set)
+        P.mask_pyr = frame_mask_for(m, P.uw, P.uh);                           // (a frame mask holds frames of its own size only)
+    }
+    // (under the frame mask's GATE scope the flags are the mask's: frames of another analysed size are an error, before anything is touched)
+    P.gate_w = gate_map_for(m, P.uw, P.uh, P.sw, P.sh, &P.npx);
+}
+
+void settings_commit(slideo_matcher* m, Setting what, FrameSettings next, const uint8_t* mask, int stride) {
+    const bool masks = what == SET_FRAME_MASK || what == SET_FRAME_MASK_SCOPE;
+    if (masks) HIP_CHECK(hipSetDevice(m->device));
+    require_idle(m);
+    frame_settings_rules(next, what, m->sift_on);
+    if (what == SET_FRAME_REGION && next.region.set) frame_region_classify(next.region);
+    // a new mask's pyramid and, under the GATE scope, the validity map of the mask in force (level 0 of the pyramid: the mask as
+    // given) come first: a mask whose map is refused leaves the mask before in force
+    DevBuf pyr, map_w;
+    const bool new_mask = what == SET_FRAME_MASK && next.mask.set;
+    if (new_mask) frame_mask_build(m, mask, next.mask.w, next.mask.h, stride, pyr);
+    if (masks && !next.gate_scope()) next.gate_map = GateMap{};
+    else if (masks && (new_mask || !next.gate_map.on)) {
+        const LevelGeom& L0 = geom_for(m, next.mask.w, next.mask.h).g.lv[0];
+        gate_map_build(m, (new_mask ? pyr : m->d_mask_pyr).as<uint8_t>() + L0.ofs, L0.pitch, next.mask.w, next.mask.h, next.gate_map, map_w);
+    }
+    if (new_mask) m->d_mask_pyr = std::move(pyr);
+    if (map_w.p) m->d_gate_w = std::move(map_w);
+    m->fs = next;
+    const SettingEnds& ends = SETTING_ENDS[what];
+    if (ends.kept) m->kept.valid = false;
+    if (ends.gate) gate_state_reset(m);
+    if (ends.map_gen) ++m->fs.gate_map_gen;
 }
 
 // S's staging buffer with room for `bytes`.  Slot 0's holds the frames slideo_changed_mask_bgr8 kept for slideo_match_kept_frames:
@@ -172,9 +204,10 @@ uint8_t* stage_for_upload(slideo_matcher* m, Slot& S, size_t bytes) {
 
 DevFrames stage_frames(slideo_matcher* m, Slot& S, const FrameSrc& src, int first, int n, hipStream_t cs, DevBuf* into) {
     const uint8_t* p = src.p + (int64_t)first * src.frame_stride;
-    const bool pre = src.reduce || src.rectify;                  // a kernel stands between the BGR view at source size and the unit's image
+    const FramePlan& P = src.plan;      // (a tap's unresolved plan is PREP_NONE: uw, uh are read under `pre` alone)
+    const bool pre = P.prep != PREP_NONE;                        // a kernel stands between the BGR view at source size and the unit's image
     if (src.on_device && !src.yuv && !pre) return DevFrames{p, src.w, src.h, src.stride, src.frame_stride};
-    const int uw = src.unit_w(), uh = src.unit_h();
+    const int uw = P.uw, uh = P.uh;
     const int64_t fb = (int64_t)src.h * src.stride;              // one frame of the BGR view at source size (stride 3w for YUV frames)
     const int64_t ub = pre ? (int64_t)uh * uw * 3 : fb;          // one frame of the unit's BGR image
     uint8_t* stage;
@@ -208,9 +241,17 @@ DevFrames stage_frames(slideo_matcher* m, Slot& S, const FrameSrc& src, int firs
         p = bgr; fs = fb;
     }
     if (!pre) return DevFrames{stage, src.w, src.h, src.stride, fb};
-    if (src.rectify) launch_rectify(m->region, p, fs, src.stride, n, stage, S.st);
+    if (P.prep == PREP_RECTIFY) launch_rectify(m->fs.region, p, fs, src.stride, n, stage, S.st);
     else launch_reduce(m, p, fs, src.stride, src.w, src.h, uw, uh, n, stage, S.st);
     return DevFrames{stage, uw, uh, uw * 3, ub};
+}
+
+void tap_staged(slideo_matcher* m, const FrameSrc& img, uint8_t* out, int64_t ob) {
+    HIP_CHECK(hipSetDevice(m->device));
+    require_idle(m);
+    Slot& S = m->slots[0];
+    HIP_CHECK(hipMemcpyAsync(out, stage_frames(m, S, img, 0, 1).p, (size_t)ob, hipMemcpyDeviceToHost, S.st));
+    HIP_CHECK(hipStreamSynchronize(S.st));
 }
 
 // the cv::RNG((uint64)-1) stream RANSACPointSetRegistrator draws its samples from, pre-drawn (ptsetreg.cpp: rng state
@@ -234,7 +275,7 @@ uint32_t kp_cap_for(const slideo_matcher* m, const PyrGeom& g) {
 
 // ---- one unit of the per-frame hot path: enqueue everything, then collect ---------------
 // `f` must stay valid until the unit is collected (reproject reads the frames).
-void unit_submit(slideo_matcher* m, Slot& S, const DevFrames& f, int n, bool allow_async) {
+void unit_submit(slideo_matcher* m, Slot& S, const DevFrames& f, int n, const uint8_t* mask_pyr, bool allow_async) {
     // (does this unit share the chip with others?  the search then runs one block per CU: stage_knn.hip knn_plan)
     { bool others = m->units_pending; for (const Slot& o : m->slots) others |= (&o != &S && o.busy); S.knn.shared = others; }
     S.gate.on = false;                             // (a gated unit: stage_gate.hip marks it after this submit)
@@ -253,10 +294,10 @@ void unit_submit(slideo_matcher* m, Slot& S, const DevFrames& f, int n, bool all
     const bool async = allow_async && m->async_submit && !knn_unit_is_valu(m) &&
                        (int64_t)n * kpcap < ((int64_t)1 << 30) &&
                        (kpcap >= (uint32_t)c.nfeatures + 1024u || kpcap >= (uint32_t)std::max(g.cand_per_frame, 1));
-    S.timed = prof; S.u_in = f; S.u_async = async;
+    S.timed = prof; S.u_in = f; S.u_mask = mask_pyr; S.u_async = async;
     if (m->orb_chain && m->last_orb_ev && m->last_orb_ev != S.ev_orb) HIP_CHECK(hipStreamWaitEvent(st, m->last_orb_ev, 0));
     if (prof) HIP_CHECK(hipEventRecord(S.ev[0], st));
-    orb_stage1(m, S, f, n, false, async ? kpcap : 0xFFFFFFFFu, frame_mask_for(m, f.w, f.h));      // (a re-run applies the mask again)
+    orb_stage1(m, S, f, n, false, async ? kpcap : 0xFFFFFFFFu, mask_pyr);      // (a re-run applies the mask again)
     uint32_t qtot, qplan;
     if (async) {
         qtot = (uint32_t)n * kpcap;                                          // capacity
@@ -301,7 +342,7 @@ void unit_collect(slideo_matcher* m, Slot& S, slideo_verdict* out_host) {
             // a frame had more keypoints than the capacity-sized path provides for (ties at a retainBest threshold are kept, as
             // in OpenCV): the whole unit again, through the exact-size path
             S.u_rerun = true;
-            unit_submit(m, S, S.u_in, n, false);
+            unit_submit(m, S, S.u_in, n, S.u_mask, false);
             unit_collect(m, S, out_host);
             return;
         }
@@ -317,7 +358,7 @@ void unit_collect(slideo_matcher* m, Slot& S, slideo_verdict* out_host) {
         HIP_CHECK(hipDeviceSynchronize());
         upload_rng_stream(m, (uint32_t)std::min<uint64_t>((uint64_t)m->rng_len * 4, cap));
         S.u_rerun = true;
-        unit_submit(m, S, S.u_in, n, false);
+        unit_submit(m, S, S.u_in, n, S.u_mask, false);
         unit_collect(m, S, out_host);
         return;
     }
@@ -341,12 +382,12 @@ void unit_collect(slideo_matcher* m, Slot& S, slideo_verdict* out_host) {
 // gated, through the gate and the changed ones through unit_submit (stage_gate.hip)
 static void unit_begin(slideo_matcher* m, Slot& S, const FrameSrc& src, int first, int n, hipStream_t cs, bool gated) {
     if (gated) gate_unit_submit(m, S, src, first, n, cs);
-    else unit_submit(m, S, stage_frames(m, S, src, first, n, cs), n);
+    else unit_submit(m, S, stage_frames(m, S, src, first, n, cs), n, src.plan.mask_pyr);
 }
 
 // max frames per unit of a call of either kind under the workspace budget
 static int unit_fit(slideo_matcher* m, const FrameSrc& src, int n, bool gated) {
-    return sub_batch_for(m, geom_for(m, src.unit_w(), src.unit_h()).g, n, src.staging_bytes(gated ? gate_small_budget(m) : 0));
+    return sub_batch_for(m, geom_for(m, src.plan.uw, src.plan.uh).g, n, src.staging_bytes(gated ? gate_small_budget(m) : 0));
 }
 
 // Synchronous matching of n frames, plain or gated (changed_out, similarity_out: a gated call's): cut into units and run them
@@ -355,13 +396,13 @@ void match_frames_impl(slideo_matcher* m, int n, FrameSrc src, slideo_verdict* o
                        float* similarity_out) {
     if (gated && n > 0 && !changed_out) fail(SLIDEO_ERR_INVALID_ARG, "null changed_out");
     validate_frames(src, m, n, out);
-    if (gated) gate_check(m, src);
+    if (gated) gate_check(m->gate, src);
     HIP_CHECK(hipSetDevice(m->device));
     require_idle(m);
     m->last_fcs.clear();
     if (n == 0) return;
     int unit = unit_fit(m, src, n, gated);
-    area_class_for(m, src.unit_w(), src.unit_h());
+    area_class_for(m, src.plan.uw, src.plan.uh);
     upload_area(m);
     if (n >= 128 && unit >= (n + 1) / 2) unit = (n + 1) / 2;      // two halves overlap ORB with kNN / verify
     // Host frames: the call is bound by the H2D copies (6.2 MB per 1080p frame: 256 frames = 29 ms at 55 GB/s against 14 ms of
@@ -414,14 +455,14 @@ static void submit_impl(slideo_matcher* m, int32_t n_frames, FrameSrc src, void*
     if (!ticket_out) fail(SLIDEO_ERR_INVALID_ARG, "null ticket_out");
     validate_frames(src, m, n_frames, ticket_out);
     if (n_frames < 1) fail(SLIDEO_ERR_INVALID_ARG, "submit needs at least one frame");
-    if (gated) gate_check(m, src);
+    if (gated) gate_check(m->gate, src);
     HIP_CHECK(hipSetDevice(m->device));
     Slot& S = m->slots[m->next_slot];
     if (S.busy) fail(SLIDEO_ERR_STATE, "all slots are in flight: collect ticket %lld first", (long long)S.ticket);
     const int fit = unit_fit(m, src, n_frames, gated);
     if (n_frames > fit)
         fail(SLIDEO_ERR_CAPACITY, "%d frames exceed the per-slot workspace budget (%d); submit smaller units or raise SLIDEO_WS_GB", n_frames, fit);
-    area_class_for(m, src.unit_w(), src.unit_h());
+    area_class_for(m, src.plan.uw, src.plan.uh);
     upload_area(m);
     { bool any = false; for (const Slot& c : m->slots) any |= c.busy; if (!any) m->last_fcs.clear(); }
     if (hip_stream) {
@@ -453,22 +494,18 @@ void changed_mask_impl(slideo_matcher* m, int n_frames, FrameSrc src, const uint
                        float* similarity_out) {
     if (n_frames < 0 || (n_frames > 0 && (!src.p || !changed_out))) fail(SLIDEO_ERR_INVALID_ARG, "null frames/changed");
     validate_frames(src);
-    apply_frame_region(m, src);
-    apply_working_size(m, src);
-    // (under the frame mask's GATE scope the flags are the mask's: frames of another analysed size are an error, before anything is touched)
-    if (m->mask.set && (m->mask_scope & SLIDEO_MASK_GATE)) { int npx_ = 0; (void)gate_map_for(m, src.unit_w(), src.unit_h(), m->gate_map.sw, m->gate_map.sh, &npx_); }
+    resolve_frames(m, src, false);
     if (n_frames == 0) return;
     HIP_CHECK(hipSetDevice(m->device));
     require_idle(m);
     Slot& S = m->slots[0];
     hipStream_t st = S.st;
-    int sw = 0, sh = 0;
     const DevFrames f = stage_frames(m, S, src, 0, n_frames);
     m->kept = slideo_matcher::Kept{true, n_frames, f.w, f.h, f.stride};      // stays in slot 0's staging buffer: slideo_match_kept_frames
-    run_small(m, f, n_frames, sw, sh, st);
-    const size_t sb = (size_t)sw * sh * 3;
-    int npx = 0;
-    const uint8_t* weights = gate_map_for(m, f.w, f.h, sw, sh, &npx);
+    run_small(m, f, n_frames, st);
+    const size_t sb = (size_t)src.plan.sw * src.plan.sh * 3;
+    const int npx = src.plan.npx;
+    const uint8_t* weights = src.plan.gate_w;
     DevBuf& prev = m->d_prev_small;
     prev.reserve(sb);
     if (prev_small) HIP_CHECK(hipMemcpyAsync(prev.p, prev_small, sb, hipMemcpyHostToDevice, st));
@@ -523,7 +560,7 @@ void analyse_pages(slideo_matcher* m, int n_pages, const uint8_t* const* data, c
             HIP_CHECK(hipMemcpyAsync(desc.data(), S.d_desc.p, (size_t)qtot * dbytes, hipMemcpyDeviceToHost, st));
         }
         int sw = 0, sh = 0;
-        run_small(m, staged, cnt, sw, sh, st);
+        run_small(m, staged, cnt, st, &sw, &sh);
         std::vector<uint8_t> smalls((size_t)cnt * sw * sh * 3);
         HIP_CHECK(hipMemcpyAsync(smalls.data(), m->d_small.p, smalls.size(), hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipStreamSynchronize(st));
@@ -722,95 +759,35 @@ int32_t slideo_working_size(int32_t w, int32_t h, int32_t max_w, int32_t max_h, 
 }
 
 int32_t slideo_matcher_set_working_size(slideo_matcher* m, int32_t max_w, int32_t max_h) {
-    if (!m) return SLIDEO_ERR_INVALID_ARG;
-    API_TRY
-    if (max_w < 0 || max_h < 0 || (max_w == 0) != (max_h == 0))
-        fail(SLIDEO_ERR_INVALID_ARG, "working size %dx%d: both sides positive, or 0, 0 for none", max_w, max_h);
-    require_idle(m);
-    if (m->region.set && max_w > 0 && (m->region.out_w > max_w || m->region.out_h > max_h))
-        fail(SLIDEO_ERR_UNSUPPORTED, "working size %dx%d is smaller than the frame region's output %dx%d: a region's output must fit the working size",
-             max_w, max_h, m->region.out_w, m->region.out_h);
-    m->work_w = max_w; m->work_h = max_h;
-    m->kept.valid = false;          // (the kept frames of an earlier mask call were sized under the earlier setting)
-    gate_state_reset(m);            // (and so was the gate's small image)
-    ++m->gate_map_gen;              // (the look-up's masked page norms are built again under the new setting)
-    API_CATCH(m)
+    return matcher_set(m, SET_WORKING_SIZE, [&](const FrameSettings& s) { return propose_working_size(s, max_w, max_h); });
 }
 
-// ---- frame mask (include/slideo_amd.h "Frame mask") -------------------------------------------------------------------------
-
-static void gate_map_swap(slideo_matcher::GateMap& a, slideo_matcher::GateMap& b) {
-    std::swap(a.on, b.on); std::swap(a.sw, b.sw); std::swap(a.sh, b.sh); std::swap(a.n_valid, b.n_valid);
-    std::swap(a.d_w.p, b.d_w.p); std::swap(a.d_w.cap, b.d_w.cap);
-}
+// ---- frame mask, frame mask scope (include/slideo_amd.h "Frame mask", "Frame mask scope") -----------------------------------
 
 int32_t slideo_matcher_set_frame_mask(slideo_matcher* m, const uint8_t* mask, int32_t width, int32_t height, int32_t stride_bytes) {
-    if (!m) return SLIDEO_ERR_INVALID_ARG;
-    API_TRY
-    if (mask) {
-        if (m->sift_on) fail(SLIDEO_ERR_UNSUPPORTED, "the frame mask filters ORB's FAST candidates: not in SIFT mode");
-        if (width < 1 || height < 1 || stride_bytes < width)
-            fail(SLIDEO_ERR_INVALID_ARG, "bad mask geometry w=%d h=%d stride=%d", width, height, stride_bytes);
-    }
-    HIP_CHECK(hipSetDevice(m->device));
-    require_idle(m);
-    direct_check_mask(mask != nullptr, m->mask_scope, m->direct_t, m->direct_scope);       // (the mask before stays in force)
-    // under the GATE scope the new mask's validity map comes first: a mask it refuses leaves the mask before in force
-    slideo_matcher::GateMap map;
-    if (mask && (m->mask_scope & SLIDEO_MASK_GATE)) {
-        (void)geom_for(m, width, height);                              // (the size rules of the mask itself, before any work)
-        DevBuf d_mask;
-        d_mask.reserve((size_t)width * height);
-        HIP_CHECK(hipMemcpy2DAsync(d_mask.p, (size_t)width, mask, (size_t)stride_bytes, (size_t)width, (size_t)height, hipMemcpyHostToDevice, m->stream));
-        gate_map_build(m, d_mask.as<uint8_t>(), width, width, height, map);      // (synchronises the stream: d_mask may go)
-    }
-    m->kept.valid = false;          // (the kept frames of an earlier mask call end, as under slideo_matcher_set_working_size)
-    m->gate_map.on = false;
-    ++m->gate_map_gen;              // (what was derived from the map before — the look-up's masked page norms — is stale)
-    frame_mask_set(m, mask, width, height, stride_bytes);
-    if (map.on) gate_map_swap(m->gate_map, map);
-    API_CATCH(m)
+    return matcher_set(m, SET_FRAME_MASK, [&](const FrameSettings& s) { return propose_frame_mask(s, mask != nullptr, width, height, stride_bytes); }, mask,
+                       stride_bytes);
 }
 
-// ---- frame mask scope (include/slideo_amd.h "Frame mask scope") -------------------------------------------------------------
-
 int32_t slideo_matcher_set_frame_mask_scope(slideo_matcher* m, uint32_t scope) {
-    if (!m) return SLIDEO_ERR_INVALID_ARG;
-    API_TRY
-    if (scope == 0 || (scope & ~(SLIDEO_MASK_DETECT | SLIDEO_MASK_GATE)))
-        fail(SLIDEO_ERR_INVALID_ARG, "frame mask scope %u: a non-empty combination of SLIDEO_MASK_DETECT (1) and SLIDEO_MASK_GATE (2)", scope);
-    HIP_CHECK(hipSetDevice(m->device));
-    require_idle(m);
-    direct_check_mask(m->mask.set, scope, m->direct_t, m->direct_scope);  // (the scope before stays in force)
-    if ((scope & SLIDEO_MASK_GATE) && m->mask.set && !m->gate_map.on) {
-        // the second of {mask, GATE scope}: the map from the mask as given, level 0 of its pyramid
-        const LevelGeom& L0 = geom_for(m, m->mask.w, m->mask.h).g.lv[0];
-        slideo_matcher::GateMap map;
-        gate_map_build(m, m->mask.d_pyr.as<uint8_t>() + L0.ofs, L0.pitch, m->mask.w, m->mask.h, map);
-        gate_map_swap(m->gate_map, map);
-    }
-    if (!(scope & SLIDEO_MASK_GATE)) m->gate_map.on = false;
-    ++m->gate_map_gen;
-    m->mask_scope = scope;
-    m->kept.valid = false;          // (as slideo_matcher_set_frame_mask; the gate state stays)
-    API_CATCH(m)
+    return matcher_set(m, SET_FRAME_MASK_SCOPE, [&](const FrameSettings& s) { return propose_frame_mask_scope(s, scope); });
 }
 
 int32_t slideo_matcher_frame_mask_scope(const slideo_matcher* m, uint32_t* scope) {
     if (!m || !scope) return SLIDEO_ERR_INVALID_ARG;
-    *scope = m->mask_scope;
+    *scope = m->fs.mask_scope;
     return SLIDEO_OK;
 }
 
 int32_t slideo_matcher_frame_mask_info(const slideo_matcher* m, int32_t* width, int32_t* height, int32_t* is_set) {
     if (!m || !width || !height || !is_set) return SLIDEO_ERR_INVALID_ARG;
-    *width = m->mask.set ? m->mask.w : 0; *height = m->mask.set ? m->mask.h : 0; *is_set = m->mask.set ? 1 : 0;
+    *width = m->fs.mask.w; *height = m->fs.mask.h; *is_set = m->fs.mask.set ? 1 : 0;
     return SLIDEO_OK;
 }
 
 int32_t slideo_matcher_get_working_size(const slideo_matcher* m, int32_t* max_w, int32_t* max_h) {
     if (!m || !max_w || !max_h) return SLIDEO_ERR_INVALID_ARG;
-    *max_w = m->work_w; *max_h = m->work_h;
+    *max_w = m->fs.work_w; *max_h = m->fs.work_h;
     return SLIDEO_OK;
 }
 
@@ -827,56 +804,21 @@ int32_t slideo_reduce_bgr8(slideo_matcher* m, const uint8_t* bgr, int32_t width,
         fail(SLIDEO_ERR_INVALID_ARG, "reduce %dx%d -> %dx%d: the target must be smaller along at least one side and larger along none", width, height, dw, dh);
     const int64_t ob = (int64_t)dw * dh * 3;
     if (ob > out_capacity) fail(SLIDEO_ERR_CAPACITY, "the reduced image needs %lld bytes", (long long)ob);
-    HIP_CHECK(hipSetDevice(m->device));
-    require_idle(m);
-    Slot& S = m->slots[0];
-    img.reduce = true; img.rw = dw; img.rh = dh;
-    HIP_CHECK(hipMemcpyAsync(out, stage_frames(m, S, img, 0, 1).p, (size_t)ob, hipMemcpyDeviceToHost, S.st));
-    HIP_CHECK(hipStreamSynchronize(S.st));
+    img.plan.unit(PREP_REDUCE, dw, dh, m->cfg.small_area);      // (the tap's own target in place of the working-size rule's)
+    tap_staged(m, img, out, ob);
     API_CATCH(m)
 }
 
 // ---- frame region (include/slideo_amd.h "Frame region") ---------------------------------------------------------------------
 
-// the rules of a region's map and sizes (slideo_matcher_set_frame_region)
-static void frame_region_check(int src_w, int src_h, const double* M, int out_w, int out_h) {
-    if (out_w < 1 || out_h < 1 || out_w > MAX_DIM || out_h > MAX_DIM)
-        fail(SLIDEO_ERR_INVALID_ARG, "frame region: output size %dx%d outside 1..%d", out_w, out_h, MAX_DIM);
-    if (src_w < 1 || src_h < 1 || src_w > MAX_DIM || src_h > MAX_DIM)
-        fail(SLIDEO_ERR_INVALID_ARG, "frame region: source size %dx%d outside 1..%d", src_w, src_h, MAX_DIM);
-    for (int i = 0; i < 9; ++i) if (!std::isfinite(M[i])) fail(SLIDEO_ERR_INVALID_ARG, "frame region: M[%d] is not finite", i);
-    // W = M6 x + M7 y + M8 is affine over the destination rectangle: one sign at its four corners is one sign everywhere
-    const double xs[2] = {0.0, (double)(out_w - 1)}, ys[2] = {0.0, (double)(out_h - 1)};
-    int pos = 0, neg = 0;
-    for (double y : ys) for (double x : xs) { const double W = M[6] * x + M[7] * y + M[8]; pos += W > 0.0; neg += W < 0.0; }
-    if (pos != 4 && neg != 4)
-        fail(SLIDEO_ERR_INVALID_ARG, "frame region: W = M6 x + M7 y + M8 is zero or changes sign over the corners of the %dx%d destination", out_w, out_h);
-}
-
 int32_t slideo_matcher_set_frame_region(slideo_matcher* m, int32_t src_w, int32_t src_h, const double* M, int32_t out_w, int32_t out_h) {
-    if (!m) return SLIDEO_ERR_INVALID_ARG;
-    API_TRY
-    FrameRegion R;
-    if (M) {
-        frame_region_check(src_w, src_h, M, out_w, out_h);
-        if (m->work_w > 0 && (out_w > m->work_w || out_h > m->work_h))
-            fail(SLIDEO_ERR_UNSUPPORTED, "frame region: output %dx%d exceeds the working size %dx%d: a region's output must fit the working size",
-                 out_w, out_h, m->work_w, m->work_h);
-        R.set = true; R.src_w = src_w; R.src_h = src_h; R.out_w = out_w; R.out_h = out_h;
-        for (int i = 0; i < 9; ++i) R.M[i] = M[i];
-        frame_region_classify(R);
-    }
-    require_idle(m);
-    m->region = R;
-    m->kept.valid = false;          // (the kept frames of an earlier mask call were made under the earlier setting)
-    gate_state_reset(m);            // (and so was the gate's small image)
-    API_CATCH(m)
+    return matcher_set(m, SET_FRAME_REGION, [&](const FrameSettings& s) { return propose_frame_region(s, src_w, src_h, M, out_w, out_h); });
 }
 
 int32_t slideo_matcher_frame_region(const slideo_matcher* m, int32_t* src_w, int32_t* src_h, double* M_out, int32_t* out_w, int32_t* out_h,
                                     int32_t* is_set) {
     if (!m || !src_w || !src_h || !M_out || !out_w || !out_h || !is_set) return SLIDEO_ERR_INVALID_ARG;
-    const FrameRegion& R = m->region;
+    const FrameRegion& R = m->fs.region;
     *src_w = R.src_w; *src_h = R.src_h; *out_w = R.out_w; *out_h = R.out_h; *is_set = R.set ? 1 : 0;
     for (int i = 0; i < 9; ++i) M_out[i] = R.M[i];
     return SLIDEO_OK;
@@ -936,17 +878,13 @@ int32_t slideo_rectify_bgr8(slideo_matcher* m, const uint8_t* bgr, int32_t width
     if (!m) return SLIDEO_ERR_INVALID_ARG;
     API_TRY
     if (!bgr || !out) fail(SLIDEO_ERR_INVALID_ARG, "null image/out");
-    if (!m->region.set) fail(SLIDEO_ERR_STATE, "no frame region is set");
+    if (!m->fs.region.set) fail(SLIDEO_ERR_STATE, "no frame region is set");
     FrameSrc img = FrameSrc::image(bgr, width, height, stride_bytes);
     validate_frames(img);
-    apply_frame_region(m, img);
-    const int64_t ob = (int64_t)img.ow * img.oh * 3;
+    resolve_unit(m, img);
+    const int64_t ob = (int64_t)img.plan.uw * img.plan.uh * 3;
     if (ob > out_capacity) fail(SLIDEO_ERR_CAPACITY, "the rectified image needs %lld bytes", (long long)ob);
-    HIP_CHECK(hipSetDevice(m->device));
-    require_idle(m);
-    Slot& S = m->slots[0];
-    HIP_CHECK(hipMemcpyAsync(out, stage_frames(m, S, img, 0, 1).p, (size_t)ob, hipMemcpyDeviceToHost, S.st));
-    HIP_CHECK(hipStreamSynchronize(S.st));
+    tap_staged(m, img, out, ob);
     API_CATCH(m)
 }
 

@@ -19,7 +19,7 @@ int32_t slideo_orb_bgr8(slideo_matcher* m, const uint8_t* bgr, int32_t width, in
     Slot& S = m->slots[0];
     hipStream_t st = S.st;
     // an image of the frame mask's size is analysed as a frame of that size is: under the mask
-    const uint8_t* mask_pyr = (m->mask.set && width == m->mask.w && height == m->mask.h) ? frame_mask_for(m, width, height) : nullptr;
+    const uint8_t* mask_pyr = (m->fs.mask.set && width == m->fs.mask.w && height == m->fs.mask.h) ? frame_mask_for(m, width, height) : nullptr;
     run_orb(m, S, stage_frames(m, S, img, 0, 1), 1, false, false, mask_pyr);
     const uint32_t q = S.orb.qtot;
     *n_out = (int32_t)q;
@@ -60,15 +60,15 @@ int32_t slideo_frame_mask_level(slideo_matcher* m, int32_t level, uint8_t* out, 
     if (!m) return SLIDEO_ERR_INVALID_ARG;
     API_TRY
     if (!out || !lw || !lh) fail(SLIDEO_ERR_INVALID_ARG, "null argument");
-    if (!m->mask.set) fail(SLIDEO_ERR_STATE, "no frame mask is set");
+    if (!m->fs.mask.set) fail(SLIDEO_ERR_STATE, "no frame mask is set");
     if (level < 0 || level >= m->cfg.nlevels) fail(SLIDEO_ERR_INVALID_ARG, "level out of range");
     HIP_CHECK(hipSetDevice(m->device));
     require_idle(m);
-    const LevelGeom& L = geom_for(m, m->mask.w, m->mask.h).g.lv[level];
+    const LevelGeom& L = geom_for(m, m->fs.mask.w, m->fs.mask.h).g.lv[level];
     *lw = L.w; *lh = L.h;
     if ((int64_t)L.w * L.h > out_capacity) fail(SLIDEO_ERR_CAPACITY, "level needs %lld bytes", (long long)L.w * L.h);
     if (L.w > 0 && L.h > 0) {
-        HIP_CHECK(hipMemcpy2DAsync(out, L.w, m->mask.d_pyr.as<uint8_t>() + L.ofs, L.pitch, L.w, L.h, hipMemcpyDeviceToHost, m->stream));
+        HIP_CHECK(hipMemcpy2DAsync(out, L.w, m->d_mask_pyr.as<uint8_t>() + L.ofs, L.pitch, L.w, L.h, hipMemcpyDeviceToHost, m->stream));
         HIP_CHECK(hipStreamSynchronize(m->stream));
     }
     API_CATCH(m)
@@ -78,18 +78,18 @@ int32_t slideo_frame_mask_small(slideo_matcher* m, uint8_t* out, int64_t out_cap
     if (!m) return SLIDEO_ERR_INVALID_ARG;
     API_TRY
     if (!sw || !sh || !n_valid) fail(SLIDEO_ERR_INVALID_ARG, "null sw/sh/n_valid");
-    if (!m->mask.set) fail(SLIDEO_ERR_STATE, "no frame mask is set");
-    if (!(m->mask_scope & SLIDEO_MASK_GATE) || !m->gate_map.on)
+    if (!m->fs.mask.set) fail(SLIDEO_ERR_STATE, "no frame mask is set");
+    if (!m->fs.gate_map.on)
         fail(SLIDEO_ERR_STATE, "the frame mask's scope lacks SLIDEO_MASK_GATE: there is no validity map (slideo_matcher_set_frame_mask_scope)");
     require_idle(m);
-    const slideo_matcher::GateMap& g = m->gate_map;
+    const GateMap& g = m->fs.gate_map;
     *sw = g.sw; *sh = g.sh; *n_valid = g.n_valid;
     const int64_t npx = (int64_t)g.sw * g.sh;
     if (out && npx > out_capacity) fail(SLIDEO_ERR_CAPACITY, "the validity map needs %lld bytes", (long long)npx);
     if (out) {
         HIP_CHECK(hipSetDevice(m->device));
         std::vector<uint8_t> w((size_t)npx * 3);
-        HIP_CHECK(hipMemcpyAsync(w.data(), g.d_w.p, w.size(), hipMemcpyDeviceToHost, m->stream));
+        HIP_CHECK(hipMemcpyAsync(w.data(), m->d_gate_w.p, w.size(), hipMemcpyDeviceToHost, m->stream));
         HIP_CHECK(hipStreamSynchronize(m->stream));
         for (int64_t i = 0; i < npx; ++i) out[i] = w[(size_t)i * 3];      // (a pixel's three weight bytes are equal)
     }
@@ -108,7 +108,7 @@ int32_t slideo_small_image_bgr8(slideo_matcher* m, const uint8_t* bgr, int32_t w
     Slot& S = m->slots[0];
     hipStream_t st = S.st;
     int sw = 0, sh = 0;
-    run_small(m, stage_frames(m, S, img, 0, 1), 1, sw, sh, st);
+    run_small(m, stage_frames(m, S, img, 0, 1), 1, st, &sw, &sh);
     *sw_out = sw; *sh_out = sh;
     if ((int64_t)sw * sh * 3 > out_capacity) fail(SLIDEO_ERR_CAPACITY, "small image needs %lld bytes", (long long)sw * sh * 3);
     HIP_CHECK(hipMemcpyAsync(out, m->d_small.p, (size_t)sw * sh * 3, hipMemcpyDeviceToHost, st));
@@ -125,11 +125,7 @@ int32_t slideo_yuv420_to_bgr8(slideo_matcher* m, const uint8_t* frame, int32_t w
     validate_frames(img);
     const size_t fb = (size_t)width * height * 3;
     if ((int64_t)fb > out_capacity) fail(SLIDEO_ERR_CAPACITY, "the BGR image needs %zu bytes", fb);
-    HIP_CHECK(hipSetDevice(m->device));
-    require_idle(m);
-    Slot& S = m->slots[0];
-    HIP_CHECK(hipMemcpyAsync(bgr_out, stage_frames(m, S, img, 0, 1).p, fb, hipMemcpyDeviceToHost, S.st));
-    HIP_CHECK(hipStreamSynchronize(S.st));
+    tap_staged(m, img, bgr_out, (int64_t)fb);
     API_CATCH(m)
 }
 

@@ -2,31 +2,16 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
-#include <stdexcept>
 #include <string>
 #include <vector>
 
+#include "error.h"
 #include "slideo_amd.h"
 
 namespace slideo {
-
-struct Error : std::runtime_error {
-    int32_t code;
-    Error(int32_t c, const std::string& m) : std::runtime_error(m), code(c) {}
-};
-
-[[noreturn]] inline void fail(int32_t code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    throw Error(code, buf);
-}
 
 #define HIP_CHECK(expr)                                                                       \
     do {                                                                                      \
@@ -43,6 +28,11 @@ struct DevBuf {
     DevBuf() = default;
     DevBuf(const DevBuf&) = delete;
     DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) { release(); p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }
+        return *this;
+    }
     ~DevBuf() { release(); }
     void release() {
         if (p) (void)hipFree(p);

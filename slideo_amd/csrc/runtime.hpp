@@ -1,7 +1,9 @@
 // runtime.hpp — the host runtime behind include/slideo_amd.h, shared by its translation units.
 //
-//   capi_runtime.hip   handles, page database, slots, frame staging (FrameSrc -> DevFrames), unit submit / collect, the drivers of the
-//                      frame calls (pipeline, submit, collect: plain and gated) and their entry points
+//   frame_settings.h   (plain C++) the frame settings record, the setters' range checks, the rules between settings, what a change ends
+//   capi_runtime.hip   handles, page database, slots, the frame settings' one commit path and their set calls, a call's frames resolved
+//                      (FrameSrc -> FramePlan) and staged (-> DevFrames), unit submit / collect, the drivers of the frame calls
+//                      (pipeline, submit, collect: plain and gated) and their entry points
 //   stage_orb.hip      ORB stage drivers          (kernels: orb.hip.h, yuv420.hip.h, reduce.hip.h, frame_region.hip.h, frame_mask.hip.h)
 //   stage_knn.hip      index build + k-NN stage   (kernels: knn.hip.h, knn_tile.hip.h, knn_l2.hip.h, knn_lsh.hip.h)
 //   stage_verify.hip   vote .. verdict, small img (kernels: verify.hip.h, homography.hip.h)
@@ -27,6 +29,7 @@
 #include <vector>
 
 #include "common.h"
+#include "frame_settings.h"
 #include "geom.h"
 #include "slideo_amd.h"
 #include "types.h"
@@ -66,6 +69,22 @@ struct HostPage {
     std::vector<uint8_t> small_img;
 };
 
+// What a call's frames are under the matcher's frame settings: resolved ONCE per call (resolve_frames), read by whatever stages,
+// sizes, gates or masks them
+enum FramePrep { PREP_NONE, PREP_REDUCE, PREP_RECTIFY };      // the kernel between the BGR view at source size and the unit's image
+struct FramePlan {
+    FramePrep prep = PREP_NONE;                 // REDUCE: the working size does not hold the frame; RECTIFY: a frame region is set
+    int uw = 0, uh = 0, sw = 0, sh = 0;         // the BGR image the units read, its small image (small_size under cfg.small_area)
+    const uint8_t* mask_pyr = nullptr;          // the frame mask's pyramid for uw x uh (frame_mask_for), null: no filter
+    const uint8_t* gate_w = nullptr;            // the gate's validity map for uw x uh (gate_map_for), null: whole small images,
+    int npx = 0;                                // and the pixels a similarity is normalised over: the map's n_valid, or sw * sh
+    void unit(FramePrep p, int w, int h, int small_area) {
+        prep = p; uw = w; uh = h;
+        small_size(w, h, small_area, sw, sh);
+        npx = sw * sh;
+    }
+};
+
 // A call's frames as the caller handed them over: BGR8 (yuv null) or YUV 4:2:0 in the layout `yuv`, in host or device memory.
 // validate_frames checks them and fills the derived fields; stage_frames turns a block of them into a unit's BGR8 view.
 struct FrameSrc {
@@ -77,28 +96,19 @@ struct FrameSrc {
     const slideo_yuv420_layout* yuv = nullptr;
     int64_t yuv_span = 0;                       // (derived) bytes of one YUV frame: its furthest byte + 1
     bool pinned = false;                        // (derived) page-locked host memory: its copies are truly asynchronous DMA
-    // (derived, match and mask calls) the matcher's working size does not hold the frame: the units read its INTER_AREA reduction
-    // to rw x rh (include/slideo_amd.h "Working size")
-    bool reduce = false;
-    int rw = 0, rh = 0;
-    // (derived, match and mask calls) the matcher carries a frame region: the units read the frame's rectified ow x oh image
-    // (include/slideo_amd.h "Frame region"); never together with reduce
-    bool rectify = false;
-    int ow = 0, oh = 0;
     // the frames are unit images already — the frames a mask call kept (slideo_match_kept_frames): no region applies to them
     bool analysed = false;
+    FramePlan plan;                             // (derived) resolve_frames
 
-    int unit_w() const { return rectify ? ow : reduce ? rw : w; }      // the BGR image the units read
-    int unit_h() const { return rectify ? oh : reduce ? rh : h; }
     // per frame, the staging in front of the unit's BGR image: 1.5 B per pixel for 4:2:0 frames (BGR calls keep their unit sizes);
     // a reducing or rectifying call: the uploaded source frame (host sources) and the source-sized BGR image of a 4:2:0 frame;
     // gated (a gated call, include/slideo_amd.h "Changed-frame gate"): + the gate staging — the BGR unit image of every frame that
     // is not the caller's own device memory — and the frame's small image (gate_small: at most 3 * small_area bytes) and gate record
     size_t staging_bytes(size_t gate_small = 0) const {
         const size_t px = (size_t)w * h;
-        const bool pre = reduce || rectify;
+        const bool pre = plan.prep != PREP_NONE;
         size_t b = !pre ? (yuv ? px * 3 / 2 : 0) : (on_device ? 0 : (yuv ? px * 3 / 2 : (size_t)h * stride)) + (yuv ? px * 3 : 0);
-        if (gate_small) b += (on_device && !yuv && !pre ? 0 : (size_t)unit_w() * unit_h() * 3) + gate_small + 32;
+        if (gate_small) b += (on_device && !yuv && !pre ? 0 : (size_t)plan.uw * plan.uh * 3) + gate_small + 32;
         return b;
     }
 
@@ -114,15 +124,6 @@ struct FrameSrc {
     static FrameSrc image(const uint8_t* p, int w, int h, int stride) { return bgr8(p, false, w, h, stride, (int64_t)h * stride); }   // one host image
     // the same frames from frame `first` on (a group member's shard)
     FrameSrc from(int first) const { FrameSrc s = *this; s.p += (int64_t)first * frame_stride; return s; }
-};
-
-// The frame region of a matcher (slideo_matcher_set_frame_region): the 3x3 map M from the rectified out_w x out_h image into source
-// frames of src_w x src_h, and the rectify_kernel instance the host chose from M (frame_region.hip.h RECT_*; tx, ty: RECT_TRANSLATE)
-struct FrameRegion {
-    bool set = false;
-    int src_w = 0, src_h = 0, out_w = 0, out_h = 0;
-    double M[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-    int kind = 0, tx = 0, ty = 0;
 };
 
 // The BGR8 frames a unit's kernels read (device memory).
@@ -158,6 +159,7 @@ struct Slot {
     hipEvent_t ev_in = nullptr, ev_orb = nullptr, ev_up = nullptr;
     // arguments of the unit in flight (re-run through the exact-size path if the capacity-sized one overflowed)
     DevFrames u_in; bool u_async = false;
+    const uint8_t* u_mask = nullptr;   // the mask pyramid the unit was submitted with (FramePlan::mask_pyr; a re-run filters with it again)
     KnnPlan knn;               // the unit's search as knn_plan_unit decided it (stage_knn.hip)
     int u_set = 0;             // the page set the unit searches (0 = the whole deck), taken from the matcher at submission
     bool u_rerun = false;      // (unit_collect's re-runs: the unit keeps its set)
@@ -256,7 +258,7 @@ struct DirectClass {
     std::vector<int32_t> pages;                   // the class's deck pages, ascending
     DevBuf d_op, d_norm, d_pages, d_all;          // operand, |b'|^2 (i64), the page list, the identity eligible list 0 .. np - 1
     // SLIDEO_DIRECT_VALID: |b'|^2 over the valid bytes of the gate's validity map (i64 per page), built at the first look-up under
-    // a map of the class's small size and kept while the matcher's gate_map_gen equals norm_v_gen (0: none)
+    // a map of the class's small size and kept while the matcher's fs.gate_map_gen equals norm_v_gen (0: none)
     DevBuf d_norm_v;
     uint64_t norm_v_gen = 0;
 };
@@ -278,22 +280,10 @@ struct slideo_matcher {
     uint32_t rng_len = 0;
     int ic_shift = 0, ic_entries = 0;     // intensity-centroid weight table of describe_kernel (geom.h ic_weight_table)
     std::vector<std::unique_ptr<slideo::GeomEntry>> geoms;
-    // working size (slideo_matcher_set_working_size): frames beyond it are reduced in front of the pipeline; 0, 0 = none
-    int work_w = 0, work_h = 0;
-    std::vector<std::unique_ptr<slideo::ReduceEntry>> reduces;
-    // frame region (slideo_matcher_set_frame_region): frames of region.src_w x src_h stand for their rectified out_w x out_h image
-    slideo::FrameRegion region;
-    // frame mask (slideo_matcher_set_frame_mask): the mask pyramid of a w x h mask, one frame in the level layout of the w x h
-    // image pyramid (stage_orb.hip frame_mask_set); frames of that analysed size keep only the FAST candidates it allows
-    struct FrameMask { bool set = false; int w = 0, h = 0; slideo::DevBuf d_pyr; } mask;
-    // frame mask scope (slideo_matcher_set_frame_mask_scope): SLIDEO_MASK_DETECT | SLIDEO_MASK_GATE; the matcher's, whatever
-    // happens to the mask.  While a mask is set and the scope has GATE, the gate's validity map (stage_gate.hip gate_map_build):
-    // one weight byte (0xFF valid, 0x00) per byte of the sw x sh small image of frames of the mask's size, n_valid valid pixels
-    uint32_t mask_scope = SLIDEO_MASK_DETECT;
-    struct GateMap { bool on = false; int sw = 0, sh = 0; int64_t n_valid = 0; slideo::DevBuf d_w; } gate_map;
-    // the map's generation: every call that can change the map (set_frame_mask, set_frame_mask_scope, set_working_size) moves it
-    // on, and what is derived from the map (the direct look-up's masked page norms) is cached under it
-    uint64_t gate_map_gen = 1;
+    // the frame settings (changed through settings_commit only) and the device buffers they own: the mask's pyramid, the validity map's weights
+    slideo::FrameSettings fs;
+    slideo::DevBuf d_mask_pyr, d_gate_w;
+    std::vector<std::unique_ptr<slideo::ReduceEntry>> reduces;      // the working-size reduce's size classes
 
     // INTER_AREA size classes
     std::vector<slideo::AreaGeom> area_geoms;
@@ -365,10 +355,8 @@ struct slideo_matcher {
     slideo::DevBuf d_gate_small;
     hipEvent_t last_gate_ev = nullptr;
 
-    // direct page look-up (include/slideo_amd.h "Direct page look-up"): the direct similarity (0: off) and, built at the first use
-    // with t > 0 after finalize, the deck's size classes
-    float direct_t = 0.f;
-    uint32_t direct_scope = SLIDEO_DIRECT_WHOLE;      // slideo_matcher_set_direct_scope: VALID = the look-up over the gate's valid pixels
+    // direct page look-up (include/slideo_amd.h "Direct page look-up"): built at the first use with fs.direct_t > 0 after finalize, the
+    // deck's size classes
     bool direct_built = false;
     std::vector<std::unique_ptr<slideo::DirectClass>> direct_classes;
 
@@ -406,24 +394,27 @@ void require_idle(slideo_matcher* m);
 void validate_image(int w, int h, int stride);
 // The argument rules of a call's frames (include/slideo_amd.h), in the order the entry points report them: a YUV source's layout
 // (its span; the stride of its BGR image), then — m != null: a match call — the matcher's state and the null frames / verdicts
-// `out`, then a BGR source's geometry, the working size (apply_working_size), the SIFT limits (on the size the units read) and —
-// match calls — a BGR source's frame stride.
+// `out`, then a BGR source's geometry, what resolve_frames reports and — match calls — a BGR source's frame stride.
 void validate_frames(FrameSrc& src, slideo_matcher* m = nullptr, int n = 0, const void* out = nullptr);
-// fills src.reduce / rw / rh from m's working size (the mask calls, which validate without a matcher, call it themselves);
-// a rectifying call is exempt: its output fits the working size by the set calls' rule
-void apply_working_size(const slideo_matcher* m, FrameSrc& src);
-// fills src.rectify / ow / oh from m's frame region; SLIDEO_ERR_INVALID_ARG for a frame of another size than the region's source
-void apply_frame_region(const slideo_matcher* m, FrameSrc& src);
+// The resolver of src.plan from m's frame settings and a validated source, in this order: prep, unit and small size — the frame
+// region (SLIDEO_ERR_INVALID_ARG at another size than its source; none for analysed frames), else the working size —; match: the source
+// limit of a reduced frame, the SIFT limits, the page set's modes, the mask's pyramid (frame_mask_for); the gate's weights and npx.
+void resolve_frames(const slideo_matcher* m, FrameSrc& src, bool match);
+// The one path by which a frame setting of m changes: idle (SLIDEO_ERR_STATE), the rules between settings on `next` (a propose_*
+// of frame_settings.h), what the mask and its scope need on the device built first and installed on success (mask: the host mask
+// of SET_FRAME_MASK, rows `stride` apart), then `next` in force and what SETTING_ENDS[what] ends ended.
+void settings_commit(slideo_matcher* m, Setting what, FrameSettings next, const uint8_t* mask = nullptr, int stride = 0);
 // Frames [first, first + n) of a validated `src` as BGR8 on the device, for slot S: a device BGR source as it is; host frames
 // copied into S.d_stage (BGR) or S.d_yuv (YUV), on `cs` when given (S.st waits for it) and on S.st otherwise; YUV converted into
 // S.d_stage on S.st; a source the working size reduces: host frames into S.d_yuv, 4:2:0 frames converted into S.d_full, then
-// reduced into S.d_stage (the DevFrames are rw x rh); under a frame region the same with the rectify in place of the reduce (device
-// BGR frames are read in the caller's memory; the DevFrames are ow x oh).  Every write of a slot's d_stage goes through here (page ingest through its staging buffer) and ends the
+// reduced into S.d_stage; under a frame region the same with the rectify in place of the reduce (device BGR frames are read in the
+// caller's memory); the DevFrames are then plan.uw x plan.uh.  Every write of a slot's d_stage goes through here (page ingest through its staging buffer) and ends the
 // frames slideo_changed_mask_bgr8 kept for slideo_match_kept_frames.
 // into: the staging buffer in place of S.d_stage (a gated unit's S.d_gstage; the kept frames of a mask call then stay).
 DevFrames stage_frames(slideo_matcher* m, Slot& S, const FrameSrc& src, int first, int n, hipStream_t cs = nullptr, DevBuf* into = nullptr);
 void upload_rng_stream(slideo_matcher* m, uint32_t len);
-void unit_submit(slideo_matcher* m, Slot& S, const DevFrames& f, int n, bool allow_async = true);
+// mask_pyr: the frame mask pyramid of the unit (FramePlan::mask_pyr), kept in S.u_mask
+void unit_submit(slideo_matcher* m, Slot& S, const DevFrames& f, int n, const uint8_t* mask_pyr, bool allow_async = true);
 void unit_collect(slideo_matcher* m, Slot& S, slideo_verdict* out_host);
 // a synchronous frame call through the unit pipeline; gated: through the gate (changed_out, similarity_out as the gated entry points')
 void match_frames_impl(slideo_matcher* m, int n, FrameSrc src, slideo_verdict* out, hipStream_t user_stream, bool gated = false,
@@ -439,9 +430,10 @@ inline float changed_similarity(unsigned long long ssd, int n) {
     float max_error = std::sqrt((255.0f * 255.0f * 3.0f) * (float)n);
     return 1.0f - (float)e / max_error;
 }
-inline float changed_similarity(unsigned long long ssd, int sw, int sh) { return changed_similarity(ssd, sw * sh); }
 // S's staging buffer with room for `bytes` (ends the kept frames of a mask call)
 uint8_t* stage_for_upload(slideo_matcher* m, Slot& S, size_t bytes);
+// the image taps: the one image of `img` staged on slot 0 (idle matcher), its ob bytes to the host
+void tap_staged(slideo_matcher* m, const FrameSrc& img, uint8_t* out, int64_t ob);
 // ProcessedImage::compute over n host pages (mo/lib.rs:92-131) WITHOUT appending them: the analysed pages, in order, into `out`
 void analyse_pages(slideo_matcher* m, int n_pages, const uint8_t* const* data, const int32_t* width, const int32_t* height, const int32_t* stride_bytes,
                    std::vector<HostPage>& out, uint64_t progress_base, uint64_t progress_total);
@@ -457,10 +449,10 @@ void orb_stage1(slideo_matcher* m, Slot& S, const DevFrames& f, int n, bool with
 void orb_wait_info(slideo_matcher* m, Slot& S);
 void orb_stage2(slideo_matcher* m, Slot& S, int w, int h, bool by_capacity = false);
 void run_orb(slideo_matcher* m, Slot& S, const DevFrames& f, int n, bool keep_host_qofs, bool with_blur = false, const uint8_t* mask_pyr = nullptr);
-// Frame mask (include/slideo_amd.h "Frame mask").  frame_mask_set: the pyramid of the w x h mask (rows `stride` apart, host memory)
-// on m->stream, replacing the one before; mask null: none.  frame_mask_for: the pyramid a frame call of analysed size w x h
+// Frame mask (include/slideo_amd.h "Frame mask").  frame_mask_build: the pyramid of the w x h mask (rows `stride` apart, host memory)
+// into `out` on m->stream (settings_commit installs it).  frame_mask_for: the pyramid a frame call of analysed size w x h
 // filters its candidates with — nullptr without a mask, SLIDEO_ERR_INVALID_ARG at another size.
-void frame_mask_set(slideo_matcher* m, const uint8_t* mask, int w, int h, int stride);
+void frame_mask_build(slideo_matcher* m, const uint8_t* mask, int w, int h, int stride, DevBuf& out);
 const uint8_t* frame_mask_for(const slideo_matcher* m, int w, int h);
 // the two ORB kernels the SIFT stage shares: BGR -> gray u8 (pitch `pitch`, frame stride gframe), and the per-frame offsets scan
 void orb_launch_gray(const slideo_matcher* m, const uint8_t* frames_dev, int64_t frame_stride, int stride, uint8_t* gray, int64_t gframe, int w, int h,
@@ -502,9 +494,10 @@ void l2_lists_to_keys(slideo_matcher* m, Slot& S, const DevBuf& lists, int kq, u
 void verify_stage_init(slideo_matcher* m);
 VerifyParams make_vp(const slideo_config& c);
 void unit_verify(slideo_matcher* m, Slot& S, const VerifyParams& vp, const DevFrames& f, int n, uint32_t qtot);
-void run_small(slideo_matcher* m, const DevFrames& imgs, int n, int& sw, int& sh, hipStream_t st);
+// (sw, sh: the small size, for callers without a FramePlan — pages, taps, the validity map)
+void run_small(slideo_matcher* m, const DevFrames& imgs, int n, hipStream_t st, int* sw = nullptr, int* sh = nullptr);
 // the same into `dst` (n small images back to back) in place of m->d_small: small images of consecutive gated units overlap
-void run_small_into(slideo_matcher* m, const DevFrames& imgs, int n, DevBuf& dst, int& sw, int& sh, hipStream_t st);
+void run_small_into(slideo_matcher* m, const DevFrames& imgs, int n, DevBuf& dst, hipStream_t st, int* sw = nullptr, int* sh = nullptr);
 // ssd[i] = sum of squared differences of the small images a + i * a_stride and b + i * b_stride (`bytes` each), i < n
 void launch_ssd(const uint8_t* a, int64_t a_stride, const uint8_t* b, int64_t b_stride, int64_t bytes, unsigned long long* ssd, int n, hipStream_t st);
 
@@ -518,20 +511,19 @@ void page_set_check_mode(const slideo_matcher* m);
 
 // ---- stage_gate.hip -------------------------------------------------------------------------------
 void gate_release(slideo_matcher* m);          // the gate's events (slideo_matcher_destroy)
-inline void gate_state_reset(slideo_matcher* m) { m->gate = slideo_matcher::GateState{}; }
+inline void gate_state_reset(slideo_matcher* m) { m->gate = slideo_matcher::GateState{}; }      // (the gate's own entry points; a setter: settings_commit)
 // FrameSrc::staging_bytes' gate_small of a gated call (a small image has at most small_area pixels)
 // (under a direct similarity: + the frame's centred operand row, its row of dot products and its record; under the direct scope
 // VALID + the masked page norms, 8 bytes per page once per matcher: counted with every frame, a unit has at least one)
 inline size_t gate_small_budget(const slideo_matcher* m) {
     const size_t small = (size_t)m->cfg.small_area * 3 + 64;
-    if (!(m->direct_t > 0.f)) return small;
+    if (!(m->fs.direct_t > 0.f)) return small;
     const size_t look = 2 * small + 128 + m->pages.size() * 8 + 64;
-    return m->direct_scope == SLIDEO_DIRECT_VALID ? look + m->pages.size() * 8 : look;
+    return m->fs.direct_scope == SLIDEO_DIRECT_VALID ? look + m->pages.size() * 8 : look;
 }
-// a validated source's frames against the gate state: one size and one format family since the last reset (SLIDEO_ERR_STATE)
-void gate_check(const slideo_matcher* m, const FrameSrc& src);
-// the same against a state held elsewhere (the N-device group's, capi_group.hip)
-void gate_check(const slideo_matcher::GateState& g, int small_area, const FrameSrc& src);
+// a validated source's frames against a gate state (m->gate, the N-device group's): one size and one format family since the last
+// reset (SLIDEO_ERR_STATE)
+void gate_check(const slideo_matcher::GateState& g, const FrameSrc& src);
 // slideo_matcher_gate_reset_from_frame_*: the gate state of an idle matcher := the small image of the ONE frame of src (frame_stride
 // as of a single frame), staged as a gated unit stages it; user_stream: the stream a device frame was produced on
 void gate_prime(slideo_matcher* m, FrameSrc src, hipStream_t user_stream);
@@ -541,11 +533,11 @@ void gate_unit_submit(slideo_matcher* m, Slot& S, const FrameSrc& src, int first
 void gate_unit_collect(slideo_matcher* m, Slot& S, uint8_t* changed_out, float* similarity_out, slideo_verdict* verdicts_out);
 
 // Frame mask scope (include/slideo_amd.h "Frame mask scope").  gate_map_build: the validity map of the w x h mask at dmask (DEVICE
-// memory, rows `pitch` apart) into `out`, on m->stream (SLIDEO_ERR_INVALID_ARG when no small pixel is valid; out is then unchanged
-// apart from its buffer).  gate_map_for: the weights a call that makes changed flags from frames of analysed size w x h sums its
+// memory, rows `pitch` apart) into `out` and its weights `out_w`, on m->stream (SLIDEO_ERR_INVALID_ARG when no small pixel is valid).
+// gate_map_for: the weights a call that makes changed flags from frames of analysed size w x h sums its
 // SSDs under, *npx the pixels its similarities are normalised over — nullptr and sw * sh unless a mask is set under the GATE scope;
 // SLIDEO_ERR_INVALID_ARG at another size than the mask's.
-void gate_map_build(slideo_matcher* m, const uint8_t* dmask, int pitch, int w, int h, slideo_matcher::GateMap& out);
+void gate_map_build(slideo_matcher* m, const uint8_t* dmask, int pitch, int w, int h, GateMap& out, DevBuf& out_w);
 const uint8_t* gate_map_for(const slideo_matcher* m, int w, int h, int sw, int sh, int* npx);
 // launch_ssd, under `weights` (gate_map_for) when not null
 void launch_gate_ssd(const uint8_t* weights, const uint8_t* a, int64_t a_stride, const uint8_t* b, int64_t b_stride, int64_t bytes,
@@ -556,9 +548,6 @@ int64_t gate_ssd_threshold(float changed_similarity_, int64_t n);
 // ---- stage_direct.hip -----------------------------------------------------------------------------
 // the largest SSD whose host similarity over n pixels is >= t (slideo_direct_ssd_threshold; -1: none)
 int64_t direct_ssd_threshold(float t, int64_t n);
-// t > 0 together with a frame mask under the GATE scope (SLIDEO_ERR_UNSUPPORTED): checked by whichever of the three set calls
-// would complete the combination, before it changes anything; never under the direct scope SLIDEO_DIRECT_VALID
-void direct_check_mask(bool mask_set, uint32_t scope, float t, uint32_t direct_scope);
 // What a gated unit of n frames with sw x sh small images looks up in: everything that can fail for want of memory — the page
 // operand at its first use, the selected set's eligible list, the slot's workspaces — happens here, in front of any change to the
 // gate state.  cls == null: no page of the set shares the small size, the unit does not look up.
@@ -594,3 +583,12 @@ void add_pages_sift(slideo_matcher* m, Slot& S, const DevFrames& pages, int cnt)
     catch (const std::exception& e) { slideo::set_err(m, e.what()); return SLIDEO_ERR_HIP; } \
     catch (...) { slideo::set_err(m, "unknown error"); return SLIDEO_ERR_HIP; }       \
     return SLIDEO_OK;
+
+// A matcher's set call as its entry point's return code: propose(fs) — frame_settings.h propose_* — into settings_commit
+template <class Propose>
+int32_t matcher_set(slideo_matcher* m, slideo::Setting what, Propose propose, const uint8_t* mask = nullptr, int stride = 0) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    slideo::settings_commit(m, what, propose(m->fs), mask, stride);
+    API_CATCH(m)
+}

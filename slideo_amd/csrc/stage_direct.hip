@@ -23,13 +23,6 @@ int64_t direct_ssd_threshold(float t, int64_t n) {
     return lo;
 }
 
-void direct_check_mask(bool mask_set, uint32_t scope, float t, uint32_t direct_scope) {
-    if (direct_scope == SLIDEO_DIRECT_VALID) return;                   // (the look-up compares what the gate compares)
-    if (t > 0.f && mask_set && (scope & SLIDEO_MASK_GATE))
-        fail(SLIDEO_ERR_UNSUPPORTED, "the direct page look-up compares whole small images: not together with a frame mask under SLIDEO_MASK_GATE "
-             "(a look-up over the valid pixels only: slideo_matcher_set_direct_scope(m, SLIDEO_DIRECT_VALID))");
-}
-
 namespace {
 
 int64_t direct_kp(int64_t L) { return cdiv64(L, DIRECT_KGRAN) * DIRECT_KGRAN; }
@@ -109,10 +102,10 @@ DirectClass* direct_class_for(slideo_matcher* m, int sw, int sh) {
 // b'^2 per page, cached with the class under the map's generation.  On m->stream, synchronised: the map changes on an idle
 // matcher only, so the unit that finds the norms stale is the only one in flight.  The deck operand is neither rebuilt nor copied.
 const long long* direct_masked_norms(slideo_matcher* m, DirectClass& c) {
-    const slideo_matcher::GateMap& g = m->gate_map;
+    const GateMap& g = m->fs.gate_map;
     if (!g.on || g.sw != c.sw || g.sh != c.sh)
         fail(SLIDEO_ERR_HIP, "internal: the gate's validity map is %dx%d (%d), the class's small images are %dx%d", g.sw, g.sh, (int)g.on, c.sw, c.sh);
-    if (c.norm_v_gen == m->gate_map_gen) return c.d_norm_v.as<long long>();
+    if (c.norm_v_gen == m->fs.gate_map_gen) return c.d_norm_v.as<long long>();
     hipStream_t st = m->stream;
     std::vector<long long> ofs((size_t)c.np);
     {
@@ -127,9 +120,9 @@ const long long* direct_masked_norms(slideo_matcher* m, DirectClass& c) {
     d_ofs.reserve((size_t)c.np * 8);
     HIP_CHECK(hipMemcpyAsync(d_ofs.p, ofs.data(), ofs.size() * 8, hipMemcpyHostToDevice, st));
     launch_centre(m->d_page_small.as<uint8_t>(), 0, d_ofs.as<long long>(), c.np, c.np_pad, c.L, c.kp, nullptr, c.d_norm_v.as<long long>(), st,
-                  g.d_w.as<uint8_t>());
+                  m->d_gate_w.as<uint8_t>());
     HIP_CHECK(hipStreamSynchronize(st));
-    c.norm_v_gen = m->gate_map_gen;
+    c.norm_v_gen = m->fs.gate_map_gen;
     return c.d_norm_v.as<long long>();
 }
 
@@ -210,7 +203,7 @@ void direct_unit_lookup(Slot& S, const DirectPlan& plan, int n) {
 }
 
 void direct_unit_gate(slideo_matcher* m, Slot& S, int n, int npx, int32_t* idx, uint32_t* count, int32_t* h_idx, uint8_t* h_rec) {
-    const long long thr = direct_ssd_threshold(m->direct_t, npx);
+    const long long thr = direct_ssd_threshold(m->fs.direct_t, npx);
     direct_gate_kernel<<<1, DIRECT_BLOCK, 0, S.st>>>(direct_best_of(S, n), n, thr, idx, count, h_idx, h_rec);
     check_launch("direct_gate_kernel");
 }
@@ -241,35 +234,22 @@ int64_t slideo_direct_ssd_threshold(float t, int64_t n_pixels) {
 }
 
 int32_t slideo_matcher_set_direct_similarity(slideo_matcher* m, float t) {
-    if (!m) return SLIDEO_ERR_INVALID_ARG;
-    API_TRY
-    if (!(t >= 0.f) || t > 1.f) fail(SLIDEO_ERR_INVALID_ARG, "direct similarity %g: 0 (off) or 0 < t <= 1", (double)t);
-    require_idle(m);
-    direct_check_mask(m->mask.set, m->mask_scope, t, m->direct_scope);
-    m->direct_t = t;
-    API_CATCH(m)
+    return matcher_set(m, SET_DIRECT_SIMILARITY, [&](const FrameSettings& s) { return propose_direct_similarity(s, t); });
 }
 
 int32_t slideo_matcher_direct_similarity(const slideo_matcher* m, float* t) {
     if (!m || !t) return SLIDEO_ERR_INVALID_ARG;
-    *t = m->direct_t;
+    *t = m->fs.direct_t;
     return SLIDEO_OK;
 }
 
 int32_t slideo_matcher_set_direct_scope(slideo_matcher* m, uint32_t scope) {
-    if (!m) return SLIDEO_ERR_INVALID_ARG;
-    API_TRY
-    if (scope != SLIDEO_DIRECT_WHOLE && scope != SLIDEO_DIRECT_VALID)
-        fail(SLIDEO_ERR_INVALID_ARG, "direct scope %u: SLIDEO_DIRECT_WHOLE (0) or SLIDEO_DIRECT_VALID (1)", scope);
-    require_idle(m);
-    direct_check_mask(m->mask.set, m->mask_scope, m->direct_t, scope);    // (the way back to WHOLE: the scope before stays in force)
-    m->direct_scope = scope;
-    API_CATCH(m)
+    return matcher_set(m, SET_DIRECT_SCOPE, [&](const FrameSettings& s) { return propose_direct_scope(s, scope); });
 }
 
 int32_t slideo_matcher_direct_scope(const slideo_matcher* m, uint32_t* scope) {
     if (!m || !scope) return SLIDEO_ERR_INVALID_ARG;
-    *scope = m->direct_scope;
+    *scope = m->fs.direct_scope;
     return SLIDEO_OK;
 }
 
@@ -281,12 +261,12 @@ static void page_small_ssd_impl(slideo_matcher* m, const uint8_t* small, int32_t
              m->cfg.small_area);
     const uint8_t* weights = nullptr;
     if (valid) {
-        const slideo_matcher::GateMap& g = m->gate_map;
-        if (!m->mask.set || !(m->mask_scope & SLIDEO_MASK_GATE) || !g.on)
+        const GateMap& g = m->fs.gate_map;
+        if (!g.on)
             fail(SLIDEO_ERR_STATE, "page_small_ssd_valid: no validity map is in force (a frame mask under SLIDEO_MASK_GATE)");
         if (sw != g.sw || sh != g.sh)
             fail(SLIDEO_ERR_INVALID_ARG, "page_small_ssd_valid: %dx%d small images, the validity map is %dx%d", sw, sh, g.sw, g.sh);
-        weights = g.d_w.as<uint8_t>();
+        weights = m->d_gate_w.as<uint8_t>();
     }
     HIP_CHECK(hipSetDevice(m->device));
     require_idle(m);

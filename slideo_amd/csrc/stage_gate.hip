@@ -30,19 +30,19 @@ int64_t gate_ssd_threshold(float changed_similarity_, int64_t n) {
 // ---- frame mask scope (include/slideo_amd.h "Frame mask scope") ----------------------------------------------------------------
 // The validity map: B = the mask binarised and replicated to three channels (mask_bgr_kernel), S = to_small_image(B) through the
 // run_small_into every frame of that size goes through, then gate_valid_kernel: weights and n_valid.  Set time; the matcher is idle.
-void gate_map_build(slideo_matcher* m, const uint8_t* dmask, int pitch, int w, int h, slideo_matcher::GateMap& out) {
+void gate_map_build(slideo_matcher* m, const uint8_t* dmask, int pitch, int w, int h, GateMap& out, DevBuf& out_w) {
     hipStream_t st = m->stream;
     DevBuf d_bgr, d_s, d_n;
     d_bgr.reserve((size_t)w * h * 3);
     mask_bgr_kernel<<<(unsigned)cdiv64((int64_t)w * h, GATE_BLOCK), GATE_BLOCK, 0, st>>>(dmask, pitch, w, h, d_bgr.as<uint8_t>());
     check_launch("mask_bgr_kernel");
     int sw = 0, sh = 0;
-    run_small_into(m, DevFrames{d_bgr.as<uint8_t>(), w, h, w * 3, (int64_t)w * h * 3}, 1, d_s, sw, sh, st);
+    run_small_into(m, DevFrames{d_bgr.as<uint8_t>(), w, h, w * 3, (int64_t)w * h * 3}, 1, d_s, st, &sw, &sh);
     const size_t sb = (size_t)sw * sh * 3;
-    out.on = false;
-    out.d_w.reserve(sb + 4);
+    out = GateMap{};
+    out_w.reserve(sb + 4);
     d_n.reserve(8);
-    gate_valid_kernel<<<1, GATE_BLOCK, 0, st>>>(d_s.as<uint8_t>(), sw * sh, out.d_w.as<uint8_t>(), d_n.as<long long>());
+    gate_valid_kernel<<<1, GATE_BLOCK, 0, st>>>(d_s.as<uint8_t>(), sw * sh, out_w.as<uint8_t>(), d_n.as<long long>());
     check_launch("gate_valid_kernel");
     long long nv = -1;
     HIP_CHECK(hipMemcpyAsync(&nv, d_n.p, 8, hipMemcpyDeviceToHost, st));
@@ -56,14 +56,15 @@ void gate_map_build(slideo_matcher* m, const uint8_t* dmask, int pitch, int w, i
 
 const uint8_t* gate_map_for(const slideo_matcher* m, int w, int h, int sw, int sh, int* npx) {
     *npx = sw * sh;
-    if (!m->mask.set || !(m->mask_scope & SLIDEO_MASK_GATE)) return nullptr;
-    if (w != m->mask.w || h != m->mask.h)
+    const FrameMask& k = m->fs.mask;
+    if (!m->fs.gate_scope()) return nullptr;
+    if (w != k.w || h != k.h)
         fail(SLIDEO_ERR_INVALID_ARG, "frame mask scope: the frames are analysed at %dx%d, the mask the gate ignores regions under is %dx%d "
-             "(slideo_matcher_set_frame_mask)", w, h, m->mask.w, m->mask.h);
-    const slideo_matcher::GateMap& g = m->gate_map;
+             "(slideo_matcher_set_frame_mask)", w, h, k.w, k.h);
+    const GateMap& g = m->fs.gate_map;      // (set-time state against the call's)
     if (!g.on || g.sw != sw || g.sh != sh) fail(SLIDEO_ERR_HIP, "internal: the gate's validity map is %dx%d (%d), the small images are %dx%d", g.sw, g.sh, (int)g.on, sw, sh);
     *npx = (int)g.n_valid;
-    return g.d_w.as<uint8_t>();
+    return m->d_gate_w.as<uint8_t>();
 }
 
 void launch_gate_ssd(const uint8_t* weights, const uint8_t* a, int64_t a_stride, const uint8_t* b, int64_t b_stride, int64_t bytes,
@@ -74,18 +75,13 @@ void launch_gate_ssd(const uint8_t* weights, const uint8_t* a, int64_t a_stride,
 }
 
 // The frames of a gated call against the gate state: one size and one format family since the last reset.  Nothing is changed here.
-void gate_check(const slideo_matcher* m, const FrameSrc& src) { gate_check(m->gate, m->cfg.small_area, src); }
-
-void gate_check(const slideo_matcher::GateState& g, int small_area, const FrameSrc& src) {
+void gate_check(const slideo_matcher::GateState& g, const FrameSrc& src) {
     if (g.seen && (g.w != src.w || g.h != src.h || g.yuv != (src.yuv != nullptr)))
         fail(SLIDEO_ERR_STATE, "gated frames changed from %dx%d %s to %dx%d %s without slideo_matcher_gate_reset", g.w, g.h, g.yuv ? "yuv420" : "bgr8",
              src.w, src.h, src.yuv ? "yuv420" : "bgr8");
-    if (g.has && !g.seen) {
-        int sw = 0, sh = 0;
-        small_size(src.unit_w(), src.unit_h(), small_area, sw, sh);
-        if (sw != g.sw || sh != g.sh)
-            fail(SLIDEO_ERR_STATE, "the gate holds a %dx%d small image, these frames' is %dx%d: slideo_matcher_gate_reset first", g.sw, g.sh, sw, sh);
-    }
+    if (g.has && !g.seen && (src.plan.sw != g.sw || src.plan.sh != g.sh))
+        fail(SLIDEO_ERR_STATE, "the gate holds a %dx%d small image, these frames' is %dx%d: slideo_matcher_gate_reset first", g.sw, g.sh, src.plan.sw,
+             src.plan.sh);
 }
 
 // slideo_matcher_gate_reset_from_frame_*: the one frame staged as a gated unit stages its frames (slot 0; plain device BGR is read in
@@ -104,13 +100,12 @@ void gate_prime(slideo_matcher* m, FrameSrc src, hipStream_t user_stream) {
     }
     if (m->last_gate_ev && m->last_gate_ev != S.ev_gate) HIP_CHECK(hipStreamWaitEvent(st, m->last_gate_ev, 0));
     const DevFrames f = stage_frames(m, S, src, 0, 1, nullptr, &S.d_gstage);
-    int sw = 0, sh = 0;
-    run_small_into(m, f, 1, m->d_gate_small, sw, sh, st);
+    run_small_into(m, f, 1, m->d_gate_small, st);
     HIP_CHECK(hipEventRecord(S.ev_gate, st));
     m->last_gate_ev = S.ev_gate;
     HIP_CHECK(hipStreamSynchronize(st));            // (the caller's frame is free again)
     gate_state_reset(m);
-    m->gate.has = true; m->gate.sw = sw; m->gate.sh = sh;
+    m->gate.has = true; m->gate.sw = src.plan.sw; m->gate.sh = src.plan.sh;
 }
 
 // One gated unit: frames [first, first + n) of src through the gate, the changed ones through unit_submit.  One short host wait
@@ -120,24 +115,17 @@ void gate_unit_submit(slideo_matcher* m, Slot& S, const FrameSrc& src, int first
     if (!S.ev_gate) HIP_CHECK(hipEventCreateWithFlags(&S.ev_gate, hipEventDisableTiming));
     // under a direct similarity: the page operand, the set's eligible list and the look-up's workspaces first, so that a failure
     // there leaves the gate state as it was (include/slideo_amd.h "Direct page look-up")
-    const bool look = m->direct_t > 0.f;
+    const FramePlan& P = src.plan;
+    const int sw = P.sw, sh = P.sh, npx = P.npx;
+    const uint8_t* weights = P.gate_w;
+    const bool look = m->fs.direct_t > 0.f;
     DirectPlan plan;
-    int psw = 0, psh = 0;
-    if (look) {
-        small_size(src.unit_w(), src.unit_h(), m->cfg.small_area, psw, psh);
-        // the direct scope VALID: over the pixels the gate compares (null without a map in force: whole images)
-        int npx_ = 0;
-        const uint8_t* dw = m->direct_scope == SLIDEO_DIRECT_VALID ? gate_map_for(m, src.unit_w(), src.unit_h(), psw, psh, &npx_) : nullptr;
-        plan = direct_unit_prepare(m, S, n, psw, psh, dw);
-    }
+    // the direct scope VALID: over the pixels the gate compares (null without a map in force: whole images)
+    if (look) plan = direct_unit_prepare(m, S, n, sw, sh, m->fs.direct_scope == SLIDEO_DIRECT_VALID ? weights : nullptr);
     const DevFrames all = stage_frames(m, S, src, first, n, cs, &S.d_gstage);
-    int sw = 0, sh = 0;
-    run_small_into(m, all, n, S.d_gsmall, sw, sh, st);
-    if (look && (sw != psw || sh != psh)) fail(SLIDEO_ERR_HIP, "internal: the look-up was prepared for %dx%d small images, the unit's are %dx%d", psw, psh, sw, sh);
+    run_small_into(m, all, n, S.d_gsmall, st);
     const int64_t sb = (int64_t)sw * sh * 3;
     const uint8_t* small = S.d_gsmall.as<uint8_t>();
-    int npx = 0;
-    const uint8_t* weights = gate_map_for(m, all.w, all.h, sw, sh, &npx);      // (validate_frames held the frames to the mask's size)
     S.d_gate.reserve((size_t)n * 13 + 16);
     unsigned long long* ssd = S.d_gate.as<unsigned long long>();
     int32_t* idx = reinterpret_cast<int32_t*>(S.d_gate.as<uint8_t>() + (size_t)n * 8);
@@ -179,7 +167,7 @@ void gate_unit_submit(slideo_matcher* m, Slot& S, const FrameSrc& src, int first
     }
     Slot::GateUnit gu;
     gu.on = true; gu.n = n; gu.k = k; gu.sw = sw; gu.sh = sh; gu.npx = npx; gu.force0 = force0;
-    gu.direct = direct; gu.direct_t = m->direct_t; gu.direct_ofs = direct_ofs;
+    gu.direct = direct; gu.direct_t = m->fs.direct_t; gu.direct_ofs = direct_ofs;
     if (k == 0) {                                   // no frame changed (or every changed one is direct): no pipeline; the collect returns at once
         S.busy = true; S.n = 0; S.u_async = false; S.timed = false;
         S.gate = gu;
@@ -200,7 +188,7 @@ void gate_unit_submit(slideo_matcher* m, Slot& S, const FrameSrc& src, int first
         check_launch("gather_frames_kernel");
         f = DevFrames{dst, all.w, all.h, row_bytes, fb};
     }
-    unit_submit(m, S, f, k);
+    unit_submit(m, S, f, k, P.mask_pyr);
     S.gate = gu;
 }
 

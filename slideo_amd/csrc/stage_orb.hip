@@ -293,15 +293,13 @@ void run_orb(slideo_matcher* m, Slot& S, const DevFrames& f, int n, bool keep_ho
 // ---- frame mask (include/slideo_amd.h "Frame mask") ---------------------------------------------------------------------------
 // The mask pyramid: level 0 the mask as given, level l the image pyramid's own resize (resize_kernel, the w x h geometry's tap
 // tables) of level l - 1 followed by threshold(254, THRESH_TOZERO) — one frame in the pyramid's level layout, so that a FAST
-// candidate's (y, x) indexes its level directly.  Made once per mask, here; the matcher is idle.
-void frame_mask_set(slideo_matcher* m, const uint8_t* mask, int w, int h, int stride) {
-    if (!mask) { m->mask.set = false; m->mask.w = m->mask.h = 0; return; }
+// candidate's (y, x) indexes its level directly.  Made once per mask, here, into `out`; the matcher is idle.
+void frame_mask_build(slideo_matcher* m, const uint8_t* mask, int w, int h, int stride, DevBuf& out) {
     GeomEntry& ge = geom_for(m, w, h);
     const PyrGeom& g = ge.g;
     hipStream_t st = m->stream;
-    m->mask.set = false;                                  // (a failure below leaves no mask rather than half of one)
-    m->mask.d_pyr.reserve((size_t)g.frame_bytes + 256);
-    uint8_t* pyr = m->mask.d_pyr.as<uint8_t>();
+    out.reserve((size_t)g.frame_bytes + 256);
+    uint8_t* pyr = out.as<uint8_t>();
     HIP_CHECK(hipMemsetAsync(pyr, 0, (size_t)g.frame_bytes + 256, st));
     HIP_CHECK(hipMemcpy2DAsync(pyr + g.lv[0].ofs, g.lv[0].pitch, mask, stride, w, h, hipMemcpyHostToDevice, st));
     for (int l = 1; l < g.nlevels; ++l) {
@@ -315,16 +313,15 @@ void frame_mask_set(slideo_matcher* m, const uint8_t* mask, int w, int h, int st
         check_launch("mask_threshold_kernel");
     }
     HIP_CHECK(hipStreamSynchronize(st));                  // (the caller's mask bytes are copied: they may go)
-    m->mask.set = true; m->mask.w = w; m->mask.h = h;
 }
 
 const uint8_t* frame_mask_for(const slideo_matcher* m, int w, int h) {
-    if (!m->mask.set) return nullptr;
-    if (w != m->mask.w || h != m->mask.h)
-        fail(SLIDEO_ERR_INVALID_ARG, "frame mask: the frames are analysed at %dx%d, the mask is %dx%d (slideo_matcher_set_frame_mask)", w, h,
-             m->mask.w, m->mask.h);
-    if (!(m->mask_scope & SLIDEO_MASK_DETECT)) return nullptr;       // (a GATE-only mask: the size rule above, no filter)
-    return m->mask.d_pyr.as<uint8_t>();
+    const FrameMask& k = m->fs.mask;
+    if (!k.set) return nullptr;
+    if (w != k.w || h != k.h)
+        fail(SLIDEO_ERR_INVALID_ARG, "frame mask: the frames are analysed at %dx%d, the mask is %dx%d (slideo_matcher_set_frame_mask)", w, h, k.w, k.h);
+    if (!(m->fs.mask_scope & SLIDEO_MASK_DETECT)) return nullptr;    // (a GATE-only mask: the size rule above, no filter)
+    return m->d_mask_pyr.as<uint8_t>();
 }
 
 }  // namespace slideo

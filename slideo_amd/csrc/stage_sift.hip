@@ -334,7 +334,7 @@ int32_t slideo_matcher_use_sift(slideo_matcher* m, const slideo_sift_config* cfg
     sift_check_cfg(cfg, 64, 64);
     if (!(ratio >= 0.f) || !(ratio <= 1.f)) fail(SLIDEO_ERR_INVALID_ARG, "ratio must be in [0, 1] (0 = the path's tolerance vote)");
     if (m->cfg.matcher != 0) fail(SLIDEO_ERR_UNSUPPORTED, "the LSH index is a Hamming index: not with SIFT features");
-    if (m->mask.set) fail(SLIDEO_ERR_UNSUPPORTED, "the frame mask filters ORB's FAST candidates: not in SIFT mode (clear it first)");
+    if (m->fs.mask.set) fail(SLIDEO_ERR_UNSUPPORTED, "the frame mask filters ORB's FAST candidates: not in SIFT mode (clear it first)");
     m->sift_on = true; m->sift_cfg = *cfg; m->sift_ratio = ratio;
     API_CATCH(m)
 }

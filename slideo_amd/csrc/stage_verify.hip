@@ -19,15 +19,16 @@ VerifyParams make_vp(const slideo_config& c) {
 }
 
 // ---- to_small_image of n equally sized device images into m->d_small --------------------
-void run_small(slideo_matcher* m, const DevFrames& imgs, int n, int& sw, int& sh, hipStream_t st) {
-    run_small_into(m, imgs, n, m->d_small, sw, sh, st);
+void run_small(slideo_matcher* m, const DevFrames& imgs, int n, hipStream_t st, int* sw, int* sh) {
+    run_small_into(m, imgs, n, m->d_small, st, sw, sh);
 }
 
-void run_small_into(slideo_matcher* m, const DevFrames& imgs, int n, DevBuf& dst, int& sw, int& sh, hipStream_t st) {
+void run_small_into(slideo_matcher* m, const DevFrames& imgs, int n, DevBuf& dst, hipStream_t st, int* sw_out, int* sh_out) {
     int ac = area_class_for(m, imgs.w, imgs.h);
     upload_area(m);
     const AreaGeom& ag = m->area_geoms[ac];
-    sw = ag.dw; sh = ag.dh;
+    const int sw = ag.dw, sh = ag.dh;
+    if (sw_out) { *sw_out = sw; *sh_out = sh; }
     dst.reserve((size_t)n * sw * sh * 3);
     int tiles = cdiv(sw, SM_TW) * cdiv(sh, SM_TH);
     small_image_kernel<<<dim3(tiles, n), 256, 0, st>>>(ag, m->d_area_taps.as<AreaTap>(), m->d_area_idx.as<int32_t>(), imgs.p,
