@@ -9,6 +9,13 @@ pub const SLIDEO_MASK_DETECT: u32 = 1;
 pub const SLIDEO_MASK_GATE: u32 = 2;
 pub const SLIDEO_DIRECT_WHOLE: u32 = 0;
 pub const SLIDEO_DIRECT_VALID: u32 = 1;
+pub const SLIDEO_YUV_MATRIX_BT601: i32 = 0;
+pub const SLIDEO_YUV_MATRIX_BT709: i32 = 1;
+pub const SLIDEO_YUV_RANGE_LIMITED: i32 = 0;
+pub const SLIDEO_YUV_RANGE_FULL: i32 = 1;
+pub const SLIDEO_YUV_DEPTH_8: i32 = 0;
+pub const SLIDEO_YUV_DEPTH_10_MSB: i32 = 1;
+pub const SLIDEO_YUV_DEPTH_10_LSB: i32 = 2;
 
 /// slideo_ocv_variants: which restatement of each OpenCV primitive runs.  slideo_config_default fills it; the
 /// application never touches it.
@@ -176,6 +183,7 @@ extern "C" {
     ) -> i32;
     // ---- decoded YUV 4:2:0 frames: the twins of the frame calls (same results as the BGR call on cvtColor's BGR image)
     pub fn slideo_yuv420_layout_packed(format: i32, width: i32, height: i32, out: *mut slideo_yuv420_layout) -> i32;
+    pub fn slideo_yuv420_layout_packed16(format: i32, width: i32, height: i32, out: *mut slideo_yuv420_layout) -> i32;
     pub fn slideo_group_match_frames_yuv420(
         g: *mut slideo_group,
         n_frames: i32,
@@ -473,6 +481,16 @@ extern "C" {
         sh: i32,
         ssd_out: *mut u64,
     ) -> i32;
+    // YUV colour description (include/slideo_amd.h "YUV colour description"): SLIDEO_YUV_MATRIX_* / _RANGE_* / _DEPTH_*
+    pub fn slideo_matcher_set_yuv_description(m: *mut slideo_matcher, matrix: i32, range: i32, depth: i32) -> i32;
+    pub fn slideo_matcher_yuv_description(
+        m: *const slideo_matcher,
+        matrix: *mut i32,
+        range: *mut i32,
+        depth: *mut i32,
+    ) -> i32;
+    pub fn slideo_group_set_yuv_description(g: *mut slideo_group, matrix: i32, range: i32, depth: i32) -> i32;
+    pub fn slideo_yuv_coefficients(matrix: i32, range: i32, out7: *mut i32) -> i32;
     // frame region (include/slideo_amd.h "Frame region"): frames stand for a rectified quadrilateral of themselves
     pub fn slideo_matcher_set_frame_region(
         m: *mut slideo_matcher,

@@ -91,6 +91,10 @@ pub struct HipImageVideoMatcher {
     /// top-right, bottom-right and bottom-left corner (slideo_frame_region_from_quad): a filmed projection screen, a slide
     /// in a sub-window.  The reference analyses the whole frame.  None (default) = no region.
     pub frame_region: Option<(i32, i32, [f64; 8], i32, i32)>,
+    /// (matrix, range, depth): how YUV 4:2:0 frames are read (slideo_group_set_yuv_description): ffi::SLIDEO_YUV_MATRIX_* /
+    /// _RANGE_* / _DEPTH_*.  BT.709 for HD recordings, full range for many screen recorders, a 10-bit depth for P010 /
+    /// yuv420p10le frames.  The reference reads every stream as BT.601 limited range: the default (0, 0, 0).
+    pub yuv_description: (i32, i32, i32),
 }
 
 impl Default for HipImageVideoMatcher {
@@ -103,6 +107,7 @@ impl Default for HipImageVideoMatcher {
             direct_similarity: 0.0,
             direct_scope: ffi::SLIDEO_DIRECT_WHOLE,
             frame_region: None,
+            yuv_description: (ffi::SLIDEO_YUV_MATRIX_BT601, ffi::SLIDEO_YUV_RANGE_LIMITED, ffi::SLIDEO_YUV_DEPTH_8),
         }
     }
 }
@@ -135,6 +140,10 @@ impl<'i> ImageVideoMatcher<'i> for HipImageVideoMatcher {
                 let mut m9 = [0f64; 9];
                 check(std::ptr::null_mut(), ffi::slideo_frame_region_from_quad(quad.as_ptr(), *ow, *oh, m9.as_mut_ptr()));
                 check(h, ffi::slideo_group_set_frame_region(h, *sw, *sh, m9.as_ptr(), *ow, *oh));
+            }
+            if self.yuv_description != (0, 0, 0) {
+                let (matrix, range, depth) = self.yuv_description;
+                check(h, ffi::slideo_group_set_yuv_description(h, matrix, range, depth));
             }
             if self.frame_mask_scope != ffi::SLIDEO_MASK_DETECT {
                 check(h, ffi::slideo_group_set_frame_mask_scope(h, self.frame_mask_scope));

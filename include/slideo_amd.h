@@ -17,7 +17,8 @@
  *   - images are 8-bit, 3 channels, BGR interleaved, row-major with a byte
  *     stride (the cv::Mat 8UC3 layout the reference holds, mo/lib.rs:77-83);
  *     the frame entry points also come as *_yuv420 twins that take decoded
- *     YUV 4:2:0 frames (NV12 / NV21 / I420 / YV12, section "YUV 4:2:0 frames");
+ *     YUV 4:2:0 frames (NV12 / NV21 / I420 / YV12, section "YUV 4:2:0 frames";
+ *     BT.709, full range and 10-bit samples: section "YUV colour description");
  *   - "page" = one rasterised PDF page, "frame" = one decoded video frame,
  *     page indices are 0-based positions in the order pages were added.
  *   - there is NO CPU fallback: without a gfx950 device every compute entry
@@ -669,6 +670,67 @@ int32_t     slideo_group_match_frames_yuv420(slideo_group* g, int32_t n_frames, 
 int32_t     slideo_group_changed_mask_yuv420(slideo_group* g, int32_t n_frames, const uint8_t* frames, int32_t width, int32_t height,
                                              const slideo_yuv420_layout* layout, int64_t frame_stride_bytes, const uint8_t* prev_small,
                                              uint8_t* last_small_out, uint8_t* changed_out, float* similarity_out);
+
+/* ---- YUV colour description (extension: how the *_yuv420 calls read their samples) -------------------------------------------------
+ * The "YUV 4:2:0 frames" door reads 8-bit samples as BT.601 limited range: OpenCV's cvtColor constants.  HD and 4K material is
+ * BT.709, screen recorders often write full range, and 10-bit streams (HEVC Main10, AV1) decode to P010 (VCN, VA-API) or
+ * yuv420p10le (FFmpeg).  A matcher carries a YUV DESCRIPTION (matrix, range, depth), a frame setting like the working size; the
+ * default (BT601, LIMITED, 8) is exactly "YUV 4:2:0 frames", and under it every call launches exactly what it launched before.
+ * It applies to EVERY call that takes a slideo_yuv420_layout — the match, submit, changed-mask and gated calls,
+ * slideo_matcher_gate_reset_from_frame_yuv420[_dev], the group's forms and the tap slideo_yuv420_to_bgr8.  BGR calls never look at it.
+ * Semantics: under a description a 4:2:0 frame STANDS FOR this BGR image (int32 arithmetic, >> arithmetic, half = 1 << 19,
+ * nearest chroma, as "YUV 4:2:0 frames"):
+ *     s8 = sample                     (SLIDEO_YUV_DEPTH_8)
+ *     s8 = sample16 >> 8              (SLIDEO_YUV_DEPTH_10_MSB: the container's high byte)
+ *     s8 = min(sample16, 1023) >> 2   (SLIDEO_YUV_DEPTH_10_LSB)
+ *     u = U8 - 128, v = V8 - 128, y = max(0, Y8 - y_offset) * CY
+ *     R = sat_u8((y + half + CVR*v) >> 20)
+ *     G = sat_u8((y + half + CVG*v + CUG*u) >> 20)
+ *     B = sat_u8((y + half + CUB*u) >> 20)
+ * Constants.  (BT601, LIMITED) keeps cvtColor's literals.  Every other pair by ONE rule, evaluated in float64 on the host: with
+ * Kr, Kb of the matrix (601: 0.299, 0.114; 709: 0.2126, 0.0722), Kg = 1 - Kr - Kb, sy = 255/219 and sc = 255/224 (both 1 for full
+ * range), y_offset = 16 (0 for full range):
+ *     CY = rint(sy * 2^20)   CVR = rint(sc * 2(1-Kr) * 2^20)   CUB = rint(sc * 2(1-Kb) * 2^20)
+ *     CUG = -rint(sc * 2(1-Kb) Kb/Kg * 2^20)                   CVG = -rint(sc * 2(1-Kr) Kr/Kg * 2^20)
+ *                         CY       CUB      CUG      CVG      CVR   y_offset
+ *     BT601 LIMITED   1220542  2116026  -409993  -852492  1673527   16
+ *     BT601 FULL      1048576  1858077  -360853  -748826  1470104    0
+ *     BT709 LIMITED   1220945  2215014  -223607  -558796  1879825   16
+ *     BT709 FULL      1048576  1945738  -196424  -490864  1651297    0
+ * Every coefficient is below 2^23 in magnitude and every other factor fits 9 signed bits (Y8 - y_offset in 0..255, u / v in
+ * -128..127): every operand fits 24 signed bits; every product (at most 255 * 1220945 = 3.11e8, 128 * 2215014 = 2.84e8) and every
+ * sum (at most 3.11e8 + 2^19 + 2.84e8) fits int32.  The kernel's 24-bit multiplies rely on it (csrc/yuv420.hip.h
+ * yuv420_to_bgr_desc_kernel).
+ * Contract: every *_yuv420 call under a description returns, bit for bit, what the matching *_bgr8 call returns on that image:
+ * verdicts, candidate traces, changed flags, similarities, small images.  Working size, frame region, frame mask and scopes, the
+ * direct look-up, page sets and SIFT mode see the converted BGR image.
+ * 16-BIT CONTAINERS (both 10-bit depths): samples are 16-bit little-endian.  All strides and offsets REMAIN BYTES, and the layout
+ * rules count two bytes per sample: y_stride >= 2 * width; uv_stride >= 2 * (width/2) * uv_step; strides, offsets and
+ * frame_stride even; with uv_step 2, |v_offset - u_offset| == 2; plane overlap and frame_stride count two bytes per sample.  A
+ * layout that is valid for 8-bit samples but not for the matcher's depth is SLIDEO_ERR_INVALID_ARG, the rule named.  A host
+ * frame is then 3 bytes per pixel of upload and staging.
+ * DEPARTURE: the reference reads every stream as BT.601 limited range; a non-default description departs from it on purpose.
+ * The 10-bit narrowing is TRUNCATION (the top 8 of the 10 bits) and is the library's own definition; swscale rounds differently. */
+#define SLIDEO_YUV_MATRIX_BT601   0   /* default */
+#define SLIDEO_YUV_MATRIX_BT709   1
+#define SLIDEO_YUV_RANGE_LIMITED  0   /* default */
+#define SLIDEO_YUV_RANGE_FULL     1
+#define SLIDEO_YUV_DEPTH_8        0   /* default: one byte per sample */
+#define SLIDEO_YUV_DEPTH_10_MSB   1   /* 16-bit little-endian containers, value in the top 10 bits (P010, and its planar form) */
+#define SLIDEO_YUV_DEPTH_10_LSB   2   /* 16-bit little-endian containers, value in the low 10 bits (yuv420p10le / I010, P010-LSB) */
+/* Before or after finalize, any number of times.  SLIDEO_ERR_STATE with units in flight; a value outside the enumerations is
+ * SLIDEO_ERR_INVALID_ARG and the state before stays.  Ends the kept frames of an earlier mask call and resets the gate state to
+ * "none", as slideo_matcher_set_frame_region does. */
+int32_t     slideo_matcher_set_yuv_description(slideo_matcher* m, int32_t matrix, int32_t range, int32_t depth);
+int32_t     slideo_matcher_yuv_description(const slideo_matcher* m, int32_t* matrix, int32_t* range, int32_t* depth);
+/* Validates every member before changing any; resets the group's gate state. */
+int32_t     slideo_group_set_yuv_description(slideo_group* g, int32_t matrix, int32_t range, int32_t depth);
+/* The seven integers of the fixed-point conversion under (matrix, range): CY, CUB, CUG, CVG, CVR, y_offset, and SHIFT (20).  A pure
+ * host function (no device). */
+int32_t     slideo_yuv_coefficients(int32_t matrix, int32_t range, int32_t* out7);
+/* The tight layout of `format` with 16-bit containers (strides and offsets in BYTES): slideo_yuv420_layout_packed's, doubled.  Such
+ * a frame is width * height * 3 bytes. */
+int32_t     slideo_yuv420_layout_packed16(int32_t format, int32_t width, int32_t height, slideo_yuv420_layout* out);
 
 /* ---- Working size (extension: the reference analyses every frame at the size it arrives in) ---------------------------------
  * A matcher carries a working size (max_w, max_h); (0, 0) = none, the default.  While one is set, a frame of w x h with

@@ -53,20 +53,47 @@ class Yuv420Layout(C.Structure):
 YUV420_FORMATS = {"nv12": 0, "nv21": 1, "i420": 2, "yv12": 3}
 
 
-def yuv420_layout(fmt, w, h, pitch=None, row_align=None):
+YUV_MATRICES = {"bt601": 0, "bt709": 1}
+YUV_RANGES = {"limited": 0, "full": 1}
+YUV_DEPTHS = {8: 0, "8": 0, "10_msb": 1, "p010": 1, "10_lsb": 2, "10le": 2}
+
+
+def _yuv_enum(table, v, what):
+    """A name of `table` (or the C value itself) -> the C value."""
+    if isinstance(v, str) or (table is YUV_DEPTHS and v == 8):
+        key = v.lower() if isinstance(v, str) else v
+        if key not in table:
+            raise SlideoError(1, "yuv description: unknown %s %r (one of %s)" % (what, v, sorted(map(str, table))))
+        return table[key]
+    return int(v)
+
+
+def yuv_coefficients(matrix="bt601", range="limited"):
+    """slideo_yuv_coefficients: (CY, CUB, CUG, CVG, CVR, y_offset, SHIFT) of the fixed-point conversion under (matrix, range)."""
+    out = (C.c_int32 * 7)()
+    rc = lib().slideo_yuv_coefficients(_yuv_enum(YUV_MATRICES, matrix, "matrix"), _yuv_enum(YUV_RANGES, range, "range"), out)
+    if rc != OK:
+        raise SlideoError(rc, "slideo_yuv_coefficients(%r, %r)" % (matrix, range))
+    return tuple(int(v) for v in out)
+
+
+def yuv420_layout(fmt, w, h, pitch=None, row_align=None, bytes_per_sample=1):
     """Layout of a `fmt` frame ('nv12', 'nv21', 'i420', 'yv12') of w x h -> (Yuv420Layout, frame bytes).  pitch: bytes per luma
-    row (default w; a planar format's chroma rows take pitch / 2); row_align: the chroma plane starts at pitch * align(h, row_align),
-    as on a decoder surface.  Without either, the tightly packed layout (what slideo_yuv420_layout_packed returns)."""
+    row (default w * bytes_per_sample; a planar format's chroma rows take pitch / 2); row_align: the chroma plane starts at
+    pitch * align(h, row_align), as on a decoder surface.  Without either, the tightly packed layout (what
+    slideo_yuv420_layout_packed / _packed16 returns).  bytes_per_sample=2: 16-bit containers ("YUV colour description")."""
     if fmt not in YUV420_FORMATS:
         raise ValueError("unknown 4:2:0 format %r" % (fmt,))
-    p = int(pitch or w)
+    if bytes_per_sample not in (1, 2):
+        raise ValueError("bytes_per_sample is 1 or 2")
+    p = int(pitch or w * bytes_per_sample)
     ah = -(-h // row_align) * row_align if row_align else h
     luma = p * ah
     L = Yuv420Layout()
     L.y_stride = p
     if fmt in ("nv12", "nv21"):
         L.uv_stride, L.uv_step = p, 2
-        L.u_offset, L.v_offset = (luma, luma + 1) if fmt == "nv12" else (luma + 1, luma)
+        L.u_offset, L.v_offset = (luma, luma + bytes_per_sample) if fmt == "nv12" else (luma + bytes_per_sample, luma)
     else:
         L.uv_stride, L.uv_step = p // 2, 1
         first, second = luma, luma + (p // 2) * (ah // 2)
@@ -74,17 +101,23 @@ def yuv420_layout(fmt, w, h, pitch=None, row_align=None):
     return L, luma * 3 // 2
 
 
-def yuv420_layout_packed(fmt, w, h):
-    """slideo_yuv420_layout_packed: the library's own tightly packed layout of `fmt`."""
+def yuv420_layout_packed(fmt, w, h, bytes_per_sample=1):
+    """slideo_yuv420_layout_packed (bytes_per_sample=2: _packed16): the library's own tightly packed layout of `fmt`."""
     L = Yuv420Layout()
-    rc = lib().slideo_yuv420_layout_packed(YUV420_FORMATS[fmt], int(w), int(h), C.byref(L))
+    name = "slideo_yuv420_layout_packed16" if bytes_per_sample == 2 else "slideo_yuv420_layout_packed"
+    rc = getattr(lib(), name)(YUV420_FORMATS[fmt], int(w), int(h), C.byref(L))
     if rc != OK:
-        raise SlideoError(rc, "slideo_yuv420_layout_packed(%s, %d, %d)" % (fmt, w, h))
+        raise SlideoError(rc, "%s(%s, %d, %d)" % (name, fmt, w, h))
     return L
 
 
 def _yuv_frames(frames, w, h, layout):
-    """frames: uint8 [n, frame_bytes] (or one frame, 1-D) -> (contiguous [n, frame_bytes], layout, frame stride)."""
+    """frames: uint8 [n, frame_bytes] (or one frame, 1-D), or little-endian uint16 samples (16-bit containers), read as their
+    bytes -> (contiguous uint8 [n, frame_bytes], layout, frame stride in bytes).  A format NAME stands for its packed 8-bit layout."""
+    frames = np.asarray(frames)
+    if frames.dtype == np.uint16:
+        frames = np.ascontiguousarray(frames, "<u2")
+        frames = frames.view(np.uint8).reshape(frames.shape[:-1] + (frames.shape[-1] * 2,))
     frames = np.ascontiguousarray(frames, np.uint8)
     frames = frames.reshape(1 if frames.ndim == 1 else frames.shape[0], -1)
     if isinstance(layout, str):
@@ -147,6 +180,8 @@ EXPORTS = [
     "slideo_matcher_set_direct_scope", "slideo_matcher_direct_scope", "slideo_group_set_direct_scope", "slideo_page_small_ssd_valid",
     "slideo_matcher_set_frame_region", "slideo_matcher_frame_region", "slideo_group_set_frame_region", "slideo_frame_region_from_quad",
     "slideo_rectify_bgr8",
+    "slideo_matcher_set_yuv_description", "slideo_matcher_yuv_description", "slideo_group_set_yuv_description", "slideo_yuv_coefficients",
+    "slideo_yuv420_layout_packed16",
 ]
 
 # frame mask scope (include/slideo_amd.h "Frame mask scope")
@@ -245,6 +280,13 @@ def lib():
             L.slideo_group_set_frame_region.argtypes = [vp, i32, i32, vp, i32, i32]
             L.slideo_frame_region_from_quad.argtypes = [vp, i32, i32, vp]
             L.slideo_rectify_bgr8.argtypes = [vp, vp, i32, i32, i32, vp, i64]
+        if hasattr(L, "slideo_matcher_set_yuv_description"):
+            vp, i32 = C.c_void_p, C.c_int32
+            L.slideo_matcher_set_yuv_description.argtypes = [vp, i32, i32, i32]
+            L.slideo_matcher_yuv_description.argtypes = [vp, vp, vp, vp]
+            L.slideo_group_set_yuv_description.argtypes = [vp, i32, i32, i32]
+            L.slideo_yuv_coefficients.argtypes = [i32, i32, vp]
+            L.slideo_yuv420_layout_packed16.argtypes = [i32, i32, i32, vp]
         _lib = L
     return _lib
 
@@ -426,6 +468,23 @@ class _FrameCalls:
         if rc != OK:
             raise SlideoError(rc, "direct_scope")
         return scope.value
+
+    # YUV colour description (include/slideo_amd.h "YUV colour description"): how every *_yuv420 call reads its samples
+    def set_yuv_description(self, matrix="bt601", range="limited", depth=8):
+        """matrix: 'bt601' | 'bt709'; range: 'limited' | 'full'; depth: 8, '10_msb' (P010: 16-bit containers, value in the top
+        10 bits) or '10_lsb' (yuv420p10le) — or the SLIDEO_YUV_* values.  The default (bt601, limited, 8) is cvtColor's reading.
+        Under a 10-bit depth layouts count BYTES of 16-bit containers (yuv420_layout(..., bytes_per_sample=2)).  The matcher must
+        be idle; ends the kept frames and resets the gate state."""
+        self._check(getattr(lib(), self._SETS + "set_yuv_description")(
+            self._h, _yuv_enum(YUV_MATRICES, matrix, "matrix"), _yuv_enum(YUV_RANGES, range, "range"), _yuv_enum(YUV_DEPTHS, depth, "depth")))
+
+    def yuv_description(self):
+        """(matrix, range, depth) as the SLIDEO_YUV_* values (a Group: member 0's)."""
+        v = [C.c_int32() for _ in range(3)]
+        rc = lib().slideo_matcher_yuv_description(self._mask_owner(), C.byref(v[0]), C.byref(v[1]), C.byref(v[2]))
+        if rc != OK:
+            raise SlideoError(rc, "yuv_description")
+        return v[0].value, v[1].value, v[2].value
 
     def _mask_owner(self):
         """The matcher handle the mask's getters read (a group's members agree: member 0)."""

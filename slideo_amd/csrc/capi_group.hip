@@ -362,6 +362,10 @@ int32_t slideo_group_set_direct_scope(slideo_group* g, uint32_t scope) {
     return group_set(g, SET_DIRECT_SCOPE, [&](const FrameSettings& s) { return propose_direct_scope(s, scope); });
 }
 
+int32_t slideo_group_set_yuv_description(slideo_group* g, int32_t matrix, int32_t range, int32_t depth) {
+    return group_set(g, SET_YUV_DESCRIPTION, [&](const FrameSettings& s) { return propose_yuv_description(s, matrix, range, depth); });
+}
+
 // Page sets: every member builds the same set from the same deck (ids are handed out in the same order: they agree)
 int32_t slideo_group_create_page_set(slideo_group* g, int32_t n_pages, const int32_t* pages, int32_t* set_out) {
     if (!g) return SLIDEO_ERR_INVALID_ARG;

@@ -84,49 +84,10 @@ void validate_image(int w, int h, int stride) {
     if (w < 1 || h < 1 || stride < w * 3) fail(SLIDEO_ERR_INVALID_ARG, "bad image geometry w=%d h=%d stride=%d", w, h, stride);
 }
 
-// the rules of include/slideo_amd.h "YUV 4:2:0 frames"; returns the bytes of one frame (its furthest byte + 1).  frame_stride < 0:
-// a single frame, no stride to check
-static int64_t yuv420_validate(int w, int h, const slideo_yuv420_layout* L, int64_t frame_stride) {
-    if (w < 1 || h < 1) fail(SLIDEO_ERR_INVALID_ARG, "bad image geometry w=%d h=%d", w, h);
-    if ((w | h) & 1) fail(SLIDEO_ERR_UNSUPPORTED, "yuv420: width and height must be even (%dx%d), as cvtColor requires", w, h);
-    if (w > MAX_DIM || h > MAX_DIM) fail(SLIDEO_ERR_UNSUPPORTED, "image size %dx%d outside 1..%d", w, h, MAX_DIM);
-    if (L->uv_step != 1 && L->uv_step != 2) fail(SLIDEO_ERR_INVALID_ARG, "yuv420 layout: uv_step %d is neither 1 (planar) nor 2 (interleaved)", L->uv_step);
-    if (L->u_offset < 0 || L->v_offset < 0) fail(SLIDEO_ERR_INVALID_ARG, "yuv420 layout: negative plane offset");
-    if (L->y_stride < w) fail(SLIDEO_ERR_INVALID_ARG, "yuv420 layout: y_stride %d < width %d", L->y_stride, w);
-    const int cw = w / 2, ch = h / 2;
-    if ((int64_t)L->uv_stride < (int64_t)cw * L->uv_step)
-        fail(SLIDEO_ERR_INVALID_ARG, "yuv420 layout: uv_stride %d < %d (width/2 chroma samples of %d bytes' step)", L->uv_stride, cw * L->uv_step, L->uv_step);
-    if (L->uv_step == 2 && std::llabs(L->u_offset - L->v_offset) != 1)
-        fail(SLIDEO_ERR_INVALID_ARG, "yuv420 layout: interleaved chroma needs |v_offset - u_offset| == 1 (got %lld, %lld)",
-             (long long)L->u_offset, (long long)L->v_offset);
-    // planes as byte ranges [lo, hi): Y, then U and V (one range when interleaved)
-    const int64_t y_hi = (int64_t)(h - 1) * L->y_stride + w;
-    const int64_t c_rows = (int64_t)(ch - 1) * L->uv_stride;
-    struct R { int64_t lo, hi; const char* name; };
-    std::vector<R> pl{{0, y_hi, "Y"}};
-    if (L->uv_step == 2) {
-        const int64_t lo = std::min(L->u_offset, L->v_offset);
-        pl.push_back({lo, lo + c_rows + 2 * cw, "UV"});
-    } else {
-        pl.push_back({L->u_offset, L->u_offset + c_rows + cw, "U"});
-        pl.push_back({L->v_offset, L->v_offset + c_rows + cw, "V"});
-    }
-    int64_t span = 0;
-    for (size_t i = 0; i < pl.size(); ++i) {
-        span = std::max(span, pl[i].hi);
-        for (size_t j = 0; j < i; ++j)
-            if (pl[i].lo < pl[j].hi && pl[j].lo < pl[i].hi)
-                fail(SLIDEO_ERR_INVALID_ARG, "yuv420 layout: the %s plane [%lld, %lld) overlaps the %s plane [%lld, %lld)", pl[i].name,
-                     (long long)pl[i].lo, (long long)pl[i].hi, pl[j].name, (long long)pl[j].lo, (long long)pl[j].hi);
-    }
-    if (frame_stride >= 0 && frame_stride < span)
-        fail(SLIDEO_ERR_INVALID_ARG, "yuv420: frame_stride %lld does not cover the frame's furthest byte (%lld)", (long long)frame_stride, (long long)span);
-    return span;
-}
-
 void validate_frames(FrameSrc& src, slideo_matcher* m, int n, const void* out) {
     if (src.yuv) {
-        src.yuv_span = yuv420_validate(src.w, src.h, src.yuv, src.frame_stride);
+        if (m) src.bps = m->fs.yuv.bytes_per_sample();              // (a tap without a matcher argument sets it itself)
+        src.yuv_span = yuv420_validate(src.w, src.h, src.yuv, src.frame_stride, src.bps);
         src.stride = src.w * 3;                                    // the BGR image the units read (d_stage)
     }
     if (m) {
@@ -237,7 +198,7 @@ DevFrames stage_frames(slideo_matcher* m, Slot& S, const FrameSrc& src, int firs
     if (src.yuv) {
         uint8_t* bgr = stage;
         if (pre) { S.d_full.reserve((size_t)fb * n + 16); bgr = S.d_full.as<uint8_t>(); }
-        launch_yuv420_to_bgr(p, fs, *src.yuv, src.w, src.h, n, bgr, S.st);
+        launch_yuv420_to_bgr(m->fs.yuv, p, fs, *src.yuv, src.w, src.h, n, bgr, S.st);
         p = bgr; fs = fb;
     }
     if (!pre) return DevFrames{stage, src.w, src.h, src.stride, fb};
@@ -493,6 +454,7 @@ static Slot& slot_of_ticket(slideo_matcher* m, int64_t ticket, bool gated) {
 void changed_mask_impl(slideo_matcher* m, int n_frames, FrameSrc src, const uint8_t* prev_small, uint8_t* last_small_out, uint8_t* changed_out,
                        float* similarity_out) {
     if (n_frames < 0 || (n_frames > 0 && (!src.p || !changed_out))) fail(SLIDEO_ERR_INVALID_ARG, "null frames/changed");
+    src.bps = m->fs.yuv.bytes_per_sample();
     validate_frames(src);
     resolve_frames(m, src, false);
     if (n_frames == 0) return;
@@ -1193,6 +1155,35 @@ int32_t slideo_yuv420_layout_packed(int32_t format, int32_t w, int32_t h, slideo
         L.v_offset = format == SLIDEO_YUV420_I420 ? luma + chroma : luma;
     }
     *out = L;
+    return SLIDEO_OK;
+}
+
+// the same with 16-bit containers: every stride and offset doubled
+int32_t slideo_yuv420_layout_packed16(int32_t format, int32_t w, int32_t h, slideo_yuv420_layout* out) {
+    slideo_yuv420_layout L{};
+    const int32_t rc = slideo_yuv420_layout_packed(format, w, h, out ? &L : nullptr);
+    if (rc != SLIDEO_OK) return rc;
+    L.y_stride *= 2; L.uv_stride *= 2; L.u_offset *= 2; L.v_offset *= 2;
+    *out = L;
+    return SLIDEO_OK;
+}
+
+// ---- YUV colour description (include/slideo_amd.h "YUV colour description") --------------------------------------------------
+
+int32_t slideo_yuv_coefficients(int32_t matrix, int32_t range, int32_t* out7) {
+    if (!out7) return SLIDEO_ERR_INVALID_ARG;
+    try { (void)propose_yuv_description(FrameSettings{}, matrix, range, SLIDEO_YUV_DEPTH_8); } catch (const slideo::Error&) { return SLIDEO_ERR_INVALID_ARG; }
+    yuv_coefficients(matrix, range, out7);
+    return SLIDEO_OK;
+}
+
+int32_t slideo_matcher_set_yuv_description(slideo_matcher* m, int32_t matrix, int32_t range, int32_t depth) {
+    return matcher_set(m, SET_YUV_DESCRIPTION, [&](const FrameSettings& s) { return propose_yuv_description(s, matrix, range, depth); });
+}
+
+int32_t slideo_matcher_yuv_description(const slideo_matcher* m, int32_t* matrix, int32_t* range, int32_t* depth) {
+    if (!m || !matrix || !range || !depth) return SLIDEO_ERR_INVALID_ARG;
+    *matrix = m->fs.yuv.matrix; *range = m->fs.yuv.range; *depth = m->fs.yuv.depth;
     return SLIDEO_OK;
 }
 

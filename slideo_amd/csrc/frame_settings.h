@@ -1,10 +1,12 @@
 // frame_settings.h — the frame settings of a matcher as ONE record (include/slideo_amd.h "Working size", "Frame region", "Frame mask",
-// "Frame mask scope", "Direct page look-up", "Direct look-up scope"): the record, every setter's proposal with its range checks, the
+// "Frame mask scope", "Direct page look-up", "Direct look-up scope", "YUV colour description"): the record, every setter's proposal with its range checks, the
 // rules between settings, what a change of each ends.  Plain C++, no HIP include (tools/frame_settings_hostcheck.cpp walks it on the
 // host); the device buffers a setting owns are the matcher's (runtime.hpp).  A change takes ONE path: settings_commit (capi_runtime.hip).
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <cstdlib>
 
 #include "error.h"
 #include "geom.h"
@@ -25,6 +27,13 @@ struct FrameMask { bool set = false; int w = 0, h = 0; };
 // sw x sh small image of frames of the mask's size (the matcher's d_gate_w), n_valid valid pixels
 struct GateMap { bool on = false; int sw = 0, sh = 0; int64_t n_valid = 0; };
 
+// How every slideo_yuv420_layout call reads its samples (SLIDEO_YUV_MATRIX_* / _RANGE_* / _DEPTH_*); all 0: the default
+struct YuvDesc {
+    int matrix = SLIDEO_YUV_MATRIX_BT601, range = SLIDEO_YUV_RANGE_LIMITED, depth = SLIDEO_YUV_DEPTH_8;
+    bool is_default() const { return matrix == SLIDEO_YUV_MATRIX_BT601 && range == SLIDEO_YUV_RANGE_LIMITED && depth == SLIDEO_YUV_DEPTH_8; }
+    int bytes_per_sample() const { return depth == SLIDEO_YUV_DEPTH_8 ? 1 : 2; }
+};
+
 struct FrameSettings {
     int work_w = 0, work_h = 0;                       // frames beyond it are reduced in front of the pipeline; 0, 0 = none
     FrameRegion region;                               // frames of region.src_w x src_h stand for their rectified image
@@ -34,17 +43,19 @@ struct FrameSettings {
     uint64_t gate_map_gen = 1;                        // what is derived from the map (the look-up's masked page norms) is cached under it
     float direct_t = 0.f;                             // the direct similarity (0: off)
     uint32_t direct_scope = SLIDEO_DIRECT_WHOLE;      // VALID = the look-up over the gate's valid pixels
+    YuvDesc yuv;                                      // 4:2:0 frames stand for the BGR image under it (BGR calls never look at it)
     bool gate_scope() const { return mask.set && (mask_scope & SLIDEO_MASK_GATE); }      // the gate compares under the mask
 };
 
-enum Setting { SET_WORKING_SIZE, SET_FRAME_REGION, SET_FRAME_MASK, SET_FRAME_MASK_SCOPE, SET_DIRECT_SIMILARITY, SET_DIRECT_SCOPE, N_SETTINGS };
+enum Setting { SET_WORKING_SIZE, SET_FRAME_REGION, SET_FRAME_MASK, SET_FRAME_MASK_SCOPE, SET_DIRECT_SIMILARITY, SET_DIRECT_SCOPE, SET_YUV_DESCRIPTION,
+               N_SETTINGS };
 
 // What a change of each setting ends: the frames a mask call kept (made under the earlier setting), the gate state (so was its small
 // image; under a mask change it stays: it is a whole frame's), the map's generation.  Applied by settings_commit and, the group's
 // half, by group_set: nowhere else.
 struct SettingEnds { bool kept, gate, map_gen; };
 constexpr SettingEnds SETTING_ENDS[N_SETTINGS] = {{true, true, true}, {true, true, false}, {true, false, true}, {true, false, true},
-                                                  {false, false, false}, {false, false, false}};
+                                                  {false, false, false}, {false, false, false}, {true, true, false}};
 
 // ---- a setter's proposal (the matcher's and the group's): `s` in force with its arguments applied, their range checked (INVALID_ARG)
 inline FrameSettings propose_working_size(FrameSettings s, int max_w, int max_h) {
@@ -98,6 +109,98 @@ inline FrameSettings propose_direct_scope(FrameSettings s, uint32_t scope) {
         fail(SLIDEO_ERR_INVALID_ARG, "direct scope %u: SLIDEO_DIRECT_WHOLE (0) or SLIDEO_DIRECT_VALID (1)", scope);
     s.direct_scope = scope;
     return s;
+}
+
+inline FrameSettings propose_yuv_description(FrameSettings s, int matrix, int range, int depth) {
+    if (matrix != SLIDEO_YUV_MATRIX_BT601 && matrix != SLIDEO_YUV_MATRIX_BT709)
+        fail(SLIDEO_ERR_INVALID_ARG, "yuv description: matrix %d is neither SLIDEO_YUV_MATRIX_BT601 (0) nor SLIDEO_YUV_MATRIX_BT709 (1)", matrix);
+    if (range != SLIDEO_YUV_RANGE_LIMITED && range != SLIDEO_YUV_RANGE_FULL)
+        fail(SLIDEO_ERR_INVALID_ARG, "yuv description: range %d is neither SLIDEO_YUV_RANGE_LIMITED (0) nor SLIDEO_YUV_RANGE_FULL (1)", range);
+    if (depth != SLIDEO_YUV_DEPTH_8 && depth != SLIDEO_YUV_DEPTH_10_MSB && depth != SLIDEO_YUV_DEPTH_10_LSB)
+        fail(SLIDEO_ERR_INVALID_ARG, "yuv description: depth %d is none of SLIDEO_YUV_DEPTH_8 (0), _10_MSB (1), _10_LSB (2)", depth);
+    s.yuv = YuvDesc{matrix, range, depth};
+    return s;
+}
+
+// The seven integers of the fixed-point conversion under (matrix, range) — CY, CUB, CUG, CVG, CVR, y_offset, SHIFT —, arguments
+// checked by the caller.  (BT601, LIMITED): cvtColor's literals.  Every other pair by the rule of include/slideo_amd.h, in float64.
+inline void yuv_coefficients(int matrix, int range, int32_t* out7) {
+    out7[6] = 20;
+    if (matrix == SLIDEO_YUV_MATRIX_BT601 && range == SLIDEO_YUV_RANGE_LIMITED) {
+        out7[0] = 1220542; out7[1] = 2116026; out7[2] = -409993; out7[3] = -852492; out7[4] = 1673527; out7[5] = 16;
+        return;
+    }
+    const bool bt709 = matrix == SLIDEO_YUV_MATRIX_BT709, full = range == SLIDEO_YUV_RANGE_FULL;
+    const double Kr = bt709 ? 0.2126 : 0.299, Kb = bt709 ? 0.0722 : 0.114, Kg = 1.0 - Kr - Kb;
+    const double sy = full ? 1.0 : 255.0 / 219.0, sc = full ? 1.0 : 255.0 / 224.0, one = 1048576.0;
+    out7[0] = (int32_t)std::rint(sy * one);
+    out7[1] = (int32_t)std::rint(sc * 2.0 * (1.0 - Kb) * one);
+    out7[2] = -(int32_t)std::rint(sc * 2.0 * (1.0 - Kb) * Kb / Kg * one);
+    out7[3] = -(int32_t)std::rint(sc * 2.0 * (1.0 - Kr) * Kr / Kg * one);
+    out7[4] = (int32_t)std::rint(sc * 2.0 * (1.0 - Kr) * one);
+    out7[5] = full ? 0 : 16;
+}
+
+// The layout rules of include/slideo_amd.h "YUV 4:2:0 frames" for samples of `bps` bytes (1; 2: the 16-bit containers of "YUV
+// colour description", whose rules count two bytes per sample); returns the bytes of one frame (its furthest byte + 1).
+// frame_stride < 0: a single frame, no stride to check
+inline int64_t yuv420_validate(int w, int h, const slideo_yuv420_layout* L, int64_t frame_stride, int bps) {
+    if (w < 1 || h < 1) fail(SLIDEO_ERR_INVALID_ARG, "bad image geometry w=%d h=%d", w, h);
+    if ((w | h) & 1) fail(SLIDEO_ERR_UNSUPPORTED, "yuv420: width and height must be even (%dx%d), as cvtColor requires", w, h);
+    if (w > MAX_DIM || h > MAX_DIM) fail(SLIDEO_ERR_UNSUPPORTED, "image size %dx%d outside 1..%d", w, h, MAX_DIM);
+    if (L->uv_step != 1 && L->uv_step != 2) fail(SLIDEO_ERR_INVALID_ARG, "yuv420 layout: uv_step %d is neither 1 (planar) nor 2 (interleaved)", L->uv_step);
+    if (L->u_offset < 0 || L->v_offset < 0) fail(SLIDEO_ERR_INVALID_ARG, "yuv420 layout: negative plane offset");
+    const int cw = w / 2, ch = h / 2;
+    if (bps == 1) {
+        if (L->y_stride < w) fail(SLIDEO_ERR_INVALID_ARG, "yuv420 layout: y_stride %d < width %d", L->y_stride, w);
+        if ((int64_t)L->uv_stride < (int64_t)cw * L->uv_step)
+            fail(SLIDEO_ERR_INVALID_ARG, "yuv420 layout: uv_stride %d < %d (width/2 chroma samples of %d bytes' step)", L->uv_stride, cw * L->uv_step, L->uv_step);
+        if (L->uv_step == 2 && std::llabs(L->u_offset - L->v_offset) != 1)
+            fail(SLIDEO_ERR_INVALID_ARG, "yuv420 layout: interleaved chroma needs |v_offset - u_offset| == 1 (got %lld, %lld)",
+                 (long long)L->u_offset, (long long)L->v_offset);
+    } else {
+        if (L->y_stride < bps * w)
+            fail(SLIDEO_ERR_INVALID_ARG, "yuv420 layout: y_stride %d < 2 * width %d (16-bit containers: strides are bytes)", L->y_stride, w);
+        if ((int64_t)L->uv_stride < (int64_t)bps * cw * L->uv_step)
+            fail(SLIDEO_ERR_INVALID_ARG, "yuv420 layout: uv_stride %d < %d (width/2 chroma samples of 2 * %d bytes' step, 16-bit containers)",
+                 L->uv_stride, bps * cw * L->uv_step, L->uv_step);
+        if ((L->y_stride | L->uv_stride) & 1)
+            fail(SLIDEO_ERR_INVALID_ARG, "yuv420 layout: 16-bit containers need even strides (y_stride %d, uv_stride %d)", L->y_stride, L->uv_stride);
+        if ((L->u_offset | L->v_offset) & 1)
+            fail(SLIDEO_ERR_INVALID_ARG, "yuv420 layout: 16-bit containers need even offsets (u_offset %lld, v_offset %lld)",
+                 (long long)L->u_offset, (long long)L->v_offset);
+        if (frame_stride >= 0 && (frame_stride & 1))
+            fail(SLIDEO_ERR_INVALID_ARG, "yuv420: 16-bit containers need an even frame_stride (%lld)", (long long)frame_stride);
+        if (L->uv_step == 2 && std::llabs(L->u_offset - L->v_offset) != 2)
+            fail(SLIDEO_ERR_INVALID_ARG, "yuv420 layout: interleaved chroma of 16-bit containers needs |v_offset - u_offset| == 2 (got %lld, %lld)",
+                 (long long)L->u_offset, (long long)L->v_offset);
+    }
+    // planes as byte ranges [lo, hi): Y, then U and V (one range when interleaved)
+    const int64_t y_hi = (int64_t)(h - 1) * L->y_stride + (int64_t)w * bps;
+    const int64_t c_rows = (int64_t)(ch - 1) * L->uv_stride;
+    struct R { int64_t lo, hi; const char* name; };
+    R pl[3] = {{0, y_hi, "Y"}, {0, 0, ""}, {0, 0, ""}};
+    int npl;
+    if (L->uv_step == 2) {
+        const int64_t lo = std::min(L->u_offset, L->v_offset);
+        pl[1] = R{lo, lo + c_rows + (int64_t)2 * cw * bps, "UV"};
+        npl = 2;
+    } else {
+        pl[1] = R{L->u_offset, L->u_offset + c_rows + (int64_t)cw * bps, "U"};
+        pl[2] = R{L->v_offset, L->v_offset + c_rows + (int64_t)cw * bps, "V"};
+        npl = 3;
+    }
+    int64_t span = 0;
+    for (int i = 0; i < npl; ++i) {
+        span = std::max(span, pl[i].hi);
+        for (int j = 0; j < i; ++j)
+            if (pl[i].lo < pl[j].hi && pl[j].lo < pl[i].hi)
+                fail(SLIDEO_ERR_INVALID_ARG, "yuv420 layout: the %s plane [%lld, %lld) overlaps the %s plane [%lld, %lld)", pl[i].name,
+                     (long long)pl[i].lo, (long long)pl[i].hi, pl[j].name, (long long)pl[j].lo, (long long)pl[j].hi);
+    }
+    if (frame_stride >= 0 && frame_stride < span)
+        fail(SLIDEO_ERR_INVALID_ARG, "yuv420: frame_stride %lld does not cover the frame's furthest byte (%lld)", (long long)frame_stride, (long long)span);
+    return span;
 }
 
 // ---- the rules between settings (SLIDEO_ERR_UNSUPPORTED), each once --------------------------------------------------------------

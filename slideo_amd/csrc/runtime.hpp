@@ -94,20 +94,23 @@ struct FrameSrc {
     int stride = 0;                             // BGR rows; a YUV source's BGR image (d_stage) has 3w, set by validate_frames
     int64_t frame_stride = 0;                   // (a single frame: -1 = no stride to check)
     const slideo_yuv420_layout* yuv = nullptr;
+    int bps = 1;                                // (derived) bytes per 4:2:0 sample: the matcher's YUV description (validate_frames)
     int64_t yuv_span = 0;                       // (derived) bytes of one YUV frame: its furthest byte + 1
     bool pinned = false;                        // (derived) page-locked host memory: its copies are truly asynchronous DMA
     // the frames are unit images already — the frames a mask call kept (slideo_match_kept_frames): no region applies to them
     bool analysed = false;
     FramePlan plan;                             // (derived) resolve_frames
 
-    // per frame, the staging in front of the unit's BGR image: 1.5 B per pixel for 4:2:0 frames (BGR calls keep their unit sizes);
+    // per frame, the staging in front of the unit's BGR image: 1.5 B per pixel for 4:2:0 frames, 3 B in 16-bit containers (BGR calls
+    // keep their unit sizes);
     // a reducing or rectifying call: the uploaded source frame (host sources) and the source-sized BGR image of a 4:2:0 frame;
     // gated (a gated call, include/slideo_amd.h "Changed-frame gate"): + the gate staging — the BGR unit image of every frame that
     // is not the caller's own device memory — and the frame's small image (gate_small: at most 3 * small_area bytes) and gate record
     size_t staging_bytes(size_t gate_small = 0) const {
         const size_t px = (size_t)w * h;
         const bool pre = plan.prep != PREP_NONE;
-        size_t b = !pre ? (yuv ? px * 3 / 2 : 0) : (on_device ? 0 : (yuv ? px * 3 / 2 : (size_t)h * stride)) + (yuv ? px * 3 : 0);
+        const size_t yb = px * 3 / 2 * (size_t)bps;
+        size_t b = !pre ? (yuv ? yb : 0) : (on_device ? 0 : (yuv ? yb : (size_t)h * stride)) + (yuv ? px * 3 : 0);
         if (gate_small) b += (on_device && !yuv && !pre ? 0 : (size_t)plan.uw * plan.uh * 3) + gate_small + 32;
         return b;
     }
@@ -465,8 +468,9 @@ void launch_reduce(slideo_matcher* m, const uint8_t* src, int64_t src_fs, int st
 void launch_rectify(const FrameRegion& R, const uint8_t* src, int64_t src_fs, int stride, int n, uint8_t* dst, hipStream_t st);
 // the rectify_kernel instance of a map: R.kind, R.tx, R.ty from R.M
 void frame_region_classify(FrameRegion& R);
-// n decoded YUV 4:2:0 frames (a layout yuv420_validate accepted, frame stride src_fs) -> BGR8 at dst, stride 3w, frame stride 3wh
-void launch_yuv420_to_bgr(const uint8_t* src, int64_t src_fs, const slideo_yuv420_layout& L, int w, int h, int n, uint8_t* dst, hipStream_t st);
+// n decoded YUV 4:2:0 frames (a layout yuv420_validate accepted under `desc`, frame stride src_fs) -> BGR8 at dst, stride 3w, frame
+// stride 3wh.  The default description: yuv420_to_bgr_kernel; any other: yuv420_to_bgr_desc_kernel
+void launch_yuv420_to_bgr(const YuvDesc& desc, const uint8_t* src, int64_t src_fs, const slideo_yuv420_layout& L, int w, int h, int n, uint8_t* dst, hipStream_t st);
 
 // ---- stage_knn.hip --------------------------------------------------------------------------------
 // FlannMatcher::new (mo/flann.rs:65-71) for the Hamming index: uploads the M packed rows, collapses equal rows, builds the

@@ -55,8 +55,42 @@ void orb_launch_gray(const slideo_matcher* m, const uint8_t* frames_dev, int64_t
     check_launch("gray_kernel");
 }
 
+// yuv420_to_bgr_desc_kernel's arguments for a validated layout: which of its wide loads and stores the addresses allow
+static YuvDescArgs yuv_desc_args(const YuvDesc& desc, const uint8_t* src, int64_t src_fs, const slideo_yuv420_layout& L, int w, int h, uint8_t* dst) {
+    YuvDescArgs a{};
+    a.src = src; a.src_frame_stride = src_fs;
+    a.interleaved = L.uv_step == 2;
+    a.v_first = a.interleaved && L.v_offset < L.u_offset;
+    a.c_ofs = a.interleaved ? std::min(L.u_offset, L.v_offset) : L.u_offset;
+    a.v_ofs = L.v_offset;
+    a.y_stride = L.y_stride; a.uv_stride = L.uv_stride;
+    a.dst = dst; a.w = w; a.h = h;
+    // 8-bit samples: dword luma, dword (interleaved) or u16 (planar) chroma; 16-bit containers: 8-byte luma, dword chroma
+    const bool wide = desc.depth != SLIDEO_YUV_DEPTH_8;
+    const uintptr_t ay = wide ? 8 : 4, ac = wide || a.interleaved ? 4 : 2, base = (uintptr_t)src;
+    auto aligned = [&](int64_t ofs, int stride, uintptr_t al) { return (base + (uintptr_t)ofs) % al == 0 && (uintptr_t)src_fs % al == 0 && (uintptr_t)stride % al == 0; };
+    a.wide_y = aligned(0, L.y_stride, ay);
+    a.wide_c = aligned(a.c_ofs, L.uv_stride, ac) && (a.interleaved || aligned(a.v_ofs, L.uv_stride, ac));
+    a.out4 = (uintptr_t)dst % 4 == 0 && w % 4 == 0;
+    return a;
+}
+
 // n decoded 4:2:0 frames (validated layout, frame stride src_fs) -> BGR8 at dst (stride 3w, frame stride 3wh)
-void launch_yuv420_to_bgr(const uint8_t* src, int64_t src_fs, const slideo_yuv420_layout& L, int w, int h, int n, uint8_t* dst, hipStream_t st) {
+void launch_yuv420_to_bgr(const YuvDesc& desc, const uint8_t* src, int64_t src_fs, const slideo_yuv420_layout& L, int w, int h, int n, uint8_t* dst,
+                          hipStream_t st) {
+    dim3 grid(cdiv(cdiv(w, 4), YUV_TX), cdiv(h / 2, YUV_TY), n);
+    if (!desc.is_default()) {
+        const YuvDescArgs d = yuv_desc_args(desc, src, src_fs, L, w, h, dst);
+        int32_t c[7];
+        yuv_coefficients(desc.matrix, desc.range, c);
+        const YuvCoef k{c[0], c[1], c[2], c[3], c[4], c[5]};
+        const dim3 block(YUV_TX, YUV_TY);
+        if (desc.depth == SLIDEO_YUV_DEPTH_8) yuv420_to_bgr_desc_kernel<YUV_D8><<<grid, block, 0, st>>>(d, k);
+        else if (desc.depth == SLIDEO_YUV_DEPTH_10_MSB) yuv420_to_bgr_desc_kernel<YUV_D10_MSB><<<grid, block, 0, st>>>(d, k);
+        else yuv420_to_bgr_desc_kernel<YUV_D10_LSB><<<grid, block, 0, st>>>(d, k);
+        check_launch("yuv420_to_bgr_desc_kernel");
+        return;
+    }
     Yuv420Args a{};
     a.src = src; a.src_frame_stride = src_fs;
     a.interleaved = L.uv_step == 2;
@@ -71,7 +105,6 @@ void launch_yuv420_to_bgr(const uint8_t* src, int64_t src_fs, const slideo_yuv42
                                       : (L.u_offset % 2 == 0 && L.v_offset % 2 == 0 && L.uv_stride % 2 == 0);
     const bool out4 = (uintptr_t)dst % 4 == 0 && w % 4 == 0;
     a.fast = luma4 && chroma && out4;
-    dim3 grid(cdiv(cdiv(w, 4), YUV_TX), cdiv(h / 2, YUV_TY), n);
     yuv420_to_bgr_kernel<<<grid, dim3(YUV_TX, YUV_TY), 0, st>>>(a);
     check_launch("yuv420_to_bgr_kernel");
 }

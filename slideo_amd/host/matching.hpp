@@ -361,6 +361,14 @@ public:
     // SLIDEO_DIRECT_WHOLE (default: whole small images, refused beside SLIDEO_MASK_GATE) or SLIDEO_DIRECT_VALID (the valid pixels
     // of the gate's validity map: a full-screen slide under a speaker thumbnail).  Applied before the direct similarity
     HipImageVideoMatcher& with_direct_scope(uint32_t scope) { direct_scope_ = scope; return *this; }
+    // How YUV 4:2:0 frames are read (slideo_group_set_yuv_description, include/slideo_amd.h "YUV colour description"):
+    // SLIDEO_YUV_MATRIX_* / _RANGE_* / _DEPTH_*; BT.709 for HD recordings, full range for many screen recorders, a 10-bit depth for
+    // P010 / yuv420p10le frames (layouts then count bytes of 16-bit containers).  The reference reads every stream as BT.601
+    // limited range.  Default: BT601, LIMITED, 8-bit
+    HipImageVideoMatcher& with_yuv_description(int32_t matrix, int32_t range, int32_t depth = SLIDEO_YUV_DEPTH_8) {
+        yuv_matrix_ = matrix; yuv_range_ = range; yuv_depth_ = depth;
+        return *this;
+    }
     // false: tasks run the stop-and-go pair slideo_group_changed_mask_bgr8 + slideo_group_match_kept_frames in place of the group's
     // gated call (the same timeline; for comparisons).  Default: gated
     HipImageVideoMatcher& with_changed_gate(bool on) { gated_ = on; return *this; }
@@ -385,6 +393,8 @@ public:
             h->check(slideo_group_set_frame_region(h->g, reg_sw_, reg_sh_, reg_M_, reg_ow_, reg_oh_));
             h->reg_w = reg_ow_; h->reg_h = reg_oh_;
         }
+        if (yuv_matrix_ != SLIDEO_YUV_MATRIX_BT601 || yuv_range_ != SLIDEO_YUV_RANGE_LIMITED || yuv_depth_ != SLIDEO_YUV_DEPTH_8)
+            h->check(slideo_group_set_yuv_description(h->g, yuv_matrix_, yuv_range_, yuv_depth_));
         if (mask_scope_ != SLIDEO_MASK_DETECT) h->check(slideo_group_set_frame_mask_scope(h->g, mask_scope_));
         if (!mask_.empty()) h->check(slideo_group_set_frame_mask(h->g, mask_.data(), mask_w_, mask_h_, mask_w_));
         if (direct_scope_ != SLIDEO_DIRECT_WHOLE) h->check(slideo_group_set_direct_scope(h->g, direct_scope_));
@@ -411,6 +421,7 @@ private:
     double reg_M_[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
     std::vector<uint8_t> mask_;
     int32_t mask_w_ = 0, mask_h_ = 0;
+    int32_t yuv_matrix_ = SLIDEO_YUV_MATRIX_BT601, yuv_range_ = SLIDEO_YUV_RANGE_LIMITED, yuv_depth_ = SLIDEO_YUV_DEPTH_8;
     uint32_t mask_scope_ = SLIDEO_MASK_DETECT, direct_scope_ = SLIDEO_DIRECT_WHOLE;
     slideo_config cfg_;
     ImageLoader loader_;

@@ -297,7 +297,7 @@ class HipImageVideoMatcher:
     """Drop-in for OpenCVImageVideoMatcher (lib.rs:34-73) behind matching::ImageVideoMatcher."""
 
     def __init__(self, cfg=None, device=None, sift=None, devices=None, working_size=None, frame_mask=None, frame_mask_scope=None,
-                 direct_similarity=None, direct_scope=None, frame_region=None):
+                 direct_similarity=None, direct_scope=None, frame_region=None, yuv_description=None):
         """devices: HIP ordinals, one matcher each behind one slideo_group (the reference fans out over the whole machine, the
         global rayon pool of lib.rs:45,174); None = every gfx950 device of the node; `device` = d is short for devices = [d].
         sift = (slideo_sift_config, ratio): the north-star's SIFT + L2 front end instead of the reference's ORB + Hamming
@@ -321,7 +321,11 @@ class HipImageVideoMatcher:
         the out_w x out_h image rectified from a fixed quadrilateral of them — a filmed projection screen, a slide in a
         sub-window; M_or_quad: the 3x3 map from the rectified image into the frame, or the slide's four corners in the frame
         (top-left, top-right, bottom-right, bottom-left); a frame mask is then of the output size, and the output must fit a
-        working size (the reference analyses the whole frame); None = no region."""
+        working size (the reference analyses the whole frame); None = no region.
+        yuv_description = (matrix, range) or (matrix, range, depth), as Matcher.set_yuv_description takes them
+        (slideo_group_set_yuv_description): how the YUV 4:2:0 videos are read — ("bt709", "limited") for HD recordings,
+        ("bt709", "full") for many screen recorders; the reference reads every stream as BT.601 limited range; RawVideoYuv420
+        files hold 8-bit samples, so depth stays 8 for them; None = BT.601 limited, 8-bit."""
         self._cfg, self._sift = cfg, sift
         self._working_size = working_size
         self._frame_mask = frame_mask
@@ -329,6 +333,7 @@ class HipImageVideoMatcher:
         self._direct_similarity = direct_similarity
         self._direct_scope = direct_scope
         self._frame_region = frame_region
+        self._yuv_description = tuple(yuv_description) if yuv_description is not None else None
         self._devices = [device] if device is not None else devices
 
     def create_video_matcher(self, images, progress_reporter: ProgressReporter) -> HipVideoMatcher:
@@ -341,6 +346,8 @@ class HipImageVideoMatcher:
             m.set_working_size(*self._working_size)
         if self._frame_region is not None:
             m.set_frame_region(*self._frame_region)
+        if self._yuv_description is not None:
+            m.set_yuv_description(*self._yuv_description)
         if self._frame_mask_scope is not None:
             m.set_frame_mask_scope(self._frame_mask_scope)
         if self._frame_mask is not None:
