@@ -527,6 +527,73 @@ extern "C" {
         out: *mut u8,
         out_capacity: i64,
     ) -> i32;
+    // frame activity map (include/slideo_amd.h "Frame activity map"): per-pixel counts of moved pairs, and the mask read out of them
+    pub fn slideo_matcher_activity_begin(m: *mut slideo_matcher, delta: i32) -> i32;
+    pub fn slideo_matcher_activity_end(m: *mut slideo_matcher) -> i32;
+    pub fn slideo_matcher_observe_frames_bgr8(
+        m: *mut slideo_matcher,
+        n_frames: i32,
+        frames: *const u8,
+        width: i32,
+        height: i32,
+        stride_bytes: i32,
+        frame_stride_bytes: i64,
+    ) -> i32;
+    pub fn slideo_matcher_observe_frames_yuv420(
+        m: *mut slideo_matcher,
+        n_frames: i32,
+        frames: *const u8,
+        width: i32,
+        height: i32,
+        layout: *const slideo_yuv420_layout,
+        frame_stride_bytes: i64,
+    ) -> i32;
+    pub fn slideo_matcher_observe_frames_bgr8_dev(
+        m: *mut slideo_matcher,
+        n_frames: i32,
+        frames_dev: *const u8,
+        width: i32,
+        height: i32,
+        stride_bytes: i32,
+        frame_stride_bytes: i64,
+        hip_stream: *mut c_void,
+    ) -> i32;
+    pub fn slideo_matcher_observe_frames_yuv420_dev(
+        m: *mut slideo_matcher,
+        n_frames: i32,
+        frames_dev: *const u8,
+        width: i32,
+        height: i32,
+        layout: *const slideo_yuv420_layout,
+        frame_stride_bytes: i64,
+        hip_stream: *mut c_void,
+    ) -> i32;
+    pub fn slideo_matcher_activity_info(
+        m: *mut slideo_matcher,
+        aw: *mut i32,
+        ah: *mut i32,
+        pairs: *mut i32,
+        delta: *mut i32,
+    ) -> i32;
+    pub fn slideo_matcher_activity_counts(
+        m: *mut slideo_matcher,
+        out: *mut u32,
+        capacity_elems: i64,
+        aw: *mut i32,
+        ah: *mut i32,
+        pairs: *mut i32,
+    ) -> i32;
+    pub fn slideo_matcher_activity_mask(
+        m: *mut slideo_matcher,
+        max_share_ppm: i32,
+        grow: i32,
+        out: *mut u8,
+        capacity: i64,
+        aw: *mut i32,
+        ah: *mut i32,
+        n_active: *mut i64,
+        n_masked: *mut i64,
+    ) -> i32;
 }
 
 /// The struct layouts above are only valid for one ABI version of the library.

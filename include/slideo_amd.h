@@ -1101,6 +1101,68 @@ int32_t     slideo_group_set_direct_scope(slideo_group* g, uint32_t scope);
  * small size.  The kernels and the masked page norms of the gated path (it builds the norms if no gated call has). */
 int32_t     slideo_page_small_ssd_valid(slideo_matcher* m, const uint8_t* small, int32_t n, int32_t sw, int32_t sh, uint64_t* ssd_out);
 
+/* ---- Frame activity map (extension: the measurement a frame mask can be made from) --------------------------------------------------
+ * The frame mask, its GATE scope and the direct look-up's VALID scope need a mask, and the caller had to know it beforehand.  An
+ * inset (a speaker, a clock) gives itself away: it changes on almost every sampled frame, a slide pixel only at slide transitions.
+ * A matcher carries an ACTIVITY ACCUMULATOR, off by default.  Its state is "none", or: an analysed size (aw, ah), not fixed until
+ * the first frame has been observed; a delta; the last observed image (device); `pairs`; count[ah][aw] as u32 (device).
+ *   observed image   of a frame: the BGR image the pipeline would analyse — the frame after the 4:2:0 conversion under the matcher's
+ *                    YUV description, then after the frame region's rectify or, failing that, the working-size reduce: exactly the
+ *                    images slideo_yuv420_to_bgr8, slideo_rectify_bgr8 and slideo_reduce_bgr8 return.  The frame mask, its scope, the
+ *                    direct settings, the page set and the deck are not looked at.
+ *   moved            for consecutive observed images a, b, pixel (x, y) moved iff |a.B-b.B| + |a.G-b.G| + |a.R-b.R| > delta, in
+ *                    integers; delta in 0..765.
+ *   count, pairs     over all frames observed since activity_begin, in submission order across calls: count[y][x] = the number of
+ *                    consecutive pairs in which (x, y) moved, pairs = the number of consecutive pairs.  The first frame after begin
+ *                    forms no pair; the last frame of a call pairs with the first frame of the next call.
+ *   active           count[y][x] * 1000000 > max_share_ppm * pairs, in unsigned 64-bit integers (strict: equality is not active).
+ *   mask             mask[y][x] = 0 iff some active pixel (x', y') of the image has |x'-x| <= grow && |y'-y| <= grow, else 255; grow in
+ *                    0..64.  n_active = the active pixels, n_masked = the zeros of the mask.
+ * It is an estimator with an exact definition, not a detector with a claim: no default delta, share or grow is chosen here
+ * (docs/EXTENSIONS.md "Frame activity map" says on what content it was tried).  The mask is never installed: the caller looks at
+ * n_masked and hands the bytes to slideo_matcher_set_frame_mask.  There is no group form: the pre-pass runs on one member,
+ * slideo_group_member(g, 0), and the result goes to slideo_group_set_frame_mask.
+ * Observing touches nothing else: the frames a mask call kept stay valid, the gate state and every setting stay, and a setter called
+ * between observes does not reset the accumulator (an analysed size that no longer fits is SLIDEO_ERR_STATE at the next observe).
+ * Where it runs (csrc/stage_activity.hip, csrc/activity.hip.h): the frames are staged as every frame call stages them (upload,
+ * 4:2:0 conversion, rectify or reduce; plain device BGR is read in the caller's memory), in blocks of at most 256 MiB of staging and 4096 frames,
+ * into a buffer of the accumulator's own; activity_kernel once per block on slot 0's stream — a thread owns 4 pixels of a row, walks
+ * the block's frames with the previous pixels and its counts in registers, one v_sad_u8 per pixel and frame, and ends with one
+ * read-modify-write of its counts and one store into the carried image: no atomic, no LDS —; one synchronise at the end.  The mask
+ * is made at read-out by activity_rows_kernel and activity_cols_kernel.
+ * Every call returns SLIDEO_ERR_INVALID_ARG for a null handle or a null required pointer. */
+/* Idle matcher (SLIDEO_ERR_STATE otherwise).  delta outside 0..765 is SLIDEO_ERR_INVALID_ARG and the state before stays.  Afterwards
+ * the accumulator is empty: no size, pairs 0.  May be called before any page is added and before finalize. */
+int32_t     slideo_matcher_activity_begin(slideo_matcher* m, int32_t delta);
+/* Idle matcher.  The state "none"; the accumulator's device buffers are released.  Fine when the state is "none" already. */
+int32_t     slideo_matcher_activity_end(slideo_matcher* m);
+/* Synchronous; idle matcher; neither pages nor finalize are needed.  The argument rules of a frame source apply (the layout rules
+ * under the YUV description, image geometry, frame stride, the frame region's source-size rule).  SLIDEO_ERR_STATE without a begin,
+ * when the analysed size differs from the accumulator's (the message names both), and when pairs would pass INT32_MAX.  n_frames == 0
+ * is a no-op.  Sizes are refused as a frame call refuses them (SLIDEO_ERR_UNSUPPORTED): an analysed image, or the source of a frame the
+ * working size reduces, wider or higher than 4096.  An argument, size or state error leaves the counts, pairs and the last image as
+ * they were.  A device (HIP) error in the middle of a call may have counted some of its blocks: it ends the accumulator (the state
+ * "none", SLIDEO_ERR_STATE until the next begin).  hip_stream: the stream the device frames were produced on (may be NULL). */
+int32_t     slideo_matcher_observe_frames_bgr8(slideo_matcher* m, int32_t n_frames, const uint8_t* frames, int32_t width, int32_t height,
+                                               int32_t stride_bytes, int64_t frame_stride_bytes);
+int32_t     slideo_matcher_observe_frames_yuv420(slideo_matcher* m, int32_t n_frames, const uint8_t* frames, int32_t width, int32_t height,
+                                                 const slideo_yuv420_layout* layout, int64_t frame_stride_bytes);
+int32_t     slideo_matcher_observe_frames_bgr8_dev(slideo_matcher* m, int32_t n_frames, const uint8_t* frames_dev, int32_t width, int32_t height,
+                                                   int32_t stride_bytes, int64_t frame_stride_bytes, void* hip_stream);
+int32_t     slideo_matcher_observe_frames_yuv420_dev(slideo_matcher* m, int32_t n_frames, const uint8_t* frames_dev, int32_t width,
+                                                     int32_t height, const slideo_yuv420_layout* layout, int64_t frame_stride_bytes,
+                                                     void* hip_stream);
+/* The accumulator's analysed size (*aw == 0 before the first frame), pairs and delta.  SLIDEO_ERR_STATE in the state "none". */
+int32_t     slideo_matcher_activity_info(slideo_matcher* m, int32_t* aw, int32_t* ah, int32_t* pairs, int32_t* delta);
+/* Idle matcher.  The counts, ah rows of aw elements (the tap the tests hold the kernel to).  SLIDEO_ERR_STATE without an observed
+ * frame; SLIDEO_ERR_CAPACITY (with *aw, *ah, *pairs set) when aw * ah > capacity_elems; out == NULL asks for the sizes only. */
+int32_t     slideo_matcher_activity_counts(slideo_matcher* m, uint32_t* out, int64_t capacity_elems, int32_t* aw, int32_t* ah, int32_t* pairs);
+/* Idle matcher.  The mask of the definition, tight (aw bytes per row), with n_active and n_masked.  SLIDEO_ERR_STATE while pairs == 0;
+ * SLIDEO_ERR_INVALID_ARG for max_share_ppm outside 0..1000000 or grow outside 0..64; SLIDEO_ERR_CAPACITY (with *aw, *ah set) when
+ * aw * ah > capacity. */
+int32_t     slideo_matcher_activity_mask(slideo_matcher* m, int32_t max_share_ppm, int32_t grow, uint8_t* out, int64_t capacity, int32_t* aw,
+                                         int32_t* ah, int64_t* n_active, int64_t* n_masked);
+
 #ifdef __cplusplus
 }
 #endif

@@ -182,6 +182,9 @@ EXPORTS = [
     "slideo_rectify_bgr8",
     "slideo_matcher_set_yuv_description", "slideo_matcher_yuv_description", "slideo_group_set_yuv_description", "slideo_yuv_coefficients",
     "slideo_yuv420_layout_packed16",
+    "slideo_matcher_activity_begin", "slideo_matcher_activity_end", "slideo_matcher_observe_frames_bgr8", "slideo_matcher_observe_frames_yuv420",
+    "slideo_matcher_observe_frames_bgr8_dev", "slideo_matcher_observe_frames_yuv420_dev", "slideo_matcher_activity_info",
+    "slideo_matcher_activity_counts", "slideo_matcher_activity_mask",
 ]
 
 # frame mask scope (include/slideo_amd.h "Frame mask scope")
@@ -287,6 +290,17 @@ def lib():
             L.slideo_group_set_yuv_description.argtypes = [vp, i32, i32, i32]
             L.slideo_yuv_coefficients.argtypes = [i32, i32, vp]
             L.slideo_yuv420_layout_packed16.argtypes = [i32, i32, i32, vp]
+        if hasattr(L, "slideo_matcher_activity_begin"):
+            vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
+            L.slideo_matcher_activity_begin.argtypes = [vp, i32]
+            L.slideo_matcher_activity_end.argtypes = [vp]
+            L.slideo_matcher_observe_frames_bgr8.argtypes = [vp, i32, vp, i32, i32, i32, i64]
+            L.slideo_matcher_observe_frames_yuv420.argtypes = [vp, i32, vp, i32, i32, vp, i64]
+            L.slideo_matcher_observe_frames_bgr8_dev.argtypes = [vp, i32, vp, i32, i32, i32, i64, vp]
+            L.slideo_matcher_observe_frames_yuv420_dev.argtypes = [vp, i32, vp, i32, i32, vp, i64, vp]
+            L.slideo_matcher_activity_info.argtypes = [vp, vp, vp, vp, vp]
+            L.slideo_matcher_activity_counts.argtypes = [vp, vp, i64, vp, vp, vp]
+            L.slideo_matcher_activity_mask.argtypes = [vp, i32, i32, vp, i64, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -805,6 +819,60 @@ class Matcher(_FrameCalls):
         ch, sim, out = self._gated_out(n)
         self._check(lib().slideo_match_changed_frames_collect(self._h, C.c_int64(t), _p(ch), _p(sim), _p(out)))
         return ch.astype(bool), sim, out
+
+    # ---- frame activity map (include/slideo_amd.h "Frame activity map") ------------------------
+    def activity_begin(self, delta):
+        """An empty accumulator: a pixel moved between consecutive observed images iff its BGR sum of absolute differences > delta."""
+        self._check(lib().slideo_matcher_activity_begin(self._h, int(delta)))
+
+    def activity_end(self):
+        self._check(lib().slideo_matcher_activity_end(self._h))
+
+    def observe_frames(self, frames):
+        """frames: uint8 [n, h, w, 3] in host memory, continuing the accumulator."""
+        frames = np.ascontiguousarray(frames, np.uint8)
+        n, h, w, c = frames.shape
+        assert c == 3
+        self._check(lib().slideo_matcher_observe_frames_bgr8(self._h, n, _p(frames), w, h, w * 3, C.c_int64(w * h * 3)))
+
+    def observe_frames_yuv420(self, frames, w, h, layout="nv12"):
+        frames, layout, fs = _yuv_frames(frames, w, h, layout)
+        self._check(lib().slideo_matcher_observe_frames_yuv420(self._h, frames.shape[0], _p(frames), w, h, C.byref(layout), C.c_int64(fs)))
+
+    def observe_frames_dev(self, dev_ptr, n, w, h, stride=None, frame_stride=None, stream=0):
+        stride = stride or w * 3
+        frame_stride = frame_stride or stride * h
+        self._check(lib().slideo_matcher_observe_frames_bgr8_dev(self._h, n, C.c_void_p(dev_ptr), w, h, stride, C.c_int64(frame_stride),
+                                                                 C.c_void_p(stream)))
+
+    def observe_frames_yuv420_dev(self, dev_ptr, n, w, h, layout, frame_stride, stream=0):
+        if isinstance(layout, str):
+            layout = yuv420_layout(layout, w, h)[0]
+        self._check(lib().slideo_matcher_observe_frames_yuv420_dev(self._h, n, C.c_void_p(dev_ptr), w, h, C.byref(layout),
+                                                                   C.c_int64(frame_stride), C.c_void_p(stream)))
+
+    def activity_info(self):
+        """-> {aw, ah, pairs, delta} (aw == 0 before the first observed frame)."""
+        aw, ah, pairs, delta = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+        self._check(lib().slideo_matcher_activity_info(self._h, C.byref(aw), C.byref(ah), C.byref(pairs), C.byref(delta)))
+        return {"aw": aw.value, "ah": ah.value, "pairs": pairs.value, "delta": delta.value}
+
+    def activity_counts(self):
+        """-> (counts uint32 [ah, aw], pairs)"""
+        aw, ah, pairs = C.c_int32(), C.c_int32(), C.c_int32()
+        self._check(lib().slideo_matcher_activity_counts(self._h, None, C.c_int64(0), C.byref(aw), C.byref(ah), C.byref(pairs)))
+        out = np.empty((ah.value, aw.value), np.uint32)
+        self._check(lib().slideo_matcher_activity_counts(self._h, _p(out), C.c_int64(out.size), C.byref(aw), C.byref(ah), C.byref(pairs)))
+        return out, pairs.value
+
+    def activity_mask(self, max_share, grow):
+        """max_share: a float in [0, 1], rounded to parts per million -> (mask uint8 [ah, aw] of 0 / 255, n_active, n_masked)"""
+        i = self.activity_info()
+        out = np.empty((i["ah"], i["aw"]), np.uint8)
+        aw, ah, na, nm = C.c_int32(), C.c_int32(), C.c_int64(), C.c_int64()
+        self._check(lib().slideo_matcher_activity_mask(self._h, int(round(float(max_share) * 1000000)), int(grow), _p(out), C.c_int64(out.size),
+                                                       C.byref(aw), C.byref(ah), C.byref(na), C.byref(nm)))
+        return out, na.value, nm.value
 
     # ---- YUV 4:2:0 frames (include/slideo_amd.h "YUV 4:2:0 frames") ---------------------------
     def match_frames_yuv420_dev(self, dev_ptr, n, w, h, layout, frame_stride, stream=0):

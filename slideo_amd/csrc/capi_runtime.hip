@@ -102,7 +102,7 @@ void validate_frames(FrameSrc& src, slideo_matcher* m, int n, const void* out) {
 }
 
 // prep, unit size and small size: the frame region, else the working size (the region's output fits it: the set calls' rule)
-static void resolve_unit(const slideo_matcher* m, FrameSrc& src) {
+void resolve_unit(const slideo_matcher* m, FrameSrc& src) {
     const FrameSettings& fs = m->fs;
     const FrameRegion& R = fs.region;
     const int small_area = m->cfg.small_area;

@@ -11,6 +11,7 @@
 //   stage_page_set.hip page sets: a subset's search operand built from the finalized deck (kernels: page_set.hip.h)
 //   stage_gate.hip     changed-frame gate: gated units, the gate state and its entry points (kernels: gate.hip.h)
 //   stage_direct.hip   direct page look-up: the page operand, a gated unit's look-up, its entry points (kernels: direct.hip.h)
+//   stage_activity.hip frame activity map: the accumulator, the observe driver, its entry points (kernels: activity.hip.h)
 //   capi_taps.hip      debug taps of the parity tests
 //   capi_group.hip     the N-device group (slideo_group_*)
 //
@@ -358,6 +359,12 @@ struct slideo_matcher {
     slideo::DevBuf d_gate_small;
     hipEvent_t last_gate_ev = nullptr;
 
+    // frame activity map (include/slideo_amd.h "Frame activity map"): the accumulator — "none" (on false), empty (aw 0) or the counts
+    // of `pairs` consecutive pairs of aw x ah analysed images — and its device buffers: the counts (u32), the carried last image, the
+    // staging of a block of observed frames (stage_frames' `into`) and the read-out's {counters | pass 1 | mask}
+    struct Activity { bool on = false; int aw = 0, ah = 0, delta = 0; int64_t pairs = 0; } activity;
+    slideo::DevBuf d_act_count, d_act_last, d_act_stage, d_act_mask;
+
     // direct page look-up (include/slideo_amd.h "Direct page look-up"): built at the first use with fs.direct_t > 0 after finalize, the
     // deck's size classes
     bool direct_built = false;
@@ -403,6 +410,8 @@ void validate_frames(FrameSrc& src, slideo_matcher* m = nullptr, int n = 0, cons
 // region (SLIDEO_ERR_INVALID_ARG at another size than its source; none for analysed frames), else the working size —; match: the source
 // limit of a reduced frame, the SIFT limits, the page set's modes, the mask's pyramid (frame_mask_for); the gate's weights and npx.
 void resolve_frames(const slideo_matcher* m, FrameSrc& src, bool match);
+// its first step alone: prep, unit size and small size of a validated source (what an observe call needs: no mask, no gate map)
+void resolve_unit(const slideo_matcher* m, FrameSrc& src);
 // The one path by which a frame setting of m changes: idle (SLIDEO_ERR_STATE), the rules between settings on `next` (a propose_*
 // of frame_settings.h), what the mask and its scope need on the device built first and installed on success (mask: the host mask
 // of SET_FRAME_MASK, rows `stride` apart), then `next` in force and what SETTING_ENDS[what] ends ended.

@@ -244,6 +244,22 @@ def _gated_matcher(m):
     return m if hasattr(m, "match_changed_frames") and hasattr(m, "gate_reset") else None
 
 
+def learn_frame_mask(matcher, frame_batches, *, delta, max_share, grow):
+    """A frame mask learnt from the frames' own motion (include/slideo_amd.h "Frame activity map"): the activity map of the host BGR
+    batches (each uint8 [n, h, w, 3], in order: the last frame of a batch pairs with the first of the next), thresholded at
+    `max_share` of the pairs and grown by `grow` pixels.  `matcher`: a Matcher (of a Group: its member 0), idle; neither pages nor
+    finalize are needed.  Returns the mask, uint8 [ah, aw] of 0 / 255 at the analysed size — what frame_mask= takes; nothing is
+    installed.  No value has a default: delta, max_share and grow depend on the content (docs/EXTENSIONS.md "Frame activity map")."""
+    matcher.activity_begin(delta)
+    try:
+        for batch in frame_batches:
+            matcher.observe_frames(batch)
+        mask, _, _ = matcher.activity_mask(max_share, grow)
+    finally:
+        matcher.activity_end()
+    return mask
+
+
 def dedup_timeline(mappings: List[Matching]) -> List[Matching]:
     """lib.rs:229-244: stable sort by time, drop consecutive mappings with the same image."""
     mappings = sorted(mappings, key=lambda mm: mm.video_time)
