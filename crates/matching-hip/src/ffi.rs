@@ -9,6 +9,8 @@ pub const SLIDEO_MASK_DETECT: u32 = 1;
 pub const SLIDEO_MASK_GATE: u32 = 2;
 pub const SLIDEO_DIRECT_WHOLE: u32 = 0;
 pub const SLIDEO_DIRECT_VALID: u32 = 1;
+pub const SLIDEO_GATE_PREVIOUS: u32 = 0;
+pub const SLIDEO_GATE_ANCHOR: u32 = 1;
 pub const SLIDEO_YUV_MATRIX_BT601: i32 = 0;
 pub const SLIDEO_YUV_MATRIX_BT709: i32 = 1;
 pub const SLIDEO_YUV_RANGE_LIMITED: i32 = 0;
@@ -479,6 +481,19 @@ extern "C" {
         n: i32,
         sw: i32,
         sh: i32,
+        ssd_out: *mut u64,
+    ) -> i32;
+    // gate reference (include/slideo_amd.h "Gate reference"): SLIDEO_GATE_PREVIOUS / SLIDEO_GATE_ANCHOR
+    pub fn slideo_matcher_set_gate_reference(m: *mut slideo_matcher, reference: u32) -> i32;
+    pub fn slideo_matcher_gate_reference(m: *const slideo_matcher, reference: *mut u32) -> i32;
+    pub fn slideo_group_set_gate_reference(g: *mut slideo_group, reference: u32) -> i32;
+    pub fn slideo_small_gram_ssd(
+        m: *mut slideo_matcher,
+        small: *const u8,
+        n: i32,
+        sw: i32,
+        sh: i32,
+        use_valid: i32,
         ssd_out: *mut u64,
     ) -> i32;
     // YUV colour description (include/slideo_amd.h "YUV colour description"): SLIDEO_YUV_MATRIX_* / _RANGE_* / _DEPTH_*

@@ -95,6 +95,11 @@ pub struct HipImageVideoMatcher {
     /// _RANGE_* / _DEPTH_*.  BT.709 for HD recordings, full range for many screen recorders, a 10-bit depth for P010 /
     /// yuv420p10le frames.  The reference reads every stream as BT.601 limited range: the default (0, 0, 0).
     pub yuv_description: (i32, i32, i32),
+    /// Which frame a gated frame is compared with (slideo_group_set_gate_reference): ffi::SLIDEO_GATE_PREVIOUS (default: the
+    /// frame before, the reference's MarkSimilarIter) or ffi::SLIDEO_GATE_ANCHOR (the last frame that was flagged: a change
+    /// spread over many frames is still flagged when every decoded frame is fed).  One device only: a group of several
+    /// refuses SLIDEO_GATE_ANCHOR when it is built.
+    pub gate_reference: u32,
 }
 
 impl Default for HipImageVideoMatcher {
@@ -108,6 +113,7 @@ impl Default for HipImageVideoMatcher {
             direct_scope: ffi::SLIDEO_DIRECT_WHOLE,
             frame_region: None,
             yuv_description: (ffi::SLIDEO_YUV_MATRIX_BT601, ffi::SLIDEO_YUV_RANGE_LIMITED, ffi::SLIDEO_YUV_DEPTH_8),
+            gate_reference: ffi::SLIDEO_GATE_PREVIOUS,
         }
     }
 }
@@ -131,6 +137,9 @@ impl<'i> ImageVideoMatcher<'i> for HipImageVideoMatcher {
                 std::ptr::null_mut(),
                 ffi::slideo_group_create(cfg.as_ptr(), self.devices.len() as i32, devices_ptr, &mut h),
             );
+            if self.gate_reference != ffi::SLIDEO_GATE_PREVIOUS {
+                check(h, ffi::slideo_group_set_gate_reference(h, self.gate_reference));
+            }
             if let Some(ratio) = self.sift_ratio {
                 let mut sc = std::mem::MaybeUninit::<ffi::slideo_sift_config>::uninit();
                 ffi::slideo_sift_config_default(sc.as_mut_ptr());

@@ -1009,6 +1009,60 @@ int32_t     slideo_group_match_changed_frames_yuv420(slideo_group* g, int32_t n_
                                                      const slideo_yuv420_layout* layout, int64_t frame_stride_bytes, uint8_t* changed_out,
                                                      float* similarity_out, slideo_verdict* verdicts_out);
 
+/* ---- Gate reference (extension: which frame a gated frame is compared with) -------------------------------------------------------
+ * MarkSimilarIter compares frame i with frame i - 1.  The reference samples one frame every five seconds, where "the frame before"
+ * is another picture after any slide change.  Fed every decoded frame — what the gate exists to make affordable — a change spread
+ * over several frames (a cross-fade, a slide transition, an animated build, slow scrolling) never crosses the threshold in one step:
+ * no frame of it is flagged, and the stream after it returns "unchanged" although it shows another slide.
+ * A matcher carries a GATE REFERENCE:
+ *   SLIDEO_GATE_PREVIOUS (default)  everything under "Changed-frame gate" above, as before.
+ *   SLIDEO_GATE_ANCHOR              the gate state is "none" or the small image of the ANCHOR: the last frame that was flagged, and
+ *                                   therefore matched.  Every unflagged frame is then within cfg.changed_similarity of a frame that
+ *                                   got a verdict.
+ * Under SLIDEO_GATE_ANCHOR, with f_0 .. f_{N-1} the frames of all gated calls and units since the last reset, in submission order:
+ *   similarity    ssd_i is the SSD of small(f_i) against the anchor in force BEFORE f_i is decided — under SLIDEO_MASK_GATE with a mask
+ *                 set over the valid small pixels, normalised over n_valid, exactly as "Frame mask scope" defines —, and
+ *                 similarity[i] is the mask call's host expression of ssd_i;
+ *   flag          changed[i] = similarity[i] < cfg.changed_similarity; on the device ssd_i >= slideo_changed_ssd_threshold[_n], as
+ *                 under PREVIOUS;
+ *   anchor        a changed frame becomes the anchor, an unchanged frame leaves it alone;
+ *   state "none"  f_0 has similarity 0.0, is changed and becomes the anchor;
+ *   independence  the result depends neither on where unit and call boundaries fall nor on how many units are in flight.
+ * Rules 2, 3, 4 and 6 of "Changed-frame gate" hold word for word.  Rule 5 becomes: slideo_matcher_gate_last_small returns the
+ * anchor's small image, unmasked; slideo_matcher_gate_reset and slideo_matcher_gate_reset_from_frame_* set the anchor.  Rule 1 is
+ * replaced by the definition above (tests/gate_anchor_ref.py restates it in numpy).  The definition is exact and in integers.
+ * The mask + kept pair: slideo_changed_mask_* takes prev_small explicitly and stays MarkSimilarIter, whatever the gate reference is.
+ * The direct page look-up works as before on the changed frames; it never depended on the flags.
+ * The reference is a frame setting: it changes on an idle matcher only (SLIDEO_ERR_STATE), an unknown value is
+ * SLIDEO_ERR_INVALID_ARG and the value before stays, and a change resets the gate state (the state means another frame).
+ * Group: a group of one member forwards the call and returns what the single matcher returns.  With more members SLIDEO_GATE_ANCHOR
+ * is SLIDEO_ERR_UNSUPPORTED and no member is changed: a shard's anchor depends on every flag before the shard, which the one-frame
+ * halo that primes a shard cannot supply.  SLIDEO_GATE_PREVIOUS is always accepted.
+ * Where it runs (csrc/gate_anchor.hip.h, csrc/stage_gate_anchor.hip; gate_unit_submit's one branch): the rule is sequential — a flag
+ * decides what the next frame is compared with — so a unit of n frames computes every pair it could need at once: the frames'
+ * centred operand (direct_centre_kernel, or direct_centre_valid_kernel under the gate's weights), frame_gram_kernel — <a'_i, a'_j>
+ * for i < j on v_mfma_i32_32x32x32_i8, page_ssd_kernel's symmetric case, SSD = |a'_i|^2 + |a'_j|^2 - 2 <a'_i, a'_j> exact in
+ * integers —, the n SSDs against the carried anchor (the shipped SSD launch; the only step that waits for the previous unit's
+ * state), gate_anchor_kernel — one wave walks the table and writes what gate_kernel writes — and gate_anchor_state_kernel, which
+ * copies the last anchor's small image into the state.  A unit that also looks pages up builds the operand twice.  The operand
+ * takes 3 sw sh bytes (padded to 128) per frame and the table 8 n^2 bytes; a gated unit is capped at 1024 frames (a synchronous
+ * call is cut accordingly, a longer submitted unit is SLIDEO_ERR_CAPACITY).  Every allocation happens before the first write of the
+ * gate state, so an error leaves the state as it was. */
+#define SLIDEO_GATE_PREVIOUS 0u  /* default: a gated frame is compared with the frame before it (MarkSimilarIter) */
+#define SLIDEO_GATE_ANCHOR   1u  /* ... with the last frame that was flagged */
+/* Idle matcher (SLIDEO_ERR_STATE otherwise).  Resets the gate state, also when the value does not change. */
+int32_t     slideo_matcher_set_gate_reference(slideo_matcher* m, uint32_t ref);
+/* The matcher's gate reference (SLIDEO_GATE_PREVIOUS unless set).  SLIDEO_ERR_INVALID_ARG for a null argument. */
+int32_t     slideo_matcher_gate_reference(const slideo_matcher* m, uint32_t* ref);
+/* Every member idle.  More than one member: SLIDEO_GATE_ANCHOR is SLIDEO_ERR_UNSUPPORTED (above).  Resets the group's gate state. */
+int32_t     slideo_group_set_gate_reference(slideo_group* g, uint32_t ref);
+/* Tap: frame_gram_kernel and the operand kernels on their own.  small: n small images of sw x sh (3 bytes per pixel, back to back, host
+ * memory); ssd_out [n * n]: ssd_out[i * n + j] = the SSD of images i and j over whole images (symmetric, 0 on the diagonal), or,
+ * use_valid != 0, over the valid pixels of the matcher's current validity map: SLIDEO_ERR_STATE without a map in force,
+ * SLIDEO_ERR_INVALID_ARG when (sw, sh) is not the map's size.  Idle matcher; needs no pages.  n <= 1024, sw * sh <= small_area. */
+int32_t     slideo_small_gram_ssd(slideo_matcher* m, const uint8_t* small, int32_t n, int32_t sw, int32_t sh, int32_t use_valid,
+                                  uint64_t* ssd_out);
+
 /* ---- Direct page look-up (extension: the reference never decides without keypoints) ---------------------------------------------
  * In a screen recording the frame IS the slide, full screen, plus codec noise.  The reference's final score for a candidate is
  * compute_similarity(to_small(warp(frame)), page.small); for such a frame the warp is the identity up to scale, so

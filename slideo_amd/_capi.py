@@ -185,6 +185,7 @@ EXPORTS = [
     "slideo_matcher_activity_begin", "slideo_matcher_activity_end", "slideo_matcher_observe_frames_bgr8", "slideo_matcher_observe_frames_yuv420",
     "slideo_matcher_observe_frames_bgr8_dev", "slideo_matcher_observe_frames_yuv420_dev", "slideo_matcher_activity_info",
     "slideo_matcher_activity_counts", "slideo_matcher_activity_mask",
+    "slideo_matcher_set_gate_reference", "slideo_matcher_gate_reference", "slideo_group_set_gate_reference", "slideo_small_gram_ssd",
 ]
 
 # frame mask scope (include/slideo_amd.h "Frame mask scope")
@@ -193,6 +194,10 @@ MASK_GATE = 2
 # direct look-up scope (include/slideo_amd.h "Direct look-up scope")
 DIRECT_WHOLE = 0
 DIRECT_VALID = 1
+# gate reference (include/slideo_amd.h "Gate reference")
+GATE_PREVIOUS = 0
+GATE_ANCHOR = 1
+GATE_REFERENCES = {"previous": GATE_PREVIOUS, "anchor": GATE_ANCHOR}
 
 _lib = None
 
@@ -301,6 +306,12 @@ def lib():
             L.slideo_matcher_activity_info.argtypes = [vp, vp, vp, vp, vp]
             L.slideo_matcher_activity_counts.argtypes = [vp, vp, i64, vp, vp, vp]
             L.slideo_matcher_activity_mask.argtypes = [vp, i32, i32, vp, i64, vp, vp, vp, vp]
+        if hasattr(L, "slideo_matcher_set_gate_reference"):
+            vp, i32, u32 = C.c_void_p, C.c_int32, C.c_uint32
+            L.slideo_matcher_set_gate_reference.argtypes = [vp, u32]
+            L.slideo_matcher_gate_reference.argtypes = [vp, vp]
+            L.slideo_group_set_gate_reference.argtypes = [vp, u32]
+            L.slideo_small_gram_ssd.argtypes = [vp, vp, i32, i32, i32, i32, vp]
         _lib = L
     return _lib
 
@@ -482,6 +493,24 @@ class _FrameCalls:
         if rc != OK:
             raise SlideoError(rc, "direct_scope")
         return scope.value
+
+    # gate reference (include/slideo_amd.h "Gate reference"): which frame a gated frame is compared with
+    def set_gate_reference(self, ref):
+        """ref: 'previous' (the default: the frame before, MarkSimilarIter) or 'anchor' (the last frame that was flagged), or the
+        SLIDEO_GATE_* value.  The matcher must be idle; resets the gate state.  A Group of more than one member refuses 'anchor'."""
+        if isinstance(ref, str):
+            if ref not in GATE_REFERENCES:
+                raise SlideoError(1, "gate reference %r: 'previous' or 'anchor'" % (ref,))
+            ref = GATE_REFERENCES[ref]
+        self._check(getattr(lib(), self._SETS + "set_gate_reference")(self._h, int(ref)))
+
+    def gate_reference(self):
+        """'previous' or 'anchor' (a Group: member 0's)."""
+        ref = C.c_uint32()
+        rc = lib().slideo_matcher_gate_reference(self._mask_owner(), C.byref(ref))
+        if rc != OK:
+            raise SlideoError(rc, "gate_reference")
+        return {v: k for k, v in GATE_REFERENCES.items()}[ref.value]
 
     # YUV colour description (include/slideo_amd.h "YUV colour description"): how every *_yuv420 call reads its samples
     def set_yuv_description(self, matrix="bt601", range="limited", depth=8):
@@ -1073,6 +1102,18 @@ class Matcher(_FrameCalls):
         n, sh, sw, _ = smalls.shape
         out = np.empty((n, self.page_count), np.uint64)
         self._check(lib().slideo_page_small_ssd_valid(self._h, _p(smalls), n, sw, sh, _p(out)))
+        return out
+
+    def small_gram_ssd(self, smalls, use_valid=False):
+        """slideo_small_gram_ssd: smalls uint8 [n, sh, sw, 3] -> uint64 [n, n], the integer SSD of every pair of them (0 on the
+        diagonal); use_valid: over the valid pixels of the matcher's current validity map.  The kernels of the gate reference
+        'anchor'; needs no pages."""
+        smalls = np.ascontiguousarray(smalls, np.uint8)
+        if smalls.ndim != 4 or smalls.shape[3] != 3:
+            raise ValueError("expected [n, sh, sw, 3] uint8 small images")
+        n, sh, sw, _ = smalls.shape
+        out = np.empty((n, n), np.uint64)
+        self._check(lib().slideo_small_gram_ssd(self._h, _p(smalls), n, sw, sh, 1 if use_valid else 0, _p(out)))
         return out
 
     def small_image(self, bgr):

@@ -366,6 +366,14 @@ int32_t slideo_group_set_yuv_description(slideo_group* g, int32_t matrix, int32_
     return group_set(g, SET_YUV_DESCRIPTION, [&](const FrameSettings& s) { return propose_yuv_description(s, matrix, range, depth); });
 }
 
+// (the group's own rule first: ANCHOR needs a group of one member, and a refused call changes no member)
+int32_t slideo_group_set_gate_reference(slideo_group* g, uint32_t ref) {
+    return group_set(g, SET_GATE_REFERENCE, [&](const FrameSettings& s) {
+        gate_reference_group_rule((int)g->members.size(), ref);
+        return propose_gate_reference(s, ref);
+    });
+}
+
 // Page sets: every member builds the same set from the same deck (ids are handed out in the same order: they agree)
 int32_t slideo_group_create_page_set(slideo_group* g, int32_t n_pages, const int32_t* pages, int32_t* set_out) {
     if (!g) return SLIDEO_ERR_INVALID_ARG;

@@ -348,7 +348,9 @@ static void unit_begin(slideo_matcher* m, Slot& S, const FrameSrc& src, int firs
 
 // max frames per unit of a call of either kind under the workspace budget
 static int unit_fit(slideo_matcher* m, const FrameSrc& src, int n, bool gated) {
-    return sub_batch_for(m, geom_for(m, src.plan.uw, src.plan.uh).g, n, src.staging_bytes(gated ? gate_small_budget(m) : 0));
+    const int fit = sub_batch_for(m, geom_for(m, src.plan.uw, src.plan.uh).g, n, src.staging_bytes(gated ? gate_small_budget(m) : 0));
+    // (under SLIDEO_GATE_ANCHOR a gated unit's pair table caps it: include/slideo_amd.h "Gate reference")
+    return gated && m->fs.gate_ref == SLIDEO_GATE_ANCHOR ? std::min(fit, GATE_ANCHOR_MAX_UNIT) : fit;
 }
 
 // Synchronous matching of n frames, plain or gated (changed_out, similarity_out: a gated call's): cut into units and run them

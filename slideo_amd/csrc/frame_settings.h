@@ -1,5 +1,5 @@
 // frame_settings.h — the frame settings of a matcher as ONE record (include/slideo_amd.h "Working size", "Frame region", "Frame mask",
-// "Frame mask scope", "Direct page look-up", "Direct look-up scope", "YUV colour description"): the record, every setter's proposal with its range checks, the
+// "Frame mask scope", "Direct page look-up", "Direct look-up scope", "YUV colour description", "Gate reference"): the record, every setter's proposal with its range checks, the
 // rules between settings, what a change of each ends.  Plain C++, no HIP include (tools/frame_settings_hostcheck.cpp walks it on the
 // host); the device buffers a setting owns are the matcher's (runtime.hpp).  A change takes ONE path: settings_commit (capi_runtime.hip).
 #pragma once
@@ -44,18 +44,20 @@ struct FrameSettings {
     float direct_t = 0.f;                             // the direct similarity (0: off)
     uint32_t direct_scope = SLIDEO_DIRECT_WHOLE;      // VALID = the look-up over the gate's valid pixels
     YuvDesc yuv;                                      // 4:2:0 frames stand for the BGR image under it (BGR calls never look at it)
+    uint32_t gate_ref = SLIDEO_GATE_PREVIOUS;         // what a gated frame is compared with: the frame before it, or the last changed one (ANCHOR)
     bool gate_scope() const { return mask.set && (mask_scope & SLIDEO_MASK_GATE); }      // the gate compares under the mask
 };
 
 enum Setting { SET_WORKING_SIZE, SET_FRAME_REGION, SET_FRAME_MASK, SET_FRAME_MASK_SCOPE, SET_DIRECT_SIMILARITY, SET_DIRECT_SCOPE, SET_YUV_DESCRIPTION,
-               N_SETTINGS };
+               SET_GATE_REFERENCE, N_SETTINGS };
 
 // What a change of each setting ends: the frames a mask call kept (made under the earlier setting), the gate state (so was its small
-// image; under a mask change it stays: it is a whole frame's), the map's generation.  Applied by settings_commit and, the group's
+// image; under a mask change it stays: it is a whole frame's; under another gate reference the state MEANS another frame), the map's generation.  Applied by settings_commit and, the group's
 // half, by group_set: nowhere else.
 struct SettingEnds { bool kept, gate, map_gen; };
 constexpr SettingEnds SETTING_ENDS[N_SETTINGS] = {{true, true, true}, {true, true, false}, {true, false, true}, {true, false, true},
-                                                  {false, false, false}, {false, false, false}, {true, true, false}};
+                                                  {false, false, false}, {false, false, false}, {true, true, false},
+                                                  {false, true, false}};
 
 // ---- a setter's proposal (the matcher's and the group's): `s` in force with its arguments applied, their range checked (INVALID_ARG)
 inline FrameSettings propose_working_size(FrameSettings s, int max_w, int max_h) {
@@ -121,6 +123,22 @@ inline FrameSettings propose_yuv_description(FrameSettings s, int matrix, int ra
     s.yuv = YuvDesc{matrix, range, depth};
     return s;
 }
+
+inline FrameSettings propose_gate_reference(FrameSettings s, uint32_t ref) {
+    if (ref != SLIDEO_GATE_PREVIOUS && ref != SLIDEO_GATE_ANCHOR)
+        fail(SLIDEO_ERR_INVALID_ARG, "gate reference %u: SLIDEO_GATE_PREVIOUS (0) or SLIDEO_GATE_ANCHOR (1)", ref);
+    s.gate_ref = ref;
+    return s;
+}
+// The group's rule for a gate reference (include/slideo_amd.h "Gate reference"): a shard's anchor depends on every flag before the
+// shard, which the one-frame halo that primes a shard cannot supply, so ANCHOR needs a group of one member.  PREVIOUS always passes.
+inline void gate_reference_group_rule(int members, uint32_t ref) {
+    if (ref == SLIDEO_GATE_ANCHOR && members > 1)
+        fail(SLIDEO_ERR_UNSUPPORTED, "gate reference SLIDEO_GATE_ANCHOR in a group of %d members: a shard's anchor depends on every flag before "
+             "the shard, and the one frame that primes a shard cannot supply it (a group of one member, or a single matcher)", members);
+}
+// frames per gated unit under SLIDEO_GATE_ANCHOR: the unit's table of dot products takes 8 n^2 bytes
+constexpr int GATE_ANCHOR_MAX_UNIT = 1024;
 
 // The seven integers of the fixed-point conversion under (matrix, range) — CY, CUB, CUG, CVG, CVR, y_offset, SHIFT —, arguments
 // checked by the caller.  (BT601, LIMITED): cvtColor's literals.  Every other pair by the rule of include/slideo_amd.h, in float64.

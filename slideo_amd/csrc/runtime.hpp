@@ -12,6 +12,7 @@
 //   stage_gate.hip     changed-frame gate: gated units, the gate state and its entry points (kernels: gate.hip.h)
 //   stage_direct.hip   direct page look-up: the page operand, a gated unit's look-up, its entry points (kernels: direct.hip.h)
 //   stage_activity.hip frame activity map: the accumulator, the observe driver, its entry points (kernels: activity.hip.h)
+//   stage_gate_anchor.hip  gate reference ANCHOR: a gated unit's pair table and walk, the setting and the tap (kernels: gate_anchor.hip.h)
 //   capi_taps.hip      debug taps of the parity tests
 //   capi_group.hip     the N-device group (slideo_group_*)
 //
@@ -181,6 +182,9 @@ struct Slot {
     // ... under a direct similarity (stage_direct.hip): the frames' centred operand, {|a'|^2 n x i64 | best n x DirectBest} and the
     // n x np dot products (reserved by the first such unit only)
     DevBuf d_dir_a, d_dir_rec, d_dir_dot;
+    // ... under SLIDEO_GATE_ANCHOR (stage_gate_anchor.hip): the frames' centred operand, {|a'|^2 n x i64 | SSDs against the carried
+    // anchor n x u64 | the unit's last anchor i32}, and the n x n dot products (reserved by the first such unit only)
+    DevBuf d_ga_a, d_ga_rec, d_ga_dot;
     hipEvent_t ev_gate = nullptr;             // the unit's small images are made and the gate state is this unit's last one
     struct GateUnit {
         bool on = false;                      // the unit in flight is gated: slideo_match_changed_frames_collect collects it
@@ -528,10 +532,13 @@ inline void gate_state_reset(slideo_matcher* m) { m->gate = slideo_matcher::Gate
 // FrameSrc::staging_bytes' gate_small of a gated call (a small image has at most small_area pixels)
 // (under a direct similarity: + the frame's centred operand row, its row of dot products and its record; under the direct scope
 // VALID + the masked page norms, 8 bytes per page once per matcher: counted with every frame, a unit has at least one)
+// (under SLIDEO_GATE_ANCHOR: + the frame's centred operand row of the pair table, its norm, carried SSD and its row of the table —
+// 8 n bytes, n <= GATE_ANCHOR_MAX_UNIT)
 inline size_t gate_small_budget(const slideo_matcher* m) {
     const size_t small = (size_t)m->cfg.small_area * 3 + 64;
-    if (!(m->fs.direct_t > 0.f)) return small;
-    const size_t look = 2 * small + 128 + m->pages.size() * 8 + 64;
+    const size_t anchor = m->fs.gate_ref == SLIDEO_GATE_ANCHOR ? small + 128 + 32 + (size_t)GATE_ANCHOR_MAX_UNIT * 8 : 0;
+    if (!(m->fs.direct_t > 0.f)) return small + anchor;
+    const size_t look = 2 * small + 128 + m->pages.size() * 8 + 64 + anchor;
     return m->fs.direct_scope == SLIDEO_DIRECT_VALID ? look + m->pages.size() * 8 : look;
 }
 // a validated source's frames against a gate state (m->gate, the N-device group's): one size and one format family since the last
@@ -581,6 +588,33 @@ size_t direct_unit_rec_bytes(int n);
 struct DirectFrameRec { unsigned long long ssd; int32_t page; bool direct; };
 uint32_t direct_rec_kept(const uint8_t* h_rec, int n);
 DirectFrameRec direct_rec_frame(const uint8_t* h_rec, int n, int i);
+
+// the operand layout of direct.hip.h (stage_direct.hip asserts it), for the units that launch on that operand without its kernels
+constexpr int DIRECT_OP_TILE = 64, DIRECT_OP_KGRAN = 128, DIRECT_OP_KCHUNK_MAX = 65536;
+int64_t direct_kp(int64_t L);               // bytes of an operand row for small images of L bytes
+int direct_rows_pad(int rows);              // operand rows for `rows` images
+// The centred operand `out` ([rows_pad][kp], direct.hip.h's layout) and the norms |x'|^2 of the n images of L bytes at
+// src + (ofs ? ofs[row] : row * stride), on st.  weights (the gate's validity map): the operand zero at the masked bytes, the norms
+// over the valid ones; out null (weights only): the norms alone
+void launch_centre(const uint8_t* src, int64_t stride, const long long* ofs, int n, int rows_pad, int64_t L, int64_t kp, uint4* out,
+                   long long* norm, hipStream_t st, const uint8_t* weights = nullptr);
+// the K chunk of a grid over n x np rows
+int64_t direct_kchunk(int n, int np, int64_t kp);
+
+// ---- stage_gate_anchor.hip ------------------------------------------------------------------------
+// Where gate_anchor_unit writes a unit's decisions: gate_kernel's outputs — device flags, kept list and count, and the pinned
+// record's header {count, n}, SSDs, kept list and flags (gate.hip.h GateHostRec and gate_rec_*)
+struct GateAnchorOut {
+    uint8_t* flags; int32_t* idx; uint32_t* count;
+    uint32_t* h_head; unsigned long long* h_ssd; int32_t* h_idx; uint8_t* h_flag;
+};
+// a unit of n frames with sw x sh small images under SLIDEO_GATE_ANCHOR: S's workspaces (everything that can fail for want of memory)
+void gate_anchor_reserve(Slot& S, int n, int sw, int sh);
+// The unit's gate under SLIDEO_GATE_ANCHOR on S.st, behind the unit's small images `small` (sb bytes each): operand, pair table, the
+// SSDs against the carried anchor m->d_gate_small (behind `wait`, the previous gated unit's event; none when force0), the walk, and
+// the new state written into m->d_gate_small.  Launches only.
+void gate_anchor_unit(slideo_matcher* m, Slot& S, const uint8_t* weights, const uint8_t* small, int64_t sb, int n, long long thr, bool force0,
+                      hipEvent_t wait, const GateAnchorOut& out);
 
 // ---- stage_sift.hip -------------------------------------------------------------------------------
 void sift_check_cfg(const slideo_sift_config* sc, int w, int h);

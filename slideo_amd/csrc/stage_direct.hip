@@ -23,7 +23,8 @@ int64_t direct_ssd_threshold(float t, int64_t n) {
     return lo;
 }
 
-namespace {
+static_assert(DIRECT_OP_TILE == DIRECT_TILE && DIRECT_OP_KGRAN == DIRECT_KGRAN && DIRECT_OP_KCHUNK_MAX == DIRECT_KCHUNK_MAX,
+              "runtime.hpp states the operand layout of direct.hip.h");
 
 int64_t direct_kp(int64_t L) { return cdiv64(L, DIRECT_KGRAN) * DIRECT_KGRAN; }
 int direct_rows_pad(int rows) { return cdiv(rows, DIRECT_TILE) * DIRECT_TILE; }
@@ -31,7 +32,7 @@ int direct_rows_pad(int rows) { return cdiv(rows, DIRECT_TILE) * DIRECT_TILE; }
 // weights (the gate's validity map, SLIDEO_DIRECT_VALID; null: whole images): the operand zero at the masked bytes, the norms over
 // the valid ones; out null (weights only): the norms alone
 void launch_centre(const uint8_t* src, int64_t stride, const long long* ofs, int n, int rows_pad, int64_t L, int64_t kp, uint4* out,
-                   long long* norm, hipStream_t st, const uint8_t* weights = nullptr) {
+                   long long* norm, hipStream_t st, const uint8_t* weights) {
     // 32-row tiles x K slices: about 2048 waves, a wave at least one group of four K steps; the norms are added to
     const int tiles = rows_pad / 32;
     const int ky = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv64(512, tiles), cdiv64(kp / DIRECT_KGRAN, DIRECT_BLOCK / 64)));
@@ -48,6 +49,8 @@ void launch_centre(const uint8_t* src, int64_t stride, const long long* ofs, int
         check_launch("direct_centre_valid_kernel (norms)");
     }
 }
+
+namespace {
 
 // The deck's size classes and their operands, on m->stream (finalized, idle matcher or the first gated unit under t > 0: nothing
 // else reads or writes these buffers)
@@ -144,6 +147,8 @@ const int32_t* direct_eligible(slideo_matcher* m, const DirectClass& c, int set,
     return ps.direct_elig.back()->d.as<int32_t>();
 }
 
+}  // namespace
+
 // K chunks of the grid: enough blocks for every CU to hold a few waves, chunks of whole granules and at most DIRECT_KCHUNK_MAX
 int64_t direct_kchunk(int n, int np, int64_t kp) {
     const int64_t tiles = (int64_t)cdiv(n, DIRECT_TILE) * cdiv(np, DIRECT_TILE);
@@ -152,6 +157,8 @@ int64_t direct_kchunk(int n, int np, int64_t kp) {
     chunk = std::max<int64_t>(chunk, 8 * DIRECT_KGRAN);
     return std::min<int64_t>(chunk, DIRECT_KCHUNK_MAX);
 }
+
+namespace {
 
 // the slot's workspaces for n small images against class c
 void direct_reserve(Slot& S, const DirectClass& c, int n) {

@@ -1,6 +1,7 @@
 // stage_gate.hip — the changed-frame gate of include/slideo_amd.h "Changed-frame gate": gated units (small images of all frames, SSDs,
 // gate_kernel, gather_frames_kernel in front of the unchanged unit_submit), the gate state and its entry points (kernels: gate.hip.h).
-// The frame calls that run gated units are capi_runtime.hip's, beside their plain twins.
+// The frame calls that run gated units are capi_runtime.hip's, beside their plain twins.  Under the gate reference SLIDEO_GATE_ANCHOR
+// gate_unit_submit hands the SSDs, the flags and the new state to stage_gate_anchor.hip (include/slideo_amd.h "Gate reference").
 #include "runtime.hpp"
 #include "gate.hip.h"
 
@@ -122,6 +123,9 @@ void gate_unit_submit(slideo_matcher* m, Slot& S, const FrameSrc& src, int first
     DirectPlan plan;
     // the direct scope VALID: over the pixels the gate compares (null without a map in force: whole images)
     if (look) plan = direct_unit_prepare(m, S, n, sw, sh, m->fs.direct_scope == SLIDEO_DIRECT_VALID ? weights : nullptr);
+    // under SLIDEO_GATE_ANCHOR: the pair table's workspaces, first for the same reason (include/slideo_amd.h "Gate reference")
+    const bool anchor = m->fs.gate_ref == SLIDEO_GATE_ANCHOR;
+    if (anchor) gate_anchor_reserve(S, n, sw, sh);
     const DevFrames all = stage_frames(m, S, src, first, n, cs, &S.d_gstage);
     run_small_into(m, all, n, S.d_gsmall, st);
     const int64_t sb = (int64_t)sw * sh * 3;
@@ -136,11 +140,21 @@ void gate_unit_submit(slideo_matcher* m, Slot& S, const FrameSrc& src, int first
     S.h_gate.reserve(look ? direct_ofs + direct_unit_rec_bytes(n) : gate_rec_bytes(n));
     const bool force0 = !m->gate.has;
     m->d_gate_small.reserve((size_t)sb);            // (grows only from the state "none": no gated unit is reading it)
-    // pair i: (small[i - 1], small[i]); pair 0: (gate state, small[0]), behind the previous gated unit's write of the state
-    if (n > 1) launch_gate_ssd(weights, small, sb, small + sb, sb, sb, ssd + 1, n - 1, st);
-    if (m->last_gate_ev && m->last_gate_ev != S.ev_gate) HIP_CHECK(hipStreamWaitEvent(st, m->last_gate_ev, 0));
-    if (!force0) launch_gate_ssd(weights, m->d_gate_small.as<uint8_t>(), 0, small, 0, sb, ssd, 1, st);
-    HIP_CHECK(hipMemcpyAsync(m->d_gate_small.p, small + sb * (n - 1), (size_t)sb, hipMemcpyDeviceToDevice, st));
+    const long long thr = gate_ssd_threshold(m->cfg.changed_similarity, npx);
+    uint8_t* const hrec = S.h_gate.as<uint8_t>();
+    if (anchor) {
+        // every pair of the unit, the carried anchor against its frames behind the previous gated unit's write of the state, the walk
+        // (gate_kernel's outputs) and the new state: the unit's last flagged frame, if any
+        const GateAnchorOut out{flags, idx, count, reinterpret_cast<uint32_t*>(hrec), reinterpret_cast<unsigned long long*>(hrec + gate_rec_ssd_ofs()),
+                                reinterpret_cast<int32_t*>(hrec + gate_rec_idx_ofs(n)), hrec + gate_rec_flag_ofs(n)};
+        gate_anchor_unit(m, S, weights, small, sb, n, thr, force0, m->last_gate_ev != S.ev_gate ? m->last_gate_ev : nullptr, out);
+    } else {
+        // pair i: (small[i - 1], small[i]); pair 0: (gate state, small[0]), behind the previous gated unit's write of the state
+        if (n > 1) launch_gate_ssd(weights, small, sb, small + sb, sb, sb, ssd + 1, n - 1, st);
+        if (m->last_gate_ev && m->last_gate_ev != S.ev_gate) HIP_CHECK(hipStreamWaitEvent(st, m->last_gate_ev, 0));
+        if (!force0) launch_gate_ssd(weights, m->d_gate_small.as<uint8_t>(), 0, small, 0, sb, ssd, 1, st);
+        HIP_CHECK(hipMemcpyAsync(m->d_gate_small.p, small + sb * (n - 1), (size_t)sb, hipMemcpyDeviceToDevice, st));
+    }
     HIP_CHECK(hipEventRecord(S.ev_gate, st));
     m->last_gate_ev = S.ev_gate;
     slideo_matcher::GateState& g = m->gate;
@@ -149,9 +163,10 @@ void gate_unit_submit(slideo_matcher* m, Slot& S, const FrameSrc& src, int first
     // the look-up of all n frames (it does not depend on the flags); none when no page of the selected set shares the small size
     const bool direct = plan.cls != nullptr;
     if (direct) direct_unit_lookup(S, plan, n);
-    const long long thr = gate_ssd_threshold(m->cfg.changed_similarity, npx);
-    gate_kernel<<<1, GATE_BLOCK, 0, st>>>(ssd, n, thr, force0 ? 1 : 0, flags, idx, count, S.h_gate.as<uint8_t>());
-    check_launch("gate_kernel");
+    if (!anchor) {
+        gate_kernel<<<1, GATE_BLOCK, 0, st>>>(ssd, n, thr, force0 ? 1 : 0, flags, idx, count, hrec);
+        check_launch("gate_kernel");
+    }
     // the direct frames leave the kept list: the one host wait below reads the reduced count
     if (direct)
         direct_unit_gate(m, S, n, npx, idx, count, reinterpret_cast<int32_t*>(S.h_gate.as<uint8_t>() + gate_rec_idx_ofs(n)),

@@ -369,6 +369,11 @@ public:
         yuv_matrix_ = matrix; yuv_range_ = range; yuv_depth_ = depth;
         return *this;
     }
+    // Which frame a gated frame is compared with (slideo_group_set_gate_reference, include/slideo_amd.h "Gate reference"):
+    // SLIDEO_GATE_PREVIOUS (default: the frame before, the reference's MarkSimilarIter) or SLIDEO_GATE_ANCHOR (the last frame that
+    // was flagged: a change spread over many frames is still flagged when every decoded frame is fed).  One device only: a group of
+    // several refuses SLIDEO_GATE_ANCHOR when it is built (SLIDEO_ERR_UNSUPPORTED)
+    HipImageVideoMatcher& with_gate_reference(uint32_t ref) { gate_ref_ = ref; return *this; }
     // false: tasks run the stop-and-go pair slideo_group_changed_mask_bgr8 + slideo_group_match_kept_frames in place of the group's
     // gated call (the same timeline; for comparisons).  Default: gated
     HipImageVideoMatcher& with_changed_gate(bool on) { gated_ = on; return *this; }
@@ -380,6 +385,7 @@ public:
         if (rc != SLIDEO_OK) throw std::runtime_error(std::string("slideo_amd error ") + std::to_string(rc) + ": " + slideo_group_last_error(nullptr));
         h->n_devices = (int)slideo_group_device_count(h->g);
         h->gated = gated_;
+        if (gate_ref_ != SLIDEO_GATE_PREVIOUS) h->check(slideo_group_set_gate_reference(h->g, gate_ref_));
         if (sift_on_) {                                                                             // the north-star's SIFT + L2 front end
             slideo_sift_config sc;
             slideo_sift_config_default(&sc);
@@ -422,7 +428,7 @@ private:
     std::vector<uint8_t> mask_;
     int32_t mask_w_ = 0, mask_h_ = 0;
     int32_t yuv_matrix_ = SLIDEO_YUV_MATRIX_BT601, yuv_range_ = SLIDEO_YUV_RANGE_LIMITED, yuv_depth_ = SLIDEO_YUV_DEPTH_8;
-    uint32_t mask_scope_ = SLIDEO_MASK_DETECT, direct_scope_ = SLIDEO_DIRECT_WHOLE;
+    uint32_t mask_scope_ = SLIDEO_MASK_DETECT, direct_scope_ = SLIDEO_DIRECT_WHOLE, gate_ref_ = SLIDEO_GATE_PREVIOUS;
     slideo_config cfg_;
     ImageLoader loader_;
 };

@@ -313,7 +313,7 @@ class HipImageVideoMatcher:
     """Drop-in for OpenCVImageVideoMatcher (lib.rs:34-73) behind matching::ImageVideoMatcher."""
 
     def __init__(self, cfg=None, device=None, sift=None, devices=None, working_size=None, frame_mask=None, frame_mask_scope=None,
-                 direct_similarity=None, direct_scope=None, frame_region=None, yuv_description=None):
+                 direct_similarity=None, direct_scope=None, frame_region=None, yuv_description=None, gate_reference=None):
         """devices: HIP ordinals, one matcher each behind one slideo_group (the reference fans out over the whole machine, the
         global rayon pool of lib.rs:45,174); None = every gfx950 device of the node; `device` = d is short for devices = [d].
         sift = (slideo_sift_config, ratio): the north-star's SIFT + L2 front end instead of the reference's ORB + Hamming
@@ -341,7 +341,11 @@ class HipImageVideoMatcher:
         yuv_description = (matrix, range) or (matrix, range, depth), as Matcher.set_yuv_description takes them
         (slideo_group_set_yuv_description): how the YUV 4:2:0 videos are read — ("bt709", "limited") for HD recordings,
         ("bt709", "full") for many screen recorders; the reference reads every stream as BT.601 limited range; RawVideoYuv420
-        files hold 8-bit samples, so depth stays 8 for them; None = BT.601 limited, 8-bit."""
+        files hold 8-bit samples, so depth stays 8 for them; None = BT.601 limited, 8-bit.
+        gate_reference = "previous" or "anchor" (slideo_group_set_gate_reference): with "anchor" a frame is compared with the last
+        frame that was flagged, not the frame before it, so a change spread over many frames (a cross-fade, an animated build) is
+        still flagged when every decoded frame is fed; one device only — with several the group refuses it here, when it is built
+        (SLIDEO_ERR_UNSUPPORTED); None = "previous", the reference's MarkSimilarIter."""
         self._cfg, self._sift = cfg, sift
         self._working_size = working_size
         self._frame_mask = frame_mask
@@ -350,12 +354,15 @@ class HipImageVideoMatcher:
         self._direct_scope = direct_scope
         self._frame_region = frame_region
         self._yuv_description = tuple(yuv_description) if yuv_description is not None else None
+        self._gate_reference = gate_reference
         self._devices = [device] if device is not None else devices
 
     def create_video_matcher(self, images, progress_reporter: ProgressReporter) -> HipVideoMatcher:
         """images: objects with get_path() (matching::MatchableImage, lib.rs:31-33)."""
         images = list(images)
         m = _capi.Group(self._cfg, self._devices)
+        if self._gate_reference is not None:
+            m.set_gate_reference(self._gate_reference)
         if self._sift is not None:
             m.use_sift(*self._sift)
         if self._working_size is not None:
