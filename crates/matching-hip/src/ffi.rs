@@ -609,6 +609,34 @@ extern "C" {
         n_active: *mut i64,
         n_masked: *mut i64,
     ) -> i32;
+    // frame content box (include/slideo_amd.h "Frame content box"): per-pixel counts of lit frames, and the box read out of them;
+    // the slideo_matcher_observe_frames_* calls above feed it
+    pub fn slideo_matcher_content_begin(m: *mut slideo_matcher, level: i32) -> i32;
+    pub fn slideo_matcher_content_end(m: *mut slideo_matcher) -> i32;
+    pub fn slideo_matcher_content_info(
+        m: *mut slideo_matcher,
+        aw: *mut i32,
+        ah: *mut i32,
+        frames: *mut i32,
+        level: *mut i32,
+    ) -> i32;
+    pub fn slideo_matcher_content_counts(
+        m: *mut slideo_matcher,
+        out: *mut u32,
+        capacity_elems: i64,
+        aw: *mut i32,
+        ah: *mut i32,
+        frames: *mut i32,
+    ) -> i32;
+    pub fn slideo_matcher_content_box(
+        m: *mut slideo_matcher,
+        min_share_ppm: i32,
+        min_fill_ppm: i32,
+        box_out: *mut i32,
+        n_content: *mut i64,
+        fill_out: *mut u32,
+        fill_capacity_elems: i64,
+    ) -> i32;
 }
 
 /// The struct layouts above are only valid for one ABI version of the library.

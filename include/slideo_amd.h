@@ -786,7 +786,7 @@ int32_t     slideo_reduce_bgr8(slideo_matcher* m, const uint8_t* bgr, int32_t wi
  * (out_w, out_h).  WORKING SIZE: the source frame of a rectifying call is exempt from it, and the output must fit it: a region
  * whose output exceeds a set working size, or a working size smaller than a set region's output, is SLIDEO_ERR_UNSUPPORTED at
  * whichever set call comes second (the caller chooses the output size, so nothing is lost).
- * Out of scope: uploading only the region's bounding rows of host frames; a per-call or moving region; finding the quad; a region
+ * Out of scope: uploading only the region's bounding rows of host frames; a per-call or moving region; finding a quad other than the axis-aligned content box; a region
  * together with a larger working size.
  * DEPARTURE: the reference never rectifies a frame.  With a region set, verdicts are those of the rectified video; off by default. */
 /* M: 9 doubles, row-major, copied; NULL clears the region (the other arguments are then ignored).  Before or after finalize, any
@@ -1216,6 +1216,61 @@ int32_t     slideo_matcher_activity_counts(slideo_matcher* m, uint32_t* out, int
  * aw * ah > capacity. */
 int32_t     slideo_matcher_activity_mask(slideo_matcher* m, int32_t max_share_ppm, int32_t grow, uint8_t* out, int64_t capacity, int32_t* aw,
                                          int32_t* ah, int64_t* n_active, int64_t* n_masked);
+
+/* ---- Frame content box (extension: the measurement a frame region can be made from) ---------------------------------------------------
+ * The frame region needs a quad, and the caller had to know it in pixels.  The most common case in which the slide does not fill the
+ * frame is mechanical: 4:3 slides pillarboxed in a 16:9 recording, 16:10 letterboxed in 16:9, a windowboxed capture.  The slide's box
+ * is static and its surroundings are black up to codec noise.  With the exact crop as a region the rectify is the clamped-copy
+ * instance, the small sizes of frame and page agree, and the direct page look-up applies.
+ * A matcher carries a CONTENT ACCUMULATOR, off by default and independent of the activity accumulator.  Its state is "none", or: a
+ * level; an analysed size (aw, ah), fixed by the first observed frame; `frames`; lit[ah][aw] as u32 (device).
+ *   observed image   of a frame: exactly the activity map's — the BGR image the pipeline would analyse, after the 4:2:0 conversion
+ *                    under the matcher's YUV description, then the frame region's rectify or, failing that, the working-size reduce.
+ *   lit              pixel (x, y) of an observed image is lit iff max(B, G, R) > level, in integers; level in 0..254.
+ *   lit[y][x], frames  lit[y][x] = the number of observed frames since content_begin, across calls, in which (x, y) is lit; frames =
+ *                    the number of observed frames.  frames may not pass INT32_MAX (SLIDEO_ERR_STATE).
+ *   content pixel    lit[y][x] * 1000000 > min_share_ppm * frames, in unsigned 64-bit integers (strict); min_share_ppm in 0..1000000.
+ *   row_fill, col_fill  row_fill[y] = the content pixels of row y, col_fill[x] = the content pixels of column x, n_content = their total.
+ *   content row      row_fill[y] * 1000000 > min_fill_ppm * aw, in unsigned 64-bit integers (strict); content column: col_fill[x] *
+ *                    1000000 > min_fill_ppm * ah; min_fill_ppm in 0..1000000.
+ *   box              {x0, y0, x1, y1}: x0 = the first content column, x1 = the last content column + 1; y0, y1 the same from the
+ *                    content rows.  Without a content row or without a content column the box is {0, 0, 0, 0}, and the call still
+ *                    returns SLIDEO_OK.
+ * It is an estimator with an exact definition, not a detector: no default level, share or fill is chosen here, and nothing is
+ * installed.  It finds an axis-aligned box on dark surroundings only: not a keystoned screen, not a sub-window on a background that is
+ * not black, and a dark-theme slide whose rows are mostly unlit needs a low min_fill or is not found (docs/EXTENSIONS.md "Frame
+ * content box" says on what content it was tried).  There is no group form: the pre-pass runs on slideo_group_member(g, 0), as the
+ * activity map's does; the box goes through slideo_frame_region_from_quad (corners at the pixel centres (x0, y0), (x1 - 1, y0),
+ * (x1 - 1, y1 - 1), (x0, y1 - 1), the output x1 - x0 by y1 - y0) to slideo_matcher_set_frame_region / slideo_group_set_frame_region.
+ * Observing: there is no observe call of its own.  The four slideo_matcher_observe_frames_* calls feed EVERY open accumulator.  With
+ * only an activity session open they launch exactly what they launched before; with neither open they return SLIDEO_ERR_STATE;
+ * with only a content session open content_kernel runs alone (no carried image, `pairs` untouched); with both open every check of
+ * both (the analysed size against each accumulator's, the pairs and the frames limits) comes before the first write, the message
+ * names the accumulator that refused, and an argument, size or state error leaves both as they were.  A device (HIP) error in the
+ * middle of a call ends both.  The two sessions begin and end independently; the staging buffer they share is released when the
+ * last of them ends.
+ * Where it runs (csrc/stage_content.hip, csrc/content.hip.h): content_kernel once per staged block on slot 0's stream, directly
+ * behind or in place of activity_kernel on the same staged frames — a thread owns 4 pixels of a row, walks the block's frames with
+ * its four counts in registers and ends with one read-modify-write of them: no atomic, no LDS —; the read-out is
+ * content_fill_kernel (a thread owns a column over a strip of rows; wave ballots, integer atomics) and a host scan of the two fill
+ * arrays.
+ * Every call returns SLIDEO_ERR_INVALID_ARG for a null handle or a null required pointer. */
+/* Idle matcher (SLIDEO_ERR_STATE otherwise).  level outside 0..254 is SLIDEO_ERR_INVALID_ARG and the state before stays.  Afterwards
+ * the accumulator is empty: no size, frames 0.  May be called before any page is added and before finalize. */
+int32_t     slideo_matcher_content_begin(slideo_matcher* m, int32_t level);
+/* Idle matcher.  The state "none"; the accumulator's device buffers are released.  Fine when the state is "none" already. */
+int32_t     slideo_matcher_content_end(slideo_matcher* m);
+/* The accumulator's analysed size (*aw == 0 before the first frame), frames and level.  SLIDEO_ERR_STATE in the state "none". */
+int32_t     slideo_matcher_content_info(slideo_matcher* m, int32_t* aw, int32_t* ah, int32_t* frames, int32_t* level);
+/* Idle matcher.  The lit counts, ah rows of aw elements (the tap the tests hold the kernel to).  SLIDEO_ERR_STATE without an observed
+ * frame; SLIDEO_ERR_CAPACITY (with *aw, *ah, *frames set) when aw * ah > capacity_elems; out == NULL asks for the sizes only. */
+int32_t     slideo_matcher_content_counts(slideo_matcher* m, uint32_t* out, int64_t capacity_elems, int32_t* aw, int32_t* ah, int32_t* frames);
+/* Idle matcher.  The box of the definition (4 values) and n_content; fill_out, when not NULL, receives the ah row fills, then the aw
+ * column fills.  SLIDEO_ERR_STATE while frames == 0; SLIDEO_ERR_INVALID_ARG for min_share_ppm or min_fill_ppm outside 0..1000000;
+ * SLIDEO_ERR_CAPACITY when fill_out is given and ah + aw > fill_capacity_elems. */
+int32_t     slideo_matcher_content_box(slideo_matcher* m, int32_t min_share_ppm, int32_t min_fill_ppm, int32_t* box /*4*/,
+                                       int64_t* n_content, uint32_t* fill_out /*nullable: ah row fills, then aw column fills*/,
+                                       int64_t fill_capacity_elems);
 
 #ifdef __cplusplus
 }

@@ -185,6 +185,8 @@ EXPORTS = [
     "slideo_matcher_activity_begin", "slideo_matcher_activity_end", "slideo_matcher_observe_frames_bgr8", "slideo_matcher_observe_frames_yuv420",
     "slideo_matcher_observe_frames_bgr8_dev", "slideo_matcher_observe_frames_yuv420_dev", "slideo_matcher_activity_info",
     "slideo_matcher_activity_counts", "slideo_matcher_activity_mask",
+    "slideo_matcher_content_begin", "slideo_matcher_content_end", "slideo_matcher_content_info", "slideo_matcher_content_counts",
+    "slideo_matcher_content_box",
     "slideo_matcher_set_gate_reference", "slideo_matcher_gate_reference", "slideo_group_set_gate_reference", "slideo_small_gram_ssd",
 ]
 
@@ -306,6 +308,13 @@ def lib():
             L.slideo_matcher_activity_info.argtypes = [vp, vp, vp, vp, vp]
             L.slideo_matcher_activity_counts.argtypes = [vp, vp, i64, vp, vp, vp]
             L.slideo_matcher_activity_mask.argtypes = [vp, i32, i32, vp, i64, vp, vp, vp, vp]
+        if hasattr(L, "slideo_matcher_content_begin"):
+            vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
+            L.slideo_matcher_content_begin.argtypes = [vp, i32]
+            L.slideo_matcher_content_end.argtypes = [vp]
+            L.slideo_matcher_content_info.argtypes = [vp, vp, vp, vp, vp]
+            L.slideo_matcher_content_counts.argtypes = [vp, vp, i64, vp, vp, vp]
+            L.slideo_matcher_content_box.argtypes = [vp, i32, i32, vp, vp, vp, i64]
         if hasattr(L, "slideo_matcher_set_gate_reference"):
             vp, i32, u32 = C.c_void_p, C.c_int32, C.c_uint32
             L.slideo_matcher_set_gate_reference.argtypes = [vp, u32]
@@ -902,6 +911,38 @@ class Matcher(_FrameCalls):
         self._check(lib().slideo_matcher_activity_mask(self._h, int(round(float(max_share) * 1000000)), int(grow), _p(out), C.c_int64(out.size),
                                                        C.byref(aw), C.byref(ah), C.byref(na), C.byref(nm)))
         return out, na.value, nm.value
+
+    # ---- frame content box (include/slideo_amd.h "Frame content box") --------------------------
+    def content_begin(self, level):
+        """An empty content accumulator: a pixel of an observed image is lit iff max(B, G, R) > level.  observe_frames* feed it."""
+        self._check(lib().slideo_matcher_content_begin(self._h, int(level)))
+
+    def content_end(self):
+        self._check(lib().slideo_matcher_content_end(self._h))
+
+    def content_info(self):
+        """-> {aw, ah, frames, level} (aw == 0 before the first observed frame)."""
+        aw, ah, frames, level = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+        self._check(lib().slideo_matcher_content_info(self._h, C.byref(aw), C.byref(ah), C.byref(frames), C.byref(level)))
+        return {"aw": aw.value, "ah": ah.value, "frames": frames.value, "level": level.value}
+
+    def content_counts(self):
+        """-> (lit uint32 [ah, aw], frames)"""
+        aw, ah, frames = C.c_int32(), C.c_int32(), C.c_int32()
+        self._check(lib().slideo_matcher_content_counts(self._h, None, C.c_int64(0), C.byref(aw), C.byref(ah), C.byref(frames)))
+        out = np.empty((ah.value, aw.value), np.uint32)
+        self._check(lib().slideo_matcher_content_counts(self._h, _p(out), C.c_int64(out.size), C.byref(aw), C.byref(ah), C.byref(frames)))
+        return out, frames.value
+
+    def content_box(self, min_share, min_fill):
+        """min_share, min_fill: floats in [0, 1], rounded to parts per million -> ((x0, y0, x1, y1), n_content, row_fill uint32 [ah],
+        col_fill uint32 [aw])"""
+        i = self.content_info()
+        fill = np.empty(i["ah"] + i["aw"], np.uint32)
+        box, nc = (C.c_int32 * 4)(), C.c_int64()
+        self._check(lib().slideo_matcher_content_box(self._h, int(round(float(min_share) * 1000000)), int(round(float(min_fill) * 1000000)), box,
+                                                     C.byref(nc), _p(fill), C.c_int64(fill.size)))
+        return tuple(box), nc.value, fill[:i["ah"]].copy(), fill[i["ah"]:].copy()
 
     # ---- YUV 4:2:0 frames (include/slideo_amd.h "YUV 4:2:0 frames") ---------------------------
     def match_frames_yuv420_dev(self, dev_ptr, n, w, h, layout, frame_stride, stream=0):

@@ -12,6 +12,7 @@
 //   stage_gate.hip     changed-frame gate: gated units, the gate state and its entry points (kernels: gate.hip.h)
 //   stage_direct.hip   direct page look-up: the page operand, a gated unit's look-up, its entry points (kernels: direct.hip.h)
 //   stage_activity.hip frame activity map: the accumulator, the observe driver, its entry points (kernels: activity.hip.h)
+//   stage_content.hip  frame content box: the content accumulator, its launch behind the observe driver, its entry points (kernels: content.hip.h)
 //   stage_gate_anchor.hip  gate reference ANCHOR: a gated unit's pair table and walk, the setting and the tap (kernels: gate_anchor.hip.h)
 //   capi_taps.hip      debug taps of the parity tests
 //   capi_group.hip     the N-device group (slideo_group_*)
@@ -369,6 +370,13 @@ struct slideo_matcher {
     struct Activity { bool on = false; int aw = 0, ah = 0, delta = 0; int64_t pairs = 0; } activity;
     slideo::DevBuf d_act_count, d_act_last, d_act_stage, d_act_mask;
 
+    // frame content box (include/slideo_amd.h "Frame content box"): the content accumulator — "none" (on false), empty (aw 0) or the
+    // lit counts of `frames` aw x ah analysed images — and its device buffers: the counts (u32) and the read-out's {n_content | row
+    // fills | column fills}.  The observe calls feed it beside the activity accumulator, from the same staged block (d_act_stage,
+    // released when the last of the two ends)
+    struct Content { bool on = false; int aw = 0, ah = 0, level = 0; int64_t frames = 0; } content;
+    slideo::DevBuf d_cnt_lit, d_cnt_fill;
+
     // direct page look-up (include/slideo_amd.h "Direct page look-up"): built at the first use with fs.direct_t > 0 after finalize, the
     // deck's size classes
     bool direct_built = false;
@@ -428,6 +436,9 @@ void settings_commit(slideo_matcher* m, Setting what, FrameSettings next, const 
 // frames slideo_changed_mask_bgr8 kept for slideo_match_kept_frames.
 // into: the staging buffer in place of S.d_stage (a gated unit's S.d_gstage; the kept frames of a mask call then stay).
 DevFrames stage_frames(slideo_matcher* m, Slot& S, const FrameSrc& src, int first, int n, hipStream_t cs = nullptr, DevBuf* into = nullptr);
+// stage_content.hip: content_kernel over a staged block of n frames into m's content accumulator (m->content.on; d_cnt_lit holds
+// f.w x f.h counts), on `st`.  Called by the observe driver (stage_activity.hip) behind or in place of activity_kernel.
+void content_launch(slideo_matcher* m, const DevFrames& f, int n, hipStream_t st);
 void upload_rng_stream(slideo_matcher* m, uint32_t len);
 // mask_pyr: the frame mask pyramid of the unit (FramePlan::mask_pyr), kept in S.u_mask
 void unit_submit(slideo_matcher* m, Slot& S, const DevFrames& f, int n, const uint8_t* mask_pyr, bool allow_async = true);

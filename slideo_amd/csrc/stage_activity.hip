@@ -1,6 +1,8 @@
 // stage_activity.hip — the frame activity map of include/slideo_amd.h "Frame activity map": the accumulator's entry points and the
 // observe driver (kernels: activity.hip.h).  Observing stages frames as every frame call does (stage_frames) but into a buffer of
 // the accumulator's own, and touches nothing else of the matcher: no setting, no gate state, not the frames a mask call kept.
+// The observe driver feeds every open accumulator: the activity map's here and, through content_launch (stage_content.hip), the
+// content box's (include/slideo_amd.h "Frame content box"), from the same staged block.
 #include "runtime.hpp"
 #include "activity.hip.h"
 
@@ -30,15 +32,22 @@ void activity_observe(slideo_matcher* m, int n, FrameSrc src, hipStream_t user_s
     HIP_CHECK(hipSetDevice(m->device));
     require_idle(m);
     slideo_matcher::Activity& A = m->activity;
-    if (!A.on) fail(SLIDEO_ERR_STATE, "no activity accumulator: slideo_matcher_activity_begin first");
+    slideo_matcher::Content& K = m->content;               // (include/slideo_amd.h "Frame content box": the calls feed every open accumulator)
+    if (!A.on && !K.on) fail(SLIDEO_ERR_STATE, "no activity accumulator: slideo_matcher_activity_begin first");
     if (n == 0) return;
     const int aw = src.plan.uw, ah = src.plan.uh;
-    if (A.aw > 0 && (A.aw != aw || A.ah != ah))
+    // every check of both accumulators in front of the first write
+    if (A.on && A.aw > 0 && (A.aw != aw || A.ah != ah))
         fail(SLIDEO_ERR_STATE, "these frames are analysed at %dx%d, the activity accumulator holds %dx%d: slideo_matcher_activity_begin first", aw, ah,
              A.aw, A.ah);
-    const bool first = A.aw == 0;
-    const int64_t pairs = A.pairs + n - (first ? 1 : 0);
-    if (pairs > INT32_MAX) fail(SLIDEO_ERR_STATE, "%lld pairs would pass INT32_MAX: read the counts out and begin again", (long long)pairs);
+    if (K.on && K.aw > 0 && (K.aw != aw || K.ah != ah))
+        fail(SLIDEO_ERR_STATE, "these frames are analysed at %dx%d, the content accumulator holds %dx%d: slideo_matcher_content_begin first", aw, ah,
+             K.aw, K.ah);
+    const bool first = A.on && A.aw == 0, kfirst = K.on && K.aw == 0;
+    const int64_t pairs = A.pairs + n - (first ? 1 : 0), kframes = K.frames + n;
+    if (A.on && pairs > INT32_MAX) fail(SLIDEO_ERR_STATE, "%lld pairs would pass INT32_MAX: read the counts out and begin again", (long long)pairs);
+    if (K.on && kframes > INT32_MAX)
+        fail(SLIDEO_ERR_STATE, "%lld frames would pass INT32_MAX in the content accumulator: read the counts out and begin again", (long long)kframes);
 
     Slot& S = m->slots[0];
     hipStream_t st = S.st;
@@ -49,33 +58,40 @@ void activity_observe(slideo_matcher* m, int n, FrameSrc src, hipStream_t user_s
     const int block = per == 0 ? n : (int)std::min<size_t>({(size_t)n, std::max<size_t>(1, ACT_BLOCK_BYTES / per), (size_t)ACT_MAX_BLOCK});
     // every allocation in front of the first write: the counts and the carried image of a first frame, the largest block's staging
     if (first) { m->d_act_count.reserve(px * 4 + 16); m->d_act_last.reserve(px * 3 + 16); }
+    if (kfirst) m->d_cnt_lit.reserve(px * 4 + 16);
     if (!in_place) m->d_act_stage.reserve((size_t)block * px * 3 + 16);
     if (src.on_device && user_stream) {                    // the frames were produced on the caller's stream
         HIP_CHECK(hipEventRecord(S.ev_in, user_stream));
         HIP_CHECK(hipStreamWaitEvent(st, S.ev_in, 0));
     }
     if (first) HIP_CHECK(hipMemsetAsync(m->d_act_count.p, 0, px * 4, st));
-    bool have_prev = !first;
+    if (kfirst) HIP_CHECK(hipMemsetAsync(m->d_cnt_lit.p, 0, px * 4, st));
+    bool have_prev = A.on && !first;
     try {
         for (int i = 0; i < n; i += block) {
             const int nb = std::min(block, n - i);
             const DevFrames f = stage_frames(m, S, src, i, nb, nullptr, &m->d_act_stage);
             if (f.w != aw || f.h != ah) fail(SLIDEO_ERR_HIP, "internal: staged %dx%d images, the plan says %dx%d", f.w, f.h, aw, ah);
-            const ActivityArgs a = activity_args(f.p, f.frame_stride, f.stride, aw, ah, nb, A.delta, have_prev, m->d_act_last.as<uint8_t>(),
-                                                 m->d_act_count.as<uint32_t>());
-            activity_kernel<<<act_grid((aw + 3) / 4, ah), dim3(ACT_TX, ACT_TY), 0, st>>>(a);
-            check_launch("activity_kernel");
-            have_prev = true;
+            if (A.on) {
+                const ActivityArgs a = activity_args(f.p, f.frame_stride, f.stride, aw, ah, nb, A.delta, have_prev, m->d_act_last.as<uint8_t>(),
+                                                     m->d_act_count.as<uint32_t>());
+                activity_kernel<<<act_grid((aw + 3) / 4, ah), dim3(ACT_TX, ACT_TY), 0, st>>>(a);
+                check_launch("activity_kernel");
+                have_prev = true;
+            }
+            if (K.on) content_launch(m, f, nb, st);        // the same staged frames, directly behind
         }
         HIP_CHECK(hipStreamSynchronize(st));               // (the caller's frames are free again)
     } catch (...) {
-        // a device error in the middle of a call: blocks may have been counted that `pairs` does not know of.  The accumulator ends
-        // (the state "none"): a new begin is needed
+        // a device error in the middle of a call: blocks may have been counted that `pairs` and `frames` do not know of.  Both
+        // accumulators end (the state "none"): a new begin is needed
         (void)hipStreamSynchronize(st);
         m->activity = slideo_matcher::Activity{};
+        m->content = slideo_matcher::Content{};
         throw;
     }
-    A.aw = aw; A.ah = ah; A.pairs = pairs;
+    if (A.on) { A.aw = aw; A.ah = ah; A.pairs = pairs; }
+    if (K.on) { K.aw = aw; K.ah = ah; K.frames = kframes; }
 }
 
 }  // namespace
@@ -100,7 +116,8 @@ int32_t slideo_matcher_activity_end(slideo_matcher* m) {
     require_idle(m);
     HIP_CHECK(hipSetDevice(m->device));
     m->activity = slideo_matcher::Activity{};
-    m->d_act_count.release(); m->d_act_last.release(); m->d_act_stage.release(); m->d_act_mask.release();
+    m->d_act_count.release(); m->d_act_last.release(); m->d_act_mask.release();
+    if (!m->content.on) m->d_act_stage.release();          // (shared with the content accumulator: released when the last of the two ends)
     API_CATCH(m)
 }
 

@@ -260,6 +260,42 @@ def learn_frame_mask(matcher, frame_batches, *, delta, max_share, grow):
     return mask
 
 
+def learn_frame_region(matcher, frame_batches, *, level, min_share, min_fill, inset=0, out_size=None):
+    """A frame region learnt from letterbox bars (include/slideo_amd.h "Frame content box"): the content box of the host BGR batches
+    (each uint8 [n, h, w, 3], all of one frame size) — a pixel is lit while max(B, G, R) > level, content while lit in more than
+    `min_share` of the frames; a row or column is content while more than `min_fill` of it is —, shrunk by `inset` pixels on each
+    side.  `matcher`: a Matcher (of a Group: its member 0), idle; neither pages nor finalize are needed.  Returns (src_w, src_h, quad,
+    out_w, out_h) — what frame_region= and Matcher.set_frame_region take; quad: the box's corner pixel centres; out_size None: the
+    box's own size, the exact crop.  Nothing is installed.  ValueError when the box is empty or narrower than 2 pixels after the
+    inset, or when the frames were not analysed at their own size (a working size reduced them, or a frame region is set): the box
+    is then not in source coordinates.  level, min_share and min_fill have no default: they depend on the content
+    (docs/EXTENSIONS.md "Frame content box")."""
+    inset = int(inset)
+    if inset < 0:
+        raise ValueError("learn_frame_region: inset %d is negative" % inset)
+    size = None
+    matcher.content_begin(level)
+    try:
+        for batch in frame_batches:
+            if size is None and len(batch):
+                size = (int(np.shape(batch)[2]), int(np.shape(batch)[1]))
+            matcher.observe_frames(batch)
+        info = matcher.content_info()
+        box, _, _, _ = matcher.content_box(min_share, min_fill)
+    finally:
+        matcher.content_end()
+    if (info["aw"], info["ah"]) != size:
+        raise ValueError("learn_frame_region: the frames are %dx%d but were analysed at %dx%d (a working size reduced them, or a frame "
+                         "region is set): the box is not in source coordinates" % (size + (info["aw"], info["ah"])))
+    x0, y0, x1, y1 = box[0] + inset, box[1] + inset, box[2] - inset, box[3] - inset
+    if x1 - x0 < 2 or y1 - y0 < 2:
+        raise ValueError("learn_frame_region: the content box %s is empty or narrower than 2 pixels on a side after an inset of %d"
+                         % (tuple(box), inset))
+    out_w, out_h = (x1 - x0, y1 - y0) if out_size is None else (int(out_size[0]), int(out_size[1]))
+    quad = [(float(x0), float(y0)), (float(x1 - 1), float(y0)), (float(x1 - 1), float(y1 - 1)), (float(x0), float(y1 - 1))]
+    return size[0], size[1], quad, out_w, out_h
+
+
 def dedup_timeline(mappings: List[Matching]) -> List[Matching]:
     """lib.rs:229-244: stable sort by time, drop consecutive mappings with the same image."""
     mappings = sorted(mappings, key=lambda mm: mm.video_time)
