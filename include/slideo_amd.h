@@ -1040,7 +1040,7 @@ int32_t     slideo_group_match_changed_frames_yuv420(slideo_group* g, int32_t n_
  * halo that primes a shard cannot supply.  SLIDEO_GATE_PREVIOUS is always accepted.
  * Where it runs (csrc/gate_anchor.hip.h, csrc/stage_gate_anchor.hip; gate_unit_submit's one branch): the rule is sequential — a flag
  * decides what the next frame is compared with — so a unit of n frames computes every pair it could need at once: the frames'
- * centred operand (direct_centre_kernel, or direct_centre_valid_kernel under the gate's weights), frame_gram_kernel — <a'_i, a'_j>
+ * centred operand (direct_centre_kernel, its weighted instance under the gate's weights), frame_gram_kernel — <a'_i, a'_j>
  * for i < j on v_mfma_i32_32x32x32_i8, page_ssd_kernel's symmetric case, SSD = |a'_i|^2 + |a'_j|^2 - 2 <a'_i, a'_j> exact in
  * integers —, the n SSDs against the carried anchor (the shipped SSD launch; the only step that waits for the previous unit's
  * state), gate_anchor_kernel — one wave walks the table and writes what gate_kernel writes — and gate_anchor_state_kernel, which
@@ -1135,7 +1135,8 @@ int32_t     slideo_page_small_ssd(slideo_matcher* m, const uint8_t* small, int32
  * 4:2:0, synchronous and submit / collect calls, and the group for every member count.
  * Where it runs: the deck's page operand is NOT rebuilt and not copied.  With a'_m = a' at the valid bytes and 0 elsewhere, the sum
  * over the valid bytes of a' b' is <a'_m, b'> against the unmasked page operand, so page_ssd_kernel, direct_best_kernel and
- * direct_gate_kernel run unchanged; direct_centre_valid_kernel (csrc/direct.hip.h) writes the frames' operand as (x ^ 0x80) & w under
+ * direct_gate_kernel run unchanged; direct_centre_kernel's weighted instance (csrc/ssd_table.hip.h; written as
+ * direct_centre_valid_kernel, since merged into the one template) writes the frames' operand as (x ^ 0x80) & w under
  * the gate's byte weights with the norm over the valid bytes, and its store-less instance makes the pages' masked norms, one i64 per
  * page of the class, built in front of any change to the gate state at the first look-up (or tap) under a map and cached with the
  * class until the map changes (slideo_matcher_set_frame_mask, _set_frame_mask_scope, _set_working_size).  docs/EXTENSIONS.md "Direct

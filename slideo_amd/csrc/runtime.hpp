@@ -11,6 +11,8 @@
 //   stage_page_set.hip page sets: a subset's search operand built from the finalized deck (kernels: page_set.hip.h)
 //   stage_gate.hip     changed-frame gate: gated units, the gate state and its entry points (kernels: gate.hip.h)
 //   stage_direct.hip   direct page look-up: the page operand, a gated unit's look-up, its entry points (kernels: direct.hip.h)
+//   stage_ssd_table.hip  the SSD-table engine under the direct page look-up and the gate reference ANCHOR: the centred operand, the
+//                      table of dot products on the int8 matrix cores, the taps' validity map (kernels: ssd_table.hip.h)
 //   stage_activity.hip frame activity map: the accumulator, the observe driver, its entry points (kernels: activity.hip.h)
 //   stage_content.hip  frame content box: the content accumulator, its launch behind the observe driver, its entry points (kernels: content.hip.h)
 //   stage_gate_anchor.hip  gate reference ANCHOR: a gated unit's pair table and walk, the setting and the tap (kernels: gate_anchor.hip.h)
@@ -259,7 +261,7 @@ struct PageSet {
 constexpr int MAX_PAGE_SETS = 64;                 // live sets per matcher
 
 // Direct page look-up (include/slideo_amd.h "Direct page look-up"): one size class of the deck's small images as the page operand
-// of page_ssd_kernel (direct.hip.h: centred i8, MFMA tile order, rows padded to DIRECT_TILE, K to DIRECT_KGRAN)
+// of page_ssd_kernel (ssd_table.hip.h: centred i8, MFMA tile order, rows and K padded as ssd_rows_pad and ssd_kp say)
 struct DirectClass {
     int sw = 0, sh = 0;
     int np = 0, np_pad = 0;                       // pages of the class, padded to whole wave tiles
@@ -600,17 +602,20 @@ struct DirectFrameRec { unsigned long long ssd; int32_t page; bool direct; };
 uint32_t direct_rec_kept(const uint8_t* h_rec, int n);
 DirectFrameRec direct_rec_frame(const uint8_t* h_rec, int n, int i);
 
-// the operand layout of direct.hip.h (stage_direct.hip asserts it), for the units that launch on that operand without its kernels
-constexpr int DIRECT_OP_TILE = 64, DIRECT_OP_KGRAN = 128, DIRECT_OP_KCHUNK_MAX = 65536;
-int64_t direct_kp(int64_t L);               // bytes of an operand row for small images of L bytes
-int direct_rows_pad(int rows);              // operand rows for `rows` images
-// The centred operand `out` ([rows_pad][kp], direct.hip.h's layout) and the norms |x'|^2 of the n images of L bytes at
+// ---- stage_ssd_table.hip --------------------------------------------------------------------------
+int64_t ssd_kp(int64_t L);                  // bytes of an operand row for small images of L bytes
+int ssd_rows_pad(int rows);                 // operand rows for `rows` images
+// The centred operand `out` ([rows_pad][kp], ssd_table.hip.h's layout) and the norms |x'|^2 of the n images of L bytes at
 // src + (ofs ? ofs[row] : row * stride), on st.  weights (the gate's validity map): the operand zero at the masked bytes, the norms
 // over the valid ones; out null (weights only): the norms alone
-void launch_centre(const uint8_t* src, int64_t stride, const long long* ofs, int n, int rows_pad, int64_t L, int64_t kp, uint4* out,
-                   long long* norm, hipStream_t st, const uint8_t* weights = nullptr);
-// the K chunk of a grid over n x np rows
-int64_t direct_kchunk(int n, int np, int64_t kp);
+void ssd_operand_build(const uint8_t* src, int64_t stride, const long long* ofs, int n, int rows_pad, int64_t L, int64_t kp, uint4* out,
+                       long long* norm, hipStream_t st, const uint8_t* weights = nullptr);
+// dot[i * np + j] = <a'_i, b'_j> of the operands a (n rows) and b (np rows), on st (page_ssd_kernel); b null: the symmetric table of
+// a, dot[i * n + j] for i < j alone (frame_gram_kernel).  Launches only.
+void ssd_table_dots(const uint4* a, int n, const uint4* b, int np, int64_t kp, unsigned long long* dot, hipStream_t st);
+// the weights a tap sums under: null unless use_valid, then the matcher's validity map — SLIDEO_ERR_STATE when none is in force,
+// SLIDEO_ERR_INVALID_ARG when it is not sw x sh (`tap`: the name the message begins with)
+const uint8_t* tap_valid_weights(const slideo_matcher* m, const char* tap, bool use_valid, int sw, int sh);
 
 // ---- stage_gate_anchor.hip ------------------------------------------------------------------------
 // Where gate_anchor_unit writes a unit's decisions: gate_kernel's outputs — device flags, kept list and count, and the pinned

@@ -1,6 +1,6 @@
 // stage_direct.hip — the direct page look-up of include/slideo_amd.h "Direct page look-up": the deck's page operand (built at the
 // first use), a gated unit's look-up in front of the gate's kept list (stage_gate.hip drives it), the setting and the tap
-// (kernels: direct.hip.h).
+// (kernels: direct.hip.h; the operands and the table of dot products: stage_ssd_table.hip).
 #include "runtime.hpp"
 #include "direct.hip.h"
 
@@ -10,44 +10,10 @@ using namespace slideo;
 
 namespace slideo {
 
+// gate_ssd_threshold is the smallest SSD whose similarity is < t: the largest one with >= t is the SSD in front of it
 int64_t direct_ssd_threshold(float t, int64_t n) {
-    const int64_t max_ssd = (int64_t)255 * 255 * 3 * n;
-    auto ok = [&](int64_t s) { return changed_similarity((unsigned long long)s, (int)n) >= t; };
-    if (!ok(0)) return -1;
-    if (ok(max_ssd)) return max_ssd;
-    int64_t lo = 0, hi = max_ssd;                   // ok(lo), !ok(hi); the expression is monotone in the SSD
-    while (hi - lo > 1) {
-        const int64_t mid = lo + (hi - lo) / 2;
-        if (ok(mid)) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-static_assert(DIRECT_OP_TILE == DIRECT_TILE && DIRECT_OP_KGRAN == DIRECT_KGRAN && DIRECT_OP_KCHUNK_MAX == DIRECT_KCHUNK_MAX,
-              "runtime.hpp states the operand layout of direct.hip.h");
-
-int64_t direct_kp(int64_t L) { return cdiv64(L, DIRECT_KGRAN) * DIRECT_KGRAN; }
-int direct_rows_pad(int rows) { return cdiv(rows, DIRECT_TILE) * DIRECT_TILE; }
-
-// weights (the gate's validity map, SLIDEO_DIRECT_VALID; null: whole images): the operand zero at the masked bytes, the norms over
-// the valid ones; out null (weights only): the norms alone
-void launch_centre(const uint8_t* src, int64_t stride, const long long* ofs, int n, int rows_pad, int64_t L, int64_t kp, uint4* out,
-                   long long* norm, hipStream_t st, const uint8_t* weights) {
-    // 32-row tiles x K slices: about 2048 waves, a wave at least one group of four K steps; the norms are added to
-    const int tiles = rows_pad / 32;
-    const int ky = (int)std::max<int64_t>(1, std::min<int64_t>(cdiv64(512, tiles), cdiv64(kp / DIRECT_KGRAN, DIRECT_BLOCK / 64)));
-    HIP_CHECK(hipMemsetAsync(norm, 0, (size_t)n * 8, st));
-    unsigned long long* nrm = reinterpret_cast<unsigned long long*>(norm);
-    if (!weights) {
-        direct_centre_kernel<<<dim3(tiles, ky), DIRECT_BLOCK, 0, st>>>(src, stride, ofs, n, L, kp, out, nrm);
-        check_launch("direct_centre_kernel");
-    } else if (out) {
-        direct_centre_valid_kernel<true><<<dim3(tiles, ky), DIRECT_BLOCK, 0, st>>>(src, stride, ofs, n, L, kp, weights, out, nrm);
-        check_launch("direct_centre_valid_kernel");
-    } else {
-        direct_centre_valid_kernel<false><<<dim3(tiles, ky), DIRECT_BLOCK, 0, st>>>(src, stride, ofs, n, L, kp, weights, nullptr, nrm);
-        check_launch("direct_centre_valid_kernel (norms)");
-    }
+    const int64_t changed = gate_ssd_threshold(t, n);
+    return changed == INT64_MAX ? (int64_t)255 * 255 * 3 * n : changed - 1;
 }
 
 namespace {
@@ -68,14 +34,14 @@ void direct_build(slideo_matcher* m) {
         if (!c) {
             classes.emplace_back(new DirectClass());
             c = classes.back().get();
-            c->sw = pg.sw; c->sh = pg.sh; c->L = (int64_t)pg.sw * pg.sh * 3; c->kp = direct_kp(c->L);
+            c->sw = pg.sw; c->sh = pg.sh; c->L = (int64_t)pg.sw * pg.sh * 3; c->kp = ssd_kp(c->L);
         }
         c->pages.push_back(p);
     }
     DevBuf d_ofs;
     for (auto& k : classes) {
         DirectClass& c = *k;
-        c.np = (int)c.pages.size(); c.np_pad = direct_rows_pad(c.np);
+        c.np = (int)c.pages.size(); c.np_pad = ssd_rows_pad(c.np);
         std::vector<long long> ofs((size_t)c.np);
         std::vector<int32_t> all((size_t)c.np);
         for (int i = 0; i < c.np; ++i) { ofs[i] = small_ofs[c.pages[i]]; all[i] = i; }
@@ -87,8 +53,8 @@ void direct_build(slideo_matcher* m) {
         HIP_CHECK(hipMemcpyAsync(d_ofs.p, ofs.data(), ofs.size() * 8, hipMemcpyHostToDevice, st));
         HIP_CHECK(hipMemcpyAsync(c.d_pages.p, c.pages.data(), c.pages.size() * 4, hipMemcpyHostToDevice, st));
         HIP_CHECK(hipMemcpyAsync(c.d_all.p, all.data(), all.size() * 4, hipMemcpyHostToDevice, st));
-        launch_centre(m->d_page_small.as<uint8_t>(), 0, d_ofs.as<long long>(), c.np, c.np_pad, c.L, c.kp, c.d_op.as<uint4>(),
-                      c.d_norm.as<long long>(), st);
+        ssd_operand_build(m->d_page_small.as<uint8_t>(), 0, d_ofs.as<long long>(), c.np, c.np_pad, c.L, c.kp, c.d_op.as<uint4>(),
+                          c.d_norm.as<long long>(), st);
         HIP_CHECK(hipStreamSynchronize(st));                           // (ofs and d_ofs are reused by the next class)
     }
     m->direct_classes = std::move(classes);
@@ -122,8 +88,8 @@ const long long* direct_masked_norms(slideo_matcher* m, DirectClass& c) {
     DevBuf d_ofs;
     d_ofs.reserve((size_t)c.np * 8);
     HIP_CHECK(hipMemcpyAsync(d_ofs.p, ofs.data(), ofs.size() * 8, hipMemcpyHostToDevice, st));
-    launch_centre(m->d_page_small.as<uint8_t>(), 0, d_ofs.as<long long>(), c.np, c.np_pad, c.L, c.kp, nullptr, c.d_norm_v.as<long long>(), st,
-                  m->d_gate_w.as<uint8_t>());
+    ssd_operand_build(m->d_page_small.as<uint8_t>(), 0, d_ofs.as<long long>(), c.np, c.np_pad, c.L, c.kp, nullptr, c.d_norm_v.as<long long>(),
+                      st, m->d_gate_w.as<uint8_t>());
     HIP_CHECK(hipStreamSynchronize(st));
     c.norm_v_gen = m->fs.gate_map_gen;
     return c.d_norm_v.as<long long>();
@@ -147,39 +113,19 @@ const int32_t* direct_eligible(slideo_matcher* m, const DirectClass& c, int set,
     return ps.direct_elig.back()->d.as<int32_t>();
 }
 
-}  // namespace
-
-// K chunks of the grid: enough blocks for every CU to hold a few waves, chunks of whole granules and at most DIRECT_KCHUNK_MAX
-int64_t direct_kchunk(int n, int np, int64_t kp) {
-    const int64_t tiles = (int64_t)cdiv(n, DIRECT_TILE) * cdiv(np, DIRECT_TILE);
-    const int64_t want = std::max<int64_t>(1, cdiv64(1024, tiles));    // waves wanted / tiles
-    int64_t chunk = cdiv64(cdiv64(kp, want), DIRECT_KGRAN) * DIRECT_KGRAN;
-    chunk = std::max<int64_t>(chunk, 8 * DIRECT_KGRAN);
-    return std::min<int64_t>(chunk, DIRECT_KCHUNK_MAX);
-}
-
-namespace {
-
 // the slot's workspaces for n small images against class c
 void direct_reserve(Slot& S, const DirectClass& c, int n) {
-    S.d_dir_a.reserve((size_t)direct_rows_pad(n) * (size_t)c.kp);
+    S.d_dir_a.reserve((size_t)ssd_rows_pad(n) * (size_t)c.kp);
     S.d_dir_rec.reserve((size_t)n * (8 + sizeof(DirectBest)));
     S.d_dir_dot.reserve((size_t)n * c.np * 8);
 }
 
 // n small images at `small` (stride L, device) against class c: S.d_dir_a, S.d_dir_rec's norms and S.d_dir_dot (direct_reserve)
 // filled on st
-// (weights: the gate's validity map, the frames' operand masked; null: today's launch)
+// (weights: the gate's validity map, the frames' operand masked; null: whole images)
 void direct_dots(Slot& S, const DirectClass& c, const uint8_t* small, int n, hipStream_t st, const uint8_t* weights) {
-    const int n_pad = direct_rows_pad(n);
-    launch_centre(small, c.L, nullptr, n, n_pad, c.L, c.kp, S.d_dir_a.as<uint4>(), S.d_dir_rec.as<long long>(), st, weights);
-    HIP_CHECK(hipMemsetAsync(S.d_dir_dot.p, 0, (size_t)n * c.np * 8, st));
-    const int64_t kchunk = direct_kchunk(n, c.np, c.kp);
-    const int64_t nz = cdiv64(c.kp, kchunk);
-    if (kchunk > DIRECT_KCHUNK_MAX || kchunk % DIRECT_KGRAN || nz > 65535) fail(SLIDEO_ERR_HIP, "internal: K chunk %lld of %lld", (long long)kchunk, (long long)c.kp);
-    page_ssd_kernel<<<dim3(cdiv(n, 2 * DIRECT_TILE), cdiv(c.np, 2 * DIRECT_TILE), (unsigned)nz), DIRECT_BLOCK, 0, st>>>(
-        S.d_dir_a.as<uint4>(), n, c.d_op.as<uint4>(), c.np, c.kp, kchunk, S.d_dir_dot.as<unsigned long long>());
-    check_launch("page_ssd_kernel");
+    ssd_operand_build(small, c.L, nullptr, n, ssd_rows_pad(n), c.L, c.kp, S.d_dir_a.as<uint4>(), S.d_dir_rec.as<long long>(), st, weights);
+    ssd_table_dots(S.d_dir_a.as<uint4>(), n, c.d_op.as<uint4>(), c.np, c.kp, S.d_dir_dot.as<unsigned long long>(), st);
 }
 
 DirectBest* direct_best_of(Slot& S, int n) { return reinterpret_cast<DirectBest*>(S.d_dir_rec.as<uint8_t>() + (size_t)n * 8); }
@@ -266,15 +212,7 @@ static void page_small_ssd_impl(slideo_matcher* m, const uint8_t* small, int32_t
     if (n < 0 || sw < 1 || sh < 1 || (int64_t)sw * sh > m->cfg.small_area || (n > 0 && (!small || !ssd_out)))
         fail(SLIDEO_ERR_INVALID_ARG, "page_small_ssd: %d small images of %dx%d (at most small_area = %d pixels), small and ssd_out not null", n, sw, sh,
              m->cfg.small_area);
-    const uint8_t* weights = nullptr;
-    if (valid) {
-        const GateMap& g = m->fs.gate_map;
-        if (!g.on)
-            fail(SLIDEO_ERR_STATE, "page_small_ssd_valid: no validity map is in force (a frame mask under SLIDEO_MASK_GATE)");
-        if (sw != g.sw || sh != g.sh)
-            fail(SLIDEO_ERR_INVALID_ARG, "page_small_ssd_valid: %dx%d small images, the validity map is %dx%d", sw, sh, g.sw, g.sh);
-        weights = m->d_gate_w.as<uint8_t>();
-    }
+    const uint8_t* weights = tap_valid_weights(m, "page_small_ssd_valid", valid, sw, sh);
     HIP_CHECK(hipSetDevice(m->device));
     require_idle(m);
     if (n == 0) return;

@@ -1,7 +1,8 @@
 // stage_gate_anchor.hip — the gate reference SLIDEO_GATE_ANCHOR of include/slideo_amd.h "Gate reference": a gated unit's pair table
 // and walk (stage_gate.hip's gate_unit_submit drives it), the setting and the tap (kernels: gate_anchor.hip.h).  The centred
-// operand is the direct page look-up's (stage_direct.hip launch_centre); a unit that also looks pages up builds it twice, each
-// into its own workspace: the look-up's is made inside direct_unit_lookup, behind the write of the gate state.
+// operand and the pair table are the SSD-table engine's (stage_ssd_table.hip), as the direct page look-up's are; a unit that also
+// looks pages up builds the operand twice, each into its own workspace: the look-up's is made inside direct_unit_lookup, behind the
+// write of the gate state.
 #include "runtime.hpp"
 #include "gate_anchor.hip.h"
 
@@ -10,9 +11,6 @@
 using namespace slideo;
 
 namespace slideo {
-
-static_assert(GRAM_TILE == DIRECT_OP_TILE && GRAM_KGRAN == DIRECT_OP_KGRAN && GRAM_KCHUNK_MAX == DIRECT_OP_KCHUNK_MAX,
-              "frame_gram_kernel reads the operand of direct.hip.h");
 
 namespace {
 
@@ -23,24 +21,17 @@ int32_t* ga_anchor(Slot& S, int n) { return reinterpret_cast<int32_t*>(S.d_ga_re
 
 // operand, norms and the table dot[i * n + j], i < j, of the n small images at `small` (stride sb = L bytes), on st
 void gram_launch(Slot& S, const uint8_t* weights, const uint8_t* small, int64_t L, int n, hipStream_t st) {
-    const int64_t kp = direct_kp(L);
-    const int n_pad = direct_rows_pad(n);
-    launch_centre(small, L, nullptr, n, n_pad, L, kp, S.d_ga_a.as<uint4>(), ga_norm(S), st, weights);
-    HIP_CHECK(hipMemsetAsync(S.d_ga_dot.p, 0, (size_t)n * n * 8, st));
-    const int64_t kchunk = direct_kchunk(n, n, kp);
-    const int64_t nz = cdiv64(kp, kchunk);
-    if (kchunk > GRAM_KCHUNK_MAX || kchunk % GRAM_KGRAN || nz > 65535) fail(SLIDEO_ERR_HIP, "internal: K chunk %lld of %lld", (long long)kchunk, (long long)kp);
-    const unsigned g = (unsigned)cdiv(n, 2 * GRAM_TILE);
-    frame_gram_kernel<<<dim3(g, g, (unsigned)nz), GRAM_BLOCK, 0, st>>>(S.d_ga_a.as<uint4>(), n, kp, kchunk, S.d_ga_dot.as<unsigned long long>());
-    check_launch("frame_gram_kernel");
+    const int64_t kp = ssd_kp(L);
+    ssd_operand_build(small, L, nullptr, n, ssd_rows_pad(n), L, kp, S.d_ga_a.as<uint4>(), ga_norm(S), st, weights);
+    ssd_table_dots(S.d_ga_a.as<uint4>(), n, nullptr, n, kp, S.d_ga_dot.as<unsigned long long>(), st);
 }
 
 }  // namespace
 
 void gate_anchor_reserve(Slot& S, int n, int sw, int sh) {
     if (n < 1 || n > GATE_ANCHOR_MAX_UNIT) fail(SLIDEO_ERR_CAPACITY, "a gated unit under SLIDEO_GATE_ANCHOR holds at most %d frames (%d)", GATE_ANCHOR_MAX_UNIT, n);
-    const int64_t kp = direct_kp((int64_t)sw * sh * 3);
-    S.d_ga_a.reserve((size_t)direct_rows_pad(n) * (size_t)kp);
+    const int64_t kp = ssd_kp((int64_t)sw * sh * 3);
+    S.d_ga_a.reserve((size_t)ssd_rows_pad(n) * (size_t)kp);
     S.d_ga_rec.reserve((size_t)n * 16 + 16);
     S.d_ga_dot.reserve((size_t)n * n * 8);
 }
@@ -81,13 +72,7 @@ int32_t slideo_small_gram_ssd(slideo_matcher* m, const uint8_t* small, int32_t n
     if (n < 0 || n > GATE_ANCHOR_MAX_UNIT || sw < 1 || sh < 1 || (int64_t)sw * sh > m->cfg.small_area || (n > 0 && (!small || !ssd_out)))
         fail(SLIDEO_ERR_INVALID_ARG, "small_gram_ssd: %d small images (at most %d) of %dx%d (at most small_area = %d pixels), small and ssd_out not null", n,
              GATE_ANCHOR_MAX_UNIT, sw, sh, m->cfg.small_area);
-    const uint8_t* weights = nullptr;
-    if (use_valid) {
-        const GateMap& g = m->fs.gate_map;
-        if (!g.on) fail(SLIDEO_ERR_STATE, "small_gram_ssd: no validity map is in force (a frame mask under SLIDEO_MASK_GATE)");
-        if (sw != g.sw || sh != g.sh) fail(SLIDEO_ERR_INVALID_ARG, "small_gram_ssd: %dx%d small images, the validity map is %dx%d", sw, sh, g.sw, g.sh);
-        weights = m->d_gate_w.as<uint8_t>();
-    }
+    const uint8_t* weights = tap_valid_weights(m, "small_gram_ssd", use_valid != 0, sw, sh);
     HIP_CHECK(hipSetDevice(m->device));
     require_idle(m);
     if (n == 0) return SLIDEO_OK;

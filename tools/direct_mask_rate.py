@@ -18,7 +18,7 @@ alternated repeats, min / median / max:
 
 Prints one line per measurement and a JSON line at the end.  --kernels-only: the gated stream twice as (b) and twice without a
 mask under SLIDEO_DIRECT_WHOLE at the same t, and nothing else, for a profiler's kernel trace of its own
-(direct_centre_valid_kernel beside direct_centre_kernel on the same units).  --step-only: the gated stream as (a) alone, through no
+(the weighted direct_centre_kernel instances beside the unweighted one on the same units).  --step-only: the gated stream as (a) alone, through no
 call an older library lacks (SLIDEO_LIB_PATH: the parent commit's build, interleaved process by process as tools/ab_libs.sh does)."""
 import argparse
 import json

@@ -11,7 +11,7 @@ d=open('$tmp/fat.bin','rb').read(); i=d.find(b'\x7fELF'); open('$tmp/co.elf','wb
     /opt/rocm/lib/llvm/bin/llvm-objdump -d --mcpu=gfx950 $tmp/co.elf 2>/dev/null | sed 's/\/\/.*//' | grep -v "file format" > $2
 }
 rc=0
-for st in stage_orb stage_knn stage_verify stage_sift stage_page_set stage_gate stage_direct stage_activity stage_gate_anchor capi_runtime; do
+for st in stage_orb stage_knn stage_verify stage_sift stage_page_set stage_gate stage_direct stage_ssd_table stage_activity stage_gate_anchor stage_content capi_runtime; do
     dis $other/$st.o $tmp/a.s; dis $mine/$st.o $tmp/b.s
     ha=$(md5sum < $tmp/a.s | cut -c1-32); hb=$(md5sum < $tmp/b.s | cut -c1-32)
     n=$(grep -c '^[0-9a-f]* <' $tmp/b.s)
