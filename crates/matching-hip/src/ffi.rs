@@ -487,6 +487,10 @@ extern "C" {
     pub fn slideo_matcher_set_gate_reference(m: *mut slideo_matcher, reference: u32) -> i32;
     pub fn slideo_matcher_gate_reference(m: *const slideo_matcher, reference: *mut u32) -> i32;
     pub fn slideo_group_set_gate_reference(g: *mut slideo_group, reference: u32) -> i32;
+    // gate settle (include/slideo_amd.h "Gate settle"): under SLIDEO_GATE_ANCHOR, (settle_similarity, max_defer); 0: off
+    pub fn slideo_matcher_set_gate_settle(m: *mut slideo_matcher, settle_similarity: f32, max_defer: i32) -> i32;
+    pub fn slideo_matcher_gate_settle(m: *const slideo_matcher, settle_similarity: *mut f32, max_defer: *mut i32) -> i32;
+    pub fn slideo_group_set_gate_settle(g: *mut slideo_group, settle_similarity: f32, max_defer: i32) -> i32;
     pub fn slideo_small_gram_ssd(
         m: *mut slideo_matcher,
         small: *const u8,

@@ -100,6 +100,21 @@ pub struct HipImageVideoMatcher {
     /// spread over many frames is still flagged when every decoded frame is fed).  One device only: a group of several
     /// refuses SLIDEO_GATE_ANCHOR when it is built.
     pub gate_reference: u32,
+    /// (settle_similarity, max_defer): the gate settle (slideo_group_set_gate_settle), under ffi::SLIDEO_GATE_ANCHOR only: a
+    /// frame away from the last matched frame is matched once it is within settle_similarity of the frame before it, or after
+    /// max_defer deferred frames; a deferred frame is reported as unchanged.  (0.0, 0): off, the default.
+    pub gate_settle: (f32, i32),
+}
+
+impl HipImageVideoMatcher {
+    /// Builder: the gate settle under the anchor reference (sets gate_reference to ffi::SLIDEO_GATE_ANCHOR when it switches one on).
+    pub fn gate_settle(mut self, settle_similarity: f32, max_defer: i32) -> Self {
+        if settle_similarity > 0.0 {
+            self.gate_reference = ffi::SLIDEO_GATE_ANCHOR;
+        }
+        self.gate_settle = (settle_similarity, max_defer);
+        self
+    }
 }
 
 impl Default for HipImageVideoMatcher {
@@ -114,6 +129,7 @@ impl Default for HipImageVideoMatcher {
             frame_region: None,
             yuv_description: (ffi::SLIDEO_YUV_MATRIX_BT601, ffi::SLIDEO_YUV_RANGE_LIMITED, ffi::SLIDEO_YUV_DEPTH_8),
             gate_reference: ffi::SLIDEO_GATE_PREVIOUS,
+            gate_settle: (0.0, 0),
         }
     }
 }
@@ -139,6 +155,9 @@ impl<'i> ImageVideoMatcher<'i> for HipImageVideoMatcher {
             );
             if self.gate_reference != ffi::SLIDEO_GATE_PREVIOUS {
                 check(h, ffi::slideo_group_set_gate_reference(h, self.gate_reference));
+            }
+            if self.gate_settle.0 != 0.0 {
+                check(h, ffi::slideo_group_set_gate_settle(h, self.gate_settle.0, self.gate_settle.1));
             }
             if let Some(ratio) = self.sift_ratio {
                 let mut sc = std::mem::MaybeUninit::<ffi::slideo_sift_config>::uninit();

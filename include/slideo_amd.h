@@ -1063,6 +1063,69 @@ int32_t     slideo_group_set_gate_reference(slideo_group* g, uint32_t ref);
 int32_t     slideo_small_gram_ssd(slideo_matcher* m, const uint8_t* small, int32_t n, int32_t sw, int32_t sh, int32_t use_valid,
                                   uint64_t* ssd_out);
 
+/* ---- Gate settle (extension: match a changed frame only once the picture stands still) -----------------------------------------
+ * Under SLIDEO_GATE_ANCHOR a cross-fade sends about every second frame of the fade through the pipeline, and every one of those
+ * verdicts is for a blend of two slides, which is no page at all.  A settle rule matches only the frame at which the change ends.
+ * A matcher carries a GATE SETTLE (settle_similarity, max_defer).  settle_similarity == 0 is off: the default, everything as
+ * before.  Otherwise 0 < settle_similarity <= 1 and 0 <= max_defer <= INT32_MAX; anything else is SLIDEO_ERR_INVALID_ARG and the
+ * value before stays.  Settle is meaningful under SLIDEO_GATE_ANCHOR only.  Everything is exact and in integers.
+ * The gate state under settle is "none", or three things: the anchor's small image, the previous gated frame's small image, and a
+ * deferral count d.  With f_0 .. f_{N-1} the frames of all gated calls and units since the last reset, in submission order, let
+ * T_c = slideo_changed_ssd_threshold[_n](cfg.changed_similarity, .) and T_s the same function of settle_similarity, both over the
+ * valid small pixels and n_valid under SLIDEO_MASK_GATE, exactly as ANCHOR does.
+ *   state "none"  f_0 has similarity 0.0, changed = 1, and becomes anchor and previous; d = 0.
+ *   otherwise     ssd_a is the SSD against the anchor in force before f_i is decided, ssd_p the SSD against the frame before it (for
+ *                 the first frame after a reset: the state's previous image); away = ssd_a >= T_c, still = ssd_p < T_s.
+ *                   !away:                                changed = 0, d = 0;
+ *                   away && (still || d >= max_defer):    changed = 1, the frame becomes the anchor, d = 0;
+ *                   away otherwise:                       changed = 0, d = min(d + 1, max_defer): the frame is DEFERRED.
+ *                 The frame becomes the previous frame in every case.
+ *   similarity    similarity[i] is the mask call's host expression of ssd_a, as under ANCHOR.  A deferred frame is therefore the one
+ *                 with changed == 0 && similarity < cfg.changed_similarity: no new output value, no new array.  changed_out stays
+ *                 0 / 1 and means "went through the pipeline and has a verdict".
+ *   records       a deferred frame's record is the unchanged record {-1, 0, 0, 0}; the kept list, the traces' indexing and the
+ *                 direct look-up see changed == 1 frames only.  Rules 2, 3, 4 and 6 of "Changed-frame gate" hold word for word.
+ *   independence  the result depends neither on unit or call boundaries nor on the number of units in flight.
+ *   state calls   slideo_matcher_gate_reset(S) and slideo_matcher_gate_reset_from_frame_* set anchor = previous = that image, d = 0;
+ *                 slideo_matcher_gate_last_small returns the anchor; anything that resets the gate state resets all three.
+ * Consequences.  With max_defer == 0 the rule is ANCHOR, bit for bit.  A change of any length gets a verdict at most max_defer
+ * frames after it began.  A hard cut is matched on the SECOND frame of the new hold (the first frame is away but not still), or
+ * on its first when max_defer == 0.  A stream sampled so sparsely that holds are one frame long never stands still: every verdict
+ * then comes max_defer frames late — such a stream wants settle off.  (tests/gate_settle_ref.py restates the rule in numpy.)
+ * The settle is part of the gate-reference frame setting: it changes on an idle matcher only (SLIDEO_ERR_STATE) and a change resets
+ * the gate state, also when the values do not change.  settle_similarity > 0 with a gate reference other than SLIDEO_GATE_ANCHOR is
+ * SLIDEO_ERR_UNSUPPORTED, whichever call would complete the combination — slideo_matcher_set_gate_settle under PREVIOUS, or
+ * slideo_matcher_set_gate_reference(PREVIOUS) while a settle is on —, and the values before stay in force.
+ * Group: a group of one member forwards the call.  With more members settle on is SLIDEO_ERR_UNSUPPORTED, checked before any member
+ * is touched; setting it off is always accepted.
+ * Where it runs (csrc/gate_settle.hip.h, csrc/stage_gate_settle.hip; one more branch of gate_unit_submit; with settle off every call
+ * launches exactly what it launched before): the unit's pair table as under ANCHOR, whose sub-diagonal gives ssd_p of frames
+ * 1 .. n - 1 for nothing; gate_carried_ssd_kernel — ONE launch behind the wait on the previous gated unit for the n SSDs against the
+ * carried anchor and frame 0's against the carried previous frame, every pair cut across several blocks that add their partial sums
+ * with one 64-bit atomic each —; gate_settle_kernel — one wave, two ballots per 64 frames: away, and from it every lane's deferral
+ * count, then the first matched lane —; gate_settle_state_kernel, which copies the unit's last anchor (if any) and its last frame
+ * into the state and stores d.  Every allocation happens before the first write of the gate state. */
+/* Idle matcher (SLIDEO_ERR_STATE otherwise).  Resets the gate state, also when the values do not change. */
+int32_t     slideo_matcher_set_gate_settle(slideo_matcher* m, float settle_similarity, int32_t max_defer);
+/* The matcher's gate settle (0, 0 unless set).  SLIDEO_ERR_INVALID_ARG for a null argument. */
+int32_t     slideo_matcher_gate_settle(const slideo_matcher* m, float* settle_similarity, int32_t* max_defer);
+/* Every member idle.  More than one member: settle_similarity > 0 is SLIDEO_ERR_UNSUPPORTED (above).  Resets the group's gate state. */
+int32_t     slideo_group_set_gate_settle(slideo_group* g, float settle_similarity, int32_t max_defer);
+/* Tap: gate_carried_ssd_kernel on its own.  anchor_small, prev_small: one small image of sw x sh each; small: n of them back to back
+ * (host memory; uploaded back to back behind the two, so odd sizes put the images at every byte alignment).  ssd_out [n + 1]:
+ * ssd_out[i] = the SSD of anchor_small and image i, ssd_out[n] = the SSD of prev_small and image 0 — over whole images, or,
+ * use_valid != 0, over the valid pixels of the matcher's current validity map (SLIDEO_ERR_STATE without one in force,
+ * SLIDEO_ERR_INVALID_ARG at another size).  Idle matcher; needs no pages.  1 <= n <= 1024, sw * sh <= small_area. */
+int32_t     slideo_small_carried_ssd(slideo_matcher* m, const uint8_t* anchor_small, const uint8_t* prev_small, const uint8_t* small, int32_t n,
+                                     int32_t sw, int32_t sh, int32_t use_valid, uint64_t* ssd_out);
+/* Tap: gate_settle_kernel on its own inputs.  dot [n * n]: <a'_i, a'_j>, read for i < j alone; norm [n]: |a'_i|^2; carried [n + 1]: the
+ * SSDs against the carried anchor, then frame 0's against the carried previous frame; thr_c, thr_s: T_c and T_s; d_in: the carried
+ * deferral count (0 <= d_in <= max_defer); none != 0: the state "none" (nothing carried is read).  changed_out [n], ssd_out [n] (ssd_a
+ * per frame), *anchor_out: the last matched frame or -1, *d_out: the count behind the unit.  Idle matcher.  1 <= n <= 1024. */
+int32_t     slideo_gate_settle_walk(slideo_matcher* m, const uint64_t* dot, const int64_t* norm, const uint64_t* carried, int32_t n, int64_t thr_c,
+                                    int64_t thr_s, int32_t max_defer, int32_t d_in, int32_t none, uint8_t* changed_out, uint64_t* ssd_out,
+                                    int32_t* anchor_out, int32_t* d_out);
+
 /* ---- Direct page look-up (extension: the reference never decides without keypoints) ---------------------------------------------
  * In a screen recording the frame IS the slide, full screen, plus codec noise.  The reference's final score for a candidate is
  * compute_similarity(to_small(warp(frame)), page.small); for such a frame the warp is the identity up to scale, so

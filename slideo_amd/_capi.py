@@ -188,6 +188,8 @@ EXPORTS = [
     "slideo_matcher_content_begin", "slideo_matcher_content_end", "slideo_matcher_content_info", "slideo_matcher_content_counts",
     "slideo_matcher_content_box",
     "slideo_matcher_set_gate_reference", "slideo_matcher_gate_reference", "slideo_group_set_gate_reference", "slideo_small_gram_ssd",
+    "slideo_matcher_set_gate_settle", "slideo_matcher_gate_settle", "slideo_group_set_gate_settle", "slideo_small_carried_ssd",
+    "slideo_gate_settle_walk",
 ]
 
 # frame mask scope (include/slideo_amd.h "Frame mask scope")
@@ -200,6 +202,13 @@ DIRECT_VALID = 1
 GATE_PREVIOUS = 0
 GATE_ANCHOR = 1
 GATE_REFERENCES = {"previous": GATE_PREVIOUS, "anchor": GATE_ANCHOR}
+
+
+def gate_deferred(changed, similarity, changed_similarity):
+    """The deferred frames of a gated call under a gate settle (include/slideo_amd.h "Gate settle"): away from the anchor and not
+    matched, changed == 0 && similarity < changed_similarity -> bool [n]."""
+    changed = np.asarray(changed).astype(bool)
+    return ~changed & (np.asarray(similarity, np.float32) < np.float32(changed_similarity))
 
 _lib = None
 
@@ -321,6 +330,13 @@ def lib():
             L.slideo_matcher_gate_reference.argtypes = [vp, vp]
             L.slideo_group_set_gate_reference.argtypes = [vp, u32]
             L.slideo_small_gram_ssd.argtypes = [vp, vp, i32, i32, i32, i32, vp]
+        if hasattr(L, "slideo_matcher_set_gate_settle"):
+            vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
+            L.slideo_matcher_set_gate_settle.argtypes = [vp, f32, i32]
+            L.slideo_matcher_gate_settle.argtypes = [vp, vp, vp]
+            L.slideo_group_set_gate_settle.argtypes = [vp, f32, i32]
+            L.slideo_small_carried_ssd.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp]
+            L.slideo_gate_settle_walk.argtypes = [vp, vp, vp, vp, i32, i64, i64, i32, i32, i32, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -520,6 +536,24 @@ class _FrameCalls:
         if rc != OK:
             raise SlideoError(rc, "gate_reference")
         return {v: k for k, v in GATE_REFERENCES.items()}[ref.value]
+
+    # gate settle (include/slideo_amd.h "Gate settle"): under 'anchor', match a changed frame only once the picture stands still
+    def set_gate_settle(self, similarity, max_defer):
+        """similarity: 0 (off, the default) or 0 < s <= 1: a frame away from the anchor is matched once it is within s of the frame
+        before it, or after max_defer (0 .. 2**31 - 1) deferred frames.  Needs the gate reference 'anchor'; the matcher must be idle;
+        resets the gate state.  A Group of more than one member refuses a settle that is on."""
+        max_defer = int(max_defer)
+        if not 0 <= max_defer <= 0x7FFFFFFF:
+            raise SlideoError(1, "gate settle: max_defer %d outside 0 .. 2**31 - 1" % max_defer)
+        self._check(getattr(lib(), self._SETS + "set_gate_settle")(self._h, C.c_float(similarity), max_defer))
+
+    def gate_settle(self):
+        """(similarity, max_defer); (0.0, 0) unless set (a Group: member 0's)."""
+        s, d = C.c_float(), C.c_int32()
+        rc = lib().slideo_matcher_gate_settle(self._mask_owner(), C.byref(s), C.byref(d))
+        if rc != OK:
+            raise SlideoError(rc, "gate_settle")
+        return s.value, d.value
 
     # YUV colour description (include/slideo_amd.h "YUV colour description"): how every *_yuv420 call reads its samples
     def set_yuv_description(self, matrix="bt601", range="limited", depth=8):
@@ -1156,6 +1190,37 @@ class Matcher(_FrameCalls):
         out = np.empty((n, n), np.uint64)
         self._check(lib().slideo_small_gram_ssd(self._h, _p(smalls), n, sw, sh, 1 if use_valid else 0, _p(out)))
         return out
+
+    def small_carried_ssd(self, anchor_small, prev_small, smalls, use_valid=False):
+        """slideo_small_carried_ssd: two small images [sh, sw, 3] and smalls uint8 [n, sh, sw, 3] -> uint64 [n + 1]: the integer SSD of
+        anchor_small against every image, then of prev_small against image 0; use_valid: over the valid pixels of the matcher's
+        current validity map.  The carried-SSD kernel of the gate settle; needs no pages."""
+        smalls = np.ascontiguousarray(smalls, np.uint8)
+        if smalls.ndim != 4 or smalls.shape[3] != 3 or len(smalls) < 1:
+            raise ValueError("expected [n >= 1, sh, sw, 3] uint8 small images")
+        n, sh, sw, _ = smalls.shape
+        a = np.ascontiguousarray(anchor_small, np.uint8)
+        p = np.ascontiguousarray(prev_small, np.uint8)
+        if a.shape != smalls.shape[1:] or p.shape != smalls.shape[1:]:
+            raise ValueError("anchor_small and prev_small have the small images' shape")
+        out = np.empty(n + 1, np.uint64)
+        self._check(lib().slideo_small_carried_ssd(self._h, _p(a), _p(p), _p(smalls), n, sw, sh, 1 if use_valid else 0, _p(out)))
+        return out
+
+    def gate_settle_walk(self, dot, norm, carried, thr_c, thr_s, max_defer, d_in=0, none=False):
+        """slideo_gate_settle_walk: dot [n, n] (<a'_i, a'_j>, read for i < j), norm int64 [n], carried uint64 [n + 1] ->
+        (changed uint8 [n], ssd uint64 [n], last matched frame or -1, the deferral count behind the unit)."""
+        norm = np.ascontiguousarray(norm, np.int64)
+        n = len(norm)
+        dot = np.ascontiguousarray(np.asarray(dot).astype(np.int64).view(np.uint64))
+        carried = np.ascontiguousarray(carried, np.uint64)
+        if dot.shape != (n, n) or carried.shape != (n + 1,):
+            raise ValueError("expected dot [n, n], norm [n], carried [n + 1]")
+        changed, ssd = np.zeros(n, np.uint8), np.zeros(n, np.uint64)
+        a, d = C.c_int32(), C.c_int32()
+        self._check(lib().slideo_gate_settle_walk(self._h, _p(dot), _p(norm), _p(carried), n, C.c_int64(int(thr_c)), C.c_int64(int(thr_s)),
+                                                  int(max_defer), int(d_in), 1 if none else 0, _p(changed), _p(ssd), C.byref(a), C.byref(d)))
+        return changed, ssd, a.value, d.value
 
     def small_image(self, bgr):
         bgr = _img3(bgr)

@@ -374,6 +374,16 @@ int32_t slideo_group_set_gate_reference(slideo_group* g, uint32_t ref) {
     });
 }
 
+// (the gate settle is part of the gate-reference setting; behind the range check the group's own rule: settle on needs a group of one
+// member, and a refused call changes no member)
+int32_t slideo_group_set_gate_settle(slideo_group* g, float settle_similarity, int32_t max_defer) {
+    return group_set(g, SET_GATE_REFERENCE, [&](const FrameSettings& s) {
+        const FrameSettings next = propose_gate_settle(s, settle_similarity, max_defer);
+        gate_settle_group_rule((int)g->members.size(), settle_similarity);
+        return next;
+    });
+}
+
 // Page sets: every member builds the same set from the same deck (ids are handed out in the same order: they agree)
 int32_t slideo_group_create_page_set(slideo_group* g, int32_t n_pages, const int32_t* pages, int32_t* set_out) {
     if (!g) return SLIDEO_ERR_INVALID_ARG;

@@ -1,5 +1,5 @@
 // frame_settings.h — the frame settings of a matcher as ONE record (include/slideo_amd.h "Working size", "Frame region", "Frame mask",
-// "Frame mask scope", "Direct page look-up", "Direct look-up scope", "YUV colour description", "Gate reference"): the record, every setter's proposal with its range checks, the
+// "Frame mask scope", "Direct page look-up", "Direct look-up scope", "YUV colour description", "Gate reference", "Gate settle"): the record, every setter's proposal with its range checks, the
 // rules between settings, what a change of each ends.  Plain C++, no HIP include (tools/frame_settings_hostcheck.cpp walks it on the
 // host); the device buffers a setting owns are the matcher's (runtime.hpp).  A change takes ONE path: settings_commit (capi_runtime.hip).
 #pragma once
@@ -45,6 +45,10 @@ struct FrameSettings {
     uint32_t direct_scope = SLIDEO_DIRECT_WHOLE;      // VALID = the look-up over the gate's valid pixels
     YuvDesc yuv;                                      // 4:2:0 frames stand for the BGR image under it (BGR calls never look at it)
     uint32_t gate_ref = SLIDEO_GATE_PREVIOUS;         // what a gated frame is compared with: the frame before it, or the last changed one (ANCHOR)
+    // the gate settle, part of the gate-reference setting ("Gate settle"): under ANCHOR a frame away from the anchor is matched once it
+    // is within settle_similarity of the frame before it, or after settle_max_defer deferred frames; 0: off
+    float settle_similarity = 0.f;
+    int32_t settle_max_defer = 0;
     bool gate_scope() const { return mask.set && (mask_scope & SLIDEO_MASK_GATE); }      // the gate compares under the mask
 };
 
@@ -129,6 +133,21 @@ inline FrameSettings propose_gate_reference(FrameSettings s, uint32_t ref) {
         fail(SLIDEO_ERR_INVALID_ARG, "gate reference %u: SLIDEO_GATE_PREVIOUS (0) or SLIDEO_GATE_ANCHOR (1)", ref);
     s.gate_ref = ref;
     return s;
+}
+// The gate settle commits under SET_GATE_REFERENCE: the state means something else, so the gate resets (its SETTING_ENDS row)
+inline FrameSettings propose_gate_settle(FrameSettings s, float settle_similarity, int32_t max_defer) {
+    if (!(settle_similarity >= 0.f) || settle_similarity > 1.f)
+        fail(SLIDEO_ERR_INVALID_ARG, "gate settle: settle_similarity %g: 0 (off) or 0 < s <= 1", (double)settle_similarity);
+    if (max_defer < 0) fail(SLIDEO_ERR_INVALID_ARG, "gate settle: max_defer %d: 0 <= max_defer <= INT32_MAX", max_defer);
+    s.settle_similarity = settle_similarity; s.settle_max_defer = max_defer;
+    return s;
+}
+// The group's rule for a gate settle (include/slideo_amd.h "Gate settle"): it needs ANCHOR, which needs a group of one member.
+// Setting it off always passes.
+inline void gate_settle_group_rule(int members, float settle_similarity) {
+    if (settle_similarity > 0.f && members > 1)
+        fail(SLIDEO_ERR_UNSUPPORTED, "a gate settle in a group of %d members: it runs under SLIDEO_GATE_ANCHOR, which a group of more than "
+             "one member does not support (a group of one member, or a single matcher)", members);
 }
 // The group's rule for a gate reference (include/slideo_amd.h "Gate reference"): a shard's anchor depends on every flag before the
 // shard, which the one-frame halo that primes a shard cannot supply, so ANCHOR needs a group of one member.  PREVIOUS always passes.
@@ -237,6 +256,11 @@ inline void frame_settings_rules(const FrameSettings& next, Setting what, bool s
     if (next.direct_t > 0.f && next.gate_scope() && next.direct_scope != SLIDEO_DIRECT_VALID)
         fail(SLIDEO_ERR_UNSUPPORTED, "the direct page look-up compares whole small images: not together with a frame mask under SLIDEO_MASK_GATE "
              "(a look-up over the valid pixels only: slideo_matcher_set_direct_scope(m, SLIDEO_DIRECT_VALID))");
+    // a gate settle defers frames that are away from the ANCHOR: it means nothing under PREVIOUS
+    if (next.settle_similarity > 0.f && next.gate_ref != SLIDEO_GATE_ANCHOR)
+        fail(SLIDEO_ERR_UNSUPPORTED, "gate settle under SLIDEO_GATE_ANCHOR only: a settle similarity %g with the gate reference SLIDEO_GATE_PREVIOUS "
+             "(slideo_matcher_set_gate_reference(m, SLIDEO_GATE_ANCHOR) first; slideo_matcher_set_gate_settle(m, 0, 0) before going back)",
+             (double)next.settle_similarity);
 }
 
 }  // namespace slideo

@@ -16,6 +16,7 @@
 //   stage_activity.hip frame activity map: the accumulator, the observe driver, its entry points (kernels: activity.hip.h)
 //   stage_content.hip  frame content box: the content accumulator, its launch behind the observe driver, its entry points (kernels: content.hip.h)
 //   stage_gate_anchor.hip  gate reference ANCHOR: a gated unit's pair table and walk, the setting and the tap (kernels: gate_anchor.hip.h)
+//   stage_gate_settle.hip  gate settle: a gated unit's carried SSDs, walk and state under a settle, the setting and the taps (kernels: gate_settle.hip.h)
 //   capi_taps.hip      debug taps of the parity tests
 //   capi_group.hip     the N-device group (slideo_group_*)
 //
@@ -188,6 +189,9 @@ struct Slot {
     // ... under SLIDEO_GATE_ANCHOR (stage_gate_anchor.hip): the frames' centred operand, {|a'|^2 n x i64 | SSDs against the carried
     // anchor n x u64 | the unit's last anchor i32}, and the n x n dot products (reserved by the first such unit only)
     DevBuf d_ga_a, d_ga_rec, d_ga_dot;
+    // ... under a gate settle (stage_gate_settle.hip): {SSDs against the carried anchor n x u64, frame 0 against the carried previous
+    // frame u64 | the unit's last anchor i32 | the deferral count behind the unit u32} (reserved by the first such unit only)
+    DevBuf d_gs_rec;
     hipEvent_t ev_gate = nullptr;             // the unit's small images are made and the gate state is this unit's last one
     struct GateUnit {
         bool on = false;                      // the unit in flight is gated: slideo_match_changed_frames_collect collects it
@@ -195,6 +199,7 @@ struct Slot {
         int sw = 0, sh = 0;
         int npx = 0;                          // the pixels the similarity is normalised over: sw * sh, the gate map's n_valid under one
         bool force0 = false;                  // no gate state at submission: frame 0 is changed, similarity 0.0
+        bool settle = false;                  // a gate settle was in force: a frame away from its anchor may be deferred (flag 0)
         // the direct page look-up ran for the unit (direct_t: the matcher's direct similarity at submission): k counts the changed
         // frames that are not direct, the record's tail (direct.hip.h direct_rec_*) is at direct_ofs; has_elig: a page was eligible
         bool direct = false, has_elig = false;
@@ -364,6 +369,9 @@ struct slideo_matcher {
         int sw = 0, sh = 0;                   // (has) the small image's size
     } gate;
     slideo::DevBuf d_gate_small;
+    // under a gate settle (include/slideo_amd.h "Gate settle") d_gate_small is the anchor's; beside it the small image of the
+    // previous gated frame and the deferral count (u32), written and read where d_gate_small is
+    slideo::DevBuf d_gate_prev, d_gate_d;
     hipEvent_t last_gate_ev = nullptr;
 
     // frame activity map (include/slideo_amd.h "Frame activity map"): the accumulator — "none" (on false), empty (aw 0) or the counts
@@ -546,10 +554,12 @@ inline void gate_state_reset(slideo_matcher* m) { m->gate = slideo_matcher::Gate
 // (under a direct similarity: + the frame's centred operand row, its row of dot products and its record; under the direct scope
 // VALID + the masked page norms, 8 bytes per page once per matcher: counted with every frame, a unit has at least one)
 // (under SLIDEO_GATE_ANCHOR: + the frame's centred operand row of the pair table, its norm, carried SSD and its row of the table —
-// 8 n bytes, n <= GATE_ANCHOR_MAX_UNIT)
+// 8 n bytes, n <= GATE_ANCHOR_MAX_UNIT; under a gate settle + the previous frame's small image and the count of the state, and
+// the unit's one more carried SSD: counted with every frame, a unit has at least one)
 inline size_t gate_small_budget(const slideo_matcher* m) {
     const size_t small = (size_t)m->cfg.small_area * 3 + 64;
-    const size_t anchor = m->fs.gate_ref == SLIDEO_GATE_ANCHOR ? small + 128 + 32 + (size_t)GATE_ANCHOR_MAX_UNIT * 8 : 0;
+    const size_t settle = m->fs.settle_similarity > 0.f ? small + 256 + 32 : 0;
+    const size_t anchor = m->fs.gate_ref == SLIDEO_GATE_ANCHOR ? small + 128 + 32 + (size_t)GATE_ANCHOR_MAX_UNIT * 8 + settle : 0;
     if (!(m->fs.direct_t > 0.f)) return small + anchor;
     const size_t look = 2 * small + 128 + m->pages.size() * 8 + 64 + anchor;
     return m->fs.direct_scope == SLIDEO_DIRECT_VALID ? look + m->pages.size() * 8 : look;
@@ -631,6 +641,22 @@ void gate_anchor_reserve(Slot& S, int n, int sw, int sh);
 // the new state written into m->d_gate_small.  Launches only.
 void gate_anchor_unit(slideo_matcher* m, Slot& S, const uint8_t* weights, const uint8_t* small, int64_t sb, int n, long long thr, bool force0,
                       hipEvent_t wait, const GateAnchorOut& out);
+// its first step alone: operand, norms (S.d_ga_rec's first n i64) and the table S.d_ga_dot[i * n + j], i < j, of the n small images at
+// `small` (L bytes each), on st; S reserved by gate_anchor_reserve
+void gram_launch(Slot& S, const uint8_t* weights, const uint8_t* small, int64_t L, int n, hipStream_t st);
+
+// ---- stage_gate_settle.hip ------------------------------------------------------------------------
+// a unit of n frames under a gate settle: gate_anchor_reserve, the settle's record of S and the matcher's previous-frame image and
+// deferral count for small images of sb bytes (everything that can fail for want of memory, in front of any write of the gate state)
+void gate_settle_reserve(slideo_matcher* m, Slot& S, int n, int sw, int sh);
+// gate_anchor_unit under a settle (m->fs.settle_similarity > 0; thr_s: its SSD threshold): the pair table, then behind `wait` ONE
+// launch for the n SSDs against the carried anchor and frame 0's against the carried previous frame, the settle walk, and the new
+// state — anchor, previous frame, deferral count.  Launches only.
+void gate_settle_unit(slideo_matcher* m, Slot& S, const uint8_t* weights, const uint8_t* small, int64_t sb, int n, long long thr, long long thr_s,
+                      bool force0, hipEvent_t wait, const GateAnchorOut& out);
+// the previous-frame image := the anchor's (m->d_gate_small, sb bytes) and the deferral count := 0, on st: what every reset of the
+// gate state to an image does under a settle
+void gate_settle_state_from_anchor(slideo_matcher* m, size_t sb, hipStream_t st);
 
 // ---- stage_sift.hip -------------------------------------------------------------------------------
 void sift_check_cfg(const slideo_sift_config* sc, int w, int h);

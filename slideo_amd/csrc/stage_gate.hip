@@ -1,7 +1,8 @@
 // stage_gate.hip — the changed-frame gate of include/slideo_amd.h "Changed-frame gate": gated units (small images of all frames, SSDs,
 // gate_kernel, gather_frames_kernel in front of the unchanged unit_submit), the gate state and its entry points (kernels: gate.hip.h).
 // The frame calls that run gated units are capi_runtime.hip's, beside their plain twins.  Under the gate reference SLIDEO_GATE_ANCHOR
-// gate_unit_submit hands the SSDs, the flags and the new state to stage_gate_anchor.hip (include/slideo_amd.h "Gate reference").
+// gate_unit_submit hands the SSDs, the flags and the new state to stage_gate_anchor.hip (include/slideo_amd.h "Gate reference"), under a
+// gate settle to stage_gate_settle.hip ("Gate settle").
 #include "runtime.hpp"
 #include "gate.hip.h"
 
@@ -102,6 +103,8 @@ void gate_prime(slideo_matcher* m, FrameSrc src, hipStream_t user_stream) {
     if (m->last_gate_ev && m->last_gate_ev != S.ev_gate) HIP_CHECK(hipStreamWaitEvent(st, m->last_gate_ev, 0));
     const DevFrames f = stage_frames(m, S, src, 0, 1, nullptr, &S.d_gstage);
     run_small_into(m, f, 1, m->d_gate_small, st);
+    // under a gate settle the frame is the anchor and the previous frame, nothing deferred
+    if (m->fs.settle_similarity > 0.f) gate_settle_state_from_anchor(m, (size_t)src.plan.sw * src.plan.sh * 3, st);
     HIP_CHECK(hipEventRecord(S.ev_gate, st));
     m->last_gate_ev = S.ev_gate;
     HIP_CHECK(hipStreamSynchronize(st));            // (the caller's frame is free again)
@@ -125,7 +128,10 @@ void gate_unit_submit(slideo_matcher* m, Slot& S, const FrameSrc& src, int first
     if (look) plan = direct_unit_prepare(m, S, n, sw, sh, m->fs.direct_scope == SLIDEO_DIRECT_VALID ? weights : nullptr);
     // under SLIDEO_GATE_ANCHOR: the pair table's workspaces, first for the same reason (include/slideo_amd.h "Gate reference")
     const bool anchor = m->fs.gate_ref == SLIDEO_GATE_ANCHOR;
-    if (anchor) gate_anchor_reserve(S, n, sw, sh);
+    // ... under a gate settle also the settle's record and the state's previous-frame image and count ("Gate settle")
+    const bool settle = anchor && m->fs.settle_similarity > 0.f;
+    if (settle) gate_settle_reserve(m, S, n, sw, sh);
+    else if (anchor) gate_anchor_reserve(S, n, sw, sh);
     const DevFrames all = stage_frames(m, S, src, first, n, cs, &S.d_gstage);
     run_small_into(m, all, n, S.d_gsmall, st);
     const int64_t sb = (int64_t)sw * sh * 3;
@@ -147,7 +153,9 @@ void gate_unit_submit(slideo_matcher* m, Slot& S, const FrameSrc& src, int first
         // (gate_kernel's outputs) and the new state: the unit's last flagged frame, if any
         const GateAnchorOut out{flags, idx, count, reinterpret_cast<uint32_t*>(hrec), reinterpret_cast<unsigned long long*>(hrec + gate_rec_ssd_ofs()),
                                 reinterpret_cast<int32_t*>(hrec + gate_rec_idx_ofs(n)), hrec + gate_rec_flag_ofs(n)};
-        gate_anchor_unit(m, S, weights, small, sb, n, thr, force0, m->last_gate_ev != S.ev_gate ? m->last_gate_ev : nullptr, out);
+        hipEvent_t wait = m->last_gate_ev != S.ev_gate ? m->last_gate_ev : nullptr;
+        if (settle) gate_settle_unit(m, S, weights, small, sb, n, thr, gate_ssd_threshold(m->fs.settle_similarity, npx), force0, wait, out);
+        else gate_anchor_unit(m, S, weights, small, sb, n, thr, force0, wait, out);
     } else {
         // pair i: (small[i - 1], small[i]); pair 0: (gate state, small[0]), behind the previous gated unit's write of the state
         if (n > 1) launch_gate_ssd(weights, small, sb, small + sb, sb, sb, ssd + 1, n - 1, st);
@@ -181,7 +189,7 @@ void gate_unit_submit(slideo_matcher* m, Slot& S, const FrameSrc& src, int first
         k = kept;
     }
     Slot::GateUnit gu;
-    gu.on = true; gu.n = n; gu.k = k; gu.sw = sw; gu.sh = sh; gu.npx = npx; gu.force0 = force0;
+    gu.on = true; gu.n = n; gu.k = k; gu.sw = sw; gu.sh = sh; gu.npx = npx; gu.force0 = force0; gu.settle = settle;
     gu.direct = direct; gu.direct_t = m->fs.direct_t; gu.direct_ofs = direct_ofs;
     if (k == 0) {                                   // no frame changed (or every changed one is direct): no pipeline; the collect returns at once
         S.busy = true; S.n = 0; S.u_async = false; S.timed = false;
@@ -220,7 +228,9 @@ void gate_unit_collect(slideo_matcher* m, Slot& S, uint8_t* changed_out, float* 
         unsigned long long s;
         std::memcpy(&s, rec + gate_rec_ssd_ofs() + (size_t)i * 8, 8);
         const float sim = (i == 0 && g.force0) ? 0.0f : changed_similarity(s, g.npx);      // video_capture.rs:92
-        if ((sim < m->cfg.changed_similarity) != (flag[i] != 0))
+        // (under a gate settle a frame away from its anchor may be deferred: flagged => away, and not away => not flagged)
+        const bool away = sim < m->cfg.changed_similarity;
+        if (g.settle ? (flag[i] != 0 && !away) || flag[i] > 1 : away != (flag[i] != 0))
             fail(SLIDEO_ERR_HIP, "internal: the gate's flag of frame %d (%d, SSD %llu) is not the host expression's", i, (int)flag[i], s);
         changed_out[i] = flag[i];
         if (similarity_out) similarity_out[i] = sim;
@@ -265,6 +275,7 @@ int32_t slideo_matcher_gate_reset(slideo_matcher* m, const uint8_t* prev_small, 
     const size_t sb = (size_t)small_w * small_h * 3;
     m->d_gate_small.reserve(sb);
     HIP_CHECK(hipMemcpyAsync(m->d_gate_small.p, prev_small, sb, hipMemcpyHostToDevice, m->stream));
+    if (m->fs.settle_similarity > 0.f) gate_settle_state_from_anchor(m, sb, m->stream);      // (anchor = previous = that image, nothing deferred)
     HIP_CHECK(hipStreamSynchronize(m->stream));
     gate_state_reset(m);
     m->gate.has = true; m->gate.sw = small_w; m->gate.sh = small_h;

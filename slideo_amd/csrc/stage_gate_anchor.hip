@@ -19,14 +19,14 @@ long long* ga_norm(Slot& S) { return S.d_ga_rec.as<long long>(); }
 unsigned long long* ga_carried(Slot& S, int n) { return S.d_ga_rec.as<unsigned long long>() + n; }
 int32_t* ga_anchor(Slot& S, int n) { return reinterpret_cast<int32_t*>(S.d_ga_rec.as<unsigned long long>() + 2 * (size_t)n); }
 
+}  // namespace
+
 // operand, norms and the table dot[i * n + j], i < j, of the n small images at `small` (stride sb = L bytes), on st
 void gram_launch(Slot& S, const uint8_t* weights, const uint8_t* small, int64_t L, int n, hipStream_t st) {
     const int64_t kp = ssd_kp(L);
     ssd_operand_build(small, L, nullptr, n, ssd_rows_pad(n), L, kp, S.d_ga_a.as<uint4>(), ga_norm(S), st, weights);
     ssd_table_dots(S.d_ga_a.as<uint4>(), n, nullptr, n, kp, S.d_ga_dot.as<unsigned long long>(), st);
 }
-
-}  // namespace
 
 void gate_anchor_reserve(Slot& S, int n, int sw, int sh) {
     if (n < 1 || n > GATE_ANCHOR_MAX_UNIT) fail(SLIDEO_ERR_CAPACITY, "a gated unit under SLIDEO_GATE_ANCHOR holds at most %d frames (%d)", GATE_ANCHOR_MAX_UNIT, n);

@@ -374,6 +374,13 @@ public:
     // was flagged: a change spread over many frames is still flagged when every decoded frame is fed).  One device only: a group of
     // several refuses SLIDEO_GATE_ANCHOR when it is built (SLIDEO_ERR_UNSUPPORTED)
     HipImageVideoMatcher& with_gate_reference(uint32_t ref) { gate_ref_ = ref; return *this; }
+    // The gate settle (slideo_group_set_gate_settle, include/slideo_amd.h "Gate settle"), under SLIDEO_GATE_ANCHOR only: a frame away
+    // from the last matched frame is matched once it is within settle_similarity of the frame before it, or after max_defer
+    // deferred frames; a deferred frame is reported as unchanged.  0: off (default)
+    HipImageVideoMatcher& with_gate_settle(float settle_similarity, int32_t max_defer) {
+        settle_similarity_ = settle_similarity; settle_max_defer_ = max_defer;
+        return *this;
+    }
     // false: tasks run the stop-and-go pair slideo_group_changed_mask_bgr8 + slideo_group_match_kept_frames in place of the group's
     // gated call (the same timeline; for comparisons).  Default: gated
     HipImageVideoMatcher& with_changed_gate(bool on) { gated_ = on; return *this; }
@@ -386,6 +393,7 @@ public:
         h->n_devices = (int)slideo_group_device_count(h->g);
         h->gated = gated_;
         if (gate_ref_ != SLIDEO_GATE_PREVIOUS) h->check(slideo_group_set_gate_reference(h->g, gate_ref_));
+        if (settle_similarity_ != 0.f) h->check(slideo_group_set_gate_settle(h->g, settle_similarity_, settle_max_defer_));
         if (sift_on_) {                                                                             // the north-star's SIFT + L2 front end
             slideo_sift_config sc;
             slideo_sift_config_default(&sc);
@@ -429,6 +437,8 @@ private:
     int32_t mask_w_ = 0, mask_h_ = 0;
     int32_t yuv_matrix_ = SLIDEO_YUV_MATRIX_BT601, yuv_range_ = SLIDEO_YUV_RANGE_LIMITED, yuv_depth_ = SLIDEO_YUV_DEPTH_8;
     uint32_t mask_scope_ = SLIDEO_MASK_DETECT, direct_scope_ = SLIDEO_DIRECT_WHOLE, gate_ref_ = SLIDEO_GATE_PREVIOUS;
+    float settle_similarity_ = 0.f;
+    int32_t settle_max_defer_ = 0;
     slideo_config cfg_;
     ImageLoader loader_;
 };
