@@ -1042,9 +1042,10 @@ int32_t     slideo_group_match_changed_frames_yuv420(slideo_group* g, int32_t n_
  * decides what the next frame is compared with — so a unit of n frames computes every pair it could need at once: the frames'
  * centred operand (direct_centre_kernel, its weighted instance under the gate's weights), frame_gram_kernel — <a'_i, a'_j>
  * for i < j on v_mfma_i32_32x32x32_i8, page_ssd_kernel's symmetric case, SSD = |a'_i|^2 + |a'_j|^2 - 2 <a'_i, a'_j> exact in
- * integers —, the n SSDs against the carried anchor (the shipped SSD launch; the only step that waits for the previous unit's
- * state), gate_anchor_kernel — one wave walks the table and writes what gate_kernel writes — and gate_anchor_state_kernel, which
- * copies the last anchor's small image into the state.  A unit that also looks pages up builds the operand twice.  The operand
+ * integers —, the n SSDs against the carried anchor (gate_carried_ssd_kernel, every pair cut across several blocks; the only step
+ * that waits for the previous unit's state), gate_settle_kernel at a cap of 0 — the walk "Gate settle" shares: one wave walks the
+ * table, one table read per step, and writes what gate_kernel writes — and gate_settle_state_kernel, which copies the last anchor's
+ * small image into the state.  A unit that also looks pages up builds the operand twice.  The operand
  * takes 3 sw sh bytes (padded to 128) per frame and the table 8 n^2 bytes; a gated unit is capped at 1024 frames (a synchronous
  * call is cut accordingly, a longer submitted unit is SLIDEO_ERR_CAPACITY).  Every allocation happens before the first write of the
  * gate state, so an error leaves the state as it was. */
@@ -1098,13 +1099,14 @@ int32_t     slideo_small_gram_ssd(slideo_matcher* m, const uint8_t* small, int32
  * slideo_matcher_set_gate_reference(PREVIOUS) while a settle is on —, and the values before stay in force.
  * Group: a group of one member forwards the call.  With more members settle on is SLIDEO_ERR_UNSUPPORTED, checked before any member
  * is touched; setting it off is always accepted.
- * Where it runs (csrc/gate_settle.hip.h, csrc/stage_gate_settle.hip; one more branch of gate_unit_submit; with settle off every call
- * launches exactly what it launched before): the unit's pair table as under ANCHOR, whose sub-diagonal gives ssd_p of frames
+ * Where it runs (csrc/gate_anchor.hip.h, csrc/stage_gate_anchor.hip: ANCHOR's one unit and gate_unit_submit's one branch — plain
+ * ANCHOR is this path with a cap of 0 and no previous-frame state): the unit's pair table, whose sub-diagonal gives ssd_p of frames
  * 1 .. n - 1 for nothing; gate_carried_ssd_kernel — ONE launch behind the wait on the previous gated unit for the n SSDs against the
  * carried anchor and frame 0's against the carried previous frame, every pair cut across several blocks that add their partial sums
  * with one 64-bit atomic each —; gate_settle_kernel — one wave, two ballots per 64 frames: away, and from it every lane's deferral
- * count, then the first matched lane —; gate_settle_state_kernel, which copies the unit's last anchor (if any) and its last frame
- * into the state and stores d.  Every allocation happens before the first write of the gate state. */
+ * count, then the first matched lane; with max_defer == 0 it reads neither the carried count nor ssd_p —; gate_settle_state_kernel,
+ * which copies the unit's last anchor (if any) and its last frame into the state and stores d.  Every allocation happens before the
+ * first write of the gate state. */
 /* Idle matcher (SLIDEO_ERR_STATE otherwise).  Resets the gate state, also when the values do not change. */
 int32_t     slideo_matcher_set_gate_settle(slideo_matcher* m, float settle_similarity, int32_t max_defer);
 /* The matcher's gate settle (0, 0 unless set).  SLIDEO_ERR_INVALID_ARG for a null argument. */
@@ -1115,10 +1117,11 @@ int32_t     slideo_group_set_gate_settle(slideo_group* g, float settle_similarit
  * (host memory; uploaded back to back behind the two, so odd sizes put the images at every byte alignment).  ssd_out [n + 1]:
  * ssd_out[i] = the SSD of anchor_small and image i, ssd_out[n] = the SSD of prev_small and image 0 — over whole images, or,
  * use_valid != 0, over the valid pixels of the matcher's current validity map (SLIDEO_ERR_STATE without one in force,
- * SLIDEO_ERR_INVALID_ARG at another size).  Idle matcher; needs no pages.  1 <= n <= 1024, sw * sh <= small_area. */
+ * SLIDEO_ERR_INVALID_ARG at another size).  prev_small == NULL: the n pairs alone, as plain ANCHOR launches them; ssd_out[0 .. n)
+ * alone is written.  Idle matcher; needs no pages.  1 <= n <= 1024, sw * sh <= small_area. */
 int32_t     slideo_small_carried_ssd(slideo_matcher* m, const uint8_t* anchor_small, const uint8_t* prev_small, const uint8_t* small, int32_t n,
                                      int32_t sw, int32_t sh, int32_t use_valid, uint64_t* ssd_out);
-/* Tap: gate_settle_kernel on its own inputs.  dot [n * n]: <a'_i, a'_j>, read for i < j alone; norm [n]: |a'_i|^2; carried [n + 1]: the
+/* Tap: gate_settle_kernel — the walk of ANCHOR with and without a settle — on its own inputs.  dot [n * n]: <a'_i, a'_j>, read for i < j alone; norm [n]: |a'_i|^2; carried [n + 1]: the
  * SSDs against the carried anchor, then frame 0's against the carried previous frame; thr_c, thr_s: T_c and T_s; d_in: the carried
  * deferral count (0 <= d_in <= max_defer); none != 0: the state "none" (nothing carried is read).  changed_out [n], ssd_out [n] (ssd_a
  * per frame), *anchor_out: the last matched frame or -1, *d_out: the count behind the unit.  Idle matcher.  1 <= n <= 1024. */

@@ -1193,17 +1193,18 @@ class Matcher(_FrameCalls):
 
     def small_carried_ssd(self, anchor_small, prev_small, smalls, use_valid=False):
         """slideo_small_carried_ssd: two small images [sh, sw, 3] and smalls uint8 [n, sh, sw, 3] -> uint64 [n + 1]: the integer SSD of
-        anchor_small against every image, then of prev_small against image 0; use_valid: over the valid pixels of the matcher's
-        current validity map.  The carried-SSD kernel of the gate settle; needs no pages."""
+        anchor_small against every image, then of prev_small against image 0; prev_small None: uint64 [n], the first alone, as plain
+        'anchor' launches it; use_valid: over the valid pixels of the matcher's current validity map.  The carried-SSD kernel of the
+        gate reference 'anchor'; needs no pages."""
         smalls = np.ascontiguousarray(smalls, np.uint8)
         if smalls.ndim != 4 or smalls.shape[3] != 3 or len(smalls) < 1:
             raise ValueError("expected [n >= 1, sh, sw, 3] uint8 small images")
         n, sh, sw, _ = smalls.shape
         a = np.ascontiguousarray(anchor_small, np.uint8)
-        p = np.ascontiguousarray(prev_small, np.uint8)
-        if a.shape != smalls.shape[1:] or p.shape != smalls.shape[1:]:
+        p = np.ascontiguousarray(prev_small, np.uint8) if prev_small is not None else None
+        if a.shape != smalls.shape[1:] or (p is not None and p.shape != smalls.shape[1:]):
             raise ValueError("anchor_small and prev_small have the small images' shape")
-        out = np.empty(n + 1, np.uint64)
+        out = np.empty(n + (p is not None), np.uint64)
         self._check(lib().slideo_small_carried_ssd(self._h, _p(a), _p(p), _p(smalls), n, sw, sh, 1 if use_valid else 0, _p(out)))
         return out
 

@@ -15,8 +15,8 @@
 //                      table of dot products on the int8 matrix cores, the taps' validity map (kernels: ssd_table.hip.h)
 //   stage_activity.hip frame activity map: the accumulator, the observe driver, its entry points (kernels: activity.hip.h)
 //   stage_content.hip  frame content box: the content accumulator, its launch behind the observe driver, its entry points (kernels: content.hip.h)
-//   stage_gate_anchor.hip  gate reference ANCHOR: a gated unit's pair table and walk, the setting and the tap (kernels: gate_anchor.hip.h)
-//   stage_gate_settle.hip  gate settle: a gated unit's carried SSDs, walk and state under a settle, the setting and the taps (kernels: gate_settle.hip.h)
+//   stage_gate_anchor.hip  gate reference ANCHOR and its gate settle: a gated unit's pair table, carried SSDs, walk and state, the two
+//                      settings and the taps (kernels: gate_anchor.hip.h)
 //   capi_taps.hip      debug taps of the parity tests
 //   capi_group.hip     the N-device group (slideo_group_*)
 //
@@ -187,11 +187,9 @@ struct Slot {
     // n x np dot products (reserved by the first such unit only)
     DevBuf d_dir_a, d_dir_rec, d_dir_dot;
     // ... under SLIDEO_GATE_ANCHOR (stage_gate_anchor.hip): the frames' centred operand, {|a'|^2 n x i64 | SSDs against the carried
-    // anchor n x u64 | the unit's last anchor i32}, and the n x n dot products (reserved by the first such unit only)
+    // anchor n x u64, frame 0 against the carried previous frame u64 | the unit's last anchor i32 | the deferral count behind the
+    // unit u32}, and the n x n dot products (reserved by the first such unit only)
     DevBuf d_ga_a, d_ga_rec, d_ga_dot;
-    // ... under a gate settle (stage_gate_settle.hip): {SSDs against the carried anchor n x u64, frame 0 against the carried previous
-    // frame u64 | the unit's last anchor i32 | the deferral count behind the unit u32} (reserved by the first such unit only)
-    DevBuf d_gs_rec;
     hipEvent_t ev_gate = nullptr;             // the unit's small images are made and the gate state is this unit's last one
     struct GateUnit {
         bool on = false;                      // the unit in flight is gated: slideo_match_changed_frames_collect collects it
@@ -634,26 +632,19 @@ struct GateAnchorOut {
     uint8_t* flags; int32_t* idx; uint32_t* count;
     uint32_t* h_head; unsigned long long* h_ssd; int32_t* h_idx; uint8_t* h_flag;
 };
-// a unit of n frames with sw x sh small images under SLIDEO_GATE_ANCHOR: S's workspaces (everything that can fail for want of memory)
-void gate_anchor_reserve(Slot& S, int n, int sw, int sh);
-// The unit's gate under SLIDEO_GATE_ANCHOR on S.st, behind the unit's small images `small` (sb bytes each): operand, pair table, the
-// SSDs against the carried anchor m->d_gate_small (behind `wait`, the previous gated unit's event; none when force0), the walk, and
-// the new state written into m->d_gate_small.  Launches only.
-void gate_anchor_unit(slideo_matcher* m, Slot& S, const uint8_t* weights, const uint8_t* small, int64_t sb, int n, long long thr, bool force0,
-                      hipEvent_t wait, const GateAnchorOut& out);
+// a unit of n frames with sw x sh small images under SLIDEO_GATE_ANCHOR: S's workspaces and, with a settle in force, the matcher's
+// previous-frame image and deferral count (everything that can fail for want of memory, in front of any write of the gate state)
+void gate_anchor_reserve(slideo_matcher* m, Slot& S, int n, int sw, int sh, bool settle);
+// The unit's gate under SLIDEO_GATE_ANCHOR on S.st, behind the unit's small images `small` (sb bytes each): operand, pair table, then
+// behind `wait` (the previous gated unit's event) ONE launch for the n SSDs against the carried anchor m->d_gate_small and, under a
+// settle, frame 0's against the carried previous frame (none when force0), the walk, and the new state — the anchor and, under a
+// settle (m->fs.settle_similarity > 0; thr_s: its SSD threshold, max_defer: its cap), the previous frame and the deferral count.
+// Without a settle thr_s = 0 and max_defer = 0: a frame away from its anchor is matched at once.  Launches only.
+void gate_anchor_unit(slideo_matcher* m, Slot& S, const uint8_t* weights, const uint8_t* small, int64_t sb, int n, long long thr, long long thr_s,
+                      int32_t max_defer, bool force0, hipEvent_t wait, const GateAnchorOut& out);
 // its first step alone: operand, norms (S.d_ga_rec's first n i64) and the table S.d_ga_dot[i * n + j], i < j, of the n small images at
 // `small` (L bytes each), on st; S reserved by gate_anchor_reserve
 void gram_launch(Slot& S, const uint8_t* weights, const uint8_t* small, int64_t L, int n, hipStream_t st);
-
-// ---- stage_gate_settle.hip ------------------------------------------------------------------------
-// a unit of n frames under a gate settle: gate_anchor_reserve, the settle's record of S and the matcher's previous-frame image and
-// deferral count for small images of sb bytes (everything that can fail for want of memory, in front of any write of the gate state)
-void gate_settle_reserve(slideo_matcher* m, Slot& S, int n, int sw, int sh);
-// gate_anchor_unit under a settle (m->fs.settle_similarity > 0; thr_s: its SSD threshold): the pair table, then behind `wait` ONE
-// launch for the n SSDs against the carried anchor and frame 0's against the carried previous frame, the settle walk, and the new
-// state — anchor, previous frame, deferral count.  Launches only.
-void gate_settle_unit(slideo_matcher* m, Slot& S, const uint8_t* weights, const uint8_t* small, int64_t sb, int n, long long thr, long long thr_s,
-                      bool force0, hipEvent_t wait, const GateAnchorOut& out);
 // the previous-frame image := the anchor's (m->d_gate_small, sb bytes) and the deferral count := 0, on st: what every reset of the
 // gate state to an image does under a settle
 void gate_settle_state_from_anchor(slideo_matcher* m, size_t sb, hipStream_t st);

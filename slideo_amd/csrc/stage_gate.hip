@@ -1,8 +1,8 @@
 // stage_gate.hip — the changed-frame gate of include/slideo_amd.h "Changed-frame gate": gated units (small images of all frames, SSDs,
 // gate_kernel, gather_frames_kernel in front of the unchanged unit_submit), the gate state and its entry points (kernels: gate.hip.h).
 // The frame calls that run gated units are capi_runtime.hip's, beside their plain twins.  Under the gate reference SLIDEO_GATE_ANCHOR
-// gate_unit_submit hands the SSDs, the flags and the new state to stage_gate_anchor.hip (include/slideo_amd.h "Gate reference"), under a
-// gate settle to stage_gate_settle.hip ("Gate settle").
+// gate_unit_submit hands the SSDs, the flags and the new state to stage_gate_anchor.hip (include/slideo_amd.h "Gate reference" and, a
+// setting of the same unit, "Gate settle").
 #include "runtime.hpp"
 #include "gate.hip.h"
 
@@ -128,10 +128,9 @@ void gate_unit_submit(slideo_matcher* m, Slot& S, const FrameSrc& src, int first
     if (look) plan = direct_unit_prepare(m, S, n, sw, sh, m->fs.direct_scope == SLIDEO_DIRECT_VALID ? weights : nullptr);
     // under SLIDEO_GATE_ANCHOR: the pair table's workspaces, first for the same reason (include/slideo_amd.h "Gate reference")
     const bool anchor = m->fs.gate_ref == SLIDEO_GATE_ANCHOR;
-    // ... under a gate settle also the settle's record and the state's previous-frame image and count ("Gate settle")
+    // ... under a gate settle also the state's previous-frame image and count ("Gate settle")
     const bool settle = anchor && m->fs.settle_similarity > 0.f;
-    if (settle) gate_settle_reserve(m, S, n, sw, sh);
-    else if (anchor) gate_anchor_reserve(S, n, sw, sh);
+    if (anchor) gate_anchor_reserve(m, S, n, sw, sh, settle);
     const DevFrames all = stage_frames(m, S, src, first, n, cs, &S.d_gstage);
     run_small_into(m, all, n, S.d_gsmall, st);
     const int64_t sb = (int64_t)sw * sh * 3;
@@ -150,12 +149,12 @@ void gate_unit_submit(slideo_matcher* m, Slot& S, const FrameSrc& src, int first
     uint8_t* const hrec = S.h_gate.as<uint8_t>();
     if (anchor) {
         // every pair of the unit, the carried anchor against its frames behind the previous gated unit's write of the state, the walk
-        // (gate_kernel's outputs) and the new state: the unit's last flagged frame, if any
+        // (gate_kernel's outputs) and the new state: the unit's last flagged frame, if any; without a settle the walk's cap is 0
         const GateAnchorOut out{flags, idx, count, reinterpret_cast<uint32_t*>(hrec), reinterpret_cast<unsigned long long*>(hrec + gate_rec_ssd_ofs()),
                                 reinterpret_cast<int32_t*>(hrec + gate_rec_idx_ofs(n)), hrec + gate_rec_flag_ofs(n)};
         hipEvent_t wait = m->last_gate_ev != S.ev_gate ? m->last_gate_ev : nullptr;
-        if (settle) gate_settle_unit(m, S, weights, small, sb, n, thr, gate_ssd_threshold(m->fs.settle_similarity, npx), force0, wait, out);
-        else gate_anchor_unit(m, S, weights, small, sb, n, thr, force0, wait, out);
+        gate_anchor_unit(m, S, weights, small, sb, n, thr, settle ? gate_ssd_threshold(m->fs.settle_similarity, npx) : 0,
+                         settle ? m->fs.settle_max_defer : 0, force0, wait, out);
     } else {
         // pair i: (small[i - 1], small[i]); pair 0: (gate state, small[0]), behind the previous gated unit's write of the state
         if (n > 1) launch_gate_ssd(weights, small, sb, small + sb, sb, sb, ssd + 1, n - 1, st);

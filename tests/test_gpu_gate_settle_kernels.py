@@ -1,17 +1,22 @@
-"""The gate settle's kernels on their own (include/slideo_amd.h "Gate settle"), every comparison exact equality.
+"""The kernels of the gate reference ANCHOR, with and without a gate settle, on their own (include/slideo_amd.h "Gate reference",
+"Gate settle"; plain ANCHOR is the settle with a cap of 0 and no previous frame), every comparison exact equality.
 
 slideo_small_carried_ssd — gate_carried_ssd_kernel — against numpy: n = 1, 2 and 65 images (the grid's second dimension is n + 1 and
 the host cuts a pair across fewer blocks as n grows) of L = 3 sw sh = 105 (one block, a body of 25 dwords), 2139 (several blocks
 of one dword per thread, a ragged tail) and 358 197 bytes (the small image of a 640x360 frame).  The tap uploads the anchor, the
 previous frame and the images back to back, so with these odd lengths they start at every byte alignment.  Contents: random bytes,
-and all-0 against all-255, the largest SSD.  use_valid: the validity map of a 640x360 mask with a hole (461x259).
+and all-0 against all-255, the largest SSD.  use_valid: the validity map of a 640x360 mask with a hole (461x259).  Without a
+previous frame (None: plain ANCHOR's launch) the grid has n rows and the host cuts a pair by n, not n + 1: the same shapes — one
+block; several blocks with a ragged tail; the workload's size —, the first n values of the same numpy.
 
 slideo_gate_settle_walk — gate_settle_kernel — against the restatement's integer walk (tests/gate_settle_ref.py): random integer
 vectors of 8 components give the table of dot products and the norms exactly; n = 1, 63, 64, 65, 130 around the 64-lane window;
 max_defer = 0, 1, 3, 70 (a run of deferred frames that crosses the window and reaches its cap behind it) and 2**30; the carried
 count zero and nonzero; the state "none".  thr_c is a quantile of the SSDs that occur, thr_s separates the walk's small steps from its
 large ones, and the test asserts on the
-restatement, before anything is compared, that every branch occurs: unchanged, matched-still, matched-by-cap, deferred."""
+restatement, before anything is compared, that every branch occurs: unchanged, matched-still, matched-by-cap, deferred.
+A cap of 0 — where the kernel reads neither the carried count nor any previous-frame SSD — is held to the plain anchor rule written
+as its own loop here, not to the settle's restatement."""
 import numpy as np
 import pytest
 
@@ -96,6 +101,29 @@ def test_carried_ssd_under_a_validity_map(masked):
     x[2:] = 255
     x[0] = 0
     assert m.small_carried_ssd(x[0], x[1], x[2:], use_valid=True)[0] == 255 * 255 * 3 * int(valid.sum())
+
+
+NO_PREV = [(n, sw, sh) for sw, sh in SIZES[:2] for n in NS] + [(2,) + SIZES[2]]
+
+
+@pytest.mark.parametrize("n,sw,sh", NO_PREV)
+def test_carried_ssd_without_a_previous_frame(plain, n, sw, sh):
+    x = _random(n, sw, sh)
+    got = plain.small_carried_ssd(x[0], None, x[2:])
+    assert got.dtype == np.uint64 and got.shape == (n,) and np.array_equal(got, _want(x[0], x[1], x[2:])[:n])
+    anchor = np.zeros((sh, sw, 3), np.uint8)
+    s = np.zeros((n, sh, sw, 3), np.uint8)
+    s[::2] = 255
+    want = _want(anchor, anchor, s)[:n]
+    assert want[0] == 255 * 255 * 3 * sw * sh and np.array_equal(plain.small_carried_ssd(anchor, None, s), want)
+
+
+def test_carried_ssd_without_a_previous_frame_under_a_validity_map(masked):
+    m, valid = masked
+    x = _random(2, 461, 259)
+    want = _want(x[0], x[1], x[2:], valid)[:2]
+    assert not np.array_equal(want, _want(x[0], x[1], x[2:])[:2]), "the hole matters"
+    assert np.array_equal(m.small_carried_ssd(x[0], None, x[2:], use_valid=True), want)
 
 
 def test_carried_ssd_refusals(capi, plain, masked):
@@ -200,6 +228,50 @@ def test_walk_all_deferred_and_all_matched(plain):
     assert fl.all() and last == n - 1
     got = plain.gate_settle_walk(dot, norm, carried, 0, 0, 0, 0, False)
     assert got[0].all() and np.array_equal(got[1].astype(np.int64), ssd) and got[2:] == (n - 1, 0)
+
+
+def _anchor_rule(table, carried, thr, none):
+    """Plain ANCHOR, frame by frame: the carried anchor until a frame is flagged, then the last flagged frame."""
+    n = len(table)
+    flags, ssd, a = np.zeros(n, np.uint8), np.zeros(n, np.int64), -1
+    for j in range(n):
+        if none and j == 0:
+            flags[0], a = 1, 0
+            continue
+        ssd[j] = carried[j] if a < 0 else table[a, j]
+        if ssd[j] >= thr:
+            flags[j], a = 1, j
+    return flags, ssd, a
+
+
+def test_a_cap_of_0_is_the_plain_anchor_rule(plain):
+    cases, flagged, unflagged, carried_across = [], 0, 0, False
+    for k, n in enumerate(WALK_NS):
+        for none in (False, True):
+            dot, norm, table, carried, thr_c, thr_s = _walk_case(n, 0, none, 0, 300 + 2 * k + none)
+            cases.append((n, none, dot, norm, table, carried, thr_c, thr_s))
+    # nothing flagged over a whole window behind the carried anchor: the walk moves on by 64 frames with the anchor still -1
+    dot, norm, table, carried, _, thr_s = _walk_case(130, 0, False, 0, 77)
+    cases.append((130, False, dot, norm, table, carried, int(carried[:100].max()) + 1, thr_s))
+    want = []
+    for n, none, dot, norm, table, carried, thr_c, thr_s in cases:
+        fl, ssd, last = _anchor_rule(table, carried, thr_c, none)
+        want.append((fl, ssd, last))
+        flagged += int(fl.sum()) - int(none)
+        unflagged += int((fl == 0).sum())
+        carried_across |= not none and n > 64 and not fl[:64].any()
+    assert flagged >= 10 and unflagged >= 10 and carried_across
+    for (n, none, dot, norm, table, carried, thr_c, thr_s), (fl, ssd, last) in zip(cases, want):
+        got = plain.gate_settle_walk(dot, norm, carried, thr_c, thr_s, 0, 0, none)
+        assert np.array_equal(got[0], fl), (n, none, "flags", np.nonzero(got[0] != fl)[0][:8])
+        assert np.array_equal(got[1].astype(np.int64), ssd), (n, none, "SSDs")
+        assert got[2:] == (last, 0), (n, none, got[2:], last)
+    # `still` is not consulted: any thr_s gives the same output
+    n, none, dot, norm, table, carried, thr_c, _ = cases[-2]
+    fl, ssd, last = want[-2]
+    for thr_s in (0, 2 ** 62):
+        got = plain.gate_settle_walk(dot, norm, carried, thr_c, thr_s, 0, 0, none)
+        assert np.array_equal(got[0], fl) and np.array_equal(got[1].astype(np.int64), ssd) and got[2:] == (last, 0), thr_s
 
 
 def test_walk_refusals(capi, plain):

@@ -1,5 +1,5 @@
 // gate_anchor_hostcheck — the host side of the gate reference (include/slideo_amd.h "Gate reference"; csrc/frame_settings.h) on its own:
-// propose_gate_reference's refusals, the SETTING_ENDS row, the group rule as a pure function, and gate_anchor_kernel's walk —
+// propose_gate_reference's refusals, the SETTING_ENDS row, the group rule as a pure function, and the walk of gate_settle_kernel at a cap of 0 —
 // restated lane by lane in plain C++: 64 frames per step, the first flagged one becomes the anchor — over the SSD tables of a case
 // file, against the flags, SSDs and last anchor the file states (tests/test_gate_anchor_abi.py writes them from the numpy
 // restatement, tests/gate_anchor_ref.py).  No GPU, nothing loaded into Python.
@@ -30,7 +30,8 @@ int code_of(F f) {
     return 0;
 }
 
-// gate_anchor_kernel's walk (csrc/gate_anchor.hip.h) with its 64 lanes as a loop: lanes test frames i .. i + 63 against the anchor a
+// The walk of gate_settle_kernel (csrc/gate_anchor.hip.h) at a cap of 0 — plain ANCHOR — as its own loop, a second opinion on the
+// kernel the settle shares: the 64 lanes test frames i .. i + 63 against the anchor a
 // (-1: the carried one), the ballot's first set bit f is the next anchor, lanes <= f write their frame
 struct Walk { std::vector<uint8_t> flags; std::vector<int64_t> ssd; std::vector<int32_t> kept; int32_t anchor; };
 Walk walk(const std::vector<int64_t>& table, const std::vector<int64_t>& carried, int n, int64_t thr, bool none) {

@@ -11,7 +11,8 @@ each a run of its own:
           ANCHOR, without and with a frame mask under SLIDEO_MASK_GATE, for a rocprofv3 --kernel-trace run of its own.  none: a held
           frame (no frame of a unit is flagged: the walk takes 64 frames per step); all: 256 unrelated frames (every frame is
           flagged: one step per frame).  --parse-trace <kernel trace csv> then prints per kernel and grid the count and the median
-          duration, and frame_gram_kernel's share of the int8 matrix-core peak by the tiles it executes.
+          duration, and frame_gram_kernel's share of the int8 matrix-core peak by the tiles it executes (gate_anchor_kernel and
+          gate_anchor_state_kernel: the walk and state write of a library from before ANCHOR ran the settle's kernels at a cap of 0).
 
               rocprofv3 --kernel-trace --stats -d OUT -o none -- python tools/gate_anchor_rate.py --kernels none
               python tools/gate_anchor_rate.py --parse-trace OUT/.../none_kernel_trace.csv
@@ -45,7 +46,8 @@ def parse_trace(path):
             key = (name, int(r["Grid_Size_X"]) if "Grid_Size_X" in r else int(r.get("Grid_Size", 0)), int(r.get("Grid_Size_Y", 1) or 1), int(r.get("Grid_Size_Z", 1) or 1))
             rows.setdefault(key, []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
     out = {}
-    want = ("ssd_kernel", "ssd_masked_kernel", "frame_gram_kernel", "gate_anchor_kernel", "gate_anchor_state_kernel", "gate_kernel", "direct_centre")
+    want = ("ssd_kernel", "ssd_masked_kernel", "gate_carried_ssd_kernel", "frame_gram_kernel", "gate_anchor_kernel", "gate_anchor_state_kernel", "gate_settle_kernel",
+            "gate_settle_state_kernel", "gate_kernel", "direct_centre", "fill")
     for key, v in sorted(rows.items()):
         if not any(w in key[0] for w in want):
             continue

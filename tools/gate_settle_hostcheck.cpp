@@ -43,7 +43,7 @@ int set(FrameSettings& s, P propose) {
     });
 }
 
-// settle_run of csrc/gate_settle.hip.h
+// settle_run of csrc/gate_anchor.hip.h
 uint32_t settle_run(uint64_t away, int pos, uint32_t d, uint32_t max_defer) {
     const uint64_t below = pos >= 64 ? ~0ull : (1ull << pos) - 1ull;
     const uint64_t stop = ~away & below;
@@ -51,16 +51,18 @@ uint32_t settle_run(uint64_t away, int pos, uint32_t d, uint32_t max_defer) {
     return run < max_defer ? run : max_defer;
 }
 
-// gate_settle_kernel's walk with its 64 lanes as loops
+// gate_settle_kernel's walk with its 64 lanes as loops; as the kernel, with max_defer == 0 (plain ANCHOR, a settle with a cap of 0)
+// it reads neither d_in nor the previous-frame SSDs — carried[n] and the table's sub-diagonal —: matched = away, d = 0
 struct Walk { std::vector<uint8_t> flags; std::vector<int64_t> ssd; std::vector<int32_t> kept; int32_t anchor; uint32_t d; };
 Walk walk(const std::vector<int64_t>& table, const std::vector<int64_t>& carried, int n, int64_t thr_c, int64_t thr_s, uint32_t max_defer, uint32_t d_in,
           bool none) {
     Walk w{std::vector<uint8_t>((size_t)n, 0xEE), std::vector<int64_t>((size_t)n, -1), {}, -1, 0};
     int a = -1, i = 0;
     uint32_t d = 0;
+    const bool defer = max_defer != 0;
     if (none) {
         if (n > 0) { w.flags[0] = 1; w.ssd[0] = 0; w.kept.push_back(0); a = 0; i = 1; }
-    } else d = d_in > max_defer ? max_defer : d_in;
+    } else if (defer) d = d_in > max_defer ? max_defer : d_in;
     while (i < n) {
         int64_t s[64];
         bool away[64], still[64];
@@ -70,13 +72,18 @@ Walk walk(const std::vector<int64_t>& table, const std::vector<int64_t>& carried
             s[lane] = 0; away[lane] = still[lane] = false;
             if (j >= n) continue;
             s[lane] = a < 0 ? carried[(size_t)j] : table[(size_t)a * n + j];
-            const int64_t p = j == 0 ? carried[(size_t)n] : table[(size_t)(j - 1) * n + j];
             away[lane] = s[lane] >= thr_c;
-            still[lane] = p < thr_s;
             if (away[lane]) ab |= 1ull << lane;
         }
-        for (int lane = 0; lane < 64; ++lane)
-            if (away[lane] && (still[lane] || settle_run(ab, lane, d, max_defer) >= max_defer)) b |= 1ull << lane;
+        b = ab;
+        if (defer) {
+            b = 0;
+            for (int lane = 0; lane < 64; ++lane) {
+                const int j = i + lane;
+                if (j < n) still[lane] = (j == 0 ? carried[(size_t)n] : table[(size_t)(j - 1) * n + j]) < thr_s;
+                if (away[lane] && (still[lane] || settle_run(ab, lane, d, max_defer) >= max_defer)) b |= 1ull << lane;
+            }
+        }
         const int f = b ? __builtin_ctzll(b) : 64;
         for (int lane = 0; lane < 64; ++lane) {
             const int j = i + lane;

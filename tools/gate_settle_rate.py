@@ -5,10 +5,17 @@
           against the shipped SSD launch for the same 256 pairs in the ANCHOR path, and the walk.  none: a held frame (nothing is
           flagged: 64 frames per step); deferred: 256 unrelated frames under (0.99, 2**30) (every frame is away and none still:
           everything deferred, 64 frames per step); matched: the same frames under (0.99, 0) (every frame matched: one step per
-          frame).  --parse-trace <kernel trace csv> then prints per kernel and grid the count and the median duration.
+          frame).  Plain ANCHOR and the settle run the same kernels (plain is the settle with a cap of 0), so a trace tells them apart
+          only by gate_carried_ssd_kernel's grid, 256 against 257 rows: --only plain | settle runs one of the two alone.
+          --parse-trace <kernel trace csv> then prints per kernel and grid the count and the median duration (gate_anchor_kernel and
+          gate_anchor_state_kernel: the walk and state write of a library from before the two paths were merged).
 
               rocprofv3 --kernel-trace --stats -d OUT -o none -- python tools/gate_settle_rate.py --kernels none
               python tools/gate_settle_rate.py --parse-trace OUT/.../none_kernel_trace.csv
+
+  (step)  --step: the same gated units, timed (submit + collect of 256 frames, median of --reps, profiler off), whole and under the
+          mask: the held frame under plain ANCHOR and under the settle, and the unrelated frames under the settle (0.99, 2**30) —
+          the three streams in which no frame goes through ORB, so the time is the gate's.
 
   (use)   --use: gate_anchor_rate.py's synthetic lecture streams of 640x360 frames (4 pages, ORB-500; a share of the page changes is
           an 8-, 16- or 32-frame linear fade, the rest hard cuts) under PREVIOUS, ANCHOR and the settle (0.99, 2**30): the share of
@@ -51,7 +58,7 @@ def parse_trace(path):
     print(json.dumps(out))
 
 
-def kernels_main(case):
+def kernels_main(case, only=None):
     import torch
     from slideo_amd import _capi, synth
     W, H, N = 640, 360, 256
@@ -73,7 +80,7 @@ def kernels_main(case):
             m.set_frame_mask_scope(_capi.MASK_DETECT | _capi.MASK_GATE)
             m.set_frame_mask(mask)
         m.set_gate_reference("anchor")
-        for s in ((0.0, 0), settle):
+        for s in [x for x, name in (((0.0, 0), "plain"), (settle, "settle")) if only in (None, name)]:
             m.set_gate_settle(*s)
             m.gate_reset_from_frame(seq[0])
             for _ in range(4):
@@ -81,6 +88,51 @@ def kernels_main(case):
             print("%s, %s, settle %s: %d of %d matched, %d deferred in the last unit" % (case, "masked" if masked else "whole", s, int(ch.sum()), N,
                                                                                          int(_capi.gate_deferred(ch, sim, m.cfg.changed_similarity).sum())), flush=True)
         m.close()
+
+
+def step_main(a):
+    import torch
+    from slideo_amd import _capi, synth
+    W, H, N = 640, 360, 256
+    pages = synth.pages(4, 800, 450, threads=NCPU)
+    base, _, _ = synth.frames(pages, 1, W, H, threads=NCPU)
+    held = torch.from_numpy(np.repeat(base[:1], N, axis=0)).cuda()
+    rnd = torch.from_numpy(np.random.default_rng(3).integers(0, 256, (N, H, W, 3), dtype=np.uint8)).cuda()
+    mask = np.full((H, W), 255, np.uint8)
+    mask[190:350, 390:630] = 0
+    res = {"lib": os.environ.get("SLIDEO_LIB_PATH", "product")}
+    ms = {}
+    runs = []
+    for masked in (False, True):
+        m = _capi.Matcher(_capi.default_config(nfeatures=500, min_rating=12.0))
+        m.add_pages(list(pages))
+        m.finalize()
+        if masked:
+            m.set_frame_mask_scope(_capi.MASK_DETECT | _capi.MASK_GATE)
+            m.set_frame_mask(mask)
+        m.set_gate_reference("anchor")
+        for name, d, s in (("held, plain", held, (0.0, 0)), ("held, settle", held, (SETTLE, NEVER)), ("deferred, settle", rnd, (SETTLE, NEVER))):
+            runs.append((m, "%s, %s" % ("masked" if masked else "whole", name), d, s))
+    for rep in range(a.reps + 1):                                # (alternating; the first round warms: workspaces sized)
+        for m, name, d, s in runs:
+            m.set_gate_settle(*s)
+            m.gate_reset_from_frame(base[0])
+            m.collect_changed(m.submit_changed_dev(d.data_ptr(), N, W, H))
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(4):
+                ch, _, _ = m.collect_changed(m.submit_changed_dev(d.data_ptr(), N, W, H))
+            torch.cuda.synchronize()
+            if int(ch.sum()):
+                raise SystemExit("%s: %d frames went through the pipeline" % (name, int(ch.sum())))
+            if rep:
+                ms.setdefault(name, []).append((time.perf_counter() - t0) * 1e3 / 4)
+    for name, v in ms.items():
+        res[name] = {"min": min(v), "median": float(np.median(v)), "max": max(v)}
+        print("%-26s min %.3f median %.3f max %.3f ms per %d frames" % (name, min(v), float(np.median(v)), max(v), N), flush=True)
+    for m in {id(r[0]): r[0] for r in runs}.values():
+        m.close()
+    print(json.dumps(res))
 
 
 def use_main(a):
@@ -139,7 +191,9 @@ def use_main(a):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--kernels", choices=["none", "deferred", "matched"], default=None)
+    ap.add_argument("--only", choices=["plain", "settle"], default=None)
     ap.add_argument("--parse-trace", default=None)
+    ap.add_argument("--step", action="store_true")
     ap.add_argument("--use", action="store_true")
     ap.add_argument("--holds", type=int, default=24)
     ap.add_argument("--reps", type=int, default=3)
@@ -147,10 +201,12 @@ def main():
     if a.parse_trace:
         return parse_trace(a.parse_trace)
     if a.kernels:
-        return kernels_main(a.kernels)
+        return kernels_main(a.kernels, a.only)
+    if a.step:
+        return step_main(a)
     if a.use:
         return use_main(a)
-    ap.error("one of --kernels, --parse-trace, --use")
+    ap.error("one of --kernels, --parse-trace, --step, --use")
 
 
 if __name__ == "__main__":
