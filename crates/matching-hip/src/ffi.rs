@@ -11,6 +11,8 @@ pub const SLIDEO_DIRECT_WHOLE: u32 = 0;
 pub const SLIDEO_DIRECT_VALID: u32 = 1;
 pub const SLIDEO_GATE_PREVIOUS: u32 = 0;
 pub const SLIDEO_GATE_ANCHOR: u32 = 1;
+pub const SLIDEO_GROUP_GATE_HALO: u32 = 0;
+pub const SLIDEO_GROUP_GATE_CHAIN: u32 = 1;
 pub const SLIDEO_YUV_MATRIX_BT601: i32 = 0;
 pub const SLIDEO_YUV_MATRIX_BT709: i32 = 1;
 pub const SLIDEO_YUV_RANGE_LIMITED: i32 = 0;
@@ -491,6 +493,16 @@ extern "C" {
     pub fn slideo_matcher_set_gate_settle(m: *mut slideo_matcher, settle_similarity: f32, max_defer: i32) -> i32;
     pub fn slideo_matcher_gate_settle(m: *const slideo_matcher, settle_similarity: *mut f32, max_defer: *mut i32) -> i32;
     pub fn slideo_group_set_gate_settle(g: *mut slideo_group, settle_similarity: f32, max_defer: i32) -> i32;
+    // gate state record (include/slideo_amd.h "Gate state record"): the whole gate state — anchor, previous image, deferral count — as bytes
+    pub fn slideo_matcher_gate_state_bytes(m: *mut slideo_matcher, bytes: *mut i64) -> i32;
+    pub fn slideo_matcher_gate_state_export(m: *mut slideo_matcher, out: *mut u8, capacity: i64, bytes: *mut i64) -> i32;
+    pub fn slideo_matcher_gate_state_import(m: *mut slideo_matcher, rec: *const u8, bytes: i64) -> i32;
+    // group gate order (include/slideo_amd.h "Group gate order"): SLIDEO_GROUP_GATE_HALO / SLIDEO_GROUP_GATE_CHAIN
+    pub fn slideo_group_set_gate_order(g: *mut slideo_group, order: u32) -> i32;
+    pub fn slideo_group_gate_order(g: *const slideo_group, order: *mut u32) -> i32;
+    pub fn slideo_group_gate_state_export(g: *mut slideo_group, out: *mut u8, capacity: i64, bytes: *mut i64) -> i32;
+    pub fn slideo_group_gate_state_import(g: *mut slideo_group, rec: *const u8, bytes: i64) -> i32;
+    pub fn slideo_group_gate_chain_waited(g: *const slideo_group, member: i32, seconds: *mut f64) -> i32;
     pub fn slideo_small_gram_ssd(
         m: *mut slideo_matcher,
         small: *const u8,

@@ -97,13 +97,18 @@ pub struct HipImageVideoMatcher {
     pub yuv_description: (i32, i32, i32),
     /// Which frame a gated frame is compared with (slideo_group_set_gate_reference): ffi::SLIDEO_GATE_PREVIOUS (default: the
     /// frame before, the reference's MarkSimilarIter) or ffi::SLIDEO_GATE_ANCHOR (the last frame that was flagged: a change
-    /// spread over many frames is still flagged when every decoded frame is fed).  One device only: a group of several
-    /// refuses SLIDEO_GATE_ANCHOR when it is built.
+    /// spread over many frames is still flagged when every decoded frame is fed).  With several devices it needs
+    /// group_gate_order = ffi::SLIDEO_GROUP_GATE_CHAIN: without it the group refuses SLIDEO_GATE_ANCHOR when it is built.
     pub gate_reference: u32,
     /// (settle_similarity, max_defer): the gate settle (slideo_group_set_gate_settle), under ffi::SLIDEO_GATE_ANCHOR only: a
     /// frame away from the last matched frame is matched once it is within settle_similarity of the frame before it, or after
     /// max_defer deferred frames; a deferred frame is reported as unchanged.  (0.0, 0): off, the default.
     pub gate_settle: (f32, i32),
+    /// How a gated group call hands the gate state from device to device (slideo_group_set_gate_order), applied before
+    /// gate_reference and gate_settle: ffi::SLIDEO_GROUP_GATE_HALO (default: a later device's shard is primed from one frame) or
+    /// ffi::SLIDEO_GROUP_GATE_CHAIN (every shard receives the whole gate state of the shard before it, so the anchor reference
+    /// and a settle run on any number of devices and return what one device returns).
+    pub group_gate_order: u32,
 }
 
 impl HipImageVideoMatcher {
@@ -113,6 +118,11 @@ impl HipImageVideoMatcher {
             self.gate_reference = ffi::SLIDEO_GATE_ANCHOR;
         }
         self.gate_settle = (settle_similarity, max_defer);
+        self
+    }
+    /// Builder: the group gate order (ffi::SLIDEO_GROUP_GATE_HALO / ffi::SLIDEO_GROUP_GATE_CHAIN).
+    pub fn group_gate_order(mut self, order: u32) -> Self {
+        self.group_gate_order = order;
         self
     }
 }
@@ -130,6 +140,7 @@ impl Default for HipImageVideoMatcher {
             yuv_description: (ffi::SLIDEO_YUV_MATRIX_BT601, ffi::SLIDEO_YUV_RANGE_LIMITED, ffi::SLIDEO_YUV_DEPTH_8),
             gate_reference: ffi::SLIDEO_GATE_PREVIOUS,
             gate_settle: (0.0, 0),
+            group_gate_order: ffi::SLIDEO_GROUP_GATE_HALO,
         }
     }
 }
@@ -153,6 +164,9 @@ impl<'i> ImageVideoMatcher<'i> for HipImageVideoMatcher {
                 std::ptr::null_mut(),
                 ffi::slideo_group_create(cfg.as_ptr(), self.devices.len() as i32, devices_ptr, &mut h),
             );
+            if self.group_gate_order != ffi::SLIDEO_GROUP_GATE_HALO {
+                check(h, ffi::slideo_group_set_gate_order(h, self.group_gate_order));
+            }
             if self.gate_reference != ffi::SLIDEO_GATE_PREVIOUS {
                 check(h, ffi::slideo_group_set_gate_reference(h, self.gate_reference));
             }

@@ -941,7 +941,8 @@ int32_t     slideo_frame_mask_small(slideo_matcher* m, uint8_t* out, int64_t out
  * options returns for the same sequence of slideo_matcher_gate_reset and slideo_match_changed_frames_* calls — for every member
  * count, more members than frames included, and wherever the shard boundaries fall.  Rules 1 - 6 hold unchanged; the call's
  * arguments are checked once, before any member is touched, so a size, format or argument error leaves the state untouched.
- * How: the call is cut into the group's contiguous shards; member 0 continues the group's state, and every later non-empty shard
+ * How (under the default group gate order, SLIDEO_GROUP_GATE_HALO; SLIDEO_GROUP_GATE_CHAIN hands the whole state from shard to
+ * shard instead: "Group gate order"): the call is cut into the group's contiguous shards; member 0 continues the group's state, and every later non-empty shard
  * [lo, hi) first sets its member's state from frame lo - 1 (slideo_matcher_gate_reset_from_frame_*: the one-frame halo of
  * slideo_group_changed_mask_bgr8 as a gate state, one extra frame upload per member and call), then runs the gated call over its
  * block.  After the call the state is the last non-empty shard's member's; the next call moves it to member 0 through a host copy of
@@ -1037,7 +1038,9 @@ int32_t     slideo_group_match_changed_frames_yuv420(slideo_group* g, int32_t n_
  * SLIDEO_ERR_INVALID_ARG and the value before stays, and a change resets the gate state (the state means another frame).
  * Group: a group of one member forwards the call and returns what the single matcher returns.  With more members SLIDEO_GATE_ANCHOR
  * is SLIDEO_ERR_UNSUPPORTED and no member is changed: a shard's anchor depends on every flag before the shard, which the one-frame
- * halo that primes a shard cannot supply.  SLIDEO_GATE_PREVIOUS is always accepted.
+ * halo that primes a shard cannot supply.  SLIDEO_GATE_PREVIOUS is always accepted.  (That is the default group gate order,
+ * SLIDEO_GROUP_GATE_HALO; under SLIDEO_GROUP_GATE_CHAIN a shard receives its predecessor's whole state and SLIDEO_GATE_ANCHOR is
+ * accepted for every member count: "Group gate order".)
  * Where it runs (csrc/gate_anchor.hip.h, csrc/stage_gate_anchor.hip; gate_unit_submit's one branch): the rule is sequential — a flag
  * decides what the next frame is compared with — so a unit of n frames computes every pair it could need at once: the frames'
  * centred operand (direct_centre_kernel, its weighted instance under the gate's weights), frame_gram_kernel — <a'_i, a'_j>
@@ -1055,7 +1058,8 @@ int32_t     slideo_group_match_changed_frames_yuv420(slideo_group* g, int32_t n_
 int32_t     slideo_matcher_set_gate_reference(slideo_matcher* m, uint32_t ref);
 /* The matcher's gate reference (SLIDEO_GATE_PREVIOUS unless set).  SLIDEO_ERR_INVALID_ARG for a null argument. */
 int32_t     slideo_matcher_gate_reference(const slideo_matcher* m, uint32_t* ref);
-/* Every member idle.  More than one member: SLIDEO_GATE_ANCHOR is SLIDEO_ERR_UNSUPPORTED (above).  Resets the group's gate state. */
+/* Every member idle.  More than one member: SLIDEO_GATE_ANCHOR is SLIDEO_ERR_UNSUPPORTED (above) unless the group gate order is
+ * SLIDEO_GROUP_GATE_CHAIN.  Resets the group's gate state. */
 int32_t     slideo_group_set_gate_reference(slideo_group* g, uint32_t ref);
 /* Tap: frame_gram_kernel and the operand kernels on their own.  small: n small images of sw x sh (3 bytes per pixel, back to back, host
  * memory); ssd_out [n * n]: ssd_out[i * n + j] = the SSD of images i and j over whole images (symmetric, 0 on the diagonal), or,
@@ -1111,7 +1115,8 @@ int32_t     slideo_small_gram_ssd(slideo_matcher* m, const uint8_t* small, int32
 int32_t     slideo_matcher_set_gate_settle(slideo_matcher* m, float settle_similarity, int32_t max_defer);
 /* The matcher's gate settle (0, 0 unless set).  SLIDEO_ERR_INVALID_ARG for a null argument. */
 int32_t     slideo_matcher_gate_settle(const slideo_matcher* m, float* settle_similarity, int32_t* max_defer);
-/* Every member idle.  More than one member: settle_similarity > 0 is SLIDEO_ERR_UNSUPPORTED (above).  Resets the group's gate state. */
+/* Every member idle.  More than one member: settle_similarity > 0 is SLIDEO_ERR_UNSUPPORTED (above) unless the group gate order is
+ * SLIDEO_GROUP_GATE_CHAIN ("Group gate order").  Resets the group's gate state. */
 int32_t     slideo_group_set_gate_settle(slideo_group* g, float settle_similarity, int32_t max_defer);
 /* Tap: gate_carried_ssd_kernel on its own.  anchor_small, prev_small: one small image of sw x sh each; small: n of them back to back
  * (host memory; uploaded back to back behind the two, so odd sizes put the images at every byte alignment).  ssd_out [n + 1]:
@@ -1128,6 +1133,73 @@ int32_t     slideo_small_carried_ssd(slideo_matcher* m, const uint8_t* anchor_sm
 int32_t     slideo_gate_settle_walk(slideo_matcher* m, const uint64_t* dot, const int64_t* norm, const uint64_t* carried, int32_t n, int64_t thr_c,
                                     int64_t thr_s, int32_t max_defer, int32_t d_in, int32_t none, uint8_t* changed_out, uint64_t* ssd_out,
                                     int32_t* anchor_out, int32_t* d_out);
+
+/* ---- Gate state record (extension: the whole gate state as bytes) ------------------------------------------------------------------
+ * slideo_matcher_gate_last_small + slideo_matcher_gate_reset move the anchor alone: under a gate settle the previous frame and the
+ * deferral count d are lost (the reset sets previous = anchor, d = 0).  The record moves all of it.
+ * Layout, little-endian: a header of eight 32-bit words (32 bytes) —
+ *     0 magic 0x54534753 ("SGST")   1 version 1   2 has (0: "none", 1)   3 gate reference (SLIDEO_GATE_*)   4 settle (0: off, 1: on)
+ *     5 sw   6 sh   7 d (the deferral count; 0 without a settle)
+ * — then, has == 1: the anchor's small image, 3 * sw * sh bytes (under SLIDEO_GATE_PREVIOUS: the last small image) and, settle == 1,
+ * the previous frame's small image, 3 * sw * sh bytes.  has == 0: the header alone, sw = sh = d = 0.
+ * Definition: after slideo_matcher_gate_state_import(B, export of A) into a matcher B with A's config, pages and settings, every
+ * later gated call on B returns, bit for bit, what it would have returned on A, and so does slideo_matcher_gate_last_small.  (The
+ * record does not hold the size and format family of the frames gated so far: like slideo_matcher_gate_reset the import forgets
+ * them, and a small image whose size is not the next gated frames' is SLIDEO_ERR_STATE at that call.)
+ * Import refuses, with SLIDEO_ERR_INVALID_ARG, the rule named and B's state as it was: a size that is not the one its header
+ * describes (or shorter than a header); a bad magic or version; a record made under another gate reference, or with the settle on
+ * where B's is off or the other way round; sw x sh outside what slideo_matcher_gate_reset accepts (sw, sh >= 1, sw * sh <=
+ * small_area); d beyond B's max_defer.  A record of "none" imports as slideo_matcher_gate_reset(m, NULL, 0, 0).
+ * All three calls need an idle matcher (SLIDEO_ERR_STATE with units in flight). */
+/* The size of the record slideo_matcher_gate_state_export would write now. */
+int32_t     slideo_matcher_gate_state_bytes(slideo_matcher* m, int64_t* bytes);
+/* *bytes = the record's size, always; SLIDEO_ERR_CAPACITY when it exceeds `capacity` or out is NULL. */
+int32_t     slideo_matcher_gate_state_export(slideo_matcher* m, uint8_t* out, int64_t capacity, int64_t* bytes);
+int32_t     slideo_matcher_gate_state_import(slideo_matcher* m, const uint8_t* rec, int64_t bytes);
+
+/* ---- Group gate order (extension: how a gated group call hands the gate state from shard to shard) -----------------------------------
+ * It extends "The N-device group's form" of "Changed-frame gate".
+ *   SLIDEO_GROUP_GATE_HALO   the default, and what that section describes: every later non-empty shard [lo, hi) primes its member from
+ *                            frame lo - 1.  One frame carries neither an anchor nor a settle's state, so with more than one member
+ *                            SLIDEO_GATE_ANCHOR and a gate settle that is on are SLIDEO_ERR_UNSUPPORTED.
+ *   SLIDEO_GROUP_GATE_CHAIN  the shards of a gated group call are decided in order: each non-empty shard's member receives the complete
+ *                            gate state its predecessor left after its last frame.  SLIDEO_GATE_ANCHOR and a gate settle are accepted
+ *                            for every member count.
+ * Definition.  Under CHAIN, for every gate reference, with or without a settle, a frame mask under SLIDEO_MASK_GATE, the direct
+ * look-up or a page set, a sequence of group resets and gated group calls returns, bit for bit, what a single matcher returns for
+ * the same sequence: flags, similarities and verdicts, the trace of the k-th pipelined frame, slideo_group_gate_last_small and
+ * slideo_group_gate_state_export — for every member count, more members than frames included, and wherever the shard boundaries
+ * fall.  Under SLIDEO_GATE_PREVIOUS that is also what HALO returns.
+ * The setter needs every member idle (SLIDEO_ERR_STATE); an unknown value is SLIDEO_ERR_INVALID_ARG and the value before stays; a
+ * successful set resets the group's gate state to "none".  With more than one member, HALO together with SLIDEO_GATE_ANCHOR or a
+ * settle that is on is SLIDEO_ERR_UNSUPPORTED at whichever of the three set calls — slideo_group_set_gate_order,
+ * slideo_group_set_gate_reference, slideo_group_set_gate_settle — would complete the combination, checked before any member is
+ * touched; the values before stay.  A group of one member forwards its calls as before and never chains.
+ * How (csrc/capi_group.hip, csrc/gate_baton.h): the call is validated once and cut into the same contiguous shards; every member
+ * runs the single matcher's gated call over its shard on a thread of its own.  A later member knows on the host that it will hold
+ * a state of the call's small size, so it submits its first unit at once: staging, small images, the operand and the pair table of
+ * all members run side by side.  Where that unit would wait for the previous gated unit's write of the state it waits for its
+ * predecessor instead: behind its last unit's state write the predecessor copies the three state buffers (anchor, previous image,
+ * d) into a pinned record the group owns and publishes a baton; the successor's thread, released, queues the copy from that record
+ * on its unit's stream.  Only the carried SSDs, the walk and the state write are chained.  No kernel reads a peer's memory, so
+ * members on one device and on distinct devices take the same path.  A member that fails before it has published fails its
+ * successor's baton: every thread ends, the lowest member's error is reported and the group's state becomes "none".
+ * Between calls the group moves its state to member 0 as a record (slideo_matcher_gate_state_export / _import), not as a small image.
+ * A limit, by construction: a member's pipeline blocks at its first unit until its predecessor has decided its last frame, so a call
+ * whose shards span many units serialises the members' uploads.  One unit per shard — 64 frames per device, what the mirrors feed — is
+ * what the order is made for. */
+#define SLIDEO_GROUP_GATE_HALO 0u
+#define SLIDEO_GROUP_GATE_CHAIN 1u
+int32_t     slideo_group_set_gate_order(slideo_group* g, uint32_t order);
+/* The group's gate order (SLIDEO_GROUP_GATE_HALO unless set).  SLIDEO_ERR_INVALID_ARG for a null argument. */
+int32_t     slideo_group_gate_order(const slideo_group* g, uint32_t* order);
+/* slideo_matcher_gate_state_export / _import on the group's one state (every member idle), under either order.  A reset's small
+ * image exports as anchor = previous = that image, d = 0, as a single matcher's does. */
+int32_t     slideo_group_gate_state_export(slideo_group* g, uint8_t* out, int64_t capacity, int64_t* bytes);
+int32_t     slideo_group_gate_state_import(slideo_group* g, const uint8_t* rec, int64_t bytes);
+/* Measurement: the seconds member `member` (1 .. members - 1) blocked on the host for its predecessor's gate state in the last
+ * chained gated call (0 when it did not run).  SLIDEO_ERR_INVALID_ARG for a null argument or a member outside that range. */
+int32_t     slideo_group_gate_chain_waited(const slideo_group* g, int32_t member, double* seconds);
 
 /* ---- Direct page look-up (extension: the reference never decides without keypoints) ---------------------------------------------
  * In a screen recording the frame IS the slide, full screen, plus codec noise.  The reference's final score for a candidate is

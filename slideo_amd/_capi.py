@@ -190,6 +190,9 @@ EXPORTS = [
     "slideo_matcher_set_gate_reference", "slideo_matcher_gate_reference", "slideo_group_set_gate_reference", "slideo_small_gram_ssd",
     "slideo_matcher_set_gate_settle", "slideo_matcher_gate_settle", "slideo_group_set_gate_settle", "slideo_small_carried_ssd",
     "slideo_gate_settle_walk",
+    "slideo_matcher_gate_state_bytes", "slideo_matcher_gate_state_export", "slideo_matcher_gate_state_import",
+    "slideo_group_set_gate_order", "slideo_group_gate_order", "slideo_group_gate_state_export", "slideo_group_gate_state_import",
+    "slideo_group_gate_chain_waited",
 ]
 
 # frame mask scope (include/slideo_amd.h "Frame mask scope")
@@ -202,6 +205,10 @@ DIRECT_VALID = 1
 GATE_PREVIOUS = 0
 GATE_ANCHOR = 1
 GATE_REFERENCES = {"previous": GATE_PREVIOUS, "anchor": GATE_ANCHOR}
+# group gate order (include/slideo_amd.h "Group gate order")
+GROUP_GATE_HALO = 0
+GROUP_GATE_CHAIN = 1
+GROUP_GATE_ORDERS = {"halo": GROUP_GATE_HALO, "chain": GROUP_GATE_CHAIN}
 
 
 def gate_deferred(changed, similarity, changed_similarity):
@@ -337,6 +344,16 @@ def lib():
             L.slideo_group_set_gate_settle.argtypes = [vp, f32, i32]
             L.slideo_small_carried_ssd.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp]
             L.slideo_gate_settle_walk.argtypes = [vp, vp, vp, vp, i32, i64, i64, i32, i32, i32, vp, vp, vp, vp]
+        if hasattr(L, "slideo_group_set_gate_order"):
+            vp, i32, i64, u32 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32
+            L.slideo_matcher_gate_state_bytes.argtypes = [vp, vp]
+            L.slideo_matcher_gate_state_export.argtypes = [vp, vp, i64, vp]
+            L.slideo_matcher_gate_state_import.argtypes = [vp, vp, i64]
+            L.slideo_group_set_gate_order.argtypes = [vp, u32]
+            L.slideo_group_gate_order.argtypes = [vp, vp]
+            L.slideo_group_gate_state_export.argtypes = [vp, vp, i64, vp]
+            L.slideo_group_gate_state_import.argtypes = [vp, vp, i64]
+            L.slideo_group_gate_chain_waited.argtypes = [vp, i32, vp]
         _lib = L
     return _lib
 
@@ -441,6 +458,21 @@ class _FrameCalls:
         out = np.empty((sh.value, sw.value, 3), np.uint8)
         self._check(getattr(lib(), self._SETS + "gate_last_small")(self._h, _p(out), C.c_int64(out.size), C.byref(sw), C.byref(sh)))
         return out
+
+    def gate_state_export(self):
+        """The whole gate state as a record (include/slideo_amd.h "Gate state record") -> bytes."""
+        n = C.c_int64()
+        rc = getattr(lib(), self._SETS + "gate_state_export")(self._h, None, C.c_int64(0), C.byref(n))
+        if rc != 7:                                               # (SLIDEO_ERR_CAPACITY with the size set: the probe's answer)
+            self._check(rc)
+        out = np.zeros(max(int(n.value), 1), np.uint8)
+        self._check(getattr(lib(), self._SETS + "gate_state_export")(self._h, _p(out), C.c_int64(out.size), C.byref(n)))
+        return out[: n.value].tobytes()
+
+    def gate_state_import(self, rec):
+        """The gate state from a record of gate_state_export: every later gated call returns what the exporting matcher's would."""
+        buf = np.frombuffer(bytes(rec), np.uint8)
+        self._check(getattr(lib(), self._SETS + "gate_state_import")(self._h, _p(buf) if buf.size else None, C.c_int64(buf.size)))
 
     @staticmethod
     def _gated_out(n):
@@ -1316,6 +1348,29 @@ class Group(_FrameCalls):
     def page_set_info(self, set_id):
         """Member 0's record of set `set_id` (every member holds the same set)."""
         return self.member(0).page_set_info(set_id)
+
+    # ---- group gate order (include/slideo_amd.h "Group gate order") --------------------------------------------------------------
+    def set_gate_order(self, order):
+        """ "halo" (the default: a later shard is primed from one frame) or "chain" (every shard receives its predecessor's whole gate
+        state: ANCHOR and a gate settle run on any member count); or the GROUP_GATE_* value.  Resets the gate state."""
+        if isinstance(order, str):
+            if order not in GROUP_GATE_ORDERS:
+                raise SlideoError(1, "group gate order %r: one of %s" % (order, sorted(GROUP_GATE_ORDERS)))
+            order = GROUP_GATE_ORDERS[order]
+        if not 0 <= int(order) <= 0xFFFFFFFF:
+            raise SlideoError(1, "group gate order %r" % (order,))
+        self._check(lib().slideo_group_set_gate_order(self._h, int(order)))
+
+    def gate_order(self):
+        v = C.c_uint32()
+        self._check(lib().slideo_group_gate_order(self._h, C.byref(v)))
+        return {b: a for a, b in GROUP_GATE_ORDERS.items()}[int(v.value)]
+
+    def gate_chain_waited(self, member):
+        """Seconds member `member` (>= 1) blocked for its predecessor's gate state in the last chained gated call."""
+        s = C.c_double()
+        self._check(lib().slideo_group_gate_chain_waited(self._h, int(member), C.byref(s)))
+        return float(s.value)
 
 
 def device_count():

@@ -12,6 +12,7 @@
 //
 // No kernel lives in this unit; it only drives the members through the functions of runtime.hpp.
 #include "runtime.hpp"
+#include "gate_baton.h"
 
 #include <thread>
 
@@ -42,6 +43,25 @@ struct slideo_group {
     slideo_matcher::GateState gate;
     int gate_owner = -1;
     std::vector<uint8_t> gate_small;
+    // group gate order (include/slideo_amd.h "Group gate order").  Under CHAIN link r carries the gate state member r leaves behind
+    // its last frame to member r + 1: a pinned record {d | anchor | previous image} of the group's and the baton that says it is there.
+    uint32_t gate_order = SLIDEO_GROUP_GATE_HALO;
+    struct GateLink {
+        GateBaton baton;
+        void* rec = nullptr;
+        size_t cap = 0;
+        double waited_s = 0.0;                // how long member r + 1 blocked on the baton in the last chained call
+        ~GateLink() { if (rec) (void)hipHostFree(rec); }
+        void reserve(size_t bytes) {
+            if (bytes <= cap) return;
+            if (rec) (void)hipHostFree(rec);
+            rec = nullptr; cap = 0;
+            HIP_CHECK(hipHostMalloc(&rec, bytes, hipHostMallocPortable));      // (read by the next member's device, written by this one's)
+            cap = bytes;
+        }
+    };
+    std::vector<std::unique_ptr<GateLink>> gate_links;      // members - 1
+    std::vector<uint8_t> gate_rec;                          // the state on its way to member 0, as a record
 };
 
 namespace {
@@ -162,9 +182,48 @@ void group_gate_none(slideo_group* g) {
     g->gate_owner = -1;
 }
 
+// Group gate order CHAIN: the hand-over of one gated call over members 0 .. last_r (the non-empty shards), small images of sw x sh.
+// Link r's record: {d u32, 12 bytes unused | anchor sb | previous image sb}.  Member r > 0 is told on the host that it holds a state
+// of that size — its predecessor, a non-empty shard, always leaves one —, so its first unit reserves the state buffers and is
+// submitted at once; where that unit waits for the state (runtime.hpp gate_chain_receive) its thread blocks on the baton and then
+// queues the record's copy on the unit's stream.  Member r < last_r copies its state out behind its last unit's write of it
+// (Slot::ev_gate) and publishes.  The links' records are reserved here, before any member is touched.
+void gate_chain_arm(slideo_group* g, int last_r, int sw, int sh) {
+    const size_t sb = (size_t)sw * sh * 3;
+    for (int r = 0; r < last_r; ++r) {
+        slideo_group::GateLink& L = *g->gate_links[r];
+        L.reserve(16 + 2 * sb);
+        L.baton.reset();
+        L.waited_s = 0.0;
+    }
+    for (int r = 0; r <= last_r; ++r) {
+        slideo_matcher* m = g->members[r];
+        if (r > 0) {
+            slideo_group::GateLink* in = g->gate_links[r - 1].get();
+            m->gate = slideo_matcher::GateState{};
+            m->gate.has = true; m->gate.sw = sw; m->gate.sh = sh;
+            m->gate_receive = [m, in, sb](hipStream_t st) {
+                in->waited_s = in->baton.await();
+                uint8_t* p = static_cast<uint8_t*>(in->rec);
+                gate_state_write(m, sb, p + 16, p + 16 + sb, reinterpret_cast<const uint32_t*>(p), st);
+            };
+        }
+        if (r < last_r) {
+            slideo_group::GateLink* out = g->gate_links[r].get();
+            m->gate_publish = [m, out, sb](Slot& S) {
+                uint8_t* p = static_cast<uint8_t*>(out->rec);
+                gate_state_read(m, S.ev_gate, sb, p + 16, p + 16 + sb, reinterpret_cast<uint32_t*>(p));
+                out->baton.publish();
+            };
+        }
+    }
+}
+
 // slideo_group_match_changed_frames_bgr8 / _yuv420: member 0 continues the group's gate state; every later non-empty shard [lo, hi)
 // primes its member from frame lo - 1 (the one-frame halo of group_mask_impl, as a gate state) and runs the single matcher's gated
 // call over its block.  The pairs compared, the small images and the pipeline of the changed frames are the single matcher's.
+// Under the group gate order CHAIN (gate_chain_arm above) no shard is primed: every later member receives its predecessor's whole
+// state where its first unit waits for it, and the state travels to member 0 between calls as a record.
 void group_gated_impl(slideo_group* g, int32_t n_frames, const FrameSrc& src, uint8_t* changed_out, float* similarity_out,
                       slideo_verdict* verdicts_out) {
     const int N = (int)g->members.size();
@@ -179,11 +238,29 @@ void group_gated_impl(slideo_group* g, int32_t n_frames, const FrameSrc& src, ui
     g->match_lo.assign((size_t)N + 1, 0);
     g->kept_valid = false;
     begin_progress(g, (uint64_t)n_frames, nullptr);
+    // (a group of one never chains: it forwards)
+    const bool chain = g->gate_order == SLIDEO_GROUP_GATE_CHAIN && N > 1;
+    // whatever happens, no member keeps a hook of this call
+    struct Unhook {
+        slideo_group* g;
+        ~Unhook() { for (slideo_matcher* m : g->members) { m->gate_receive = nullptr; m->gate_publish = nullptr; } }
+    } unhook{g};
     try {
         // the state to member 0
         if (g->gate_owner != 0) {
             if (!g->gate.has) check_member_call(m0, slideo_matcher_gate_reset(m0, nullptr, 0, 0));
-            else {
+            else if (chain && g->gate_owner > 0) {
+                // the whole state, as a record: under a settle the previous frame and the deferral count travel too
+                slideo_matcher* o = g->members[g->gate_owner];
+                int64_t bytes = 0;
+                check_member_call(o, slideo_matcher_gate_state_bytes(o, &bytes));
+                g->gate_rec.resize((size_t)bytes);
+                check_member_call(o, slideo_matcher_gate_state_export(o, g->gate_rec.data(), bytes, &bytes));
+                check_member_call(m0, slideo_matcher_gate_state_import(m0, g->gate_rec.data(), bytes));
+                if (!m0->gate.has || m0->gate.sw != g->gate.sw || m0->gate.sh != g->gate.sh)
+                    fail(SLIDEO_ERR_STATE, "member %d holds a %dx%d gate state (%d), the group's is %dx%d (a member was gated directly)", g->gate_owner,
+                         m0->gate.sw, m0->gate.sh, (int)m0->gate.has, g->gate.sw, g->gate.sh);
+            } else {
                 if (g->gate_owner > 0) {
                     slideo_matcher* o = g->members[g->gate_owner];
                     int32_t sw = 0, sh = 0;
@@ -199,11 +276,19 @@ void group_gated_impl(slideo_group* g, int32_t n_frames, const FrameSrc& src, ui
         }
         int last_r = 0;
         for (int r = 0; r < N; ++r) { int lo, hi; shard_range(n_frames, r, N, lo, hi); if (hi > lo) last_r = r; }
+        if (chain) gate_chain_arm(g, last_r, checked.plan.sw, checked.plan.sh);
         for_each_member(g, [&](int r) {
             int lo, hi;
             shard_range(n_frames, r, N, lo, hi);
-            if (hi <= lo) return;
+            if (hi <= lo) return;               // (the empty shards are the trailing ones: the chain ends at last_r)
             slideo_matcher* m = g->members[r];
+            if (chain) {
+                // dropped unpublished — this member threw before its last unit's state was handed over — it releases the successor
+                GateBatonGuard owed(r < last_r ? &g->gate_links[r]->baton : nullptr);
+                match_frames_impl(m, hi - lo, src.from(lo), verdicts_out + lo, nullptr, true, changed_out + lo,
+                                  similarity_out ? similarity_out + lo : nullptr);
+                return;
+            }
             if (r > 0) {
                 FrameSrc halo = src.from(lo - 1);
                 if (halo.yuv) halo.frame_stride = -1;           // (a single frame: no stride to check)
@@ -300,6 +385,7 @@ int32_t slideo_group_create(const slideo_config* cfg, int32_t n_devices, const i
         if (rc != SLIDEO_OK) fail(rc, "member %d (device %d): %s", i, devices[i], slideo_last_error(nullptr));
         g->members.push_back(m);
     }
+    for (int i = 1; i < n_devices; ++i) g->gate_links.emplace_back(new slideo_group::GateLink());
     g->tramps.resize((size_t)n_devices);
     for (auto& t : g->tramps) t.g = g.get();
     guard.g = nullptr;
@@ -366,12 +452,32 @@ int32_t slideo_group_set_yuv_description(slideo_group* g, int32_t matrix, int32_
     return group_set(g, SET_YUV_DESCRIPTION, [&](const FrameSettings& s) { return propose_yuv_description(s, matrix, range, depth); });
 }
 
-// (the group's own rule first: ANCHOR needs a group of one member, and a refused call changes no member)
+// (the group's own rule first: ANCHOR needs a group of one member or the gate order CHAIN, and a refused call changes no member)
 int32_t slideo_group_set_gate_reference(slideo_group* g, uint32_t ref) {
     return group_set(g, SET_GATE_REFERENCE, [&](const FrameSettings& s) {
-        gate_reference_group_rule((int)g->members.size(), ref);
+        gate_reference_group_rule((int)g->members.size(), ref, g->gate_order);
         return propose_gate_reference(s, ref);
     });
+}
+
+// Group gate order (include/slideo_amd.h "Group gate order"): the group's own value, beside the members' frame settings.  Validated
+// before anything changes: the value, every member idle, the rule against the members' gate reference and settle.
+int32_t slideo_group_set_gate_order(slideo_group* g, uint32_t order) {
+    if (!g) return SLIDEO_ERR_INVALID_ARG;
+    GROUP_TRY
+    const uint32_t next = propose_group_gate_order(order);
+    for (slideo_matcher* m : g->members) require_idle(m);
+    const FrameSettings& fs = g->members[0]->fs;        // (the group's setters keep every member's alike)
+    group_gate_order_rule((int)g->members.size(), next, fs.gate_ref, fs.settle_similarity);
+    g->gate_order = next;
+    group_gate_none(g);
+    GROUP_CATCH(g)
+}
+
+int32_t slideo_group_gate_order(const slideo_group* g, uint32_t* order) {
+    if (!g || !order) return SLIDEO_ERR_INVALID_ARG;
+    *order = g->gate_order;
+    return SLIDEO_OK;
 }
 
 // (the gate settle is part of the gate-reference setting; behind the range check the group's own rule: settle on needs a group of one
@@ -379,7 +485,7 @@ int32_t slideo_group_set_gate_reference(slideo_group* g, uint32_t ref) {
 int32_t slideo_group_set_gate_settle(slideo_group* g, float settle_similarity, int32_t max_defer) {
     return group_set(g, SET_GATE_REFERENCE, [&](const FrameSettings& s) {
         const FrameSettings next = propose_gate_settle(s, settle_similarity, max_defer);
-        gate_settle_group_rule((int)g->members.size(), settle_similarity);
+        gate_settle_group_rule((int)g->members.size(), settle_similarity, g->gate_order);
         return next;
     });
 }
@@ -553,6 +659,51 @@ int32_t slideo_group_gate_last_small(slideo_group* g, uint8_t* out, int64_t out_
     *sw = g->gate.sw; *sh = g->gate.sh;
     if ((int64_t)g->gate_small.size() > out_capacity) fail(SLIDEO_ERR_CAPACITY, "small image needs %lld bytes", (long long)g->gate_small.size());
     if (out) std::memcpy(out, g->gate_small.data(), g->gate_small.size());
+    GROUP_CATCH(g)
+}
+
+int32_t slideo_group_gate_chain_waited(const slideo_group* g, int32_t member, double* seconds) {
+    if (!g || !seconds || member < 1 || member >= (int)g->members.size()) return SLIDEO_ERR_INVALID_ARG;
+    *seconds = g->gate_links[(size_t)member - 1]->waited_s;
+    return SLIDEO_OK;
+}
+
+// The group's one state as a record: its owner's, or — a reset's small image — what a single matcher exports after that reset
+int32_t slideo_group_gate_state_export(slideo_group* g, uint8_t* out, int64_t capacity, int64_t* bytes) {
+    if (!g) return SLIDEO_ERR_INVALID_ARG;
+    GROUP_TRY
+    if (!bytes) fail(SLIDEO_ERR_INVALID_ARG, "null bytes");
+    for (slideo_matcher* m : g->members) require_idle(m);
+    if (g->gate.has && g->gate_owner >= 0) {
+        slideo_matcher* o = g->members[g->gate_owner];
+        check_member_call(o, slideo_matcher_gate_state_export(o, out, capacity, bytes));
+        return SLIDEO_OK;
+    }
+    const FrameSettings& fs = g->members[0]->fs;
+    GateRecordHead h;
+    h.has = g->gate.has; h.gate_ref = fs.gate_ref; h.settle = fs.settle_similarity > 0.f;
+    if (h.has) { h.sw = g->gate.sw; h.sh = g->gate.sh; }
+    *bytes = h.bytes();
+    if (!out || h.bytes() > capacity) fail(SLIDEO_ERR_CAPACITY, "the gate state record needs %lld bytes", (long long)h.bytes());
+    gate_record_encode(h, out);
+    if (h.has) {
+        std::memcpy(out + GATE_RECORD_HEADER, g->gate_small.data(), g->gate_small.size());
+        if (h.settle) std::memcpy(out + GATE_RECORD_HEADER + g->gate_small.size(), g->gate_small.data(), g->gate_small.size());
+    }
+    GROUP_CATCH(g)
+}
+
+// ... and back: into member 0, where the next gated call's first frame is compared (a refused record leaves the group's state)
+int32_t slideo_group_gate_state_import(slideo_group* g, const uint8_t* rec, int64_t bytes) {
+    if (!g) return SLIDEO_ERR_INVALID_ARG;
+    GROUP_TRY
+    slideo_matcher* m0 = g->members[0];
+    (void)gate_record_validate(rec, bytes, m0->fs.gate_ref, m0->fs.settle_similarity, m0->fs.settle_max_defer, m0->cfg.small_area);
+    for (slideo_matcher* m : g->members) require_idle(m);
+    check_member_call(m0, slideo_matcher_gate_state_import(m0, rec, bytes));
+    group_gate_none(g);
+    g->gate = m0->gate;
+    g->gate_owner = 0;
     GROUP_CATCH(g)
 }
 

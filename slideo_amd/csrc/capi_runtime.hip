@@ -402,6 +402,8 @@ void match_frames_impl(slideo_matcher* m, int n, FrameSrc src, slideo_verdict* o
             m->next_slot = (m->next_slot + 1) % NSLOTS;
             unit_begin(m, S, src, i, std::min(unit, n - i), cs, gated);
             pend.push_back({&S, i});
+            // a chained group call: the state behind the call's last unit goes to the successor while this member's pipeline runs on
+            if (gated && i + unit >= n && m->gate_publish) m->gate_publish(S);
         }
         for (Pending& p : pend) collect(p);
         m->units_pending = false;

@@ -142,19 +142,90 @@ inline FrameSettings propose_gate_settle(FrameSettings s, float settle_similarit
     s.settle_similarity = settle_similarity; s.settle_max_defer = max_defer;
     return s;
 }
-// The group's rule for a gate settle (include/slideo_amd.h "Gate settle"): it needs ANCHOR, which needs a group of one member.
-// Setting it off always passes.
-inline void gate_settle_group_rule(int members, float settle_similarity) {
-    if (settle_similarity > 0.f && members > 1)
+// The group's rule for a gate settle (include/slideo_amd.h "Gate settle"): it needs ANCHOR, which needs a group of one member
+// or the group gate order CHAIN ("Group gate order").  Setting it off always passes.
+inline void gate_settle_group_rule(int members, float settle_similarity, uint32_t order = SLIDEO_GROUP_GATE_HALO) {
+    if (settle_similarity > 0.f && members > 1 && order != SLIDEO_GROUP_GATE_CHAIN)
         fail(SLIDEO_ERR_UNSUPPORTED, "a gate settle in a group of %d members: it runs under SLIDEO_GATE_ANCHOR, which a group of more than "
              "one member does not support (a group of one member, or a single matcher)", members);
 }
 // The group's rule for a gate reference (include/slideo_amd.h "Gate reference"): a shard's anchor depends on every flag before the
-// shard, which the one-frame halo that primes a shard cannot supply, so ANCHOR needs a group of one member.  PREVIOUS always passes.
-inline void gate_reference_group_rule(int members, uint32_t ref) {
-    if (ref == SLIDEO_GATE_ANCHOR && members > 1)
+// shard, which the one-frame halo that primes a shard cannot supply, so ANCHOR needs a group of one member — or the group gate order
+// CHAIN, under which a shard receives its predecessor's whole state ("Group gate order").  PREVIOUS always passes.
+inline void gate_reference_group_rule(int members, uint32_t ref, uint32_t order = SLIDEO_GROUP_GATE_HALO) {
+    if (ref == SLIDEO_GATE_ANCHOR && members > 1 && order != SLIDEO_GROUP_GATE_CHAIN)
         fail(SLIDEO_ERR_UNSUPPORTED, "gate reference SLIDEO_GATE_ANCHOR in a group of %d members: a shard's anchor depends on every flag before "
              "the shard, and the one frame that primes a shard cannot supply it (a group of one member, or a single matcher)", members);
+}
+// The group gate order's proposal and its rule (include/slideo_amd.h "Group gate order"): HALO primes a shard from one frame, which
+// carries neither an anchor nor a settle's state, so with more than one member it stands beside PREVIOUS without a settle only.  The
+// third of the three set calls that can complete the refused combination.
+inline uint32_t propose_group_gate_order(uint32_t order) {
+    if (order != SLIDEO_GROUP_GATE_HALO && order != SLIDEO_GROUP_GATE_CHAIN)
+        fail(SLIDEO_ERR_INVALID_ARG, "group gate order %u: SLIDEO_GROUP_GATE_HALO (0) or SLIDEO_GROUP_GATE_CHAIN (1)", order);
+    return order;
+}
+inline void group_gate_order_rule(int members, uint32_t order, uint32_t gate_ref, float settle_similarity) {
+    if (order == SLIDEO_GROUP_GATE_CHAIN || members <= 1) return;
+    if (gate_ref == SLIDEO_GATE_ANCHOR || settle_similarity > 0.f)
+        fail(SLIDEO_ERR_UNSUPPORTED, "group gate order SLIDEO_GROUP_GATE_HALO in a group of %d members under %s: the one frame that primes a shard "
+             "carries neither an anchor nor a settle's state (slideo_group_set_gate_settle(g, 0, 0) and "
+             "slideo_group_set_gate_reference(g, SLIDEO_GATE_PREVIOUS) before going back)", members,
+             settle_similarity > 0.f ? "a gate settle" : "SLIDEO_GATE_ANCHOR");
+}
+
+// ---- the gate state as a record (include/slideo_amd.h "Gate state record") ---------------------------------------------------------
+// A fixed little-endian header of GATE_RECORD_HEADER bytes — magic, version, has, gate reference, settle on, sw, sh, d: eight 32-bit
+// words — then, has: the anchor's small image (under PREVIOUS: the last small image) and, under a settle, the previous frame's, 3 *
+// sw * sh bytes each.  "none": the header alone, sw = sh = d = 0.
+constexpr uint32_t GATE_RECORD_MAGIC = 0x54534753u;      // "SGST"
+constexpr uint32_t GATE_RECORD_VERSION = 1;
+constexpr int64_t GATE_RECORD_HEADER = 32;
+struct GateRecordHead {
+    bool has = false;
+    uint32_t gate_ref = SLIDEO_GATE_PREVIOUS;
+    bool settle = false;
+    int32_t sw = 0, sh = 0;
+    uint32_t d = 0;
+    int64_t image_bytes() const { return has ? (int64_t)sw * sh * 3 : 0; }
+    int64_t bytes() const { return GATE_RECORD_HEADER + image_bytes() * (settle ? 2 : 1); }
+};
+inline void gate_record_put32(uint8_t* p, uint32_t v) { for (int i = 0; i < 4; ++i) p[i] = (uint8_t)(v >> (8 * i)); }
+inline uint32_t gate_record_get32(const uint8_t* p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
+inline void gate_record_encode(const GateRecordHead& h, uint8_t* out32) {
+    const uint32_t w[8] = {GATE_RECORD_MAGIC, GATE_RECORD_VERSION, h.has ? 1u : 0u, h.gate_ref, h.settle ? 1u : 0u, (uint32_t)h.sw, (uint32_t)h.sh, h.d};
+    for (int i = 0; i < 8; ++i) gate_record_put32(out32 + 4 * i, w[i]);
+}
+// The header of a record of `bytes` bytes for a matcher under (gate_ref, settle_similarity, max_defer, small_area): every refusal is
+// SLIDEO_ERR_INVALID_ARG with the rule named; nothing is written anywhere.
+inline GateRecordHead gate_record_validate(const uint8_t* rec, int64_t bytes, uint32_t gate_ref, float settle_similarity, int32_t max_defer,
+                                           int small_area) {
+    if (!rec) fail(SLIDEO_ERR_INVALID_ARG, "gate state record: null record");
+    if (bytes < GATE_RECORD_HEADER)
+        fail(SLIDEO_ERR_INVALID_ARG, "gate state record: %lld bytes, the header alone takes %lld", (long long)bytes, (long long)GATE_RECORD_HEADER);
+    uint32_t w[8];
+    for (int i = 0; i < 8; ++i) w[i] = gate_record_get32(rec + 4 * i);
+    if (w[0] != GATE_RECORD_MAGIC) fail(SLIDEO_ERR_INVALID_ARG, "gate state record: magic %08x is not %08x", w[0], GATE_RECORD_MAGIC);
+    if (w[1] != GATE_RECORD_VERSION) fail(SLIDEO_ERR_INVALID_ARG, "gate state record: version %u, this library reads version %u", w[1], GATE_RECORD_VERSION);
+    if (w[2] > 1 || w[4] > 1) fail(SLIDEO_ERR_INVALID_ARG, "gate state record: has %u and settle %u must be 0 or 1", w[2], w[4]);
+    GateRecordHead h;
+    h.has = w[2] == 1; h.gate_ref = w[3]; h.settle = w[4] == 1; h.sw = (int32_t)w[5]; h.sh = (int32_t)w[6]; h.d = w[7];
+    const bool settle = settle_similarity > 0.f;
+    if (h.gate_ref != gate_ref)
+        fail(SLIDEO_ERR_INVALID_ARG, "gate state record: made under gate reference %u, the matcher's is %u", h.gate_ref, gate_ref);
+    if (h.settle != settle)
+        fail(SLIDEO_ERR_INVALID_ARG, "gate state record: made with the gate settle %s, the matcher's is %s", h.settle ? "on" : "off", settle ? "on" : "off");
+    if (!h.has) {
+        if (h.sw != 0 || h.sh != 0 || h.d != 0) fail(SLIDEO_ERR_INVALID_ARG, "gate state record: a record of \"none\" with sw %d, sh %d, d %u", h.sw, h.sh, h.d);
+    } else {
+        // (slideo_matcher_gate_reset's size check)
+        if (h.sw < 1 || h.sh < 1 || (int64_t)h.sw * h.sh > small_area)
+            fail(SLIDEO_ERR_INVALID_ARG, "gate state record: a %dx%d small image (at most small_area = %d pixels)", h.sw, h.sh, small_area);
+        if (h.d > (settle ? (uint32_t)max_defer : 0u))
+            fail(SLIDEO_ERR_INVALID_ARG, "gate state record: deferral count %u beyond the matcher's max_defer %d", h.d, settle ? max_defer : 0);
+    }
+    if (bytes != h.bytes()) fail(SLIDEO_ERR_INVALID_ARG, "gate state record: %lld bytes, its header describes %lld", (long long)bytes, (long long)h.bytes());
+    return h;
 }
 // frames per gated unit under SLIDEO_GATE_ANCHOR: the unit's table of dot products takes 8 n^2 bytes
 constexpr int GATE_ANCHOR_MAX_UNIT = 1024;

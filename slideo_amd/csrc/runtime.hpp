@@ -1,6 +1,8 @@
 // runtime.hpp — the host runtime behind include/slideo_amd.h, shared by its translation units.
 //
-//   frame_settings.h   (plain C++) the frame settings record, the setters' range checks, the rules between settings, what a change ends
+//   frame_settings.h   (plain C++) the frame settings record, the setters' range checks, the rules between settings, what a change ends,
+//                      the group gate order's rule and the gate state record's header
+//   gate_baton.h       (plain C++) the host baton of the group gate chain: publish, fail, await and the guard
 //   capi_runtime.hip   handles, page database, slots, the frame settings' one commit path and their set calls, a call's frames resolved
 //                      (FrameSrc -> FramePlan) and staged (-> DevFrames), unit submit / collect, the drivers of the frame calls
 //                      (pipeline, submit, collect: plain and gated) and their entry points
@@ -9,7 +11,7 @@
 //   stage_verify.hip   vote .. verdict, small img (kernels: verify.hip.h, homography.hip.h)
 //   stage_sift.hip     SIFT stage + entry points  (kernels: sift.hip.h)
 //   stage_page_set.hip page sets: a subset's search operand built from the finalized deck (kernels: page_set.hip.h)
-//   stage_gate.hip     changed-frame gate: gated units, the gate state and its entry points (kernels: gate.hip.h)
+//   stage_gate.hip     changed-frame gate: gated units, the gate state, its record and its entry points (kernels: gate.hip.h)
 //   stage_direct.hip   direct page look-up: the page operand, a gated unit's look-up, its entry points (kernels: direct.hip.h)
 //   stage_ssd_table.hip  the SSD-table engine under the direct page look-up and the gate reference ANCHOR: the centred operand, the
 //                      table of dot products on the int8 matrix cores, the taps' validity map (kernels: ssd_table.hip.h)
@@ -18,7 +20,7 @@
 //   stage_gate_anchor.hip  gate reference ANCHOR and its gate settle: a gated unit's pair table, carried SSDs, walk and state, the two
 //                      settings and the taps (kernels: gate_anchor.hip.h)
 //   capi_taps.hip      debug taps of the parity tests
-//   capi_group.hip     the N-device group (slideo_group_*)
+//   capi_group.hip     the N-device group (slideo_group_*), the group gate order and its hand-over from member to member
 //
 // Every kernel header is compiled by exactly one unit; what crosses units is the functions declared below and the plain
 // records of types.h.  There is no CPU fallback anywhere in here.
@@ -28,6 +30,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -371,6 +374,12 @@ struct slideo_matcher {
     // previous gated frame and the deferral count (u32), written and read where d_gate_small is
     slideo::DevBuf d_gate_prev, d_gate_d;
     hipEvent_t last_gate_ev = nullptr;
+    // group gate chain (include/slideo_amd.h "Group gate order"; capi_group.hip sets both for ONE gated call, a single matcher never).
+    // gate_receive: called once, on the first gated unit's stream, exactly where that unit waits for the previous gated unit's write of
+    // the state — it blocks the host until the predecessor's state has arrived and queues its copy into the three state buffers.
+    // gate_publish: called once behind the submission of the call's last unit, whose ev_gate marks the state the successor receives.
+    std::function<void(hipStream_t)> gate_receive;
+    std::function<void(slideo::Slot&)> gate_publish;
 
     // frame activity map (include/slideo_amd.h "Frame activity map"): the accumulator — "none" (on false), empty (aw 0) or the counts
     // of `pairs` consecutive pairs of aw x ah analysed images — and its device buffers: the counts (u32), the carried last image, the
@@ -568,6 +577,19 @@ void gate_check(const slideo_matcher::GateState& g, const FrameSrc& src);
 // slideo_matcher_gate_reset_from_frame_*: the gate state of an idle matcher := the small image of the ONE frame of src (frame_stride
 // as of a single frame), staged as a gated unit stages it; user_stream: the stream a device frame was produced on
 void gate_prime(slideo_matcher* m, FrameSrc src, hipStream_t user_stream);
+// The gate state's device buffers (include/slideo_amd.h "Gate state record"): gate_state_read copies the anchor (sb bytes) and, under
+// a settle, the previous image and the deferral count to host memory behind `behind` (may be null) on the matcher's copy stream, and
+// waits for them; gate_state_write reserves the buffers and queues the opposite copies on st (the host memory stays valid and
+// unchanged until st has run them).
+void gate_state_read(slideo_matcher* m, hipEvent_t behind, size_t sb, uint8_t* anchor, uint8_t* prev, uint32_t* d);
+void gate_state_write(slideo_matcher* m, size_t sb, const uint8_t* anchor, const uint8_t* prev, const uint32_t* d, hipStream_t st);
+// the pending hand-over of a chained group call, where a gated unit waits for the state (no-op on a single matcher)
+inline void gate_chain_receive(slideo_matcher* m, hipStream_t st) {
+    if (!m->gate_receive) return;
+    const std::function<void(hipStream_t)> f = std::move(m->gate_receive);
+    m->gate_receive = nullptr;
+    f(st);
+}
 // One gated unit on slot S: frames [first, first + n) of src through the gate, the changed ones through unit_submit (S.n = their
 // count, 0: no pipeline ran); its collect: flags and similarities of all n frames, verdicts of the changed ones
 void gate_unit_submit(slideo_matcher* m, Slot& S, const FrameSrc& src, int first, int n, hipStream_t cs);

@@ -112,6 +112,28 @@ void gate_prime(slideo_matcher* m, FrameSrc src, hipStream_t user_stream) {
     m->gate.has = true; m->gate.sw = src.plan.sw; m->gate.sh = src.plan.sh;
 }
 
+void gate_state_read(slideo_matcher* m, hipEvent_t behind, size_t sb, uint8_t* anchor, uint8_t* prev, uint32_t* d) {
+    hipStream_t st = m->copy_st;
+    const bool settle = m->fs.settle_similarity > 0.f;
+    if (behind) HIP_CHECK(hipStreamWaitEvent(st, behind, 0));
+    HIP_CHECK(hipMemcpyAsync(anchor, m->d_gate_small.p, sb, hipMemcpyDeviceToHost, st));
+    if (settle) {
+        HIP_CHECK(hipMemcpyAsync(prev, m->d_gate_prev.p, sb, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipMemcpyAsync(d, m->d_gate_d.p, 4, hipMemcpyDeviceToHost, st));
+    }
+    HIP_CHECK(hipStreamSynchronize(st));
+}
+
+void gate_state_write(slideo_matcher* m, size_t sb, const uint8_t* anchor, const uint8_t* prev, const uint32_t* d, hipStream_t st) {
+    const bool settle = m->fs.settle_similarity > 0.f;
+    m->d_gate_small.reserve(sb);                    // (every allocation in front of the first write of the state)
+    if (settle) { m->d_gate_prev.reserve(sb); m->d_gate_d.reserve(16); }
+    HIP_CHECK(hipMemcpyAsync(m->d_gate_small.p, anchor, sb, hipMemcpyHostToDevice, st));
+    if (!settle) return;
+    HIP_CHECK(hipMemcpyAsync(m->d_gate_prev.p, prev, sb, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemcpyAsync(m->d_gate_d.p, d, 4, hipMemcpyHostToDevice, st));
+}
+
 // One gated unit: frames [first, first + n) of src through the gate, the changed ones through unit_submit.  One short host wait
 // in the middle (the kept count), as the exact-size path's orb_wait_info: the other slots' units keep the GPU busy meanwhile.
 void gate_unit_submit(slideo_matcher* m, Slot& S, const FrameSrc& src, int first, int n, hipStream_t cs) {
@@ -159,6 +181,7 @@ void gate_unit_submit(slideo_matcher* m, Slot& S, const FrameSrc& src, int first
         // pair i: (small[i - 1], small[i]); pair 0: (gate state, small[0]), behind the previous gated unit's write of the state
         if (n > 1) launch_gate_ssd(weights, small, sb, small + sb, sb, sb, ssd + 1, n - 1, st);
         if (m->last_gate_ev && m->last_gate_ev != S.ev_gate) HIP_CHECK(hipStreamWaitEvent(st, m->last_gate_ev, 0));
+        gate_chain_receive(m, st);                  // (a chained group call's later member: the predecessor's state arrives here)
         if (!force0) launch_gate_ssd(weights, m->d_gate_small.as<uint8_t>(), 0, small, 0, sb, ssd, 1, st);
         HIP_CHECK(hipMemcpyAsync(m->d_gate_small.p, small + sb * (n - 1), (size_t)sb, hipMemcpyDeviceToDevice, st));
     }
@@ -249,6 +272,14 @@ void gate_unit_collect(slideo_matcher* m, Slot& S, uint8_t* changed_out, float* 
     if (r != g.k) fail(SLIDEO_ERR_HIP, "internal: %d frames scattered, the pipeline ran for %d", r, g.k);
 }
 
+// the header of m's gate state as a record, d still to be read from the device
+static GateRecordHead gate_record_head_of(const slideo_matcher* m) {
+    GateRecordHead h;
+    h.has = m->gate.has; h.gate_ref = m->fs.gate_ref; h.settle = m->fs.settle_similarity > 0.f;
+    if (h.has) { h.sw = m->gate.sw; h.sh = m->gate.sh; }
+    return h;
+}
+
 }  // namespace slideo
 
 extern "C" {
@@ -328,6 +359,51 @@ int32_t slideo_matcher_gate_last_small(slideo_matcher* m, uint8_t* out, int64_t 
         HIP_CHECK(hipMemcpyAsync(out, m->d_gate_small.p, (size_t)sb, hipMemcpyDeviceToHost, m->stream));
         HIP_CHECK(hipStreamSynchronize(m->stream));
     }
+    API_CATCH(m)
+}
+
+// ---- the gate state as a record (include/slideo_amd.h "Gate state record"; the header: frame_settings.h) -----------------------------
+int32_t slideo_matcher_gate_state_bytes(slideo_matcher* m, int64_t* bytes) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    if (!bytes) fail(SLIDEO_ERR_INVALID_ARG, "null bytes");
+    require_idle(m);
+    *bytes = gate_record_head_of(m).bytes();
+    API_CATCH(m)
+}
+
+int32_t slideo_matcher_gate_state_export(slideo_matcher* m, uint8_t* out, int64_t capacity, int64_t* bytes) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    if (!bytes) fail(SLIDEO_ERR_INVALID_ARG, "null bytes");
+    require_idle(m);
+    GateRecordHead h = gate_record_head_of(m);
+    *bytes = h.bytes();
+    if (!out || h.bytes() > capacity) fail(SLIDEO_ERR_CAPACITY, "the gate state record needs %lld bytes", (long long)h.bytes());
+    if (h.has) {
+        HIP_CHECK(hipSetDevice(m->device));
+        for (Slot& S : m->slots) HIP_CHECK(hipStreamSynchronize(S.st));          // (a collected unit's write of the state may still be running)
+        const size_t sb = (size_t)h.image_bytes();
+        gate_state_read(m, m->last_gate_ev, sb, out + GATE_RECORD_HEADER, out + GATE_RECORD_HEADER + sb, &h.d);
+    }
+    gate_record_encode(h, out);
+    API_CATCH(m)
+}
+
+int32_t slideo_matcher_gate_state_import(slideo_matcher* m, const uint8_t* rec, int64_t bytes) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    const GateRecordHead h = gate_record_validate(rec, bytes, m->fs.gate_ref, m->fs.settle_similarity, m->fs.settle_max_defer, m->cfg.small_area);
+    require_idle(m);
+    if (!h.has) { gate_state_reset(m); return SLIDEO_OK; }
+    HIP_CHECK(hipSetDevice(m->device));
+    const size_t sb = (size_t)h.image_bytes();
+    const uint32_t d = h.d;
+    if (m->last_gate_ev) HIP_CHECK(hipStreamWaitEvent(m->stream, m->last_gate_ev, 0));
+    gate_state_write(m, sb, rec + GATE_RECORD_HEADER, rec + GATE_RECORD_HEADER + sb, &d, m->stream);
+    HIP_CHECK(hipStreamSynchronize(m->stream));      // (the record and d are the caller's and this frame's)
+    gate_state_reset(m);
+    m->gate.has = true; m->gate.sw = h.sw; m->gate.sh = h.sh;
     API_CATCH(m)
 }
 

@@ -76,6 +76,7 @@ void gate_anchor_unit(slideo_matcher* m, Slot& S, const uint8_t* weights, const 
     // the carried anchor against the unit's frames and, under a settle, the carried previous frame against frame 0, behind the
     // previous gated unit's write of the state
     if (wait) HIP_CHECK(hipStreamWaitEvent(st, wait, 0));
+    gate_chain_receive(m, st);                      // (a chained group call's later member: the predecessor's state arrives here)
     if (!force0) launch_carried_ssd(weights, m->d_gate_small.as<uint8_t>(), prev, small, sb, n, ga_carried(S, n), st);
     gate_settle_kernel<<<1, 64, 0, st>>>(S.d_ga_dot.as<unsigned long long>(), ga_norm(S), ga_carried(S, n), n, thr, thr_s, (uint32_t)max_defer, d_state,
                                           force0 ? 1 : 0, out.flags, out.idx, out.count, out.h_head, out.h_ssd, out.h_idx, out.h_flag, ga_anchor(S, n),

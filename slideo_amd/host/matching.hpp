@@ -381,6 +381,10 @@ public:
         settle_similarity_ = settle_similarity; settle_max_defer_ = max_defer;
         return *this;
     }
+    // The group gate order (slideo_group_set_gate_order, include/slideo_amd.h "Group gate order"), applied before the gate reference
+    // and the settle: SLIDEO_GROUP_GATE_HALO (default: a later device's shard is primed from one frame) or SLIDEO_GROUP_GATE_CHAIN
+    // (every shard receives the whole gate state of the shard before it: SLIDEO_GATE_ANCHOR and a settle on any number of devices)
+    HipImageVideoMatcher& with_group_gate_order(uint32_t order) { gate_order_ = order; return *this; }
     // false: tasks run the stop-and-go pair slideo_group_changed_mask_bgr8 + slideo_group_match_kept_frames in place of the group's
     // gated call (the same timeline; for comparisons).  Default: gated
     HipImageVideoMatcher& with_changed_gate(bool on) { gated_ = on; return *this; }
@@ -392,6 +396,7 @@ public:
         if (rc != SLIDEO_OK) throw std::runtime_error(std::string("slideo_amd error ") + std::to_string(rc) + ": " + slideo_group_last_error(nullptr));
         h->n_devices = (int)slideo_group_device_count(h->g);
         h->gated = gated_;
+        if (gate_order_ != SLIDEO_GROUP_GATE_HALO) h->check(slideo_group_set_gate_order(h->g, gate_order_));
         if (gate_ref_ != SLIDEO_GATE_PREVIOUS) h->check(slideo_group_set_gate_reference(h->g, gate_ref_));
         if (settle_similarity_ != 0.f) h->check(slideo_group_set_gate_settle(h->g, settle_similarity_, settle_max_defer_));
         if (sift_on_) {                                                                             // the north-star's SIFT + L2 front end
@@ -437,6 +442,7 @@ private:
     int32_t mask_w_ = 0, mask_h_ = 0;
     int32_t yuv_matrix_ = SLIDEO_YUV_MATRIX_BT601, yuv_range_ = SLIDEO_YUV_RANGE_LIMITED, yuv_depth_ = SLIDEO_YUV_DEPTH_8;
     uint32_t mask_scope_ = SLIDEO_MASK_DETECT, direct_scope_ = SLIDEO_DIRECT_WHOLE, gate_ref_ = SLIDEO_GATE_PREVIOUS;
+    uint32_t gate_order_ = SLIDEO_GROUP_GATE_HALO;
     float settle_similarity_ = 0.f;
     int32_t settle_max_defer_ = 0;
     slideo_config cfg_;

@@ -349,7 +349,8 @@ class HipImageVideoMatcher:
     """Drop-in for OpenCVImageVideoMatcher (lib.rs:34-73) behind matching::ImageVideoMatcher."""
 
     def __init__(self, cfg=None, device=None, sift=None, devices=None, working_size=None, frame_mask=None, frame_mask_scope=None,
-                 direct_similarity=None, direct_scope=None, frame_region=None, yuv_description=None, gate_reference=None, gate_settle=None):
+                 direct_similarity=None, direct_scope=None, frame_region=None, yuv_description=None, gate_reference=None, gate_settle=None,
+                 group_gate_order=None):
         """devices: HIP ordinals, one matcher each behind one slideo_group (the reference fans out over the whole machine, the
         global rayon pool of lib.rs:45,174); None = every gfx950 device of the node; `device` = d is short for devices = [d].
         sift = (slideo_sift_config, ratio): the north-star's SIFT + L2 front end instead of the reference's ORB + Hamming
@@ -380,12 +381,15 @@ class HipImageVideoMatcher:
         files hold 8-bit samples, so depth stays 8 for them; None = BT.601 limited, 8-bit.
         gate_reference = "previous" or "anchor" (slideo_group_set_gate_reference): with "anchor" a frame is compared with the last
         frame that was flagged, not the frame before it, so a change spread over many frames (a cross-fade, an animated build) is
-        still flagged when every decoded frame is fed; one device only — with several the group refuses it here, when it is built
-        (SLIDEO_ERR_UNSUPPORTED); None = "previous", the reference's MarkSimilarIter.
+        still flagged when every decoded frame is fed; with several devices it needs group_gate_order = "chain" — without it the
+        group refuses it here, when it is built (SLIDEO_ERR_UNSUPPORTED); None = "previous", the reference's MarkSimilarIter.
         gate_settle = (similarity, max_defer) (slideo_group_set_gate_settle), under gate_reference "anchor" only: a frame away
         from the last matched frame is matched once it is within `similarity` of the frame before it — the picture stands
         still — or after max_defer deferred frames, so a cross-fade costs one verdict, not one for every second frame of it; a
-        deferred frame is reported as unchanged; None = off."""
+        deferred frame is reported as unchanged; None = off.
+        group_gate_order = "halo" or "chain" (slideo_group_set_gate_order), applied before gate_reference and gate_settle: with
+        "chain" every device's shard of a gated call receives the whole gate state of the shard before it, so "anchor" and a
+        settle run on any number of devices and return what one device returns; None = "halo", a shard primed from one frame."""
         self._cfg, self._sift = cfg, sift
         self._working_size = working_size
         self._frame_mask = frame_mask
@@ -396,12 +400,15 @@ class HipImageVideoMatcher:
         self._yuv_description = tuple(yuv_description) if yuv_description is not None else None
         self._gate_reference = gate_reference
         self._gate_settle = tuple(gate_settle) if gate_settle is not None else None
+        self._group_gate_order = group_gate_order
         self._devices = [device] if device is not None else devices
 
     def create_video_matcher(self, images, progress_reporter: ProgressReporter) -> HipVideoMatcher:
         """images: objects with get_path() (matching::MatchableImage, lib.rs:31-33)."""
         images = list(images)
         m = _capi.Group(self._cfg, self._devices)
+        if self._group_gate_order is not None:
+            m.set_gate_order(self._group_gate_order)
         if self._gate_reference is not None:
             m.set_gate_reference(self._gate_reference)
         if self._gate_settle is not None:
