@@ -20,6 +20,10 @@ pub const SLIDEO_YUV_RANGE_FULL: i32 = 1;
 pub const SLIDEO_YUV_DEPTH_8: i32 = 0;
 pub const SLIDEO_YUV_DEPTH_10_MSB: i32 = 1;
 pub const SLIDEO_YUV_DEPTH_10_LSB: i32 = 2;
+pub const SLIDEO_YUV_SAMPLING_420: i32 = 0;
+pub const SLIDEO_YUV_SAMPLING_422: i32 = 1;
+pub const SLIDEO_YUV_SAMPLING_444: i32 = 2;
+pub const SLIDEO_YUV_SAMPLING_422_PACKED: i32 = 3;
 
 /// slideo_ocv_variants: which restatement of each OpenCV primitive runs.  slideo_config_default fills it; the
 /// application never touches it.
@@ -130,6 +134,18 @@ pub const SLIDEO_YUV420_NV12: i32 = 0;
 pub const SLIDEO_YUV420_NV21: i32 = 1;
 pub const SLIDEO_YUV420_I420: i32 = 2;
 pub const SLIDEO_YUV420_YV12: i32 = 3;
+pub const SLIDEO_YUV422_I422: i32 = 16;
+pub const SLIDEO_YUV422_YV16: i32 = 17;
+pub const SLIDEO_YUV422_NV16: i32 = 18;
+pub const SLIDEO_YUV422_NV61: i32 = 19;
+pub const SLIDEO_YUV422_YUY2: i32 = 20;
+pub const SLIDEO_YUV422_UYVY: i32 = 21;
+pub const SLIDEO_YUV422_YVYU: i32 = 22;
+pub const SLIDEO_YUV422_VYUY: i32 = 23;
+pub const SLIDEO_YUV444_I444: i32 = 24;
+pub const SLIDEO_YUV444_YV24: i32 = 25;
+pub const SLIDEO_YUV444_NV24: i32 = 26;
+pub const SLIDEO_YUV444_NV42: i32 = 27;
 
 extern "C" {
     pub fn slideo_abi_version() -> u32;
@@ -522,6 +538,11 @@ extern "C" {
     ) -> i32;
     pub fn slideo_group_set_yuv_description(g: *mut slideo_group, matrix: i32, range: i32, depth: i32) -> i32;
     pub fn slideo_yuv_coefficients(matrix: i32, range: i32, out7: *mut i32) -> i32;
+    // YUV sampling (include/slideo_amd.h "YUV sampling"): SLIDEO_YUV_SAMPLING_*; the layouts of SLIDEO_YUV422_* / SLIDEO_YUV444_*
+    pub fn slideo_matcher_set_yuv_sampling(m: *mut slideo_matcher, sampling: i32) -> i32;
+    pub fn slideo_matcher_yuv_sampling(m: *const slideo_matcher, sampling: *mut i32) -> i32;
+    pub fn slideo_group_set_yuv_sampling(g: *mut slideo_group, sampling: i32) -> i32;
+    pub fn slideo_yuv_layout_packed(format: i32, width: i32, height: i32, bytes_per_sample: i32, out: *mut slideo_yuv420_layout) -> i32;
     // frame region (include/slideo_amd.h "Frame region"): frames stand for a rectified quadrilateral of themselves
     pub fn slideo_matcher_set_frame_region(
         m: *mut slideo_matcher,

@@ -95,6 +95,10 @@ pub struct HipImageVideoMatcher {
     /// _RANGE_* / _DEPTH_*.  BT.709 for HD recordings, full range for many screen recorders, a 10-bit depth for P010 /
     /// yuv420p10le frames.  The reference reads every stream as BT.601 limited range: the default (0, 0, 0).
     pub yuv_description: (i32, i32, i32),
+    /// Where the samples of the YUV frames lie (slideo_group_set_yuv_sampling): ffi::SLIDEO_YUV_SAMPLING_420 (default), _422,
+    /// _444 (screen recorders) or _422_PACKED (YUY2 / UYVY of capture cards; 8-bit).  Every call that takes a
+    /// slideo_yuv420_layout reads its frames under it.  The reference knows BGR only.
+    pub yuv_sampling: i32,
     /// Which frame a gated frame is compared with (slideo_group_set_gate_reference): ffi::SLIDEO_GATE_PREVIOUS (default: the
     /// frame before, the reference's MarkSimilarIter) or ffi::SLIDEO_GATE_ANCHOR (the last frame that was flagged: a change
     /// spread over many frames is still flagged when every decoded frame is fed).  With several devices it needs
@@ -138,6 +142,7 @@ impl Default for HipImageVideoMatcher {
             direct_scope: ffi::SLIDEO_DIRECT_WHOLE,
             frame_region: None,
             yuv_description: (ffi::SLIDEO_YUV_MATRIX_BT601, ffi::SLIDEO_YUV_RANGE_LIMITED, ffi::SLIDEO_YUV_DEPTH_8),
+            yuv_sampling: ffi::SLIDEO_YUV_SAMPLING_420,
             gate_reference: ffi::SLIDEO_GATE_PREVIOUS,
             gate_settle: (0.0, 0),
             group_gate_order: ffi::SLIDEO_GROUP_GATE_HALO,
@@ -186,6 +191,9 @@ impl<'i> ImageVideoMatcher<'i> for HipImageVideoMatcher {
             if self.yuv_description != (0, 0, 0) {
                 let (matrix, range, depth) = self.yuv_description;
                 check(h, ffi::slideo_group_set_yuv_description(h, matrix, range, depth));
+            }
+            if self.yuv_sampling != ffi::SLIDEO_YUV_SAMPLING_420 {
+                check(h, ffi::slideo_group_set_yuv_sampling(h, self.yuv_sampling));
             }
             if self.frame_mask_scope != ffi::SLIDEO_MASK_DETECT {
                 check(h, ffi::slideo_group_set_frame_mask_scope(h, self.frame_mask_scope));

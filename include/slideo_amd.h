@@ -732,6 +732,70 @@ int32_t     slideo_yuv_coefficients(int32_t matrix, int32_t range, int32_t* out7
  * a frame is width * height * 3 bytes. */
 int32_t     slideo_yuv420_layout_packed16(int32_t format, int32_t width, int32_t height, slideo_yuv420_layout* out);
 
+/* ---- YUV sampling (extension: 4:2:2, 4:4:4 and packed 4:2:2 frames through the *_yuv420 calls) ------------------------------------
+ * Screen recorders write 4:4:4 (OBS "I444", x264 High 4:4:4: 4:2:0 smears coloured text), ProRes / DNxHD and broadcast recorders
+ * decode to 4:2:2 (yuv422p, NV16, yuv422p10le, P210), and HDMI capture cards and UVC devices hand out packed 4:2:2 (YUY2 / UYVY).
+ * A matcher carries a YUV SAMPLING, the fourth component of its YUV description, set on its own; the default is
+ * SLIDEO_YUV_SAMPLING_420, under which every call launches exactly what it launched before.  Under another sampling EVERY call
+ * that takes a slideo_yuv420_layout reads its frames under that sampling — the match, submit / collect, changed-mask and gated
+ * calls, slideo_matcher_observe_frames_yuv420[_dev], slideo_matcher_gate_reset_from_frame_yuv420[_dev], the group's forms and the
+ * tap slideo_yuv420_to_bgr8.  THE NAMES KEEP THEIR `420`: the record, the calls and the tap are the YUV door, whatever the sampling.
+ * Semantics: the per-pixel formula is "YUV colour description"'s, unchanged — s8 by the depth, u = U8 - 128, v = V8 - 128,
+ * y = max(0, Y8 - y_offset) * CY, the three int32 sums with half = 1 << 19, >> 20, saturate, the seven integers of the matcher's
+ * (matrix, range).  Only WHICH chroma sample a pixel takes, and where the samples lie, depend on the sampling:
+ *   SLIDEO_YUV_SAMPLING_422, _444: the record's fields mean what they mean for 4:2:0.  Luma at the base with y_stride; U and V at
+ *     u_offset / v_offset with uv_stride between chroma rows; uv_step 1 planar, 2 interleaved.  Chroma has `height` rows and width/2
+ *     (422: pixel (x, y) takes chroma (x/2, y)) or width (444: pixel (x, y) takes chroma (x, y)) samples per row.  422 needs an
+ *     even width (else SLIDEO_ERR_UNSUPPORTED, as an odd side is for 4:2:0) and takes any height; 444 takes any width and height.
+ *     All three depths apply; with 16-bit containers the rules count two bytes per sample exactly as for 4:2:0.  The rules
+ *     (SLIDEO_ERR_INVALID_ARG, named, the message carrying the sampling): uv_step 1 or 2; offsets >= 0; y_stride >= bps * width;
+ *     uv_stride >= bps * chroma width * uv_step; 16-bit: even strides, offsets and frame_stride; with uv_step 2,
+ *     |v_offset - u_offset| == bps; the planes (chroma of `height` rows) do not overlap; frame_stride covers the furthest byte.
+ *   SLIDEO_YUV_SAMPLING_422_PACKED: ONE plane of 4-byte macropixels, two pixels each.  Rules, each SLIDEO_ERR_INVALID_ARG with the
+ *     rule named: uv_step == 4; uv_stride == y_stride; y_stride >= 2 * width; (u_offset, v_offset) one of (1, 3) YUY2, (3, 1) YVYU,
+ *     (0, 2) UYVY, (2, 0) VYUY.  The luma byte of pixel (x, y) is at y * y_stride + 2x + ((u_offset & 1) ^ 1); its U is at
+ *     y * y_stride + u_offset + 4 * (x/2); V likewise.  The frame's span is (height-1) * y_stride + 2 * width.  Even width, any
+ *     height.  The overlap rule does not apply: there is one plane.  The depth must be SLIDEO_YUV_DEPTH_8: whichever of
+ *     slideo_matcher_set_yuv_sampling and slideo_matcher_set_yuv_description would complete 422_PACKED with a 10-bit depth is
+ *     SLIDEO_ERR_UNSUPPORTED, and the values before stay.
+ * Under the default (BT601, LIMITED, 8) a packed frame stands for the image of OpenCV's cvtColor(COLOR_YUV2BGR_YUY2 / _UYVY /
+ * _YVYU) [OCV A.14: the same literals and the same SHIFT 20, recalled from color_yuv.simd.hpp and unpinned, confidence M].
+ * DEPARTURE: planar 4:2:2 and 4:4:4 in this fixed point have no cvtColor counterpart: they are the library's own definition.  The
+ * reference decodes everything to BGR through swscale and knows none of these doors.
+ * Contract: a call under a sampling returns, bit for bit, what its *_bgr8 twin returns on that image.  Working size, frame region,
+ * frame mask and scopes, the direct look-up, page sets and SIFT mode see the converted image.  A host frame is 2 * bps bytes per
+ * pixel of upload and staging under both 4:2:2 forms, 3 * bps under 4:4:4; the upload's extent is the frame's span.
+ * Out of scope: 4-byte BGRA / RGBA input; packed 10-bit (Y210, v210); 4:1:1 and 4:4:0; chroma siting other than nearest; fusing
+ * the grey write into the conversion.
+ * Kernel: csrc/yuv_sampling.hip.h yuv_sampled_to_bgr_kernel<SAMPLING, DEPTH>, launched iff the sampling is not 420. */
+#define SLIDEO_YUV_SAMPLING_420         0   /* default */
+#define SLIDEO_YUV_SAMPLING_422         1   /* planar or semi-planar: chroma (w/2) x h, pixel (x, y) takes chroma (x/2, y) */
+#define SLIDEO_YUV_SAMPLING_444         2   /* planar or semi-planar: chroma w x h, pixel (x, y) takes chroma (x, y)       */
+#define SLIDEO_YUV_SAMPLING_422_PACKED  3   /* one plane of 4-byte macropixels (YUY2, UYVY, YVYU, VYUY); 8-bit only        */
+/* As slideo_matcher_set_yuv_description: before or after finalize; SLIDEO_ERR_STATE with units in flight; a value outside the
+ * enumeration is SLIDEO_ERR_INVALID_ARG and the state before stays; ends the kept frames and resets the gate state to "none".
+ * slideo_matcher_set_yuv_description leaves the sampling alone, and slideo_matcher_yuv_description keeps its three outputs. */
+int32_t     slideo_matcher_set_yuv_sampling(slideo_matcher* m, int32_t sampling);
+int32_t     slideo_matcher_yuv_sampling(const slideo_matcher* m, int32_t* sampling);
+/* Validates every member before changing any; resets the group's gate state. */
+int32_t     slideo_group_set_yuv_sampling(slideo_group* g, int32_t sampling);
+#define SLIDEO_YUV422_I422 16   /* planar: Y, U, V */
+#define SLIDEO_YUV422_YV16 17   /* planar: Y, V, U */
+#define SLIDEO_YUV422_NV16 18   /* Y, then interleaved U V */
+#define SLIDEO_YUV422_NV61 19   /* Y, then interleaved V U */
+#define SLIDEO_YUV422_YUY2 20   /* packed Y0 U Y1 V */
+#define SLIDEO_YUV422_UYVY 21   /* packed U Y0 V Y1 */
+#define SLIDEO_YUV422_YVYU 22   /* packed Y0 V Y1 U */
+#define SLIDEO_YUV422_VYUY 23   /* packed V Y0 U Y1 */
+#define SLIDEO_YUV444_I444 24   /* planar: Y, U, V */
+#define SLIDEO_YUV444_YV24 25   /* planar: Y, V, U */
+#define SLIDEO_YUV444_NV24 26   /* Y, then interleaved U V */
+#define SLIDEO_YUV444_NV42 27   /* Y, then interleaved V U */
+/* The tight layout of `format` (SLIDEO_YUV422_* / SLIDEO_YUV444_*, numbered from 16 so that they cannot be taken for
+ * SLIDEO_YUV420_*) at width x height with samples of bytes_per_sample (1 or 2) bytes: planes back to back, strides and offsets in
+ * BYTES.  A packed format with bytes_per_sample 2, and an odd width of a 4:2:2 format, are SLIDEO_ERR_UNSUPPORTED. */
+int32_t     slideo_yuv_layout_packed(int32_t format, int32_t width, int32_t height, int32_t bytes_per_sample, slideo_yuv420_layout* out);
+
 /* ---- Working size (extension: the reference analyses every frame at the size it arrives in) ---------------------------------
  * A matcher carries a working size (max_w, max_h); (0, 0) = none, the default.  While one is set, a frame of w x h with
  * w <= max_w and h <= max_h is untouched; any other frame STANDS FOR the image cv::resize(frame, Size(dw, dh), 0, 0, INTER_AREA)

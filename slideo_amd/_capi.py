@@ -111,6 +111,69 @@ def yuv420_layout_packed(fmt, w, h, bytes_per_sample=1):
     return L
 
 
+# "YUV sampling": the formats of slideo_yuv_layout_packed (SLIDEO_YUV422_* / SLIDEO_YUV444_*) and the samplings
+YUV_FORMATS = {"i422": 16, "yv16": 17, "nv16": 18, "nv61": 19, "yuy2": 20, "uyvy": 21, "yvyu": 22, "vyuy": 23,
+               "i444": 24, "yv24": 25, "nv24": 26, "nv42": 27}
+YUV_PACKED_OFFSETS = {"yuy2": (1, 3), "yvyu": (3, 1), "uyvy": (0, 2), "vyuy": (2, 0)}
+YUV_SAMPLINGS = {"420": 0, "422": 1, "444": 2, "422_packed": 3}
+
+
+def yuv_format_sampling(fmt):
+    """The sampling name a format is read under."""
+    if fmt in YUV420_FORMATS:
+        return "420"
+    if fmt not in YUV_FORMATS:
+        raise ValueError("unknown YUV format %r" % (fmt,))
+    return "422_packed" if fmt in YUV_PACKED_OFFSETS else "444" if YUV_FORMATS[fmt] >= 24 else "422"
+
+
+def yuv_layout(fmt, w, h, pitch=None, row_align=None, bytes_per_sample=1):
+    """Layout of a `fmt` frame of w x h -> (Yuv420Layout, frame bytes): the four 4:2:0 names go to yuv420_layout; the twelve of
+    "YUV sampling" ('i422', 'yv16', 'nv16', 'nv61', 'yuy2', 'uyvy', 'yvyu', 'vyuy', 'i444', 'yv24', 'nv24', 'nv42') are laid out
+    here.  pitch: bytes per luma row (a packed format's one plane: default 2 w); planar 4:2:2 chroma rows take pitch / 2,
+    interleaved 4:4:4 chroma rows 2 * pitch, the others pitch.  row_align: every plane has align(h, row_align) rows.  Without
+    either, the tight layout slideo_yuv_layout_packed returns."""
+    if fmt in YUV420_FORMATS:
+        return yuv420_layout(fmt, w, h, pitch, row_align, bytes_per_sample)
+    sampling = yuv_format_sampling(fmt)
+    if bytes_per_sample not in (1, 2):
+        raise ValueError("bytes_per_sample is 1 or 2")
+    b = bytes_per_sample
+    ah = -(-h // row_align) * row_align if row_align else h
+    L = Yuv420Layout()
+    if sampling == "422_packed":
+        if b != 1:
+            raise SlideoError(5, "packed 4:2:2 is 8-bit")
+        p = int(pitch or 2 * w)
+        L.y_stride = L.uv_stride = p
+        L.uv_step = 4
+        L.u_offset, L.v_offset = YUV_PACKED_OFFSETS[fmt]
+        return L, p * ah
+    p = int(pitch or w * b)
+    luma = p * ah
+    L.y_stride = p
+    kind = (YUV_FORMATS[fmt] - 16) % 8 if sampling == "422" else YUV_FORMATS[fmt] - 24      # 0 U V planes, 1 V U planes, 2 U V pairs, 3 V U pairs
+    if kind >= 2:
+        cp = p if sampling == "422" else 2 * p
+        L.uv_stride, L.uv_step = cp, 2
+        L.u_offset, L.v_offset = (luma, luma + b) if kind == 2 else (luma + b, luma)
+        return L, luma + cp * ah
+    cp = p // 2 if sampling == "422" else p
+    L.uv_stride, L.uv_step = cp, 1
+    first, second = luma, luma + cp * ah
+    L.u_offset, L.v_offset = (first, second) if kind == 0 else (second, first)
+    return L, luma + 2 * cp * ah
+
+
+def yuv_layout_packed(fmt, w, h, bytes_per_sample=1):
+    """slideo_yuv_layout_packed: the library's own tight layout of a "YUV sampling" format."""
+    L = Yuv420Layout()
+    rc = lib().slideo_yuv_layout_packed(YUV_FORMATS[fmt], int(w), int(h), int(bytes_per_sample), C.byref(L))
+    if rc != OK:
+        raise SlideoError(rc, "slideo_yuv_layout_packed(%s, %d, %d, %d)" % (fmt, w, h, bytes_per_sample))
+    return L
+
+
 def _yuv_frames(frames, w, h, layout):
     """frames: uint8 [n, frame_bytes] (or one frame, 1-D), or little-endian uint16 samples (16-bit containers), read as their
     bytes -> (contiguous uint8 [n, frame_bytes], layout, frame stride in bytes).  A format NAME stands for its packed 8-bit layout."""
@@ -121,7 +184,7 @@ def _yuv_frames(frames, w, h, layout):
     frames = np.ascontiguousarray(frames, np.uint8)
     frames = frames.reshape(1 if frames.ndim == 1 else frames.shape[0], -1)
     if isinstance(layout, str):
-        layout = yuv420_layout(layout, w, h)[0]
+        layout = yuv_layout(layout, w, h)[0]
     return frames, layout, frames.shape[1]
 
 
@@ -182,6 +245,7 @@ EXPORTS = [
     "slideo_rectify_bgr8",
     "slideo_matcher_set_yuv_description", "slideo_matcher_yuv_description", "slideo_group_set_yuv_description", "slideo_yuv_coefficients",
     "slideo_yuv420_layout_packed16",
+    "slideo_matcher_set_yuv_sampling", "slideo_matcher_yuv_sampling", "slideo_group_set_yuv_sampling", "slideo_yuv_layout_packed",
     "slideo_matcher_activity_begin", "slideo_matcher_activity_end", "slideo_matcher_observe_frames_bgr8", "slideo_matcher_observe_frames_yuv420",
     "slideo_matcher_observe_frames_bgr8_dev", "slideo_matcher_observe_frames_yuv420_dev", "slideo_matcher_activity_info",
     "slideo_matcher_activity_counts", "slideo_matcher_activity_mask",
@@ -313,6 +377,11 @@ def lib():
             L.slideo_group_set_yuv_description.argtypes = [vp, i32, i32, i32]
             L.slideo_yuv_coefficients.argtypes = [i32, i32, vp]
             L.slideo_yuv420_layout_packed16.argtypes = [i32, i32, i32, vp]
+        if hasattr(L, "slideo_matcher_set_yuv_sampling"):
+            L.slideo_matcher_set_yuv_sampling.argtypes = [vp, i32]
+            L.slideo_matcher_yuv_sampling.argtypes = [vp, vp]
+            L.slideo_group_set_yuv_sampling.argtypes = [vp, i32]
+            L.slideo_yuv_layout_packed.argtypes = [i32, i32, i32, i32, vp]
         if hasattr(L, "slideo_matcher_activity_begin"):
             vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
             L.slideo_matcher_activity_begin.argtypes = [vp, i32]
@@ -604,6 +673,25 @@ class _FrameCalls:
             raise SlideoError(rc, "yuv_description")
         return v[0].value, v[1].value, v[2].value
 
+    # YUV sampling (include/slideo_amd.h "YUV sampling"): where every *_yuv420 call finds its samples
+    def set_yuv_sampling(self, sampling="420"):
+        """'420' (the default) | '422' | '444' | '422_packed' — or the SLIDEO_YUV_SAMPLING_* value.  Every call that takes a layout
+        then reads 4:2:2 / 4:4:4 planes (yuv_layout('nv16' ...)) or packed macropixels ('yuy2', 'uyvy' ...); the names keep their
+        `420`.  The matcher must be idle; ends the kept frames and resets the gate state.  set_yuv_description leaves it alone."""
+        if isinstance(sampling, str):
+            if sampling.lower() not in YUV_SAMPLINGS:
+                raise SlideoError(1, "yuv sampling: unknown %r (one of %s)" % (sampling, sorted(YUV_SAMPLINGS)))
+            sampling = YUV_SAMPLINGS[sampling.lower()]
+        self._check(getattr(lib(), self._SETS + "set_yuv_sampling")(self._h, int(sampling)))
+
+    def yuv_sampling(self):
+        """The SLIDEO_YUV_SAMPLING_* value (a Group: member 0's)."""
+        v = C.c_int32()
+        rc = lib().slideo_matcher_yuv_sampling(self._mask_owner(), C.byref(v))
+        if rc != OK:
+            raise SlideoError(rc, "yuv_sampling")
+        return v.value
+
     def _mask_owner(self):
         """The matcher handle the mask's getters read (a group's members agree: member 0)."""
         return self._h if self._SETS == "slideo_matcher_" else C.c_void_p(lib().slideo_group_member(self._h, 0))
@@ -882,7 +970,7 @@ class Matcher(_FrameCalls):
 
     def gate_reset_from_frame_yuv420_dev(self, dev_ptr, w, h, layout, stream=0):
         if isinstance(layout, str):
-            layout = yuv420_layout(layout, w, h)[0]
+            layout = yuv_layout(layout, w, h)[0]
         self._check(lib().slideo_matcher_gate_reset_from_frame_yuv420_dev(self._h, C.c_void_p(dev_ptr), w, h, C.byref(layout), C.c_void_p(stream)))
 
     def match_changed_frames_dev(self, dev_ptr, n, w, h, stride=None, frame_stride=None, stream=0):
@@ -895,7 +983,7 @@ class Matcher(_FrameCalls):
 
     def match_changed_frames_yuv420_dev(self, dev_ptr, n, w, h, layout, frame_stride, stream=0):
         if isinstance(layout, str):
-            layout = yuv420_layout(layout, w, h)[0]
+            layout = yuv_layout(layout, w, h)[0]
         ch, sim, out = self._gated_out(n)
         self._check(lib().slideo_match_changed_frames_yuv420_dev(self._h, n, C.c_void_p(dev_ptr), w, h, C.byref(layout),
                                                                  C.c_int64(frame_stride), _p(ch), _p(sim), _p(out), C.c_void_p(stream)))
@@ -912,7 +1000,7 @@ class Matcher(_FrameCalls):
 
     def submit_changed_yuv420_dev(self, dev_ptr, n, w, h, layout, frame_stride, stream=0):
         if isinstance(layout, str):
-            layout = yuv420_layout(layout, w, h)[0]
+            layout = yuv_layout(layout, w, h)[0]
         t = C.c_int64()
         self._check(lib().slideo_match_changed_frames_submit_yuv420_dev(self._h, n, C.c_void_p(dev_ptr), w, h, C.byref(layout),
                                                                         C.c_int64(frame_stride), C.c_void_p(stream), C.byref(t)))
@@ -951,7 +1039,7 @@ class Matcher(_FrameCalls):
 
     def observe_frames_yuv420_dev(self, dev_ptr, n, w, h, layout, frame_stride, stream=0):
         if isinstance(layout, str):
-            layout = yuv420_layout(layout, w, h)[0]
+            layout = yuv_layout(layout, w, h)[0]
         self._check(lib().slideo_matcher_observe_frames_yuv420_dev(self._h, n, C.c_void_p(dev_ptr), w, h, C.byref(layout),
                                                                    C.c_int64(frame_stride), C.c_void_p(stream)))
 
@@ -1013,7 +1101,7 @@ class Matcher(_FrameCalls):
     # ---- YUV 4:2:0 frames (include/slideo_amd.h "YUV 4:2:0 frames") ---------------------------
     def match_frames_yuv420_dev(self, dev_ptr, n, w, h, layout, frame_stride, stream=0):
         if isinstance(layout, str):
-            layout = yuv420_layout(layout, w, h)[0]
+            layout = yuv_layout(layout, w, h)[0]
         out = np.zeros(n, VERDICT_DTYPE)
         self._check(lib().slideo_match_frames_yuv420_dev(self._h, n, C.c_void_p(dev_ptr), w, h, C.byref(layout), C.c_int64(frame_stride),
                                                          _p(out), C.c_void_p(stream)))
@@ -1022,7 +1110,7 @@ class Matcher(_FrameCalls):
     def submit_yuv420_dev(self, dev_ptr, n, w, h, layout, frame_stride, stream=0):
         """As submit_dev; collect() collects it."""
         if isinstance(layout, str):
-            layout = yuv420_layout(layout, w, h)[0]
+            layout = yuv_layout(layout, w, h)[0]
         t = C.c_int64()
         self._check(lib().slideo_match_frames_submit_yuv420_dev(self._h, n, C.c_void_p(dev_ptr), w, h, C.byref(layout),
                                                                 C.c_int64(frame_stride), C.c_void_p(stream), C.byref(t)))

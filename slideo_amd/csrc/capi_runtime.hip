@@ -86,8 +86,8 @@ void validate_image(int w, int h, int stride) {
 
 void validate_frames(FrameSrc& src, slideo_matcher* m, int n, const void* out) {
     if (src.yuv) {
-        if (m) src.bps = m->fs.yuv.bytes_per_sample();              // (a tap without a matcher argument sets it itself)
-        src.yuv_span = yuv420_validate(src.w, src.h, src.yuv, src.frame_stride, src.bps);
+        if (m) src.describe(m->fs.yuv);                            // (a tap without a matcher argument sets it itself)
+        src.yuv_span = yuv420_validate(src.w, src.h, src.yuv, src.frame_stride, src.bps, src.sampling);
         src.stride = src.w * 3;                                    // the BGR image the units read (d_stage)
     }
     if (m) {
@@ -458,7 +458,7 @@ static Slot& slot_of_ticket(slideo_matcher* m, int64_t ticket, bool gated) {
 void changed_mask_impl(slideo_matcher* m, int n_frames, FrameSrc src, const uint8_t* prev_small, uint8_t* last_small_out, uint8_t* changed_out,
                        float* similarity_out) {
     if (n_frames < 0 || (n_frames > 0 && (!src.p || !changed_out))) fail(SLIDEO_ERR_INVALID_ARG, "null frames/changed");
-    src.bps = m->fs.yuv.bytes_per_sample();
+    src.describe(m->fs.yuv);
     validate_frames(src);
     resolve_frames(m, src, false);
     if (n_frames == 0) return;
@@ -1188,6 +1188,48 @@ int32_t slideo_matcher_set_yuv_description(slideo_matcher* m, int32_t matrix, in
 int32_t slideo_matcher_yuv_description(const slideo_matcher* m, int32_t* matrix, int32_t* range, int32_t* depth) {
     if (!m || !matrix || !range || !depth) return SLIDEO_ERR_INVALID_ARG;
     *matrix = m->fs.yuv.matrix; *range = m->fs.yuv.range; *depth = m->fs.yuv.depth;
+    return SLIDEO_OK;
+}
+
+// ---- YUV sampling (include/slideo_amd.h "YUV sampling") -----------------------------------------------------------------------
+
+int32_t slideo_matcher_set_yuv_sampling(slideo_matcher* m, int32_t sampling) {
+    return matcher_set(m, SET_YUV_DESCRIPTION, [&](const FrameSettings& s) { return propose_yuv_sampling(s, sampling); });
+}
+
+int32_t slideo_matcher_yuv_sampling(const slideo_matcher* m, int32_t* sampling) {
+    if (!m || !sampling) return SLIDEO_ERR_INVALID_ARG;
+    *sampling = m->fs.yuv.sampling;
+    return SLIDEO_OK;
+}
+
+int32_t slideo_yuv_layout_packed(int32_t format, int32_t w, int32_t h, int32_t bytes_per_sample, slideo_yuv420_layout* out) {
+    if (!out || format < SLIDEO_YUV422_I422 || format > SLIDEO_YUV444_NV42 || w < 1 || h < 1 || (bytes_per_sample != 1 && bytes_per_sample != 2))
+        return SLIDEO_ERR_INVALID_ARG;
+    const bool s444 = format >= SLIDEO_YUV444_I444, packed = format >= SLIDEO_YUV422_YUY2 && format <= SLIDEO_YUV422_VYUY;
+    if ((!s444 && (w & 1)) || (packed && bytes_per_sample != 1)) return SLIDEO_ERR_UNSUPPORTED;
+    const int64_t b = bytes_per_sample;
+    slideo_yuv420_layout L{};
+    if (packed) {
+        L.y_stride = L.uv_stride = 2 * w; L.uv_step = 4;
+        L.u_offset = format == SLIDEO_YUV422_YUY2 ? 1 : format == SLIDEO_YUV422_YVYU ? 3 : format == SLIDEO_YUV422_UYVY ? 0 : 2;
+        L.v_offset = L.u_offset ^ 2;
+        *out = L;
+        return SLIDEO_OK;
+    }
+    const int64_t cw = s444 ? w : w / 2, luma = b * w * h, chroma = b * cw * h;
+    const int kind = (format - (s444 ? SLIDEO_YUV444_I444 : SLIDEO_YUV422_I422));      // 0 U V planes, 1 V U planes, 2 U V pairs, 3 V U pairs
+    L.y_stride = (int32_t)(b * w);
+    if (kind >= 2) {
+        L.uv_stride = (int32_t)(2 * b * cw); L.uv_step = 2;
+        L.u_offset = luma + (kind == 3 ? b : 0);
+        L.v_offset = luma + (kind == 2 ? b : 0);
+    } else {
+        L.uv_stride = (int32_t)(b * cw); L.uv_step = 1;
+        L.u_offset = kind == 0 ? luma : luma + chroma;
+        L.v_offset = kind == 0 ? luma + chroma : luma;
+    }
+    *out = L;
     return SLIDEO_OK;
 }
 

@@ -1,5 +1,5 @@
 // frame_settings.h — the frame settings of a matcher as ONE record (include/slideo_amd.h "Working size", "Frame region", "Frame mask",
-// "Frame mask scope", "Direct page look-up", "Direct look-up scope", "YUV colour description", "Gate reference", "Gate settle"): the record, every setter's proposal with its range checks, the
+// "Frame mask scope", "Direct page look-up", "Direct look-up scope", "YUV colour description", "YUV sampling", "Gate reference", "Gate settle"): the record, every setter's proposal with its range checks, the
 // rules between settings, what a change of each ends.  Plain C++, no HIP include (tools/frame_settings_hostcheck.cpp walks it on the
 // host); the device buffers a setting owns are the matcher's (runtime.hpp).  A change takes ONE path: settings_commit (capi_runtime.hip).
 #pragma once
@@ -27,9 +27,11 @@ struct FrameMask { bool set = false; int w = 0, h = 0; };
 // sw x sh small image of frames of the mask's size (the matcher's d_gate_w), n_valid valid pixels
 struct GateMap { bool on = false; int sw = 0, sh = 0; int64_t n_valid = 0; };
 
-// How every slideo_yuv420_layout call reads its samples (SLIDEO_YUV_MATRIX_* / _RANGE_* / _DEPTH_*); all 0: the default
+// How every slideo_yuv420_layout call reads its samples (SLIDEO_YUV_MATRIX_* / _RANGE_* / _DEPTH_*); all 0: the default.  The
+// sampling (SLIDEO_YUV_SAMPLING_*, "YUV sampling") is set on its own and says where the samples lie; is_default() is the colour's
 struct YuvDesc {
     int matrix = SLIDEO_YUV_MATRIX_BT601, range = SLIDEO_YUV_RANGE_LIMITED, depth = SLIDEO_YUV_DEPTH_8;
+    int sampling = SLIDEO_YUV_SAMPLING_420;
     bool is_default() const { return matrix == SLIDEO_YUV_MATRIX_BT601 && range == SLIDEO_YUV_RANGE_LIMITED && depth == SLIDEO_YUV_DEPTH_8; }
     int bytes_per_sample() const { return depth == SLIDEO_YUV_DEPTH_8 ? 1 : 2; }
 };
@@ -124,7 +126,15 @@ inline FrameSettings propose_yuv_description(FrameSettings s, int matrix, int ra
         fail(SLIDEO_ERR_INVALID_ARG, "yuv description: range %d is neither SLIDEO_YUV_RANGE_LIMITED (0) nor SLIDEO_YUV_RANGE_FULL (1)", range);
     if (depth != SLIDEO_YUV_DEPTH_8 && depth != SLIDEO_YUV_DEPTH_10_MSB && depth != SLIDEO_YUV_DEPTH_10_LSB)
         fail(SLIDEO_ERR_INVALID_ARG, "yuv description: depth %d is none of SLIDEO_YUV_DEPTH_8 (0), _10_MSB (1), _10_LSB (2)", depth);
-    s.yuv = YuvDesc{matrix, range, depth};
+    s.yuv.matrix = matrix; s.yuv.range = range; s.yuv.depth = depth;       // (the sampling stays: it is set on its own)
+    return s;
+}
+// The sampling commits under SET_YUV_DESCRIPTION like the description: it ends the kept frames and resets the gate
+inline FrameSettings propose_yuv_sampling(FrameSettings s, int sampling) {
+    if (sampling != SLIDEO_YUV_SAMPLING_420 && sampling != SLIDEO_YUV_SAMPLING_422 && sampling != SLIDEO_YUV_SAMPLING_444 &&
+        sampling != SLIDEO_YUV_SAMPLING_422_PACKED)
+        fail(SLIDEO_ERR_INVALID_ARG, "yuv sampling: %d is none of SLIDEO_YUV_SAMPLING_420 (0), _422 (1), _444 (2), _422_PACKED (3)", sampling);
+    s.yuv.sampling = sampling;
     return s;
 }
 
@@ -251,8 +261,11 @@ inline void yuv_coefficients(int matrix, int range, int32_t* out7) {
 
 // The layout rules of include/slideo_amd.h "YUV 4:2:0 frames" for samples of `bps` bytes (1; 2: the 16-bit containers of "YUV
 // colour description", whose rules count two bytes per sample); returns the bytes of one frame (its furthest byte + 1).
-// frame_stride < 0: a single frame, no stride to check
-inline int64_t yuv420_validate(int w, int h, const slideo_yuv420_layout* L, int64_t frame_stride, int bps) {
+// frame_stride < 0: a single frame, no stride to check.  `sampling` other than 420: the rules of "YUV sampling"
+// (yuv_sampled_validate); under 420 every rule and every message is as it was before the sampling existed.
+inline int64_t yuv_sampled_validate(int w, int h, const slideo_yuv420_layout* L, int64_t frame_stride, int bps, int sampling);
+inline int64_t yuv420_validate(int w, int h, const slideo_yuv420_layout* L, int64_t frame_stride, int bps, int sampling = SLIDEO_YUV_SAMPLING_420) {
+    if (sampling != SLIDEO_YUV_SAMPLING_420) return yuv_sampled_validate(w, h, L, frame_stride, bps, sampling);
     if (w < 1 || h < 1) fail(SLIDEO_ERR_INVALID_ARG, "bad image geometry w=%d h=%d", w, h);
     if ((w | h) & 1) fail(SLIDEO_ERR_UNSUPPORTED, "yuv420: width and height must be even (%dx%d), as cvtColor requires", w, h);
     if (w > MAX_DIM || h > MAX_DIM) fail(SLIDEO_ERR_UNSUPPORTED, "image size %dx%d outside 1..%d", w, h, MAX_DIM);
@@ -311,6 +324,77 @@ inline int64_t yuv420_validate(int w, int h, const slideo_yuv420_layout* L, int6
     return span;
 }
 
+// The layout rules of include/slideo_amd.h "YUV sampling": 4:2:2 (chroma (w/2) x h) and 4:4:4 (chroma w x h) in the record's own
+// terms, and packed 4:2:2 (one plane of 4-byte macropixels).  Messages carry the sampling's name (yuv422 / yuv444 / yuv422 packed).
+inline int64_t yuv_sampled_validate(int w, int h, const slideo_yuv420_layout* L, int64_t frame_stride, int bps, int sampling) {
+    const bool packed = sampling == SLIDEO_YUV_SAMPLING_422_PACKED, s444 = sampling == SLIDEO_YUV_SAMPLING_444;
+    const char* name = packed ? "yuv422 packed" : s444 ? "yuv444" : "yuv422";
+    if (w < 1 || h < 1) fail(SLIDEO_ERR_INVALID_ARG, "bad image geometry w=%d h=%d", w, h);
+    if (!s444 && (w & 1)) fail(SLIDEO_ERR_UNSUPPORTED, "%s: the width must be even (%dx%d): two pixels share a chroma sample", name, w, h);
+    if (w > MAX_DIM || h > MAX_DIM) fail(SLIDEO_ERR_UNSUPPORTED, "image size %dx%d outside 1..%d", w, h, MAX_DIM);
+    if (packed) {
+        if (bps != 1) fail(SLIDEO_ERR_UNSUPPORTED, "%s: 8-bit samples only (SLIDEO_YUV_DEPTH_8)", name);
+        if (L->uv_step != 4) fail(SLIDEO_ERR_INVALID_ARG, "%s layout: uv_step %d is not 4 (one macropixel of two pixels)", name, L->uv_step);
+        if (L->uv_stride != L->y_stride)
+            fail(SLIDEO_ERR_INVALID_ARG, "%s layout: uv_stride %d is not y_stride %d (there is one plane)", name, L->uv_stride, L->y_stride);
+        if ((int64_t)L->y_stride < (int64_t)2 * w) fail(SLIDEO_ERR_INVALID_ARG, "%s layout: y_stride %d < 2 * width %d", name, L->y_stride, w);
+        const int64_t u = L->u_offset, v = L->v_offset;
+        if (!((u == 1 && v == 3) || (u == 3 && v == 1) || (u == 0 && v == 2) || (u == 2 && v == 0)))
+            fail(SLIDEO_ERR_INVALID_ARG, "%s layout: (u_offset, v_offset) = (%lld, %lld) is none of (1, 3) YUY2, (3, 1) YVYU, (0, 2) UYVY, (2, 0) VYUY",
+                 name, (long long)u, (long long)v);
+        const int64_t span = (int64_t)(h - 1) * L->y_stride + (int64_t)2 * w;
+        if (frame_stride >= 0 && frame_stride < span)
+            fail(SLIDEO_ERR_INVALID_ARG, "%s: frame_stride %lld does not cover the frame's furthest byte (%lld)", name, (long long)frame_stride, (long long)span);
+        return span;
+    }
+    if (L->uv_step != 1 && L->uv_step != 2) fail(SLIDEO_ERR_INVALID_ARG, "%s layout: uv_step %d is neither 1 (planar) nor 2 (interleaved)", name, L->uv_step);
+    if (L->u_offset < 0 || L->v_offset < 0) fail(SLIDEO_ERR_INVALID_ARG, "%s layout: negative plane offset", name);
+    const int cw = s444 ? w : w / 2;
+    const char* cws = s444 ? "width" : "width/2";
+    if ((int64_t)L->y_stride < (int64_t)bps * w) fail(SLIDEO_ERR_INVALID_ARG, "%s layout: y_stride %d < %d (width %d samples of %d bytes)", name, L->y_stride, bps * w, w, bps);
+    if ((int64_t)L->uv_stride < (int64_t)bps * cw * L->uv_step)
+        fail(SLIDEO_ERR_INVALID_ARG, "%s layout: uv_stride %d < %lld (%s chroma samples of %d bytes, step %d)", name, L->uv_stride,
+             (long long)bps * cw * L->uv_step, cws, bps, L->uv_step);
+    if (bps == 2) {
+        if ((L->y_stride | L->uv_stride) & 1)
+            fail(SLIDEO_ERR_INVALID_ARG, "%s layout: 16-bit containers need even strides (y_stride %d, uv_stride %d)", name, L->y_stride, L->uv_stride);
+        if ((L->u_offset | L->v_offset) & 1)
+            fail(SLIDEO_ERR_INVALID_ARG, "%s layout: 16-bit containers need even offsets (u_offset %lld, v_offset %lld)", name,
+                 (long long)L->u_offset, (long long)L->v_offset);
+        if (frame_stride >= 0 && (frame_stride & 1))
+            fail(SLIDEO_ERR_INVALID_ARG, "%s: 16-bit containers need an even frame_stride (%lld)", name, (long long)frame_stride);
+    }
+    if (L->uv_step == 2 && std::llabs(L->u_offset - L->v_offset) != bps)
+        fail(SLIDEO_ERR_INVALID_ARG, "%s layout: interleaved chroma needs |v_offset - u_offset| == %d (got %lld, %lld)", name, bps,
+             (long long)L->u_offset, (long long)L->v_offset);
+    // planes as byte ranges [lo, hi): Y, then U and V (one range when interleaved); chroma has h rows
+    const int64_t y_hi = (int64_t)(h - 1) * L->y_stride + (int64_t)w * bps;
+    const int64_t c_rows = (int64_t)(h - 1) * L->uv_stride;
+    struct R { int64_t lo, hi; const char* name; };
+    R pl[3] = {{0, y_hi, "Y"}, {0, 0, ""}, {0, 0, ""}};
+    int npl;
+    if (L->uv_step == 2) {
+        const int64_t lo = std::min(L->u_offset, L->v_offset);
+        pl[1] = R{lo, lo + c_rows + (int64_t)2 * cw * bps, "UV"};
+        npl = 2;
+    } else {
+        pl[1] = R{L->u_offset, L->u_offset + c_rows + (int64_t)cw * bps, "U"};
+        pl[2] = R{L->v_offset, L->v_offset + c_rows + (int64_t)cw * bps, "V"};
+        npl = 3;
+    }
+    int64_t span = 0;
+    for (int i = 0; i < npl; ++i) {
+        span = std::max(span, pl[i].hi);
+        for (int j = 0; j < i; ++j)
+            if (pl[i].lo < pl[j].hi && pl[j].lo < pl[i].hi)
+                fail(SLIDEO_ERR_INVALID_ARG, "%s layout: the %s plane [%lld, %lld) of %d rows overlaps the %s plane [%lld, %lld)", name, pl[i].name,
+                     (long long)pl[i].lo, (long long)pl[i].hi, h, pl[j].name, (long long)pl[j].lo, (long long)pl[j].hi);
+    }
+    if (frame_stride >= 0 && frame_stride < span)
+        fail(SLIDEO_ERR_INVALID_ARG, "%s: frame_stride %lld does not cover the frame's furthest byte (%lld)", name, (long long)frame_stride, (long long)span);
+    return span;
+}
+
 // ---- the rules between settings (SLIDEO_ERR_UNSUPPORTED), each once --------------------------------------------------------------
 // `next`: the settings in force with the proposed change of `what` applied.  The settings in force keep every rule, so the call
 // that would complete a refused combination fails, and the values before stay in force.
@@ -332,6 +416,10 @@ inline void frame_settings_rules(const FrameSettings& next, Setting what, bool s
         fail(SLIDEO_ERR_UNSUPPORTED, "gate settle under SLIDEO_GATE_ANCHOR only: a settle similarity %g with the gate reference SLIDEO_GATE_PREVIOUS "
              "(slideo_matcher_set_gate_reference(m, SLIDEO_GATE_ANCHOR) first; slideo_matcher_set_gate_settle(m, 0, 0) before going back)",
              (double)next.settle_similarity);
+    // packed 4:2:2 is 8-bit: whichever of the two set calls (sampling, description) would complete the pair is refused
+    if (next.yuv.sampling == SLIDEO_YUV_SAMPLING_422_PACKED && next.yuv.depth != SLIDEO_YUV_DEPTH_8)
+        fail(SLIDEO_ERR_UNSUPPORTED, "SLIDEO_YUV_SAMPLING_422_PACKED reads 8-bit samples: not together with a 10-bit depth (%d); packed 10-bit "
+             "formats (Y210, v210) are not supported", next.yuv.depth);
 }
 
 }  // namespace slideo

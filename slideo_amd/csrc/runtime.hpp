@@ -103,22 +103,25 @@ struct FrameSrc {
     int stride = 0;                             // BGR rows; a YUV source's BGR image (d_stage) has 3w, set by validate_frames
     int64_t frame_stride = 0;                   // (a single frame: -1 = no stride to check)
     const slideo_yuv420_layout* yuv = nullptr;
-    int bps = 1;                                // (derived) bytes per 4:2:0 sample: the matcher's YUV description (validate_frames)
+    int bps = 1;                                // (derived) bytes per YUV sample: the matcher's YUV description (validate_frames)
+    int sampling = SLIDEO_YUV_SAMPLING_420;     // (derived) the matcher's YUV sampling, with bps (describe)
     int64_t yuv_span = 0;                       // (derived) bytes of one YUV frame: its furthest byte + 1
     bool pinned = false;                        // (derived) page-locked host memory: its copies are truly asynchronous DMA
     // the frames are unit images already — the frames a mask call kept (slideo_match_kept_frames): no region applies to them
     bool analysed = false;
     FramePlan plan;                             // (derived) resolve_frames
 
-    // per frame, the staging in front of the unit's BGR image: 1.5 B per pixel for 4:2:0 frames, 3 B in 16-bit containers (BGR calls
-    // keep their unit sizes);
+    void describe(const YuvDesc& d) { bps = d.bytes_per_sample(); sampling = d.sampling; }
+
+    // per frame, the staging in front of the unit's BGR image: 1.5 B per pixel for 4:2:0 frames, 3 B in 16-bit containers, 2 * bps
+    // under both 4:2:2 forms and 3 * bps under 4:4:4 ("YUV sampling"; BGR calls keep their unit sizes);
     // a reducing or rectifying call: the uploaded source frame (host sources) and the source-sized BGR image of a 4:2:0 frame;
     // gated (a gated call, include/slideo_amd.h "Changed-frame gate"): + the gate staging — the BGR unit image of every frame that
     // is not the caller's own device memory — and the frame's small image (gate_small: at most 3 * small_area bytes) and gate record
     size_t staging_bytes(size_t gate_small = 0) const {
         const size_t px = (size_t)w * h;
         const bool pre = plan.prep != PREP_NONE;
-        const size_t yb = px * 3 / 2 * (size_t)bps;
+        const size_t yb = (sampling == SLIDEO_YUV_SAMPLING_420 ? px * 3 / 2 : sampling == SLIDEO_YUV_SAMPLING_444 ? px * 3 : px * 2) * (size_t)bps;
         size_t b = !pre ? (yuv ? yb : 0) : (on_device ? 0 : (yuv ? yb : (size_t)h * stride)) + (yuv ? px * 3 : 0);
         if (gate_small) b += (on_device && !yuv && !pre ? 0 : (size_t)plan.uw * plan.uh * 3) + gate_small + 32;
         return b;

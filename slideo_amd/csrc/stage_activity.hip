@@ -22,7 +22,7 @@ dim3 act_grid(int threads_x, int ah) { return dim3((unsigned)cdiv64(threads_x, A
 // slideo_matcher_observe_frames_*: everything is validated before anything is written
 void activity_observe(slideo_matcher* m, int n, FrameSrc src, hipStream_t user_stream) {
     if (n < 0 || (n > 0 && !src.p)) fail(SLIDEO_ERR_INVALID_ARG, "null frames");
-    src.bps = m->fs.yuv.bytes_per_sample();
+    src.describe(m->fs.yuv);
     validate_frames(src);                                  // a frame source's rules without the deck's (m == nullptr)
     if (!src.yuv && src.frame_stride < (int64_t)src.h * src.stride) fail(SLIDEO_ERR_INVALID_ARG, "frame_stride smaller than one frame");
     resolve_unit(m, src);                                  // the analysed size: the frame region's source-size rule, else the working size

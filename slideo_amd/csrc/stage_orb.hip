@@ -4,6 +4,7 @@
 #include "runtime.hpp"
 #include "orb.hip.h"
 #include "yuv420.hip.h"
+#include "yuv_sampling.hip.h"
 #include "reduce.hip.h"
 #include "frame_region.hip.h"
 #include "frame_mask.hip.h"
@@ -75,9 +76,35 @@ static YuvDescArgs yuv_desc_args(const YuvDesc& desc, const uint8_t* src, int64_
     return a;
 }
 
-// n decoded 4:2:0 frames (validated layout, frame stride src_fs) -> BGR8 at dst (stride 3w, frame stride 3wh)
+// the frames of a sampling other than 4:2:0 ("YUV sampling"): one thread per four columns of one row
+static void launch_yuv_sampled(const YuvDesc& desc, const uint8_t* src, int64_t src_fs, const slideo_yuv420_layout& L, int w, int h, int n, uint8_t* dst,
+                               hipStream_t st) {
+    const YuvSampArgs a = yuv_sampled_args(desc.sampling, desc.depth, src, src_fs, L, w, h, n, dst);
+    int32_t c[7];
+    yuv_coefficients(desc.matrix, desc.range, c);
+    const YuvCoef k{c[0], c[1], c[2], c[3], c[4], c[5]};
+    const dim3 grid(cdiv(cdiv(w, 4), YUV_TX), cdiv(h, YUV_TY), n), block(YUV_TX, YUV_TY);
+    const int d = desc.depth;
+    if (desc.sampling == SLIDEO_YUV_SAMPLING_422_PACKED) {
+        if (d != SLIDEO_YUV_DEPTH_8) fail(SLIDEO_ERR_UNSUPPORTED, "internal: packed 4:2:2 under a 10-bit depth");
+        yuv_sampled_to_bgr_kernel<YUV_S422P, YUV_D8><<<grid, block, 0, st>>>(a, k);
+    } else if (desc.sampling == SLIDEO_YUV_SAMPLING_422) {
+        if (d == SLIDEO_YUV_DEPTH_8) yuv_sampled_to_bgr_kernel<YUV_S422, YUV_D8><<<grid, block, 0, st>>>(a, k);
+        else if (d == SLIDEO_YUV_DEPTH_10_MSB) yuv_sampled_to_bgr_kernel<YUV_S422, YUV_D10_MSB><<<grid, block, 0, st>>>(a, k);
+        else yuv_sampled_to_bgr_kernel<YUV_S422, YUV_D10_LSB><<<grid, block, 0, st>>>(a, k);
+    } else {
+        if (d == SLIDEO_YUV_DEPTH_8) yuv_sampled_to_bgr_kernel<YUV_S444, YUV_D8><<<grid, block, 0, st>>>(a, k);
+        else if (d == SLIDEO_YUV_DEPTH_10_MSB) yuv_sampled_to_bgr_kernel<YUV_S444, YUV_D10_MSB><<<grid, block, 0, st>>>(a, k);
+        else yuv_sampled_to_bgr_kernel<YUV_S444, YUV_D10_LSB><<<grid, block, 0, st>>>(a, k);
+    }
+    check_launch("yuv_sampled_to_bgr_kernel");
+}
+
+// n decoded YUV frames (validated layout, frame stride src_fs) -> BGR8 at dst (stride 3w, frame stride 3wh).  Under the 4:2:0
+// sampling exactly what it launched before the sampling existed
 void launch_yuv420_to_bgr(const YuvDesc& desc, const uint8_t* src, int64_t src_fs, const slideo_yuv420_layout& L, int w, int h, int n, uint8_t* dst,
                           hipStream_t st) {
+    if (desc.sampling != SLIDEO_YUV_SAMPLING_420) { launch_yuv_sampled(desc, src, src_fs, L, w, h, n, dst, st); return; }
     dim3 grid(cdiv(cdiv(w, 4), YUV_TX), cdiv(h / 2, YUV_TY), n);
     if (!desc.is_default()) {
         const YuvDescArgs d = yuv_desc_args(desc, src, src_fs, L, w, h, dst);

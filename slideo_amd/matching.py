@@ -350,7 +350,7 @@ class HipImageVideoMatcher:
 
     def __init__(self, cfg=None, device=None, sift=None, devices=None, working_size=None, frame_mask=None, frame_mask_scope=None,
                  direct_similarity=None, direct_scope=None, frame_region=None, yuv_description=None, gate_reference=None, gate_settle=None,
-                 group_gate_order=None):
+                 group_gate_order=None, yuv_sampling=None):
         """devices: HIP ordinals, one matcher each behind one slideo_group (the reference fans out over the whole machine, the
         global rayon pool of lib.rs:45,174); None = every gfx950 device of the node; `device` = d is short for devices = [d].
         sift = (slideo_sift_config, ratio): the north-star's SIFT + L2 front end instead of the reference's ORB + Hamming
@@ -379,6 +379,9 @@ class HipImageVideoMatcher:
         (slideo_group_set_yuv_description): how the YUV 4:2:0 videos are read — ("bt709", "limited") for HD recordings,
         ("bt709", "full") for many screen recorders; the reference reads every stream as BT.601 limited range; RawVideoYuv420
         files hold 8-bit samples, so depth stays 8 for them; None = BT.601 limited, 8-bit.
+        yuv_sampling = "420" | "422" | "444" | "422_packed" (slideo_group_set_yuv_sampling): where the frames' samples lie — 4:4:4
+        for screen recorders, 4:2:2 for ProRes / broadcast recorders, packed 4:2:2 (YUY2, UYVY) for capture cards; every call that
+        takes a layout then reads its frames under it; the reference knows BGR only; None = 4:2:0.
         gate_reference = "previous" or "anchor" (slideo_group_set_gate_reference): with "anchor" a frame is compared with the last
         frame that was flagged, not the frame before it, so a change spread over many frames (a cross-fade, an animated build) is
         still flagged when every decoded frame is fed; with several devices it needs group_gate_order = "chain" — without it the
@@ -398,6 +401,7 @@ class HipImageVideoMatcher:
         self._direct_scope = direct_scope
         self._frame_region = frame_region
         self._yuv_description = tuple(yuv_description) if yuv_description is not None else None
+        self._yuv_sampling = yuv_sampling
         self._gate_reference = gate_reference
         self._gate_settle = tuple(gate_settle) if gate_settle is not None else None
         self._group_gate_order = group_gate_order
@@ -421,6 +425,8 @@ class HipImageVideoMatcher:
             m.set_frame_region(*self._frame_region)
         if self._yuv_description is not None:
             m.set_yuv_description(*self._yuv_description)
+        if self._yuv_sampling is not None:
+            m.set_yuv_sampling(self._yuv_sampling)
         if self._frame_mask_scope is not None:
             m.set_frame_mask_scope(self._frame_mask_scope)
         if self._frame_mask is not None:
