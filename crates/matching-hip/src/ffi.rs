@@ -13,6 +13,9 @@ pub const SLIDEO_GATE_PREVIOUS: u32 = 0;
 pub const SLIDEO_GATE_ANCHOR: u32 = 1;
 pub const SLIDEO_GROUP_GATE_HALO: u32 = 0;
 pub const SLIDEO_GROUP_GATE_CHAIN: u32 = 1;
+pub const SLIDEO_GATE_MEMORY_MAX: i32 = 64;
+pub const SLIDEO_GATE_REF_RESET: i64 = -1;
+pub const SLIDEO_GATE_REF_DEFERRED: i64 = -2;
 pub const SLIDEO_YUV_MATRIX_BT601: i32 = 0;
 pub const SLIDEO_YUV_MATRIX_BT709: i32 = 1;
 pub const SLIDEO_YUV_RANGE_LIMITED: i32 = 0;
@@ -519,6 +522,12 @@ extern "C" {
     pub fn slideo_group_gate_state_export(g: *mut slideo_group, out: *mut u8, capacity: i64, bytes: *mut i64) -> i32;
     pub fn slideo_group_gate_state_import(g: *mut slideo_group, rec: *const u8, bytes: i64) -> i32;
     pub fn slideo_group_gate_chain_waited(g: *const slideo_group, member: i32, seconds: *mut f64) -> i32;
+    // gate memory (include/slideo_amd.h "Gate memory"): under SLIDEO_GATE_ANCHOR, the last `capacity` matched frames; 0: off
+    pub fn slideo_matcher_set_gate_memory(m: *mut slideo_matcher, capacity: i32) -> i32;
+    pub fn slideo_matcher_gate_memory(m: *const slideo_matcher, capacity: *mut i32) -> i32;
+    pub fn slideo_group_set_gate_memory(g: *mut slideo_group, capacity: i32) -> i32;
+    pub fn slideo_matcher_last_gate_refs(m: *mut slideo_matcher, refs_out: *mut i64, capacity: i64, n: *mut i64) -> i32;
+    pub fn slideo_group_last_gate_refs(g: *mut slideo_group, refs_out: *mut i64, capacity: i64, n: *mut i64) -> i32;
     pub fn slideo_small_gram_ssd(
         m: *mut slideo_matcher,
         small: *const u8,

@@ -113,9 +113,66 @@ pub struct HipImageVideoMatcher {
     /// ffi::SLIDEO_GROUP_GATE_CHAIN (every shard receives the whole gate state of the shard before it, so the anchor reference
     /// and a settle run on any number of devices and return what one device returns).
     pub group_gate_order: u32,
+    /// The gate memory's capacity (slideo_group_set_gate_memory), under ffi::SLIDEO_GATE_ANCHOR only, applied after
+    /// gate_reference and gate_settle: the last `gate_memory` (1 ..= 64) matched frames are remembered and a frame that returns
+    /// to one of them is recalled, not matched again; the task emits the remembered verdict at that frame's time.  One device
+    /// only.  0: off, the default.
+    pub gate_memory: i32,
+}
+
+/// The task's side of the gate memory (slideo_amd.h "Gate memory") behind a gate reset to "none": the verdicts of the matched
+/// ordinals it remembers (at most `capacity`, the library's own ring), the next frame's ordinal and the last frame's ref.
+pub struct GateMemory {
+    pub verdicts: std::collections::BTreeMap<i64, ffi::slideo_verdict>,
+    pub next: i64,
+    pub prev_ref: i64,
+    pub capacity: usize,
+}
+
+impl GateMemory {
+    pub fn new(capacity: usize) -> Self {
+        GateMemory { verdicts: std::collections::BTreeMap::new(), next: 0, prev_ref: i64::MIN, capacity }
+    }
+}
+
+/// What one gated call emits under a gate memory: (index in the call, verdict), in order.  A matched frame emits its own verdict,
+/// which is remembered under its ordinal; a frame that is not matched and whose ref >= 0 differs from the ref of the frame before
+/// it (a recall, or the return to the anchor behind deferred frames) emits the verdict of the frame it stands behind.
+pub fn gate_memory_emission(
+    changed: &[u8],
+    refs: &[i64],
+    verdicts: &[ffi::slideo_verdict],
+    memory: &mut GateMemory,
+) -> Vec<(usize, ffi::slideo_verdict)> {
+    let mut out = Vec::new();
+    for i in 0..changed.len() {
+        if changed[i] != 0 {
+            memory.verdicts.insert(memory.next + i as i64, verdicts[i]);
+            while memory.verdicts.len() > memory.capacity {
+                let oldest = *memory.verdicts.keys().next().unwrap();
+                memory.verdicts.remove(&oldest);
+            }
+            out.push((i, verdicts[i]));
+        } else if refs[i] >= 0 && refs[i] != memory.prev_ref {
+            if let Some(v) = memory.verdicts.get(&refs[i]) {
+                out.push((i, *v));
+            }
+        }
+        memory.prev_ref = refs[i];
+    }
+    memory.next += changed.len() as i64;
+    out
 }
 
 impl HipImageVideoMatcher {
+    /// Builder: the gate memory under the anchor reference (sets gate_reference to ffi::SLIDEO_GATE_ANCHOR when it switches one on).
+    pub fn gate_memory(mut self, capacity: i32) -> Self {
+        if capacity > 0 {
+            self.gate_reference = ffi::SLIDEO_GATE_ANCHOR;
+        }
+        self.gate_memory = capacity;
+        self
+    }
     /// Builder: the gate settle under the anchor reference (sets gate_reference to ffi::SLIDEO_GATE_ANCHOR when it switches one on).
     pub fn gate_settle(mut self, settle_similarity: f32, max_defer: i32) -> Self {
         if settle_similarity > 0.0 {
@@ -146,6 +203,7 @@ impl Default for HipImageVideoMatcher {
             gate_reference: ffi::SLIDEO_GATE_PREVIOUS,
             gate_settle: (0.0, 0),
             group_gate_order: ffi::SLIDEO_GROUP_GATE_HALO,
+            gate_memory: 0,
         }
     }
 }
@@ -177,6 +235,9 @@ impl<'i> ImageVideoMatcher<'i> for HipImageVideoMatcher {
             }
             if self.gate_settle.0 != 0.0 {
                 check(h, ffi::slideo_group_set_gate_settle(h, self.gate_settle.0, self.gate_settle.1));
+            }
+            if self.gate_memory != 0 {
+                check(h, ffi::slideo_group_set_gate_memory(h, self.gate_memory));
             }
             if let Some(ratio) = self.sift_ratio {
                 let mut sc = std::mem::MaybeUninit::<ffi::slideo_sift_config>::uninit();
@@ -247,6 +308,7 @@ impl<'i> ImageVideoMatcher<'i> for HipImageVideoMatcher {
             handle: Arc::new(Handle { raw: Mutex::new(RawHandle(h)) }),
             images: Arc::new(images),
             n_devices: n_members,
+            gate_memory: self.gate_memory.max(0) as usize,
         })
     }
 }
@@ -255,6 +317,7 @@ struct HipVideoMatcher<I> {
     handle: Arc<Handle>,
     images: Arc<Vec<I>>,
     n_devices: usize,
+    gate_memory: usize,
 }
 
 impl<'i, I: MatchableImage + Send + Sync + Copy + Eq + 'i> VideoMatcher<'i, I> for HipVideoMatcher<I> {
@@ -272,6 +335,7 @@ impl<'i, I: MatchableImage + Send + Sync + Copy + Eq + 'i> VideoMatcher<'i, I> f
             handle: self.handle.clone(),
             images: self.images.clone(),
             n_devices: self.n_devices,
+            gate_memory: self.gate_memory,
             video_path: video_path.to_owned(),
             progress_reporter,
         })
@@ -282,6 +346,7 @@ struct HipVideoMatcherTask<I> {
     handle: Arc<Handle>,
     images: Arc<Vec<I>>,
     n_devices: usize,
+    gate_memory: usize,
     video_path: PathBuf,
     progress_reporter: ProgressReporter,
 }
@@ -317,6 +382,7 @@ impl<I: MatchableImage + Send + Sync + Copy + Eq> VideoMatcherTask<I> for HipVid
             // the first frame of the video is always changed
             unsafe { check(h, ffi::slideo_group_gate_reset(h, std::ptr::null(), 0, 0)) };
         }
+        let mut memory = GateMemory::new(self.gate_memory);
         // one call = one shard of FRAMES_PER_CALL_PER_DEVICE sampled frames per device (mo/lib.rs:213: one task per frame over the pool)
         for batch in decode::batches(vid, FRAMES_PER_CALL_PER_DEVICE * self.n_devices) {
             let n = batch.meta.len();
@@ -344,9 +410,19 @@ impl<I: MatchableImage + Send + Sync + Copy + Eq> VideoMatcherTask<I> for HipVid
                         ),
                     );
                 }
-                for i in (0..n).filter(|&i| changed[i] != 0) {
-                    let (time, frame_idx) = batch.meta[i];
-                    let v = &all[i];
+                // under a gate memory a recalled frame has changed == 0 but shows another page than the frame before it: the
+                // verdict of the frame it stands behind is emitted at its time (slideo_amd.h "Gate memory")
+                let hits: Vec<(usize, ffi::slideo_verdict)> = if self.gate_memory > 0 {
+                    let mut refs = vec![0i64; n];
+                    let mut n_refs = 0i64;
+                    unsafe { check(h, ffi::slideo_group_last_gate_refs(h, refs.as_mut_ptr(), n as i64, &mut n_refs)) };
+                    assert_eq!(n_refs, n as i64, "slideo_group_last_gate_refs: the refs are not the call's");
+                    gate_memory_emission(&changed, &refs, &all, &mut memory)
+                } else {
+                    (0..n).filter(|&i| changed[i] != 0).map(|i| (i, all[i])).collect()
+                };
+                for (i, v) in hits.iter() {
+                    let (time, frame_idx) = batch.meta[*i];
                     results.push(Matching {
                         video_time: time,
                         video_frame_idx: frame_idx,

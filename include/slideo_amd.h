@@ -1475,6 +1475,99 @@ int32_t     slideo_matcher_content_box(slideo_matcher* m, int32_t min_share_ppm,
                                        int64_t* n_content, uint32_t* fill_out /*nullable: ah row fills, then aw column fills*/,
                                        int64_t fill_capacity_elems);
 
+/* ---- Gate memory (extension: recall the verdict of an earlier matched frame) --------------------------------------------------------
+ * Under SLIDEO_GATE_ANCHOR the gate knows ONE earlier picture, the anchor.  A lecture recording returns to pictures it has shown
+ * before — a cut back from the speaker camera to the slide, a flip back two slides, a toggled build, a recurring agenda slide —, and
+ * every such return is "away from the anchor": it goes through the pipeline and gets a verdict the library already computed for a
+ * frame of the same picture, within the threshold the gate already trusts.  The second verdict need not even equal the first.
+ * A matcher carries a GATE MEMORY capacity M.  0 is off: the default, everything as before.  1 <= M <= SLIDEO_GATE_MEMORY_MAX (64:
+ * one lane per entry); anything else is SLIDEO_ERR_INVALID_ARG and the value before stays.  It is meaningful under
+ * SLIDEO_GATE_ANCHOR only, with or without a gate settle.  Everything is exact and in integers.
+ * The gate state is then "none", or: an ordered list E of at most M ENTRIES, oldest first — each the small image of a frame that
+ * was matched, plus that frame's ORDINAL —; which entry is the ANCHOR; the previous gated frame's small image and the deferral count
+ * d, as under a settle.  A frame's ordinal is its position among the frames of all gated calls and units since the last reset, from
+ * 0, as int64.  Frame f with ordinal t is decided as follows; T_c, T_s, ssd_a, ssd_p, away and still are exactly as in "Gate
+ * settle" (over the valid small pixels and n_valid under SLIDEO_MASK_GATE):
+ *   state "none"  f is matched: changed = 1, similarity 0.0; E = [(f, t)], it is the anchor and the previous frame, d = 0, ref = t.
+ *   !away         changed = 0, d = 0, ref = the anchor's ordinal.
+ *   away          let ssd_e be the SSD of f against each entry e of E and r the entry with the smallest ssd_e, ties to the greatest
+ *                 ordinal.  If ssd_r < T_c, f is RECALLED: changed = 0, the anchor becomes r, d = 0, ref = r's ordinal.  No test
+ *                 excludes the anchor: it cannot qualify, being away.
+ *                 Nothing recalled: the rule in force decides.  f is MATCHED if there is no settle, or if still, or if d >=
+ *                 max_defer: changed = 1 and (f, t) is appended to E — when E already holds M entries the oldest is dropped first
+ *                 (FIFO: a recall does not refresh an entry) —, f is the anchor, d = 0, ref = t.  Otherwise f is DEFERRED:
+ *                 changed = 0, d = min(d + 1, max_defer), ref = SLIDEO_GATE_REF_DEFERRED.
+ *   In every case f becomes the previous frame and the next ordinal is t + 1.
+ *   similarity    similarity[i] is the mask call's host expression of ssd_a, against the anchor in force BEFORE the frame is
+ *                 decided, as under ANCHOR.  A recalled frame, like a deferred one, has changed == 0 && similarity <
+ *                 cfg.changed_similarity; ref tells them apart (slideo_matcher_last_gate_refs).
+ *   records       a recalled frame's record is the unchanged record {-1, 0, 0, 0}; the kept list, the traces' indexing and the
+ *                 direct look-up see changed == 1 frames only.  Rules 2, 3, 4 and 6 of "Changed-frame gate" hold word for word.
+ *   independence  the result depends neither on unit and call boundaries nor on the number of units in flight.
+ *   state calls   slideo_matcher_gate_reset(S) and slideo_matcher_gate_reset_from_frame_* leave E = [(S, SLIDEO_GATE_REF_RESET)],
+ *                 S as anchor and previous frame, d = 0, the next ordinal 0; a reset to "none" leaves the next ordinal 0;
+ *                 slideo_matcher_gate_last_small returns the anchor's small image, unmasked; everything that resets the gate state
+ *                 resets the memory.
+ * Consequences.  With M = 1, flags, similarities, verdicts, traces and the last small image equal those of the same stream without
+ * a memory, bit for bit.  Every frame with ref >= 0 is within cfg.changed_similarity of the frame with that ordinal, which got a
+ * verdict.  A recall stands behind the verdict that frame got under whatever page set was selected then.  (tests/gate_memory_ref.py
+ * restates the rule in numpy.)
+ * The capacity is part of the gate-reference frame setting: it changes on an idle matcher only (SLIDEO_ERR_STATE) and a set call
+ * resets the gate state, also when the value does not change.  M > 0 with a gate reference other than SLIDEO_GATE_ANCHOR is
+ * SLIDEO_ERR_UNSUPPORTED, whichever call would complete the combination — slideo_matcher_set_gate_memory under PREVIOUS, or
+ * slideo_matcher_set_gate_reference(PREVIOUS) while a memory is on —, and the values before stay in force.
+ * Refused by name, the state before kept: a group of more than one member refuses M > 0 with SLIDEO_ERR_UNSUPPORTED, checked before
+ * any member is touched (the chain's baton carries three buffers, not a ring); a group of one member forwards.  While M > 0,
+ * slideo_matcher_gate_state_bytes / _export / _import and the group forms return SLIDEO_ERR_UNSUPPORTED: record version 1 holds no
+ * memory, and with M = 0 everything about it stays as it is.  LRU refresh, capacities above 64 and the memory in the record are
+ * follow-ups.
+ * Where it runs (csrc/gate_anchor.hip.h, csrc/stage_gate_anchor.hip; gate_unit_submit's one branch into gate_anchor_unit, which with
+ * M == 0 launches exactly what it launched before).  With M > 0 a unit of n frames: its operand, norms and pair table as before;
+ * then, behind the wait on the previous gated unit, the memory's centred operand and norms (direct_centre_kernel over the memory's
+ * WHOLE small images under the gate weights in force now, rebuilt per unit: a frame-mask change keeps the gate state), the table
+ * mdot[j * M + c] = <a'_j, e'_c> (page_ssd_kernel, the engine as it is) and, under a settle, frame 0's SSD against the carried
+ * previous frame (gate_carried_ssd_kernel); gate_recall_kernel — one wave, no LDS: lane l < M holds slot l's occupant, a carried
+ * entry or a frame of this unit; the 64 lanes test frames i .. i + 63 against the anchor, one ballot gives away, the lanes below the
+ * first away frame j are unchanged; for j every lane computes its occupant's SSD, a wave reduction on (SSD, then greater ordinal)
+ * finds r, and j is recalled, matched (slot head := j, head = (head + 1) % M) or deferred; the walk continues at j + 1, so a unit
+ * with more than M matches evicts inside the walk —; gate_memory_state_kernel copies every slot whose occupant is a frame of this
+ * unit into the memory with its ordinal, the previous frame, d, head, count and the anchor slot.  The memory takes M small images,
+ * its operand 64 rows, the table 8 n M bytes and the refs 8 n; every allocation happens before the first write of the gate state. */
+#define SLIDEO_GATE_MEMORY_MAX 64
+#define SLIDEO_GATE_REF_RESET (-1)      /* ref: the frame stands behind the image of slideo_matcher_gate_reset[_from_frame_*] */
+#define SLIDEO_GATE_REF_DEFERRED (-2)   /* ref: the frame is deferred and stands behind no verdict */
+/* Idle matcher (SLIDEO_ERR_STATE otherwise).  Resets the gate state, also when the value does not change. */
+int32_t     slideo_matcher_set_gate_memory(slideo_matcher* m, int32_t capacity);
+/* The matcher's gate memory capacity (0 unless set).  SLIDEO_ERR_INVALID_ARG for a null argument. */
+int32_t     slideo_matcher_gate_memory(const slideo_matcher* m, int32_t* capacity);
+/* Every member idle.  More than one member: capacity > 0 is SLIDEO_ERR_UNSUPPORTED (above).  Resets the group's gate state. */
+int32_t     slideo_group_set_gate_memory(slideo_group* g, int32_t capacity);
+/* The ref of every frame of the last synchronous gated call (all its units, in order) or of the last collected gated ticket: the
+ * ordinal of the matched frame it stands behind (its own when it was matched), SLIDEO_GATE_REF_RESET or SLIDEO_GATE_REF_DEFERRED.
+ * *n is always set.  SLIDEO_ERR_CAPACITY when n > capacity or refs_out is NULL; SLIDEO_ERR_STATE when M == 0 or no gated call was
+ * made since the setting.  Units may be in flight (a collect leaves them). */
+int32_t     slideo_matcher_last_gate_refs(slideo_matcher* m, int64_t* refs_out, int64_t capacity, int64_t* n);
+/* A group of one member: its matcher's.  More members hold no memory: SLIDEO_ERR_STATE. */
+int32_t     slideo_group_last_gate_refs(slideo_group* g, int64_t* refs_out, int64_t capacity, int64_t* n);
+/* Tap, idle matcher: the entries, oldest first — *count of them, their ordinals in ordinals_out [64] — and the anchor's index among
+ * them.  The state "none": *count = 0, *anchor = -1.  SLIDEO_ERR_STATE when M == 0. */
+int32_t     slideo_matcher_gate_memory_entries(slideo_matcher* m, int32_t* count, int32_t* anchor, int64_t* ordinals_out /*64*/);
+/* Tap, idle matcher: the small image of entry `entry` (0: the oldest), unmasked.  *sw, *sh always set when entries exist;
+ * SLIDEO_ERR_INVALID_ARG for an entry outside 0 .. count - 1, SLIDEO_ERR_CAPACITY when it takes more than `capacity` bytes. */
+int32_t     slideo_matcher_gate_memory_small(slideo_matcher* m, int32_t entry, uint8_t* out, int64_t capacity, int32_t* sw, int32_t* sh);
+/* Tap: gate_recall_kernel on its own inputs.  dot [n * n], norm [n]: the unit's, as slideo_gate_settle_walk takes them; mdot [n * M]:
+ * mdot[j * M + c] = <a'_j, e'_c>, mnorm [M]: |e'_c|^2 of the carried slots; ordinals [M], count, head, anchor_slot: the carried ring
+ * (slots 0 .. count - 1 are occupied, head is the slot the next match overwrites; with count < M head == count); prev_ssd0: frame 0's
+ * SSD against the carried previous frame; thr_c, thr_s, max_defer (0 without a settle), d_in (0 <= d_in <= max_defer); none != 0:
+ * the state "none" (nothing carried is read); t0: frame 0's ordinal; 1 <= M <= 64; 1 <= n <= 1024.
+ * -> changed_out [n], ssd_out [n] (ssd_a per frame), refs_out [n], occupants_out [64] (per slot the frame of this unit that occupies
+ * it behind the unit, -1: what it carried, or nothing), *head_out, *count_out, *anchor_out (a slot), *d_out.  Idle matcher. */
+int32_t     slideo_gate_recall_walk(slideo_matcher* m, const uint64_t* dot, const int64_t* norm, const uint64_t* mdot, const int64_t* mnorm,
+                                    const int64_t* ordinals, int32_t count, int32_t head, int32_t anchor_slot, uint64_t prev_ssd0, int32_t n,
+                                    int32_t M, int64_t thr_c, int64_t thr_s, int32_t max_defer, int32_t d_in, int32_t none, int64_t t0,
+                                    uint8_t* changed_out, uint64_t* ssd_out, int64_t* refs_out, int32_t* occupants_out /*64*/,
+                                    int32_t* head_out, int32_t* count_out, int32_t* anchor_out, int32_t* d_out);
+
 #ifdef __cplusplus
 }
 #endif

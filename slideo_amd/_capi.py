@@ -257,6 +257,8 @@ EXPORTS = [
     "slideo_matcher_gate_state_bytes", "slideo_matcher_gate_state_export", "slideo_matcher_gate_state_import",
     "slideo_group_set_gate_order", "slideo_group_gate_order", "slideo_group_gate_state_export", "slideo_group_gate_state_import",
     "slideo_group_gate_chain_waited",
+    "slideo_matcher_set_gate_memory", "slideo_matcher_gate_memory", "slideo_group_set_gate_memory", "slideo_matcher_last_gate_refs",
+    "slideo_group_last_gate_refs", "slideo_matcher_gate_memory_entries", "slideo_matcher_gate_memory_small", "slideo_gate_recall_walk",
 ]
 
 # frame mask scope (include/slideo_amd.h "Frame mask scope")
@@ -273,6 +275,10 @@ GATE_REFERENCES = {"previous": GATE_PREVIOUS, "anchor": GATE_ANCHOR}
 GROUP_GATE_HALO = 0
 GROUP_GATE_CHAIN = 1
 GROUP_GATE_ORDERS = {"halo": GROUP_GATE_HALO, "chain": GROUP_GATE_CHAIN}
+# gate memory (include/slideo_amd.h "Gate memory"): the capacity's limit and the two refs that are no ordinal
+GATE_MEMORY_MAX = 64
+GATE_REF_RESET = -1
+GATE_REF_DEFERRED = -2
 
 
 def gate_deferred(changed, similarity, changed_similarity):
@@ -423,6 +429,17 @@ def lib():
             L.slideo_group_gate_state_export.argtypes = [vp, vp, i64, vp]
             L.slideo_group_gate_state_import.argtypes = [vp, vp, i64]
             L.slideo_group_gate_chain_waited.argtypes = [vp, i32, vp]
+        if hasattr(L, "slideo_matcher_set_gate_memory"):
+            vp, i32, i64, u64 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64
+            L.slideo_matcher_set_gate_memory.argtypes = [vp, i32]
+            L.slideo_matcher_gate_memory.argtypes = [vp, vp]
+            L.slideo_group_set_gate_memory.argtypes = [vp, i32]
+            L.slideo_matcher_last_gate_refs.argtypes = [vp, vp, i64, vp]
+            L.slideo_group_last_gate_refs.argtypes = [vp, vp, i64, vp]
+            L.slideo_matcher_gate_memory_entries.argtypes = [vp, vp, vp, vp]
+            L.slideo_matcher_gate_memory_small.argtypes = [vp, i32, vp, i64, vp, vp]
+            L.slideo_gate_recall_walk.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, u64, i32, i32, i64, i64, i32, i32, i32, i64,
+                                                  vp, vp, vp, vp, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -655,6 +672,37 @@ class _FrameCalls:
         if rc != OK:
             raise SlideoError(rc, "gate_settle")
         return s.value, d.value
+
+    # gate memory (include/slideo_amd.h "Gate memory"): under 'anchor', recall the verdict of an earlier matched frame
+    def set_gate_memory(self, capacity):
+        """capacity: 0 (off, the default) or 1 .. GATE_MEMORY_MAX: the last `capacity` matched frames are remembered, and a frame away
+        from the anchor that is within changed_similarity of one of them is recalled (changed == 0, last_gate_refs() names the frame
+        it stands behind).  Needs the gate reference 'anchor'; the matcher must be idle; resets the gate state.  A Group of more than
+        one member refuses a memory that is on."""
+        capacity = int(capacity)
+        if not 0 <= capacity <= GATE_MEMORY_MAX:
+            raise SlideoError(1, "gate memory: capacity %d outside 0 .. %d" % (capacity, GATE_MEMORY_MAX))
+        self._check(getattr(lib(), self._SETS + "set_gate_memory")(self._h, capacity))
+
+    def gate_memory(self):
+        """The gate memory's capacity; 0 unless set (a Group: member 0's)."""
+        c = C.c_int32()
+        rc = lib().slideo_matcher_gate_memory(self._mask_owner(), C.byref(c))
+        if rc != OK:
+            raise SlideoError(rc, "gate_memory")
+        return c.value
+
+    def last_gate_refs(self):
+        """int64 [n]: for every frame of the last synchronous gated call, or of the last collected gated ticket, the ordinal of the
+        matched frame it stands behind (its own when it was matched), GATE_REF_RESET or GATE_REF_DEFERRED."""
+        f = getattr(lib(), self._SETS + "last_gate_refs")
+        n = C.c_int64()
+        rc = f(self._h, None, 0, C.byref(n))
+        if rc not in (OK, 7):                                    # (SLIDEO_ERR_CAPACITY: *n is the size to ask with)
+            self._check(rc)
+        out = np.empty(n.value, np.int64)
+        self._check(f(self._h, _p(out), n.value, C.byref(n)))
+        return out
 
     # YUV colour description (include/slideo_amd.h "YUV colour description"): how every *_yuv420 call reads its samples
     def set_yuv_description(self, matrix="bt601", range="limited", depth=8):
@@ -1342,6 +1390,42 @@ class Matcher(_FrameCalls):
         self._check(lib().slideo_gate_settle_walk(self._h, _p(dot), _p(norm), _p(carried), n, C.c_int64(int(thr_c)), C.c_int64(int(thr_s)),
                                                   int(max_defer), int(d_in), 1 if none else 0, _p(changed), _p(ssd), C.byref(a), C.byref(d)))
         return changed, ssd, a.value, d.value
+
+    def gate_memory_entries(self):
+        """slideo_matcher_gate_memory_entries -> (ordinals int64 [count], oldest first, the anchor's index among them or -1)."""
+        count, anchor = C.c_int32(), C.c_int32()
+        ords = np.zeros(GATE_MEMORY_MAX, np.int64)
+        self._check(lib().slideo_matcher_gate_memory_entries(self._h, C.byref(count), C.byref(anchor), _p(ords)))
+        return ords[:count.value].copy(), anchor.value
+
+    def gate_memory_small(self, entry):
+        """The small image [sh, sw, 3] of entry `entry` of the gate memory (0: the oldest), unmasked."""
+        sw, sh = C.c_int32(), C.c_int32()
+        out = np.empty(self.cfg.small_area * 3, np.uint8)
+        self._check(lib().slideo_matcher_gate_memory_small(self._h, int(entry), _p(out), C.c_int64(out.size), C.byref(sw), C.byref(sh)))
+        return out[:sw.value * sh.value * 3].reshape(sh.value, sw.value, 3).copy()
+
+    def gate_recall_walk(self, dot, norm, mdot, mnorm, ordinals, count, head, anchor_slot, prev_ssd0, thr_c, thr_s, max_defer, d_in=0, none=False,
+                         t0=0):
+        """slideo_gate_recall_walk: dot [n, n] (read for i < j), norm int64 [n], mdot [n, M], mnorm int64 [M], the carried ring
+        (ordinals int64 [M], count, head, anchor slot), frame 0's SSD against the carried previous frame ->
+        (changed uint8 [n], ssd uint64 [n], refs int64 [n], occupants int32 [64], head, count, anchor slot, d)."""
+        norm = np.ascontiguousarray(norm, np.int64)
+        mnorm = np.ascontiguousarray(mnorm, np.int64)
+        n, M = len(norm), len(mnorm)
+        dot = np.ascontiguousarray(np.asarray(dot).astype(np.int64).view(np.uint64))
+        mdot = np.ascontiguousarray(np.asarray(mdot).astype(np.int64).view(np.uint64))
+        ordinals = np.ascontiguousarray(ordinals, np.int64)
+        if dot.shape != (n, n) or mdot.shape != (n, M) or ordinals.shape != (M,):
+            raise ValueError("expected dot [n, n], norm [n], mdot [n, M], mnorm [M], ordinals [M]")
+        changed, ssd, refs = np.zeros(n, np.uint8), np.zeros(n, np.uint64), np.zeros(n, np.int64)
+        occ = np.zeros(GATE_MEMORY_MAX, np.int32)
+        h, c, a, d = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+        self._check(lib().slideo_gate_recall_walk(
+            self._h, _p(dot), _p(norm), _p(mdot), _p(mnorm), _p(ordinals), int(count), int(head), int(anchor_slot), C.c_uint64(int(prev_ssd0)), n, M,
+            C.c_int64(int(thr_c)), C.c_int64(int(thr_s)), int(max_defer), int(d_in), 1 if none else 0, C.c_int64(int(t0)), _p(changed), _p(ssd),
+            _p(refs), _p(occ), C.byref(h), C.byref(c), C.byref(a), C.byref(d)))
+        return changed, ssd, refs, occ, h.value, c.value, a.value, d.value
 
     def small_image(self, bgr):
         bgr = _img3(bgr)

@@ -493,6 +493,29 @@ int32_t slideo_group_set_gate_settle(slideo_group* g, float settle_similarity, i
     });
 }
 
+// (the gate memory is part of the gate-reference setting; behind the range check the group's own rule: a memory that is on needs a
+// group of one member, and a refused call changes no member)
+int32_t slideo_group_set_gate_memory(slideo_group* g, int32_t capacity) {
+    return group_set(g, SET_GATE_REFERENCE, [&](const FrameSettings& s) {
+        const FrameSettings next = propose_gate_memory(s, capacity);
+        gate_memory_group_rule((int)g->members.size(), capacity);
+        return next;
+    });
+}
+
+// a group of one member forwards; with more members no memory can be on
+int32_t slideo_group_last_gate_refs(slideo_group* g, int64_t* refs_out, int64_t capacity, int64_t* n) {
+    if (!g) return SLIDEO_ERR_INVALID_ARG;
+    GROUP_TRY
+    if (!n) fail(SLIDEO_ERR_INVALID_ARG, "null n");
+    *n = 0;
+    slideo_matcher* m0 = g->members[0];
+    if (g->members.size() > 1 || m0->fs.gate_memory == 0) fail(SLIDEO_ERR_STATE, "last_gate_refs: no gate memory is on (slideo_group_set_gate_memory)");
+    const int32_t rc = slideo_matcher_last_gate_refs(m0, refs_out, capacity, n);
+    if (rc != SLIDEO_OK) fail(rc, "%s", slideo_last_error(m0));
+    GROUP_CATCH(g)
+}
+
 // Page sets: every member builds the same set from the same deck (ids are handed out in the same order: they agree)
 int32_t slideo_group_create_page_set(slideo_group* g, int32_t n_pages, const int32_t* pages, int32_t* set_out) {
     if (!g) return SLIDEO_ERR_INVALID_ARG;
@@ -676,6 +699,7 @@ int32_t slideo_group_gate_state_export(slideo_group* g, uint8_t* out, int64_t ca
     if (!g) return SLIDEO_ERR_INVALID_ARG;
     GROUP_TRY
     if (!bytes) fail(SLIDEO_ERR_INVALID_ARG, "null bytes");
+    gate_record_memory_rule(g->members[0]->fs.gate_memory);
     for (slideo_matcher* m : g->members) require_idle(m);
     if (g->gate.has && g->gate_owner >= 0) {
         slideo_matcher* o = g->members[g->gate_owner];
@@ -701,6 +725,7 @@ int32_t slideo_group_gate_state_import(slideo_group* g, const uint8_t* rec, int6
     if (!g) return SLIDEO_ERR_INVALID_ARG;
     GROUP_TRY
     slideo_matcher* m0 = g->members[0];
+    gate_record_memory_rule(m0->fs.gate_memory);
     (void)gate_record_validate(rec, bytes, m0->fs.gate_ref, m0->fs.settle_similarity, m0->fs.settle_max_defer, m0->cfg.small_area);
     for (slideo_matcher* m : g->members) require_idle(m);
     check_member_call(m0, slideo_matcher_gate_state_import(m0, rec, bytes));

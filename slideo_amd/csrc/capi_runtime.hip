@@ -56,7 +56,7 @@ void upload_area(slideo_matcher* m) {
 }
 
 // max frames of size (w,h) per unit under the workspace budget (the slots share it)
-int sub_batch_for(slideo_matcher* m, const PyrGeom& g, int n, size_t staging) {
+int sub_batch_for(slideo_matcher* m, const PyrGeom& g, int n, size_t staging, size_t fixed) {
     size_t per = (size_t)g.frame_bytes * (blur_is_f32(m) ? 2 : 1) + (size_t)g.cand_per_frame * 4 + (size_t)g.nlevels * 258 * 4 + (size_t)g.w * g.h * 3;
     per += staging;          // the 4:2:0 staging in front of the BGR image, the source-sized frames of a reducing call (other calls keep their unit sizes)
     // downstream of ORB, sized by the per-frame keypoint capacity: items 8 + keypoint 24 + descriptor 32 B, the key lists
@@ -64,7 +64,9 @@ int sub_batch_for(slideo_matcher* m, const PyrGeom& g, int n, size_t staging) {
     // (keypoint, neighbour) the vote 8 B + point pair 16 B + mask 1 B
     const size_t kc = kp_cap_for(m, g);
     per += kc * (8 + sizeof(slideo_keypoint) + 32 + (size_t)KLIST * 4 * 4 + (size_t)m->cfg.knn_k * 25) + sizeof(FrameCands) + MAXR * sizeof(PairDesc);
-    size_t fit = std::max<size_t>(1, (m->ws_budget / NSLOTS) / std::max<size_t>(per, 1));
+    // fixed: what a unit takes whatever its frame count (the gate memory's ring and operand), out of the slot's share first
+    const size_t share = m->ws_budget / NSLOTS;
+    size_t fit = std::max<size_t>(1, (share - std::min(fixed, share)) / std::max<size_t>(per, 1));
     return (int)std::min<size_t>({(size_t)std::max(n, 1), fit, (size_t)4096});
 }
 
@@ -151,7 +153,7 @@ void settings_commit(slideo_matcher* m, Setting what, FrameSettings next, const 
     m->fs = next;
     const SettingEnds& ends = SETTING_ENDS[what];
     if (ends.kept) m->kept.valid = false;
-    if (ends.gate) gate_state_reset(m);
+    if (ends.gate) { gate_state_reset(m); m->gate_refs.clear(); m->gate_refs_valid = false; }
     if (ends.map_gen) ++m->fs.gate_map_gen;
 }
 
@@ -348,7 +350,8 @@ static void unit_begin(slideo_matcher* m, Slot& S, const FrameSrc& src, int firs
 
 // max frames per unit of a call of either kind under the workspace budget
 static int unit_fit(slideo_matcher* m, const FrameSrc& src, int n, bool gated) {
-    const int fit = sub_batch_for(m, geom_for(m, src.plan.uw, src.plan.uh).g, n, src.staging_bytes(gated ? gate_small_budget(m) : 0));
+    const int fit = sub_batch_for(m, geom_for(m, src.plan.uw, src.plan.uh).g, n, src.staging_bytes(gated ? gate_small_budget(m) : 0),
+                                  gated ? gate_memory_budget(m) : 0);
     // (under SLIDEO_GATE_ANCHOR a gated unit's pair table caps it: include/slideo_amd.h "Gate reference")
     return gated && m->fs.gate_ref == SLIDEO_GATE_ANCHOR ? std::min(fit, GATE_ANCHOR_MAX_UNIT) : fit;
 }
@@ -385,6 +388,9 @@ void match_frames_impl(slideo_matcher* m, int n, FrameSrc src, slideo_verdict* o
     // through the copy stream)
     hipStream_t cs = src.pinned ? m->copy_st : nullptr;
     m->units_pending = n > unit;
+    // with a gate memory the call's units append their refs in order ("Gate memory": slideo_matcher_last_gate_refs)
+    struct RefsCall { slideo_matcher* m; ~RefsCall() { m->gate_refs_call = false; } } refs_call{m};
+    if (gated && m->fs.gate_ref == SLIDEO_GATE_ANCHOR && m->fs.gate_memory > 0) { m->gate_refs.clear(); m->gate_refs_call = true; }
     auto collect = [&](const Pending& p) {
         if (gated) {
             gate_unit_collect(m, *p.S, changed_out + p.ofs, similarity_out ? similarity_out + p.ofs : nullptr, out + p.ofs);

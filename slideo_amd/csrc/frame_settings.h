@@ -1,5 +1,5 @@
 // frame_settings.h — the frame settings of a matcher as ONE record (include/slideo_amd.h "Working size", "Frame region", "Frame mask",
-// "Frame mask scope", "Direct page look-up", "Direct look-up scope", "YUV colour description", "YUV sampling", "Gate reference", "Gate settle"): the record, every setter's proposal with its range checks, the
+// "Frame mask scope", "Direct page look-up", "Direct look-up scope", "YUV colour description", "YUV sampling", "Gate reference", "Gate settle", "Gate memory"): the record, every setter's proposal with its range checks, the
 // rules between settings, what a change of each ends.  Plain C++, no HIP include (tools/frame_settings_hostcheck.cpp walks it on the
 // host); the device buffers a setting owns are the matcher's (runtime.hpp).  A change takes ONE path: settings_commit (capi_runtime.hip).
 #pragma once
@@ -51,6 +51,9 @@ struct FrameSettings {
     // is within settle_similarity of the frame before it, or after settle_max_defer deferred frames; 0: off
     float settle_similarity = 0.f;
     int32_t settle_max_defer = 0;
+    // the gate memory, part of the gate-reference setting ("Gate memory"): under ANCHOR the last gate_memory matched frames are kept
+    // and a frame away from the anchor that is within changed_similarity of one of them is recalled, not matched; 0: off
+    int32_t gate_memory = 0;
     bool gate_scope() const { return mask.set && (mask_scope & SLIDEO_MASK_GATE); }      // the gate compares under the mask
 };
 
@@ -151,6 +154,26 @@ inline FrameSettings propose_gate_settle(FrameSettings s, float settle_similarit
     if (max_defer < 0) fail(SLIDEO_ERR_INVALID_ARG, "gate settle: max_defer %d: 0 <= max_defer <= INT32_MAX", max_defer);
     s.settle_similarity = settle_similarity; s.settle_max_defer = max_defer;
     return s;
+}
+// The gate memory commits under SET_GATE_REFERENCE as the settle does: the state means something else, so the gate resets
+inline FrameSettings propose_gate_memory(FrameSettings s, int32_t capacity) {
+    if (capacity < 0 || capacity > SLIDEO_GATE_MEMORY_MAX)
+        fail(SLIDEO_ERR_INVALID_ARG, "gate memory: capacity %d: 0 (off) or 1 .. %d", capacity, SLIDEO_GATE_MEMORY_MAX);
+    s.gate_memory = capacity;
+    return s;
+}
+// The group's rule for a gate memory (include/slideo_amd.h "Gate memory"): the chain's baton carries three buffers, not a ring, and
+// a one-frame halo carries no memory, so a memory that is on needs a group of one member.  Setting it off always passes.
+inline void gate_memory_group_rule(int members, int32_t capacity) {
+    if (capacity > 0 && members > 1)
+        fail(SLIDEO_ERR_UNSUPPORTED, "a gate memory in a group of %d members: the gate state a shard hands on carries no memory (a group of "
+             "one member, or a single matcher)", members);
+}
+// The gate state as a record holds no memory (record version 1): refused by name while a memory is on
+inline void gate_record_memory_rule(int32_t gate_memory) {
+    if (gate_memory > 0)
+        fail(SLIDEO_ERR_UNSUPPORTED, "the gate state record (version %u) does not carry the gate memory: not while a gate memory of %d is on "
+             "(slideo_matcher_set_gate_memory(m, 0) first)", 1u, gate_memory);
 }
 // The group's rule for a gate settle (include/slideo_amd.h "Gate settle"): it needs ANCHOR, which needs a group of one member
 // or the group gate order CHAIN ("Group gate order").  Setting it off always passes.
@@ -416,6 +439,11 @@ inline void frame_settings_rules(const FrameSettings& next, Setting what, bool s
         fail(SLIDEO_ERR_UNSUPPORTED, "gate settle under SLIDEO_GATE_ANCHOR only: a settle similarity %g with the gate reference SLIDEO_GATE_PREVIOUS "
              "(slideo_matcher_set_gate_reference(m, SLIDEO_GATE_ANCHOR) first; slideo_matcher_set_gate_settle(m, 0, 0) before going back)",
              (double)next.settle_similarity);
+    // a gate memory recalls frames that are away from the ANCHOR: it means nothing under PREVIOUS
+    if (next.gate_memory > 0 && next.gate_ref != SLIDEO_GATE_ANCHOR)
+        fail(SLIDEO_ERR_UNSUPPORTED, "gate memory under SLIDEO_GATE_ANCHOR only: a capacity of %d with the gate reference SLIDEO_GATE_PREVIOUS "
+             "(slideo_matcher_set_gate_reference(m, SLIDEO_GATE_ANCHOR) first; slideo_matcher_set_gate_memory(m, 0) before going back)",
+             next.gate_memory);
     // packed 4:2:2 is 8-bit: whichever of the two set calls (sampling, description) would complete the pair is refused
     if (next.yuv.sampling == SLIDEO_YUV_SAMPLING_422_PACKED && next.yuv.depth != SLIDEO_YUV_DEPTH_8)
         fail(SLIDEO_ERR_UNSUPPORTED, "SLIDEO_YUV_SAMPLING_422_PACKED reads 8-bit samples: not together with a 10-bit depth (%d); packed 10-bit "

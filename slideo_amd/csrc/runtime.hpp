@@ -196,6 +196,10 @@ struct Slot {
     // anchor n x u64, frame 0 against the carried previous frame u64 | the unit's last anchor i32 | the deferral count behind the
     // unit u32}, and the n x n dot products (reserved by the first such unit only)
     DevBuf d_ga_a, d_ga_rec, d_ga_dot;
+    // ... with a gate memory ("Gate memory"): the memory's centred operand, {|e'|^2 64 x i64 | frame 0 against the carried previous
+    // frame u64 | the walk's GateMemoryUnit | ref n x i64}, the n x M dot products and the refs' pinned twin (the first such unit only)
+    DevBuf d_gm_op, d_gm_rec, d_gm_dot;
+    PinBuf h_gm;
     hipEvent_t ev_gate = nullptr;             // the unit's small images are made and the gate state is this unit's last one
     struct GateUnit {
         bool on = false;                      // the unit in flight is gated: slideo_match_changed_frames_collect collects it
@@ -204,6 +208,8 @@ struct Slot {
         int npx = 0;                          // the pixels the similarity is normalised over: sw * sh, the gate map's n_valid under one
         bool force0 = false;                  // no gate state at submission: frame 0 is changed, similarity 0.0
         bool settle = false;                  // a gate settle was in force: a frame away from its anchor may be deferred (flag 0)
+        bool memory = false;                  // a gate memory was in force: the refs (S.h_gm) tell recalled and deferred frames apart
+        int64_t t0 = 0;                       // ... frame 0's ordinal
         // the direct page look-up ran for the unit (direct_t: the matcher's direct similarity at submission): k counts the changed
         // frames that are not direct, the record's tail (direct.hip.h direct_rec_*) is at direct_ofs; has_elig: a page was eligible
         bool direct = false, has_elig = false;
@@ -371,12 +377,21 @@ struct slideo_matcher {
         bool seen = false;                    // frames were gated since the reset: w, h, yuv are theirs
         int w = 0, h = 0; bool yuv = false;
         int sw = 0, sh = 0;                   // (has) the small image's size
+        int64_t next_ord = 0;                 // the next gated frame's ordinal ("Gate memory"): frames gated since the last reset
     } gate;
     slideo::DevBuf d_gate_small;
     // under a gate settle (include/slideo_amd.h "Gate settle") d_gate_small is the anchor's; beside it the small image of the
     // previous gated frame and the deferral count (u32), written and read where d_gate_small is
     slideo::DevBuf d_gate_prev, d_gate_d;
     hipEvent_t last_gate_ev = nullptr;
+    // gate memory (include/slideo_amd.h "Gate memory"), while fs.gate_memory = M > 0: the M small images of the ring (gm_stride
+    // bytes apart) and its GateMemoryMeta; d_gate_small is then written by the resets alone and d_gate_d not at all (d is the
+    // meta's).  gate_refs: the refs of the last synchronous gated call or the last collected gated ticket (gate_refs_valid: there
+    // was one since the setting; gate_refs_call: a synchronous call is appending its units')
+    slideo::DevBuf d_gm_img, d_gm_meta;
+    int64_t gm_stride = 0;
+    std::vector<int64_t> gate_refs;
+    bool gate_refs_valid = false, gate_refs_call = false;
     // group gate chain (include/slideo_amd.h "Group gate order"; capi_group.hip sets both for ONE gated call, a single matcher never).
     // gate_receive: called once, on the first gated unit's stream, exactly where that unit waits for the previous gated unit's write of
     // the state — it blocks the host until the predecessor's state has arrived and queues its copy into the three state buffers.
@@ -431,7 +446,8 @@ void upload_area(slideo_matcher* m);
 inline bool blur_is_f32(const slideo_matcher* m) { return m->cfg.ocv.blur <= 1; }
 uint32_t kp_cap_for(const slideo_matcher* m, const PyrGeom& g);
 // staging: bytes per frame in front of the unit's BGR image (FrameSrc::staging_bytes)
-int sub_batch_for(slideo_matcher* m, const PyrGeom& g, int n, size_t staging = 0);
+// fixed: bytes a unit takes whatever its frame count (gate_memory_budget), taken out of the slot's share before the frames are counted
+int sub_batch_for(slideo_matcher* m, const PyrGeom& g, int n, size_t staging = 0, size_t fixed = 0);
 void require_idle(slideo_matcher* m);
 void validate_image(int w, int h, int stride);
 // The argument rules of a call's frames (include/slideo_amd.h), in the order the entry points report them: a YUV source's layout
@@ -569,10 +585,19 @@ inline void gate_state_reset(slideo_matcher* m) { m->gate = slideo_matcher::Gate
 inline size_t gate_small_budget(const slideo_matcher* m) {
     const size_t small = (size_t)m->cfg.small_area * 3 + 64;
     const size_t settle = m->fs.settle_similarity > 0.f ? small + 256 + 32 : 0;
-    const size_t anchor = m->fs.gate_ref == SLIDEO_GATE_ANCHOR ? small + 128 + 32 + (size_t)GATE_ANCHOR_MAX_UNIT * 8 + settle : 0;
+    // (with a gate memory of M: + the frame's row of the n x M table and its ref; the ring and its operand: gate_memory_budget)
+    const size_t M = (size_t)m->fs.gate_memory;
+    const size_t memory = M > 0 ? 8 * M + 8 : 0;
+    const size_t anchor = m->fs.gate_ref == SLIDEO_GATE_ANCHOR ? small + 128 + 32 + (size_t)GATE_ANCHOR_MAX_UNIT * 8 + settle + memory : 0;
     if (!(m->fs.direct_t > 0.f)) return small + anchor;
     const size_t look = 2 * small + 128 + m->pages.size() * 8 + 64 + anchor;
     return m->fs.direct_scope == SLIDEO_DIRECT_VALID ? look + m->pages.size() * 8 : look;
+}
+// what a gated unit under a gate memory of M takes whatever its frame count ("Gate memory"): the ring's M small images, its centred
+// operand of ssd_rows_pad(M) = 64 rows and the unit's record
+inline size_t gate_memory_budget(const slideo_matcher* m) {
+    const size_t M = m->fs.gate_ref == SLIDEO_GATE_ANCHOR ? (size_t)m->fs.gate_memory : 0;
+    return M > 0 ? (M + 64) * ((size_t)m->cfg.small_area * 3 + 64 + 128) + 2048 : 0;
 }
 // a validated source's frames against a gate state (m->gate, the N-device group's): one size and one format family since the last
 // reset (SLIDEO_ERR_STATE)
@@ -659,7 +684,8 @@ struct GateAnchorOut {
 };
 // a unit of n frames with sw x sh small images under SLIDEO_GATE_ANCHOR: S's workspaces and, with a settle in force, the matcher's
 // previous-frame image and deferral count (everything that can fail for want of memory, in front of any write of the gate state)
-void gate_anchor_reserve(slideo_matcher* m, Slot& S, int n, int sw, int sh, bool settle);
+// memory: the gate memory's capacity in force (0: none) — + the matcher's ring and the slot's workspaces of "Gate memory"
+void gate_anchor_reserve(slideo_matcher* m, Slot& S, int n, int sw, int sh, bool settle, int memory = 0);
 // The unit's gate under SLIDEO_GATE_ANCHOR on S.st, behind the unit's small images `small` (sb bytes each): operand, pair table, then
 // behind `wait` (the previous gated unit's event) ONE launch for the n SSDs against the carried anchor m->d_gate_small and, under a
 // settle, frame 0's against the carried previous frame (none when force0), the walk, and the new state — the anchor and, under a
@@ -673,6 +699,11 @@ void gram_launch(Slot& S, const uint8_t* weights, const uint8_t* small, int64_t 
 // the previous-frame image := the anchor's (m->d_gate_small, sb bytes) and the deferral count := 0, on st: what every reset of the
 // gate state to an image does under a settle
 void gate_settle_state_from_anchor(slideo_matcher* m, size_t sb, hipStream_t st);
+// with a gate memory in force: the ring := [(the anchor's image m->d_gate_small, SLIDEO_GATE_REF_RESET)], anchor slot 0, d = 0, on st
+// (reserves the ring: every allocation in front of the first write); what every reset of the gate state to an image does
+void gate_memory_state_from_anchor(slideo_matcher* m, size_t sb, hipStream_t st);
+// the anchor's small image (sb bytes) of the ring -> out (host), behind everything queued; idle matcher, state not "none"
+void gate_memory_read_anchor(slideo_matcher* m, size_t sb, uint8_t* out);
 
 // ---- stage_sift.hip -------------------------------------------------------------------------------
 void sift_check_cfg(const slideo_sift_config* sc, int w, int h);

@@ -105,6 +105,8 @@ void gate_prime(slideo_matcher* m, FrameSrc src, hipStream_t user_stream) {
     run_small_into(m, f, 1, m->d_gate_small, st);
     // under a gate settle the frame is the anchor and the previous frame, nothing deferred
     if (m->fs.settle_similarity > 0.f) gate_settle_state_from_anchor(m, (size_t)src.plan.sw * src.plan.sh * 3, st);
+    // with a gate memory the frame is the ring's one entry ("Gate memory")
+    if (m->fs.gate_memory > 0) gate_memory_state_from_anchor(m, (size_t)src.plan.sw * src.plan.sh * 3, st);
     HIP_CHECK(hipEventRecord(S.ev_gate, st));
     m->last_gate_ev = S.ev_gate;
     HIP_CHECK(hipStreamSynchronize(st));            // (the caller's frame is free again)
@@ -152,7 +154,8 @@ void gate_unit_submit(slideo_matcher* m, Slot& S, const FrameSrc& src, int first
     const bool anchor = m->fs.gate_ref == SLIDEO_GATE_ANCHOR;
     // ... under a gate settle also the state's previous-frame image and count ("Gate settle")
     const bool settle = anchor && m->fs.settle_similarity > 0.f;
-    if (anchor) gate_anchor_reserve(m, S, n, sw, sh, settle);
+    // ... with a gate memory also the ring and the unit's table against it ("Gate memory")
+    if (anchor) gate_anchor_reserve(m, S, n, sw, sh, settle, m->fs.gate_memory);
     const DevFrames all = stage_frames(m, S, src, first, n, cs, &S.d_gstage);
     run_small_into(m, all, n, S.d_gsmall, st);
     const int64_t sb = (int64_t)sw * sh * 3;
@@ -188,7 +191,8 @@ void gate_unit_submit(slideo_matcher* m, Slot& S, const FrameSrc& src, int first
     HIP_CHECK(hipEventRecord(S.ev_gate, st));
     m->last_gate_ev = S.ev_gate;
     slideo_matcher::GateState& g = m->gate;
-    g.has = true; g.seen = true; g.w = src.w; g.h = src.h; g.yuv = src.yuv != nullptr; g.sw = sw; g.sh = sh;
+    const int64_t t0 = g.next_ord;                  // (gate_anchor_unit read it: the unit's frames have the ordinals t0 .. t0 + n - 1)
+    g.has = true; g.seen = true; g.w = src.w; g.h = src.h; g.yuv = src.yuv != nullptr; g.sw = sw; g.sh = sh; g.next_ord = t0 + n;
 
     // the look-up of all n frames (it does not depend on the flags); none when no page of the selected set shares the small size
     const bool direct = plan.cls != nullptr;
@@ -213,6 +217,7 @@ void gate_unit_submit(slideo_matcher* m, Slot& S, const FrameSrc& src, int first
     Slot::GateUnit gu;
     gu.on = true; gu.n = n; gu.k = k; gu.sw = sw; gu.sh = sh; gu.npx = npx; gu.force0 = force0; gu.settle = settle;
     gu.direct = direct; gu.direct_t = m->fs.direct_t; gu.direct_ofs = direct_ofs;
+    gu.memory = anchor && m->fs.gate_memory > 0; gu.t0 = t0;
     if (k == 0) {                                   // no frame changed (or every changed one is direct): no pipeline; the collect returns at once
         S.busy = true; S.n = 0; S.u_async = false; S.timed = false;
         S.gate = gu;
@@ -245,6 +250,13 @@ void gate_unit_collect(slideo_matcher* m, Slot& S, uint8_t* changed_out, float* 
     else S.busy = false;
     S.gate.on = false;
     const uint8_t* flag = rec + gate_rec_flag_ofs(g.n);
+    // with a gate memory: the unit's refs, behind the synchronous call's earlier units' or, a collected ticket, alone
+    const long long* ref = g.memory ? S.h_gm.as<long long>() : nullptr;
+    if (g.memory) {
+        if (!m->gate_refs_call) m->gate_refs.clear();
+        m->gate_refs.insert(m->gate_refs.end(), ref, ref + g.n);
+        m->gate_refs_valid = true;
+    }
     int r = 0;
     for (int i = 0; i < g.n; ++i) {
         unsigned long long s;
@@ -252,7 +264,12 @@ void gate_unit_collect(slideo_matcher* m, Slot& S, uint8_t* changed_out, float* 
         const float sim = (i == 0 && g.force0) ? 0.0f : changed_similarity(s, g.npx);      // video_capture.rs:92
         // (under a gate settle a frame away from its anchor may be deferred: flagged => away, and not away => not flagged)
         const bool away = sim < m->cfg.changed_similarity;
-        if (g.settle ? (flag[i] != 0 && !away) || flag[i] > 1 : away != (flag[i] != 0))
+        // (with a gate memory a frame away from its anchor may be recalled or deferred — flag 0 —, which ref tells apart: a matched
+        // frame stands behind itself, a frame that is not away behind its anchor, never behind nothing)
+        if (g.memory ? flag[i] > 1 || (flag[i] != 0 && (!away || ref[i] != g.t0 + i)) || (!away && ref[i] == SLIDEO_GATE_REF_DEFERRED) ||
+                           (flag[i] == 0 && (ref[i] >= g.t0 + i || ref[i] < SLIDEO_GATE_REF_DEFERRED)) ||
+                           (!g.settle && ref[i] == SLIDEO_GATE_REF_DEFERRED)
+                     : g.settle ? (flag[i] != 0 && !away) || flag[i] > 1 : away != (flag[i] != 0))
             fail(SLIDEO_ERR_HIP, "internal: the gate's flag of frame %d (%d, SSD %llu) is not the host expression's", i, (int)flag[i], s);
         changed_out[i] = flag[i];
         if (similarity_out) similarity_out[i] = sim;
@@ -306,6 +323,7 @@ int32_t slideo_matcher_gate_reset(slideo_matcher* m, const uint8_t* prev_small, 
     m->d_gate_small.reserve(sb);
     HIP_CHECK(hipMemcpyAsync(m->d_gate_small.p, prev_small, sb, hipMemcpyHostToDevice, m->stream));
     if (m->fs.settle_similarity > 0.f) gate_settle_state_from_anchor(m, sb, m->stream);      // (anchor = previous = that image, nothing deferred)
+    if (m->fs.gate_memory > 0) gate_memory_state_from_anchor(m, sb, m->stream);               // (the ring's one entry, SLIDEO_GATE_REF_RESET)
     HIP_CHECK(hipStreamSynchronize(m->stream));
     gate_state_reset(m);
     m->gate.has = true; m->gate.sw = small_w; m->gate.sh = small_h;
@@ -355,6 +373,7 @@ int32_t slideo_matcher_gate_last_small(slideo_matcher* m, uint8_t* out, int64_t 
     if (sb > out_capacity) fail(SLIDEO_ERR_CAPACITY, "small image needs %lld bytes", (long long)sb);
     if (out) {
         HIP_CHECK(hipSetDevice(m->device));
+        if (m->fs.gate_memory > 0) { gate_memory_read_anchor(m, (size_t)sb, out); return SLIDEO_OK; }      // (the anchor is a slot of the ring)
         for (Slot& S : m->slots) HIP_CHECK(hipStreamSynchronize(S.st));          // (a collected unit's write of the state may still be running)
         HIP_CHECK(hipMemcpyAsync(out, m->d_gate_small.p, (size_t)sb, hipMemcpyDeviceToHost, m->stream));
         HIP_CHECK(hipStreamSynchronize(m->stream));
@@ -367,6 +386,7 @@ int32_t slideo_matcher_gate_state_bytes(slideo_matcher* m, int64_t* bytes) {
     if (!m) return SLIDEO_ERR_INVALID_ARG;
     API_TRY
     if (!bytes) fail(SLIDEO_ERR_INVALID_ARG, "null bytes");
+    gate_record_memory_rule(m->fs.gate_memory);
     require_idle(m);
     *bytes = gate_record_head_of(m).bytes();
     API_CATCH(m)
@@ -376,6 +396,7 @@ int32_t slideo_matcher_gate_state_export(slideo_matcher* m, uint8_t* out, int64_
     if (!m) return SLIDEO_ERR_INVALID_ARG;
     API_TRY
     if (!bytes) fail(SLIDEO_ERR_INVALID_ARG, "null bytes");
+    gate_record_memory_rule(m->fs.gate_memory);
     require_idle(m);
     GateRecordHead h = gate_record_head_of(m);
     *bytes = h.bytes();
@@ -393,6 +414,7 @@ int32_t slideo_matcher_gate_state_export(slideo_matcher* m, uint8_t* out, int64_
 int32_t slideo_matcher_gate_state_import(slideo_matcher* m, const uint8_t* rec, int64_t bytes) {
     if (!m) return SLIDEO_ERR_INVALID_ARG;
     API_TRY
+    gate_record_memory_rule(m->fs.gate_memory);
     const GateRecordHead h = gate_record_validate(rec, bytes, m->fs.gate_ref, m->fs.settle_similarity, m->fs.settle_max_defer, m->cfg.small_area);
     require_idle(m);
     if (!h.has) { gate_state_reset(m); return SLIDEO_OK; }

@@ -21,6 +21,7 @@
 #include <filesystem>
 #include <fstream>
 #include <functional>
+#include <map>
 #include <memory>
 #include <optional>
 #include <stdexcept>
@@ -169,11 +170,37 @@ struct Handle {
     int32_t work_w = 0, work_h = 0;          // the working size the group was given (0, 0: none)
     int32_t reg_w = 0, reg_h = 0;            // the output size of the frame region the group was given (0, 0: none)
     bool gated = true;                       // tasks use the group's gated call (false: the stop-and-go mask + kept pair)
+    int32_t gate_memory = 0;                 // the gate memory's capacity the group was given (0: none)
     ~Handle() { if (g) slideo_group_destroy(g); }
     void check(int32_t rc) const {
         if (rc != SLIDEO_OK) throw std::runtime_error(std::string("slideo_amd error ") + std::to_string(rc) + ": " + slideo_group_last_error(g));
     }
 };
+// The task's side of the gate memory (include/slideo_amd.h "Gate memory") behind a gate reset to "none": the verdicts of the matched
+// ordinals it remembers (at most `capacity`, the library's own ring), the next frame's ordinal and the last frame's ref
+struct GateMemory {
+    std::map<int64_t, slideo_verdict> verdicts;
+    int64_t next = 0, prev_ref = INT64_MIN;
+    int32_t capacity = 0;
+};
+// What one gated call of n frames emits under a gate memory: (index in the call, verdict), in order.  A matched frame emits its own
+// verdict, which is remembered under its ordinal; a frame that is not matched and whose ref >= 0 differs from the ref of the frame
+// before it — a recall, or the return to the anchor behind deferred frames — emits the verdict of the frame it stands behind
+inline void gate_memory_emission(int n, const uint8_t* changed, const int64_t* refs, const slideo_verdict* verdicts, GateMemory& mem,
+                                 std::vector<int32_t>& idx, std::vector<slideo_verdict>& v) {
+    for (int i = 0; i < n; ++i) {
+        if (changed[i]) {
+            mem.verdicts[mem.next + i] = verdicts[i];
+            while ((int64_t)mem.verdicts.size() > mem.capacity) mem.verdicts.erase(mem.verdicts.begin());
+            idx.push_back(i); v.push_back(verdicts[i]);
+        } else if (refs[i] >= 0 && refs[i] != mem.prev_ref) {
+            const auto it = mem.verdicts.find(refs[i]);
+            if (it != mem.verdicts.end()) { idx.push_back(i); v.push_back(it->second); }
+        }
+        mem.prev_ref = refs[i];
+    }
+    mem.next += n;
+}
 inline void tramp(void* user, uint64_t d, uint64_t t, const char* msg) {
     static_cast<const ProgressReporter*>(user)->report(d, t, msg ? msg : "");
 }
@@ -219,6 +246,8 @@ public:
         // every shard after the first primed from the frame before its block, the last small image carried in the group
         const bool gate = h_->gated;
         if (gate) h_->check(slideo_group_gate_reset(h_->g, nullptr, 0, 0));             // the first frame of the video is always changed
+        detail::GateMemory memory;
+        memory.capacity = h_->gate_memory;
         auto emit = [&](const std::vector<int32_t>& idx, const slideo_verdict* v) {
             for (size_t k = 0; k < idx.size(); ++k) {
                 std::optional<I> img;
@@ -235,7 +264,16 @@ public:
                 h_->check(slideo_group_match_changed_frames_bgr8(h_->g, n, frames.data(), video.width, video.height, video.width * 3, (int64_t)fb,
                                                                  changed.data(), nullptr, all.data()));
                 std::vector<int32_t> idx;
-                for (int i = 0; i < n; ++i) if (changed[i]) { idx.push_back(i); v.push_back(all[i]); }
+                if (memory.capacity > 0) {
+                    // a recalled frame has changed == 0 but shows another page than the frame before it: the verdict of the frame
+                    // it stands behind is emitted at its time (slideo_amd.h "Gate memory")
+                    std::vector<int64_t> refs((size_t)n);
+                    int64_t nrefs = 0;
+                    h_->check(slideo_group_last_gate_refs(h_->g, refs.data(), n, &nrefs));
+                    if (nrefs != n) throw std::runtime_error("slideo_group_last_gate_refs: the refs are not the call's");
+                    detail::gate_memory_emission(n, changed.data(), refs.data(), all.data(), memory, idx, v);
+                } else
+                    for (int i = 0; i < n; ++i) if (changed[i]) { idx.push_back(i); v.push_back(all[i]); }
                 emit(idx, v.data());
                 for (int i = 0; i < n; ++i) rep_.report(++progress, frames_to_process, "Processing frames of '" + name + "'...");   // mo/lib.rs:192-203
                 meta.clear(); frames.clear();
@@ -385,6 +423,10 @@ public:
         settle_similarity_ = settle_similarity; settle_max_defer_ = max_defer;
         return *this;
     }
+    // The gate memory (slideo_group_set_gate_memory, include/slideo_amd.h "Gate memory"), under SLIDEO_GATE_ANCHOR only, applied after
+    // the gate reference and the settle: the last `capacity` (1 .. 64) matched frames are remembered and a frame that returns to one
+    // of them is recalled, not matched again; the task emits the remembered verdict at that frame's time.  One device only.  0: off
+    HipImageVideoMatcher& with_gate_memory(int32_t capacity) { gate_memory_ = capacity; return *this; }
     // The group gate order (slideo_group_set_gate_order, include/slideo_amd.h "Group gate order"), applied before the gate reference
     // and the settle: SLIDEO_GROUP_GATE_HALO (default: a later device's shard is primed from one frame) or SLIDEO_GROUP_GATE_CHAIN
     // (every shard receives the whole gate state of the shard before it: SLIDEO_GATE_ANCHOR and a settle on any number of devices)
@@ -403,6 +445,7 @@ public:
         if (gate_order_ != SLIDEO_GROUP_GATE_HALO) h->check(slideo_group_set_gate_order(h->g, gate_order_));
         if (gate_ref_ != SLIDEO_GATE_PREVIOUS) h->check(slideo_group_set_gate_reference(h->g, gate_ref_));
         if (settle_similarity_ != 0.f) h->check(slideo_group_set_gate_settle(h->g, settle_similarity_, settle_max_defer_));
+        if (gate_memory_ != 0) { h->check(slideo_group_set_gate_memory(h->g, gate_memory_)); h->gate_memory = gate_memory_; }
         if (sift_on_) {                                                                             // the north-star's SIFT + L2 front end
             slideo_sift_config sc;
             slideo_sift_config_default(&sc);
@@ -451,6 +494,7 @@ private:
     uint32_t gate_order_ = SLIDEO_GROUP_GATE_HALO;
     float settle_similarity_ = 0.f;
     int32_t settle_max_defer_ = 0;
+    int32_t gate_memory_ = 0;
     slideo_config cfg_;
     ImageLoader loader_;
 };

@@ -188,6 +188,8 @@ class HipVideoMatcherTask:
         gate = _gated_matcher(m)
         if gate is not None:
             gate.gate_reset(None)                                # the first frame of the video is always changed
+        capacity = gate.gate_memory() if gate is not None and hasattr(gate, "gate_memory") else 0
+        memory = new_gate_memory(capacity) if capacity > 0 else None
 
         def emit(idx, verdicts):
             for j, v in zip(idx, verdicts):
@@ -205,8 +207,14 @@ class HipVideoMatcherTask:
                     changed, _, verdicts = gate.match_changed_frames_yuv420(stack, video.width, video.height, yuv)
                 else:
                     changed, _, verdicts = gate.match_changed_frames(stack)
-                idx = np.nonzero(changed)[0]
-                emit(idx, verdicts[idx])
+                if memory is not None:
+                    # under a gate memory a recalled frame has changed == 0 but shows another page than the frame before it: the
+                    # verdict of the frame it stands behind is emitted at its time
+                    hits = gate_memory_emission(changed, gate.last_gate_refs(), verdicts, memory)
+                    emit([j for j, _ in hits], [v for _, v in hits])
+                else:
+                    idx = np.nonzero(changed)[0]
+                    emit(idx, verdicts[idx])
                 for _ in pend_frames:
                     report_progress()
                 pend_frames.clear(); pend_meta.clear()
@@ -236,6 +244,33 @@ class HipVideoMatcherTask:
         flush()
         self._rep.report(frames_to_process, frames_to_process, "Finished!")           # lib.rs:223-227
         return dedup_timeline(results)
+
+
+def new_gate_memory(capacity):
+    """The task's side of the gate memory (include/slideo_amd.h "Gate memory") behind a gate reset to "none": the verdicts of the
+    matched ordinals it remembers (at most `capacity`, the library's own ring), the next frame's ordinal and the last frame's ref."""
+    return {"verdicts": {}, "next": 0, "prev_ref": None, "capacity": int(capacity)}
+
+
+def gate_memory_emission(changed, refs, verdicts, memory):
+    """What one gated call emits under a gate memory -> [(index in the call, verdict)], in order.  A matched frame (changed) emits
+    its own verdict, which is remembered under its ordinal (the `capacity` most recent are kept).  A frame that is not matched and
+    whose ref >= 0 differs from the ref of the frame before it — a recall, or the return to the anchor behind deferred frames —
+    emits the verdict remembered for the frame it stands behind.  `memory` (new_gate_memory) carries on from call to call."""
+    out = []
+    known = memory["verdicts"]
+    for i in range(len(changed)):
+        ref = int(refs[i])
+        if changed[i]:
+            known[memory["next"] + i] = verdicts[i]
+            for k in sorted(known)[:-memory["capacity"]]:
+                del known[k]
+            out.append((i, verdicts[i]))
+        elif ref >= 0 and ref != memory["prev_ref"] and ref in known:
+            out.append((i, known[ref]))
+        memory["prev_ref"] = ref
+    memory["next"] += len(changed)
+    return out
 
 
 def _gated_matcher(m):
@@ -350,7 +385,7 @@ class HipImageVideoMatcher:
 
     def __init__(self, cfg=None, device=None, sift=None, devices=None, working_size=None, frame_mask=None, frame_mask_scope=None,
                  direct_similarity=None, direct_scope=None, frame_region=None, yuv_description=None, gate_reference=None, gate_settle=None,
-                 group_gate_order=None, yuv_sampling=None):
+                 group_gate_order=None, yuv_sampling=None, gate_memory=None):
         """devices: HIP ordinals, one matcher each behind one slideo_group (the reference fans out over the whole machine, the
         global rayon pool of lib.rs:45,174); None = every gfx950 device of the node; `device` = d is short for devices = [d].
         sift = (slideo_sift_config, ratio): the north-star's SIFT + L2 front end instead of the reference's ORB + Hamming
@@ -390,6 +425,10 @@ class HipImageVideoMatcher:
         from the last matched frame is matched once it is within `similarity` of the frame before it — the picture stands
         still — or after max_defer deferred frames, so a cross-fade costs one verdict, not one for every second frame of it; a
         deferred frame is reported as unchanged; None = off.
+        gate_memory = M in 1 .. 64 (slideo_group_set_gate_memory), under gate_reference "anchor" only, applied after gate_reference
+        and gate_settle: the last M matched frames are remembered, and a frame that returns to one of them — a cut back to the
+        slide, a flip back — is recalled instead of matched again; the task then emits the remembered verdict at that frame's time
+        (gate_memory_emission).  One device only; None or 0 = off.
         group_gate_order = "halo" or "chain" (slideo_group_set_gate_order), applied before gate_reference and gate_settle: with
         "chain" every device's shard of a gated call receives the whole gate state of the shard before it, so "anchor" and a
         settle run on any number of devices and return what one device returns; None = "halo", a shard primed from one frame."""
@@ -404,6 +443,7 @@ class HipImageVideoMatcher:
         self._yuv_sampling = yuv_sampling
         self._gate_reference = gate_reference
         self._gate_settle = tuple(gate_settle) if gate_settle is not None else None
+        self._gate_memory = gate_memory
         self._group_gate_order = group_gate_order
         self._devices = [device] if device is not None else devices
 
@@ -417,6 +457,8 @@ class HipImageVideoMatcher:
             m.set_gate_reference(self._gate_reference)
         if self._gate_settle is not None:
             m.set_gate_settle(*self._gate_settle)
+        if self._gate_memory is not None:
+            m.set_gate_memory(self._gate_memory)
         if self._sift is not None:
             m.use_sift(*self._sift)
         if self._working_size is not None:
