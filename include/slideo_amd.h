@@ -553,6 +553,18 @@ typedef struct slideo_candidate {
 int32_t     slideo_last_frame_candidates(const slideo_matcher* m, int32_t frame_in_batch,
                                          slideo_candidate* out, int32_t capacity, int32_t* n_out);
 
+/* slideo_match_frames_bgr8 from the frames' features on (the frame-side counterpart of slideo_matcher_add_page_features, for the
+ * tests of the verify stage): frame f's keypoints and 32-byte descriptors are rows [sum kp_counts[0..f), + kp_counts[f]) of kp /
+ * desc32 and take the place of ORB's output; the search, the vote, RANSAC, the rating, the re-projection (which reads the n
+ * equally sized host frames) and the verdict run as in a frame call.  Synchronous, one unit, the exact-size search; verdicts as
+ * slideo_match_frames_bgr8 returns them, slideo_last_frame_candidates works after it.  ORB mode with the exact Hamming search
+ * (matcher 0) only, frames as given (no working size, no frame region): otherwise SLIDEO_ERR_INVALID_ARG; SLIDEO_ERR_STATE before
+ * slideo_matcher_finalize_pages or with a unit in flight.  At most 4096 frames. */
+int32_t     slideo_match_frames_features_bgr8(slideo_matcher* m, int32_t n_frames, const uint8_t* frames, int32_t width,
+                                              int32_t height, int32_t stride_bytes, int64_t frame_stride_bytes,
+                                              const int32_t* kp_counts, const slideo_keypoint* kp, const uint8_t* desc32,
+                                              slideo_verdict* verdicts_out);
+
 /* ---- N-device group ----------------------------------------------------------------------------------------------
  * One matcher per device behind ONE handle: what the reference's fan-out over every core of the machine becomes on a node
  * with several GPUs (rayon: one task per changed frame, mo/lib.rs:174,213; pages par_iter, mo/lib.rs:45-47).  The page

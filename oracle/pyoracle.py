@@ -448,6 +448,31 @@ class PageDB:
         assert rc == 0, rc
         return v[0], cands[: n.value].copy()
 
+    def add_page_features(self, width, height, kp, desc, small):
+        """A page analysed elsewhere (the product's Matcher.add_page_features): keypoints, 32-byte descriptors, small image."""
+        kp = np.ascontiguousarray(kp, KEYPOINT_DTYPE)
+        desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        small = _img3(small)
+        assert len(kp) == len(desc)
+        rc = lib().so_pagedb_add_page_features(C.c_void_p(self._h), int(width), int(height), _p(kp), _p(desc), len(kp),
+                                               _p(small), small.shape[1], small.shape[0])
+        assert rc == 0, rc
+
+    def match_features_trace(self, frame, kp, desc):
+        """match_frame_trace from the frame's features on: kp / desc stand in for ORB's output, `frame` is re-projected."""
+        frame = _img3(frame)
+        h, w, _ = frame.shape
+        kp = np.ascontiguousarray(kp, KEYPOINT_DTYPE)
+        desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        assert len(kp) == len(desc)
+        v = np.zeros(1, VERDICT_DTYPE)
+        cands = np.zeros(64, CANDIDATE_DTYPE)
+        n = C.c_int32()
+        rc = lib().so_match_features_trace(C.c_void_p(self._h), _p(frame), w, h, w * 3, _p(kp), _p(desc), len(kp), _p(v),
+                                           _p(cands), 64, C.byref(n))
+        assert rc == 0, rc
+        return v[0], cands[: n.value].copy()
+
     def __del__(self):
         try:
             lib().so_pagedb_destroy(C.c_void_p(self._h))

@@ -1701,6 +1701,11 @@ namespace {
 
 struct Vote { int q, t_local; };
 
+static void match_features(const so_pagedb& db, const OrbResult& fr, const uint8_t* bgr, int w, int h, int stride,
+                           slideo_verdict& out, std::vector<slideo_candidate>* trace);
+static void verify_votes(const so_pagedb& db, const OrbResult& fr, const std::vector<std::vector<Vote>>& votes, const uint8_t* bgr,
+                         int w, int h, int stride, slideo_verdict& out, std::vector<slideo_candidate>* trace);
+
 static void match_frame(const so_pagedb& db, const uint8_t* bgr, int w, int h, int stride,
                         slideo_verdict& out, std::vector<slideo_candidate>* trace) {
     const slideo_config& c = db.cfg;
@@ -1744,8 +1749,22 @@ static void match_frame(const so_pagedb& db, const uint8_t* bgr, int w, int h, i
                 }
             }
         }
-    } else {
+        verify_votes(db, fr, votes, bgr, w, h, stride, out, trace);
+        return;
+    }
     orb_detect_describe(bgr, w, h, stride, c, fr);           // mo/lib.rs:264-265
+    match_features(db, fr, bgr, w, h, stride, out, trace);
+}
+
+// The ORB / Hamming path from a frame's features on: search, vote, then the common tail.  `fr`: ORB's output or rows made elsewhere
+// (so_match_features_trace); bgr: the frame the survivors are re-projected from.
+static void match_features(const so_pagedb& db, const OrbResult& fr, const uint8_t* bgr, int w, int h, int stride,
+                           slideo_verdict& out, std::vector<slideo_candidate>* trace) {
+    const slideo_config& c = db.cfg;
+    out.page_idx = -1; out.similarity = 0; out.inliers = 0; out.n_keypoints = 0;
+    if (trace) trace->clear();
+    int P = (int)db.pages.size();
+    std::vector<std::vector<Vote>> votes(P);
     int K = (int)fr.kp.size(), M = (int)db.train_page.size(), k = c.knn_k;
     out.n_keypoints = K;
     if (K == 0) return;
@@ -1779,7 +1798,14 @@ static void match_frame(const so_pagedb& db, const uint8_t* bgr, int w, int h, i
             }
         }
     }
-    }   // ORB / Hamming front end
+    verify_votes(db, fr, votes, bgr, w, h, stride, out, trace);
+}
+
+// Everything after the vote (either front end): candidate ranking, estimator, rating, re-projection, verdict.
+static void verify_votes(const so_pagedb& db, const OrbResult& fr, const std::vector<std::vector<Vote>>& votes, const uint8_t* bgr,
+                         int w, int h, int stride, slideo_verdict& out, std::vector<slideo_candidate>* trace) {
+    const slideo_config& c = db.cfg;
+    const int P = (int)db.pages.size();
     // candidate ranking, mo/lib.rs:284-295: stable by count desc over ascending page index
     std::vector<int> cand;
     for (int p = 0; p < P; ++p) if (!votes[p].empty()) cand.push_back(p);
@@ -2205,6 +2231,39 @@ int so_match_frame_trace(const so_pagedb* db, const uint8_t* bgr, int w, int h, 
     if (!db->finalized || db->train_page.empty()) return 6;
     std::vector<slideo_candidate> tr;
     match_frame(*db, bgr, w, h, stride, *out, &tr);
+    *n_cands = (int32_t)tr.size();
+    int m = std::min((int)tr.size(), cap);
+    std::memcpy(cands, tr.data(), (size_t)m * sizeof(slideo_candidate));
+    return 0;
+}
+
+// A page analysed elsewhere: its keypoints, 32-byte descriptors and small image as given (the product's
+// slideo_matcher_add_page_features); the small image must have the to_small_image size of a w x h page.
+int so_pagedb_add_page_features(so_pagedb* db, int w, int h, const slideo_keypoint* kp, const uint8_t* desc, int n,
+                                const uint8_t* small, int sw, int sh) {
+    if (db->finalized) return 4;
+    if (db->sift || n < 0 || (n > 0 && (!kp || !desc)) || !small) return 1;
+    int ew, eh; small_size(w, h, db->cfg.small_area, ew, eh);
+    if (sw != ew || sh != eh) return 1;
+    Page p; p.w = w; p.h = h; p.sw = sw; p.sh = sh;
+    p.orb.kp.assign(kp, kp + n);
+    p.orb.desc.assign(desc, desc + (size_t)n * 32);
+    p.small.assign(small, small + (size_t)sw * sh * 3);
+    db->pages.push_back(std::move(p));
+    return 0;
+}
+
+// so_match_frame_trace from the frame's features on: kp / desc (n rows) stand in for ORB's output, bgr is the frame the
+// survivors are re-projected from (match_features)
+int so_match_features_trace(const so_pagedb* db, const uint8_t* bgr, int w, int h, int stride, const slideo_keypoint* kp,
+                            const uint8_t* desc, int n, slideo_verdict* out, slideo_candidate* cands, int cap, int32_t* n_cands) {
+    if (!db->finalized || db->train_page.empty()) return 6;
+    if (db->sift || n < 0 || (n > 0 && (!kp || !desc))) return 1;
+    OrbResult fr;
+    fr.kp.assign(kp, kp + n);
+    fr.desc.assign(desc, desc + (size_t)n * 32);
+    std::vector<slideo_candidate> tr;
+    match_features(*db, fr, bgr, w, h, stride, *out, &tr);
     *n_cands = (int32_t)tr.size();
     int m = std::min((int)tr.size(), cap);
     std::memcpy(cands, tr.data(), (size_t)m * sizeof(slideo_candidate));

@@ -259,6 +259,7 @@ EXPORTS = [
     "slideo_group_gate_chain_waited",
     "slideo_matcher_set_gate_memory", "slideo_matcher_gate_memory", "slideo_group_set_gate_memory", "slideo_matcher_last_gate_refs",
     "slideo_group_last_gate_refs", "slideo_matcher_gate_memory_entries", "slideo_matcher_gate_memory_small", "slideo_gate_recall_walk",
+    "slideo_match_frames_features_bgr8",
 ]
 
 # frame mask scope (include/slideo_amd.h "Frame mask scope")
@@ -440,6 +441,9 @@ def lib():
             L.slideo_matcher_gate_memory_small.argtypes = [vp, i32, vp, i64, vp, vp]
             L.slideo_gate_recall_walk.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, u64, i32, i32, i64, i64, i32, i32, i32, i64,
                                                   vp, vp, vp, vp, vp, vp, vp, vp]
+        if hasattr(L, "slideo_match_frames_features_bgr8"):
+            vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
+            L.slideo_match_frames_features_bgr8.argtypes = [vp, i32, vp, i32, i32, i32, i64, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -1435,6 +1439,24 @@ class Matcher(_FrameCalls):
         a = C.c_int32(); b = C.c_int32()
         self._check(lib().slideo_small_image_bgr8(self._h, _p(bgr), w, h, w * 3, _p(out), C.c_int64(out.size),
                                                   C.byref(a), C.byref(b)))
+        return out
+
+    def match_features(self, frames, kps, descs):
+        """slideo_match_frames_features_bgr8 (debug tap): match_frames from the frames' features on.  frames: uint8 [n, h, w, 3];
+        kps / descs: per frame a KEYPOINT_DTYPE array and its uint8 [k, 32] descriptors, in place of ORB's output -> verdict records
+        (last_candidates works after it)."""
+        frames = np.ascontiguousarray(frames, np.uint8)
+        n, h, w, c = frames.shape
+        assert c == 3 and len(kps) == n and len(descs) == n
+        kps = [np.ascontiguousarray(k, KEYPOINT_DTYPE).reshape(-1) for k in kps]
+        descs = [np.ascontiguousarray(d, np.uint8).reshape(-1, 32) for d in descs]
+        assert all(len(k) == len(d) for k, d in zip(kps, descs))
+        counts = np.array([len(k) for k in kps], np.int32)
+        kp = np.ascontiguousarray(np.concatenate(kps)) if n else np.zeros(0, KEYPOINT_DTYPE)
+        desc = np.ascontiguousarray(np.concatenate(descs)) if n else np.zeros((0, 32), np.uint8)
+        out = np.zeros(n, VERDICT_DTYPE)
+        self._check(lib().slideo_match_frames_features_bgr8(self._h, n, _p(frames), w, h, w * 3, C.c_int64(w * h * 3), _p(counts),
+                                                            _p(kp), _p(desc), _p(out)))
         return out
 
 
