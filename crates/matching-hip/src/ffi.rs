@@ -27,6 +27,15 @@ pub const SLIDEO_YUV_SAMPLING_420: i32 = 0;
 pub const SLIDEO_YUV_SAMPLING_422: i32 = 1;
 pub const SLIDEO_YUV_SAMPLING_444: i32 = 2;
 pub const SLIDEO_YUV_SAMPLING_422_PACKED: i32 = 3;
+pub const SLIDEO_PIXEL_BGR8: i32 = 0;
+pub const SLIDEO_PIXEL_RGB8: i32 = 1;
+pub const SLIDEO_PIXEL_BGRA8: i32 = 2;
+pub const SLIDEO_PIXEL_RGBA8: i32 = 3;
+pub const SLIDEO_PIXEL_ARGB8: i32 = 4;
+pub const SLIDEO_PIXEL_ABGR8: i32 = 5;
+pub const SLIDEO_PIXEL_PLANAR_RGB8: i32 = 6;
+pub const SLIDEO_PIXEL_PLANAR_BGR8: i32 = 7;
+pub const SLIDEO_PIXEL_PLANAR_GBR8: i32 = 8;
 
 /// slideo_ocv_variants: which restatement of each OpenCV primitive runs.  slideo_config_default fills it; the
 /// application never touches it.
@@ -552,6 +561,14 @@ extern "C" {
     pub fn slideo_matcher_yuv_sampling(m: *const slideo_matcher, sampling: *mut i32) -> i32;
     pub fn slideo_group_set_yuv_sampling(g: *mut slideo_group, sampling: i32) -> i32;
     pub fn slideo_yuv_layout_packed(format: i32, width: i32, height: i32, bytes_per_sample: i32, out: *mut slideo_yuv420_layout) -> i32;
+    // frame pixel format (include/slideo_amd.h "Frame pixel format"): SLIDEO_PIXEL_*; how every *_bgr8 frame call reads its frames
+    pub fn slideo_matcher_set_pixel_format(m: *mut slideo_matcher, format: i32) -> i32;
+    pub fn slideo_matcher_pixel_format(m: *const slideo_matcher, format: *mut i32) -> i32;
+    pub fn slideo_group_set_pixel_format(g: *mut slideo_group, format: i32) -> i32;
+    pub fn slideo_pixel_format_info(format: i32, bytes_per_pixel: *mut i32, planes: *mut i32) -> i32;
+    pub fn slideo_pixels_to_bgr8(
+        m: *mut slideo_matcher, frame: *const u8, width: i32, height: i32, stride_bytes: i32, bgr_out: *mut u8, out_capacity: i64,
+    ) -> i32;
     // frame region (include/slideo_amd.h "Frame region"): frames stand for a rectified quadrilateral of themselves
     pub fn slideo_matcher_set_frame_region(
         m: *mut slideo_matcher,

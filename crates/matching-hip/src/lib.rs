@@ -99,6 +99,11 @@ pub struct HipImageVideoMatcher {
     /// _444 (screen recorders) or _422_PACKED (YUY2 / UYVY of capture cards; 8-bit).  Every call that takes a
     /// slideo_yuv420_layout reads its frames under it.  The reference knows BGR only.
     pub yuv_sampling: i32,
+    /// How the frames of the BGR door are read (slideo_group_set_pixel_format): ffi::SLIDEO_PIXEL_BGR8 (default), _RGB8, the
+    /// four-byte _BGRA8 / _RGBA8 / _ARGB8 / _ABGR8 of screen-capture APIs, or the planar _PLANAR_RGB8 / _PLANAR_BGR8 /
+    /// _PLANAR_GBR8.  The frame source then hands out frames in that format; pages stay BGR.  The reference only ever sees
+    /// OpenCV's BGR.
+    pub pixel_format: i32,
     /// Which frame a gated frame is compared with (slideo_group_set_gate_reference): ffi::SLIDEO_GATE_PREVIOUS (default: the
     /// frame before, the reference's MarkSimilarIter) or ffi::SLIDEO_GATE_ANCHOR (the last frame that was flagged: a change
     /// spread over many frames is still flagged when every decoded frame is fed).  With several devices it needs
@@ -200,6 +205,7 @@ impl Default for HipImageVideoMatcher {
             frame_region: None,
             yuv_description: (ffi::SLIDEO_YUV_MATRIX_BT601, ffi::SLIDEO_YUV_RANGE_LIMITED, ffi::SLIDEO_YUV_DEPTH_8),
             yuv_sampling: ffi::SLIDEO_YUV_SAMPLING_420,
+            pixel_format: ffi::SLIDEO_PIXEL_BGR8,
             gate_reference: ffi::SLIDEO_GATE_PREVIOUS,
             gate_settle: (0.0, 0),
             group_gate_order: ffi::SLIDEO_GROUP_GATE_HALO,
@@ -255,6 +261,9 @@ impl<'i> ImageVideoMatcher<'i> for HipImageVideoMatcher {
             }
             if self.yuv_sampling != ffi::SLIDEO_YUV_SAMPLING_420 {
                 check(h, ffi::slideo_group_set_yuv_sampling(h, self.yuv_sampling));
+            }
+            if self.pixel_format != ffi::SLIDEO_PIXEL_BGR8 {
+                check(h, ffi::slideo_group_set_pixel_format(h, self.pixel_format));
             }
             if self.frame_mask_scope != ffi::SLIDEO_MASK_DETECT {
                 check(h, ffi::slideo_group_set_frame_mask_scope(h, self.frame_mask_scope));

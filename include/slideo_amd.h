@@ -808,6 +808,61 @@ int32_t     slideo_group_set_yuv_sampling(slideo_group* g, int32_t sampling);
  * BYTES.  A packed format with bytes_per_sample 2, and an odd width of a 4:2:2 format, are SLIDEO_ERR_UNSUPPORTED. */
 int32_t     slideo_yuv_layout_packed(int32_t format, int32_t width, int32_t height, int32_t bytes_per_sample, slideo_yuv420_layout* out);
 
+/* ---- Frame pixel format (extension: RGB, BGRA / RGBA / ARGB / ABGR and planar RGB frames through the *_bgr8 frame calls) --------------
+ * B, G, R in three bytes is OpenCV's order.  Screen-capture APIs hand out four-byte pixels (PipeWire, X11 and DXGI: BGRx; macOS and
+ * browsers: RGBA), GPU decoders with a colour stage and PNG / JPEG decoders give RGB(A), every PyTorch pipeline gives uint8
+ * [N, 3, H, W] planar RGB, and FFmpeg's lossless screen codecs decode to gbrp.  A matcher carries a PIXEL FORMAT, a frame setting
+ * like the YUV sampling; the default is SLIDEO_PIXEL_BGR8, under which every call launches and copies exactly what it did before
+ * the format existed, and device frames are still read in place.  Under another format EVERY call that takes BGR frames with a
+ * stride_bytes and a frame_stride_bytes reads its frames under it: slideo_match_frames_bgr8[_dev], slideo_match_frames_submit_dev,
+ * slideo_changed_mask_bgr8 (slideo_match_kept_frames then matches the kept, converted frames), slideo_match_changed_frames_bgr8[_dev],
+ * slideo_match_changed_frames_submit_dev, slideo_matcher_observe_frames_bgr8[_dev], slideo_matcher_gate_reset_from_frame_bgr8[_dev],
+ * slideo_match_frames_features_bgr8 and the group's forms.  THE NAMES KEEP THEIR `bgr8`, as the YUV calls kept their `420`: they are
+ * the BGR door, whatever the format.  Pages (slideo_matcher_add_pages_bgr8, slideo_group_add_pages_bgr8) and the single-image taps
+ * (slideo_orb_bgr8, slideo_small_image_bgr8, slideo_reduce_bgr8, slideo_rectify_bgr8, ...) stay BGR: the format is a FRAME setting.
+ * This closes the first item of "YUV sampling"'s out-of-scope list (4-byte BGRA / RGBA input).
+ * Layout rules, each SLIDEO_ERR_INVALID_ARG with the rule and the format named:
+ *   packed formats (bpp 3 or 4 bytes per pixel): row y starts at y * stride_bytes; stride_bytes >= bpp * width; a frame spans
+ *     height * stride_bytes; frame_stride_bytes >= height * stride_bytes, the rule as it stood.
+ *   planar formats: stride_bytes is the row stride of EVERY plane; stride_bytes >= width; plane p starts at
+ *     p * height * stride_bytes; a frame spans 3 * height * stride_bytes, which frame_stride_bytes must cover.
+ *   A single frame (the gate-reset calls, the tap) has no frame stride to check.  Under the default format the rules and the
+ *   message are what they were ("bad image geometry ...").
+ * Semantics: a frame stands for the BGR image whose pixel (x, y) has the frame's B, G and R bytes of that pixel.  The fourth byte
+ * (x below: alpha or padding) is ignored: no un-premultiplying, no blending.  Contract: a call under a format returns, bit for
+ * bit, what the same call under the default returns on that image — verdicts, candidate traces, changed flags, similarities,
+ * small images, gate state, gate refs, activity and content counts.  Working size, frame region, frame mask and scopes, the
+ * direct look-up, page sets and SIFT mode see the converted image.  *_yuv420 calls never look at the pixel format, and *_bgr8
+ * calls never look at the YUV description or sampling; the gate's "one format family" rule still tells the two doors apart only.
+ * A host frame is uploaded at its span (4 bytes per pixel for the four-byte formats) and converted on the device; a device frame
+ * is read from the caller's memory by the conversion, which costs the in-place read the default keeps.
+ * DEPARTURE: the reference only ever sees OpenCV's BGR.
+ * Out of scope: 16-bit forms (BGR48, BGRA64, gbrp10le); GRAY8; premultiplied alpha; pages in other formats; a channel order baked
+ * into the ORB or re-projection kernels; fusing the grey write into the conversion.
+ * Kernel: csrc/pixel_format.hip.h pixels_to_bgr_kernel<FORM>, launched iff the format is not SLIDEO_PIXEL_BGR8. */
+#define SLIDEO_PIXEL_BGR8         0   /* default: B G R, 3 bytes per pixel             */
+#define SLIDEO_PIXEL_RGB8         1   /* R G B, 3 bytes per pixel                      */
+#define SLIDEO_PIXEL_BGRA8        2   /* B G R x  (x: alpha or padding, ignored)       */
+#define SLIDEO_PIXEL_RGBA8        3   /* R G B x                                       */
+#define SLIDEO_PIXEL_ARGB8        4   /* x R G B                                       */
+#define SLIDEO_PIXEL_ABGR8        5   /* x B G R                                       */
+#define SLIDEO_PIXEL_PLANAR_RGB8  6   /* three planes R, G, B  (torch [3, H, W])       */
+#define SLIDEO_PIXEL_PLANAR_BGR8  7   /* three planes B, G, R                          */
+#define SLIDEO_PIXEL_PLANAR_GBR8  8   /* three planes G, B, R  (FFmpeg gbrp)           */
+/* As slideo_matcher_set_yuv_sampling: before or after finalize; SLIDEO_ERR_STATE with units in flight; a value outside the
+ * enumeration is SLIDEO_ERR_INVALID_ARG and the state before stays; ends the kept frames and resets the gate state to "none". */
+int32_t     slideo_matcher_set_pixel_format(slideo_matcher* m, int32_t format);
+int32_t     slideo_matcher_pixel_format(const slideo_matcher* m, int32_t* format);
+/* Validates every member before changing any; resets the group's gate state. */
+int32_t     slideo_group_set_pixel_format(slideo_group* g, int32_t format);
+/* Pure: the bytes per pixel of a row (3, 4; 1: a plane's) and the planes (1, 3) of `format`; either output may be null.  A value
+ * outside the enumeration is SLIDEO_ERR_INVALID_ARG. */
+int32_t     slideo_pixel_format_info(int32_t format, int32_t* bytes_per_pixel, int32_t* planes);
+/* Tap: ONE host frame under the matcher's pixel format -> the BGR image it stands for, width * height * 3 bytes at stride
+ * 3 * width (SLIDEO_ERR_CAPACITY when out_capacity is smaller).  Under the default format a row-by-row copy. */
+int32_t     slideo_pixels_to_bgr8(slideo_matcher* m, const uint8_t* frame, int32_t width, int32_t height, int32_t stride_bytes,
+                                  uint8_t* bgr_out, int64_t out_capacity);
+
 /* ---- Working size (extension: the reference analyses every frame at the size it arrives in) ---------------------------------
  * A matcher carries a working size (max_w, max_h); (0, 0) = none, the default.  While one is set, a frame of w x h with
  * w <= max_w and h <= max_h is untouched; any other frame STANDS FOR the image cv::resize(frame, Size(dw, dh), 0, 0, INTER_AREA)

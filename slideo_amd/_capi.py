@@ -118,6 +118,30 @@ YUV_PACKED_OFFSETS = {"yuy2": (1, 3), "yvyu": (3, 1), "uyvy": (0, 2), "vyuy": (2
 YUV_SAMPLINGS = {"420": 0, "422": 1, "444": 2, "422_packed": 3}
 
 
+# "Frame pixel format": the formats every *_bgr8 frame call can read its frames under (SLIDEO_PIXEL_*)
+PIXEL_FORMATS = {"bgr": 0, "rgb": 1, "bgra": 2, "rgba": 3, "argb": 4, "abgr": 5, "planar_rgb": 6, "planar_bgr": 7, "planar_gbr": 8}
+
+
+def pixel_format_value(fmt):
+    """The SLIDEO_PIXEL_* value of a name of PIXEL_FORMATS (or the value itself)."""
+    if isinstance(fmt, str):
+        if fmt.lower() not in PIXEL_FORMATS:
+            raise SlideoError(1, "pixel format: unknown %r (one of %s)" % (fmt, sorted(PIXEL_FORMATS)))
+        return PIXEL_FORMATS[fmt.lower()]
+    return int(fmt)
+
+
+def pixel_format_info(fmt):
+    """slideo_pixel_format_info: (bytes per pixel of a row: 3, 4, or 1 for a plane's; planes: 1 or 3)."""
+    bpp, planes = C.c_int32(), C.c_int32()
+    if not hasattr(lib(), "slideo_pixel_format_info") and pixel_format_value(fmt) == 0:
+        return 3, 1                                               # (SLIDEO_LIB_PATH may name an older build: tools/ab_libs.sh)
+    rc = lib().slideo_pixel_format_info(pixel_format_value(fmt), C.byref(bpp), C.byref(planes))
+    if rc != OK:
+        raise SlideoError(rc, "slideo_pixel_format_info(%r)" % (fmt,))
+    return bpp.value, planes.value
+
+
 def yuv_format_sampling(fmt):
     """The sampling name a format is read under."""
     if fmt in YUV420_FORMATS:
@@ -246,6 +270,8 @@ EXPORTS = [
     "slideo_matcher_set_yuv_description", "slideo_matcher_yuv_description", "slideo_group_set_yuv_description", "slideo_yuv_coefficients",
     "slideo_yuv420_layout_packed16",
     "slideo_matcher_set_yuv_sampling", "slideo_matcher_yuv_sampling", "slideo_group_set_yuv_sampling", "slideo_yuv_layout_packed",
+    "slideo_matcher_set_pixel_format", "slideo_matcher_pixel_format", "slideo_group_set_pixel_format", "slideo_pixel_format_info",
+    "slideo_pixels_to_bgr8",
     "slideo_matcher_activity_begin", "slideo_matcher_activity_end", "slideo_matcher_observe_frames_bgr8", "slideo_matcher_observe_frames_yuv420",
     "slideo_matcher_observe_frames_bgr8_dev", "slideo_matcher_observe_frames_yuv420_dev", "slideo_matcher_activity_info",
     "slideo_matcher_activity_counts", "slideo_matcher_activity_mask",
@@ -389,6 +415,12 @@ def lib():
             L.slideo_matcher_yuv_sampling.argtypes = [vp, vp]
             L.slideo_group_set_yuv_sampling.argtypes = [vp, i32]
             L.slideo_yuv_layout_packed.argtypes = [i32, i32, i32, i32, vp]
+        if hasattr(L, "slideo_matcher_set_pixel_format"):
+            L.slideo_matcher_set_pixel_format.argtypes = [vp, i32]
+            L.slideo_matcher_pixel_format.argtypes = [vp, vp]
+            L.slideo_group_set_pixel_format.argtypes = [vp, i32]
+            L.slideo_pixel_format_info.argtypes = [i32, vp, vp]
+            L.slideo_pixels_to_bgr8.argtypes = [vp, vp, i32, i32, i32, vp, C.c_int64]
         if hasattr(L, "slideo_matcher_activity_begin"):
             vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
             L.slideo_matcher_activity_begin.argtypes = [vp, i32]
@@ -478,13 +510,34 @@ class _FrameCalls:
     def _call(self, name, *args):
         self._check(getattr(lib(), self._PREFIX + name)(self._h, *args))
 
-    def match_frames(self, frames):
-        """frames: uint8 [n, h, w, 3] in host memory -> verdict records."""
+    def _pix_frames(self, frames, what="frames"):
+        """Host frames in the array shape of the pixel format in force ("Frame pixel format") — [n, h, w, 3], [n, h, w, 4] or
+        [n, 3, h, w] — -> (the contiguous array, n, w, h, stride_bytes, frame_stride_bytes)."""
         frames = np.ascontiguousarray(frames, np.uint8)
-        n, h, w, c = frames.shape
-        assert c == 3
+        fmt = self.pixel_format()
+        bpp, planes = pixel_format_info(fmt)
+        name = {v: k for k, v in PIXEL_FORMATS.items()}[fmt]
+        if planes == 3:
+            if frames.ndim != 4 or frames.shape[1] != 3:
+                raise ValueError("%s: expected uint8 [n, 3, h, w] under the pixel format %r, got %s" % (what, name, frames.shape))
+            n, _, h, w = frames.shape
+            return frames, n, w, h, w, 3 * w * h
+        if frames.ndim != 4 or frames.shape[3] != bpp:
+            raise ValueError("%s: expected uint8 [n, h, w, %d] under the pixel format %r, got %s" % (what, bpp, name, frames.shape))
+        n, h, w, _ = frames.shape
+        return frames, n, w, h, w * bpp, w * h * bpp
+
+    def _pix_strides(self, w, h, stride, frame_stride):
+        """The default stride_bytes / frame_stride_bytes of tightly packed device frames under the pixel format in force."""
+        bpp, planes = pixel_format_info(self.pixel_format())
+        stride = stride or w * bpp
+        return stride, frame_stride or planes * stride * h
+
+    def match_frames(self, frames):
+        """frames: uint8 [n, h, w, 3] in host memory (the array shape of the pixel format in force) -> verdict records."""
+        frames, n, w, h, st, fs = self._pix_frames(frames, "match_frames")
         out = np.zeros(n, VERDICT_DTYPE)
-        self._call("match_frames_bgr8", n, _p(frames), w, h, w * 3, C.c_int64(w * h * 3), _p(out))
+        self._call("match_frames_bgr8", n, _p(frames), w, h, st, C.c_int64(fs), _p(out))
         return out
 
     def last_candidates(self, frame_in_batch):
@@ -494,9 +547,8 @@ class _FrameCalls:
         return cands[: n.value].copy()
 
     def changed_mask(self, frames, prev_small=None):
-        frames = np.ascontiguousarray(frames, np.uint8)
-        n, h, w, _ = frames.shape
-        return self._mask("changed_mask_bgr8", n, w, h, prev_small, _p(frames), w, h, w * 3, C.c_int64(w * h * 3))
+        frames, n, w, h, st, fs = self._pix_frames(frames, "changed_mask")
+        return self._mask("changed_mask_bgr8", n, w, h, prev_small, _p(frames), w, h, st, C.c_int64(fs))
 
     # YUV 4:2:0 frames (include/slideo_amd.h "YUV 4:2:0 frames"): uint8 [n, frame_bytes] in host memory; layout: a Yuv420Layout
     # or a format name (its packed layout)
@@ -570,11 +622,9 @@ class _FrameCalls:
 
     def match_changed_frames(self, frames):
         """frames: uint8 [n, h, w, 3] in host memory, continuing the gate."""
-        frames = np.ascontiguousarray(frames, np.uint8)
-        n, h, w, c = frames.shape
-        assert c == 3
+        frames, n, w, h, st, fs = self._pix_frames(frames, "match_changed_frames")
         ch, sim, out = self._gated_out(n)
-        self._call("match_changed_frames_bgr8", n, _p(frames), w, h, w * 3, C.c_int64(w * h * 3), _p(ch), _p(sim), _p(out))
+        self._call("match_changed_frames_bgr8", n, _p(frames), w, h, st, C.c_int64(fs), _p(ch), _p(sim), _p(out))
         return ch.astype(bool), sim, out
 
     def match_changed_frames_yuv420(self, frames, w, h, layout="nv12"):
@@ -742,6 +792,24 @@ class _FrameCalls:
         rc = lib().slideo_matcher_yuv_sampling(self._mask_owner(), C.byref(v))
         if rc != OK:
             raise SlideoError(rc, "yuv_sampling")
+        return v.value
+
+    # frame pixel format (include/slideo_amd.h "Frame pixel format"): how every *_bgr8 frame call reads its frames
+    def set_pixel_format(self, fmt="bgr"):
+        """'bgr' (the default) | 'rgb' | 'bgra' | 'rgba' | 'argb' | 'abgr' | 'planar_rgb' | 'planar_bgr' | 'planar_gbr' — or the
+        SLIDEO_PIXEL_* value.  Every frame call of the BGR door then reads its frames under it (host arrays [n, h, w, 3],
+        [n, h, w, 4] or [n, 3, h, w]); pages and single-image taps stay BGR.  The matcher must be idle; ends the kept frames and
+        resets the gate state."""
+        self._check(getattr(lib(), self._SETS + "set_pixel_format")(self._h, pixel_format_value(fmt)))
+
+    def pixel_format(self):
+        """The SLIDEO_PIXEL_* value (a Group: member 0's)."""
+        if not hasattr(lib(), "slideo_matcher_pixel_format"):       # (SLIDEO_LIB_PATH may name an older build: tools/ab_libs.sh)
+            return 0
+        v = C.c_int32()
+        rc = lib().slideo_matcher_pixel_format(self._mask_owner(), C.byref(v))
+        if rc != OK:
+            raise SlideoError(rc, "pixel_format")
         return v.value
 
     def _mask_owner(self):
@@ -978,8 +1046,7 @@ class Matcher(_FrameCalls):
     # ---- frames (the host calls: _FrameCalls) --------------------------------------------
     def match_frames_dev(self, dev_ptr, n, w, h, stride=None, frame_stride=None, stream=0):
         """Frames already resident in HBM (raw device pointer)."""
-        stride = stride or w * 3
-        frame_stride = frame_stride or stride * h
+        stride, frame_stride = self._pix_strides(w, h, stride, frame_stride)
         out = np.zeros(n, VERDICT_DTYPE)
         self._check(lib().slideo_match_frames_bgr8_dev(self._h, n, C.c_void_p(dev_ptr), w, h, stride,
                                                        C.c_int64(frame_stride), _p(out),
@@ -991,8 +1058,7 @@ class Matcher(_FrameCalls):
 
     def submit_dev(self, dev_ptr, n, w, h, stride=None, frame_stride=None, stream=0):
         """Streaming form: returns a ticket; at most max_in_flight() units in flight; collect in order."""
-        stride = stride or w * 3
-        frame_stride = frame_stride or stride * h
+        stride, frame_stride = self._pix_strides(w, h, stride, frame_stride)
         t = C.c_int64()
         self._check(lib().slideo_match_frames_submit_dev(self._h, n, C.c_void_p(dev_ptr), w, h, stride,
                                                          C.c_int64(frame_stride), C.c_void_p(stream), C.byref(t)))
@@ -1008,17 +1074,18 @@ class Matcher(_FrameCalls):
     # ---- changed-frame gate (include/slideo_amd.h "Changed-frame gate") ------------------------
     # Gated calls return (changed [n] bool, similarity [n] f32, verdicts [n]); an unchanged frame's verdict is (-1, 0, 0, 0).
     def gate_reset_from_frame(self, frame):
-        """The gate state from one host BGR frame [h, w, 3]: what gate_reset(changed_mask([frame])'s last small image) leaves."""
-        frame = _img3(frame)
-        h, w, _ = frame.shape
-        self._check(lib().slideo_matcher_gate_reset_from_frame_bgr8(self._h, _p(frame), w, h, w * 3))
+        """The gate state from one host frame ([h, w, 3] BGR, or the shape of the pixel format in force): what
+        gate_reset(changed_mask([frame])'s last small image) leaves."""
+        frame, _, w, h, st, _ = self._pix_frames(np.asarray(frame)[None], "gate_reset_from_frame")
+        self._check(lib().slideo_matcher_gate_reset_from_frame_bgr8(self._h, _p(frame), w, h, st))
 
     def gate_reset_from_frame_yuv420(self, frame, w, h, layout="nv12"):
         frames, layout, _ = _yuv_frames(np.asarray(frame).reshape(-1), w, h, layout)
         self._check(lib().slideo_matcher_gate_reset_from_frame_yuv420(self._h, _p(frames), w, h, C.byref(layout)))
 
     def gate_reset_from_frame_dev(self, dev_ptr, w, h, stride=None, stream=0):
-        self._check(lib().slideo_matcher_gate_reset_from_frame_bgr8_dev(self._h, C.c_void_p(dev_ptr), w, h, stride or w * 3, C.c_void_p(stream)))
+        stride, _ = self._pix_strides(w, h, stride, None)
+        self._check(lib().slideo_matcher_gate_reset_from_frame_bgr8_dev(self._h, C.c_void_p(dev_ptr), w, h, stride, C.c_void_p(stream)))
 
     def gate_reset_from_frame_yuv420_dev(self, dev_ptr, w, h, layout, stream=0):
         if isinstance(layout, str):
@@ -1026,8 +1093,7 @@ class Matcher(_FrameCalls):
         self._check(lib().slideo_matcher_gate_reset_from_frame_yuv420_dev(self._h, C.c_void_p(dev_ptr), w, h, C.byref(layout), C.c_void_p(stream)))
 
     def match_changed_frames_dev(self, dev_ptr, n, w, h, stride=None, frame_stride=None, stream=0):
-        stride = stride or w * 3
-        frame_stride = frame_stride or stride * h
+        stride, frame_stride = self._pix_strides(w, h, stride, frame_stride)
         ch, sim, out = self._gated_out(n)
         self._check(lib().slideo_match_changed_frames_bgr8_dev(self._h, n, C.c_void_p(dev_ptr), w, h, stride, C.c_int64(frame_stride),
                                                                _p(ch), _p(sim), _p(out), C.c_void_p(stream)))
@@ -1043,8 +1109,7 @@ class Matcher(_FrameCalls):
 
     def submit_changed_dev(self, dev_ptr, n, w, h, stride=None, frame_stride=None, stream=0):
         """A gated unit (streaming form): a ticket for collect_changed; tickets of gated and plain units share one order."""
-        stride = stride or w * 3
-        frame_stride = frame_stride or stride * h
+        stride, frame_stride = self._pix_strides(w, h, stride, frame_stride)
         t = C.c_int64()
         self._check(lib().slideo_match_changed_frames_submit_dev(self._h, n, C.c_void_p(dev_ptr), w, h, stride, C.c_int64(frame_stride),
                                                                  C.c_void_p(stream), C.byref(t)))
@@ -1073,19 +1138,16 @@ class Matcher(_FrameCalls):
         self._check(lib().slideo_matcher_activity_end(self._h))
 
     def observe_frames(self, frames):
-        """frames: uint8 [n, h, w, 3] in host memory, continuing the accumulator."""
-        frames = np.ascontiguousarray(frames, np.uint8)
-        n, h, w, c = frames.shape
-        assert c == 3
-        self._check(lib().slideo_matcher_observe_frames_bgr8(self._h, n, _p(frames), w, h, w * 3, C.c_int64(w * h * 3)))
+        """frames: uint8 [n, h, w, 3] in host memory (the array shape of the pixel format in force), continuing the accumulator."""
+        frames, n, w, h, st, fs = self._pix_frames(frames, "observe_frames")
+        self._check(lib().slideo_matcher_observe_frames_bgr8(self._h, n, _p(frames), w, h, st, C.c_int64(fs)))
 
     def observe_frames_yuv420(self, frames, w, h, layout="nv12"):
         frames, layout, fs = _yuv_frames(frames, w, h, layout)
         self._check(lib().slideo_matcher_observe_frames_yuv420(self._h, frames.shape[0], _p(frames), w, h, C.byref(layout), C.c_int64(fs)))
 
     def observe_frames_dev(self, dev_ptr, n, w, h, stride=None, frame_stride=None, stream=0):
-        stride = stride or w * 3
-        frame_stride = frame_stride or stride * h
+        stride, frame_stride = self._pix_strides(w, h, stride, frame_stride)
         self._check(lib().slideo_matcher_observe_frames_bgr8_dev(self._h, n, C.c_void_p(dev_ptr), w, h, stride, C.c_int64(frame_stride),
                                                                  C.c_void_p(stream)))
 
@@ -1167,6 +1229,19 @@ class Matcher(_FrameCalls):
         self._check(lib().slideo_match_frames_submit_yuv420_dev(self._h, n, C.c_void_p(dev_ptr), w, h, C.byref(layout),
                                                                 C.c_int64(frame_stride), C.c_void_p(stream), C.byref(t)))
         return (t.value, n)
+
+    def pixels_to_bgr(self, frame, stride=None):
+        """The BGR image (h, w, 3) one host frame stands for under the pixel format in force (the conversion tap).  frame: the
+        format's array shape ([h, w, 3], [h, w, 4] or [3, h, w]); or, with `stride`, a (flat buffer, w, h) triple whose rows lie
+        `stride` bytes apart."""
+        if stride is None:
+            frame, _, w, h, stride, _ = self._pix_frames(np.asarray(frame)[None], "pixels_to_bgr")
+        else:
+            frame, w, h = frame
+            frame = np.ascontiguousarray(frame, np.uint8)
+        out = np.empty((h, w, 3), np.uint8)
+        self._check(lib().slideo_pixels_to_bgr8(self._h, _p(frame), w, h, int(stride), _p(out), C.c_int64(out.size)))
+        return out
 
     def yuv420_to_bgr(self, frame, w, h, layout="nv12"):
         """The BGR image (h, w, 3) the library makes of one 4:2:0 frame (the conversion tap)."""

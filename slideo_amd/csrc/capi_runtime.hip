@@ -87,10 +87,14 @@ void validate_image(int w, int h, int stride) {
 }
 
 void validate_frames(FrameSrc& src, slideo_matcher* m, int n, const void* out) {
+    if (m) src.describe(m->fs);                                    // (a call without a matcher argument here sets it itself)
     if (src.yuv) {
-        if (m) src.describe(m->fs.yuv);                            // (a tap without a matcher argument sets it itself)
         src.yuv_span = yuv420_validate(src.w, src.h, src.yuv, src.frame_stride, src.bps, src.sampling);
         src.stride = src.w * 3;                                    // the BGR image the units read (d_stage)
+    } else if (src.pixel_format != SLIDEO_PIXEL_BGR8 && src.src_stride == 0) {
+        src.pix_span = pixel_format_validate(src.pixel_format, src.w, src.h, src.stride, src.frame_stride);
+        src.src_stride = src.stride;
+        src.stride = src.w * 3;                                    // likewise
     }
     if (m) {
         if (!m->finalized) fail(SLIDEO_ERR_STATE, "slideo_matcher_finalize_pages must be called before matching");
@@ -99,7 +103,7 @@ void validate_frames(FrameSrc& src, slideo_matcher* m, int n, const void* out) {
     }
     validate_image(src.w, src.h, src.stride);
     if (m) resolve_frames(m, src, true);
-    if (m && !src.yuv && src.frame_stride < (int64_t)src.h * src.stride) fail(SLIDEO_ERR_INVALID_ARG, "frame_stride smaller than one frame");
+    if (m && !src.converted() && src.frame_stride < (int64_t)src.h * src.stride) fail(SLIDEO_ERR_INVALID_ARG, "frame_stride smaller than one frame");
     src.pinned = !src.on_device && src.p && host_is_pinned(src.p);
 }
 
@@ -169,7 +173,7 @@ DevFrames stage_frames(slideo_matcher* m, Slot& S, const FrameSrc& src, int firs
     const uint8_t* p = src.p + (int64_t)first * src.frame_stride;
     const FramePlan& P = src.plan;      // (a tap's unresolved plan is PREP_NONE: uw, uh are read under `pre` alone)
     const bool pre = P.prep != PREP_NONE;                        // a kernel stands between the BGR view at source size and the unit's image
-    if (src.on_device && !src.yuv && !pre) return DevFrames{p, src.w, src.h, src.stride, src.frame_stride};
+    if (src.on_device && !src.converted() && !pre) return DevFrames{p, src.w, src.h, src.stride, src.frame_stride};
     const int uw = P.uw, uh = P.uh;
     const int64_t fb = (int64_t)src.h * src.stride;              // one frame of the BGR view at source size (stride 3w for YUV frames)
     const int64_t ub = pre ? (int64_t)uh * uw * 3 : fb;          // one frame of the unit's BGR image
@@ -179,9 +183,9 @@ DevFrames stage_frames(slideo_matcher* m, Slot& S, const FrameSrc& src, int firs
     int64_t fs = src.frame_stride;
     if (!src.on_device) {
         // host frames back to back into d_stage, or into d_yuv for the conversion / the reduce / the rectify below
-        const int64_t bytes = src.yuv ? src.yuv_span : fb;
+        const int64_t bytes = src.converted() ? src.src_span() : fb;
         uint8_t* dst = stage;
-        if (src.yuv || pre) { S.d_yuv.reserve((size_t)bytes * n + 16); dst = S.d_yuv.as<uint8_t>(); }
+        if (src.converted() || pre) { S.d_yuv.reserve((size_t)bytes * n + 16); dst = S.d_yuv.as<uint8_t>(); }
         hipStream_t st = cs ? cs : S.st;
         if (fs == bytes) {
             HIP_CHECK(hipMemcpyAsync(dst, p, (size_t)bytes * n, hipMemcpyHostToDevice, st));
@@ -197,10 +201,12 @@ DevFrames stage_frames(slideo_matcher* m, Slot& S, const FrameSrc& src, int firs
     }
     // 4:2:0 frames: converted on the slot's stream into its d_stage, which lives until the unit is collected (verify's re-projection
     // reads the frames); into d_full when the image is reduced or rectified next (both come after convert)
-    if (src.yuv) {
+    // frames of another pixel format: the same, device frames out of the caller's memory
+    if (src.converted()) {
         uint8_t* bgr = stage;
         if (pre) { S.d_full.reserve((size_t)fb * n + 16); bgr = S.d_full.as<uint8_t>(); }
-        launch_yuv420_to_bgr(m->fs.yuv, p, fs, *src.yuv, src.w, src.h, n, bgr, S.st);
+        if (src.yuv) launch_yuv420_to_bgr(m->fs.yuv, p, fs, *src.yuv, src.w, src.h, n, bgr, S.st);
+        else launch_pixels_to_bgr(src.pixel_format, p, fs, src.src_stride, src.w, src.h, n, bgr, S.st);
         p = bgr; fs = fb;
     }
     if (!pre) return DevFrames{stage, src.w, src.h, src.stride, fb};
@@ -464,7 +470,7 @@ static Slot& slot_of_ticket(slideo_matcher* m, int64_t ticket, bool gated) {
 void changed_mask_impl(slideo_matcher* m, int n_frames, FrameSrc src, const uint8_t* prev_small, uint8_t* last_small_out, uint8_t* changed_out,
                        float* similarity_out) {
     if (n_frames < 0 || (n_frames > 0 && (!src.p || !changed_out))) fail(SLIDEO_ERR_INVALID_ARG, "null frames/changed");
-    src.describe(m->fs.yuv);
+    src.describe(m->fs);
     validate_frames(src);
     resolve_frames(m, src, false);
     if (n_frames == 0) return;
@@ -1207,6 +1213,44 @@ int32_t slideo_matcher_yuv_sampling(const slideo_matcher* m, int32_t* sampling) 
     if (!m || !sampling) return SLIDEO_ERR_INVALID_ARG;
     *sampling = m->fs.yuv.sampling;
     return SLIDEO_OK;
+}
+
+// ---- Frame pixel format (include/slideo_amd.h "Frame pixel format") -------------------------------------------------------------
+
+int32_t slideo_matcher_set_pixel_format(slideo_matcher* m, int32_t format) {
+    return matcher_set(m, SET_YUV_DESCRIPTION, [&](const FrameSettings& s) { return propose_pixel_format(s, format); });
+}
+
+int32_t slideo_matcher_pixel_format(const slideo_matcher* m, int32_t* format) {
+    if (!m || !format) return SLIDEO_ERR_INVALID_ARG;
+    *format = m->fs.pixel_format;
+    return SLIDEO_OK;
+}
+
+int32_t slideo_pixel_format_info(int32_t format, int32_t* bytes_per_pixel, int32_t* planes) {
+    int bpp = 0, np = 0;
+    if (!pixel_format_info(format, &bpp, &np)) return SLIDEO_ERR_INVALID_ARG;
+    if (bytes_per_pixel) *bytes_per_pixel = bpp;
+    if (planes) *planes = np;
+    return SLIDEO_OK;
+}
+
+int32_t slideo_pixels_to_bgr8(slideo_matcher* m, const uint8_t* frame, int32_t width, int32_t height, int32_t stride_bytes, uint8_t* bgr_out,
+                              int64_t out_capacity) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    if (!frame || !bgr_out) fail(SLIDEO_ERR_INVALID_ARG, "null frame/bgr_out");
+    FrameSrc img = FrameSrc::bgr8(frame, false, width, height, stride_bytes, -1);
+    img.describe(m->fs);
+    validate_frames(img);
+    const size_t row = (size_t)width * 3, fb = row * (size_t)height;
+    if ((int64_t)fb > out_capacity) fail(SLIDEO_ERR_CAPACITY, "the BGR image needs %zu bytes", fb);
+    if (!img.converted()) {                         // the default format: the frame is the image, row by row
+        for (int y = 0; y < height; ++y) std::memcpy(bgr_out + (size_t)y * row, frame + (size_t)y * stride_bytes, row);
+        return SLIDEO_OK;
+    }
+    tap_staged(m, img, bgr_out, (int64_t)fb);
+    API_CATCH(m)
 }
 
 int32_t slideo_yuv_layout_packed(int32_t format, int32_t w, int32_t h, int32_t bytes_per_sample, slideo_yuv420_layout* out) {

@@ -1,5 +1,5 @@
 // frame_settings.h — the frame settings of a matcher as ONE record (include/slideo_amd.h "Working size", "Frame region", "Frame mask",
-// "Frame mask scope", "Direct page look-up", "Direct look-up scope", "YUV colour description", "YUV sampling", "Gate reference", "Gate settle", "Gate memory"): the record, every setter's proposal with its range checks, the
+// "Frame mask scope", "Direct page look-up", "Direct look-up scope", "YUV colour description", "YUV sampling", "Gate reference", "Gate settle", "Gate memory", "Frame pixel format"): the record, every setter's proposal with its range checks, the
 // rules between settings, what a change of each ends.  Plain C++, no HIP include (tools/frame_settings_hostcheck.cpp walks it on the
 // host); the device buffers a setting owns are the matcher's (runtime.hpp).  A change takes ONE path: settings_commit (capi_runtime.hip).
 #pragma once
@@ -46,6 +46,7 @@ struct FrameSettings {
     float direct_t = 0.f;                             // the direct similarity (0: off)
     uint32_t direct_scope = SLIDEO_DIRECT_WHOLE;      // VALID = the look-up over the gate's valid pixels
     YuvDesc yuv;                                      // 4:2:0 frames stand for the BGR image under it (BGR calls never look at it)
+    int pixel_format = SLIDEO_PIXEL_BGR8;             // how every *_bgr8 frame call reads its frames (YUV calls never look at it)
     uint32_t gate_ref = SLIDEO_GATE_PREVIOUS;         // what a gated frame is compared with: the frame before it, or the last changed one (ANCHOR)
     // the gate settle, part of the gate-reference setting ("Gate settle"): under ANCHOR a frame away from the anchor is matched once it
     // is within settle_similarity of the frame before it, or after settle_max_defer deferred frames; 0: off
@@ -139,6 +140,54 @@ inline FrameSettings propose_yuv_sampling(FrameSettings s, int sampling) {
         fail(SLIDEO_ERR_INVALID_ARG, "yuv sampling: %d is none of SLIDEO_YUV_SAMPLING_420 (0), _422 (1), _444 (2), _422_PACKED (3)", sampling);
     s.yuv.sampling = sampling;
     return s;
+}
+
+// ---- the frame pixel format (include/slideo_amd.h "Frame pixel format") -----------------------------------------------------------
+// bytes per pixel of a row (3 or 4; 1: a plane's) and planes (1 or 3) of a format; false: not a format
+inline bool pixel_format_info(int format, int* bytes_per_pixel, int* planes) {
+    if (format < SLIDEO_PIXEL_BGR8 || format > SLIDEO_PIXEL_PLANAR_GBR8) return false;
+    const bool planar = format >= SLIDEO_PIXEL_PLANAR_RGB8, four = format >= SLIDEO_PIXEL_BGRA8 && !planar;
+    if (bytes_per_pixel) *bytes_per_pixel = planar ? 1 : four ? 4 : 3;
+    if (planes) *planes = planar ? 3 : 1;
+    return true;
+}
+inline const char* pixel_format_name(int format) {
+    static const char* const names[] = {"SLIDEO_PIXEL_BGR8", "SLIDEO_PIXEL_RGB8", "SLIDEO_PIXEL_BGRA8", "SLIDEO_PIXEL_RGBA8", "SLIDEO_PIXEL_ARGB8",
+                                        "SLIDEO_PIXEL_ABGR8", "SLIDEO_PIXEL_PLANAR_RGB8", "SLIDEO_PIXEL_PLANAR_BGR8", "SLIDEO_PIXEL_PLANAR_GBR8"};
+    return format >= SLIDEO_PIXEL_BGR8 && format <= SLIDEO_PIXEL_PLANAR_GBR8 ? names[format] : "?";
+}
+// where a pixel's B, G and R lie: the byte of a packed pixel, the plane of a planar frame
+inline void pixel_format_channels(int format, int* b, int* g, int* r) {
+    static const int pos[9][3] = {{0, 1, 2}, {2, 1, 0}, {0, 1, 2}, {2, 1, 0}, {3, 2, 1}, {1, 2, 3}, {2, 1, 0}, {0, 1, 2}, {1, 0, 2}};
+    *b = pos[format][0]; *g = pos[format][1]; *r = pos[format][2];
+}
+// The format commits under SET_YUV_DESCRIPTION like the sampling: it ends the kept frames and resets the gate
+inline FrameSettings propose_pixel_format(FrameSettings s, int format) {
+    if (!pixel_format_info(format, nullptr, nullptr))
+        fail(SLIDEO_ERR_INVALID_ARG, "pixel format: %d is none of SLIDEO_PIXEL_BGR8 (0) .. SLIDEO_PIXEL_PLANAR_GBR8 (8)", format);
+    s.pixel_format = format;
+    return s;
+}
+// The layout rules of a frame under a format other than SLIDEO_PIXEL_BGR8 (whose rules and messages are validate_image's); returns the
+// bytes of one frame.  frame_stride < 0: a single frame, no stride to check.
+inline int64_t pixel_format_validate(int format, int w, int h, int stride, int64_t frame_stride) {
+    int bpp = 0, planes = 0;
+    if (!pixel_format_info(format, &bpp, &planes)) fail(SLIDEO_ERR_INVALID_ARG, "pixel format: %d is not a format", format);
+    const char* name = pixel_format_name(format);
+    if (w < 1 || h < 1) fail(SLIDEO_ERR_INVALID_ARG, "bad image geometry w=%d h=%d stride=%d", w, h, stride);
+    if ((int64_t)stride < (int64_t)bpp * w) {
+        if (planes == 3) fail(SLIDEO_ERR_INVALID_ARG, "%s: stride_bytes %d < width %d (the row stride of every plane)", name, stride, w);
+        fail(SLIDEO_ERR_INVALID_ARG, "%s: stride_bytes %d < %d * width %d", name, stride, bpp, w);
+    }
+    const int64_t span = (int64_t)planes * h * stride;
+    if (frame_stride >= 0 && frame_stride < span) {
+        if (planes == 3)
+            fail(SLIDEO_ERR_INVALID_ARG, "%s: frame_stride %lld does not cover the frame's three planes (3 * height %d * stride_bytes %d = %lld)", name,
+                 (long long)frame_stride, h, stride, (long long)span);
+        fail(SLIDEO_ERR_INVALID_ARG, "%s: frame_stride %lld smaller than one frame (height %d * stride_bytes %d = %lld)", name, (long long)frame_stride, h,
+             stride, (long long)span);
+    }
+    return span;
 }
 
 inline FrameSettings propose_gate_reference(FrameSettings s, uint32_t ref) {

@@ -6,7 +6,8 @@
 //   capi_runtime.hip   handles, page database, slots, the frame settings' one commit path and their set calls, a call's frames resolved
 //                      (FrameSrc -> FramePlan) and staged (-> DevFrames), unit submit / collect, the drivers of the frame calls
 //                      (pipeline, submit, collect: plain and gated) and their entry points
-//   stage_orb.hip      ORB stage drivers          (kernels: orb.hip.h, yuv420.hip.h, reduce.hip.h, frame_region.hip.h, frame_mask.hip.h)
+//   stage_orb.hip      ORB stage drivers          (kernels: orb.hip.h, yuv420.hip.h, yuv_sampling.hip.h, pixel_format.hip.h, reduce.hip.h,
+//                                                 frame_region.hip.h, frame_mask.hip.h)
 //   stage_knn.hip      index build + k-NN stage   (kernels: knn.hip.h, knn_tile.hip.h, knn_l2.hip.h, knn_lsh.hip.h)
 //   stage_verify.hip   vote .. verdict, small img (kernels: verify.hip.h, homography.hip.h)
 //   stage_sift.hip     SIFT stage + entry points  (kernels: sift.hip.h)
@@ -94,13 +95,14 @@ struct FramePlan {
     }
 };
 
-// A call's frames as the caller handed them over: BGR8 (yuv null) or YUV 4:2:0 in the layout `yuv`, in host or device memory.
+// A call's frames as the caller handed them over: through the BGR door (yuv null; under the matcher's pixel format) or YUV in the
+// layout `yuv`, in host or device memory.
 // validate_frames checks them and fills the derived fields; stage_frames turns a block of them into a unit's BGR8 view.
 struct FrameSrc {
     const uint8_t* p = nullptr;
     bool on_device = false;
     int w = 0, h = 0;
-    int stride = 0;                             // BGR rows; a YUV source's BGR image (d_stage) has 3w, set by validate_frames
+    int stride = 0;                             // BGR rows; a converted source's BGR image (d_stage) has 3w, set by validate_frames
     int64_t frame_stride = 0;                   // (a single frame: -1 = no stride to check)
     const slideo_yuv420_layout* yuv = nullptr;
     int bps = 1;                                // (derived) bytes per YUV sample: the matcher's YUV description (validate_frames)
@@ -110,11 +112,23 @@ struct FrameSrc {
     // the frames are unit images already — the frames a mask call kept (slideo_match_kept_frames): no region applies to them
     bool analysed = false;
     FramePlan plan;                             // (derived) resolve_frames
+    // (derived) the matcher's pixel format for frames through the BGR door (describe; YUV and analysed frames: BGR8), the source's
+    // row stride and the bytes of one source frame (validate_frames; 0 under BGR8: `stride` is the source's)
+    int pixel_format = SLIDEO_PIXEL_BGR8;
+    int src_stride = 0;
+    int64_t pix_span = 0;
 
-    void describe(const YuvDesc& d) { bps = d.bytes_per_sample(); sampling = d.sampling; }
+    void describe(const FrameSettings& fs) {
+        bps = fs.yuv.bytes_per_sample(); sampling = fs.yuv.sampling;
+        pixel_format = yuv || analysed ? SLIDEO_PIXEL_BGR8 : fs.pixel_format;
+    }
+    // a converter stands in front of the unit's BGR image: the frames are not read as they lie
+    bool converted() const { return yuv != nullptr || pixel_format != SLIDEO_PIXEL_BGR8; }
+    int64_t src_span() const { return yuv ? yuv_span : pix_span; }      // bytes of one frame a converter reads
 
     // per frame, the staging in front of the unit's BGR image: 1.5 B per pixel for 4:2:0 frames, 3 B in 16-bit containers, 2 * bps
-    // under both 4:2:2 forms and 3 * bps under 4:4:4 ("YUV sampling"; BGR calls keep their unit sizes);
+    // under both 4:2:2 forms and 3 * bps under 4:4:4 ("YUV sampling"; BGR calls keep their unit sizes); under a pixel format a HOST
+    // frame's span (a device frame is converted out of the caller's memory: nothing extra);
     // a reducing or rectifying call: the uploaded source frame (host sources) and the source-sized BGR image of a 4:2:0 frame;
     // gated (a gated call, include/slideo_amd.h "Changed-frame gate"): + the gate staging — the BGR unit image of every frame that
     // is not the caller's own device memory — and the frame's small image (gate_small: at most 3 * small_area bytes) and gate record
@@ -122,8 +136,9 @@ struct FrameSrc {
         const size_t px = (size_t)w * h;
         const bool pre = plan.prep != PREP_NONE;
         const size_t yb = (sampling == SLIDEO_YUV_SAMPLING_420 ? px * 3 / 2 : sampling == SLIDEO_YUV_SAMPLING_444 ? px * 3 : px * 2) * (size_t)bps;
-        size_t b = !pre ? (yuv ? yb : 0) : (on_device ? 0 : (yuv ? yb : (size_t)h * stride)) + (yuv ? px * 3 : 0);
-        if (gate_small) b += (on_device && !yuv && !pre ? 0 : (size_t)plan.uw * plan.uh * 3) + gate_small + 32;
+        const size_t cb = yuv ? yb : (size_t)pix_span;              // the frame a converter reads (0: plain BGR, no converter)
+        size_t b = !pre ? (yuv || !on_device ? cb : 0) : (on_device ? 0 : (converted() ? cb : (size_t)h * stride)) + (converted() ? px * 3 : 0);
+        if (gate_small) b += (on_device && !converted() && !pre ? 0 : (size_t)plan.uw * plan.uh * 3) + gate_small + 32;
         return b;
     }
 
@@ -465,8 +480,8 @@ void resolve_unit(const slideo_matcher* m, FrameSrc& src);
 // of SET_FRAME_MASK, rows `stride` apart), then `next` in force and what SETTING_ENDS[what] ends ended.
 void settings_commit(slideo_matcher* m, Setting what, FrameSettings next, const uint8_t* mask = nullptr, int stride = 0);
 // Frames [first, first + n) of a validated `src` as BGR8 on the device, for slot S: a device BGR source as it is; host frames
-// copied into S.d_stage (BGR) or S.d_yuv (YUV), on `cs` when given (S.st waits for it) and on S.st otherwise; YUV converted into
-// S.d_stage on S.st; a source the working size reduces: host frames into S.d_yuv, 4:2:0 frames converted into S.d_full, then
+// copied into S.d_stage (BGR) or S.d_yuv (YUV, another pixel format), on `cs` when given (S.st waits for it) and on S.st otherwise; YUV and other pixel formats converted into
+// S.d_stage on S.st (device frames of another pixel format out of the caller's memory); a source the working size reduces: host frames into S.d_yuv, 4:2:0 frames converted into S.d_full, then
 // reduced into S.d_stage; under a frame region the same with the rectify in place of the reduce (device BGR frames are read in the
 // caller's memory); the DevFrames are then plan.uw x plan.uh.  Every write of a slot's d_stage goes through here (page ingest through its staging buffer) and ends the
 // frames slideo_changed_mask_bgr8 kept for slideo_match_kept_frames.
@@ -531,6 +546,9 @@ void frame_region_classify(FrameRegion& R);
 // n decoded YUV 4:2:0 frames (a layout yuv420_validate accepted under `desc`, frame stride src_fs) -> BGR8 at dst, stride 3w, frame
 // stride 3wh.  The default description: yuv420_to_bgr_kernel; any other: yuv420_to_bgr_desc_kernel
 void launch_yuv420_to_bgr(const YuvDesc& desc, const uint8_t* src, int64_t src_fs, const slideo_yuv420_layout& L, int w, int h, int n, uint8_t* dst, hipStream_t st);
+// n frames under the pixel format `format` (not SLIDEO_PIXEL_BGR8; a layout pixel_format_validate accepted, rows `stride` and frames
+// src_fs apart) -> BGR8 at dst, stride 3w, frame stride 3wh: pixels_to_bgr_kernel (pixel_format.hip.h)
+void launch_pixels_to_bgr(int format, const uint8_t* src, int64_t src_fs, int stride, int w, int h, int n, uint8_t* dst, hipStream_t st);
 
 // ---- stage_knn.hip --------------------------------------------------------------------------------
 // FlannMatcher::new (mo/flann.rs:65-71) for the Hamming index: uploads the M packed rows, collapses equal rows, builds the

@@ -22,9 +22,9 @@ dim3 act_grid(int threads_x, int ah) { return dim3((unsigned)cdiv64(threads_x, A
 // slideo_matcher_observe_frames_*: everything is validated before anything is written
 void activity_observe(slideo_matcher* m, int n, FrameSrc src, hipStream_t user_stream) {
     if (n < 0 || (n > 0 && !src.p)) fail(SLIDEO_ERR_INVALID_ARG, "null frames");
-    src.describe(m->fs.yuv);
+    src.describe(m->fs);
     validate_frames(src);                                  // a frame source's rules without the deck's (m == nullptr)
-    if (!src.yuv && src.frame_stride < (int64_t)src.h * src.stride) fail(SLIDEO_ERR_INVALID_ARG, "frame_stride smaller than one frame");
+    if (!src.converted() && src.frame_stride < (int64_t)src.h * src.stride) fail(SLIDEO_ERR_INVALID_ARG, "frame_stride smaller than one frame");
     resolve_unit(m, src);                                  // the analysed size: the frame region's source-size rule, else the working size
     // the sizes the pipeline analyses, refused as a frame call refuses them: a reduced frame's source (resolve_frames), the unit (geom_for)
     if (src.plan.prep == PREP_REDUCE && (src.w > MAX_DIM || src.h > MAX_DIM)) fail(SLIDEO_ERR_UNSUPPORTED, "image size %dx%d outside 1..%d", src.w, src.h, MAX_DIM);
@@ -53,7 +53,7 @@ void activity_observe(slideo_matcher* m, int n, FrameSrc src, hipStream_t user_s
     hipStream_t st = S.st;
     const size_t px = (size_t)aw * ah;
     // frames per block: what a frame stages in front of its analysed image, and that image unless it is the caller's own memory
-    const bool in_place = src.on_device && !src.yuv && src.plan.prep == PREP_NONE;
+    const bool in_place = src.on_device && !src.converted() && src.plan.prep == PREP_NONE;
     const size_t per = src.staging_bytes() + (in_place ? 0 : px * 3);
     const int block = per == 0 ? n : (int)std::min<size_t>({(size_t)n, std::max<size_t>(1, ACT_BLOCK_BYTES / per), (size_t)ACT_MAX_BLOCK});
     // every allocation in front of the first write: the counts and the carried image of a first frame, the largest block's staging

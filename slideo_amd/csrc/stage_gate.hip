@@ -90,7 +90,9 @@ void gate_check(const slideo_matcher::GateState& g, const FrameSrc& src) {
 // place), its small image written into the gate state behind the last gated unit's write of it.  What slideo_matcher_gate_reset
 // leaves with that small image: the frame's own size and format family are not recorded.
 void gate_prime(slideo_matcher* m, FrameSrc src, hipStream_t user_stream) {
-    validate_frames(src, m, 1, src.p);              // (a gated call's rules; the frame itself stands for the null frames / verdicts check)
+    // (a single frame under another pixel format has no stride to check: a BGR frame's own, height * stride_bytes, covers one plane)
+    if (!src.yuv && m->fs.pixel_format != SLIDEO_PIXEL_BGR8) src.frame_stride = -1;
+    validate_frames(src, m, 1, src.p);             // (a gated call's rules; the frame itself stands for the null frames / verdicts check)
     HIP_CHECK(hipSetDevice(m->device));
     require_idle(m);
     Slot& S = m->slots[0];

@@ -1,10 +1,11 @@
-// stage_orb.hip — drivers of the ORB stage (kernels: orb.hip.h) and of the front doors in front of it: YUV 4:2:0 frames
-// (yuv420.hip.h), the working-size reduce (reduce.hip.h) and the frame region's rectify (frame_region.hip.h); the frame mask's
+// stage_orb.hip — drivers of the ORB stage (kernels: orb.hip.h) and of the front doors in front of it: YUV frames
+// (yuv420.hip.h, yuv_sampling.hip.h), frames of another pixel format (pixel_format.hip.h), the working-size reduce (reduce.hip.h) and the frame region's rectify (frame_region.hip.h); the frame mask's
 // pyramid and candidate filter (frame_mask.hip.h).
 #include "runtime.hpp"
 #include "orb.hip.h"
 #include "yuv420.hip.h"
 #include "yuv_sampling.hip.h"
+#include "pixel_format.hip.h"
 #include "reduce.hip.h"
 #include "frame_region.hip.h"
 #include "frame_mask.hip.h"
@@ -134,6 +135,19 @@ void launch_yuv420_to_bgr(const YuvDesc& desc, const uint8_t* src, int64_t src_f
     a.fast = luma4 && chroma && out4;
     yuv420_to_bgr_kernel<<<grid, dim3(YUV_TX, YUV_TY), 0, st>>>(a);
     check_launch("yuv420_to_bgr_kernel");
+}
+
+// n frames under a pixel format other than SLIDEO_PIXEL_BGR8 (a layout pixel_format_validate accepted: rows `stride`, frames src_fs
+// apart) -> BGR8 at dst (stride 3w, frame stride 3wh)
+void launch_pixels_to_bgr(int format, const uint8_t* src, int64_t src_fs, int stride, int w, int h, int n, uint8_t* dst, hipStream_t st) {
+    if (format == SLIDEO_PIXEL_BGR8) fail(SLIDEO_ERR_HIP, "internal: SLIDEO_PIXEL_BGR8 frames are not converted");
+    const PixArgs a = pixels_args(format, src, src_fs, stride, w, h, n, dst);
+    const dim3 grid(cdiv(cdiv(w, 4), YUV_TX), cdiv(h, YUV_TY), n), block(YUV_TX, YUV_TY);
+    const int form = pixel_format_form(format);
+    if (form == PIX_PACKED3) pixels_to_bgr_kernel<PIX_PACKED3><<<grid, block, 0, st>>>(a);
+    else if (form == PIX_PACKED4) pixels_to_bgr_kernel<PIX_PACKED4><<<grid, block, 0, st>>>(a);
+    else pixels_to_bgr_kernel<PIX_PLANAR><<<grid, block, 0, st>>>(a);
+    check_launch("pixels_to_bgr_kernel");
 }
 
 // the reduce class (w, h) -> (dw, dh): ResizeAreaFast when both factors are integers (the test of resize.cpp, in double), else the

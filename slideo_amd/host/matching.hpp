@@ -411,6 +411,11 @@ public:
     // SLIDEO_YUV_SAMPLING_420 (default), _422, _444 (screen recorders) or _422_PACKED (YUY2 / UYVY of capture cards; 8-bit).  Every
     // call that takes a slideo_yuv420_layout reads its frames under it.  The reference knows BGR only
     HipImageVideoMatcher& with_yuv_sampling(int32_t sampling) { yuv_sampling_ = sampling; return *this; }
+    // How the frames of the BGR door are read (slideo_group_set_pixel_format, include/slideo_amd.h "Frame pixel format"):
+    // SLIDEO_PIXEL_BGR8 (default), _RGB8, the four-byte _BGRA8 / _RGBA8 / _ARGB8 / _ABGR8 of screen-capture APIs, or the planar
+    // _PLANAR_RGB8 / _PLANAR_BGR8 / _PLANAR_GBR8.  The frame source then hands out frames in that format; pages stay BGR.  The
+    // reference only ever sees OpenCV's BGR
+    HipImageVideoMatcher& with_pixel_format(int32_t format) { pixel_format_ = format; return *this; }
     // Which frame a gated frame is compared with (slideo_group_set_gate_reference, include/slideo_amd.h "Gate reference"):
     // SLIDEO_GATE_PREVIOUS (default: the frame before, the reference's MarkSimilarIter) or SLIDEO_GATE_ANCHOR (the last frame that
     // was flagged: a change spread over many frames is still flagged when every decoded frame is fed).  One device only: a group of
@@ -462,6 +467,7 @@ public:
         if (yuv_matrix_ != SLIDEO_YUV_MATRIX_BT601 || yuv_range_ != SLIDEO_YUV_RANGE_LIMITED || yuv_depth_ != SLIDEO_YUV_DEPTH_8)
             h->check(slideo_group_set_yuv_description(h->g, yuv_matrix_, yuv_range_, yuv_depth_));
         if (yuv_sampling_ != SLIDEO_YUV_SAMPLING_420) h->check(slideo_group_set_yuv_sampling(h->g, yuv_sampling_));
+        if (pixel_format_ != SLIDEO_PIXEL_BGR8) h->check(slideo_group_set_pixel_format(h->g, pixel_format_));
         if (mask_scope_ != SLIDEO_MASK_DETECT) h->check(slideo_group_set_frame_mask_scope(h->g, mask_scope_));
         if (!mask_.empty()) h->check(slideo_group_set_frame_mask(h->g, mask_.data(), mask_w_, mask_h_, mask_w_));
         if (direct_scope_ != SLIDEO_DIRECT_WHOLE) h->check(slideo_group_set_direct_scope(h->g, direct_scope_));
@@ -490,6 +496,7 @@ private:
     int32_t mask_w_ = 0, mask_h_ = 0;
     int32_t yuv_matrix_ = SLIDEO_YUV_MATRIX_BT601, yuv_range_ = SLIDEO_YUV_RANGE_LIMITED, yuv_depth_ = SLIDEO_YUV_DEPTH_8;
     int32_t yuv_sampling_ = SLIDEO_YUV_SAMPLING_420;
+    int32_t pixel_format_ = SLIDEO_PIXEL_BGR8;
     uint32_t mask_scope_ = SLIDEO_MASK_DETECT, direct_scope_ = SLIDEO_DIRECT_WHOLE, gate_ref_ = SLIDEO_GATE_PREVIOUS;
     uint32_t gate_order_ = SLIDEO_GROUP_GATE_HALO;
     float settle_similarity_ = 0.f;

@@ -385,7 +385,7 @@ class HipImageVideoMatcher:
 
     def __init__(self, cfg=None, device=None, sift=None, devices=None, working_size=None, frame_mask=None, frame_mask_scope=None,
                  direct_similarity=None, direct_scope=None, frame_region=None, yuv_description=None, gate_reference=None, gate_settle=None,
-                 group_gate_order=None, yuv_sampling=None, gate_memory=None):
+                 group_gate_order=None, yuv_sampling=None, gate_memory=None, pixel_format=None):
         """devices: HIP ordinals, one matcher each behind one slideo_group (the reference fans out over the whole machine, the
         global rayon pool of lib.rs:45,174); None = every gfx950 device of the node; `device` = d is short for devices = [d].
         sift = (slideo_sift_config, ratio): the north-star's SIFT + L2 front end instead of the reference's ORB + Hamming
@@ -417,6 +417,10 @@ class HipImageVideoMatcher:
         yuv_sampling = "420" | "422" | "444" | "422_packed" (slideo_group_set_yuv_sampling): where the frames' samples lie — 4:4:4
         for screen recorders, 4:2:2 for ProRes / broadcast recorders, packed 4:2:2 (YUY2, UYVY) for capture cards; every call that
         takes a layout then reads its frames under it; the reference knows BGR only; None = 4:2:0.
+        pixel_format = "bgr" | "rgb" | "bgra" | "rgba" | "argb" | "abgr" | "planar_rgb" | "planar_bgr" | "planar_gbr"
+        (slideo_group_set_pixel_format): how the frames of the BGR door are read.  The frame source then yields frames in that
+        format — [h, w, 3], [h, w, 4] or [3, h, w] — and no swizzle pass runs on the host; page images stay BGR; the reference only
+        ever sees OpenCV's BGR; None = "bgr".
         gate_reference = "previous" or "anchor" (slideo_group_set_gate_reference): with "anchor" a frame is compared with the last
         frame that was flagged, not the frame before it, so a change spread over many frames (a cross-fade, an animated build) is
         still flagged when every decoded frame is fed; with several devices it needs group_gate_order = "chain" — without it the
@@ -441,6 +445,7 @@ class HipImageVideoMatcher:
         self._frame_region = frame_region
         self._yuv_description = tuple(yuv_description) if yuv_description is not None else None
         self._yuv_sampling = yuv_sampling
+        self._pixel_format = pixel_format
         self._gate_reference = gate_reference
         self._gate_settle = tuple(gate_settle) if gate_settle is not None else None
         self._gate_memory = gate_memory
@@ -469,6 +474,8 @@ class HipImageVideoMatcher:
             m.set_yuv_description(*self._yuv_description)
         if self._yuv_sampling is not None:
             m.set_yuv_sampling(self._yuv_sampling)
+        if self._pixel_format is not None:
+            m.set_pixel_format(self._pixel_format)
         if self._frame_mask_scope is not None:
             m.set_frame_mask_scope(self._frame_mask_scope)
         if self._frame_mask is not None:
