@@ -569,6 +569,19 @@ extern "C" {
     pub fn slideo_pixels_to_bgr8(
         m: *mut slideo_matcher, frame: *const u8, width: i32, height: i32, stride_bytes: i32, bgr_out: *mut u8, out_capacity: i64,
     ) -> i32;
+    // frame levels (include/slideo_amd.h "Frame levels"): a per-channel tone table uint8 [3][256] in front of the pipeline, and its learner
+    pub fn slideo_matcher_set_frame_levels(m: *mut slideo_matcher, lut768: *const u8) -> i32;
+    pub fn slideo_matcher_frame_levels(m: *const slideo_matcher, lut768_out: *mut u8, set_out: *mut i32) -> i32;
+    pub fn slideo_group_set_frame_levels(g: *mut slideo_group, lut768: *const u8) -> i32;
+    pub fn slideo_frame_levels_lut(lo: *const i32, hi: *const i32, lut768_out: *mut u8) -> i32;
+    pub fn slideo_levels_bgr8(
+        m: *mut slideo_matcher, bgr: *const u8, width: i32, height: i32, stride_bytes: i32, bgr_out: *mut u8, out_capacity: i64,
+    ) -> i32;
+    pub fn slideo_matcher_levels_begin(m: *mut slideo_matcher) -> i32;
+    pub fn slideo_matcher_levels_end(m: *mut slideo_matcher) -> i32;
+    pub fn slideo_matcher_levels_info(m: *mut slideo_matcher, frames: *mut i64, pixels: *mut i64) -> i32;
+    pub fn slideo_matcher_levels_histogram(m: *mut slideo_matcher, hist768: *mut u64) -> i32;
+    pub fn slideo_matcher_levels_points(m: *mut slideo_matcher, low_ppm: i32, high_ppm: i32, lo: *mut i32, hi: *mut i32) -> i32;
     // frame region (include/slideo_amd.h "Frame region"): frames stand for a rectified quadrilateral of themselves
     pub fn slideo_matcher_set_frame_region(
         m: *mut slideo_matcher,

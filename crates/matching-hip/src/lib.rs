@@ -104,6 +104,11 @@ pub struct HipImageVideoMatcher {
     /// _PLANAR_GBR8.  The frame source then hands out frames in that format; pages stay BGR.  The reference only ever sees
     /// OpenCV's BGR.
     pub pixel_format: i32,
+    /// A per-channel tone table uint8 [3][256] (B, G, R; slideo_group_set_frame_levels) applied to every frame's analysed image as
+    /// the last step in front of the pipeline: what ffi::slideo_frame_levels_lut makes of the points
+    /// ffi::slideo_matcher_levels_points learnt from a dim, low-contrast or colour-cast recording.  Pages are untouched; None:
+    /// off.  The reference analyses the frames as they are.
+    pub frame_levels: Option<Box<[u8; 768]>>,
     /// Which frame a gated frame is compared with (slideo_group_set_gate_reference): ffi::SLIDEO_GATE_PREVIOUS (default: the
     /// frame before, the reference's MarkSimilarIter) or ffi::SLIDEO_GATE_ANCHOR (the last frame that was flagged: a change
     /// spread over many frames is still flagged when every decoded frame is fed).  With several devices it needs
@@ -206,6 +211,7 @@ impl Default for HipImageVideoMatcher {
             yuv_description: (ffi::SLIDEO_YUV_MATRIX_BT601, ffi::SLIDEO_YUV_RANGE_LIMITED, ffi::SLIDEO_YUV_DEPTH_8),
             yuv_sampling: ffi::SLIDEO_YUV_SAMPLING_420,
             pixel_format: ffi::SLIDEO_PIXEL_BGR8,
+            frame_levels: None,
             gate_reference: ffi::SLIDEO_GATE_PREVIOUS,
             gate_settle: (0.0, 0),
             group_gate_order: ffi::SLIDEO_GROUP_GATE_HALO,
@@ -264,6 +270,9 @@ impl<'i> ImageVideoMatcher<'i> for HipImageVideoMatcher {
             }
             if self.pixel_format != ffi::SLIDEO_PIXEL_BGR8 {
                 check(h, ffi::slideo_group_set_pixel_format(h, self.pixel_format));
+            }
+            if let Some(lut) = &self.frame_levels {
+                check(h, ffi::slideo_group_set_frame_levels(h, lut.as_ptr()));
             }
             if self.frame_mask_scope != ffi::SLIDEO_MASK_DETECT {
                 check(h, ffi::slideo_group_set_frame_mask_scope(h, self.frame_mask_scope));

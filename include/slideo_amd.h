@@ -863,6 +863,77 @@ int32_t     slideo_pixel_format_info(int32_t format, int32_t* bytes_per_pixel, i
 int32_t     slideo_pixels_to_bgr8(slideo_matcher* m, const uint8_t* frame, int32_t width, int32_t height, int32_t stride_bytes,
                                   uint8_t* bgr_out, int64_t out_capacity);
 
+/* ---- Frame levels (extension: a per-channel tone table in front of the pipeline, learnt from the frames' own histogram) ---------------
+ * Every door and shaping step puts the right geometry and the right bytes in front of the pipeline; none touches tone.  The verdict
+ * is decided by a re-projection similarity, 1 - RMS / 255 between small images, which ranks the candidates and rejects any at or
+ * below min_similarity.  ORB and RANSAC survive a dim, low-contrast or colour-cast picture (a filmed projection screen, limited
+ * range written into a full-range container, a washed-out capture card); that number does not: a darker look-alike wins the
+ * ranking, and below about a third of the contrast every frame is lost.  One per-channel linear stretch learnt from the frames' own
+ * histogram cures it (docs/EXTENSIONS.md "Frame levels" has the figures).
+ * A matcher carries FRAME LEVELS, a frame setting like the pixel format: a table uint8 [3][256] (B, G, R; 768 bytes, lut[c * 256 +
+ * v]), off by default, under which every call launches, copies and budgets exactly what it did before the table existed.
+ * THE TABLE
+ *   Under levels a frame stands for the image out[y][x][c] = lut[c][in[y][x][c]], where `in` is the unit's BGR image as it was
+ *   before: after the YUV or pixel-format conversion and after the working-size reduce or the frame region's rectify.  The levels
+ *   are the LAST step in front of the unit.  Contract: every call that stages frames returns, bit for bit, what the same call under
+ *   the default returns on those images — slideo_match_frames_*, submit / collect, slideo_changed_mask_* with
+ *   slideo_match_kept_frames (the kept frames are unit images already and are not levelled twice), the gated calls,
+ *   slideo_matcher_observe_frames_*, slideo_matcher_gate_reset_from_frame_*, slideo_match_frames_features_bgr8, SIFT mode, the group's
+ *   forms, both doors: verdicts, candidate traces, changed flags, similarities, small images, gate state and refs, activity and
+ *   content counts.  Pages, the single-image taps (slideo_orb_bgr8, slideo_small_image_bgr8, slideo_reduce_bgr8, slideo_rectify_bgr8,
+ *   the conversion taps slideo_yuv420_to_bgr8 and slideo_pixels_to_bgr8, ...) and slideo_matcher_gate_reset(small) are untouched.
+ *   A device frame is never written: plain device BGR frames, which the default reads in place, are levelled out of the caller's
+ *   memory into the unit's staging, which such frames then budget in gated and observing calls.
+ *   The identity table is stored as off: it reports set == 0 and nothing new launches.
+ * THE STRETCH TABLE  slideo_frame_levels_lut, pure:
+ *   lut[c][x] = clamp(floor((510 * (x - lo[c]) + (hi[c] - lo[c])) / (2 * (hi[c] - lo[c]))), 0, 255)
+ *   the rounded 255 * (x - lo) / (hi - lo) in integers.  It requires 0 <= lo[c] < hi[c] <= 255; (0, 255) gives the identity.
+ * THE LEARNER  A matcher carries a LEVELS HISTOGRAM session beside the activity and the content accumulator: "none", or frames,
+ *   pixels and hist[3][256] as u64 (device) — the number of samples of every value per channel of the OBSERVED IMAGES (exactly the
+ *   activity map's: the BGR images the pipeline would analyse) since levels_begin, across calls.  It holds no frame size: frames of
+ *   any sizes add up.  The four slideo_matcher_observe_frames_* calls feed every open session in one pass; with the levels session
+ *   open alone levels_hist_kernel runs alone.  A device (HIP) error in the middle of a call ends all three.
+ *   Points, per channel c with total = its samples: lo[c] is the value of the sample of ascending rank floor(total * low_ppm / 1e6),
+ *   0-based; hi[c] the value of the sample of rank total - 1 - floor(total * high_ppm / 1e6) (either rank clamped into 0 .. total -
+ *   1).  Computed on the host from the 768 counters, in integers, and reported as they are: slideo_frame_levels_lut is what refuses
+ *   hi <= lo (a constant picture).  A table learnt on levelled frames is not the source's: levels_begin refuses while a table is
+ *   set, and setting a table refuses while the session is open (SLIDEO_ERR_STATE, the rule named).  It is an estimator with an exact
+ *   definition: nothing is installed and no default cut is chosen.  There is no group form of the learner: the pre-pass runs on
+ *   slideo_group_member(g, 0); the table goes to slideo_group_set_frame_levels.
+ * DEPARTURE: the reference analyses the frames as they are.
+ * Out of scope: levels in front of the reduce or the rectify; per-call or time-varying tables; gamma estimation; levels for pages;
+ * 16-bit tables; fusing the table into the converters.
+ * Kernels (csrc/levels.hip.h): levels_kernel, launched iff a table is set, the last launch of the staging — in place on the staged
+ * image, or out of a plain device BGR frame into the staging; levels_hist_kernel, launched iff the session is open.
+ * Every call returns SLIDEO_ERR_INVALID_ARG for a null handle or a null required pointer. */
+/* lut768 == NULL (or the identity table): off.  As slideo_matcher_set_pixel_format: before or after finalize; SLIDEO_ERR_STATE with
+ * units in flight, and while the levels histogram is open; ends the kept frames and resets the gate state to "none". */
+int32_t     slideo_matcher_set_frame_levels(slideo_matcher* m, const uint8_t* lut768);
+/* *set_out = 1 with the table in lut768_out, or 0 with the identity there; lut768_out may be null. */
+int32_t     slideo_matcher_frame_levels(const slideo_matcher* m, uint8_t* lut768_out, int32_t* set_out);
+/* Validates every member (idle, no levels histogram open) before changing any; resets the group's gate state. */
+int32_t     slideo_group_set_frame_levels(slideo_group* g, const uint8_t* lut768);
+/* Pure: the stretch table of the rule above.  SLIDEO_ERR_INVALID_ARG unless 0 <= lo[c] < hi[c] <= 255 for c = 0, 1, 2 (B, G, R);
+ * slideo_last_error(NULL) then names the channel. */
+int32_t     slideo_frame_levels_lut(const int32_t* lo /*3*/, const int32_t* hi /*3*/, uint8_t* lut768_out);
+/* Tap: ONE host BGR image (rows stride_bytes apart, height * stride_bytes readable) under the matcher's table -> width * height * 3
+ * bytes at stride 3 * width (SLIDEO_ERR_CAPACITY when out_capacity is smaller), through levels_kernel as a frame's unit image goes.
+ * Off: a row-by-row copy. */
+int32_t     slideo_levels_bgr8(slideo_matcher* m, const uint8_t* bgr, int32_t width, int32_t height, int32_t stride_bytes, uint8_t* bgr_out,
+                               int64_t out_capacity);
+/* Idle matcher (SLIDEO_ERR_STATE otherwise, and while a table is set).  Afterwards the histogram is empty: frames 0, pixels 0.  May be
+ * called before any page is added and before finalize. */
+int32_t     slideo_matcher_levels_begin(slideo_matcher* m);
+/* Idle matcher.  The state "none"; the session's device buffers are released.  Fine when the state is "none" already. */
+int32_t     slideo_matcher_levels_end(slideo_matcher* m);
+/* The observed frames and their pixels in all.  SLIDEO_ERR_STATE in the state "none". */
+int32_t     slideo_matcher_levels_info(slideo_matcher* m, int64_t* frames, int64_t* pixels);
+/* Idle matcher.  hist768[c * 256 + v] (the tap the tests hold the kernel to).  SLIDEO_ERR_STATE without an observed frame. */
+int32_t     slideo_matcher_levels_histogram(slideo_matcher* m, uint64_t* hist768);
+/* Idle matcher.  The points of the definition.  SLIDEO_ERR_STATE without an observed frame; SLIDEO_ERR_INVALID_ARG for low_ppm or
+ * high_ppm outside 0..1000000. */
+int32_t     slideo_matcher_levels_points(slideo_matcher* m, int32_t low_ppm, int32_t high_ppm, int32_t* lo /*3*/, int32_t* hi /*3*/);
+
 /* ---- Working size (extension: the reference analyses every frame at the size it arrives in) ---------------------------------
  * A matcher carries a working size (max_w, max_h); (0, 0) = none, the default.  While one is set, a frame of w x h with
  * w <= max_w and h <= max_h is untouched; any other frame STANDS FOR the image cv::resize(frame, Size(dw, dh), 0, 0, INTER_AREA)

@@ -142,6 +142,34 @@ def pixel_format_info(fmt):
     return bpp.value, planes.value
 
 
+def _levels_table(lut):
+    """A frame levels table as contiguous uint8 [3, 256] (B, G, R); ValueError for another shape, dtype or range."""
+    a = np.asarray(lut)
+    if a.shape not in ((3, 256), (768,)):
+        raise ValueError("frame levels: expected a table of shape [3, 256] (B, G, R), got %s" % (a.shape,))
+    if a.dtype != np.uint8:
+        if not np.issubdtype(a.dtype, np.integer) or a.min() < 0 or a.max() > 255:
+            raise ValueError("frame levels: the table's entries are integers in 0..255")
+    return np.ascontiguousarray(a.reshape(3, 256), np.uint8)
+
+
+def frame_levels_lut(lo, hi):
+    """slideo_frame_levels_lut: the stretch table uint8 [3, 256] (B, G, R) of the points lo, hi (three each, or one for all three):
+    lut[c][x] = clamp(floor((510 (x - lo) + (hi - lo)) / (2 (hi - lo))), 0, 255).  ValueError unless 0 <= lo < hi <= 255."""
+    lo3 = [int(v) for v in (lo if np.ndim(lo) else [lo] * 3)]
+    hi3 = [int(v) for v in (hi if np.ndim(hi) else [hi] * 3)]
+    if len(lo3) != 3 or len(hi3) != 3:
+        raise ValueError("frame_levels_lut: three lo and three hi (B, G, R), got %d and %d" % (len(lo3), len(hi3)))
+    for c in range(3):
+        if not 0 <= lo3[c] < hi3[c] <= 255:
+            raise ValueError("frame_levels_lut: channel %d has lo %d, hi %d: 0 <= lo < hi <= 255" % (c, lo3[c], hi3[c]))
+    out = np.empty((3, 256), np.uint8)
+    rc = lib().slideo_frame_levels_lut((C.c_int32 * 3)(*lo3), (C.c_int32 * 3)(*hi3), _p(out))
+    if rc != OK:
+        raise SlideoError(rc, lib().slideo_last_error(None).decode())
+    return out
+
+
 def yuv_format_sampling(fmt):
     """The sampling name a format is read under."""
     if fmt in YUV420_FORMATS:
@@ -272,6 +300,9 @@ EXPORTS = [
     "slideo_matcher_set_yuv_sampling", "slideo_matcher_yuv_sampling", "slideo_group_set_yuv_sampling", "slideo_yuv_layout_packed",
     "slideo_matcher_set_pixel_format", "slideo_matcher_pixel_format", "slideo_group_set_pixel_format", "slideo_pixel_format_info",
     "slideo_pixels_to_bgr8",
+    "slideo_matcher_set_frame_levels", "slideo_matcher_frame_levels", "slideo_group_set_frame_levels", "slideo_frame_levels_lut",
+    "slideo_levels_bgr8", "slideo_matcher_levels_begin", "slideo_matcher_levels_end", "slideo_matcher_levels_info",
+    "slideo_matcher_levels_histogram", "slideo_matcher_levels_points",
     "slideo_matcher_activity_begin", "slideo_matcher_activity_end", "slideo_matcher_observe_frames_bgr8", "slideo_matcher_observe_frames_yuv420",
     "slideo_matcher_observe_frames_bgr8_dev", "slideo_matcher_observe_frames_yuv420_dev", "slideo_matcher_activity_info",
     "slideo_matcher_activity_counts", "slideo_matcher_activity_mask",
@@ -439,6 +470,18 @@ def lib():
             L.slideo_matcher_content_info.argtypes = [vp, vp, vp, vp, vp]
             L.slideo_matcher_content_counts.argtypes = [vp, vp, i64, vp, vp, vp]
             L.slideo_matcher_content_box.argtypes = [vp, i32, i32, vp, vp, vp, i64]
+        if hasattr(L, "slideo_matcher_set_frame_levels"):
+            vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
+            L.slideo_matcher_set_frame_levels.argtypes = [vp, vp]
+            L.slideo_matcher_frame_levels.argtypes = [vp, vp, vp]
+            L.slideo_group_set_frame_levels.argtypes = [vp, vp]
+            L.slideo_frame_levels_lut.argtypes = [vp, vp, vp]
+            L.slideo_levels_bgr8.argtypes = [vp, vp, i32, i32, i32, vp, i64]
+            L.slideo_matcher_levels_begin.argtypes = [vp]
+            L.slideo_matcher_levels_end.argtypes = [vp]
+            L.slideo_matcher_levels_info.argtypes = [vp, vp, vp]
+            L.slideo_matcher_levels_histogram.argtypes = [vp, vp]
+            L.slideo_matcher_levels_points.argtypes = [vp, i32, i32, vp, vp]
         if hasattr(L, "slideo_matcher_set_gate_reference"):
             vp, i32, u32 = C.c_void_p, C.c_int32, C.c_uint32
             L.slideo_matcher_set_gate_reference.argtypes = [vp, u32]
@@ -811,6 +854,25 @@ class _FrameCalls:
         if rc != OK:
             raise SlideoError(rc, "pixel_format")
         return v.value
+
+    # frame levels (include/slideo_amd.h "Frame levels"): a per-channel tone table, the last step in front of the unit's image
+    def set_frame_levels(self, lut=None):
+        """lut: uint8 [3, 256] (B, G, R), or None (= the identity) for off.  Every frame call then analyses lut[c][image]; pages and
+        single-image taps are untouched.  The matcher must be idle and its levels histogram closed; ends the kept frames and resets
+        the gate state."""
+        if lut is not None:
+            lut = _levels_table(lut)
+        self._check(getattr(lib(), self._SETS + "set_frame_levels")(self._h, _p(lut) if lut is not None else None))
+
+    def frame_levels(self):
+        """The table uint8 [3, 256] in force, or None when off (a Group: member 0's)."""
+        if not hasattr(lib(), "slideo_matcher_frame_levels"):       # (SLIDEO_LIB_PATH may name an older build: tools/ab_libs.sh)
+            return None
+        out, on = np.empty((3, 256), np.uint8), C.c_int32()
+        rc = lib().slideo_matcher_frame_levels(self._mask_owner(), _p(out), C.byref(on))
+        if rc != OK:
+            raise SlideoError(rc, "frame_levels")
+        return out if on.value else None
 
     def _mask_owner(self):
         """The matcher handle the mask's getters read (a group's members agree: member 0)."""
@@ -1229,6 +1291,51 @@ class Matcher(_FrameCalls):
         self._check(lib().slideo_match_frames_submit_yuv420_dev(self._h, n, C.c_void_p(dev_ptr), w, h, C.byref(layout),
                                                                 C.c_int64(frame_stride), C.c_void_p(stream), C.byref(t)))
         return (t.value, n)
+
+    # ---- frame levels: the tap and the learner (include/slideo_amd.h "Frame levels") ----------
+    def levels_bgr(self, image, stride=None):
+        """One host BGR image [h, w, 3] under the table in force (the tap; off: the image itself).  With `stride`: a (flat buffer, w,
+        h) triple whose rows lie `stride` bytes apart (height * stride bytes are read)."""
+        if stride is None:
+            image = _img3(image)
+            h, w, _ = image.shape
+            stride = w * 3
+        else:
+            image, w, h = image
+            image = np.ascontiguousarray(image, np.uint8)
+            if image.size < h * int(stride):
+                raise ValueError("levels_bgr: the buffer holds %d bytes, height * stride is %d" % (image.size, h * int(stride)))
+        out = np.empty((h, w, 3), np.uint8)
+        self._check(lib().slideo_levels_bgr8(self._h, _p(image), w, h, int(stride), _p(out), C.c_int64(out.size)))
+        return out
+
+    def levels_begin(self):
+        """An empty levels histogram; observe_frames* feed it.  Refused while a table is set."""
+        self._check(lib().slideo_matcher_levels_begin(self._h))
+
+    def levels_end(self):
+        self._check(lib().slideo_matcher_levels_end(self._h))
+
+    def levels_info(self):
+        """-> {frames, pixels}"""
+        fr, px = C.c_int64(), C.c_int64()
+        self._check(lib().slideo_matcher_levels_info(self._h, C.byref(fr), C.byref(px)))
+        return {"frames": fr.value, "pixels": px.value}
+
+    def levels_histogram(self):
+        """-> uint64 [3, 256] (B, G, R): the samples of every value of the observed images"""
+        out = np.empty((3, 256), np.uint64)
+        self._check(lib().slideo_matcher_levels_histogram(self._h, _p(out)))
+        return out
+
+    def levels_points(self, low, high):
+        """low, high: the shares cut at either end, floats in [0, 1], rounded to parts per million -> (lo [3], hi [3]) as lists"""
+        for name, v in (("low", low), ("high", high)):
+            if not 0.0 <= float(v) <= 1.0:
+                raise ValueError("levels_points: %s = %r outside [0, 1]" % (name, v))
+        lo, hi = (C.c_int32 * 3)(), (C.c_int32 * 3)()
+        self._check(lib().slideo_matcher_levels_points(self._h, int(round(float(low) * 1000000)), int(round(float(high) * 1000000)), lo, hi))
+        return list(lo), list(hi)
 
     def pixels_to_bgr(self, frame, stride=None):
         """The BGR image (h, w, 3) one host frame stands for under the pixel format in force (the conversion tap).  frame: the

@@ -457,6 +457,12 @@ int32_t slideo_group_set_yuv_sampling(slideo_group* g, int32_t sampling) {
 int32_t slideo_group_set_pixel_format(slideo_group* g, int32_t format) {
     return group_set(g, SET_YUV_DESCRIPTION, [&](const FrameSettings& s) { return propose_pixel_format(s, format); });
 }
+// (a member whose levels histogram is open refuses, before any member changes)
+int32_t slideo_group_set_frame_levels(slideo_group* g, const uint8_t* lut768) {
+    bool open = false;
+    if (g) for (const slideo_matcher* m : g->members) open |= m->levels.on;
+    return group_set(g, SET_YUV_DESCRIPTION, [&](const FrameSettings& s) { return propose_frame_levels(s, lut768, open); });
+}
 
 // (the group's own rule first: ANCHOR needs a group of one member or the gate order CHAIN, and a refused call changes no member)
 int32_t slideo_group_set_gate_reference(slideo_group* g, uint32_t ref) {

@@ -154,6 +154,12 @@ void settings_commit(slideo_matcher* m, Setting what, FrameSettings next, const 
     }
     if (new_mask) m->d_mask_pyr = std::move(pyr);
     if (map_w.p) m->d_gate_w = std::move(map_w);
+    // a new levels table's device copy (the matcher is idle: no kernel is reading the one before)
+    if (next.levels.set && (!m->fs.levels.set || std::memcmp(next.levels.lut, m->fs.levels.lut, 768) != 0)) {
+        HIP_CHECK(hipSetDevice(m->device));
+        m->d_levels.reserve(768);
+        HIP_CHECK(hipMemcpy(m->d_levels.p, next.levels.lut, 768, hipMemcpyHostToDevice));
+    }
     m->fs = next;
     const SettingEnds& ends = SETTING_ENDS[what];
     if (ends.kept) m->kept.valid = false;
@@ -173,7 +179,7 @@ DevFrames stage_frames(slideo_matcher* m, Slot& S, const FrameSrc& src, int firs
     const uint8_t* p = src.p + (int64_t)first * src.frame_stride;
     const FramePlan& P = src.plan;      // (a tap's unresolved plan is PREP_NONE: uw, uh are read under `pre` alone)
     const bool pre = P.prep != PREP_NONE;                        // a kernel stands between the BGR view at source size and the unit's image
-    if (src.on_device && !src.converted() && !pre) return DevFrames{p, src.w, src.h, src.stride, src.frame_stride};
+    if (src.on_device && !src.kernel_in_front()) return DevFrames{p, src.w, src.h, src.stride, src.frame_stride};
     const int uw = P.uw, uh = P.uh;
     const int64_t fb = (int64_t)src.h * src.stride;              // one frame of the BGR view at source size (stride 3w for YUV frames)
     const int64_t ub = pre ? (int64_t)uh * uw * 3 : fb;          // one frame of the unit's BGR image
@@ -209,9 +215,15 @@ DevFrames stage_frames(slideo_matcher* m, Slot& S, const FrameSrc& src, int firs
         else launch_pixels_to_bgr(src.pixel_format, p, fs, src.src_stride, src.w, src.h, n, bgr, S.st);
         p = bgr; fs = fb;
     }
-    if (!pre) return DevFrames{stage, src.w, src.h, src.stride, fb};
+    // frame levels: the last step in front of the unit, in place on the staged image — but plain device BGR frames, which nothing has
+    // staged yet, out of the caller's memory (never written) into the stage, rows as far apart as the caller's
+    if (!pre) {
+        if (src.levels) launch_levels(m, p, fs, src.stride, stage, fb, src.stride, src.w, src.h, n, S.st);
+        return DevFrames{stage, src.w, src.h, src.stride, fb};
+    }
     if (P.prep == PREP_RECTIFY) launch_rectify(m->fs.region, p, fs, src.stride, n, stage, S.st);
     else launch_reduce(m, p, fs, src.stride, src.w, src.h, uw, uh, n, stage, S.st);
+    if (src.levels) launch_levels(m, stage, ub, uw * 3, stage, ub, uw * 3, uw, uh, n, S.st);
     return DevFrames{stage, uw, uh, uw * 3, ub};
 }
 
@@ -1242,6 +1254,7 @@ int32_t slideo_pixels_to_bgr8(slideo_matcher* m, const uint8_t* frame, int32_t w
     if (!frame || !bgr_out) fail(SLIDEO_ERR_INVALID_ARG, "null frame/bgr_out");
     FrameSrc img = FrameSrc::bgr8(frame, false, width, height, stride_bytes, -1);
     img.describe(m->fs);
+    img.levels = false;                             // (the conversion's image: the frame levels come behind it, slideo_levels_bgr8)
     validate_frames(img);
     const size_t row = (size_t)width * 3, fb = row * (size_t)height;
     if ((int64_t)fb > out_capacity) fail(SLIDEO_ERR_CAPACITY, "the BGR image needs %zu bytes", fb);
@@ -1250,6 +1263,52 @@ int32_t slideo_pixels_to_bgr8(slideo_matcher* m, const uint8_t* frame, int32_t w
         return SLIDEO_OK;
     }
     tap_staged(m, img, bgr_out, (int64_t)fb);
+    API_CATCH(m)
+}
+
+// ---- Frame levels (include/slideo_amd.h "Frame levels"; the learner: stage_activity.hip) -----------------------------------------
+
+int32_t slideo_matcher_set_frame_levels(slideo_matcher* m, const uint8_t* lut768) {
+    return matcher_set(m, SET_YUV_DESCRIPTION, [&](const FrameSettings& s) { return propose_frame_levels(s, lut768, m->levels.on); });
+}
+
+int32_t slideo_matcher_frame_levels(const slideo_matcher* m, uint8_t* lut768_out, int32_t* set_out) {
+    if (!m || !set_out) return SLIDEO_ERR_INVALID_ARG;
+    const FrameLevels& L = m->fs.levels;
+    *set_out = L.set ? 1 : 0;
+    if (lut768_out)
+        for (int i = 0; i < 768; ++i) lut768_out[i] = L.set ? L.lut[i] : (uint8_t)(i & 255);      // (off: the identity)
+    return SLIDEO_OK;
+}
+
+int32_t slideo_frame_levels_lut(const int32_t* lo, const int32_t* hi, uint8_t* lut768_out) {
+    API_TRY
+    if (!lo || !hi || !lut768_out) fail(SLIDEO_ERR_INVALID_ARG, "null lo/hi/lut768_out");
+    frame_levels_lut(lo, hi, lut768_out);
+    API_CATCH(nullptr)
+}
+
+// Tap: one host BGR image under the matcher's table, staged and levelled as a frame's unit image is (in place on the slot's stage)
+int32_t slideo_levels_bgr8(slideo_matcher* m, const uint8_t* bgr, int32_t width, int32_t height, int32_t stride_bytes, uint8_t* bgr_out,
+                           int64_t out_capacity) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    if (!bgr || !bgr_out) fail(SLIDEO_ERR_INVALID_ARG, "null bgr/bgr_out");
+    FrameSrc img = FrameSrc::image(bgr, width, height, stride_bytes);
+    validate_frames(img);
+    img.levels = m->fs.levels.set;                  // (the image is the unit's already: no pixel format, no working size, no region)
+    const size_t row = (size_t)width * 3, fb = row * (size_t)height;
+    if ((int64_t)fb > out_capacity) fail(SLIDEO_ERR_CAPACITY, "the levelled image needs %zu bytes", fb);
+    if (!img.levels) {                              // off: the image itself, row by row
+        for (int y = 0; y < height; ++y) std::memcpy(bgr_out + (size_t)y * row, bgr + (size_t)y * stride_bytes, row);
+        return SLIDEO_OK;
+    }
+    HIP_CHECK(hipSetDevice(m->device));
+    require_idle(m);
+    Slot& S = m->slots[0];
+    const DevFrames f = stage_frames(m, S, img, 0, 1);
+    HIP_CHECK(hipMemcpy2DAsync(bgr_out, row, f.p, (size_t)f.stride, row, (size_t)height, hipMemcpyDeviceToHost, S.st));
+    HIP_CHECK(hipStreamSynchronize(S.st));
     API_CATCH(m)
 }
 

@@ -208,6 +208,7 @@ int32_t slideo_yuv420_to_bgr8(slideo_matcher* m, const uint8_t* frame, int32_t w
     if (!frame || !bgr_out) fail(SLIDEO_ERR_INVALID_ARG, "null frame/bgr_out");
     FrameSrc img = FrameSrc::yuv420(frame, false, width, height, layout, -1);
     img.describe(m->fs);
+    img.levels = false;                             // (the conversion's image: the frame levels come behind it, slideo_levels_bgr8)
     validate_frames(img);
     const size_t fb = (size_t)width * height * 3;
     if ((int64_t)fb > out_capacity) fail(SLIDEO_ERR_CAPACITY, "the BGR image needs %zu bytes", fb);

@@ -1,5 +1,5 @@
 // frame_settings.h — the frame settings of a matcher as ONE record (include/slideo_amd.h "Working size", "Frame region", "Frame mask",
-// "Frame mask scope", "Direct page look-up", "Direct look-up scope", "YUV colour description", "YUV sampling", "Gate reference", "Gate settle", "Gate memory", "Frame pixel format"): the record, every setter's proposal with its range checks, the
+// "Frame mask scope", "Direct page look-up", "Direct look-up scope", "YUV colour description", "YUV sampling", "Gate reference", "Gate settle", "Gate memory", "Frame pixel format", "Frame levels"): the record, every setter's proposal with its range checks, the
 // rules between settings, what a change of each ends.  Plain C++, no HIP include (tools/frame_settings_hostcheck.cpp walks it on the
 // host); the device buffers a setting owns are the matcher's (runtime.hpp).  A change takes ONE path: settings_commit (capi_runtime.hip).
 #pragma once
@@ -35,6 +35,9 @@ struct YuvDesc {
     bool is_default() const { return matrix == SLIDEO_YUV_MATRIX_BT601 && range == SLIDEO_YUV_RANGE_LIMITED && depth == SLIDEO_YUV_DEPTH_8; }
     int bytes_per_sample() const { return depth == SLIDEO_YUV_DEPTH_8 ? 1 : 2; }
 };
+// The per-channel tone table of "Frame levels": lut[c * 256 + v], c = 0, 1, 2 for B, G, R (the matcher's d_levels holds its copy on
+// the device); set false: off, and the identity table is stored as off
+struct FrameLevels { bool set = false; uint8_t lut[768] = {}; };
 
 struct FrameSettings {
     int work_w = 0, work_h = 0;                       // frames beyond it are reduced in front of the pipeline; 0, 0 = none
@@ -47,6 +50,7 @@ struct FrameSettings {
     uint32_t direct_scope = SLIDEO_DIRECT_WHOLE;      // VALID = the look-up over the gate's valid pixels
     YuvDesc yuv;                                      // 4:2:0 frames stand for the BGR image under it (BGR calls never look at it)
     int pixel_format = SLIDEO_PIXEL_BGR8;             // how every *_bgr8 frame call reads its frames (YUV calls never look at it)
+    FrameLevels levels;                               // the unit's BGR image goes through it, the last step in front of the unit
     uint32_t gate_ref = SLIDEO_GATE_PREVIOUS;         // what a gated frame is compared with: the frame before it, or the last changed one (ANCHOR)
     // the gate settle, part of the gate-reference setting ("Gate settle"): under ANCHOR a frame away from the anchor is matched once it
     // is within settle_similarity of the frame before it, or after settle_max_defer deferred frames; 0: off
@@ -188,6 +192,66 @@ inline int64_t pixel_format_validate(int format, int w, int h, int stride, int64
              stride, (long long)span);
     }
     return span;
+}
+
+// ---- the frame levels (include/slideo_amd.h "Frame levels") ---------------------------------------------------------------------------
+inline bool frame_levels_identity(const uint8_t* lut768) {
+    for (int i = 0; i < 768; ++i) if (lut768[i] != (uint8_t)(i & 255)) return false;
+    return true;
+}
+// The table commits under SET_YUV_DESCRIPTION like the pixel format: it ends the kept frames and resets the gate.  lut768 null, or
+// the identity: off.  session_open: the matcher's levels histogram is open (a table learnt on levelled frames is not the source's)
+inline FrameSettings propose_frame_levels(FrameSettings s, const uint8_t* lut768, bool session_open) {
+    if (session_open)
+        fail(SLIDEO_ERR_STATE, "frame levels: the levels histogram is open, and a table learnt on levelled frames is not the source's "
+                               "(slideo_matcher_levels_end first)");
+    s.levels = FrameLevels{};
+    if (!lut768 || frame_levels_identity(lut768)) return s;
+    s.levels.set = true;
+    for (int i = 0; i < 768; ++i) s.levels.lut[i] = lut768[i];
+    return s;
+}
+// The stretch table of the points (lo, hi) per channel: lut[c][x] = clamp(floor((510 (x - lo) + (hi - lo)) / (2 (hi - lo))), 0, 255),
+// the rounded 255 (x - lo) / (hi - lo) in integers; (0, 255) is the identity
+inline void frame_levels_lut(const int32_t* lo, const int32_t* hi, uint8_t* lut768) {
+    static const char* const names[3] = {"B", "G", "R"};
+    for (int c = 0; c < 3; ++c)
+        if (lo[c] < 0 || hi[c] > 255 || lo[c] >= hi[c])
+            fail(SLIDEO_ERR_INVALID_ARG, "frame levels: channel %d (%s) has lo %d, hi %d: 0 <= lo < hi <= 255", c, names[c], lo[c], hi[c]);
+    for (int c = 0; c < 3; ++c) {
+        const int d = hi[c] - lo[c];
+        for (int x = 0; x < 256; ++x) {
+            const int num = 510 * (x - lo[c]) + d;             // (floor of a negative quotient: below 0 either way)
+            const int v = num < 0 ? 0 : num / (2 * d);
+            lut768[c * 256 + x] = (uint8_t)(v > 255 ? 255 : v);
+        }
+    }
+}
+// The points of a histogram hist[c * 256 + v] at (low_ppm, high_ppm): per channel, with total its samples, lo is the value of the
+// sample of ascending rank floor(total * low_ppm / 1e6) (0-based) and hi that of rank total - 1 - floor(total * high_ppm / 1e6);
+// reported as they are (frame_levels_lut is what refuses hi <= lo).  A channel without samples: STATE
+constexpr int LEVELS_MAX_PPM = 1000000;
+inline uint64_t levels_ppm_rank(uint64_t total, uint64_t ppm) {           // floor(total * ppm / 1e6) without a 128-bit product
+    return total / 1000000u * ppm + total % 1000000u * ppm / 1000000u;
+}
+inline int levels_value_at(const uint64_t* hist256, uint64_t rank) {      // the value of the sample of ascending rank `rank` < total
+    uint64_t below = 0;
+    for (int v = 0; v < 256; ++v) { below += hist256[v]; if (rank < below) return v; }
+    return 255;
+}
+inline void levels_points(const uint64_t* hist768, int low_ppm, int high_ppm, int32_t* lo, int32_t* hi) {
+    if (low_ppm < 0 || low_ppm > LEVELS_MAX_PPM || high_ppm < 0 || high_ppm > LEVELS_MAX_PPM)
+        fail(SLIDEO_ERR_INVALID_ARG, "levels_points: low_ppm %d, high_ppm %d outside 0..%d", low_ppm, high_ppm, LEVELS_MAX_PPM);
+    for (int c = 0; c < 3; ++c) {
+        const uint64_t* h = hist768 + c * 256;
+        uint64_t total = 0;
+        for (int v = 0; v < 256; ++v) total += h[v];
+        if (total == 0) fail(SLIDEO_ERR_STATE, "the levels histogram has observed no frame");
+        const uint64_t rl = std::min(levels_ppm_rank(total, (uint64_t)low_ppm), total - 1);
+        const uint64_t cut = std::min(levels_ppm_rank(total, (uint64_t)high_ppm), total - 1);
+        lo[c] = levels_value_at(h, rl);
+        hi[c] = levels_value_at(h, total - 1 - cut);
+    }
 }
 
 inline FrameSettings propose_gate_reference(FrameSettings s, uint32_t ref) {

@@ -7,7 +7,7 @@
 //                      (FrameSrc -> FramePlan) and staged (-> DevFrames), unit submit / collect, the drivers of the frame calls
 //                      (pipeline, submit, collect: plain and gated) and their entry points
 //   stage_orb.hip      ORB stage drivers          (kernels: orb.hip.h, yuv420.hip.h, yuv_sampling.hip.h, pixel_format.hip.h, reduce.hip.h,
-//                                                 frame_region.hip.h, frame_mask.hip.h)
+//                                                 frame_region.hip.h, frame_mask.hip.h, levels.hip.h levels_kernel)
 //   stage_knn.hip      index build + k-NN stage   (kernels: knn.hip.h, knn_tile.hip.h, knn_l2.hip.h, knn_lsh.hip.h)
 //   stage_verify.hip   vote .. verdict, small img (kernels: verify.hip.h, homography.hip.h)
 //   stage_sift.hip     SIFT stage + entry points  (kernels: sift.hip.h)
@@ -16,7 +16,8 @@
 //   stage_direct.hip   direct page look-up: the page operand, a gated unit's look-up, its entry points (kernels: direct.hip.h)
 //   stage_ssd_table.hip  the SSD-table engine under the direct page look-up and the gate reference ANCHOR: the centred operand, the
 //                      table of dot products on the int8 matrix cores, the taps' validity map (kernels: ssd_table.hip.h)
-//   stage_activity.hip frame activity map: the accumulator, the observe driver, its entry points (kernels: activity.hip.h)
+//   stage_activity.hip frame activity map: the accumulator, the observe driver, its entry points (kernels: activity.hip.h); the levels
+//                      histogram's session and entry points (kernel: levels.hip.h levels_hist_kernel)
 //   stage_content.hip  frame content box: the content accumulator, its launch behind the observe driver, its entry points (kernels: content.hip.h)
 //   stage_gate_anchor.hip  gate reference ANCHOR and its gate settle: a gated unit's pair table, carried SSDs, walk and state, the two
 //                      settings and the taps (kernels: gate_anchor.hip.h)
@@ -117,18 +118,27 @@ struct FrameSrc {
     int pixel_format = SLIDEO_PIXEL_BGR8;
     int src_stride = 0;
     int64_t pix_span = 0;
+    // (derived) the matcher's frame levels apply: the unit's image goes through the table as the last step (describe; analysed
+    // frames are unit images already, levelled when they were kept)
+    bool levels = false;
 
     void describe(const FrameSettings& fs) {
         bps = fs.yuv.bytes_per_sample(); sampling = fs.yuv.sampling;
         pixel_format = yuv || analysed ? SLIDEO_PIXEL_BGR8 : fs.pixel_format;
+        levels = fs.levels.set && !analysed;
     }
     // a converter stands in front of the unit's BGR image: the frames are not read as they lie
     bool converted() const { return yuv != nullptr || pixel_format != SLIDEO_PIXEL_BGR8; }
     int64_t src_span() const { return yuv ? yuv_span : pix_span; }      // bytes of one frame a converter reads
+    // a kernel stands in front of the unit's image (a converter, the reduce or the rectify, the levels): device frames are not the
+    // unit's image as they lie in the caller's memory
+    bool kernel_in_front() const { return converted() || plan.prep != PREP_NONE || levels; }
 
     // per frame, the staging in front of the unit's BGR image: 1.5 B per pixel for 4:2:0 frames, 3 B in 16-bit containers, 2 * bps
     // under both 4:2:2 forms and 3 * bps under 4:4:4 ("YUV sampling"; BGR calls keep their unit sizes); under a pixel format a HOST
-    // frame's span (a device frame is converted out of the caller's memory: nothing extra);
+    // frame's span (a device frame is converted out of the caller's memory: nothing extra); under frame levels a plain device BGR
+    // frame is no longer the caller's own memory below: the table is applied out of it into the unit image (which sub_batch_for
+    // counts for every frame) or the gate staging;
     // a reducing or rectifying call: the uploaded source frame (host sources) and the source-sized BGR image of a 4:2:0 frame;
     // gated (a gated call, include/slideo_amd.h "Changed-frame gate"): + the gate staging — the BGR unit image of every frame that
     // is not the caller's own device memory — and the frame's small image (gate_small: at most 3 * small_area bytes) and gate record
@@ -138,7 +148,7 @@ struct FrameSrc {
         const size_t yb = (sampling == SLIDEO_YUV_SAMPLING_420 ? px * 3 / 2 : sampling == SLIDEO_YUV_SAMPLING_444 ? px * 3 : px * 2) * (size_t)bps;
         const size_t cb = yuv ? yb : (size_t)pix_span;              // the frame a converter reads (0: plain BGR, no converter)
         size_t b = !pre ? (yuv || !on_device ? cb : 0) : (on_device ? 0 : (converted() ? cb : (size_t)h * stride)) + (converted() ? px * 3 : 0);
-        if (gate_small) b += (on_device && !converted() && !pre ? 0 : (size_t)plan.uw * plan.uh * 3) + gate_small + 32;
+        if (gate_small) b += (on_device && !kernel_in_front() ? 0 : (size_t)plan.uw * plan.uh * 3) + gate_small + 32;
         return b;
     }
 
@@ -427,6 +437,13 @@ struct slideo_matcher {
     struct Content { bool on = false; int aw = 0, ah = 0, level = 0; int64_t frames = 0; } content;
     slideo::DevBuf d_cnt_lit, d_cnt_fill;
 
+    // frame levels (include/slideo_amd.h "Frame levels"): the device copy of fs.levels.lut (written by settings_commit while the
+    // matcher is idle), and the levels histogram — "none" (on false) or the per-channel counts (u64 [3][256], d_lv_hist) of `frames`
+    // analysed images of `pixels` pixels in all, of any sizes.  The observe calls feed it beside the other two accumulators
+    slideo::DevBuf d_levels;
+    struct Levels { bool on = false; int64_t frames = 0, pixels = 0; } levels;
+    slideo::DevBuf d_lv_hist;
+
     // direct page look-up (include/slideo_amd.h "Direct page look-up"): built at the first use with fs.direct_t > 0 after finalize, the
     // deck's size classes
     bool direct_built = false;
@@ -484,7 +501,8 @@ void settings_commit(slideo_matcher* m, Setting what, FrameSettings next, const 
 // S.d_stage on S.st (device frames of another pixel format out of the caller's memory); a source the working size reduces: host frames into S.d_yuv, 4:2:0 frames converted into S.d_full, then
 // reduced into S.d_stage; under a frame region the same with the rectify in place of the reduce (device BGR frames are read in the
 // caller's memory); the DevFrames are then plan.uw x plan.uh.  Every write of a slot's d_stage goes through here (page ingest through its staging buffer) and ends the
-// frames slideo_changed_mask_bgr8 kept for slideo_match_kept_frames.
+// frames slideo_changed_mask_bgr8 kept for slideo_match_kept_frames.  Under frame levels (src.levels) the table is applied last, in
+// place on what was staged; a plain device BGR source, otherwise returned as it is, is levelled out of the caller's memory into the stage.
 // into: the staging buffer in place of S.d_stage (a gated unit's S.d_gstage; the kept frames of a mask call then stay).
 DevFrames stage_frames(slideo_matcher* m, Slot& S, const FrameSrc& src, int first, int n, hipStream_t cs = nullptr, DevBuf* into = nullptr);
 // stage_content.hip: content_kernel over a staged block of n frames into m's content accumulator (m->content.on; d_cnt_lit holds
@@ -549,6 +567,10 @@ void launch_yuv420_to_bgr(const YuvDesc& desc, const uint8_t* src, int64_t src_f
 // n frames under the pixel format `format` (not SLIDEO_PIXEL_BGR8; a layout pixel_format_validate accepted, rows `stride` and frames
 // src_fs apart) -> BGR8 at dst, stride 3w, frame stride 3wh: pixels_to_bgr_kernel (pixel_format.hip.h)
 void launch_pixels_to_bgr(int format, const uint8_t* src, int64_t src_fs, int stride, int w, int h, int n, uint8_t* dst, hipStream_t st);
+// n BGR8 images of w x h through the matcher's levels table (m->d_levels; fs.levels.set), src == dst with equal strides: in place:
+// levels_kernel (levels.hip.h)
+void launch_levels(slideo_matcher* m, const uint8_t* src, int64_t src_fs, int src_stride, uint8_t* dst, int64_t dst_fs, int dst_stride, int w, int h,
+                   int n, hipStream_t st);
 
 // ---- stage_knn.hip --------------------------------------------------------------------------------
 // FlannMatcher::new (mo/flann.rs:65-71) for the Hamming index: uploads the M packed rows, collapses equal rows, builds the

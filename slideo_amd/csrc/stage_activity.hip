@@ -2,9 +2,12 @@
 // observe driver (kernels: activity.hip.h).  Observing stages frames as every frame call does (stage_frames) but into a buffer of
 // the accumulator's own, and touches nothing else of the matcher: no setting, no gate state, not the frames a mask call kept.
 // The observe driver feeds every open accumulator: the activity map's here and, through content_launch (stage_content.hip), the
-// content box's (include/slideo_amd.h "Frame content box"), from the same staged block.
+// content box's (include/slideo_amd.h "Frame content box"), from the same staged block; and the levels histogram's ("Frame levels"),
+// whose entry points and kernel (levels.hip.h levels_hist_kernel) live here too.
 #include "runtime.hpp"
 #include "activity.hip.h"
+#define LEVELS_HIST_KERNEL       // (levels_kernel is stage_orb.hip's)
+#include "levels.hip.h"
 
 #include <climits>
 
@@ -15,6 +18,7 @@ namespace slideo {
 namespace {
 
 constexpr int ACT_MAX_BLOCK = 4096;                         // frames per block (the staging kernels' grid.z; sub_batch_for's cap)
+static_assert(ACT_MAX_BLOCK <= LVH_MAX_FRAMES, "levels_hist_kernel's u32 bins are bounded by the frames of a block");
 constexpr size_t ACT_BLOCK_BYTES = (size_t)256 << 20;       // staging per block of frames (slideo_amd.h states it)
 
 dim3 act_grid(int threads_x, int ah) { return dim3((unsigned)cdiv64(threads_x, ACT_TX), (unsigned)cdiv64(ah, ACT_TY)); }
@@ -33,7 +37,8 @@ void activity_observe(slideo_matcher* m, int n, FrameSrc src, hipStream_t user_s
     require_idle(m);
     slideo_matcher::Activity& A = m->activity;
     slideo_matcher::Content& K = m->content;               // (include/slideo_amd.h "Frame content box": the calls feed every open accumulator)
-    if (!A.on && !K.on) fail(SLIDEO_ERR_STATE, "no activity accumulator: slideo_matcher_activity_begin first");
+    slideo_matcher::Levels& L = m->levels;                 // (include/slideo_amd.h "Frame levels": likewise; it holds no frame size)
+    if (!A.on && !K.on && !L.on) fail(SLIDEO_ERR_STATE, "no activity accumulator: slideo_matcher_activity_begin first");
     if (n == 0) return;
     const int aw = src.plan.uw, ah = src.plan.uh;
     // every check of both accumulators in front of the first write
@@ -53,12 +58,14 @@ void activity_observe(slideo_matcher* m, int n, FrameSrc src, hipStream_t user_s
     hipStream_t st = S.st;
     const size_t px = (size_t)aw * ah;
     // frames per block: what a frame stages in front of its analysed image, and that image unless it is the caller's own memory
-    const bool in_place = src.on_device && !src.converted() && src.plan.prep == PREP_NONE;
+    const bool in_place = src.on_device && !src.kernel_in_front();
     const size_t per = src.staging_bytes() + (in_place ? 0 : px * 3);
     const int block = per == 0 ? n : (int)std::min<size_t>({(size_t)n, std::max<size_t>(1, ACT_BLOCK_BYTES / per), (size_t)ACT_MAX_BLOCK});
     // every allocation in front of the first write: the counts and the carried image of a first frame, the largest block's staging
     if (first) { m->d_act_count.reserve(px * 4 + 16); m->d_act_last.reserve(px * 3 + 16); }
     if (kfirst) m->d_cnt_lit.reserve(px * 4 + 16);
+    const bool lfirst = L.on && L.frames == 0;
+    if (lfirst) m->d_lv_hist.reserve(768 * 8);
     if (!in_place) m->d_act_stage.reserve((size_t)block * px * 3 + 16);
     if (src.on_device && user_stream) {                    // the frames were produced on the caller's stream
         HIP_CHECK(hipEventRecord(S.ev_in, user_stream));
@@ -66,6 +73,7 @@ void activity_observe(slideo_matcher* m, int n, FrameSrc src, hipStream_t user_s
     }
     if (first) HIP_CHECK(hipMemsetAsync(m->d_act_count.p, 0, px * 4, st));
     if (kfirst) HIP_CHECK(hipMemsetAsync(m->d_cnt_lit.p, 0, px * 4, st));
+    if (lfirst) HIP_CHECK(hipMemsetAsync(m->d_lv_hist.p, 0, 768 * 8, st));
     bool have_prev = A.on && !first;
     try {
         for (int i = 0; i < n; i += block) {
@@ -80,18 +88,40 @@ void activity_observe(slideo_matcher* m, int n, FrameSrc src, hipStream_t user_s
                 have_prev = true;
             }
             if (K.on) content_launch(m, f, nb, st);        // the same staged frames, directly behind
+            if (L.on) {
+                const LevelsHistArgs a = levels_hist_args(f.p, f.frame_stride, f.stride, aw, ah, nb, m->d_lv_hist.as<unsigned long long>());
+                levels_hist_kernel<<<dim3((unsigned)cdiv64((aw + 3) / 4, LVL_TX), (unsigned)levels_hist_grid_y(ah)), dim3(LVL_TX, LVL_TY), 0, st>>>(a);
+                check_launch("levels_hist_kernel");
+            }
         }
         HIP_CHECK(hipStreamSynchronize(st));               // (the caller's frames are free again)
     } catch (...) {
         // a device error in the middle of a call: blocks may have been counted that `pairs` and `frames` do not know of.  Both
-        // accumulators end (the state "none"): a new begin is needed
+        // accumulators end (the state "none"): a new begin is needed; so does the levels histogram
         (void)hipStreamSynchronize(st);
         m->activity = slideo_matcher::Activity{};
         m->content = slideo_matcher::Content{};
+        m->levels = slideo_matcher::Levels{};
         throw;
     }
     if (A.on) { A.aw = aw; A.ah = ah; A.pairs = pairs; }
     if (K.on) { K.aw = aw; K.ah = ah; K.frames = kframes; }
+    if (L.on) { L.frames += n; L.pixels += (int64_t)n * (int64_t)px; }
+}
+
+// the histogram of an open session that has observed a frame, on the host
+void levels_read(slideo_matcher* m, uint64_t* hist768) {
+    require_idle(m);
+    if (!m->levels.on || m->levels.frames == 0) fail(SLIDEO_ERR_STATE, "the levels histogram has observed no frame");
+    HIP_CHECK(hipSetDevice(m->device));
+    HIP_CHECK(hipMemcpyAsync(hist768, m->d_lv_hist.p, 768 * 8, hipMemcpyDeviceToHost, m->stream));
+    HIP_CHECK(hipStreamSynchronize(m->stream));
+    const uint64_t px = (uint64_t)m->levels.pixels;
+    for (int c = 0; c < 3; ++c) {
+        uint64_t t = 0;
+        for (int v = 0; v < 256; ++v) t += hist768[c * 256 + v];
+        if (t != px) fail(SLIDEO_ERR_HIP, "internal: channel %d of the levels histogram holds %llu samples of %llu", c, (unsigned long long)t, (unsigned long long)px);
+    }
 }
 
 }  // namespace
@@ -117,7 +147,7 @@ int32_t slideo_matcher_activity_end(slideo_matcher* m) {
     HIP_CHECK(hipSetDevice(m->device));
     m->activity = slideo_matcher::Activity{};
     m->d_act_count.release(); m->d_act_last.release(); m->d_act_mask.release();
-    if (!m->content.on) m->d_act_stage.release();          // (shared with the content accumulator: released when the last of the two ends)
+    if (!m->content.on && !m->levels.on) m->d_act_stage.release();      // (shared by the sessions: released when the last of them ends)
     API_CATCH(m)
 }
 
@@ -152,6 +182,60 @@ int32_t slideo_matcher_observe_frames_yuv420_dev(slideo_matcher* m, int32_t n_fr
     API_TRY
     activity_observe(m, n_frames, FrameSrc::yuv420(frames_dev, true, width, height, layout, frame_stride_bytes),
                      reinterpret_cast<hipStream_t>(hip_stream));
+    API_CATCH(m)
+}
+
+// ---- the levels histogram (include/slideo_amd.h "Frame levels") -------------------------------------------------------------------
+
+int32_t slideo_matcher_levels_begin(slideo_matcher* m) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    require_idle(m);
+    if (m->fs.levels.set)
+        fail(SLIDEO_ERR_STATE, "levels_begin: a frame levels table is set, and a table learnt on levelled frames is not the source's "
+                               "(slideo_matcher_set_frame_levels(m, NULL) first)");
+    m->levels = slideo_matcher::Levels{};
+    m->levels.on = true;
+    API_CATCH(m)
+}
+
+int32_t slideo_matcher_levels_end(slideo_matcher* m) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    require_idle(m);
+    HIP_CHECK(hipSetDevice(m->device));
+    m->levels = slideo_matcher::Levels{};
+    m->d_lv_hist.release();
+    if (!m->activity.on && !m->content.on) m->d_act_stage.release();
+    API_CATCH(m)
+}
+
+int32_t slideo_matcher_levels_info(slideo_matcher* m, int64_t* frames, int64_t* pixels) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    if (!frames || !pixels) fail(SLIDEO_ERR_INVALID_ARG, "null frames/pixels");
+    if (!m->levels.on) fail(SLIDEO_ERR_STATE, "no levels histogram: slideo_matcher_levels_begin first");
+    *frames = m->levels.frames; *pixels = m->levels.pixels;
+    API_CATCH(m)
+}
+
+int32_t slideo_matcher_levels_histogram(slideo_matcher* m, uint64_t* hist768) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    if (!hist768) fail(SLIDEO_ERR_INVALID_ARG, "null hist768");
+    levels_read(m, hist768);
+    API_CATCH(m)
+}
+
+int32_t slideo_matcher_levels_points(slideo_matcher* m, int32_t low_ppm, int32_t high_ppm, int32_t* lo3, int32_t* hi3) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    if (!lo3 || !hi3) fail(SLIDEO_ERR_INVALID_ARG, "null lo/hi");
+    if (low_ppm < 0 || low_ppm > LEVELS_MAX_PPM || high_ppm < 0 || high_ppm > LEVELS_MAX_PPM)
+        fail(SLIDEO_ERR_INVALID_ARG, "levels_points: low_ppm %d, high_ppm %d outside 0..%d", low_ppm, high_ppm, LEVELS_MAX_PPM);
+    uint64_t hist[768];
+    levels_read(m, hist);
+    levels_points(hist, low_ppm, high_ppm, lo3, hi3);
     API_CATCH(m)
 }
 

@@ -38,7 +38,7 @@ int32_t slideo_matcher_content_end(slideo_matcher* m) {
     HIP_CHECK(hipSetDevice(m->device));
     m->content = slideo_matcher::Content{};
     m->d_cnt_lit.release(); m->d_cnt_fill.release();
-    if (!m->activity.on) m->d_act_stage.release();         // (shared with the activity accumulator: released when the last of the two ends)
+    if (!m->activity.on && !m->levels.on) m->d_act_stage.release();      // (shared by the sessions: released when the last of them ends)
     API_CATCH(m)
 }
 

@@ -1,11 +1,13 @@
 // stage_orb.hip — drivers of the ORB stage (kernels: orb.hip.h) and of the front doors in front of it: YUV frames
-// (yuv420.hip.h, yuv_sampling.hip.h), frames of another pixel format (pixel_format.hip.h), the working-size reduce (reduce.hip.h) and the frame region's rectify (frame_region.hip.h); the frame mask's
+// (yuv420.hip.h, yuv_sampling.hip.h), frames of another pixel format (pixel_format.hip.h), the frame levels' table (levels.hip.h), the working-size reduce (reduce.hip.h) and the frame region's rectify (frame_region.hip.h); the frame mask's
 // pyramid and candidate filter (frame_mask.hip.h).
 #include "runtime.hpp"
 #include "orb.hip.h"
 #include "yuv420.hip.h"
 #include "yuv_sampling.hip.h"
 #include "pixel_format.hip.h"
+#define LEVELS_APPLY_KERNEL      // (levels_hist_kernel is stage_activity.hip's)
+#include "levels.hip.h"
 #include "reduce.hip.h"
 #include "frame_region.hip.h"
 #include "frame_mask.hip.h"
@@ -148,6 +150,16 @@ void launch_pixels_to_bgr(int format, const uint8_t* src, int64_t src_fs, int st
     else if (form == PIX_PACKED4) pixels_to_bgr_kernel<PIX_PACKED4><<<grid, block, 0, st>>>(a);
     else pixels_to_bgr_kernel<PIX_PLANAR><<<grid, block, 0, st>>>(a);
     check_launch("pixels_to_bgr_kernel");
+}
+
+// n BGR8 images through the matcher's levels table; src == dst (and equal strides): in place
+void launch_levels(slideo_matcher* m, const uint8_t* src, int64_t src_fs, int src_stride, uint8_t* dst, int64_t dst_fs, int dst_stride, int w, int h,
+                   int n, hipStream_t st) {
+    if (!m->fs.levels.set || !m->d_levels.p) fail(SLIDEO_ERR_HIP, "internal: no frame levels table to apply");
+    const LevelsArgs a = levels_args(m->d_levels.as<uint8_t>(), src, src_fs, src_stride, dst, dst_fs, dst_stride, w, h, n);
+    const dim3 grid(cdiv(cdiv(w, 4), LVL_TX), cdiv(h, LVL_TY), n), block(LVL_TX, LVL_TY);
+    levels_kernel<<<grid, block, 0, st>>>(a);
+    check_launch("levels_kernel");
 }
 
 // the reduce class (w, h) -> (dw, dh): ResizeAreaFast when both factors are integers (the test of resize.cpp, in double), else the

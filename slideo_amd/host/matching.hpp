@@ -416,6 +416,14 @@ public:
     // _PLANAR_RGB8 / _PLANAR_BGR8 / _PLANAR_GBR8.  The frame source then hands out frames in that format; pages stay BGR.  The
     // reference only ever sees OpenCV's BGR
     HipImageVideoMatcher& with_pixel_format(int32_t format) { pixel_format_ = format; return *this; }
+    // A per-channel tone table uint8 [3][256] (B, G, R; slideo_group_set_frame_levels, include/slideo_amd.h "Frame levels") applied to
+    // every frame's analysed image as the last step in front of the pipeline: what slideo_frame_levels_lut makes of the points
+    // slideo_matcher_levels_points learnt from a dim, low-contrast or colour-cast recording.  Pages are untouched; null: off.  The
+    // reference analyses the frames as they are
+    HipImageVideoMatcher& with_frame_levels(const uint8_t* lut768) {
+        if (lut768) frame_levels_.assign(lut768, lut768 + 768); else frame_levels_.clear();
+        return *this;
+    }
     // Which frame a gated frame is compared with (slideo_group_set_gate_reference, include/slideo_amd.h "Gate reference"):
     // SLIDEO_GATE_PREVIOUS (default: the frame before, the reference's MarkSimilarIter) or SLIDEO_GATE_ANCHOR (the last frame that
     // was flagged: a change spread over many frames is still flagged when every decoded frame is fed).  One device only: a group of
@@ -468,6 +476,7 @@ public:
             h->check(slideo_group_set_yuv_description(h->g, yuv_matrix_, yuv_range_, yuv_depth_));
         if (yuv_sampling_ != SLIDEO_YUV_SAMPLING_420) h->check(slideo_group_set_yuv_sampling(h->g, yuv_sampling_));
         if (pixel_format_ != SLIDEO_PIXEL_BGR8) h->check(slideo_group_set_pixel_format(h->g, pixel_format_));
+        if (!frame_levels_.empty()) h->check(slideo_group_set_frame_levels(h->g, frame_levels_.data()));
         if (mask_scope_ != SLIDEO_MASK_DETECT) h->check(slideo_group_set_frame_mask_scope(h->g, mask_scope_));
         if (!mask_.empty()) h->check(slideo_group_set_frame_mask(h->g, mask_.data(), mask_w_, mask_h_, mask_w_));
         if (direct_scope_ != SLIDEO_DIRECT_WHOLE) h->check(slideo_group_set_direct_scope(h->g, direct_scope_));
@@ -497,6 +506,7 @@ private:
     int32_t yuv_matrix_ = SLIDEO_YUV_MATRIX_BT601, yuv_range_ = SLIDEO_YUV_RANGE_LIMITED, yuv_depth_ = SLIDEO_YUV_DEPTH_8;
     int32_t yuv_sampling_ = SLIDEO_YUV_SAMPLING_420;
     int32_t pixel_format_ = SLIDEO_PIXEL_BGR8;
+    std::vector<uint8_t> frame_levels_;
     uint32_t mask_scope_ = SLIDEO_MASK_DETECT, direct_scope_ = SLIDEO_DIRECT_WHOLE, gate_ref_ = SLIDEO_GATE_PREVIOUS;
     uint32_t gate_order_ = SLIDEO_GROUP_GATE_HALO;
     float settle_similarity_ = 0.f;

@@ -331,6 +331,26 @@ def learn_frame_region(matcher, frame_batches, *, level, min_share, min_fill, in
     return size[0], size[1], quad, out_w, out_h
 
 
+def learn_frame_levels(matcher, frame_batches, low=0.01, high=0.01):
+    """A frame levels table learnt from the frames' own histogram (include/slideo_amd.h "Frame levels"): the per-channel histogram of
+    the host BGR batches (each uint8 [n, h, w, 3], or the array shape of the pixel format in force; any sizes), cut by the share `low`
+    at the dark end and `high` at the bright end of every channel, and the linear stretch between the two points.  `matcher`: a
+    Matcher (of a Group: its member 0), idle; neither pages nor finalize are needed.  Returns the table uint8 [3, 256] (B, G, R) — what
+    frame_levels= and set_frame_levels take; nothing is installed.  ValueError while a table is set (a table learnt on levelled
+    frames is not the source's), or when a channel's points coincide (a constant picture has no stretch)."""
+    if matcher.frame_levels() is not None:
+        raise ValueError("learn_frame_levels: a frame levels table is set, and a table learnt on levelled frames is not the source's "
+                         "(set_frame_levels(None) first)")
+    matcher.levels_begin()
+    try:
+        for batch in frame_batches:
+            matcher.observe_frames(batch)
+        lo, hi = matcher.levels_points(low, high)
+    finally:
+        matcher.levels_end()
+    return _capi.frame_levels_lut(lo, hi)
+
+
 def dedup_timeline(mappings: List[Matching]) -> List[Matching]:
     """lib.rs:229-244: stable sort by time, drop consecutive mappings with the same image."""
     mappings = sorted(mappings, key=lambda mm: mm.video_time)
@@ -385,7 +405,7 @@ class HipImageVideoMatcher:
 
     def __init__(self, cfg=None, device=None, sift=None, devices=None, working_size=None, frame_mask=None, frame_mask_scope=None,
                  direct_similarity=None, direct_scope=None, frame_region=None, yuv_description=None, gate_reference=None, gate_settle=None,
-                 group_gate_order=None, yuv_sampling=None, gate_memory=None, pixel_format=None):
+                 group_gate_order=None, yuv_sampling=None, gate_memory=None, pixel_format=None, frame_levels=None):
         """devices: HIP ordinals, one matcher each behind one slideo_group (the reference fans out over the whole machine, the
         global rayon pool of lib.rs:45,174); None = every gfx950 device of the node; `device` = d is short for devices = [d].
         sift = (slideo_sift_config, ratio): the north-star's SIFT + L2 front end instead of the reference's ORB + Hamming
@@ -421,6 +441,9 @@ class HipImageVideoMatcher:
         (slideo_group_set_pixel_format): how the frames of the BGR door are read.  The frame source then yields frames in that
         format — [h, w, 3], [h, w, 4] or [3, h, w] — and no swizzle pass runs on the host; page images stay BGR; the reference only
         ever sees OpenCV's BGR; None = "bgr".
+        frame_levels = uint8 [3, 256] (B, G, R; slideo_group_set_frame_levels): a per-channel tone table applied to every frame's
+        analysed image as the last step in front of the pipeline — what learn_frame_levels returns for dim, low-contrast or
+        colour-cast recordings; pages are untouched; the reference analyses the frames as they are; None = off.
         gate_reference = "previous" or "anchor" (slideo_group_set_gate_reference): with "anchor" a frame is compared with the last
         frame that was flagged, not the frame before it, so a change spread over many frames (a cross-fade, an animated build) is
         still flagged when every decoded frame is fed; with several devices it needs group_gate_order = "chain" — without it the
@@ -446,6 +469,7 @@ class HipImageVideoMatcher:
         self._yuv_description = tuple(yuv_description) if yuv_description is not None else None
         self._yuv_sampling = yuv_sampling
         self._pixel_format = pixel_format
+        self._frame_levels = frame_levels
         self._gate_reference = gate_reference
         self._gate_settle = tuple(gate_settle) if gate_settle is not None else None
         self._gate_memory = gate_memory
@@ -476,6 +500,8 @@ class HipImageVideoMatcher:
             m.set_yuv_sampling(self._yuv_sampling)
         if self._pixel_format is not None:
             m.set_pixel_format(self._pixel_format)
+        if self._frame_levels is not None:
+            m.set_frame_levels(self._frame_levels)
         if self._frame_mask_scope is not None:
             m.set_frame_mask_scope(self._frame_mask_scope)
         if self._frame_mask is not None:
