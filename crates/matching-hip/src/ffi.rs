@@ -27,6 +27,10 @@ pub const SLIDEO_YUV_SAMPLING_420: i32 = 0;
 pub const SLIDEO_YUV_SAMPLING_422: i32 = 1;
 pub const SLIDEO_YUV_SAMPLING_444: i32 = 2;
 pub const SLIDEO_YUV_SAMPLING_422_PACKED: i32 = 3;
+pub const SLIDEO_YUV_CHROMA_NEAREST: i32 = 0;
+pub const SLIDEO_YUV_CHROMA_BILINEAR_LEFT: i32 = 1;
+pub const SLIDEO_YUV_CHROMA_BILINEAR_CENTER: i32 = 2;
+pub const SLIDEO_YUV_CHROMA_BILINEAR_TOPLEFT: i32 = 3;
 pub const SLIDEO_PIXEL_BGR8: i32 = 0;
 pub const SLIDEO_PIXEL_RGB8: i32 = 1;
 pub const SLIDEO_PIXEL_BGRA8: i32 = 2;
@@ -561,6 +565,11 @@ extern "C" {
     pub fn slideo_matcher_yuv_sampling(m: *const slideo_matcher, sampling: *mut i32) -> i32;
     pub fn slideo_group_set_yuv_sampling(g: *mut slideo_group, sampling: i32) -> i32;
     pub fn slideo_yuv_layout_packed(format: i32, width: i32, height: i32, bytes_per_sample: i32, out: *mut slideo_yuv420_layout) -> i32;
+    // YUV chroma filter (include/slideo_amd.h "YUV chroma filter"): SLIDEO_YUV_CHROMA_*; out12 = wh[2][3], wv[2][3]
+    pub fn slideo_matcher_set_yuv_chroma(m: *mut slideo_matcher, filter: i32) -> i32;
+    pub fn slideo_matcher_yuv_chroma(m: *const slideo_matcher, filter: *mut i32) -> i32;
+    pub fn slideo_group_set_yuv_chroma(g: *mut slideo_group, filter: i32) -> i32;
+    pub fn slideo_yuv_chroma_weights(filter: i32, sampling: i32, out12: *mut i32) -> i32;
     // frame pixel format (include/slideo_amd.h "Frame pixel format"): SLIDEO_PIXEL_*; how every *_bgr8 frame call reads its frames
     pub fn slideo_matcher_set_pixel_format(m: *mut slideo_matcher, format: i32) -> i32;
     pub fn slideo_matcher_pixel_format(m: *const slideo_matcher, format: *mut i32) -> i32;

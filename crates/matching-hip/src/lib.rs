@@ -99,6 +99,10 @@ pub struct HipImageVideoMatcher {
     /// _444 (screen recorders) or _422_PACKED (YUY2 / UYVY of capture cards; 8-bit).  Every call that takes a
     /// slideo_yuv420_layout reads its frames under it.  The reference knows BGR only.
     pub yuv_sampling: i32,
+    /// How a pixel's chroma is read from 4:2:0 and 4:2:2 frames (slideo_group_set_yuv_chroma): ffi::SLIDEO_YUV_CHROMA_NEAREST
+    /// (default: cvtColor's rule, and what the reference's swscale path does), _BILINEAR_LEFT (the siting of H.264 / HEVC / MPEG-2
+    /// streams), _BILINEAR_CENTER (JPEG, MPEG-1) or _BILINEAR_TOPLEFT (BT.2020).  4:4:4 frames are untouched.
+    pub yuv_chroma: i32,
     /// How the frames of the BGR door are read (slideo_group_set_pixel_format): ffi::SLIDEO_PIXEL_BGR8 (default), _RGB8, the
     /// four-byte _BGRA8 / _RGBA8 / _ARGB8 / _ABGR8 of screen-capture APIs, or the planar _PLANAR_RGB8 / _PLANAR_BGR8 /
     /// _PLANAR_GBR8.  The frame source then hands out frames in that format; pages stay BGR.  The reference only ever sees
@@ -210,6 +214,7 @@ impl Default for HipImageVideoMatcher {
             frame_region: None,
             yuv_description: (ffi::SLIDEO_YUV_MATRIX_BT601, ffi::SLIDEO_YUV_RANGE_LIMITED, ffi::SLIDEO_YUV_DEPTH_8),
             yuv_sampling: ffi::SLIDEO_YUV_SAMPLING_420,
+            yuv_chroma: ffi::SLIDEO_YUV_CHROMA_NEAREST,
             pixel_format: ffi::SLIDEO_PIXEL_BGR8,
             frame_levels: None,
             gate_reference: ffi::SLIDEO_GATE_PREVIOUS,
@@ -267,6 +272,9 @@ impl<'i> ImageVideoMatcher<'i> for HipImageVideoMatcher {
             }
             if self.yuv_sampling != ffi::SLIDEO_YUV_SAMPLING_420 {
                 check(h, ffi::slideo_group_set_yuv_sampling(h, self.yuv_sampling));
+            }
+            if self.yuv_chroma != ffi::SLIDEO_YUV_CHROMA_NEAREST {
+                check(h, ffi::slideo_group_set_yuv_chroma(h, self.yuv_chroma));
             }
             if self.pixel_format != ffi::SLIDEO_PIXEL_BGR8 {
                 check(h, ffi::slideo_group_set_pixel_format(h, self.pixel_format));

@@ -777,8 +777,8 @@ int32_t     slideo_yuv420_layout_packed16(int32_t format, int32_t width, int32_t
  * Contract: a call under a sampling returns, bit for bit, what its *_bgr8 twin returns on that image.  Working size, frame region,
  * frame mask and scopes, the direct look-up, page sets and SIFT mode see the converted image.  A host frame is 2 * bps bytes per
  * pixel of upload and staging under both 4:2:2 forms, 3 * bps under 4:4:4; the upload's extent is the frame's span.
- * Out of scope: 4-byte BGRA / RGBA input; packed 10-bit (Y210, v210); 4:1:1 and 4:4:0; chroma siting other than nearest; fusing
- * the grey write into the conversion.
+ * Out of scope: 4-byte BGRA / RGBA input; packed 10-bit (Y210, v210); 4:1:1 and 4:4:0; fusing the grey write into the
+ * conversion.  (Chroma siting other than nearest: "YUV chroma filter" below.)
  * Kernel: csrc/yuv_sampling.hip.h yuv_sampled_to_bgr_kernel<SAMPLING, DEPTH>, launched iff the sampling is not 420. */
 #define SLIDEO_YUV_SAMPLING_420         0   /* default */
 #define SLIDEO_YUV_SAMPLING_422         1   /* planar or semi-planar: chroma (w/2) x h, pixel (x, y) takes chroma (x/2, y) */
@@ -807,6 +807,49 @@ int32_t     slideo_group_set_yuv_sampling(slideo_group* g, int32_t sampling);
  * SLIDEO_YUV420_*) at width x height with samples of bytes_per_sample (1 or 2) bytes: planes back to back, strides and offsets in
  * BYTES.  A packed format with bytes_per_sample 2, and an odd width of a 4:2:2 format, are SLIDEO_ERR_UNSUPPORTED. */
 int32_t     slideo_yuv_layout_packed(int32_t format, int32_t width, int32_t height, int32_t bytes_per_sample, slideo_yuv420_layout* out);
+
+/* ---- YUV chroma filter (extension: bilinear, sited chroma for 4:2:0 and 4:2:2 frames through the *_yuv420 calls) -------------------
+ * Under the nearest rule — OpenCV's cvtColor, and the default — pixel (x, y) takes chroma (x/2, y/2) under 4:2:0 and (x/2, y) under
+ * 4:2:2: every chroma sample is repeated over a block, and it is drawn half a luma pixel to the right of where an H.264 / HEVC /
+ * MPEG-2 encoder put it.  A matcher carries a YUV CHROMA FILTER, the fifth component of its YUV description, set on its own as the
+ * sampling is; the default is SLIDEO_YUV_CHROMA_NEAREST, under which every call launches exactly what it launched before.  Under
+ * another filter EVERY call that takes a slideo_yuv420_layout reads the chroma of its 4:2:0 / 4:2:2 frames through a bilinear filter
+ * whose phase is the filter's siting — the match, submit / collect, changed-mask and gated calls,
+ * slideo_matcher_observe_frames_yuv420[_dev], slideo_matcher_gate_reset_from_frame_yuv420[_dev], the group's forms and the tap
+ * slideo_yuv420_to_bgr8.  BGR calls never look at it.
+ * Semantics (exact integers): the per-pixel formula is "YUV colour description"'s, unchanged; only U8 and V8 of a pixel change.
+ * Let C be one chroma plane's s8 values (the depth's narrowing comes FIRST: the filter works on 8-bit values at every depth), cw
+ * samples per row and chh rows, every index clamped to the plane (replicate).  Weights in quarters over the samples (k-1, k, k+1):
+ *                 parity 0     parity 1
+ *     co-sited    (0, 4, 0)    (0, 2, 2)
+ *     centred     (1, 3, 0)    (0, 3, 1)
+ *   4:2:0, k = x >> 1, j = y >> 1:   H(x, r) = sum_i wh[x & 1][i] * C[r][k - 1 + i]
+ *                                    U8(x, y) = (sum_i wv[y & 1][i] * H(x, j - 1 + i) + 8) >> 4
+ *   4:2:2 planar, semi-planar and 422_PACKED:   U8(x, y) = (H(x, y) + 2) >> 2   (no vertical step)
+ *   SLIDEO_YUV_CHROMA_BILINEAR_LEFT: wh co-sited, wv centred; _CENTER: both centred; _TOPLEFT: both co-sited.  Under 4:2:2 LEFT and
+ *   TOPLEFT coincide.  Under 4:4:4 the setting is accepted and changes nothing: the kernel launched is the sampling's.
+ *   The weights sum to 16 (4:2:0) or 4 (4:2:2): the result lies in 0..255 without a clamp.
+ * Layout and size rules are unchanged (4:2:0: even width and height; 4:2:2: even width), and so are the bytes of upload and staging.
+ * Contract: a call under a filter returns, bit for bit, what its *_bgr8 twin returns on that image.
+ * DEPARTURE: the filter is the library's own definition.  Neither cvtColor nor the reference's swscale fast path interpolates chroma.
+ * Kernel: csrc/yuv_chroma.hip.h yuv_chroma_to_bgr_kernel<SAMPLING, DEPTH>, launched iff the filter is not NEAREST and the sampling
+ * is not 444. */
+#define SLIDEO_YUV_CHROMA_NEAREST          0   /* default: everything as before */
+#define SLIDEO_YUV_CHROMA_BILINEAR_LEFT    1   /* horizontally co-sited, vertically centred (H.264 / HEVC / MPEG-2 default) */
+#define SLIDEO_YUV_CHROMA_BILINEAR_CENTER  2   /* centred on both axes (JPEG, MPEG-1) */
+#define SLIDEO_YUV_CHROMA_BILINEAR_TOPLEFT 3   /* co-sited on both axes (BT.2020 / UHD) */
+/* As slideo_matcher_set_yuv_sampling: before or after finalize; SLIDEO_ERR_STATE with units in flight; a value outside the
+ * enumeration is SLIDEO_ERR_INVALID_ARG and the state before stays; ends the kept frames and resets the gate state to "none".
+ * slideo_matcher_set_yuv_description and slideo_matcher_set_yuv_sampling leave the filter alone, and
+ * slideo_matcher_yuv_description keeps its three outputs. */
+int32_t     slideo_matcher_set_yuv_chroma(slideo_matcher* m, int32_t filter);
+int32_t     slideo_matcher_yuv_chroma(const slideo_matcher* m, int32_t* filter);
+/* Validates every member before changing any; resets the group's gate state. */
+int32_t     slideo_group_set_yuv_chroma(slideo_group* g, int32_t filter);
+/* Pure: out12 = wh[2][3], wv[2][3] of (filter, sampling), [parity][sample k-1, k, k+1], in quarters.  An axis that is not
+ * interpolated is (0, 4, 0) twice: both axes under NEAREST and under 444, wv under the 4:2:2 forms.  A value outside either
+ * enumeration, or a null out12, is SLIDEO_ERR_INVALID_ARG. */
+int32_t     slideo_yuv_chroma_weights(int32_t filter, int32_t sampling, int32_t* out12);
 
 /* ---- Frame pixel format (extension: RGB, BGRA / RGBA / ARGB / ABGR and planar RGB frames through the *_bgr8 frame calls) --------------
  * B, G, R in three bytes is OpenCV's order.  Screen-capture APIs hand out four-byte pixels (PipeWire, X11 and DXGI: BGRx; macOS and

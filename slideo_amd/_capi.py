@@ -116,6 +116,35 @@ YUV_FORMATS = {"i422": 16, "yv16": 17, "nv16": 18, "nv61": 19, "yuy2": 20, "uyvy
                "i444": 24, "yv24": 25, "nv24": 26, "nv42": 27}
 YUV_PACKED_OFFSETS = {"yuy2": (1, 3), "yvyu": (3, 1), "uyvy": (0, 2), "vyuy": (2, 0)}
 YUV_SAMPLINGS = {"420": 0, "422": 1, "444": 2, "422_packed": 3}
+# "YUV chroma filter": the SLIDEO_YUV_CHROMA_* values
+YUV_CHROMA_FILTERS = {"nearest": 0, "left": 1, "center": 2, "topleft": 3}
+
+
+def yuv_chroma_value(filt):
+    """A name of YUV_CHROMA_FILTERS (or the SLIDEO_YUV_CHROMA_* value itself) -> the C value; ValueError for an unknown name or a
+    value that is no integer."""
+    if isinstance(filt, str):
+        if filt.lower() not in YUV_CHROMA_FILTERS:
+            raise ValueError("yuv chroma filter: unknown %r (one of %s)" % (filt, sorted(YUV_CHROMA_FILTERS)))
+        return YUV_CHROMA_FILTERS[filt.lower()]
+    if isinstance(filt, bool) or not isinstance(filt, (int, np.integer)):
+        raise ValueError("yuv chroma filter: a name (one of %s) or a SLIDEO_YUV_CHROMA_* value, got %r" % (sorted(YUV_CHROMA_FILTERS), filt))
+    return int(filt)
+
+
+def yuv_chroma_weights(filt="left", sampling="420"):
+    """slideo_yuv_chroma_weights: (wh, wv), each ((parity 0: k-1, k, k+1), (parity 1: ...)) in quarters, of the bilinear chroma
+    filter `filt` under `sampling` (names or C values); an axis that is not interpolated is (0, 4, 0) twice."""
+    if isinstance(sampling, str):
+        if sampling.lower() not in YUV_SAMPLINGS:
+            raise ValueError("yuv sampling: unknown %r (one of %s)" % (sampling, sorted(YUV_SAMPLINGS)))
+        sampling = YUV_SAMPLINGS[sampling.lower()]
+    out = (C.c_int32 * 12)()
+    rc = lib().slideo_yuv_chroma_weights(yuv_chroma_value(filt), int(sampling), out)
+    if rc != OK:
+        raise SlideoError(rc, "slideo_yuv_chroma_weights(%r, %r)" % (filt, sampling))
+    v = [int(x) for x in out]
+    return (tuple(v[0:3]), tuple(v[3:6])), (tuple(v[6:9]), tuple(v[9:12]))
 
 
 # "Frame pixel format": the formats every *_bgr8 frame call can read its frames under (SLIDEO_PIXEL_*)
@@ -298,6 +327,7 @@ EXPORTS = [
     "slideo_matcher_set_yuv_description", "slideo_matcher_yuv_description", "slideo_group_set_yuv_description", "slideo_yuv_coefficients",
     "slideo_yuv420_layout_packed16",
     "slideo_matcher_set_yuv_sampling", "slideo_matcher_yuv_sampling", "slideo_group_set_yuv_sampling", "slideo_yuv_layout_packed",
+    "slideo_matcher_set_yuv_chroma", "slideo_matcher_yuv_chroma", "slideo_group_set_yuv_chroma", "slideo_yuv_chroma_weights",
     "slideo_matcher_set_pixel_format", "slideo_matcher_pixel_format", "slideo_group_set_pixel_format", "slideo_pixel_format_info",
     "slideo_pixels_to_bgr8",
     "slideo_matcher_set_frame_levels", "slideo_matcher_frame_levels", "slideo_group_set_frame_levels", "slideo_frame_levels_lut",
@@ -445,6 +475,11 @@ def lib():
             L.slideo_matcher_set_yuv_sampling.argtypes = [vp, i32]
             L.slideo_matcher_yuv_sampling.argtypes = [vp, vp]
             L.slideo_group_set_yuv_sampling.argtypes = [vp, i32]
+        if hasattr(L, "slideo_matcher_set_yuv_chroma"):
+            L.slideo_matcher_set_yuv_chroma.argtypes = [vp, i32]
+            L.slideo_matcher_yuv_chroma.argtypes = [vp, vp]
+            L.slideo_group_set_yuv_chroma.argtypes = [vp, i32]
+            L.slideo_yuv_chroma_weights.argtypes = [i32, i32, vp]
             L.slideo_yuv_layout_packed.argtypes = [i32, i32, i32, i32, vp]
         if hasattr(L, "slideo_matcher_set_pixel_format"):
             L.slideo_matcher_set_pixel_format.argtypes = [vp, i32]
@@ -835,6 +870,22 @@ class _FrameCalls:
         rc = lib().slideo_matcher_yuv_sampling(self._mask_owner(), C.byref(v))
         if rc != OK:
             raise SlideoError(rc, "yuv_sampling")
+        return v.value
+
+    # YUV chroma filter (include/slideo_amd.h "YUV chroma filter"): how a pixel's chroma is read from the samples
+    def set_yuv_chroma(self, filt="nearest"):
+        """'nearest' (the default) | 'left' (H.264 / HEVC / MPEG-2) | 'center' (JPEG, MPEG-1) | 'topleft' (BT.2020 / UHD) — or the
+        SLIDEO_YUV_CHROMA_* value.  Every call that takes a layout then reads the chroma of 4:2:0 and 4:2:2 frames through the
+        bilinear filter of that siting; 4:4:4 frames are untouched.  ValueError for an unknown name.  The matcher must be idle; ends
+        the kept frames and resets the gate state.  set_yuv_description and set_yuv_sampling leave it alone."""
+        self._check(getattr(lib(), self._SETS + "set_yuv_chroma")(self._h, yuv_chroma_value(filt)))
+
+    def yuv_chroma(self):
+        """The SLIDEO_YUV_CHROMA_* value (a Group: member 0's)."""
+        v = C.c_int32()
+        rc = lib().slideo_matcher_yuv_chroma(self._mask_owner(), C.byref(v))
+        if rc != OK:
+            raise SlideoError(rc, "yuv_chroma")
         return v.value
 
     # frame pixel format (include/slideo_amd.h "Frame pixel format"): how every *_bgr8 frame call reads its frames

@@ -1312,6 +1312,22 @@ int32_t slideo_levels_bgr8(slideo_matcher* m, const uint8_t* bgr, int32_t width,
     API_CATCH(m)
 }
 
+// ---- YUV chroma filter (include/slideo_amd.h "YUV chroma filter") -------------------------------------------------------------
+
+int32_t slideo_matcher_set_yuv_chroma(slideo_matcher* m, int32_t filter) {
+    return matcher_set(m, SET_YUV_DESCRIPTION, [&](const FrameSettings& s) { return propose_yuv_chroma(s, filter); });
+}
+
+int32_t slideo_matcher_yuv_chroma(const slideo_matcher* m, int32_t* filter) {
+    if (!m || !filter) return SLIDEO_ERR_INVALID_ARG;
+    *filter = m->fs.yuv.chroma;
+    return SLIDEO_OK;
+}
+
+int32_t slideo_yuv_chroma_weights(int32_t filter, int32_t sampling, int32_t* out12) {
+    return out12 && yuv_chroma_weights(filter, sampling, out12) ? SLIDEO_OK : SLIDEO_ERR_INVALID_ARG;
+}
+
 int32_t slideo_yuv_layout_packed(int32_t format, int32_t w, int32_t h, int32_t bytes_per_sample, slideo_yuv420_layout* out) {
     if (!out || format < SLIDEO_YUV422_I422 || format > SLIDEO_YUV444_NV42 || w < 1 || h < 1 || (bytes_per_sample != 1 && bytes_per_sample != 2))
         return SLIDEO_ERR_INVALID_ARG;

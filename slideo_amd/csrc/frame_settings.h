@@ -1,5 +1,5 @@
 // frame_settings.h — the frame settings of a matcher as ONE record (include/slideo_amd.h "Working size", "Frame region", "Frame mask",
-// "Frame mask scope", "Direct page look-up", "Direct look-up scope", "YUV colour description", "YUV sampling", "Gate reference", "Gate settle", "Gate memory", "Frame pixel format", "Frame levels"): the record, every setter's proposal with its range checks, the
+// "Frame mask scope", "Direct page look-up", "Direct look-up scope", "YUV colour description", "YUV sampling", "YUV chroma filter", "Gate reference", "Gate settle", "Gate memory", "Frame pixel format", "Frame levels"): the record, every setter's proposal with its range checks, the
 // rules between settings, what a change of each ends.  Plain C++, no HIP include (tools/frame_settings_hostcheck.cpp walks it on the
 // host); the device buffers a setting owns are the matcher's (runtime.hpp).  A change takes ONE path: settings_commit (capi_runtime.hip).
 #pragma once
@@ -28,10 +28,14 @@ struct FrameMask { bool set = false; int w = 0, h = 0; };
 struct GateMap { bool on = false; int sw = 0, sh = 0; int64_t n_valid = 0; };
 
 // How every slideo_yuv420_layout call reads its samples (SLIDEO_YUV_MATRIX_* / _RANGE_* / _DEPTH_*); all 0: the default.  The
-// sampling (SLIDEO_YUV_SAMPLING_*, "YUV sampling") is set on its own and says where the samples lie; is_default() is the colour's
+// sampling (SLIDEO_YUV_SAMPLING_*, "YUV sampling") is set on its own and says where the samples lie; is_default() is the colour's.
+// The chroma filter (SLIDEO_YUV_CHROMA_*, "YUV chroma filter") is set on its own too and says how a pixel's chroma is read from them
 struct YuvDesc {
     int matrix = SLIDEO_YUV_MATRIX_BT601, range = SLIDEO_YUV_RANGE_LIMITED, depth = SLIDEO_YUV_DEPTH_8;
     int sampling = SLIDEO_YUV_SAMPLING_420;
+    int chroma = SLIDEO_YUV_CHROMA_NEAREST;
+    // the bilinear kernel converts the frames: a filter is set and the sampling has chroma to interpolate
+    bool filtered() const { return chroma != SLIDEO_YUV_CHROMA_NEAREST && sampling != SLIDEO_YUV_SAMPLING_444; }
     bool is_default() const { return matrix == SLIDEO_YUV_MATRIX_BT601 && range == SLIDEO_YUV_RANGE_LIMITED && depth == SLIDEO_YUV_DEPTH_8; }
     int bytes_per_sample() const { return depth == SLIDEO_YUV_DEPTH_8 ? 1 : 2; }
 };
@@ -134,7 +138,7 @@ inline FrameSettings propose_yuv_description(FrameSettings s, int matrix, int ra
         fail(SLIDEO_ERR_INVALID_ARG, "yuv description: range %d is neither SLIDEO_YUV_RANGE_LIMITED (0) nor SLIDEO_YUV_RANGE_FULL (1)", range);
     if (depth != SLIDEO_YUV_DEPTH_8 && depth != SLIDEO_YUV_DEPTH_10_MSB && depth != SLIDEO_YUV_DEPTH_10_LSB)
         fail(SLIDEO_ERR_INVALID_ARG, "yuv description: depth %d is none of SLIDEO_YUV_DEPTH_8 (0), _10_MSB (1), _10_LSB (2)", depth);
-    s.yuv.matrix = matrix; s.yuv.range = range; s.yuv.depth = depth;       // (the sampling stays: it is set on its own)
+    s.yuv.matrix = matrix; s.yuv.range = range; s.yuv.depth = depth;       // (the sampling and the chroma filter stay: each is set on its own)
     return s;
 }
 // The sampling commits under SET_YUV_DESCRIPTION like the description: it ends the kept frames and resets the gate
@@ -144,6 +148,28 @@ inline FrameSettings propose_yuv_sampling(FrameSettings s, int sampling) {
         fail(SLIDEO_ERR_INVALID_ARG, "yuv sampling: %d is none of SLIDEO_YUV_SAMPLING_420 (0), _422 (1), _444 (2), _422_PACKED (3)", sampling);
     s.yuv.sampling = sampling;
     return s;
+}
+// The chroma filter commits under SET_YUV_DESCRIPTION like the sampling: it ends the kept frames and resets the gate
+inline FrameSettings propose_yuv_chroma(FrameSettings s, int filter) {
+    if (filter != SLIDEO_YUV_CHROMA_NEAREST && filter != SLIDEO_YUV_CHROMA_BILINEAR_LEFT && filter != SLIDEO_YUV_CHROMA_BILINEAR_CENTER &&
+        filter != SLIDEO_YUV_CHROMA_BILINEAR_TOPLEFT)
+        fail(SLIDEO_ERR_INVALID_ARG, "yuv chroma filter: %d is none of SLIDEO_YUV_CHROMA_NEAREST (0), _BILINEAR_LEFT (1), _BILINEAR_CENTER (2), "
+             "_BILINEAR_TOPLEFT (3)", filter);
+    s.yuv.chroma = filter;
+    return s;
+}
+// The weight rule of "YUV chroma filter": out12 = wh[2][3], wv[2][3], [parity][sample k - 1, k, k + 1], in quarters.  An axis that
+// is not interpolated — both under NEAREST and 4:4:4, the vertical one under the 4:2:2 forms — is (0, 4, 0) twice; a co-sited axis is
+// (0, 4, 0), (0, 2, 2); a centred one (1, 3, 0), (0, 3, 1).  false: not a filter or not a sampling
+inline bool yuv_chroma_weights(int filter, int sampling, int32_t* out12) {
+    if (filter < SLIDEO_YUV_CHROMA_NEAREST || filter > SLIDEO_YUV_CHROMA_BILINEAR_TOPLEFT) return false;
+    if (sampling < SLIDEO_YUV_SAMPLING_420 || sampling > SLIDEO_YUV_SAMPLING_422_PACKED) return false;
+    static const int32_t NONE[6] = {0, 4, 0, 0, 4, 0}, COSITED[6] = {0, 4, 0, 0, 2, 2}, CENTRED[6] = {1, 3, 0, 0, 3, 1};
+    const bool on = filter != SLIDEO_YUV_CHROMA_NEAREST && sampling != SLIDEO_YUV_SAMPLING_444;
+    const int32_t* wh = !on ? NONE : filter == SLIDEO_YUV_CHROMA_BILINEAR_CENTER ? CENTRED : COSITED;
+    const int32_t* wv = !on || sampling != SLIDEO_YUV_SAMPLING_420 ? NONE : filter == SLIDEO_YUV_CHROMA_BILINEAR_TOPLEFT ? COSITED : CENTRED;
+    for (int i = 0; i < 6; ++i) { out12[i] = wh[i]; out12[6 + i] = wv[i]; }
+    return true;
 }
 
 // ---- the frame pixel format (include/slideo_amd.h "Frame pixel format") -----------------------------------------------------------

@@ -108,6 +108,7 @@ struct FrameSrc {
     const slideo_yuv420_layout* yuv = nullptr;
     int bps = 1;                                // (derived) bytes per YUV sample: the matcher's YUV description (validate_frames)
     int sampling = SLIDEO_YUV_SAMPLING_420;     // (derived) the matcher's YUV sampling, with bps (describe)
+    int chroma = SLIDEO_YUV_CHROMA_NEAREST;     // (derived) the matcher's YUV chroma filter, with them; it changes no byte count
     int64_t yuv_span = 0;                       // (derived) bytes of one YUV frame: its furthest byte + 1
     bool pinned = false;                        // (derived) page-locked host memory: its copies are truly asynchronous DMA
     // the frames are unit images already — the frames a mask call kept (slideo_match_kept_frames): no region applies to them
@@ -123,7 +124,7 @@ struct FrameSrc {
     bool levels = false;
 
     void describe(const FrameSettings& fs) {
-        bps = fs.yuv.bytes_per_sample(); sampling = fs.yuv.sampling;
+        bps = fs.yuv.bytes_per_sample(); sampling = fs.yuv.sampling; chroma = fs.yuv.chroma;
         pixel_format = yuv || analysed ? SLIDEO_PIXEL_BGR8 : fs.pixel_format;
         levels = fs.levels.set && !analysed;
     }

@@ -1,10 +1,11 @@
 // stage_orb.hip — drivers of the ORB stage (kernels: orb.hip.h) and of the front doors in front of it: YUV frames
-// (yuv420.hip.h, yuv_sampling.hip.h), frames of another pixel format (pixel_format.hip.h), the frame levels' table (levels.hip.h), the working-size reduce (reduce.hip.h) and the frame region's rectify (frame_region.hip.h); the frame mask's
+// (yuv420.hip.h, yuv_sampling.hip.h, yuv_chroma.hip.h), frames of another pixel format (pixel_format.hip.h), the frame levels' table (levels.hip.h), the working-size reduce (reduce.hip.h) and the frame region's rectify (frame_region.hip.h); the frame mask's
 // pyramid and candidate filter (frame_mask.hip.h).
 #include "runtime.hpp"
 #include "orb.hip.h"
 #include "yuv420.hip.h"
 #include "yuv_sampling.hip.h"
+#include "yuv_chroma.hip.h"
 #include "pixel_format.hip.h"
 #define LEVELS_APPLY_KERNEL      // (levels_hist_kernel is stage_activity.hip's)
 #include "levels.hip.h"
@@ -103,10 +104,41 @@ static void launch_yuv_sampled(const YuvDesc& desc, const uint8_t* src, int64_t 
     check_launch("yuv_sampled_to_bgr_kernel");
 }
 
+// 4:2:0 and 4:2:2 frames under a chroma filter other than NEAREST ("YUV chroma filter"): one thread per four columns of the two
+// luma rows of a chroma row (420) or of one row (422)
+static void launch_yuv_chroma(const YuvDesc& desc, const uint8_t* src, int64_t src_fs, const slideo_yuv420_layout& L, int w, int h, int n, uint8_t* dst,
+                              hipStream_t st) {
+    int32_t w12[12];
+    YuvChromaArgs a;
+    if (!yuv_chroma_weights(desc.chroma, desc.sampling, w12) || !yuv_chroma_args(desc.sampling, desc.depth, w12, src, src_fs, L, w, h, n, dst, &a))
+        fail(SLIDEO_ERR_HIP, "internal: no chroma filter kernel for filter %d under sampling %d", desc.chroma, desc.sampling);
+    int32_t c[7];
+    yuv_coefficients(desc.matrix, desc.range, c);
+    const YuvCoef k{c[0], c[1], c[2], c[3], c[4], c[5]};
+    const bool s420 = desc.sampling == SLIDEO_YUV_SAMPLING_420;
+    const dim3 grid(cdiv(cdiv(w, 4), YUV_TX), cdiv(s420 ? h / 2 : h, YUV_TY), n), block(YUV_TX, YUV_TY);
+    const int d = desc.depth;
+    if (desc.sampling == SLIDEO_YUV_SAMPLING_422_PACKED) {
+        if (d != SLIDEO_YUV_DEPTH_8) fail(SLIDEO_ERR_UNSUPPORTED, "internal: packed 4:2:2 under a 10-bit depth");
+        yuv_chroma_to_bgr_kernel<YUV_S422P, YUV_D8><<<grid, block, 0, st>>>(a, k);
+    } else if (s420) {
+        if (d == SLIDEO_YUV_DEPTH_8) yuv_chroma_to_bgr_kernel<YUV_S420, YUV_D8><<<grid, block, 0, st>>>(a, k);
+        else if (d == SLIDEO_YUV_DEPTH_10_MSB) yuv_chroma_to_bgr_kernel<YUV_S420, YUV_D10_MSB><<<grid, block, 0, st>>>(a, k);
+        else yuv_chroma_to_bgr_kernel<YUV_S420, YUV_D10_LSB><<<grid, block, 0, st>>>(a, k);
+    } else {
+        if (d == SLIDEO_YUV_DEPTH_8) yuv_chroma_to_bgr_kernel<YUV_S422, YUV_D8><<<grid, block, 0, st>>>(a, k);
+        else if (d == SLIDEO_YUV_DEPTH_10_MSB) yuv_chroma_to_bgr_kernel<YUV_S422, YUV_D10_MSB><<<grid, block, 0, st>>>(a, k);
+        else yuv_chroma_to_bgr_kernel<YUV_S422, YUV_D10_LSB><<<grid, block, 0, st>>>(a, k);
+    }
+    check_launch("yuv_chroma_to_bgr_kernel");
+}
+
 // n decoded YUV frames (validated layout, frame stride src_fs) -> BGR8 at dst (stride 3w, frame stride 3wh).  Under the 4:2:0
-// sampling exactly what it launched before the sampling existed
+// sampling exactly what it launched before the sampling existed, and under the NEAREST chroma filter, or 4:4:4, exactly what it
+// launched before the filter existed
 void launch_yuv420_to_bgr(const YuvDesc& desc, const uint8_t* src, int64_t src_fs, const slideo_yuv420_layout& L, int w, int h, int n, uint8_t* dst,
                           hipStream_t st) {
+    if (desc.filtered()) { launch_yuv_chroma(desc, src, src_fs, L, w, h, n, dst, st); return; }
     if (desc.sampling != SLIDEO_YUV_SAMPLING_420) { launch_yuv_sampled(desc, src, src_fs, L, w, h, n, dst, st); return; }
     dim3 grid(cdiv(cdiv(w, 4), YUV_TX), cdiv(h / 2, YUV_TY), n);
     if (!desc.is_default()) {

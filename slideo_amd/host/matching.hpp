@@ -411,6 +411,10 @@ public:
     // SLIDEO_YUV_SAMPLING_420 (default), _422, _444 (screen recorders) or _422_PACKED (YUY2 / UYVY of capture cards; 8-bit).  Every
     // call that takes a slideo_yuv420_layout reads its frames under it.  The reference knows BGR only
     HipImageVideoMatcher& with_yuv_sampling(int32_t sampling) { yuv_sampling_ = sampling; return *this; }
+    // How a pixel's chroma is read from 4:2:0 and 4:2:2 frames (slideo_group_set_yuv_chroma, include/slideo_amd.h "YUV chroma
+    // filter"): SLIDEO_YUV_CHROMA_NEAREST (default: cvtColor's rule), _BILINEAR_LEFT (H.264 / HEVC / MPEG-2 siting), _BILINEAR_CENTER
+    // (JPEG, MPEG-1) or _BILINEAR_TOPLEFT (BT.2020).  The reference's swscale path takes the nearest sample
+    HipImageVideoMatcher& with_yuv_chroma(int32_t filter) { yuv_chroma_ = filter; return *this; }
     // How the frames of the BGR door are read (slideo_group_set_pixel_format, include/slideo_amd.h "Frame pixel format"):
     // SLIDEO_PIXEL_BGR8 (default), _RGB8, the four-byte _BGRA8 / _RGBA8 / _ARGB8 / _ABGR8 of screen-capture APIs, or the planar
     // _PLANAR_RGB8 / _PLANAR_BGR8 / _PLANAR_GBR8.  The frame source then hands out frames in that format; pages stay BGR.  The
@@ -475,6 +479,7 @@ public:
         if (yuv_matrix_ != SLIDEO_YUV_MATRIX_BT601 || yuv_range_ != SLIDEO_YUV_RANGE_LIMITED || yuv_depth_ != SLIDEO_YUV_DEPTH_8)
             h->check(slideo_group_set_yuv_description(h->g, yuv_matrix_, yuv_range_, yuv_depth_));
         if (yuv_sampling_ != SLIDEO_YUV_SAMPLING_420) h->check(slideo_group_set_yuv_sampling(h->g, yuv_sampling_));
+        if (yuv_chroma_ != SLIDEO_YUV_CHROMA_NEAREST) h->check(slideo_group_set_yuv_chroma(h->g, yuv_chroma_));
         if (pixel_format_ != SLIDEO_PIXEL_BGR8) h->check(slideo_group_set_pixel_format(h->g, pixel_format_));
         if (!frame_levels_.empty()) h->check(slideo_group_set_frame_levels(h->g, frame_levels_.data()));
         if (mask_scope_ != SLIDEO_MASK_DETECT) h->check(slideo_group_set_frame_mask_scope(h->g, mask_scope_));
@@ -505,6 +510,7 @@ private:
     int32_t mask_w_ = 0, mask_h_ = 0;
     int32_t yuv_matrix_ = SLIDEO_YUV_MATRIX_BT601, yuv_range_ = SLIDEO_YUV_RANGE_LIMITED, yuv_depth_ = SLIDEO_YUV_DEPTH_8;
     int32_t yuv_sampling_ = SLIDEO_YUV_SAMPLING_420;
+    int32_t yuv_chroma_ = SLIDEO_YUV_CHROMA_NEAREST;
     int32_t pixel_format_ = SLIDEO_PIXEL_BGR8;
     std::vector<uint8_t> frame_levels_;
     uint32_t mask_scope_ = SLIDEO_MASK_DETECT, direct_scope_ = SLIDEO_DIRECT_WHOLE, gate_ref_ = SLIDEO_GATE_PREVIOUS;

@@ -405,7 +405,7 @@ class HipImageVideoMatcher:
 
     def __init__(self, cfg=None, device=None, sift=None, devices=None, working_size=None, frame_mask=None, frame_mask_scope=None,
                  direct_similarity=None, direct_scope=None, frame_region=None, yuv_description=None, gate_reference=None, gate_settle=None,
-                 group_gate_order=None, yuv_sampling=None, gate_memory=None, pixel_format=None, frame_levels=None):
+                 group_gate_order=None, yuv_sampling=None, gate_memory=None, pixel_format=None, frame_levels=None, yuv_chroma=None):
         """devices: HIP ordinals, one matcher each behind one slideo_group (the reference fans out over the whole machine, the
         global rayon pool of lib.rs:45,174); None = every gfx950 device of the node; `device` = d is short for devices = [d].
         sift = (slideo_sift_config, ratio): the north-star's SIFT + L2 front end instead of the reference's ORB + Hamming
@@ -437,6 +437,9 @@ class HipImageVideoMatcher:
         yuv_sampling = "420" | "422" | "444" | "422_packed" (slideo_group_set_yuv_sampling): where the frames' samples lie — 4:4:4
         for screen recorders, 4:2:2 for ProRes / broadcast recorders, packed 4:2:2 (YUY2, UYVY) for capture cards; every call that
         takes a layout then reads its frames under it; the reference knows BGR only; None = 4:2:0.
+        yuv_chroma = "nearest" | "left" | "center" | "topleft" (slideo_group_set_yuv_chroma): how a pixel's chroma is read from 4:2:0
+        and 4:2:2 frames — "left" is the bilinear filter at the siting of H.264 / HEVC / MPEG-2 streams, "center" JPEG's and MPEG-1's,
+        "topleft" BT.2020's; cvtColor and the reference's swscale path take the nearest sample; None = nearest.
         pixel_format = "bgr" | "rgb" | "bgra" | "rgba" | "argb" | "abgr" | "planar_rgb" | "planar_bgr" | "planar_gbr"
         (slideo_group_set_pixel_format): how the frames of the BGR door are read.  The frame source then yields frames in that
         format — [h, w, 3], [h, w, 4] or [3, h, w] — and no swizzle pass runs on the host; page images stay BGR; the reference only
@@ -468,6 +471,7 @@ class HipImageVideoMatcher:
         self._frame_region = frame_region
         self._yuv_description = tuple(yuv_description) if yuv_description is not None else None
         self._yuv_sampling = yuv_sampling
+        self._yuv_chroma = yuv_chroma
         self._pixel_format = pixel_format
         self._frame_levels = frame_levels
         self._gate_reference = gate_reference
@@ -498,6 +502,8 @@ class HipImageVideoMatcher:
             m.set_yuv_description(*self._yuv_description)
         if self._yuv_sampling is not None:
             m.set_yuv_sampling(self._yuv_sampling)
+        if self._yuv_chroma is not None:
+            m.set_yuv_chroma(self._yuv_chroma)
         if self._pixel_format is not None:
             m.set_pixel_format(self._pixel_format)
         if self._frame_levels is not None:
