@@ -31,6 +31,9 @@ pub const SLIDEO_YUV_CHROMA_NEAREST: i32 = 0;
 pub const SLIDEO_YUV_CHROMA_BILINEAR_LEFT: i32 = 1;
 pub const SLIDEO_YUV_CHROMA_BILINEAR_CENTER: i32 = 2;
 pub const SLIDEO_YUV_CHROMA_BILINEAR_TOPLEFT: i32 = 3;
+pub const SLIDEO_YUV_TRANSFER_SDR: i32 = 0;
+pub const SLIDEO_YUV_TRANSFER_HLG: i32 = 1;
+pub const SLIDEO_YUV_TRANSFER_PQ: i32 = 2;
 pub const SLIDEO_PIXEL_BGR8: i32 = 0;
 pub const SLIDEO_PIXEL_RGB8: i32 = 1;
 pub const SLIDEO_PIXEL_BGRA8: i32 = 2;
@@ -570,6 +573,11 @@ extern "C" {
     pub fn slideo_matcher_yuv_chroma(m: *const slideo_matcher, filter: *mut i32) -> i32;
     pub fn slideo_group_set_yuv_chroma(g: *mut slideo_group, filter: i32) -> i32;
     pub fn slideo_yuv_chroma_weights(filter: i32, sampling: i32, out12: *mut i32) -> i32;
+    // YUV transfer (include/slideo_amd.h "YUV transfer"): SLIDEO_YUV_TRANSFER_*; white_nits 0 = 203; coef7, gamut9, lin1024, out4096
+    pub fn slideo_matcher_set_yuv_transfer(m: *mut slideo_matcher, transfer: i32, white_nits: f32) -> i32;
+    pub fn slideo_matcher_yuv_transfer(m: *const slideo_matcher, transfer: *mut i32, white_nits: *mut f32) -> i32;
+    pub fn slideo_group_set_yuv_transfer(g: *mut slideo_group, transfer: i32, white_nits: f32) -> i32;
+    pub fn slideo_yuv_transfer_tables(transfer: i32, range: i32, white_nits: f32, coef7: *mut i32, gamut9: *mut i32, lin1024: *mut u16, out4096: *mut u8) -> i32;
     // frame pixel format (include/slideo_amd.h "Frame pixel format"): SLIDEO_PIXEL_*; how every *_bgr8 frame call reads its frames
     pub fn slideo_matcher_set_pixel_format(m: *mut slideo_matcher, format: i32) -> i32;
     pub fn slideo_matcher_pixel_format(m: *const slideo_matcher, format: *mut i32) -> i32;

@@ -103,6 +103,10 @@ pub struct HipImageVideoMatcher {
     /// (default: cvtColor's rule, and what the reference's swscale path does), _BILINEAR_LEFT (the siting of H.264 / HEVC / MPEG-2
     /// streams), _BILINEAR_CENTER (JPEG, MPEG-1) or _BILINEAR_TOPLEFT (BT.2020).  4:4:4 frames are untouched.
     pub yuv_chroma: i32,
+    /// HDR frames to SDR (slideo_group_set_yuv_transfer): (ffi::SLIDEO_YUV_TRANSFER_SDR (default) | _HLG | _PQ, white_nits) — both
+    /// BT.2020; white_nits is the display light that becomes SDR white, 0 = 203.  Needs a 10-bit depth in yuv_description and
+    /// nearest chroma (or 4:4:4).  The reference knows no HDR.
+    pub yuv_transfer: (i32, f32),
     /// How the frames of the BGR door are read (slideo_group_set_pixel_format): ffi::SLIDEO_PIXEL_BGR8 (default), _RGB8, the
     /// four-byte _BGRA8 / _RGBA8 / _ARGB8 / _ABGR8 of screen-capture APIs, or the planar _PLANAR_RGB8 / _PLANAR_BGR8 /
     /// _PLANAR_GBR8.  The frame source then hands out frames in that format; pages stay BGR.  The reference only ever sees
@@ -215,6 +219,7 @@ impl Default for HipImageVideoMatcher {
             yuv_description: (ffi::SLIDEO_YUV_MATRIX_BT601, ffi::SLIDEO_YUV_RANGE_LIMITED, ffi::SLIDEO_YUV_DEPTH_8),
             yuv_sampling: ffi::SLIDEO_YUV_SAMPLING_420,
             yuv_chroma: ffi::SLIDEO_YUV_CHROMA_NEAREST,
+            yuv_transfer: (ffi::SLIDEO_YUV_TRANSFER_SDR, 0.0),
             pixel_format: ffi::SLIDEO_PIXEL_BGR8,
             frame_levels: None,
             gate_reference: ffi::SLIDEO_GATE_PREVIOUS,
@@ -275,6 +280,9 @@ impl<'i> ImageVideoMatcher<'i> for HipImageVideoMatcher {
             }
             if self.yuv_chroma != ffi::SLIDEO_YUV_CHROMA_NEAREST {
                 check(h, ffi::slideo_group_set_yuv_chroma(h, self.yuv_chroma));
+            }
+            if self.yuv_transfer.0 != ffi::SLIDEO_YUV_TRANSFER_SDR {
+                check(h, ffi::slideo_group_set_yuv_transfer(h, self.yuv_transfer.0, self.yuv_transfer.1));
             }
             if self.pixel_format != ffi::SLIDEO_PIXEL_BGR8 {
                 check(h, ffi::slideo_group_set_pixel_format(h, self.pixel_format));

@@ -851,6 +851,66 @@ int32_t     slideo_group_set_yuv_chroma(slideo_group* g, int32_t filter);
  * enumeration, or a null out12, is SLIDEO_ERR_INVALID_ARG. */
 int32_t     slideo_yuv_chroma_weights(int32_t filter, int32_t sampling, int32_t* out12);
 
+/* ---- YUV transfer (extension: HLG and PQ BT.2020 frames to SDR through the *_yuv420 calls) ----------------------------------------
+ * The description above reads every frame as an SDR BT.601 / BT.709 picture and cuts 10-bit samples to their top 8 bits.  Phones
+ * record HLG / BT.2020 10-bit 4:2:0, HDR screen recorders and HDMI capture write PQ / BT.2020; read as SDR a white page comes out
+ * grey and the similarity test fails.  A matcher carries a YUV TRANSFER, set on its own as the sampling and the chroma filter are;
+ * the default is SLIDEO_YUV_TRANSFER_SDR, under which every call launches exactly what it launched before.  Under another transfer
+ * EVERY call that takes a slideo_yuv420_layout — the match, submit / collect, changed-mask and gated calls,
+ * slideo_matcher_observe_frames_yuv420[_dev], slideo_matcher_gate_reset_from_frame_yuv420[_dev], the group's forms and the tap
+ * slideo_yuv420_to_bgr8 — reads its frames as HLG (ARIB STD-B67 / BT.2100) or PQ (SMPTE ST 2084) signals with BT.2020 primaries
+ * and the BT.2020 non-constant-luminance matrix.  The description's MATRIX IS NOT CONSULTED (the matrix is part of the transfer's
+ * meaning); its range and depth are used.  BGR calls never look at it.
+ * white_nits is the display light that becomes SDR white: 0 means 203, the BT.2408 reference white; any other value must be finite
+ * and in 1 .. 10000; under SDR it must be 0.  slideo_matcher_yuv_transfer reports the value in force (203 for a 0; 0 under SDR).
+ * Semantics (int32 arithmetic, arithmetic >>, nearest chroma exactly as the sampling defines it); a frame stands for this image:
+ *   1. samples at 10 bits: s10 = sample16 >> 6 (10_MSB), min(sample16, 1023) (10_LSB).  Nothing is truncated to 8 bits.
+ *   2. Y'CbCr -> R'G'B' codes: the description's rule at 10 bits, SHIFT = 18 (at 20 the sums leave int32), Kr = 0.2627,
+ *      Kb = 0.0593, Kg = 1 - Kr - Kb; limited range sy = 1023/876, sc = 1023/896, y_offset = 64; full range 1, 1, 0.
+ *      CY = rint(sy 2^18), CVR = rint(sc 2(1-Kr) 2^18), CUB = rint(sc 2(1-Kb) 2^18), CUG = -rint(sc 2(1-Kb) Kb/Kg 2^18),
+ *      CVG = -rint(sc 2(1-Kr) Kr/Kg 2^18); u = U10 - 512, v = V10 - 512, y = max(0, Y10 - y_offset) CY, half = 1 << 17,
+ *      R' = clamp((y + half + CVR v) >> 18, 0, 1023), G' = clamp((y + half + CVG v + CUG u) >> 18, 0, 1023),
+ *      B' = clamp((y + half + CUB u) >> 18, 0, 1023).  Every operand fits 24 signed bits, every product (at most 2.94e8) and
+ *      every sum (at most 5.82e8) int32.  coef7 = CY, CUB, CUG, CVG, CVR, y_offset, SHIFT:
+ *      limited 306134, 563104, -49251, -171006, 441349, 64, 18; full 262144, 493198, -43137, -149777, 386558, 0, 18.
+ *   3. linear light per channel: lin = LIN[c'], uint16 [1024], 16383 = SDR white:
+ *      LIN[i] = rint(16383 min(1, nits(i / 1023) / white_nits)); PQ: nits(e) = 10000 (max(e^(1/m2) - c1, 0) / (c2 - c3
+ *      e^(1/m2)))^(1/m1), the ST 2084 constants; HLG: nits(e) = 1000 E(e)^1.2, E the inverse OETF e^2 / 3 for e <= 1/2 and
+ *      (exp((e - c) / a) + b) / 12 above, a = 0.17883277, b = 0.28466892, c = 0.55991073 (a nominal 1000-nit display, the system
+ *      gamma per channel).  Everything above white_nits clips: a slide's white is meant to become 255.
+ *   4. gamut: G = M709^-1 M2020 from the two sets of primaries and D65, float64; gamut9[r][c] = rint(G 2^14) off the diagonal, the
+ *      diagonal such that every row sums to exactly 2^14 (grey stays grey): 27206 -9628 -1194 / -2041 18562 -137 / -297 -1648 18329.
+ *      o_r = clamp((sum_c gamut9[r][c] lin_c + (1 << 13)) >> 14, 0, 16383); products at most 4.46e8.
+ *   5. encode: OUT uint8 [4096], OUT[i] = rint(255 srgb_oetf(i / 4095)); the byte is OUT[min(4095, (o + 2) >> 2)], stored B, G, R.
+ * THE LIBRARY'S TABLES ARE THE DEFINITION: the host computes them once per set call in float64 and slideo_yuv_transfer_tables
+ * returns them; the kernel reads those integers.  Frame levels run after the conversion as before, for anything finer.
+ * Rules between settings (SLIDEO_ERR_UNSUPPORTED; whichever set call would complete the pair is refused and the values before stay):
+ * a transfer other than SDR together with SLIDEO_YUV_DEPTH_8 (which also excludes SLIDEO_YUV_SAMPLING_422_PACKED); a transfer other
+ * than SDR together with a chroma filter other than NEAREST while the sampling is not 4:4:4 (bilinear chroma under a transfer is
+ * out of scope).
+ * Contract: a call under a transfer returns, bit for bit, what its *_bgr8 twin returns on that image.  Working size, frame region,
+ * frame mask and scopes, the direct look-up, page sets, frame levels and SIFT mode see the converted image.
+ * DEPARTURE: the reference knows no HDR.  The per-channel system gamma, the hard clip at white_nits and the sRGB encode are the
+ * library's own definition; it is no broadcast-grade tone mapper.
+ * Out of scope: bilinear chroma under a transfer; a luminance-based OOTF or any tone curve other than the clip; HDR10+ / Dolby
+ * Vision metadata; BT.2020 constant luminance; an SDR BT.2020 matrix value in the description; 12-bit samples; an HDR BGR door.
+ * Kernel: csrc/yuv_transfer.hip.h yuv_transfer_to_bgr_kernel<SAMPLING, DEPTH>, launched iff the transfer is not SDR. */
+#define SLIDEO_YUV_TRANSFER_SDR 0   /* default: everything as before */
+#define SLIDEO_YUV_TRANSFER_HLG 1   /* ARIB STD-B67 / BT.2100 HLG, BT.2020 primaries, BT.2020 non-constant-luminance matrix */
+#define SLIDEO_YUV_TRANSFER_PQ  2   /* SMPTE ST 2084, BT.2020 primaries, BT.2020 NCL matrix */
+/* As slideo_matcher_set_yuv_sampling: before or after finalize; SLIDEO_ERR_STATE with units in flight; a transfer outside the
+ * enumeration or a white_nits outside its rule is SLIDEO_ERR_INVALID_ARG and the state before stays; ends the kept frames and resets
+ * the gate state to "none".  The description's, the sampling's and the chroma filter's set calls leave the transfer alone. */
+int32_t     slideo_matcher_set_yuv_transfer(slideo_matcher* m, int32_t transfer, float white_nits);
+int32_t     slideo_matcher_yuv_transfer(const slideo_matcher* m, int32_t* transfer, float* white_nits);
+/* Validates every member before changing any; resets the group's gate state. */
+int32_t     slideo_group_set_yuv_transfer(slideo_group* g, int32_t transfer, float white_nits);
+/* Pure host, no device: the whole definition as integers — coef7 (step 2), gamut9 (step 4, row-major), lin1024 (step 3), out4096
+ * (step 5) of (transfer, range, white_nits); any output may be null.  SLIDEO_YUV_TRANSFER_SDR (it has no tables), a value outside
+ * either enumeration or a white_nits outside the set call's rule is SLIDEO_ERR_INVALID_ARG. */
+int32_t     slideo_yuv_transfer_tables(int32_t transfer, int32_t range, float white_nits, int32_t* coef7, int32_t* gamut9,
+                                       uint16_t* lin1024, uint8_t* out4096);
+
 /* ---- Frame pixel format (extension: RGB, BGRA / RGBA / ARGB / ABGR and planar RGB frames through the *_bgr8 frame calls) --------------
  * B, G, R in three bytes is OpenCV's order.  Screen-capture APIs hand out four-byte pixels (PipeWire, X11 and DXGI: BGRx; macOS and
  * browsers: RGBA), GPU decoders with a colour stage and PNG / JPEG decoders give RGB(A), every PyTorch pipeline gives uint8

@@ -147,6 +147,39 @@ def yuv_chroma_weights(filt="left", sampling="420"):
     return (tuple(v[0:3]), tuple(v[3:6])), (tuple(v[6:9]), tuple(v[9:12]))
 
 
+# "YUV transfer": the SLIDEO_YUV_TRANSFER_* values
+YUV_TRANSFERS = {"sdr": 0, "hlg": 1, "pq": 2}
+
+
+def yuv_transfer_value(transfer):
+    """A name of YUV_TRANSFERS (or the SLIDEO_YUV_TRANSFER_* value itself) -> the C value; ValueError for an unknown name or a value
+    that is no integer."""
+    if isinstance(transfer, str):
+        if transfer.lower() not in YUV_TRANSFERS:
+            raise ValueError("yuv transfer: unknown %r (one of %s)" % (transfer, sorted(YUV_TRANSFERS)))
+        return YUV_TRANSFERS[transfer.lower()]
+    if isinstance(transfer, bool) or not isinstance(transfer, (int, np.integer)):
+        raise ValueError("yuv transfer: a name (one of %s) or a SLIDEO_YUV_TRANSFER_* value, got %r" % (sorted(YUV_TRANSFERS), transfer))
+    return int(transfer)
+
+
+def yuv_transfer_tables(transfer="hlg", range_="limited", white_nits=0):
+    """slideo_yuv_transfer_tables: the whole definition of "YUV transfer" as integers — (coef7 int32 [7]: CY, CUB, CUG, CVG, CVR,
+    y_offset, SHIFT; gamut9 int32 [3, 3]; LIN uint16 [1024]; OUT uint8 [4096]) of (transfer, range, white_nits); names or C values.
+    Pure host: no device is touched."""
+    if isinstance(range_, str):
+        if range_.lower() not in YUV_RANGES:
+            raise ValueError("yuv range: unknown %r (one of %s)" % (range_, sorted(YUV_RANGES)))
+        range_ = YUV_RANGES[range_.lower()]
+    coef, gamut = np.zeros(7, np.int32), np.zeros((3, 3), np.int32)
+    lin, out = np.zeros(1024, np.uint16), np.zeros(4096, np.uint8)
+    rc = lib().slideo_yuv_transfer_tables(yuv_transfer_value(transfer), int(range_), C.c_float(white_nits), coef.ctypes.data, gamut.ctypes.data,
+                                          lin.ctypes.data, out.ctypes.data)
+    if rc != OK:
+        raise SlideoError(rc, "slideo_yuv_transfer_tables(%r, %r, %r)" % (transfer, range_, white_nits))
+    return coef, gamut, lin, out
+
+
 # "Frame pixel format": the formats every *_bgr8 frame call can read its frames under (SLIDEO_PIXEL_*)
 PIXEL_FORMATS = {"bgr": 0, "rgb": 1, "bgra": 2, "rgba": 3, "argb": 4, "abgr": 5, "planar_rgb": 6, "planar_bgr": 7, "planar_gbr": 8}
 
@@ -328,6 +361,7 @@ EXPORTS = [
     "slideo_yuv420_layout_packed16",
     "slideo_matcher_set_yuv_sampling", "slideo_matcher_yuv_sampling", "slideo_group_set_yuv_sampling", "slideo_yuv_layout_packed",
     "slideo_matcher_set_yuv_chroma", "slideo_matcher_yuv_chroma", "slideo_group_set_yuv_chroma", "slideo_yuv_chroma_weights",
+    "slideo_matcher_set_yuv_transfer", "slideo_matcher_yuv_transfer", "slideo_group_set_yuv_transfer", "slideo_yuv_transfer_tables",
     "slideo_matcher_set_pixel_format", "slideo_matcher_pixel_format", "slideo_group_set_pixel_format", "slideo_pixel_format_info",
     "slideo_pixels_to_bgr8",
     "slideo_matcher_set_frame_levels", "slideo_matcher_frame_levels", "slideo_group_set_frame_levels", "slideo_frame_levels_lut",
@@ -480,6 +514,11 @@ def lib():
             L.slideo_matcher_yuv_chroma.argtypes = [vp, vp]
             L.slideo_group_set_yuv_chroma.argtypes = [vp, i32]
             L.slideo_yuv_chroma_weights.argtypes = [i32, i32, vp]
+        if hasattr(L, "slideo_matcher_set_yuv_transfer"):
+            L.slideo_matcher_set_yuv_transfer.argtypes = [vp, i32, C.c_float]
+            L.slideo_matcher_yuv_transfer.argtypes = [vp, vp, vp]
+            L.slideo_group_set_yuv_transfer.argtypes = [vp, i32, C.c_float]
+            L.slideo_yuv_transfer_tables.argtypes = [i32, i32, C.c_float, vp, vp, vp, vp]
             L.slideo_yuv_layout_packed.argtypes = [i32, i32, i32, i32, vp]
         if hasattr(L, "slideo_matcher_set_pixel_format"):
             L.slideo_matcher_set_pixel_format.argtypes = [vp, i32]
@@ -887,6 +926,23 @@ class _FrameCalls:
         if rc != OK:
             raise SlideoError(rc, "yuv_chroma")
         return v.value
+
+    # YUV transfer (include/slideo_amd.h "YUV transfer"): HLG and PQ BT.2020 frames to SDR
+    def set_yuv_transfer(self, transfer="sdr", white_nits=0):
+        """'sdr' (the default) | 'hlg' (ARIB STD-B67 / BT.2100) | 'pq' (SMPTE ST 2084) — or the SLIDEO_YUV_TRANSFER_* value; both
+        with BT.2020 primaries and the BT.2020 non-constant-luminance matrix (the description's matrix is not consulted; its range
+        and depth are).  white_nits: the display light that becomes SDR white — 0 means 203; else 1 .. 10000; 0 under 'sdr'.  Needs
+        a 10-bit depth and nearest chroma (or 4:4:4).  ValueError for an unknown name.  The matcher must be idle; ends the kept
+        frames and resets the gate state.  set_yuv_description, set_yuv_sampling and set_yuv_chroma leave it alone."""
+        self._check(getattr(lib(), self._SETS + "set_yuv_transfer")(self._h, yuv_transfer_value(transfer), C.c_float(white_nits)))
+
+    def yuv_transfer(self):
+        """(SLIDEO_YUV_TRANSFER_* value, white_nits in force: 203.0 for a 0, 0.0 under SDR) (a Group: member 0's)."""
+        t, n = C.c_int32(), C.c_float()
+        rc = lib().slideo_matcher_yuv_transfer(self._mask_owner(), C.byref(t), C.byref(n))
+        if rc != OK:
+            raise SlideoError(rc, "yuv_transfer")
+        return t.value, n.value
 
     # frame pixel format (include/slideo_amd.h "Frame pixel format"): how every *_bgr8 frame call reads its frames
     def set_pixel_format(self, fmt="bgr"):

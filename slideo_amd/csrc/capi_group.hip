@@ -457,6 +457,9 @@ int32_t slideo_group_set_yuv_sampling(slideo_group* g, int32_t sampling) {
 int32_t slideo_group_set_yuv_chroma(slideo_group* g, int32_t filter) {
     return group_set(g, SET_YUV_DESCRIPTION, [&](const FrameSettings& s) { return propose_yuv_chroma(s, filter); });
 }
+int32_t slideo_group_set_yuv_transfer(slideo_group* g, int32_t transfer, float white_nits) {
+    return group_set(g, SET_YUV_DESCRIPTION, [&](const FrameSettings& s) { return propose_yuv_transfer(s, transfer, white_nits); });
+}
 int32_t slideo_group_set_pixel_format(slideo_group* g, int32_t format) {
     return group_set(g, SET_YUV_DESCRIPTION, [&](const FrameSettings& s) { return propose_pixel_format(s, format); });
 }

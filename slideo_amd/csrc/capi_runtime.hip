@@ -160,6 +160,16 @@ void settings_commit(slideo_matcher* m, Setting what, FrameSettings next, const 
         m->d_levels.reserve(768);
         HIP_CHECK(hipMemcpy(m->d_levels.p, next.levels.lut, 768, hipMemcpyHostToDevice));
     }
+    // a new transfer's tables (likewise)
+    if (next.yuv.transfer != SLIDEO_YUV_TRANSFER_SDR && (next.yuv.transfer != m->fs.yuv.transfer || next.yuv.white_nits != m->fs.yuv.white_nits)) {
+        std::vector<uint8_t> tab(2 * YUV_TR_LIN + YUV_TR_OUT);
+        std::vector<uint16_t> lin(YUV_TR_LIN);
+        yuv_transfer_lin_out(next.yuv.transfer, (double)next.yuv.white_nits, lin.data(), tab.data() + 2 * YUV_TR_LIN);
+        std::memcpy(tab.data(), lin.data(), 2 * YUV_TR_LIN);
+        HIP_CHECK(hipSetDevice(m->device));
+        m->d_transfer.reserve(tab.size());
+        HIP_CHECK(hipMemcpy(m->d_transfer.p, tab.data(), tab.size(), hipMemcpyHostToDevice));
+    }
     m->fs = next;
     const SettingEnds& ends = SETTING_ENDS[what];
     if (ends.kept) m->kept.valid = false;
@@ -211,7 +221,7 @@ DevFrames stage_frames(slideo_matcher* m, Slot& S, const FrameSrc& src, int firs
     if (src.converted()) {
         uint8_t* bgr = stage;
         if (pre) { S.d_full.reserve((size_t)fb * n + 16); bgr = S.d_full.as<uint8_t>(); }
-        if (src.yuv) launch_yuv420_to_bgr(m->fs.yuv, p, fs, *src.yuv, src.w, src.h, n, bgr, S.st);
+        if (src.yuv) launch_yuv420_to_bgr(m->fs.yuv, p, fs, *src.yuv, src.w, src.h, n, bgr, S.st, m->d_transfer.as<uint32_t>());
         else launch_pixels_to_bgr(src.pixel_format, p, fs, src.src_stride, src.w, src.h, n, bgr, S.st);
         p = bgr; fs = fb;
     }
@@ -1326,6 +1336,23 @@ int32_t slideo_matcher_yuv_chroma(const slideo_matcher* m, int32_t* filter) {
 
 int32_t slideo_yuv_chroma_weights(int32_t filter, int32_t sampling, int32_t* out12) {
     return out12 && yuv_chroma_weights(filter, sampling, out12) ? SLIDEO_OK : SLIDEO_ERR_INVALID_ARG;
+}
+
+// ---- YUV transfer (include/slideo_amd.h "YUV transfer") ---------------------------------------------------------------------------
+
+int32_t slideo_matcher_set_yuv_transfer(slideo_matcher* m, int32_t transfer, float white_nits) {
+    return matcher_set(m, SET_YUV_DESCRIPTION, [&](const FrameSettings& s) { return propose_yuv_transfer(s, transfer, white_nits); });
+}
+
+int32_t slideo_matcher_yuv_transfer(const slideo_matcher* m, int32_t* transfer, float* white_nits) {
+    if (!m || !transfer || !white_nits) return SLIDEO_ERR_INVALID_ARG;
+    *transfer = m->fs.yuv.transfer; *white_nits = m->fs.yuv.white_nits;
+    return SLIDEO_OK;
+}
+
+int32_t slideo_yuv_transfer_tables(int32_t transfer, int32_t range, float white_nits, int32_t* coef7, int32_t* gamut9, uint16_t* lin1024,
+                                   uint8_t* out4096) {
+    return yuv_transfer_tables(transfer, range, white_nits, coef7, gamut9, lin1024, out4096) ? SLIDEO_OK : SLIDEO_ERR_INVALID_ARG;
 }
 
 int32_t slideo_yuv_layout_packed(int32_t format, int32_t w, int32_t h, int32_t bytes_per_sample, slideo_yuv420_layout* out) {

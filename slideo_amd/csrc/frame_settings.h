@@ -1,5 +1,5 @@
 // frame_settings.h — the frame settings of a matcher as ONE record (include/slideo_amd.h "Working size", "Frame region", "Frame mask",
-// "Frame mask scope", "Direct page look-up", "Direct look-up scope", "YUV colour description", "YUV sampling", "YUV chroma filter", "Gate reference", "Gate settle", "Gate memory", "Frame pixel format", "Frame levels"): the record, every setter's proposal with its range checks, the
+// "Frame mask scope", "Direct page look-up", "Direct look-up scope", "YUV colour description", "YUV sampling", "YUV chroma filter", "YUV transfer", "Gate reference", "Gate settle", "Gate memory", "Frame pixel format", "Frame levels"): the record, every setter's proposal with its range checks, the
 // rules between settings, what a change of each ends.  Plain C++, no HIP include (tools/frame_settings_hostcheck.cpp walks it on the
 // host); the device buffers a setting owns are the matcher's (runtime.hpp).  A change takes ONE path: settings_commit (capi_runtime.hip).
 #pragma once
@@ -34,6 +34,10 @@ struct YuvDesc {
     int matrix = SLIDEO_YUV_MATRIX_BT601, range = SLIDEO_YUV_RANGE_LIMITED, depth = SLIDEO_YUV_DEPTH_8;
     int sampling = SLIDEO_YUV_SAMPLING_420;
     int chroma = SLIDEO_YUV_CHROMA_NEAREST;
+    // the transfer (SLIDEO_YUV_TRANSFER_*, "YUV transfer") is set on its own as well; white_nits: the display light that becomes SDR
+    // white, as resolved (0 under SDR; a set call's 0 is stored as 203).  The matcher's d_transfer holds the tables' device copy
+    int transfer = SLIDEO_YUV_TRANSFER_SDR;
+    float white_nits = 0.f;
     // the bilinear kernel converts the frames: a filter is set and the sampling has chroma to interpolate
     bool filtered() const { return chroma != SLIDEO_YUV_CHROMA_NEAREST && sampling != SLIDEO_YUV_SAMPLING_444; }
     bool is_default() const { return matrix == SLIDEO_YUV_MATRIX_BT601 && range == SLIDEO_YUV_RANGE_LIMITED && depth == SLIDEO_YUV_DEPTH_8; }
@@ -156,6 +160,18 @@ inline FrameSettings propose_yuv_chroma(FrameSettings s, int filter) {
         fail(SLIDEO_ERR_INVALID_ARG, "yuv chroma filter: %d is none of SLIDEO_YUV_CHROMA_NEAREST (0), _BILINEAR_LEFT (1), _BILINEAR_CENTER (2), "
              "_BILINEAR_TOPLEFT (3)", filter);
     s.yuv.chroma = filter;
+    return s;
+}
+// The transfer commits under SET_YUV_DESCRIPTION like the sampling: it ends the kept frames and resets the gate
+inline FrameSettings propose_yuv_transfer(FrameSettings s, int transfer, float white_nits) {
+    if (transfer != SLIDEO_YUV_TRANSFER_SDR && transfer != SLIDEO_YUV_TRANSFER_HLG && transfer != SLIDEO_YUV_TRANSFER_PQ)
+        fail(SLIDEO_ERR_INVALID_ARG, "yuv transfer: %d is none of SLIDEO_YUV_TRANSFER_SDR (0), _HLG (1), _PQ (2)", transfer);
+    if (transfer == SLIDEO_YUV_TRANSFER_SDR) {
+        if (!(white_nits == 0.f)) fail(SLIDEO_ERR_INVALID_ARG, "yuv transfer: white_nits %g under SLIDEO_YUV_TRANSFER_SDR must be 0", (double)white_nits);
+    } else if (!(white_nits == 0.f) && !(std::isfinite(white_nits) && white_nits >= 1.f && white_nits <= 10000.f))
+        fail(SLIDEO_ERR_INVALID_ARG, "yuv transfer: white_nits %g: 0 (203, the BT.2408 reference white) or a finite value in 1 .. 10000", (double)white_nits);
+    s.yuv.transfer = transfer;
+    s.yuv.white_nits = transfer == SLIDEO_YUV_TRANSFER_SDR ? 0.f : white_nits == 0.f ? 203.f : white_nits;
     return s;
 }
 // The weight rule of "YUV chroma filter": out12 = wh[2][3], wv[2][3], [parity][sample k - 1, k, k + 1], in quarters.  An axis that
@@ -421,6 +437,98 @@ inline void yuv_coefficients(int matrix, int range, int32_t* out7) {
     out7[5] = full ? 0 : 16;
 }
 
+// ---- the integers of "YUV transfer" (include/slideo_amd.h), in float64 ------------------------------------------------------------
+constexpr int YUV_TR_SHIFT = 18, YUV_TR_LIN = 1024, YUV_TR_OUT = 4096, YUV_TR_WHITE = 16383, YUV_TR_GAMUT_SHIFT = 14;
+// step 2: CY, CUB, CUG, CVG, CVR, y_offset, SHIFT of the BT.2020 non-constant-luminance matrix at 10 bits under `range`
+inline void yuv_transfer_coefficients(int range, int32_t* out7) {
+    const bool full = range == SLIDEO_YUV_RANGE_FULL;
+    const double Kr = 0.2627, Kb = 0.0593, Kg = 1.0 - Kr - Kb;
+    const double sy = full ? 1.0 : 1023.0 / 876.0, sc = full ? 1.0 : 1023.0 / 896.0, one = (double)(1 << YUV_TR_SHIFT);
+    out7[0] = (int32_t)std::rint(sy * one);
+    out7[1] = (int32_t)std::rint(sc * 2.0 * (1.0 - Kb) * one);
+    out7[2] = -(int32_t)std::rint(sc * 2.0 * (1.0 - Kb) * Kb / Kg * one);
+    out7[3] = -(int32_t)std::rint(sc * 2.0 * (1.0 - Kr) * Kr / Kg * one);
+    out7[4] = (int32_t)std::rint(sc * 2.0 * (1.0 - Kr) * one);
+    out7[5] = full ? 0 : 64;
+    out7[6] = YUV_TR_SHIFT;
+}
+inline void mat3_inverse(const double* m, double* o) {
+    const double c0 = m[4] * m[8] - m[5] * m[7], c1 = m[5] * m[6] - m[3] * m[8], c2 = m[3] * m[7] - m[4] * m[6];
+    const double d = m[0] * c0 + m[1] * c1 + m[2] * c2;
+    o[0] = c0 / d; o[1] = (m[2] * m[7] - m[1] * m[8]) / d; o[2] = (m[1] * m[5] - m[2] * m[4]) / d;
+    o[3] = c1 / d; o[4] = (m[0] * m[8] - m[2] * m[6]) / d; o[5] = (m[2] * m[3] - m[0] * m[5]) / d;
+    o[6] = c2 / d; o[7] = (m[1] * m[6] - m[0] * m[7]) / d; o[8] = (m[0] * m[4] - m[1] * m[3]) / d;
+}
+// RGB -> XYZ of a set of primaries (x, y of R, G, B) and the D65 white point: the columns are the primaries' XYZ, scaled so that
+// RGB = (1, 1, 1) is the white
+inline void yuv_transfer_rgb_to_xyz(const double* xy6, double* M9) {
+    double P[9], W[3] = {0.3127 / 0.3290, 1.0, (1.0 - 0.3127 - 0.3290) / 0.3290};
+    for (int c = 0; c < 3; ++c) { P[c] = xy6[2 * c] / xy6[2 * c + 1]; P[3 + c] = 1.0; P[6 + c] = (1.0 - xy6[2 * c] - xy6[2 * c + 1]) / xy6[2 * c + 1]; }
+    double I[9];
+    mat3_inverse(P, I);
+    for (int c = 0; c < 3; ++c) {
+        const double s = I[3 * c] * W[0] + I[3 * c + 1] * W[1] + I[3 * c + 2] * W[2];
+        for (int r = 0; r < 3; ++r) M9[3 * r + c] = P[3 * r + c] * s;
+    }
+}
+// step 4: BT.2020 -> BT.709 linear light, off the diagonal rint(G 2^14), the diagonal such that every row sums to 2^14
+inline void yuv_transfer_gamut(int32_t* out9) {
+    static const double P709[6] = {0.640, 0.330, 0.300, 0.600, 0.150, 0.060}, P2020[6] = {0.708, 0.292, 0.170, 0.797, 0.131, 0.046};
+    double A[9], B[9], Ai[9];
+    yuv_transfer_rgb_to_xyz(P709, A);
+    yuv_transfer_rgb_to_xyz(P2020, B);
+    mat3_inverse(A, Ai);
+    for (int r = 0; r < 3; ++r) {
+        int32_t off = 0;
+        for (int c = 0; c < 3; ++c) {
+            if (c == r) continue;
+            const double g = Ai[3 * r] * B[c] + Ai[3 * r + 1] * B[3 + c] + Ai[3 * r + 2] * B[6 + c];
+            out9[3 * r + c] = (int32_t)std::rint(g * (double)(1 << YUV_TR_GAMUT_SHIFT));
+            off += out9[3 * r + c];
+        }
+        out9[3 * r + r] = (1 << YUV_TR_GAMUT_SHIFT) - off;
+    }
+}
+// the display light in nits of the signal e in 0..1: ST 2084's EOTF; HLG's inverse OETF with the 1.2 system gamma of a nominal
+// 1000-nit display, per channel
+inline double yuv_transfer_nits(int transfer, double e) {
+    if (transfer == SLIDEO_YUV_TRANSFER_PQ) {
+        const double m1 = 2610.0 / 16384.0, m2 = 2523.0 / 4096.0 * 128.0, c1 = 3424.0 / 4096.0, c2 = 2413.0 / 4096.0 * 32.0, c3 = 2392.0 / 4096.0 * 32.0;
+        const double p = std::pow(e, 1.0 / m2);
+        return 10000.0 * std::pow(std::max(p - c1, 0.0) / (c2 - c3 * p), 1.0 / m1);
+    }
+    const double a = 0.17883277, b = 0.28466892, c = 0.55991073;
+    const double E = e <= 0.5 ? e * e / 3.0 : (std::exp((e - c) / a) + b) / 12.0;
+    return 1000.0 * std::pow(E, 1.2);
+}
+// steps 3 and 5: LIN[i] = rint(16383 min(1, nits(i / 1023) / white_nits)), OUT[i] = rint(255 srgb_oetf(i / 4095)).  white_nits as
+// resolved (never 0)
+inline void yuv_transfer_lin_out(int transfer, double white_nits, uint16_t* lin1024, uint8_t* out4096) {
+    for (int i = 0; i < YUV_TR_LIN; ++i)
+        lin1024[i] = (uint16_t)std::rint((double)YUV_TR_WHITE * std::min(1.0, yuv_transfer_nits(transfer, (double)i / 1023.0) / white_nits));
+    for (int i = 0; i < YUV_TR_OUT; ++i) {
+        const double l = (double)i / 4095.0;
+        out4096[i] = (uint8_t)std::rint(255.0 * (l <= 0.0031308 ? 12.92 * l : 1.055 * std::pow(l, 1.0 / 2.4) - 0.055));
+    }
+}
+// slideo_yuv_transfer_tables: the whole definition; every output may be null.  false: not a transfer with tables (SDR has none), not
+// a range, or nits outside the setter's rule
+inline bool yuv_transfer_tables(int transfer, int range, float white_nits, int32_t* coef7, int32_t* gamut9, uint16_t* lin1024, uint8_t* out4096) {
+    if (transfer != SLIDEO_YUV_TRANSFER_HLG && transfer != SLIDEO_YUV_TRANSFER_PQ) return false;
+    if (range != SLIDEO_YUV_RANGE_LIMITED && range != SLIDEO_YUV_RANGE_FULL) return false;
+    if (!(white_nits == 0.f) && !(std::isfinite(white_nits) && white_nits >= 1.f && white_nits <= 10000.f)) return false;
+    if (coef7) yuv_transfer_coefficients(range, coef7);
+    if (gamut9) yuv_transfer_gamut(gamut9);
+    if (lin1024 || out4096) {
+        uint16_t lin[YUV_TR_LIN];
+        uint8_t out[YUV_TR_OUT];
+        yuv_transfer_lin_out(transfer, white_nits == 0.f ? 203.0 : (double)white_nits, lin, out);
+        if (lin1024) std::copy(lin, lin + YUV_TR_LIN, lin1024);
+        if (out4096) std::copy(out, out + YUV_TR_OUT, out4096);
+    }
+    return true;
+}
+
 // The layout rules of include/slideo_amd.h "YUV 4:2:0 frames" for samples of `bps` bytes (1; 2: the 16-bit containers of "YUV
 // colour description", whose rules count two bytes per sample); returns the bytes of one frame (its furthest byte + 1).
 // frame_stride < 0: a single frame, no stride to check.  `sampling` other than 420: the rules of "YUV sampling"
@@ -587,6 +695,15 @@ inline void frame_settings_rules(const FrameSettings& next, Setting what, bool s
     if (next.yuv.sampling == SLIDEO_YUV_SAMPLING_422_PACKED && next.yuv.depth != SLIDEO_YUV_DEPTH_8)
         fail(SLIDEO_ERR_UNSUPPORTED, "SLIDEO_YUV_SAMPLING_422_PACKED reads 8-bit samples: not together with a 10-bit depth (%d); packed 10-bit "
              "formats (Y210, v210) are not supported", next.yuv.depth);
+    // a transfer reads 10-bit samples in full: whichever of the two set calls (transfer, description) would complete the pair is refused
+    if (next.yuv.transfer != SLIDEO_YUV_TRANSFER_SDR && next.yuv.depth == SLIDEO_YUV_DEPTH_8)
+        fail(SLIDEO_ERR_UNSUPPORTED, "a YUV transfer (%d) reads 10-bit samples: not together with SLIDEO_YUV_DEPTH_8 (and so not with "
+             "SLIDEO_YUV_SAMPLING_422_PACKED, which is 8-bit); slideo_matcher_set_yuv_description with a 10-bit depth first", next.yuv.transfer);
+    // bilinear chroma under a transfer is out of scope: whichever of the three set calls (transfer, chroma filter, sampling) would
+    // complete the combination is refused
+    if (next.yuv.transfer != SLIDEO_YUV_TRANSFER_SDR && next.yuv.filtered())
+        fail(SLIDEO_ERR_UNSUPPORTED, "a YUV transfer (%d) together with the chroma filter %d under sampling %d: bilinear chroma under a transfer "
+             "is out of scope (SLIDEO_YUV_CHROMA_NEAREST, or 4:4:4 frames)", next.yuv.transfer, next.yuv.chroma, next.yuv.sampling);
 }
 
 }  // namespace slideo

@@ -442,6 +442,9 @@ struct slideo_matcher {
     // matcher is idle), and the levels histogram — "none" (on false) or the per-channel counts (u64 [3][256], d_lv_hist) of `frames`
     // analysed images of `pixels` pixels in all, of any sizes.  The observe calls feed it beside the other two accumulators
     slideo::DevBuf d_levels;
+    // YUV transfer (include/slideo_amd.h "YUV transfer"): the device copy of LIN (uint16 [1024]) and OUT (uint8 [4096]) of
+    // (fs.yuv.transfer, fs.yuv.white_nits), 6144 bytes, rewritten by settings_commit while the matcher is idle
+    slideo::DevBuf d_transfer;
     struct Levels { bool on = false; int64_t frames = 0, pixels = 0; } levels;
     slideo::DevBuf d_lv_hist;
 
@@ -563,8 +566,10 @@ void launch_rectify(const FrameRegion& R, const uint8_t* src, int64_t src_fs, in
 // the rectify_kernel instance of a map: R.kind, R.tx, R.ty from R.M
 void frame_region_classify(FrameRegion& R);
 // n decoded YUV 4:2:0 frames (a layout yuv420_validate accepted under `desc`, frame stride src_fs) -> BGR8 at dst, stride 3w, frame
-// stride 3wh.  The default description: yuv420_to_bgr_kernel; any other: yuv420_to_bgr_desc_kernel
-void launch_yuv420_to_bgr(const YuvDesc& desc, const uint8_t* src, int64_t src_fs, const slideo_yuv420_layout& L, int w, int h, int n, uint8_t* dst, hipStream_t st);
+// stride 3wh.  The default description: yuv420_to_bgr_kernel; any other: yuv420_to_bgr_desc_kernel.  transfer_tab: the matcher's
+// d_transfer, read under a transfer other than SDR alone (yuv_transfer_to_bgr_kernel)
+void launch_yuv420_to_bgr(const YuvDesc& desc, const uint8_t* src, int64_t src_fs, const slideo_yuv420_layout& L, int w, int h, int n, uint8_t* dst, hipStream_t st,
+                          const uint32_t* transfer_tab = nullptr);
 // n frames under the pixel format `format` (not SLIDEO_PIXEL_BGR8; a layout pixel_format_validate accepted, rows `stride` and frames
 // src_fs apart) -> BGR8 at dst, stride 3w, frame stride 3wh: pixels_to_bgr_kernel (pixel_format.hip.h)
 void launch_pixels_to_bgr(int format, const uint8_t* src, int64_t src_fs, int stride, int w, int h, int n, uint8_t* dst, hipStream_t st);

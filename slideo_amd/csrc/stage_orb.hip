@@ -1,11 +1,12 @@
 // stage_orb.hip — drivers of the ORB stage (kernels: orb.hip.h) and of the front doors in front of it: YUV frames
-// (yuv420.hip.h, yuv_sampling.hip.h, yuv_chroma.hip.h), frames of another pixel format (pixel_format.hip.h), the frame levels' table (levels.hip.h), the working-size reduce (reduce.hip.h) and the frame region's rectify (frame_region.hip.h); the frame mask's
+// (yuv420.hip.h, yuv_sampling.hip.h, yuv_chroma.hip.h, yuv_transfer.hip.h), frames of another pixel format (pixel_format.hip.h), the frame levels' table (levels.hip.h), the working-size reduce (reduce.hip.h) and the frame region's rectify (frame_region.hip.h); the frame mask's
 // pyramid and candidate filter (frame_mask.hip.h).
 #include "runtime.hpp"
 #include "orb.hip.h"
 #include "yuv420.hip.h"
 #include "yuv_sampling.hip.h"
 #include "yuv_chroma.hip.h"
+#include "yuv_transfer.hip.h"
 #include "pixel_format.hip.h"
 #define LEVELS_APPLY_KERNEL      // (levels_hist_kernel is stage_activity.hip's)
 #include "levels.hip.h"
@@ -133,11 +134,41 @@ static void launch_yuv_chroma(const YuvDesc& desc, const uint8_t* src, int64_t s
     check_launch("yuv_chroma_to_bgr_kernel");
 }
 
+// 10-bit frames under a transfer other than SDR ("YUV transfer"): the thread shapes of the nearest kernels; tab: the matcher's device
+// copy of LIN and OUT.  The description's matrix is not consulted
+static void launch_yuv_transfer(const YuvDesc& desc, const uint8_t* src, int64_t src_fs, const slideo_yuv420_layout& L, int w, int h, int n, uint8_t* dst,
+                                hipStream_t st, const uint32_t* tab32) {
+    const uint4* tab = reinterpret_cast<const uint4*>(tab32);
+    const int d = desc.depth, s = desc.sampling;
+    if (!tab || d == SLIDEO_YUV_DEPTH_8 || s == SLIDEO_YUV_SAMPLING_422_PACKED || desc.filtered())
+        fail(SLIDEO_ERR_HIP, "internal: no transfer kernel for transfer %d under depth %d, sampling %d, chroma filter %d", desc.transfer, d, s, desc.chroma);
+    const YuvTransferArgs a = yuv_transfer_args(src, src_fs, L, w, h, n, dst);
+    int32_t c[7];
+    YuvTransferCoef k{};
+    yuv_transfer_coefficients(desc.range, c);
+    k.cy = c[0]; k.cub = c[1]; k.cug = c[2]; k.cvg = c[3]; k.cvr = c[4]; k.yofs = c[5];
+    yuv_transfer_gamut(k.g);
+    const bool s420 = s == SLIDEO_YUV_SAMPLING_420, msb = d == SLIDEO_YUV_DEPTH_10_MSB;
+    const dim3 grid(cdiv(cdiv(w, 4), YUV_TX), cdiv(s420 ? h / 2 : h, YUV_TY * YUV_TRK_ROWS), n), block(YUV_TX, YUV_TY);
+    if (s420) {
+        if (msb) yuv_transfer_to_bgr_kernel<YUV_T420, YUV_D10_MSB><<<grid, block, 0, st>>>(a, k, tab);
+        else yuv_transfer_to_bgr_kernel<YUV_T420, YUV_D10_LSB><<<grid, block, 0, st>>>(a, k, tab);
+    } else if (s == SLIDEO_YUV_SAMPLING_422) {
+        if (msb) yuv_transfer_to_bgr_kernel<YUV_S422, YUV_D10_MSB><<<grid, block, 0, st>>>(a, k, tab);
+        else yuv_transfer_to_bgr_kernel<YUV_S422, YUV_D10_LSB><<<grid, block, 0, st>>>(a, k, tab);
+    } else {
+        if (msb) yuv_transfer_to_bgr_kernel<YUV_S444, YUV_D10_MSB><<<grid, block, 0, st>>>(a, k, tab);
+        else yuv_transfer_to_bgr_kernel<YUV_S444, YUV_D10_LSB><<<grid, block, 0, st>>>(a, k, tab);
+    }
+    check_launch("yuv_transfer_to_bgr_kernel");
+}
+
 // n decoded YUV frames (validated layout, frame stride src_fs) -> BGR8 at dst (stride 3w, frame stride 3wh).  Under the 4:2:0
-// sampling exactly what it launched before the sampling existed, and under the NEAREST chroma filter, or 4:4:4, exactly what it
-// launched before the filter existed
+// sampling exactly what it launched before the sampling existed, under the NEAREST chroma filter, or 4:4:4, exactly what it
+// launched before the filter existed, and under the SDR transfer exactly what it launched before the transfer existed
 void launch_yuv420_to_bgr(const YuvDesc& desc, const uint8_t* src, int64_t src_fs, const slideo_yuv420_layout& L, int w, int h, int n, uint8_t* dst,
-                          hipStream_t st) {
+                          hipStream_t st, const uint32_t* transfer_tab) {
+    if (desc.transfer != SLIDEO_YUV_TRANSFER_SDR) { launch_yuv_transfer(desc, src, src_fs, L, w, h, n, dst, st, transfer_tab); return; }
     if (desc.filtered()) { launch_yuv_chroma(desc, src, src_fs, L, w, h, n, dst, st); return; }
     if (desc.sampling != SLIDEO_YUV_SAMPLING_420) { launch_yuv_sampled(desc, src, src_fs, L, w, h, n, dst, st); return; }
     dim3 grid(cdiv(cdiv(w, 4), YUV_TX), cdiv(h / 2, YUV_TY), n);

@@ -415,6 +415,10 @@ public:
     // filter"): SLIDEO_YUV_CHROMA_NEAREST (default: cvtColor's rule), _BILINEAR_LEFT (H.264 / HEVC / MPEG-2 siting), _BILINEAR_CENTER
     // (JPEG, MPEG-1) or _BILINEAR_TOPLEFT (BT.2020).  The reference's swscale path takes the nearest sample
     HipImageVideoMatcher& with_yuv_chroma(int32_t filter) { yuv_chroma_ = filter; return *this; }
+    // HDR frames to SDR (slideo_group_set_yuv_transfer, include/slideo_amd.h "YUV transfer"): SLIDEO_YUV_TRANSFER_SDR (default),
+    // _HLG or _PQ, both BT.2020; white_nits: the display light that becomes SDR white (0 = 203).  Needs a 10-bit depth and nearest
+    // chroma (or 4:4:4).  The reference knows no HDR
+    HipImageVideoMatcher& with_yuv_transfer(int32_t transfer, float white_nits = 0.f) { yuv_transfer_ = transfer; yuv_white_nits_ = white_nits; return *this; }
     // How the frames of the BGR door are read (slideo_group_set_pixel_format, include/slideo_amd.h "Frame pixel format"):
     // SLIDEO_PIXEL_BGR8 (default), _RGB8, the four-byte _BGRA8 / _RGBA8 / _ARGB8 / _ABGR8 of screen-capture APIs, or the planar
     // _PLANAR_RGB8 / _PLANAR_BGR8 / _PLANAR_GBR8.  The frame source then hands out frames in that format; pages stay BGR.  The
@@ -480,6 +484,7 @@ public:
             h->check(slideo_group_set_yuv_description(h->g, yuv_matrix_, yuv_range_, yuv_depth_));
         if (yuv_sampling_ != SLIDEO_YUV_SAMPLING_420) h->check(slideo_group_set_yuv_sampling(h->g, yuv_sampling_));
         if (yuv_chroma_ != SLIDEO_YUV_CHROMA_NEAREST) h->check(slideo_group_set_yuv_chroma(h->g, yuv_chroma_));
+        if (yuv_transfer_ != SLIDEO_YUV_TRANSFER_SDR) h->check(slideo_group_set_yuv_transfer(h->g, yuv_transfer_, yuv_white_nits_));
         if (pixel_format_ != SLIDEO_PIXEL_BGR8) h->check(slideo_group_set_pixel_format(h->g, pixel_format_));
         if (!frame_levels_.empty()) h->check(slideo_group_set_frame_levels(h->g, frame_levels_.data()));
         if (mask_scope_ != SLIDEO_MASK_DETECT) h->check(slideo_group_set_frame_mask_scope(h->g, mask_scope_));
@@ -511,6 +516,8 @@ private:
     int32_t yuv_matrix_ = SLIDEO_YUV_MATRIX_BT601, yuv_range_ = SLIDEO_YUV_RANGE_LIMITED, yuv_depth_ = SLIDEO_YUV_DEPTH_8;
     int32_t yuv_sampling_ = SLIDEO_YUV_SAMPLING_420;
     int32_t yuv_chroma_ = SLIDEO_YUV_CHROMA_NEAREST;
+    int32_t yuv_transfer_ = SLIDEO_YUV_TRANSFER_SDR;
+    float yuv_white_nits_ = 0.f;
     int32_t pixel_format_ = SLIDEO_PIXEL_BGR8;
     std::vector<uint8_t> frame_levels_;
     uint32_t mask_scope_ = SLIDEO_MASK_DETECT, direct_scope_ = SLIDEO_DIRECT_WHOLE, gate_ref_ = SLIDEO_GATE_PREVIOUS;

@@ -405,7 +405,8 @@ class HipImageVideoMatcher:
 
     def __init__(self, cfg=None, device=None, sift=None, devices=None, working_size=None, frame_mask=None, frame_mask_scope=None,
                  direct_similarity=None, direct_scope=None, frame_region=None, yuv_description=None, gate_reference=None, gate_settle=None,
-                 group_gate_order=None, yuv_sampling=None, gate_memory=None, pixel_format=None, frame_levels=None, yuv_chroma=None):
+                 group_gate_order=None, yuv_sampling=None, gate_memory=None, pixel_format=None, frame_levels=None, yuv_chroma=None,
+                 yuv_transfer=None):
         """devices: HIP ordinals, one matcher each behind one slideo_group (the reference fans out over the whole machine, the
         global rayon pool of lib.rs:45,174); None = every gfx950 device of the node; `device` = d is short for devices = [d].
         sift = (slideo_sift_config, ratio): the north-star's SIFT + L2 front end instead of the reference's ORB + Hamming
@@ -440,6 +441,10 @@ class HipImageVideoMatcher:
         yuv_chroma = "nearest" | "left" | "center" | "topleft" (slideo_group_set_yuv_chroma): how a pixel's chroma is read from 4:2:0
         and 4:2:2 frames — "left" is the bilinear filter at the siting of H.264 / HEVC / MPEG-2 streams, "center" JPEG's and MPEG-1's,
         "topleft" BT.2020's; cvtColor and the reference's swscale path take the nearest sample; None = nearest.
+        yuv_transfer = ("hlg" | "pq" | "sdr", white_nits) or the name alone (slideo_group_set_yuv_transfer): HDR frames — HLG / BT.2020
+        of phones, PQ / BT.2020 of HDR screen recorders and capture — are converted to SDR on the GPU: full 10-bit samples, the
+        BT.2020 matrix, linear light with white_nits (0 = 203) as SDR white, BT.2020 -> BT.709, sRGB; needs a 10-bit yuv_description;
+        the reference knows no HDR; None = SDR.
         pixel_format = "bgr" | "rgb" | "bgra" | "rgba" | "argb" | "abgr" | "planar_rgb" | "planar_bgr" | "planar_gbr"
         (slideo_group_set_pixel_format): how the frames of the BGR door are read.  The frame source then yields frames in that
         format — [h, w, 3], [h, w, 4] or [3, h, w] — and no swizzle pass runs on the host; page images stay BGR; the reference only
@@ -472,6 +477,7 @@ class HipImageVideoMatcher:
         self._yuv_description = tuple(yuv_description) if yuv_description is not None else None
         self._yuv_sampling = yuv_sampling
         self._yuv_chroma = yuv_chroma
+        self._yuv_transfer = (yuv_transfer, 0) if isinstance(yuv_transfer, (str, int)) else tuple(yuv_transfer) if yuv_transfer is not None else None
         self._pixel_format = pixel_format
         self._frame_levels = frame_levels
         self._gate_reference = gate_reference
@@ -504,6 +510,8 @@ class HipImageVideoMatcher:
             m.set_yuv_sampling(self._yuv_sampling)
         if self._yuv_chroma is not None:
             m.set_yuv_chroma(self._yuv_chroma)
+        if self._yuv_transfer is not None:
+            m.set_yuv_transfer(*self._yuv_transfer)
         if self._pixel_format is not None:
             m.set_pixel_format(self._pixel_format)
         if self._frame_levels is not None:

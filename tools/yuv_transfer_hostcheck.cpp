@@ -1,0 +1,173 @@
+// yuv_transfer_hostcheck — the per-thread body of csrc/yuv_transfer.hip.h (yuv_transfer_thread, compiled for the host) run lane by
+// lane over the whole launch grid, and the host rules of csrc/frame_settings.h that go with "YUV transfer", for
+// tests/test_yuv_transfer_abi.py, which compares the outcome with tests/yuv_transfer_ref.py.  The kernel's LDS tables are a plain
+// array here.
+//   g++ -O1 -g -std=c++17 [-fsanitize=address,undefined] -I include -I slideo_amd/csrc tools/yuv_transfer_hostcheck.cpp -o hostcheck
+//   hostcheck convert <cases> <out>
+//       <cases>: any number of records, each int32 {w, h, n, transfer, range, depth, sampling, y_stride, uv_stride, uv_step,
+//       white_nits (the float's bits), data bytes}, int64 {u_offset, v_offset, frame_stride}, then `data bytes` of frames, of which
+//       the first (n - 1) * frame_stride + span are the frames' (the rest is padding behind the last frame).  <out>: per record n
+//       images of h x w x 3.
+//       Every record is converted with its source 0, 1, 2, 4 and 8 bytes past the 16-byte aligned base of an allocation that ends
+//       with the last frame byte, into an exact-size destination, with tables in exact-size allocations: a load or store past any
+//       end is the sanitizer's to report, and so is a wide load at an address that is not a multiple of its size.  The five images
+//       must agree (exit 4 if not); the first is written.  Prints how often each load and store path was taken.
+//   hostcheck set <op> <value> ...      op: t <transfer> <white_nits> | c <filter> | s <sampling> | d <matrix> <range> <depth>
+//       walks the set calls in order over one FrameSettings as settings_commit does (proposal, then the rules between settings; a
+//       refused call leaves the record as it was) and prints per call "<code> <message>", then "state matrix range depth sampling
+//       filter transfer white_nits"
+//   hostcheck tables <transfer> <range> <white_nits>      prints "<code>", then coef7, gamut9, LIN and OUT, one line each
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+struct Hits {
+    long y8, y4, y_bytes, c8, c4, c_bytes, out4, out_bytes;
+};
+static Hits g_hits;
+#define YUV_TRANSFER_HIT(path) (++g_hits.path)
+
+#include "frame_settings.h"
+#include "yuv_transfer.hip.h"
+
+using namespace slideo;
+
+namespace {
+
+template <int SAMPLING, int DEPTH>
+void run_grid(const YuvTransferArgs& a, const YuvTransferCoef& k, const uint16_t* lin, const uint8_t* out, int n) {
+    const int rows = SAMPLING == YUV_T420 ? a.h / 2 : a.h;
+    const int gx = ((a.w + 3) / 4 + YUV_TX - 1) / YUV_TX, gy = (rows + YUV_TY - 1) / YUV_TY;
+    for (int z = 0; z < n; ++z)
+        for (int by = 0; by < gy; ++by)
+            for (int bx = 0; bx < gx; ++bx)
+                for (int ty = 0; ty < YUV_TY; ++ty)
+                    for (int tx = 0; tx < YUV_TX; ++tx) yuv_transfer_thread<SAMPLING, DEPTH>(a, k, lin, out, bx * YUV_TX + tx, by * YUV_TY + ty, z);
+}
+
+template <int SAMPLING>
+void run_depth(int depth, const YuvTransferArgs& a, const YuvTransferCoef& k, const uint16_t* lin, const uint8_t* out, int n) {
+    if (depth == SLIDEO_YUV_DEPTH_10_MSB) run_grid<SAMPLING, YUV_D10_MSB>(a, k, lin, out, n);
+    else run_grid<SAMPLING, YUV_D10_LSB>(a, k, lin, out, n);
+}
+
+int convert(const char* in, const char* outp) {
+    FILE* f = std::fopen(in, "rb");
+    FILE* fo = std::fopen(outp, "wb");
+    if (!f || !fo) return 2;
+    int32_t hd[12];
+    int64_t of[3];
+    long records = 0;
+    while (std::fread(hd, 4, 12, f) == 12) {
+        if (std::fread(of, 8, 3, f) != 3) return 2;
+        const int w = hd[0], h = hd[1], n = hd[2], transfer = hd[3], range = hd[4], depth = hd[5], sampling = hd[6];
+        float nits;
+        std::memcpy(&nits, &hd[10], 4);
+        slideo_yuv420_layout L{};
+        L.y_stride = hd[7]; L.uv_stride = hd[8]; L.uv_step = hd[9]; L.u_offset = of[0]; L.v_offset = of[1];
+        const int64_t fs = of[2];
+        int64_t span = 0;
+        FrameSettings s;
+        try {
+            // (the matrix is not consulted under a transfer: any will do)
+            s = propose_yuv_description(FrameSettings{}, SLIDEO_YUV_MATRIX_BT709, range, depth);
+            frame_settings_rules(s, SET_YUV_DESCRIPTION, false);
+            s = propose_yuv_sampling(s, sampling);
+            frame_settings_rules(s, SET_YUV_DESCRIPTION, false);
+            s = propose_yuv_transfer(s, transfer, nits);
+            frame_settings_rules(s, SET_YUV_DESCRIPTION, false);
+            if (s.yuv.transfer == SLIDEO_YUV_TRANSFER_SDR) fail(SLIDEO_ERR_INVALID_ARG, "SLIDEO_YUV_TRANSFER_SDR launches another kernel");
+            span = yuv420_validate(w, h, &L, n > 1 ? fs : -1, s.yuv.bytes_per_sample(), sampling);
+        } catch (const Error& e) { std::fprintf(stderr, "record %ld: %d %s\n", records, e.code, e.what()); return 3; }
+        const size_t total = (size_t)(fs * (n - 1) + span);
+        if (hd[11] < 0 || (size_t)hd[11] < total) return 2;
+        std::vector<uint8_t> frames((size_t)hd[11]);
+        if (std::fread(frames.data(), 1, frames.size(), f) != frames.size()) return 2;
+        int32_t c[7];
+        YuvTransferCoef k{};
+        // exact-size tables, as the kernel's LDS arrays are
+        uint16_t* lin = static_cast<uint16_t*>(std::malloc(2 * YUV_TR_LIN));
+        uint8_t* out = static_cast<uint8_t*>(std::malloc(YUV_TR_OUT));
+        if (!lin || !out || !yuv_transfer_tables(transfer, range, nits, c, k.g, lin, out)) return 3;
+        k.cy = c[0]; k.cub = c[1]; k.cug = c[2]; k.cvg = c[3]; k.cvr = c[4]; k.yofs = c[5];
+        const size_t ob = (size_t)w * h * 3 * n;
+        std::vector<uint8_t> first;
+        static const int OFS[5] = {0, 1, 2, 4, 8};
+        for (int o = 0; o < 5; ++o) {
+            // malloc's blocks are 16-byte aligned: the source starts OFS[o] bytes in and ends with the block
+            uint8_t* exact = static_cast<uint8_t*>(std::malloc(OFS[o] + total));
+            uint8_t* dst = static_cast<uint8_t*>(std::malloc(ob));
+            if (!exact || !dst || (uintptr_t)exact % 16 != 0) return 2;
+            std::memcpy(exact + OFS[o], frames.data(), total);
+            std::memset(dst, 0xA5, ob);
+            const YuvTransferArgs a = yuv_transfer_args(exact + OFS[o], fs, L, w, h, n, dst);
+            if (sampling == SLIDEO_YUV_SAMPLING_420) run_depth<YUV_T420>(depth, a, k, lin, out, n);
+            else if (sampling == SLIDEO_YUV_SAMPLING_422) run_depth<YUV_S422>(depth, a, k, lin, out, n);
+            else run_depth<YUV_S444>(depth, a, k, lin, out, n);
+            if (o == 0) first.assign(dst, dst + ob);
+            else if (std::memcmp(first.data(), dst, ob) != 0) {
+                std::fprintf(stderr, "record %ld: the image at source offset %d differs from the one at offset 0\n", records, OFS[o]);
+                return 4;
+            }
+            std::free(dst);
+            std::free(exact);
+        }
+        std::free(lin);
+        std::free(out);
+        if (std::fwrite(first.data(), 1, ob, fo) != ob) return 2;
+        ++records;
+    }
+    std::fclose(f);
+    std::fclose(fo);
+    const Hits& g = g_hits;
+    std::printf("records %ld\ny8 %ld\ny4 %ld\ny_bytes %ld\nc8 %ld\nc4 %ld\nc_bytes %ld\nout4 %ld\nout_bytes %ld\n", records, g.y8, g.y4, g.y_bytes, g.c8, g.c4,
+                g.c_bytes, g.out4, g.out_bytes);
+    return 0;
+}
+
+}  // namespace
+
+int main(int argc, char** argv) {
+    if (argc >= 4 && !std::strcmp(argv[1], "convert")) return convert(argv[2], argv[3]);
+    if (argc >= 5 && !std::strcmp(argv[1], "tables")) {
+        int32_t c[7] = {}, g[9] = {};
+        std::vector<uint16_t> lin(YUV_TR_LIN);
+        std::vector<uint8_t> out(YUV_TR_OUT);
+        const bool ok = yuv_transfer_tables(std::atoi(argv[2]), std::atoi(argv[3]), (float)std::atof(argv[4]), c, g, lin.data(), out.data());
+        std::printf("%d\n", ok ? 0 : 1);
+        for (int i = 0; i < 7; ++i) std::printf("%d ", c[i]);
+        std::printf("\n");
+        for (int i = 0; i < 9; ++i) std::printf("%d ", g[i]);
+        std::printf("\n");
+        for (int i = 0; i < YUV_TR_LIN; ++i) std::printf("%d ", (int)lin[i]);
+        std::printf("\n");
+        for (int i = 0; i < YUV_TR_OUT; ++i) std::printf("%d ", (int)out[i]);
+        std::printf("\n");
+        return 0;
+    }
+    if (argc >= 2 && !std::strcmp(argv[1], "set")) {
+        FrameSettings s{};
+        for (int i = 2; i < argc;) {
+            const char op = argv[i][0];
+            const int at = i;
+            i += op == 'd' ? 4 : op == 't' ? 3 : 2;
+            if ((op != 't' && op != 'c' && op != 's' && op != 'd') || argv[at][1] || i > argc) return 2;
+            try {
+                const FrameSettings next = op == 't'   ? propose_yuv_transfer(s, std::atoi(argv[at + 1]), (float)std::atof(argv[at + 2]))
+                                           : op == 'c' ? propose_yuv_chroma(s, std::atoi(argv[at + 1]))
+                                           : op == 's' ? propose_yuv_sampling(s, std::atoi(argv[at + 1]))
+                                                       : propose_yuv_description(s, std::atoi(argv[at + 1]), std::atoi(argv[at + 2]), std::atoi(argv[at + 3]));
+                frame_settings_rules(next, SET_YUV_DESCRIPTION, false);
+                s = next;
+                std::printf("0 ok\n");
+            } catch (const Error& e) { std::printf("%d %s\n", e.code, e.what()); }
+        }
+        std::printf("state %d %d %d %d %d %d %g\n", s.yuv.matrix, s.yuv.range, s.yuv.depth, s.yuv.sampling, s.yuv.chroma, s.yuv.transfer,
+                    (double)s.yuv.white_nits);
+        return 0;
+    }
+    std::fprintf(stderr, "usage: %s convert <cases> <out> | tables <transfer> <range> <white_nits> | set (t <transfer> <white_nits> | c <filter> | "
+                         "s <sampling> | d <matrix> <range> <depth>) ...\n", argv[0]);
+    return 2;
+}
