@@ -635,6 +635,81 @@ extern "C" {
         out: *mut u8,
         out_capacity: i64,
     ) -> i32;
+    // match evidence map (include/slideo_amd.h "Match evidence map"): where the keypoints of matched frames fall and which of them the
+    // winning page's transform explains; the mask and the box made of the counts
+    pub fn slideo_matcher_evidence_begin(m: *mut slideo_matcher, cell: i32, min_inliers: i32) -> i32;
+    pub fn slideo_matcher_evidence_end(m: *mut slideo_matcher) -> i32;
+    pub fn slideo_matcher_evidence_info(
+        m: *mut slideo_matcher,
+        cell: *mut i32,
+        min_inliers: *mut i32,
+        aw: *mut i32,
+        ah: *mut i32,
+        gw: *mut i32,
+        gh: *mut i32,
+        frames_through: *mut i64,
+        frames_counted: *mut i64,
+    ) -> i32;
+    pub fn slideo_matcher_evidence_counts(
+        m: *mut slideo_matcher,
+        seen_out: *mut u32,
+        hit_out: *mut u32,
+        capacity_elems: i64,
+        gw: *mut i32,
+        gh: *mut i32,
+        frames_through: *mut i64,
+        frames_counted: *mut i64,
+    ) -> i32;
+    pub fn slideo_group_evidence_begin(g: *mut slideo_group, cell: i32, min_inliers: i32) -> i32;
+    pub fn slideo_group_evidence_end(g: *mut slideo_group) -> i32;
+    pub fn slideo_group_evidence_info(
+        g: *mut slideo_group,
+        cell: *mut i32,
+        min_inliers: *mut i32,
+        aw: *mut i32,
+        ah: *mut i32,
+        gw: *mut i32,
+        gh: *mut i32,
+        frames_through: *mut i64,
+        frames_counted: *mut i64,
+    ) -> i32;
+    pub fn slideo_group_evidence_counts(
+        g: *mut slideo_group,
+        seen_out: *mut u32,
+        hit_out: *mut u32,
+        capacity_elems: i64,
+        gw: *mut i32,
+        gh: *mut i32,
+        frames_through: *mut i64,
+        frames_counted: *mut i64,
+    ) -> i32;
+    pub fn slideo_evidence_mask(
+        seen: *const u32,
+        hit: *const u32,
+        gw: i32,
+        gh: i32,
+        cell: i32,
+        aw: i32,
+        ah: i32,
+        min_seen: i64,
+        min_hit_ppm: i32,
+        grow: i32,
+        mask_out: *mut u8,
+        stride_bytes: i64,
+    ) -> i32;
+    pub fn slideo_evidence_box(
+        seen: *const u32,
+        hit: *const u32,
+        gw: i32,
+        gh: i32,
+        cell: i32,
+        aw: i32,
+        ah: i32,
+        min_hits: i64,
+        min_hit_ppm: i32,
+        box_out4: *mut i32,
+    ) -> i32;
+    pub fn slideo_matcher_rng_stream_len(m: *const slideo_matcher, len: *mut i64) -> i32;
     // frame activity map (include/slideo_amd.h "Frame activity map"): per-pixel counts of moved pairs, and the mask read out of them
     pub fn slideo_matcher_activity_begin(m: *mut slideo_matcher, delta: i32) -> i32;
     pub fn slideo_matcher_activity_end(m: *mut slideo_matcher) -> i32;

@@ -62,6 +62,7 @@
  *   SLIDEO_SIFT_WS_MB n           SIFT pyramid budget per pass (98304 on a device with >= 192 GB, else 24576)  [per call]
  *   SLIDEO_SIFT_LIST_CAP n        start capacity of SIFT's per-frame extrema list (65536; the tests force its growth path) [per call]
  *   SLIDEO_RNG_STREAM_LEN n       start length of the pre-drawn cv::RNG stream (the tests force its growth path)
+ *   SLIDEO_EVIDENCE_MAX_FRAMES n  the frames limit of an evidence session, read at evidence_begin, 1..2^20 (the tests reach the refusal with it)
  *   SLIDEO_RANSAC_WINDOW=0        ransac_kernel's redraw schedule by the fixed point only                       [per unit]
  *   SLIDEO_RH_TAIL_ROUNDS n       verify_model 1: rounds before a candidate moves to ransac_h_tail_kernel (256; 0 = never) [per unit]
  *   SLIDEO_REFINE_LANE_LM 0|1     verify_model 1: the small candidates' LM in refine_h_kernel<1> / in the eigen kernel's lanes [per unit]
@@ -1682,7 +1683,7 @@ int32_t     slideo_matcher_activity_mask(slideo_matcher* m, int32_t max_share_pp
  *                    returns SLIDEO_OK.
  * It is an estimator with an exact definition, not a detector: no default level, share or fill is chosen here, and nothing is
  * installed.  It finds an axis-aligned box on dark surroundings only: not a keystoned screen, not a sub-window on a background that is
- * not black, and a dark-theme slide whose rows are mostly unlit needs a low min_fill or is not found (docs/EXTENSIONS.md "Frame
+ * not black ("Match evidence map" below learns that one from the matches), and a dark-theme slide whose rows are mostly unlit needs a low min_fill or is not found (docs/EXTENSIONS.md "Frame
  * content box" says on what content it was tried).  There is no group form: the pre-pass runs on slideo_group_member(g, 0), as the
  * activity map's does; the box goes through slideo_frame_region_from_quad (corners at the pixel centres (x0, y0), (x1 - 1, y0),
  * (x1 - 1, y1 - 1), (x0, y1 - 1), the output x1 - x0 by y1 - y0) to slideo_matcher_set_frame_region / slideo_group_set_frame_region.
@@ -1808,6 +1809,100 @@ int32_t     slideo_gate_recall_walk(slideo_matcher* m, const uint64_t* dot, cons
                                     int32_t M, int64_t thr_c, int64_t thr_s, int32_t max_defer, int32_t d_in, int32_t none, int64_t t0,
                                     uint8_t* changed_out, uint64_t* ssd_out, int64_t* refs_out, int32_t* occupants_out /*64*/,
                                     int32_t* head_out, int32_t* count_out, int32_t* anchor_out, int32_t* d_out);
+
+/* ---- Match evidence map (extension: the measurement a frame mask and a frame region can be made from, out of the matches) ----------
+ * The activity map finds what moves, the content box what stands on black.  A filmed or composited lecture has neither: the slide is
+ * a sub-window, and the rest of the frame — the room, a lectern, a window's chrome, a logo strip — is static and textured.  Its
+ * keypoints take part of each pyramid level's retainBest quota and vote for arbitrary pages.  What tells slide from clutter exists
+ * after the verdicts and only on the device: where the keypoints of matched frames fall, and which of them the winning page's
+ * transform explains.
+ * A matcher carries an EVIDENCE SESSION, off by default.  Its state is "none", or: a cell (16, 32 or 64), min_inliers >= 0, an
+ * analysed size (aw, ah), not fixed until the first counted call; the grid gw = ceil(aw / cell), gh = ceil(ah / cell); seen[gh][gw]
+ * and hit[gh][gw] as u32 (device); frames_through and frames_counted.
+ * The session counts during MATCH calls (the observe calls never look at it).  Every call form that runs the verify stage counts:
+ * synchronous calls and submit / collect, host and device frames, the BGR and the YUV door, gated calls, slideo_match_kept_frames,
+ * slideo_match_frames_features_bgr8, and the group's forms through their members.  The first counted call fixes (aw, ah): the size
+ * of the image the pipeline analyses (after the frame region's rectify or the working-size reduce).  A later call at another
+ * analysed size is SLIDEO_ERR_INVALID_ARG (the message names both sizes), before anything runs.
+ *   contributes      a frame contributes iff it went through the pipeline and its verdict has page_idx >= 0 && inliers >=
+ *                    min_inliers.  Unchanged, deferred, recalled and direct frames of a gated call never went through it.
+ *                    frames_through counts the frames that went through, frames_counted those that contribute.
+ * For a contributing frame with winning page p, and M the transform of p's candidate slot exactly as slideo_last_frame_candidates
+ * returns it:
+ *   cell             keypoint q at (X, Y) (the slideo_keypoint floats) lies in cell ((int)X / cell, (int)Y / cell).  A keypoint
+ *                    outside [0, aw) x [0, ah) (only a caller's own features can hold one) has no cell and counts nowhere.
+ *   seen             seen[cell] += 1 for every keypoint of the frame.
+ *   hit              q is a hit iff some vote (q, t) of the frame with train_page[t] == p has dx*dx + dy*dy <= ransac_threshold^2
+ *                    IN FLOAT64, with (x, y) = page_xy[t] (the page keypoint's floats):
+ *                      verify_model 0: dx = M0 x + M1 y + M2 - X, dy = M3 x + M4 y + M5 - Y;
+ *                      verify_model 1: w = M6 x + M7 y + M8; w == 0: not a hit; else dx = (M0 x + M1 y + M2) / w - X, dy likewise.
+ *                    Products and sums are evaluated left to right, each rounded once (no fused multiply-add).
+ *                    hit[cell] += 1 per hit keypoint, once, however many of its votes pass.
+ * This is the library's own definition under the FINAL (refined) transform of the winner.  It is NOT RANSAC's inlier mask: that
+ * mask belongs to the sampled model before the refinement, lives in the kernel's LDS and is not kept; the sum of hit over a frame
+ * need not equal the verdict's `inliers`.
+ * Counters are u32 and a session holds at most 2^20 counted frames: a call that could take frames_counted past 2^20 (its frames
+ * and those of the units in flight counted as if all contributed) is refused with SLIDEO_ERR_INVALID_ARG and nothing runs.  (2^20
+ * frames of fewer than 4096 keypoints each cannot wrap a counter.)
+ * Installing nothing: the session changes no verdict, no trace and no setting; verdict bytes are identical with and without it.
+ * The caller reads the counts out, makes a mask or a box with the two pure functions below, looks at it, and hands it to
+ * slideo_matcher_set_frame_mask / slideo_frame_region_from_quad + slideo_matcher_set_frame_region.  No threshold has a default:
+ * they depend on the content (docs/EXTENSIONS.md "Match evidence map" says on what content it was tried).
+ * What ends a session with the state "none": slideo_matcher_evidence_end; a setter that ends the kept frames AND resets the gate
+ * (working size, frame region, YUV description, sampling, chroma, transfer, pixel format, levels: the analysed image is another);
+ * a counted call, submit or collect that fails after its first unit was submitted (a HIP error, an overflow that cannot be served),
+ * which may have counted a unit whose verdicts are never returned.  (The activity and content
+ * accumulators survive a setter and refuse at the next observe; an evidence session cannot, its grid is fixed.)  The frame mask, its
+ * scope, the direct settings, the gate reference and page sets leave the session open: a session may span a mask change.
+ * SIFT mode is out of scope: begin in SIFT mode and slideo_matcher_use_sift under an open session are SLIDEO_ERR_UNSUPPORTED.
+ * matcher 1, ratio_test, page sets (page_idx and train_page are deck indices), working size, frame region, pixel formats and levels
+ * run the same verify stage and need nothing of their own.
+ * Where it runs (csrc/evidence.hip.h, launched by csrc/stage_verify.hip unit_verify behind verdict_kernel on the unit's stream, only
+ * while a session is open): evidence_kernel, one block of 256 threads per frame — the verdict and the winner's slot, the slot's votes
+ * at qofs[f] * k + ofs[slot] tested in f64 into an LDS bitset (windows of 2048 keypoints), then the keypoints' adds, integer global
+ * atomics whose result is not read.  Integer adds commute: the four units in flight share one accumulator.  A unit that is run
+ * again (the RNG stream grew, a frame overflowed the keypoint capacity) raised its flag before verdict_kernel; the kernel reads the
+ * unit's flags word and leaves without counting, so only the run whose verdicts are returned counts.  The kernel's per-frame body
+ * is a host + device function (tools/evidence_hostcheck.cpp runs it on the CPU).
+ * Every call returns SLIDEO_ERR_INVALID_ARG for a null handle or a null required pointer. */
+/* Idle matcher, no session open (SLIDEO_ERR_STATE otherwise); cell other than 16, 32, 64 or min_inliers < 0: SLIDEO_ERR_INVALID_ARG;
+ * SIFT mode: SLIDEO_ERR_UNSUPPORTED.  Afterwards the session is empty: no size, every count 0.  May be called before finalize. */
+int32_t     slideo_matcher_evidence_begin(slideo_matcher* m, int32_t cell, int32_t min_inliers);
+/* Idle matcher.  The state "none"; the device buffer is released.  Fine when the state is "none" already. */
+int32_t     slideo_matcher_evidence_end(slideo_matcher* m);
+/* The session's values (*aw, *ah, *gw, *gh are 0 before the first counted call); the frame counts are those of the collected units.
+ * SLIDEO_ERR_STATE in the state "none". */
+int32_t     slideo_matcher_evidence_info(slideo_matcher* m, int32_t* cell, int32_t* min_inliers, int32_t* aw, int32_t* ah, int32_t* gw, int32_t* gh,
+                                         int64_t* frames_through, int64_t* frames_counted);
+/* Idle matcher (SLIDEO_ERR_STATE with units in flight, and in the state "none").  seen_out, hit_out: gh rows of gw elements each;
+ * both NULL asks for the sizes and frame counts only.  Before the first counted call *gw == *gh == 0 and nothing is written.
+ * SLIDEO_ERR_CAPACITY (with the sizes set) when gw * gh > capacity_elems. */
+int32_t     slideo_matcher_evidence_counts(slideo_matcher* m, uint32_t* seen_out, uint32_t* hit_out, int64_t capacity_elems, int32_t* gw,
+                                           int32_t* gh, int64_t* frames_through, int64_t* frames_counted);
+/* The group forms: begin and end start and end EVERY member's session (validated on every member before one is touched); info and
+ * counts return the members' element-wise sums (a member whose shards were all empty has counted nothing and fixes no size).  The
+ * frames limit holds per member; a summed counter that would pass UINT32_MAX is SLIDEO_ERR_CAPACITY (read the members one by one). */
+int32_t     slideo_group_evidence_begin(slideo_group* g, int32_t cell, int32_t min_inliers);
+int32_t     slideo_group_evidence_end(slideo_group* g);
+int32_t     slideo_group_evidence_info(slideo_group* g, int32_t* cell, int32_t* min_inliers, int32_t* aw, int32_t* ah, int32_t* gw, int32_t* gh,
+                                       int64_t* frames_through, int64_t* frames_counted);
+int32_t     slideo_group_evidence_counts(slideo_group* g, uint32_t* seen_out, uint32_t* hit_out, int64_t capacity_elems, int32_t* gw, int32_t* gh,
+                                         int64_t* frames_through, int64_t* frames_counted);
+/* Two pure host functions over count arrays (no handle, no device).  seen, hit: gh rows of gw elements, gw == ceil(aw / cell) and
+ * gh == ceil(ah / cell), cell 16, 32 or 64, 1 <= aw, ah <= 4096; anything else, a ppm outside 0..1000000, a negative count or one
+ * above UINT32_MAX, grow outside 0..256 or stride_bytes < aw is SLIDEO_ERR_INVALID_ARG and nothing is written (SLIDEO_ERR_CAPACITY: no host memory for the grid).
+ *   mask   a cell is CLUTTER iff seen >= min_seen && hit * 1000000 < min_hit_ppm * seen (unsigned 64-bit); every other cell is kept;
+ *          a cell within `grow` cells (Chebyshev) of a kept cell is kept too; pixel (x, y) gets 255 if cell (x / cell, y / cell) is
+ *          kept, else 0.  mask_out: ah rows of aw bytes, stride_bytes apart: what slideo_matcher_set_frame_mask takes.
+ *   box    the bounding box of the cells with hit >= min_hits && hit * 1000000 >= min_hit_ppm * seen, in pixels, clipped to
+ *          (aw, ah): {x0, y0, x1, y1}, x1 and y1 exclusive; all -1 when no cell qualifies.  Axis-aligned: a keystoned screen needs
+ *          a quad, which the traces' transforms can give on the host. */
+int32_t     slideo_evidence_mask(const uint32_t* seen, const uint32_t* hit, int32_t gw, int32_t gh, int32_t cell, int32_t aw, int32_t ah,
+                                 int64_t min_seen, int32_t min_hit_ppm, int32_t grow, uint8_t* mask_out, int64_t stride_bytes);
+int32_t     slideo_evidence_box(const uint32_t* seen, const uint32_t* hit, int32_t gw, int32_t gh, int32_t cell, int32_t aw, int32_t ah,
+                                int64_t min_hits, int32_t min_hit_ppm, int32_t* box_out4);
+/* Tap: the length of the pre-drawn cv::RNG stream now: SLIDEO_RNG_STREAM_LEN at creation, larger once a unit outran it and was run again. */
+int32_t     slideo_matcher_rng_stream_len(const slideo_matcher* m, int64_t* len);
 
 #ifdef __cplusplus
 }

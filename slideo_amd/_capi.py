@@ -381,6 +381,9 @@ EXPORTS = [
     "slideo_matcher_set_gate_memory", "slideo_matcher_gate_memory", "slideo_group_set_gate_memory", "slideo_matcher_last_gate_refs",
     "slideo_group_last_gate_refs", "slideo_matcher_gate_memory_entries", "slideo_matcher_gate_memory_small", "slideo_gate_recall_walk",
     "slideo_match_frames_features_bgr8",
+    "slideo_matcher_evidence_begin", "slideo_matcher_evidence_end", "slideo_matcher_evidence_info", "slideo_matcher_evidence_counts",
+    "slideo_group_evidence_begin", "slideo_group_evidence_end", "slideo_group_evidence_info", "slideo_group_evidence_counts",
+    "slideo_evidence_mask", "slideo_evidence_box", "slideo_matcher_rng_stream_len",
 ]
 
 # frame mask scope (include/slideo_amd.h "Frame mask scope")
@@ -537,6 +540,16 @@ def lib():
             L.slideo_matcher_activity_info.argtypes = [vp, vp, vp, vp, vp]
             L.slideo_matcher_activity_counts.argtypes = [vp, vp, i64, vp, vp, vp]
             L.slideo_matcher_activity_mask.argtypes = [vp, i32, i32, vp, i64, vp, vp, vp, vp]
+        if hasattr(L, "slideo_matcher_evidence_begin"):
+            vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
+            for pre in ("slideo_matcher_", "slideo_group_"):
+                getattr(L, pre + "evidence_begin").argtypes = [vp, i32, i32]
+                getattr(L, pre + "evidence_end").argtypes = [vp]
+                getattr(L, pre + "evidence_info").argtypes = [vp] * 9
+                getattr(L, pre + "evidence_counts").argtypes = [vp, vp, vp, i64, vp, vp, vp, vp]
+            L.slideo_evidence_mask.argtypes = [vp, vp, i32, i32, i32, i32, i32, i64, i32, i32, vp, i64]
+            L.slideo_evidence_box.argtypes = [vp, vp, i32, i32, i32, i32, i32, i64, i32, vp]
+            L.slideo_matcher_rng_stream_len.argtypes = [vp, vp]
         if hasattr(L, "slideo_matcher_content_begin"):
             vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
             L.slideo_matcher_content_begin.argtypes = [vp, i32]
@@ -656,6 +669,31 @@ class _FrameCalls:
         out = np.zeros(n, VERDICT_DTYPE)
         self._call("match_frames_bgr8", n, _p(frames), w, h, st, C.c_int64(fs), _p(out))
         return out
+
+    # ---- match evidence map (include/slideo_amd.h "Match evidence map"); a Group's are the members' sums ----
+    def evidence_begin(self, cell, min_inliers):
+        """An empty evidence session: match calls from now on count, per cell x cell cell of the analysed image, the keypoints of the
+        frames whose verdict has a page and at least min_inliers inliers (seen), and those the winner's transform explains (hit)."""
+        self._check(getattr(lib(), self._SETS + "evidence_begin")(self._h, int(cell), int(min_inliers)))
+
+    def evidence_end(self):
+        self._check(getattr(lib(), self._SETS + "evidence_end")(self._h))
+
+    def evidence_info(self):
+        """-> {cell, min_inliers, aw, ah, gw, gh, frames_through, frames_counted} (aw == 0 before the first counted call)."""
+        v = [C.c_int32() for _ in range(6)] + [C.c_int64(), C.c_int64()]
+        self._check(getattr(lib(), self._SETS + "evidence_info")(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("cell", "min_inliers", "aw", "ah", "gw", "gh", "frames_through", "frames_counted"), (x.value for x in v)))
+
+    def evidence_counts(self):
+        """-> (seen uint32 [gh, gw], hit uint32 [gh, gw], frames_through, frames_counted); [0, 0] arrays before the first counted call."""
+        gw, gh, ft, fc = C.c_int32(), C.c_int32(), C.c_int64(), C.c_int64()
+        fn = getattr(lib(), self._SETS + "evidence_counts")
+        self._check(fn(self._h, None, None, C.c_int64(0), C.byref(gw), C.byref(gh), C.byref(ft), C.byref(fc)))
+        seen, hit = np.zeros((gh.value, gw.value), np.uint32), np.zeros((gh.value, gw.value), np.uint32)
+        if seen.size:
+            self._check(fn(self._h, _p(seen), _p(hit), C.c_int64(seen.size), C.byref(gw), C.byref(gh), C.byref(ft), C.byref(fc)))
+        return seen, hit, ft.value, fc.value
 
     def last_candidates(self, frame_in_batch):
         cands = np.zeros(64, CANDIDATE_DTYPE)
@@ -1221,6 +1259,12 @@ class Matcher(_FrameCalls):
                                                        C.c_int64(frame_stride), _p(out),
                                                        C.c_void_p(stream)))
         return out
+
+    def rng_stream_len(self):
+        """The length of the pre-drawn RNG stream now (it grows when a unit outran it and was run again)."""
+        n = C.c_int64()
+        self._check(lib().slideo_matcher_rng_stream_len(self._h, C.byref(n)))
+        return n.value
 
     def max_in_flight(self):
         return int(lib().slideo_matcher_max_in_flight(self._h))
@@ -1867,6 +1911,36 @@ def device_list():
     arr = (C.c_int32 * max(n, 1))()
     n = min(n, int(lib().slideo_device_list(arr, n)))
     return [int(arr[i]) for i in range(n)]
+
+
+def _evidence_arrays(seen, hit):
+    seen, hit = np.ascontiguousarray(seen, np.uint32), np.ascontiguousarray(hit, np.uint32)
+    if seen.ndim != 2 or seen.shape != hit.shape:
+        raise ValueError("seen and hit: two uint32 [gh, gw] arrays, got %s and %s" % (seen.shape, hit.shape))
+    return seen, hit, seen.shape[1], seen.shape[0]
+
+
+def evidence_mask(seen, hit, cell, aw, ah, min_seen, min_hit, grow):
+    """slideo_evidence_mask (include/slideo_amd.h "Match evidence map"): min_hit a float in [0, 1], rounded to parts per million ->
+    mask uint8 [ah, aw] of 0 / 255, what set_frame_mask takes."""
+    seen, hit, gw, gh = _evidence_arrays(seen, hit)
+    out = np.empty((max(int(ah), 0), max(int(aw), 0)), np.uint8)
+    rc = lib().slideo_evidence_mask(_p(seen), _p(hit), gw, gh, int(cell), int(aw), int(ah), C.c_int64(int(min_seen)),
+                                    int(round(float(min_hit) * 1000000)), int(grow), _p(out) if out.size else None, C.c_int64(int(aw)))
+    if rc != OK:
+        raise SlideoError(rc, "slideo_evidence_mask: an argument outside its range (include/slideo_amd.h \"Match evidence map\")")
+    return out
+
+
+def evidence_box(seen, hit, cell, aw, ah, min_hits, min_hit):
+    """slideo_evidence_box: -> (x0, y0, x1, y1), x1 and y1 exclusive; all -1 when no cell qualifies."""
+    seen, hit, gw, gh = _evidence_arrays(seen, hit)
+    box = (C.c_int32 * 4)()
+    rc = lib().slideo_evidence_box(_p(seen), _p(hit), gw, gh, int(cell), int(aw), int(ah), C.c_int64(int(min_hits)),
+                                   int(round(float(min_hit) * 1000000)), box)
+    if rc != OK:
+        raise SlideoError(rc, "slideo_evidence_box: an argument outside its range (include/slideo_amd.h \"Match evidence map\")")
+    return tuple(box)
 
 
 def changed_ssd_threshold(changed_similarity, small_w, small_h):

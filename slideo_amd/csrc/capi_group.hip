@@ -770,4 +770,88 @@ int32_t slideo_group_match_changed_frames_yuv420(slideo_group* g, int32_t n_fram
     GROUP_CATCH(g)
 }
 
+// ---- Match evidence map (include/slideo_amd.h "Match evidence map"): every member carries a session, the read-outs return the sums --
+int32_t slideo_group_evidence_begin(slideo_group* g, int32_t cell, int32_t min_inliers) {
+    if (!g) return SLIDEO_ERR_INVALID_ARG;
+    GROUP_TRY
+    if (cell != 16 && cell != 32 && cell != 64) fail(SLIDEO_ERR_INVALID_ARG, "evidence_begin: cell %d is none of 16, 32, 64", cell);
+    if (min_inliers < 0) fail(SLIDEO_ERR_INVALID_ARG, "evidence_begin: min_inliers %d below 0", min_inliers);
+    // validated before any member is touched
+    for (slideo_matcher* m : g->members) {
+        if (m->sift_on) fail(SLIDEO_ERR_UNSUPPORTED, "evidence_begin: the evidence map is not defined in SIFT mode");
+        require_idle(m);
+        if (m->evidence.on) fail(SLIDEO_ERR_STATE, "evidence_begin: a session is open (slideo_group_evidence_end first)");
+    }
+    for (slideo_matcher* m : g->members) check_member_call(m, slideo_matcher_evidence_begin(m, cell, min_inliers));
+    GROUP_CATCH(g)
+}
+
+int32_t slideo_group_evidence_end(slideo_group* g) {
+    if (!g) return SLIDEO_ERR_INVALID_ARG;
+    GROUP_TRY
+    for (slideo_matcher* m : g->members) require_idle(m);
+    for (slideo_matcher* m : g->members) check_member_call(m, slideo_matcher_evidence_end(m));
+    GROUP_CATCH(g)
+}
+
+namespace {
+// the members' sessions as one: every member's open, the members that counted agree on the analysed size
+void group_evidence(slideo_group* g, slideo_matcher::Evidence& sum) {
+    sum = slideo_matcher::Evidence{};
+    for (slideo_matcher* m : g->members) {
+        const slideo_matcher::Evidence& E = m->evidence;
+        if (!E.on) fail(SLIDEO_ERR_STATE, "no evidence session on every member: slideo_group_evidence_begin first");
+        if (!sum.on) { sum = E; sum.aw = sum.ah = sum.gw = sum.gh = 0; sum.through = sum.counted = 0; }
+        if (E.cell != sum.cell || E.min_inliers != sum.min_inliers) fail(SLIDEO_ERR_STATE, "the members' evidence sessions differ (one was begun directly)");
+        if (E.aw > 0) {
+            if (sum.aw > 0 && (sum.aw != E.aw || sum.ah != E.ah))
+                fail(SLIDEO_ERR_STATE, "the members' evidence sessions count at %dx%d and %dx%d (a member was called directly)", sum.aw, sum.ah, E.aw, E.ah);
+            sum.aw = E.aw; sum.ah = E.ah; sum.gw = E.gw; sum.gh = E.gh;
+        }
+        sum.through += E.through; sum.counted += E.counted;
+    }
+}
+}  // namespace
+
+int32_t slideo_group_evidence_info(slideo_group* g, int32_t* cell, int32_t* min_inliers, int32_t* aw, int32_t* ah, int32_t* gw, int32_t* gh,
+                                   int64_t* frames_through, int64_t* frames_counted) {
+    if (!g) return SLIDEO_ERR_INVALID_ARG;
+    GROUP_TRY
+    if (!cell || !min_inliers || !aw || !ah || !gw || !gh || !frames_through || !frames_counted) fail(SLIDEO_ERR_INVALID_ARG, "null output");
+    slideo_matcher::Evidence E;
+    group_evidence(g, E);
+    *cell = E.cell; *min_inliers = E.min_inliers; *aw = E.aw; *ah = E.ah; *gw = E.gw; *gh = E.gh;
+    *frames_through = E.through; *frames_counted = E.counted;
+    GROUP_CATCH(g)
+}
+
+int32_t slideo_group_evidence_counts(slideo_group* g, uint32_t* seen_out, uint32_t* hit_out, int64_t capacity_elems, int32_t* gw, int32_t* gh,
+                                     int64_t* frames_through, int64_t* frames_counted) {
+    if (!g) return SLIDEO_ERR_INVALID_ARG;
+    GROUP_TRY
+    if (!gw || !gh || !frames_through || !frames_counted) fail(SLIDEO_ERR_INVALID_ARG, "null gw/gh/frames_through/frames_counted");
+    for (slideo_matcher* m : g->members) require_idle(m);
+    slideo_matcher::Evidence E;
+    group_evidence(g, E);
+    *gw = E.gw; *gh = E.gh; *frames_through = E.through; *frames_counted = E.counted;
+    if (E.aw == 0 || (!seen_out && !hit_out)) return SLIDEO_OK;
+    if (!seen_out || !hit_out) fail(SLIDEO_ERR_INVALID_ARG, "seen_out and hit_out go together");
+    const int64_t nc = (int64_t)E.gw * E.gh;
+    if (nc > capacity_elems) fail(SLIDEO_ERR_CAPACITY, "the counts need %lld elements each", (long long)nc);
+    std::vector<uint32_t> part((size_t)nc * 2);
+    std::fill(seen_out, seen_out + nc, 0u);
+    std::fill(hit_out, hit_out + nc, 0u);
+    for (slideo_matcher* m : g->members) {
+        if (m->evidence.aw == 0) continue;               // (its shards were empty: nothing counted)
+        int32_t w = 0, h = 0; int64_t t = 0, c = 0;
+        check_member_call(m, slideo_matcher_evidence_counts(m, part.data(), part.data() + nc, nc, &w, &h, &t, &c));
+        for (int64_t i = 0; i < nc; ++i) {
+            // (the frames limit holds per member: a sum over members can pass u32, which is refused, never wrapped)
+            if (seen_out[i] > 0xFFFFFFFFu - part[(size_t)i]) fail(SLIDEO_ERR_CAPACITY, "a summed counter passes UINT32_MAX: read the members' counts one by one");
+            seen_out[i] += part[(size_t)i]; hit_out[i] += part[(size_t)(nc + i)];
+        }
+    }
+    GROUP_CATCH(g)
+}
+
 }  // extern "C"

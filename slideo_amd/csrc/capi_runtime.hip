@@ -173,6 +173,7 @@ void settings_commit(slideo_matcher* m, Setting what, FrameSettings next, const 
     m->fs = next;
     const SettingEnds& ends = SETTING_ENDS[what];
     if (ends.kept) m->kept.valid = false;
+    if (ends.kept && ends.gate) evidence_drop(m);      // (the analysed image changes under an open evidence session: the state "none")
     if (ends.gate) { gate_state_reset(m); m->gate_refs.clear(); m->gate_refs_valid = false; }
     if (ends.map_gen) ++m->fs.gate_map_gen;
 }
@@ -318,7 +319,15 @@ void unit_submit(slideo_matcher* m, Slot& S, const DevFrames& f, int n, const ui
     unit_verify(m, S, vp, f, n, qtot);
 }
 
+static void unit_collect_body(slideo_matcher* m, Slot& S, slideo_verdict* out_host);
+// (a collect that fails — a HIP error, an overflow that cannot be served — may leave a unit counted whose verdicts are never
+// returned: an open evidence session ends with it)
 void unit_collect(slideo_matcher* m, Slot& S, slideo_verdict* out_host) {
+    try { unit_collect_body(m, S, out_host); }
+    catch (...) { evidence_drop(m); throw; }
+}
+
+static void unit_collect_body(slideo_matcher* m, Slot& S, slideo_verdict* out_host) {
     const int n = S.n;
     HIP_CHECK(hipStreamSynchronize(S.st));
     S.busy = false;
@@ -364,6 +373,7 @@ void unit_collect(slideo_matcher* m, Slot& S, slideo_verdict* out_host) {
         HIP_CHECK(hipEventElapsedTime(&t, S.ev[0], S.ev[4])); m->prof_ms[3] += t; m->prof_n[3]++;
     }
     std::memcpy(out_host, ho, (size_t)n * sizeof(slideo_verdict));
+    evidence_tally(m, out_host, n);                  // (the run whose verdicts are returned: evidence_kernel counted this one alone)
     const size_t base = m->last_fcs.size();
     m->last_fcs.resize(base + n);
     std::memcpy(m->last_fcs.data() + base, ho + (size_t)n * sizeof(slideo_verdict), (size_t)n * sizeof(FrameCands));
@@ -395,6 +405,7 @@ void match_frames_impl(slideo_matcher* m, int n, FrameSrc src, slideo_verdict* o
     require_idle(m);
     m->last_fcs.clear();
     if (n == 0) return;
+    evidence_admit(m, src.plan.uw, src.plan.uh, n);
     int unit = unit_fit(m, src, n, gated);
     area_class_for(m, src.plan.uw, src.plan.uh);
     upload_area(m);
@@ -445,6 +456,7 @@ void match_frames_impl(slideo_matcher* m, int n, FrameSrc src, slideo_verdict* o
         m->units_pending = false;
         (void)hipStreamSynchronize(m->copy_st);          // (DMA from the caller's pinned buffer may still be running)
         for (Slot& S : m->slots) { (void)hipStreamSynchronize(S.st); S.busy = false; S.gate.on = false; }
+        evidence_drop(m);                                // (units of the call may have counted: an open evidence session ends)
         throw;
     }
 }
@@ -461,6 +473,7 @@ static void submit_impl(slideo_matcher* m, int32_t n_frames, FrameSrc src, void*
     const int fit = unit_fit(m, src, n_frames, gated);
     if (n_frames > fit)
         fail(SLIDEO_ERR_CAPACITY, "%d frames exceed the per-slot workspace budget (%d); submit smaller units or raise SLIDEO_WS_GB", n_frames, fit);
+    evidence_admit(m, src.plan.uw, src.plan.uh, n_frames);
     area_class_for(m, src.plan.uw, src.plan.uh);
     upload_area(m);
     { bool any = false; for (const Slot& c : m->slots) any |= c.busy; if (!any) m->last_fcs.clear(); }
@@ -468,7 +481,8 @@ static void submit_impl(slideo_matcher* m, int32_t n_frames, FrameSrc src, void*
         HIP_CHECK(hipEventRecord(S.ev_in, reinterpret_cast<hipStream_t>(hip_stream)));
         HIP_CHECK(hipStreamWaitEvent(S.st, S.ev_in, 0));
     }
-    unit_begin(m, S, src, 0, n_frames, nullptr, gated);
+    try { unit_begin(m, S, src, 0, n_frames, nullptr, gated); }
+    catch (...) { evidence_drop(m); throw; }      // (a unit half submitted may count: an open evidence session ends)
     S.ticket = m->next_ticket++;
     *ticket_out = S.ticket;
     m->next_slot = (m->next_slot + 1) % NSLOTS;

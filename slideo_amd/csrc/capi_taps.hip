@@ -144,6 +144,9 @@ int32_t slideo_match_frames_features_bgr8(slideo_matcher* m, int32_t n_frames, c
     require_idle(m);
     m->last_fcs.clear();
     if (n == 0) return SLIDEO_OK;
+    evidence_admit(m, width, height, n);
+    // (a failure from here on may leave rows counted whose verdicts are never returned: an open evidence session ends with it)
+    struct EvidenceGuard { slideo_matcher* m; bool ok; ~EvidenceGuard() { if (!ok) evidence_drop(m); } } ev_guard{m, false};
     area_class_for(m, width, height);
     upload_area(m);
     const slideo_config& c = m->cfg;
@@ -196,9 +199,18 @@ int32_t slideo_match_frames_features_bgr8(slideo_matcher* m, int32_t n_frames, c
     }
     const uint8_t* ho = S.h_out.as<uint8_t>();
     std::memcpy(verdicts_out, ho, (size_t)n * sizeof(slideo_verdict));
+    evidence_tally(m, verdicts_out, n);
+    ev_guard.ok = true;
     m->last_fcs.resize((size_t)n);
     std::memcpy(m->last_fcs.data(), ho + (size_t)n * sizeof(slideo_verdict), (size_t)n * sizeof(FrameCands));
     API_CATCH(m)
+}
+
+// Tap: the length of the pre-drawn cv::RNG stream now (it starts at SLIDEO_RNG_STREAM_LEN and grows when a unit outran it and was run again)
+int32_t slideo_matcher_rng_stream_len(const slideo_matcher* m, int64_t* len) {
+    if (!m || !len) return SLIDEO_ERR_INVALID_ARG;
+    *len = (int64_t)m->rng_len;
+    return SLIDEO_OK;
 }
 
 int32_t slideo_yuv420_to_bgr8(slideo_matcher* m, const uint8_t* frame, int32_t width, int32_t height, const slideo_yuv420_layout* layout,

@@ -9,7 +9,8 @@
 //   stage_orb.hip      ORB stage drivers          (kernels: orb.hip.h, yuv420.hip.h, yuv_sampling.hip.h, pixel_format.hip.h, reduce.hip.h,
 //                                                 frame_region.hip.h, frame_mask.hip.h, levels.hip.h levels_kernel)
 //   stage_knn.hip      index build + k-NN stage   (kernels: knn.hip.h, knn_tile.hip.h, knn_l2.hip.h, knn_lsh.hip.h)
-//   stage_verify.hip   vote .. verdict, small img (kernels: verify.hip.h, homography.hip.h)
+//   stage_verify.hip   vote .. verdict, small img (kernels: verify.hip.h, homography.hip.h); the match evidence map's session, its
+//                      launch behind the verdicts and its entry points (kernel: evidence.hip.h)
 //   stage_sift.hip     SIFT stage + entry points  (kernels: sift.hip.h)
 //   stage_page_set.hip page sets: a subset's search operand built from the finalized deck (kernels: page_set.hip.h)
 //   stage_gate.hip     changed-frame gate: gated units, the gate state, its record and its entry points (kernels: gate.hip.h)
@@ -448,6 +449,13 @@ struct slideo_matcher {
     struct Levels { bool on = false; int64_t frames = 0, pixels = 0; } levels;
     slideo::DevBuf d_lv_hist;
 
+    // match evidence map (include/slideo_amd.h "Match evidence map"): the session — "none" (on false), empty (aw 0) or the counts of
+    // the match calls since evidence_begin at the analysed size aw x ah — and its device buffer {seen [gh][gw] | hit [gh][gw]} (u32),
+    // which evidence_kernel adds to on the units' streams.  through, counted: the frames of the collected units (unit_collect)
+    // max_frames: the session's frames limit, 2^20 unless SLIDEO_EVIDENCE_MAX_FRAMES lowered it at begin (the tests' seam)
+    struct Evidence { bool on = false; int cell = 0, min_inliers = 0, aw = 0, ah = 0, gw = 0, gh = 0; int64_t through = 0, counted = 0, max_frames = 0; } evidence;
+    slideo::DevBuf d_evidence;
+
     // direct page look-up (include/slideo_amd.h "Direct page look-up"): built at the first use with fs.direct_t > 0 after finalize, the
     // deck's size classes
     bool direct_built = false;
@@ -604,6 +612,12 @@ void l2_lists_to_keys(slideo_matcher* m, Slot& S, const DevBuf& lists, int kq, u
 void verify_stage_init(slideo_matcher* m);
 VerifyParams make_vp(const slideo_config& c);
 void unit_verify(slideo_matcher* m, Slot& S, const VerifyParams& vp, const DevFrames& f, int n, uint32_t qtot);
+// Match evidence map (evidence.hip.h), no-ops without a session.  evidence_admit: in front of a match call's first unit — the
+// analysed size against the session's (SLIDEO_ERR_INVALID_ARG), the frames limit, and at the session's first call the zeroed counts.
+// evidence_tally: the frame counts of a collected unit from the verdicts it returns.  evidence_drop: the state "none".
+void evidence_admit(slideo_matcher* m, int uw, int uh, int n);
+void evidence_tally(slideo_matcher* m, const slideo_verdict* v, int n);
+inline void evidence_drop(slideo_matcher* m) { m->evidence = slideo_matcher::Evidence{}; }
 // (sw, sh: the small size, for callers without a FramePlan — pages, taps, the validity map)
 void run_small(slideo_matcher* m, const DevFrames& imgs, int n, hipStream_t st, int* sw = nullptr, int* sh = nullptr);
 // the same into `dst` (n small images back to back) in place of m->d_small: small images of consecutive gated units overlap

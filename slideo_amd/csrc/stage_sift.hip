@@ -335,6 +335,7 @@ int32_t slideo_matcher_use_sift(slideo_matcher* m, const slideo_sift_config* cfg
     if (!(ratio >= 0.f) || !(ratio <= 1.f)) fail(SLIDEO_ERR_INVALID_ARG, "ratio must be in [0, 1] (0 = the path's tolerance vote)");
     if (m->cfg.matcher != 0) fail(SLIDEO_ERR_UNSUPPORTED, "the LSH index is a Hamming index: not with SIFT features");
     if (m->fs.mask.set) fail(SLIDEO_ERR_UNSUPPORTED, "the frame mask filters ORB's FAST candidates: not in SIFT mode (clear it first)");
+    if (m->evidence.on) fail(SLIDEO_ERR_UNSUPPORTED, "the evidence map is not defined in SIFT mode (slideo_matcher_evidence_end first)");
     m->sift_on = true; m->sift_cfg = *cfg; m->sift_ratio = ratio;
     API_CATCH(m)
 }

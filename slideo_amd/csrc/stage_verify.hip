@@ -1,7 +1,12 @@
-// stage_verify.hip — drivers of the verification stage, vote .. verdict, and of to_small_image (kernels: verify.hip.h, homography.hip.h).
+// stage_verify.hip — drivers of the verification stage, vote .. verdict, and of to_small_image (kernels: verify.hip.h, homography.hip.h);
+// the match evidence map of include/slideo_amd.h "Match evidence map": its session, its launch behind the verdicts and its entry
+// points (kernel: evidence.hip.h).
 #include "runtime.hpp"
 #include "verify.hip.h"
 #include "homography.hip.h"
+#include "evidence.hip.h"
+
+#include <cstring>
 
 using namespace slideo;
 
@@ -39,6 +44,53 @@ void run_small_into(slideo_matcher* m, const DevFrames& imgs, int n, DevBuf& dst
 void launch_ssd(const uint8_t* a, int64_t a_stride, const uint8_t* b, int64_t b_stride, int64_t bytes, unsigned long long* ssd, int n, hipStream_t st) {
     ssd_kernel<<<n, 256, 0, st>>>(a, a_stride, b, b_stride, bytes, ssd);
     check_launch("ssd_kernel");
+}
+
+// ---- match evidence map -----------------------------------------------------------------------------------------------------------
+void evidence_admit(slideo_matcher* m, int uw, int uh, int n) {
+    slideo_matcher::Evidence& E = m->evidence;
+    if (!E.on || n <= 0) return;
+    if (E.aw > 0 && (E.aw != uw || E.ah != uh))
+        fail(SLIDEO_ERR_INVALID_ARG, "these frames are analysed at %dx%d, the evidence session counts at %dx%d: slideo_matcher_evidence_end first", uw, uh,
+             E.aw, E.ah);
+    int64_t pending = 0;
+    for (const Slot& S : m->slots) if (S.busy) pending += S.n;
+    if (E.counted + pending + n > E.max_frames)
+        fail(SLIDEO_ERR_INVALID_ARG, "%lld frames would pass the evidence session's %lld: read the counts out and begin again", (long long)(E.counted + pending + n),
+             (long long)E.max_frames);
+    if (E.aw > 0) return;
+    // the session's first counted call fixes the grid; the zeroed counts stand before any unit of the call is submitted
+    const int gw = cdiv(uw, E.cell), gh = cdiv(uh, E.cell);
+    const size_t bytes = (size_t)gw * gh * 8;
+    m->d_evidence.reserve(bytes + 16);
+    HIP_CHECK(hipMemsetAsync(m->d_evidence.p, 0, bytes, m->stream));
+    HIP_CHECK(hipStreamSynchronize(m->stream));
+    E.aw = uw; E.ah = uh; E.gw = gw; E.gh = gh;
+}
+
+void evidence_tally(slideo_matcher* m, const slideo_verdict* v, int n) {
+    slideo_matcher::Evidence& E = m->evidence;
+    if (!E.on || E.aw == 0) return;
+    E.through += n;
+    for (int i = 0; i < n; ++i) E.counted += v[i].page_idx >= 0 && v[i].inliers >= E.min_inliers;
+}
+
+// evidence_kernel over the unit's frames, behind verdict_kernel on the unit's stream
+static void evidence_launch(slideo_matcher* m, Slot& S, const VerifyParams& vp, const DevFrames& f, int n) {
+    const slideo_matcher::Evidence& E = m->evidence;
+    if (E.aw != f.w || E.ah != f.h) fail(SLIDEO_ERR_HIP, "internal: a unit of %dx%d images under an evidence session of %dx%d", f.w, f.h, E.aw, E.ah);
+    EvidenceArgs a{};
+    a.verdicts = S.d_verdicts.as<slideo_verdict>(); a.fcs = S.d_fcs.as<FrameCands>(); a.qofs = S.d_qofs.as<uint32_t>();
+    a.kp = S.d_kp.as<slideo_keypoint>();
+    a.page_xy = reinterpret_cast<const EvXY*>(m->d_page_xy.as<float2>());
+    a.votes = reinterpret_cast<const EvVote*>(S.d_votes.as<uint2>());
+    a.flags = S.d_flags.as<uint32_t>();
+    a.rerun_mask = S.u_async ? 12u : 4u;      // unit_collect's re-run rules: the RNG stream; the keypoint capacity of the capacity-sized path
+    a.k = vp.k; a.model = vp.model; a.min_inliers = E.min_inliers; a.thr2 = vp.thr * vp.thr;
+    a.aw = E.aw; a.ah = E.ah; a.cell = E.cell; a.gw = E.gw; a.gh = E.gh;
+    a.seen = m->d_evidence.as<uint32_t>(); a.hit = a.seen + (size_t)E.gw * E.gh;
+    evidence_kernel<<<n, EV_THREADS, 0, S.st>>>(a);
+    check_launch("evidence_kernel");
 }
 
 // Everything after the neighbour lists (S.d_keys, Hamming key format) of a unit: the per-page vote, RANSAC (similarity or
@@ -155,6 +207,7 @@ void unit_verify(slideo_matcher* m, Slot& S, const VerifyParams& vp, const DevFr
     verdict_kernel<<<cdiv(n, 64), 64, 0, st>>>(vp, n, S.d_qofs.as<uint32_t>(), m->d_pageinfo.as<PageInfo>(), S.d_fcs.as<FrameCands>(),
                                                S.d_verdicts.as<slideo_verdict>());
     check_launch("verdict_kernel");
+    if (m->evidence.on && qtot > 0) evidence_launch(m, S, vp, f, n);
     if (prof) HIP_CHECK(hipEventRecord(S.ev[3], st));
     uint8_t* ho = S.h_out.as<uint8_t>();
     const size_t tail = (size_t)n * (sizeof(slideo_verdict) + sizeof(FrameCands));
@@ -192,3 +245,86 @@ void verify_stage_init(slideo_matcher* m) {
 
 }  // namespace slideo
 
+// ---- Match evidence map (include/slideo_amd.h "Match evidence map") ------------------------------------------------------------------
+extern "C" {
+
+int32_t slideo_matcher_evidence_begin(slideo_matcher* m, int32_t cell, int32_t min_inliers) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    if (!evidence_cell_ok(cell)) fail(SLIDEO_ERR_INVALID_ARG, "evidence_begin: cell %d is none of 16, 32, 64", cell);
+    if (min_inliers < 0) fail(SLIDEO_ERR_INVALID_ARG, "evidence_begin: min_inliers %d below 0", min_inliers);
+    if (m->sift_on) fail(SLIDEO_ERR_UNSUPPORTED, "evidence_begin: the evidence map is not defined in SIFT mode");
+    require_idle(m);
+    if (m->evidence.on) fail(SLIDEO_ERR_STATE, "evidence_begin: a session is open (slideo_matcher_evidence_end first)");
+    m->evidence = slideo_matcher::Evidence{};
+    m->evidence.on = true; m->evidence.cell = cell; m->evidence.min_inliers = min_inliers;
+    m->evidence.max_frames = std::min<int64_t>(EV_MAX_FRAMES, std::max<long>(1, env_long("SLIDEO_EVIDENCE_MAX_FRAMES", EV_MAX_FRAMES)));
+    API_CATCH(m)
+}
+
+int32_t slideo_matcher_evidence_end(slideo_matcher* m) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    require_idle(m);
+    HIP_CHECK(hipSetDevice(m->device));
+    evidence_drop(m);
+    m->d_evidence.release();
+    API_CATCH(m)
+}
+
+int32_t slideo_matcher_evidence_info(slideo_matcher* m, int32_t* cell, int32_t* min_inliers, int32_t* aw, int32_t* ah, int32_t* gw, int32_t* gh,
+                                     int64_t* frames_through, int64_t* frames_counted) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    if (!cell || !min_inliers || !aw || !ah || !gw || !gh || !frames_through || !frames_counted) fail(SLIDEO_ERR_INVALID_ARG, "null output");
+    const slideo_matcher::Evidence& E = m->evidence;
+    if (!E.on) fail(SLIDEO_ERR_STATE, "no evidence session: slideo_matcher_evidence_begin first");
+    *cell = E.cell; *min_inliers = E.min_inliers; *aw = E.aw; *ah = E.ah; *gw = E.gw; *gh = E.gh;
+    *frames_through = E.through; *frames_counted = E.counted;
+    API_CATCH(m)
+}
+
+int32_t slideo_matcher_evidence_counts(slideo_matcher* m, uint32_t* seen_out, uint32_t* hit_out, int64_t capacity_elems, int32_t* gw, int32_t* gh,
+                                       int64_t* frames_through, int64_t* frames_counted) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    if (!gw || !gh || !frames_through || !frames_counted) fail(SLIDEO_ERR_INVALID_ARG, "null gw/gh/frames_through/frames_counted");
+    require_idle(m);
+    const slideo_matcher::Evidence& E = m->evidence;
+    if (!E.on) fail(SLIDEO_ERR_STATE, "no evidence session: slideo_matcher_evidence_begin first");
+    *gw = E.gw; *gh = E.gh; *frames_through = E.through; *frames_counted = E.counted;
+    if (E.aw == 0 || (!seen_out && !hit_out)) return SLIDEO_OK;      // (no counted call yet: a grid of 0 x 0)
+    if (!seen_out || !hit_out) fail(SLIDEO_ERR_INVALID_ARG, "seen_out and hit_out go together");
+    const int64_t nc = (int64_t)E.gw * E.gh;
+    if (nc > capacity_elems) fail(SLIDEO_ERR_CAPACITY, "the counts need %lld elements each", (long long)nc);
+    HIP_CHECK(hipSetDevice(m->device));
+    HIP_CHECK(hipMemcpyAsync(seen_out, m->d_evidence.p, (size_t)nc * 4, hipMemcpyDeviceToHost, m->stream));
+    HIP_CHECK(hipMemcpyAsync(hit_out, m->d_evidence.as<uint32_t>() + nc, (size_t)nc * 4, hipMemcpyDeviceToHost, m->stream));
+    HIP_CHECK(hipStreamSynchronize(m->stream));
+    API_CATCH(m)
+}
+
+static int32_t evidence_grid_check(const uint32_t* seen, const uint32_t* hit, int32_t gw, int32_t gh, int32_t cell, int32_t aw, int32_t ah) {
+    if (!seen || !hit || !evidence_cell_ok(cell) || aw < 1 || ah < 1 || aw > MAX_DIM || ah > MAX_DIM) return SLIDEO_ERR_INVALID_ARG;
+    if (gw != cdiv(aw, cell) || gh != cdiv(ah, cell)) return SLIDEO_ERR_INVALID_ARG;
+    return SLIDEO_OK;
+}
+
+int32_t slideo_evidence_mask(const uint32_t* seen, const uint32_t* hit, int32_t gw, int32_t gh, int32_t cell, int32_t aw, int32_t ah, int64_t min_seen,
+                             int32_t min_hit_ppm, int32_t grow, uint8_t* mask_out, int64_t stride_bytes) {
+    if (evidence_grid_check(seen, hit, gw, gh, cell, aw, ah) != SLIDEO_OK || !mask_out || stride_bytes < aw) return SLIDEO_ERR_INVALID_ARG;
+    if (min_seen < 0 || min_seen > 0xFFFFFFFFll || min_hit_ppm < 0 || min_hit_ppm > 1000000 || grow < 0 || grow > 256) return SLIDEO_ERR_INVALID_ARG;
+    try { evidence_mask(seen, hit, gw, gh, cell, aw, ah, (uint32_t)min_seen, (uint32_t)min_hit_ppm, grow, mask_out, stride_bytes); }
+    catch (const std::bad_alloc&) { return SLIDEO_ERR_CAPACITY; }      // (two bytes per cell of host memory)
+    return SLIDEO_OK;
+}
+
+int32_t slideo_evidence_box(const uint32_t* seen, const uint32_t* hit, int32_t gw, int32_t gh, int32_t cell, int32_t aw, int32_t ah, int64_t min_hits,
+                            int32_t min_hit_ppm, int32_t* box_out4) {
+    if (evidence_grid_check(seen, hit, gw, gh, cell, aw, ah) != SLIDEO_OK || !box_out4) return SLIDEO_ERR_INVALID_ARG;
+    if (min_hits < 0 || min_hits > 0xFFFFFFFFll || min_hit_ppm < 0 || min_hit_ppm > 1000000) return SLIDEO_ERR_INVALID_ARG;
+    evidence_box(seen, hit, gw, gh, cell, aw, ah, (uint32_t)min_hits, (uint32_t)min_hit_ppm, box_out4);
+    return SLIDEO_OK;
+}
+
+}  // extern "C"

@@ -345,6 +345,29 @@ public:
         reporter.report(0, (uint64_t)(video.total_time() / 5.0), "");                               // mo/lib.rs:148-150
         return std::make_unique<HipVideoMatcherTask<I>>(h_, images_, video_path, std::move(reporter), 0.98f);
     }
+    // Match evidence map (include/slideo_amd.h "Match evidence map"; an extension): while a session is open, the tasks' match calls
+    // count where the keypoints of matched frames fall (seen) and which of them the winning page's transform explains (hit), per
+    // cell x cell cell of the analysed image, summed over the devices.  No task may be running at begin, counts or end.  The counts go
+    // to slideo_evidence_mask / slideo_evidence_box; nothing is installed, and no value has a default.
+    struct EvidenceCounts {
+        int32_t cell = 0, min_inliers = 0, aw = 0, ah = 0, gw = 0, gh = 0;
+        int64_t frames_through = 0, frames_counted = 0;
+        std::vector<uint32_t> seen, hit;               // gh rows of gw elements (evidence_info leaves them empty)
+    };
+    void evidence_begin(int32_t cell, int32_t min_inliers) { h_->check(slideo_group_evidence_begin(h_->g, cell, min_inliers)); }
+    void evidence_end() { h_->check(slideo_group_evidence_end(h_->g)); }
+    EvidenceCounts evidence_info() const {
+        EvidenceCounts e;
+        h_->check(slideo_group_evidence_info(h_->g, &e.cell, &e.min_inliers, &e.aw, &e.ah, &e.gw, &e.gh, &e.frames_through, &e.frames_counted));
+        return e;
+    }
+    EvidenceCounts evidence_counts() const {
+        EvidenceCounts e = evidence_info();
+        const size_t nc = (size_t)e.gw * e.gh;
+        e.seen.assign(nc, 0); e.hit.assign(nc, 0);
+        if (nc) h_->check(slideo_group_evidence_counts(h_->g, e.seen.data(), e.hit.data(), (int64_t)nc, &e.gw, &e.gh, &e.frames_through, &e.frames_counted));
+        return e;
+    }
 private:
     std::shared_ptr<detail::Handle> h_;
     std::shared_ptr<std::vector<I>> images_;

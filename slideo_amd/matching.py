@@ -331,6 +331,61 @@ def learn_frame_region(matcher, frame_batches, *, level, min_share, min_fill, in
     return size[0], size[1], quad, out_w, out_h
 
 
+def _evidence_counts(matcher, frame_batches, cell, min_inliers):
+    """The evidence counts of matching the host BGR batches with `matcher`: (seen, hit, info, frame size)."""
+    size = None
+    matcher.evidence_begin(cell, min_inliers)
+    try:
+        for batch in frame_batches:
+            if size is None and len(batch):
+                size = (int(np.shape(batch)[2]), int(np.shape(batch)[1]))
+            matcher.match_frames(batch)
+        info = matcher.evidence_info()
+        seen, hit, _, _ = matcher.evidence_counts()
+    finally:
+        matcher.evidence_end()
+    if info["aw"] == 0:
+        raise ValueError("no frame was matched: the evidence map is empty")
+    return seen, hit, info, size
+
+
+def learn_frame_mask_from_matches(matcher, frame_batches, *, cell, min_inliers, min_seen, min_hit, grow):
+    """A frame mask learnt from the matches themselves (include/slideo_amd.h "Match evidence map"): the host BGR batches (each uint8
+    [n, h, w, 3], all of one frame size) are matched against the matcher's finalized deck under an evidence session of `cell` and
+    `min_inliers`; a cell is clutter when at least `min_seen` keypoints of contributing frames fell into it and less than the share
+    `min_hit` of them agreed with the winning page's transform; the other cells, grown by `grow` cells, are kept.  `matcher`: a
+    Matcher or a Group, idle, finalized.  Returns the mask, uint8 [ah, aw] of 0 / 255 at the analysed size — what frame_mask= and
+    set_frame_mask take; nothing is installed.  No value has a default: they depend on the content (docs/EXTENSIONS.md "Match
+    evidence map")."""
+    seen, hit, info, _ = _evidence_counts(matcher, frame_batches, cell, min_inliers)
+    return _capi.evidence_mask(seen, hit, info["cell"], info["aw"], info["ah"], min_seen, min_hit, grow)
+
+
+def learn_frame_box_from_matches(matcher, frame_batches, *, cell, min_inliers, min_hits, min_hit, inset=0, out_size=None):
+    """A frame region learnt from the matches themselves ("Match evidence map"): the bounding box of the cells into which at least
+    `min_hits` keypoints fell that agreed with the winning page's transform, and at least the share `min_hit` of the cell's
+    keypoints did, shrunk by `inset` pixels on each side.  Frames and `matcher` as learn_frame_mask_from_matches.  Returns what
+    learn_frame_region returns — (src_w, src_h, quad, out_w, out_h), quad: the box's corner pixel centres; out_size None: the box's
+    own size, the exact crop — and installs nothing.  ValueError when no cell qualifies, when the box is narrower than 2 pixels
+    after the inset, or when the frames were not analysed at their own size (a working size reduced them, or a frame region is set):
+    the box is then not in source coordinates.  cell, min_inliers, min_hits and min_hit have no default."""
+    inset = int(inset)
+    if inset < 0:
+        raise ValueError("learn_frame_box_from_matches: inset %d is negative" % inset)
+    seen, hit, info, size = _evidence_counts(matcher, frame_batches, cell, min_inliers)
+    if (info["aw"], info["ah"]) != size:
+        raise ValueError("learn_frame_box_from_matches: the frames are %dx%d but were analysed at %dx%d (a working size reduced them, or a "
+                         "frame region is set): the box is not in source coordinates" % (size + (info["aw"], info["ah"])))
+    box = _capi.evidence_box(seen, hit, info["cell"], info["aw"], info["ah"], min_hits, min_hit)
+    x0, y0, x1, y1 = box[0] + inset, box[1] + inset, box[2] - inset, box[3] - inset
+    if box[0] < 0 or x1 - x0 < 2 or y1 - y0 < 2:
+        raise ValueError("learn_frame_box_from_matches: the evidence box %s is empty or narrower than 2 pixels on a side after an inset of %d"
+                         % (tuple(box), inset))
+    out_w, out_h = (x1 - x0, y1 - y0) if out_size is None else (int(out_size[0]), int(out_size[1]))
+    quad = [(float(x0), float(y0)), (float(x1 - 1), float(y0)), (float(x1 - 1), float(y1 - 1)), (float(x0), float(y1 - 1))]
+    return size[0], size[1], quad, out_w, out_h
+
+
 def learn_frame_levels(matcher, frame_batches, low=0.01, high=0.01):
     """A frame levels table learnt from the frames' own histogram (include/slideo_amd.h "Frame levels"): the per-channel histogram of
     the host BGR batches (each uint8 [n, h, w, 3], or the array shape of the pixel format in force; any sizes), cut by the share `low`
