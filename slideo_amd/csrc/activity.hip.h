@@ -2,7 +2,7 @@
 // consecutive-frame pairs in which it moved, and the mask read out of those counts.
 //
 //   activity_kernel        one launch per staged block of n frames.  A thread owns 4 consecutive pixels of a row (the decomposition of
-//                          reduce2x2_kernel, rectify_kernel and yuv420_to_bgr_kernel) and walks the block's frames in order with the
+//                          reduce2x2_kernel, rectify_kernel and yuv420_to_bgr_desc_kernel) and walks the block's frames in order with the
 //                          previous frame's four pixels and its four counts in registers; at the end ONE read-modify-write of its
 //                          counts and ONE store of its last 12 bytes into the carried image.  Every count and every carried byte has
 //                          exactly one owner: no atomic, no LDS.  A stream: 3 B in per pixel and frame, 4 + 3 B in and out per pixel

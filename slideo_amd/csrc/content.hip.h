@@ -3,7 +3,7 @@
 //
 //   content_kernel         one launch per staged block of n frames, behind or in place of activity_kernel on the same frames.  A thread
 //                          owns 4 consecutive pixels of a row (the decomposition of activity_kernel, reduce2x2_kernel and
-//                          yuv420_to_bgr_kernel) and walks the block's frames with its four counts in registers; at the end ONE
+//                          yuv420_to_bgr_desc_kernel) and walks the block's frames with its four counts in registers; at the end ONE
 //                          read-modify-write of its counts.  Every count has exactly one owner: no atomic, no LDS.  A stream: 3 B in
 //                          per pixel and frame, 4 B in and out per pixel once per block.  It carries no previous pixels.
 //   content_fill_kernel    read-out: content = lit * 1000000 > min_share_ppm * frames (u64).  A thread owns a column and walks a strip

@@ -26,6 +26,8 @@
 
 #include <cmath>
 
+#include "bgr_store.hip.h"
+
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 #define RECT_HD __host__ __device__ __forceinline__
@@ -113,18 +115,6 @@ RECT_HD uint32_t rect_blend(uint32_t p00, uint32_t p01, uint32_t p10, uint32_t p
             512u) >> 10;
 }
 
-// `cnt` pixels (b | g << 8 | r << 16 each) to d: 3 dwords when all 4 are there and d is dword-aligned, bytes otherwise
-RECT_HD void rect_store4(uint8_t* d, const uint32_t (&p)[4], int cnt, bool dwords) {
-    if (dwords && cnt == 4) {
-        uint32_t* q = reinterpret_cast<uint32_t*>(d);
-        q[0] = p[0] | (p[1] << 24);                   // b0 g0 r0 b1
-        q[1] = (p[1] >> 8) | (p[2] << 16);            // g1 r1 b2 g2
-        q[2] = (p[2] >> 16) | (p[3] << 8);            // r2 b3 g3 r3
-        return;
-    }
-    for (int i = 0; i < cnt; ++i) { d[3 * i] = (uint8_t)p[i]; d[3 * i + 1] = (uint8_t)(p[i] >> 8); d[3 * i + 2] = (uint8_t)(p[i] >> 16); }
-}
-
 // The thread that owns destination pixels 4 tix .. 4 tix + 3 of row dy of frame z
 template <int KIND>
 RECT_HD void rectify_thread(const RectifyArgs& a, int tix, int dy, int z) {
@@ -170,7 +160,7 @@ RECT_HD void rectify_thread(const RectifyArgs& a, int tix, int dy, int z) {
         }
     }
     uint8_t* d = a.dst + ((int64_t)z * a.dh + dy) * a.dw * 3 + (int64_t)x0 * 3;
-    rect_store4(d, p, cnt, a.out4 != 0);
+    bgr_store4(d, p, cnt, a.out4 != 0);
 }
 
 // The instance of a map (host): an integer translation (a copy), an affine map (W constant), or the projective kernel

@@ -28,7 +28,7 @@ struct FrameMask { bool set = false; int w = 0, h = 0; };
 struct GateMap { bool on = false; int sw = 0, sh = 0; int64_t n_valid = 0; };
 
 // How every slideo_yuv420_layout call reads its samples (SLIDEO_YUV_MATRIX_* / _RANGE_* / _DEPTH_*); all 0: the default.  The
-// sampling (SLIDEO_YUV_SAMPLING_*, "YUV sampling") is set on its own and says where the samples lie; is_default() is the colour's.
+// sampling (SLIDEO_YUV_SAMPLING_*, "YUV sampling") is set on its own and says where the samples lie.
 // The chroma filter (SLIDEO_YUV_CHROMA_*, "YUV chroma filter") is set on its own too and says how a pixel's chroma is read from them
 struct YuvDesc {
     int matrix = SLIDEO_YUV_MATRIX_BT601, range = SLIDEO_YUV_RANGE_LIMITED, depth = SLIDEO_YUV_DEPTH_8;
@@ -40,7 +40,6 @@ struct YuvDesc {
     float white_nits = 0.f;
     // the bilinear kernel converts the frames: a filter is set and the sampling has chroma to interpolate
     bool filtered() const { return chroma != SLIDEO_YUV_CHROMA_NEAREST && sampling != SLIDEO_YUV_SAMPLING_444; }
-    bool is_default() const { return matrix == SLIDEO_YUV_MATRIX_BT601 && range == SLIDEO_YUV_RANGE_LIMITED && depth == SLIDEO_YUV_DEPTH_8; }
     int bytes_per_sample() const { return depth == SLIDEO_YUV_DEPTH_8 ? 1 : 2; }
 };
 // The per-channel tone table of "Frame levels": lut[c * 256 + v], c = 0, 1, 2 for B, G, R (the matcher's d_levels holds its copy on

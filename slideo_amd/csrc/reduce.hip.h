@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "bgr_store.hip.h"
 #include "geom.h"
 
 namespace slideo {
@@ -33,18 +34,6 @@ struct ReduceArgs {
 
 // saturate_cast<uchar>(float): cvRound (ties to even), then the clamp
 __device__ __forceinline__ uint32_t red_sat_u8(float v) { return (uint32_t)min(max((int)rintf(v), 0), 255); }
-
-// `cnt` pixels (b | g << 8 | r << 16 each) to d: 3 dwords when all 4 are there and d is dword-aligned, bytes otherwise
-__device__ __forceinline__ void red_store4(uint8_t* __restrict__ d, const uint32_t (&p)[4], int cnt, bool dwords) {
-    if (dwords && cnt == 4) {
-        uint32_t* q = reinterpret_cast<uint32_t*>(d);
-        q[0] = p[0] | (p[1] << 24);                   // b0 g0 r0 b1
-        q[1] = (p[1] >> 8) | (p[2] << 16);            // g1 r1 b2 g2
-        q[2] = (p[2] >> 16) | (p[3] << 8);            // r2 b3 g3 r3
-        return;
-    }
-    for (int i = 0; i < cnt; ++i) { d[3 * i] = (uint8_t)p[i]; d[3 * i + 1] = (uint8_t)(p[i] >> 8); d[3 * i + 2] = (uint8_t)(p[i] >> 16); }
-}
 
 // The launch guarantees (launch_reduce): sw == 2 dw, sh == 2 dh, dw % 4 == 0, src / src_stride / src_frame_stride multiples of 8,
 // dst dword-aligned.  A thread reads the 8 source pixels under its 4 outputs from both rows as 3 + 3 aligned 8-byte loads (byte
@@ -79,7 +68,7 @@ __global__ __launch_bounds__(RED_TX * RED_TY) void reduce2x2_kernel(ReduceArgs a
         p[i] = b | (g << 8) | (r << 16);
     }
     uint8_t* d = a.dst + ((int64_t)blockIdx.z * a.dh + dy) * a.dw * 3 + (int64_t)x0 * 3;
-    red_store4(d, p, 4, true);
+    bgr_store4(d, p, 4, true);
 }
 
 // ResizeAreaFast for any integer factors ix, iy (sw == ix dw, sh == iy dh), bytes.
@@ -104,7 +93,7 @@ __global__ __launch_bounds__(RED_TX * RED_TY) void reduce_int_kernel(ReduceArgs 
         else p[i] = red_sat_u8((float)s0 * a.inv_area) | (red_sat_u8((float)s1 * a.inv_area) << 8) | (red_sat_u8((float)s2 * a.inv_area) << 16);
     }
     uint8_t* d = a.dst + ((int64_t)blockIdx.z * a.dh + dy) * a.dw * 3 + (int64_t)x0 * 3;
-    red_store4(d, p, cnt, a.out4 != 0);
+    bgr_store4(d, p, cnt, a.out4 != 0);
 }
 
 // ResizeArea_Invoker: taps / idx are the class's own tables (ag's offsets index them), as build_area_geom_to made them.
@@ -135,7 +124,7 @@ __global__ __launch_bounds__(RED_TX * RED_TY) void reduce_area_kernel(ReduceArgs
         p[i] = red_sat_u8(s0) | (red_sat_u8(s1) << 8) | (red_sat_u8(s2) << 16);
     }
     uint8_t* d = a.dst + ((int64_t)blockIdx.z * a.dh + dy) * a.dw * 3 + (int64_t)x0 * 3;
-    red_store4(d, p, cnt, a.out4 != 0);
+    bgr_store4(d, p, cnt, a.out4 != 0);
 }
 
 }  // namespace slideo

@@ -574,7 +574,7 @@ void launch_rectify(const FrameRegion& R, const uint8_t* src, int64_t src_fs, in
 // the rectify_kernel instance of a map: R.kind, R.tx, R.ty from R.M
 void frame_region_classify(FrameRegion& R);
 // n decoded YUV 4:2:0 frames (a layout yuv420_validate accepted under `desc`, frame stride src_fs) -> BGR8 at dst, stride 3w, frame
-// stride 3wh.  The default description: yuv420_to_bgr_kernel; any other: yuv420_to_bgr_desc_kernel.  transfer_tab: the matcher's
+// stride 3wh.  One kernel family per call (stage_orb.hip): transfer, chroma filter, sampling, else yuv420_to_bgr_desc_kernel.  transfer_tab: the matcher's
 // d_transfer, read under a transfer other than SDR alone (yuv_transfer_to_bgr_kernel)
 void launch_yuv420_to_bgr(const YuvDesc& desc, const uint8_t* src, int64_t src_fs, const slideo_yuv420_layout& L, int w, int h, int n, uint8_t* dst, hipStream_t st,
                           const uint32_t* transfer_tab = nullptr);

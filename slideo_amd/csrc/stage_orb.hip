@@ -1,6 +1,9 @@
-// stage_orb.hip — drivers of the ORB stage (kernels: orb.hip.h) and of the front doors in front of it: YUV frames
-// (yuv420.hip.h, yuv_sampling.hip.h, yuv_chroma.hip.h, yuv_transfer.hip.h), frames of another pixel format (pixel_format.hip.h), the frame levels' table (levels.hip.h), the working-size reduce (reduce.hip.h) and the frame region's rectify (frame_region.hip.h); the frame mask's
-// pyramid and candidate filter (frame_mask.hip.h).
+// stage_orb.hip — drivers of the ORB stage (kernels: orb.hip.h) and of the front doors in front of it: YUV frames (one argument
+// record and one dispatch over the kernel families of yuv420.hip.h, yuv_sampling.hip.h, yuv_chroma.hip.h, yuv_transfer.hip.h), frames of
+// another pixel format (pixel_format.hip.h), the frame levels' table (levels.hip.h), the working-size reduce (reduce.hip.h) and the
+// frame region's rectify (frame_region.hip.h); the frame mask's pyramid and candidate filter (frame_mask.hip.h).
+#include <type_traits>
+
 #include "runtime.hpp"
 #include "orb.hip.h"
 #include "yuv420.hip.h"
@@ -61,145 +64,92 @@ void orb_launch_gray(const slideo_matcher* m, const uint8_t* frames_dev, int64_t
     check_launch("gray_kernel");
 }
 
-// yuv420_to_bgr_desc_kernel's arguments for a validated layout: which of its wide loads and stores the addresses allow
-static YuvDescArgs yuv_desc_args(const YuvDesc& desc, const uint8_t* src, int64_t src_fs, const slideo_yuv420_layout& L, int w, int h, uint8_t* dst) {
-    YuvDescArgs a{};
-    a.src = src; a.src_frame_stride = src_fs;
-    a.interleaved = L.uv_step == 2;
-    a.v_first = a.interleaved && L.v_offset < L.u_offset;
-    a.c_ofs = a.interleaved ? std::min(L.u_offset, L.v_offset) : L.u_offset;
-    a.v_ofs = L.v_offset;
-    a.y_stride = L.y_stride; a.uv_stride = L.uv_stride;
-    a.dst = dst; a.w = w; a.h = h;
-    // 8-bit samples: dword luma, dword (interleaved) or u16 (planar) chroma; 16-bit containers: 8-byte luma, dword chroma
-    const bool wide = desc.depth != SLIDEO_YUV_DEPTH_8;
-    const uintptr_t ay = wide ? 8 : 4, ac = wide || a.interleaved ? 4 : 2, base = (uintptr_t)src;
-    auto aligned = [&](int64_t ofs, int stride, uintptr_t al) { return (base + (uintptr_t)ofs) % al == 0 && (uintptr_t)src_fs % al == 0 && (uintptr_t)stride % al == 0; };
-    a.wide_y = aligned(0, L.y_stride, ay);
-    a.wide_c = aligned(a.c_ofs, L.uv_stride, ac) && (a.interleaved || aligned(a.v_ofs, L.uv_stride, ac));
-    a.out4 = (uintptr_t)dst % 4 == 0 && w % 4 == 0;
-    return a;
-}
-
-// the frames of a sampling other than 4:2:0 ("YUV sampling"): one thread per four columns of one row
-static void launch_yuv_sampled(const YuvDesc& desc, const uint8_t* src, int64_t src_fs, const slideo_yuv420_layout& L, int w, int h, int n, uint8_t* dst,
-                               hipStream_t st) {
-    const YuvSampArgs a = yuv_sampled_args(desc.sampling, desc.depth, src, src_fs, L, w, h, n, dst);
+// ---- the YUV door: one argument record (yuv420.hip.h YuvArgs, filled by yuv_args and each family's two lines on it), one dispatch -------
+static YuvCoef yuv_coef(const YuvDesc& desc) {
     int32_t c[7];
     yuv_coefficients(desc.matrix, desc.range, c);
-    const YuvCoef k{c[0], c[1], c[2], c[3], c[4], c[5]};
-    const dim3 grid(cdiv(cdiv(w, 4), YUV_TX), cdiv(h, YUV_TY), n), block(YUV_TX, YUV_TY);
-    const int d = desc.depth;
-    if (desc.sampling == SLIDEO_YUV_SAMPLING_422_PACKED) {
-        if (d != SLIDEO_YUV_DEPTH_8) fail(SLIDEO_ERR_UNSUPPORTED, "internal: packed 4:2:2 under a 10-bit depth");
-        yuv_sampled_to_bgr_kernel<YUV_S422P, YUV_D8><<<grid, block, 0, st>>>(a, k);
-    } else if (desc.sampling == SLIDEO_YUV_SAMPLING_422) {
-        if (d == SLIDEO_YUV_DEPTH_8) yuv_sampled_to_bgr_kernel<YUV_S422, YUV_D8><<<grid, block, 0, st>>>(a, k);
-        else if (d == SLIDEO_YUV_DEPTH_10_MSB) yuv_sampled_to_bgr_kernel<YUV_S422, YUV_D10_MSB><<<grid, block, 0, st>>>(a, k);
-        else yuv_sampled_to_bgr_kernel<YUV_S422, YUV_D10_LSB><<<grid, block, 0, st>>>(a, k);
-    } else {
-        if (d == SLIDEO_YUV_DEPTH_8) yuv_sampled_to_bgr_kernel<YUV_S444, YUV_D8><<<grid, block, 0, st>>>(a, k);
-        else if (d == SLIDEO_YUV_DEPTH_10_MSB) yuv_sampled_to_bgr_kernel<YUV_S444, YUV_D10_MSB><<<grid, block, 0, st>>>(a, k);
-        else yuv_sampled_to_bgr_kernel<YUV_S444, YUV_D10_LSB><<<grid, block, 0, st>>>(a, k);
-    }
-    check_launch("yuv_sampled_to_bgr_kernel");
+    return YuvCoef{c[0], c[1], c[2], c[3], c[4], c[5]};
 }
 
-// 4:2:0 and 4:2:2 frames under a chroma filter other than NEAREST ("YUV chroma filter"): one thread per four columns of the two
-// luma rows of a chroma row (420) or of one row (422)
-static void launch_yuv_chroma(const YuvDesc& desc, const uint8_t* src, int64_t src_fs, const slideo_yuv420_layout& L, int w, int h, int n, uint8_t* dst,
-                              hipStream_t st) {
-    int32_t w12[12];
-    YuvChromaArgs a;
-    if (!yuv_chroma_weights(desc.chroma, desc.sampling, w12) || !yuv_chroma_args(desc.sampling, desc.depth, w12, src, src_fs, L, w, h, n, dst, &a))
-        fail(SLIDEO_ERR_HIP, "internal: no chroma filter kernel for filter %d under sampling %d", desc.chroma, desc.sampling);
-    int32_t c[7];
-    yuv_coefficients(desc.matrix, desc.range, c);
-    const YuvCoef k{c[0], c[1], c[2], c[3], c[4], c[5]};
-    const bool s420 = desc.sampling == SLIDEO_YUV_SAMPLING_420;
-    const dim3 grid(cdiv(cdiv(w, 4), YUV_TX), cdiv(s420 ? h / 2 : h, YUV_TY), n), block(YUV_TX, YUV_TY);
-    const int d = desc.depth;
-    if (desc.sampling == SLIDEO_YUV_SAMPLING_422_PACKED) {
-        if (d != SLIDEO_YUV_DEPTH_8) fail(SLIDEO_ERR_UNSUPPORTED, "internal: packed 4:2:2 under a 10-bit depth");
-        yuv_chroma_to_bgr_kernel<YUV_S422P, YUV_D8><<<grid, block, 0, st>>>(a, k);
-    } else if (s420) {
-        if (d == SLIDEO_YUV_DEPTH_8) yuv_chroma_to_bgr_kernel<YUV_S420, YUV_D8><<<grid, block, 0, st>>>(a, k);
-        else if (d == SLIDEO_YUV_DEPTH_10_MSB) yuv_chroma_to_bgr_kernel<YUV_S420, YUV_D10_MSB><<<grid, block, 0, st>>>(a, k);
-        else yuv_chroma_to_bgr_kernel<YUV_S420, YUV_D10_LSB><<<grid, block, 0, st>>>(a, k);
-    } else {
-        if (d == SLIDEO_YUV_DEPTH_8) yuv_chroma_to_bgr_kernel<YUV_S422, YUV_D8><<<grid, block, 0, st>>>(a, k);
-        else if (d == SLIDEO_YUV_DEPTH_10_MSB) yuv_chroma_to_bgr_kernel<YUV_S422, YUV_D10_MSB><<<grid, block, 0, st>>>(a, k);
-        else yuv_chroma_to_bgr_kernel<YUV_S422, YUV_D10_LSB><<<grid, block, 0, st>>>(a, k);
-    }
-    check_launch("yuv_chroma_to_bgr_kernel");
+// the runtime depth, and (sampling, depth), as template constants: f(integral_constant<int, YUV_D*>) and f(integral_constant<int,
+// YUV_S*>, integral_constant<int, YUV_D*>).  A family launches the instances it has; for a pair it has none for, which the rules in
+// front of it never let through, it calls yuv_no_kernel
+template <class F>
+static void yuv_dispatch_depth(int depth, F&& f) {
+    if (depth == SLIDEO_YUV_DEPTH_8) f(std::integral_constant<int, YUV_D8>{});
+    else if (depth == SLIDEO_YUV_DEPTH_10_MSB) f(std::integral_constant<int, YUV_D10_MSB>{});
+    else f(std::integral_constant<int, YUV_D10_LSB>{});
+}
+template <class F>
+static void yuv_dispatch(int sampling, int depth, F&& f) {
+    auto at_depth = [&](auto s) { yuv_dispatch_depth(depth, [&](auto d) { f(s, d); }); };
+    if (sampling == SLIDEO_YUV_SAMPLING_422_PACKED) {
+        if (depth != SLIDEO_YUV_DEPTH_8) fail(SLIDEO_ERR_UNSUPPORTED, "internal: packed 4:2:2 under a 10-bit depth");
+        f(std::integral_constant<int, YUV_S422P>{}, std::integral_constant<int, YUV_D8>{});
+    } else if (sampling == SLIDEO_YUV_SAMPLING_420) at_depth(std::integral_constant<int, YUV_S420>{});
+    else if (sampling == SLIDEO_YUV_SAMPLING_422) at_depth(std::integral_constant<int, YUV_S422>{});
+    else at_depth(std::integral_constant<int, YUV_S444>{});
 }
 
-// 10-bit frames under a transfer other than SDR ("YUV transfer"): the thread shapes of the nearest kernels; tab: the matcher's device
-// copy of LIN and OUT.  The description's matrix is not consulted
-static void launch_yuv_transfer(const YuvDesc& desc, const uint8_t* src, int64_t src_fs, const slideo_yuv420_layout& L, int w, int h, int n, uint8_t* dst,
-                                hipStream_t st, const uint32_t* tab32) {
-    const uint4* tab = reinterpret_cast<const uint4*>(tab32);
-    const int d = desc.depth, s = desc.sampling;
-    if (!tab || d == SLIDEO_YUV_DEPTH_8 || s == SLIDEO_YUV_SAMPLING_422_PACKED || desc.filtered())
-        fail(SLIDEO_ERR_HIP, "internal: no transfer kernel for transfer %d under depth %d, sampling %d, chroma filter %d", desc.transfer, d, s, desc.chroma);
-    const YuvTransferArgs a = yuv_transfer_args(src, src_fs, L, w, h, n, dst);
-    int32_t c[7];
-    YuvTransferCoef k{};
-    yuv_transfer_coefficients(desc.range, c);
-    k.cy = c[0]; k.cub = c[1]; k.cug = c[2]; k.cvg = c[3]; k.cvr = c[4]; k.yofs = c[5];
-    yuv_transfer_gamut(k.g);
-    const bool s420 = s == SLIDEO_YUV_SAMPLING_420, msb = d == SLIDEO_YUV_DEPTH_10_MSB;
-    const dim3 grid(cdiv(cdiv(w, 4), YUV_TX), cdiv(s420 ? h / 2 : h, YUV_TY * YUV_TRK_ROWS), n), block(YUV_TX, YUV_TY);
-    if (s420) {
-        if (msb) yuv_transfer_to_bgr_kernel<YUV_T420, YUV_D10_MSB><<<grid, block, 0, st>>>(a, k, tab);
-        else yuv_transfer_to_bgr_kernel<YUV_T420, YUV_D10_LSB><<<grid, block, 0, st>>>(a, k, tab);
-    } else if (s == SLIDEO_YUV_SAMPLING_422) {
-        if (msb) yuv_transfer_to_bgr_kernel<YUV_S422, YUV_D10_MSB><<<grid, block, 0, st>>>(a, k, tab);
-        else yuv_transfer_to_bgr_kernel<YUV_S422, YUV_D10_LSB><<<grid, block, 0, st>>>(a, k, tab);
-    } else {
-        if (msb) yuv_transfer_to_bgr_kernel<YUV_S444, YUV_D10_MSB><<<grid, block, 0, st>>>(a, k, tab);
-        else yuv_transfer_to_bgr_kernel<YUV_S444, YUV_D10_LSB><<<grid, block, 0, st>>>(a, k, tab);
-    }
-    check_launch("yuv_transfer_to_bgr_kernel");
+[[noreturn]] static void yuv_no_kernel(const char* family, int sampling, int depth) {
+    fail(SLIDEO_ERR_HIP, "internal: no %s kernel for sampling %d under depth %d", family, sampling, depth);
 }
 
-// n decoded YUV frames (validated layout, frame stride src_fs) -> BGR8 at dst (stride 3w, frame stride 3wh).  Under the 4:2:0
-// sampling exactly what it launched before the sampling existed, under the NEAREST chroma filter, or 4:4:4, exactly what it
-// launched before the filter existed, and under the SDR transfer exactly what it launched before the transfer existed
+// n decoded YUV frames (validated layout, frame stride src_fs) -> BGR8 at dst (stride 3w, frame stride 3wh).  One kernel family per
+// call, in this order: a transfer other than SDR (10-bit frames; tab: the matcher's device copy of LIN and OUT; the description's
+// matrix is not consulted), a chroma filter other than NEAREST where the sampling has chroma to interpolate, a sampling other than
+// 4:2:0, else the 4:2:0 description kernel — the default description (BT.601, limited, 8) included, whose coefficients are
+// cvtColor(COLOR_YUV2BGR_*)'s.  A thread owns four columns of one row, or of the two luma rows of a chroma row (rows2)
 void launch_yuv420_to_bgr(const YuvDesc& desc, const uint8_t* src, int64_t src_fs, const slideo_yuv420_layout& L, int w, int h, int n, uint8_t* dst,
                           hipStream_t st, const uint32_t* transfer_tab) {
-    if (desc.transfer != SLIDEO_YUV_TRANSFER_SDR) { launch_yuv_transfer(desc, src, src_fs, L, w, h, n, dst, st, transfer_tab); return; }
-    if (desc.filtered()) { launch_yuv_chroma(desc, src, src_fs, L, w, h, n, dst, st); return; }
-    if (desc.sampling != SLIDEO_YUV_SAMPLING_420) { launch_yuv_sampled(desc, src, src_fs, L, w, h, n, dst, st); return; }
-    dim3 grid(cdiv(cdiv(w, 4), YUV_TX), cdiv(h / 2, YUV_TY), n);
-    if (!desc.is_default()) {
-        const YuvDescArgs d = yuv_desc_args(desc, src, src_fs, L, w, h, dst);
+    const int s = desc.sampling, d = desc.depth;
+    const bool rows2 = s == SLIDEO_YUV_SAMPLING_420;
+    const dim3 block(YUV_TX, YUV_TY);
+    if (desc.transfer != SLIDEO_YUV_TRANSFER_SDR) {
+        const uint4* tab = reinterpret_cast<const uint4*>(transfer_tab);
+        if (!tab || d == SLIDEO_YUV_DEPTH_8 || s == SLIDEO_YUV_SAMPLING_422_PACKED || desc.filtered())
+            fail(SLIDEO_ERR_HIP, "internal: no transfer kernel for transfer %d under depth %d, sampling %d, chroma filter %d", desc.transfer, d, s, desc.chroma);
+        const YuvArgs a = yuv_transfer_args(s, src, src_fs, L, w, h, n, dst);
         int32_t c[7];
-        yuv_coefficients(desc.matrix, desc.range, c);
-        const YuvCoef k{c[0], c[1], c[2], c[3], c[4], c[5]};
-        const dim3 block(YUV_TX, YUV_TY);
-        if (desc.depth == SLIDEO_YUV_DEPTH_8) yuv420_to_bgr_desc_kernel<YUV_D8><<<grid, block, 0, st>>>(d, k);
-        else if (desc.depth == SLIDEO_YUV_DEPTH_10_MSB) yuv420_to_bgr_desc_kernel<YUV_D10_MSB><<<grid, block, 0, st>>>(d, k);
-        else yuv420_to_bgr_desc_kernel<YUV_D10_LSB><<<grid, block, 0, st>>>(d, k);
+        YuvTransferCoef k{};
+        yuv_transfer_coefficients(desc.range, c);
+        k.cy = c[0]; k.cub = c[1]; k.cug = c[2]; k.cvg = c[3]; k.cvr = c[4]; k.yofs = c[5];
+        yuv_transfer_gamut(k.g);
+        const dim3 grid(cdiv(cdiv(w, 4), YUV_TX), cdiv(rows2 ? h / 2 : h, YUV_TY * YUV_TRK_ROWS), n);
+        yuv_dispatch(s, d, [&](auto S, auto D) {
+            if constexpr (S() != YUV_S422P && D() != YUV_D8) yuv_transfer_to_bgr_kernel<S(), D()><<<grid, block, 0, st>>>(a, k, tab);
+            else yuv_no_kernel("transfer", s, d);
+        });
+        check_launch("yuv_transfer_to_bgr_kernel");
+    } else if (desc.filtered()) {
+        int32_t w12[12];
+        YuvArgs a;
+        YuvChromaW wt;
+        if (!yuv_chroma_weights(desc.chroma, s, w12) || !yuv_chroma_args(s, d, w12, src, src_fs, L, w, h, n, dst, &a, &wt))
+            fail(SLIDEO_ERR_HIP, "internal: no chroma filter kernel for filter %d under sampling %d", desc.chroma, s);
+        const YuvCoef k = yuv_coef(desc);
+        const dim3 grid(cdiv(cdiv(w, 4), YUV_TX), cdiv(rows2 ? h / 2 : h, YUV_TY), n);
+        yuv_dispatch(s, d, [&](auto S, auto D) {
+            if constexpr (S() != YUV_S444) yuv_chroma_to_bgr_kernel<S(), D()><<<grid, block, 0, st>>>(a, wt, k);
+            else yuv_no_kernel("chroma filter", s, d);
+        });
+        check_launch("yuv_chroma_to_bgr_kernel");
+    } else if (!rows2) {
+        const YuvArgs a = yuv_sampled_args(s, d, src, src_fs, L, w, h, n, dst);
+        const YuvCoef k = yuv_coef(desc);
+        const dim3 grid(cdiv(cdiv(w, 4), YUV_TX), cdiv(h, YUV_TY), n);
+        yuv_dispatch(s, d, [&](auto S, auto D) {
+            if constexpr (S() != YUV_S420) yuv_sampled_to_bgr_kernel<S(), D()><<<grid, block, 0, st>>>(a, k);
+            else yuv_no_kernel("sampling", s, d);
+        });
+        check_launch("yuv_sampled_to_bgr_kernel");
+    } else {
+        const YuvArgs a = yuv_desc_args(d, src, src_fs, L, w, h, n, dst);
+        const YuvCoef k = yuv_coef(desc);
+        const dim3 grid(cdiv(cdiv(w, 4), YUV_TX), cdiv(h / 2, YUV_TY), n);
+        yuv_dispatch_depth(d, [&](auto D) { yuv420_to_bgr_desc_kernel<D()><<<grid, block, 0, st>>>(a, k); });
         check_launch("yuv420_to_bgr_desc_kernel");
-        return;
     }
-    Yuv420Args a{};
-    a.src = src; a.src_frame_stride = src_fs;
-    a.interleaved = L.uv_step == 2;
-    a.v_first = a.interleaved && L.v_offset < L.u_offset;
-    a.c_ofs = a.interleaved ? std::min(L.u_offset, L.v_offset) : L.u_offset;
-    a.v_ofs = L.v_offset;
-    a.y_stride = L.y_stride; a.uv_stride = L.uv_stride;
-    a.dst = dst; a.w = w; a.h = h;
-    // dword luma loads at x % 4 == 0, a dword (interleaved) or u16 (planar) chroma load at x (x / 2), 3 dword stores at 3x
-    const bool luma4 = (uintptr_t)src % 4 == 0 && src_fs % 4 == 0 && L.y_stride % 4 == 0;
-    const bool chroma = a.interleaved ? (a.c_ofs % 4 == 0 && L.uv_stride % 4 == 0)
-                                      : (L.u_offset % 2 == 0 && L.v_offset % 2 == 0 && L.uv_stride % 2 == 0);
-    const bool out4 = (uintptr_t)dst % 4 == 0 && w % 4 == 0;
-    a.fast = luma4 && chroma && out4;
-    yuv420_to_bgr_kernel<<<grid, dim3(YUV_TX, YUV_TY), 0, st>>>(a);
-    check_launch("yuv420_to_bgr_kernel");
 }
 
 // n frames under a pixel format other than SLIDEO_PIXEL_BGR8 (a layout pixel_format_validate accepted: rows `stride`, frames src_fs

@@ -7,7 +7,7 @@
 // 422 at three depths, packed at 8 bits.  The per-pixel arithmetic is yuv420.hip.h's description kernel's by inclusion (yuv_desc_px,
 // yuv_s8, yuv_pack4, yuv_load4: coefficients in SGPRs, 24-bit multiplies, clamp before shift; the chroma terms are yuv_desc_chroma's
 // integers, computed per pixel with the - 128 folded into a constant: yuv_chroma_terms), the load helpers are yuv_sampling.hip.h's
-// (yuv_apart, yuv_ld64, yuv_ld16, yuv_plane_align).  Only U8 and V8 of a pixel are new.
+// (yuv_apart, yuv_ld64, yuv_ld16).  Only U8 and V8 of a pixel are new.
 // Thread shape: four consecutive pixels of two luma rows 2cy, 2cy + 1 (420: the rows that share chroma row cy) or of one row (422);
 // block YUV_TX x YUV_TY = 64 threads along a row x 4 thread rows, so a wave is 64 consecutive threads of one thread row.
 // The stencil.  The tables of slideo_yuv_chroma_weights have two structural zeros per axis — parity 0 never reaches sample k + 1,
@@ -31,8 +31,6 @@
 // No multi-dword load is issued at an address that is not a multiple of its size; no LDS, no scratch.
 // The per-thread body is a host + device function: tools/yuv_chroma_hostcheck.cpp runs it lane by lane on the CPU.
 #pragma once
-#include <algorithm>
-
 #include "slideo_amd.h"
 #include "yuv_sampling.hip.h"
 
@@ -42,67 +40,38 @@
 
 namespace slideo {
 
-constexpr int YUV_S420 = 0;                                       // = SLIDEO_YUV_SAMPLING_420 (422 and packed: yuv_sampling.hip.h)
-
-struct YuvChromaArgs {
-    const uint8_t* src;
-    int64_t src_frame_stride;    // all strides and offsets in BYTES, whatever the container
-    int64_t c_ofs;               // interleaved: the first byte of the chroma plane (min of u_offset, v_offset); planar: u_offset
-    int64_t v_ofs;               // planar: v_offset
-    int y_stride, uv_stride;
-    int interleaved, v_first;
-    uint8_t* dst;                // BGR8, row stride 3w, frame stride 3wh
-    int w, h;
-    int wide_y;                  // planar luma: 1 = a thread's 4 samples of a row are one aligned load; packed: 8 / 4 = its 8 bytes are one / two
-    int wide_c;                  // chroma: nonzero = the thread's own samples are wide loads; interleaved 16-bit: 8 / 4, the load's size
-    int out4;                    // dword stores: dst dword-aligned and w % 4 == 0
-    uint32_t sel_y;              // packed: v_perm selector of Y0 Y1 Y2 Y3 out of a thread's 8 bytes
-    uint32_t sel_c;              // packed, interleaved: v_perm selector of U0 U1 V0 V1 out of the thread's chroma bytes
-    uint32_t wh[4];              // wh[0][0], wh[0][1], wh[1][1], wh[1][2] of slideo_yuv_chroma_weights, each in both 16-bit halves
+// the EIGHT weights that can be nonzero, each in both 16-bit halves
+struct YuvChromaW {
+    uint32_t wh[4];              // wh[0][0], wh[0][1], wh[1][1], wh[1][2] of slideo_yuv_chroma_weights
     uint32_t wv[4];              // wv likewise (422: unused)
 };
 
 // The kernel's arguments for n frames in a layout yuv420_validate accepted under (sampling, depth), with the twelve integers of
-// slideo_yuv_chroma_weights: which wide loads and stores the addresses allow.  A single frame has no stride to be aligned.
+// slideo_yuv_chroma_weights: yuv_args' record with this family's wide_y and wide_c, and the weights.
 // false: the table is not one this kernel computes (a structural zero is not zero)
 inline bool yuv_chroma_args(int sampling, int depth, const int32_t* w12, const uint8_t* src, int64_t src_fs, const slideo_yuv420_layout& L, int w, int h,
-                            int n, uint8_t* dst, YuvChromaArgs* out) {
-    YuvChromaArgs a{};
+                            int n, uint8_t* dst, YuvArgs* out, YuvChromaW* wt) {
     for (int ax = 0; ax < 2; ++ax) {
         const int32_t* t = w12 + 6 * ax;
         if (t[2] != 0 || t[3] != 0) return false;
         const int32_t four[4] = {t[0], t[1], t[4], t[5]};
         for (int i = 0; i < 4; ++i) {
             if (four[i] < 0 || four[i] > 4) return false;
-            (ax ? a.wv : a.wh)[i] = (uint32_t)four[i] * 0x00010001u;
+            (ax ? wt->wv : wt->wh)[i] = (uint32_t)four[i] * 0x00010001u;
         }
     }
-    a.src = src; a.src_frame_stride = src_fs;
-    a.y_stride = L.y_stride; a.uv_stride = L.uv_stride;
-    a.dst = dst; a.w = w; a.h = h;
-    a.out4 = (uintptr_t)dst % 4 == 0 && w % 4 == 0;
-    const int64_t fs = n > 1 ? src_fs : 0;
+    int ay, ac;
+    YuvArgs a = yuv_args(sampling, src, src_fs, L, w, h, n, dst, &ay, &ac);
     const int B = depth == SLIDEO_YUV_DEPTH_8 ? 1 : 2;
-    const int ay = yuv_plane_align(src, 0, fs, L.y_stride);
-    if (sampling == SLIDEO_YUV_SAMPLING_422_PACKED) {
-        const uint32_t ly = (uint32_t)((L.u_offset & 1) ^ 1), uo = (uint32_t)L.u_offset, vo = (uint32_t)L.v_offset;
-        a.sel_y = ly | (ly + 2) << 8 | (ly + 4) << 16 | (ly + 6) << 24;
-        a.sel_c = uo | (uo + 4) << 8 | vo << 16 | (vo + 4) << 24;
-        a.wide_y = ay >= 8 ? 8 : ay >= 4 ? 4 : 0;
-        *out = a;
-        return true;
+    // wide_y: planar luma, 1 = a thread's 4 samples of a row are one aligned load; packed, 8 / 4 = its 8 bytes are one / two.
+    // wide_c, a thread's own chroma: interleaved 4 B bytes (8-bit: one dword; 16-bit: 8 / 4, one 8-byte load or two dwords), planar
+    // 2 B per plane
+    if (sampling == SLIDEO_YUV_SAMPLING_422_PACKED) a.wide_y = yuv_load_mode(ay);
+    else {
+        a.wide_y = ay >= 4 * B;
+        if (a.interleaved) a.wide_c = B == 1 ? ac >= 4 : yuv_load_mode(ac);
+        else a.wide_c = ac >= 2 * B;
     }
-    a.interleaved = L.uv_step == 2;
-    a.v_first = a.interleaved && L.v_offset < L.u_offset;
-    a.c_ofs = a.interleaved ? std::min(L.u_offset, L.v_offset) : L.u_offset;
-    a.v_ofs = L.v_offset;
-    a.sel_c = a.v_first ? 0x02000301u : 0x03010200u;              // first0 second0 first1 second1 -> U0 U1 V0 V1
-    a.wide_y = ay >= 4 * B;
-    const int au = yuv_plane_align(src, a.c_ofs, fs, L.uv_stride);
-    const int ac = a.interleaved ? au : std::min(au, yuv_plane_align(src, a.v_ofs, fs, L.uv_stride));
-    // a thread's own chroma: interleaved 4 B bytes (8-bit: one dword; 16-bit: one 8-byte load, or two dwords), planar 2 B per plane
-    if (a.interleaved) a.wide_c = B == 1 ? ac >= 4 : (ac >= 8 ? 8 : ac >= 4 ? 4 : 0);
-    else a.wide_c = ac >= 2 * B;
     *out = a;
     return true;
 }
@@ -120,7 +89,7 @@ YUV_HD uint32_t yuv_mad2(uint32_t w2, uint32_t p, uint32_t acc) {
 // chroma sample k of chroma row crow as U | V << 16, 8-bit values: byte loads, any alignment (halo samples and unaligned layouts).
 // _pair: packed macropixels and interleaved planes; _planar: two planes; yuv_chroma_at picks one (a.interleaved is uniform)
 template <int SAMPLING, int DEPTH>
-YUV_HD uint32_t yuv_chroma_at_pair(const YuvChromaArgs& a, const uint8_t* f, int crow, int k) {
+YUV_HD uint32_t yuv_chroma_at_pair(const YuvArgs& a, const uint8_t* f, int crow, int k) {
     constexpr int B = DEPTH == YUV_D8 ? 1 : 2;
     if (SAMPLING == YUV_S422P) {
         const uint8_t* p = f + (int64_t)crow * a.y_stride + (int64_t)k * 4;
@@ -131,13 +100,13 @@ YUV_HD uint32_t yuv_chroma_at_pair(const YuvChromaArgs& a, const uint8_t* f, int
     return a.v_first ? second | first << 16 : first | second << 16;
 }
 template <int SAMPLING, int DEPTH>
-YUV_HD uint32_t yuv_chroma_at_planar(const YuvChromaArgs& a, const uint8_t* f, int crow, int k) {
+YUV_HD uint32_t yuv_chroma_at_planar(const YuvArgs& a, const uint8_t* f, int crow, int k) {
     constexpr int B = DEPTH == YUV_D8 ? 1 : 2;
     const int64_t o = (int64_t)crow * a.uv_stride + (int64_t)k * B;
     return yuv_s8<DEPTH>(f + a.c_ofs + o) | yuv_s8<DEPTH>(f + a.v_ofs + o) << 16;
 }
 template <int SAMPLING, int DEPTH>
-YUV_HD uint32_t yuv_chroma_at(const YuvChromaArgs& a, const uint8_t* f, int crow, int k) {
+YUV_HD uint32_t yuv_chroma_at(const YuvArgs& a, const uint8_t* f, int crow, int k) {
     return SAMPLING == YUV_S422P || a.interleaved ? yuv_chroma_at_pair<SAMPLING, DEPTH>(a, f, crow, k) : yuv_chroma_at_planar<SAMPLING, DEPTH>(a, f, crow, k);
 }
 
@@ -147,7 +116,7 @@ YUV_HD uint32_t yuv_chroma_at(const YuvChromaArgs& a, const uint8_t* f, int crow
 // returned through y4 when asked for.  `mine`: the calling thread's own load (a host build's neighbour look-up is not counted)
 struct YuvChromaRaw { uint32_t lo, hi; };        // the wide load's dwords (planar: U's, V's); the byte path: lo is the finished dword
 template <int SAMPLING, int DEPTH>
-YUV_HD YuvChromaRaw yuv_chroma_own_load(const YuvChromaArgs& a, const uint8_t* f, int tix, int crow, uint32_t* y4, bool mine) {
+YUV_HD YuvChromaRaw yuv_chroma_own_load(const YuvArgs& a, const uint8_t* f, int tix, int crow, uint32_t* y4, bool mine) {
     constexpr int B = DEPTH == YUV_D8 ? 1 : 2;
     const int x0 = tix * 4, k0 = x0 >> 1;
     const bool full = x0 + 3 < a.w;
@@ -186,7 +155,7 @@ YUV_HD YuvChromaRaw yuv_chroma_own_load(const YuvChromaArgs& a, const uint8_t* f
     return YuvChromaRaw{p0 | p1 << 8, 0u};
 }
 template <int SAMPLING, int DEPTH>
-YUV_HD uint32_t yuv_chroma_own(const YuvChromaArgs& a, int tix, const YuvChromaRaw& raw, uint32_t* y4) {
+YUV_HD uint32_t yuv_chroma_own(const YuvArgs& a, int tix, const YuvChromaRaw& raw, uint32_t* y4) {
     const bool full = tix * 4 + 3 < a.w;
     if (SAMPLING == YUV_S422P) {
         if (!(full && a.wide_y)) return raw.lo;
@@ -202,7 +171,7 @@ YUV_HD uint32_t yuv_chroma_own(const YuvChromaArgs& a, int tix, const YuvChromaR
 // thread row of the block).  Device: two ds_bpermute_b32; a lane past the row's end has left, and its slot reads as nothing anybody
 // uses.  Host: the neighbour's dword, computed directly.  Lane 0's prev and lane 63's next are never used (yuv_chroma_thread).
 template <int SAMPLING, int DEPTH>
-YUV_HD void yuv_chroma_exchange(const YuvChromaArgs& a, const uint8_t* f, int tix, int lane, int crow, uint32_t own, uint32_t* prev, uint32_t* next) {
+YUV_HD void yuv_chroma_exchange(const YuvArgs& a, const uint8_t* f, int tix, int lane, int crow, uint32_t own, uint32_t* prev, uint32_t* next) {
 #if defined(__HIP_DEVICE_COMPILE__)
     (void)a; (void)f; (void)tix; (void)crow;
     *prev = (uint32_t)__builtin_amdgcn_ds_bpermute((lane - 1) << 2, (int)own);
@@ -229,7 +198,7 @@ YUV_HD YuvDC yuv_chroma_terms(uint32_t uv, const YuvCoef& k, const YuvChromaK& c
 // row, then the halo samples of the first and the last lane — so that a wave waits for memory once; then the exchange, the filter
 // and the conversion.
 template <int SAMPLING, int DEPTH>
-YUV_HD void yuv_chroma_thread(const YuvChromaArgs& a, const YuvCoef& k, int tix, int lane, int row, int z) {
+YUV_HD void yuv_chroma_thread(const YuvArgs& a, const YuvChromaW& wt, const YuvCoef& k, int tix, int lane, int row, int z) {
     constexpr int B = DEPTH == YUV_D8 ? 1 : 2;
     constexpr bool S420 = SAMPLING == YUV_S420, PACKED = SAMPLING == YUV_S422P;
     constexpr int NR = S420 ? 2 : 1;                 // luma rows of this thread
@@ -254,7 +223,7 @@ YUV_HD void yuv_chroma_thread(const YuvChromaArgs& a, const YuvCoef& k, int tix,
     }
     // (uniform: kernel arguments) the row above is read only where its weight is nonzero — co-sited vertical siting never reaches it
     const int crow[3] = {row, row > 0 ? row - 1 : 0, row + 1 < chh ? row + 1 : chh - 1};
-    const bool use[3] = {true, S420 && a.wv[0] != 0, S420 && a.wv[3] != 0};
+    const bool use[3] = {true, S420 && wt.wv[0] != 0, S420 && wt.wv[3] != 0};
     YuvChromaRaw raw[NC] = {};
     uint32_t halo[NC] = {};
     for (int i = 0; i < NC; ++i)
@@ -284,9 +253,9 @@ YUV_HD void yuv_chroma_thread(const YuvChromaArgs& a, const YuvCoef& k, int tix,
         else if (lane == YUV_TX - 1) P[3] = halo[i];
         else { P[3] = next & 0x00ff00ffu; YUV_CHROMA_HIT(neighbour); }
         if (!S420) { for (int j = 0; j < 4; ++j) T[0][j] = P[j]; }
-        else if (i == 0) { for (int j = 0; j < 4; ++j) { T[0][j] = yuv_mad2(a.wv[1], P[j], T[0][j]); T[NR - 1][j] = yuv_mad2(a.wv[2], P[j], T[NR - 1][j]); } }
-        else if (i == 1) { for (int j = 0; j < 4; ++j) T[0][j] = yuv_mad2(a.wv[0], P[j], T[0][j]); }
-        else { for (int j = 0; j < 4; ++j) T[NR - 1][j] = yuv_mad2(a.wv[3], P[j], T[NR - 1][j]); }
+        else if (i == 0) { for (int j = 0; j < 4; ++j) { T[0][j] = yuv_mad2(wt.wv[1], P[j], T[0][j]); T[NR - 1][j] = yuv_mad2(wt.wv[2], P[j], T[NR - 1][j]); } }
+        else if (i == 1) { for (int j = 0; j < 4; ++j) T[0][j] = yuv_mad2(wt.wv[0], P[j], T[0][j]); }
+        else { for (int j = 0; j < 4; ++j) T[NR - 1][j] = yuv_mad2(wt.wv[3], P[j], T[NR - 1][j]); }
     }
     const uint32_t rnd = S420 ? 0x00080008u : 0x00020002u;
     constexpr int SH = S420 ? 4 : 2;
@@ -295,10 +264,10 @@ YUV_HD void yuv_chroma_thread(const YuvChromaArgs& a, const YuvCoef& k, int tix,
     for (int r = 0; r < NR; ++r) {
         const uint32_t* V = T[r];
         // columns 0 and 2 have parity 0 (samples k - 1, k), columns 1 and 3 parity 1 (samples k, k + 1)
-        const uint32_t c0 = (yuv_mad2(a.wh[0], V[0], yuv_mad2(a.wh[1], V[1], rnd)) >> SH) & 0x00ff00ffu;
-        const uint32_t c1 = (yuv_mad2(a.wh[2], V[1], yuv_mad2(a.wh[3], V[2], rnd)) >> SH) & 0x00ff00ffu;
-        const uint32_t c2 = (yuv_mad2(a.wh[0], V[1], yuv_mad2(a.wh[1], V[2], rnd)) >> SH) & 0x00ff00ffu;
-        const uint32_t c3 = (yuv_mad2(a.wh[2], V[2], yuv_mad2(a.wh[3], V[3], rnd)) >> SH) & 0x00ff00ffu;
+        const uint32_t c0 = (yuv_mad2(wt.wh[0], V[0], yuv_mad2(wt.wh[1], V[1], rnd)) >> SH) & 0x00ff00ffu;
+        const uint32_t c1 = (yuv_mad2(wt.wh[2], V[1], yuv_mad2(wt.wh[3], V[2], rnd)) >> SH) & 0x00ff00ffu;
+        const uint32_t c2 = (yuv_mad2(wt.wh[0], V[1], yuv_mad2(wt.wh[1], V[2], rnd)) >> SH) & 0x00ff00ffu;
+        const uint32_t c3 = (yuv_mad2(wt.wh[2], V[2], yuv_mad2(wt.wh[3], V[3], rnd)) >> SH) & 0x00ff00ffu;
         const uint32_t p0 = yuv_desc_px(y4[r] & 255, yuv_chroma_terms(c0, k, ck), k);
         const uint32_t p1 = yuv_desc_px((y4[r] >> 8) & 255, yuv_chroma_terms(c1, k, ck), k);
         const uint32_t p2 = yuv_desc_px((y4[r] >> 16) & 255, yuv_chroma_terms(c2, k, ck), k);
@@ -322,8 +291,8 @@ YUV_HD void yuv_chroma_thread(const YuvChromaArgs& a, const YuvCoef& k, int tix,
 #if defined(__HIPCC__)
 // grid (ceil(ceil(w/4) / YUV_TX), ceil(rows / YUV_TY), n) with rows = h / 2 (420) or h (422), block (YUV_TX, YUV_TY)
 template <int SAMPLING, int DEPTH>
-__global__ __launch_bounds__(YUV_TX * YUV_TY) void yuv_chroma_to_bgr_kernel(YuvChromaArgs a, YuvCoef k) {
-    yuv_chroma_thread<SAMPLING, DEPTH>(a, k, blockIdx.x * YUV_TX + threadIdx.x, threadIdx.x, blockIdx.y * YUV_TY + threadIdx.y, blockIdx.z);
+__global__ __launch_bounds__(YUV_TX * YUV_TY) void yuv_chroma_to_bgr_kernel(YuvArgs a, YuvChromaW wt, YuvCoef k) {
+    yuv_chroma_thread<SAMPLING, DEPTH>(a, wt, k, blockIdx.x * YUV_TX + threadIdx.x, threadIdx.x, blockIdx.y * YUV_TY + threadIdx.y, blockIdx.z);
 }
 #endif
 

@@ -5,7 +5,7 @@
 //                                                 byte of sample, 3wh out)
 // Launched iff the sampling is not 4:2:0 (stage_orb.hip launch_yuv420_to_bgr); seven instances: 422 and 444 at three depths, packed
 // at 8 bits.  The arithmetic is yuv420.hip.h's description kernel's by inclusion — coefficients as kernel arguments (SGPRs), products
-// on the 24-bit multipliers, clamp before shift (yuv_sat8 there says why), the 16-bit narrowing of yuv_s8 / yuv_pack4 / yuv_load4 —
+// on the 24-bit multipliers, clamp before shift (yuv_desc_sat8 there says why), the 16-bit narrowing of yuv_s8 / yuv_pack4 / yuv_load4 —
 // and so are its bounds: every operand fits 24 signed bits, every product and sum int32.
 // Thread shape: four consecutive pixels of ONE row (chroma is not shared between rows, so the 2-row thread of the 4:2:0 kernels
 // buys nothing); block YUV_TX x YUV_TY = 64 threads along a row x 4 rows.  12 bytes out as three dwords where the destination is
@@ -23,63 +23,23 @@
 //                            4-aligned; luma and chroma bytes out of the macropixels by v_perm_b32, the selectors from the host
 // The per-thread body is a host + device function: tools/yuv_sampling_hostcheck.cpp runs it lane by lane on the CPU.
 #pragma once
-#include <algorithm>
-
 #include "slideo_amd.h"
 #include "yuv420.hip.h"
 
 namespace slideo {
 
-constexpr int YUV_S422 = 1, YUV_S444 = 2, YUV_S422P = 3;          // = SLIDEO_YUV_SAMPLING_* (420 has its own kernels)
-
-struct YuvSampArgs {
-    const uint8_t* src;
-    int64_t src_frame_stride;    // all strides and offsets in BYTES, whatever the container
-    int64_t c_ofs;               // interleaved: the first byte of the chroma plane (min of u_offset, v_offset); planar: u_offset
-    int64_t v_ofs;               // planar: v_offset
-    int y_stride, uv_stride;
-    int interleaved, v_first;
-    uint8_t* dst;                // BGR8, row stride 3w, frame stride 3wh
-    int w, h;
-    int wide_y;                  // planar luma: 1 = a thread's 4 samples are one aligned load; packed: 8 / 4 = its 8 bytes are one / two
-    int wide_c;                  // chroma: nonzero = the wide load of the table above applies; 444 interleaved: 8 / 4, the load's size
-    int out4;                    // dword stores: dst dword-aligned and w % 4 == 0
-    uint32_t sel_y, sel_c;       // packed: v_perm selectors of Y0 Y1 Y2 Y3 and of U0 U1 V0 V1 out of a thread's 8 bytes
-};
-
-// the largest of 8, 4, 2, 1 that divides the address of a plane's every row in every frame
-inline int yuv_plane_align(const uint8_t* src, int64_t ofs, int64_t frame_stride, int stride) {
-    const uint64_t v = ((uint64_t)(uintptr_t)src + (uint64_t)ofs) | (uint64_t)frame_stride | (uint64_t)(int64_t)stride;
-    return v % 8 == 0 ? 8 : v % 4 == 0 ? 4 : v % 2 == 0 ? 2 : 1;
-}
-
-// The kernel's arguments for n frames in a layout yuv420_validate accepted under (sampling, depth): which wide loads and stores
-// the addresses allow.  A single frame has no stride to be aligned.
-inline YuvSampArgs yuv_sampled_args(int sampling, int depth, const uint8_t* src, int64_t src_fs, const slideo_yuv420_layout& L, int w, int h, int n,
-                                    uint8_t* dst) {
-    YuvSampArgs a{};
-    a.src = src; a.src_frame_stride = src_fs;
-    a.y_stride = L.y_stride; a.uv_stride = L.uv_stride;
-    a.dst = dst; a.w = w; a.h = h;
-    a.out4 = (uintptr_t)dst % 4 == 0 && w % 4 == 0;
-    const int64_t fs = n > 1 ? src_fs : 0;
+// The kernel's arguments for n frames in a layout yuv420_validate accepted under (sampling, depth): yuv_args' record with this
+// family's wide_y and wide_c, by the table above
+inline YuvArgs yuv_sampled_args(int sampling, int depth, const uint8_t* src, int64_t src_fs, const slideo_yuv420_layout& L, int w, int h, int n,
+                                uint8_t* dst) {
+    int ay, ac;
+    YuvArgs a = yuv_args(sampling, src, src_fs, L, w, h, n, dst, &ay, &ac);
     const int B = depth == SLIDEO_YUV_DEPTH_8 ? 1 : 2;
-    const int ay = yuv_plane_align(src, 0, fs, L.y_stride);
-    if (sampling == SLIDEO_YUV_SAMPLING_422_PACKED) {
-        const uint32_t ly = (uint32_t)((L.u_offset & 1) ^ 1), uo = (uint32_t)L.u_offset, vo = (uint32_t)L.v_offset;
-        a.sel_y = ly | (ly + 2) << 8 | (ly + 4) << 16 | (ly + 6) << 24;
-        a.sel_c = uo | (uo + 4) << 8 | vo << 16 | (vo + 4) << 24;
-        a.wide_y = ay >= 8 ? 8 : ay >= 4 ? 4 : 0;
-        return a;
-    }
-    a.interleaved = L.uv_step == 2;
-    a.v_first = a.interleaved && L.v_offset < L.u_offset;
-    a.c_ofs = a.interleaved ? std::min(L.u_offset, L.v_offset) : L.u_offset;
-    a.v_ofs = L.v_offset;
+    // wide_y: planar luma, 1 = a thread's 4 samples are one aligned load; packed, 8 / 4 = its 8 bytes are one / two.  wide_c: nonzero
+    // = the wide load applies; 444 interleaved: 8 / 4, the load's size
+    if (sampling == SLIDEO_YUV_SAMPLING_422_PACKED) { a.wide_y = yuv_load_mode(ay); return a; }
     a.wide_y = ay >= 4 * B;
-    const int au = yuv_plane_align(src, a.c_ofs, fs, L.uv_stride);
-    const int ac = a.interleaved ? au : std::min(au, yuv_plane_align(src, a.v_ofs, fs, L.uv_stride));
-    if (sampling == SLIDEO_YUV_SAMPLING_444) a.wide_c = a.interleaved ? (ac >= 8 ? 8 : ac >= 4 ? 4 : 0) : ac >= 4 * B;
+    if (sampling == SLIDEO_YUV_SAMPLING_444) a.wide_c = a.interleaved ? yuv_load_mode(ac) : ac >= 4 * B;
     else a.wide_c = ac >= (a.interleaved ? 4 * B : 2 * B);
     return a;
 }
@@ -97,7 +57,7 @@ YUV_HD uint32_t yuv_ld16(const uint8_t* p) { return *reinterpret_cast<const uint
 
 // One thread of the launch grid: columns 4 tix .. 4 tix + 3 of row `row` of frame z.
 template <int SAMPLING, int DEPTH>
-YUV_HD void yuv_sampled_thread(const YuvSampArgs& a, const YuvCoef& k, int tix, int row, int z) {
+YUV_HD void yuv_sampled_thread(const YuvArgs& a, const YuvCoef& k, int tix, int row, int z) {
     constexpr int B = DEPTH == YUV_D8 ? 1 : 2;
     constexpr bool S444 = SAMPLING == YUV_S444;
     const int x0 = tix * 4;
@@ -196,7 +156,7 @@ YUV_HD void yuv_sampled_thread(const YuvSampArgs& a, const YuvCoef& k, int tix, 
 #if defined(__HIPCC__)
 // grid (ceil(ceil(w/4) / YUV_TX), ceil(h / YUV_TY), n), block (YUV_TX, YUV_TY)
 template <int SAMPLING, int DEPTH>
-__global__ __launch_bounds__(YUV_TX * YUV_TY) void yuv_sampled_to_bgr_kernel(YuvSampArgs a, YuvCoef k) {
+__global__ __launch_bounds__(YUV_TX * YUV_TY) void yuv_sampled_to_bgr_kernel(YuvArgs a, YuvCoef k) {
     yuv_sampled_thread<SAMPLING, DEPTH>(a, k, blockIdx.x * YUV_TX + threadIdx.x, blockIdx.y * YUV_TY + threadIdx.y, blockIdx.z);
 }
 #endif

@@ -7,14 +7,14 @@
 // depths.  Per pixel, in exact integers (the header's steps 1-5): the samples at their full 10 bits, the BT.2020 matrix at SHIFT 18
 // (coefficients and the gamut's nine integers as kernel arguments, SGPRs; every operand fits 24 signed bits, every product and sum
 // int32: 959 * 306134 = 2.94e8, 512 * 563104 = 2.88e8, their sum + 2^17 = 5.82e8; 27206 * 16383 = 4.46e8), clamp BEFORE the shift
-// (yuv420.hip.h yuv_sat8 says why), three reads of LIN (uint16 [1024]), nine 24-bit multiplies, three reads of OUT (uint8 [4096]).
+// (yuv420.hip.h yuv_desc_sat8 says why), three reads of LIN (uint16 [1024]), nine 24-bit multiplies, three reads of OUT (uint8 [4096]).
 // Both tables live in LDS: the matcher's device copy (LIN then OUT, 6144 bytes = 1536 dwords) is loaded once per block with
 // cooperative 16-byte loads and one barrier BEFORE any thread leaves, so every thread of the block reaches the barrier; a block then
 // converts YUV_TRK_ROWS thread rows one after the other.  Neighbouring lanes of a slide mostly read the same entries, which the LDS
 // broadcasts.
 // Thread shapes, loads and stores are the nearest kernels': 2 rows x 4 columns under 4:2:0 (yuv420.hip.h), four pixels of one row
 // under 4:2:2 and 4:4:4 (yuv_sampling.hip.h); block YUV_TX x YUV_TY, YUV_TRK_ROWS times.  Loads, each plane's path chosen by the
-// host from the addresses (yuv_transfer_args, yuv_plane_align): 8 = 8-byte loads, 4 = dword loads kept apart (yuv_apart), 0 = sample
+// host from the addresses (yuv_transfer_args over yuv420.hip.h's yuv_args): 8 = 8-byte loads, 4 = dword loads kept apart (yuv_apart), 0 = sample
 // by sample with byte loads — so are the ragged last columns of a row.  No multi-dword load is ever issued at an address that is
 // not a multiple of its size.
 //   luma                          4 containers, 8 bytes
@@ -27,8 +27,6 @@
 // The per-thread body is a host + device function: tools/yuv_transfer_hostcheck.cpp runs it lane by lane on the CPU, the tables a
 // plain array argument.
 #pragma once
-#include <algorithm>
-
 #include "slideo_amd.h"
 #include "yuv_sampling.hip.h"
 
@@ -38,44 +36,19 @@
 
 namespace slideo {
 
-constexpr int YUV_T420 = 0;                                       // = SLIDEO_YUV_SAMPLING_420 (422, 444: yuv_sampling.hip.h)
 constexpr int YUV_TRK_SHIFT = 18, YUV_TRK_HALF = 1 << (YUV_TRK_SHIFT - 1);
 constexpr int YUV_TRK_LIN_BYTES = 2048, YUV_TRK_OUT_BYTES = 4096, YUV_TRK_DWORDS = (YUV_TRK_LIN_BYTES + YUV_TRK_OUT_BYTES) / 4;
-
-struct YuvTransferArgs {
-    const uint8_t* src;
-    int64_t src_frame_stride;    // all strides and offsets in BYTES
-    int64_t c_ofs;               // interleaved: the first byte of the chroma plane (min of u_offset, v_offset); planar: u_offset
-    int64_t v_ofs;               // planar: v_offset
-    int y_stride, uv_stride;
-    int interleaved, v_first;
-    uint8_t* dst;                // BGR8, row stride 3w, frame stride 3wh
-    int w, h;
-    int wide_y;                  // luma: 8 / 4 / 0, the load mode of the table above
-    int wide_c;                  // chroma likewise (planar: the lesser of the two planes')
-    int out4;                    // dword stores: dst dword-aligned and w % 4 == 0
-};
 
 // step 2's integers and step 4's, as the kernel takes them
 struct YuvTransferCoef { int cy, cub, cug, cvg, cvr, yofs; int g[9]; };
 
-// The kernel's arguments for n frames in a layout yuv420_validate accepted under (sampling, a 10-bit depth): which loads and stores
-// the addresses allow.  A single frame has no stride to be aligned.
-inline YuvTransferArgs yuv_transfer_args(const uint8_t* src, int64_t src_fs, const slideo_yuv420_layout& L, int w, int h, int n, uint8_t* dst) {
-    YuvTransferArgs a{};
-    a.src = src; a.src_frame_stride = src_fs;
-    a.y_stride = L.y_stride; a.uv_stride = L.uv_stride;
-    a.dst = dst; a.w = w; a.h = h;
-    a.out4 = (uintptr_t)dst % 4 == 0 && w % 4 == 0;
-    const int64_t fs = n > 1 ? src_fs : 0;
-    a.interleaved = L.uv_step == 2;
-    a.v_first = a.interleaved && L.v_offset < L.u_offset;
-    a.c_ofs = a.interleaved ? std::min(L.u_offset, L.v_offset) : L.u_offset;
-    a.v_ofs = L.v_offset;
-    auto mode = [](int al) { return al >= 8 ? 8 : al >= 4 ? 4 : 0; };
-    a.wide_y = mode(yuv_plane_align(src, 0, fs, L.y_stride));
-    const int au = yuv_plane_align(src, a.c_ofs, fs, L.uv_stride);
-    a.wide_c = mode(a.interleaved ? au : std::min(au, yuv_plane_align(src, a.v_ofs, fs, L.uv_stride)));
+// The kernel's arguments for n frames in a layout yuv420_validate accepted under (sampling, a 10-bit depth): yuv_args' record with
+// this family's wide_y and wide_c, each 8 / 4 / 0: the load mode of the table above
+inline YuvArgs yuv_transfer_args(int sampling, const uint8_t* src, int64_t src_fs, const slideo_yuv420_layout& L, int w, int h, int n, uint8_t* dst) {
+    int ay, ac;
+    YuvArgs a = yuv_args(sampling, src, src_fs, L, w, h, n, dst, &ay, &ac);
+    a.wide_y = yuv_load_mode(ay);
+    a.wide_c = yuv_load_mode(ac);
     return a;
 }
 
@@ -129,8 +102,8 @@ YUV_HD uint32_t yuv_transfer_px(int Y10, const YuvDC& c, const YuvTransferCoef& 
 // One thread of the launch grid: columns 4 tix .. 4 tix + 3 of luma rows 2 row and 2 row + 1 (420) or of luma row `row` (422, 444)
 // of frame z.  lin, out: the two tables (device: LDS)
 template <int SAMPLING, int DEPTH>
-YUV_HD void yuv_transfer_thread(const YuvTransferArgs& a, const YuvTransferCoef& k, const uint16_t* lin, const uint8_t* out, int tix, int row, int z) {
-    constexpr bool S420 = SAMPLING == YUV_T420, S444 = SAMPLING == YUV_S444;
+YUV_HD void yuv_transfer_thread(const YuvArgs& a, const YuvTransferCoef& k, const uint16_t* lin, const uint8_t* out, int tix, int row, int z) {
+    constexpr bool S420 = SAMPLING == YUV_S420, S444 = SAMPLING == YUV_S444;
     constexpr int NR = S420 ? 2 : 1;                 // luma rows of this thread
     constexpr int NCS = S444 ? 4 : 2;                // chroma samples of a full thread, per plane
     const int x0 = tix * 4, r0 = S420 ? 2 * row : row;
@@ -221,7 +194,7 @@ constexpr int YUV_TRK_ROWS = 4;
 // grid (ceil(ceil(w/4) / YUV_TX), ceil(rows / (YUV_TY * YUV_TRK_ROWS)), n) with rows = h / 2 (420) or h (422, 444), block (YUV_TX,
 // YUV_TY).  tab: LIN uint16 [1024] then OUT uint8 [4096], 16-byte aligned (the matcher's d_transfer): 384 16-byte loads a block
 template <int SAMPLING, int DEPTH>
-__global__ __launch_bounds__(YUV_TX * YUV_TY) void yuv_transfer_to_bgr_kernel(YuvTransferArgs a, YuvTransferCoef k, const uint4* __restrict__ tab) {
+__global__ __launch_bounds__(YUV_TX * YUV_TY) void yuv_transfer_to_bgr_kernel(YuvArgs a, YuvTransferCoef k, const uint4* __restrict__ tab) {
     __shared__ uint4 lds[YUV_TRK_DWORDS / 4];
     for (int i = threadIdx.y * YUV_TX + threadIdx.x; i < YUV_TRK_DWORDS / 4; i += YUV_TX * YUV_TY) lds[i] = tab[i];
     __syncthreads();                                 // (before any thread returns: yuv_transfer_thread's first line may)

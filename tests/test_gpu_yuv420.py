@@ -63,6 +63,38 @@ def test_conversion_tap_bit_exact(capi, tap, w, h, pitched):
         assert np.array_equal(got, want), (fmt, w, h, pitched, np.argwhere(got != want)[:4])
 
 
+@pytest.mark.parametrize("w,h", [(6, 4), (18, 10)])
+@pytest.mark.parametrize("fmt", ["nv12", "i420"])
+def test_batch_of_two_with_a_frame_stride_of_2_mod_4(capi, tap, fmt, w, h):
+    """Two device frames in the decoder-pitched layout, whose rows allow every wide load of the 4:2:0 kernel, read in place at a
+    frame stride of fb (the wide loads) and of fb + 2 (2 mod 4: the host takes the wide loads away, and the second frame's rows
+    start where no dword load may).  No call returns the converted pixels of a batch; the activity accumulator
+    (tests/activity_ref.py) counts the pixels that differ between consecutive converted frames.  The same frame twice: none
+    differs, so frame 1 is converted as frame 0 is, which the tap holds to the restatement.  Two different frames: the counts of the
+    restatement's two images.  Which flags the host chose at such a stride is tests/test_yuv_args_golden.py's to pin ("pitched+2")."""
+    import torch
+    import activity_ref as A
+    L, fb = _pitched(capi, fmt, w, h)
+    assert fb % 8 == 0 and L.y_stride % 8 == 0 and L.uv_stride % 4 == 0
+    rng = np.random.default_rng(w * 131 + h + len(fmt))
+    f0, f1 = rng.integers(0, 256, fb, dtype=np.uint8), rng.integers(0, 256, fb, dtype=np.uint8)
+    want0, want1 = ref.to_bgr(f0, w, h, L), ref.to_bgr(f1, w, h, L)
+    assert np.array_equal(tap.yuv420_to_bgr(f0, w, h, L), want0)
+    for fs in (fb, fb + 2):
+        for delta, second, want_second in ((0, f0, want0), (255, f1, want1)):
+            buf = rng.integers(0, 256, 2 * fs, dtype=np.uint8)       # (the bytes between and behind the frames are noise)
+            buf[:fb], buf[fs:fs + fb] = f0, second
+            d = torch.from_numpy(buf).cuda()
+            assert d.data_ptr() % 8 == 0
+            tap.activity_begin(delta)
+            tap.observe_frames_yuv420_dev(d.data_ptr(), 2, w, h, L, fs)
+            got = tap.activity_counts()
+            tap.activity_end()
+            want = A.counts(np.stack([want0, want_second]), delta)
+            assert got[1] == want[1] == 1 and np.array_equal(got[0], want[0]), (fmt, w, h, fs, delta, np.argwhere(got[0] != want[0])[:4])
+        assert not want[0].all() and want[0].any()       # (delta 255 splits random frames: a wrong second frame would show)
+
+
 @pytest.mark.parametrize("fmt", ["nv12", "i420"])
 def test_match_frames_equal_bgr_and_oracle(capi, oracle, cfg0_data, fmt):
     from test_gpu_parity import _build_both, _compare_traces

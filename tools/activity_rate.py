@@ -12,7 +12,7 @@ min / median / max:
                                   [--amplitudes 10,40,80] [--rate-only] [--kernels-only]
 
 Prints one line per measurement and a JSON line at the end.  --kernels-only: for a rocprofv3 --kernel-trace --stats run of its own —
-128 device-resident 1080p frames observed as BGR (activity_kernel alone), as NV12 (yuv420_to_bgr_kernel in front) and 128 4K frames
+128 device-resident 1080p frames observed as BGR (activity_kernel alone), as NV12 (yuv420_to_bgr_desc_kernel in front) and 128 4K frames
 under a 1920x1080 working size (reduce2x2_kernel in front), three times each and nothing else."""
 import argparse
 import json

@@ -11,7 +11,7 @@ ORB-1000) on a lecture-like sequence: holds of identical frames whose lengths ar
     python tools/changed_gate_rate.py [--share 0.1] [--frames 256] [--reps 3] [--kernels-only]
 
 Prints one line per measurement and a JSON line at the end.  --kernels-only: (c) alone, twice, for a
-rocprofv3 --kernel-trace --stats run of its own (gate_kernel, gather_frames_kernel beside yuv420_to_bgr_kernel).
+rocprofv3 --kernel-trace --stats run of its own (gate_kernel, gather_frames_kernel beside yuv420_to_bgr_desc_kernel).
 
 --devices 0,1,2 | 0,0 | all: the N-device group over these HIP ordinals instead (an ordinal may repeat: members then share a
 device, which measures the mechanism and not scaling; all = every gfx950 device of the node).  Pinned BGR and NV12 host frames in

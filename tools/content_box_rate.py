@@ -15,7 +15,7 @@ min / median / max:
 
 Prints one line per measurement and a JSON line at the end.  --kernels-only: for a rocprofv3 --kernel-trace --stats run of its own —
 128 device-resident 1080p frames observed as BGR with an activity session only, a content session only and both (activity_kernel and
-content_kernel on the same frames), as NV12 with both open (yuv420_to_bgr_kernel in front) and 128 4K frames under a 1920x1080
+content_kernel on the same frames), as NV12 with both open (yuv420_to_bgr_desc_kernel in front) and 128 4K frames under a 1920x1080
 working size with both open (reduce2x2_kernel in front), three times each, then the box read out three times (content_fill_kernel),
 and nothing else."""
 import argparse

@@ -20,13 +20,26 @@ for st in stage_orb stage_knn stage_verify stage_sift stage_page_set stage_gate 
         # per kernel: the text of each symbol without its address (a unit that gained kernels differs as a whole; the kernels both
         # builds have must still be the same code)
         python3 - $tmp/a.s $tmp/b.s > $tmp/per.txt <<'PY'
-import hashlib, re, sys
+import hashlib, re, subprocess, sys
+def names(path):                                # every symbol of a listing, demangled in one c++filt run
+    found = [m.group(1) for m in (re.match(r'^[0-9a-f]+ <(.+)>:', l) for l in open(path)) if m]
+    out = subprocess.run(['c++filt'], input='\n'.join(found), capture_output=True, text=True).stdout.split('\n')
+    return dict(zip(found, out))
+def key(d):                                     # kernel name and template arguments without the trailing parameter list, so that a
+    if not d.endswith(')'): return d            # kernel whose argument record was renamed pairs up; nothing else of the name goes
+    depth = 0
+    for i in range(len(d) - 1, -1, -1):
+        depth += (d[i] == ')') - (d[i] == '(')
+        if depth == 0: return re.sub(r'^void ', '', d[:i])
+    return d
 def syms(path):
-    out, cur = {}, None
+    out, cur, dem = {}, None, names(path)
     for line in open(path):
         m = re.match(r'^[0-9a-f]+ <(.+)>:', line)
         if m:
-            cur = m.group(1); out[cur] = []
+            cur = key(dem[m.group(1)])
+            if cur in out: cur = m.group(1)     # (two symbols of one key, overloads: keep both, under their mangled names)
+            out[cur] = []
         elif cur is not None and line.strip():
             out[cur].append(re.sub(r'\s+', ' ', line.strip()))
     for v in out.values():                      # (the alignment padding behind a kernel depends on what follows it)

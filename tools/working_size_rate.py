@@ -9,7 +9,7 @@ and the share of frames assigned to the synthetic truth in (a), (b), (c).
     python tools/working_size_rate.py [--reps 3] [--frames 64] [--kernels-only]
 
 Prints one line per measurement and a JSON line at the end.  --kernels-only: one call per reduce kernel and one 4K NV12 call (a
-short run to trace reduce*_kernel beside yuv420_to_bgr_kernel under rocprofv3 --kernel-trace --stats; a launch covers --frames
+short run to trace reduce*_kernel beside yuv420_to_bgr_desc_kernel under rocprofv3 --kernel-trace --stats; a launch covers --frames
 frames)."""
 import argparse
 import json
@@ -73,7 +73,7 @@ def main():
             dev(dq.data_ptr(), 2560, 1440, WS)                                   # reduce_area_kernel (4/3)
             dev(d3.data_ptr(), 2880, 1620, (960, 540))                           # reduce_int_kernel (factor 3)
             m.set_working_size(*WS)
-            m.match_frames_yuv420_dev(dnv.data_ptr(), nh, 3840, 2160, L, fb)     # yuv420_to_bgr_kernel at 4K, then reduce2x2_kernel
+            m.match_frames_yuv420_dev(dnv.data_ptr(), nh, 3840, 2160, L, fb)     # yuv420_to_bgr_desc_kernel at 4K, then reduce2x2_kernel
         m.close()
         return
 

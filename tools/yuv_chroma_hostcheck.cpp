@@ -35,21 +35,21 @@ using namespace slideo;
 namespace {
 
 template <int SAMPLING, int DEPTH>
-void run_grid(const YuvChromaArgs& a, const YuvCoef& k, int n) {
+void run_grid(const YuvArgs& a, const YuvChromaW& cw, const YuvCoef& k, int n) {
     const int rows = SAMPLING == YUV_S420 ? a.h / 2 : a.h;
     const int gx = ((a.w + 3) / 4 + YUV_TX - 1) / YUV_TX, gy = (rows + YUV_TY - 1) / YUV_TY;
     for (int z = 0; z < n; ++z)
         for (int by = 0; by < gy; ++by)
             for (int bx = 0; bx < gx; ++bx)
                 for (int ty = 0; ty < YUV_TY; ++ty)
-                    for (int tx = 0; tx < YUV_TX; ++tx) yuv_chroma_thread<SAMPLING, DEPTH>(a, k, bx * YUV_TX + tx, tx, by * YUV_TY + ty, z);
+                    for (int tx = 0; tx < YUV_TX; ++tx) yuv_chroma_thread<SAMPLING, DEPTH>(a, cw, k, bx * YUV_TX + tx, tx, by * YUV_TY + ty, z);
 }
 
 template <int SAMPLING>
-void run_depth(int depth, const YuvChromaArgs& a, const YuvCoef& k, int n) {
-    if (depth == SLIDEO_YUV_DEPTH_8) run_grid<SAMPLING, YUV_D8>(a, k, n);
-    else if (depth == SLIDEO_YUV_DEPTH_10_MSB) run_grid<SAMPLING, YUV_D10_MSB>(a, k, n);
-    else run_grid<SAMPLING, YUV_D10_LSB>(a, k, n);
+void run_depth(int depth, const YuvArgs& a, const YuvChromaW& cw, const YuvCoef& k, int n) {
+    if (depth == SLIDEO_YUV_DEPTH_8) run_grid<SAMPLING, YUV_D8>(a, cw, k, n);
+    else if (depth == SLIDEO_YUV_DEPTH_10_MSB) run_grid<SAMPLING, YUV_D10_MSB>(a, cw, k, n);
+    else run_grid<SAMPLING, YUV_D10_LSB>(a, cw, k, n);
 }
 
 int convert(const char* in, const char* outp) {
@@ -93,11 +93,12 @@ int convert(const char* in, const char* outp) {
             if (!exact || !dst || (uintptr_t)exact % 16 != 0) return 2;
             std::memcpy(exact + OFS[o], frames.data(), total);
             std::memset(dst, 0xA5, ob);
-            YuvChromaArgs a;
-            if (!yuv_chroma_args(sampling, depth, w12, exact + OFS[o], fs, L, w, h, n, dst, &a)) return 3;
-            if (sampling == SLIDEO_YUV_SAMPLING_422_PACKED) run_grid<YUV_S422P, YUV_D8>(a, k, n);
-            else if (sampling == SLIDEO_YUV_SAMPLING_422) run_depth<YUV_S422>(depth, a, k, n);
-            else run_depth<YUV_S420>(depth, a, k, n);
+            YuvArgs a;
+            YuvChromaW cw;
+            if (!yuv_chroma_args(sampling, depth, w12, exact + OFS[o], fs, L, w, h, n, dst, &a, &cw)) return 3;
+            if (sampling == SLIDEO_YUV_SAMPLING_422_PACKED) run_grid<YUV_S422P, YUV_D8>(a, cw, k, n);
+            else if (sampling == SLIDEO_YUV_SAMPLING_422) run_depth<YUV_S422>(depth, a, cw, k, n);
+            else run_depth<YUV_S420>(depth, a, cw, k, n);
             if (o == 0) first.assign(dst, dst + ob);
             else if (std::memcmp(first.data(), dst, ob) != 0) {
                 std::fprintf(stderr, "record %ld: the image at source offset %d differs from the one at offset 0\n", records, OFS[o]);

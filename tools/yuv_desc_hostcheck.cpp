@@ -22,27 +22,8 @@ using namespace slideo;
 
 namespace {
 
-// stage_orb.hip yuv_desc_args, for a host allocation
-YuvDescArgs args_for(int depth, const uint8_t* src, int64_t fs, const slideo_yuv420_layout& L, int w, int h, uint8_t* dst) {
-    YuvDescArgs a{};
-    a.src = src; a.src_frame_stride = fs;
-    a.interleaved = L.uv_step == 2;
-    a.v_first = a.interleaved && L.v_offset < L.u_offset;
-    a.c_ofs = a.interleaved ? std::min(L.u_offset, L.v_offset) : L.u_offset;
-    a.v_ofs = L.v_offset;
-    a.y_stride = L.y_stride; a.uv_stride = L.uv_stride;
-    a.dst = dst; a.w = w; a.h = h;
-    const bool wide = depth != SLIDEO_YUV_DEPTH_8;
-    const uintptr_t ay = wide ? 8 : 4, ac = wide || a.interleaved ? 4 : 2, base = (uintptr_t)src;
-    auto aligned = [&](int64_t ofs, int stride, uintptr_t al) { return (base + (uintptr_t)ofs) % al == 0 && (uintptr_t)fs % al == 0 && (uintptr_t)stride % al == 0; };
-    a.wide_y = aligned(0, L.y_stride, ay);
-    a.wide_c = aligned(a.c_ofs, L.uv_stride, ac) && (a.interleaved || aligned(a.v_ofs, L.uv_stride, ac));
-    a.out4 = (uintptr_t)dst % 4 == 0 && w % 4 == 0;
-    return a;
-}
-
 template <int DEPTH>
-void run_grid(const YuvDescArgs& a, const YuvCoef& k, int n) {
+void run_grid(const YuvArgs& a, const YuvCoef& k, int n) {
     const int gx = ((a.w + 3) / 4 + YUV_TX - 1) / YUV_TX, gy = (a.h / 2 + YUV_TY - 1) / YUV_TY;
     for (int z = 0; z < n; ++z)
         for (int by = 0; by < gy; ++by)
@@ -77,7 +58,7 @@ int convert(const char* in, const char* outp) {
     int32_t c[7];
     yuv_coefficients(matrix, range, c);
     const YuvCoef k{c[0], c[1], c[2], c[3], c[4], c[5]};
-    const YuvDescArgs a = args_for(depth, src, fs, L, w, h, dst);
+    const YuvArgs a = yuv_desc_args(depth, src, fs, L, w, h, n, dst);
     if (depth == SLIDEO_YUV_DEPTH_8) run_grid<YUV_D8>(a, k, n);
     else if (depth == SLIDEO_YUV_DEPTH_10_MSB) run_grid<YUV_D10_MSB>(a, k, n);
     else run_grid<YUV_D10_LSB>(a, k, n);

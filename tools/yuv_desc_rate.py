@@ -1,9 +1,11 @@
 """Cost and use of the YUV colour description (include/slideo_amd.h "YUV colour description").  One process per mode:
 
   --kernels   128 1080p frames through the mask call (conversion + small images, no pages needed), three times under each of: the
-              default (yuv420_to_bgr_kernel), (bt709, limited, 8), (bt709, limited, 10_msb: P010) and (bt709, limited, 10_lsb).  Run
-              it under a profiler's kernel trace with statistics, in a run of its own: the yuv420_to_bgr* rows are the time per 128
-              frames of each kernel.  It prints nothing but the wall times.
+              default and (bt709, limited, 8) over three 8-bit layouts (NV12 tight, I420 tight, NV12 with a luma pitch of 2 mod 4,
+              where no dword luma load applies), then (bt709, limited, 10_msb: P010) and (bt709, limited, 10_lsb).  Run it under a
+              profiler's kernel trace with statistics, in a run of its own: the yuv420_to_bgr* rows are the time per 128 frames of
+              each launch (one kernel converts all of them; a library that still has yuv420_to_bgr_kernel, named by
+              SLIDEO_LIB_PATH, runs that one under the default).  It prints nothing but the wall times.
   --rates     host-fed match calls from PINNED memory, --frames 1080p frames against --pages pages, ORB-1000: NV12 8-bit under the
               default against P010 under (bt709, limited, 10_msb), alternated, min / median / max.  --nv12-only: the first alone,
               through no call an older library lacks (SLIDEO_LIB_PATH: the parent commit's build, interleaved process by process).
@@ -93,14 +95,19 @@ def kernels(a):
     y8 = rng.integers(0, 256, (n, W * H * 3 // 2), dtype=np.uint8)
     y16 = (rng.integers(0, 1024, (n, W * H * 3 // 2), dtype=np.uint16))
     L8 = _capi.yuv420_layout("nv12", W, H)[0]
+    Li = _capi.yuv420_layout("i420", W, H)[0]
+    Lp, fbp = _capi.yuv420_layout("nv12", W, H, pitch=W + 2, row_align=2)       # luma pitch = 2 mod 4: no dword luma loads
+    yp = rng.integers(0, 256, (n, fbp), dtype=np.uint8)
     L16 = _capi.yuv420_layout("nv12", W, H, bytes_per_sample=2)[0]
-    for desc, buf, L in ((("bt601", "limited", 8), y8, L8), (("bt709", "limited", 8), y8, L8), (("bt709", "limited", "10_msb"), y16 << 6, L16),
-                         (("bt709", "limited", "10_lsb"), y16, L16)):
+    for desc, name, buf, L in ((("bt601", "limited", 8), "nv12", y8, L8), (("bt709", "limited", 8), "nv12", y8, L8),
+                               (("bt601", "limited", 8), "i420", y8, Li), (("bt709", "limited", 8), "i420", y8, Li),
+                               (("bt601", "limited", 8), "nv12 pitch %d" % (W + 2), yp, Lp), (("bt709", "limited", 8), "nv12 pitch %d" % (W + 2), yp, Lp),
+                               (("bt709", "limited", "10_msb"), "p010", y16 << 6, L16), (("bt709", "limited", "10_lsb"), "nv12 16-bit", y16, L16)):
         m.set_yuv_description(*desc)
         for _ in range(3):
             t0 = time.perf_counter()
             m.changed_mask_yuv420(buf, W, H, L)
-            print("kernels: %-28s mask call of %d frames %.1f ms" % (desc, n, (time.perf_counter() - t0) * 1e3), flush=True)
+            print("kernels: %-28s %-16s mask call of %d frames %.1f ms" % (desc, name, n, (time.perf_counter() - t0) * 1e3), flush=True)
     m.close()
 
 

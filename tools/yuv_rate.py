@@ -4,7 +4,7 @@ the host entry point (pageable and pinned sources) for BGR and NV12, and the dev
     python tools/yuv_rate.py [--reps 3] [--device-only]
 
 Prints one line per measurement and a JSON line at the end.  --device-only skips the host calls (a short run to trace
-yuv420_to_bgr_kernel under rocprofv3 --kernel-trace --stats)."""
+yuv420_to_bgr_desc_kernel under rocprofv3 --kernel-trace --stats)."""
 import argparse
 import json
 import os

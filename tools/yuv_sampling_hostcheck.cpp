@@ -25,7 +25,7 @@ using namespace slideo;
 namespace {
 
 template <int SAMPLING, int DEPTH>
-void run_grid(const YuvSampArgs& a, const YuvCoef& k, int n) {
+void run_grid(const YuvArgs& a, const YuvCoef& k, int n) {
     const int gx = ((a.w + 3) / 4 + YUV_TX - 1) / YUV_TX, gy = (a.h + YUV_TY - 1) / YUV_TY;
     for (int z = 0; z < n; ++z)
         for (int by = 0; by < gy; ++by)
@@ -35,7 +35,7 @@ void run_grid(const YuvSampArgs& a, const YuvCoef& k, int n) {
 }
 
 template <int SAMPLING>
-void run_depth(int depth, const YuvSampArgs& a, const YuvCoef& k, int n) {
+void run_depth(int depth, const YuvArgs& a, const YuvCoef& k, int n) {
     if (depth == SLIDEO_YUV_DEPTH_8) run_grid<SAMPLING, YUV_D8>(a, k, n);
     else if (depth == SLIDEO_YUV_DEPTH_10_MSB) run_grid<SAMPLING, YUV_D10_MSB>(a, k, n);
     else run_grid<SAMPLING, YUV_D10_LSB>(a, k, n);
@@ -71,7 +71,7 @@ int convert(const char* in, const char* outp) {
     int32_t c[7];
     yuv_coefficients(matrix, range, c);
     const YuvCoef k{c[0], c[1], c[2], c[3], c[4], c[5]};
-    const YuvSampArgs a = yuv_sampled_args(sampling, depth, src, fs, L, w, h, n, dst);
+    const YuvArgs a = yuv_sampled_args(sampling, depth, src, fs, L, w, h, n, dst);
     if (sampling == SLIDEO_YUV_SAMPLING_422_PACKED) run_grid<YUV_S422P, YUV_D8>(a, k, n);
     else if (sampling == SLIDEO_YUV_SAMPLING_422) run_depth<YUV_S422>(depth, a, k, n);
     else run_depth<YUV_S444>(depth, a, k, n);

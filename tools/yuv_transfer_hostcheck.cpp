@@ -36,8 +36,8 @@ using namespace slideo;
 namespace {
 
 template <int SAMPLING, int DEPTH>
-void run_grid(const YuvTransferArgs& a, const YuvTransferCoef& k, const uint16_t* lin, const uint8_t* out, int n) {
-    const int rows = SAMPLING == YUV_T420 ? a.h / 2 : a.h;
+void run_grid(const YuvArgs& a, const YuvTransferCoef& k, const uint16_t* lin, const uint8_t* out, int n) {
+    const int rows = SAMPLING == YUV_S420 ? a.h / 2 : a.h;
     const int gx = ((a.w + 3) / 4 + YUV_TX - 1) / YUV_TX, gy = (rows + YUV_TY - 1) / YUV_TY;
     for (int z = 0; z < n; ++z)
         for (int by = 0; by < gy; ++by)
@@ -47,7 +47,7 @@ void run_grid(const YuvTransferArgs& a, const YuvTransferCoef& k, const uint16_t
 }
 
 template <int SAMPLING>
-void run_depth(int depth, const YuvTransferArgs& a, const YuvTransferCoef& k, const uint16_t* lin, const uint8_t* out, int n) {
+void run_depth(int depth, const YuvArgs& a, const YuvTransferCoef& k, const uint16_t* lin, const uint8_t* out, int n) {
     if (depth == SLIDEO_YUV_DEPTH_10_MSB) run_grid<SAMPLING, YUV_D10_MSB>(a, k, lin, out, n);
     else run_grid<SAMPLING, YUV_D10_LSB>(a, k, lin, out, n);
 }
@@ -101,8 +101,8 @@ int convert(const char* in, const char* outp) {
             if (!exact || !dst || (uintptr_t)exact % 16 != 0) return 2;
             std::memcpy(exact + OFS[o], frames.data(), total);
             std::memset(dst, 0xA5, ob);
-            const YuvTransferArgs a = yuv_transfer_args(exact + OFS[o], fs, L, w, h, n, dst);
-            if (sampling == SLIDEO_YUV_SAMPLING_420) run_depth<YUV_T420>(depth, a, k, lin, out, n);
+            const YuvArgs a = yuv_transfer_args(sampling, exact + OFS[o], fs, L, w, h, n, dst);
+            if (sampling == SLIDEO_YUV_SAMPLING_420) run_depth<YUV_S420>(depth, a, k, lin, out, n);
             else if (sampling == SLIDEO_YUV_SAMPLING_422) run_depth<YUV_S422>(depth, a, k, lin, out, n);
             else run_depth<YUV_S444>(depth, a, k, lin, out, n);
             if (o == 0) first.assign(dst, dst + ob);
