@@ -710,6 +710,41 @@ extern "C" {
         box_out4: *mut i32,
     ) -> i32;
     pub fn slideo_matcher_rng_stream_len(m: *const slideo_matcher, len: *mut i64) -> i32;
+    // match tone table (include/slideo_amd.h "Match tone table"): per channel and frame value, the page values of the small-image
+    // pixels that the contributing candidate's hits enclose; the levels table made of the counts
+    pub fn slideo_matcher_tone_begin(m: *mut slideo_matcher, min_inliers: i32, min_hits: i32, flat: i32) -> i32;
+    pub fn slideo_matcher_tone_end(m: *mut slideo_matcher) -> i32;
+    pub fn slideo_matcher_tone_info(
+        m: *mut slideo_matcher,
+        min_inliers: *mut i32,
+        min_hits: *mut i32,
+        flat: *mut i32,
+        frames_through: *mut i64,
+    ) -> i32;
+    pub fn slideo_matcher_tone_counts(
+        m: *mut slideo_matcher,
+        cnt_out: *mut u64,
+        sum_out: *mut u64,
+        frames_through: *mut i64,
+        frames_counted: *mut i64,
+    ) -> i32;
+    pub fn slideo_group_tone_begin(g: *mut slideo_group, min_inliers: i32, min_hits: i32, flat: i32) -> i32;
+    pub fn slideo_group_tone_end(g: *mut slideo_group) -> i32;
+    pub fn slideo_group_tone_info(
+        g: *mut slideo_group,
+        min_inliers: *mut i32,
+        min_hits: *mut i32,
+        flat: *mut i32,
+        frames_through: *mut i64,
+    ) -> i32;
+    pub fn slideo_group_tone_counts(
+        g: *mut slideo_group,
+        cnt_out: *mut u64,
+        sum_out: *mut u64,
+        frames_through: *mut i64,
+        frames_counted: *mut i64,
+    ) -> i32;
+    pub fn slideo_tone_lut(cnt: *const u64, sum: *const u64, min_count: i64, lut_out: *mut u8) -> i32;
     // frame activity map (include/slideo_amd.h "Frame activity map"): per-pixel counts of moved pairs, and the mask read out of them
     pub fn slideo_matcher_activity_begin(m: *mut slideo_matcher, delta: i32) -> i32;
     pub fn slideo_matcher_activity_end(m: *mut slideo_matcher) -> i32;

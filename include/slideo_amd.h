@@ -63,6 +63,7 @@
  *   SLIDEO_SIFT_LIST_CAP n        start capacity of SIFT's per-frame extrema list (65536; the tests force its growth path) [per call]
  *   SLIDEO_RNG_STREAM_LEN n       start length of the pre-drawn cv::RNG stream (the tests force its growth path)
  *   SLIDEO_EVIDENCE_MAX_FRAMES n  the frames limit of an evidence session, read at evidence_begin, 1..2^20 (the tests reach the refusal with it)
+ *   SLIDEO_TONE_MAX_FRAMES n      the frames limit of a tone session, read at tone_begin, 1..2^31 (the tests reach the refusal with it)
  *   SLIDEO_RANSAC_WINDOW=0        ransac_kernel's redraw schedule by the fixed point only                       [per unit]
  *   SLIDEO_RH_TAIL_ROUNDS n       verify_model 1: rounds before a candidate moves to ransac_h_tail_kernel (256; 0 = never) [per unit]
  *   SLIDEO_REFINE_LANE_LM 0|1     verify_model 1: the small candidates' LM in refine_h_kernel<1> / in the eigen kernel's lanes [per unit]
@@ -1903,6 +1904,81 @@ int32_t     slideo_evidence_box(const uint32_t* seen, const uint32_t* hit, int32
                                 int64_t min_hits, int32_t min_hit_ppm, int32_t* box_out4);
 /* Tap: the length of the pre-drawn cv::RNG stream now: SLIDEO_RNG_STREAM_LEN at creation, larger once a unit outran it and was run again. */
 int32_t     slideo_matcher_rng_stream_len(const slideo_matcher* m, int64_t* len);
+
+/* ---- Match tone table (extension: the measurement a frame levels table can be made from, out of the matches) ------------------------
+ * The levels histogram ("Frame levels") is blind: it reads every pixel of the frame and stretches each channel between two
+ * percentile points.  On a filmed or composited lecture the histogram is the room's, not the slide's, and a stretch is linear per
+ * channel where a projector's raised black, gamma and colour cast are not.  After a match the device holds what relates the tones
+ * directly: a candidate's transform, the page's small image, the analysed frame, the votes and the keypoints.
+ * A matcher carries a TONE SESSION, off by default, beside the evidence session and built like it.  Its state is "none", or:
+ * min_inliers >= 0, min_hits >= 1, flat in 0..255; the accumulators cnt[3][256] and sum[3][256] (u64, channel B, G, R by frame
+ * value) and frames_counted (u64), all on the device; frames_through.
+ * The session counts during MATCH calls.  Every call form that runs the verify stage counts, the evidence map's list: synchronous
+ * calls and submit / collect, host and device frames, the BGR and the YUV door, gated calls, slideo_match_kept_frames,
+ * slideo_match_frames_features_bgr8, and the group's forms through their members.  Unchanged, deferred, recalled and direct frames
+ * of a gated call never went through the pipeline and never count.  frames_through counts the frames that went through.
+ *   the contributor  NOT the verdict (its similarity test is what a bad tone breaks).  Of the frame's candidate slots, as
+ *                    slideo_last_frame_candidates returns them, keep those whose model was found (transform not all zero) and whose
+ *                    inliers >= min_inliers; the contributor is the one with the most inliers, ties to the first slot.  A frame
+ *                    with no such slot does not contribute.
+ * With the contributor's page p and transform M:
+ *   hits             a vote (q, t) of the contributor's run is a hit under the evidence map's rule, unchanged: dx*dx + dy*dy <=
+ *                    ransac_threshold^2 in float64, verify_model 0 and 1, w == 0 is no hit, left to right, no fused multiply-add.
+ *                    Fewer than min_hits hits: the frame does not contribute.  The HIT BOX, in PAGE coordinates, over the hits'
+ *                    page_xy[t]: bx0 = floor(min x), bx1 = ceil(max x), by0 = floor(min y), by1 = ceil(max y).
+ *   samples          with (w, h) the page's size and (sw, sh) its small image's: for every pixel (i, j) of the small image, its
+ *                    centre's page coordinate is x = ((i + 0.5) * w) / sw - 0.5, y = ((j + 0.5) * h) / sh - 0.5, in float64.  The
+ *                    pixel is sampled iff  bx0 <= x <= bx1 && by0 <= y <= by1;  its four edge-clamped neighbours in the small image
+ *                    differ from it by at most `flat` in every channel;  and (Xi, Yi) = (floor(X + 0.5), floor(Y + 0.5)) lies in
+ *                    [0, aw) x [0, ah), where (X, Y) is M applied to (x, y) with the hit test's arithmetic (verify_model 1: w == 0
+ *                    is no sample) and aw x ah is the analysed frame: the image the pipeline analyses, levels included.
+ *                    For each channel c, with fv = frame[Yi][Xi][c] and pv = small[j][i][c]:  cnt[c][fv] += 1; sum[c][fv] += pv.
+ *   frames_counted   += 1 for a frame with a contributor and at least min_hits hits.
+ * Integer adds commute: the units in flight and the group's members share or sum accumulators, and no order enters.  A unit that is
+ * run again counts once (the evidence kernel's flags-word rule).
+ * A session holds at most 2^31 frames through (u64 cannot overflow below that): a call that could pass it (its frames and those
+ * of the units in flight included) is refused with SLIDEO_ERR_INVALID_ARG and nothing runs.
+ * Installing nothing: the session changes no verdict, no trace and no setting; verdict bytes are identical with and without it.
+ * The caller reads the counts out, makes a table with slideo_tone_lut, looks at it, and hands it to slideo_matcher_set_frame_levels
+ * (which, like every setter that changes the analysed image, ends the session).  No parameter has a default.
+ * Whatever ends an evidence session ends a tone session (see there: the setters that change the analysed image, a counted call
+ * that fails after its first unit was submitted), and slideo_matcher_tone_end.  The frame mask, its scope, the direct settings, the
+ * gate reference and page sets leave it open.  A tone session and an evidence session may be open together; each one's results are
+ * what they are alone.  SIFT mode: begin in SIFT mode and slideo_matcher_use_sift under an open session are SLIDEO_ERR_UNSUPPORTED.
+ * Where it runs (csrc/tone.hip.h, launched by csrc/stage_verify.hip unit_verify behind verdict_kernel, and behind evidence_kernel
+ * when both sessions are open, on the unit's stream, only while a session is open): tone_kernel, one block of 256 threads per frame
+ * — the votes with the hit box through LDS min / max, then the samples into per-block LDS bins, a thread walking 32 consecutive
+ * pixels of a small-image row and adding a run only when the bin changes; the block's nonzero bins go to the u64 arrays with 64-bit
+ * atomics whose result is not read.  The per-frame body is host + device functions (tools/tone_hostcheck.cpp runs it on the CPU).
+ * Limits: the table is a conditional mean — at text edges the area-averaged page pixel and the point-sampled frame pixel disagree,
+ * and `flat` trades samples for cleanliness; a speaker in front of the slide pollutes bins in proportion to the area covered; one
+ * table per channel cannot undo vignetting or a gradient; frames so dark that RANSAC finds no model teach nothing.
+ * Every call returns SLIDEO_ERR_INVALID_ARG for a null handle or a null required pointer. */
+/* Idle matcher, no tone session open (SLIDEO_ERR_STATE otherwise); min_inliers < 0, min_hits < 1 or flat outside 0..255:
+ * SLIDEO_ERR_INVALID_ARG; SIFT mode: SLIDEO_ERR_UNSUPPORTED.  Afterwards every count is 0.  May be called before finalize. */
+int32_t     slideo_matcher_tone_begin(slideo_matcher* m, int32_t min_inliers, int32_t min_hits, int32_t flat);
+/* Idle matcher.  The state "none"; the device buffer is released.  Fine when the state is "none" already. */
+int32_t     slideo_matcher_tone_end(slideo_matcher* m);
+/* The session's settings and the frames of the collected units.  SLIDEO_ERR_STATE in the state "none". */
+int32_t     slideo_matcher_tone_info(slideo_matcher* m, int32_t* min_inliers, int32_t* min_hits, int32_t* flat, int64_t* frames_through);
+/* Idle matcher (SLIDEO_ERR_STATE with units in flight, and in the state "none").  cnt_out, sum_out: 3 x 256 elements each. */
+int32_t     slideo_matcher_tone_counts(slideo_matcher* m, uint64_t* cnt_out /*[3][256]*/, uint64_t* sum_out /*[3][256]*/, int64_t* frames_through,
+                                       int64_t* frames_counted);
+/* The group forms: begin and end start and end EVERY member's session (validated on every member before one is touched); info and
+ * counts return the members' sums.  The frames limit holds per member. */
+int32_t     slideo_group_tone_begin(slideo_group* g, int32_t min_inliers, int32_t min_hits, int32_t flat);
+int32_t     slideo_group_tone_end(slideo_group* g);
+int32_t     slideo_group_tone_info(slideo_group* g, int32_t* min_inliers, int32_t* min_hits, int32_t* flat, int64_t* frames_through);
+int32_t     slideo_group_tone_counts(slideo_group* g, uint64_t* cnt_out /*[3][256]*/, uint64_t* sum_out /*[3][256]*/, int64_t* frames_through,
+                                     int64_t* frames_counted);
+/* A pure host function in integers (no handle, no device): the levels table of the counts, what slideo_matcher_set_frame_levels
+ * takes.  Per channel:  the ANCHORS are the values v with cnt[v] >= min_count;  mean[v] = (2 * sum[v] + cnt[v]) / (2 * cnt[v]);
+ * m[v] is the running maximum of mean over the anchors up to v (the table is monotone);  lut[x] = m[first anchor] for x below the
+ * first anchor and m[last anchor] above the last;  between neighbouring anchors a < x < b:
+ * lut[x] = (2 * (m[a] * (b - x) + m[b] * (x - a)) + (b - a)) / (2 * (b - a)).
+ * SLIDEO_ERR_INVALID_ARG, and nothing written: min_count < 1, a channel without an anchor, a cnt above 2^48 or a sum[v] above
+ * 255 * cnt[v] (no session gives either). */
+int32_t     slideo_tone_lut(const uint64_t* cnt /*[3][256]*/, const uint64_t* sum /*[3][256]*/, int64_t min_count, uint8_t* lut_out /*[3][256]*/);
 
 #ifdef __cplusplus
 }

@@ -384,6 +384,8 @@ EXPORTS = [
     "slideo_matcher_evidence_begin", "slideo_matcher_evidence_end", "slideo_matcher_evidence_info", "slideo_matcher_evidence_counts",
     "slideo_group_evidence_begin", "slideo_group_evidence_end", "slideo_group_evidence_info", "slideo_group_evidence_counts",
     "slideo_evidence_mask", "slideo_evidence_box", "slideo_matcher_rng_stream_len",
+    "slideo_matcher_tone_begin", "slideo_matcher_tone_end", "slideo_matcher_tone_info", "slideo_matcher_tone_counts",
+    "slideo_group_tone_begin", "slideo_group_tone_end", "slideo_group_tone_info", "slideo_group_tone_counts", "slideo_tone_lut",
 ]
 
 # frame mask scope (include/slideo_amd.h "Frame mask scope")
@@ -550,6 +552,14 @@ def lib():
             L.slideo_evidence_mask.argtypes = [vp, vp, i32, i32, i32, i32, i32, i64, i32, i32, vp, i64]
             L.slideo_evidence_box.argtypes = [vp, vp, i32, i32, i32, i32, i32, i64, i32, vp]
             L.slideo_matcher_rng_stream_len.argtypes = [vp, vp]
+        if hasattr(L, "slideo_matcher_tone_begin"):
+            vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
+            for pre in ("slideo_matcher_", "slideo_group_"):
+                getattr(L, pre + "tone_begin").argtypes = [vp, i32, i32, i32]
+                getattr(L, pre + "tone_end").argtypes = [vp]
+                getattr(L, pre + "tone_info").argtypes = [vp] * 5
+                getattr(L, pre + "tone_counts").argtypes = [vp] * 5
+            L.slideo_tone_lut.argtypes = [vp, vp, i64, vp]
         if hasattr(L, "slideo_matcher_content_begin"):
             vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
             L.slideo_matcher_content_begin.argtypes = [vp, i32]
@@ -694,6 +704,29 @@ class _FrameCalls:
         if seen.size:
             self._check(fn(self._h, _p(seen), _p(hit), C.c_int64(seen.size), C.byref(gw), C.byref(gh), C.byref(ft), C.byref(fc)))
         return seen, hit, ft.value, fc.value
+
+    # ---- match tone table (include/slideo_amd.h "Match tone table"); a Group's are the members' sums ----
+    def tone_begin(self, min_inliers, min_hits, flat):
+        """An empty tone session: match calls from now on count, per channel and frame value, the page values of the small-image
+        pixels that the contributing candidate's hits enclose (the candidate with a model and the most inliers, at least min_inliers;
+        at least min_hits hits; small-image pixels whose neighbours differ by at most flat)."""
+        self._check(getattr(lib(), self._SETS + "tone_begin")(self._h, int(min_inliers), int(min_hits), int(flat)))
+
+    def tone_end(self):
+        self._check(getattr(lib(), self._SETS + "tone_end")(self._h))
+
+    def tone_info(self):
+        """-> {min_inliers, min_hits, flat, frames_through}."""
+        v = [C.c_int32() for _ in range(3)] + [C.c_int64()]
+        self._check(getattr(lib(), self._SETS + "tone_info")(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("min_inliers", "min_hits", "flat", "frames_through"), (x.value for x in v)))
+
+    def tone_counts(self):
+        """-> (cnt uint64 [3, 256], sum uint64 [3, 256], frames_through, frames_counted)."""
+        cnt, sm = np.zeros((3, 256), np.uint64), np.zeros((3, 256), np.uint64)
+        ft, fc = C.c_int64(), C.c_int64()
+        self._check(getattr(lib(), self._SETS + "tone_counts")(self._h, _p(cnt), _p(sm), C.byref(ft), C.byref(fc)))
+        return cnt, sm, ft.value, fc.value
 
     def last_candidates(self, frame_in_batch):
         cands = np.zeros(64, CANDIDATE_DTYPE)
@@ -1941,6 +1974,20 @@ def evidence_box(seen, hit, cell, aw, ah, min_hits, min_hit):
     if rc != OK:
         raise SlideoError(rc, "slideo_evidence_box: an argument outside its range (include/slideo_amd.h \"Match evidence map\")")
     return tuple(box)
+
+
+def tone_lut(cnt, sm, min_count):
+    """slideo_tone_lut (include/slideo_amd.h "Match tone table"): cnt, sm uint64 [3, 256] -> the table uint8 [3, 256], what
+    set_frame_levels takes.  SlideoError: min_count < 1, or a channel in which no frame value was seen min_count times."""
+    cnt, sm = np.ascontiguousarray(cnt, np.uint64), np.ascontiguousarray(sm, np.uint64)
+    if cnt.shape != (3, 256) or sm.shape != (3, 256):
+        raise ValueError("cnt and sum: two uint64 [3, 256] arrays, got %s and %s" % (cnt.shape, sm.shape))
+    out = np.zeros((3, 256), np.uint8)
+    rc = lib().slideo_tone_lut(_p(cnt), _p(sm), C.c_int64(int(min_count)), _p(out))
+    if rc != OK:
+        raise SlideoError(rc, "slideo_tone_lut: min_count below 1, a channel without an anchor, or counts no session gives "
+                              "(include/slideo_amd.h \"Match tone table\")")
+    return out
 
 
 def changed_ssd_threshold(changed_similarity, small_w, small_h):

@@ -854,4 +854,76 @@ int32_t slideo_group_evidence_counts(slideo_group* g, uint32_t* seen_out, uint32
     GROUP_CATCH(g)
 }
 
+// ---- Match tone table (include/slideo_amd.h "Match tone table"): every member carries a session, the read-outs return the sums -------
+int32_t slideo_group_tone_begin(slideo_group* g, int32_t min_inliers, int32_t min_hits, int32_t flat) {
+    if (!g) return SLIDEO_ERR_INVALID_ARG;
+    GROUP_TRY
+    if (min_inliers < 0) fail(SLIDEO_ERR_INVALID_ARG, "tone_begin: min_inliers %d below 0", min_inliers);
+    if (min_hits < 1) fail(SLIDEO_ERR_INVALID_ARG, "tone_begin: min_hits %d below 1", min_hits);
+    if (flat < 0 || flat > 255) fail(SLIDEO_ERR_INVALID_ARG, "tone_begin: flat %d outside 0..255", flat);
+    // validated before any member is touched
+    for (slideo_matcher* m : g->members) {
+        if (m->sift_on) fail(SLIDEO_ERR_UNSUPPORTED, "tone_begin: the tone table is not defined in SIFT mode");
+        require_idle(m);
+        if (m->tone.on) fail(SLIDEO_ERR_STATE, "tone_begin: a session is open (slideo_group_tone_end first)");
+    }
+    for (slideo_matcher* m : g->members) check_member_call(m, slideo_matcher_tone_begin(m, min_inliers, min_hits, flat));
+    GROUP_CATCH(g)
+}
+
+int32_t slideo_group_tone_end(slideo_group* g) {
+    if (!g) return SLIDEO_ERR_INVALID_ARG;
+    GROUP_TRY
+    for (slideo_matcher* m : g->members) require_idle(m);
+    for (slideo_matcher* m : g->members) check_member_call(m, slideo_matcher_tone_end(m));
+    GROUP_CATCH(g)
+}
+
+namespace {
+// the members' sessions as one: every member's open and of the same settings; `through` summed
+void group_tone(slideo_group* g, slideo_matcher::Tone& sum) {
+    sum = slideo_matcher::Tone{};
+    for (slideo_matcher* m : g->members) {
+        const slideo_matcher::Tone& T = m->tone;
+        if (!T.on) fail(SLIDEO_ERR_STATE, "no tone session on every member: slideo_group_tone_begin first");
+        if (!sum.on) { sum = T; sum.through = 0; }
+        if (T.min_inliers != sum.min_inliers || T.min_hits != sum.min_hits || T.flat != sum.flat)
+            fail(SLIDEO_ERR_STATE, "the members' tone sessions differ (one was begun directly)");
+        sum.through += T.through;
+    }
+}
+}  // namespace
+
+int32_t slideo_group_tone_info(slideo_group* g, int32_t* min_inliers, int32_t* min_hits, int32_t* flat, int64_t* frames_through) {
+    if (!g) return SLIDEO_ERR_INVALID_ARG;
+    GROUP_TRY
+    if (!min_inliers || !min_hits || !flat || !frames_through) fail(SLIDEO_ERR_INVALID_ARG, "null output");
+    slideo_matcher::Tone T;
+    group_tone(g, T);
+    *min_inliers = T.min_inliers; *min_hits = T.min_hits; *flat = T.flat; *frames_through = T.through;
+    GROUP_CATCH(g)
+}
+
+int32_t slideo_group_tone_counts(slideo_group* g, uint64_t* cnt_out, uint64_t* sum_out, int64_t* frames_through, int64_t* frames_counted) {
+    if (!g) return SLIDEO_ERR_INVALID_ARG;
+    GROUP_TRY
+    if (!cnt_out || !sum_out || !frames_through || !frames_counted) fail(SLIDEO_ERR_INVALID_ARG, "null cnt_out/sum_out/frames_through/frames_counted");
+    for (slideo_matcher* m : g->members) require_idle(m);
+    slideo_matcher::Tone T;
+    group_tone(g, T);
+    // (every member holds fewer than 2^31 frames of fewer than 2^24 samples of at most 255: the members' sums stay inside u64)
+    std::vector<uint64_t> part(1536), cnt(768, 0), sum(768, 0);
+    int64_t counted = 0;
+    for (slideo_matcher* m : g->members) {
+        int64_t t = 0, c = 0;
+        check_member_call(m, slideo_matcher_tone_counts(m, part.data(), part.data() + 768, &t, &c));
+        for (int i = 0; i < 768; ++i) { cnt[(size_t)i] += part[(size_t)i]; sum[(size_t)i] += part[(size_t)(768 + i)]; }
+        counted += c;
+    }
+    std::copy(cnt.begin(), cnt.end(), cnt_out);
+    std::copy(sum.begin(), sum.end(), sum_out);
+    *frames_through = T.through; *frames_counted = counted;
+    GROUP_CATCH(g)
+}
+
 }  // extern "C"

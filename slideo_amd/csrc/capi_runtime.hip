@@ -173,7 +173,7 @@ void settings_commit(slideo_matcher* m, Setting what, FrameSettings next, const 
     m->fs = next;
     const SettingEnds& ends = SETTING_ENDS[what];
     if (ends.kept) m->kept.valid = false;
-    if (ends.kept && ends.gate) evidence_drop(m);      // (the analysed image changes under an open evidence session: the state "none")
+    if (ends.kept && ends.gate) sessions_drop(m);      // (the analysed image changes under an open evidence or tone session: the state "none")
     if (ends.gate) { gate_state_reset(m); m->gate_refs.clear(); m->gate_refs_valid = false; }
     if (ends.map_gen) ++m->fs.gate_map_gen;
 }
@@ -324,7 +324,7 @@ static void unit_collect_body(slideo_matcher* m, Slot& S, slideo_verdict* out_ho
 // returned: an open evidence session ends with it)
 void unit_collect(slideo_matcher* m, Slot& S, slideo_verdict* out_host) {
     try { unit_collect_body(m, S, out_host); }
-    catch (...) { evidence_drop(m); throw; }
+    catch (...) { sessions_drop(m); throw; }
 }
 
 static void unit_collect_body(slideo_matcher* m, Slot& S, slideo_verdict* out_host) {
@@ -373,6 +373,7 @@ static void unit_collect_body(slideo_matcher* m, Slot& S, slideo_verdict* out_ho
         HIP_CHECK(hipEventElapsedTime(&t, S.ev[0], S.ev[4])); m->prof_ms[3] += t; m->prof_n[3]++;
     }
     std::memcpy(out_host, ho, (size_t)n * sizeof(slideo_verdict));
+    tone_tally(m, n);
     evidence_tally(m, out_host, n);                  // (the run whose verdicts are returned: evidence_kernel counted this one alone)
     const size_t base = m->last_fcs.size();
     m->last_fcs.resize(base + n);
@@ -406,6 +407,7 @@ void match_frames_impl(slideo_matcher* m, int n, FrameSrc src, slideo_verdict* o
     m->last_fcs.clear();
     if (n == 0) return;
     evidence_admit(m, src.plan.uw, src.plan.uh, n);
+    tone_admit(m, n);
     int unit = unit_fit(m, src, n, gated);
     area_class_for(m, src.plan.uw, src.plan.uh);
     upload_area(m);
@@ -456,7 +458,7 @@ void match_frames_impl(slideo_matcher* m, int n, FrameSrc src, slideo_verdict* o
         m->units_pending = false;
         (void)hipStreamSynchronize(m->copy_st);          // (DMA from the caller's pinned buffer may still be running)
         for (Slot& S : m->slots) { (void)hipStreamSynchronize(S.st); S.busy = false; S.gate.on = false; }
-        evidence_drop(m);                                // (units of the call may have counted: an open evidence session ends)
+        sessions_drop(m);                                // (units of the call may have counted: an open evidence or tone session ends)
         throw;
     }
 }
@@ -474,6 +476,7 @@ static void submit_impl(slideo_matcher* m, int32_t n_frames, FrameSrc src, void*
     if (n_frames > fit)
         fail(SLIDEO_ERR_CAPACITY, "%d frames exceed the per-slot workspace budget (%d); submit smaller units or raise SLIDEO_WS_GB", n_frames, fit);
     evidence_admit(m, src.plan.uw, src.plan.uh, n_frames);
+    tone_admit(m, n_frames);
     area_class_for(m, src.plan.uw, src.plan.uh);
     upload_area(m);
     { bool any = false; for (const Slot& c : m->slots) any |= c.busy; if (!any) m->last_fcs.clear(); }
@@ -482,7 +485,7 @@ static void submit_impl(slideo_matcher* m, int32_t n_frames, FrameSrc src, void*
         HIP_CHECK(hipStreamWaitEvent(S.st, S.ev_in, 0));
     }
     try { unit_begin(m, S, src, 0, n_frames, nullptr, gated); }
-    catch (...) { evidence_drop(m); throw; }      // (a unit half submitted may count: an open evidence session ends)
+    catch (...) { sessions_drop(m); throw; }      // (a unit half submitted may count: an open evidence or tone session ends)
     S.ticket = m->next_ticket++;
     *ticket_out = S.ticket;
     m->next_slot = (m->next_slot + 1) % NSLOTS;

@@ -10,7 +10,7 @@
 //                                                 frame_region.hip.h, frame_mask.hip.h, levels.hip.h levels_kernel)
 //   stage_knn.hip      index build + k-NN stage   (kernels: knn.hip.h, knn_tile.hip.h, knn_l2.hip.h, knn_lsh.hip.h)
 //   stage_verify.hip   vote .. verdict, small img (kernels: verify.hip.h, homography.hip.h); the match evidence map's session, its
-//                      launch behind the verdicts and its entry points (kernel: evidence.hip.h)
+//                      launch behind the verdicts and its entry points (kernel: evidence.hip.h); the match tone table's likewise (kernel: tone.hip.h)
 //   stage_sift.hip     SIFT stage + entry points  (kernels: sift.hip.h)
 //   stage_page_set.hip page sets: a subset's search operand built from the finalized deck (kernels: page_set.hip.h)
 //   stage_gate.hip     changed-frame gate: gated units, the gate state, its record and its entry points (kernels: gate.hip.h)
@@ -456,6 +456,12 @@ struct slideo_matcher {
     struct Evidence { bool on = false; int cell = 0, min_inliers = 0, aw = 0, ah = 0, gw = 0, gh = 0; int64_t through = 0, counted = 0, max_frames = 0; } evidence;
     slideo::DevBuf d_evidence;
 
+    // match tone table (include/slideo_amd.h "Match tone table"): the session — "none" (on false) or the settings of tone_begin and the
+    // frames of the collected units (through) — and its device buffer {cnt u64 [3][256] | sum u64 [3][256] | frames_counted u64},
+    // zeroed at begin, which tone_kernel adds to on the units' streams.  max_frames: 2^31 unless SLIDEO_TONE_MAX_FRAMES lowered it at begin
+    struct Tone { bool on = false; int min_inliers = 0, min_hits = 0, flat = 0; int64_t through = 0, max_frames = 0; } tone;
+    slideo::DevBuf d_tone;
+
     // direct page look-up (include/slideo_amd.h "Direct page look-up"): built at the first use with fs.direct_t > 0 after finalize, the
     // deck's size classes
     bool direct_built = false;
@@ -618,6 +624,12 @@ void unit_verify(slideo_matcher* m, Slot& S, const VerifyParams& vp, const DevFr
 void evidence_admit(slideo_matcher* m, int uw, int uh, int n);
 void evidence_tally(slideo_matcher* m, const slideo_verdict* v, int n);
 inline void evidence_drop(slideo_matcher* m) { m->evidence = slideo_matcher::Evidence{}; }
+// Match tone table (tone.hip.h), no-ops without a session.  tone_admit: in front of a match call's first unit, the frames limit.
+// tone_tally: the frames of a collected unit.  tone_drop: the state "none".  sessions_drop: what ends an evidence session ends a tone session
+void tone_admit(slideo_matcher* m, int n);
+inline void tone_tally(slideo_matcher* m, int n) { if (m->tone.on) m->tone.through += n; }
+inline void tone_drop(slideo_matcher* m) { m->tone = slideo_matcher::Tone{}; }
+inline void sessions_drop(slideo_matcher* m) { evidence_drop(m); tone_drop(m); }
 // (sw, sh: the small size, for callers without a FramePlan — pages, taps, the validity map)
 void run_small(slideo_matcher* m, const DevFrames& imgs, int n, hipStream_t st, int* sw = nullptr, int* sh = nullptr);
 // the same into `dst` (n small images back to back) in place of m->d_small: small images of consecutive gated units overlap

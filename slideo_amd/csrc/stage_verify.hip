@@ -1,10 +1,11 @@
 // stage_verify.hip — drivers of the verification stage, vote .. verdict, and of to_small_image (kernels: verify.hip.h, homography.hip.h);
 // the match evidence map of include/slideo_amd.h "Match evidence map": its session, its launch behind the verdicts and its entry
-// points (kernel: evidence.hip.h).
+// points (kernel: evidence.hip.h); the match tone table of "Match tone table" likewise (kernel: tone.hip.h).
 #include "runtime.hpp"
 #include "verify.hip.h"
 #include "homography.hip.h"
 #include "evidence.hip.h"
+#include "tone.hip.h"
 
 #include <cstring>
 
@@ -91,6 +92,35 @@ static void evidence_launch(slideo_matcher* m, Slot& S, const VerifyParams& vp, 
     a.seen = m->d_evidence.as<uint32_t>(); a.hit = a.seen + (size_t)E.gw * E.gh;
     evidence_kernel<<<n, EV_THREADS, 0, S.st>>>(a);
     check_launch("evidence_kernel");
+}
+
+// ---- match tone table ---------------------------------------------------------------------------------------------------------------
+void tone_admit(slideo_matcher* m, int n) {
+    const slideo_matcher::Tone& T = m->tone;
+    if (!T.on || n <= 0) return;
+    int64_t pending = 0;
+    for (const Slot& S : m->slots) if (S.busy) pending += S.n;
+    if (T.through + pending + n > T.max_frames)
+        fail(SLIDEO_ERR_INVALID_ARG, "%lld frames would pass the tone session's %lld: read the counts out and begin again", (long long)(T.through + pending + n),
+             (long long)T.max_frames);
+}
+
+// tone_kernel over the unit's frames, behind verdict_kernel (and evidence_kernel) on the unit's stream
+static void tone_launch(slideo_matcher* m, Slot& S, const VerifyParams& vp, const DevFrames& f, int n) {
+    const slideo_matcher::Tone& T = m->tone;
+    ToneArgs a{};
+    a.ev.fcs = S.d_fcs.as<FrameCands>(); a.ev.qofs = S.d_qofs.as<uint32_t>(); a.ev.kp = S.d_kp.as<slideo_keypoint>();
+    a.ev.page_xy = reinterpret_cast<const EvXY*>(m->d_page_xy.as<float2>());
+    a.ev.votes = reinterpret_cast<const EvVote*>(S.d_votes.as<uint2>());
+    a.ev.flags = S.d_flags.as<uint32_t>();
+    a.ev.rerun_mask = S.u_async ? 12u : 4u;      // (evidence_launch's: unit_collect's re-run rules)
+    a.ev.k = vp.k; a.ev.model = vp.model; a.ev.thr2 = vp.thr * vp.thr;
+    a.pageinfo = m->d_pageinfo.as<PageInfo>(); a.page_small = m->d_page_small.as<uint8_t>();
+    a.frames = f.p; a.frame_stride = f.frame_stride; a.stride = f.stride; a.aw = f.w; a.ah = f.h;
+    a.min_inliers = T.min_inliers; a.min_hits = T.min_hits; a.flat = T.flat;
+    a.acc = m->d_tone.as<unsigned long long>();
+    tone_kernel<<<n, TONE_THREADS, 0, S.st>>>(a);
+    check_launch("tone_kernel");
 }
 
 // Everything after the neighbour lists (S.d_keys, Hamming key format) of a unit: the per-page vote, RANSAC (similarity or
@@ -208,6 +238,7 @@ void unit_verify(slideo_matcher* m, Slot& S, const VerifyParams& vp, const DevFr
                                                S.d_verdicts.as<slideo_verdict>());
     check_launch("verdict_kernel");
     if (m->evidence.on && qtot > 0) evidence_launch(m, S, vp, f, n);
+    if (m->tone.on && qtot > 0) tone_launch(m, S, vp, f, n);
     if (prof) HIP_CHECK(hipEventRecord(S.ev[3], st));
     uint8_t* ho = S.h_out.as<uint8_t>();
     const size_t tail = (size_t)n * (sizeof(slideo_verdict) + sizeof(FrameCands));
@@ -325,6 +356,76 @@ int32_t slideo_evidence_box(const uint32_t* seen, const uint32_t* hit, int32_t g
     if (min_hits < 0 || min_hits > 0xFFFFFFFFll || min_hit_ppm < 0 || min_hit_ppm > 1000000) return SLIDEO_ERR_INVALID_ARG;
     evidence_box(seen, hit, gw, gh, cell, aw, ah, (uint32_t)min_hits, (uint32_t)min_hit_ppm, box_out4);
     return SLIDEO_OK;
+}
+
+}  // extern "C"
+
+// ---- Match tone table (include/slideo_amd.h "Match tone table") ----------------------------------------------------------------------
+extern "C" {
+
+int32_t slideo_matcher_tone_begin(slideo_matcher* m, int32_t min_inliers, int32_t min_hits, int32_t flat) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    if (min_inliers < 0) fail(SLIDEO_ERR_INVALID_ARG, "tone_begin: min_inliers %d below 0", min_inliers);
+    if (min_hits < 1) fail(SLIDEO_ERR_INVALID_ARG, "tone_begin: min_hits %d below 1", min_hits);
+    if (flat < 0 || flat > 255) fail(SLIDEO_ERR_INVALID_ARG, "tone_begin: flat %d outside 0..255", flat);
+    if (m->sift_on) fail(SLIDEO_ERR_UNSUPPORTED, "tone_begin: the tone table is not defined in SIFT mode");
+    require_idle(m);
+    if (m->tone.on) fail(SLIDEO_ERR_STATE, "tone_begin: a session is open (slideo_matcher_tone_end first)");
+    HIP_CHECK(hipSetDevice(m->device));
+    const size_t bytes = (size_t)(TONE_BINS + 1) * 8;
+    m->d_tone.reserve(bytes + 16);
+    HIP_CHECK(hipMemsetAsync(m->d_tone.p, 0, bytes, m->stream));      // (the zeroed counts stand before any unit is submitted)
+    HIP_CHECK(hipStreamSynchronize(m->stream));
+    m->tone = slideo_matcher::Tone{};
+    m->tone.on = true; m->tone.min_inliers = min_inliers; m->tone.min_hits = min_hits; m->tone.flat = flat;
+    m->tone.max_frames = std::min<int64_t>(TONE_MAX_FRAMES, std::max<long>(1, env_long("SLIDEO_TONE_MAX_FRAMES", (long)TONE_MAX_FRAMES)));
+    API_CATCH(m)
+}
+
+int32_t slideo_matcher_tone_end(slideo_matcher* m) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    require_idle(m);
+    HIP_CHECK(hipSetDevice(m->device));
+    tone_drop(m);
+    m->d_tone.release();
+    API_CATCH(m)
+}
+
+int32_t slideo_matcher_tone_info(slideo_matcher* m, int32_t* min_inliers, int32_t* min_hits, int32_t* flat, int64_t* frames_through) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    if (!min_inliers || !min_hits || !flat || !frames_through) fail(SLIDEO_ERR_INVALID_ARG, "null output");
+    const slideo_matcher::Tone& T = m->tone;
+    if (!T.on) fail(SLIDEO_ERR_STATE, "no tone session: slideo_matcher_tone_begin first");
+    *min_inliers = T.min_inliers; *min_hits = T.min_hits; *flat = T.flat; *frames_through = T.through;
+    API_CATCH(m)
+}
+
+int32_t slideo_matcher_tone_counts(slideo_matcher* m, uint64_t* cnt_out, uint64_t* sum_out, int64_t* frames_through, int64_t* frames_counted) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    if (!cnt_out || !sum_out || !frames_through || !frames_counted) fail(SLIDEO_ERR_INVALID_ARG, "null cnt_out/sum_out/frames_through/frames_counted");
+    require_idle(m);
+    const slideo_matcher::Tone& T = m->tone;
+    if (!T.on) fail(SLIDEO_ERR_STATE, "no tone session: slideo_matcher_tone_begin first");
+    HIP_CHECK(hipSetDevice(m->device));
+    uint64_t counted = 0;
+    HIP_CHECK(hipMemcpyAsync(cnt_out, m->d_tone.p, 768 * 8, hipMemcpyDeviceToHost, m->stream));
+    HIP_CHECK(hipMemcpyAsync(sum_out, m->d_tone.as<uint64_t>() + 768, 768 * 8, hipMemcpyDeviceToHost, m->stream));
+    HIP_CHECK(hipMemcpyAsync(&counted, m->d_tone.as<uint64_t>() + TONE_BINS, 8, hipMemcpyDeviceToHost, m->stream));
+    HIP_CHECK(hipStreamSynchronize(m->stream));
+    *frames_through = T.through; *frames_counted = (int64_t)counted;
+    API_CATCH(m)
+}
+
+int32_t slideo_tone_lut(const uint64_t* cnt, const uint64_t* sum, int64_t min_count, uint8_t* lut_out) {
+    if (!cnt || !sum || !lut_out || min_count < 1) return SLIDEO_ERR_INVALID_ARG;
+    // (no mean above 255, and 2 * sum + cnt stays far inside u64)
+    for (int i = 0; i < 768; ++i)
+        if (cnt[i] > ((uint64_t)1 << 48) || sum[i] > 255 * cnt[i]) return SLIDEO_ERR_INVALID_ARG;
+    return tone_lut(cnt, sum, (uint64_t)min_count, lut_out) ? SLIDEO_OK : SLIDEO_ERR_INVALID_ARG;
 }
 
 }  // extern "C"

@@ -368,6 +368,33 @@ public:
         if (nc) h_->check(slideo_group_evidence_counts(h_->g, e.seen.data(), e.hit.data(), (int64_t)nc, &e.gw, &e.gh, &e.frames_through, &e.frames_counted));
         return e;
     }
+    // Match tone table (include/slideo_amd.h "Match tone table"; an extension): while a session is open, the tasks' match calls count,
+    // per channel and frame value, the page values of the small-image pixels that the contributing candidate's hits enclose, summed
+    // over the devices.  No task may be running at begin, counts or end.  tone_lut makes the levels table of the counts (what
+    // slideo_group_set_frame_levels takes); nothing is installed, and no value has a default.
+    struct ToneCounts {
+        int32_t min_inliers = 0, min_hits = 0, flat = 0;
+        int64_t frames_through = 0, frames_counted = 0;
+        std::vector<uint64_t> cnt, sum;                // 3 x 256 each: B, G, R by frame value (tone_info leaves them empty)
+    };
+    void tone_begin(int32_t min_inliers, int32_t min_hits, int32_t flat) { h_->check(slideo_group_tone_begin(h_->g, min_inliers, min_hits, flat)); }
+    void tone_end() { h_->check(slideo_group_tone_end(h_->g)); }
+    ToneCounts tone_info() const {
+        ToneCounts t;
+        h_->check(slideo_group_tone_info(h_->g, &t.min_inliers, &t.min_hits, &t.flat, &t.frames_through));
+        return t;
+    }
+    ToneCounts tone_counts() const {
+        ToneCounts t = tone_info();
+        t.cnt.assign(768, 0); t.sum.assign(768, 0);
+        h_->check(slideo_group_tone_counts(h_->g, t.cnt.data(), t.sum.data(), &t.frames_through, &t.frames_counted));
+        return t;
+    }
+    // the table of the counts; false: a channel in which no frame value was seen min_count times
+    static bool tone_lut(const ToneCounts& t, int64_t min_count, std::vector<uint8_t>& lut768) {
+        lut768.assign(768, 0);
+        return t.cnt.size() == 768 && t.sum.size() == 768 && slideo_tone_lut(t.cnt.data(), t.sum.data(), min_count, lut768.data()) == SLIDEO_OK;
+    }
 private:
     std::shared_ptr<detail::Handle> h_;
     std::shared_ptr<std::vector<I>> images_;

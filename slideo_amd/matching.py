@@ -406,6 +406,32 @@ def learn_frame_levels(matcher, frame_batches, low=0.01, high=0.01):
     return _capi.frame_levels_lut(lo, hi)
 
 
+def learn_frame_levels_from_matches(matcher, frame_batches, *, min_inliers, min_hits, flat=255, min_count):
+    """A frame levels table learnt from the matches themselves (include/slideo_amd.h "Match tone table"): the host BGR batches (each
+    uint8 [n, h, w, 3]) are matched against the matcher's finalized deck under a tone session of `min_inliers`, `min_hits` and
+    `flat`; per channel, the mean page value of the samples of every frame value seen at least `min_count` times, made monotone
+    and interpolated (slideo_tone_lut).  `matcher`: a Matcher or a Group, idle, finalized.  Returns the table uint8 [3, 256]
+    (B, G, R) — what frame_levels= and set_frame_levels take; nothing is installed.  While the matcher carries a levels table T1
+    the samples are the levelled image's, and what is returned is the COMPOSITION lut[c][T1[c][x]]: the table for the frames as
+    they come, to be set in T1's place.  ValueError when no frame contributed.  min_inliers, min_hits and min_count have no default:
+    they depend on the content (docs/EXTENSIONS.md "Match tone table")."""
+    t1 = matcher.frame_levels()
+    matcher.tone_begin(min_inliers, min_hits, flat)
+    try:
+        for batch in frame_batches:
+            matcher.match_frames(batch)
+        cnt, sm, through, counted = matcher.tone_counts()
+    finally:
+        matcher.tone_end()
+    if counted == 0:
+        raise ValueError("learn_frame_levels_from_matches: none of the %d frames contributed (no candidate with a model, %d inliers and "
+                         "%d hits): the tone table is empty" % (through, int(min_inliers), int(min_hits)))
+    lut = _capi.tone_lut(cnt, sm, min_count)
+    if t1 is not None:
+        lut = np.stack([lut[c][t1[c]] for c in range(3)])
+    return lut
+
+
 def dedup_timeline(mappings: List[Matching]) -> List[Matching]:
     """lib.rs:229-244: stable sort by time, drop consecutive mappings with the same image."""
     mappings = sorted(mappings, key=lambda mm: mm.video_time)
