@@ -842,6 +842,80 @@ extern "C" {
     ) -> i32;
 }
 
+/// slideo_frame_list (include/slideo_amd.h, "Frame lists"): a batch described by per-frame plane pointers instead of base + stride,
+/// so that frames decoded into separate buffers are matched without a copy into one batch.  `planes` is a host array of
+/// `n_frames * 3` addresses; `stride[k]` the bytes between rows of the plane at `planes[3 * i + k]`.
+pub const SLIDEO_FRAME_LIST_BGR: i32 = 0;
+pub const SLIDEO_FRAME_LIST_YUV: i32 = 1;
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
+pub struct slideo_frame_list {
+    pub door: i32,
+    pub on_device: i32,
+    pub n_frames: i32,
+    pub width: i32,
+    pub height: i32,
+    pub uv_step: i32,
+    pub stride: [i64; 3],
+    pub planes: *const *const c_void,
+}
+
+extern "C" {
+    pub fn slideo_match_frames_list(
+        m: *mut slideo_matcher,
+        list: *const slideo_frame_list,
+        verdicts_out: *mut slideo_verdict,
+        hip_stream: *mut c_void,
+    ) -> i32;
+    pub fn slideo_match_frames_submit_list(
+        m: *mut slideo_matcher,
+        list: *const slideo_frame_list,
+        hip_stream: *mut c_void,
+        ticket_out: *mut i64,
+    ) -> i32;
+    pub fn slideo_match_changed_frames_list(
+        m: *mut slideo_matcher,
+        list: *const slideo_frame_list,
+        changed_out: *mut u8,
+        similarity_out: *mut f32,
+        verdicts_out: *mut slideo_verdict,
+        hip_stream: *mut c_void,
+    ) -> i32;
+    pub fn slideo_match_changed_frames_submit_list(
+        m: *mut slideo_matcher,
+        list: *const slideo_frame_list,
+        hip_stream: *mut c_void,
+        ticket_out: *mut i64,
+    ) -> i32;
+    pub fn slideo_changed_mask_list(
+        m: *mut slideo_matcher,
+        list: *const slideo_frame_list,
+        prev_small: *const u8,
+        last_small_out: *mut u8,
+        changed_out: *mut u8,
+        similarity_out: *mut f32,
+    ) -> i32;
+    pub fn slideo_matcher_observe_frames_list(m: *mut slideo_matcher, list: *const slideo_frame_list, hip_stream: *mut c_void) -> i32;
+    pub fn slideo_matcher_gate_reset_from_frame_list(m: *mut slideo_matcher, list: *const slideo_frame_list, hip_stream: *mut c_void) -> i32;
+    pub fn slideo_group_match_frames_list(g: *mut slideo_group, list: *const slideo_frame_list, verdicts_out: *mut slideo_verdict) -> i32;
+    pub fn slideo_group_match_changed_frames_list(
+        g: *mut slideo_group,
+        list: *const slideo_frame_list,
+        changed_out: *mut u8,
+        similarity_out: *mut f32,
+        verdicts_out: *mut slideo_verdict,
+    ) -> i32;
+    pub fn slideo_group_changed_mask_list(
+        g: *mut slideo_group,
+        list: *const slideo_frame_list,
+        prev_small: *const u8,
+        last_small_out: *mut u8,
+        changed_out: *mut u8,
+        similarity_out: *mut f32,
+    ) -> i32;
+    pub fn slideo_frame_list_to_bgr8(m: *mut slideo_matcher, list: *const slideo_frame_list, bgr_out: *mut u8, out_capacity: i64) -> i32;
+}
+
 /// The struct layouts above are only valid for one ABI version of the library.
 pub fn assert_abi() {
     let v = unsafe { slideo_abi_version() };
@@ -853,4 +927,5 @@ pub fn assert_abi() {
     assert_eq!(std::mem::size_of::<slideo_config>(), 168);
     assert_eq!(std::mem::size_of::<slideo_verdict>(), 16);
     assert_eq!(std::mem::size_of::<slideo_yuv420_layout>(), 32);
+    assert_eq!(std::mem::size_of::<slideo_frame_list>(), 56);
 }

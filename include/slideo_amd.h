@@ -1980,6 +1980,81 @@ int32_t     slideo_group_tone_counts(slideo_group* g, uint64_t* cnt_out /*[3][25
  * 255 * cnt[v] (no session gives either). */
 int32_t     slideo_tone_lut(const uint64_t* cnt /*[3][256]*/, const uint64_t* sum /*[3][256]*/, int64_t min_count, uint8_t* lut_out /*[3][256]*/);
 
+/* ---- Frame lists (extension: a batch given as per-frame plane pointers) -----------------------------------------------------------
+ * Every frame call above takes one base pointer and one frame_stride_bytes: frames equally spaced in one allocation, every plane of a
+ * YUV frame at a fixed offset from its frame's base.  Frame sources hand out something else — one cv::Mat per sampled frame, an
+ * AVFrame with data[0..2] / linesize[0..2] out of buffer pools, decoder surfaces out of a pool of allocations — and had to be copied
+ * into a batch buffer first.  A FRAME LIST describes a batch by per-frame plane addresses instead; one list form of every frame-call
+ * family takes it, for host and device memory, through both doors and under every frame setting the matcher carries.
+ *
+ * Contract: a list call returns, bit for bit, what the contiguous call of the same family returns for frames holding the same samples
+ * (verdicts and candidate traces, changed flags and similarities, gate state and refs, small images, activity / content / levels /
+ * evidence / tone counts).  The ABI stays 7; no existing record changes.
+ *
+ * The record.  `door` says how the frames are read: SLIDEO_FRAME_LIST_BGR like the *_bgr8 calls (under the matcher's pixel format),
+ * SLIDEO_FRAME_LIST_YUV like the *_yuv420 calls (description, sampling, chroma filter, transfer).  `planes` is a HOST array of
+ * n_frames x 3 addresses, frame i's at planes[3i .. 3i + 2]; the addresses are host or device memory by `on_device`.  stride[k] is
+ * the bytes between rows of the plane at planes[3i + k], the same for every frame.  By sample address (bps, the bytes per sample, and
+ * the chroma plane's size come from the matcher's depth and sampling):
+ *   YUV door, planar and semi-planar   Y (x, y) at planes[3i] + y * stride[0] + x * bps;  U (cx, cy) at planes[3i + 1] + cy * stride[1]
+ *                                      + cx * uv_step * bps;  V the same from planes[3i + 2] and stride[2].  uv_step 1: planar, 2:
+ *                                      interleaved (planes[3i + 2] - planes[3i + 1] == +-bps, stride[1] == stride[2])
+ *   YUV door, packed 4:2:2             planes[3i] is the frame's first byte, planes[3i + 1] and planes[3i + 2] are planes[3i] plus one
+ *                                      of the four (u_offset, v_offset) pairs of "YUV sampling"; uv_step 4, the three strides equal
+ *   BGR door, packed pixel formats     planes[3i] is the frame, stride[0] its row stride; the other two addresses are NULL (stride[1],
+ *                                      stride[2] are not read)
+ *   BGR door, planar RGB / BGR / GBR   three planes in the order the [N, 3, H, W] form has them; uv_step is not read through this door
+ * Rules (SLIDEO_ERR_INVALID_ARG, each with a message naming it, unless stated otherwise): a NULL record or array, a needed plane
+ * that is NULL and an unneeded plane that is not are refused; so are a door or an on_device outside the values above and a negative
+ * n_frames; stride[k] is at least the plane's row bytes (a negative stride is refused); in 16-bit containers every address and stride
+ * is even; an interleaved or packed list keeps the relations above; a uv_step the sampling does not have is refused.  The size rules
+ * are the door's, with their codes (even sizes under 4:2:0, even width under the 4:2:2 forms, the image limits).  Frames and planes
+ * may alias or repeat: nothing is written, there is no overlap rule.  The record and the `planes` array are copied at the call: a
+ * submit form needs only the frames themselves to stay valid until collect.  Sizes and strides are the list's, not a frame's: per-frame
+ * sizes, flipped (negative) strides and pages by list are not part of this.
+ *
+ * Where it runs.  A list is one more source form in front of the one place that stages a call's frames.  HOST lists: every plane of
+ * every frame is copied into the slot's upload buffer in a tight staged layout (rows packed; planar chroma U then V; interleaved
+ * chroma as one plane in the list's U / V order; packed and BGR planes row-tight) — one asynchronous copy per plane whose stride is
+ * its row bytes, one 2-D copy per pitched plane; through the ordered copy stream iff every frame's first plane is page-locked.
+ * DEVICE lists: one kernel (csrc/frame_list.hip.h frame_gather_kernel) gathers the planes into the same staged layout, out of a
+ * pointer table uploaded with the unit.  From the staged layout on a list unit IS a host-frame unit after its upload: the
+ * converters, the reduce, the rectify, the levels, the gate staging and the observe driver run as they do for host frames, and the
+ * unit sizes count a device list as they count a host frame.  So a device list gives up the read-in-place shortcut of contiguous
+ * device BGR8 frames: its frames are gathered into the unit's image (one extra read and write of every byte).
+ *
+ * Error codes and state rules (idle matcher, tickets in order, kept frames ended by an upload) are those of the contiguous twin;
+ * arguments behind `list` are the twin's.  slideo_match_frames_submit_list and slideo_match_changed_frames_submit_list take device
+ * lists (a host list: SLIDEO_ERR_INVALID_ARG, as the contiguous submit has no host form); the existing collect calls collect them.
+ * slideo_matcher_gate_reset_from_frame_list takes a list of one.  The group forms take host lists; shards are sub-ranges of the
+ * array, and a later shard is primed from the list entry before its block.  The tap returns the BGR image at source size (without
+ * working size, region or levels) of every frame, back to back at row stride 3 * width: the list counterpart of
+ * slideo_yuv420_to_bgr8 / slideo_pixels_to_bgr8. */
+#define SLIDEO_FRAME_LIST_BGR 0   /* read like the *_bgr8 calls: under the matcher's pixel format */
+#define SLIDEO_FRAME_LIST_YUV 1   /* read like the *_yuv420 calls: description, sampling, chroma filter, transfer */
+typedef struct slideo_frame_list {
+    int32_t door, on_device, n_frames, width, height, uv_step;
+    int64_t stride[3];               /* bytes between rows of the plane at planes[3i+k] */
+    const void* const* planes;       /* HOST array of n_frames x 3 addresses (host or device memory by on_device) */
+} slideo_frame_list;                 /* 56 bytes */
+
+int32_t     slideo_match_frames_list(slideo_matcher* m, const slideo_frame_list* list, slideo_verdict* verdicts_out, void* hip_stream);
+int32_t     slideo_match_frames_submit_list(slideo_matcher* m, const slideo_frame_list* list, void* hip_stream, int64_t* ticket_out);
+int32_t     slideo_match_changed_frames_list(slideo_matcher* m, const slideo_frame_list* list, uint8_t* changed_out, float* similarity_out,
+                                             slideo_verdict* verdicts_out, void* hip_stream);
+int32_t     slideo_match_changed_frames_submit_list(slideo_matcher* m, const slideo_frame_list* list, void* hip_stream, int64_t* ticket_out);
+int32_t     slideo_changed_mask_list(slideo_matcher* m, const slideo_frame_list* list, const uint8_t* prev_small, uint8_t* last_small_out,
+                                     uint8_t* changed_out, float* similarity_out);
+int32_t     slideo_matcher_observe_frames_list(slideo_matcher* m, const slideo_frame_list* list, void* hip_stream);
+int32_t     slideo_matcher_gate_reset_from_frame_list(slideo_matcher* m, const slideo_frame_list* list, void* hip_stream);
+int32_t     slideo_group_match_frames_list(slideo_group* g, const slideo_frame_list* list, slideo_verdict* verdicts_out);
+int32_t     slideo_group_match_changed_frames_list(slideo_group* g, const slideo_frame_list* list, uint8_t* changed_out, float* similarity_out,
+                                                   slideo_verdict* verdicts_out);
+int32_t     slideo_group_changed_mask_list(slideo_group* g, const slideo_frame_list* list, const uint8_t* prev_small, uint8_t* last_small_out,
+                                           uint8_t* changed_out, float* similarity_out);
+/* Tap: out_capacity >= n_frames * width * height * 3. */
+int32_t     slideo_frame_list_to_bgr8(slideo_matcher* m, const slideo_frame_list* list, uint8_t* bgr_out, int64_t out_capacity);
+
 #ifdef __cplusplus
 }
 #endif

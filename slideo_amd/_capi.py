@@ -302,6 +302,103 @@ def _yuv_frames(frames, w, h, layout):
     return frames, layout, frames.shape[1]
 
 
+# ---- frame lists (include/slideo_amd.h "Frame lists") ---------------------------------------------------------------------------------
+FRAME_LIST_BGR = 0
+FRAME_LIST_YUV = 1
+FRAME_LIST_DOORS = {"bgr": FRAME_LIST_BGR, "yuv": FRAME_LIST_YUV}
+
+
+class FrameListRec(C.Structure):
+    """slideo_frame_list (56 bytes)."""
+    _fields_ = [("door", C.c_int32), ("on_device", C.c_int32), ("n_frames", C.c_int32), ("width", C.c_int32), ("height", C.c_int32),
+                ("uv_step", C.c_int32), ("stride", C.c_int64 * 3), ("planes", C.c_void_p)]
+
+
+class FrameList:
+    """A slideo_frame_list record with its `planes` array, and the frames themselves kept alive (frame_list builds it)."""
+
+    def __init__(self, rec, table, keep):
+        self.rec, self.table, self.keep = rec, table, keep
+
+    n = property(lambda self: self.rec.n_frames)
+    width = property(lambda self: self.rec.width)
+    height = property(lambda self: self.rec.height)
+
+    def ref(self):
+        return C.cast(C.byref(self.rec), C.c_void_p)
+
+
+def _plane_of(a):
+    """(address, bytes between rows, on_device, bytes per element) of one plane: a numpy array or a tensor whose rows are contiguous."""
+    if isinstance(a, np.ndarray):
+        if a.ndim < 1 or any(a.strides[i] != a.strides[i + 1] * a.shape[i + 1] for i in range(1, a.ndim - 1)) or a.strides[-1] != a.itemsize:
+            raise ValueError("frame_list: the rows of a plane must be contiguous (strides %s of shape %s)" % (a.strides, a.shape))
+        return a.ctypes.data, (a.strides[0] if a.ndim > 1 else a.nbytes), False, a.itemsize
+    if hasattr(a, "data_ptr"):                                     # a torch tensor, host or device
+        es = a.element_size()
+        if a.dim() < 1 or a.stride(-1) != 1 or any(a.stride(i) != a.stride(i + 1) * a.shape[i + 1] for i in range(1, a.dim() - 1)):
+            raise ValueError("frame_list: the rows of a plane must be contiguous (strides %s of shape %s)" % (a.stride(), tuple(a.shape)))
+        return a.data_ptr(), (a.stride(0) * es if a.dim() > 1 else a.numel() * es), bool(a.is_cuda), es
+    raise TypeError("frame_list: a plane is a numpy array or a tensor, got %r" % type(a))
+
+
+def frame_list(frames, door="bgr", width=None, height=None, chroma=None, planar=False, bps=None):
+    """The record of a frame list from a sequence of frames, each a numpy array or a tensor (one plane) or a tuple of planes, all in
+    host memory or all in device memory; the frames are kept alive by the returned FrameList.
+      door "bgr", packed formats   a frame is [h, w, 3] or [h, w, 4]
+      door "bgr", planar=True      a frame is [3, h, w], or a tuple of three [h, w] planes
+      door "yuv", chroma None      a frame is (Y, U, V)
+      door "yuv", chroma "uv"/"vu" a frame is (Y, C) with interleaved chroma in that order
+      door "yuv", chroma "yuy2" .. a frame is one packed 4:2:2 plane [h, 2 w]
+    width, height: needed through the YUV door (the BGR door reads them off the first frame).  Row strides come from the arrays and
+    must agree between frames.  bps: the bytes per sample of interleaved chroma (default: the plane's element size, so uint8 arrays
+    that hold 16-bit containers need bps=2)."""
+    door_v = FRAME_LIST_DOORS[door] if isinstance(door, str) else int(door)
+    frames = list(frames)
+    n = len(frames)
+    table = (C.c_void_p * max(3 * n, 1))()
+    strides, on_dev, uv_step = None, None, 0
+    for i, f in enumerate(frames):
+        planes = list(f) if isinstance(f, (tuple, list)) else [f]
+        if door_v == FRAME_LIST_BGR and planar and len(planes) == 1:
+            planes = [planes[0][c] for c in range(3)]
+        got = [_plane_of(p) for p in planes]
+        addr = [g[0] for g in got] + [0] * (3 - len(got))
+        st = [g[1] for g in got] + [0] * (3 - len(got))
+        if door_v == FRAME_LIST_YUV:
+            if chroma in ("uv", "vu"):
+                if len(got) != 2:
+                    raise ValueError("frame_list: interleaved chroma takes (Y, C) frames")
+                bps = int(bps or got[1][3])
+                addr = [addr[0], addr[1] + (bps if chroma == "vu" else 0), addr[1] + (bps if chroma == "uv" else 0)]
+                st, uv_step = [st[0], st[1], st[1]], 2
+            elif chroma is not None:
+                if len(got) != 1:
+                    raise ValueError("frame_list: packed 4:2:2 frames are one plane")
+                u, v = YUV_PACKED_OFFSETS[chroma]
+                addr, st, uv_step = [addr[0], addr[0] + u, addr[0] + v], [st[0]] * 3, 4
+            else:
+                if len(got) != 3:
+                    raise ValueError("frame_list: planar YUV frames are (Y, U, V)")
+                uv_step = 1
+        elif i == 0 and width is None:
+            shp = tuple(planes[0].shape)
+            height, width = (shp[0], shp[1])
+        if any(g[2] != got[0][2] for g in got) or (on_dev is not None and got[0][2] != on_dev):
+            raise ValueError("frame_list: host and device memory in one list")
+        on_dev = got[0][2]
+        if strides is not None and st != strides:
+            raise ValueError("frame_list: frame %d has row strides %s, frame 0 has %s (one stride per plane for the whole list)" % (i, st, strides))
+        strides = st
+        for k in range(3):
+            table[3 * i + k] = addr[k] or None
+    if width is None or height is None:
+        raise ValueError("frame_list: width and height are needed")
+    rec = FrameListRec(door_v, int(bool(on_dev)), n, int(width), int(height), uv_step, (C.c_int64 * 3)(*(strides or [0, 0, 0])),
+                       C.cast(table, C.c_void_p))
+    return FrameList(rec, table, frames)
+
+
 def sift_config(**over):
     c = SiftConfig()
     lib().slideo_sift_config_default(C.byref(c))
@@ -386,6 +483,10 @@ EXPORTS = [
     "slideo_evidence_mask", "slideo_evidence_box", "slideo_matcher_rng_stream_len",
     "slideo_matcher_tone_begin", "slideo_matcher_tone_end", "slideo_matcher_tone_info", "slideo_matcher_tone_counts",
     "slideo_group_tone_begin", "slideo_group_tone_end", "slideo_group_tone_info", "slideo_group_tone_counts", "slideo_tone_lut",
+    "slideo_match_frames_list", "slideo_match_frames_submit_list", "slideo_match_changed_frames_list",
+    "slideo_match_changed_frames_submit_list", "slideo_changed_mask_list", "slideo_matcher_observe_frames_list",
+    "slideo_matcher_gate_reset_from_frame_list", "slideo_group_match_frames_list", "slideo_group_match_changed_frames_list",
+    "slideo_group_changed_mask_list", "slideo_frame_list_to_bgr8",
 ]
 
 # frame mask scope (include/slideo_amd.h "Frame mask scope")
@@ -468,6 +569,19 @@ def lib():
             L.slideo_group_gate_last_small.argtypes = [vp, vp, i64, vp, vp]
             L.slideo_group_match_changed_frames_bgr8.argtypes = [vp, i32, vp, i32, i32, i32, i64, vp, vp, vp]
             L.slideo_group_match_changed_frames_yuv420.argtypes = [vp, i32, vp, i32, i32, vp, i64, vp, vp, vp]
+        if hasattr(L, "slideo_match_frames_list"):                 # ("Frame lists")
+            vp, i64 = C.c_void_p, C.c_int64
+            L.slideo_match_frames_list.argtypes = [vp, vp, vp, vp]
+            L.slideo_match_frames_submit_list.argtypes = [vp, vp, vp, vp]
+            L.slideo_match_changed_frames_list.argtypes = [vp, vp, vp, vp, vp, vp]
+            L.slideo_match_changed_frames_submit_list.argtypes = [vp, vp, vp, vp]
+            L.slideo_changed_mask_list.argtypes = [vp, vp, vp, vp, vp, vp]
+            L.slideo_matcher_observe_frames_list.argtypes = [vp, vp, vp]
+            L.slideo_matcher_gate_reset_from_frame_list.argtypes = [vp, vp, vp]
+            L.slideo_group_match_frames_list.argtypes = [vp, vp, vp]
+            L.slideo_group_match_changed_frames_list.argtypes = [vp, vp, vp, vp, vp]
+            L.slideo_group_changed_mask_list.argtypes = [vp, vp, vp, vp, vp, vp]
+            L.slideo_frame_list_to_bgr8.argtypes = [vp, vp, vp, i64]
         if hasattr(L, "slideo_matcher_set_frame_mask"):
             vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
             L.slideo_matcher_set_frame_mask.argtypes = [vp, vp, i32, i32, i32]
@@ -673,8 +787,22 @@ class _FrameCalls:
         stride = stride or w * bpp
         return stride, frame_stride or planes * stride * h
 
+    def _separate(self, frames):
+        """A list or tuple of separate host frames in the array shape of the pixel format in force -> their FrameList ("Frame
+        lists": no copy into one batch); anything else -> None (the contiguous call)."""
+        if not isinstance(frames, (list, tuple)) or not frames or not all(isinstance(f, np.ndarray) and f.dtype == np.uint8 and f.ndim == 3 for f in frames):
+            return None
+        bpp, planes = pixel_format_info(self.pixel_format())
+        if any(f.shape != frames[0].shape or (f.shape[0] != 3 if planes == 3 else f.shape[2] != bpp) for f in frames):
+            return None
+        return frame_list([np.ascontiguousarray(f) for f in frames], "bgr", planar=planes == 3)
+
     def match_frames(self, frames):
-        """frames: uint8 [n, h, w, 3] in host memory (the array shape of the pixel format in force) -> verdict records."""
+        """frames: uint8 [n, h, w, 3] in host memory (the array shape of the pixel format in force) -> verdict records.  A list of
+        separate frame arrays goes as a frame list."""
+        fl = self._separate(frames)
+        if fl is not None:
+            return self.match_frames_list(fl)
         frames, n, w, h, st, fs = self._pix_frames(frames, "match_frames")
         out = np.zeros(n, VERDICT_DTYPE)
         self._call("match_frames_bgr8", n, _p(frames), w, h, st, C.c_int64(fs), _p(out))
@@ -735,6 +863,9 @@ class _FrameCalls:
         return cands[: n.value].copy()
 
     def changed_mask(self, frames, prev_small=None):
+        fl = self._separate(frames)
+        if fl is not None:
+            return self.changed_mask_list(fl, prev_small)
         frames, n, w, h, st, fs = self._pix_frames(frames, "changed_mask")
         return self._mask("changed_mask_bgr8", n, w, h, prev_small, _p(frames), w, h, st, C.c_int64(fs))
 
@@ -759,6 +890,30 @@ class _FrameCalls:
         if prev_small is not None:
             prev_small = np.ascontiguousarray(prev_small, np.uint8)
         self._call(name, n, *frame_args, _p(prev_small), _p(last), _p(changed), _p(sims))
+        return changed.astype(bool), sims, last
+
+    # ---- frame lists (include/slideo_amd.h "Frame lists"): fl is a FrameList (frame_list); a Group takes host lists -------------
+    def _list_stream(self, stream):
+        return () if self._PREFIX == "slideo_group_" else (C.c_void_p(stream or None),)
+
+    def match_frames_list(self, fl, stream=0):
+        out = np.zeros(fl.n, VERDICT_DTYPE)
+        self._call("match_frames_list", fl.ref(), _p(out), *self._list_stream(stream))
+        return out
+
+    def match_changed_frames_list(self, fl, stream=0):
+        ch, sim, out = self._gated_out(fl.n)
+        self._call("match_changed_frames_list", fl.ref(), _p(ch), _p(sim), _p(out), *self._list_stream(stream))
+        return ch.astype(bool), sim, out
+
+    def changed_mask_list(self, fl, prev_small=None):
+        """-> (changed [n] bool, similarity [n] f32, the last frame's small image); match_kept_frames follows as it does changed_mask."""
+        changed, sims = np.zeros(fl.n, np.uint8), np.zeros(fl.n, np.float32)
+        sw, sh = small_size(*self._unit_size(fl.width, fl.height), self.cfg.small_area)
+        last = np.zeros((sh, sw, 3), np.uint8)
+        if prev_small is not None:
+            prev_small = np.ascontiguousarray(prev_small, np.uint8)
+        self._call("changed_mask_list", fl.ref(), _p(prev_small), _p(last), _p(changed), _p(sims))
         return changed.astype(bool), sims, last
 
     def match_kept_frames(self, sel):
@@ -809,7 +964,10 @@ class _FrameCalls:
         return np.zeros(n, np.uint8), np.zeros(n, np.float32), np.zeros(n, VERDICT_DTYPE)
 
     def match_changed_frames(self, frames):
-        """frames: uint8 [n, h, w, 3] in host memory, continuing the gate."""
+        """frames: uint8 [n, h, w, 3] in host memory, continuing the gate.  A list of separate frame arrays goes as a frame list."""
+        fl = self._separate(frames)
+        if fl is not None:
+            return self.match_changed_frames_list(fl)
         frames, n, w, h, st, fs = self._pix_frames(frames, "match_changed_frames")
         ch, sim, out = self._gated_out(n)
         self._call("match_changed_frames_bgr8", n, _p(frames), w, h, st, C.c_int64(fs), _p(ch), _p(sim), _p(out))
@@ -1291,6 +1449,31 @@ class Matcher(_FrameCalls):
         self._check(lib().slideo_match_frames_bgr8_dev(self._h, n, C.c_void_p(dev_ptr), w, h, stride,
                                                        C.c_int64(frame_stride), _p(out),
                                                        C.c_void_p(stream)))
+        return out
+
+    # ---- frame lists: the forms a single matcher has beyond _FrameCalls' ----
+    def submit_list(self, fl, stream=0):
+        """Streaming form of a DEVICE list: a ticket for collect.  The record is copied at the call; the frames stay valid until collect."""
+        t = C.c_int64()
+        self._check(lib().slideo_match_frames_submit_list(self._h, fl.ref(), C.c_void_p(stream or None), C.byref(t)))
+        return (t.value, fl.n)
+
+    def submit_changed_list(self, fl, stream=0):
+        t = C.c_int64()
+        self._check(lib().slideo_match_changed_frames_submit_list(self._h, fl.ref(), C.c_void_p(stream or None), C.byref(t)))
+        return (t.value, fl.n)
+
+    def observe_frames_list(self, fl, stream=0):
+        self._check(lib().slideo_matcher_observe_frames_list(self._h, fl.ref(), C.c_void_p(stream or None)))
+
+    def gate_reset_from_frame_list(self, fl, stream=0):
+        """The gate state from a list of one frame."""
+        self._check(lib().slideo_matcher_gate_reset_from_frame_list(self._h, fl.ref(), C.c_void_p(stream or None)))
+
+    def frame_list_to_bgr8(self, fl):
+        """Tap: the BGR image at source size of every frame of the list -> uint8 [n, h, w, 3]."""
+        out = np.zeros((fl.n, fl.height, fl.width, 3), np.uint8)
+        self._check(lib().slideo_frame_list_to_bgr8(self._h, fl.ref(), _p(out), C.c_int64(out.size)))
         return out
 
     def rng_stream_len(self):

@@ -619,6 +619,39 @@ int32_t slideo_group_match_frames_yuv420(slideo_group* g, int32_t n_frames, cons
     GROUP_CATCH(g)
 }
 
+// ---- Frame lists (include/slideo_amd.h "Frame lists"): host lists; a shard is a sub-range of the array (FrameSrc::from) --------------
+static FrameSrc group_list_src(slideo_group* g, const slideo_frame_list* list) {
+    FrameSrc src = FrameSrc::from_list(list, g->members[0]->fs);
+    if (src.on_device) fail(SLIDEO_ERR_INVALID_ARG, "frame list: the group's forms take host lists (on_device 0)");
+    return src;
+}
+
+int32_t slideo_group_match_frames_list(slideo_group* g, const slideo_frame_list* list, slideo_verdict* verdicts_out) {
+    if (!g) return SLIDEO_ERR_INVALID_ARG;
+    GROUP_TRY
+    const FrameSrc src = group_list_src(g, list);
+    group_match_impl(g, list->n_frames, src, verdicts_out);
+    GROUP_CATCH(g)
+}
+
+int32_t slideo_group_changed_mask_list(slideo_group* g, const slideo_frame_list* list, const uint8_t* prev_small, uint8_t* last_small_out,
+                                       uint8_t* changed_out, float* similarity_out) {
+    if (!g) return SLIDEO_ERR_INVALID_ARG;
+    GROUP_TRY
+    const FrameSrc src = group_list_src(g, list);
+    group_mask_impl(g, list->n_frames, src, prev_small, last_small_out, changed_out, similarity_out);
+    GROUP_CATCH(g)
+}
+
+int32_t slideo_group_match_changed_frames_list(slideo_group* g, const slideo_frame_list* list, uint8_t* changed_out, float* similarity_out,
+                                               slideo_verdict* verdicts_out) {
+    if (!g) return SLIDEO_ERR_INVALID_ARG;
+    GROUP_TRY
+    const FrameSrc src = group_list_src(g, list);
+    group_gated_impl(g, list->n_frames, src, changed_out, similarity_out, verdicts_out);
+    GROUP_CATCH(g)
+}
+
 int32_t slideo_group_last_frame_candidates(const slideo_group* g, int32_t frame_in_batch, slideo_candidate* out, int32_t capacity, int32_t* n_out) {
     if (!g || !n_out || g->match_lo.empty()) return SLIDEO_ERR_INVALID_ARG;
     for (size_t r = 0; r + 1 < g->match_lo.size(); ++r)

@@ -105,6 +105,33 @@ void validate_frames(FrameSrc& src, slideo_matcher* m, int n, const void* out) {
     if (m) resolve_frames(m, src, true);
     if (m && !src.converted() && src.frame_stride < (int64_t)src.h * src.stride) fail(SLIDEO_ERR_INVALID_ARG, "frame_stride smaller than one frame");
     src.pinned = !src.on_device && src.p && host_is_pinned(src.p);
+    // (a list counts as pinned iff every frame's first plane is)
+    if (src.list && src.pinned)
+        for (int i = 1; i < src.list_count() && src.pinned; ++i) src.pinned = host_is_pinned(src.list_planes(i)[0]);
+}
+
+// A list's frames [first, first + n) into the plan's staged layout at dst (frames P.frame_bytes apart).  Host lists: one copy per
+// plane on st — one span where the plane's stride is its row bytes, else one 2-D copy; interleaved chroma from the lower of the U and
+// V addresses.  Device lists: the unit's addresses into the slot's table, then frame_gather_kernel on the slot's stream.
+static void stage_list(Slot& S, const FrameSrc& src, int first, int n, uint8_t* dst, hipStream_t st) {
+    const FrameListPlan& P = src.list->plan;
+    const uint8_t* const* a = src.list_planes(first);
+    if (src.on_device) {
+        S.u_list = src.list;                            // (the addresses stay the library's until the slot's next list unit)
+        S.d_ltab.reserve((size_t)n * 3 * sizeof(void*) + 16);
+        // (the library's copy of the addresses is pageable: the runtime has staged it when the call returns)
+        HIP_CHECK(hipMemcpyAsync(S.d_ltab.p, a, (size_t)n * 3 * sizeof(void*), hipMemcpyHostToDevice, S.st));
+        launch_frame_gather(P, S.d_ltab.as<const uint8_t*>(), n, dst, S.st);
+        return;
+    }
+    for (int i = 0; i < n; ++i)
+        for (int j = 0; j < P.n_planes; ++j) {
+            const uint8_t* s = a[3 * (size_t)i + P.k[j]];
+            uint8_t* d = dst + P.frame_bytes * i + P.dst_ofs[j];
+            const size_t rb = (size_t)P.row_bytes[j];
+            if (P.src_stride[j] == P.row_bytes[j]) HIP_CHECK(hipMemcpyAsync(d, s, rb * (size_t)P.rows[j], hipMemcpyHostToDevice, st));
+            else HIP_CHECK(hipMemcpy2DAsync(d, rb, s, (size_t)P.src_stride[j], rb, (size_t)P.rows[j], hipMemcpyHostToDevice, st));
+        }
 }
 
 // prep, unit size and small size: the frame region, else the working size (the region's output fits it: the set calls' rule)
@@ -187,7 +214,7 @@ uint8_t* stage_for_upload(slideo_matcher* m, Slot& S, size_t bytes) {
 }
 
 DevFrames stage_frames(slideo_matcher* m, Slot& S, const FrameSrc& src, int first, int n, hipStream_t cs, DevBuf* into) {
-    const uint8_t* p = src.p + (int64_t)first * src.frame_stride;
+    const uint8_t* p = src.list ? nullptr : src.p + (int64_t)first * src.frame_stride;
     const FramePlan& P = src.plan;      // (a tap's unresolved plan is PREP_NONE: uw, uh are read under `pre` alone)
     const bool pre = P.prep != PREP_NONE;                        // a kernel stands between the BGR view at source size and the unit's image
     if (src.on_device && !src.kernel_in_front()) return DevFrames{p, src.w, src.h, src.stride, src.frame_stride};
@@ -198,7 +225,18 @@ DevFrames stage_frames(slideo_matcher* m, Slot& S, const FrameSrc& src, int firs
     if (into) { into->reserve((size_t)ub * n + 16); stage = into->as<uint8_t>(); }
     else stage = stage_for_upload(m, S, (size_t)ub * n);
     int64_t fs = src.frame_stride;
-    if (!src.on_device) {
+    if (src.list) {
+        // a frame list, host or device: into the staged layout where a host frame's upload goes, and a host-frame unit from there on
+        uint8_t* dst = stage;
+        fs = src.list->plan.frame_bytes;                // (a single frame's frame_stride may be -1)
+        if (src.converted() || pre) { S.d_yuv.reserve((size_t)fs * n + 16); dst = S.d_yuv.as<uint8_t>(); }
+        stage_list(S, src, first, n, dst, !src.on_device && cs ? cs : S.st);
+        if (!src.on_device && cs) {
+            HIP_CHECK(hipEventRecord(S.ev_up, cs));
+            HIP_CHECK(hipStreamWaitEvent(S.st, S.ev_up, 0));
+        }
+        p = dst;
+    } else if (!src.on_device) {
         // host frames back to back into d_stage, or into d_yuv for the conversion / the reduce / the rectify below
         const int64_t bytes = src.converted() ? src.src_span() : fb;
         uint8_t* dst = stage;
@@ -1400,6 +1438,83 @@ int32_t slideo_yuv_layout_packed(int32_t format, int32_t w, int32_t h, int32_t b
     }
     *out = L;
     return SLIDEO_OK;
+}
+
+// ---- Frame lists (include/slideo_amd.h "Frame lists"): each form fills a FrameSrc and calls its contiguous twin's driver ------------
+
+int32_t slideo_match_frames_list(slideo_matcher* m, const slideo_frame_list* list, slideo_verdict* verdicts_out, void* hip_stream) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    const FrameSrc src = FrameSrc::from_list(list, m->fs);
+    match_frames_impl(m, list->n_frames, src, verdicts_out, reinterpret_cast<hipStream_t>(hip_stream));
+    API_CATCH(m)
+}
+
+// the submit forms take device lists, as the contiguous submit has no host form
+static FrameSrc submit_list_src(slideo_matcher* m, const slideo_frame_list* list) {
+    FrameSrc src = FrameSrc::from_list(list, m->fs);
+    if (!src.on_device) fail(SLIDEO_ERR_INVALID_ARG, "frame list: a submit form takes device lists (on_device 1); host lists go through the synchronous form");
+    return src;
+}
+
+int32_t slideo_match_frames_submit_list(slideo_matcher* m, const slideo_frame_list* list, void* hip_stream, int64_t* ticket_out) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    const FrameSrc src = submit_list_src(m, list);
+    submit_impl(m, list->n_frames, src, hip_stream, ticket_out, false);
+    API_CATCH(m)
+}
+
+int32_t slideo_match_changed_frames_list(slideo_matcher* m, const slideo_frame_list* list, uint8_t* changed_out, float* similarity_out,
+                                         slideo_verdict* verdicts_out, void* hip_stream) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    const FrameSrc src = FrameSrc::from_list(list, m->fs);
+    match_frames_impl(m, list->n_frames, src, verdicts_out, reinterpret_cast<hipStream_t>(hip_stream), true, changed_out, similarity_out);
+    API_CATCH(m)
+}
+
+int32_t slideo_match_changed_frames_submit_list(slideo_matcher* m, const slideo_frame_list* list, void* hip_stream, int64_t* ticket_out) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    const FrameSrc src = submit_list_src(m, list);
+    submit_impl(m, list->n_frames, src, hip_stream, ticket_out, true);
+    API_CATCH(m)
+}
+
+int32_t slideo_changed_mask_list(slideo_matcher* m, const slideo_frame_list* list, const uint8_t* prev_small, uint8_t* last_small_out,
+                                 uint8_t* changed_out, float* similarity_out) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    const FrameSrc src = FrameSrc::from_list(list, m->fs);
+    changed_mask_impl(m, list->n_frames, src, prev_small, last_small_out, changed_out, similarity_out);
+    API_CATCH(m)
+}
+
+// Tap: the BGR image at source size of every frame of the list (no working size, region or levels), back to back at stride 3 * width
+int32_t slideo_frame_list_to_bgr8(slideo_matcher* m, const slideo_frame_list* list, uint8_t* bgr_out, int64_t out_capacity) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    FrameSrc img = FrameSrc::from_list(list, m->fs);
+    if (list->n_frames > 0 && !bgr_out) fail(SLIDEO_ERR_INVALID_ARG, "null bgr_out");
+    img.describe(m->fs);
+    img.levels = false;                             // (the conversion's image: the frame levels come behind it, slideo_levels_bgr8)
+    validate_frames(img);
+    const int n = list->n_frames;
+    const size_t fb = (size_t)list->width * list->height * 3;
+    if ((int64_t)(fb * (size_t)n) > out_capacity) fail(SLIDEO_ERR_CAPACITY, "the BGR images need %zu bytes", fb * (size_t)n);
+    if (n == 0) return SLIDEO_OK;
+    HIP_CHECK(hipSetDevice(m->device));
+    require_idle(m);
+    Slot& S = m->slots[0];
+    const int block = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, ((size_t)64 << 20) / fb));
+    for (int i = 0; i < n; i += block) {
+        const int nb = std::min(block, n - i);
+        const DevFrames f = stage_frames(m, S, img, i, nb);
+        HIP_CHECK(hipMemcpyAsync(bgr_out + fb * (size_t)i, f.p, fb * (size_t)nb, hipMemcpyDeviceToHost, S.st));
+        HIP_CHECK(hipStreamSynchronize(S.st));
+    }
+    API_CATCH(m)
 }
 
 int32_t slideo_match_frames_yuv420(slideo_matcher* m, int32_t n_frames, const uint8_t* frames, int32_t width, int32_t height,

@@ -664,6 +664,118 @@ inline int64_t yuv_sampled_validate(int w, int h, const slideo_yuv420_layout* L,
     return span;
 }
 
+// ---- frame lists (include/slideo_amd.h "Frame lists") ---------------------------------------------------------------------------------
+// What a list's frames become in the library's own memory, the same for host and device lists: per frame `frame_bytes` bytes, staged
+// plane j (n_planes of them) holding rows[j] rows of row_bytes[j] bytes packed tight at dst_ofs[j], read from the address
+// planes[3i + k[j]] at rows src_stride[j] apart.  Interleaved chroma is ONE staged plane from the lower of the U and V addresses.
+// The staged frames are what the contiguous twin takes: `yuv` (YUV door: the tight layout of the format class) or rows `stride`
+// apart (BGR door; planar formats: every plane's), frames frame_bytes apart.
+struct FrameListPlan {
+    bool yuv_door = false;
+    int n_planes = 0;
+    int k[3] = {0, 0, 0}, rows[3] = {0, 0, 0};
+    int64_t row_bytes[3] = {0, 0, 0}, src_stride[3] = {0, 0, 0}, dst_ofs[3] = {0, 0, 0};
+    int64_t frame_bytes = 0;
+    slideo_yuv420_layout yuv{};
+    int stride = 0;
+};
+
+// The one host-side planning function of a list: every rule of "Frame lists" (each names itself), then the plan.  Nothing is written
+// anywhere.  yuv, pixel_format: the matcher's (the list's door picks which is read).
+inline FrameListPlan frame_list_plan(const slideo_frame_list* L, const YuvDesc& yuv, int pixel_format) {
+    if (!L) fail(SLIDEO_ERR_INVALID_ARG, "frame list: null record");
+    if (L->door != SLIDEO_FRAME_LIST_BGR && L->door != SLIDEO_FRAME_LIST_YUV)
+        fail(SLIDEO_ERR_INVALID_ARG, "frame list: door %d is neither SLIDEO_FRAME_LIST_BGR (0) nor SLIDEO_FRAME_LIST_YUV (1)", L->door);
+    if (L->on_device != 0 && L->on_device != 1) fail(SLIDEO_ERR_INVALID_ARG, "frame list: on_device %d is neither 0 (host) nor 1 (device)", L->on_device);
+    if (L->n_frames < 0) fail(SLIDEO_ERR_INVALID_ARG, "frame list: n_frames %d is negative", L->n_frames);
+    if (L->n_frames > 0 && !L->planes) fail(SLIDEO_ERR_INVALID_ARG, "frame list: null planes array");
+    const int w = L->width, h = L->height, n = L->n_frames;
+    const uint8_t* const* A = reinterpret_cast<const uint8_t* const*>(L->planes);
+    FrameListPlan P;
+    P.yuv_door = L->door == SLIDEO_FRAME_LIST_YUV;
+    int bps = 1;
+    bool paired = false;                             // interleaved or packed: stride[1], stride[2] repeat another plane's
+    if (P.yuv_door) {
+        bps = yuv.bytes_per_sample();
+        const bool packed = yuv.sampling == SLIDEO_YUV_SAMPLING_422_PACKED;
+        if (packed ? L->uv_step != 4 : (L->uv_step != 1 && L->uv_step != 2))
+            fail(SLIDEO_ERR_INVALID_ARG, "frame list: uv_step %d is not one the sampling %d has (%s)", L->uv_step, yuv.sampling,
+                 packed ? "4: one macropixel of two pixels" : "1: planar, 2: interleaved");
+        // the U / V order (interleaved) or the offset pair (packed) of the list: frame 0's, which every frame must repeat (below)
+        int64_t du = packed ? 1 : 0, dv = packed ? 3 : bps;
+        if (n > 0 && A[0] && A[1] && A[2]) {
+            if (packed) { du = A[1] - A[0]; dv = A[2] - A[0]; }
+            else if (L->uv_step == 2) { du = A[1] < A[2] ? 0 : bps; dv = A[1] < A[2] ? bps : 0; }
+        }
+        const int cw = yuv.sampling == SLIDEO_YUV_SAMPLING_444 ? w : w / 2, ch = yuv.sampling == SLIDEO_YUV_SAMPLING_420 ? h / 2 : h;
+        const int64_t luma = (int64_t)bps * w * h, chroma = (int64_t)bps * cw * ch;
+        slideo_yuv420_layout& T = P.yuv;
+        T.uv_step = L->uv_step;
+        if (packed) { T.y_stride = T.uv_stride = 2 * w; T.u_offset = du; T.v_offset = dv; }
+        else {
+            T.y_stride = bps * w; T.uv_stride = bps * cw * L->uv_step;
+            T.u_offset = L->uv_step == 2 ? luma + du : luma;
+            T.v_offset = L->uv_step == 2 ? luma + dv : luma + chroma;
+        }
+        // the door's size rules and image limits with their codes and messages (and, packed, its offset-pair rule) on the tight layout
+        P.frame_bytes = yuv420_validate(w, h, &T, -1, bps, yuv.sampling);
+        paired = packed || L->uv_step == 2;
+        P.n_planes = packed ? 1 : L->uv_step == 2 ? 2 : 3;
+        P.rows[0] = h; P.row_bytes[0] = packed ? (int64_t)2 * w : (int64_t)bps * w;
+        for (int j = 1; j < P.n_planes; ++j) {
+            P.k[j] = L->uv_step == 2 ? (du == 0 ? 1 : 2) : j;
+            P.rows[j] = ch; P.row_bytes[j] = (int64_t)bps * cw * L->uv_step;
+            P.dst_ofs[j] = luma + (j - 1) * chroma;
+        }
+    } else {
+        int bpp = 0, planes = 0;
+        if (!pixel_format_info(pixel_format, &bpp, &planes)) fail(SLIDEO_ERR_INVALID_ARG, "pixel format: %d is not a format", pixel_format);
+        if (w < 1 || h < 1) fail(SLIDEO_ERR_INVALID_ARG, "bad image geometry w=%d h=%d", w, h);
+        if ((int64_t)bpp * w > INT32_MAX) fail(SLIDEO_ERR_UNSUPPORTED, "image size %dx%d outside 1..%d", w, h, MAX_DIM);
+        P.stride = bpp * w;
+        P.n_planes = planes;
+        for (int j = 0; j < planes; ++j) { P.k[j] = j; P.rows[j] = h; P.row_bytes[j] = (int64_t)bpp * w; P.dst_ofs[j] = (int64_t)j * h * P.stride; }
+        P.frame_bytes = (int64_t)planes * h * P.stride;
+    }
+    // strides: of every plane the door reads
+    const int nread = P.yuv_door ? 3 : P.n_planes;
+    for (int k = 0; k < nread; ++k) {
+        const int j = paired ? (P.n_planes == 1 ? 0 : std::min(k, 1)) : k;       // the staged plane whose rows plane k's stride steps over
+        if (L->stride[k] < 0) fail(SLIDEO_ERR_INVALID_ARG, "frame list: stride[%d] %lld is negative (flipped frames are not supported)", k, (long long)L->stride[k]);
+        if (L->stride[k] < P.row_bytes[j])
+            fail(SLIDEO_ERR_INVALID_ARG, "frame list: stride[%d] %lld < the plane's row bytes %lld", k, (long long)L->stride[k], (long long)P.row_bytes[j]);
+        if (bps == 2 && (L->stride[k] & 1)) fail(SLIDEO_ERR_INVALID_ARG, "frame list: 16-bit containers need even strides (stride[%d] %lld)", k, (long long)L->stride[k]);
+    }
+    if (paired && L->stride[1] != L->stride[2])
+        fail(SLIDEO_ERR_INVALID_ARG, "frame list: %s chroma needs stride[1] == stride[2] (got %lld, %lld)", P.n_planes == 1 ? "packed" : "interleaved",
+             (long long)L->stride[1], (long long)L->stride[2]);
+    if (paired && P.n_planes == 1 && L->stride[1] != L->stride[0])
+        fail(SLIDEO_ERR_INVALID_ARG, "frame list: packed frames have one plane: stride[1] %lld is not stride[0] %lld", (long long)L->stride[1], (long long)L->stride[0]);
+    for (int j = 0; j < P.n_planes; ++j) P.src_stride[j] = L->stride[P.k[j]];
+    // addresses: of every frame
+    for (int i = 0; i < n; ++i) {
+        const uint8_t* const* a = A + 3 * (int64_t)i;
+        for (int k = 0; k < 3; ++k) {
+            if (k < nread && !a[k]) fail(SLIDEO_ERR_INVALID_ARG, "frame list: frame %d: plane %d is needed and NULL", i, k);
+            if (k >= nread && a[k]) fail(SLIDEO_ERR_INVALID_ARG, "frame list: frame %d: plane %d is not read under this format and not NULL", i, k);
+            if (bps == 2 && ((uintptr_t)a[k] & 1)) fail(SLIDEO_ERR_INVALID_ARG, "frame list: frame %d: 16-bit containers need even addresses (plane %d)", i, k);
+        }
+        if (!paired) continue;
+        if (P.n_planes == 1) {
+            if (a[1] - a[0] != P.yuv.u_offset || a[2] - a[0] != P.yuv.v_offset)
+                fail(SLIDEO_ERR_INVALID_ARG, "frame list: frame %d: packed planes at (%lld, %lld) past the frame, frame 0's valid pair is (%lld, %lld)", i,
+                     (long long)(a[1] - a[0]), (long long)(a[2] - a[0]), (long long)P.yuv.u_offset, (long long)P.yuv.v_offset);
+        } else {
+            const int64_t d = a[2] - a[1];
+            if (d != bps && d != -bps)
+                fail(SLIDEO_ERR_INVALID_ARG, "frame list: frame %d: interleaved chroma needs planes[3i+2] - planes[3i+1] == +-%d (got %lld)", i, bps, (long long)d);
+            if ((d > 0) != (P.k[1] == 1))
+                fail(SLIDEO_ERR_INVALID_ARG, "frame list: frame %d: interleaved chroma in another U / V order than frame 0's", i);
+        }
+    }
+    return P;
+}
+
 // ---- the rules between settings (SLIDEO_ERR_UNSUPPORTED), each once --------------------------------------------------------------
 // `next`: the settings in force with the proposed change of `what` applied.  The settings in force keep every rule, so the call
 // that would complete a refused combination fails, and the values before stay in force.

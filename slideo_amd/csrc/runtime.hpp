@@ -7,7 +7,7 @@
 //                      (FrameSrc -> FramePlan) and staged (-> DevFrames), unit submit / collect, the drivers of the frame calls
 //                      (pipeline, submit, collect: plain and gated) and their entry points
 //   stage_orb.hip      ORB stage drivers          (kernels: orb.hip.h, yuv420.hip.h, yuv_sampling.hip.h, pixel_format.hip.h, reduce.hip.h,
-//                                                 frame_region.hip.h, frame_mask.hip.h, levels.hip.h levels_kernel)
+//                                                 frame_region.hip.h, frame_mask.hip.h, levels.hip.h levels_kernel, frame_list.hip.h)
 //   stage_knn.hip      index build + k-NN stage   (kernels: knn.hip.h, knn_tile.hip.h, knn_l2.hip.h, knn_lsh.hip.h)
 //   stage_verify.hip   vote .. verdict, small img (kernels: verify.hip.h, homography.hip.h); the match evidence map's session, its
 //                      launch behind the verdicts and its entry points (kernel: evidence.hip.h); the match tone table's likewise (kernel: tone.hip.h)
@@ -97,6 +97,13 @@ struct FramePlan {
     }
 };
 
+// A frame list as the library keeps it (include/slideo_amd.h "Frame lists"): its own copy of the addresses, 3 per frame, and the plan
+// of its staged layout (frame_settings.h frame_list_plan, whose rules it passed)
+struct FrameListData {
+    std::vector<const uint8_t*> planes;
+    FrameListPlan plan;
+};
+
 // A call's frames as the caller handed them over: through the BGR door (yuv null; under the matcher's pixel format) or YUV in the
 // layout `yuv`, in host or device memory.
 // validate_frames checks them and fills the derived fields; stage_frames turns a block of them into a unit's BGR8 view.
@@ -123,6 +130,10 @@ struct FrameSrc {
     // (derived) the matcher's frame levels apply: the unit's image goes through the table as the last step (describe; analysed
     // frames are unit images already, levelled when they were kept)
     bool levels = false;
+    // a frame list: the frames are frames list_first .. of `list`, and p, stride, frame_stride and yuv describe the STAGED frames —
+    // what stage_frames leaves in the library's memory in front of everything else (p itself: the first frame's first plane)
+    std::shared_ptr<const FrameListData> list;
+    int list_first = 0;
 
     void describe(const FrameSettings& fs) {
         bps = fs.yuv.bytes_per_sample(); sampling = fs.yuv.sampling; chroma = fs.yuv.chroma;
@@ -134,7 +145,10 @@ struct FrameSrc {
     int64_t src_span() const { return yuv ? yuv_span : pix_span; }      // bytes of one frame a converter reads
     // a kernel stands in front of the unit's image (a converter, the reduce or the rectify, the levels): device frames are not the
     // unit's image as they lie in the caller's memory
-    bool kernel_in_front() const { return converted() || plan.prep != PREP_NONE || levels; }
+    // (a list's frames never are: they are gathered first)
+    bool kernel_in_front() const { return converted() || plan.prep != PREP_NONE || levels || list; }
+    // device frames a converter or a prep kernel reads out of the caller's memory; a list's are staged like a host frame's
+    bool in_place() const { return on_device && !list; }
 
     // per frame, the staging in front of the unit's BGR image: 1.5 B per pixel for 4:2:0 frames, 3 B in 16-bit containers, 2 * bps
     // under both 4:2:2 forms and 3 * bps under 4:4:4 ("YUV sampling"; BGR calls keep their unit sizes); under a pixel format a HOST
@@ -143,8 +157,10 @@ struct FrameSrc {
     // counts for every frame) or the gate staging;
     // a reducing or rectifying call: the uploaded source frame (host sources) and the source-sized BGR image of a 4:2:0 frame;
     // gated (a gated call, include/slideo_amd.h "Changed-frame gate"): + the gate staging — the BGR unit image of every frame that
-    // is not the caller's own device memory — and the frame's small image (gate_small: at most 3 * small_area bytes) and gate record
+    // is not the caller's own device memory — and the frame's small image (gate_small: at most 3 * small_area bytes) and gate record;
+    // a device frame list counts as a host frame does
     size_t staging_bytes(size_t gate_small = 0) const {
+        const bool on_device = in_place();
         const size_t px = (size_t)w * h;
         const bool pre = plan.prep != PREP_NONE;
         const size_t yb = (sampling == SLIDEO_YUV_SAMPLING_420 ? px * 3 / 2 : sampling == SLIDEO_YUV_SAMPLING_444 ? px * 3 : px * 2) * (size_t)bps;
@@ -165,7 +181,30 @@ struct FrameSrc {
     }
     static FrameSrc image(const uint8_t* p, int w, int h, int stride) { return bgr8(p, false, w, h, stride, (int64_t)h * stride); }   // one host image
     // the same frames from frame `first` on (a group member's shard)
-    FrameSrc from(int first) const { FrameSrc s = *this; s.p += (int64_t)first * frame_stride; return s; }
+    FrameSrc from(int first) const {
+        FrameSrc s = *this;
+        if (!list) { s.p += (int64_t)first * frame_stride; return s; }
+        s.list_first += first;
+        s.p = (size_t)s.list_first * 3 < list->planes.size() ? list->planes[(size_t)s.list_first * 3] : nullptr;
+        return s;
+    }
+    // a frame list under the settings fs: every rule of the list checked, the addresses copied (the caller's record and array are
+    // free again)
+    static FrameSrc from_list(const slideo_frame_list* L, const FrameSettings& fs) {
+        auto data = std::make_shared<FrameListData>();
+        data->plan = frame_list_plan(L, fs.yuv, fs.pixel_format);
+        const uint8_t* const* a = reinterpret_cast<const uint8_t* const*>(L->planes);
+        data->planes.assign(a, a + (size_t)L->n_frames * 3);
+        const FrameListPlan& P = data->plan;
+        FrameSrc s{L->n_frames > 0 ? a[0] : nullptr, L->on_device != 0, L->width, L->height};
+        s.frame_stride = P.frame_bytes;
+        if (P.yuv_door) s.yuv = &data->plan.yuv; else s.stride = P.stride;
+        s.list = std::move(data);
+        return s;
+    }
+    // the plane addresses of list frame `first` of the call (3 per frame)
+    const uint8_t* const* list_planes(int first) const { return list->planes.data() + (size_t)(list_first + first) * 3; }
+    int list_count() const { return (int)(list->planes.size() / 3) - list_first; }
 };
 
 // The BGR8 frames a unit's kernels read (device memory).
@@ -209,6 +248,8 @@ struct Slot {
     DevBuf d_items, d_kp, d_desc, d_keys, d_knn_pend, d_votes, d_gpts, d_gmask, d_fcs, d_verdicts, d_pairs, d_blurmask, d_qkeys, d_tail, d_refine;
     DevBuf d_yuv;              // host frames of the unit in front of d_stage: YUV 4:2:0 frames to convert, source-sized frames to reduce
                                // or rectify (reserved by the first YUV, reducing or rectifying call only)
+    DevBuf d_ltab;             // a device frame list's plane addresses of the unit (reserved by the first such unit only)
+    std::shared_ptr<const FrameListData> u_list;      // ... and the host copy they were uploaded from
     DevBuf d_full;             // the source-sized BGR image of 4:2:0 frames that are reduced or rectified (reserved by the first such call only)
     PinBuf h_info, h_out;
     OrbOut orb;
@@ -587,6 +628,9 @@ void launch_yuv420_to_bgr(const YuvDesc& desc, const uint8_t* src, int64_t src_f
 // n frames under the pixel format `format` (not SLIDEO_PIXEL_BGR8; a layout pixel_format_validate accepted, rows `stride` and frames
 // src_fs apart) -> BGR8 at dst, stride 3w, frame stride 3wh: pixels_to_bgr_kernel (pixel_format.hip.h)
 void launch_pixels_to_bgr(int format, const uint8_t* src, int64_t src_fs, int stride, int w, int h, int n, uint8_t* dst, hipStream_t st);
+// n frames of a device frame list (tab_dev: their 3n plane addresses in device memory) gathered into the plan's staged layout at dst,
+// frames P.frame_bytes apart: frame_gather_kernel (frame_list.hip.h)
+void launch_frame_gather(const FrameListPlan& P, const uint8_t* const* tab_dev, int n, uint8_t* dst, hipStream_t st);
 // n BGR8 images of w x h through the matcher's levels table (m->d_levels; fs.levels.set), src == dst with equal strides: in place:
 // levels_kernel (levels.hip.h)
 void launch_levels(slideo_matcher* m, const uint8_t* src, int64_t src_fs, int src_stride, uint8_t* dst, int64_t dst_fs, int dst_stride, int w, int h,

@@ -185,6 +185,14 @@ int32_t slideo_matcher_observe_frames_yuv420_dev(slideo_matcher* m, int32_t n_fr
     API_CATCH(m)
 }
 
+int32_t slideo_matcher_observe_frames_list(slideo_matcher* m, const slideo_frame_list* list, void* hip_stream) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    const FrameSrc src = FrameSrc::from_list(list, m->fs);
+    activity_observe(m, list->n_frames, src, reinterpret_cast<hipStream_t>(hip_stream));
+    API_CATCH(m)
+}
+
 // ---- the levels histogram (include/slideo_amd.h "Frame levels") -------------------------------------------------------------------
 
 int32_t slideo_matcher_levels_begin(slideo_matcher* m) {

@@ -332,6 +332,16 @@ int32_t slideo_matcher_gate_reset(slideo_matcher* m, const uint8_t* prev_small, 
     API_CATCH(m)
 }
 
+// a list of one (include/slideo_amd.h "Frame lists")
+int32_t slideo_matcher_gate_reset_from_frame_list(slideo_matcher* m, const slideo_frame_list* list, void* hip_stream) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    const FrameSrc src = FrameSrc::from_list(list, m->fs);
+    if (list->n_frames != 1) fail(SLIDEO_ERR_INVALID_ARG, "frame list: the gate is reset from a list of one frame (n_frames %d)", list->n_frames);
+    gate_prime(m, src, reinterpret_cast<hipStream_t>(hip_stream));
+    API_CATCH(m)
+}
+
 int32_t slideo_matcher_gate_reset_from_frame_bgr8(slideo_matcher* m, const uint8_t* frame, int32_t width, int32_t height, int32_t stride_bytes) {
     if (!m) return SLIDEO_ERR_INVALID_ARG;
     API_TRY

@@ -1,7 +1,8 @@
 // stage_orb.hip — drivers of the ORB stage (kernels: orb.hip.h) and of the front doors in front of it: YUV frames (one argument
 // record and one dispatch over the kernel families of yuv420.hip.h, yuv_sampling.hip.h, yuv_chroma.hip.h, yuv_transfer.hip.h), frames of
 // another pixel format (pixel_format.hip.h), the frame levels' table (levels.hip.h), the working-size reduce (reduce.hip.h) and the
-// frame region's rectify (frame_region.hip.h); the frame mask's pyramid and candidate filter (frame_mask.hip.h).
+// frame region's rectify (frame_region.hip.h); the frame mask's pyramid and candidate filter (frame_mask.hip.h); the gather of a device
+// frame list's planes (frame_list.hip.h).
 #include <type_traits>
 
 #include "runtime.hpp"
@@ -11,6 +12,7 @@
 #include "yuv_chroma.hip.h"
 #include "yuv_transfer.hip.h"
 #include "pixel_format.hip.h"
+#include "frame_list.hip.h"
 #define LEVELS_APPLY_KERNEL      // (levels_hist_kernel is stage_activity.hip's)
 #include "levels.hip.h"
 #include "reduce.hip.h"
@@ -163,6 +165,15 @@ void launch_pixels_to_bgr(int format, const uint8_t* src, int64_t src_fs, int st
     else if (form == PIX_PACKED4) pixels_to_bgr_kernel<PIX_PACKED4><<<grid, block, 0, st>>>(a);
     else pixels_to_bgr_kernel<PIX_PLANAR><<<grid, block, 0, st>>>(a);
     check_launch("pixels_to_bgr_kernel");
+}
+
+// n frames of a device frame list (tab_dev: their 3n plane addresses, device memory) -> the plan's staged layout at dst, frames
+// P.frame_bytes apart: what a host list's copies leave there
+void launch_frame_gather(const FrameListPlan& P, const uint8_t* const* tab_dev, int n, uint8_t* dst, hipStream_t st) {
+    const GatherArgs a = frame_gather_args(P, tab_dev, dst);
+    const dim3 grid(frame_gather_chunks(a), a.n_planes, n), block(GATHER_TX, GATHER_TY);
+    frame_gather_kernel<<<grid, block, 0, st>>>(a);
+    check_launch("frame_gather_kernel");
 }
 
 // n BGR8 images through the matcher's levels table; src == dst (and equal strides): in place

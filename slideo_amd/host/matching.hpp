@@ -345,6 +345,34 @@ public:
         reporter.report(0, (uint64_t)(video.total_time() / 5.0), "");                               // mo/lib.rs:148-150
         return std::make_unique<HipVideoMatcherTask<I>>(h_, images_, video_path, std::move(reporter), 0.98f);
     }
+    // Frame lists (include/slideo_amd.h "Frame lists"; an extension): a batch given as per-frame plane pointers — one cv::Mat or one
+    // AVFrame per frame — instead of one contiguous buffer.  Host lists; the results are the contiguous calls' bit for bit.
+    // bgr_frame_list: the record of n BGR-door frames, each its own buffer with rows `stride_bytes` apart (planes: 3 n entries, filled
+    // here and kept by the caller until the call returns).
+    static slideo_frame_list bgr_frame_list(const std::vector<const uint8_t*>& frames, int32_t width, int32_t height, int64_t stride_bytes,
+                                            std::vector<const void*>& planes) {
+        planes.assign(frames.size() * 3, nullptr);
+        for (size_t i = 0; i < frames.size(); ++i) planes[3 * i] = frames[i];
+        slideo_frame_list L{};
+        L.door = SLIDEO_FRAME_LIST_BGR; L.n_frames = (int32_t)frames.size(); L.width = width; L.height = height;
+        L.stride[0] = stride_bytes;
+        L.planes = planes.data();
+        return L;
+    }
+    std::vector<slideo_verdict> match_frames_list(const slideo_frame_list& list) {
+        std::vector<slideo_verdict> out((size_t)std::max(list.n_frames, 0));
+        h_->check(slideo_group_match_frames_list(h_->g, &list, out.data()));
+        return out;
+    }
+    // -> verdicts; changed [n] and similarity [n] (may be null) as slideo_group_match_changed_frames_bgr8 fills them
+    std::vector<slideo_verdict> match_changed_frames_list(const slideo_frame_list& list, uint8_t* changed, float* similarity = nullptr) {
+        std::vector<slideo_verdict> out((size_t)std::max(list.n_frames, 0));
+        h_->check(slideo_group_match_changed_frames_list(h_->g, &list, changed, similarity, out.data()));
+        return out;
+    }
+    void changed_mask_list(const slideo_frame_list& list, const uint8_t* prev_small, uint8_t* last_small_out, uint8_t* changed, float* similarity = nullptr) {
+        h_->check(slideo_group_changed_mask_list(h_->g, &list, prev_small, last_small_out, changed, similarity));
+    }
     // Match evidence map (include/slideo_amd.h "Match evidence map"; an extension): while a session is open, the tasks' match calls
     // count where the keypoints of matched frames fall (seen) and which of them the winning page's transform explains (hit), per
     // cell x cell cell of the analysed image, summed over the devices.  No task may be running at begin, counts or end.  The counts go

@@ -201,7 +201,9 @@ class HipVideoMatcherTask:
             nonlocal prev_small
             if not pend_frames:
                 return
-            stack = np.stack(pend_frames)
+            # BGR frames are separate arrays: a library handle takes them as they are, as a frame list ("Frame lists"), without the
+            # copy into one batch (_capi._FrameCalls._separate); YUV frames and other handles get the stacked batch
+            stack = pend_frames[:] if not yuv and isinstance(m, _capi._FrameCalls) else np.stack(pend_frames)
             if gate is not None:                       # MarkSimilarIter + match_images_with_frame of the changed frames, one call
                 if yuv:
                     changed, _, verdicts = gate.match_changed_frames_yuv420(stack, video.width, video.height, yuv)
@@ -231,7 +233,7 @@ class HipVideoMatcherTask:
                 elif yuv:
                     verdicts = m.match_frames_yuv420(stack[idx], video.width, video.height, yuv)
                 else:
-                    verdicts = m.match_frames(stack[idx])
+                    verdicts = m.match_frames(np.stack(pend_frames)[idx])
                 emit(idx, verdicts)
             for _ in pend_frames:
                 report_progress()
