@@ -4,7 +4,14 @@
  * CPU restatement of cv::SIFT::detectAndCompute of OpenCV 4.5.2 (features2d/src/sift.dispatch.cpp, sift.simd.hpp), RECALLED:
  * BASELINE configs[2] / north_star name "SIFT keypoint detect+describe", which the reference never calls (its only extractor is
  * ORB, crates/matching-opencv/src/feature_extractor.rs:3-4,13 — SURVEY F6, section 8(f) N4).  There is therefore no reference
- * call site, test or golden vector to anchor on: the parity target of the HIP extractor (csrc/sift.hip.h) is THIS restatement.
+ * call site and no OpenCV output to pin it to (OpenCV's own SIFT stays UNPINNED); the bit-for-bit parity target of the HIP
+ * extractor (csrc/sift.hip.h) is THIS restatement.  What anchors both is tests/f64_defs_sift.py, float64 definitions written
+ * from Lowe 2004 and OpenCV's documented conventions: tests/test_oracle_sift_definitions.py holds this restatement, and
+ * tests/test_gpu_sift_definitions.py the kernels, to them step by step (bounds derived in tests/f64_checks.py) — every blur
+ * within (2 taps + 4) u max|src| (u = 2^-24), octave step, DoG, raw extrema, retainBest and canonical order exactly, refined
+ * keypoints within u (|x| + scale) + 4e-6 scale in x / y and a few ulp in size / response (at most 2 % of an image's candidates
+ * may lie within 1e-3 of a decision boundary), orientation peaks within a per-peak bound of at most 3 degrees (at most 3 % of
+ * the peaks within 0.002 max of not being one), descriptor bytes within 0.5 + delta < 1.5 of the unrounded definition value.
  *
  *   createInitialImage    BGR -> gray (8 bit, the ORB path's cvtColor) -> f32, 2x bilinear upsample (firstOctave = -1),
  *                         GaussianBlur(sig_diff = sqrt(sigma^2 - 4 * 0.5^2))

@@ -3,7 +3,9 @@
 // the parity target is the CPU restatement of cv::SIFT::detectAndCompute (OpenCV 4.5.2, recalled) in oracle/sift_oracle.h, whose
 // header lists what is restated and the two documented departures (fixed-point histogram sums, canonical keypoint order).
 // Every float operation below is written in the oracle's order, so the whole extractor is bit-exact against it: pyramid layers,
-// keypoints and the 128 descriptor bytes.
+// keypoints and the 128 descriptor bytes.  The restatement and these kernels alike are held to float64 definitions of every
+// step (tests/f64_defs_sift.py, written from Lowe 2004 and OpenCV's documented conventions; tests/test_gpu_sift_definitions.py
+// through sift / sift_layer; bounds in tests/f64_checks.py and in the oracle's header); OpenCV's own output stays unpinned.
 //
 //   sift_base_kernel      gray (u8, the ORB path's gray_kernel) -> f32, 2x bilinear upsample (firstOctave = -1)
 //   sift_blur_kernel      GaussianBlur on f32 = sepFilter2D: row pass (taps in order) and column pass (centre, then symmetric
