@@ -745,6 +745,79 @@ extern "C" {
         frames_counted: *mut i64,
     ) -> i32;
     pub fn slideo_tone_lut(cnt: *const u64, sum: *const u64, min_count: i64, lut_out: *mut u8) -> i32;
+    // match placement map (include/slideo_amd.h "Match placement map"): per cell, the frame positions of the keypoints the contributing
+    // candidate explains and the unit-slide positions of their page points, summed; the keystoned quad fitted to the cells
+    pub fn slideo_matcher_placement_begin(m: *mut slideo_matcher, cell: i32, min_inliers: i32, reach: f64) -> i32;
+    pub fn slideo_matcher_placement_end(m: *mut slideo_matcher) -> i32;
+    pub fn slideo_matcher_placement_info(
+        m: *mut slideo_matcher,
+        cell: *mut i32,
+        min_inliers: *mut i32,
+        reach: *mut f64,
+        aw: *mut i32,
+        ah: *mut i32,
+        gw: *mut i32,
+        gh: *mut i32,
+        frames_through: *mut i64,
+    ) -> i32;
+    pub fn slideo_matcher_placement_sums(
+        m: *mut slideo_matcher,
+        n_out: *mut u64,
+        sfx_out: *mut u64,
+        sfy_out: *mut u64,
+        su_out: *mut u64,
+        sv_out: *mut u64,
+        capacity_elems: i64,
+        gw: *mut i32,
+        gh: *mut i32,
+        frames_through: *mut i64,
+        frames_counted: *mut i64,
+    ) -> i32;
+    pub fn slideo_group_placement_begin(g: *mut slideo_group, cell: i32, min_inliers: i32, reach: f64) -> i32;
+    pub fn slideo_group_placement_end(g: *mut slideo_group) -> i32;
+    pub fn slideo_group_placement_info(
+        g: *mut slideo_group,
+        cell: *mut i32,
+        min_inliers: *mut i32,
+        reach: *mut f64,
+        aw: *mut i32,
+        ah: *mut i32,
+        gw: *mut i32,
+        gh: *mut i32,
+        frames_through: *mut i64,
+    ) -> i32;
+    pub fn slideo_group_placement_sums(
+        g: *mut slideo_group,
+        n_out: *mut u64,
+        sfx_out: *mut u64,
+        sfy_out: *mut u64,
+        su_out: *mut u64,
+        sv_out: *mut u64,
+        capacity_elems: i64,
+        gw: *mut i32,
+        gh: *mut i32,
+        frames_through: *mut i64,
+        frames_counted: *mut i64,
+    ) -> i32;
+    pub fn slideo_placement_quad(
+        n: *const u64,
+        sfx: *const u64,
+        sfy: *const u64,
+        su: *const u64,
+        sv: *const u64,
+        gw: i32,
+        gh: i32,
+        cell: i32,
+        aw: i32,
+        ah: i32,
+        min_count: i64,
+        trim_px: f64,
+        rounds: i32,
+        quad_out8: *mut f64,
+        h_out9: *mut f64,
+        cells_used: *mut i32,
+        rms_px: *mut f64,
+    ) -> i32;
     // frame activity map (include/slideo_amd.h "Frame activity map"): per-pixel counts of moved pairs, and the mask read out of them
     pub fn slideo_matcher_activity_begin(m: *mut slideo_matcher, delta: i32) -> i32;
     pub fn slideo_matcher_activity_end(m: *mut slideo_matcher) -> i32;

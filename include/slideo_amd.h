@@ -64,6 +64,7 @@
  *   SLIDEO_RNG_STREAM_LEN n       start length of the pre-drawn cv::RNG stream (the tests force its growth path)
  *   SLIDEO_EVIDENCE_MAX_FRAMES n  the frames limit of an evidence session, read at evidence_begin, 1..2^20 (the tests reach the refusal with it)
  *   SLIDEO_TONE_MAX_FRAMES n      the frames limit of a tone session, read at tone_begin, 1..2^31 (the tests reach the refusal with it)
+ *   SLIDEO_PLACEMENT_MAX_FRAMES n the frames limit of a placement session, read at placement_begin, 1..2^20 (the tests reach the refusal with it)
  *   SLIDEO_RANSAC_WINDOW=0        ransac_kernel's redraw schedule by the fixed point only                       [per unit]
  *   SLIDEO_RH_TAIL_ROUNDS n       verify_model 1: rounds before a candidate moves to ransac_h_tail_kernel (256; 0 = never) [per unit]
  *   SLIDEO_REFINE_LANE_LM 0|1     verify_model 1: the small candidates' LM in refine_h_kernel<1> / in the eigen kernel's lanes [per unit]
@@ -1093,7 +1094,7 @@ int32_t     slideo_reduce_bgr8(slideo_matcher* m, const uint8_t* bgr, int32_t wi
  * (out_w, out_h).  WORKING SIZE: the source frame of a rectifying call is exempt from it, and the output must fit it: a region
  * whose output exceeds a set working size, or a working size smaller than a set region's output, is SLIDEO_ERR_UNSUPPORTED at
  * whichever set call comes second (the caller chooses the output size, so nothing is lost).
- * Out of scope: uploading only the region's bounding rows of host frames; a per-call or moving region; finding a quad other than the axis-aligned content box; a region
+ * Out of scope: uploading only the region's bounding rows of host frames; a per-call or moving region; finding a quad other than the axis-aligned content box here ("Match placement map" below learns a keystoned one from the matches); a region
  * together with a larger working size.
  * DEPARTURE: the reference never rectifies a frame.  With a region set, verdicts are those of the rectified video; off by default. */
 /* M: 9 doubles, row-major, copied; NULL clears the region (the other arguments are then ignored).  Before or after finalize, any
@@ -1897,7 +1898,7 @@ int32_t     slideo_group_evidence_counts(slideo_group* g, uint32_t* seen_out, ui
  *          kept, else 0.  mask_out: ah rows of aw bytes, stride_bytes apart: what slideo_matcher_set_frame_mask takes.
  *   box    the bounding box of the cells with hit >= min_hits && hit * 1000000 >= min_hit_ppm * seen, in pixels, clipped to
  *          (aw, ah): {x0, y0, x1, y1}, x1 and y1 exclusive; all -1 when no cell qualifies.  Axis-aligned: a keystoned screen needs
- *          a quad, which the traces' transforms can give on the host. */
+ *          a quad, which "Match placement map" below learns from the matches (a similarity transform of verify_model 0 cannot express one). */
 int32_t     slideo_evidence_mask(const uint32_t* seen, const uint32_t* hit, int32_t gw, int32_t gh, int32_t cell, int32_t aw, int32_t ah,
                                  int64_t min_seen, int32_t min_hit_ppm, int32_t grow, uint8_t* mask_out, int64_t stride_bytes);
 int32_t     slideo_evidence_box(const uint32_t* seen, const uint32_t* hit, int32_t gw, int32_t gh, int32_t cell, int32_t aw, int32_t ah,
@@ -2054,6 +2055,102 @@ int32_t     slideo_group_changed_mask_list(slideo_group* g, const slideo_frame_l
                                            uint8_t* changed_out, float* similarity_out);
 /* Tap: out_capacity >= n_frames * width * height * 3. */
 int32_t     slideo_frame_list_to_bgr8(slideo_matcher* m, const slideo_frame_list* list, uint8_t* bgr_out, int64_t out_capacity);
+
+/* ---- Match placement map (extension: the measurement a keystoned frame region can be made from, out of the matches) -----------------
+ * The frame region ("Frame region") rectifies a fixed quadrilateral of every frame: a camera at the back of the room filming the
+ * projection screen.  It needs the quad in pixels.  Under the default similarity model (verify_model 0) a candidate's transform has
+ * four degrees of freedom and cannot express a keystone; what can is the pooled point correspondences of many matched frames: each
+ * keypoint's frame position against where its page point lies on the slide.  They exist only on the device, per unit.
+ * A matcher carries a PLACEMENT SESSION, off by default, beside the evidence and tone sessions and built like the evidence session.
+ * Its state is "none", or: a cell (16, 32 or 64), min_inliers >= 0, reach (a finite double > 0, pixels of the analysed image), an
+ * analysed size (aw, ah), not fixed until the first counted call; the grid gw = ceil(aw / cell), gh = ceil(ah / cell); five sums
+ * n, sfx, sfy, su, sv [gh][gw] and frames_counted, all u64 on the device; frames_through.
+ * The evidence map's rules hold unchanged wherever this text does not say otherwise: the call forms that count (every form that
+ * runs the verify stage; unchanged, deferred, recalled and direct frames of a gated call never count), the first counted call
+ * fixing (aw, ah) and the SLIDEO_ERR_INVALID_ARG of a later call at another analysed size (the message names both sizes), what
+ * ends a session (slideo_matcher_placement_end, the setters that change the analysed image, a counted call that fails after its
+ * first unit was submitted) and what leaves it open, the idle and state rules, SIFT mode (SLIDEO_ERR_UNSUPPORTED in either order),
+ * and a unit that is run again counting once through the unit's flags word.  Any combination of the three sessions may be open at
+ * once; each one's results are what they are alone.
+ *   the contributor  the tone table's, NOT the verdict's winner (an unrectified keystone is exactly what pushes the re-projection
+ *                    similarity under min_similarity and removes the verdict): of the frame's candidate slots, as
+ *                    slideo_last_frame_candidates returns them, those whose model was found (transform not all zero) and whose
+ *                    inliers >= min_inliers; the one with the most inliers, ties to the first slot.  A frame with no such slot
+ *                    does not contribute.  frames_counted += 1 for a frame with a contributor.
+ * With the contributor's page p of full size (pw, ph) and its transform M:
+ *   residual         for each vote (q, t) of the contributor's run, d2 = dx*dx + dy*dy as the evidence map computes it, under both
+ *                    verify_model values: in float64, left to right, each operation rounded once, no fused multiply-add; w == 0 or
+ *                    a non-finite d2: the vote does not pass.  The vote PASSES iff d2 <= reach * reach.  reach is the session's own
+ *                    radius and may exceed ransac_threshold: under a keystone the similarity fits only part of the screen within
+ *                    3 px, and the correspondences further out are the ones the fit needs.
+ *   one per keypoint a keypoint q with at least one passing vote contributes once, through its passing vote of smallest d2, ties to
+ *                    the smallest train row t.  The order in which the votes are stored does not matter.
+ *   coordinates      the keypoint's floats (X, Y) and (x, y) = page_xy[t].  A keypoint outside [0, aw) x [0, ah), a page point
+ *                    outside [0, pw - 1] x [0, ph - 1], and a page with pw < 2 or ph < 2 contribute nothing.
+ *   sums             otherwise, into cell ((int)X / cell, (int)Y / cell):  n += 1;  sfx += rint(X * 16);  sfy += rint(Y * 16);
+ *                    su += rint(x / (double)(pw - 1) * 1048576.0);  sv += rint(y / (double)(ph - 1) * 1048576.0), in float64 with
+ *                    round-half-even.  (su, sv) / n / 2^20 is the position on the UNIT SLIDE whose corners are the page's corner
+ *                    pixel centres — the convention of slideo_frame_region_from_quad —, so pages of different sizes share one
+ *                    accumulator.
+ * A session holds at most 2^20 frames through: a call that could pass it (its frames and those of the units in flight included) is
+ * refused with SLIDEO_ERR_INVALID_ARG and nothing runs.  Bound: 2^20 frames of fewer than 4096 keypoints each adding at most 2^20
+ * keep every sum below 2^52, far inside u64 and exact in a double.
+ * Installing nothing: the session changes no verdict, no trace and no setting; verdict bytes are identical with and without it.  The
+ * caller reads the sums out, fits a quad with slideo_placement_quad, looks at it, and hands it to slideo_frame_region_from_quad +
+ * slideo_matcher_set_frame_region.  No threshold has a default.
+ * Where it runs (csrc/placement.hip.h, launched by csrc/stage_verify.hip unit_verify behind verdict_kernel, and behind
+ * evidence_kernel and tone_kernel when those sessions are open, on the unit's stream, only while a session is open):
+ * placement_kernel, one block of 256 threads per frame, by windows of 2048 keypoints — the votes' d2 patterns into LDS with a 64-bit
+ * unsigned min (the pattern of a non-negative finite double orders as the double does), the rows of the votes at the minimum with a
+ * 32-bit min, then per keypoint with a winner five 64-bit global atomic adds whose result is not read.  24 KB of LDS, no
+ * compare-and-swap loop.  The per-frame body is host + device functions (tools/placement_hostcheck.cpp runs it on the CPU).
+ * Limits: the estimator assumes a FIXED camera and screen over the session; a moving camera smears the cells.  SIFT mode, weighting
+ * the cells, a geometric refinement of the fit and installing the region are out of scope.
+ * Every call returns SLIDEO_ERR_INVALID_ARG for a null handle or a null required pointer. */
+/* Idle matcher, no placement session open (SLIDEO_ERR_STATE otherwise); cell other than 16, 32, 64, min_inliers < 0, or a reach that
+ * is not above 0 or whose square is not finite: SLIDEO_ERR_INVALID_ARG; SIFT mode: SLIDEO_ERR_UNSUPPORTED.  Afterwards the session
+ * is empty: no size, every sum 0.  May be called before finalize. */
+int32_t     slideo_matcher_placement_begin(slideo_matcher* m, int32_t cell, int32_t min_inliers, double reach);
+/* Idle matcher.  The state "none"; the device buffer is released.  Fine when the state is "none" already. */
+int32_t     slideo_matcher_placement_end(slideo_matcher* m);
+/* The session's values (*aw, *ah, *gw, *gh are 0 before the first counted call) and the frames of the collected units.
+ * SLIDEO_ERR_STATE in the state "none". */
+int32_t     slideo_matcher_placement_info(slideo_matcher* m, int32_t* cell, int32_t* min_inliers, double* reach, int32_t* aw, int32_t* ah, int32_t* gw,
+                                          int32_t* gh, int64_t* frames_through);
+/* Idle matcher (SLIDEO_ERR_STATE with units in flight, and in the state "none").  The five arrays: gh rows of gw elements each; all
+ * five NULL asks for the sizes and frame counts only (some NULL: SLIDEO_ERR_INVALID_ARG).  Before the first counted call *gw == *gh
+ * == 0 and nothing is written.  SLIDEO_ERR_CAPACITY (with the sizes set) when gw * gh > capacity_elems. */
+int32_t     slideo_matcher_placement_sums(slideo_matcher* m, uint64_t* n_out, uint64_t* sfx_out, uint64_t* sfy_out, uint64_t* su_out, uint64_t* sv_out,
+                                          int64_t capacity_elems, int32_t* gw, int32_t* gh, int64_t* frames_through, int64_t* frames_counted);
+/* The group forms: begin and end start and end EVERY member's session (validated on every member before one is touched); info and
+ * sums return the members' element-wise sums (a member whose shards were all empty fixes no size).  The frames limit holds per member. */
+int32_t     slideo_group_placement_begin(slideo_group* g, int32_t cell, int32_t min_inliers, double reach);
+int32_t     slideo_group_placement_end(slideo_group* g);
+int32_t     slideo_group_placement_info(slideo_group* g, int32_t* cell, int32_t* min_inliers, double* reach, int32_t* aw, int32_t* ah, int32_t* gw, int32_t* gh,
+                                        int64_t* frames_through);
+int32_t     slideo_group_placement_sums(slideo_group* g, uint64_t* n_out, uint64_t* sfx_out, uint64_t* sfy_out, uint64_t* su_out, uint64_t* sv_out,
+                                        int64_t capacity_elems, int32_t* gw, int32_t* gh, int64_t* frames_through, int64_t* frames_counted);
+/* A pure host function in float64 (no handle, no device): the quad of the sums.  The grid is validated as slideo_evidence_box
+ * validates its own (gw == ceil(aw / cell), gh == ceil(ah / cell), cell 16, 32 or 64, 1 <= aw, ah <= 4096); min_count >= 1,
+ * trim_px finite and > 0, rounds in 0..8; a count above 2^32 or a sum above its count times 2^16 (sfx, sfy) or 2^20 (su, sv): no
+ * session gives them.
+ *   points   every cell with n >= min_count is ONE point, unweighted: (u, v) = (su / n / 2^20, sv / n / 2^20), (X, Y) = (sfx / n
+ *            / 16, sfy / n / 16).  The cell mean is an ESTIMATOR: the mean of images is not the image of the mean under a
+ *            homography; the difference is second-order over a cell.  It assumes a fixed camera and screen.
+ *   fit      H = [[h0 h1 h2] [h3 h4 h5] [h6 h7 1]] mapping (u, v) to (X, Y) / s, s = max(aw, ah): the least-squares solution of
+ *            two linear equations per point,  h0 u + h1 v + h2 - xh u h6 - xh v h7 = xh  and  h3 u + h4 v + h5 - yh u h6 - yh v h7
+ *            = yh,  with (xh, yh) = (X, Y) / s; by a Householder QR with column pivoting.  Rank deficient: a diagonal entry of R
+ *            at or below 1e-10 of the first.
+ *   trim     at most `rounds` times: a point's residual is the pixel distance between s * H(u, v) and (X, Y); the points of the
+ *            current set with a residual above trim_px (or none, w == 0) are dropped; if none was, stop; otherwise refit.
+ *   outputs  quad_out8: s * H applied to (0,0), (1,0), (1,1), (0,1) — top-left, top-right, bottom-right, bottom-left as x, y pairs,
+ *            exactly what slideo_frame_region_from_quad takes; H_out9 row-major; cells_used, the points of the last fit; rms_px,
+ *            the root mean square of their residuals.
+ * SLIDEO_ERR_INVALID_ARG, and nothing written: a bad argument, fewer than 4 points at any stage, a rank-deficient system, a corner
+ * that does not come out finite.  SLIDEO_ERR_CAPACITY: no host memory for the system. */
+int32_t     slideo_placement_quad(const uint64_t* n, const uint64_t* sfx, const uint64_t* sfy, const uint64_t* su, const uint64_t* sv, int32_t gw,
+                                  int32_t gh, int32_t cell, int32_t aw, int32_t ah, int64_t min_count, double trim_px, int32_t rounds,
+                                  double* quad_out8, double* H_out9, int32_t* cells_used, double* rms_px);
 
 #ifdef __cplusplus
 }

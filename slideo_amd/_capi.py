@@ -483,6 +483,9 @@ EXPORTS = [
     "slideo_evidence_mask", "slideo_evidence_box", "slideo_matcher_rng_stream_len",
     "slideo_matcher_tone_begin", "slideo_matcher_tone_end", "slideo_matcher_tone_info", "slideo_matcher_tone_counts",
     "slideo_group_tone_begin", "slideo_group_tone_end", "slideo_group_tone_info", "slideo_group_tone_counts", "slideo_tone_lut",
+    "slideo_matcher_placement_begin", "slideo_matcher_placement_end", "slideo_matcher_placement_info", "slideo_matcher_placement_sums",
+    "slideo_group_placement_begin", "slideo_group_placement_end", "slideo_group_placement_info", "slideo_group_placement_sums",
+    "slideo_placement_quad",
     "slideo_match_frames_list", "slideo_match_frames_submit_list", "slideo_match_changed_frames_list",
     "slideo_match_changed_frames_submit_list", "slideo_changed_mask_list", "slideo_matcher_observe_frames_list",
     "slideo_matcher_gate_reset_from_frame_list", "slideo_group_match_frames_list", "slideo_group_match_changed_frames_list",
@@ -674,6 +677,14 @@ def lib():
                 getattr(L, pre + "tone_info").argtypes = [vp] * 5
                 getattr(L, pre + "tone_counts").argtypes = [vp] * 5
             L.slideo_tone_lut.argtypes = [vp, vp, i64, vp]
+        if hasattr(L, "slideo_matcher_placement_begin"):
+            vp, i32, i64, f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_double
+            for pre in ("slideo_matcher_", "slideo_group_"):
+                getattr(L, pre + "placement_begin").argtypes = [vp, i32, i32, f64]
+                getattr(L, pre + "placement_end").argtypes = [vp]
+                getattr(L, pre + "placement_info").argtypes = [vp] * 9
+                getattr(L, pre + "placement_sums").argtypes = [vp] * 6 + [i64] + [vp] * 4
+            L.slideo_placement_quad.argtypes = [vp] * 5 + [i32] * 5 + [i64, f64, i32] + [vp] * 4
         if hasattr(L, "slideo_matcher_content_begin"):
             vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
             L.slideo_matcher_content_begin.argtypes = [vp, i32]
@@ -855,6 +866,32 @@ class _FrameCalls:
         ft, fc = C.c_int64(), C.c_int64()
         self._check(getattr(lib(), self._SETS + "tone_counts")(self._h, _p(cnt), _p(sm), C.byref(ft), C.byref(fc)))
         return cnt, sm, ft.value, fc.value
+
+    # ---- match placement map (include/slideo_amd.h "Match placement map"); a Group's are the members' sums ----
+    def placement_begin(self, cell, min_inliers, reach):
+        """An empty placement session: match calls from now on sum, per cell x cell cell of the analysed image, the frame positions of
+        the keypoints that the contributing candidate (a model, the most inliers, at least min_inliers) explains within `reach`
+        pixels, and the unit-slide positions of their page points."""
+        self._check(getattr(lib(), self._SETS + "placement_begin")(self._h, int(cell), int(min_inliers), C.c_double(float(reach))))
+
+    def placement_end(self):
+        self._check(getattr(lib(), self._SETS + "placement_end")(self._h))
+
+    def placement_info(self):
+        """-> {cell, min_inliers, reach, aw, ah, gw, gh, frames_through} (aw == 0 before the first counted call)."""
+        v = [C.c_int32(), C.c_int32(), C.c_double()] + [C.c_int32() for _ in range(4)] + [C.c_int64()]
+        self._check(getattr(lib(), self._SETS + "placement_info")(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("cell", "min_inliers", "reach", "aw", "ah", "gw", "gh", "frames_through"), (x.value for x in v)))
+
+    def placement_sums(self):
+        """-> (sums uint64 [5, gh, gw]: n, sfx, sfy, su, sv; frames_through, frames_counted); [5, 0, 0] before the first counted call."""
+        gw, gh, ft, fc = C.c_int32(), C.c_int32(), C.c_int64(), C.c_int64()
+        fn = getattr(lib(), self._SETS + "placement_sums")
+        self._check(fn(self._h, None, None, None, None, None, C.c_int64(0), C.byref(gw), C.byref(gh), C.byref(ft), C.byref(fc)))
+        sums = np.zeros((5, gh.value, gw.value), np.uint64)
+        if sums.size:
+            self._check(fn(self._h, *[_p(sums[i]) for i in range(5)], C.c_int64(sums[0].size), C.byref(gw), C.byref(gh), C.byref(ft), C.byref(fc)))
+        return sums, ft.value, fc.value
 
     def last_candidates(self, frame_in_batch):
         cands = np.zeros(64, CANDIDATE_DTYPE)
@@ -2171,6 +2208,24 @@ def tone_lut(cnt, sm, min_count):
         raise SlideoError(rc, "slideo_tone_lut: min_count below 1, a channel without an anchor, or counts no session gives "
                               "(include/slideo_amd.h \"Match tone table\")")
     return out
+
+
+def placement_quad(sums, cell, aw, ah, min_count, trim_px, rounds):
+    """slideo_placement_quad (include/slideo_amd.h "Match placement map"): sums uint64 [5, gh, gw] (n, sfx, sfy, su, sv) -> (quad
+    [(x, y)] * 4 top-left, top-right, bottom-right, bottom-left in pixels of the analysed image, H float64 [3, 3], cells_used,
+    rms_px).  SlideoError: an argument outside its range, fewer than 4 cells with min_count keypoints at a stage, or cells that do
+    not determine a homography."""
+    sums = np.ascontiguousarray(sums, np.uint64)
+    if sums.ndim != 3 or sums.shape[0] != 5:
+        raise ValueError("sums: one uint64 [5, gh, gw] array, got %s" % (sums.shape,))
+    quad, H = np.zeros(8, np.float64), np.zeros(9, np.float64)
+    used, rms = C.c_int32(), C.c_double()
+    rc = lib().slideo_placement_quad(*[_p(sums[i]) for i in range(5)], sums.shape[2], sums.shape[1], int(cell), int(aw), int(ah),
+                                     C.c_int64(int(min_count)), C.c_double(float(trim_px)), int(rounds), _p(quad), _p(H), C.byref(used), C.byref(rms))
+    if rc != OK:
+        raise SlideoError(rc, "slideo_placement_quad: an argument outside its range, fewer than 4 cells of min_count keypoints, or cells "
+                              "that determine no homography (include/slideo_amd.h \"Match placement map\")")
+    return [(float(quad[2 * i]), float(quad[2 * i + 1])) for i in range(4)], H.reshape(3, 3), used.value, rms.value
 
 
 def changed_ssd_threshold(changed_similarity, small_w, small_h):

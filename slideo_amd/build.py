@@ -25,7 +25,7 @@ HIP_SOURCES = ["capi_runtime.hip", "capi_group.hip", "capi_taps.hip", "stage_orb
 # the kernel headers each unit includes (beyond runtime.hpp and the plain headers, which every unit depends on)
 HIP_UNIT_HEADERS = {"stage_orb.hip": ["orb.hip.h", "cv_math.hip.h", "yuv420.hip.h", "yuv_sampling.hip.h", "yuv_chroma.hip.h", "yuv_transfer.hip.h", "pixel_format.hip.h", "frame_list.hip.h", "bgr_store.hip.h", "reduce.hip.h", "frame_region.hip.h", "frame_mask.hip.h", "levels.hip.h"],
                     "stage_knn.hip": ["knn.hip.h", "knn_tile.hip.h", "knn_l2.hip.h", "knn_lsh.hip.h"],
-                    "stage_verify.hip": ["verify.hip.h", "homography.hip.h", "evidence.hip.h", "tone.hip.h"],
+                    "stage_verify.hip": ["verify.hip.h", "homography.hip.h", "evidence.hip.h", "tone.hip.h", "placement.hip.h"],
                     "stage_sift.hip": ["sift.hip.h", "cv_math.hip.h"],
                     "stage_page_set.hip": ["page_set.hip.h"],
                     "stage_gate.hip": ["gate.hip.h"],

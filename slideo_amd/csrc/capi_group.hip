@@ -959,4 +959,93 @@ int32_t slideo_group_tone_counts(slideo_group* g, uint64_t* cnt_out, uint64_t* s
     GROUP_CATCH(g)
 }
 
+// ---- Match placement map (include/slideo_amd.h "Match placement map"): every member carries a session, the read-outs return the sums --
+int32_t slideo_group_placement_begin(slideo_group* g, int32_t cell, int32_t min_inliers, double reach) {
+    if (!g) return SLIDEO_ERR_INVALID_ARG;
+    GROUP_TRY
+    if (cell != 16 && cell != 32 && cell != 64) fail(SLIDEO_ERR_INVALID_ARG, "placement_begin: cell %d is none of 16, 32, 64", cell);
+    if (min_inliers < 0) fail(SLIDEO_ERR_INVALID_ARG, "placement_begin: min_inliers %d below 0", min_inliers);
+    if (!(reach > 0.0) || !std::isfinite(reach * reach)) fail(SLIDEO_ERR_INVALID_ARG, "placement_begin: reach %g is not a finite distance above 0", reach);
+    // validated before any member is touched
+    for (slideo_matcher* m : g->members) {
+        if (m->sift_on) fail(SLIDEO_ERR_UNSUPPORTED, "placement_begin: the placement map is not defined in SIFT mode");
+        require_idle(m);
+        if (m->placement.on) fail(SLIDEO_ERR_STATE, "placement_begin: a session is open (slideo_group_placement_end first)");
+    }
+    for (slideo_matcher* m : g->members) check_member_call(m, slideo_matcher_placement_begin(m, cell, min_inliers, reach));
+    GROUP_CATCH(g)
+}
+
+int32_t slideo_group_placement_end(slideo_group* g) {
+    if (!g) return SLIDEO_ERR_INVALID_ARG;
+    GROUP_TRY
+    for (slideo_matcher* m : g->members) require_idle(m);
+    for (slideo_matcher* m : g->members) check_member_call(m, slideo_matcher_placement_end(m));
+    GROUP_CATCH(g)
+}
+
+namespace {
+// the members' sessions as one: every member's open, the members that counted agree on the analysed size
+void group_placement(slideo_group* g, slideo_matcher::Placement& sum) {
+    sum = slideo_matcher::Placement{};
+    for (slideo_matcher* m : g->members) {
+        const slideo_matcher::Placement& P = m->placement;
+        if (!P.on) fail(SLIDEO_ERR_STATE, "no placement session on every member: slideo_group_placement_begin first");
+        if (!sum.on) { sum = P; sum.aw = sum.ah = sum.gw = sum.gh = 0; sum.through = 0; }
+        if (P.cell != sum.cell || P.min_inliers != sum.min_inliers || P.reach != sum.reach)
+            fail(SLIDEO_ERR_STATE, "the members' placement sessions differ (one was begun directly)");
+        if (P.aw > 0) {
+            if (sum.aw > 0 && (sum.aw != P.aw || sum.ah != P.ah))
+                fail(SLIDEO_ERR_STATE, "the members' placement sessions count at %dx%d and %dx%d (a member was called directly)", sum.aw, sum.ah, P.aw, P.ah);
+            sum.aw = P.aw; sum.ah = P.ah; sum.gw = P.gw; sum.gh = P.gh;
+        }
+        sum.through += P.through;
+    }
+}
+}  // namespace
+
+int32_t slideo_group_placement_info(slideo_group* g, int32_t* cell, int32_t* min_inliers, double* reach, int32_t* aw, int32_t* ah, int32_t* gw, int32_t* gh,
+                                    int64_t* frames_through) {
+    if (!g) return SLIDEO_ERR_INVALID_ARG;
+    GROUP_TRY
+    if (!cell || !min_inliers || !reach || !aw || !ah || !gw || !gh || !frames_through) fail(SLIDEO_ERR_INVALID_ARG, "null output");
+    slideo_matcher::Placement P;
+    group_placement(g, P);
+    *cell = P.cell; *min_inliers = P.min_inliers; *reach = P.reach; *aw = P.aw; *ah = P.ah; *gw = P.gw; *gh = P.gh; *frames_through = P.through;
+    GROUP_CATCH(g)
+}
+
+int32_t slideo_group_placement_sums(slideo_group* g, uint64_t* n_out, uint64_t* sfx_out, uint64_t* sfy_out, uint64_t* su_out, uint64_t* sv_out,
+                                    int64_t capacity_elems, int32_t* gw, int32_t* gh, int64_t* frames_through, int64_t* frames_counted) {
+    if (!g) return SLIDEO_ERR_INVALID_ARG;
+    GROUP_TRY
+    if (!gw || !gh || !frames_through || !frames_counted) fail(SLIDEO_ERR_INVALID_ARG, "null gw/gh/frames_through/frames_counted");
+    for (slideo_matcher* m : g->members) require_idle(m);
+    slideo_matcher::Placement P;
+    group_placement(g, P);
+    *gw = P.gw; *gh = P.gh; *frames_through = P.through; *frames_counted = 0;
+    if (P.aw == 0) return SLIDEO_OK;
+    uint64_t* outs[5] = {n_out, sfx_out, sfy_out, su_out, sv_out};
+    int given = 0;
+    for (uint64_t* o : outs) given += o != nullptr;
+    if (given != 0 && given != 5) fail(SLIDEO_ERR_INVALID_ARG, "the five output arrays go together");
+    const int64_t nc = (int64_t)P.gw * P.gh;
+    if (given && nc > capacity_elems) fail(SLIDEO_ERR_CAPACITY, "the sums need %lld elements each", (long long)nc);
+    // (every member's sums stay below 2^52: the members' sums stay inside u64)
+    std::vector<uint64_t> part(given ? (size_t)nc * 5 : 0);
+    for (int i = 0; given && i < 5; ++i) std::fill(outs[i], outs[i] + nc, (uint64_t)0);
+    int64_t counted = 0;
+    for (slideo_matcher* m : g->members) {
+        if (m->placement.aw == 0) continue;              // (its shards were empty: nothing counted)
+        int32_t w = 0, h = 0; int64_t t = 0, c = 0;
+        uint64_t* p = given ? part.data() : nullptr;
+        check_member_call(m, slideo_matcher_placement_sums(m, p, p ? p + nc : p, p ? p + 2 * nc : p, p ? p + 3 * nc : p, p ? p + 4 * nc : p, nc, &w, &h, &t, &c));
+        for (int i = 0; given && i < 5; ++i)
+            for (int64_t j = 0; j < nc; ++j) outs[i][j] += part[(size_t)(i * nc + j)];
+        counted += c;
+    }
+    *frames_counted = counted;
+    GROUP_CATCH(g)
+}
+
 }  // extern "C"

@@ -412,6 +412,7 @@ static void unit_collect_body(slideo_matcher* m, Slot& S, slideo_verdict* out_ho
     }
     std::memcpy(out_host, ho, (size_t)n * sizeof(slideo_verdict));
     tone_tally(m, n);
+    placement_tally(m, n);
     evidence_tally(m, out_host, n);                  // (the run whose verdicts are returned: evidence_kernel counted this one alone)
     const size_t base = m->last_fcs.size();
     m->last_fcs.resize(base + n);
@@ -446,6 +447,7 @@ void match_frames_impl(slideo_matcher* m, int n, FrameSrc src, slideo_verdict* o
     if (n == 0) return;
     evidence_admit(m, src.plan.uw, src.plan.uh, n);
     tone_admit(m, n);
+    placement_admit(m, src.plan.uw, src.plan.uh, n);
     int unit = unit_fit(m, src, n, gated);
     area_class_for(m, src.plan.uw, src.plan.uh);
     upload_area(m);
@@ -515,6 +517,7 @@ static void submit_impl(slideo_matcher* m, int32_t n_frames, FrameSrc src, void*
         fail(SLIDEO_ERR_CAPACITY, "%d frames exceed the per-slot workspace budget (%d); submit smaller units or raise SLIDEO_WS_GB", n_frames, fit);
     evidence_admit(m, src.plan.uw, src.plan.uh, n_frames);
     tone_admit(m, n_frames);
+    placement_admit(m, src.plan.uw, src.plan.uh, n_frames);
     area_class_for(m, src.plan.uw, src.plan.uh);
     upload_area(m);
     { bool any = false; for (const Slot& c : m->slots) any |= c.busy; if (!any) m->last_fcs.clear(); }

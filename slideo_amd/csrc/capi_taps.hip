@@ -146,6 +146,7 @@ int32_t slideo_match_frames_features_bgr8(slideo_matcher* m, int32_t n_frames, c
     if (n == 0) return SLIDEO_OK;
     evidence_admit(m, width, height, n);
     tone_admit(m, n);
+    placement_admit(m, width, height, n);
     // (a failure from here on may leave rows counted whose verdicts are never returned: an open evidence session ends with it)
     struct EvidenceGuard { slideo_matcher* m; bool ok; ~EvidenceGuard() { if (!ok) sessions_drop(m); } } ev_guard{m, false};
     area_class_for(m, width, height);
@@ -202,6 +203,7 @@ int32_t slideo_match_frames_features_bgr8(slideo_matcher* m, int32_t n_frames, c
     std::memcpy(verdicts_out, ho, (size_t)n * sizeof(slideo_verdict));
     evidence_tally(m, verdicts_out, n);
     tone_tally(m, n);
+    placement_tally(m, n);
     ev_guard.ok = true;
     m->last_fcs.resize((size_t)n);
     std::memcpy(m->last_fcs.data(), ho + (size_t)n * sizeof(slideo_verdict), (size_t)n * sizeof(FrameCands));

@@ -10,7 +10,8 @@
 //                                                 frame_region.hip.h, frame_mask.hip.h, levels.hip.h levels_kernel, frame_list.hip.h)
 //   stage_knn.hip      index build + k-NN stage   (kernels: knn.hip.h, knn_tile.hip.h, knn_l2.hip.h, knn_lsh.hip.h)
 //   stage_verify.hip   vote .. verdict, small img (kernels: verify.hip.h, homography.hip.h); the match evidence map's session, its
-//                      launch behind the verdicts and its entry points (kernel: evidence.hip.h); the match tone table's likewise (kernel: tone.hip.h)
+//                      launch behind the verdicts and its entry points (kernel: evidence.hip.h); the match tone table's likewise (kernel: tone.hip.h),
+//                      and the match placement map's (kernel: placement.hip.h)
 //   stage_sift.hip     SIFT stage + entry points  (kernels: sift.hip.h)
 //   stage_page_set.hip page sets: a subset's search operand built from the finalized deck (kernels: page_set.hip.h)
 //   stage_gate.hip     changed-frame gate: gated units, the gate state, its record and its entry points (kernels: gate.hip.h)
@@ -503,6 +504,13 @@ struct slideo_matcher {
     struct Tone { bool on = false; int min_inliers = 0, min_hits = 0, flat = 0; int64_t through = 0, max_frames = 0; } tone;
     slideo::DevBuf d_tone;
 
+    // match placement map (include/slideo_amd.h "Match placement map"): the session — "none" (on false), empty (aw 0) or the sums of
+    // the match calls since placement_begin at the analysed size aw x ah — and its device buffer {n | sfx | sfy | su | sv} (u64
+    // [gh][gw] each) | frames_counted u64, zeroed at the first counted call, which placement_kernel adds to on the units' streams.
+    // through: the frames of the collected units.  max_frames: 2^20 unless SLIDEO_PLACEMENT_MAX_FRAMES lowered it at begin
+    struct Placement { bool on = false; int cell = 0, min_inliers = 0, aw = 0, ah = 0, gw = 0, gh = 0; double reach = 0; int64_t through = 0, max_frames = 0; } placement;
+    slideo::DevBuf d_placement;
+
     // direct page look-up (include/slideo_amd.h "Direct page look-up"): built at the first use with fs.direct_t > 0 after finalize, the
     // deck's size classes
     bool direct_built = false;
@@ -673,7 +681,12 @@ inline void evidence_drop(slideo_matcher* m) { m->evidence = slideo_matcher::Evi
 void tone_admit(slideo_matcher* m, int n);
 inline void tone_tally(slideo_matcher* m, int n) { if (m->tone.on) m->tone.through += n; }
 inline void tone_drop(slideo_matcher* m) { m->tone = slideo_matcher::Tone{}; }
-inline void sessions_drop(slideo_matcher* m) { evidence_drop(m); tone_drop(m); }
+// Match placement map (placement.hip.h), no-ops without a session.  placement_admit: evidence_admit's checks and first-call zeroing
+// with the limit on the frames through.  placement_tally: the frames of a collected unit.  placement_drop: the state "none"
+void placement_admit(slideo_matcher* m, int uw, int uh, int n);
+inline void placement_tally(slideo_matcher* m, int n) { if (m->placement.on && m->placement.aw > 0) m->placement.through += n; }
+inline void placement_drop(slideo_matcher* m) { m->placement = slideo_matcher::Placement{}; }
+inline void sessions_drop(slideo_matcher* m) { evidence_drop(m); tone_drop(m); placement_drop(m); }
 // (sw, sh: the small size, for callers without a FramePlan — pages, taps, the validity map)
 void run_small(slideo_matcher* m, const DevFrames& imgs, int n, hipStream_t st, int* sw = nullptr, int* sh = nullptr);
 // the same into `dst` (n small images back to back) in place of m->d_small: small images of consecutive gated units overlap

@@ -1,11 +1,13 @@
 // stage_verify.hip — drivers of the verification stage, vote .. verdict, and of to_small_image (kernels: verify.hip.h, homography.hip.h);
 // the match evidence map of include/slideo_amd.h "Match evidence map": its session, its launch behind the verdicts and its entry
-// points (kernel: evidence.hip.h); the match tone table of "Match tone table" likewise (kernel: tone.hip.h).
+// points (kernel: evidence.hip.h); the match tone table of "Match tone table" likewise (kernel: tone.hip.h), and the match placement map of
+// "Match placement map" (kernel: placement.hip.h).
 #include "runtime.hpp"
 #include "verify.hip.h"
 #include "homography.hip.h"
 #include "evidence.hip.h"
 #include "tone.hip.h"
+#include "placement.hip.h"
 
 #include <cstring>
 
@@ -121,6 +123,47 @@ static void tone_launch(slideo_matcher* m, Slot& S, const VerifyParams& vp, cons
     a.acc = m->d_tone.as<unsigned long long>();
     tone_kernel<<<n, TONE_THREADS, 0, S.st>>>(a);
     check_launch("tone_kernel");
+}
+
+// ---- match placement map ----------------------------------------------------------------------------------------------------------
+void placement_admit(slideo_matcher* m, int uw, int uh, int n) {
+    slideo_matcher::Placement& P = m->placement;
+    if (!P.on || n <= 0) return;
+    if (P.aw > 0 && (P.aw != uw || P.ah != uh))
+        fail(SLIDEO_ERR_INVALID_ARG, "these frames are analysed at %dx%d, the placement session counts at %dx%d: slideo_matcher_placement_end first", uw, uh,
+             P.aw, P.ah);
+    int64_t pending = 0;
+    for (const Slot& S : m->slots) if (S.busy) pending += S.n;
+    if (P.through + pending + n > P.max_frames)
+        fail(SLIDEO_ERR_INVALID_ARG, "%lld frames would pass the placement session's %lld: read the sums out and begin again", (long long)(P.through + pending + n),
+             (long long)P.max_frames);
+    if (P.aw > 0) return;
+    // the session's first counted call fixes the grid; the zeroed sums stand before any unit of the call is submitted
+    const int gw = cdiv(uw, P.cell), gh = cdiv(uh, P.cell);
+    const size_t bytes = ((size_t)gw * gh * 5 + 1) * 8;
+    m->d_placement.reserve(bytes + 16);
+    HIP_CHECK(hipMemsetAsync(m->d_placement.p, 0, bytes, m->stream));
+    HIP_CHECK(hipStreamSynchronize(m->stream));
+    P.aw = uw; P.ah = uh; P.gw = gw; P.gh = gh;
+}
+
+// placement_kernel over the unit's frames, behind verdict_kernel (and evidence_kernel, tone_kernel) on the unit's stream
+static void placement_launch(slideo_matcher* m, Slot& S, const VerifyParams& vp, const DevFrames& f, int n) {
+    const slideo_matcher::Placement& P = m->placement;
+    if (P.aw != f.w || P.ah != f.h) fail(SLIDEO_ERR_HIP, "internal: a unit of %dx%d images under a placement session of %dx%d", f.w, f.h, P.aw, P.ah);
+    PlacementArgs a{};
+    a.ev.fcs = S.d_fcs.as<FrameCands>(); a.ev.qofs = S.d_qofs.as<uint32_t>(); a.ev.kp = S.d_kp.as<slideo_keypoint>();
+    a.ev.page_xy = reinterpret_cast<const EvXY*>(m->d_page_xy.as<float2>());
+    a.ev.votes = reinterpret_cast<const EvVote*>(S.d_votes.as<uint2>());
+    a.ev.flags = S.d_flags.as<uint32_t>();
+    a.ev.rerun_mask = S.u_async ? 12u : 4u;      // (evidence_launch's: unit_collect's re-run rules)
+    a.ev.k = vp.k; a.ev.model = vp.model;
+    a.pageinfo = m->d_pageinfo.as<PageInfo>();
+    a.reach2 = P.reach * P.reach;
+    a.aw = P.aw; a.ah = P.ah; a.cell = P.cell; a.gw = P.gw; a.gh = P.gh; a.min_inliers = P.min_inliers;
+    a.acc = m->d_placement.as<unsigned long long>();
+    placement_kernel<<<n, PL_THREADS, 0, S.st>>>(a);
+    check_launch("placement_kernel");
 }
 
 // Everything after the neighbour lists (S.d_keys, Hamming key format) of a unit: the per-page vote, RANSAC (similarity or
@@ -239,6 +282,7 @@ void unit_verify(slideo_matcher* m, Slot& S, const VerifyParams& vp, const DevFr
     check_launch("verdict_kernel");
     if (m->evidence.on && qtot > 0) evidence_launch(m, S, vp, f, n);
     if (m->tone.on && qtot > 0) tone_launch(m, S, vp, f, n);
+    if (m->placement.on && qtot > 0) placement_launch(m, S, vp, f, n);
     if (prof) HIP_CHECK(hipEventRecord(S.ev[3], st));
     uint8_t* ho = S.h_out.as<uint8_t>();
     const size_t tail = (size_t)n * (sizeof(slideo_verdict) + sizeof(FrameCands));
@@ -426,6 +470,89 @@ int32_t slideo_tone_lut(const uint64_t* cnt, const uint64_t* sum, int64_t min_co
     for (int i = 0; i < 768; ++i)
         if (cnt[i] > ((uint64_t)1 << 48) || sum[i] > 255 * cnt[i]) return SLIDEO_ERR_INVALID_ARG;
     return tone_lut(cnt, sum, (uint64_t)min_count, lut_out) ? SLIDEO_OK : SLIDEO_ERR_INVALID_ARG;
+}
+
+}  // extern "C"
+
+// ---- Match placement map (include/slideo_amd.h "Match placement map") ---------------------------------------------------------------
+extern "C" {
+
+int32_t slideo_matcher_placement_begin(slideo_matcher* m, int32_t cell, int32_t min_inliers, double reach) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    if (!evidence_cell_ok(cell)) fail(SLIDEO_ERR_INVALID_ARG, "placement_begin: cell %d is none of 16, 32, 64", cell);
+    if (min_inliers < 0) fail(SLIDEO_ERR_INVALID_ARG, "placement_begin: min_inliers %d below 0", min_inliers);
+    if (!(reach > 0.0) || !std::isfinite(reach * reach)) fail(SLIDEO_ERR_INVALID_ARG, "placement_begin: reach %g is not a finite distance above 0", reach);
+    if (m->sift_on) fail(SLIDEO_ERR_UNSUPPORTED, "placement_begin: the placement map is not defined in SIFT mode");
+    require_idle(m);
+    if (m->placement.on) fail(SLIDEO_ERR_STATE, "placement_begin: a session is open (slideo_matcher_placement_end first)");
+    m->placement = slideo_matcher::Placement{};
+    m->placement.on = true; m->placement.cell = cell; m->placement.min_inliers = min_inliers; m->placement.reach = reach;
+    m->placement.max_frames = std::min<int64_t>(PL_MAX_FRAMES, std::max<long>(1, env_long("SLIDEO_PLACEMENT_MAX_FRAMES", (long)PL_MAX_FRAMES)));
+    API_CATCH(m)
+}
+
+int32_t slideo_matcher_placement_end(slideo_matcher* m) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    require_idle(m);
+    HIP_CHECK(hipSetDevice(m->device));
+    placement_drop(m);
+    m->d_placement.release();
+    API_CATCH(m)
+}
+
+int32_t slideo_matcher_placement_info(slideo_matcher* m, int32_t* cell, int32_t* min_inliers, double* reach, int32_t* aw, int32_t* ah, int32_t* gw, int32_t* gh,
+                                      int64_t* frames_through) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    if (!cell || !min_inliers || !reach || !aw || !ah || !gw || !gh || !frames_through) fail(SLIDEO_ERR_INVALID_ARG, "null output");
+    const slideo_matcher::Placement& P = m->placement;
+    if (!P.on) fail(SLIDEO_ERR_STATE, "no placement session: slideo_matcher_placement_begin first");
+    *cell = P.cell; *min_inliers = P.min_inliers; *reach = P.reach; *aw = P.aw; *ah = P.ah; *gw = P.gw; *gh = P.gh; *frames_through = P.through;
+    API_CATCH(m)
+}
+
+int32_t slideo_matcher_placement_sums(slideo_matcher* m, uint64_t* n_out, uint64_t* sfx_out, uint64_t* sfy_out, uint64_t* su_out, uint64_t* sv_out,
+                                      int64_t capacity_elems, int32_t* gw, int32_t* gh, int64_t* frames_through, int64_t* frames_counted) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    if (!gw || !gh || !frames_through || !frames_counted) fail(SLIDEO_ERR_INVALID_ARG, "null gw/gh/frames_through/frames_counted");
+    require_idle(m);
+    const slideo_matcher::Placement& P = m->placement;
+    if (!P.on) fail(SLIDEO_ERR_STATE, "no placement session: slideo_matcher_placement_begin first");
+    *gw = P.gw; *gh = P.gh; *frames_through = P.through; *frames_counted = 0;
+    if (P.aw == 0) return SLIDEO_OK;      // (no counted call yet: a grid of 0 x 0)
+    uint64_t* outs[5] = {n_out, sfx_out, sfy_out, su_out, sv_out};
+    int given = 0;
+    for (uint64_t* o : outs) given += o != nullptr;
+    if (given != 0 && given != 5) fail(SLIDEO_ERR_INVALID_ARG, "the five output arrays go together");
+    const int64_t nc = (int64_t)P.gw * P.gh;
+    if (given && nc > capacity_elems) fail(SLIDEO_ERR_CAPACITY, "the sums need %lld elements each", (long long)nc);
+    HIP_CHECK(hipSetDevice(m->device));
+    uint64_t counted = 0;
+    for (int i = 0; given && i < 5; ++i)
+        HIP_CHECK(hipMemcpyAsync(outs[i], m->d_placement.as<uint64_t>() + (size_t)i * nc, (size_t)nc * 8, hipMemcpyDeviceToHost, m->stream));
+    HIP_CHECK(hipMemcpyAsync(&counted, m->d_placement.as<uint64_t>() + 5 * (size_t)nc, 8, hipMemcpyDeviceToHost, m->stream));
+    HIP_CHECK(hipStreamSynchronize(m->stream));
+    *frames_counted = (int64_t)counted;
+    API_CATCH(m)
+}
+
+int32_t slideo_placement_quad(const uint64_t* n, const uint64_t* sfx, const uint64_t* sfy, const uint64_t* su, const uint64_t* sv, int32_t gw, int32_t gh,
+                              int32_t cell, int32_t aw, int32_t ah, int64_t min_count, double trim_px, int32_t rounds, double* quad_out8, double* H_out9,
+                              int32_t* cells_used, double* rms_px) {
+    if (!n || !sfx || !sfy || !su || !sv || !quad_out8 || !H_out9 || !cells_used || !rms_px) return SLIDEO_ERR_INVALID_ARG;
+    if (!evidence_cell_ok(cell) || aw < 1 || ah < 1 || aw > MAX_DIM || ah > MAX_DIM || gw != cdiv(aw, cell) || gh != cdiv(ah, cell)) return SLIDEO_ERR_INVALID_ARG;
+    if (min_count < 1 || !(trim_px > 0.0) || !std::isfinite(trim_px) || rounds < 0 || rounds > 8) return SLIDEO_ERR_INVALID_ARG;
+    // (no session gives a count above 2^32 or a sum above its count times the coordinate's range; the means stay exact in f64)
+    for (size_t c = 0; c < (size_t)gw * gh; ++c)
+        if (n[c] > ((uint64_t)1 << 32) || sfx[c] > n[c] * 65536 || sfy[c] > n[c] * 65536 || su[c] > n[c] * 1048576 || sv[c] > n[c] * 1048576)
+            return SLIDEO_ERR_INVALID_ARG;
+    try {
+        return placement_quad(n, sfx, sfy, su, sv, gw, gh, aw, ah, (uint64_t)min_count, trim_px, rounds, quad_out8, H_out9, cells_used, rms_px) ? SLIDEO_OK
+                                                                                                                                               : SLIDEO_ERR_INVALID_ARG;
+    } catch (const std::bad_alloc&) { return SLIDEO_ERR_CAPACITY; }
 }
 
 }  // extern "C"

@@ -423,6 +423,40 @@ public:
         lut768.assign(768, 0);
         return t.cnt.size() == 768 && t.sum.size() == 768 && slideo_tone_lut(t.cnt.data(), t.sum.data(), min_count, lut768.data()) == SLIDEO_OK;
     }
+    // Match placement map (include/slideo_amd.h "Match placement map"; an extension): while a session is open, the tasks' match calls
+    // sum, per cell of the analysed image, the frame positions of the keypoints that the contributing candidate explains within
+    // `reach` pixels and the unit-slide positions of their page points, over the devices.  No task may be running at begin, sums or
+    // end.  placement_quad fits the keystoned quad (what slideo_frame_region_from_quad takes); nothing is installed, no value has a default.
+    struct PlacementSums {
+        int32_t cell = 0, min_inliers = 0, aw = 0, ah = 0, gw = 0, gh = 0;
+        double reach = 0;
+        int64_t frames_through = 0, frames_counted = 0;
+        std::vector<uint64_t> n, sfx, sfy, su, sv;     // gh rows of gw each (placement_info leaves them empty)
+    };
+    struct PlacementQuad { double quad[8] = {0}, H[9] = {0}, rms_px = 0; int32_t cells_used = 0; };
+    void placement_begin(int32_t cell, int32_t min_inliers, double reach) { h_->check(slideo_group_placement_begin(h_->g, cell, min_inliers, reach)); }
+    void placement_end() { h_->check(slideo_group_placement_end(h_->g)); }
+    PlacementSums placement_info() const {
+        PlacementSums p;
+        h_->check(slideo_group_placement_info(h_->g, &p.cell, &p.min_inliers, &p.reach, &p.aw, &p.ah, &p.gw, &p.gh, &p.frames_through));
+        return p;
+    }
+    PlacementSums placement_sums() const {
+        PlacementSums p = placement_info();
+        const size_t nc = (size_t)p.gw * (size_t)p.gh;
+        p.n.assign(nc, 0); p.sfx.assign(nc, 0); p.sfy.assign(nc, 0); p.su.assign(nc, 0); p.sv.assign(nc, 0);
+        if (nc)
+            h_->check(slideo_group_placement_sums(h_->g, p.n.data(), p.sfx.data(), p.sfy.data(), p.su.data(), p.sv.data(), (int64_t)nc, &p.gw, &p.gh,
+                                                  &p.frames_through, &p.frames_counted));
+        return p;
+    }
+    // the quad of the sums; false: fewer than 4 cells of min_count keypoints at a stage, or cells that determine no homography
+    static bool placement_quad(const PlacementSums& p, int64_t min_count, double trim_px, int32_t rounds, PlacementQuad& out) {
+        const size_t nc = (size_t)p.gw * (size_t)p.gh;
+        if (!nc || p.n.size() != nc || p.sfx.size() != nc || p.sfy.size() != nc || p.su.size() != nc || p.sv.size() != nc) return false;
+        return slideo_placement_quad(p.n.data(), p.sfx.data(), p.sfy.data(), p.su.data(), p.sv.data(), p.gw, p.gh, p.cell, p.aw, p.ah, min_count, trim_px,
+                                     rounds, out.quad, out.H, &out.cells_used, &out.rms_px) == SLIDEO_OK;
+    }
 private:
     std::shared_ptr<detail::Handle> h_;
     std::shared_ptr<std::vector<I>> images_;

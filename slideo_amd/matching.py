@@ -434,6 +434,60 @@ def learn_frame_levels_from_matches(matcher, frame_batches, *, min_inliers, min_
     return lut
 
 
+def learn_frame_quad_from_matches(matcher, frame_batches, *, cell, min_inliers, reach, min_count, trim, rounds, inset=0, out_size=None):
+    """A keystoned frame region learnt from the matches themselves (include/slideo_amd.h "Match placement map"): the host BGR batches
+    (each uint8 [n, h, w, 3], all of one frame size) are matched against the matcher's finalized deck under a placement session of
+    `cell`, `min_inliers` and `reach`; every cell with at least `min_count` explained keypoints is one correspondence between the
+    unit slide and the frame, and slideo_placement_quad fits the homography to them, dropping cells further than `trim` pixels
+    from it at most `rounds` times.  `matcher`: a Matcher or a Group, idle, finalized; the camera and the screen must not move over
+    the batches.  Returns what learn_frame_region returns — (src_w, src_h, quad, out_w, out_h), quad: where the slide's corner
+    pixel centres lie in the frame, top-left, top-right, bottom-right, bottom-left — and installs nothing.  inset: the slide's
+    corners are taken `inset` pixels inside the slide on every side (measured along the quad's mean edge lengths, mapped through
+    the fitted homography).  out_size None: the rounded mean lengths of the quad's opposite edge pairs, at least 2.  ValueError when
+    no frame was matched, or when the frames were not analysed at their own size (a working size reduced them, or a frame region is
+    set): the quad is then not in source coordinates; SlideoError when the cells determine no quad.  No threshold has a default."""
+    inset = float(inset)
+    if inset < 0:
+        raise ValueError("learn_frame_quad_from_matches: inset %g is negative" % inset)
+    size = None
+    matcher.placement_begin(cell, min_inliers, reach)
+    try:
+        for batch in frame_batches:
+            if size is None and len(batch):
+                size = (int(np.shape(batch)[2]), int(np.shape(batch)[1]))
+            matcher.match_frames(batch)
+        info = matcher.placement_info()
+        sums, _, _ = matcher.placement_sums()
+    finally:
+        matcher.placement_end()
+    if info["aw"] == 0:
+        raise ValueError("no frame was matched: the placement map is empty")
+    if (info["aw"], info["ah"]) != size:
+        raise ValueError("learn_frame_quad_from_matches: the frames are %dx%d but were analysed at %dx%d (a working size reduced them, or a "
+                         "frame region is set): the quad is not in source coordinates" % (size + (info["aw"], info["ah"])))
+    quad, H, _, _ = _capi.placement_quad(sums, info["cell"], info["aw"], info["ah"], min_count, trim, rounds)
+
+    def edges(q):
+        d = lambda a, b: float(np.hypot(q[a][0] - q[b][0], q[a][1] - q[b][1]))
+        return (d(0, 1) + d(3, 2)) / 2, (d(0, 3) + d(1, 2)) / 2
+    if inset > 0:
+        ew, eh = edges(quad)
+        if not (2 * inset < ew and 2 * inset < eh):
+            raise ValueError("learn_frame_quad_from_matches: an inset of %g leaves nothing of a quad of mean edges %.1f x %.1f" % (inset, ew, eh))
+        s = float(max(info["aw"], info["ah"]))
+        eu, ev = inset / ew, inset / eh
+        quad = []
+        for u, v in ((eu, ev), (1 - eu, ev), (1 - eu, 1 - ev), (eu, 1 - ev)):
+            p = H @ np.array([u, v, 1.0])
+            quad.append((float(s * p[0] / p[2]), float(s * p[1] / p[2])))
+    if out_size is None:
+        ew, eh = edges(quad)
+        out_w, out_h = max(2, int(round(ew))), max(2, int(round(eh)))
+    else:
+        out_w, out_h = int(out_size[0]), int(out_size[1])
+    return size[0], size[1], quad, out_w, out_h
+
+
 def dedup_timeline(mappings: List[Matching]) -> List[Matching]:
     """lib.rs:229-244: stable sort by time, drop consecutive mappings with the same image."""
     mappings = sorted(mappings, key=lambda mm: mm.video_time)
