@@ -599,6 +599,40 @@ extern "C" {
     pub fn slideo_matcher_levels_info(m: *mut slideo_matcher, frames: *mut i64, pixels: *mut i64) -> i32;
     pub fn slideo_matcher_levels_histogram(m: *mut slideo_matcher, hist768: *mut u64) -> i32;
     pub fn slideo_matcher_levels_points(m: *mut slideo_matcher, low_ppm: i32, high_ppm: i32, lo: *mut i32, hi: *mut i32) -> i32;
+    // frame shading (include/slideo_amd.h "Frame shading"): a bilinear Q8.8 gain field uint16 [gh + 1][gw + 1] in front of the levels
+    pub fn slideo_matcher_set_frame_shading(m: *mut slideo_matcher, aw: i32, ah: i32, cell: i32, gains: *const u16) -> i32;
+    pub fn slideo_matcher_frame_shading(
+        m: *const slideo_matcher, gains_out: *mut u16, capacity_elems: i64, aw: *mut i32, ah: *mut i32, cell: *mut i32, set_out: *mut i32,
+    ) -> i32;
+    pub fn slideo_group_set_frame_shading(g: *mut slideo_group, aw: i32, ah: i32, cell: i32, gains: *const u16) -> i32;
+    pub fn slideo_shading_bgr8(
+        m: *mut slideo_matcher, bgr: *const u8, width: i32, height: i32, stride_bytes: i32, bgr_out: *mut u8, out_capacity: i64,
+    ) -> i32;
+    pub fn slideo_shading_field(
+        cnt: *const u64, sum_f: *const u64, sum_p: *const u64, gw: i32, gh: i32, cell: i32, min_count: i64, min_gain_q8: i32, max_gain_q8: i32,
+        smooth: i32, gains_out: *mut u16, cells_used_out: *mut i32,
+    ) -> i32;
+    // match shading map (include/slideo_amd.h "Match shading map"): per-cell sums of matched pixel pairs, u64 [gh][gw] each
+    pub fn slideo_matcher_shading_begin(m: *mut slideo_matcher, cell: i32, min_inliers: i32, min_hits: i32, flat: i32) -> i32;
+    pub fn slideo_matcher_shading_end(m: *mut slideo_matcher) -> i32;
+    pub fn slideo_matcher_shading_info(
+        m: *mut slideo_matcher, cell: *mut i32, min_inliers: *mut i32, min_hits: *mut i32, flat: *mut i32, aw: *mut i32, ah: *mut i32, gw: *mut i32,
+        gh: *mut i32, frames_through: *mut i64,
+    ) -> i32;
+    pub fn slideo_matcher_shading_sums(
+        m: *mut slideo_matcher, cnt_out: *mut u64, sum_f_out: *mut u64, sum_p_out: *mut u64, capacity_elems: i64, gw: *mut i32, gh: *mut i32,
+        frames_through: *mut i64, frames_counted: *mut i64,
+    ) -> i32;
+    pub fn slideo_group_shading_begin(g: *mut slideo_group, cell: i32, min_inliers: i32, min_hits: i32, flat: i32) -> i32;
+    pub fn slideo_group_shading_end(g: *mut slideo_group) -> i32;
+    pub fn slideo_group_shading_info(
+        g: *mut slideo_group, cell: *mut i32, min_inliers: *mut i32, min_hits: *mut i32, flat: *mut i32, aw: *mut i32, ah: *mut i32, gw: *mut i32,
+        gh: *mut i32, frames_through: *mut i64,
+    ) -> i32;
+    pub fn slideo_group_shading_sums(
+        g: *mut slideo_group, cnt_out: *mut u64, sum_f_out: *mut u64, sum_p_out: *mut u64, capacity_elems: i64, gw: *mut i32, gh: *mut i32,
+        frames_through: *mut i64, frames_counted: *mut i64,
+    ) -> i32;
     // frame region (include/slideo_amd.h "Frame region"): frames stand for a rectified quadrilateral of themselves
     pub fn slideo_matcher_set_frame_region(
         m: *mut slideo_matcher,

@@ -117,6 +117,11 @@ pub struct HipImageVideoMatcher {
     /// ffi::slideo_matcher_levels_points learnt from a dim, low-contrast or colour-cast recording.  Pages are untouched; None:
     /// off.  The reference analyses the frames as they are.
     pub frame_levels: Option<Box<[u8; 768]>>,
+    /// (aw, ah, cell, gains): a bilinear Q8.8 gain field (slideo_group_set_frame_shading) over the aw x ah analysed image — uint16
+    /// [gh + 1][gw + 1] nodes `cell` (16, 32 or 64) pixels apart, 256 = 1.0 — applied in front of frame_levels: what
+    /// ffi::slideo_shading_field makes of per-cell sums, for the vignetting of a filmed projection screen.  Pages are untouched;
+    /// None: off.
+    pub frame_shading: Option<(i32, i32, i32, Vec<u16>)>,
     /// Which frame a gated frame is compared with (slideo_group_set_gate_reference): ffi::SLIDEO_GATE_PREVIOUS (default: the
     /// frame before, the reference's MarkSimilarIter) or ffi::SLIDEO_GATE_ANCHOR (the last frame that was flagged: a change
     /// spread over many frames is still flagged when every decoded frame is fed).  With several devices it needs
@@ -222,6 +227,7 @@ impl Default for HipImageVideoMatcher {
             yuv_transfer: (ffi::SLIDEO_YUV_TRANSFER_SDR, 0.0),
             pixel_format: ffi::SLIDEO_PIXEL_BGR8,
             frame_levels: None,
+            frame_shading: None,
             gate_reference: ffi::SLIDEO_GATE_PREVIOUS,
             gate_settle: (0.0, 0),
             group_gate_order: ffi::SLIDEO_GROUP_GATE_HALO,
@@ -286,6 +292,11 @@ impl<'i> ImageVideoMatcher<'i> for HipImageVideoMatcher {
             }
             if self.pixel_format != ffi::SLIDEO_PIXEL_BGR8 {
                 check(h, ffi::slideo_group_set_pixel_format(h, self.pixel_format));
+            }
+            if let Some((aw, ah, cell, gains)) = &self.frame_shading {
+                let nodes = ((*aw + *cell - 1) / *cell + 1) as usize * ((*ah + *cell - 1) / *cell + 1) as usize;
+                assert_eq!(gains.len(), nodes, "frame_shading is not (gh + 1) x (gw + 1) gains");
+                check(h, ffi::slideo_group_set_frame_shading(h, *aw, *ah, *cell, gains.as_ptr()));
             }
             if let Some(lut) = &self.frame_levels {
                 check(h, ffi::slideo_group_set_frame_levels(h, lut.as_ptr()));

@@ -65,6 +65,7 @@
  *   SLIDEO_EVIDENCE_MAX_FRAMES n  the frames limit of an evidence session, read at evidence_begin, 1..2^20 (the tests reach the refusal with it)
  *   SLIDEO_TONE_MAX_FRAMES n      the frames limit of a tone session, read at tone_begin, 1..2^31 (the tests reach the refusal with it)
  *   SLIDEO_PLACEMENT_MAX_FRAMES n the frames limit of a placement session, read at placement_begin, 1..2^20 (the tests reach the refusal with it)
+ *   SLIDEO_SHADING_MAX_FRAMES n  the frames limit of a shading session, read at shading_begin, 1..2^20 (the tests reach the refusal with it)
  *   SLIDEO_RANSAC_WINDOW=0        ransac_kernel's redraw schedule by the fixed point only                       [per unit]
  *   SLIDEO_RH_TAIL_ROUNDS n       verify_model 1: rounds before a candidate moves to ransac_h_tail_kernel (256; 0 = never) [per unit]
  *   SLIDEO_REFINE_LANE_LM 0|1     verify_model 1: the small candidates' LM in refine_h_kernel<1> / in the eigen kernel's lanes [per unit]
@@ -1039,6 +1040,75 @@ int32_t     slideo_matcher_levels_histogram(slideo_matcher* m, uint64_t* hist768
 /* Idle matcher.  The points of the definition.  SLIDEO_ERR_STATE without an observed frame; SLIDEO_ERR_INVALID_ARG for low_ppm or
  * high_ppm outside 0..1000000. */
 int32_t     slideo_matcher_levels_points(slideo_matcher* m, int32_t low_ppm, int32_t high_ppm, int32_t* lo /*3*/, int32_t* hi /*3*/);
+
+/* ---- Frame shading (extension: a smooth per-cell gain field in front of the levels, for vignetting and gradients) ---------------------
+ * The frame levels are ONE table per channel for the whole picture: they cannot undo a gradient across the screen.  A camera filming
+ * a projection screen sees exactly that — projector hot spot, screen gain and lens falloff darken the corners of the slide by a
+ * factor of two to five.  ORB and RANSAC survive it; the re-projection similarity 1 - RMS / 255 does not (docs/EXTENSIONS.md "Frame
+ * shading" has the figures).
+ * A matcher carries a FRAME SHADING, a frame setting like the levels: a field of Q8.8 gains on the nodes of a grid over the analysed
+ * image, off by default, under which every call launches, copies and budgets exactly what it did before the field existed.
+ * THE FIELD  in exact integers.  cell is 16, 32 or 64; gw = ceil(aw / cell), gh = ceil(ah / cell); node (i, j) sits at pixel (i *
+ *   cell, j * cell) for 0 <= i <= gw, 0 <= j <= gh; gains is uint16 [gh + 1][gw + 1], 256 = 1.0; every gain is at least 1 (a gain of
+ *   0 is refused, the node named).  For pixel (x, y):
+ *     i = x / cell, j = y / cell, fx = x - i * cell, fy = y - j * cell
+ *     L = g[j][i]   * (cell - fy) + g[j+1][i]   * fy
+ *     R = g[j][i+1] * (cell - fy) + g[j+1][i+1] * fy
+ *     G = (L * (cell - fx) + R * fx + cell * cell / 2) >> (2 * log2(cell))
+ *     out[c] = min(255, (in[c] * G + 128) >> 8)          c = B, G, R: one gain for all three
+ *   L * (cell - fx) + R * fx stays below 2^28 and in * G below 2^24.  An all-256 field is the identity and is stored as off: it
+ *   reports set == 0 and nothing new launches.  The field is bilinear between nodes and not constant per cell: a step at a cell edge
+ *   would be a FAST corner of the library's own making.  It is one gain for all channels: colour belongs to the levels table.
+ * WHERE IT STANDS  after the conversion and after the reduce or the rectify, and BEFORE the levels, which stay the last step in front
+ *   of the unit; everything "Frame levels" says stays true, with `in` the shaded image.  Both orders are exact for a power-law camera
+ *   tone; this one is the order under which a field and then a table can be learnt from the matches ("Match tone table" sees shaded
+ *   frames once a field is set, and the table it yields is applied after the field).
+ *   Contract, as for the levels: every call that stages frames returns, bit for bit, what the same call under the default returns on
+ *   the shaded images — verdicts, candidate traces, changed flags, similarities, small images, gate state and refs, activity,
+ *   content, levels, evidence, tone and placement counts; both doors, SIFT mode, the group's forms.  The frames a mask call kept are
+ *   not shaded twice.  Pages, the other single-image taps and slideo_matcher_gate_reset(small) are untouched.
+ *   A device frame is never written.  A frame call whose analysed size differs from the field's fails with SLIDEO_ERR_INVALID_ARG
+ *   before anything is touched, as under a frame mask.
+ * Kernel (csrc/shading.hip.h): shading_kernel, launched iff a field is set, in two instances — the plain one, and with a levels table
+ *   set too the fused one, which does the table look-up on the shaded bytes in the same pass: levels_kernel is then not launched.
+ *   levels_kernel's thread shape, loads and stores; a thread's four pixels lie in one cell, so it reads four nodes once.
+ * DEPARTURE: the reference analyses the frames as they are.
+ * Limits: the field is multiplicative, so a raised black is the table's job; one gain serves all channels; a fixed camera and screen
+ *   are assumed.  Out of scope: per-channel fields, a field in front of the reduce or the rectify, time-varying fields, shading pages.
+ * Every call returns SLIDEO_ERR_INVALID_ARG for a null handle or a null required pointer. */
+/* gains == NULL (or every node 256): off, and aw, ah, cell are not looked at.  Otherwise cell 16, 32 or 64 and 1 <= aw, ah <= 4096
+ * (SLIDEO_ERR_INVALID_ARG).  As slideo_matcher_set_frame_levels: before or after finalize; SLIDEO_ERR_STATE with units in flight; ends
+ * the kept frames and the evidence, tone, placement and shading sessions, and resets the gate state to "none". */
+int32_t     slideo_matcher_set_frame_shading(slideo_matcher* m, int32_t aw, int32_t ah, int32_t cell, const uint16_t* gains);
+/* *set_out = 1 with the field's *aw, *ah, *cell, or 0 with zeros there.  gains_out == NULL asks for those alone; otherwise the (gh +
+ * 1) * (gw + 1) nodes are written, or SLIDEO_ERR_CAPACITY (with the sizes set) when capacity_elems is smaller.  Off: nothing written. */
+int32_t     slideo_matcher_frame_shading(const slideo_matcher* m, uint16_t* gains_out, int64_t capacity_elems, int32_t* aw, int32_t* ah,
+                                         int32_t* cell, int32_t* set_out);
+/* Validates every member (idle) before changing any; resets the group's gate state. */
+int32_t     slideo_group_set_frame_shading(slideo_group* g, int32_t aw, int32_t ah, int32_t cell, const uint16_t* gains);
+/* Tap: ONE host BGR image of the field's size (SLIDEO_ERR_INVALID_ARG at another) -> width * height * 3 bytes at stride 3 * width
+ * (SLIDEO_ERR_CAPACITY when out_capacity is smaller), through shading_kernel as a frame's unit image goes: the plain instance, or,
+ * with a levels table set, the fused one (the shaded and levelled image).  No field: a row-by-row copy. */
+int32_t     slideo_shading_bgr8(slideo_matcher* m, const uint8_t* bgr, int32_t width, int32_t height, int32_t stride_bytes, uint8_t* bgr_out,
+                                int64_t out_capacity);
+/* A pure host function in integers (no handle, no device): the field of per-cell sums cnt, sum_f, sum_p [gh][gw] — samples, the sum
+ * of B + G + R over the FRAME pixels and over the PAGE-side pixels they are matched with, per cell of the analysed image.
+ *   1. a cell is valid iff cnt >= min_count and sum_f >= 1; its value is r = clamp((2 * 4096 * sum_p + sum_f) / (2 * sum_f),
+ *      16 * min_gain_q8, 16 * max_gain_q8) (Q12; the product in 128 bits)
+ *   2. fill: in rounds, every invalid cell with at least one valid 4-neighbour gets (2 * S + n) / (2 * n) over its n valid
+ *      4-neighbours' values of the previous round and becomes valid; repeated until none is invalid
+ *   3. smooth: `smooth` times, every cell becomes (2 * S + 9) / 18 over its edge-clamped 3x3 neighbourhood of the previous round
+ *   4. node (i, j) is the rounded mean (2 * S + n) / (2 * n) of the cells (i-1..i, j-1..j) that exist: 1, 2 or 4 cells
+ *   5. gain = clamp((node + 8) >> 4, min_gain_q8, max_gain_q8)
+ * gains_out: (gh + 1) * (gw + 1) nodes, what slideo_matcher_set_frame_shading takes; cells_used_out (may be null): the valid cells of
+ * step 1.  SLIDEO_ERR_INVALID_ARG, and nothing written: min_count < 1; bounds outside 1 <= min_gain_q8 <= 256 <= max_gain_q8 <=
+ * 65535; smooth outside 0..16; cell other than 16, 32, 64 or gw, gh outside 1..ceil(4096 / cell); a count above 2^54 or a sum above
+ * 765 * cnt (no pixel sums to more); no valid cell.
+ * It is an ESTIMATOR, a ratio of sums dominated by the bright background; filled cells are extrapolation; nothing is installed and no
+ * parameter has a default. */
+int32_t     slideo_shading_field(const uint64_t* cnt, const uint64_t* sum_f, const uint64_t* sum_p, int32_t gw, int32_t gh, int32_t cell,
+                                 int64_t min_count, int32_t min_gain_q8, int32_t max_gain_q8, int32_t smooth, uint16_t* gains_out,
+                                 int32_t* cells_used_out);
 
 /* ---- Working size (extension: the reference analyses every frame at the size it arrives in) ---------------------------------
  * A matcher carries a working size (max_w, max_h); (0, 0) = none, the default.  While one is set, a frame of w x h with
@@ -2151,6 +2221,66 @@ int32_t     slideo_group_placement_sums(slideo_group* g, uint64_t* n_out, uint64
 int32_t     slideo_placement_quad(const uint64_t* n, const uint64_t* sfx, const uint64_t* sfy, const uint64_t* su, const uint64_t* sv, int32_t gw,
                                   int32_t gh, int32_t cell, int32_t aw, int32_t ah, int64_t min_count, double trim_px, int32_t rounds,
                                   double* quad_out8, double* H_out9, int32_t* cells_used, double* rms_px);
+
+/* ---- Match shading map (extension: the measurement a frame shading can be made from, out of the matches) ------------------------------
+ * The frame shading ("Frame shading") needs its gains.  What can give them is what the tone table is learnt from — the pixel pairs
+ * (frame pixel, page small-image pixel) that a matched frame's contributing candidate puts in correspondence — binned by WHERE they
+ * lie in the analysed frame instead of by their value: the ratio of the page side's sum to the frame side's sum over a cell is the
+ * gain that cell wants.
+ * A matcher carries a SHADING SESSION, off by default, beside the evidence, tone and placement sessions and built like the placement
+ * session.  Its state is "none", or: a cell (16, 32 or 64), min_inliers >= 0, min_hits >= 1, flat in 0..255, an analysed size (aw,
+ * ah), not fixed until the first counted call; the grid gw = ceil(aw / cell), gh = ceil(ah / cell); three sums cnt, sum_f, sum_p
+ * [gh][gw] and frames_counted, all u64 on the device; frames_through.
+ * Everything up to the sample is the tone table's ("Match tone table"), unchanged: the contributor (the candidate slot with a model
+ * and the most inliers, at least min_inliers, ties to the first slot), its hits by the evidence map's float64 test (at least
+ * min_hits of them), the hit box in page coordinates, and the sample test — a small-image pixel (i, j) is a sample iff its centre lies
+ * in the box, its four edge-clamped neighbours differ from it by at most `flat` in every channel, and (Xi, Yi) = (floor(X + 0.5),
+ * floor(Y + 0.5)) lies in the analysed frame.  For a sample, with k = (Yi / cell) * gw + Xi / cell:
+ *   cnt[k] += 1;  sum_f[k] += B + G + R of the frame pixel (Xi, Yi);  sum_p[k] += B + G + R of the small-image pixel (i, j)
+ * and frames_counted += 1 per contributing frame.
+ * The placement map's rules hold unchanged wherever this text does not say otherwise: the call forms that count, the first counted
+ * call fixing (aw, ah) and the SLIDEO_ERR_INVALID_ARG of a later call at another analysed size (the message names both sizes), what
+ * ends a session (slideo_matcher_shading_end, the setters that change the analysed image — the frame shading's and the levels' own
+ * among them —, a counted call that fails after its first unit was submitted), the idle and state rules, SIFT mode
+ * (SLIDEO_ERR_UNSUPPORTED in either order), and a unit that is run again counting once.  Any combination of the four sessions may be
+ * open at once; each one's results are what they are alone.  Verdict bytes are identical with and without a session.
+ * Its own rules: begin is refused with SLIDEO_ERR_STATE while a frame shading is set (a field learnt on shaded frames is not the
+ * source's) and while a frame levels table is set (a gain learnt behind the table cannot be installed in front of it: learn the field
+ * first and the table second).  A grid of more than 4096 cells is refused at the first counted call with SLIDEO_ERR_UNSUPPORTED, the
+ * next cell size named (1080p at cell 32 and 4K at cell 64 have 2040).  A session holds at most 2^20 frames through.
+ * Installing nothing: the caller reads the sums out, makes a field with slideo_shading_field ("Frame shading"), looks at it, and hands
+ * it to slideo_matcher_set_frame_shading.  No parameter has a default.
+ * Where it runs (csrc/shading.hip.h, launched by csrc/stage_verify.hip unit_verify behind verdict_kernel and the other sessions'
+ * kernels, on the unit's stream, only while a session is open): shading_map_kernel, one block of 256 threads per frame; the tone
+ * kernel's phase 1; work items of 32 consecutive small-image pixels whose thread keeps one cell index with a run count and two run
+ * sums and adds to the block's u32 bins [3][cells] in LDS (at most 48 KB) only when the cell changes; row tiles of at most 2^22
+ * pixels; the nonzero bins go to the u64 arrays with 64-bit atomics whose result is not read.
+ * Limits: the estimator is a ratio of sums, dominated by the bright background; a speaker or an occluder biases the cells it covers;
+ * clipped highlights bias low; a FIXED camera and screen are assumed; cell 16 needs more frames than cell 32.
+ * Every call returns SLIDEO_ERR_INVALID_ARG for a null handle or a null required pointer. */
+/* Idle matcher, no shading session open, no frame shading and no frame levels set (SLIDEO_ERR_STATE otherwise); cell other than 16,
+ * 32, 64, min_inliers < 0, min_hits < 1 or flat outside 0..255: SLIDEO_ERR_INVALID_ARG; SIFT mode: SLIDEO_ERR_UNSUPPORTED.  Afterwards
+ * the session is empty: no size, every sum 0.  May be called before finalize. */
+int32_t     slideo_matcher_shading_begin(slideo_matcher* m, int32_t cell, int32_t min_inliers, int32_t min_hits, int32_t flat);
+/* Idle matcher.  The state "none"; the device buffer is released.  Fine when the state is "none" already. */
+int32_t     slideo_matcher_shading_end(slideo_matcher* m);
+/* The session's values (*aw, *ah, *gw, *gh are 0 before the first counted call) and the frames of the collected units.
+ * SLIDEO_ERR_STATE in the state "none". */
+int32_t     slideo_matcher_shading_info(slideo_matcher* m, int32_t* cell, int32_t* min_inliers, int32_t* min_hits, int32_t* flat, int32_t* aw,
+                                        int32_t* ah, int32_t* gw, int32_t* gh, int64_t* frames_through);
+/* Idle matcher (SLIDEO_ERR_STATE with units in flight, and in the state "none").  The three arrays: gh rows of gw elements each; all
+ * three NULL asks for the sizes and frame counts only (some NULL: SLIDEO_ERR_INVALID_ARG).  Before the first counted call *gw == *gh
+ * == 0 and nothing is written.  SLIDEO_ERR_CAPACITY (with the sizes set) when gw * gh > capacity_elems. */
+int32_t     slideo_matcher_shading_sums(slideo_matcher* m, uint64_t* cnt_out, uint64_t* sum_f_out, uint64_t* sum_p_out, int64_t capacity_elems,
+                                        int32_t* gw, int32_t* gh, int64_t* frames_through, int64_t* frames_counted);
+/* The group forms: begin and end start and end EVERY member's session (validated on every member before one is touched); info and
+ * sums return the members' element-wise sums (a member whose shards were all empty fixes no size).  The frames limit holds per member. */
+int32_t     slideo_group_shading_begin(slideo_group* g, int32_t cell, int32_t min_inliers, int32_t min_hits, int32_t flat);
+int32_t     slideo_group_shading_end(slideo_group* g);
+int32_t     slideo_group_shading_info(slideo_group* g, int32_t* cell, int32_t* min_inliers, int32_t* min_hits, int32_t* flat, int32_t* aw, int32_t* ah,
+                                      int32_t* gw, int32_t* gh, int64_t* frames_through);
+int32_t     slideo_group_shading_sums(slideo_group* g, uint64_t* cnt_out, uint64_t* sum_f_out, uint64_t* sum_p_out, int64_t capacity_elems, int32_t* gw,
+                                      int32_t* gh, int64_t* frames_through, int64_t* frames_counted);
 
 #ifdef __cplusplus
 }

@@ -215,6 +215,43 @@ def _levels_table(lut):
     return np.ascontiguousarray(a.reshape(3, 256), np.uint8)
 
 
+def _shading_field(aw, ah, cell, gains):
+    """A frame shading as (aw, ah, cell, contiguous uint16 [gh + 1, gw + 1]); ValueError for another cell, shape, dtype or range."""
+    aw, ah, cell = int(aw), int(ah), int(cell)
+    if cell not in (16, 32, 64):
+        raise ValueError("frame shading: cell %d is none of 16, 32, 64" % cell)
+    if aw < 1 or ah < 1:
+        raise ValueError("frame shading: analysed size %dx%d" % (aw, ah))
+    gw, gh = -(-aw // cell), -(-ah // cell)
+    a = np.asarray(gains)
+    if a.shape not in ((gh + 1, gw + 1), ((gh + 1) * (gw + 1),)):
+        raise ValueError("frame shading: expected gains of shape [%d, %d] (gh + 1, gw + 1), got %s" % (gh + 1, gw + 1, a.shape))
+    if a.dtype != np.uint16:
+        if not np.issubdtype(a.dtype, np.integer) or a.min() < 0 or a.max() > 65535:
+            raise ValueError("frame shading: the gains are integers in 1..65535 (Q8.8, 256 = 1.0)")
+    if a.min() < 1:
+        raise ValueError("frame shading: a gain of 0 (every gain is at least 1)")
+    return aw, ah, cell, np.ascontiguousarray(a.reshape(gh + 1, gw + 1), np.uint16)
+
+
+def shading_field(cnt, sum_f, sum_p, cell, min_count, min_gain, max_gain, smooth):
+    """slideo_shading_field: the Q8.8 nodes uint16 [gh + 1, gw + 1] of per-cell sums cnt, sum_f, sum_p [gh, gw], and the number of
+    valid cells.  min_gain, max_gain: Q8.8 integers.  SlideoError for what the header refuses."""
+    cnt = np.ascontiguousarray(cnt, np.uint64)
+    if cnt.ndim != 2:
+        raise ValueError("shading_field: cnt is [gh, gw], got %s" % (cnt.shape,))
+    gh, gw = cnt.shape
+    sum_f, sum_p = np.ascontiguousarray(sum_f, np.uint64), np.ascontiguousarray(sum_p, np.uint64)
+    if sum_f.shape != cnt.shape or sum_p.shape != cnt.shape:
+        raise ValueError("shading_field: the three arrays share one shape")
+    out, used = np.empty((gh + 1, gw + 1), np.uint16), C.c_int32()
+    rc = lib().slideo_shading_field(_p(cnt), _p(sum_f), _p(sum_p), gw, gh, int(cell), C.c_int64(int(min_count)), int(min_gain), int(max_gain),
+                                    int(smooth), _p(out), C.byref(used))
+    if rc != OK:
+        raise SlideoError(rc, "slideo_shading_field")
+    return out, used.value
+
+
 def frame_levels_lut(lo, hi):
     """slideo_frame_levels_lut: the stretch table uint8 [3, 256] (B, G, R) of the points lo, hi (three each, or one for all three):
     lut[c][x] = clamp(floor((510 (x - lo) + (hi - lo)) / (2 (hi - lo))), 0, 255).  ValueError unless 0 <= lo < hi <= 255."""
@@ -464,6 +501,10 @@ EXPORTS = [
     "slideo_matcher_set_frame_levels", "slideo_matcher_frame_levels", "slideo_group_set_frame_levels", "slideo_frame_levels_lut",
     "slideo_levels_bgr8", "slideo_matcher_levels_begin", "slideo_matcher_levels_end", "slideo_matcher_levels_info",
     "slideo_matcher_levels_histogram", "slideo_matcher_levels_points",
+    "slideo_matcher_set_frame_shading", "slideo_matcher_frame_shading", "slideo_group_set_frame_shading", "slideo_shading_bgr8",
+    "slideo_shading_field",
+    "slideo_matcher_shading_begin", "slideo_matcher_shading_end", "slideo_matcher_shading_info", "slideo_matcher_shading_sums",
+    "slideo_group_shading_begin", "slideo_group_shading_end", "slideo_group_shading_info", "slideo_group_shading_sums",
     "slideo_matcher_activity_begin", "slideo_matcher_activity_end", "slideo_matcher_observe_frames_bgr8", "slideo_matcher_observe_frames_yuv420",
     "slideo_matcher_observe_frames_bgr8_dev", "slideo_matcher_observe_frames_yuv420_dev", "slideo_matcher_activity_info",
     "slideo_matcher_activity_counts", "slideo_matcher_activity_mask",
@@ -704,6 +745,18 @@ def lib():
             L.slideo_matcher_levels_info.argtypes = [vp, vp, vp]
             L.slideo_matcher_levels_histogram.argtypes = [vp, vp]
             L.slideo_matcher_levels_points.argtypes = [vp, i32, i32, vp, vp]
+        if hasattr(L, "slideo_matcher_set_frame_shading"):
+            L.slideo_matcher_set_frame_shading.argtypes = [vp, i32, i32, i32, vp]
+            L.slideo_matcher_frame_shading.argtypes = [vp, vp, i64, vp, vp, vp, vp]
+            L.slideo_group_set_frame_shading.argtypes = [vp, i32, i32, i32, vp]
+            L.slideo_shading_bgr8.argtypes = [vp, vp, i32, i32, i32, vp, i64]
+            L.slideo_shading_field.argtypes = [vp, vp, vp, i32, i32, i32, i64, i32, i32, i32, vp, vp]
+        if hasattr(L, "slideo_matcher_shading_begin"):
+            for who in ("matcher", "group"):
+                getattr(L, "slideo_%s_shading_begin" % who).argtypes = [vp, i32, i32, i32, i32]
+                getattr(L, "slideo_%s_shading_end" % who).argtypes = [vp]
+                getattr(L, "slideo_%s_shading_info" % who).argtypes = [vp] * 10
+                getattr(L, "slideo_%s_shading_sums" % who).argtypes = [vp, vp, vp, vp, i64, vp, vp, vp, vp]
         if hasattr(L, "slideo_matcher_set_gate_reference"):
             vp, i32, u32 = C.c_void_p, C.c_int32, C.c_uint32
             L.slideo_matcher_set_gate_reference.argtypes = [vp, u32]
@@ -891,6 +944,32 @@ class _FrameCalls:
         sums = np.zeros((5, gh.value, gw.value), np.uint64)
         if sums.size:
             self._check(fn(self._h, *[_p(sums[i]) for i in range(5)], C.c_int64(sums[0].size), C.byref(gw), C.byref(gh), C.byref(ft), C.byref(fc)))
+        return sums, ft.value, fc.value
+
+    # ---- match shading map (include/slideo_amd.h "Match shading map"); a Group's are the members' sums ----
+    def shading_begin(self, cell, min_inliers, min_hits, flat):
+        """An empty shading session: match calls from now on sum, per cell x cell cell of the analysed image, the samples of the tone
+        table's sampler that land there, their frame pixels' B + G + R and their page small-image pixels' B + G + R.  Refused while a
+        frame shading or a frame levels table is set."""
+        self._check(getattr(lib(), self._SETS + "shading_begin")(self._h, int(cell), int(min_inliers), int(min_hits), int(flat)))
+
+    def shading_end(self):
+        self._check(getattr(lib(), self._SETS + "shading_end")(self._h))
+
+    def shading_info(self):
+        """-> {cell, min_inliers, min_hits, flat, aw, ah, gw, gh, frames_through} (aw == 0 before the first counted call)."""
+        v = [C.c_int32() for _ in range(8)] + [C.c_int64()]
+        self._check(getattr(lib(), self._SETS + "shading_info")(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("cell", "min_inliers", "min_hits", "flat", "aw", "ah", "gw", "gh", "frames_through"), (x.value for x in v)))
+
+    def shading_sums(self):
+        """-> (sums uint64 [3, gh, gw]: cnt, sum_f, sum_p; frames_through, frames_counted); [3, 0, 0] before the first counted call."""
+        gw, gh, ft, fc = C.c_int32(), C.c_int32(), C.c_int64(), C.c_int64()
+        fn = getattr(lib(), self._SETS + "shading_sums")
+        self._check(fn(self._h, None, None, None, C.c_int64(0), C.byref(gw), C.byref(gh), C.byref(ft), C.byref(fc)))
+        sums = np.zeros((3, gh.value, gw.value), np.uint64)
+        if sums.size:
+            self._check(fn(self._h, *[_p(sums[i]) for i in range(3)], C.c_int64(sums[0].size), C.byref(gw), C.byref(gh), C.byref(ft), C.byref(fc)))
         return sums, ft.value, fc.value
 
     def last_candidates(self, frame_in_batch):
@@ -1246,6 +1325,32 @@ class _FrameCalls:
         if rc != OK:
             raise SlideoError(rc, "frame_levels")
         return out if on.value else None
+
+    # frame shading (include/slideo_amd.h "Frame shading"): a bilinear Q8.8 gain field on the unit's image, in front of the levels
+    def set_frame_shading(self, aw=0, ah=0, cell=0, gains=None):
+        """gains: uint16 [gh + 1, gw + 1] Q8.8 nodes over the aw x ah analysed image at `cell` (16, 32, 64), or None (= all 256) for
+        off.  Every frame call then analyses min(255, (image * G + 128) >> 8); pages and single-image taps are untouched.  The
+        matcher must be idle; ends the kept frames and the match sessions and resets the gate state."""
+        if gains is not None:
+            aw, ah, cell, gains = _shading_field(aw, ah, cell, gains)
+        self._check(getattr(lib(), self._SETS + "set_frame_shading")(self._h, int(aw), int(ah), int(cell), _p(gains) if gains is not None else None))
+
+    def frame_shading(self):
+        """(aw, ah, cell, gains uint16 [gh + 1, gw + 1]) in force, or None when off (a Group: member 0's)."""
+        if not hasattr(lib(), "slideo_matcher_frame_shading"):      # (SLIDEO_LIB_PATH may name an older build: tools/ab_libs.sh)
+            return None
+        aw, ah, cell, on = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int32()
+        rc = lib().slideo_matcher_frame_shading(self._mask_owner(), None, C.c_int64(0), C.byref(aw), C.byref(ah), C.byref(cell), C.byref(on))
+        if rc != OK:
+            raise SlideoError(rc, "frame_shading")
+        if not on.value:
+            return None
+        gw, gh = -(-aw.value // cell.value), -(-ah.value // cell.value)
+        out = np.empty((gh + 1, gw + 1), np.uint16)
+        rc = lib().slideo_matcher_frame_shading(self._mask_owner(), _p(out), C.c_int64(out.size), C.byref(aw), C.byref(ah), C.byref(cell), C.byref(on))
+        if rc != OK:
+            raise SlideoError(rc, "frame_shading")
+        return aw.value, ah.value, cell.value, out
 
     def _mask_owner(self):
         """The matcher handle the mask's getters read (a group's members agree: member 0)."""
@@ -1711,6 +1816,22 @@ class Matcher(_FrameCalls):
                 raise ValueError("levels_bgr: the buffer holds %d bytes, height * stride is %d" % (image.size, h * int(stride)))
         out = np.empty((h, w, 3), np.uint8)
         self._check(lib().slideo_levels_bgr8(self._h, _p(image), w, h, int(stride), _p(out), C.c_int64(out.size)))
+        return out
+
+    def shading_bgr(self, image, stride=None):
+        """One host BGR image [h, w, 3] of the field's size through the shading step as a frame's unit image goes: the field and, with
+        a levels table set, the table in the same pass (the tap; no field: the image itself).  `stride`: as levels_bgr."""
+        if stride is None:
+            image = _img3(image)
+            h, w, _ = image.shape
+            stride = w * 3
+        else:
+            image, w, h = image
+            image = np.ascontiguousarray(image, np.uint8)
+            if image.size < h * int(stride):
+                raise ValueError("shading_bgr: the buffer holds %d bytes, height * stride is %d" % (image.size, h * int(stride)))
+        out = np.empty((h, w, 3), np.uint8)
+        self._check(lib().slideo_shading_bgr8(self._h, _p(image), w, h, int(stride), _p(out), C.c_int64(out.size)))
         return out
 
     def levels_begin(self):

@@ -469,6 +469,9 @@ int32_t slideo_group_set_frame_levels(slideo_group* g, const uint8_t* lut768) {
     if (g) for (const slideo_matcher* m : g->members) open |= m->levels.on;
     return group_set(g, SET_YUV_DESCRIPTION, [&](const FrameSettings& s) { return propose_frame_levels(s, lut768, open); });
 }
+int32_t slideo_group_set_frame_shading(slideo_group* g, int32_t aw, int32_t ah, int32_t cell, const uint16_t* gains) {
+    return group_set(g, SET_YUV_DESCRIPTION, [&](const FrameSettings& s) { return propose_frame_shading(s, aw, ah, cell, gains); });
+}
 
 // (the group's own rule first: ANCHOR needs a group of one member or the gate order CHAIN, and a refused call changes no member)
 int32_t slideo_group_set_gate_reference(slideo_group* g, uint32_t ref) {
@@ -1041,6 +1044,89 @@ int32_t slideo_group_placement_sums(slideo_group* g, uint64_t* n_out, uint64_t* 
         uint64_t* p = given ? part.data() : nullptr;
         check_member_call(m, slideo_matcher_placement_sums(m, p, p ? p + nc : p, p ? p + 2 * nc : p, p ? p + 3 * nc : p, p ? p + 4 * nc : p, nc, &w, &h, &t, &c));
         for (int i = 0; given && i < 5; ++i)
+            for (int64_t j = 0; j < nc; ++j) outs[i][j] += part[(size_t)(i * nc + j)];
+        counted += c;
+    }
+    *frames_counted = counted;
+    GROUP_CATCH(g)
+}
+
+// ---- Match shading map (include/slideo_amd.h "Match shading map"): every member carries a session, the read-outs return the sums ------
+int32_t slideo_group_shading_begin(slideo_group* g, int32_t cell, int32_t min_inliers, int32_t min_hits, int32_t flat) {
+    if (!g) return SLIDEO_ERR_INVALID_ARG;
+    GROUP_TRY
+    // validated on every member before one is touched: the matcher's own rules
+    for (slideo_matcher* m : g->members) shading_map_begin_check(m, cell, min_inliers, min_hits, flat);
+    for (slideo_matcher* m : g->members) check_member_call(m, slideo_matcher_shading_begin(m, cell, min_inliers, min_hits, flat));
+    GROUP_CATCH(g)
+}
+
+int32_t slideo_group_shading_end(slideo_group* g) {
+    if (!g) return SLIDEO_ERR_INVALID_ARG;
+    GROUP_TRY
+    for (slideo_matcher* m : g->members) require_idle(m);
+    for (slideo_matcher* m : g->members) check_member_call(m, slideo_matcher_shading_end(m));
+    GROUP_CATCH(g)
+}
+
+namespace {
+// the members' sessions as one: every member's open, the members that counted agree on the analysed size
+void group_shading_map(slideo_group* g, slideo_matcher::ShadingMap& sum) {
+    sum = slideo_matcher::ShadingMap{};
+    for (slideo_matcher* m : g->members) {
+        const slideo_matcher::ShadingMap& H = m->shading_map;
+        if (!H.on) fail(SLIDEO_ERR_STATE, "no shading session on every member: slideo_group_shading_begin first");
+        if (!sum.on) { sum = H; sum.aw = sum.ah = sum.gw = sum.gh = 0; sum.through = 0; }
+        if (H.cell != sum.cell || H.min_inliers != sum.min_inliers || H.min_hits != sum.min_hits || H.flat != sum.flat)
+            fail(SLIDEO_ERR_STATE, "the members' shading sessions differ (one was begun directly)");
+        if (H.aw > 0) {
+            if (sum.aw > 0 && (sum.aw != H.aw || sum.ah != H.ah))
+                fail(SLIDEO_ERR_STATE, "the members' shading sessions count at %dx%d and %dx%d (a member was called directly)", sum.aw, sum.ah, H.aw, H.ah);
+            sum.aw = H.aw; sum.ah = H.ah; sum.gw = H.gw; sum.gh = H.gh;
+        }
+        sum.through += H.through;
+    }
+}
+}  // namespace
+
+int32_t slideo_group_shading_info(slideo_group* g, int32_t* cell, int32_t* min_inliers, int32_t* min_hits, int32_t* flat, int32_t* aw, int32_t* ah,
+                                  int32_t* gw, int32_t* gh, int64_t* frames_through) {
+    if (!g) return SLIDEO_ERR_INVALID_ARG;
+    GROUP_TRY
+    if (!cell || !min_inliers || !min_hits || !flat || !aw || !ah || !gw || !gh || !frames_through) fail(SLIDEO_ERR_INVALID_ARG, "null output");
+    slideo_matcher::ShadingMap H;
+    group_shading_map(g, H);
+    *cell = H.cell; *min_inliers = H.min_inliers; *min_hits = H.min_hits; *flat = H.flat; *aw = H.aw; *ah = H.ah; *gw = H.gw; *gh = H.gh;
+    *frames_through = H.through;
+    GROUP_CATCH(g)
+}
+
+int32_t slideo_group_shading_sums(slideo_group* g, uint64_t* cnt_out, uint64_t* sum_f_out, uint64_t* sum_p_out, int64_t capacity_elems, int32_t* gw,
+                                  int32_t* gh, int64_t* frames_through, int64_t* frames_counted) {
+    if (!g) return SLIDEO_ERR_INVALID_ARG;
+    GROUP_TRY
+    if (!gw || !gh || !frames_through || !frames_counted) fail(SLIDEO_ERR_INVALID_ARG, "null gw/gh/frames_through/frames_counted");
+    for (slideo_matcher* m : g->members) require_idle(m);
+    slideo_matcher::ShadingMap H;
+    group_shading_map(g, H);
+    *gw = H.gw; *gh = H.gh; *frames_through = H.through; *frames_counted = 0;
+    if (H.aw == 0) return SLIDEO_OK;
+    uint64_t* outs[3] = {cnt_out, sum_f_out, sum_p_out};
+    int given = 0;
+    for (uint64_t* o : outs) given += o != nullptr;
+    if (given != 0 && given != 3) fail(SLIDEO_ERR_INVALID_ARG, "the three output arrays go together");
+    const int64_t nc = (int64_t)H.gw * H.gh;
+    if (given && nc > capacity_elems) fail(SLIDEO_ERR_CAPACITY, "the sums need %lld elements each", (long long)nc);
+    // (a member's sums stay below 765 * 2^24 * 2^20 < 2^54: the members' sums stay inside u64)
+    std::vector<uint64_t> part(given ? (size_t)nc * 3 : 0);
+    for (int i = 0; given && i < 3; ++i) std::fill(outs[i], outs[i] + nc, (uint64_t)0);
+    int64_t counted = 0;
+    for (slideo_matcher* m : g->members) {
+        if (m->shading_map.aw == 0) continue;            // (its shards were empty: nothing counted)
+        int32_t w = 0, h = 0; int64_t t = 0, c = 0;
+        uint64_t* p = given ? part.data() : nullptr;
+        check_member_call(m, slideo_matcher_shading_sums(m, p, p ? p + nc : p, p ? p + 2 * nc : p, nc, &w, &h, &t, &c));
+        for (int i = 0; given && i < 3; ++i)
             for (int64_t j = 0; j < nc; ++j) outs[i][j] += part[(size_t)(i * nc + j)];
         counted += c;
     }

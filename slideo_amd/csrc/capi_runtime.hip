@@ -1,5 +1,6 @@
 // capi_runtime.hip — handles, page database, workspace slots, unit submit / collect and the match entry points of include/slideo_amd.h (no kernel of its own).
 #include "runtime.hpp"
+#include "shading_field.h"
 #include <chrono>
 
 using namespace slideo;
@@ -148,6 +149,11 @@ void resolve_unit(const slideo_matcher* m, FrameSrc& src) {
         working_size_rule(src.w, src.h, fs.work_w, fs.work_h, rw, rh);
         src.plan.unit(PREP_REDUCE, rw, rh, small_area);
     } else src.plan.unit(PREP_NONE, src.w, src.h, small_area);
+    // (a frame shading holds frames of its own analysed size only, as a frame mask does: refused before anything is touched)
+    const FrameShading& F = fs.shading;
+    if (src.shading && (src.plan.uw != F.aw || src.plan.uh != F.ah))
+        fail(SLIDEO_ERR_INVALID_ARG, "frames analysed at %dx%d under a frame shading of %dx%d (slideo_matcher_set_frame_shading)", src.plan.uw, src.plan.uh,
+             F.aw, F.ah);
 }
 
 void resolve_frames(const slideo_matcher* m, FrameSrc& src, bool match) {
@@ -186,6 +192,13 @@ void settings_commit(slideo_matcher* m, Setting what, FrameSettings next, const 
         HIP_CHECK(hipSetDevice(m->device));
         m->d_levels.reserve(768);
         HIP_CHECK(hipMemcpy(m->d_levels.p, next.levels.lut, 768, hipMemcpyHostToDevice));
+    }
+    // a new gain field's device copy (likewise; the nodes are shared, so another pointer is another field)
+    if (next.shading.set && next.shading.gains != m->fs.shading.gains) {
+        HIP_CHECK(hipSetDevice(m->device));
+        const size_t bytes = next.shading.gains->size() * sizeof(uint16_t);
+        m->d_shading.reserve(bytes);
+        HIP_CHECK(hipMemcpy(m->d_shading.p, next.shading.gains->data(), bytes, hipMemcpyHostToDevice));
     }
     // a new transfer's tables (likewise)
     if (next.yuv.transfer != SLIDEO_YUV_TRANSFER_SDR && (next.yuv.transfer != m->fs.yuv.transfer || next.yuv.white_nits != m->fs.yuv.white_nits)) {
@@ -266,13 +279,16 @@ DevFrames stage_frames(slideo_matcher* m, Slot& S, const FrameSrc& src, int firs
     }
     // frame levels: the last step in front of the unit, in place on the staged image — but plain device BGR frames, which nothing has
     // staged yet, out of the caller's memory (never written) into the stage, rows as far apart as the caller's
+    // frame shading: in front of the levels, by the same rule; with both set ONE pass does both (shading_kernel's fused instance)
     if (!pre) {
-        if (src.levels) launch_levels(m, p, fs, src.stride, stage, fb, src.stride, src.w, src.h, n, S.st);
+        if (src.shading) launch_shading(m, src.levels, p, fs, src.stride, stage, fb, src.stride, src.w, src.h, n, S.st);
+        else if (src.levels) launch_levels(m, p, fs, src.stride, stage, fb, src.stride, src.w, src.h, n, S.st);
         return DevFrames{stage, src.w, src.h, src.stride, fb};
     }
     if (P.prep == PREP_RECTIFY) launch_rectify(m->fs.region, p, fs, src.stride, n, stage, S.st);
     else launch_reduce(m, p, fs, src.stride, src.w, src.h, uw, uh, n, stage, S.st);
-    if (src.levels) launch_levels(m, stage, ub, uw * 3, stage, ub, uw * 3, uw, uh, n, S.st);
+    if (src.shading) launch_shading(m, src.levels, stage, ub, uw * 3, stage, ub, uw * 3, uw, uh, n, S.st);
+    else if (src.levels) launch_levels(m, stage, ub, uw * 3, stage, ub, uw * 3, uw, uh, n, S.st);
     return DevFrames{stage, uw, uh, uw * 3, ub};
 }
 
@@ -413,6 +429,7 @@ static void unit_collect_body(slideo_matcher* m, Slot& S, slideo_verdict* out_ho
     std::memcpy(out_host, ho, (size_t)n * sizeof(slideo_verdict));
     tone_tally(m, n);
     placement_tally(m, n);
+    shading_map_tally(m, n);
     evidence_tally(m, out_host, n);                  // (the run whose verdicts are returned: evidence_kernel counted this one alone)
     const size_t base = m->last_fcs.size();
     m->last_fcs.resize(base + n);
@@ -448,6 +465,7 @@ void match_frames_impl(slideo_matcher* m, int n, FrameSrc src, slideo_verdict* o
     evidence_admit(m, src.plan.uw, src.plan.uh, n);
     tone_admit(m, n);
     placement_admit(m, src.plan.uw, src.plan.uh, n);
+    shading_map_admit(m, src.plan.uw, src.plan.uh, n);
     int unit = unit_fit(m, src, n, gated);
     area_class_for(m, src.plan.uw, src.plan.uh);
     upload_area(m);
@@ -518,6 +536,7 @@ static void submit_impl(slideo_matcher* m, int32_t n_frames, FrameSrc src, void*
     evidence_admit(m, src.plan.uw, src.plan.uh, n_frames);
     tone_admit(m, n_frames);
     placement_admit(m, src.plan.uw, src.plan.uh, n_frames);
+    shading_map_admit(m, src.plan.uw, src.plan.uh, n_frames);
     area_class_for(m, src.plan.uw, src.plan.uh);
     upload_area(m);
     { bool any = false; for (const Slot& c : m->slots) any |= c.busy; if (!any) m->last_fcs.clear(); }
@@ -1322,7 +1341,7 @@ int32_t slideo_pixels_to_bgr8(slideo_matcher* m, const uint8_t* frame, int32_t w
     if (!frame || !bgr_out) fail(SLIDEO_ERR_INVALID_ARG, "null frame/bgr_out");
     FrameSrc img = FrameSrc::bgr8(frame, false, width, height, stride_bytes, -1);
     img.describe(m->fs);
-    img.levels = false;                             // (the conversion's image: the frame levels come behind it, slideo_levels_bgr8)
+    img.levels = img.shading = false;               // (the conversion's image: the shading and the levels come behind it, slideo_levels_bgr8)
     validate_frames(img);
     const size_t row = (size_t)width * 3, fb = row * (size_t)height;
     if ((int64_t)fb > out_capacity) fail(SLIDEO_ERR_CAPACITY, "the BGR image needs %zu bytes", fb);
@@ -1378,6 +1397,60 @@ int32_t slideo_levels_bgr8(slideo_matcher* m, const uint8_t* bgr, int32_t width,
     HIP_CHECK(hipMemcpy2DAsync(bgr_out, row, f.p, (size_t)f.stride, row, (size_t)height, hipMemcpyDeviceToHost, S.st));
     HIP_CHECK(hipStreamSynchronize(S.st));
     API_CATCH(m)
+}
+
+// ---- Frame shading (include/slideo_amd.h "Frame shading") ---------------------------------------------------------------------------
+
+int32_t slideo_matcher_set_frame_shading(slideo_matcher* m, int32_t aw, int32_t ah, int32_t cell, const uint16_t* gains) {
+    return matcher_set(m, SET_YUV_DESCRIPTION, [&](const FrameSettings& s) { return propose_frame_shading(s, aw, ah, cell, gains); });
+}
+
+int32_t slideo_matcher_frame_shading(const slideo_matcher* m, uint16_t* gains_out, int64_t capacity_elems, int32_t* aw, int32_t* ah, int32_t* cell,
+                                     int32_t* set_out) {
+    if (!m || !aw || !ah || !cell || !set_out) return SLIDEO_ERR_INVALID_ARG;
+    const FrameShading& F = m->fs.shading;
+    *set_out = F.set ? 1 : 0;
+    *aw = F.aw; *ah = F.ah; *cell = F.cell;
+    if (!F.set || !gains_out) return SLIDEO_OK;
+    if ((int64_t)F.gains->size() > capacity_elems) return SLIDEO_ERR_CAPACITY;
+    std::copy(F.gains->begin(), F.gains->end(), gains_out);
+    return SLIDEO_OK;
+}
+
+// Tap: one host BGR image of the field's size through shading_kernel as a frame's unit image goes (in place on the slot's stage): the
+// plain instance, or with a levels table set the fused one — the shaded and levelled image.  No field: a row-by-row copy
+int32_t slideo_shading_bgr8(slideo_matcher* m, const uint8_t* bgr, int32_t width, int32_t height, int32_t stride_bytes, uint8_t* bgr_out,
+                            int64_t out_capacity) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    if (!bgr || !bgr_out) fail(SLIDEO_ERR_INVALID_ARG, "null bgr/bgr_out");
+    FrameSrc img = FrameSrc::image(bgr, width, height, stride_bytes);
+    validate_frames(img);
+    img.shading = m->fs.shading.set;                // (the image is the unit's already: no pixel format, no working size, no region)
+    img.levels = img.shading && m->fs.levels.set;
+    const size_t row = (size_t)width * 3, fb = row * (size_t)height;
+    if ((int64_t)fb > out_capacity) fail(SLIDEO_ERR_CAPACITY, "the shaded image needs %zu bytes", fb);
+    if (!img.shading) {                             // off: the image itself, row by row
+        for (int y = 0; y < height; ++y) std::memcpy(bgr_out + (size_t)y * row, bgr + (size_t)y * stride_bytes, row);
+        return SLIDEO_OK;
+    }
+    if (width != m->fs.shading.aw || height != m->fs.shading.ah)
+        fail(SLIDEO_ERR_INVALID_ARG, "a %dx%d image under a frame shading of %dx%d", width, height, m->fs.shading.aw, m->fs.shading.ah);
+    HIP_CHECK(hipSetDevice(m->device));
+    require_idle(m);
+    Slot& S = m->slots[0];
+    const DevFrames f = stage_frames(m, S, img, 0, 1);
+    HIP_CHECK(hipMemcpy2DAsync(bgr_out, row, f.p, (size_t)f.stride, row, (size_t)height, hipMemcpyDeviceToHost, S.st));
+    HIP_CHECK(hipStreamSynchronize(S.st));
+    API_CATCH(m)
+}
+
+int32_t slideo_shading_field(const uint64_t* cnt, const uint64_t* sum_f, const uint64_t* sum_p, int32_t gw, int32_t gh, int32_t cell, int64_t min_count,
+                             int32_t min_gain_q8, int32_t max_gain_q8, int32_t smooth, uint16_t* gains_out, int32_t* cells_used_out) {
+    API_TRY
+    if (!shading_field(cnt, sum_f, sum_p, gw, gh, cell, min_count, min_gain_q8, max_gain_q8, smooth, gains_out, cells_used_out))
+        return SLIDEO_ERR_INVALID_ARG;
+    API_CATCH(nullptr)
 }
 
 // ---- YUV chroma filter (include/slideo_amd.h "YUV chroma filter") -------------------------------------------------------------
@@ -1501,7 +1574,7 @@ int32_t slideo_frame_list_to_bgr8(slideo_matcher* m, const slideo_frame_list* li
     FrameSrc img = FrameSrc::from_list(list, m->fs);
     if (list->n_frames > 0 && !bgr_out) fail(SLIDEO_ERR_INVALID_ARG, "null bgr_out");
     img.describe(m->fs);
-    img.levels = false;                             // (the conversion's image: the frame levels come behind it, slideo_levels_bgr8)
+    img.levels = img.shading = false;               // (the conversion's image: the shading and the levels come behind it, slideo_levels_bgr8)
     validate_frames(img);
     const int n = list->n_frames;
     const size_t fb = (size_t)list->width * list->height * 3;

@@ -147,6 +147,7 @@ int32_t slideo_match_frames_features_bgr8(slideo_matcher* m, int32_t n_frames, c
     evidence_admit(m, width, height, n);
     tone_admit(m, n);
     placement_admit(m, width, height, n);
+    shading_map_admit(m, width, height, n);
     // (a failure from here on may leave rows counted whose verdicts are never returned: an open evidence session ends with it)
     struct EvidenceGuard { slideo_matcher* m; bool ok; ~EvidenceGuard() { if (!ok) sessions_drop(m); } } ev_guard{m, false};
     area_class_for(m, width, height);
@@ -204,6 +205,7 @@ int32_t slideo_match_frames_features_bgr8(slideo_matcher* m, int32_t n_frames, c
     evidence_tally(m, verdicts_out, n);
     tone_tally(m, n);
     placement_tally(m, n);
+    shading_map_tally(m, n);
     ev_guard.ok = true;
     m->last_fcs.resize((size_t)n);
     std::memcpy(m->last_fcs.data(), ho + (size_t)n * sizeof(slideo_verdict), (size_t)n * sizeof(FrameCands));
@@ -224,7 +226,7 @@ int32_t slideo_yuv420_to_bgr8(slideo_matcher* m, const uint8_t* frame, int32_t w
     if (!frame || !bgr_out) fail(SLIDEO_ERR_INVALID_ARG, "null frame/bgr_out");
     FrameSrc img = FrameSrc::yuv420(frame, false, width, height, layout, -1);
     img.describe(m->fs);
-    img.levels = false;                             // (the conversion's image: the frame levels come behind it, slideo_levels_bgr8)
+    img.levels = img.shading = false;               // (the conversion's image: the shading and the levels come behind it, slideo_levels_bgr8)
     validate_frames(img);
     const size_t fb = (size_t)width * height * 3;
     if ((int64_t)fb > out_capacity) fail(SLIDEO_ERR_CAPACITY, "the BGR image needs %zu bytes", fb);

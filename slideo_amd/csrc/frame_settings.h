@@ -1,12 +1,15 @@
 // frame_settings.h — the frame settings of a matcher as ONE record (include/slideo_amd.h "Working size", "Frame region", "Frame mask",
-// "Frame mask scope", "Direct page look-up", "Direct look-up scope", "YUV colour description", "YUV sampling", "YUV chroma filter", "YUV transfer", "Gate reference", "Gate settle", "Gate memory", "Frame pixel format", "Frame levels"): the record, every setter's proposal with its range checks, the
+// "Frame mask scope", "Direct page look-up", "Direct look-up scope", "YUV colour description", "YUV sampling", "YUV chroma filter", "YUV transfer", "Gate reference", "Gate settle", "Gate memory", "Frame pixel format", "Frame levels", "Frame shading"): the record, every setter's proposal with its range checks, the
 // rules between settings, what a change of each ends.  Plain C++, no HIP include (tools/frame_settings_hostcheck.cpp walks it on the
-// host); the device buffers a setting owns are the matcher's (runtime.hpp).  A change takes ONE path: settings_commit (capi_runtime.hip).
+// host); the device buffers a setting owns are the matcher's (runtime.hpp); the frame
+// shading's nodes are the record's own, shared by pointer between its copies.  A change takes ONE path: settings_commit (capi_runtime.hip).
 #pragma once
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdlib>
+#include <memory>
+#include <vector>
 
 #include "error.h"
 #include "geom.h"
@@ -45,6 +48,16 @@ struct YuvDesc {
 // The per-channel tone table of "Frame levels": lut[c * 256 + v], c = 0, 1, 2 for B, G, R (the matcher's d_levels holds its copy on
 // the device); set false: off, and the identity table is stored as off
 struct FrameLevels { bool set = false; uint8_t lut[768] = {}; };
+// The gain field of "Frame shading": Q8.8 nodes gains[j * (gw + 1) + i] at pixel (i * cell, j * cell) of the aw x ah analysed image,
+// gw = ceil(aw / cell), gh = ceil(ah / cell) (the matcher's d_shading holds their copy on the device); set false: off, and the
+// all-256 field is stored as off.  The nodes are shared by every copy of the record, never written after the proposal
+struct FrameShading {
+    bool set = false;
+    int aw = 0, ah = 0, cell = 0;
+    std::shared_ptr<const std::vector<uint16_t>> gains;
+    int gw() const { return (aw + cell - 1) / cell; }
+    int gh() const { return (ah + cell - 1) / cell; }
+};
 
 struct FrameSettings {
     int work_w = 0, work_h = 0;                       // frames beyond it are reduced in front of the pipeline; 0, 0 = none
@@ -57,6 +70,7 @@ struct FrameSettings {
     uint32_t direct_scope = SLIDEO_DIRECT_WHOLE;      // VALID = the look-up over the gate's valid pixels
     YuvDesc yuv;                                      // 4:2:0 frames stand for the BGR image under it (BGR calls never look at it)
     int pixel_format = SLIDEO_PIXEL_BGR8;             // how every *_bgr8 frame call reads its frames (YUV calls never look at it)
+    FrameShading shading;                             // the unit's BGR image is multiplied by it, in front of the levels
     FrameLevels levels;                               // the unit's BGR image goes through it, the last step in front of the unit
     uint32_t gate_ref = SLIDEO_GATE_PREVIOUS;         // what a gated frame is compared with: the frame before it, or the last changed one (ANCHOR)
     // the gate settle, part of the gate-reference setting ("Gate settle"): under ANCHOR a frame away from the anchor is matched once it
@@ -293,6 +307,39 @@ inline void levels_points(const uint64_t* hist768, int low_ppm, int high_ppm, in
         lo[c] = levels_value_at(h, rl);
         hi[c] = levels_value_at(h, total - 1 - cut);
     }
+}
+
+// ---- the frame shading (include/slideo_amd.h "Frame shading") -------------------------------------------------------------------------
+inline bool shading_cell_ok(int cell) { return cell == 16 || cell == 32 || cell == 64; }
+// The field commits under SET_YUV_DESCRIPTION like the levels table: it ends the kept frames and resets the gate.  gains null, or
+// every node 256: off (aw, ah and cell are then not looked at).  A gain of 0 is refused by its node
+inline FrameSettings propose_frame_shading(FrameSettings s, int aw, int ah, int cell, const uint16_t* gains) {
+    s.shading = FrameShading{};
+    if (!gains) return s;
+    if (!shading_cell_ok(cell)) fail(SLIDEO_ERR_INVALID_ARG, "frame shading: cell %d is none of 16, 32, 64", cell);
+    if (aw < 1 || ah < 1 || aw > MAX_DIM || ah > MAX_DIM) fail(SLIDEO_ERR_INVALID_ARG, "frame shading: analysed size %dx%d outside 1..%d", aw, ah, MAX_DIM);
+    const int gw = (aw + cell - 1) / cell, gh = (ah + cell - 1) / cell;
+    const size_t nodes = (size_t)(gw + 1) * (gh + 1);
+    bool identity = true;
+    for (size_t k = 0; k < nodes; ++k) {
+        if (gains[k] == 0)
+            fail(SLIDEO_ERR_INVALID_ARG, "frame shading: node (%d, %d) has gain 0: every gain is at least 1 (Q8.8, 256 = 1.0)", (int)(k % (size_t)(gw + 1)),
+                 (int)(k / (size_t)(gw + 1)));
+        identity &= gains[k] == 256;
+    }
+    if (identity) return s;
+    s.shading.set = true; s.shading.aw = aw; s.shading.ah = ah; s.shading.cell = cell;
+    s.shading.gains = std::make_shared<const std::vector<uint16_t>>(gains, gains + nodes);
+    return s;
+}
+// The rule of the header for one pixel of a B, G or R byte `in` at (x, y): the definition the kernel and the restatement are held to
+inline uint8_t frame_shading_pixel(const uint16_t* g, int gw, int cell, int x, int y, uint8_t in) {
+    const int sh = cell == 16 ? 4 : cell == 32 ? 5 : 6, i = x >> sh, j = y >> sh, fx = x - (i << sh), fy = y - (j << sh), p = gw + 1;
+    const uint32_t L = (uint32_t)g[j * p + i] * (uint32_t)(cell - fy) + (uint32_t)g[(j + 1) * p + i] * (uint32_t)fy;
+    const uint32_t R = (uint32_t)g[j * p + i + 1] * (uint32_t)(cell - fy) + (uint32_t)g[(j + 1) * p + i + 1] * (uint32_t)fy;
+    const uint32_t G = (L * (uint32_t)(cell - fx) + R * (uint32_t)fx + (uint32_t)(cell * cell / 2)) >> (2 * sh);
+    const uint32_t v = ((uint32_t)in * G + 128u) >> 8;
+    return (uint8_t)(v < 255u ? v : 255u);
 }
 
 inline FrameSettings propose_gate_reference(FrameSettings s, uint32_t ref) {

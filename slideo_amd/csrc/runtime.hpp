@@ -7,7 +7,7 @@
 //                      (FrameSrc -> FramePlan) and staged (-> DevFrames), unit submit / collect, the drivers of the frame calls
 //                      (pipeline, submit, collect: plain and gated) and their entry points
 //   stage_orb.hip      ORB stage drivers          (kernels: orb.hip.h, yuv420.hip.h, yuv_sampling.hip.h, pixel_format.hip.h, reduce.hip.h,
-//                                                 frame_region.hip.h, frame_mask.hip.h, levels.hip.h levels_kernel, frame_list.hip.h)
+//                                                 frame_region.hip.h, frame_mask.hip.h, levels.hip.h levels_kernel, shading.hip.h, frame_list.hip.h)
 //   stage_knn.hip      index build + k-NN stage   (kernels: knn.hip.h, knn_tile.hip.h, knn_l2.hip.h, knn_lsh.hip.h)
 //   stage_verify.hip   vote .. verdict, small img (kernels: verify.hip.h, homography.hip.h); the match evidence map's session, its
 //                      launch behind the verdicts and its entry points (kernel: evidence.hip.h); the match tone table's likewise (kernel: tone.hip.h),
@@ -131,6 +131,9 @@ struct FrameSrc {
     // (derived) the matcher's frame levels apply: the unit's image goes through the table as the last step (describe; analysed
     // frames are unit images already, levelled when they were kept)
     bool levels = false;
+    // (derived) the matcher's frame shading applies: the unit's image is multiplied by the field, in front of the levels (describe;
+    // analysed frames were shaded when they were kept)
+    bool shading = false;
     // a frame list: the frames are frames list_first .. of `list`, and p, stride, frame_stride and yuv describe the STAGED frames —
     // what stage_frames leaves in the library's memory in front of everything else (p itself: the first frame's first plane)
     std::shared_ptr<const FrameListData> list;
@@ -140,14 +143,15 @@ struct FrameSrc {
         bps = fs.yuv.bytes_per_sample(); sampling = fs.yuv.sampling; chroma = fs.yuv.chroma;
         pixel_format = yuv || analysed ? SLIDEO_PIXEL_BGR8 : fs.pixel_format;
         levels = fs.levels.set && !analysed;
+        shading = fs.shading.set && !analysed;
     }
     // a converter stands in front of the unit's BGR image: the frames are not read as they lie
     bool converted() const { return yuv != nullptr || pixel_format != SLIDEO_PIXEL_BGR8; }
     int64_t src_span() const { return yuv ? yuv_span : pix_span; }      // bytes of one frame a converter reads
-    // a kernel stands in front of the unit's image (a converter, the reduce or the rectify, the levels): device frames are not the
+    // a kernel stands in front of the unit's image (a converter, the reduce or the rectify, the shading, the levels): device frames are not the
     // unit's image as they lie in the caller's memory
     // (a list's frames never are: they are gathered first)
-    bool kernel_in_front() const { return converted() || plan.prep != PREP_NONE || levels || list; }
+    bool kernel_in_front() const { return converted() || plan.prep != PREP_NONE || shading || levels || list; }
     // device frames a converter or a prep kernel reads out of the caller's memory; a list's are staged like a host frame's
     bool in_place() const { return on_device && !list; }
 
@@ -485,6 +489,9 @@ struct slideo_matcher {
     // matcher is idle), and the levels histogram — "none" (on false) or the per-channel counts (u64 [3][256], d_lv_hist) of `frames`
     // analysed images of `pixels` pixels in all, of any sizes.  The observe calls feed it beside the other two accumulators
     slideo::DevBuf d_levels;
+    // frame shading (include/slideo_amd.h "Frame shading"): the device copy of fs.shading.gains (u16 [gh + 1][gw + 1]), written by
+    // settings_commit while the matcher is idle
+    slideo::DevBuf d_shading;
     // YUV transfer (include/slideo_amd.h "YUV transfer"): the device copy of LIN (uint16 [1024]) and OUT (uint8 [4096]) of
     // (fs.yuv.transfer, fs.yuv.white_nits), 6144 bytes, rewritten by settings_commit while the matcher is idle
     slideo::DevBuf d_transfer;
@@ -510,6 +517,13 @@ struct slideo_matcher {
     // through: the frames of the collected units.  max_frames: 2^20 unless SLIDEO_PLACEMENT_MAX_FRAMES lowered it at begin
     struct Placement { bool on = false; int cell = 0, min_inliers = 0, aw = 0, ah = 0, gw = 0, gh = 0; double reach = 0; int64_t through = 0, max_frames = 0; } placement;
     slideo::DevBuf d_placement;
+
+    // match shading map (include/slideo_amd.h "Match shading map"): the session — "none" (on false), empty (aw 0) or the sums of the
+    // match calls since shading_begin at the analysed size aw x ah — and its device buffer {cnt | sum_f | sum_p} (u64 [gh][gw] each)
+    // | frames_counted u64, zeroed at the first counted call, which shading_map_kernel adds to on the units' streams.  through: the
+    // frames of the collected units.  max_frames: 2^20 unless SLIDEO_SHADING_MAX_FRAMES lowered it at begin
+    struct ShadingMap { bool on = false; int cell = 0, min_inliers = 0, min_hits = 0, flat = 0, aw = 0, ah = 0, gw = 0, gh = 0; int64_t through = 0, max_frames = 0; } shading_map;
+    slideo::DevBuf d_shading_map;
 
     // direct page look-up (include/slideo_amd.h "Direct page look-up"): built at the first use with fs.direct_t > 0 after finalize, the
     // deck's size classes
@@ -643,6 +657,11 @@ void launch_frame_gather(const FrameListPlan& P, const uint8_t* const* tab_dev, 
 // levels_kernel (levels.hip.h)
 void launch_levels(slideo_matcher* m, const uint8_t* src, int64_t src_fs, int src_stride, uint8_t* dst, int64_t dst_fs, int dst_stride, int w, int h,
                    int n, hipStream_t st);
+// n BGR8 images of w x h — the field's analysed size — through the matcher's gain field (m->d_shading; fs.shading.set) and, with
+// `levels`, through the levels table in the same pass (the fused instance; levels_kernel is then not launched); src == dst with equal
+// strides: in place: shading_kernel (shading.hip.h)
+void launch_shading(slideo_matcher* m, bool levels, const uint8_t* src, int64_t src_fs, int src_stride, uint8_t* dst, int64_t dst_fs, int dst_stride,
+                    int w, int h, int n, hipStream_t st);
 
 // ---- stage_knn.hip --------------------------------------------------------------------------------
 // FlannMatcher::new (mo/flann.rs:65-71) for the Hamming index: uploads the M packed rows, collapses equal rows, builds the
@@ -686,7 +705,14 @@ inline void tone_drop(slideo_matcher* m) { m->tone = slideo_matcher::Tone{}; }
 void placement_admit(slideo_matcher* m, int uw, int uh, int n);
 inline void placement_tally(slideo_matcher* m, int n) { if (m->placement.on && m->placement.aw > 0) m->placement.through += n; }
 inline void placement_drop(slideo_matcher* m) { m->placement = slideo_matcher::Placement{}; }
-inline void sessions_drop(slideo_matcher* m) { evidence_drop(m); tone_drop(m); placement_drop(m); }
+// Match shading map (shading.hip.h), no-ops without a session.  shading_map_admit: placement_admit's checks and first-call zeroing,
+// and the grid's limit of 4096 cells (SLIDEO_ERR_UNSUPPORTED).  shading_map_tally: the frames of a collected unit
+void shading_map_admit(slideo_matcher* m, int uw, int uh, int n);
+// every argument and state rule of slideo_matcher_shading_begin (SLIDEO_ERR_INVALID_ARG, _UNSUPPORTED, _STATE), nothing changed
+void shading_map_begin_check(slideo_matcher* m, int cell, int min_inliers, int min_hits, int flat);
+inline void shading_map_tally(slideo_matcher* m, int n) { if (m->shading_map.on && m->shading_map.aw > 0) m->shading_map.through += n; }
+inline void shading_map_drop(slideo_matcher* m) { m->shading_map = slideo_matcher::ShadingMap{}; }
+inline void sessions_drop(slideo_matcher* m) { evidence_drop(m); tone_drop(m); placement_drop(m); shading_map_drop(m); }
 // (sw, sh: the small size, for callers without a FramePlan — pages, taps, the validity map)
 void run_small(slideo_matcher* m, const DevFrames& imgs, int n, hipStream_t st, int* sw = nullptr, int* sh = nullptr);
 // the same into `dst` (n small images back to back) in place of m->d_small: small images of consecutive gated units overlap

@@ -15,6 +15,8 @@
 #include "frame_list.hip.h"
 #define LEVELS_APPLY_KERNEL      // (levels_hist_kernel is stage_activity.hip's)
 #include "levels.hip.h"
+#define SHADING_APPLY_KERNEL
+#include "shading.hip.h"
 #include "reduce.hip.h"
 #include "frame_region.hip.h"
 #include "frame_mask.hip.h"
@@ -184,6 +186,21 @@ void launch_levels(slideo_matcher* m, const uint8_t* src, int64_t src_fs, int sr
     const dim3 grid(cdiv(cdiv(w, 4), LVL_TX), cdiv(h, LVL_TY), n), block(LVL_TX, LVL_TY);
     levels_kernel<<<grid, block, 0, st>>>(a);
     check_launch("levels_kernel");
+}
+
+// n BGR8 images through the matcher's gain field, and through its levels table in the same pass when `levels`
+void launch_shading(slideo_matcher* m, bool levels, const uint8_t* src, int64_t src_fs, int src_stride, uint8_t* dst, int64_t dst_fs, int dst_stride,
+                    int w, int h, int n, hipStream_t st) {
+    const FrameShading& F = m->fs.shading;
+    if (!F.set || !m->d_shading.p) fail(SLIDEO_ERR_HIP, "internal: no frame shading field to apply");
+    if (levels && (!m->fs.levels.set || !m->d_levels.p)) fail(SLIDEO_ERR_HIP, "internal: no frame levels table to apply");
+    if (w != F.aw || h != F.ah) fail(SLIDEO_ERR_INVALID_ARG, "analysed size %dx%d is not the frame shading's %dx%d", w, h, F.aw, F.ah);
+    const ShadingArgs a = shading_args(m->d_shading.as<uint16_t>(), F.cell, levels ? m->d_levels.as<uint8_t>() : nullptr, src, src_fs, src_stride, dst,
+                                       dst_fs, dst_stride, w, h, n);
+    const dim3 grid(cdiv(cdiv(w, 4), LVL_TX), cdiv(h, LVL_TY), n), block(LVL_TX, LVL_TY);
+    if (levels) shading_kernel<true><<<grid, block, 0, st>>>(a);
+    else shading_kernel<false><<<grid, block, 0, st>>>(a);
+    check_launch("shading_kernel");
 }
 
 // the reduce class (w, h) -> (dw, dh): ResizeAreaFast when both factors are integers (the test of resize.cpp, in double), else the

@@ -338,6 +338,7 @@ int32_t slideo_matcher_use_sift(slideo_matcher* m, const slideo_sift_config* cfg
     if (m->evidence.on) fail(SLIDEO_ERR_UNSUPPORTED, "the evidence map is not defined in SIFT mode (slideo_matcher_evidence_end first)");
     if (m->tone.on) fail(SLIDEO_ERR_UNSUPPORTED, "the tone table is not defined in SIFT mode (slideo_matcher_tone_end first)");
     if (m->placement.on) fail(SLIDEO_ERR_UNSUPPORTED, "the placement map is not defined in SIFT mode (slideo_matcher_placement_end first)");
+    if (m->shading_map.on) fail(SLIDEO_ERR_UNSUPPORTED, "the shading map is not defined in SIFT mode (slideo_matcher_shading_end first)");
     m->sift_on = true; m->sift_cfg = *cfg; m->sift_ratio = ratio;
     API_CATCH(m)
 }

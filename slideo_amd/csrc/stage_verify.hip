@@ -8,6 +8,8 @@
 #include "evidence.hip.h"
 #include "tone.hip.h"
 #include "placement.hip.h"
+#define SHADING_MAP              // (shading_kernel is stage_orb.hip's)
+#include "shading.hip.h"
 
 #include <cstring>
 
@@ -166,6 +168,68 @@ static void placement_launch(slideo_matcher* m, Slot& S, const VerifyParams& vp,
     check_launch("placement_kernel");
 }
 
+// ---- match shading map --------------------------------------------------------------------------------------------------------------
+void shading_map_admit(slideo_matcher* m, int uw, int uh, int n) {
+    slideo_matcher::ShadingMap& H = m->shading_map;
+    if (!H.on || n <= 0) return;
+    if (H.aw > 0 && (H.aw != uw || H.ah != uh))
+        fail(SLIDEO_ERR_INVALID_ARG, "these frames are analysed at %dx%d, the shading session counts at %dx%d: slideo_matcher_shading_end first", uw, uh,
+             H.aw, H.ah);
+    int64_t pending = 0;
+    for (const Slot& S : m->slots) if (S.busy) pending += S.n;
+    if (H.through + pending + n > H.max_frames)
+        fail(SLIDEO_ERR_INVALID_ARG, "%lld frames would pass the shading session's %lld: read the sums out and begin again", (long long)(H.through + pending + n),
+             (long long)H.max_frames);
+    if (H.aw > 0) return;
+    // the session's first counted call fixes the grid; the zeroed sums stand before any unit of the call is submitted
+    const int gw = cdiv(uw, H.cell), gh = cdiv(uh, H.cell);
+    if ((int64_t)gw * gh > SHM_MAX_CELLS)
+        fail(SLIDEO_ERR_UNSUPPORTED, "a shading session of %dx%d cells (%dx%d at cell %d): at most %d cells, which cell %d gives", gw, gh, uw, uh, H.cell,
+             SHM_MAX_CELLS, H.cell * 2);
+    const size_t bytes = ((size_t)gw * gh * 3 + 1) * 8;
+    m->d_shading_map.reserve(bytes + 16);
+    HIP_CHECK(hipMemsetAsync(m->d_shading_map.p, 0, bytes, m->stream));
+    HIP_CHECK(hipStreamSynchronize(m->stream));
+    H.aw = uw; H.ah = uh; H.gw = gw; H.gh = gh;
+}
+
+// what slideo_matcher_shading_begin refuses (the group's begin runs it over every member before it touches one)
+void shading_map_begin_check(slideo_matcher* m, int cell, int min_inliers, int min_hits, int flat) {
+    if (!evidence_cell_ok(cell)) fail(SLIDEO_ERR_INVALID_ARG, "shading_begin: cell %d is none of 16, 32, 64", cell);
+    if (min_inliers < 0) fail(SLIDEO_ERR_INVALID_ARG, "shading_begin: min_inliers %d below 0", min_inliers);
+    if (min_hits < 1) fail(SLIDEO_ERR_INVALID_ARG, "shading_begin: min_hits %d below 1", min_hits);
+    if (flat < 0 || flat > 255) fail(SLIDEO_ERR_INVALID_ARG, "shading_begin: flat %d outside 0..255", flat);
+    if (m->sift_on) fail(SLIDEO_ERR_UNSUPPORTED, "shading_begin: the shading map is not defined in SIFT mode");
+    require_idle(m);
+    if (m->shading_map.on) fail(SLIDEO_ERR_STATE, "shading_begin: a session is open (slideo_matcher_shading_end first)");
+    if (m->fs.shading.set)
+        fail(SLIDEO_ERR_STATE, "shading_begin: a frame shading is set, and a field learnt on shaded frames is not the source's "
+                               "(slideo_matcher_set_frame_shading(m, 0, 0, 0, NULL) first)");
+    if (m->fs.levels.set)
+        fail(SLIDEO_ERR_STATE, "shading_begin: a frame levels table is set, and a gain learnt behind the table cannot be installed in front of it: "
+                               "learn the field first and the table second (slideo_matcher_set_frame_levels(m, NULL) first)");
+}
+
+// shading_map_kernel over the unit's frames, behind verdict_kernel and the other sessions' kernels on the unit's stream
+static void shading_map_launch(slideo_matcher* m, Slot& S, const VerifyParams& vp, const DevFrames& f, int n) {
+    const slideo_matcher::ShadingMap& H = m->shading_map;
+    if (H.aw != f.w || H.ah != f.h) fail(SLIDEO_ERR_HIP, "internal: a unit of %dx%d images under a shading session of %dx%d", f.w, f.h, H.aw, H.ah);
+    ShadingMapArgs a{};
+    a.t.ev.fcs = S.d_fcs.as<FrameCands>(); a.t.ev.qofs = S.d_qofs.as<uint32_t>(); a.t.ev.kp = S.d_kp.as<slideo_keypoint>();
+    a.t.ev.page_xy = reinterpret_cast<const EvXY*>(m->d_page_xy.as<float2>());
+    a.t.ev.votes = reinterpret_cast<const EvVote*>(S.d_votes.as<uint2>());
+    a.t.ev.flags = S.d_flags.as<uint32_t>();
+    a.t.ev.rerun_mask = S.u_async ? 12u : 4u;    // (evidence_launch's: unit_collect's re-run rules)
+    a.t.ev.k = vp.k; a.t.ev.model = vp.model; a.t.ev.thr2 = vp.thr * vp.thr;
+    a.t.pageinfo = m->d_pageinfo.as<PageInfo>(); a.t.page_small = m->d_page_small.as<uint8_t>();
+    a.t.frames = f.p; a.t.frame_stride = f.frame_stride; a.t.stride = f.stride; a.t.aw = f.w; a.t.ah = f.h;
+    a.t.min_inliers = H.min_inliers; a.t.min_hits = H.min_hits; a.t.flat = H.flat;
+    a.shift = H.cell == 16 ? 4 : H.cell == 32 ? 5 : 6; a.gw = H.gw; a.cells = H.gw * H.gh;
+    a.acc = m->d_shading_map.as<unsigned long long>();
+    shading_map_kernel<<<n, TONE_THREADS, ((size_t)a.cells * 3 + 5) * sizeof(uint32_t), S.st>>>(a);
+    check_launch("shading_map_kernel");
+}
+
 // Everything after the neighbour lists (S.d_keys, Hamming key format) of a unit: the per-page vote, RANSAC (similarity or
 // homography), rating, re-projection, verdicts, and the unit's one D2H copy.  `f`: the unit's frames (re-projection).
 void unit_verify(slideo_matcher* m, Slot& S, const VerifyParams& vp, const DevFrames& f, int n, uint32_t qtot) {
@@ -283,6 +347,7 @@ void unit_verify(slideo_matcher* m, Slot& S, const VerifyParams& vp, const DevFr
     if (m->evidence.on && qtot > 0) evidence_launch(m, S, vp, f, n);
     if (m->tone.on && qtot > 0) tone_launch(m, S, vp, f, n);
     if (m->placement.on && qtot > 0) placement_launch(m, S, vp, f, n);
+    if (m->shading_map.on && qtot > 0) shading_map_launch(m, S, vp, f, n);
     if (prof) HIP_CHECK(hipEventRecord(S.ev[3], st));
     uint8_t* ho = S.h_out.as<uint8_t>();
     const size_t tail = (size_t)n * (sizeof(slideo_verdict) + sizeof(FrameCands));
@@ -553,6 +618,70 @@ int32_t slideo_placement_quad(const uint64_t* n, const uint64_t* sfx, const uint
         return placement_quad(n, sfx, sfy, su, sv, gw, gh, aw, ah, (uint64_t)min_count, trim_px, rounds, quad_out8, H_out9, cells_used, rms_px) ? SLIDEO_OK
                                                                                                                                                : SLIDEO_ERR_INVALID_ARG;
     } catch (const std::bad_alloc&) { return SLIDEO_ERR_CAPACITY; }
+}
+
+}  // extern "C"
+
+// ---- Match shading map (include/slideo_amd.h "Match shading map") -------------------------------------------------------------------
+extern "C" {
+
+int32_t slideo_matcher_shading_begin(slideo_matcher* m, int32_t cell, int32_t min_inliers, int32_t min_hits, int32_t flat) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    shading_map_begin_check(m, cell, min_inliers, min_hits, flat);
+    m->shading_map = slideo_matcher::ShadingMap{};
+    m->shading_map.on = true; m->shading_map.cell = cell; m->shading_map.min_inliers = min_inliers; m->shading_map.min_hits = min_hits;
+    m->shading_map.flat = flat;
+    m->shading_map.max_frames = std::min<int64_t>(SHM_MAX_FRAMES, std::max<long>(1, env_long("SLIDEO_SHADING_MAX_FRAMES", (long)SHM_MAX_FRAMES)));
+    API_CATCH(m)
+}
+
+int32_t slideo_matcher_shading_end(slideo_matcher* m) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    require_idle(m);
+    HIP_CHECK(hipSetDevice(m->device));
+    shading_map_drop(m);
+    m->d_shading_map.release();
+    API_CATCH(m)
+}
+
+int32_t slideo_matcher_shading_info(slideo_matcher* m, int32_t* cell, int32_t* min_inliers, int32_t* min_hits, int32_t* flat, int32_t* aw, int32_t* ah,
+                                    int32_t* gw, int32_t* gh, int64_t* frames_through) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    if (!cell || !min_inliers || !min_hits || !flat || !aw || !ah || !gw || !gh || !frames_through) fail(SLIDEO_ERR_INVALID_ARG, "null output");
+    const slideo_matcher::ShadingMap& H = m->shading_map;
+    if (!H.on) fail(SLIDEO_ERR_STATE, "no shading session: slideo_matcher_shading_begin first");
+    *cell = H.cell; *min_inliers = H.min_inliers; *min_hits = H.min_hits; *flat = H.flat; *aw = H.aw; *ah = H.ah; *gw = H.gw; *gh = H.gh;
+    *frames_through = H.through;
+    API_CATCH(m)
+}
+
+int32_t slideo_matcher_shading_sums(slideo_matcher* m, uint64_t* cnt_out, uint64_t* sum_f_out, uint64_t* sum_p_out, int64_t capacity_elems, int32_t* gw,
+                                    int32_t* gh, int64_t* frames_through, int64_t* frames_counted) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    if (!gw || !gh || !frames_through || !frames_counted) fail(SLIDEO_ERR_INVALID_ARG, "null gw/gh/frames_through/frames_counted");
+    require_idle(m);
+    const slideo_matcher::ShadingMap& H = m->shading_map;
+    if (!H.on) fail(SLIDEO_ERR_STATE, "no shading session: slideo_matcher_shading_begin first");
+    *gw = H.gw; *gh = H.gh; *frames_through = H.through; *frames_counted = 0;
+    if (H.aw == 0) return SLIDEO_OK;      // (no counted call yet: a grid of 0 x 0)
+    uint64_t* outs[3] = {cnt_out, sum_f_out, sum_p_out};
+    int given = 0;
+    for (uint64_t* o : outs) given += o != nullptr;
+    if (given != 0 && given != 3) fail(SLIDEO_ERR_INVALID_ARG, "the three output arrays go together");
+    const int64_t nc = (int64_t)H.gw * H.gh;
+    if (given && nc > capacity_elems) fail(SLIDEO_ERR_CAPACITY, "the sums need %lld elements each", (long long)nc);
+    HIP_CHECK(hipSetDevice(m->device));
+    uint64_t counted = 0;
+    for (int i = 0; given && i < 3; ++i)
+        HIP_CHECK(hipMemcpyAsync(outs[i], m->d_shading_map.as<uint64_t>() + (size_t)i * nc, (size_t)nc * 8, hipMemcpyDeviceToHost, m->stream));
+    HIP_CHECK(hipMemcpyAsync(&counted, m->d_shading_map.as<uint64_t>() + 3 * (size_t)nc, 8, hipMemcpyDeviceToHost, m->stream));
+    HIP_CHECK(hipStreamSynchronize(m->stream));
+    *frames_counted = (int64_t)counted;
+    API_CATCH(m)
 }
 
 }  // extern "C"

@@ -450,6 +450,41 @@ public:
                                                   &p.frames_through, &p.frames_counted));
         return p;
     }
+    // Match shading map (include/slideo_amd.h "Match shading map"; an extension): while a session is open, the tasks' match calls sum,
+    // per cell of the analysed image, the samples of the tone table's sampler that land there and the B + G + R of their frame and
+    // page pixels, over the devices.  No task may be running at begin, sums or end; refused while a frame shading or a levels table
+    // is set.  shading_field makes the gains (what with_frame_shading takes); nothing is installed, no value has a default.
+    struct ShadingSums {
+        int32_t cell = 0, min_inliers = 0, min_hits = 0, flat = 0, aw = 0, ah = 0, gw = 0, gh = 0;
+        int64_t frames_through = 0, frames_counted = 0;
+        std::vector<uint64_t> cnt, sum_f, sum_p;       // gh rows of gw each (shading_info leaves them empty)
+    };
+    void shading_begin(int32_t cell, int32_t min_inliers, int32_t min_hits, int32_t flat) {
+        h_->check(slideo_group_shading_begin(h_->g, cell, min_inliers, min_hits, flat));
+    }
+    void shading_end() { h_->check(slideo_group_shading_end(h_->g)); }
+    ShadingSums shading_info() const {
+        ShadingSums p;
+        h_->check(slideo_group_shading_info(h_->g, &p.cell, &p.min_inliers, &p.min_hits, &p.flat, &p.aw, &p.ah, &p.gw, &p.gh, &p.frames_through));
+        return p;
+    }
+    ShadingSums shading_sums() const {
+        ShadingSums p = shading_info();
+        const size_t nc = (size_t)p.gw * (size_t)p.gh;
+        p.cnt.assign(nc, 0); p.sum_f.assign(nc, 0); p.sum_p.assign(nc, 0);
+        if (nc)
+            h_->check(slideo_group_shading_sums(h_->g, p.cnt.data(), p.sum_f.data(), p.sum_p.data(), (int64_t)nc, &p.gw, &p.gh, &p.frames_through,
+                                                &p.frames_counted));
+        return p;
+    }
+    // the field of the sums, (gh + 1) * (gw + 1) Q8.8 nodes; false: a bad argument or no cell of min_count samples
+    static bool shading_field(const ShadingSums& p, int64_t min_count, int32_t min_gain_q8, int32_t max_gain_q8, int32_t smooth, std::vector<uint16_t>& gains) {
+        const size_t nc = (size_t)p.gw * (size_t)p.gh;
+        if (!nc || p.cnt.size() != nc || p.sum_f.size() != nc || p.sum_p.size() != nc) return false;
+        gains.assign((size_t)(p.gw + 1) * (size_t)(p.gh + 1), 256);
+        return slideo_shading_field(p.cnt.data(), p.sum_f.data(), p.sum_p.data(), p.gw, p.gh, p.cell, min_count, min_gain_q8, max_gain_q8, smooth,
+                                    gains.data(), nullptr) == SLIDEO_OK;
+    }
     // the quad of the sums; false: fewer than 4 cells of min_count keypoints at a stage, or cells that determine no homography
     static bool placement_quad(const PlacementSums& p, int64_t min_count, double trim_px, int32_t rounds, PlacementQuad& out) {
         const size_t nc = (size_t)p.gw * (size_t)p.gh;
@@ -544,6 +579,15 @@ public:
         if (lut768) frame_levels_.assign(lut768, lut768 + 768); else frame_levels_.clear();
         return *this;
     }
+    // A bilinear Q8.8 gain field (slideo_group_set_frame_shading, include/slideo_amd.h "Frame shading") over the aw x ah analysed image:
+    // uint16 [gh + 1][gw + 1] nodes cell (16, 32 or 64) pixels apart, 256 = 1.0, applied in front of the frame levels — what
+    // slideo_shading_field makes of per-cell sums, for the vignetting of a filmed projection screen.  Pages are untouched; null: off
+    HipImageVideoMatcher& with_frame_shading(int32_t aw, int32_t ah, int32_t cell, const uint16_t* gains) {
+        shading_.clear();
+        if (gains && cell > 0 && aw > 0 && ah > 0) shading_.assign(gains, gains + (size_t)((aw + cell - 1) / cell + 1) * ((ah + cell - 1) / cell + 1));
+        shading_aw_ = aw; shading_ah_ = ah; shading_cell_ = cell;
+        return *this;
+    }
     // Which frame a gated frame is compared with (slideo_group_set_gate_reference, include/slideo_amd.h "Gate reference"):
     // SLIDEO_GATE_PREVIOUS (default: the frame before, the reference's MarkSimilarIter) or SLIDEO_GATE_ANCHOR (the last frame that
     // was flagged: a change spread over many frames is still flagged when every decoded frame is fed).  One device only: a group of
@@ -598,6 +642,7 @@ public:
         if (yuv_chroma_ != SLIDEO_YUV_CHROMA_NEAREST) h->check(slideo_group_set_yuv_chroma(h->g, yuv_chroma_));
         if (yuv_transfer_ != SLIDEO_YUV_TRANSFER_SDR) h->check(slideo_group_set_yuv_transfer(h->g, yuv_transfer_, yuv_white_nits_));
         if (pixel_format_ != SLIDEO_PIXEL_BGR8) h->check(slideo_group_set_pixel_format(h->g, pixel_format_));
+        if (!shading_.empty()) h->check(slideo_group_set_frame_shading(h->g, shading_aw_, shading_ah_, shading_cell_, shading_.data()));
         if (!frame_levels_.empty()) h->check(slideo_group_set_frame_levels(h->g, frame_levels_.data()));
         if (mask_scope_ != SLIDEO_MASK_DETECT) h->check(slideo_group_set_frame_mask_scope(h->g, mask_scope_));
         if (!mask_.empty()) h->check(slideo_group_set_frame_mask(h->g, mask_.data(), mask_w_, mask_h_, mask_w_));
@@ -632,6 +677,8 @@ private:
     float yuv_white_nits_ = 0.f;
     int32_t pixel_format_ = SLIDEO_PIXEL_BGR8;
     std::vector<uint8_t> frame_levels_;
+    std::vector<uint16_t> shading_;
+    int32_t shading_aw_ = 0, shading_ah_ = 0, shading_cell_ = 0;
     uint32_t mask_scope_ = SLIDEO_MASK_DETECT, direct_scope_ = SLIDEO_DIRECT_WHOLE, gate_ref_ = SLIDEO_GATE_PREVIOUS;
     uint32_t gate_order_ = SLIDEO_GROUP_GATE_HALO;
     float settle_similarity_ = 0.f;

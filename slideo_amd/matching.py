@@ -434,6 +434,31 @@ def learn_frame_levels_from_matches(matcher, frame_batches, *, min_inliers, min_
     return lut
 
 
+def learn_frame_shading_from_matches(matcher, frame_batches, *, cell, min_inliers, min_hits, flat, min_count, min_gain, max_gain, smooth):
+    """A frame shading learnt from the matches themselves (include/slideo_amd.h "Match shading map"): the host BGR batches (each uint8
+    [n, h, w, 3], all of one frame size) are matched against the matcher's finalized deck under a shading session of `cell`,
+    `min_inliers`, `min_hits` and `flat`; every cell with at least `min_count` samples gives the ratio of its page side's sum to its
+    frame side's, and slideo_shading_field fills, smooths (`smooth` rounds) and clamps them to min_gain .. max_gain (Q8.8 integers,
+    256 = 1.0) on the grid's nodes.  `matcher`: a Matcher or a Group, idle, finalized, with neither a frame shading nor a frame levels
+    table set (learn the field first and the table second); the camera and the screen must not move over the batches.  Returns
+    (aw, ah, cell, gains uint16 [gh + 1, gw + 1]) — what frame_shading= and set_frame_shading(*result) take; nothing is installed.
+    ValueError when no frame contributed.  No parameter has a default: they depend on the content (docs/EXTENSIONS.md "Match shading
+    map")."""
+    matcher.shading_begin(cell, min_inliers, min_hits, flat)
+    try:
+        for batch in frame_batches:
+            matcher.match_frames(batch)
+        info = matcher.shading_info()
+        sums, through, counted = matcher.shading_sums()
+    finally:
+        matcher.shading_end()
+    if counted == 0:
+        raise ValueError("learn_frame_shading_from_matches: none of the %d frames contributed (no candidate with a model, %d inliers and "
+                         "%d hits): the shading map is empty" % (through, int(min_inliers), int(min_hits)))
+    gains, _ = _capi.shading_field(sums[0], sums[1], sums[2], cell, min_count, min_gain, max_gain, smooth)
+    return info["aw"], info["ah"], int(cell), gains
+
+
 def learn_frame_quad_from_matches(matcher, frame_batches, *, cell, min_inliers, reach, min_count, trim, rounds, inset=0, out_size=None):
     """A keystoned frame region learnt from the matches themselves (include/slideo_amd.h "Match placement map"): the host BGR batches
     (each uint8 [n, h, w, 3], all of one frame size) are matched against the matcher's finalized deck under a placement session of
@@ -542,7 +567,7 @@ class HipImageVideoMatcher:
 
     def __init__(self, cfg=None, device=None, sift=None, devices=None, working_size=None, frame_mask=None, frame_mask_scope=None,
                  direct_similarity=None, direct_scope=None, frame_region=None, yuv_description=None, gate_reference=None, gate_settle=None,
-                 group_gate_order=None, yuv_sampling=None, gate_memory=None, pixel_format=None, frame_levels=None, yuv_chroma=None,
+                 group_gate_order=None, yuv_sampling=None, gate_memory=None, pixel_format=None, frame_levels=None, frame_shading=None, yuv_chroma=None,
                  yuv_transfer=None):
         """devices: HIP ordinals, one matcher each behind one slideo_group (the reference fans out over the whole machine, the
         global rayon pool of lib.rs:45,174); None = every gfx950 device of the node; `device` = d is short for devices = [d].
@@ -589,6 +614,9 @@ class HipImageVideoMatcher:
         frame_levels = uint8 [3, 256] (B, G, R; slideo_group_set_frame_levels): a per-channel tone table applied to every frame's
         analysed image as the last step in front of the pipeline — what learn_frame_levels returns for dim, low-contrast or
         colour-cast recordings; pages are untouched; the reference analyses the frames as they are; None = off.
+        frame_shading = (aw, ah, cell, gains uint16 [gh + 1, gw + 1]) (slideo_group_set_frame_shading): a bilinear Q8.8 gain field
+        over the aw x ah analysed image, applied in front of frame_levels — for the vignetting and gradients of a filmed projection
+        screen, which one table per channel cannot undo; pages are untouched; frames analysed at another size are refused; None = off.
         gate_reference = "previous" or "anchor" (slideo_group_set_gate_reference): with "anchor" a frame is compared with the last
         frame that was flagged, not the frame before it, so a change spread over many frames (a cross-fade, an animated build) is
         still flagged when every decoded frame is fed; with several devices it needs group_gate_order = "chain" — without it the
@@ -617,6 +645,7 @@ class HipImageVideoMatcher:
         self._yuv_transfer = (yuv_transfer, 0) if isinstance(yuv_transfer, (str, int)) else tuple(yuv_transfer) if yuv_transfer is not None else None
         self._pixel_format = pixel_format
         self._frame_levels = frame_levels
+        self._frame_shading = tuple(frame_shading) if frame_shading is not None else None
         self._gate_reference = gate_reference
         self._gate_settle = tuple(gate_settle) if gate_settle is not None else None
         self._gate_memory = gate_memory
@@ -651,6 +680,8 @@ class HipImageVideoMatcher:
             m.set_yuv_transfer(*self._yuv_transfer)
         if self._pixel_format is not None:
             m.set_pixel_format(self._pixel_format)
+        if self._frame_shading is not None:
+            m.set_frame_shading(*self._frame_shading)
         if self._frame_levels is not None:
             m.set_frame_levels(self._frame_levels)
         if self._frame_mask_scope is not None:
