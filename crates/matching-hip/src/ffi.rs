@@ -669,6 +669,30 @@ extern "C" {
         out: *mut u8,
         out_capacity: i64,
     ) -> i32;
+    // frame lens (include/slideo_amd.h "Frame lens"): radial undistortion in the launch that rectifies
+    pub fn slideo_matcher_set_frame_lens(m: *mut slideo_matcher, src_w: i32, src_h: i32, cx: f64, cy: f64, f: f64, k1: f64, k2: f64) -> i32;
+    pub fn slideo_matcher_frame_lens(
+        m: *const slideo_matcher,
+        src_w: *mut i32,
+        src_h: *mut i32,
+        cx: *mut f64,
+        cy: *mut f64,
+        f: *mut f64,
+        k1: *mut f64,
+        k2: *mut f64,
+        is_set: *mut i32,
+    ) -> i32;
+    pub fn slideo_group_set_frame_lens(g: *mut slideo_group, src_w: i32, src_h: i32, cx: f64, cy: f64, f: f64, k1: f64, k2: f64) -> i32;
+    pub fn slideo_frame_lens_point(cx: f64, cy: f64, f: f64, k1: f64, k2: f64, u: f64, v: f64, xd: *mut f64, yd: *mut f64) -> i32;
+    pub fn slideo_undistort_bgr8(
+        m: *mut slideo_matcher,
+        bgr: *const u8,
+        width: i32,
+        height: i32,
+        stride_bytes: i32,
+        out: *mut u8,
+        out_capacity: i64,
+    ) -> i32;
     // match evidence map (include/slideo_amd.h "Match evidence map"): where the keypoints of matched frames fall and which of them the
     // winning page's transform explains; the mask and the box made of the counts
     pub fn slideo_matcher_evidence_begin(m: *mut slideo_matcher, cell: i32, min_inliers: i32) -> i32;
@@ -847,6 +871,32 @@ extern "C" {
         min_count: i64,
         trim_px: f64,
         rounds: i32,
+        quad_out8: *mut f64,
+        h_out9: *mut f64,
+        cells_used: *mut i32,
+        rms_px: *mut f64,
+    ) -> i32;
+    // placement lens (include/slideo_amd.h "Placement lens"): the frame lens and the quad fitted jointly to the same sums
+    pub fn slideo_placement_lens(
+        n: *const u64,
+        sfx: *const u64,
+        sfy: *const u64,
+        su: *const u64,
+        sv: *const u64,
+        gw: i32,
+        gh: i32,
+        cell: i32,
+        aw: i32,
+        ah: i32,
+        min_count: i64,
+        cx: f64,
+        cy: f64,
+        f: f64,
+        order: i32,
+        trim_px: f64,
+        rounds: i32,
+        iters: i32,
+        k_out2: *mut f64,
         quad_out8: *mut f64,
         h_out9: *mut f64,
         cells_used: *mut i32,

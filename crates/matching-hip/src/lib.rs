@@ -91,6 +91,10 @@ pub struct HipImageVideoMatcher {
     /// top-right, bottom-right and bottom-left corner (slideo_frame_region_from_quad): a filmed projection screen, a slide
     /// in a sub-window.  The reference analyses the whole frame.  None (default) = no region.
     pub frame_region: Option<(i32, i32, [f64; 8], i32, i32)>,
+    /// Some((src_w, src_h, cx, cy, f, k1, k2)): the frame lens (slideo_group_set_frame_lens): the radial distortion of a
+    /// wide-angle room camera, c + (p - c) (1 + k1 r2 + k2 r2^2) with r2 = |p - c|^2 / f^2, removed in the launch that
+    /// rectifies; frame_region's quad is then in ideal coordinates.  Applied after frame_region.  None (default) = no lens.
+    pub frame_lens: Option<(i32, i32, f64, f64, f64, f64, f64)>,
     /// (matrix, range, depth): how YUV 4:2:0 frames are read (slideo_group_set_yuv_description): ffi::SLIDEO_YUV_MATRIX_* /
     /// _RANGE_* / _DEPTH_*.  BT.709 for HD recordings, full range for many screen recorders, a 10-bit depth for P010 /
     /// yuv420p10le frames.  The reference reads every stream as BT.601 limited range: the default (0, 0, 0).
@@ -221,6 +225,7 @@ impl Default for HipImageVideoMatcher {
             direct_similarity: 0.0,
             direct_scope: ffi::SLIDEO_DIRECT_WHOLE,
             frame_region: None,
+            frame_lens: None,
             yuv_description: (ffi::SLIDEO_YUV_MATRIX_BT601, ffi::SLIDEO_YUV_RANGE_LIMITED, ffi::SLIDEO_YUV_DEPTH_8),
             yuv_sampling: ffi::SLIDEO_YUV_SAMPLING_420,
             yuv_chroma: ffi::SLIDEO_YUV_CHROMA_NEAREST,
@@ -276,6 +281,9 @@ impl<'i> ImageVideoMatcher<'i> for HipImageVideoMatcher {
                 let mut m9 = [0f64; 9];
                 check(std::ptr::null_mut(), ffi::slideo_frame_region_from_quad(quad.as_ptr(), *ow, *oh, m9.as_mut_ptr()));
                 check(h, ffi::slideo_group_set_frame_region(h, *sw, *sh, m9.as_ptr(), *ow, *oh));
+            }
+            if let Some((sw, sh, cx, cy, f, k1, k2)) = self.frame_lens {
+                check(h, ffi::slideo_group_set_frame_lens(h, sw, sh, cx, cy, f, k1, k2));
             }
             if self.yuv_description != (0, 0, 0) {
                 let (matrix, range, depth) = self.yuv_description;

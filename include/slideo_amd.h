@@ -1189,6 +1189,61 @@ int32_t     slideo_frame_region_from_quad(const double* quad, int32_t out_w, int
 int32_t     slideo_rectify_bgr8(slideo_matcher* m, const uint8_t* bgr, int32_t width, int32_t height, int32_t stride_bytes, uint8_t* out,
                                 int64_t out_capacity);
 
+/* ---- Frame lens (extension: radial undistortion fused into the rectify; the reference analyses the frame as the camera saw it) ----
+ * A room camera sees the projection screen through a wide-angle lens; barrel distortion is not projective, so no region's M removes
+ * it.  A matcher carries an optional FRAME LENS: Brown's radial terms, in the direction initUndistortRectifyMap uses (no inversion,
+ * no iteration).  A point p of the ideal, distortion-free source plane is seen by the camera at
+ *     c + (p - c) * g(r2),   r2 = |p - c|^2 / f^2,   g = 1 + k1 r2 + k2 r2^2
+ * c = (cx, cy) in source pixel-centre coordinates; f the normaliser in pixels (a focal length, or — the mirrors' default — half the
+ * source diagonal, so that k1 is the relative displacement at the corner).  While a lens is set, a frame call whose source size is
+ * (src_w, src_h) STANDS FOR its analysed image U, made on the GPU in the SAME single launch that rectifies
+ * (csrc/frame_lens.hip.h); shading and levels follow it, as they follow the rectify.  Without a region U is src_w x src_h; with one
+ * (of the same source size) it is out_w x out_h, and the region's quad is given in IDEAL coordinates.
+ * Definition, the library's own, for destination pixel (x, y) of U; float64, every operation rounded once, nothing fused:
+ *   1  the ideal point.  Without a region u = x, v = y exactly.  With a region M:
+ *          N0 = (M0*x + M1*y) + M2;  N1 = (M3*x + M4*y) + M5;  W = (M6*x + M7*y) + M8;  Wi = 1.0 / W;  u = N0 * Wi;  v = N1 * Wi
+ *      (no column-block term: under a lens the region's own three instances are not used; an affine or translating M takes this
+ *      path too)
+ *   2  the lens.  dx = u - cx;  dy = v - cy;  r2 = (dx*dx + dy*dy) * q, with q = 1.0 / (f*f) computed once on the host;
+ *          t = r2 * k2;  t = k1 + t;  t = r2 * t;  g = 1.0 + t;  xd = cx + dx*g;  yd = cy + dy*g
+ *   3  X = (int)rint(clamp(32.0 * xd, INT_MIN, INT_MAX));  Y likewise from yd
+ *   4  taps and blend exactly the region's: sx = X >> 5, ax = X & 31, the replicate clamp, integer weights of sum 1024,
+ *      (sum + 512) >> 10 per channel.
+ * Rules.  SLIDEO_ERR_INVALID_ARG, the rule named, the values before staying in force: a source size outside 1..4096; a non-finite
+ * argument; f <= 0; the radial map r g(r) not strictly increasing over the REACH — with R2 the largest r2 of the ideal images of the
+ * four destination corners (the image of the rectangle is convex, so a corner is its farthest point), 1 + 3 k1 s + 5 k2 s^2 > 0
+ * must hold at s = 0, at s = R2 and at the vertex -3 k1 / (10 k2) where that lies inside (0, R2).  The rule is evaluated at the
+ * commit with the region in force, so setting either of the two can trip it.  SLIDEO_ERR_UNSUPPORTED at whichever set call comes
+ * second: a lens and a region of different source sizes; a lens without a region whose analysed size src_w x src_h exceeds a set
+ * working size (such a lens counts as a rectifying call: its output must fit the working size and the source is exempt, as for
+ * the region).  A frame call at another source size than the lens's is SLIDEO_ERR_INVALID_ARG naming both sizes: never silently
+ * left distorted.  The lens commits as the region does: it needs an idle matcher (SLIDEO_ERR_STATE), ends the kept frames, resets
+ * the gate state to "none" and ends the match sessions.  small_area, SIFT's side limit, a frame mask's size and a shading field's
+ * size refer to the analysed size.  Pages and the other single-image taps are untouched — slideo_rectify_bgr8 stays the tap of the
+ * region alone.  A device frame is never written.
+ * Contract: every call that stages frames — host and device, BGR and every YUV form, every pixel format, frame lists, submit /
+ * collect, gated calls, kept frames, the observe calls, groups, SIFT mode, page sets — returns, bit for bit, what the same call
+ * under the default returns on the images slideo_undistort_bgr8 gives.
+ * Out of scope: tangential (decentering) terms; a learnt centre or f; fisheye models; a per-call or moving lens; undistorting
+ * pages; a lens in slideo_match_frames_features_bgr8; uploading only the rows a lens reads.
+ * DEPARTURE: the reference never undistorts a frame.  Off by default. */
+/* k1 == 0 && k2 == 0 is stored as off, and the other arguments are then not looked at (the convention of the identity levels
+ * table).  Before or after finalize, any number of times. */
+int32_t     slideo_matcher_set_frame_lens(slideo_matcher* m, int32_t src_w, int32_t src_h, double cx, double cy, double f, double k1, double k2);
+/* The lens as set (is_set 0: none; every value is then 0). */
+int32_t     slideo_matcher_frame_lens(const slideo_matcher* m, int32_t* src_w, int32_t* src_h, double* cx, double* cy, double* f, double* k1,
+                                      double* k2, int32_t* is_set);
+/* Forwards to every member (validated on every member before one is touched) and resets the group's gate state. */
+int32_t     slideo_group_set_frame_lens(slideo_group* g, int32_t src_w, int32_t src_h, double cx, double cy, double f, double k1, double k2);
+/* A pure host function (no device, no matcher): step 2 of the definition for one ideal point (u, v), the kernel's own arithmetic.
+ * k1 == 0 && k2 == 0 is the off value here too: the point itself, exactly (step 2's cx + (u - cx) would round).  SLIDEO_ERR_INVALID_ARG: a null output, a non-finite argument, f <= 0. */
+int32_t     slideo_frame_lens_point(double cx, double cy, double f, double k1, double k2, double u, double v, double* xd, double* yd);
+/* Tap: U of one host image under the matcher's lens, and its region if one is set (out: stride 3 * the analysed width; out_capacity
+ * >= the analysed size * 3).  No small_area limit.  SLIDEO_ERR_STATE without a lens; SLIDEO_ERR_INVALID_ARG at another size than
+ * the lens's source. */
+int32_t     slideo_undistort_bgr8(slideo_matcher* m, const uint8_t* bgr, int32_t width, int32_t height, int32_t stride_bytes, uint8_t* out,
+                                  int64_t out_capacity);
+
 /* ---- Frame mask (cv::ORB::detectAndCompute's `mask` argument; the reference passes no_array(), mo/feature_extractor.rs:35) ----------
  * [OCV — recalled, unpinned, like the rest of SURVEY.md Appendix A: OpenCV 4.5.2 features2d/orb.cpp detectAndCompute /
  * computeKeyPoints and KeyPointsFilter::runByPixelsMask.]
@@ -2221,6 +2276,37 @@ int32_t     slideo_group_placement_sums(slideo_group* g, uint64_t* n_out, uint64
 int32_t     slideo_placement_quad(const uint64_t* n, const uint64_t* sfx, const uint64_t* sfy, const uint64_t* su, const uint64_t* sv, int32_t gw,
                                   int32_t gh, int32_t cell, int32_t aw, int32_t ah, int64_t min_count, double trim_px, int32_t rounds,
                                   double* quad_out8, double* H_out9, int32_t* cells_used, double* rms_px);
+
+/* ---- Placement lens (extension: the frame lens and the quad learnt jointly from the placement session's sums) ------------------------
+ * Under lens distortion a homography fits only a patch of the screen, and slideo_placement_quad's trim drops exactly the outer cells
+ * that carry the signal.  slideo_placement_lens fits H and the radial terms of "Frame lens" JOINTLY to the sums a placement session
+ * gives when it ran with NO lens and NO region set.  A pure host function in float64 (no handle, no device); it installs nothing.
+ * Arguments: the grid, min_count, trim_px and rounds as slideo_placement_quad validates them; cx, cy finite, f > 0 (the lens's centre
+ * and normaliser, GIVEN, not learnt); order 1 (k1) or 2 (k1 and k2); iters in 1..1000.
+ *   points   slideo_placement_quad's: a cell with n >= min_count is one unweighted correspondence (u, v) -> (X, Y).
+ *   model    P = s * H(u, v), s = max(aw, ah), H = [[h0 h1 h2] [h3 h4 h5] [h6 h7 1]] — the ideal pixel of the unit-slide point —,
+ *            D(P) = c + (P - c) (1 + k1 r2 + k2 r2^2), r2 = |P - c|^2 / f^2; the residual of a point is D(P) - (X, Y), in pixels.
+ *            Parameters: h0 .. h7 (scaled by s as slideo_placement_quad scales them), k1 and, at order 2, k2 (0 at order 1).
+ *   start    slideo_placement_quad's linear fit over ALL points, WITHOUT trimming; k = 0.
+ *   iterate  at most `iters` damped Gauss-Newton steps with the analytic Jacobian J: with A = J^T J and g = J^T r, the step solves
+ *            (A + lambda diag(A)) d = -g (Cholesky on the system scaled to a unit diagonal); lambda starts at 1e-3 on every run
+ *            of the iteration.  A step that lowers the cost C = |r|^2 is taken and lambda becomes max(lambda / 10, 1e-12); the
+ *            iteration stops when the taken step lowered C by no more than 1e-12 C, or when C is 0.  A step that does not lower C
+ *            (or leaves a point without a finite image) is not taken and lambda becomes 10 lambda; the iteration stops when lambda
+ *            exceeds 1e8.  Either kind of step counts towards `iters`.  After the iteration the UNDAMPED A at the result must have
+ *            full rank: a Cholesky pivot of the unit-diagonal A at or below 1e-12 refuses.
+ *   trim     at most `rounds` times: the points further than trim_px from the joint fit (or without an image) are dropped; if none
+ *            was, stop; otherwise the iteration runs again from the current parameters.
+ *   outputs  k_out2 = (k1, k2); H_out9 row-major, mapping the unit slide to IDEAL pixels (rows 0 and 1 multiplied by s); quad_out8
+ *            its images of (0,0), (1,0), (1,1), (0,1) in ideal coordinates — exactly what slideo_frame_region_from_quad takes while
+ *            that lens is set —; cells_used and rms_px of the last fit.
+ * SLIDEO_ERR_INVALID_ARG, and nothing written: a bad argument; fewer than 4 + order points at any stage; a rank-deficient or
+ * non-finite step; a result whose radial map is not strictly increasing (the rule of "Frame lens") up to the largest r2 of the kept
+ * cells' ideal points.  SLIDEO_ERR_CAPACITY: no host memory. */
+int32_t     slideo_placement_lens(const uint64_t* n, const uint64_t* sfx, const uint64_t* sfy, const uint64_t* su, const uint64_t* sv, int32_t gw,
+                                  int32_t gh, int32_t cell, int32_t aw, int32_t ah, int64_t min_count, double cx, double cy, double f, int32_t order,
+                                  double trim_px, int32_t rounds, int32_t iters, double* k_out2, double* quad_out8, double* H_out9,
+                                  int32_t* cells_used, double* rms_px);
 
 /* ---- Match shading map (extension: the measurement a frame shading can be made from, out of the matches) ------------------------------
  * The frame shading ("Frame shading") needs its gains.  What can give them is what the tone table is learnt from — the pixel pairs

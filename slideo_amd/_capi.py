@@ -527,6 +527,8 @@ EXPORTS = [
     "slideo_matcher_placement_begin", "slideo_matcher_placement_end", "slideo_matcher_placement_info", "slideo_matcher_placement_sums",
     "slideo_group_placement_begin", "slideo_group_placement_end", "slideo_group_placement_info", "slideo_group_placement_sums",
     "slideo_placement_quad",
+    "slideo_matcher_set_frame_lens", "slideo_matcher_frame_lens", "slideo_group_set_frame_lens", "slideo_frame_lens_point",
+    "slideo_undistort_bgr8", "slideo_placement_lens",
     "slideo_match_frames_list", "slideo_match_frames_submit_list", "slideo_match_changed_frames_list",
     "slideo_match_changed_frames_submit_list", "slideo_changed_mask_list", "slideo_matcher_observe_frames_list",
     "slideo_matcher_gate_reset_from_frame_list", "slideo_group_match_frames_list", "slideo_group_match_changed_frames_list",
@@ -661,6 +663,14 @@ def lib():
             L.slideo_group_set_frame_region.argtypes = [vp, i32, i32, vp, i32, i32]
             L.slideo_frame_region_from_quad.argtypes = [vp, i32, i32, vp]
             L.slideo_rectify_bgr8.argtypes = [vp, vp, i32, i32, i32, vp, i64]
+        if hasattr(L, "slideo_matcher_set_frame_lens"):
+            vp, i32, i64, f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_double
+            L.slideo_matcher_set_frame_lens.argtypes = [vp, i32, i32] + [f64] * 5
+            L.slideo_matcher_frame_lens.argtypes = [vp] * 9
+            L.slideo_group_set_frame_lens.argtypes = [vp, i32, i32] + [f64] * 5
+            L.slideo_frame_lens_point.argtypes = [f64] * 7 + [vp, vp]
+            L.slideo_undistort_bgr8.argtypes = [vp, vp, i32, i32, i32, vp, i64]
+            L.slideo_placement_lens.argtypes = [vp] * 5 + [i32] * 5 + [i64, f64, f64, f64, i32, f64, i32, i32] + [vp] * 5
         if hasattr(L, "slideo_matcher_set_yuv_description"):
             vp, i32 = C.c_void_p, C.c_int32
             L.slideo_matcher_set_yuv_description.argtypes = [vp, i32, i32, i32]
@@ -1425,11 +1435,57 @@ class _FrameCalls:
 
     frame_region_from_quad = staticmethod(lambda quad, out_w, out_h: frame_region_from_quad(quad, out_w, out_h))
 
+    # frame lens (include/slideo_amd.h "Frame lens"): frames of the lens's source size are undistorted in the rectify's launch
+    def set_frame_lens(self, src_w, src_h, cx=None, cy=None, f=None, k1=0.0, k2=0.0):
+        """The radial lens c + (p - c) (1 + k1 r2 + k2 r2^2), r2 = |p - c|^2 / f^2.  cx, cy None: the image centre ((src_w - 1) / 2,
+        (src_h - 1) / 2); f None: half the source diagonal, so that k1 is the relative displacement at the corner.  k1 == k2 == 0:
+        off.  The matcher must be idle."""
+        cx, cy, f = frame_lens_defaults(src_w, src_h, cx, cy, f)
+        self._check(getattr(lib(), self._SETS + "set_frame_lens")(self._h, int(src_w), int(src_h), float(cx), float(cy), float(f), float(k1), float(k2)))
+
+    def clear_frame_lens(self):
+        self._check(getattr(lib(), self._SETS + "set_frame_lens")(self._h, 0, 0, 0.0, 0.0, 0.0, 0.0, 0.0))
+
+    @property
+    def frame_lens(self):
+        """(src_w, src_h, cx, cy, f, k1, k2), or None."""
+        if not hasattr(lib(), "slideo_matcher_frame_lens"):         # (SLIDEO_LIB_PATH may name an older build: tools/ab_libs.sh)
+            return None
+        h = self._mask_owner()
+        s = [C.c_int32(), C.c_int32()]
+        d = [C.c_double() for _ in range(5)]
+        on = C.c_int32()
+        rc = lib().slideo_matcher_frame_lens(h, C.byref(s[0]), C.byref(s[1]), *[C.byref(x) for x in d], C.byref(on))
+        if rc != OK:
+            raise SlideoError(rc, "frame_lens")
+        return (s[0].value, s[1].value) + tuple(x.value for x in d) if on.value else None
+
+    def undistort(self, bgr):
+        """The analysed image of one host image under the lens, and the region if one is set (the tap; a Group: member 0's)."""
+        bgr = _img3(bgr)
+        h, w, _ = bgr.shape
+        return self.undistort_pitched(bgr, w, h, w * 3)
+
+    def undistort_pitched(self, buf, w, h, stride):
+        """The same for an image of w x h in `buf` with rows `stride` bytes apart."""
+        buf = np.ascontiguousarray(buf, np.uint8)
+        lens, reg = self.frame_lens, self.frame_region
+        ow, oh = (reg[3], reg[4]) if reg else (lens[0], lens[1]) if lens else (0, 0)
+        out = np.empty((oh, ow, 3), np.uint8)
+        hd = self._mask_owner()
+        rc = lib().slideo_undistort_bgr8(hd, _p(buf), int(w), int(h), int(stride), _p(out), C.c_int64(out.size))
+        if rc != OK:
+            raise SlideoError(rc, lib().slideo_last_error(hd).decode())
+        return out
+
     def _unit_size(self, w, h):
         """The size of the image the pipeline reads for a w x h frame."""
         reg = self.frame_region
         if reg is not None:
             return reg[3], reg[4]
+        lens = self.frame_lens
+        if lens is not None:
+            return lens[0], lens[1]
         mw, mh = self.working_size
         return working_size(w, h, mw, mh) if mw > 0 else (w, h)
 
@@ -2347,6 +2403,42 @@ def placement_quad(sums, cell, aw, ah, min_count, trim_px, rounds):
         raise SlideoError(rc, "slideo_placement_quad: an argument outside its range, fewer than 4 cells of min_count keypoints, or cells "
                               "that determine no homography (include/slideo_amd.h \"Match placement map\")")
     return [(float(quad[2 * i]), float(quad[2 * i + 1])) for i in range(4)], H.reshape(3, 3), used.value, rms.value
+
+
+def frame_lens_defaults(src_w, src_h, cx=None, cy=None, f=None):
+    """The mirrors' defaults of "Frame lens": the image centre and half the source diagonal."""
+    cx = (src_w - 1) / 2.0 if cx is None else cx
+    cy = (src_h - 1) / 2.0 if cy is None else cy
+    f = 0.5 * float(np.hypot(src_w, src_h)) if f is None else f
+    return float(cx), float(cy), float(f)
+
+
+def frame_lens_point(cx, cy, f, k1, k2, u, v):
+    """slideo_frame_lens_point: where the camera sees the ideal point (u, v) under the lens -> (xd, yd).  A pure host function."""
+    xd, yd = C.c_double(), C.c_double()
+    rc = lib().slideo_frame_lens_point(float(cx), float(cy), float(f), float(k1), float(k2), float(u), float(v), C.byref(xd), C.byref(yd))
+    if rc != OK:
+        raise SlideoError(rc, "slideo_frame_lens_point: a non-finite argument or f <= 0")
+    return xd.value, yd.value
+
+
+def placement_lens(sums, cell, aw, ah, min_count, cx, cy, f, order, trim_px, rounds, iters):
+    """slideo_placement_lens (include/slideo_amd.h "Placement lens"): sums uint64 [5, gh, gw] of a placement session that ran with no
+    lens and no region -> ((k1, k2), quad [(x, y)] * 4 in IDEAL pixels, H float64 [3, 3] unit slide -> ideal pixels, cells_used,
+    rms_px).  SlideoError: an argument outside its range, too few cells at a stage, cells that do not determine the fit, or a fit
+    whose radial map is not increasing over the kept cells."""
+    sums = np.ascontiguousarray(sums, np.uint64)
+    if sums.ndim != 3 or sums.shape[0] != 5:
+        raise ValueError("sums: one uint64 [5, gh, gw] array, got %s" % (sums.shape,))
+    k, quad, H = np.zeros(2, np.float64), np.zeros(8, np.float64), np.zeros(9, np.float64)
+    used, rms = C.c_int32(), C.c_double()
+    rc = lib().slideo_placement_lens(*[_p(sums[i]) for i in range(5)], sums.shape[2], sums.shape[1], int(cell), int(aw), int(ah),
+                                     C.c_int64(int(min_count)), float(cx), float(cy), float(f), int(order), float(trim_px), int(rounds), int(iters),
+                                     _p(k), _p(quad), _p(H), C.byref(used), C.byref(rms))
+    if rc != OK:
+        raise SlideoError(rc, "slideo_placement_lens: an argument outside its range, fewer than 4 + order cells of min_count keypoints, cells "
+                              "that determine no fit, or a radial map that is not increasing (include/slideo_amd.h \"Placement lens\")")
+    return (float(k[0]), float(k[1])), [(float(quad[2 * i]), float(quad[2 * i + 1])) for i in range(4)], H.reshape(3, 3), used.value, rms.value
 
 
 def changed_ssd_threshold(changed_similarity, small_w, small_h):

@@ -23,7 +23,7 @@ SYNTH_LIB = os.path.join(LIBDIR, "libslideo_synth.so")
 # levels.hip.h holds two kernels, one each for stage_orb.hip and stage_activity.hip; shading.hip.h likewise, for stage_orb.hip and stage_verify.hip)
 HIP_SOURCES = ["capi_runtime.hip", "capi_group.hip", "capi_taps.hip", "stage_orb.hip", "stage_knn.hip", "stage_verify.hip", "stage_sift.hip", "stage_page_set.hip", "stage_gate.hip", "stage_direct.hip", "stage_ssd_table.hip", "stage_activity.hip", "stage_gate_anchor.hip", "stage_content.hip"]
 # the kernel headers each unit includes (beyond runtime.hpp and the plain headers, which every unit depends on)
-HIP_UNIT_HEADERS = {"stage_orb.hip": ["orb.hip.h", "cv_math.hip.h", "yuv420.hip.h", "yuv_sampling.hip.h", "yuv_chroma.hip.h", "yuv_transfer.hip.h", "pixel_format.hip.h", "frame_list.hip.h", "bgr_store.hip.h", "reduce.hip.h", "frame_region.hip.h", "frame_mask.hip.h", "levels.hip.h", "shading.hip.h"],
+HIP_UNIT_HEADERS = {"stage_orb.hip": ["orb.hip.h", "cv_math.hip.h", "yuv420.hip.h", "yuv_sampling.hip.h", "yuv_chroma.hip.h", "yuv_transfer.hip.h", "pixel_format.hip.h", "frame_list.hip.h", "bgr_store.hip.h", "reduce.hip.h", "frame_region.hip.h", "frame_lens.hip.h", "frame_mask.hip.h", "levels.hip.h", "shading.hip.h"],
                     "stage_knn.hip": ["knn.hip.h", "knn_tile.hip.h", "knn_l2.hip.h", "knn_lsh.hip.h"],
                     "stage_verify.hip": ["verify.hip.h", "homography.hip.h", "evidence.hip.h", "tone.hip.h", "placement.hip.h", "shading.hip.h", "levels.hip.h"],
                     "stage_sift.hip": ["sift.hip.h", "cv_math.hip.h"],
@@ -34,7 +34,7 @@ HIP_UNIT_HEADERS = {"stage_orb.hip": ["orb.hip.h", "cv_math.hip.h", "yuv420.hip.
                     "stage_activity.hip": ["activity.hip.h", "levels.hip.h"],
                     "stage_gate_anchor.hip": ["gate_anchor.hip.h"],
                     "stage_content.hip": ["content.hip.h"]}
-HIP_COMMON_HEADERS = ["runtime.hpp", "common.h", "error.h", "frame_settings.h", "geom.h", "types.h", "shading_field.h"]
+HIP_COMMON_HEADERS = ["runtime.hpp", "common.h", "error.h", "frame_settings.h", "geom.h", "types.h", "shading_field.h", "placement_lens.h"]
 OBJDIR = os.path.join(LIBDIR, "obj")
 
 

@@ -434,6 +434,9 @@ int32_t slideo_group_set_working_size(slideo_group* g, int32_t max_w, int32_t ma
 int32_t slideo_group_set_frame_region(slideo_group* g, int32_t src_w, int32_t src_h, const double* M, int32_t out_w, int32_t out_h) {
     return group_set(g, SET_FRAME_REGION, [&](const FrameSettings& s) { return propose_frame_region(s, src_w, src_h, M, out_w, out_h); });
 }
+int32_t slideo_group_set_frame_lens(slideo_group* g, int32_t src_w, int32_t src_h, double cx, double cy, double f, double k1, double k2) {
+    return group_set(g, SET_FRAME_REGION, [&](const FrameSettings& s) { return propose_frame_lens(s, src_w, src_h, cx, cy, f, k1, k2); });
+}
 int32_t slideo_group_set_frame_mask(slideo_group* g, const uint8_t* mask, int32_t width, int32_t height, int32_t stride_bytes) {
     return group_set(g, SET_FRAME_MASK, [&](const FrameSettings& s) { return propose_frame_mask(s, mask != nullptr, width, height, stride_bytes); }, mask,
                      stride_bytes);

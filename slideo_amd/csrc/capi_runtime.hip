@@ -136,14 +136,20 @@ static void stage_list(Slot& S, const FrameSrc& src, int first, int n, uint8_t* 
 }
 
 // prep, unit size and small size: the frame region, else the working size (the region's output fits it: the set calls' rule)
-void resolve_unit(const slideo_matcher* m, FrameSrc& src) {
+void resolve_unit(const slideo_matcher* m, FrameSrc& src, bool with_lens) {
     const FrameSettings& fs = m->fs;
     const FrameRegion& R = fs.region;
+    const FrameLens& L = fs.lens;
+    const bool lens = L.set && with_lens;
     const int small_area = m->cfg.small_area;
-    if (R.set && !src.analysed) {
-        if (src.w != R.src_w || src.h != R.src_h)
+    if ((R.set || lens) && !src.analysed) {
+        if (R.set && (src.w != R.src_w || src.h != R.src_h))
             fail(SLIDEO_ERR_INVALID_ARG, "frame size %dx%d is not the frame region's source size %dx%d", src.w, src.h, R.src_w, R.src_h);
-        src.plan.unit(PREP_RECTIFY, R.out_w, R.out_h, small_area);
+        if (lens && (src.w != L.src_w || src.h != L.src_h))
+            fail(SLIDEO_ERR_INVALID_ARG, "frame size %dx%d is not the frame lens's source size %dx%d", src.w, src.h, L.src_w, L.src_h);
+        // (a lens without a region: a rectifying call of its own source size, which fits the working size — the set calls' rule)
+        src.plan.unit(PREP_RECTIFY, R.set ? R.out_w : L.src_w, R.set ? R.out_h : L.src_h, small_area);
+        src.plan.lens = lens;
     } else if (fs.work_w > 0 && (src.w > fs.work_w || src.h > fs.work_h)) {
         int rw = 0, rh = 0;
         working_size_rule(src.w, src.h, fs.work_w, fs.work_h, rw, rh);
@@ -285,7 +291,7 @@ DevFrames stage_frames(slideo_matcher* m, Slot& S, const FrameSrc& src, int firs
         else if (src.levels) launch_levels(m, p, fs, src.stride, stage, fb, src.stride, src.w, src.h, n, S.st);
         return DevFrames{stage, src.w, src.h, src.stride, fb};
     }
-    if (P.prep == PREP_RECTIFY) launch_rectify(m->fs.region, p, fs, src.stride, n, stage, S.st);
+    if (P.prep == PREP_RECTIFY) launch_rectify(m->fs.region, P.lens ? &m->fs.lens : nullptr, p, fs, src.stride, n, stage, S.st);
     else launch_reduce(m, p, fs, src.stride, src.w, src.h, uw, uh, n, stage, S.st);
     if (src.shading) launch_shading(m, src.levels, stage, ub, uw * 3, stage, ub, uw * 3, uw, uh, n, S.st);
     else if (src.levels) launch_levels(m, stage, ub, uw * 3, stage, ub, uw * 3, uw, uh, n, S.st);
@@ -958,9 +964,53 @@ int32_t slideo_rectify_bgr8(slideo_matcher* m, const uint8_t* bgr, int32_t width
     if (!m->fs.region.set) fail(SLIDEO_ERR_STATE, "no frame region is set");
     FrameSrc img = FrameSrc::image(bgr, width, height, stride_bytes);
     validate_frames(img);
-    resolve_unit(m, img);
+    resolve_unit(m, img, false);                                  // (the tap of the region ALONE: a lens that is set stays out of it)
     const int64_t ob = (int64_t)img.plan.uw * img.plan.uh * 3;
     if (ob > out_capacity) fail(SLIDEO_ERR_CAPACITY, "the rectified image needs %lld bytes", (long long)ob);
+    tap_staged(m, img, out, ob);
+    API_CATCH(m)
+}
+
+// ---- frame lens (include/slideo_amd.h "Frame lens") ---------------------------------------------------------------------------
+// The lens commits under the region's row: an idle matcher; it ends the kept frames, the gate state and the match sessions
+
+int32_t slideo_matcher_set_frame_lens(slideo_matcher* m, int32_t src_w, int32_t src_h, double cx, double cy, double f, double k1, double k2) {
+    return matcher_set(m, SET_FRAME_REGION, [&](const FrameSettings& s) { return propose_frame_lens(s, src_w, src_h, cx, cy, f, k1, k2); });
+}
+
+int32_t slideo_matcher_frame_lens(const slideo_matcher* m, int32_t* src_w, int32_t* src_h, double* cx, double* cy, double* f, double* k1, double* k2,
+                                  int32_t* is_set) {
+    if (!m || !src_w || !src_h || !cx || !cy || !f || !k1 || !k2 || !is_set) return SLIDEO_ERR_INVALID_ARG;
+    const FrameLens& L = m->fs.lens;
+    *src_w = L.src_w; *src_h = L.src_h; *cx = L.cx; *cy = L.cy; *f = L.f; *k1 = L.k1; *k2 = L.k2; *is_set = L.set ? 1 : 0;
+    return SLIDEO_OK;
+}
+
+// step 2 of the definition for one point (no device, no matcher)
+int32_t slideo_frame_lens_point(double cx, double cy, double f, double k1, double k2, double u, double v, double* xd, double* yd) {
+    if (!xd || !yd) return SLIDEO_ERR_INVALID_ARG;
+    const double a[7] = {cx, cy, f, k1, k2, u, v};
+    for (double x : a) if (!std::isfinite(x)) return SLIDEO_ERR_INVALID_ARG;
+    if (!(f > 0.0)) return SLIDEO_ERR_INVALID_ARG;
+    const double q = 1.0 / (f * f);
+    if (!std::isfinite(q) || !(q > 0.0)) return SLIDEO_ERR_INVALID_ARG;
+    if (k1 == 0.0 && k2 == 0.0) { *xd = u; *yd = v; return SLIDEO_OK; }       // (off: no lens runs, and cx + (u - cx) is not always u)
+    frame_lens_point(cx, cy, q, k1, k2, u, v, xd, yd);
+    return SLIDEO_OK;
+}
+
+// Tap: the analysed image of one host image under the matcher's lens, and its region if one is set (no small_area limit)
+int32_t slideo_undistort_bgr8(slideo_matcher* m, const uint8_t* bgr, int32_t width, int32_t height, int32_t stride_bytes, uint8_t* out,
+                              int64_t out_capacity) {
+    if (!m) return SLIDEO_ERR_INVALID_ARG;
+    API_TRY
+    if (!bgr || !out) fail(SLIDEO_ERR_INVALID_ARG, "null image/out");
+    if (!m->fs.lens.set) fail(SLIDEO_ERR_STATE, "no frame lens is set");
+    FrameSrc img = FrameSrc::image(bgr, width, height, stride_bytes);
+    validate_frames(img);
+    resolve_unit(m, img);
+    const int64_t ob = (int64_t)img.plan.uw * img.plan.uh * 3;
+    if (ob > out_capacity) fail(SLIDEO_ERR_CAPACITY, "the undistorted image needs %lld bytes", (long long)ob);
     tap_staged(m, img, out, ob);
     API_CATCH(m)
 }

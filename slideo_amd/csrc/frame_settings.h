@@ -1,5 +1,5 @@
 // frame_settings.h — the frame settings of a matcher as ONE record (include/slideo_amd.h "Working size", "Frame region", "Frame mask",
-// "Frame mask scope", "Direct page look-up", "Direct look-up scope", "YUV colour description", "YUV sampling", "YUV chroma filter", "YUV transfer", "Gate reference", "Gate settle", "Gate memory", "Frame pixel format", "Frame levels", "Frame shading"): the record, every setter's proposal with its range checks, the
+// "Frame mask scope", "Direct page look-up", "Direct look-up scope", "YUV colour description", "YUV sampling", "YUV chroma filter", "YUV transfer", "Gate reference", "Gate settle", "Gate memory", "Frame pixel format", "Frame levels", "Frame shading", "Frame lens"): the record, every setter's proposal with its range checks, the
 // rules between settings, what a change of each ends.  Plain C++, no HIP include (tools/frame_settings_hostcheck.cpp walks it on the
 // host); the device buffers a setting owns are the matcher's (runtime.hpp); the frame
 // shading's nodes are the record's own, shared by pointer between its copies.  A change takes ONE path: settings_commit (capi_runtime.hip).
@@ -23,6 +23,13 @@ struct FrameRegion {
     int src_w = 0, src_h = 0, out_w = 0, out_h = 0;
     double M[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
     int kind = 0, tx = 0, ty = 0;
+};
+// The radial lens of "Frame lens": a point p of the ideal source plane is seen at c + (p - c) g(r2), r2 = |p - c|^2 / f^2, g = 1 + k1 r2 +
+// k2 r2^2; q = 1.0 / (f * f), computed once at the proposal.  set false: off, and k1 == k2 == 0 is stored as off
+struct FrameLens {
+    bool set = false;
+    int src_w = 0, src_h = 0;
+    double cx = 0, cy = 0, f = 0, k1 = 0, k2 = 0, q = 0;
 };
 // A w x h mask; frames of that analysed size keep only the FAST candidates its pyramid (the matcher's d_mask_pyr) allows
 struct FrameMask { bool set = false; int w = 0, h = 0; };
@@ -62,6 +69,7 @@ struct FrameShading {
 struct FrameSettings {
     int work_w = 0, work_h = 0;                       // frames beyond it are reduced in front of the pipeline; 0, 0 = none
     FrameRegion region;                               // frames of region.src_w x src_h stand for their rectified image
+    FrameLens lens;                                   // frames of lens.src_w x src_h are undistorted in the rectify's launch
     FrameMask mask;
     uint32_t mask_scope = SLIDEO_MASK_DETECT;         // SLIDEO_MASK_DETECT | SLIDEO_MASK_GATE; the matcher's, whatever happens to the mask
     GateMap gate_map;
@@ -122,6 +130,54 @@ inline FrameSettings propose_frame_region(FrameSettings s, int src_w, int src_h,
     s.region.set = true; s.region.src_w = src_w; s.region.src_h = src_h; s.region.out_w = out_w; s.region.out_h = out_h;
     for (int i = 0; i < 9; ++i) s.region.M[i] = M[i];
     return s;
+}
+// The lens commits under SET_FRAME_REGION like the region: it ends the kept frames, the gate state and the match sessions.  k1 == 0 and
+// k2 == 0: off, and the other arguments are not looked at.  (The reach rule needs the region in force: frame_settings_rules.)
+inline FrameSettings propose_frame_lens(FrameSettings s, int src_w, int src_h, double cx, double cy, double f, double k1, double k2) {
+    s.lens = FrameLens{};
+    if (k1 == 0.0 && k2 == 0.0) return s;
+    if (src_w < 1 || src_h < 1 || src_w > MAX_DIM || src_h > MAX_DIM)
+        fail(SLIDEO_ERR_INVALID_ARG, "frame lens: source size %dx%d outside 1..%d", src_w, src_h, MAX_DIM);
+    const double a[5] = {cx, cy, f, k1, k2};
+    static const char* const names[5] = {"cx", "cy", "f", "k1", "k2"};
+    for (int i = 0; i < 5; ++i) if (!std::isfinite(a[i])) fail(SLIDEO_ERR_INVALID_ARG, "frame lens: %s is not finite", names[i]);
+    if (!(f > 0.0)) fail(SLIDEO_ERR_INVALID_ARG, "frame lens: f %g: the normaliser is positive", f);
+    const double q = 1.0 / (f * f);
+    if (!std::isfinite(q) || !(q > 0.0)) fail(SLIDEO_ERR_INVALID_ARG, "frame lens: f %g: 1 / f^2 is not a positive finite number", f);
+    s.lens.set = true; s.lens.src_w = src_w; s.lens.src_h = src_h;
+    s.lens.cx = cx; s.lens.cy = cy; s.lens.f = f; s.lens.k1 = k1; s.lens.k2 = k2; s.lens.q = q;
+    return s;
+}
+// The monotonicity rule of "Frame lens": d/dr (r g(r)) = 1 + 3 k1 s + 5 k2 s^2 > 0 (s = r2) at 0, at R2 and at the vertex
+// -3 k1 / (10 k2) where that lies inside (0, R2): the radial map is strictly increasing over [0, sqrt(R2)]
+inline bool frame_lens_monotone(double k1, double k2, double R2) {
+    if (!std::isfinite(R2) || R2 < 0.0) return false;
+    const auto d = [&](double s) { return 1.0 + 3.0 * k1 * s + 5.0 * k2 * s * s; };
+    if (!(d(0.0) > 0.0) || !(d(R2) > 0.0)) return false;
+    if (k2 != 0.0) {
+        const double sv = -3.0 * k1 / (10.0 * k2);
+        if (sv > 0.0 && sv < R2 && !(d(sv) > 0.0)) return false;
+    }
+    return true;
+}
+// The reach R2 of a lens beside a region (or none): the largest r2 of the ideal images of the destination's four corners (the image
+// of the rectangle is convex, so a corner is its farthest point).  Not finite: W == 0 at a corner
+inline double frame_lens_reach(const FrameLens& L, const FrameRegion& R) {
+    const int dw = R.set ? R.out_w : L.src_w, dh = R.set ? R.out_h : L.src_h;
+    const double xs[2] = {0.0, (double)(dw - 1)}, ys[2] = {0.0, (double)(dh - 1)};
+    double R2 = 0.0;
+    for (double y : ys) for (double x : xs) {
+        double u = x, v = y;
+        if (R.set) {
+            const double* M = R.M;
+            const double W = M[6] * x + M[7] * y + M[8];
+            u = (M[0] * x + M[1] * y + M[2]) / W; v = (M[3] * x + M[4] * y + M[5]) / W;
+        }
+        const double r2 = ((u - L.cx) * (u - L.cx) + (v - L.cy) * (v - L.cy)) * L.q;
+        if (!std::isfinite(r2)) return r2;              // (the rule then fails)
+        if (r2 > R2) R2 = r2;
+    }
+    return R2;
 }
 // set false: no mask.  (The pyramid and the validity map are built at the commit.)
 inline FrameSettings propose_frame_mask(FrameSettings s, bool set, int width, int height, int stride_bytes) {
@@ -835,6 +891,23 @@ inline void frame_settings_rules(const FrameSettings& next, Setting what, bool s
     if (R.set && next.work_w > 0 && (R.out_w > next.work_w || R.out_h > next.work_h))
         fail(SLIDEO_ERR_UNSUPPORTED, "%s: the frame region's output %dx%d exceeds the working size %dx%d: a region's output must fit the working size",
              what == SET_WORKING_SIZE ? "working size" : "frame region", R.out_w, R.out_h, next.work_w, next.work_h);
+    // a lens and a region describe the same source frames; a lens alone is a rectifying call of its own source size, which must fit
+    // the working size (the source is exempt, as for the region); the radial map is strictly increasing over the reach, whichever of
+    // the two set calls changes the reach
+    const FrameLens& L = next.lens;
+    if (L.set && R.set && (L.src_w != R.src_w || L.src_h != R.src_h))
+        fail(SLIDEO_ERR_UNSUPPORTED, "the frame lens's source size %dx%d is not the frame region's source size %dx%d: both describe the same frames",
+             L.src_w, L.src_h, R.src_w, R.src_h);
+    if (L.set && !R.set && next.work_w > 0 && (L.src_w > next.work_w || L.src_h > next.work_h))
+        fail(SLIDEO_ERR_UNSUPPORTED, "%s: a frame lens without a region analyses frames at its source size %dx%d, which exceeds the working size %dx%d "
+             "(a lens counts as a rectifying call: its output must fit the working size)", what == SET_WORKING_SIZE ? "working size" : "frame lens",
+             L.src_w, L.src_h, next.work_w, next.work_h);
+    if (L.set && (what == SET_FRAME_REGION || what == SET_WORKING_SIZE)) {
+        const double R2 = frame_lens_reach(L, R);
+        if (!frame_lens_monotone(L.k1, L.k2, R2))
+            fail(SLIDEO_ERR_INVALID_ARG, "frame lens: the radial map r (1 + k1 r^2 + k2 r^4) with k1 %g, k2 %g is not strictly increasing over the reach "
+                 "r^2 <= %g of the %s's corners (1 + 3 k1 s + 5 k2 s^2 > 0 over 0 <= s <= r^2)", L.k1, L.k2, R2, R.set ? "frame region" : "source frame");
+    }
     // a direct similarity compares whole small images: not beside a mask the gate compares under, unless the look-up does too
     if (next.direct_t > 0.f && next.gate_scope() && next.direct_scope != SLIDEO_DIRECT_VALID)
         fail(SLIDEO_ERR_UNSUPPORTED, "the direct page look-up compares whole small images: not together with a frame mask under SLIDEO_MASK_GATE "

@@ -86,13 +86,14 @@ struct HostPage {
 // sizes, gates or masks them
 enum FramePrep { PREP_NONE, PREP_REDUCE, PREP_RECTIFY };      // the kernel between the BGR view at source size and the unit's image
 struct FramePlan {
-    FramePrep prep = PREP_NONE;                 // REDUCE: the working size does not hold the frame; RECTIFY: a frame region is set
+    FramePrep prep = PREP_NONE;                 // REDUCE: the working size does not hold the frame; RECTIFY: a frame region or lens is set
+    bool lens = false;                          // RECTIFY: the launch undistorts under the matcher's frame lens (resolve_unit)
     int uw = 0, uh = 0, sw = 0, sh = 0;         // the BGR image the units read, its small image (small_size under cfg.small_area)
     const uint8_t* mask_pyr = nullptr;          // the frame mask's pyramid for uw x uh (frame_mask_for), null: no filter
     const uint8_t* gate_w = nullptr;            // the gate's validity map for uw x uh (gate_map_for), null: whole small images,
     int npx = 0;                                // and the pixels a similarity is normalised over: the map's n_valid, or sw * sh
     void unit(FramePrep p, int w, int h, int small_area) {
-        prep = p; uw = w; uh = h;
+        prep = p; uw = w; uh = h; lens = false;
         small_size(w, h, small_area, sw, sh);
         npx = sw * sh;
     }
@@ -572,7 +573,9 @@ void validate_frames(FrameSrc& src, slideo_matcher* m = nullptr, int n = 0, cons
 // limit of a reduced frame, the SIFT limits, the page set's modes, the mask's pyramid (frame_mask_for); the gate's weights and npx.
 void resolve_frames(const slideo_matcher* m, FrameSrc& src, bool match);
 // its first step alone: prep, unit size and small size of a validated source (what an observe call needs: no mask, no gate map)
-void resolve_unit(const slideo_matcher* m, FrameSrc& src);
+// with_lens false: the frame lens stays out of it (slideo_rectify_bgr8, the tap of the region alone); else a lens that is set makes
+// the call a rectifying one of the region's output size, or of the lens's source size where no region is set
+void resolve_unit(const slideo_matcher* m, FrameSrc& src, bool with_lens = true);
 // The one path by which a frame setting of m changes: idle (SLIDEO_ERR_STATE), the rules between settings on `next` (a propose_*
 // of frame_settings.h), what the mask and its scope need on the device built first and installed on success (mask: the host mask
 // of SET_FRAME_MASK, rows `stride` apart), then `next` in force and what SETTING_ENDS[what] ends ended.
@@ -639,7 +642,10 @@ void orb_launch_scan(const uint32_t* counts, int n, uint32_t* qofs, uint32_t* in
 void launch_reduce(slideo_matcher* m, const uint8_t* src, int64_t src_fs, int stride, int w, int h, int dw, int dh, int n, uint8_t* dst,
                    hipStream_t st);
 // n BGR8 frames of R.src_w x R.src_h -> their rectified R.out_w x R.out_h images at dst (stride 3 out_w, frame stride 3 out_w out_h)
-void launch_rectify(const FrameRegion& R, const uint8_t* src, int64_t src_fs, int stride, int n, uint8_t* dst, hipStream_t st);
+// L: the lens that is set, undistorted in the same launch (frame_lens.hip.h; without a region: at the lens's source size); null: none
+void launch_rectify(const FrameRegion& R, const FrameLens* L, const uint8_t* src, int64_t src_fs, int stride, int n, uint8_t* dst, hipStream_t st);
+// step 2 of "Frame lens" for one point, the kernel's own host build (q = 1.0 / (f * f))
+void frame_lens_point(double cx, double cy, double q, double k1, double k2, double u, double v, double* xd, double* yd);
 // the rectify_kernel instance of a map: R.kind, R.tx, R.ty from R.M
 void frame_region_classify(FrameRegion& R);
 // n decoded YUV 4:2:0 frames (a layout yuv420_validate accepted under `desc`, frame stride src_fs) -> BGR8 at dst, stride 3w, frame

@@ -1,8 +1,8 @@
 // stage_orb.hip — drivers of the ORB stage (kernels: orb.hip.h) and of the front doors in front of it: YUV frames (one argument
 // record and one dispatch over the kernel families of yuv420.hip.h, yuv_sampling.hip.h, yuv_chroma.hip.h, yuv_transfer.hip.h), frames of
 // another pixel format (pixel_format.hip.h), the frame levels' table (levels.hip.h), the working-size reduce (reduce.hip.h) and the
-// frame region's rectify (frame_region.hip.h); the frame mask's pyramid and candidate filter (frame_mask.hip.h); the gather of a device
-// frame list's planes (frame_list.hip.h).
+// frame region's rectify (frame_region.hip.h) with the frame lens fused into it (frame_lens.hip.h); the frame mask's pyramid and
+// candidate filter (frame_mask.hip.h); the gather of a device frame list's planes (frame_list.hip.h).
 #include <type_traits>
 
 #include "runtime.hpp"
@@ -19,6 +19,7 @@
 #include "shading.hip.h"
 #include "reduce.hip.h"
 #include "frame_region.hip.h"
+#include "frame_lens.hip.h"
 #include "frame_mask.hip.h"
 
 using namespace slideo;
@@ -244,14 +245,29 @@ void launch_reduce(slideo_matcher* m, const uint8_t* src, int64_t src_fs, int st
 
 void frame_region_classify(FrameRegion& R) { R.kind = rect_classify(R.M, R.tx, R.ty); }
 
-// n BGR8 frames of R.src_w x R.src_h (rows `stride`, frames src_fs apart) -> their rectified images at dst (stride 3 out_w)
-void launch_rectify(const FrameRegion& R, const uint8_t* src, int64_t src_fs, int stride, int n, uint8_t* dst, hipStream_t st) {
+// n BGR8 frames of R.src_w x R.src_h (rows `stride`, frames src_fs apart) -> their rectified images at dst (stride 3 out_w).
+// L (a lens that is set): the ONE launch undistorts as well — lens_kernel, with the region's map in front where R is set, else at
+// the lens's source size
+void launch_rectify(const FrameRegion& R, const FrameLens* L, const uint8_t* src, int64_t src_fs, int stride, int n, uint8_t* dst, hipStream_t st) {
+    if (L) {
+        const int dw = R.set ? R.out_w : L->src_w, dh = R.set ? R.out_h : L->src_h;
+        const LensArgs a = lens_args(R.set ? R.M : nullptr, L->cx, L->cy, L->q, L->k1, L->k2, src, src_fs, stride, L->src_w, L->src_h, dst, dw, dh);
+        const dim3 grid(cdiv(cdiv(dw, 4), RECT_TX), cdiv(dh, RECT_TY), n), block(RECT_TX, RECT_TY);
+        if (R.set) lens_kernel<true><<<grid, block, 0, st>>>(a);
+        else lens_kernel<false><<<grid, block, 0, st>>>(a);
+        check_launch("lens_kernel");
+        return;
+    }
     const RectifyArgs a = rect_args(R.M, R.kind, R.tx, R.ty, src, src_fs, stride, R.src_w, R.src_h, dst, R.out_w, R.out_h);
     const dim3 grid(cdiv(cdiv(R.out_w, 4), RECT_TX), cdiv(R.out_h, RECT_TY), n), block(RECT_TX, RECT_TY);
     if (R.kind == RECT_TRANSLATE) rectify_kernel<RECT_TRANSLATE><<<grid, block, 0, st>>>(a);
     else if (R.kind == RECT_AFFINE) rectify_kernel<RECT_AFFINE><<<grid, block, 0, st>>>(a);
     else rectify_kernel<RECT_PROJECTIVE><<<grid, block, 0, st>>>(a);
     check_launch("rectify_kernel");
+}
+
+void frame_lens_point(double cx, double cy, double q, double k1, double k2, double u, double v, double* xd, double* yd) {
+    lens_point(cx, cy, q, k1, k2, u, v, *xd, *yd);
 }
 
 void orb_launch_scan(const uint32_t* counts, int n, uint32_t* qofs, uint32_t* info, hipStream_t st) {

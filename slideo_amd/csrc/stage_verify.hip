@@ -8,6 +8,7 @@
 #include "evidence.hip.h"
 #include "tone.hip.h"
 #include "placement.hip.h"
+#include "placement_lens.h"
 #define SHADING_MAP              // (shading_kernel is stage_orb.hip's)
 #include "shading.hip.h"
 
@@ -617,6 +618,25 @@ int32_t slideo_placement_quad(const uint64_t* n, const uint64_t* sfx, const uint
     try {
         return placement_quad(n, sfx, sfy, su, sv, gw, gh, aw, ah, (uint64_t)min_count, trim_px, rounds, quad_out8, H_out9, cells_used, rms_px) ? SLIDEO_OK
                                                                                                                                                : SLIDEO_ERR_INVALID_ARG;
+    } catch (const std::bad_alloc&) { return SLIDEO_ERR_CAPACITY; }
+}
+
+// "Placement lens": the joint fit of lens and quad to the same sums (placement_lens.h)
+int32_t slideo_placement_lens(const uint64_t* n, const uint64_t* sfx, const uint64_t* sfy, const uint64_t* su, const uint64_t* sv, int32_t gw, int32_t gh,
+                              int32_t cell, int32_t aw, int32_t ah, int64_t min_count, double cx, double cy, double f, int32_t order, double trim_px,
+                              int32_t rounds, int32_t iters, double* k_out2, double* quad_out8, double* H_out9, int32_t* cells_used, double* rms_px) {
+    if (!n || !sfx || !sfy || !su || !sv || !k_out2 || !quad_out8 || !H_out9 || !cells_used || !rms_px) return SLIDEO_ERR_INVALID_ARG;
+    if (!evidence_cell_ok(cell) || aw < 1 || ah < 1 || aw > MAX_DIM || ah > MAX_DIM || gw != cdiv(aw, cell) || gh != cdiv(ah, cell)) return SLIDEO_ERR_INVALID_ARG;
+    if (min_count < 1 || !(trim_px > 0.0) || !std::isfinite(trim_px) || rounds < 0 || rounds > 8) return SLIDEO_ERR_INVALID_ARG;
+    if (!std::isfinite(cx) || !std::isfinite(cy) || !std::isfinite(f) || !(f > 0.0) || !std::isfinite(1.0 / (f * f)) || !(1.0 / (f * f) > 0.0))
+        return SLIDEO_ERR_INVALID_ARG;
+    if ((order != 1 && order != 2) || iters < 1 || iters > 1000) return SLIDEO_ERR_INVALID_ARG;
+    for (size_t c = 0; c < (size_t)gw * gh; ++c)
+        if (n[c] > ((uint64_t)1 << 32) || sfx[c] > n[c] * 65536 || sfy[c] > n[c] * 65536 || su[c] > n[c] * 1048576 || sv[c] > n[c] * 1048576)
+            return SLIDEO_ERR_INVALID_ARG;
+    try {
+        return placement_lens(n, sfx, sfy, su, sv, gw, gh, aw, ah, (uint64_t)min_count, cx, cy, f, order, trim_px, rounds, iters, k_out2, quad_out8, H_out9,
+                              cells_used, rms_px) ? SLIDEO_OK : SLIDEO_ERR_INVALID_ARG;
     } catch (const std::bad_alloc&) { return SLIDEO_ERR_CAPACITY; }
 }
 

@@ -492,6 +492,17 @@ public:
         return slideo_placement_quad(p.n.data(), p.sfx.data(), p.sfy.data(), p.su.data(), p.sv.data(), p.gw, p.gh, p.cell, p.aw, p.ah, min_count, trim_px,
                                      rounds, out.quad, out.H, &out.cells_used, &out.rms_px) == SLIDEO_OK;
     }
+    // the lens and the quad of the sums, fitted jointly (slideo_placement_lens, include/slideo_amd.h "Placement lens"): the sums of a
+    // session that ran with no lens and no region; cx, cy, f: the lens's centre and normaliser, given; order 1 (k1) or 2 (k1, k2).
+    // out.quad is in IDEAL coordinates (what with_frame_region takes beside with_frame_lens).  false: refused
+    struct PlacementLens { double k[2] = {0, 0}, quad[8] = {0}, H[9] = {0}, rms_px = 0; int32_t cells_used = 0; };
+    static bool placement_lens(const PlacementSums& p, int64_t min_count, double cx, double cy, double f, int32_t order, double trim_px, int32_t rounds,
+                               int32_t iters, PlacementLens& out) {
+        const size_t nc = (size_t)p.gw * (size_t)p.gh;
+        if (!nc || p.n.size() != nc || p.sfx.size() != nc || p.sfy.size() != nc || p.su.size() != nc || p.sv.size() != nc) return false;
+        return slideo_placement_lens(p.n.data(), p.sfx.data(), p.sfy.data(), p.su.data(), p.sv.data(), p.gw, p.gh, p.cell, p.aw, p.ah, min_count, cx, cy, f,
+                                     order, trim_px, rounds, iters, out.k, out.quad, out.H, &out.cells_used, &out.rms_px) == SLIDEO_OK;
+    }
 private:
     std::shared_ptr<detail::Handle> h_;
     std::shared_ptr<std::vector<I>> images_;
@@ -526,6 +537,16 @@ public:
     HipImageVideoMatcher& with_frame_region(int32_t src_w, int32_t src_h, const double (&quad)[8], int32_t out_w, int32_t out_h) {
         if (slideo_frame_region_from_quad(quad, out_w, out_h, reg_M_) != SLIDEO_OK) throw std::runtime_error("with_frame_region: a degenerate or non-convex quad");
         reg_sw_ = src_w; reg_sh_ = src_h; reg_ow_ = out_w; reg_oh_ = out_h;
+        return *this;
+    }
+    // The radial lens of a wide-angle room camera (slideo_group_set_frame_lens, include/slideo_amd.h "Frame lens"): a point p of the
+    // ideal source plane is seen at c + (p - c) (1 + k1 r2 + k2 r2^2), r2 = |p - c|^2 / f^2, and frames of src_w x src_h are
+    // undistorted in the launch that rectifies; a region's quad is then given in ideal coordinates.  cx, cy, f < 0: the image centre
+    // and half the source diagonal.  Applied after the region.  The reference analyses the frame as the camera saw it.  Default: none
+    HipImageVideoMatcher& with_frame_lens(int32_t src_w, int32_t src_h, double k1, double k2 = 0.0, double cx = -1.0, double cy = -1.0, double f = -1.0) {
+        lens_sw_ = src_w; lens_sh_ = src_h; lens_k1_ = k1; lens_k2_ = k2;
+        lens_cx_ = cx < 0 ? (src_w - 1) / 2.0 : cx; lens_cy_ = cy < 0 ? (src_h - 1) / 2.0 : cy;
+        lens_f_ = f < 0 ? 0.5 * std::sqrt((double)src_w * src_w + (double)src_h * src_h) : f;
         return *this;
     }
     HipImageVideoMatcher& with_frame_mask(std::vector<uint8_t> mask, int32_t width, int32_t height) {
@@ -636,6 +657,8 @@ public:
             h->check(slideo_group_set_frame_region(h->g, reg_sw_, reg_sh_, reg_M_, reg_ow_, reg_oh_));
             h->reg_w = reg_ow_; h->reg_h = reg_oh_;
         }
+        if (lens_k1_ != 0.0 || lens_k2_ != 0.0)
+            h->check(slideo_group_set_frame_lens(h->g, lens_sw_, lens_sh_, lens_cx_, lens_cy_, lens_f_, lens_k1_, lens_k2_));
         if (yuv_matrix_ != SLIDEO_YUV_MATRIX_BT601 || yuv_range_ != SLIDEO_YUV_RANGE_LIMITED || yuv_depth_ != SLIDEO_YUV_DEPTH_8)
             h->check(slideo_group_set_yuv_description(h->g, yuv_matrix_, yuv_range_, yuv_depth_));
         if (yuv_sampling_ != SLIDEO_YUV_SAMPLING_420) h->check(slideo_group_set_yuv_sampling(h->g, yuv_sampling_));
@@ -668,6 +691,8 @@ private:
     int32_t work_w_ = 0, work_h_ = 0;
     int32_t reg_sw_ = 0, reg_sh_ = 0, reg_ow_ = 0, reg_oh_ = 0;
     double reg_M_[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    int32_t lens_sw_ = 0, lens_sh_ = 0;
+    double lens_cx_ = 0, lens_cy_ = 0, lens_f_ = 0, lens_k1_ = 0, lens_k2_ = 0;
     std::vector<uint8_t> mask_;
     int32_t mask_w_ = 0, mask_h_ = 0;
     int32_t yuv_matrix_ = SLIDEO_YUV_MATRIX_BT601, yuv_range_ = SLIDEO_YUV_RANGE_LIMITED, yuv_depth_ = SLIDEO_YUV_DEPTH_8;

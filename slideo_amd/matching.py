@@ -513,6 +513,45 @@ def learn_frame_quad_from_matches(matcher, frame_batches, *, cell, min_inliers, 
     return size[0], size[1], quad, out_w, out_h
 
 
+def learn_frame_lens_from_matches(matcher, frame_batches, *, cell, min_inliers, reach, min_count, trim_px, rounds, order, centre=None, f=None):
+    """A frame lens and the quad beside it, learnt jointly from the matches (include/slideo_amd.h "Placement lens"): the host BGR
+    batches (each uint8 [n, h, w, 3], all of one frame size) are matched against the matcher's finalized deck under a placement
+    session of `cell`, `min_inliers` and `reach`, with NO lens and NO region set; slideo_placement_lens fits a homography and the
+    radial terms k1 (order 1) or k1 and k2 (order 2) to the cells with at least `min_count` explained keypoints, dropping cells
+    further than `trim_px` from the joint fit at most `rounds` times.  `matcher`: a Matcher or a Group, idle, finalized; camera and
+    screen must not move over the batches.  centre None: the image centre ((aw - 1) / 2, (ah - 1) / 2); f None: half the diagonal.
+    Returns (frame_lens, quad): frame_lens = (src_w, src_h, cx, cy, f, k1, k2), what frame_lens= and set_frame_lens(*frame_lens)
+    take; quad: the slide's corners in IDEAL coordinates, top-left, top-right, bottom-right, bottom-left — what a frame region takes
+    while that lens is set.  Nothing is installed.  ValueError when no frame was matched, when a lens or a region is set, or when a
+    working size reduced the frames; SlideoError when the cells determine no fit.  No threshold has a default."""
+    if matcher.frame_lens is not None or matcher.frame_region is not None:
+        raise ValueError("learn_frame_lens_from_matches: a frame lens or a frame region is set: the sums are then not the source's")
+    size = None
+    matcher.placement_begin(cell, min_inliers, reach)
+    try:
+        for batch in frame_batches:
+            if size is None and len(batch):
+                size = (int(np.shape(batch)[2]), int(np.shape(batch)[1]))
+            matcher.match_frames(batch)
+        info = matcher.placement_info()
+        sums, _, _ = matcher.placement_sums()
+    finally:
+        matcher.placement_end()
+    if info["aw"] == 0:
+        raise ValueError("no frame was matched: the placement map is empty")
+    if (info["aw"], info["ah"]) != size:
+        raise ValueError("learn_frame_lens_from_matches: the frames are %dx%d but were analysed at %dx%d (a working size reduced them): the "
+                         "fit is not in source coordinates" % (size + (info["aw"], info["ah"])))
+    cx, cy, f = _capi.frame_lens_defaults(size[0], size[1], None if centre is None else centre[0], None if centre is None else centre[1], f)
+    k, quad, _, _, _ = _capi.placement_lens(sums, info["cell"], info["aw"], info["ah"], min_count, cx, cy, f, order, trim_px, rounds,
+                                            LENS_FIT_ITERS)
+    return (size[0], size[1], cx, cy, f, k[0], k[1]), quad
+
+
+# the damped Gauss-Newton steps learn_frame_lens_from_matches allows a run of the iteration (it stops on its own rule long before)
+LENS_FIT_ITERS = 100
+
+
 def dedup_timeline(mappings: List[Matching]) -> List[Matching]:
     """lib.rs:229-244: stable sort by time, drop consecutive mappings with the same image."""
     mappings = sorted(mappings, key=lambda mm: mm.video_time)
@@ -568,7 +607,7 @@ class HipImageVideoMatcher:
     def __init__(self, cfg=None, device=None, sift=None, devices=None, working_size=None, frame_mask=None, frame_mask_scope=None,
                  direct_similarity=None, direct_scope=None, frame_region=None, yuv_description=None, gate_reference=None, gate_settle=None,
                  group_gate_order=None, yuv_sampling=None, gate_memory=None, pixel_format=None, frame_levels=None, frame_shading=None, yuv_chroma=None,
-                 yuv_transfer=None):
+                 yuv_transfer=None, frame_lens=None):
         """devices: HIP ordinals, one matcher each behind one slideo_group (the reference fans out over the whole machine, the
         global rayon pool of lib.rs:45,174); None = every gfx950 device of the node; `device` = d is short for devices = [d].
         sift = (slideo_sift_config, ratio): the north-star's SIFT + L2 front end instead of the reference's ORB + Hamming
@@ -593,6 +632,10 @@ class HipImageVideoMatcher:
         sub-window; M_or_quad: the 3x3 map from the rectified image into the frame, or the slide's four corners in the frame
         (top-left, top-right, bottom-right, bottom-left); a frame mask is then of the output size, and the output must fit a
         working size (the reference analyses the whole frame); None = no region.
+        frame_lens = (src_w, src_h, cx, cy, f, k1, k2) (slideo_group_set_frame_lens): the radial distortion of a wide-angle room
+        camera, c + (p - c) (1 + k1 r2 + k2 r2^2) with r2 = |p - c|^2 / f^2, removed in the same launch that rectifies — what
+        learn_frame_lens_from_matches returns; a frame_region's quad is then given in ideal (undistorted) coordinates; applied
+        after frame_region; the reference analyses the frame as the camera saw it; None = no lens.
         yuv_description = (matrix, range) or (matrix, range, depth), as Matcher.set_yuv_description takes them
         (slideo_group_set_yuv_description): how the YUV 4:2:0 videos are read — ("bt709", "limited") for HD recordings,
         ("bt709", "full") for many screen recorders; the reference reads every stream as BT.601 limited range; RawVideoYuv420
@@ -639,6 +682,7 @@ class HipImageVideoMatcher:
         self._direct_similarity = direct_similarity
         self._direct_scope = direct_scope
         self._frame_region = frame_region
+        self._frame_lens = tuple(frame_lens) if frame_lens is not None else None
         self._yuv_description = tuple(yuv_description) if yuv_description is not None else None
         self._yuv_sampling = yuv_sampling
         self._yuv_chroma = yuv_chroma
@@ -670,6 +714,8 @@ class HipImageVideoMatcher:
             m.set_working_size(*self._working_size)
         if self._frame_region is not None:
             m.set_frame_region(*self._frame_region)
+        if self._frame_lens is not None:
+            m.set_frame_lens(*self._frame_lens)
         if self._yuv_description is not None:
             m.set_yuv_description(*self._yuv_description)
         if self._yuv_sampling is not None:
